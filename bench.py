@@ -193,6 +193,30 @@ def parity_sample_dec(frames, back, nbl, fs, ms, hr, ch, calls, sample):
                     "the timed launches' output buffer sample for sample" % calls}
 
 
+DUMP_BYTES = 60 << 20                          # --dump-outputs: the sampled output array stays under this (all files together under 64 MB)
+
+
+def dump_outputs(d, decode, res, nbl):
+    """--dump-outputs DIR: what the last timed step handed its caller, as float32 .npy files (exact: the outputs are uint8 / int16).
+    Encoder: frames [S, T, stride] (bytes past a stream's frame size are not output and are written as 0); decoder: pcm [S, T, ch, N].
+    S streams of this rank's B: all of them when they fit under DUMP_BYTES, else a fixed seeded sample (the same for the same arguments);
+    streams.npy holds their indices, num_bytes.npy their frame sizes."""
+    import numpy as np
+    import torch
+    B = res.shape[0]
+    per_stream = res[0].numel() * 4
+    S = min(B, DUMP_BYTES // per_stream)
+    idx = np.arange(B) if S == B else np.sort(np.random.default_rng(0).choice(B, S, replace=False))
+    x = res[torch.from_numpy(idx).to(res.device)].cpu().numpy().astype(np.float32)
+    nb = np.asarray(nbl)[idx]
+    if not decode:
+        x *= np.arange(x.shape[2])[None, None, :] < nb[:, None, None]
+    os.makedirs(d, exist_ok=True)
+    np.save(os.path.join(d, "pcm.npy" if decode else "frames.npy"), x)
+    np.save(os.path.join(d, "streams.npy"), idx.astype(np.float64))
+    np.save(os.path.join(d, "num_bytes.npy"), nb.astype(np.float64))
+
+
 def gpu_numa_cpus(local):
     """The CPUs of the NUMA node the local_rank-th AMD GPU hangs off (sysfs only: nothing here touches the GPU), or None.  Devices in PCI address order,
     which is HIP's enumeration order unless HIP_VISIBLE_DEVICES reorders them (then: None)."""
@@ -296,7 +320,11 @@ def main():
     ap.add_argument("--no-extras", action="store_true", help="skip the host-I/O and T = 1 side measurements of the default line")
     ap.add_argument("--serial-calls", action="store_true", help="encoder: do not declare the PCM ready ahead of the calls (no overlap between consecutive calls)")
     ap.add_argument("--workload", default="c1", choices=sorted(WORKLOADS), help="c1 = BASELINE configs[1] (the metric's configuration)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last one computed (rank 0's streams) as DIR/<name>.npy, float32, "
+                                                          "at most 64 MB: a fixed seeded sample of the streams when all of them do not fit")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     rank, world, local = rank_env()
     if "WORLD_SIZE" not in os.environ and a.gpus > 1:
@@ -361,6 +389,8 @@ def main():
     wall = timed_steps(timed_step, a.steps, a.warmup, lambda: torch.cuda.synchronize(dev), dist, dev)
     wall_local = timed_steps.local_wall
     kern_ms = e0.elapsed_time(e1) / a.steps
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, decode, back if decode else out, nbl)     # before the side measurements below write `out` again
     par = None
     if not decode:
         nz = int(out[:, -1, :min(nbl)].ne(0).any(dim=1).sum().item())

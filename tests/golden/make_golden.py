@@ -40,6 +40,7 @@ save("c3_48k_10ms_stereo_128k", fs=48000, frame_ms=10.0, hrmode=0, pairs=np.arra
 wav = "/root/reference/LC3plus_ETSI_src_v17171_20200723/testvec/input/thetest48.wav"
 w = wave.open(wav)
 x = np.frombuffer(w.readframes(w.getnframes()), dtype=np.int16)
+save("c0_thetest48_pcm", pcm=x)                                   # the whole file's PCM: the full-length test runs from it
 Tall = x.size // 480
 allpcm = x[:Tall * 480].reshape(1, Tall, 480)
 full = ref_encode_streams(allpcm, 48000, 10.0, 0, [64000])[0]
