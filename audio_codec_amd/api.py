@@ -27,7 +27,7 @@ EXPORTS = [
     "lc3_free_decoder_structs",
     "lc3plus_dec_batch_create", "lc3plus_dec_batch_destroy", "lc3plus_dec_batch_output_samples", "lc3plus_dec_batch_delay",
     "lc3plus_dec_batch_num_bytes", "lc3plus_dec_batch_set_num_bytes", "lc3plus_dec_batch_decode",
-    "lc3plus_dec_batch_last_kernel_ms", "lc3plus_dec_batch_set_input_ready",
+    "lc3plus_dec_batch_last_kernel_ms", "lc3plus_dec_batch_set_input_ready", "lc3plus_dec_batch_decode_sizes",
 ]
 
 
@@ -81,6 +81,10 @@ def load_library():
                                                C.POINTER(C.c_int), C.c_int]
         L.lc3plus_dec_batch_decode.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int,
                                                C.c_void_p, C.c_void_p, C.c_int]
+        L.lc3plus_dec_batch_decode_sizes.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
+                                                     C.c_int, C.c_void_p, C.c_void_p, C.c_int]
+        L.lc3plus_dec_plan_sizes.argtypes = [C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.lc3plus_dec_batch_decode_traced.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
                                                       C.c_void_p, C.c_void_p]
         L.lc3plus_dec_batch_last_kernel_ms.restype = C.c_float
@@ -256,12 +260,28 @@ class Encoder:
             pass
 
 
+def dec_plan_sizes(samplerate, channels, frame_ms, hrmode, start, num_bytes, bfi=None, in_stride=None):
+    """The per-frame size rule of DecBatch.decode(num_bytes=...) on the host (test hook lc3plus_dec_plan_sizes, no device needed):
+    -> (LC3_Error code, effective sizes [S, T] uint16, lost [S, T] uint8, sizes after the call [S], largest channel frame not lost)."""
+    L = load_library()
+    num_bytes = np.ascontiguousarray(num_bytes, dtype=np.int32)
+    S, T = num_bytes.shape
+    start = np.ascontiguousarray(start, dtype=np.int32)
+    bfi = np.ascontiguousarray(bfi, dtype=np.uint8) if bfi is not None else None
+    eff = np.zeros((S, T), np.uint16); lost = np.zeros((S, T), np.uint8); end = np.zeros(S, np.int32); mx = C.c_int(0)
+    rc = L.lc3plus_dec_plan_sizes(samplerate, channels, frame_ms, hrmode, S, start.ctypes.data, num_bytes.ctypes.data,
+                                  bfi.ctypes.data if bfi is not None else None, T, int(in_stride if in_stride is not None else 1 << 20),
+                                  eff.ctypes.data, lost.ctypes.data, end.ctypes.data, C.byref(mx))
+    return rc, eff, lost, end, mx.value
+
+
 class DecBatch:
     """n_streams independent decoders (lc3plus_dec_batch_*), state resident on the GPU between decode() calls."""
 
     def __init__(self, n_streams, samplerate, channels, frame_ms, hrmode, num_bytes, device=-1):
+        """num_bytes: bytes per stream-frame of every stream, or None (sizes set later or passed with the frames)."""
         self.lib = load_library()
-        nb = (C.c_int * n_streams)(*[int(b) for b in num_bytes])
+        nb = (C.c_int * n_streams)(*[int(b) for b in num_bytes]) if num_bytes is not None else None
         self.h = C.c_void_p()
         rc = self.lib.lc3plus_dec_batch_create(C.byref(self.h), n_streams, samplerate, channels, frame_ms, hrmode, nb, device)
         if rc:
@@ -300,9 +320,23 @@ class DecBatch:
         status = np.zeros((S, T), dtype=np.uint8)
         return frames, T, stride, bfi, pcm, status
 
-    def decode(self, frames, bfi=None, bps=16):
-        """frames: uint8 [n_streams, T, stride]; bfi: optional [n_streams, T] -> (pcm [n_streams, T, channels, N], status)."""
+    def _sizes(self, num_bytes, T):
+        num_bytes = np.ascontiguousarray(num_bytes, dtype=np.int32)
+        if num_bytes.shape != (self.n_streams, T):                 # the C call reads n_streams * T entries
+            raise ValueError("num_bytes must have shape %s, not %s" % ((self.n_streams, T), num_bytes.shape))
+        return num_bytes
+
+    def decode(self, frames, bfi=None, bps=16, num_bytes=None):
+        """frames: uint8 [n_streams, T, stride]; bfi: optional [n_streams, T] -> (pcm [n_streams, T, channels, N], status).
+        num_bytes: optional [n_streams, T] bytes of every stream-frame, 0 = lost (lc3plus_dec_batch_decode_sizes)."""
         frames, T, stride, bfi, pcm, status = self._prep(frames, bfi, bps)
+        if num_bytes is not None:
+            nb = self._sizes(num_bytes, T)
+            rc = self.lib.lc3plus_dec_batch_decode_sizes(self.h, frames.ctypes.data, 0, stride, nb.ctypes.data, bfi.ctypes.data if bfi is not None else None,
+                                                         T, pcm.ctypes.data, 0, bps, status.ctypes.data, None, 1)
+            if rc:
+                raise LC3Error(rc, "lc3plus_dec_batch_decode_sizes")
+            return pcm, status
         rc = self.lib.lc3plus_dec_batch_decode(self.h, frames.ctypes.data, 0, stride, bfi.ctypes.data if bfi is not None else None, T,
                                                pcm.ctypes.data, 0, bps, status.ctypes.data, None, 1)
         if rc:
@@ -325,8 +359,21 @@ class DecBatch:
         if rc:
             raise LC3Error(rc, "lc3plus_dec_batch_set_input_ready")
 
-    def decode_device(self, d_frames_ptr, in_stride, T, d_pcm_ptr, bps=16, hip_stream=None, sync=False):
-        """Device-resident variant: raw device pointers, no bad-frame flags."""
+    def decode_device(self, d_frames_ptr, in_stride, T, d_pcm_ptr, bps=16, hip_stream=None, sync=False, num_bytes=None, bfi=None):
+        """Device-resident variant: raw device pointers.  Without num_bytes no bad-frame flags; with num_bytes ([n_streams, T] host ints, 0 = lost)
+        and optional host bfi the ordered per-frame-size call (lc3plus_dec_batch_decode_sizes), which returns when it is done."""
+        if num_bytes is not None:
+            nb = self._sizes(num_bytes, T)
+            if bfi is not None:
+                bfi = np.ascontiguousarray(bfi, dtype=np.uint8)
+                if bfi.shape != (self.n_streams, T):
+                    raise ValueError("bfi must have shape %s, not %s" % ((self.n_streams, T), bfi.shape))
+            rc = self.lib.lc3plus_dec_batch_decode_sizes(self.h, C.c_void_p(d_frames_ptr), 1, in_stride, nb.ctypes.data,
+                                                         bfi.ctypes.data if bfi is not None else None, T, C.c_void_p(d_pcm_ptr), 1, bps, None,
+                                                         C.c_void_p(hip_stream) if hip_stream else None, 1 if sync else 0)
+            if rc:
+                raise LC3Error(rc, "lc3plus_dec_batch_decode_sizes(device)")
+            return
         rc = self.lib.lc3plus_dec_batch_decode(self.h, C.c_void_p(d_frames_ptr), 1, in_stride, None, T, C.c_void_p(d_pcm_ptr), 1, bps, None,
                                                C.c_void_p(hip_stream) if hip_stream else None, 1 if sync else 0)
         if rc:

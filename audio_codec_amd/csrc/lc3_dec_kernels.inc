@@ -46,7 +46,7 @@ struct __attribute__((aligned(16))) SynLds {         /* lc3_dec_synth_kernel */
     float ly[DEC_LY + 480];              /* LTPF: [output history | this frame's output] */
 #endif
     float sc[160];
-    int pc[LC3D_PLAN_HEAD_WORDS]; int dc[8]; int st[16]; int isc[64];
+    int pc[LC3D_PLAN_HEAD_WORDS]; int st[16]; int isc[64];
 #ifdef LC3_STAGE_TIMING
     long long tacc[16];
 #endif
@@ -59,8 +59,6 @@ static_assert(offsetof(SynLds, A) == offsetof(SynLds, lxh) + 64 && offsetof(SynL
 #endif
 #define DPI(f) uni(L.pc[offsetof(lc3d_plan, f) / 4])
 #define DPF(f) __int_as_float(uni(L.pc[offsetof(lc3d_plan, f) / 4]))
-#define DCI(f) uni(L.dc[offsetof(lc3d_dchan, f) / 4])
-#define DCF(f) __int_as_float(uni(L.dc[offsetof(lc3d_dchan, f) / 4]))
 
 /* forward complex DFT of N/2 points, X -> A: the encoder's stages (same plan, same LDS member names) */
 __device__ __forceinline__ void dec_dft(const lc3d_plan* __restrict__ P, ImdLds& L, int lane)
@@ -136,7 +134,7 @@ __device__ __noinline__ const float* dec_ltpf(const lc3d_plan* __restrict__ P, S
     int p0 = uni(L.isc[30]), p1v = uni(L.isc[31]), p2v = uni(L.isc[32]);
     int pitch_int = 0, pitch_fr = 0;
     float gain = 0;
-    const float beta = DCF(ltpf_beta); const int beta_idx = DCI(ltpf_beta_idx);
+    const float beta = __int_as_float(uni(L.isc[PR_LTPF])); const int beta_idx = uni(L.isc[PR_LTPF + 1]);      /* this frame's configuration (wave-uniform: one channel-stream) */
     if (bfi == 1) { p0 = 0; p1v = 0; }
     if (bfi != 1) {
         if (p0 == 1) {
@@ -224,13 +222,17 @@ __device__ __noinline__ const float* dec_ltpf(const lc3d_plan* __restrict__ P, S
 #ifndef LC3_BIG
 /* Concealment bookkeeping: one channel-stream per lane, frames in order.  nbLostCmpt, the cumulative attenuation and the sign
  * generator's seed (R/plc_main.c, R/plc_noise_substitution0.c:13-40, R/plc_update.c:13-30) depend only on which frames are bad; a
- * lost frame gets (count, attenuation, first seed, index of the last good frame of this launch or -1) into its record. */
+ * lost frame gets (count, attenuation, first seed, index of the last good frame of this launch or -1) into its record.
+ * Every frame also gets its LTPF configuration (PR_LTPF): the channel's configuration, or with per-frame sizes (0 = lost) that of the frame's
+ * size, a lost frame keeping the one of the last good frame (R/dec_lc3_fl.c:146-155) - the channel's configuration before the call at first. */
 extern "C" __global__ void __launch_bounds__(WAVE)
-lc3_dec_plc_kernel(const lc3d_plan* __restrict__ P, float* __restrict__ state, int* __restrict__ rec, int T, int ncs)
+lc3_dec_plc_kernel(const lc3d_plan* __restrict__ P, const lc3d_dchan* __restrict__ chans, const uint16_t* __restrict__ sizes /* [stream][T] or null */,
+                   const lc3d_dchan* __restrict__ dtab, float* __restrict__ state, int* __restrict__ rec, int T, int ncs)
 {
     const int cs = blockIdx.x * WAVE + threadIdx.x;
     const bool valid = cs < ncs;
-    const int Lspec = P->ylen;
+    const int Lspec = P->ylen, channels = P->channels, strm = cs / channels, ch = cs % channels;
+    float beta = valid ? chans[cs].ltpf_beta : 0.0f; int beta_idx = valid ? chans[cs].ltpf_beta_idx : -1;
     int* sc = (int*)(state + (size_t)(valid ? cs : 0) * DST_WORDS + DST_SCAL);
     int nbl = valid ? sc[DS_NBLOST] : 0, seed = valid ? sc[DS_PLC_SEED] : 0, prev = valid ? sc[DS_PREV_BFI] : 0, pprev = valid ? sc[DS_PREVPREV_BFI] : 0;
     float ca = valid ? __int_as_float(sc[DS_CUM_ALPHA]) : 1.0f;
@@ -239,6 +241,11 @@ lc3_dec_plc_kernel(const lc3d_plan* __restrict__ P, float* __restrict__ state, i
         int* r = rec + ((size_t)(valid ? cs : 0) * T + t) * PR_WORDS;
         const int bfi = valid ? r[PR_BFI] : 0;
         const bool lost = valid && bfi == 1;
+        if (valid) {
+            const int fsz = sizes ? (int)sizes[(size_t)strm * T + t] : 0;
+            if (fsz) { const lc3d_dchan* d = &dtab[fsz / channels + (ch < fsz % channels)]; beta = d->ltpf_beta; beta_idx = d->ltpf_beta_idx; }
+            r[PR_LTPF] = __float_as_int(beta); r[PR_LTPF + 1] = beta_idx;
+        }
         if (lost) {
             nbl = nbl + 1;
             const float alpha = nbl < 4 ? 1.0f : nbl < 8 ? (float)0.9 : (float)0.85;
@@ -410,7 +417,7 @@ DEC_IMDCT_KERNEL(const lc3d_plan* __restrict__ P, const float* __restrict__ stat
 #define DEC_SYNTH_EU 4
 #endif
 extern "C" __global__ void __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(DEC_SYNTH_EU, DEC_SYNTH_EU)))
-DEC_SYNTH_KERNEL(const lc3d_plan* __restrict__ P, const lc3d_dchan* __restrict__ chans, float* __restrict__ state,
+DEC_SYNTH_KERNEL(const lc3d_plan* __restrict__ P, float* __restrict__ state,
                  const int* __restrict__ rec, const float* __restrict__ ws, const float* __restrict__ ov /* [cs][T][OV_ROW(N)] */, int T,
                  void* __restrict__ pcm, int bps, int ncs, uint8_t* __restrict__ status /* [stream][T] or null */, lc3d_dec_trace* __restrict__ trace)
 {
@@ -418,7 +425,6 @@ DEC_SYNTH_KERNEL(const lc3d_plan* __restrict__ P, const lc3d_dchan* __restrict__
     const int lane = threadIdx.x, cs = blockIdx.x;
     if (cs >= ncs) return;
     if (lane < LC3D_PLAN_HEAD_WORDS) L.pc[lane] = ((const int*)P)[lane];
-    if (lane < 8) L.dc[lane] = ((const int*)&chans[cs])[lane];
     float* stp = state + (size_t)cs * DST_WORDS;
 #ifndef LC3_BIG
     for (int i = lane; i < DEC_LY; i += WAVE) L.ly[i] = stp[DST_LY + i];

@@ -124,10 +124,14 @@ template <int OFF, int MMAX> __device__ __forceinline__ void pl_pvq(const unsign
     }
 }
 
-/* Workgroup = up to four waves that share the model tables (7.5 KB); every wave owns a slice of the dynamic LDS. */
-template <bool GLOB> __device__ __forceinline__ void
+/* Workgroup = up to four waves that share the model tables (7.5 KB); every wave owns a slice of the dynamic LDS.  VAR: per-frame sizes (a kernel of its own,
+ * so that the fixed-size kernels stay the code they were). */
+template <bool GLOB, bool VAR> __device__ __forceinline__ void
 dec_parse_body(const lc3d_plan* __restrict__ P, const lc3d_dchan* __restrict__ chans, const uint8_t* __restrict__ in, int in_stride,
-                     const uint8_t* __restrict__ bfi_flags /* [stream][T] or null */, int T, int n_streams, int nw_max /* LDS words staged per frame; 0: frames are read from global memory */,
+                     const uint8_t* __restrict__ bfi_flags /* [stream][T] or null */,
+                     const uint16_t* __restrict__ sizes /* VAR: [stream][T] bytes of each stream-frame, 0 where lost */,
+                     const lc3d_dchan* __restrict__ dtab /* VAR: configuration per channel byte count; otherwise chans[channel-stream] */,
+                     int T, int n_streams, int nw_max /* LDS words staged per frame; 0: frames are read from global memory */,
                      int* __restrict__ rec /* [cs][T][PR_WORDS] */, float* __restrict__ ws /* [cs][T][wsr] */, int wsr /* words per spectrum row */)
 {
     __shared__ ParseLds L;
@@ -150,12 +154,18 @@ dec_parse_body(const lc3d_plan* __restrict__ P, const lc3d_dchan* __restrict__ c
     const int max_lev = hr == 1 ? 13 + 8 : 13;
     const int bwrow = (dms == 25 ? 0 : dms == 50 ? 1 : 2) * 6;
 
+    /* VAR: a lane configures its channels from its own stream-frame size, split as R/dec_lc3_fl.c:148 does - at most two channels, the first
+     * (fsz + 1) / 2 bytes, the second fsz / 2 behind it; the lanes of a wave may differ in every field of the configuration (they already do where a wave
+     * spans two streams).  A lost frame comes with size 0: the zeroed configuration, which reads no byte of its slot (the concealment kernel gives it its
+     * carried LTPF configuration). */
     for (int ch = 0; ch < channels; ch++) {
         const int cs = strm * channels + ch;
+        const int fsz = VAR && valid ? (int)sizes[(size_t)strm * T + t] : 0;      /* (read again per channel: nothing of it stays live across the parse) */
         lc3d_dchan dc;
-        { const int* s = (const int*)&chans[valid ? cs : 0]; int* d = (int*)&dc;
+        { const int* s = (const int*)(VAR ? &dtab[(fsz + channels - 1 - ch) >> (channels - 1)] : &chans[valid ? cs : 0]); int* d = (int*)&dc;
 #pragma unroll
           for (int i = 0; i < 8; i++) d[i] = s[i]; }
+        if (VAR) dc.in_off = ch ? (fsz + 1) >> 1 : 0;
         const int nbytes = valid ? dc.nbytes : 0;
         /* ---- stage the frame bytes: fw[w][lane], bytes from nbytes on are zero ---- */
         {
@@ -555,16 +565,19 @@ dec_parse_body(const lc3d_plan* __restrict__ P, const lc3d_dchan* __restrict__ c
 }
 
 #undef XR
-/* frames staged in LDS (up to 128 bytes) */
+/* frames staged in LDS (up to 128 bytes); frames read from global memory (nw_max = 0); each with one size per channel-stream (chans) or with
+ * per-frame sizes (_var) */
 #ifndef DEC_PARSE_EU
 #define DEC_PARSE_EU 4
 #endif
-extern "C" __global__ void __launch_bounds__(4 * WAVE) __attribute__((amdgpu_waves_per_eu(DEC_PARSE_EU, DEC_PARSE_EU)))
-lc3_dec_parse_kernel(const lc3d_plan* __restrict__ P, const lc3d_dchan* __restrict__ chans, const uint8_t* __restrict__ in, int in_stride,
-                     const uint8_t* __restrict__ bfi_flags, int T, int n_streams, int nw_max, int* __restrict__ rec, float* __restrict__ ws, int wsr)
-{ dec_parse_body<false>(P, chans, in, in_stride, bfi_flags, T, n_streams, nw_max, rec, ws, wsr); }
-/* larger frames, read from global memory (nw_max = 0) */
-extern "C" __global__ void __launch_bounds__(4 * WAVE) __attribute__((amdgpu_waves_per_eu(DEC_PARSE_EU, DEC_PARSE_EU)))
-lc3_dec_parse_kernel_g(const lc3d_plan* __restrict__ P, const lc3d_dchan* __restrict__ chans, const uint8_t* __restrict__ in, int in_stride,
-                       const uint8_t* __restrict__ bfi_flags, int T, int n_streams, int nw_max, int* __restrict__ rec, float* __restrict__ ws, int wsr)
-{ dec_parse_body<true>(P, chans, in, in_stride, bfi_flags, T, n_streams, nw_max, rec, ws, wsr); }
+#define DEC_PARSE_KERNEL(name, GLOB, VAR) \
+extern "C" __global__ void __launch_bounds__(4 * WAVE) __attribute__((amdgpu_waves_per_eu(DEC_PARSE_EU, DEC_PARSE_EU))) \
+name(const lc3d_plan* __restrict__ P, const lc3d_dchan* __restrict__ chans, const uint8_t* __restrict__ in, int in_stride, \
+     const uint8_t* __restrict__ bfi_flags, const uint16_t* __restrict__ sizes, const lc3d_dchan* __restrict__ dtab, int T, int n_streams, int nw_max, \
+     int* __restrict__ rec, float* __restrict__ ws, int wsr) \
+{ dec_parse_body<GLOB, VAR>(P, chans, in, in_stride, bfi_flags, sizes, dtab, T, n_streams, nw_max, rec, ws, wsr); }
+DEC_PARSE_KERNEL(lc3_dec_parse_kernel, false, false)
+DEC_PARSE_KERNEL(lc3_dec_parse_kernel_g, true, false)
+DEC_PARSE_KERNEL(lc3_dec_parse_kernel_var, false, true)
+DEC_PARSE_KERNEL(lc3_dec_parse_kernel_g_var, true, true)
+#undef DEC_PARSE_KERNEL

@@ -661,10 +661,59 @@ static LC3_Error derive_dstream(const geom_t* g, int num_bytes, lc3d_dchan* d /*
     return LC3_OK;
 }
 
+/* per-frame sizes: the configuration of every channel byte count 0 .. max, from derive_dchan (entry 0 and the sizes it rejects: zeroed, which is what a
+ * channel created without a size has).  An entry is valid where its nbytes equals its index and is not 0. */
+static int dec_max_chan_bytes(const geom_t* g) { return g->hrmode ? (g->dms == 25 ? 210 : g->dms == 50 ? 375 : 625) : 400; }
+static lc3d_dchan* dec_build_table(const geom_t* g, int* n)
+{
+    *n = dec_max_chan_bytes(g) + 1;
+    lc3d_dchan* tab = (lc3d_dchan*)calloc((size_t)*n, sizeof(lc3d_dchan));
+    if (!tab) return NULL;
+    for (int k = 1; k < *n; k++) if (derive_dchan(g, k, &tab[k])) memset(&tab[k], 0, sizeof tab[k]);
+    return tab;
+}
+
+/* The per-frame size rule of lc3plus_dec_batch_decode_sizes (R/dec_lc3_fl.c:134-163 per stream): a frame is lost where bfi is 1 or its size is 0; a good
+ * frame's size configures its channels, a lost one keeps the size of the stream's last good frame (start[s] before the first).  Validates every good size
+ * (geometry limits through the table, <= in_stride) and every flag (0 or 1) before anything is written.  Out: eff [s][t] the size each frame is configured
+ * with, lost [s][t] 0 / 1, end[s] the size after the call, *max_chan the largest channel frame that is not lost (0: none). */
+static LC3_Error dec_plan_sizes(const geom_t* g, const lc3d_dchan* tab, int tab_n, int n_streams, const int* start, const int* num_bytes, const uint8_t* bfi,
+                                int n_frames, int in_stride, uint16_t* eff, uint8_t* lost, int* end, int* max_chan)
+{
+    const int C = g->channels;
+    const size_t n = (size_t)n_streams * n_frames;
+    int mx = 0;
+    for (size_t i = 0; i < n; i++) {
+        if (bfi && bfi[i] > 1) return LC3_ERROR;
+        const int nb = num_bytes[i];
+        if ((bfi && bfi[i]) || nb == 0) continue;
+        if (nb < 0 || nb > in_stride) return LC3_NUMBYTES_ERROR;
+        for (int c = 0; c < C; c++) {
+            const int k = nb / C + (c < nb % C);
+            if (k >= tab_n || k == 0 || tab[k].nbytes != k) return LC3_NUMBYTES_ERROR;
+        }
+        if ((nb + C - 1) / C > mx) mx = (nb + C - 1) / C;
+    }
+    for (int s = 0; s < n_streams; s++) {
+        int cur = start[s];
+        for (int t = 0; t < n_frames; t++) {
+            const size_t i = (size_t)s * n_frames + t;
+            const int l = (bfi && bfi[i]) || num_bytes[i] == 0;
+            if (!l) cur = num_bytes[i];
+            eff[i] = (uint16_t)cur; lost[i] = (uint8_t)l;
+        }
+        end[s] = cur;
+    }
+    *max_chan = mx;
+    return LC3_OK;
+}
+
 struct lc3plus_dec_batch {
     geom_t g; int n_streams;
     lc3d_dchan* chans;               /* [n_streams * channels] host mirror */
     void* dev;
+    lc3d_dchan* tab; int tab_n;      /* dec_build_table, also on the device */
+    uint16_t* eff; uint8_t* lost; int* sz; size_t plan_cap;          /* per-frame sizes: host buffers of dec_plan_sizes, grown as needed */
 };
 
 LC3_Error lc3plus_dec_batch_create(lc3plus_dec_batch** out, int n_streams, int samplerate, int channels, float frame_ms, int hrmode,
@@ -701,7 +750,8 @@ LC3_Error lc3plus_dec_batch_create(lc3plus_dec_batch** out, int n_streams, int s
     int rc = lc3hip_dec_create(&b->dev, plan, n_streams, device);
     free(plan);
     if (!rc) rc = lc3hip_dec_upload_chans(b->dev, b->chans, 0, n_streams * channels);
-    if (rc) { if (b->dev) lc3hip_dec_destroy(b->dev); free(b->chans); free(b); return LC3_ERROR; }
+    if (!rc) { b->tab = dec_build_table(&b->g, &b->tab_n); rc = !b->tab || lc3hip_dec_upload_table(b->dev, b->tab, b->tab_n); }
+    if (rc) { if (b->dev) lc3hip_dec_destroy(b->dev); free(b->tab); free(b->chans); free(b); return LC3_ERROR; }
     *out = b;
     return LC3_OK;
 }
@@ -722,6 +772,7 @@ LC3_Error lc3plus_dec_batch_destroy(lc3plus_dec_batch* b)
 {
     if (!b) return LC3_NULL_ERROR;
     lc3hip_dec_destroy(b->dev);
+    free(b->tab); free(b->eff); free(b->lost); free(b->sz);
     free(b->chans); free(b);
     return LC3_OK;
 }
@@ -756,8 +807,65 @@ static LC3_Error dec_batch_decode(lc3plus_dec_batch* b, const void* frames, int 
     if (bps != 16 && bps != 24 && bps != 32) return LC3_ERROR;
     if (n_frames <= 0) return LC3_ERROR;
     for (int i = 0; i < b->n_streams; i++) if (lc3plus_dec_batch_num_bytes(b, i) > in_stride) return LC3_NUMBYTES_ERROR;
-    return lc3hip_dec_decode(b->dev, frames, frames_on_device, in_stride, bfi, n_frames, pcm, pcm_on_device, bps, status, hip_stream, sync, traces)
+    return lc3hip_dec_decode(b->dev, frames, frames_on_device, in_stride, bfi, NULL, 0, n_frames, pcm, pcm_on_device, bps, status, hip_stream, sync, traces)
                ? LC3_ERROR : LC3_OK;
+}
+LC3_Error lc3plus_dec_batch_decode_sizes(lc3plus_dec_batch* b, const void* frames, int frames_on_device, int in_stride, const int* num_bytes,
+                                         const uint8_t* bfi, int n_frames, void* pcm, int pcm_on_device, int bps, uint8_t* status, void* hip_stream, int sync)
+{
+    if (!b || !frames || !pcm || !num_bytes) return LC3_NULL_ERROR;
+    if (bps != 16 && bps != 24 && bps != 32) return LC3_ERROR;
+    if (n_frames <= 0) return LC3_ERROR;
+    const size_t n = (size_t)b->n_streams * n_frames;
+    if (b->plan_cap < n) {
+        free(b->eff); free(b->lost); b->plan_cap = 0;
+        b->eff = (uint16_t*)malloc(n * sizeof(uint16_t)); b->lost = (uint8_t*)malloc(n);
+        if (!b->eff || !b->lost) return LC3_ERROR;
+        b->plan_cap = n;
+    }
+    if (!b->sz) { b->sz = (int*)malloc(2 * sizeof(int) * (size_t)b->n_streams); if (!b->sz) return LC3_ERROR; }
+    int* start = b->sz; int* end = b->sz + b->n_streams;
+    for (int i = 0; i < b->n_streams; i++) start[i] = lc3plus_dec_batch_num_bytes(b, i);
+    int max_chan = 0;
+    LC3_Error e = dec_plan_sizes(&b->g, b->tab, b->tab_n, b->n_streams, start, num_bytes, bfi, n_frames, in_stride, b->eff, b->lost, end, &max_chan);
+    if (e) return e;
+    /* the kernels take the size of every good frame and 0 for a lost one: the parser reads nothing of a lost frame's slot, and the concealment kernel
+     * carries the last good configuration from frame to frame (from the stream's configuration before the call), as dec_plan_sizes does here */
+    for (size_t i = 0; i < n; i++) if (b->lost[i]) b->eff[i] = 0;
+    /* the call is ordered and synchronous (it passes flags), and no kernel of it reads the per-stream configuration: that is brought to the last good
+     * size of every stream after it */
+    if (lc3hip_dec_decode(b->dev, frames, frames_on_device, in_stride, b->lost, b->eff, max_chan, n_frames, pcm, pcm_on_device, bps, status, hip_stream, sync, NULL))
+        return LC3_ERROR;
+    int changed = 0;
+    for (int i = 0; i < b->n_streams; i++) {
+        if (end[i] == start[i]) continue;
+        lc3d_dchan* d = b->chans + (size_t)i * b->g.channels;
+        for (int c = 0, off = 0; c < b->g.channels; c++) {
+            d[c] = b->tab[end[i] / b->g.channels + (c < end[i] % b->g.channels)];
+            d[c].in_off = off; off += d[c].nbytes;
+        }
+        changed = 1;
+    }
+    if (changed && lc3hip_dec_upload_chans(b->dev, b->chans, 0, b->n_streams * b->g.channels)) return LC3_ERROR;
+    return LC3_OK;
+}
+/* test hook: dec_plan_sizes for a geometry, without a device (the batch builds the same table at create) */
+LC3_Error lc3plus_dec_plan_sizes(int samplerate, int channels, float frame_ms, int hrmode, int n_streams, const int* start, const int* num_bytes,
+                                 const uint8_t* bfi, int n_frames, int in_stride, uint16_t* eff, uint8_t* lost, int* end, int* max_chan)
+{
+    if (!start || !num_bytes || !eff || !lost || !end || !max_chan) return LC3_NULL_ERROR;
+    if (!samplerate_ok(samplerate)) return LC3_SAMPLERATE_ERROR;
+    if (channels < 1 || channels > MAX_CH) return LC3_CHANNELS_ERROR;
+    geom_t g;
+    geom_init(&g, samplerate, channels);
+    g.dms = (int)(frame_ms * 10); g.frame_ms = frame_ms; g.hrmode = hrmode > 0;
+    geom_update_ex(&g, 1);
+    int tab_n = 0;
+    lc3d_dchan* tab = dec_build_table(&g, &tab_n);
+    if (!tab) return LC3_ERROR;
+    LC3_Error e = dec_plan_sizes(&g, tab, tab_n, n_streams, start, num_bytes, bfi, n_frames, in_stride, eff, lost, end, max_chan);
+    free(tab);
+    return e;
 }
 LC3_Error lc3plus_dec_batch_decode(lc3plus_dec_batch* b, const void* frames, int frames_on_device, int in_stride, const uint8_t* bfi, int n_frames,
                                    void* pcm, int pcm_on_device, int bps, uint8_t* status, void* hip_stream, int sync)

@@ -3595,7 +3595,7 @@ extern "C" int lc3hip_destroy(void* ctx)
 /* ---- decoder shim ---- */
 extern "C" __global__ void lc3_dec_imdct_kernel_big(const lc3d_plan* __restrict__ P, const float* __restrict__ state, const int* __restrict__ rec, const float* __restrict__ ws,
                                                     int T, int ncs, float* __restrict__ ov, lc3d_dec_trace* __restrict__ trace);
-extern "C" __global__ void lc3_dec_synth_kernel_big(const lc3d_plan* __restrict__ P, const lc3d_dchan* __restrict__ chans, float* __restrict__ state, const int* __restrict__ rec,
+extern "C" __global__ void lc3_dec_synth_kernel_big(const lc3d_plan* __restrict__ P, float* __restrict__ state, const int* __restrict__ rec,
                                                     const float* __restrict__ ws, const float* __restrict__ ov, int T, void* __restrict__ pcm, int bps, int ncs,
                                                     uint8_t* __restrict__ status, lc3d_dec_trace* __restrict__ trace);
 #ifndef DEC_SETS
@@ -3606,13 +3606,25 @@ struct lc3hip_dctx {
     int device, ncs, n_streams, channels, N, big;
     lc3d_plan* d_plan; lc3d_dchan* d_chans; float* d_state;
     uint8_t* d_in; size_t in_cap; void* d_pcm; size_t pcm_cap; uint8_t* d_bfi; size_t bfi_cap;
+    lc3d_dchan* d_tab; uint16_t* d_sizes; size_t sizes_cap;          /* per-frame sizes: configuration per channel byte count, effective size per stream-frame */
     lc3d_dec_trace* d_trace; size_t trace_cap; uint8_t* d_status; size_t status_cap;
     int* d_rec; float* d_ws; float* d_ov; size_t hand_cap; int max_nbytes; int* h_nbytes;
     hipStream_t stream, last_stream; hipEvent_t ev0, ev1; float last_ms;
     /* lc3hip_dec_set_input_ready: the parse kernel of a call runs on a stream of its own beside the transform and synthesis of the call before; a
      * second set of hand-over buffers (records, spectrum rows), alternating */
     int input_ready, set; int* d_recx[DEC_SETS - 1]; float* d_wsx[DEC_SETS - 1]; size_t handx_cap; hipStream_t s_par, s_plc; hipEvent_t ev_par[DEC_SETS], ev_free[DEC_SETS], ev_plc; int free_armed[DEC_SETS];
+    /* the end of the last ordered call (bad-frame flags, per-frame sizes, status, host pointers) under the promise: the next parse-ahead waits for it */
+    hipEvent_t ev_ord; int ord_pending;
 };
+static int dec_side_streams(lc3hip_dctx* c)                       /* the parse-ahead stream, the concealment stream and their events, created once */
+{
+    if (c->s_par) return 0;
+    HIPCHK(hipStreamCreateWithFlags(&c->s_par, hipStreamNonBlocking));
+    for (int i = 0; i < DEC_SETS; i++) { HIPCHK(hipEventCreateWithFlags(&c->ev_par[i], hipEventDisableTiming)); HIPCHK(hipEventCreateWithFlags(&c->ev_free[i], hipEventDisableTiming)); }
+    HIPCHK(hipStreamCreateWithFlags(&c->s_plc, hipStreamNonBlocking)); HIPCHK(hipEventCreateWithFlags(&c->ev_plc, hipEventDisableTiming));
+    HIPCHK(hipEventCreateWithFlags(&c->ev_ord, hipEventDisableTiming));
+    return 0;
+}
 extern "C" int lc3hip_dec_destroy(void* ctx);
 extern "C" int lc3hip_dec_create(void** out_ctx, const lc3d_plan* plan, int n_streams, int device)
 {
@@ -3660,8 +3672,19 @@ extern "C" int lc3hip_dec_upload_chans(void* ctx, const lc3d_dchan* chans, int f
     for (int i = 0; i < c->ncs; i++) if (c->h_nbytes[i] > c->max_nbytes) c->max_nbytes = c->h_nbytes[i];
     return 0;
 }
-extern "C" int lc3hip_dec_decode(void* ctx, const void* frames, int frames_on_device, int in_stride, const uint8_t* bfi_host, int n_frames,
-                                 void* pcm, int pcm_on_device, int bps, uint8_t* status_host, void* hip_stream, int sync, void* trace_host)
+extern "C" int lc3hip_dec_upload_table(void* ctx, const lc3d_dchan* tab, int n)
+{
+    lc3hip_dctx* c = (lc3hip_dctx*)ctx;
+    HIPCHK(hipSetDevice(c->device));
+    if (c->d_tab) HIPCHK(hipFree(c->d_tab));
+    c->d_tab = nullptr;
+    HIPCHK(hipMalloc((void**)&c->d_tab, sizeof(lc3d_dchan) * (size_t)n));
+    HIPCHK(hipMemcpy(c->d_tab, tab, sizeof(lc3d_dchan) * (size_t)n, hipMemcpyHostToDevice));
+    return 0;
+}
+extern "C" int lc3hip_dec_decode(void* ctx, const void* frames, int frames_on_device, int in_stride, const uint8_t* bfi_host, const uint16_t* sizes_host,
+                                 int sizes_max_nbytes, int n_frames, void* pcm, int pcm_on_device, int bps, uint8_t* status_host, void* hip_stream, int sync,
+                                 void* trace_host)
 {
     lc3hip_dctx* c = (lc3hip_dctx*)ctx;
     HIPCHK(hipSetDevice(c->device));
@@ -3683,6 +3706,14 @@ extern "C" int lc3hip_dec_decode(void* ctx, const void* frames, int frames_on_de
         if (c->bfi_cap < fb) { if (c->d_bfi) HIPCHK(hipFree(c->d_bfi)); HIPCHK(hipMalloc((void**)&c->d_bfi, fb)); c->bfi_cap = fb; }
         HIPCHK(hipMemcpyAsync(c->d_bfi, bfi_host, fb, hipMemcpyHostToDevice, s));
         dbfi = c->d_bfi;
+    }
+    const uint16_t* dsizes = nullptr;
+    if (sizes_host) {                                               /* per-frame sizes: the host merged the lost frames into bfi_host, so this call is ordered */
+        if (!bfi_host || !c->d_tab) return 1;
+        const size_t fb = sizeof(uint16_t) * (size_t)c->n_streams * n_frames;
+        if (c->sizes_cap < fb) { if (c->d_sizes) HIPCHK(hipFree(c->d_sizes)); HIPCHK(hipMalloc((void**)&c->d_sizes, fb)); c->sizes_cap = fb; }
+        HIPCHK(hipMemcpyAsync(c->d_sizes, sizes_host, fb, hipMemcpyHostToDevice, s));
+        dsizes = c->d_sizes;
     }
     if (trace_host) {
         const size_t tb = sizeof(lc3d_dec_trace) * (size_t)c->ncs * n_frames;
@@ -3716,11 +3747,7 @@ extern "C" int lc3hip_dec_decode(void* ctx, const void* frames, int frames_on_de
     int* rec_w = c->d_rec; float* ws_w = c->d_ws;
     if (ahead) {
         const size_t cf = (size_t)c->ncs * n_frames;
-        if (!c->s_par) {
-            HIPCHK(hipStreamCreateWithFlags(&c->s_par, hipStreamNonBlocking));
-            for (int i = 0; i < DEC_SETS; i++) { HIPCHK(hipEventCreateWithFlags(&c->ev_par[i], hipEventDisableTiming)); HIPCHK(hipEventCreateWithFlags(&c->ev_free[i], hipEventDisableTiming)); }
-            HIPCHK(hipStreamCreateWithFlags(&c->s_plc, hipStreamNonBlocking)); HIPCHK(hipEventCreateWithFlags(&c->ev_plc, hipEventDisableTiming));
-        }
+        if (dec_side_streams(c)) return 1;
         if (c->handx_cap < cf) {
             HIPCHK(hipDeviceSynchronize());
             for (int i = 0; i < DEC_SETS - 1; i++) {
@@ -3739,17 +3766,24 @@ extern "C" int lc3hip_dec_decode(void* ctx, const void* frames, int frames_on_de
     }
     hipStream_t sp = ahead ? c->s_par : s;
     /* frames of up to 128 bytes are staged in LDS; larger ones would cut the waves per workgroup and are read from global memory */
-    const int nw_max = c->max_nbytes > 128 ? 0 : c->max_nbytes > 0 ? (c->max_nbytes + 3) / 4 : 1;
+    /* (per-frame sizes: the largest channel frame of the call that is not lost - lost frames stage nothing) */
+    const int max_nb = dsizes ? sizes_max_nbytes : c->max_nbytes;
+    const int nw_max = max_nb > 128 ? 0 : max_nb > 0 ? (max_nb + 3) / 4 : 1;
     const int nlw = (WS_ROW(c->N) / 2 + 31) / 32;                          /* >= (ylen / 2 + 31) / 32 of the plan */
     const size_t per_wave = (size_t)(nw_max + nlw) * WAVE * sizeof(unsigned);
     int wpg = (int)((64 * 1024 - sizeof(ParseLds)) / per_wave);            /* waves per workgroup: they share the model tables */
     if (wpg > 4) wpg = 4;
-    if (wpg < 1) { fprintf(stderr, "lc3plus_hip: frame of %d bytes exceeds the parse kernel's LDS staging\n", c->max_nbytes); return 1; }
+    if (wpg < 1) { fprintf(stderr, "lc3plus_hip: frame of %d bytes exceeds the parse kernel's LDS staging\n", max_nb); return 1; }
     const long long tasks = (long long)c->n_streams * n_frames, per_wg = (long long)wpg * WAVE;
     HIPCHK(hipEventRecord(c->ev0, s));
     /* parse: one stream-frame per lane; concealment bookkeeping: one channel-stream per lane; IMDCT: one channel-frame per wave;
      * synthesis: one channel-stream per wave (lc3_dec_kernels.inc) */
     if (ahead && c->free_armed[c->set]) HIPCHK(hipStreamWaitEvent(sp, c->ev_free[c->set], 0));      /* this set was last read by the synthesis of the call DEC_SETS back */
+    /* The first parse-ahead behind an ordered call waits for all of it: that call's transform and synthesis read the first set of hand-over buffers, and its
+     * concealment kernel (on s) must not be overtaken by this call's (on s_plc, behind this parser) - both read-modify-write the concealment words.  Today
+     * every ordered call made under the promise returns only when it is done (it passes flags, sizes, status or host pointers, see the synchronisation at
+     * the end), so the event has completed when this wait is queued; it states the order instead of leaving it to that synchronisation. */
+    if (ahead && c->ord_pending) { HIPCHK(hipStreamWaitEvent(sp, c->ev_ord, 0)); c->ord_pending = 0; }
     /* How many parse waves a CU holds.  The kernel for frames of more than 128 bytes reads its frames from global memory and needs little LDS, so its 4 096
      * waves of 128 registers fill every SIMD, and the 64-wave concealment kernel and the transform of the call before wait for parse waves to retire; 24 KB of
      * padding per workgroup leave room beside them: d5 81.3 -> 88.7 Mframes/s (20 KB: 87.1, 28 KB: 77.1).  The kernel that stages its frames in LDS (d1) loses
@@ -3758,10 +3792,9 @@ extern "C" int lc3hip_dec_decode(void* ctx, const void* frames, int frames_on_de
      * with the tables of the time) */
     const size_t quarter = (160u << 10) / 4, used = sizeof(ParseLds) + per_wave * wpg;
     const size_t pad = c->opt.dec_parse_pad_kb >= 0 ? (size_t)c->opt.dec_parse_pad_kb << 10 : (nw_max || used >= quarter ? 0 : quarter - used);
-    if (nw_max) hipLaunchKernelGGL(lc3_dec_parse_kernel, dim3((unsigned)((tasks + per_wg - 1) / per_wg)), dim3(wpg * WAVE), per_wave * wpg + pad, sp, c->d_plan, c->d_chans, din, in_stride,
-                                   dbfi, n_frames, c->n_streams, nw_max, rec_w, ws_w, WS_ROW(c->N));
-    else hipLaunchKernelGGL(lc3_dec_parse_kernel_g, dim3((unsigned)((tasks + per_wg - 1) / per_wg)), dim3(wpg * WAVE), per_wave * wpg + pad, sp, c->d_plan, c->d_chans, din, in_stride,
-                            dbfi, n_frames, c->n_streams, nw_max, rec_w, ws_w, WS_ROW(c->N));
+    auto parse = dsizes ? (nw_max ? lc3_dec_parse_kernel_var : lc3_dec_parse_kernel_g_var) : (nw_max ? lc3_dec_parse_kernel : lc3_dec_parse_kernel_g);
+    hipLaunchKernelGGL(parse, dim3((unsigned)((tasks + per_wg - 1) / per_wg)), dim3(wpg * WAVE), per_wave * wpg + pad, sp, c->d_plan, c->d_chans, din, in_stride,
+                       dbfi, dsizes, c->d_tab, n_frames, c->n_streams, nw_max, rec_w, ws_w, WS_ROW(c->N));
     HIPCHK(hipGetLastError());
     /* The concealment bookkeeping needs its call's parser and the bookkeeping of the call before - NOT the transform or the synthesis of the call before.  On the caller's stream it
      * became runnable at the moment the NEXT call's parser did (both behind the previous synthesis; the parser waits for its set of hand-over buffers), lost the race for the SIMDs to
@@ -3773,24 +3806,28 @@ extern "C" int lc3hip_dec_decode(void* ctx, const void* frames, int frames_on_de
         HIPCHK(hipEventRecord(c->ev_par[c->set], sp)); HIPCHK(hipStreamWaitEvent(spl, c->ev_par[c->set], 0));
     } else if (ahead) { HIPCHK(hipEventRecord(c->ev_par[c->set], sp)); HIPCHK(hipStreamWaitEvent(s, c->ev_par[c->set], 0)); }
     else if (c->s_plc) HIPCHK(hipStreamWaitEvent(s, c->ev_plc, 0));      /* an ordered call behind ahead calls: the bookkeeping is a chain (the event of the last one, if any: waiting on a fresh event is a no-op) */
-    hipLaunchKernelGGL(lc3_dec_plc_kernel, dim3((unsigned)((c->ncs + WAVE - 1) / WAVE)), dim3(WAVE), 0, spl, c->d_plan, c->d_state, rec_w, n_frames, c->ncs);
+    hipLaunchKernelGGL(lc3_dec_plc_kernel, dim3((unsigned)((c->ncs + WAVE - 1) / WAVE)), dim3(WAVE), 0, spl, c->d_plan, c->d_chans, dsizes, c->d_tab, c->d_state, rec_w, n_frames, c->ncs);
     HIPCHK(hipGetLastError());
     if (spl != s) { HIPCHK(hipEventRecord(c->ev_plc, spl)); HIPCHK(hipStreamWaitEvent(s, c->ev_plc, 0)); }
     const unsigned ncf = (unsigned)((size_t)c->ncs * ((n_frames + IMDCT_FPW - 1) / IMDCT_FPW));     /* runs of IMDCT_FPW frames */
     if (c->big) {
         hipLaunchKernelGGL(lc3_dec_imdct_kernel_big, dim3(ncf), dim3(WAVE), 0, s, c->d_plan, c->d_state, rec_w, ws_w, n_frames, c->ncs, c->d_ov, dtr);
-        hipLaunchKernelGGL(lc3_dec_synth_kernel_big, dim3(c->ncs), dim3(WAVE), 0, s, c->d_plan, c->d_chans, c->d_state, rec_w, ws_w, c->d_ov, n_frames, dpcm, bps, c->ncs, dst, dtr);
+        hipLaunchKernelGGL(lc3_dec_synth_kernel_big, dim3(c->ncs), dim3(WAVE), 0, s, c->d_plan, c->d_state, rec_w, ws_w, c->d_ov, n_frames, dpcm, bps, c->ncs, dst, dtr);
     } else {
         const int i4 = c->opt.dec_imdct4;
         if (i4 && !dtr && c->N == 480)
             hipLaunchKernelGGL(lc3_dec_imdct4_kernel, dim3((unsigned)((size_t)c->ncs * ((n_frames + 3) / 4))), dim3(WAVE), 0, s, c->d_plan, c->d_state, rec_w, ws_w, n_frames, c->ncs, c->d_ov);
         else
         hipLaunchKernelGGL(lc3_dec_imdct_kernel, dim3(ncf), dim3(WAVE), 0, s, c->d_plan, c->d_state, rec_w, ws_w, n_frames, c->ncs, c->d_ov, dtr);
-        hipLaunchKernelGGL(lc3_dec_synth_kernel, dim3(c->ncs), dim3(WAVE), 0, s, c->d_plan, c->d_chans, c->d_state, rec_w, ws_w, c->d_ov, n_frames, dpcm, bps, c->ncs, dst, dtr);
+        hipLaunchKernelGGL(lc3_dec_synth_kernel, dim3(c->ncs), dim3(WAVE), 0, s, c->d_plan, c->d_state, rec_w, ws_w, c->d_ov, n_frames, dpcm, bps, c->ncs, dst, dtr);
     }
     HIPCHK(hipGetLastError());
     if (ahead) { HIPCHK(hipEventRecord(c->ev_free[c->set], s)); c->free_armed[c->set] = 1; c->set = (c->set + 1) % DEC_SETS; }
     else if (c->s_par) { HIPCHK(hipEventRecord(c->ev_free[0], s)); c->free_armed[0] = 1; }      /* an ordered call reads the first set: a later parse-ahead into it waits for this one */
+    if (!ahead && c->input_ready) {                                  /* ... and the next parse-ahead waits for the whole call (see above) */
+        if (dec_side_streams(c)) return 1;
+        HIPCHK(hipEventRecord(c->ev_ord, s)); c->ord_pending = 1;
+    }
     c->last_stream = s;
     HIPCHK(hipEventRecord(c->ev1, s));
     if (!pcm_on_device) HIPCHK(hipMemcpyAsync(pcm, dpcm, pcm_bytes, hipMemcpyDeviceToHost, s));
@@ -3838,9 +3875,9 @@ extern "C" int lc3hip_dec_destroy(void* ctx)
     if (!c) return 0;
     hipSetDevice(c->device);
     hipDeviceSynchronize();
-    void* bufs[] = {c->d_plan, c->d_chans, c->d_state, c->d_in, c->d_pcm, c->d_bfi, c->d_trace, c->d_status, c->d_rec, c->d_ws, c->d_ov};
+    void* bufs[] = {c->d_plan, c->d_chans, c->d_state, c->d_in, c->d_pcm, c->d_bfi, c->d_trace, c->d_status, c->d_rec, c->d_ws, c->d_ov, c->d_tab, c->d_sizes};
     for (int i = 0; i < DEC_SETS - 1; i++) { if (c->d_recx[i]) hipFree(c->d_recx[i]); if (c->d_wsx[i]) hipFree(c->d_wsx[i]); }
-    if (c->s_par) { hipStreamDestroy(c->s_par); for (int i = 0; i < DEC_SETS; i++) { hipEventDestroy(c->ev_par[i]); hipEventDestroy(c->ev_free[i]); } hipStreamDestroy(c->s_plc); hipEventDestroy(c->ev_plc); }
+    if (c->s_par) { hipStreamDestroy(c->s_par); for (int i = 0; i < DEC_SETS; i++) { hipEventDestroy(c->ev_par[i]); hipEventDestroy(c->ev_free[i]); } hipStreamDestroy(c->s_plc); hipEventDestroy(c->ev_plc); hipEventDestroy(c->ev_ord); }
     for (void* p : bufs) if (p) hipFree(p);
     if (c->stream) hipStreamDestroy(c->stream);
     if (c->ev0) hipEventDestroy(c->ev0);

@@ -123,12 +123,13 @@ typedef struct {                         /* per channel-stream decoder configura
 #define PK_XQ  224                       /* quantised spectrum up to lastnz: one word per 2-tuple (int16 pairs), or int32 lines in high-resolution mode */
 #define PK_STRIDE(N, hr) (PK_XQ + ((hr) ? ((N) > 480 ? 960 : 480) : ((N) > 480 ? 480 : 240)))
 /* hand-over between the two decoder kernels (lc3_dec_parse.inc -> lc3_dec_kernels.inc), both in HBM */
-#define PR_WORDS 112                     /* per channel-frame record: isc[0..38] of the decoder (side information), [39] = bfi after parsing, [48..111] = the 64 SNS band gains */
+#define PR_WORDS 112                     /* per channel-frame record: isc[0..38] of the decoder (side information), [39] = bfi after parsing, [44..45] LTPF configuration, [48..111] = the 64 SNS band gains */
 #define PR_GAINS 48
 #define PR_PLC 40                        /* lost frames: [40] nbLostCmpt, [41] cumulative attenuation (float), [42] first seed, [43] last good frame of the launch or -1 */
 #define OV_ROW_STD 480                    /* transformed frame in HBM: the N samples of the time-domain aliasing buffer (R/imdct.c:34-44), standard layout */
 #define OV_ROW_BIG 960                    /* large layout */
 #define PR_BFI 39
+#define PR_LTPF 44                       /* the frame's LTPF configuration, written by the concealment kernel: [44] ltpf_beta (float), [45] ltpf_beta_idx (frame sizes can change per frame) */
 #define WS_ROW(N) ((N) > 480 ? 960 : 480)  /* per channel-frame spectrum row (words) */
 enum { DS_PITCH_INT = 0, DS_PITCH_FR, DS_BETA_IDX, DS_PARAM0, DS_PARAM1, DS_PARAM2, DS_GAIN /* float */, DS_NBLOST, DS_CUM_ALPHA /* float */, DS_PLC_SEED,
        DS_PREV_BFI, DS_PREVPREV_BFI };

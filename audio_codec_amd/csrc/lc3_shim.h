@@ -26,8 +26,12 @@ extern "C" {
 #endif
 int   lc3hip_dec_create(void** ctx, const lc3d_plan* plan, int n_streams, int device);
 int   lc3hip_dec_upload_chans(void* ctx, const lc3d_dchan* chans, int first, int count);
-int   lc3hip_dec_decode(void* ctx, const void* frames, int frames_on_device, int in_stride, const uint8_t* bfi_flags_host, int n_frames,
-                        void* pcm, int pcm_on_device, int bps, uint8_t* status_host, void* hip_stream, int sync, void* trace_host);
+int   lc3hip_dec_upload_table(void* ctx, const lc3d_dchan* tab, int n);      /* configuration per channel byte count 0 .. n - 1 (per-frame sizes) */
+/* sizes_host: null, or [n_streams][n_frames] stream-frame sizes, 0 where lost (bfi_flags_host then holds every lost frame); sizes_max_nbytes: the largest
+ * channel frame of the call that is not lost */
+int   lc3hip_dec_decode(void* ctx, const void* frames, int frames_on_device, int in_stride, const uint8_t* bfi_flags_host, const uint16_t* sizes_host,
+                        int sizes_max_nbytes, int n_frames, void* pcm, int pcm_on_device, int bps, uint8_t* status_host, void* hip_stream, int sync,
+                        void* trace_host);
 float lc3hip_dec_last_ms(void* ctx);
 int   lc3hip_dec_destroy(void* ctx);
 int   lc3hip_create(void** ctx, const lc3d_plan* plan, int n_streams, int device);

@@ -82,7 +82,7 @@ int lc3plus_enc_batch_record_words(void);
 
 /* ---- batched decoder: n_streams independent decoder instances, one wavefront per channel-stream; same
  * conventions as the encoder batch.  num_bytes[n_streams] = bytes per stream-frame (all channels; may be NULL
- * and set later per stream).  R/dec_lc3_fl.c:134-163 is what one (stream, frame) does. ---- */
+ * and set later per stream, or come with the frames: lc3plus_dec_batch_decode_sizes).  R/dec_lc3_fl.c:134-163 is what one (stream, frame) does. ---- */
 typedef struct lc3plus_dec_batch lc3plus_dec_batch;
 LC3_Error lc3plus_dec_batch_create(lc3plus_dec_batch** batch, int n_streams, int samplerate, int channels,
                                    float frame_ms, int hrmode, const int* num_bytes, int device);
@@ -98,6 +98,20 @@ LC3_Error lc3plus_dec_batch_set_num_bytes(lc3plus_dec_batch* batch, int stream, 
 LC3_Error lc3plus_dec_batch_decode(lc3plus_dec_batch* batch, const void* frames, int frames_on_device, int in_stride,
                                    const uint8_t* bfi, int n_frames, void* pcm, int pcm_on_device, int bps,
                                    uint8_t* status, void* hip_stream, int sync);
+/* Per-frame frame sizes, as the reference takes them (R/dec_lc3_fl.c:134-163: one size per lc3_dec_fl call).  Arguments as decode(), and
+ *   num_bytes : host pointer, [n_streams][n_frames] bytes of each stream-frame (all channels); 0 = lost frame (R/dec_lc3_fl.c:140-143)
+ *   bfi       : host pointer or NULL, [n_streams][n_frames] flags 0 or 1 (any other value: LC3_ERROR)
+ * Per stream: a frame is lost where bfi is 1 or its size is 0, and is concealed (status 1).  A good frame configures its channels from its own size,
+ * split over the channels as the reference does; a lost frame keeps the configuration of the stream's last good frame - across calls: the first
+ * frame of a call carries the size the stream had before it (from create, set_num_bytes or the last good frame of an earlier call).  After the
+ * call num_bytes(stream) is the size of the stream's last good frame, and a later decode() continues from it; the frame sizes stay configuration,
+ * not state (get_state / set_state are unchanged: a checkpoint resumes on a batch created with those sizes).  A lost frame's slot is never read.
+ * Every good size is checked before any work: outside the limits of the geometry, or larger than in_stride, the call returns LC3_NUMBYTES_ERROR
+ * and decodes nothing (the reference fails at the bad frame, after decoding the ones before it).  The call is ordered and returns when it is done,
+ * as a decode() with bfi; frames and pcm may be device pointers. */
+LC3_Error lc3plus_dec_batch_decode_sizes(lc3plus_dec_batch* batch, const void* frames, int frames_on_device, int in_stride,
+                                         const int* num_bytes, const uint8_t* bfi, int n_frames, void* pcm, int pcm_on_device,
+                                         int bps, uint8_t* status, void* hip_stream, int sync);
 float     lc3plus_dec_batch_last_kernel_ms(lc3plus_dec_batch* batch);
 /* checkpoint / resume of the decoders' cross-frame state (overlap-add memory, last good spectrum, LTPF histories, concealment words), as
  * for the encoder batch; the frame sizes are configuration (lc3plus_dec_batch_set_num_bytes), not state */

@@ -4,8 +4,9 @@
  * same container reader (R/codec_exe.c:670-703 header, :751-815 frames), same options that matter for decoding, same frame loop
  * (error pattern file :397-399, delay compensation :230,:433-435, zero padding of a short tail :447-450) and the same WAV writer
  * conventions (R/tinywaveout_c.h: 44-byte header, 16 / 24 / 32 bit little-endian PCM), so its output files are byte-comparable
- * with `LC3plus -D ...` of the reference.  A file is ONE stream: it is pushed through lc3plus_dec_batch_decode() in runs of frames
- * of equal size so that the decoder memories stay on the GPU between the frames of a run.
+ * with `LC3plus -D ...` of the reference.  A file is ONE stream: it is pushed through lc3plus_dec_batch_decode_sizes() in blocks of
+ * up to 256 frames, each with its own size (bitrate switching, lost frames), so that the decoder memories stay on the GPU between the
+ * frames of a block.
  *
  *   lc3plus_dec_cli [-D] [-q] [-bps 16|24|32] [-dc 0|1|2] [-epf FILE] [-edf FILE] [-formatG192] [-cfgG192 FILE] in.lc3plus out.wav
  */
@@ -134,37 +135,32 @@ int main(int ac, char** av)
     FILE* fed = edf ? fopen(edf, "wb") : NULL;
     if (edf && !fed) die("Error creating error detection file!");
 
-    /* ---- decode in runs of equal frame size ---- */
+    /* ---- decode in blocks of frames, every frame with its own size ---- */
     lc3plus_dec_batch* b = NULL;
     err = lc3plus_dec_batch_create(&b, 1, rate, C, frame_ms, hrmode, NULL, -1);
     if (err) { fprintf(stderr, "lc3plus_dec_cli: cannot create the GPU decoder (LC3_Error %d)\n", (int)err); return 1; }
     const int CH = 256;
     uint8_t* in_buf = (uint8_t*)calloc((size_t)CH, LC3_MAX_BYTES);
     uint8_t* flags = (uint8_t*)malloc(CH); uint8_t* status = (uint8_t*)malloc(CH);
+    int* sizes = (int*)malloc(CH * sizeof(int));
     void* pcm = malloc((size_t)CH * C * N * 4);
     uint32_t data_bytes = 0, clipped = 0;
-    int cur = 0;                                                            /* bytes per frame the decoder is configured for */
     size_t f0 = 0;
     while (f0 < nf) {
-        /* R/dec_lc3_fl.c:140-155: a lost frame (bfi_ext = 1 or num_bytes = 0) keeps the configuration, a good one of another size changes it */
-        int lost0 = fr[f0].bfi == 1 || (fr[f0].bfi == 0 && fr[f0].nbytes == 0);
-        if (!lost0 && fr[f0].nbytes != cur) {
-            err = lc3plus_dec_batch_set_num_bytes(b, 0, fr[f0].nbytes);
-            if (err) { fprintf(stderr, "lc3plus_dec_cli: frame size %d rejected (LC3_Error %d)\n", fr[f0].nbytes, (int)err); return 1; }
-            cur = fr[f0].nbytes;
+        /* R/dec_lc3_fl.c:140-155 per frame: a lost frame (bfi_ext = 1 or num_bytes = 0) keeps the configuration, a good one of another size changes it */
+        const int T = nf - f0 < (size_t)CH ? (int)(nf - f0) : CH;
+        int stride = 1;
+        for (int t = 0; t < T; t++) if (fr[f0 + t].bfi != 1 && fr[f0 + t].nbytes > stride) stride = fr[f0 + t].nbytes;
+        for (int t = 0; t < T; t++) {
+            const frame_t* f = &fr[f0 + t];
+            const int lost = f->bfi == 1 || f->nbytes == 0;
+            memset(in_buf + (size_t)t * stride, 0, stride);
+            if (!lost) memcpy(in_buf + (size_t)t * stride, f->data, f->nbytes);
+            sizes[t] = lost ? 0 : f->nbytes;
+            flags[t] = (uint8_t)lost;                                       /* (bfi_ext 3 of a G.192 file decodes as a good frame in the float codec) */
         }
-        int T = 0;
-        const int stride = cur > 0 ? cur : 1;
-        while (T < CH && f0 + T < nf) {
-            const frame_t* f = &fr[f0 + T];
-            const int lost = f->bfi == 1 || (f->bfi == 0 && f->nbytes == 0);
-            if (!lost && f->nbytes != cur) break;
-            memset(in_buf + (size_t)T * stride, 0, stride);
-            if (!lost) memcpy(in_buf + (size_t)T * stride, f->data, f->nbytes);
-            flags[T] = lost ? 1 : (uint8_t)f->bfi;
-            T++;
-        }
-        err = lc3plus_dec_batch_decode(b, in_buf, 0, stride, flags, T, pcm, 0, bps, status, NULL, 1);
+        err = lc3plus_dec_batch_decode_sizes(b, in_buf, 0, stride, sizes, flags, T, pcm, 0, bps, status, NULL, 1);
+        if (err == LC3_NUMBYTES_ERROR) { fprintf(stderr, "lc3plus_dec_cli: frame size rejected (LC3_Error %d)\n", (int)err); return 1; }
         if (err) { fprintf(stderr, "lc3plus_dec_cli: decode failed (LC3_Error %d)\n", (int)err); return 1; }
         for (int t = 0; t < T; t++) {
             if (fed) { const int16_t e = status[t]; fwrite(&e, 2, 1, fed); }
@@ -200,6 +196,6 @@ int main(int ac, char** av)
     if (!quiet) { puts("\nProcessing done!"); printf("%u samples clipped!\n", clipped); }
     lc3plus_dec_batch_destroy(b);
     for (size_t k = 0; k < nf; k++) free(fr[k].data);
-    free(fr); free(in_buf); free(flags); free(status); free(pcm);
+    free(fr); free(in_buf); free(flags); free(status); free(sizes); free(pcm);
     return 0;
 }
