@@ -28,6 +28,7 @@ EXPORTS = [
     "lc3plus_dec_batch_create", "lc3plus_dec_batch_destroy", "lc3plus_dec_batch_output_samples", "lc3plus_dec_batch_delay",
     "lc3plus_dec_batch_num_bytes", "lc3plus_dec_batch_set_num_bytes", "lc3plus_dec_batch_decode",
     "lc3plus_dec_batch_last_kernel_ms", "lc3plus_dec_batch_set_input_ready", "lc3plus_dec_batch_decode_sizes",
+    "lc3plus_enc_batch_encode_bitrates",
 ]
 
 
@@ -56,6 +57,10 @@ def load_library():
         L.lc3plus_enc_batch_encode.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,
                                                C.c_void_p, C.c_int]
         L.lc3plus_enc_batch_encode_traced.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
+        L.lc3plus_enc_batch_encode_bitrates.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int,
+                                                        C.c_void_p, C.c_void_p, C.c_int]
+        L.lc3plus_enc_batch_encode_bitrates_traced.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
+        L.lc3plus_enc_plan_bitrates.argtypes = [C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         L.lc3plus_enc_batch_last_kernel_ms.restype = C.c_float
         L.lc3plus_enc_batch_last_kernel_ms.argtypes = [C.c_void_p]
         L.lc3plus_enc_batch_last_status.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
@@ -109,6 +114,8 @@ class Batch:
         if rc:
             raise LC3Error(rc, "lc3plus_enc_batch_create")
         self.n_streams, self.channels = n_streams, channels
+        self.samplerate, self.frame_ms, self.hrmode = samplerate, frame_ms, hrmode
+        self.last_num_bytes = None
         self.N = self.lib.lc3plus_enc_batch_input_samples(self.h)
 
     @property
@@ -124,10 +131,28 @@ class Batch:
     def set_bandwidth(self, stream, bw):
         return self.lib.lc3plus_enc_batch_set_bandwidth(self.h, stream, bw)
 
-    def encode(self, pcm, bitdepth=16):
-        """pcm: host array [n_streams, T, channels, N] (or [n_streams, T, N] for mono) -> uint8 [n_streams, T, stride]."""
+    def _bitrates(self, bitrates, T):
+        """int32 [n_streams, T] per-frame bitrates, and the host buffer their frame sizes come back in (last_num_bytes)."""
+        br = np.ascontiguousarray(np.broadcast_to(np.asarray(bitrates, dtype=np.int32), (self.n_streams, T)), dtype=np.int32)
+        self.last_num_bytes = np.zeros((self.n_streams, T), dtype=np.int32)
+        return br
+
+    def encode(self, pcm, bitdepth=16, bitrates=None):
+        """pcm: host array [n_streams, T, channels, N] (or [n_streams, T, N] for mono) -> uint8 [n_streams, T, stride].
+        bitrates: None, or [n_streams, T] total bitrate per stream-frame (lc3plus_enc_batch_encode_bitrates): the output is then
+        [n_streams, T, largest frame of the call] and last_num_bytes [n_streams, T] holds each frame's size."""
         pcm = np.ascontiguousarray(pcm)
         T = pcm.shape[1]
+        if bitrates is not None:
+            br = self._bitrates(bitrates, T)
+            nb = enc_plan_bitrates_for(self, br)
+            stride = max(int(nb.max()), 1)
+            out = np.zeros((self.n_streams, T, stride), dtype=np.uint8)
+            rc = self.lib.lc3plus_enc_batch_encode_bitrates(self.h, pcm.ctypes.data, 0, bitdepth, br.ctypes.data, T, out.ctypes.data, stride, 0,
+                                                            self.last_num_bytes.ctypes.data, None, 1)
+            if rc:
+                raise LC3Error(rc, "lc3plus_enc_batch_encode_bitrates")
+            return out
         stride = self.stride
         out = np.zeros((self.n_streams, T, stride), dtype=np.uint8)
         rc = self.lib.lc3plus_enc_batch_encode(self.h, pcm.ctypes.data, 0, bitdepth, T, out.ctypes.data, stride, 0, None, 1)
@@ -186,20 +211,39 @@ class Batch:
             raise LC3Error(1, "lc3plus_enc_batch_last_records (%d of %d words: T does not match the last call)" % (n, rec.size))
         return rec
 
-    def encode_traced(self, pcm, bitdepth=16):
+    def encode_traced(self, pcm, bitdepth=16, bitrates=None):
         pcm = np.ascontiguousarray(pcm)
         T = pcm.shape[1]
-        stride = self.stride
-        out = np.zeros((self.n_streams, T, stride), dtype=np.uint8)
         tsz = self.lib.lc3plus_trace_sizeof()
         traces = np.zeros((self.n_streams * self.channels * T, tsz), dtype=np.uint8)
+        if bitrates is not None:
+            br = self._bitrates(bitrates, T)
+            self.last_num_bytes[:] = enc_plan_bitrates_for(self, br)
+            stride = max(int(self.last_num_bytes.max()), 1)
+            out = np.zeros((self.n_streams, T, stride), dtype=np.uint8)
+            rc = self.lib.lc3plus_enc_batch_encode_bitrates_traced(self.h, pcm.ctypes.data, bitdepth, br.ctypes.data, T, out.ctypes.data, stride,
+                                                                   traces.ctypes.data)
+            if rc:
+                raise LC3Error(rc, "lc3plus_enc_batch_encode_bitrates_traced")
+            return out, traces
+        stride = self.stride
+        out = np.zeros((self.n_streams, T, stride), dtype=np.uint8)
         rc = self.lib.lc3plus_enc_batch_encode_traced(self.h, pcm.ctypes.data, bitdepth, T, out.ctypes.data, stride, traces.ctypes.data)
         if rc:
             raise LC3Error(rc, "lc3plus_enc_batch_encode_traced")
         return out, traces
 
-    def encode_device(self, d_pcm_ptr, bitdepth, T, d_out_ptr, out_stride, hip_stream=None, sync=False):
-        """Device-resident variant: raw device pointers (e.g. torch tensors' data_ptr())."""
+    def encode_device(self, d_pcm_ptr, bitdepth, T, d_out_ptr, out_stride, hip_stream=None, sync=False, bitrates=None):
+        """Device-resident variant: raw device pointers (e.g. torch tensors' data_ptr()).  bitrates: as for encode() (a host array;
+        last_num_bytes then holds the frame sizes)."""
+        if bitrates is not None:
+            br = self._bitrates(bitrates, T)
+            rc = self.lib.lc3plus_enc_batch_encode_bitrates(self.h, C.c_void_p(d_pcm_ptr), 1, bitdepth, br.ctypes.data, T, C.c_void_p(d_out_ptr),
+                                                            out_stride, 1, self.last_num_bytes.ctypes.data,
+                                                            C.c_void_p(hip_stream) if hip_stream else None, 1 if sync else 0)
+            if rc:
+                raise LC3Error(rc, "lc3plus_enc_batch_encode_bitrates(device)")
+            return
         rc = self.lib.lc3plus_enc_batch_encode(self.h, C.c_void_p(d_pcm_ptr), 1, bitdepth, T, C.c_void_p(d_out_ptr), out_stride, 1,
                                                C.c_void_p(hip_stream) if hip_stream else None, 1 if sync else 0)
         if rc:
@@ -218,6 +262,24 @@ class Batch:
             self.close()
         except Exception:
             pass
+
+
+def enc_plan_bitrates(samplerate, channels, frame_ms, hrmode, bitrates):
+    """The per-frame bitrate rule of Batch.encode(bitrates=...) on the host (test hook lc3plus_enc_plan_bitrates, no device needed):
+    bitrates [n_streams, n_frames] -> (num_bytes int32 [n_streams, n_frames], largest frame).  Raises LC3Error with the call's code."""
+    L = load_library()
+    br = np.ascontiguousarray(np.atleast_2d(np.asarray(bitrates)), dtype=np.int32)
+    S, T = br.shape
+    nb = np.zeros((S, T), dtype=np.int32)
+    mx = C.c_int(0)
+    rc = L.lc3plus_enc_plan_bitrates(samplerate, channels, frame_ms, hrmode, S, br.ctypes.data, T, nb.ctypes.data, C.byref(mx))
+    if rc:
+        raise LC3Error(rc, "lc3plus_enc_plan_bitrates")
+    return nb, mx.value
+
+
+def enc_plan_bitrates_for(batch, bitrates):
+    return enc_plan_bitrates(batch.samplerate, batch.channels, batch.frame_ms, batch.hrmode, bitrates)[0]
 
 
 class Encoder:

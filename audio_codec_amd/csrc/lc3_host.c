@@ -74,8 +74,8 @@ static void geom_update(geom_t* g) { geom_update_ex(g, 0); }              /* R/s
 static int fft_supported(int len);
 static int geom_supported(const geom_t* g) { return g->tab && g->N <= LC3D_MAX_N && fft_supported(g->N / 2) && g->N - g->la <= LC3D_MEMCAP_BIG; }
 
-/* R/setup_enc_lc3.c:196-375: bitrate -> per-channel budgets.  Returns an LC3_Error. */
-static LC3_Error derive_bitrate(const geom_t* g, int bitrate, lc3d_chan* ch /* [channels] */)
+/* R/setup_enc_lc3.c:196-230: the bitrate limits of the geometry (all channels).  Returns an LC3_Error. */
+static LC3_Error bitrate_limits(const geom_t* g, int* lo, int* hi)
 {
     int minBR = 0, maxBR = 0;
     if (g->hrmode) {
@@ -91,39 +91,80 @@ static LC3_Error derive_bitrate(const geom_t* g, int bitrate, lc3d_chan* ch /* [
         maxBR = 400 * 8 * (1000 / g->frame_ms) * (g->fs_in == 44100 ? 441. / 480 : 1);
     }
     minBR *= g->channels; maxBR *= g->channels;
+    *lo = minBR; *hi = maxBR;
+    return LC3_OK;
+}
+/* R/setup_enc_lc3.c:231-375 for one channel of nbytes bytes: everything a bitrate sets is a function of the channel's byte count and the geometry */
+static void derive_chan(const geom_t* g, int nbytes, lc3d_chan* s)
+{
+    s->nbytes = nbytes;
+    s->total_bits = s->nbytes << 3;
+    s->target_bits_init = s->total_bits - 38 - 8 - 3 - g->bw_bits - (int)ceil(log2f(g->N / 2)) - 2 - 1;
+    if (s->total_bits > 1280) s->target_bits_init -= 1;
+    if (s->total_bits > 2560) s->target_bits_init -= 1;
+    if (g->hrmode) s->target_bits_init -= 1;
+    s->lpc_weighting = s->total_bits < 480;
+    if (g->frame_ms == 5) s->lpc_weighting = s->total_bits < 240;
+    if (g->frame_ms == 2.5) s->lpc_weighting = s->total_bits < 120;
+    s->gg_off = -(IMIN(115, s->total_bits / (10 * (g->fs_idx + 1))) + 105 + 5 * (g->fs_idx + 1));
+    if (g->frame_ms == 10 && ((g->fs_in >= 44100 && s->nbytes >= 100) || (g->fs_in == 32000 && s->nbytes >= 81)) &&
+        s->nbytes < 340 && g->hrmode == 0) s->attack_handling = 1;
+    else { s->attack_handling = 0; s->reset_attack = 1; }
+    int bitsTmp = s->total_bits;
+    if (g->frame_ms == 2.5) bitsTmp = bitsTmp * 4.0 * (1.0 - 0.4);
+    if (g->frame_ms == 5) bitsTmp = bitsTmp * 2 - 160;
+    s->ltpf_enable = bitsTmp < 640 + (g->fs_idx - 1) * 80;
+    if (g->hrmode) s->ltpf_enable = 0;
+    if (g->hrmode && g->fs_idx >= 4) {
+        int real_rate = s->nbytes * 8000 / g->frame_ms;
+        s->reg_bits = real_rate / 12500;
+        if (g->fs_idx == 5) { if (g->frame_ms == 10) s->reg_bits += 2; if (g->frame_ms == 2.5) s->reg_bits -= 6; }
+        else { if (g->frame_ms == 2.5) s->reg_bits -= 6; if (g->frame_ms == 10) s->reg_bits += 5; }
+    } else s->reg_bits = -1;
+}
+/* R/setup_enc_lc3.c:196-375: bitrate -> per-channel budgets.  Returns an LC3_Error. */
+static LC3_Error derive_bitrate(const geom_t* g, int bitrate, lc3d_chan* ch /* [channels] */)
+{
+    int minBR = 0, maxBR = 0;
+    LC3_Error e = bitrate_limits(g, &minBR, &maxBR);
+    if (e) return e;
     if (bitrate < minBR || bitrate > maxBR) return LC3_BITRATE_ERROR;
     const int totalBytes = bitrate * g->N / (8 * g->fs_in);
     int off = 0;
     for (int c = 0; c < g->channels; c++) {
-        lc3d_chan* s = &ch[c];
-        const int was_attack = s->attack_handling;
-        s->nbytes = totalBytes / g->channels + (c < (totalBytes % g->channels));
-        s->out_off = off; off += s->nbytes;
-        s->total_bits = s->nbytes << 3;
-        s->target_bits_init = s->total_bits - 38 - 8 - 3 - g->bw_bits - (int)ceil(log2f(g->N / 2)) - 2 - 1;
-        if (s->total_bits > 1280) s->target_bits_init -= 1;
-        if (s->total_bits > 2560) s->target_bits_init -= 1;
-        if (g->hrmode) s->target_bits_init -= 1;
-        s->lpc_weighting = s->total_bits < 480;
-        if (g->frame_ms == 5) s->lpc_weighting = s->total_bits < 240;
-        if (g->frame_ms == 2.5) s->lpc_weighting = s->total_bits < 120;
-        s->gg_off = -(IMIN(115, s->total_bits / (10 * (g->fs_idx + 1))) + 105 + 5 * (g->fs_idx + 1));
-        if (g->frame_ms == 10 && ((g->fs_in >= 44100 && s->nbytes >= 100) || (g->fs_in == 32000 && s->nbytes >= 81)) &&
-            s->nbytes < 340 && g->hrmode == 0) s->attack_handling = 1;
-        else { s->attack_handling = 0; s->reset_attack = 1; }
-        (void)was_attack;
-        int bitsTmp = s->total_bits;
-        if (g->frame_ms == 2.5) bitsTmp = bitsTmp * 4.0 * (1.0 - 0.4);
-        if (g->frame_ms == 5) bitsTmp = bitsTmp * 2 - 160;
-        s->ltpf_enable = bitsTmp < 640 + (g->fs_idx - 1) * 80;
-        if (g->hrmode) s->ltpf_enable = 0;
-        if (g->hrmode && g->fs_idx >= 4) {
-            int real_rate = s->nbytes * 8000 / g->frame_ms;
-            s->reg_bits = real_rate / 12500;
-            if (g->fs_idx == 5) { if (g->frame_ms == 10) s->reg_bits += 2; if (g->frame_ms == 2.5) s->reg_bits -= 6; }
-            else { if (g->frame_ms == 2.5) s->reg_bits -= 6; if (g->frame_ms == 10) s->reg_bits += 5; }
-        } else s->reg_bits = -1;
+        derive_chan(g, totalBytes / g->channels + (c < (totalBytes % g->channels)), &ch[c]);
+        ch[c].out_off = off; off += ch[c].nbytes;
     }
+    return LC3_OK;
+}
+
+/* per-frame bitrates: the configuration of every channel byte count 0 .. max, from derive_chan (entry 0 zeroed; out_off and the bandwidth words are
+ * not used from it: the kernel takes the channel's offset from the stream-frame size and the bandwidth from the stream) */
+static int enc_max_chan_bytes(const geom_t* g) { return g->hrmode ? (g->dms == 25 ? 210 : g->dms == 50 ? 375 : 625) : 400; }
+static lc3d_chan* enc_build_table(const geom_t* g, int* n)
+{
+    *n = enc_max_chan_bytes(g) + 1;
+    lc3d_chan* tab = (lc3d_chan*)calloc((size_t)*n, sizeof(lc3d_chan));
+    if (!tab) return NULL;
+    for (int k = 1; k < *n; k++) derive_chan(g, k, &tab[k]);
+    return tab;
+}
+/* The per-frame bitrate rule of lc3plus_enc_batch_encode_bitrates: every rate is checked with the limits of derive_bitrate before anything is written, and
+ * gives the stream-frame's byte count as derive_bitrate computes it.  Out: fsz [n] (n = stream-frames), *max_bytes the largest. */
+static LC3_Error enc_plan_bitrates(const geom_t* g, const int* bitrates, size_t n, uint16_t* fsz, int* max_bytes)
+{
+    int lo = 0, hi = 0, mx = 0;
+    LC3_Error e = bitrate_limits(g, &lo, &hi);
+    if (e) return e;
+    for (size_t i = 0; i < n; i++) {
+        const int br = bitrates[i];
+        if (br <= 0 || br < lo || br > hi) return LC3_BITRATE_ERROR;
+        const int tb = br * g->N / (8 * g->fs_in);
+        if (tb / g->channels < 1 || (tb + g->channels - 1) / g->channels > enc_max_chan_bytes(g)) return LC3_BITRATE_ERROR;   /* inside the table (always, by the limits) */
+        fsz[i] = (uint16_t)tb;
+        if (tb > mx) mx = tb;
+    }
+    *max_bytes = mx;
     return LC3_OK;
 }
 
@@ -265,6 +306,7 @@ struct lc3plus_batch {
     lc3d_chan* chans;               /* [n_streams * channels] host mirror */
     int* bitrates;
     void* dev;
+    uint16_t* fsz; size_t fsz_cap;  /* per-frame bitrates: stream-frame sizes of enc_plan_bitrates, grown as needed */
 };
 
 static LC3_Error batch_upload(lc3plus_batch* b, int first_stream, int count)
@@ -319,6 +361,7 @@ LC3_Error lc3plus_enc_batch_create(lc3plus_batch** out, int n_streams, int sampl
     free(plan);
     if (!rc) rc = lc3hip_reset_state(b->dev, st);
     if (!rc) rc = batch_upload(b, 0, n_streams) != LC3_OK;
+    if (!rc) { int tab_n = 0; lc3d_chan* tab = enc_build_table(&b->g, &tab_n); rc = !tab || lc3hip_upload_enc_table(b->dev, tab, tab_n); free(tab); }
     if (rc) { if (b->dev) lc3hip_destroy(b->dev); free(b->chans); free(b->bitrates); free(b); return LC3_ERROR; }
     *out = b;
     return LC3_OK;
@@ -328,7 +371,7 @@ LC3_Error lc3plus_enc_batch_destroy(lc3plus_batch* b)
 {
     if (!b) return LC3_NULL_ERROR;
     lc3hip_destroy(b->dev);
-    free(b->chans); free(b->bitrates); free(b);
+    free(b->chans); free(b->bitrates); free(b->fsz); free(b);
     return LC3_OK;
 }
 
@@ -384,7 +427,7 @@ static LC3_Error batch_encode(lc3plus_batch* b, const void* pcm, int pcm_on_devi
     if (!b || !pcm || !out) return LC3_NULL_ERROR;
     if (bitdepth != 16 && bitdepth != 24 && bitdepth != 32) return LC3_ERROR;
     if (n_frames <= 0 || out_stride < b->stride) return LC3_ERROR;
-    if (lc3hip_encode(b->dev, pcm, pcm_on_device, bitdepth, n_frames, out, out_stride, out_on_device, hip_stream, sync, trace)) return LC3_ERROR;
+    if (lc3hip_encode(b->dev, pcm, pcm_on_device, bitdepth, n_frames, out, out_stride, out_on_device, hip_stream, sync, trace, NULL)) return LC3_ERROR;
     /* one-shot attack-state reset requests have been consumed by this launch */
     int dirty = 0;
     for (int i = 0; i < b->n_streams * b->g.channels; i++) if (b->chans[i].reset_attack) { b->chans[i].reset_attack = 0; dirty = 1; }
@@ -396,6 +439,77 @@ LC3_Error lc3plus_enc_batch_encode(lc3plus_batch* b, const void* pcm, int pcm_on
                                    int out_stride, int out_on_device, void* hip_stream, int sync)
 {
     return batch_encode(b, pcm, pcm_on_device, bitdepth, n_frames, out, out_stride, out_on_device, hip_stream, sync, NULL);
+}
+
+static LC3_Error batch_encode_bitrates(lc3plus_batch* b, const void* pcm, int pcm_on_device, int bitdepth, const int* bitrates, int n_frames, void* out,
+                                       int out_stride, int out_on_device, int* num_bytes, void* hip_stream, int sync, void* trace)
+{
+    if (!b || !pcm || !out || !bitrates) return LC3_NULL_ERROR;
+    if (bitdepth != 16 && bitdepth != 24 && bitdepth != 32) return LC3_ERROR;
+    if (n_frames <= 0) return LC3_ERROR;
+    const size_t n = (size_t)b->n_streams * n_frames;
+    if (b->fsz_cap < n) {
+        free(b->fsz); b->fsz_cap = 0;
+        b->fsz = (uint16_t*)malloc(n * sizeof(uint16_t));
+        if (!b->fsz) return LC3_ERROR;
+        b->fsz_cap = n;
+    }
+    int max_bytes = 0;
+    LC3_Error e = enc_plan_bitrates(&b->g, bitrates, n, b->fsz, &max_bytes);
+    if (e) return e;
+    if (out_stride < max_bytes) return LC3_ERROR;
+    if (lc3hip_encode(b->dev, pcm, pcm_on_device, bitdepth, n_frames, out, out_stride, out_on_device, hip_stream, sync, trace, b->fsz)) return LC3_ERROR;
+    if (num_bytes) for (size_t i = 0; i < n; i++) num_bytes[i] = b->fsz[i];
+    /* every stream is configured with its last frame's rate; the kernel has done every attack-detector reset the call asked for, and the one-shot
+     * requests pending from set_bitrate before it */
+    int dirty = 0;
+    for (int i = 0; i < b->n_streams; i++) {
+        lc3d_chan* ch = b->chans + (size_t)i * b->g.channels;
+        const int br = bitrates[(size_t)i * n_frames + n_frames - 1];
+        for (int c = 0; c < b->g.channels; c++) if (ch[c].reset_attack) { ch[c].reset_attack = 0; dirty = 1; }
+        if (br == b->bitrates[i]) continue;
+        if (derive_bitrate(&b->g, br, ch) != LC3_OK) return LC3_ERROR;          /* checked by enc_plan_bitrates */
+        for (int c = 0; c < b->g.channels; c++) ch[c].reset_attack = 0;
+        b->bitrates[i] = br; dirty = 1;
+    }
+    if (!dirty) return LC3_OK;
+    batch_restride(b);
+    /* on the call's stream behind its kernels: the call does not wait for them (sync = 0) */
+    return lc3hip_upload_chans_async(b->dev, b->chans, 0, b->n_streams * b->g.channels, hip_stream) ? LC3_ERROR : LC3_OK;
+}
+LC3_Error lc3plus_enc_batch_encode_bitrates(lc3plus_batch* b, const void* pcm, int pcm_on_device, int bitdepth, const int* bitrates, int n_frames, void* out,
+                                            int out_stride, int out_on_device, int* num_bytes, void* hip_stream, int sync)
+{
+    return batch_encode_bitrates(b, pcm, pcm_on_device, bitdepth, bitrates, n_frames, out, out_stride, out_on_device, num_bytes, hip_stream, sync, NULL);
+}
+/* debug entry point used by tests: encode_bitrates with host pointers and one lc3d_trace per channel-frame */
+LC3_Error lc3plus_enc_batch_encode_bitrates_traced(lc3plus_batch* b, const void* pcm, int bitdepth, const int* bitrates, int n_frames, void* out, int out_stride,
+                                                   void* traces)
+{
+    if (!traces) return LC3_NULL_ERROR;
+    return batch_encode_bitrates(b, pcm, 0, bitdepth, bitrates, n_frames, out, out_stride, 0, NULL, NULL, 1, traces);
+}
+/* test hook: the per-frame bitrate rule for a geometry, without a device.  num_bytes [n_streams * n_frames] out, *max_bytes the largest */
+LC3_Error lc3plus_enc_plan_bitrates(int samplerate, int channels, float frame_ms, int hrmode, int n_streams, const int* bitrates, int n_frames,
+                                    int* num_bytes, int* max_bytes)
+{
+    if (!bitrates || !num_bytes || !max_bytes) return LC3_NULL_ERROR;
+    if (n_streams <= 0 || n_frames <= 0) return LC3_ERROR;
+    if (!samplerate_ok(samplerate)) return LC3_SAMPLERATE_ERROR;
+    if (channels < 1 || channels > MAX_CH) return LC3_CHANNELS_ERROR;
+    { int d = (int)ceil(frame_ms * 10); if (d != 25 && d != 50 && d != 100) return LC3_FRAMEMS_ERROR; }
+    if (samplerate < 48000 && hrmode != 0) return LC3_SAMPLERATE_ERROR;
+    geom_t g;
+    geom_init(&g, samplerate, channels);
+    g.dms = (int)(frame_ms * 10); g.frame_ms = frame_ms; g.hrmode = hrmode > 0;
+    geom_update(&g);
+    const size_t n = (size_t)n_streams * n_frames;
+    uint16_t* fsz = (uint16_t*)malloc(n * sizeof(uint16_t));
+    if (!fsz) return LC3_ERROR;
+    LC3_Error e = enc_plan_bitrates(&g, bitrates, n, fsz, max_bytes);
+    if (!e) for (size_t i = 0; i < n; i++) num_bytes[i] = fsz[i];
+    free(fsz);
+    return e;
 }
 
 /* debug / stage-parity entry point used by tests: additionally returns one lc3d_trace per channel-frame */

@@ -40,13 +40,21 @@
 #define MAXN 960
 #define MEMCAP LC3D_MEMCAP_BIG
 #define SMW 1088                /* sm[]: holds the resampler's scaled input (120 + 960 samples) */
+#ifdef LC3_ENC_VAR
+#define KERNEL_NAME lc3_encode_kernel_big_var
+#else
 #define KERNEL_NAME lc3_encode_kernel_big
+#endif
 #define KERNEL_WAVES 2
 #else
 #define MAXN 480
 #define MEMCAP LC3D_MEMCAP_STD  /* MDCT overlap memory: N - la_zeros <= 300 for every N <= 480 except 96 kHz / 5 ms */
 #define SMW 548
+#ifdef LC3_ENC_VAR
+#define KERNEL_NAME lc3_encode_kernel_var
+#else
 #define KERNEL_NAME lc3_encode_kernel
+#endif
 #ifndef KERNEL_WAVES
 #define KERNEL_WAVES 4
 #endif
@@ -2641,6 +2649,11 @@ template <class LdsT> STAGE void st_bitstream(const lc3d_plan* __restrict__ P, c
 /* ------------------------------------------------------------------------------------------------ */
 /* the kernel: one wave per channel-stream, frames in time order  (frame driver R/enc_lc3_fl.c:13-160) */
 /* ------------------------------------------------------------------------------------------------ */
+/* -DLC3_ENC_VAR: per-frame bitrates (lc3plus_enc_batch_encode_bitrates), kernel lc3_encode_kernel_var (_big_var) in an object of its own, so that the
+ * fixed-rate kernel stays the code it is.  Per frame the wave reloads the rate-derived words of its configuration from etab, the configuration per channel
+ * byte count, at the channel's share of fsz[stream][dt0 + t] (the stream-frame's bytes, split over the channels as derive_bitrate does); the bandwidth
+ * words stay the stream's (chans).  A frame whose rate disables attack handling clears the detector first (R/setup_enc_lc3.c:297-308).  The in-kernel
+ * writer then addresses the output by the call's frames: [stream][dT][out_stride], frame dt0 + t. */
 extern "C" __global__ void __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(KERNEL_WAVES, KERNEL_WAVES)))
 KERNEL_NAME(const lc3d_plan* __restrict__ P, const lc3d_chan* __restrict__ chans, float* __restrict__ state,
                   const void* __restrict__ pcm, int bitdepth, int T, uint8_t* __restrict__ out, int out_stride, int ncs,
@@ -2650,7 +2663,11 @@ KERNEL_NAME(const lc3d_plan* __restrict__ P, const lc3d_chan* __restrict__ chans
                   int dT, int dt0 /* the hand-over and the status rows hold dT frames per channel-stream; this launch's frame t is their frame dt0 + t */,
                   const float* __restrict__ spec /* [cs][T][N] MDCT spectra from lc3_enc_front_kernel, or null: transform here */,
                   const float* __restrict__ frec /* [cs][T][FR_WORDS] with the SNS result of lc3_enc_snsvq_kernel */,
-                  const float* __restrict__ xnext /* [cs][MEMCAP] MDCT memory after the last frame */)
+                  const float* __restrict__ xnext /* [cs][MEMCAP] MDCT memory after the last frame */
+#ifdef LC3_ENC_VAR
+                  , const uint16_t* __restrict__ fsz /* [stream][dT] bytes of each stream-frame */, const lc3d_chan* __restrict__ etab /* per channel byte count */
+#endif
+                  )
 {
     __shared__ WaveLds L;
     const int lane = threadIdx.x;
@@ -2704,6 +2721,17 @@ KERNEL_NAME(const lc3d_plan* __restrict__ P, const lc3d_chan* __restrict__ chans
         lc3d_trace* tr = nullptr;
 #else
         lc3d_trace* tr = trace ? &trace[(size_t)cs * T + t] : nullptr;
+#endif
+#ifdef LC3_ENC_VAR
+        {                                                /* this frame's configuration (the words before out_off) and the channel's payload offset */
+            const int fb = fsz[(size_t)strm * dT + dt0 + t];
+            const int k = channels == 1 ? fb : ch ? fb >> 1 : (fb + 1) >> 1;
+            if (lane < 8) L.cc[lane] = ((const int*)&etab[k])[lane];
+            if (lane == 8) L.cc[lane] = ch ? (fb + 1) >> 1 : 0;
+            LSYNC();
+            if (!CI(attack_handling) && lane == 0) { L.fsc[F_ATT_M0] = 0; L.fsc[F_ATT_M1] = 0; L.fsc[F_ATT_ACC] = 0; L.isc[I_ATT_POS] = 0; L.isc[I_ATT_FLAG] = 0; }
+            LSYNC();
+        }
 #endif
         /* ---- PCM in (R/enc_lc3_fl.c:30-42) ---- */
         const size_t fidx = ((size_t)strm * T + t) * channels + ch;
@@ -2863,7 +2891,11 @@ KERNEL_NAME(const lc3d_plan* __restrict__ P, const lc3d_chan* __restrict__ chans
         TICK(16);
         if (tr && lane == 0) { tr->n_res_bits = L.isc[I_NRES]; tr->bp_side = L.isc[I_BP_SIDE]; tr->mask_side = L.isc[I_MASK_SIDE]; }
         /* ---- bytes out ---- */
+#ifdef LC3_ENC_VAR
+        uint8_t* o = out + ((size_t)strm * dT + dt0 + t) * out_stride + CI(out_off);
+#else
         uint8_t* o = out + ((size_t)strm * T + t) * out_stride + CI(out_off);
+#endif
         const int nby = CI(nbytes);
         if (((nby | (int)(size_t)o) & 3) == 0) { for (int i = lane; i < (nby >> 2); i += WAVE) ((uint32_t*)o)[i] = ((const uint32_t*)BYTES(L))[i]; }
         else for (int i = lane; i < nby; i += WAVE) o[i] = BYTES(L)[i];
@@ -2882,6 +2914,7 @@ KERNEL_NAME(const lc3d_plan* __restrict__ P, const lc3d_chan* __restrict__ chans
     if (lane < 16 && !(spec && (lane == I_ATT_POS || lane == I_ATT_FLAG))) ((int*)stp)[LC3D_ST_SCAL(MEMCAP) + 16 + lane] = L.isc[lane];
     (void)ml;
 }
+#ifndef LC3_ENC_VAR             /* the per-frame-bitrate objects hold only that kernel */
 
 /* ------------------------------------------------------------------------------------------------ */
 /* C-ABI device shim (lc3_shim.h): context, uploads, launch                                          */
@@ -2903,6 +2936,16 @@ extern "C" __global__ void lc3_encode_kernel_big(const lc3d_plan* __restrict__ P
                                                  lc3d_trace* __restrict__ trace, int* __restrict__ dump, int dstride, const float* __restrict__ y12,
                                                  uint8_t* __restrict__ status, int dT, int dt0, const float* __restrict__ spec, const float* __restrict__ frec,
                                                  const float* __restrict__ xnext);
+extern "C" __global__ void lc3_encode_kernel_var(const lc3d_plan* __restrict__ P, const lc3d_chan* __restrict__ chans, float* __restrict__ state,
+                                                 const void* __restrict__ pcm, int bitdepth, int T, uint8_t* __restrict__ out, int out_stride, int ncs,
+                                                 lc3d_trace* __restrict__ trace, int* __restrict__ dump, int dstride, const float* __restrict__ y12,
+                                                 uint8_t* __restrict__ status, int dT, int dt0, const float* __restrict__ spec, const float* __restrict__ frec,
+                                                 const float* __restrict__ xnext, const uint16_t* __restrict__ fsz, const lc3d_chan* __restrict__ etab);
+extern "C" __global__ void lc3_encode_kernel_big_var(const lc3d_plan* __restrict__ P, const lc3d_chan* __restrict__ chans, float* __restrict__ state,
+                                                     const void* __restrict__ pcm, int bitdepth, int T, uint8_t* __restrict__ out, int out_stride, int ncs,
+                                                     lc3d_trace* __restrict__ trace, int* __restrict__ dump, int dstride, const float* __restrict__ y12,
+                                                     uint8_t* __restrict__ status, int dT, int dt0, const float* __restrict__ spec, const float* __restrict__ frec,
+                                                     const float* __restrict__ xnext, const uint16_t* __restrict__ fsz, const lc3d_chan* __restrict__ etab);
 extern "C" __global__ void lc3_enc_front_kernel_big(const lc3d_plan* __restrict__ P, const lc3d_chan* __restrict__ chans, const float* __restrict__ state, const void* __restrict__ pcm,
                                                     int bitdepth, int T, int tb, int nt, int fpw, int ncs, float* __restrict__ spec, int srow, int RT, int r0, float* __restrict__ rec, float* __restrict__ xnext, const float* __restrict__ xprev, int xprev_stride, int do_scf);
 extern "C" __global__ void lc3_enc_shape_kernel_big(const lc3d_plan* __restrict__ P, const lc3d_chan* __restrict__ chans, int T, int tb, int nt, int fpw, int ncs,
@@ -2985,6 +3028,12 @@ struct lc3hip_ctx {
     int ylen, srow, la, len12, fm_frames; const float* last_frec; int last_frec_frames;      /* the records of the last pipelined call (lc3hip_last_records) */
     hipStream_t stream, last_stream; hipEvent_t ev0, ev1; float last_ms;
     hipEvent_t ev_ours, ev_now; int ours_armed;       /* LC3PLUS_CHECK_READY: the tail of the library's own work on the caller's stream */
+    /* per-frame bitrates: the configuration per channel byte count (lc3hip_upload_enc_table), and per call the stream-frame sizes, through pinned
+     * staging, in LC3D_SETS rotating buffers (a buffer is written again once the call that read it has finished: calls with sync = 0) */
+    lc3d_chan* d_etab; uint16_t* d_fsz[LC3D_SETS]; uint16_t* h_fsz[LC3D_SETS]; size_t fsz_cap; hipEvent_t ev_fsz[LC3D_SETS]; int fsz_armed[LC3D_SETS], fsz_set;
+    /* lc3hip_upload_chans_async: the configuration a per-frame-bitrate call leaves, queued on its stream behind its kernels from pinned staging; every later
+     * call waits for the copy (ev_chans) on its own stream */
+    lc3d_chan* h_chans; hipEvent_t ev_chans; int chans_armed;
 };
 
 #define LC3D_FUSED_MAX_T 8
@@ -3061,6 +3110,23 @@ extern "C" int lc3hip_reset_state(void* ctx, const float* init_state_one /* LC3D
     return 0;
 }
 
+static int chans_host_side(lc3hip_ctx* c, const lc3d_chan* chans, int first, int count);
+extern "C" int lc3hip_upload_chans_async(void* ctx, const lc3d_chan* chans, int first, int count, void* hip_stream)
+{
+    lc3hip_ctx* c = (lc3hip_ctx*)ctx;
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : c->stream;
+    if (!c->h_chans) {
+        HIPCHK(hipHostMalloc((void**)&c->h_chans, sizeof(lc3d_chan) * (size_t)c->ncs, hipHostMallocDefault));
+        HIPCHK(hipEventCreateWithFlags(&c->ev_chans, hipEventDisableTiming));
+    }
+    if (c->chans_armed) HIPCHK(hipEventSynchronize(c->ev_chans));      /* the staging of the previous copy is free */
+    memcpy(c->h_chans + first, chans, sizeof(lc3d_chan) * (size_t)count);
+    HIPCHK(hipMemcpyAsync(c->d_chans + first, c->h_chans + first, sizeof(lc3d_chan) * (size_t)count, hipMemcpyHostToDevice, s));
+    HIPCHK(hipEventRecord(c->ev_chans, s)); c->chans_armed = 1;
+    if (c->opt.check_ready && c->ev_ours) { HIPCHK(hipEventRecord(c->ev_ours, s)); c->ours_armed = 1; }      /* the copy is the library's own work */
+    return chans_host_side(c, chans, first, count);
+}
 extern "C" int lc3hip_upload_chans(void* ctx, const lc3d_chan* chans, int first, int count)
 {
     lc3hip_ctx* c = (lc3hip_ctx*)ctx;
@@ -3068,7 +3134,13 @@ extern "C" int lc3hip_upload_chans(void* ctx, const lc3d_chan* chans, int first,
     /* a launch with sync = 0 may still be reading d_chans, possibly on a caller's non-blocking stream that a plain hipMemcpy does not
      * wait for: drain the stream the last launch went to first */
     if (c->last_stream) { HIPCHK(hipStreamSynchronize(c->last_stream)); c->last_stream = nullptr; }
+    if (c->chans_armed) HIPCHK(hipEventSynchronize(c->ev_chans));      /* a queued copy of lc3hip_upload_chans_async lands first */
     HIPCHK(hipMemcpy(c->d_chans + first, chans, sizeof(lc3d_chan) * count, hipMemcpyHostToDevice));
+    return chans_host_side(c, chans, first, count);
+}
+/* what the launch decisions read of the configuration, on the host */
+static int chans_host_side(lc3hip_ctx* c, const lc3d_chan* chans, int first, int count)
+{
     /* streams with attack handling need lc3_enc_attack_kernel between the front and the quantiser */
     if (!c->h_attack) { c->h_attack = (uint8_t*)calloc((size_t)c->ncs, 1); if (!c->h_attack) return 1; }
     for (int i = 0; i < count; i++) c->h_attack[first + i] = chans[i].attack_handling != 0 || chans[i].reset_attack != 0;   /* a pending reset needs the kernel too */
@@ -3109,7 +3181,7 @@ static void launch_resample(lc3hip_ctx* c, hipStream_t st, const void* dpcm, int
         hipLaunchKernelGGL(lc3_enc_resample_kernel, dim3((unsigned)c->ncs * pruns), dim3(WAVE), 0, st, c->d_plan, c->d_state, c->state_words, mc, dpcm, bitdepth, n_frames, hb, hn, c->ncs, dy12, xprev, xprev_stride);
 }
 static int enc_launch(lc3hip_ctx* c, const void* dpcm, int bitdepth, int n_frames, uint8_t* dout, int out_stride, hipStream_t s, lc3d_trace* dtr,
-                      int dT, int dt0, bool pack)
+                      int dT, int dt0, bool pack, const uint16_t* dfsz /* per-frame bitrates: [stream][dT] stream-frame bytes, or null */)
 {
     /* two kernels: lc3_encode_kernel (one wave per channel-stream, frames in order) leaves each frame's parameters and quantised
      * spectrum in a record; lc3_enc_pack_kernel (one channel-frame per lane, any frame size) writes the bytes.  With stage traces,
@@ -3122,7 +3194,8 @@ static int enc_launch(lc3hip_ctx* c, const void* dpcm, int bitdepth, int n_frame
     /* with the input-ready promise consecutive short calls overlap on the pipelined path, which then wins from 4 frames per call
      * (4096 streams, Mframes/s pipelined / in-kernel writer: 3 frames 31.9 / 36.3, 4: 39.8 / 38.0, 6: 48.6 / 40.2, 8: 53.9 / 41.2; without the
      * promise 8: 40.2 / 41.2) */
-    const bool in_kernel_writer = dtr || c->fused || dT <= (c->input_ready ? LC3D_FUSED_MAX_T_READY : LC3D_FUSED_MAX_T);
+    /* (per-frame bitrates: always - lc3_encode_kernel_var reloads the configuration per frame; it is the only kernel that does) */
+    const bool in_kernel_writer = dtr || c->fused || dfsz || dT <= (c->input_ready ? LC3D_FUSED_MAX_T_READY : LC3D_FUSED_MAX_T);
     if (!in_kernel_writer) {
         dstride = PK_STRIDE(c->N, c->hr);
         const size_t need = (size_t)c->ncs * dT * dstride;
@@ -3160,7 +3233,13 @@ static int enc_launch(lc3hip_ctx* c, const void* dpcm, int bitdepth, int n_frame
             hipLaunchKernelGGL(lc3_enc_hp50_kernel, dim3((unsigned)((c->ncs + WAVE - 1) / WAVE)), dim3(WAVE), 0, s, c->d_plan, c->d_state, c->state_words, LC3D_ST_SCAL(mc), n_frames, 0, n_frames, c->ncs, dy12);
             HIPCHK(hipGetLastError());
         }
-        if (c->big) hipLaunchKernelGGL(lc3_encode_kernel_big, dim3(c->ncs), dim3(WAVE), 0, s, c->d_plan, c->d_chans, c->d_state, dpcm, bitdepth, n_frames,
+        if (dfsz && c->big) hipLaunchKernelGGL(lc3_encode_kernel_big_var, dim3(c->ncs), dim3(WAVE), 0, s, c->d_plan, c->d_chans, c->d_state, dpcm, bitdepth, n_frames,
+                                               dout, out_stride, c->ncs, dtr, ddump, dstride, dy12, c->d_status, dT, dt0, (const float*)nullptr, (const float*)nullptr,
+                                               (const float*)nullptr, dfsz, (const lc3d_chan*)c->d_etab);
+        else if (dfsz) hipLaunchKernelGGL(lc3_encode_kernel_var, dim3(c->ncs), dim3(WAVE), 0, s, c->d_plan, c->d_chans, c->d_state, dpcm, bitdepth, n_frames,
+                                          dout, out_stride, c->ncs, dtr, ddump, dstride, dy12, c->d_status, dT, dt0, (const float*)nullptr, (const float*)nullptr,
+                                          (const float*)nullptr, dfsz, (const lc3d_chan*)c->d_etab);
+        else if (c->big) hipLaunchKernelGGL(lc3_encode_kernel_big, dim3(c->ncs), dim3(WAVE), 0, s, c->d_plan, c->d_chans, c->d_state, dpcm, bitdepth, n_frames,
                                        dout, out_stride, c->ncs, dtr, ddump, dstride, dy12, c->d_status, dT, dt0, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr);
         else hipLaunchKernelGGL(lc3_encode_kernel, dim3(c->ncs), dim3(WAVE), 0, s, c->d_plan, c->d_chans, c->d_state, dpcm, bitdepth, n_frames,
                                 dout, out_stride, c->ncs, dtr, ddump, dstride, dy12, c->d_status, dT, dt0, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr);
@@ -3394,14 +3473,14 @@ static bool host_ptr_is_pinned(const void* p)
  * overlaps with the GPU work of the previous run.  The bitstream writer runs ONCE behind the last run over all frames of the call (one
  * frame per lane makes it latency bound: per run it would cost as much as for the whole call), then the frames come down in one
  * linear copy.  State stays on the device between runs.  The first run is short so that the kernels start early. */
-static int encode_host(lc3hip_ctx* c, const void* pcm, int bitdepth, int n_frames, void* out, int out_stride, hipStream_t s)
+static int encode_host(lc3hip_ctx* c, const void* pcm, int bitdepth, int n_frames, void* out, int out_stride, hipStream_t s, const uint16_t* dfsz)
 {
     const size_t bps = bitdepth == 16 ? 2 : 4;
     const size_t fr_in = (size_t)c->channels * c->N * bps;                    /* bytes of one stream-frame of PCM */
     const size_t pcm_bytes = (size_t)c->n_streams * n_frames * fr_in, out_bytes = (size_t)c->n_streams * n_frames * out_stride;
     int K = (int)(pcm_bytes >> 25);                                           /* ~32 MB of PCM per run */
     if (K < 1) K = 1; if (K > 8) K = 8; if (K > n_frames) K = n_frames;
-    if (c->fused || n_frames <= LC3D_FUSED_MAX_T) K = 1;                                                      /* diagnostic single-kernel path: the first kernel addresses the output by its own frame count */
+    if (!dfsz && (c->fused || n_frames <= LC3D_FUSED_MAX_T)) K = 1;                                          /* diagnostic single-kernel path: the first kernel addresses the output by its own frame count (the per-frame-bitrate kernel by the call's) */
     const int Tc = (n_frames + K - 1) / K, T0 = K > 1 ? (Tc + 1) / 2 : Tc;   /* first run: half a run */
     const bool pin_in = host_ptr_is_pinned(pcm);
     const size_t cin = (size_t)c->n_streams * Tc * fr_in;
@@ -3429,7 +3508,7 @@ static int encode_host(lc3hip_ctx* c, const void* pcm, int bitdepth, int n_frame
         }
         HIPCHK(hipEventRecord(c->ev_h2d[i], c->s_h2d));
         HIPCHK(hipStreamWaitEvent(s, c->ev_h2d[i], 0));
-        if (enc_launch(c, c->hp_dpcm[i], bitdepth, tc, c->d_out, out_stride, s, nullptr, n_frames, t0, t0 + tc >= n_frames)) return 1;
+        if (enc_launch(c, c->hp_dpcm[i], bitdepth, tc, c->d_out, out_stride, s, nullptr, n_frames, t0, t0 + tc >= n_frames, dfsz)) return 1;
         HIPCHK(hipEventRecord(c->ev_k[i], s));
         t0 += tc;
     }
@@ -3440,14 +3519,55 @@ static int encode_host(lc3hip_ctx* c, const void* pcm, int bitdepth, int n_frame
     return 0;
 }
 
+extern "C" int lc3hip_upload_enc_table(void* ctx, const lc3d_chan* tab, int n)
+{
+    lc3hip_ctx* c = (lc3hip_ctx*)ctx;
+    HIPCHK(hipSetDevice(c->device));
+    if (c->d_etab) HIPCHK(hipFree(c->d_etab));
+    c->d_etab = nullptr;
+    HIPCHK(hipMalloc((void**)&c->d_etab, sizeof(lc3d_chan) * (size_t)n));
+    HIPCHK(hipMemcpy(c->d_etab, tab, sizeof(lc3d_chan) * (size_t)n, hipMemcpyHostToDevice));
+    return 0;
+}
+/* the stream-frame sizes of a per-frame-bitrate call to the device, queued on s ahead of its kernels: copied into pinned staging first, so that the caller's
+ * array is free when the call returns; the buffer pair of the call LC3D_SETS back is waited for before it is written again */
+static int upload_fsz(lc3hip_ctx* c, const uint16_t* fsz_host, int n_frames, hipStream_t s, const uint16_t** dfsz, hipEvent_t* ev)
+{
+    const size_t fb = sizeof(uint16_t) * (size_t)c->n_streams * n_frames;
+    const int k = c->fsz_set;
+    if (c->fsz_armed[k]) HIPCHK(hipEventSynchronize(c->ev_fsz[k]));
+    if (c->fsz_cap < fb) {
+        for (int i = 0; i < LC3D_SETS; i++) if (c->fsz_armed[i]) { HIPCHK(hipEventSynchronize(c->ev_fsz[i])); c->fsz_armed[i] = 0; }   /* no call reads them any more */
+        for (int i = 0; i < LC3D_SETS; i++) {
+            if (c->d_fsz[i]) HIPCHK(hipFree(c->d_fsz[i])); if (c->h_fsz[i]) HIPCHK(hipHostFree(c->h_fsz[i])); c->d_fsz[i] = nullptr; c->h_fsz[i] = nullptr;
+        }
+        c->fsz_cap = 0;
+        for (int i = 0; i < LC3D_SETS; i++) { HIPCHK(hipMalloc((void**)&c->d_fsz[i], fb)); HIPCHK(hipHostMalloc((void**)&c->h_fsz[i], fb, hipHostMallocDefault)); }
+        c->fsz_cap = fb;
+    }
+    if (!c->ev_fsz[0]) for (int i = 0; i < LC3D_SETS; i++) HIPCHK(hipEventCreateWithFlags(&c->ev_fsz[i], hipEventDisableTiming));
+    memcpy(c->h_fsz[k], fsz_host, fb);
+    HIPCHK(hipMemcpyAsync(c->d_fsz[k], c->h_fsz[k], fb, hipMemcpyHostToDevice, s));
+    *dfsz = c->d_fsz[k]; *ev = c->ev_fsz[k];
+    c->fsz_armed[k] = 1; c->fsz_set = (k + 1) % LC3D_SETS;
+    return 0;
+}
 extern "C" int lc3hip_encode(void* ctx, const void* pcm, int pcm_on_device, int bitdepth, int n_frames, void* out, int out_stride,
-                             int out_on_device, void* hip_stream, int sync, void* trace_host)
+                             int out_on_device, void* hip_stream, int sync, void* trace_host, const uint16_t* fsz_host)
 {
     lc3hip_ctx* c = (lc3hip_ctx*)ctx;
     HIPCHK(hipSetDevice(c->device));
     if (!hip_stream && !c->stream) HIPCHK(hipStreamCreate(&c->stream));
     hipStream_t s = hip_stream ? (hipStream_t)hip_stream : c->stream;
-    if (!pcm_on_device && !out_on_device && !trace_host) return encode_host(c, pcm, bitdepth, n_frames, out, out_stride, s);
+    const uint16_t* dfsz = nullptr; hipEvent_t ev_fsz = nullptr;
+    if (fsz_host && !c->d_etab) return 1;
+    if (!pcm_on_device && !out_on_device && !trace_host) {
+        if (c->chans_armed) HIPCHK(hipStreamWaitEvent(s, c->ev_chans, 0));
+        if (fsz_host && upload_fsz(c, fsz_host, n_frames, s, &dfsz, &ev_fsz)) return 1;
+        if (encode_host(c, pcm, bitdepth, n_frames, out, out_stride, s, dfsz)) return 1;
+        if (ev_fsz) HIPCHK(hipEventRecord(ev_fsz, s));
+        return 0;
+    }
     const size_t bps = bitdepth == 16 ? 2 : 4;
     const size_t pcm_bytes = (size_t)c->n_streams * n_frames * c->channels * c->N * bps;
     const size_t out_bytes = (size_t)c->n_streams * n_frames * out_stride;
@@ -3481,9 +3601,13 @@ extern "C" int lc3hip_encode(void* ctx, const void* pcm, int pcm_on_device, int 
         }
         (void)hipGetLastError();
     }
+    /* behind the LC3PLUS_CHECK_READY test, which must see no copy of ours pending on s */
+    if (c->chans_armed) HIPCHK(hipStreamWaitEvent(s, c->ev_chans, 0));
+    if (fsz_host && upload_fsz(c, fsz_host, n_frames, s, &dfsz, &ev_fsz)) return 1;
     HIPCHK(hipEventRecord(c->ev0, s));
-    if (enc_launch(c, dpcm, bitdepth, n_frames, dout, out_stride, s, dtr, n_frames, 0, true)) return 1;
+    if (enc_launch(c, dpcm, bitdepth, n_frames, dout, out_stride, s, dtr, n_frames, 0, true, dfsz)) return 1;
     HIPCHK(hipEventRecord(c->ev1, s));
+    if (ev_fsz) HIPCHK(hipEventRecord(ev_fsz, s));
     if (c->opt.check_ready && c->ev_ours) { HIPCHK(hipEventRecord(c->ev_ours, s)); c->ours_armed = 1; }
     if (!out_on_device) HIPCHK(hipMemcpyAsync(out, dout, out_bytes, hipMemcpyDeviceToHost, s));
     if (trace_host) HIPCHK(hipMemcpyAsync(trace_host, dtr, sizeof(lc3d_trace) * (size_t)c->ncs * n_frames, hipMemcpyDeviceToHost, s));
@@ -3575,6 +3699,9 @@ extern "C" int lc3hip_destroy(void* ctx)
     for (int i = 0; i < LC3D_SETS; i++) { if (c->d_spec[i]) hipFree(c->d_spec[i]); if (c->d_frec[i]) hipFree(c->d_frec[i]); }
     for (int i = 0; i < LC3D_SETS + 1; i++) if (c->d_xnext[i]) hipFree(c->d_xnext[i]);
     free(c->h_attack); free(c->h_nb);
+    if (c->d_etab) hipFree(c->d_etab);
+    if (c->h_chans) { hipHostFree(c->h_chans); hipEventDestroy(c->ev_chans); }
+    for (int i = 0; i < LC3D_SETS; i++) { if (c->d_fsz[i]) hipFree(c->d_fsz[i]); if (c->h_fsz[i]) hipHostFree(c->h_fsz[i]); if (c->ev_fsz[i]) hipEventDestroy(c->ev_fsz[i]); }
     for (int i = 0; i < 2; i++) {
         if (c->hp_dpcm[i]) hipFree(c->hp_dpcm[i]);
         if (c->hp_pin_in[i]) hipHostFree(c->hp_pin_in[i]);
@@ -3887,3 +4014,4 @@ extern "C" int lc3hip_dec_destroy(void* ctx)
     return 0;
 }
 #endif /* !LC3_BIG */
+#endif  /* LC3_ENC_VAR */

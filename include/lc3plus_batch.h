@@ -43,6 +43,25 @@ LC3_Error lc3plus_enc_batch_encode(lc3plus_batch* batch, const void* pcm, int pc
                                    int n_frames, void* out, int out_stride, int out_on_device,
                                    void* hip_stream, int sync);
 
+/* Per-frame bitrates, as the reference takes them (R/codec_exe.c:296-302: lc3_enc_set_bitrate before every frame of a switching file).  Arguments
+ * as encode(), and
+ *   bitrates  : host pointer, [n_streams][n_frames] total bitrate of each stream-frame (all channels); may be reused when the call returns
+ *   num_bytes : host pointer or NULL, [n_streams][n_frames]: bytes written per stream-frame
+ * Frame t of stream s is encoded byte for byte as the reference encodes it right after lc3_enc_set_bitrate(bitrates[s][t]): the frame's bytes
+ * split over its channels, the bit budgets, gain offset and regularisation bits, LPC weighting, the LTPF enable and attack handling - a frame
+ * whose rate disables attack handling clears the attack detector first (R/setup_enc_lc3.c:297-308), and a later frame whose rate enables it
+ * starts from that cleared state.  Bandwidths stay per stream (set_bandwidth).  Rates equal to the stream's current one everywhere give the
+ * output of encode().  Every rate is checked before any work, with the limits of set_bitrate for the geometry (high-resolution minimums,
+ * 44.1 kHz scaling): a rate outside them returns LC3_BITRATE_ERROR, an out_stride below the call's largest stream-frame LC3_ERROR, and the
+ * batch is left unchanged.  Each frame's payload starts at its slot of out; the bytes behind it are untouched.  After the call each stream is
+ * configured with its last frame's rate (num_bytes(stream), stride(), and a following encode() continue from it); the rates stay
+ * configuration, not state (get_state / set_state are unchanged).  Host or device pointers, sync 0 or 1 and hip_stream as for encode(); the
+ * new configuration is queued on hip_stream behind the call's kernels, so a call with sync = 0 returns without waiting for them.  The frames run in the
+ * one-wave-per-channel-stream kernel, whose writer is inside it: last_status reports the call, last_records returns 0 words after it. */
+LC3_Error lc3plus_enc_batch_encode_bitrates(lc3plus_batch* batch, const void* pcm, int pcm_on_device, int bitdepth,
+                                            const int* bitrates, int n_frames, void* out, int out_stride, int out_on_device,
+                                            int* num_bytes, void* hip_stream, int sync);
+
 /* Checkpoint / resume.  The cross-frame state of every channel-stream of the batch (MDCT / resampler memory, pitch and LTPF histories,
  * rate-control and attack-detector words; R/setup_enc_lc3.h:17-62) as one opaque host array of state_size() bytes.  A batch created with
  * the same (n_streams, samplerate, channels, frame_ms, hrmode, bitrates, bandwidths) that is given the state continues the streams

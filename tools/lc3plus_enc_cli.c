@@ -11,8 +11,8 @@
  *                   in.wav out.lc3plus BITRATE|FILE
  *
  * Switching files (R/codec_exe.c:296-326, loopy_read64 :858-866) hold one int64 per frame and wrap around: the bitrate per channel
- * (-swf FILE, or a file name in place of BITRATE) and the audio bandwidth in Hz (-bandwidth FILE).  Frames with equal settings are
- * still pushed through the GPU in runs; a change of setting ends the run.
+ * (-swf FILE, or a file name in place of BITRATE) and the audio bandwidth in Hz (-bandwidth FILE).  Frames go through the GPU in blocks of up
+ * to 256 with one bitrate per frame (lc3plus_enc_batch_encode_bitrates); a change of bandwidth ends a block.
  */
 #include <stdint.h>
 #include <stdio.h>
@@ -127,31 +127,33 @@ int main(int ac, char** av)
 
     const uint32_t total_frames = (w.frames + (uint32_t)N - 1) / (uint32_t)N;
     const int CH = 256;                                   /* frames per launch */
+    const int S = LC3_MAX_BYTES * 2;                      /* output slot per frame: the largest stream-frame */
     const int wide = w.bits != 16;
     void* pcm = calloc((size_t)CH * C * N, wide ? 4 : 2);
-    uint8_t* out = (uint8_t*)malloc((size_t)CH * LC3_MAX_BYTES * 2);
+    uint8_t* out = (uint8_t*)malloc((size_t)CH * S);
+    int* rates = (int*)malloc(sizeof(int) * CH); int* sizes = (int*)malloc(sizeof(int) * CH);
+    if (!pcm || !out || !rates || !sizes) die("out of memory");
     const int bps = w.bits / 8;
     int cur_bitrate = bitrate, cur_bw = bandwidth;
     uint32_t f0 = 0;
     while (f0 < total_frames) {
         /* settings of frame f0 (the reference applies them before reading the frame, R/codec_exe.c:296-326) */
         int64_t nbr = fswf ? loopy_read64(fswf) * C : cur_bitrate, nbw = fbwf ? loopy_read64(fbwf) : cur_bw;
-        if ((int)nbr != cur_bitrate) {
-            err = lc3plus_enc_batch_set_bitrate(b, 0, (int)nbr); if (err) { fprintf(stderr, "lc3plus_enc_cli: bitrate switch failed (LC3_Error %d)\n", (int)err); return 1; }
-            cur_bitrate = (int)nbr; nbytes = lc3plus_enc_batch_num_bytes(b, 0);
-        }
         if ((int)nbw != cur_bw) {
             err = lc3plus_enc_batch_set_bandwidth(b, 0, (int)nbw); if (err && err < LC3_WARNING) die("bandwidth error");
             cur_bw = (int)nbw;
         }
-        /* extend the run while the switching files keep the settings */
+        /* a block of up to CH frames with one rate per frame (lc3plus_enc_batch_encode_bitrates, as the reference's lc3_enc_set_bitrate before
+         * every frame); only a bandwidth change ends it */
+        rates[0] = (int)nbr;
         int T = 1;
         while (T < CH && f0 + T < total_frames) {
-            if (fswf || fbwf) {
-                const long ps = fswf ? ftell(fswf) : 0, pb = fbwf ? ftell(fbwf) : 0;
-                const int64_t br2 = fswf ? loopy_read64(fswf) * C : cur_bitrate, bw2 = fbwf ? loopy_read64(fbwf) : cur_bw;
-                if ((int)br2 != cur_bitrate || (int)bw2 != cur_bw) { if (fswf) fseek(fswf, ps, SEEK_SET); if (fbwf) fseek(fbwf, pb, SEEK_SET); break; }
-            }
+            if (fbwf) {
+                const long ps = fswf ? ftell(fswf) : 0, pb = ftell(fbwf);
+                const int64_t br2 = fswf ? loopy_read64(fswf) * C : cur_bitrate, bw2 = loopy_read64(fbwf);
+                if ((int)bw2 != cur_bw) { if (fswf) fseek(fswf, ps, SEEK_SET); fseek(fbwf, pb, SEEK_SET); break; }
+                rates[T] = (int)br2;
+            } else rates[T] = fswf ? (int)(loopy_read64(fswf) * C) : cur_bitrate;
             T++;
         }
         memset(pcm, 0, (size_t)T * C * N * (wide ? 4 : 2));
@@ -166,21 +168,29 @@ int main(int ac, char** av)
                 else ((int32_t*)pcm)[o] = ((int32_t)rd32(p)) >> 8;   /* the reference reader narrows 32-bit WAV to 24 bit (R/tinywavein_c.h:528-533) and still calls lc3_enc32 */
             }
         }
-        err = lc3plus_enc_batch_encode(b, pcm, 0, w.bits, T, out, nbytes, 0, NULL, 1);
-        if (err) { fprintf(stderr, "lc3plus_enc_cli: encode failed (LC3_Error %d)\n", (int)err); return 1; }
+        if (fswf) {
+            err = lc3plus_enc_batch_encode_bitrates(b, pcm, 0, w.bits, rates, T, out, S, 0, sizes, NULL, 1);
+            if (err) { fprintf(stderr, "lc3plus_enc_cli: encode failed (LC3_Error %d)\n", (int)err); return 1; }
+            cur_bitrate = rates[T - 1];
+        } else {
+            err = lc3plus_enc_batch_encode(b, pcm, 0, w.bits, T, out, S, 0, NULL, 1);
+            if (err) { fprintf(stderr, "lc3plus_enc_cli: encode failed (LC3_Error %d)\n", (int)err); return 1; }
+            for (int t = 0; t < T; t++) sizes[t] = nbytes;
+        }
         for (int t = 0; t < T; t++) {
-            const uint8_t* fr = out + (size_t)t * nbytes;
+            const uint8_t* fr = out + (size_t)t * S;
+            const int nb_t = sizes[t];
             if (g192) {                                   /* R/codec_exe.c:705-735 */
-                const uint16_t sync = 0x6B21, nbits = (uint16_t)(nbytes * 8);
+                const uint16_t sync = 0x6B21, nbits = (uint16_t)(nb_t * 8);
                 fwrite(&sync, 2, 1, fo); fwrite(&nbits, 2, 1, fo);
-                for (int k = 0; k < nbytes; k++) for (int bit = 0; bit < 8; bit++) {
+                for (int k = 0; k < nb_t; k++) for (int bit = 0; bit < 8; bit++) {
                     const int16_t v = (fr[k] >> bit) & 1 ? 0x0081 : 0x007F;
                     fwrite(&v, 2, 1, fo);
                 }
             } else {                                      /* R/codec_exe.c:742-748 */
-                const uint16_t nb = (uint16_t)nbytes;
+                const uint16_t nb = (uint16_t)nb_t;
                 fwrite(&nb, 2, 1, fo);
-                fwrite(fr, 1, nbytes, fo);
+                fwrite(fr, 1, nb_t, fo);
             }
         }
         f0 += (uint32_t)T;
@@ -189,6 +199,6 @@ int main(int ac, char** av)
     if (!quiet) puts("\nProcessing done!");
     fclose(fo);
     lc3plus_enc_batch_destroy(b);
-    free(pcm); free(out);
+    free(pcm); free(out); free(rates); free(sizes);
     return 0;
 }
