@@ -28,7 +28,7 @@ EXPORTS = [
     "lc3plus_dec_batch_create", "lc3plus_dec_batch_destroy", "lc3plus_dec_batch_output_samples", "lc3plus_dec_batch_delay",
     "lc3plus_dec_batch_num_bytes", "lc3plus_dec_batch_set_num_bytes", "lc3plus_dec_batch_decode",
     "lc3plus_dec_batch_last_kernel_ms", "lc3plus_dec_batch_set_input_ready", "lc3plus_dec_batch_decode_sizes",
-    "lc3plus_enc_batch_encode_bitrates",
+    "lc3plus_dec_batch_decode_sizes_device", "lc3plus_enc_batch_encode_bitrates",
 ]
 
 
@@ -90,6 +90,10 @@ def load_library():
                                                      C.c_int, C.c_void_p, C.c_void_p, C.c_int]
         L.lc3plus_dec_plan_sizes.argtypes = [C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.lc3plus_dec_batch_decode_sizes_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
+                                                            C.c_void_p, C.c_void_p, C.c_int]
+        L.lc3plus_dec_plan_sizes_lenient.argtypes = [C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                                     C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.lc3plus_dec_batch_decode_traced.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
                                                       C.c_void_p, C.c_void_p]
         L.lc3plus_dec_batch_last_kernel_ms.restype = C.c_float
@@ -337,6 +341,23 @@ def dec_plan_sizes(samplerate, channels, frame_ms, hrmode, start, num_bytes, bfi
     return rc, eff, lost, end, mx.value
 
 
+def dec_plan_sizes_lenient(samplerate, channels, frame_ms, hrmode, start, num_bytes, bfi=None, in_stride=None):
+    """The per-frame size rule of DecBatch.decode_device_sizes on the host (test hook lc3plus_dec_plan_sizes_lenient, no device needed): as
+    dec_plan_sizes, but an invalid size or flag makes its frame lost instead of failing the call -> (LC3_Error code, effective sizes [S, T] uint16,
+    lost [S, T] uint8, invalid [S, T] uint8, sizes after the call [S], largest channel frame not lost)."""
+    L = load_library()
+    num_bytes = np.ascontiguousarray(num_bytes, dtype=np.int32)
+    S, T = num_bytes.shape
+    start = np.ascontiguousarray(start, dtype=np.int32)
+    bfi = np.ascontiguousarray(bfi, dtype=np.uint8) if bfi is not None else None
+    eff = np.zeros((S, T), np.uint16); lost = np.zeros((S, T), np.uint8); inv = np.zeros((S, T), np.uint8); end = np.zeros(S, np.int32)
+    mx = C.c_int(0)
+    rc = L.lc3plus_dec_plan_sizes_lenient(samplerate, channels, frame_ms, hrmode, S, start.ctypes.data, num_bytes.ctypes.data,
+                                          bfi.ctypes.data if bfi is not None else None, T, int(in_stride if in_stride is not None else 1 << 20),
+                                          eff.ctypes.data, lost.ctypes.data, inv.ctypes.data, end.ctypes.data, C.byref(mx))
+    return rc, eff, lost, inv, end, mx.value
+
+
 class DecBatch:
     """n_streams independent decoders (lc3plus_dec_batch_*), state resident on the GPU between decode() calls."""
 
@@ -404,6 +425,18 @@ class DecBatch:
         if rc:
             raise LC3Error(rc, "lc3plus_dec_batch_decode")
         return pcm, status
+
+    def decode_device_sizes(self, d_frames_ptr, in_stride, T, d_pcm_ptr, d_num_bytes_ptr, d_bfi_ptr=None, d_status_ptr=None, bps=16, hip_stream=None,
+                            sync=False):
+        """Per-frame sizes and flags in device memory (lc3plus_dec_batch_decode_sizes_device): raw device pointers only - frames [n_streams, T, in_stride]
+        uint8, num_bytes [n_streams, T] int32 (0 = lost), optional bfi [n_streams, T] uint8 and status [n_streams, T] uint8, pcm [n_streams, T, channels, N].
+        Queued on hip_stream; returns at once unless sync.  An invalid size or flag conceals its frame (status bit 1) instead of failing the call."""
+        rc = self.lib.lc3plus_dec_batch_decode_sizes_device(self.h, C.c_void_p(d_frames_ptr), in_stride, C.c_void_p(d_num_bytes_ptr),
+                                                            C.c_void_p(d_bfi_ptr) if d_bfi_ptr else None, T, C.c_void_p(d_pcm_ptr), bps,
+                                                            C.c_void_p(d_status_ptr) if d_status_ptr else None,
+                                                            C.c_void_p(hip_stream) if hip_stream else None, 1 if sync else 0)
+        if rc:
+            raise LC3Error(rc, "lc3plus_dec_batch_decode_sizes_device")
 
     def decode_traced(self, frames, bfi=None, bps=16):
         frames, T, stride, bfi, pcm, status = self._prep(frames, bfi, bps)

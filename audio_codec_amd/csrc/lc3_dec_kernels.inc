@@ -265,6 +265,48 @@ lc3_dec_plc_kernel(const lc3d_plan* __restrict__ P, const lc3d_dchan* __restrict
     }
     if (valid) { sc[DS_NBLOST] = nbl; sc[DS_CUM_ALPHA] = __float_as_int(ca); sc[DS_PLC_SEED] = seed; sc[DS_PREV_BFI] = prev; sc[DS_PREVPREV_BFI] = pprev; }
 }
+
+/* Per-frame sizes and flags in device memory (lc3plus_dec_batch_decode_sizes_device), before the parser: one stream-frame per lane, the rule of
+ * lc3d_dec_frame_class (lc3_plan.h).  Writes what the per-frame-size kernels take - the size of every good frame and 0 where the frame is lost, and the
+ * lost flag - and marks the frames lost because their size or flag is invalid. */
+extern "C" __global__ void __launch_bounds__(256)
+lc3_dec_plan_sizes_kernel(const int32_t* __restrict__ num_bytes, const uint8_t* __restrict__ bfi /* or null */, const lc3d_dchan* __restrict__ dtab,
+                          int tab_n, int channels, int in_stride, long long n, uint16_t* __restrict__ sizes, uint8_t* __restrict__ lost,
+                          uint8_t* __restrict__ invalid)
+{
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int nb = num_bytes[i];
+    const int k = lc3d_dec_frame_class(nb, bfi ? (int)bfi[i] : 0, in_stride, dtab, tab_n, channels);
+    sizes[i] = k == LC3D_FRAME_GOOD ? (uint16_t)nb : (uint16_t)0;
+    lost[i] = k != LC3D_FRAME_GOOD;
+    invalid[i] = k >= LC3D_FRAME_BAD_FLAG;
+}
+
+/* ... and after the synthesis: one stream-frame per lane.  An invalid frame's status gets LC3D_DEC_ST_INVALID beside the concealment bit the synthesis
+ * wrote.  The lane of a stream's last frame configures the stream with the size of its last good frame of the call (the configuration stays when the
+ * call has none): every channel from dtab, with its payload offset, as lc3plus_dec_batch_decode_sizes does on the host.  The concealment kernel of the
+ * next call starts its LTPF carry from there, and a later fixed-size parser reads it. */
+extern "C" __global__ void __launch_bounds__(256)
+lc3_dec_sizes_tail_kernel(const uint16_t* __restrict__ sizes, const uint8_t* __restrict__ invalid, const lc3d_dchan* __restrict__ dtab, int channels,
+                          int n_streams, int T, lc3d_dchan* __restrict__ chans, uint8_t* __restrict__ status /* [stream][T] or null */)
+{
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (long long)n_streams * T) return;
+    if (status && invalid[i]) status[i] |= LC3D_DEC_ST_INVALID;
+    if (i % T != T - 1) return;
+    const long long s = i / T;
+    const uint16_t* z = sizes + s * T;
+    int t = T - 1;
+    while (t >= 0 && z[t] == 0) t--;
+    if (t < 0) return;
+    const int fsz = z[t];
+    for (int c = 0, off = 0; c < channels; c++) {
+        lc3d_dchan d = dtab[fsz / channels + (c < fsz % channels)];
+        d.in_off = off; off += d.nbytes;
+        chans[s * channels + c] = d;
+    }
+}
 #endif
 
 /* ------------------------------------------------------------------------------------------------ */

@@ -798,15 +798,11 @@ static LC3_Error dec_plan_sizes(const geom_t* g, const lc3d_dchan* tab, int tab_
     const size_t n = (size_t)n_streams * n_frames;
     int mx = 0;
     for (size_t i = 0; i < n; i++) {
-        if (bfi && bfi[i] > 1) return LC3_ERROR;
         const int nb = num_bytes[i];
-        if ((bfi && bfi[i]) || nb == 0) continue;
-        if (nb < 0 || nb > in_stride) return LC3_NUMBYTES_ERROR;
-        for (int c = 0; c < C; c++) {
-            const int k = nb / C + (c < nb % C);
-            if (k >= tab_n || k == 0 || tab[k].nbytes != k) return LC3_NUMBYTES_ERROR;
-        }
-        if ((nb + C - 1) / C > mx) mx = (nb + C - 1) / C;
+        const int k = lc3d_dec_frame_class(nb, bfi ? bfi[i] : 0, in_stride, tab, tab_n, C);
+        if (k == LC3D_FRAME_BAD_FLAG) return LC3_ERROR;
+        if (k == LC3D_FRAME_BAD_SIZE) return LC3_NUMBYTES_ERROR;
+        if (k == LC3D_FRAME_GOOD && (nb + C - 1) / C > mx) mx = (nb + C - 1) / C;
     }
     for (int s = 0; s < n_streams; s++) {
         int cur = start[s];
@@ -822,9 +818,31 @@ static LC3_Error dec_plan_sizes(const geom_t* g, const lc3d_dchan* tab, int tab_
     return LC3_OK;
 }
 
+/* The rule of lc3plus_dec_batch_decode_sizes_device on the host (on the device: lc3_dec_plan_sizes_kernel and lc3_dec_sizes_tail_kernel): as
+ * dec_plan_sizes, except that a size or flag the host call refuses does not fail the call - the frame is lost, marked in invalid[s][t], and does not
+ * move the carry.  Nothing is refused. */
+static void dec_plan_sizes_lenient(const geom_t* g, const lc3d_dchan* tab, int tab_n, int n_streams, const int* start, const int* num_bytes, const uint8_t* bfi,
+                                   int n_frames, int in_stride, uint16_t* eff, uint8_t* lost, uint8_t* invalid, int* end, int* max_chan)
+{
+    const int C = g->channels;
+    int mx = 0;
+    for (int s = 0; s < n_streams; s++) {
+        int cur = start[s];
+        for (int t = 0; t < n_frames; t++) {
+            const size_t i = (size_t)s * n_frames + t;
+            const int k = lc3d_dec_frame_class(num_bytes[i], bfi ? bfi[i] : 0, in_stride, tab, tab_n, C);
+            if (k == LC3D_FRAME_GOOD) { cur = num_bytes[i]; if ((cur + C - 1) / C > mx) mx = (cur + C - 1) / C; }
+            eff[i] = (uint16_t)cur; lost[i] = k != LC3D_FRAME_GOOD; invalid[i] = k >= LC3D_FRAME_BAD_FLAG;
+        }
+        end[s] = cur;
+    }
+    *max_chan = mx;
+}
+
 struct lc3plus_dec_batch {
     geom_t g; int n_streams;
     lc3d_dchan* chans;               /* [n_streams * channels] host mirror */
+    int chans_stale;                 /* a call with sizes in device memory has changed the configuration on the device: dec_refresh before reading chans */
     void* dev;
     lc3d_dchan* tab; int tab_n;      /* dec_build_table, also on the device */
     uint16_t* eff; uint8_t* lost; int* sz; size_t plan_cap;          /* per-frame sizes: host buffers of dec_plan_sizes, grown as needed */
@@ -893,9 +911,19 @@ LC3_Error lc3plus_dec_batch_destroy(lc3plus_dec_batch* b)
 
 int lc3plus_dec_batch_output_samples(const lc3plus_dec_batch* b) { return b ? b->g.N : 0; }
 int lc3plus_dec_batch_delay(const lc3plus_dec_batch* b) { return b ? b->g.N - 2 * b->g.la : 0; }
+/* Brings the host mirror of the configuration back after calls with sizes in device memory: waits for the batch's last call and downloads it, once. */
+static LC3_Error dec_refresh(lc3plus_dec_batch* b)
+{
+    if (!b->chans_stale) return LC3_OK;
+    if (lc3hip_dec_download_chans(b->dev, b->chans)) return LC3_ERROR;
+    b->chans_stale = 0;
+    return LC3_OK;
+}
 int lc3plus_dec_batch_num_bytes(const lc3plus_dec_batch* b, int stream)
 {
     if (!b || stream < 0 || stream >= b->n_streams) return 0;
+    /* (the mirror is a cache of the device's configuration: refreshing it leaves the batch as it was) */
+    if (dec_refresh((lc3plus_dec_batch*)b)) return 0;
     int n = 0;
     for (int c = 0; c < b->g.channels; c++) n += b->chans[stream * b->g.channels + c].nbytes;
     return n;
@@ -910,6 +938,7 @@ LC3_Error lc3plus_dec_batch_set_num_bytes(lc3plus_dec_batch* b, int stream, int 
     memset(tmp, 0, sizeof tmp);
     LC3_Error e = derive_dstream(&b->g, num_bytes, tmp);
     if (e) return e;
+    if (dec_refresh(b)) return LC3_ERROR;
     memcpy(b->chans + (size_t)stream * b->g.channels, tmp, sizeof(lc3d_dchan) * b->g.channels);
     return lc3hip_dec_upload_chans(b->dev, tmp, stream * b->g.channels, b->g.channels) ? LC3_ERROR : LC3_OK;
 }
@@ -920,6 +949,7 @@ static LC3_Error dec_batch_decode(lc3plus_dec_batch* b, const void* frames, int 
     if (!b || !frames || !pcm) return LC3_NULL_ERROR;
     if (bps != 16 && bps != 24 && bps != 32) return LC3_ERROR;
     if (n_frames <= 0) return LC3_ERROR;
+    if (dec_refresh(b)) return LC3_ERROR;
     for (int i = 0; i < b->n_streams; i++) if (lc3plus_dec_batch_num_bytes(b, i) > in_stride) return LC3_NUMBYTES_ERROR;
     return lc3hip_dec_decode(b->dev, frames, frames_on_device, in_stride, bfi, NULL, 0, n_frames, pcm, pcm_on_device, bps, status, hip_stream, sync, traces)
                ? LC3_ERROR : LC3_OK;
@@ -930,6 +960,7 @@ LC3_Error lc3plus_dec_batch_decode_sizes(lc3plus_dec_batch* b, const void* frame
     if (!b || !frames || !pcm || !num_bytes) return LC3_NULL_ERROR;
     if (bps != 16 && bps != 24 && bps != 32) return LC3_ERROR;
     if (n_frames <= 0) return LC3_ERROR;
+    if (dec_refresh(b)) return LC3_ERROR;
     const size_t n = (size_t)b->n_streams * n_frames;
     if (b->plan_cap < n) {
         free(b->eff); free(b->lost); b->plan_cap = 0;
@@ -963,23 +994,49 @@ LC3_Error lc3plus_dec_batch_decode_sizes(lc3plus_dec_batch* b, const void* frame
     if (changed && lc3hip_dec_upload_chans(b->dev, b->chans, 0, b->n_streams * b->g.channels)) return LC3_ERROR;
     return LC3_OK;
 }
-/* test hook: dec_plan_sizes for a geometry, without a device (the batch builds the same table at create) */
+LC3_Error lc3plus_dec_batch_decode_sizes_device(lc3plus_dec_batch* b, const void* frames, int in_stride, const int32_t* num_bytes, const uint8_t* bfi,
+                                                int n_frames, void* pcm, int bps, uint8_t* status, void* hip_stream, int sync)
+{
+    if (!b || !frames || !pcm || !num_bytes) return LC3_NULL_ERROR;
+    if (bps != 16 && bps != 24 && bps != 32) return LC3_ERROR;
+    if (n_frames <= 0 || in_stride <= 0) return LC3_ERROR;
+    /* the sizes, the carry and the configuration after the call are on the device only: the host mirror is read back by the next host-side reader */
+    if (lc3hip_dec_decode_dsizes(b->dev, frames, in_stride, num_bytes, bfi, n_frames, pcm, bps, status, hip_stream, sync)) return LC3_ERROR;
+    b->chans_stale = 1;
+    return LC3_OK;
+}
+/* test hooks: dec_plan_sizes and dec_plan_sizes_lenient for a geometry, without a device (the batch builds the same table at create) */
+static LC3_Error dec_hook_table(int samplerate, int channels, float frame_ms, int hrmode, geom_t* g, lc3d_dchan** tab, int* tab_n)
+{
+    if (!samplerate_ok(samplerate)) return LC3_SAMPLERATE_ERROR;
+    if (channels < 1 || channels > MAX_CH) return LC3_CHANNELS_ERROR;
+    geom_init(g, samplerate, channels);
+    g->dms = (int)(frame_ms * 10); g->frame_ms = frame_ms; g->hrmode = hrmode > 0;
+    geom_update_ex(g, 1);
+    *tab = dec_build_table(g, tab_n);
+    return *tab ? LC3_OK : LC3_ERROR;
+}
 LC3_Error lc3plus_dec_plan_sizes(int samplerate, int channels, float frame_ms, int hrmode, int n_streams, const int* start, const int* num_bytes,
                                  const uint8_t* bfi, int n_frames, int in_stride, uint16_t* eff, uint8_t* lost, int* end, int* max_chan)
 {
     if (!start || !num_bytes || !eff || !lost || !end || !max_chan) return LC3_NULL_ERROR;
-    if (!samplerate_ok(samplerate)) return LC3_SAMPLERATE_ERROR;
-    if (channels < 1 || channels > MAX_CH) return LC3_CHANNELS_ERROR;
-    geom_t g;
-    geom_init(&g, samplerate, channels);
-    g.dms = (int)(frame_ms * 10); g.frame_ms = frame_ms; g.hrmode = hrmode > 0;
-    geom_update_ex(&g, 1);
-    int tab_n = 0;
-    lc3d_dchan* tab = dec_build_table(&g, &tab_n);
-    if (!tab) return LC3_ERROR;
-    LC3_Error e = dec_plan_sizes(&g, tab, tab_n, n_streams, start, num_bytes, bfi, n_frames, in_stride, eff, lost, end, max_chan);
+    geom_t g; lc3d_dchan* tab = NULL; int tab_n = 0;
+    LC3_Error e = dec_hook_table(samplerate, channels, frame_ms, hrmode, &g, &tab, &tab_n);
+    if (e) return e;
+    e = dec_plan_sizes(&g, tab, tab_n, n_streams, start, num_bytes, bfi, n_frames, in_stride, eff, lost, end, max_chan);
     free(tab);
     return e;
+}
+LC3_Error lc3plus_dec_plan_sizes_lenient(int samplerate, int channels, float frame_ms, int hrmode, int n_streams, const int* start, const int* num_bytes,
+                                         const uint8_t* bfi, int n_frames, int in_stride, uint16_t* eff, uint8_t* lost, uint8_t* invalid, int* end, int* max_chan)
+{
+    if (!start || !num_bytes || !eff || !lost || !invalid || !end || !max_chan) return LC3_NULL_ERROR;
+    geom_t g; lc3d_dchan* tab = NULL; int tab_n = 0;
+    LC3_Error e = dec_hook_table(samplerate, channels, frame_ms, hrmode, &g, &tab, &tab_n);
+    if (e) return e;
+    dec_plan_sizes_lenient(&g, tab, tab_n, n_streams, start, num_bytes, bfi, n_frames, in_stride, eff, lost, invalid, end, max_chan);
+    free(tab);
+    return LC3_OK;
 }
 LC3_Error lc3plus_dec_batch_decode(lc3plus_dec_batch* b, const void* frames, int frames_on_device, int in_stride, const uint8_t* bfi, int n_frames,
                                    void* pcm, int pcm_on_device, int bps, uint8_t* status, void* hip_stream, int sync)

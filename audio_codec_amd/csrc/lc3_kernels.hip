@@ -3733,7 +3733,8 @@ struct lc3hip_dctx {
     int device, ncs, n_streams, channels, N, big;
     lc3d_plan* d_plan; lc3d_dchan* d_chans; float* d_state;
     uint8_t* d_in; size_t in_cap; void* d_pcm; size_t pcm_cap; uint8_t* d_bfi; size_t bfi_cap;
-    lc3d_dchan* d_tab; uint16_t* d_sizes; size_t sizes_cap;          /* per-frame sizes: configuration per channel byte count, effective size per stream-frame */
+    lc3d_dchan* d_tab; int tab_n; uint16_t* d_sizes; size_t sizes_cap;          /* per-frame sizes: configuration per channel byte count, effective size per stream-frame */
+    uint8_t* d_inval; size_t inval_cap;                              /* per-frame sizes from device memory: the frames lost because their size or flag is invalid */
     lc3d_dec_trace* d_trace; size_t trace_cap; uint8_t* d_status; size_t status_cap;
     int* d_rec; float* d_ws; float* d_ov; size_t hand_cap; int max_nbytes; int* h_nbytes;
     hipStream_t stream, last_stream; hipEvent_t ev0, ev1; float last_ms;
@@ -3807,13 +3808,25 @@ extern "C" int lc3hip_dec_upload_table(void* ctx, const lc3d_dchan* tab, int n)
     c->d_tab = nullptr;
     HIPCHK(hipMalloc((void**)&c->d_tab, sizeof(lc3d_dchan) * (size_t)n));
     HIPCHK(hipMemcpy(c->d_tab, tab, sizeof(lc3d_dchan) * (size_t)n, hipMemcpyHostToDevice));
+    c->tab_n = n;
     return 0;
 }
-extern "C" int lc3hip_dec_decode(void* ctx, const void* frames, int frames_on_device, int in_stride, const uint8_t* bfi_host, const uint16_t* sizes_host,
-                                 int sizes_max_nbytes, int n_frames, void* pcm, int pcm_on_device, int bps, uint8_t* status_host, void* hip_stream, int sync,
-                                 void* trace_host)
+extern "C" int lc3hip_dec_download_chans(void* ctx, lc3d_dchan* chans)
 {
     lc3hip_dctx* c = (lc3hip_dctx*)ctx;
+    HIPCHK(hipSetDevice(c->device));
+    if (c->last_stream) { HIPCHK(hipStreamSynchronize(c->last_stream)); c->last_stream = nullptr; }
+    HIPCHK(hipMemcpy(chans, c->d_chans, sizeof(lc3d_dchan) * c->ncs, hipMemcpyDeviceToHost));
+    if (!c->h_nbytes) { c->h_nbytes = (int*)calloc((size_t)c->ncs, sizeof(int)); if (!c->h_nbytes) return 1; }
+    c->max_nbytes = 0;
+    for (int i = 0; i < c->ncs; i++) { c->h_nbytes[i] = chans[i].nbytes; if (c->h_nbytes[i] > c->max_nbytes) c->max_nbytes = c->h_nbytes[i]; }
+    return 0;
+}
+/* nb_dev: per-frame sizes in device memory (lc3hip_dec_decode_dsizes) - with bfi_dev (or null) and status_dev (or null), all device pointers like frames and pcm */
+static int dec_decode(lc3hip_dctx* c, const void* frames, int frames_on_device, int in_stride, const uint8_t* bfi_host, const uint16_t* sizes_host,
+                      int sizes_max_nbytes, int n_frames, void* pcm, int pcm_on_device, int bps, uint8_t* status_host, void* hip_stream, int sync,
+                      void* trace_host, const int32_t* nb_dev, const uint8_t* bfi_dev, uint8_t* status_dev)
+{
     HIPCHK(hipSetDevice(c->device));
     hipStream_t s = hip_stream ? (hipStream_t)hip_stream : c->stream;
     const size_t in_bytes = (size_t)c->n_streams * n_frames * in_stride;
@@ -3854,9 +3867,25 @@ extern "C" int lc3hip_dec_decode(void* ctx, const void* frames, int frames_on_de
         if (c->status_cap < fb) { if (c->d_status) HIPCHK(hipFree(c->d_status)); HIPCHK(hipMalloc((void**)&c->d_status, fb)); c->status_cap = fb; }
         dst = c->d_status;
     }
+    if (nb_dev) {                                                   /* sizes and flags from device memory: the plan kernel below fills d_sizes / d_bfi / d_inval */
+        if (!c->d_tab) return 1;
+        const size_t fb = (size_t)c->n_streams * n_frames;
+        if (c->sizes_cap < sizeof(uint16_t) * fb || c->bfi_cap < fb || c->inval_cap < fb) {
+            /* a smaller buffer of an earlier call may still be read (calls of this kind do not wait): growing it waits for the device, once; the first
+             * allocation does not */
+            if ((c->d_sizes && c->sizes_cap < sizeof(uint16_t) * fb) || (c->d_bfi && c->bfi_cap < fb) || (c->d_inval && c->inval_cap < fb))
+                HIPCHK(hipDeviceSynchronize());
+            if (c->sizes_cap < sizeof(uint16_t) * fb) { if (c->d_sizes) HIPCHK(hipFree(c->d_sizes)); c->d_sizes = nullptr; c->sizes_cap = 0;
+                                                         HIPCHK(hipMalloc((void**)&c->d_sizes, sizeof(uint16_t) * fb)); c->sizes_cap = sizeof(uint16_t) * fb; }
+            if (c->bfi_cap < fb) { if (c->d_bfi) HIPCHK(hipFree(c->d_bfi)); c->d_bfi = nullptr; c->bfi_cap = 0; HIPCHK(hipMalloc((void**)&c->d_bfi, fb)); c->bfi_cap = fb; }
+            if (c->inval_cap < fb) { if (c->d_inval) HIPCHK(hipFree(c->d_inval)); c->d_inval = nullptr; c->inval_cap = 0; HIPCHK(hipMalloc((void**)&c->d_inval, fb)); c->inval_cap = fb; }
+        }
+        dsizes = c->d_sizes; dbfi = c->d_bfi; dst = status_dev;
+    }
     {   /* hand-over buffers between the two kernels: records and spectrum rows of every channel-frame of this call */
         const size_t cf = (size_t)c->ncs * n_frames;
         if (c->hand_cap < cf) {
+            if (c->d_rec) HIPCHK(hipDeviceSynchronize());            /* an earlier call that did not wait may still read them (not on the first call) */
             if (c->d_rec) HIPCHK(hipFree(c->d_rec));
             if (c->d_ws) HIPCHK(hipFree(c->d_ws));
             if (c->d_ov) HIPCHK(hipFree(c->d_ov));
@@ -3870,7 +3899,7 @@ extern "C" int lc3hip_dec_decode(void* ctx, const void* frames, int frames_on_de
     /* Under the input-ready promise (the frames of a call are complete on the device when the call is made) the parse kernel - stateless: a frame's
      * record and spectrum row depend on that frame's bytes only - does not wait for what is queued on s: it runs on its own stream into the other set of
      * hand-over buffers while the concealment bookkeeping, transform and synthesis of the call before (the stateful part, in order on s) read theirs. */
-    const bool ahead = c->input_ready && frames_on_device && pcm_on_device && !bfi_host && !trace_host && !status_host;
+    const bool ahead = c->input_ready && frames_on_device && pcm_on_device && !bfi_host && !trace_host && !status_host && !nb_dev;
     int* rec_w = c->d_rec; float* ws_w = c->d_ws;
     if (ahead) {
         const size_t cf = (size_t)c->ncs * n_frames;
@@ -3893,8 +3922,10 @@ extern "C" int lc3hip_dec_decode(void* ctx, const void* frames, int frames_on_de
     }
     hipStream_t sp = ahead ? c->s_par : s;
     /* frames of up to 128 bytes are staged in LDS; larger ones would cut the waves per workgroup and are read from global memory */
-    /* (per-frame sizes: the largest channel frame of the call that is not lost - lost frames stage nothing) */
-    const int max_nb = dsizes ? sizes_max_nbytes : c->max_nbytes;
+    /* (per-frame sizes: the largest channel frame of the call that is not lost - lost frames stage nothing; sizes in device memory are not seen by the
+     * host: the bound it knows, a channel's share of in_stride up to the geometry's largest channel frame - a tight in_stride keeps the staged parser) */
+    const int ch_share = (in_stride + c->channels - 1) / c->channels;
+    const int max_nb = nb_dev ? (ch_share < c->tab_n - 1 ? ch_share : c->tab_n - 1) : dsizes ? sizes_max_nbytes : c->max_nbytes;
     const int nw_max = max_nb > 128 ? 0 : max_nb > 0 ? (max_nb + 3) / 4 : 1;
     const int nlw = (WS_ROW(c->N) / 2 + 31) / 32;                          /* >= (ylen / 2 + 31) / 32 of the plan */
     const size_t per_wave = (size_t)(nw_max + nlw) * WAVE * sizeof(unsigned);
@@ -3903,13 +3934,23 @@ extern "C" int lc3hip_dec_decode(void* ctx, const void* frames, int frames_on_de
     if (wpg < 1) { fprintf(stderr, "lc3plus_hip: frame of %d bytes exceeds the parse kernel's LDS staging\n", max_nb); return 1; }
     const long long tasks = (long long)c->n_streams * n_frames, per_wg = (long long)wpg * WAVE;
     HIPCHK(hipEventRecord(c->ev0, s));
+    if (nb_dev) {
+        const long long n = (long long)c->n_streams * n_frames;
+        hipLaunchKernelGGL(lc3_dec_plan_sizes_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, nb_dev, bfi_dev, c->d_tab, c->tab_n, c->channels, in_stride, n,
+                           c->d_sizes, c->d_bfi, c->d_inval);
+        HIPCHK(hipGetLastError());
+    }
     /* parse: one stream-frame per lane; concealment bookkeeping: one channel-stream per lane; IMDCT: one channel-frame per wave;
      * synthesis: one channel-stream per wave (lc3_dec_kernels.inc) */
     if (ahead && c->free_armed[c->set]) HIPCHK(hipStreamWaitEvent(sp, c->ev_free[c->set], 0));      /* this set was last read by the synthesis of the call DEC_SETS back */
-    /* The first parse-ahead behind an ordered call waits for all of it: that call's transform and synthesis read the first set of hand-over buffers, and its
-     * concealment kernel (on s) must not be overtaken by this call's (on s_plc, behind this parser) - both read-modify-write the concealment words.  Today
-     * every ordered call made under the promise returns only when it is done (it passes flags, sizes, status or host pointers, see the synchronisation at
-     * the end), so the event has completed when this wait is queued; it states the order instead of leaving it to that synchronisation. */
+    /* The first parse-ahead behind an ordered call waits for all of it: that call's transform and synthesis read the first set of hand-over buffers, its
+     * concealment kernel (on s) must not be overtaken by this call's (on s_plc, behind this parser) - both read-modify-write the concealment words
+     * (DS_NBLOST, DS_CUM_ALPHA, DS_PLC_SEED, DS_PREV_BFI) - and with sizes from device memory its tail kernel writes the configuration this parser reads.
+     * Every ordered call made today has completed when this wait is queued: the host-array calls return when they are done, and a call with sizes in
+     * device memory (which returns before its work is done) leaves the host's copy of the configuration stale, so the fixed-size call that makes this
+     * parse-ahead reads it back first (lc3_host.c dec_refresh), waiting for that call on the host.  The event states the order on the device instead of
+     * leaving it to those host waits.  The other direction, an ordered call behind parse-ahead calls, waits on the device for the last of their
+     * concealment kernels (ev_plc, below) - there a device-size call with sync = 0 does rely on it. */
     if (ahead && c->ord_pending) { HIPCHK(hipStreamWaitEvent(sp, c->ev_ord, 0)); c->ord_pending = 0; }
     /* How many parse waves a CU holds.  The kernel for frames of more than 128 bytes reads its frames from global memory and needs little LDS, so its 4 096
      * waves of 128 registers fill every SIMD, and the 64-wave concealment kernel and the transform of the call before wait for parse waves to retire; 24 KB of
@@ -3949,6 +3990,12 @@ extern "C" int lc3hip_dec_decode(void* ctx, const void* frames, int frames_on_de
         hipLaunchKernelGGL(lc3_dec_synth_kernel, dim3(c->ncs), dim3(WAVE), 0, s, c->d_plan, c->d_state, rec_w, ws_w, c->d_ov, n_frames, dpcm, bps, c->ncs, dst, dtr);
     }
     HIPCHK(hipGetLastError());
+    if (nb_dev) {                                                    /* behind the synthesis: the status bits and the stream's configuration for the next call */
+        const long long n = (long long)c->n_streams * n_frames;
+        hipLaunchKernelGGL(lc3_dec_sizes_tail_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, c->d_sizes, c->d_inval, c->d_tab, c->channels,
+                           c->n_streams, n_frames, c->d_chans, dst);
+        HIPCHK(hipGetLastError());
+    }
     if (ahead) { HIPCHK(hipEventRecord(c->ev_free[c->set], s)); c->free_armed[c->set] = 1; c->set = (c->set + 1) % DEC_SETS; }
     else if (c->s_par) { HIPCHK(hipEventRecord(c->ev_free[0], s)); c->free_armed[0] = 1; }      /* an ordered call reads the first set: a later parse-ahead into it waits for this one */
     if (!ahead && c->input_ready) {                                  /* ... and the next parse-ahead waits for the whole call (see above) */
@@ -3965,6 +4012,19 @@ extern "C" int lc3hip_dec_decode(void* ctx, const void* frames, int frames_on_de
         float ms = 0; if (hipEventElapsedTime(&ms, c->ev0, c->ev1) == hipSuccess) c->last_ms = ms;
     }
     return 0;
+}
+extern "C" int lc3hip_dec_decode(void* ctx, const void* frames, int frames_on_device, int in_stride, const uint8_t* bfi_host, const uint16_t* sizes_host,
+                                 int sizes_max_nbytes, int n_frames, void* pcm, int pcm_on_device, int bps, uint8_t* status_host, void* hip_stream, int sync,
+                                 void* trace_host)
+{
+    return dec_decode((lc3hip_dctx*)ctx, frames, frames_on_device, in_stride, bfi_host, sizes_host, sizes_max_nbytes, n_frames, pcm, pcm_on_device, bps, status_host,
+                      hip_stream, sync, trace_host, nullptr, nullptr, nullptr);
+}
+extern "C" int lc3hip_dec_decode_dsizes(void* ctx, const void* frames, int in_stride, const int32_t* num_bytes_dev, const uint8_t* bfi_dev, int n_frames,
+                                        void* pcm, int bps, uint8_t* status_dev, void* hip_stream, int sync)
+{
+    return dec_decode((lc3hip_dctx*)ctx, frames, 1, in_stride, nullptr, nullptr, 0, n_frames, pcm, 1, bps, nullptr, hip_stream, sync, nullptr,
+                      num_bytes_dev, bfi_dev, status_dev);
 }
 extern "C" int lc3hip_dec_set_input_ready(void* ctx, int ready)
 {
@@ -4002,7 +4062,7 @@ extern "C" int lc3hip_dec_destroy(void* ctx)
     if (!c) return 0;
     hipSetDevice(c->device);
     hipDeviceSynchronize();
-    void* bufs[] = {c->d_plan, c->d_chans, c->d_state, c->d_in, c->d_pcm, c->d_bfi, c->d_trace, c->d_status, c->d_rec, c->d_ws, c->d_ov, c->d_tab, c->d_sizes};
+    void* bufs[] = {c->d_plan, c->d_chans, c->d_state, c->d_in, c->d_pcm, c->d_bfi, c->d_trace, c->d_status, c->d_rec, c->d_ws, c->d_ov, c->d_tab, c->d_sizes, c->d_inval};
     for (int i = 0; i < DEC_SETS - 1; i++) { if (c->d_recx[i]) hipFree(c->d_recx[i]); if (c->d_wsx[i]) hipFree(c->d_wsx[i]); }
     if (c->s_par) { hipStreamDestroy(c->s_par); for (int i = 0; i < DEC_SETS; i++) { hipEventDestroy(c->ev_par[i]); hipEventDestroy(c->ev_free[i]); } hipStreamDestroy(c->s_plc); hipEventDestroy(c->ev_plc); hipEventDestroy(c->ev_ord); }
     for (void* p : bufs) if (p) hipFree(p);

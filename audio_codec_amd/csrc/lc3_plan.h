@@ -111,6 +111,30 @@ typedef struct {                         /* per channel-stream decoder configura
     int32_t nbytes, lpc_weighting, gg_off, N_red_tns, fs_red_tns, ltpf_beta_idx; float ltpf_beta; int32_t in_off;
 } lc3d_dchan;
 
+/* The per-frame rule of the per-frame-size decode calls, one (stream, frame) at a time, on the host (lc3_host.c: the checks of
+ * lc3plus_dec_batch_decode_sizes, the test hooks) and on the device (lc3_dec_plan_sizes_kernel).  tab[tab_n]: the configuration per channel
+ * byte count (an entry is valid where its nbytes equals its index and is not 0); a stream-frame of nb bytes is split over the channels as
+ * R/dec_lc3_fl.c:148 does.  A frame is lost where bfi is 1 or its size is 0 - its size is then not looked at; a flag other than 0 / 1, and a size
+ * that is negative, larger than in_stride or outside the table for any channel of the split, is invalid. */
+#if defined(__HIPCC__)
+#define LC3D_HD __host__ __device__
+#else
+#define LC3D_HD
+#endif
+enum { LC3D_FRAME_GOOD = 0, LC3D_FRAME_LOST = 1, LC3D_FRAME_BAD_FLAG = 2, LC3D_FRAME_BAD_SIZE = 3 };
+#define LC3D_DEC_ST_INVALID 2            /* status bit of lc3plus_dec_batch_decode_sizes_device: concealed because the size or flag was invalid */
+static inline LC3D_HD int lc3d_dec_frame_class(int nb, int bfi, int in_stride, const lc3d_dchan* tab, int tab_n, int channels)
+{
+    if (bfi > 1) return LC3D_FRAME_BAD_FLAG;
+    if (bfi == 1 || nb == 0) return LC3D_FRAME_LOST;
+    if (nb < 0 || nb > in_stride) return LC3D_FRAME_BAD_SIZE;
+    for (int c = 0; c < channels; c++) {
+        const int k = nb / channels + (c < nb % channels);
+        if (k >= tab_n || k == 0 || tab[k].nbytes != k) return LC3D_FRAME_BAD_SIZE;
+    }
+    return LC3D_FRAME_GOOD;
+}
+
 /* decoder state words per channel-stream */
 #define DST_IMEM   0                                   /* 600: IMDCT overlap memory (300 used by the standard layout) */
 #define DST_QPREV  600                                 /* 960: last good spectrum (concealment) */

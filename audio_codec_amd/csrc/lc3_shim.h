@@ -32,6 +32,11 @@ int   lc3hip_dec_upload_table(void* ctx, const lc3d_dchan* tab, int n);      /* 
 int   lc3hip_dec_decode(void* ctx, const void* frames, int frames_on_device, int in_stride, const uint8_t* bfi_flags_host, const uint16_t* sizes_host,
                         int sizes_max_nbytes, int n_frames, void* pcm, int pcm_on_device, int bps, uint8_t* status_host, void* hip_stream, int sync,
                         void* trace_host);
+/* per-frame sizes (and bfi_dev, status_dev: null or) in device memory, as frames and pcm: ordered on hip_stream, does not wait unless sync; the per-stream
+ * configuration on the device follows each stream's last good frame, the host's copy of it is then unknown (lc3hip_dec_download_chans) */
+int   lc3hip_dec_decode_dsizes(void* ctx, const void* frames, int in_stride, const int32_t* num_bytes_dev, const uint8_t* bfi_dev, int n_frames,
+                               void* pcm, int bps, uint8_t* status_dev, void* hip_stream, int sync);
+int   lc3hip_dec_download_chans(void* ctx, lc3d_dchan* chans);    /* waits for the last call, copies the per-channel-stream configuration to chans[ncs] */
 float lc3hip_dec_last_ms(void* ctx);
 int   lc3hip_dec_destroy(void* ctx);
 int   lc3hip_create(void** ctx, const lc3d_plan* plan, int n_streams, int device);

@@ -101,7 +101,8 @@ int lc3plus_enc_batch_record_words(void);
 
 /* ---- batched decoder: n_streams independent decoder instances, one wavefront per channel-stream; same
  * conventions as the encoder batch.  num_bytes[n_streams] = bytes per stream-frame (all channels; may be NULL
- * and set later per stream, or come with the frames: lc3plus_dec_batch_decode_sizes).  R/dec_lc3_fl.c:134-163 is what one (stream, frame) does. ---- */
+ * and set later per stream, or come with the frames: lc3plus_dec_batch_decode_sizes, from host arrays, or
+ * lc3plus_dec_batch_decode_sizes_device, from device memory).  R/dec_lc3_fl.c:134-163 is what one (stream, frame) does. ---- */
 typedef struct lc3plus_dec_batch lc3plus_dec_batch;
 LC3_Error lc3plus_dec_batch_create(lc3plus_dec_batch** batch, int n_streams, int samplerate, int channels,
                                    float frame_ms, int hrmode, const int* num_bytes, int device);
@@ -131,6 +132,25 @@ LC3_Error lc3plus_dec_batch_decode(lc3plus_dec_batch* batch, const void* frames,
 LC3_Error lc3plus_dec_batch_decode_sizes(lc3plus_dec_batch* batch, const void* frames, int frames_on_device, int in_stride,
                                          const int* num_bytes, const uint8_t* bfi, int n_frames, void* pcm, int pcm_on_device,
                                          int bps, uint8_t* status, void* hip_stream, int sync);
+/* Per-frame frame sizes and bad-frame flags in device memory, for receivers whose packets never reach the host.  Every pointer is a device pointer:
+ *   frames    : [n_streams][n_frames][in_stride] bytes
+ *   num_bytes : [n_streams][n_frames] bytes of each stream-frame (all channels); 0 = lost frame
+ *   bfi       : [n_streams][n_frames] flags, or NULL
+ *   pcm       : [n_streams][n_frames][channels][output_samples], int16_t (bps 16) or int32_t (24/32)
+ *   status    : [n_streams][n_frames], or NULL: bit 0 the frame was concealed, bit 1 it was concealed because its size or flag was invalid
+ * The call is queued on hip_stream (NULL = the batch's own stream) in order with the batch's other calls there, and returns at once when sync = 0: it
+ * does not wait, copy synchronously or read anything back.  The arguments are checked on the host before any work - NULL frames, pcm or num_bytes:
+ * LC3_NULL_ERROR; a bad bps, n_frames <= 0 or in_stride <= 0: LC3_ERROR; nothing is queued then.  The frame rule of decode_sizes() holds per stream,
+ * evaluated on the device, with its carry across calls of both kinds - except that a size or flag decode_sizes() refuses does not fail this call: a
+ * size outside the geometry's limits for any channel of the split, larger than in_stride or negative, or a flag other than 0 / 1, makes its frame lost
+ * (concealed, status bit 1; it does not move the carry and its slot is never read).  After the call each stream is configured with its last good size
+ * on the device; the first host-side reader after such calls (num_bytes, set_num_bytes, decode, decode_sizes) waits for the batch's last call and reads
+ * that configuration back, once.  The parser stages frames in LDS up to ceil(in_stride / channels) bytes per channel (the host does not see the
+ * sizes): a tight in_stride keeps the staged parser.  Consecutive calls with sync = 0 on different hip_streams are not ordered with each other.  A call
+ * with more frames than any earlier call, on a batch that already holds smaller buffers, waits once for the device while it grows them. */
+LC3_Error lc3plus_dec_batch_decode_sizes_device(lc3plus_dec_batch* batch, const void* frames, int in_stride, const int32_t* num_bytes,
+                                                const uint8_t* bfi, int n_frames, void* pcm, int bps, uint8_t* status,
+                                                void* hip_stream, int sync);
 float     lc3plus_dec_batch_last_kernel_ms(lc3plus_dec_batch* batch);
 /* checkpoint / resume of the decoders' cross-frame state (overlap-add memory, last good spectrum, LTPF histories, concealment words), as
  * for the encoder batch; the frame sizes are configuration (lc3plus_dec_batch_set_num_bytes), not state */
