@@ -29,6 +29,8 @@ EXPORTS = [
     "lc3plus_dec_batch_num_bytes", "lc3plus_dec_batch_set_num_bytes", "lc3plus_dec_batch_decode",
     "lc3plus_dec_batch_last_kernel_ms", "lc3plus_dec_batch_set_input_ready", "lc3plus_dec_batch_decode_sizes",
     "lc3plus_dec_batch_decode_sizes_device", "lc3plus_enc_batch_encode_bitrates",
+    "lc3plus_enc_batch_stream_state_size", "lc3plus_enc_batch_reset_streams", "lc3plus_enc_batch_export_streams", "lc3plus_enc_batch_import_streams",
+    "lc3plus_dec_batch_stream_state_size", "lc3plus_dec_batch_reset_streams", "lc3plus_dec_batch_export_streams", "lc3plus_dec_batch_import_streams",
 ]
 
 
@@ -70,6 +72,14 @@ def load_library():
             getattr(L, nm + "_state_size").argtypes = [C.c_void_p]; getattr(L, nm + "_state_size").restype = C.c_size_t
             getattr(L, nm + "_get_state").argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
             getattr(L, nm + "_set_state").argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+        for nm in ("lc3plus_enc_batch", "lc3plus_dec_batch"):
+            getattr(L, nm + "_stream_state_size").argtypes = [C.c_void_p]; getattr(L, nm + "_stream_state_size").restype = C.c_size_t
+            getattr(L, nm + "_reset_streams").argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int]
+            getattr(L, nm + "_export_streams").argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int]
+            getattr(L, nm + "_import_streams").argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int]
+        L.lc3plus_stream_list_check.argtypes = [C.c_int, C.c_void_p, C.c_int]
+        L.lc3plus_stream_state_header.argtypes = [C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_void_p]
+        L.lc3plus_stream_header_ok.argtypes = [C.c_void_p, C.c_void_p]
         for f in ("lc3plus_enc_batch_destroy", "lc3plus_enc_batch_input_samples", "lc3plus_enc_batch_stride"):
             getattr(L, f).argtypes = [C.c_void_p]
         L.lc3plus_enc_batch_num_bytes.argtypes = [C.c_void_p, C.c_int]
@@ -107,7 +117,92 @@ def load_library():
     return _LIB
 
 
-class Batch:
+def _stream_list(streams):
+    return np.ascontiguousarray(np.atleast_1d(np.asarray(streams)), dtype=np.int32)
+
+
+class _StreamLifecycle:
+    """Reset, export and import single streams (lc3plus_{enc,dec}_batch_{reset,export,import}_streams; include/lc3plus_batch.h).  Stream lists are host
+    sequences of indices; blobs are stream_state_size bytes per stream."""
+    _ss = None                                                      # C prefix of the batch kind
+
+    def _ssf(self, name):
+        return getattr(self.lib, self._ss + name)
+
+    @property
+    def stream_state_size(self):
+        return int(self._ssf("_stream_state_size")(self.h))
+
+    def _reset(self, streams, config, hip_stream, sync):
+        st = _stream_list(streams)
+        cfg = _stream_list(config) if config is not None else None
+        if cfg is not None and cfg.size != st.size:
+            raise ValueError("one configuration value per listed stream")
+        rc = self._ssf("_reset_streams")(self.h, st.ctypes.data, st.size, cfg.ctypes.data if cfg is not None else None,
+                                          C.c_void_p(hip_stream) if hip_stream else None, 1 if sync else 0)
+        if rc:
+            raise LC3Error(rc, self._ss + "_reset_streams")
+
+    def export_streams(self, streams):
+        """uint8 [n, stream_state_size]: the listed streams' blobs (returns with the data)."""
+        st = _stream_list(streams)
+        blob = np.zeros((st.size, self.stream_state_size), dtype=np.uint8)
+        rc = self._ssf("_export_streams")(self.h, st.ctypes.data, st.size, blob.ctypes.data, 0, None, 1)
+        if rc:
+            raise LC3Error(rc, self._ss + "_export_streams")
+        return blob
+
+    def import_streams(self, streams, blob):
+        """blob: uint8 [n, stream_state_size] from export_streams of a batch of the same codec and geometry (LC3Error where a header differs)."""
+        st = _stream_list(streams)
+        blob = np.ascontiguousarray(blob, dtype=np.uint8)
+        if blob.size != st.size * self.stream_state_size:
+            raise ValueError("blob must hold %d bytes per listed stream" % self.stream_state_size)
+        rc = self._ssf("_import_streams")(self.h, st.ctypes.data, st.size, blob.ctypes.data, 0, None, None, 1)
+        if rc:
+            raise LC3Error(rc, self._ss + "_import_streams")
+
+    def export_streams_device(self, streams, d_ptr, hip_stream=None, sync=False):
+        """The listed streams' blobs into device memory at d_ptr (16-byte aligned, n * stream_state_size bytes), queued on hip_stream."""
+        st = _stream_list(streams)
+        rc = self._ssf("_export_streams")(self.h, st.ctypes.data, st.size, C.c_void_p(d_ptr), 1, C.c_void_p(hip_stream) if hip_stream else None,
+                                           1 if sync else 0)
+        if rc:
+            raise LC3Error(rc, self._ss + "_export_streams(device)")
+
+    def import_streams_device(self, streams, d_ptr, d_status_ptr=None, hip_stream=None, sync=False):
+        """Blobs from device memory at d_ptr; d_status_ptr: device uint8 [n] or None, 1 where a blob's header does not match (that stream is left as it was)."""
+        st = _stream_list(streams)
+        rc = self._ssf("_import_streams")(self.h, st.ctypes.data, st.size, C.c_void_p(d_ptr), 1, C.c_void_p(d_status_ptr) if d_status_ptr else None,
+                                           C.c_void_p(hip_stream) if hip_stream else None, 1 if sync else 0)
+        if rc:
+            raise LC3Error(rc, self._ss + "_import_streams(device)")
+
+
+def stream_list_check(n_streams, streams):
+    """The index-list rule of the lifecycle calls (test hook lc3plus_stream_list_check, no device needed) -> LC3_Error code."""
+    st = _stream_list(streams) if streams is not None else None
+    return load_library().lc3plus_stream_list_check(n_streams, st.ctypes.data if st is not None else None, st.size if st is not None else 0)
+
+
+def stream_state_header(decoder, samplerate, channels, frame_ms, hrmode):
+    """The blob header of a geometry (test hook lc3plus_stream_state_header) -> uint32 [4], or LC3Error where a batch would refuse the geometry."""
+    h = np.zeros(4, np.uint32)
+    rc = load_library().lc3plus_stream_state_header(1 if decoder else 0, samplerate, channels, frame_ms, hrmode, h.ctypes.data)
+    if rc:
+        raise LC3Error(rc, "lc3plus_stream_state_header")
+    return h
+
+
+def stream_header_ok(header, blob):
+    """The header check of an import (test hook lc3plus_stream_header_ok): True where the blob starts with header."""
+    h = np.ascontiguousarray(header, dtype=np.uint32)
+    b = np.ascontiguousarray(blob, dtype=np.uint8)
+    assert h.size == 4 and b.size >= 16
+    return bool(load_library().lc3plus_stream_header_ok(h.ctypes.data, b.ctypes.data))
+
+
+class Batch(_StreamLifecycle):
     """n_streams independent encoders (lc3plus_enc_batch_*), state resident on the GPU between encode() calls."""
 
     def __init__(self, n_streams, samplerate, channels, frame_ms, hrmode, bitrates, device=-1):
@@ -180,6 +275,12 @@ class Batch:
         rc = self.lib.lc3plus_enc_batch_set_input_ready(self.h, 1 if ready else 0)
         if rc:
             raise LC3Error(rc, "lc3plus_enc_batch_set_input_ready")
+
+    _ss = "lc3plus_enc_batch"
+
+    def reset_streams(self, streams, bitrates=None, hip_stream=None, sync=True):
+        """The listed streams start afresh; bitrates: None (configuration kept) or one total bitrate per listed stream."""
+        self._reset(streams, bitrates, hip_stream, sync)
 
     def get_state(self):
         """The cross-frame state of all streams (opaque bytes): checkpoint for set_state() on a batch of the same configuration."""
@@ -358,7 +459,7 @@ def dec_plan_sizes_lenient(samplerate, channels, frame_ms, hrmode, start, num_by
     return rc, eff, lost, inv, end, mx.value
 
 
-class DecBatch:
+class DecBatch(_StreamLifecycle):
     """n_streams independent decoders (lc3plus_dec_batch_*), state resident on the GPU between decode() calls."""
 
     def __init__(self, n_streams, samplerate, channels, frame_ms, hrmode, num_bytes, device=-1):
@@ -372,8 +473,14 @@ class DecBatch:
         self.n_streams, self.channels = n_streams, channels
         self.N = self.lib.lc3plus_dec_batch_output_samples(self.h)
 
+    _ss = "lc3plus_dec_batch"
+
     def num_bytes(self, stream):
         return self.lib.lc3plus_dec_batch_num_bytes(self.h, stream)
+
+    def reset_streams(self, streams, num_bytes=None, hip_stream=None, sync=True):
+        """The listed streams start afresh; num_bytes: None (sizes kept) or one stream-frame size per listed stream."""
+        self._reset(streams, num_bytes, hip_stream, sync)
 
     def set_num_bytes(self, stream, nbytes):
         return self.lib.lc3plus_dec_batch_set_num_bytes(self.h, stream, nbytes)

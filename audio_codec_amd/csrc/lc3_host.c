@@ -298,6 +298,68 @@ static void init_state(float* st, int memcap)                             /* zer
     ((int*)st)[LC3D_S_OLPA_PITCH_WORD(memcap)] = 17;
 }
 
+/* the decoder's counterpart: zeros; ltpf_mem_beta_idx = -1, cum_alpha = 1, PLC seed 24607 (R/setup_dec_lc3.c:170-183) */
+static void dec_init_state(float* st)
+{
+    memset(st, 0, sizeof(float) * DST_WORDS);
+    int* sc = (int*)(st + DST_SCAL);
+    sc[DS_BETA_IDX] = -1; ((float*)sc)[DS_CUM_ALPHA] = 1.0f; sc[DS_PLC_SEED] = 24607;
+}
+
+/* ---- stream lifecycle (lc3plus_{enc,dec}_batch_{reset,export,import}_streams) ---- */
+enum { SS_ENC = 'E', SS_DEC = 'D' };
+/* words of one channel-stream's state row: LC3D_STATE_WORDS of the encoder's kernel layout, DST_WORDS for the decoder */
+static int stream_row_words(int codec, const geom_t* g)
+{
+    return codec == SS_DEC ? DST_WORDS : LC3D_STATE_WORDS(LC3D_LAYOUT_BIG(g->N, g->la) ? LC3D_MEMCAP_BIG : LC3D_MEMCAP_STD);
+}
+/* The header of a stream's blob: "L3S" and the codec, the input sample rate, frame length (ms x 10) | hrmode << 8 | channels << 16, and the row length in
+ * words.  Two batches whose blobs carry the same header have the same state layout. */
+static void stream_header(int codec, const geom_t* g, uint32_t h[4])
+{
+    h[0] = 'L' | '3' << 8 | 'S' << 16 | (uint32_t)codec << 24;
+    h[1] = (uint32_t)g->fs_in;
+    h[2] = (uint32_t)g->dms | (uint32_t)g->hrmode << 8 | (uint32_t)g->channels << 16;
+    h[3] = (uint32_t)stream_row_words(codec, g);
+}
+/* The blob-header rule of an import: a blob is accepted where its first LC3D_SS_HEADER bytes equal the batch's header (the kernel applies the same rule to
+ * device blobs) */
+static int stream_header_ok(const uint32_t want[4], const void* blob) { return memcmp(want, blob, LC3D_SS_HEADER) == 0; }
+static size_t stream_blob_bytes(int codec, const geom_t* g) { return LC3D_SS_HEADER + sizeof(float) * (size_t)g->channels * stream_row_words(codec, g); }
+/* The index-list rule of the lifecycle calls: a list, n >= 1, every index in [0, n_streams) and none twice.  Returns an LC3_Error. */
+static LC3_Error stream_list_check(int n_streams, const int* streams, int n)
+{
+    if (!streams) return LC3_NULL_ERROR;
+    if (n <= 0 || n_streams <= 0) return LC3_ERROR;
+    uint8_t* seen = (uint8_t*)calloc(((size_t)n_streams + 7) / 8, 1);
+    if (!seen) return LC3_ERROR;
+    LC3_Error e = LC3_OK;
+    for (int i = 0; i < n && !e; i++) {
+        const int s = streams[i];
+        if (s < 0 || s >= n_streams || (seen[s >> 3] >> (s & 7) & 1)) e = LC3_ERROR;
+        else seen[s >> 3] |= (uint8_t)(1 << (s & 7));
+    }
+    free(seen);
+    return e;
+}
+/* the argument checks every export / import shares, before any work */
+static LC3_Error stream_blob_check(int n_streams, const int* streams, int n, const void* blob, int blob_on_device)
+{
+    if (!blob) return LC3_NULL_ERROR;
+    LC3_Error e = stream_list_check(n_streams, streams, n);
+    if (e) return e;
+    return blob_on_device && ((uintptr_t)blob & 15) ? LC3_ERROR : LC3_OK;
+}
+/* host blobs: every header checked before anything is queued */
+static LC3_Error stream_import_host_check(int codec, const geom_t* g, const void* blob, int n)
+{
+    uint32_t h[4];
+    stream_header(codec, g, h);
+    const size_t sz = stream_blob_bytes(codec, g);
+    for (int i = 0; i < n; i++) if (!stream_header_ok(h, (const uint8_t*)blob + (size_t)i * sz)) return LC3_ERROR;
+    return LC3_OK;
+}
+
 /* ------------------------------------------------------------------------------------------------ */
 /* batch object                                                                                      */
 /* ------------------------------------------------------------------------------------------------ */
@@ -359,7 +421,7 @@ LC3_Error lc3plus_enc_batch_create(lc3plus_batch** out, int n_streams, int sampl
     init_state(st, LC3D_LAYOUT_BIG(b->g.N, b->g.la) ? LC3D_MEMCAP_BIG : LC3D_MEMCAP_STD);
     int rc = lc3hip_create(&b->dev, plan, n_streams, device);
     free(plan);
-    if (!rc) rc = lc3hip_reset_state(b->dev, st);
+    if (!rc) rc = lc3hip_set_template(b->dev, st);
     if (!rc) rc = batch_upload(b, 0, n_streams) != LC3_OK;
     if (!rc) { int tab_n = 0; lc3d_chan* tab = enc_build_table(&b->g, &tab_n); rc = !tab || lc3hip_upload_enc_table(b->dev, tab, tab_n); free(tab); }
     if (rc) { if (b->dev) lc3hip_destroy(b->dev); free(b->chans); free(b->bitrates); free(b); return LC3_ERROR; }
@@ -542,6 +604,61 @@ LC3_Error lc3plus_enc_batch_set_state(lc3plus_batch* b, const void* state, size_
 {
     if (!b || !state) return LC3_NULL_ERROR;
     return lc3hip_set_state(b->dev, state, size) ? LC3_ERROR : LC3_OK;
+}
+
+size_t lc3plus_enc_batch_stream_state_size(const lc3plus_batch* b) { return b ? stream_blob_bytes(SS_ENC, &b->g) : 0; }
+LC3_Error lc3plus_enc_batch_reset_streams(lc3plus_batch* b, const int* streams, int n, const int* bitrates, void* hip_stream, int sync)
+{
+    if (!b) return LC3_NULL_ERROR;
+    LC3_Error e = stream_list_check(b->n_streams, streams, n);
+    if (e) return e;
+    const int C = b->g.channels;
+    lc3d_chan* cfg = NULL;
+    if (bitrates) {                             /* as set_bitrate configures a stream, every rate checked first; the bandwidth is kept */
+        cfg = (lc3d_chan*)malloc(sizeof(lc3d_chan) * (size_t)n * C);
+        if (!cfg) return LC3_ERROR;
+        for (int i = 0; i < n && !e; i++) {
+            lc3d_chan* ch = cfg + (size_t)i * C;
+            memcpy(ch, b->chans + (size_t)streams[i] * C, sizeof(lc3d_chan) * C);
+            e = bitrates[i] <= 0 ? LC3_BITRATE_ERROR : derive_bitrate(&b->g, bitrates[i], ch);
+            for (int c = 0; c < C; c++) ch[c].reset_attack = 0;           /* the fresh attack detector is clear already */
+        }
+        if (e) { free(cfg); return e; }
+    }
+    uint32_t h[4];
+    stream_header(SS_ENC, &b->g, h);
+    if (lc3hip_stream_state(b->dev, LC3D_SS_RESET, streams, n, cfg, NULL, 0, h, NULL, hip_stream, sync)) { free(cfg); return LC3_ERROR; }
+    if (cfg) {
+        for (int i = 0; i < n; i++) {
+            memcpy(b->chans + (size_t)streams[i] * C, cfg + (size_t)i * C, sizeof(lc3d_chan) * C);
+            b->bitrates[streams[i]] = bitrates[i];
+        }
+        batch_restride(b);
+        free(cfg);
+    }
+    return LC3_OK;
+}
+LC3_Error lc3plus_enc_batch_export_streams(lc3plus_batch* b, const int* streams, int n, void* blob, int blob_on_device, void* hip_stream, int sync)
+{
+    if (!b) return LC3_NULL_ERROR;
+    LC3_Error e = stream_blob_check(b->n_streams, streams, n, blob, blob_on_device);
+    if (e) return e;
+    uint32_t h[4];
+    stream_header(SS_ENC, &b->g, h);
+    return lc3hip_stream_state(b->dev, LC3D_SS_EXPORT, streams, n, NULL, blob, blob_on_device, h, NULL, hip_stream, sync) ? LC3_ERROR : LC3_OK;
+}
+LC3_Error lc3plus_enc_batch_import_streams(lc3plus_batch* b, const int* streams, int n, const void* blob, int blob_on_device, uint8_t* status,
+                                           void* hip_stream, int sync)
+{
+    if (!b) return LC3_NULL_ERROR;
+    LC3_Error e = stream_blob_check(b->n_streams, streams, n, blob, blob_on_device);
+    if (!e && !blob_on_device) e = stream_import_host_check(SS_ENC, &b->g, blob, n);
+    if (e) return e;
+    uint32_t h[4];
+    stream_header(SS_ENC, &b->g, h);
+    if (lc3hip_stream_state(b->dev, LC3D_SS_IMPORT, streams, n, NULL, (void*)blob, blob_on_device, h, status, hip_stream, sync)) return LC3_ERROR;
+    if (status && !blob_on_device) memset(status, 0, (size_t)n);
+    return LC3_OK;
 }
 
 LC3_Error lc3plus_enc_batch_set_input_ready(lc3plus_batch* b, int ready)
@@ -879,7 +996,9 @@ LC3_Error lc3plus_dec_batch_create(lc3plus_dec_batch** out, int n_streams, int s
     lc3d_plan* plan = (lc3d_plan*)malloc(sizeof *plan);
     if (!plan) { free(b->chans); free(b); return LC3_ERROR; }
     build_plan(&b->g, plan);
-    int rc = lc3hip_dec_create(&b->dev, plan, n_streams, device);
+    float st[DST_WORDS];
+    dec_init_state(st);
+    int rc = lc3hip_dec_create(&b->dev, plan, st, n_streams, device);
     free(plan);
     if (!rc) rc = lc3hip_dec_upload_chans(b->dev, b->chans, 0, n_streams * channels);
     if (!rc) { b->tab = dec_build_table(&b->g, &b->tab_n); rc = !b->tab || lc3hip_dec_upload_table(b->dev, b->tab, b->tab_n); }
@@ -1005,6 +1124,74 @@ LC3_Error lc3plus_dec_batch_decode_sizes_device(lc3plus_dec_batch* b, const void
     b->chans_stale = 1;
     return LC3_OK;
 }
+size_t lc3plus_dec_batch_stream_state_size(const lc3plus_dec_batch* b) { return b ? stream_blob_bytes(SS_DEC, &b->g) : 0; }
+LC3_Error lc3plus_dec_batch_reset_streams(lc3plus_dec_batch* b, const int* streams, int n, const int* num_bytes, void* hip_stream, int sync)
+{
+    if (!b) return LC3_NULL_ERROR;
+    LC3_Error e = stream_list_check(b->n_streams, streams, n);
+    if (e) return e;
+    const int C = b->g.channels;
+    lc3d_dchan* cfg = NULL;
+    if (num_bytes) {                            /* as set_num_bytes configures a stream, every size checked first */
+        cfg = (lc3d_dchan*)calloc((size_t)n * C, sizeof(lc3d_dchan));
+        if (!cfg) return LC3_ERROR;
+        for (int i = 0; i < n && !e; i++) e = derive_dstream(&b->g, num_bytes[i], cfg + (size_t)i * C);
+        if (e) { free(cfg); return e; }
+    }
+    uint32_t h[4];
+    stream_header(SS_DEC, &b->g, h);
+    /* no dec_refresh: the configuration is written on the device, in order; a stale host copy stays stale and is read back by the next host-side reader */
+    if (lc3hip_dec_stream_state(b->dev, LC3D_SS_RESET, streams, n, cfg, NULL, 0, h, NULL, hip_stream, sync)) { free(cfg); return LC3_ERROR; }
+    if (cfg && !b->chans_stale)
+        for (int i = 0; i < n; i++) memcpy(b->chans + (size_t)streams[i] * C, cfg + (size_t)i * C, sizeof(lc3d_dchan) * C);
+    free(cfg);
+    return LC3_OK;
+}
+LC3_Error lc3plus_dec_batch_export_streams(lc3plus_dec_batch* b, const int* streams, int n, void* blob, int blob_on_device, void* hip_stream, int sync)
+{
+    if (!b) return LC3_NULL_ERROR;
+    LC3_Error e = stream_blob_check(b->n_streams, streams, n, blob, blob_on_device);
+    if (e) return e;
+    uint32_t h[4];
+    stream_header(SS_DEC, &b->g, h);
+    return lc3hip_dec_stream_state(b->dev, LC3D_SS_EXPORT, streams, n, NULL, blob, blob_on_device, h, NULL, hip_stream, sync) ? LC3_ERROR : LC3_OK;
+}
+LC3_Error lc3plus_dec_batch_import_streams(lc3plus_dec_batch* b, const int* streams, int n, const void* blob, int blob_on_device, uint8_t* status,
+                                           void* hip_stream, int sync)
+{
+    if (!b) return LC3_NULL_ERROR;
+    LC3_Error e = stream_blob_check(b->n_streams, streams, n, blob, blob_on_device);
+    if (!e && !blob_on_device) e = stream_import_host_check(SS_DEC, &b->g, blob, n);
+    if (e) return e;
+    uint32_t h[4];
+    stream_header(SS_DEC, &b->g, h);
+    if (lc3hip_dec_stream_state(b->dev, LC3D_SS_IMPORT, streams, n, NULL, (void*)blob, blob_on_device, h, status, hip_stream, sync)) return LC3_ERROR;
+    if (status && !blob_on_device) memset(status, 0, (size_t)n);
+    return LC3_OK;
+}
+/* test hooks of the lifecycle rules, without a device: the index-list rule; the blob header of a geometry (decoder != 0: the decoder's; the checks of the
+ * batch's create, LC3_ERROR where the kernels do not support the geometry); the header check of an import */
+LC3_Error lc3plus_stream_list_check(int n_streams, const int* streams, int n) { return stream_list_check(n_streams, streams, n); }
+LC3_Error lc3plus_stream_state_header(int decoder, int samplerate, int channels, float frame_ms, int hrmode, uint32_t* header)
+{
+    if (!header) return LC3_NULL_ERROR;
+    if (!samplerate_ok(samplerate)) return LC3_SAMPLERATE_ERROR;
+    if (channels < 1 || channels > MAX_CH) return LC3_CHANNELS_ERROR;
+    { int d = (int)ceil(frame_ms * 10); if (d != 25 && d != 50 && d != 100) return LC3_FRAMEMS_ERROR; }
+    geom_t g;
+    geom_init(&g, samplerate, channels);
+    if (decoder) {
+        if (g.fs_idx < 4 && hrmode != 0) return LC3_SAMPLERATE_ERROR;
+        if (g.fs_idx == 5 && hrmode == 0) return LC3_HRMODE_ERROR;
+    } else if (samplerate < 48000 && hrmode != 0) return LC3_SAMPLERATE_ERROR;
+    g.dms = (int)(frame_ms * 10); g.frame_ms = frame_ms; g.hrmode = hrmode > 0;
+    geom_update_ex(&g, decoder != 0);
+    if (!geom_supported(&g)) return LC3_ERROR;
+    stream_header(decoder ? SS_DEC : SS_ENC, &g, header);
+    return LC3_OK;
+}
+int lc3plus_stream_header_ok(const uint32_t* header, const void* blob) { return header && blob && stream_header_ok(header, blob); }
+
 /* test hooks: dec_plan_sizes and dec_plan_sizes_lenient for a geometry, without a device (the batch builds the same table at create) */
 static LC3_Error dec_hook_table(int samplerate, int channels, float frame_ms, int hrmode, geom_t* g, lc3d_dchan** tab, int* tab_n)
 {

@@ -3010,6 +3010,53 @@ static void read_opts(lc3hip_opts* o)
     o->check_ready = env_int("LC3PLUS_CHECK_READY", 0, 1, 0);        /* debug aid for lc3plus_enc_batch_set_input_ready: refuse a call made while foreign work is pending on the caller's stream */
     o->dec_imdct4 = env_int("LC3PLUS_DEC_IMDCT4", 0, 1, 1);          /* 0 = the one-frame-at-a-time IMDCT for N = 480 too */
 }
+/* ---- stream lifecycle: one kernel for the encoder and the decoder (include/lc3plus_batch.h: lc3plus_{enc,dec}_batch_{reset,export,import}_streams) ----
+ * LC3D_SS_RESET : the listed channel-streams' state rows <- the batch's fresh-row template, and with cfg their configuration entries <- cfg [n][channels]
+ * LC3D_SS_EXPORT: the listed streams' rows -> blob i (LC3D_SS_HEADER bytes of header h0..h3, then the stream's rows, channel 0 first), back to back in list order
+ * LC3D_SS_IMPORT: blob i -> the rows of stream list[i] where its header equals h0..h3; status[i] = 1 and the stream untouched where it does not
+ * One wave per channel row.  A row is 240 (encoder), 315 (encoder, large layout) or 614 (decoder) 16-byte chunks: four to ten dwordx4 loads and stores per
+ * lane, enough to keep a wave's memory pipeline busy, and the rows of a stereo stream are independent.  A workgroup per stream would only add a barrier for
+ * the header decision, which the wave of each row takes from its own lane 0.  list null: stream i (create).  Rows, template and blobs are 16-byte aligned
+ * (row lengths are multiples of 4 words; the host checks a device blob's address). */
+extern "C" __global__ void __launch_bounds__(WAVE) lc3_stream_state_kernel(int mode, float* __restrict__ state, int row_words, int channels, const int* __restrict__ list,
+                                                                           int n, const float* __restrict__ tmpl, uint8_t* __restrict__ blob, uint32_t h0, uint32_t h1,
+                                                                           uint32_t h2, uint32_t h3, uint8_t* __restrict__ status, const uint32_t* __restrict__ cfg,
+                                                                           uint32_t* __restrict__ chans, int cfg_words)
+{
+    const int lane = threadIdx.x;
+    const int i = (int)(blockIdx.x / (unsigned)channels), ch = (int)(blockIdx.x % (unsigned)channels);
+    if (i >= n) return;
+    const size_t cs = (size_t)(list ? list[i] : i) * channels + ch;
+    float4* row = (float4*)(state + cs * row_words);
+    const int n4 = row_words >> 2;
+    if (mode == LC3D_SS_RESET) {
+        const float4* t4 = (const float4*)tmpl;
+        for (int k = lane; k < n4; k += WAVE) row[k] = t4[k];
+        if (cfg) for (int k = lane; k < cfg_words; k += WAVE) chans[cs * cfg_words + k] = cfg[((size_t)i * channels + ch) * cfg_words + k];
+        return;
+    }
+    uint8_t* b = blob + (size_t)i * (LC3D_SS_HEADER + (size_t)channels * row_words * 4);
+    float4* brow = (float4*)(b + LC3D_SS_HEADER + (size_t)ch * row_words * 4);
+    if (mode == LC3D_SS_EXPORT) {
+        if (ch == 0 && lane == 0) *(uint4*)b = make_uint4(h0, h1, h2, h3);
+        for (int k = lane; k < n4; k += WAVE) brow[k] = row[k];
+        return;
+    }
+    int ok = 0;                                                       /* import: lane 0 reads the header and decides, the wave follows before it writes */
+    if (lane == 0) { const uint4 h = *(const uint4*)b; ok = h.x == h0 && h.y == h1 && h.z == h2 && h.w == h3; }
+    ok = __builtin_amdgcn_readfirstlane(ok);
+    if (status && ch == 0 && lane == 0) status[i] = ok ? 0 : 1;
+    if (!ok) return;
+    for (int k = lane; k < n4; k += WAVE) row[k] = brow[k];
+}
+/* What a batch keeps for those calls: the fresh-row template, and LC3D_SETS staging slots (pinned host memory for the index list, configuration entries and
+ * host blobs, and its device copy) used in turn, each guarded by the event recorded behind the call that used it last; ev_done: behind the last call, for
+ * later calls on other streams */
+struct lc3hip_ss {
+    float* d_tmpl; int row_words;
+    uint8_t* h[LC3D_SETS]; uint8_t* d[LC3D_SETS]; size_t cap[LC3D_SETS]; hipEvent_t ev[LC3D_SETS]; int armed[LC3D_SETS], k;
+    hipEvent_t ev_prev, ev_done; int done_armed;
+};
 struct lc3hip_ctx {
     lc3hip_opts opt;
     int device, ncs, n_streams, channels, N, big, state_words, rs48, rs96;
@@ -3032,8 +3079,9 @@ struct lc3hip_ctx {
      * staging, in LC3D_SETS rotating buffers (a buffer is written again once the call that read it has finished: calls with sync = 0) */
     lc3d_chan* d_etab; uint16_t* d_fsz[LC3D_SETS]; uint16_t* h_fsz[LC3D_SETS]; size_t fsz_cap; hipEvent_t ev_fsz[LC3D_SETS]; int fsz_armed[LC3D_SETS], fsz_set;
     /* lc3hip_upload_chans_async: the configuration a per-frame-bitrate call leaves, queued on its stream behind its kernels from pinned staging; every later
-     * call waits for the copy (ev_chans) on its own stream */
+     * call waits for the copy (ev_chans) on its own stream - and for the last stream-lifecycle call (lc3hip_stream_state), which records the same event */
     lc3d_chan* h_chans; hipEvent_t ev_chans; int chans_armed;
+    lc3hip_ss ss;                                   /* lc3hip_set_template, lc3hip_stream_state */
 };
 
 #define LC3D_FUSED_MAX_T 8
@@ -3041,6 +3089,64 @@ struct lc3hip_ctx {
 #define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { fprintf(stderr, "lc3plus_hip: %s failed: %s (%s:%d)\n", #x, hipGetErrorString(e_), __FILE__, __LINE__); return 1; } } while (0)
 /* inside the create functions: release what has been allocated so far (the caller only sees ctx == NULL) */
 #define HIPCHK_OR(x, cleanup) do { hipError_t e_ = (x); if (e_ != hipSuccess) { fprintf(stderr, "lc3plus_hip: %s failed: %s (%s:%d)\n", #x, hipGetErrorString(e_), __FILE__, __LINE__); cleanup; return 1; } } while (0)
+static size_t ss_up(size_t x) { return (x + 255) & ~(size_t)255; }
+/* the template to the device, and every row of the batch reset from it (create) */
+static int ss_init(lc3hip_ss* q, int device, float* state, int row_words, int ncs, const float* tmpl)
+{
+    HIPCHK(hipSetDevice(device));
+    q->row_words = row_words;
+    HIPCHK(hipMalloc((void**)&q->d_tmpl, sizeof(float) * (size_t)row_words));
+    HIPCHK(hipMemcpy(q->d_tmpl, tmpl, sizeof(float) * (size_t)row_words, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(lc3_stream_state_kernel, dim3((unsigned)ncs), dim3(WAVE), 0, (hipStream_t)0, (int)LC3D_SS_RESET, state, row_words, 1, (const int*)nullptr, ncs,
+                       (const float*)q->d_tmpl, (uint8_t*)nullptr, 0u, 0u, 0u, 0u, (uint8_t*)nullptr, (const uint32_t*)nullptr, (uint32_t*)nullptr, 0);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize((hipStream_t)0));
+    return 0;
+}
+static void ss_free(lc3hip_ss* q)
+{
+    if (q->d_tmpl) hipFree(q->d_tmpl);
+    for (int i = 0; i < LC3D_SETS; i++) { if (q->h[i]) hipHostFree(q->h[i]); if (q->d[i]) hipFree(q->d[i]); if (q->ev[i]) hipEventDestroy(q->ev[i]); }
+    if (q->ev_prev) { hipEventDestroy(q->ev_prev); hipEventDestroy(q->ev_done); }
+}
+/* one lifecycle call on stream s, behind `last` (the stream of the batch's last call); cfg_bytes: bytes of one configuration entry */
+static int ss_run(lc3hip_ss* q, hipStream_t s, hipStream_t last, int mode, float* state, int channels, const int* list, int n, const void* cfg, int cfg_bytes,
+                  void* chans, void* blob, int blob_on_device, const uint32_t* hdr, uint8_t* status, int sync)
+{
+    if (!q->ev_prev) {
+        HIPCHK(hipEventCreateWithFlags(&q->ev_prev, hipEventDisableTiming)); HIPCHK(hipEventCreateWithFlags(&q->ev_done, hipEventDisableTiming));
+        for (int i = 0; i < LC3D_SETS; i++) HIPCHK(hipEventCreateWithFlags(&q->ev[i], hipEventDisableTiming));
+    }
+    const size_t blob_bytes = (size_t)n * (LC3D_SS_HEADER + (size_t)channels * q->row_words * 4);
+    const size_t o_cfg = ss_up(sizeof(int) * (size_t)n), n_cfg = cfg ? (size_t)n * channels * cfg_bytes : 0;
+    const size_t o_blob = o_cfg + ss_up(n_cfg), need = o_blob + (blob_on_device ? 0 : blob_bytes);
+    const int k = q->k;
+    if (q->armed[k]) { HIPCHK(hipEventSynchronize(q->ev[k])); q->armed[k] = 0; }      /* the call LC3D_SETS back has read this slot */
+    if (q->cap[k] < need) {
+        if (q->h[k]) HIPCHK(hipHostFree(q->h[k])); if (q->d[k]) HIPCHK(hipFree(q->d[k]));
+        q->h[k] = nullptr; q->d[k] = nullptr; q->cap[k] = 0;
+        const size_t cap = need < (64u << 10) ? (64u << 10) : need;
+        HIPCHK(hipHostMalloc((void**)&q->h[k], cap, hipHostMallocDefault)); HIPCHK(hipMalloc((void**)&q->d[k], cap));
+        q->cap[k] = cap;
+    }
+    memcpy(q->h[k], list, sizeof(int) * (size_t)n);
+    if (cfg) memcpy(q->h[k] + o_cfg, cfg, n_cfg);
+    if (mode == LC3D_SS_IMPORT && !blob_on_device) memcpy(q->h[k] + o_blob, blob, blob_bytes);
+    if (last && last != s) { HIPCHK(hipEventRecord(q->ev_prev, last)); HIPCHK(hipStreamWaitEvent(s, q->ev_prev, 0)); }
+    HIPCHK(hipMemcpyAsync(q->d[k], q->h[k], mode == LC3D_SS_IMPORT && !blob_on_device ? o_blob + blob_bytes : o_blob, hipMemcpyHostToDevice, s));
+    uint8_t* dblob = blob_on_device ? (uint8_t*)blob : q->d[k] + o_blob;
+    hipLaunchKernelGGL(lc3_stream_state_kernel, dim3((unsigned)((size_t)n * channels)), dim3(WAVE), 0, s, mode, state, q->row_words, channels, (const int*)q->d[k], n,
+                       (const float*)q->d_tmpl, dblob, hdr[0], hdr[1], hdr[2], hdr[3], blob_on_device ? status : (uint8_t*)nullptr,
+                       (const uint32_t*)(cfg ? q->d[k] + o_cfg : nullptr), (uint32_t*)chans, cfg_bytes / 4);
+    HIPCHK(hipGetLastError());
+    if (mode == LC3D_SS_EXPORT && !blob_on_device) HIPCHK(hipMemcpyAsync(q->h[k] + o_blob, dblob, blob_bytes, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipEventRecord(q->ev[k], s)); q->armed[k] = 1; q->k = (k + 1) % LC3D_SETS;
+    HIPCHK(hipEventRecord(q->ev_done, s)); q->done_armed = 1;
+    if (mode == LC3D_SS_EXPORT && !blob_on_device) { HIPCHK(hipStreamSynchronize(s)); memcpy(blob, q->h[k] + o_blob, blob_bytes); }
+    else if (sync) HIPCHK(hipStreamSynchronize(s));
+    return 0;
+}
+
 
 /* test hook (tests/test_gpu_parity.py::test_device_fastmath_equals_host): lc3_fastmath.h as the kernels evaluate it, over an array.  kind 0 log2, 1 log10, 2 2^x */
 extern "C" __global__ void lc3_fastmath_test_kernel(int kind, const float* __restrict__ x, float* __restrict__ y, long long n)
@@ -3095,17 +3201,10 @@ extern "C" int lc3hip_create(void** out_ctx, const lc3d_plan* plan, int n_stream
     return 0;
 }
 
-extern "C" int lc3hip_reset_state(void* ctx, const float* init_state_one /* LC3D_STATE_WORDS floats */)
+extern "C" int lc3hip_set_template(void* ctx, const float* tmpl)
 {
     lc3hip_ctx* c = (lc3hip_ctx*)ctx;
-    HIPCHK(hipSetDevice(c->device));
-    const size_t sw = (size_t)c->state_words;
-    float* h = (float*)malloc(sizeof(float) * sw * (size_t)c->ncs);
-    if (!h) return 1;
-    for (int i = 0; i < c->ncs; i++) memcpy(h + (size_t)i * sw, init_state_one, sizeof(float) * sw);
-    hipError_t e = hipMemcpy(c->d_state, h, sizeof(float) * sw * (size_t)c->ncs, hipMemcpyHostToDevice);
-    free(h);
-    HIPCHK(e);
+    if (ss_init(&c->ss, c->device, c->d_state, c->state_words, c->ncs, tmpl)) return 1;
     c->ahead_ok = 0;                       /* the MDCT memory is in the state again, not in the hand-over of a previous call */
     return 0;
 }
@@ -3116,10 +3215,8 @@ extern "C" int lc3hip_upload_chans_async(void* ctx, const lc3d_chan* chans, int 
     lc3hip_ctx* c = (lc3hip_ctx*)ctx;
     HIPCHK(hipSetDevice(c->device));
     hipStream_t s = hip_stream ? (hipStream_t)hip_stream : c->stream;
-    if (!c->h_chans) {
-        HIPCHK(hipHostMalloc((void**)&c->h_chans, sizeof(lc3d_chan) * (size_t)c->ncs, hipHostMallocDefault));
-        HIPCHK(hipEventCreateWithFlags(&c->ev_chans, hipEventDisableTiming));
-    }
+    if (!c->h_chans) HIPCHK(hipHostMalloc((void**)&c->h_chans, sizeof(lc3d_chan) * (size_t)c->ncs, hipHostMallocDefault));
+    if (!c->ev_chans) HIPCHK(hipEventCreateWithFlags(&c->ev_chans, hipEventDisableTiming));
     if (c->chans_armed) HIPCHK(hipEventSynchronize(c->ev_chans));      /* the staging of the previous copy is free */
     memcpy(c->h_chans + first, chans, sizeof(lc3d_chan) * (size_t)count);
     HIPCHK(hipMemcpyAsync(c->d_chans + first, c->h_chans + first, sizeof(lc3d_chan) * (size_t)count, hipMemcpyHostToDevice, s));
@@ -3138,21 +3235,24 @@ extern "C" int lc3hip_upload_chans(void* ctx, const lc3d_chan* chans, int first,
     HIPCHK(hipMemcpy(c->d_chans + first, chans, sizeof(lc3d_chan) * count, hipMemcpyHostToDevice));
     return chans_host_side(c, chans, first, count);
 }
-/* what the launch decisions read of the configuration, on the host */
-static int chans_host_side(lc3hip_ctx* c, const lc3d_chan* chans, int first, int count)
+/* what the launch decisions read of the configuration, on the host: channel-streams first ... first + count - 1, or with list the channels of streams list[0 .. count / channels - 1] */
+static int chans_host_side_list(lc3hip_ctx* c, const lc3d_chan* chans, int first, int count, const int* list)
 {
-    /* streams with attack handling need lc3_enc_attack_kernel between the front and the quantiser */
     if (!c->h_attack) { c->h_attack = (uint8_t*)calloc((size_t)c->ncs, 1); if (!c->h_attack) return 1; }
-    for (int i = 0; i < count; i++) c->h_attack[first + i] = chans[i].attack_handling != 0 || chans[i].reset_attack != 0;   /* a pending reset needs the kernel too */
+    if (!c->h_nb) { c->h_nb = (int*)calloc((size_t)c->ncs, sizeof(int)); if (!c->h_nb) return 1; }
+    for (int i = 0; i < count; i++) {
+        const int cs = list ? list[i / c->channels] * c->channels + i % c->channels : first + i;
+        c->h_attack[cs] = chans[i].attack_handling != 0 || chans[i].reset_attack != 0;     /* streams with attack handling need lc3_enc_attack_kernel; a pending reset too */
+        c->h_nb[cs] = chans[i].nbytes;
+    }
     c->any_attack = 0;
     for (int i = 0; i < c->ncs; i++) c->any_attack |= c->h_attack[i];
     /* mean frame size: decides where the rate chain runs (enc_launch) */
-    if (!c->h_nb) { c->h_nb = (int*)calloc((size_t)c->ncs, sizeof(int)); if (!c->h_nb) return 1; }
-    for (int i = 0; i < count; i++) c->h_nb[first + i] = chans[i].nbytes;
     { long long sum = 0; int mn = 1 << 30, mx = 0; for (int i = 0; i < c->ncs; i++) { sum += c->h_nb[i]; if (c->h_nb[i] < mn) mn = c->h_nb[i]; if (c->h_nb[i] > mx) mx = c->h_nb[i]; }
       c->mean_nbytes = (int)(sum / (c->ncs > 0 ? c->ncs : 1)); c->min_nbytes = mn; c->max_nbytes = mx; }
     return 0;
 }
+static int chans_host_side(lc3hip_ctx* c, const lc3d_chan* chans, int first, int count) { return chans_host_side_list(c, chans, first, count, nullptr); }
 
 /* the kernels of one call (or of one run of frames of a call) on stream s, PCM and output in device memory.  n_frames frames from
  * dpcm [stream][n_frames][channel][N]; the hand-over records and status bytes are rows of dT frames per channel-stream in which this
@@ -3666,6 +3766,26 @@ extern "C" int lc3hip_set_state(void* ctx, const void* host, size_t bytes)
     return 0;
 }
 
+extern "C" int lc3hip_stream_state(void* ctx, int mode, const int* streams, int n, const lc3d_chan* cfg, void* blob, int blob_on_device, const uint32_t* hdr,
+                                   uint8_t* status, void* hip_stream, int sync)
+{
+    lc3hip_ctx* c = (lc3hip_ctx*)ctx;
+    HIPCHK(hipSetDevice(c->device));
+    if (!hip_stream && !c->stream) HIPCHK(hipStreamCreate(&c->stream));
+    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : c->stream;
+    /* behind the batch's last call: on its stream the writer, and the rate chain of a pipelined call, whose last rate kernel has written the MDCT memory
+     * into the state (the side streams carry nothing of that call's state work beyond it); behind a configuration copy queued on another stream */
+    if (c->chans_armed) HIPCHK(hipStreamWaitEvent(s, c->ev_chans, 0));
+    if (ss_run(&c->ss, s, c->last_stream, mode, c->d_state, c->channels, streams, n, cfg, (int)sizeof(lc3d_chan), c->d_chans, blob, blob_on_device, hdr, status, sync)) return 1;
+    /* every later call waits for this one on its own stream (ev_chans: encode, the configuration copies); the next call does not read the MDCT memory from a
+     * hand-over, and starts its side streams behind this call */
+    if (!c->ev_chans) HIPCHK(hipEventCreateWithFlags(&c->ev_chans, hipEventDisableTiming));
+    HIPCHK(hipEventRecord(c->ev_chans, s)); c->chans_armed = 1;
+    c->ahead_ok = 0;
+    c->last_stream = s;
+    return cfg ? chans_host_side_list(c, cfg, 0, n * c->channels, streams) : 0;
+}
+
 extern "C" int lc3hip_set_input_ready(void* ctx, int ready)
 {
     lc3hip_ctx* c = (lc3hip_ctx*)ctx;
@@ -3700,7 +3820,9 @@ extern "C" int lc3hip_destroy(void* ctx)
     for (int i = 0; i < LC3D_SETS + 1; i++) if (c->d_xnext[i]) hipFree(c->d_xnext[i]);
     free(c->h_attack); free(c->h_nb);
     if (c->d_etab) hipFree(c->d_etab);
-    if (c->h_chans) { hipHostFree(c->h_chans); hipEventDestroy(c->ev_chans); }
+    if (c->h_chans) hipHostFree(c->h_chans);
+    if (c->ev_chans) hipEventDestroy(c->ev_chans);
+    ss_free(&c->ss);
     for (int i = 0; i < LC3D_SETS; i++) { if (c->d_fsz[i]) hipFree(c->d_fsz[i]); if (c->h_fsz[i]) hipHostFree(c->h_fsz[i]); if (c->ev_fsz[i]) hipEventDestroy(c->ev_fsz[i]); }
     for (int i = 0; i < 2; i++) {
         if (c->hp_dpcm[i]) hipFree(c->hp_dpcm[i]);
@@ -3743,6 +3865,7 @@ struct lc3hip_dctx {
     int input_ready, set; int* d_recx[DEC_SETS - 1]; float* d_wsx[DEC_SETS - 1]; size_t handx_cap; hipStream_t s_par, s_plc; hipEvent_t ev_par[DEC_SETS], ev_free[DEC_SETS], ev_plc; int free_armed[DEC_SETS];
     /* the end of the last ordered call (bad-frame flags, per-frame sizes, status, host pointers) under the promise: the next parse-ahead waits for it */
     hipEvent_t ev_ord; int ord_pending;
+    lc3hip_ss ss;                                   /* the fresh-row template, lc3hip_dec_stream_state */
 };
 static int dec_side_streams(lc3hip_dctx* c)                       /* the parse-ahead stream, the concealment stream and their events, created once */
 {
@@ -3754,7 +3877,7 @@ static int dec_side_streams(lc3hip_dctx* c)                       /* the parse-a
     return 0;
 }
 extern "C" int lc3hip_dec_destroy(void* ctx);
-extern "C" int lc3hip_dec_create(void** out_ctx, const lc3d_plan* plan, int n_streams, int device)
+extern "C" int lc3hip_dec_create(void** out_ctx, const lc3d_plan* plan, const float* tmpl, int n_streams, int device)
 {
     int ndev = 0;
     *out_ctx = nullptr;
@@ -3771,17 +3894,7 @@ extern "C" int lc3hip_dec_create(void** out_ctx, const lc3d_plan* plan, int n_st
     HIPCHK_OR(hipMemcpy(c->d_plan, plan, sizeof(lc3d_plan), hipMemcpyHostToDevice), lc3hip_dec_destroy(c));
     HIPCHK_OR(hipMalloc((void**)&c->d_chans, sizeof(lc3d_dchan) * c->ncs), lc3hip_dec_destroy(c));
     HIPCHK_OR(hipMalloc((void**)&c->d_state, sizeof(float) * DST_WORDS * (size_t)c->ncs), lc3hip_dec_destroy(c));
-    {   /* initial state: zeros; ltpf_mem_beta_idx = -1, cum_alpha = 1, PLC seed 24607 (R/setup_dec_lc3.c:170-183) */
-        float* h = (float*)calloc((size_t)DST_WORDS * c->ncs, sizeof(float));
-        if (!h) { lc3hip_dec_destroy(c); return 1; }
-        for (int i = 0; i < c->ncs; i++) {
-            int* sc = (int*)(h + (size_t)i * DST_WORDS + DST_SCAL);
-            sc[DS_BETA_IDX] = -1; ((float*)sc)[DS_CUM_ALPHA] = 1.0f; sc[DS_PLC_SEED] = 24607;
-        }
-        hipError_t e = hipMemcpy(c->d_state, h, sizeof(float) * DST_WORDS * (size_t)c->ncs, hipMemcpyHostToDevice);
-        free(h);
-        HIPCHK_OR(e, lc3hip_dec_destroy(c));
-    }
+    if (ss_init(&c->ss, c->device, c->d_state, DST_WORDS, c->ncs, tmpl)) { lc3hip_dec_destroy(c); return 1; }
     HIPCHK_OR(hipStreamCreate(&c->stream), lc3hip_dec_destroy(c));
     HIPCHK_OR(hipEventCreate(&c->ev0), lc3hip_dec_destroy(c)); HIPCHK_OR(hipEventCreate(&c->ev1), lc3hip_dec_destroy(c));
     *out_ctx = c;
@@ -3829,6 +3942,7 @@ static int dec_decode(lc3hip_dctx* c, const void* frames, int frames_on_device, 
 {
     HIPCHK(hipSetDevice(c->device));
     hipStream_t s = hip_stream ? (hipStream_t)hip_stream : c->stream;
+    if (c->ss.done_armed) HIPCHK(hipStreamWaitEvent(s, c->ss.ev_done, 0));      /* behind the last stream-lifecycle call, whichever stream it was queued on */
     const size_t in_bytes = (size_t)c->n_streams * n_frames * in_stride;
     const size_t pcm_bytes = (size_t)c->ncs * n_frames * c->N * (bps == 16 ? 2 : 4);
     const uint8_t* din = (const uint8_t*)frames; void* dpcm = pcm; const uint8_t* dbfi = nullptr; lc3d_dec_trace* dtr = nullptr;
@@ -4026,6 +4140,25 @@ extern "C" int lc3hip_dec_decode_dsizes(void* ctx, const void* frames, int in_st
     return dec_decode((lc3hip_dctx*)ctx, frames, 1, in_stride, nullptr, nullptr, 0, n_frames, pcm, 1, bps, nullptr, hip_stream, sync, nullptr,
                       num_bytes_dev, bfi_dev, status_dev);
 }
+extern "C" int lc3hip_dec_stream_state(void* ctx, int mode, const int* streams, int n, const lc3d_dchan* cfg, void* blob, int blob_on_device, const uint32_t* hdr,
+                                       uint8_t* status, void* hip_stream, int sync)
+{
+    lc3hip_dctx* c = (lc3hip_dctx*)ctx;
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : c->stream;
+    /* behind the batch's last call: a parse-ahead call's concealment kernel (its stream's tail waits for it) and a device-size call's configuration tail included */
+    if (ss_run(&c->ss, s, c->last_stream, mode, c->d_state, c->channels, streams, n, cfg, (int)sizeof(lc3d_dchan), c->d_chans, blob, blob_on_device, hdr, status, sync)) return 1;
+    c->last_stream = s;
+    /* the next parse-ahead reads the configuration and its concealment kernel the state this call writes: it waits for this call, as behind an ordered call */
+    if (c->input_ready) { if (dec_side_streams(c)) return 1; HIPCHK(hipEventRecord(c->ev_ord, s)); c->ord_pending = 1; }
+    if (cfg) {                                  /* the largest frame of the batch selects the parser's staging */
+        if (!c->h_nbytes) { c->h_nbytes = (int*)calloc((size_t)c->ncs, sizeof(int)); if (!c->h_nbytes) return 1; }
+        for (int i = 0; i < n * c->channels; i++) c->h_nbytes[streams[i / c->channels] * c->channels + i % c->channels] = cfg[i].nbytes;
+        c->max_nbytes = 0;
+        for (int i = 0; i < c->ncs; i++) if (c->h_nbytes[i] > c->max_nbytes) c->max_nbytes = c->h_nbytes[i];
+    }
+    return 0;
+}
 extern "C" int lc3hip_dec_set_input_ready(void* ctx, int ready)
 {
     lc3hip_dctx* c = (lc3hip_dctx*)ctx;
@@ -4069,6 +4202,7 @@ extern "C" int lc3hip_dec_destroy(void* ctx)
     if (c->stream) hipStreamDestroy(c->stream);
     if (c->ev0) hipEventDestroy(c->ev0);
     if (c->ev1) hipEventDestroy(c->ev1);
+    ss_free(&c->ss);
     free(c->h_nbytes);
     free(c);
     return 0;

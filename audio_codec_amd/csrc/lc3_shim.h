@@ -21,10 +21,16 @@ typedef struct {
 } lc3d_dec_trace;
 
 
+/* stream lifecycle (include/lc3plus_batch.h: lc3plus_{enc,dec}_batch_{reset,export,import}_streams).  A stream's blob is LC3D_SS_HEADER bytes of header
+ * (lc3_host.c stream_header), then its state rows, channel 0 first. */
+#define LC3D_SS_HEADER 16
+enum { LC3D_SS_RESET = 0, LC3D_SS_EXPORT = 1, LC3D_SS_IMPORT = 2 };
+
 #ifdef __cplusplus
 extern "C" {
 #endif
-int   lc3hip_dec_create(void** ctx, const lc3d_plan* plan, int n_streams, int device);
+/* tmpl: one channel-stream's fresh state row (DST_WORDS words, dec_init_state in lc3_host.c): kept on the device, every row starts from it */
+int   lc3hip_dec_create(void** ctx, const lc3d_plan* plan, const float* tmpl, int n_streams, int device);
 int   lc3hip_dec_upload_chans(void* ctx, const lc3d_dchan* chans, int first, int count);
 int   lc3hip_dec_upload_table(void* ctx, const lc3d_dchan* tab, int n);      /* configuration per channel byte count 0 .. n - 1 (per-frame sizes) */
 /* sizes_host: null, or [n_streams][n_frames] stream-frame sizes, 0 where lost (bfi_flags_host then holds every lost frame); sizes_max_nbytes: the largest
@@ -40,7 +46,7 @@ int   lc3hip_dec_download_chans(void* ctx, lc3d_dchan* chans);    /* waits for t
 float lc3hip_dec_last_ms(void* ctx);
 int   lc3hip_dec_destroy(void* ctx);
 int   lc3hip_create(void** ctx, const lc3d_plan* plan, int n_streams, int device);
-int   lc3hip_reset_state(void* ctx, const float* init_state_one);
+int   lc3hip_set_template(void* ctx, const float* tmpl);       /* one channel-stream's fresh state row (init_state): kept on the device, every row reset from it */
 int   lc3hip_upload_chans(void* ctx, const lc3d_chan* chans, int first, int count);
 /* the same, queued on hip_stream (NULL: the context's stream) behind the work already there, without waiting for it; later calls wait for the copy */
 int   lc3hip_upload_chans_async(void* ctx, const lc3d_chan* chans, int first, int count, void* hip_stream);
@@ -55,6 +61,16 @@ int   lc3hip_set_state(void* ctx, const void* host, size_t bytes);
 size_t lc3hip_dec_state_bytes(void* ctx);
 int   lc3hip_dec_get_state(void* ctx, void* host, size_t bytes);
 int   lc3hip_dec_set_state(void* ctx, const void* host, size_t bytes);
+/* One stream-lifecycle call, mode LC3D_SS_*, queued on hip_stream (NULL: the context's stream) behind every earlier call of the batch, whose later calls follow
+ * it; the next call does not take the overlapped path (encoder: ahead_ok, decoder: parse-ahead).  streams [n]: host, checked by the caller.  cfg (reset): null,
+ * or [n][channels] configuration entries written for the listed streams.  blob (export, import): n blobs, in host memory (staged through pinned memory; an
+ * export returns with the data) or, with blob_on_device, in device memory (16-byte aligned).  hdr: the batch's 4-word blob header; an import writes a
+ * stream only where its blob carries it, status (device import only, null or device [n]): 1 where it did not.  Waits for the device only with sync, for a
+ * host export, and for the staging slot of the call LC3D_SETS back. */
+int   lc3hip_stream_state(void* ctx, int mode, const int* streams, int n, const lc3d_chan* cfg, void* blob, int blob_on_device, const uint32_t* hdr,
+                          uint8_t* status, void* hip_stream, int sync);
+int   lc3hip_dec_stream_state(void* ctx, int mode, const int* streams, int n, const lc3d_dchan* cfg, void* blob, int blob_on_device, const uint32_t* hdr,
+                              uint8_t* status, void* hip_stream, int sync);
 int   lc3hip_dec_set_input_ready(void* ctx, int ready);          /* see lc3plus_dec_batch_set_input_ready (include/lc3plus_batch.h) */
 int   lc3hip_set_input_ready(void* ctx, int ready);              /* see lc3plus_enc_batch_set_input_ready (include/lc3plus_batch.h) */
 int   lc3hip_last_status(void* ctx, uint8_t* status_host, int n);        /* LC3D_ENC_ST_* bits per channel-frame of the last call; returns the count copied */

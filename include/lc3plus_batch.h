@@ -70,6 +70,32 @@ size_t    lc3plus_enc_batch_state_size(const lc3plus_batch* batch);
 LC3_Error lc3plus_enc_batch_get_state(lc3plus_batch* batch, void* state, size_t size);
 LC3_Error lc3plus_enc_batch_set_state(lc3plus_batch* batch, const void* state, size_t size);
 
+/* Stream lifecycle: reset, export and import single streams of a batch, without touching the others.  A server starts a session in a free slot with
+ * reset_streams, and moves a live stream to another batch or device with export_streams / import_streams.
+ *   streams    : host array of n stream indices, each in [0, n_streams) and none twice; may be reused when the call returns.  NULL (streams, blob):
+ *                LC3_NULL_ERROR; n <= 0, an index out of range or repeated: LC3_ERROR.  Every argument is checked before any work: on an error nothing is queued.
+ *   hip_stream : the call is queued there (NULL = the batch's own stream) behind every earlier call of the batch - pipelined calls whose work is still on
+ *                the batch's side streams included - and every later call sees the state it leaves.  With sync = 0 it returns after queueing: it does not wait
+ *                for the device, copy synchronously or read anything back, except an export into a host blob, which returns with the data.  The call after
+ *                a reset or import runs ordered (the encoder's pipelined call does not take the MDCT memory from the previous call's hand-over, the decoder's
+ *                parse-ahead waits); results are byte-identical either way.
+ * reset_streams: every listed stream's state becomes that of a freshly created stream (what lc3_enc_init gives).  bitrates: NULL keeps each stream's
+ *                configuration; otherwise [n] total bitrates, each listed stream configured as set_bitrate configures it (bandwidth kept) - every rate is
+ *                checked before any work, a bad one returns LC3_BITRATE_ERROR and changes nothing.
+ * Blob         : stream_state_size() bytes per stream: a 16-byte header naming the codec (encoder / decoder), the geometry (sample rate, frame length, hrmode,
+ *                channels) and the row length, then the stream's state rows, channel 0 first - exactly the bytes get_state() holds for that stream.  An
+ *                export writes n blobs back to back, in list order.  blob_on_device: 0 = host memory, 1 = device memory, 16-byte aligned (LC3_ERROR otherwise).
+ * import_streams: the blobs must come from a batch of the same codec and geometry; a stream's header is checked before its rows are written, and a
+ *                mismatched stream is never written.  Host blob: every header is checked first, a mismatch returns LC3_ERROR and nothing is queued; the blob
+ *                is staged through pinned memory and may be reused when the call returns; status (host [n] or NULL) is all 0.  Device blob: the kernel checks
+ *                each header - status (device [n] or NULL) is 1 for a stream whose header does not match, which is left unchanged, 0 for the others.  Import
+ *                does not change configuration: set the bitrate as after set_state. */
+size_t    lc3plus_enc_batch_stream_state_size(const lc3plus_batch* batch);
+LC3_Error lc3plus_enc_batch_reset_streams(lc3plus_batch* batch, const int* streams, int n, const int* bitrates, void* hip_stream, int sync);
+LC3_Error lc3plus_enc_batch_export_streams(lc3plus_batch* batch, const int* streams, int n, void* blob, int blob_on_device, void* hip_stream, int sync);
+LC3_Error lc3plus_enc_batch_import_streams(lc3plus_batch* batch, const int* streams, int n, const void* blob, int blob_on_device, uint8_t* status,
+                                           void* hip_stream, int sync);
+
 /* A promise about device-pointer calls, off by default: with ready != 0 the caller guarantees that the PCM passed to every following
  * encode() call is COMPLETE in device memory when the call is made - not merely queued earlier on hip_stream (so it is wrong for PCM
  * that a kernel or copy queued on hip_stream is still producing).  The batch then lets the frame-parallel and pitch kernels of a
@@ -157,6 +183,15 @@ float     lc3plus_dec_batch_last_kernel_ms(lc3plus_dec_batch* batch);
 size_t    lc3plus_dec_batch_state_size(const lc3plus_dec_batch* batch);
 LC3_Error lc3plus_dec_batch_get_state(lc3plus_dec_batch* batch, void* state, size_t size);
 LC3_Error lc3plus_dec_batch_set_state(lc3plus_dec_batch* batch, const void* state, size_t size);
+/* Stream lifecycle of the decoder batch: as for the encoder batch (lc3plus_enc_batch_reset_streams ...).  reset_streams takes num_bytes (NULL keeps each
+ * stream's size; otherwise [n] stream-frame sizes, each listed stream configured as set_num_bytes configures it, every size checked first:
+ * LC3_NUMBYTES_ERROR).  The reset does not wait for the device, also after decode_sizes_device calls: the listed streams' configuration is written on the
+ * device in order, and num_bytes(stream) reads it back as after those calls.  Import does not change configuration (set_num_bytes). */
+size_t    lc3plus_dec_batch_stream_state_size(const lc3plus_dec_batch* batch);
+LC3_Error lc3plus_dec_batch_reset_streams(lc3plus_dec_batch* batch, const int* streams, int n, const int* num_bytes, void* hip_stream, int sync);
+LC3_Error lc3plus_dec_batch_export_streams(lc3plus_dec_batch* batch, const int* streams, int n, void* blob, int blob_on_device, void* hip_stream, int sync);
+LC3_Error lc3plus_dec_batch_import_streams(lc3plus_dec_batch* batch, const int* streams, int n, const void* blob, int blob_on_device, uint8_t* status,
+                                           void* hip_stream, int sync);
 /* The decoder's counterpart of lc3plus_enc_batch_set_input_ready: with ready != 0 the caller guarantees that the frames passed to every
  * following decode() call with device pointers (no bad-frame flags, no status) are COMPLETE in device memory when the call is made.  The
  * bitstream parser of a call - stateless - then runs on a stream of the batch beside the transform and synthesis of the call before; results
