@@ -31,7 +31,9 @@ EXPORTS = [
     "lc3plus_dec_batch_decode_sizes_device", "lc3plus_enc_batch_encode_bitrates",
     "lc3plus_enc_batch_stream_state_size", "lc3plus_enc_batch_reset_streams", "lc3plus_enc_batch_export_streams", "lc3plus_enc_batch_import_streams",
     "lc3plus_dec_batch_stream_state_size", "lc3plus_dec_batch_reset_streams", "lc3plus_dec_batch_export_streams", "lc3plus_dec_batch_import_streams",
+    "lc3plus_enc_batch_encode_bandwidths", "lc3plus_enc_batch_bandwidth", "lc3plus_enc_plan_bandwidths",
 ]
+LC3_BW_WARNING = 18
 
 
 class LC3Error(RuntimeError):
@@ -63,6 +65,10 @@ def load_library():
                                                         C.c_void_p, C.c_void_p, C.c_int]
         L.lc3plus_enc_batch_encode_bitrates_traced.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
         L.lc3plus_enc_plan_bitrates.argtypes = [C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        L.lc3plus_enc_batch_encode_bandwidths.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
+                                                          C.c_int, C.c_void_p, C.c_void_p, C.c_int]
+        L.lc3plus_enc_batch_bandwidth.argtypes = [C.c_void_p, C.c_int]
+        L.lc3plus_enc_plan_bandwidths.argtypes = [C.c_int, C.c_float, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
         L.lc3plus_enc_batch_last_kernel_ms.restype = C.c_float
         L.lc3plus_enc_batch_last_kernel_ms.argtypes = [C.c_void_p]
         L.lc3plus_enc_batch_last_status.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
@@ -215,6 +221,7 @@ class Batch(_StreamLifecycle):
         self.n_streams, self.channels = n_streams, channels
         self.samplerate, self.frame_ms, self.hrmode = samplerate, frame_ms, hrmode
         self.last_num_bytes = None
+        self.last_result = 0          # LC3_Error of the last per-frame-bandwidth call: 0, or LC3_BW_WARNING where a value was refused (not raised)
         self.N = self.lib.lc3plus_enc_batch_input_samples(self.h)
 
     @property
@@ -230,18 +237,43 @@ class Batch(_StreamLifecycle):
     def set_bandwidth(self, stream, bw):
         return self.lib.lc3plus_enc_batch_set_bandwidth(self.h, stream, bw)
 
+    def bandwidth(self, stream):
+        """The bandwidth in force for the stream, Hz (0: none)."""
+        return self.lib.lc3plus_enc_batch_bandwidth(self.h, stream)
+
+    def _encode_bandwidths(self, pcm_ptr, on_device, bitdepth, bandwidths, bitrates, T, out_ptr, out_stride, hip_stream, sync):
+        """lc3plus_enc_batch_encode_bandwidths: bandwidths (and bitrates, or None) broadcast to [n_streams, T]; frame sizes in last_num_bytes,
+        the result (0 or LC3_BW_WARNING) in last_result; any other code raises."""
+        bw = np.ascontiguousarray(np.broadcast_to(np.asarray(bandwidths, dtype=np.int32), (self.n_streams, T)), dtype=np.int32)
+        br = self._bitrates(bitrates, T) if bitrates is not None else None
+        if br is None:
+            self.last_num_bytes = np.zeros((self.n_streams, T), dtype=np.int32)
+        rc = self.lib.lc3plus_enc_batch_encode_bandwidths(self.h, pcm_ptr, on_device, bitdepth, bw.ctypes.data, br.ctypes.data if br is not None else None,
+                                                          T, out_ptr, out_stride, on_device, self.last_num_bytes.ctypes.data,
+                                                          C.c_void_p(hip_stream) if hip_stream else None, 1 if sync else 0)
+        if rc not in (0, LC3_BW_WARNING):
+            raise LC3Error(rc, "lc3plus_enc_batch_encode_bandwidths")
+        self.last_result = rc
+
     def _bitrates(self, bitrates, T):
         """int32 [n_streams, T] per-frame bitrates, and the host buffer their frame sizes come back in (last_num_bytes)."""
         br = np.ascontiguousarray(np.broadcast_to(np.asarray(bitrates, dtype=np.int32), (self.n_streams, T)), dtype=np.int32)
         self.last_num_bytes = np.zeros((self.n_streams, T), dtype=np.int32)
         return br
 
-    def encode(self, pcm, bitdepth=16, bitrates=None):
+    def encode(self, pcm, bitdepth=16, bitrates=None, bandwidths=None):
         """pcm: host array [n_streams, T, channels, N] (or [n_streams, T, N] for mono) -> uint8 [n_streams, T, stride].
         bitrates: None, or [n_streams, T] total bitrate per stream-frame (lc3plus_enc_batch_encode_bitrates): the output is then
-        [n_streams, T, largest frame of the call] and last_num_bytes [n_streams, T] holds each frame's size."""
+        [n_streams, T, largest frame of the call] and last_num_bytes [n_streams, T] holds each frame's size.
+        bandwidths: None, or [n_streams, T] bandwidth in Hz per stream-frame, anything that broadcasts to it (lc3plus_enc_batch_encode_bandwidths),
+        with or without bitrates; last_result is then 0 or LC3_BW_WARNING (a refused value kept the bandwidth in force)."""
         pcm = np.ascontiguousarray(pcm)
         T = pcm.shape[1]
+        if bandwidths is not None:
+            stride = max(int(enc_plan_bitrates_for(self, self._bitrates(bitrates, T)).max()), 1) if bitrates is not None else self.stride
+            out = np.zeros((self.n_streams, T, stride), dtype=np.uint8)
+            self._encode_bandwidths(pcm.ctypes.data, 0, bitdepth, bandwidths, bitrates, T, out.ctypes.data, stride, None, True)
+            return out
         if bitrates is not None:
             br = self._bitrates(bitrates, T)
             nb = enc_plan_bitrates_for(self, br)
@@ -338,9 +370,12 @@ class Batch(_StreamLifecycle):
             raise LC3Error(rc, "lc3plus_enc_batch_encode_traced")
         return out, traces
 
-    def encode_device(self, d_pcm_ptr, bitdepth, T, d_out_ptr, out_stride, hip_stream=None, sync=False, bitrates=None):
-        """Device-resident variant: raw device pointers (e.g. torch tensors' data_ptr()).  bitrates: as for encode() (a host array;
+    def encode_device(self, d_pcm_ptr, bitdepth, T, d_out_ptr, out_stride, hip_stream=None, sync=False, bitrates=None, bandwidths=None):
+        """Device-resident variant: raw device pointers (e.g. torch tensors' data_ptr()).  bitrates, bandwidths: as for encode() (host arrays;
         last_num_bytes then holds the frame sizes)."""
+        if bandwidths is not None:
+            self._encode_bandwidths(C.c_void_p(d_pcm_ptr), 1, bitdepth, bandwidths, bitrates, T, C.c_void_p(d_out_ptr), out_stride, hip_stream, sync)
+            return
         if bitrates is not None:
             br = self._bitrates(bitrates, T)
             rc = self.lib.lc3plus_enc_batch_encode_bitrates(self.h, C.c_void_p(d_pcm_ptr), 1, bitdepth, br.ctypes.data, T, C.c_void_p(d_out_ptr),
@@ -385,6 +420,21 @@ def enc_plan_bitrates(samplerate, channels, frame_ms, hrmode, bitrates):
 
 def enc_plan_bitrates_for(batch, bitrates):
     return enc_plan_bitrates(batch.samplerate, batch.channels, batch.frame_ms, batch.hrmode, bitrates)[0]
+
+
+def enc_plan_bandwidths(samplerate, frame_ms, hrmode, start, bandwidths):
+    """The per-frame bandwidth rule of Batch.encode(bandwidths=...) on the host (lc3plus_enc_plan_bandwidths, no device needed): start [n_streams]
+    the bandwidth in force before the call, bandwidths [n_streams, n_frames] (or [n_frames] for one stream) -> (in_force int32 [n_streams, n_frames],
+    0 or LC3_BW_WARNING).  Raises LC3Error with any other code."""
+    L = load_library()
+    bw = np.ascontiguousarray(np.atleast_2d(np.asarray(bandwidths)), dtype=np.int32)
+    S, T = bw.shape
+    st = np.ascontiguousarray(np.broadcast_to(np.asarray(start, dtype=np.int32), (S,)), dtype=np.int32)
+    f = np.zeros((S, T), dtype=np.int32)
+    rc = L.lc3plus_enc_plan_bandwidths(samplerate, frame_ms, hrmode, S, st.ctypes.data, bw.ctypes.data, T, f.ctypes.data)
+    if rc not in (0, LC3_BW_WARNING):
+        raise LC3Error(rc, "lc3plus_enc_plan_bandwidths")
+    return f, rc
 
 
 class Encoder:

@@ -35,7 +35,11 @@
 #endif
 #define RATE_WAVES RATE_WAVES_BIG
 #else
+#ifdef LC3_ENC_VBW
+#define SHAPE_KERNEL_NAME lc3_enc_shape_kernel_vbw      /* per-frame bandwidths (lc3_kernels.hip, -DLC3_ENC_VBW): only this kernel of the file */
+#else
 #define SHAPE_KERNEL_NAME lc3_enc_shape_kernel
+#endif
 #define RATE_KERNEL_NAME  lc3_enc_rate_kernel
 #define TAILW_KERNEL_NAME lc3_enc_tailw_kernel
 #ifndef SHAPE_WAVES
@@ -65,7 +69,11 @@ struct __attribute__((aligned(16))) ShapeLds {
 
 extern "C" __global__ void __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(SHAPE_WAVES, SHAPE_WAVES)))
 SHAPE_KERNEL_NAME(const lc3d_plan* __restrict__ P, const lc3d_chan* __restrict__ chans, int T /* rows per channel-stream */, int tb, int nt, int fpw, int ncs,
-                  float* __restrict__ rows /* [cs][T][srow] */, int srow, float* __restrict__ frec /* [cs][T][FR_WORDS] */)
+                  float* __restrict__ rows /* [cs][T][srow] */, int srow, float* __restrict__ frec /* [cs][T][FR_WORDS] */
+#ifdef LC3_ENC_VBW
+                  , const uint16_t* __restrict__ bwf /* [stream][T] bandwidth in force for each stream-frame, Hz */
+#endif
+                  )
 {
     __shared__ ShapeLds L;
     const int lane = threadIdx.x;
@@ -103,6 +111,17 @@ SHAPE_KERNEL_NAME(const lc3d_plan* __restrict__ P, const lc3d_chan* __restrict__
         st_sns_apply(P, L, lane, XCUR(L), bob[0], bob[1], bob[2], bob[3]);
 #endif
         int bw = uni(L.isc[I_BW]);
+#ifdef LC3_ENC_VBW
+        const int fbw = bwf[(size_t)(cs / PI(channels)) * T + t];
+        if (fbw) {                                            /* R/cutoff_bandwidth.c:13-26 */
+            const int bin = lc3d_bw_cut_bin(fbw, PI(dms));
+            if (ylen > bin) {
+                if (lane < 4) { const float sc4[4] = {0.5f, 0.25f, 0.125f, 0.0625f}; L.A[bin - 1 + lane] = L.A[bin - 1 + lane] * sc4[lane]; }
+                for (int i = bin + 3 + lane; i < ylen; i += WAVE) L.A[i] = 0;
+            }
+            bw = imin(bw, lc3d_bw_index(fbw));
+        }
+#else
         if (CI(bandwidth)) {                                  /* R/cutoff_bandwidth.c:13-26 */
             const int bin = CI(bw_cut_bin);
             if (ylen > bin) {
@@ -111,6 +130,7 @@ SHAPE_KERNEL_NAME(const lc3d_plan* __restrict__ P, const lc3d_chan* __restrict__
             }
             bw = imin(bw, CI(bw_index));
         }
+#endif
         const int bw_bin = lc3t_bw_bins[PI(bw_cls) * 6 + bw];
         if (lane < 16) L.isc[I_TNS_IDX0 + lane] = 0;
         if (lane < 2) L.isc[I_TNS_ORD0 + lane] = 0;
@@ -131,6 +151,7 @@ SHAPE_KERNEL_NAME(const lc3d_plan* __restrict__ P, const lc3d_chan* __restrict__
     }
 #undef SHAPE_PREFETCH
 }
+#ifndef LC3_ENC_VBW
 
 /* ------------------------------------------------------------------------------------------------------------------------------ */
 /* The bit-count tables live in LDS, shared by the RATE_WG waves (channel-streams) of a workgroup: a gather from global memory would be waited for with
@@ -428,3 +449,4 @@ TAILW_KERNEL_NAME(const lc3d_plan* __restrict__ P, const lc3d_chan* __restrict__
     }
 #undef TAILW_PREFETCH
 }
+#endif  /* !LC3_ENC_VBW */

@@ -61,9 +61,18 @@ __device__ __attribute__((noinline)) void shl_lpc_weight(const float* a_in, cons
 #else
 #define SHL_ATTR __attribute__((amdgpu_waves_per_eu(SHL_WAVES, SHL_WAVES)))
 #endif
+#ifdef LC3_ENC_VBW
+#define SHL_KERNEL_NAME lc3_enc_shape_lane_kernel_vbw   /* per-frame bandwidths (lc3_kernels.hip, -DLC3_ENC_VBW): only this kernel of the file */
+#else
+#define SHL_KERNEL_NAME lc3_enc_shape_lane_kernel
+#endif
 extern "C" __global__ void __launch_bounds__(WAVE) SHL_ATTR
-lc3_enc_shape_lane_kernel(const lc3d_plan* __restrict__ P, const lc3d_chan* __restrict__ chans, int RT /* rows per channel-stream */, int r0 /* first row of this launch */, int nt, int ncs,
-                          float* __restrict__ rows /* [cs][RT][srow] */, int srow, float* __restrict__ frec /* [cs][RT][FR_WORDS] */)
+SHL_KERNEL_NAME(const lc3d_plan* __restrict__ P, const lc3d_chan* __restrict__ chans, int RT /* rows per channel-stream */, int r0 /* first row of this launch */, int nt, int ncs,
+                          float* __restrict__ rows /* [cs][RT][srow] */, int srow, float* __restrict__ frec /* [cs][RT][FR_WORDS] */
+#ifdef LC3_ENC_VBW
+                          , const uint16_t* __restrict__ bwf /* [stream][RT] bandwidth in force for each stream-frame, Hz */
+#endif
+                          )
 {
     __shared__ ShlLds L;
     const int lane = threadIdx.x;
@@ -117,8 +126,14 @@ lc3_enc_shape_lane_kernel(const lc3d_plan* __restrict__ P, const lc3d_chan* __re
     };
     /* ---- bandwidth controller R/cutoff_bandwidth.c:13-26 and the TNS geometry R/tns_coder.c:196-246 ---- */
     int bw = ((const int*)rec)[FR_BW];
+#ifdef LC3_ENC_VBW
+    const int fbw = bwf[(size_t)(cs / PI(channels)) * RT + t];          /* this lane's frame: cut and cbin are per lane here */
+    const bool cut = fbw != 0; const int cbin = lc3d_bw_cut_bin(fbw, dms);
+    if (cut) bw = imin(bw, lc3d_bw_index(fbw));
+#else
     const bool cut = C->bandwidth != 0; const int cbin = C->bw_cut_bin;
     if (cut) bw = imin(bw, C->bw_index);
+#endif
     const int bw_bin = lc3t_bw_bins[PI(bw_cls) * 6 + bw];
     int numfilters, start0, start1 = 0, stop0, stop1 = 0, obits_off = 8; float maxPG = 2;
     const int maxOrder = dms == 100 ? 8 : 4, nSub = dms == 100 ? 3 : 2;
@@ -505,7 +520,7 @@ lc3_enc_shape_lane_kernel(const lc3d_plan* __restrict__ P, const lc3d_chan* __re
 }
 #endif
 
-#ifndef LC3_BIG
+#if !defined(LC3_BIG) && !defined(LC3_ENC_VBW)
 /* lc3_enc_scf_lane_kernel -- per-band energies (R/per_band_energy.c:13-30), bandwidth detector (R/detect_cutoff_warped.c:13-83) and SNS scale
  * factors (R/sns_compute_scf.c:13-176), one channel-frame per LANE.  In the wave-per-frame front these stages are short serial walks over 64
  * (or fewer) values - 64-term ordered sums read lane by lane, the detector's band walk, the 6-tap down-sampling - about 720 instructions per

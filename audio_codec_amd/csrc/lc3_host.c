@@ -369,6 +369,7 @@ struct lc3plus_batch {
     int* bitrates;
     void* dev;
     uint16_t* fsz; size_t fsz_cap;  /* per-frame bitrates: stream-frame sizes of enc_plan_bitrates, grown as needed */
+    uint16_t* bwf; size_t bwf_cap;  /* per-frame bandwidths: the values in force of enc_plan_bandwidths, grown as needed */
 };
 
 static LC3_Error batch_upload(lc3plus_batch* b, int first_stream, int count)
@@ -433,7 +434,7 @@ LC3_Error lc3plus_enc_batch_destroy(lc3plus_batch* b)
 {
     if (!b) return LC3_NULL_ERROR;
     lc3hip_destroy(b->dev);
-    free(b->chans); free(b->bitrates); free(b->fsz); free(b);
+    free(b->chans); free(b->bitrates); free(b->fsz); free(b->bwf); free(b);
     return LC3_OK;
 }
 
@@ -475,8 +476,8 @@ LC3_Error lc3plus_enc_batch_set_bandwidth(lc3plus_batch* b, int stream, int band
         if (bandwidth * 2 > eff) return LC3_BW_WARNING;
         for (int c = 0; c < b->g.channels; c++) {
             ch[c].bandwidth = bandwidth;
-            ch[c].bw_cut_bin = (bandwidth * b->g.dms) / 5000;
-            ch[c].bw_index = IMAX(0, (bandwidth / 4000) - 1);
+            ch[c].bw_cut_bin = lc3d_bw_cut_bin(bandwidth, b->g.dms);
+            ch[c].bw_index = lc3d_bw_index(bandwidth);
         }
         return batch_upload(b, stream, 1);
     }
@@ -489,7 +490,7 @@ static LC3_Error batch_encode(lc3plus_batch* b, const void* pcm, int pcm_on_devi
     if (!b || !pcm || !out) return LC3_NULL_ERROR;
     if (bitdepth != 16 && bitdepth != 24 && bitdepth != 32) return LC3_ERROR;
     if (n_frames <= 0 || out_stride < b->stride) return LC3_ERROR;
-    if (lc3hip_encode(b->dev, pcm, pcm_on_device, bitdepth, n_frames, out, out_stride, out_on_device, hip_stream, sync, trace, NULL)) return LC3_ERROR;
+    if (lc3hip_encode(b->dev, pcm, pcm_on_device, bitdepth, n_frames, out, out_stride, out_on_device, hip_stream, sync, trace, NULL, NULL)) return LC3_ERROR;
     /* one-shot attack-state reset requests have been consumed by this launch */
     int dirty = 0;
     for (int i = 0; i < b->n_streams * b->g.channels; i++) if (b->chans[i].reset_attack) { b->chans[i].reset_attack = 0; dirty = 1; }
@@ -520,7 +521,7 @@ static LC3_Error batch_encode_bitrates(lc3plus_batch* b, const void* pcm, int pc
     LC3_Error e = enc_plan_bitrates(&b->g, bitrates, n, b->fsz, &max_bytes);
     if (e) return e;
     if (out_stride < max_bytes) return LC3_ERROR;
-    if (lc3hip_encode(b->dev, pcm, pcm_on_device, bitdepth, n_frames, out, out_stride, out_on_device, hip_stream, sync, trace, b->fsz)) return LC3_ERROR;
+    if (lc3hip_encode(b->dev, pcm, pcm_on_device, bitdepth, n_frames, out, out_stride, out_on_device, hip_stream, sync, trace, b->fsz, NULL)) return LC3_ERROR;
     if (num_bytes) for (size_t i = 0; i < n; i++) num_bytes[i] = b->fsz[i];
     /* every stream is configured with its last frame's rate; the kernel has done every attack-detector reset the call asked for, and the one-shot
      * requests pending from set_bitrate before it */
@@ -537,7 +538,7 @@ static LC3_Error batch_encode_bitrates(lc3plus_batch* b, const void* pcm, int pc
     if (!dirty) return LC3_OK;
     batch_restride(b);
     /* on the call's stream behind its kernels: the call does not wait for them (sync = 0) */
-    return lc3hip_upload_chans_async(b->dev, b->chans, 0, b->n_streams * b->g.channels, hip_stream) ? LC3_ERROR : LC3_OK;
+    return lc3hip_upload_chans_async(b->dev, b->chans, 0, b->n_streams * b->g.channels, hip_stream, 0) ? LC3_ERROR : LC3_OK;
 }
 LC3_Error lc3plus_enc_batch_encode_bitrates(lc3plus_batch* b, const void* pcm, int pcm_on_device, int bitdepth, const int* bitrates, int n_frames, void* out,
                                             int out_stride, int out_on_device, int* num_bytes, void* hip_stream, int sync)
@@ -551,6 +552,129 @@ LC3_Error lc3plus_enc_batch_encode_bitrates_traced(lc3plus_batch* b, const void*
     if (!traces) return LC3_NULL_ERROR;
     return batch_encode_bitrates(b, pcm, 0, bitdepth, bitrates, n_frames, out, out_stride, 0, NULL, NULL, 1, traces);
 }
+/* ---- per-frame bandwidths (lc3plus_enc_batch_encode_bandwidths) ---- */
+/* The values a call refuses outright: a negative bandwidth, and a positive one whose cut-off line is below 1 (the controller would write in front of the
+ * spectrum, R/cutoff_bandwidth.c:17-19).  0 switches the controller off. */
+static int bw_value_ok(int bw, int dms) { return bw == 0 || (bw > 0 && bw >= (5000 + dms - 1) / dms); }      /* lc3d_bw_cut_bin(bw, dms) >= 1, without overflow */
+/* The per-frame rule: frame t of stream s applies lc3_enc_set_bandwidth(bandwidths[s][t]) to the value in force before it (start[s] for frame 0,
+ * R/lc3.c:187-208): a new value that 2 * bw > min(fs_in, 40000) refuses keeps the value in force and makes the call's result LC3_BW_WARNING.  Values
+ * have been checked with bw_value_ok; start values are what set_bandwidth accepted, and one with a cut-off line below 1 that stays in force is refused
+ * here too.  Out: in_force [n_streams][n_frames]. */
+static LC3_Error enc_plan_bandwidths(const geom_t* g, int n_streams, const int* start, const int* bandwidths, int n_frames, uint16_t* in_force)
+{
+    const int eff = g->fs_in > 40000 ? 40000 : g->fs_in;
+    LC3_Error res = LC3_OK;
+    for (int s = 0; s < n_streams; s++) {
+        int cur = start[s];
+        for (int t = 0; t < n_frames; t++) {
+            const int v = bandwidths[(size_t)s * n_frames + t];
+            if (v != cur) { if (v > eff / 2) res = LC3_BW_WARNING; else cur = v; }          /* 2 * v > eff: eff is even */
+            if (!bw_value_ok(cur, g->dms) || cur > 0xFFFF) return LC3_ERROR;
+            in_force[(size_t)s * n_frames + t] = (uint16_t)cur;
+        }
+    }
+    return res;
+}
+static LC3_Error batch_encode_bandwidths(lc3plus_batch* b, const void* pcm, int pcm_on_device, int bitdepth, const int* bandwidths, const int* bitrates,
+                                         int n_frames, void* out, int out_stride, int out_on_device, int* num_bytes, void* hip_stream, int sync)
+{
+    if (!b) return LC3_NULL_ERROR;
+    if (b->g.hrmode) return LC3_HRMODE_BW_ERROR;
+    const size_t n = (size_t)b->n_streams * (n_frames > 0 ? n_frames : 0);
+    if (bandwidths) for (size_t i = 0; i < n; i++) if (!bw_value_ok(bandwidths[i], b->g.dms)) return LC3_ERROR;
+    if (!pcm || !out || !bandwidths) return LC3_NULL_ERROR;
+    if (bitdepth != 16 && bitdepth != 24 && bitdepth != 32) return LC3_ERROR;
+    if (n_frames <= 0) return LC3_ERROR;
+    if (bitrates) {
+        if (b->fsz_cap < n) {
+            free(b->fsz); b->fsz_cap = 0;
+            b->fsz = (uint16_t*)malloc(n * sizeof(uint16_t));
+            if (!b->fsz) return LC3_ERROR;
+            b->fsz_cap = n;
+        }
+        int max_bytes = 0;
+        LC3_Error e = enc_plan_bitrates(&b->g, bitrates, n, b->fsz, &max_bytes);
+        if (e) return e;
+        if (out_stride < max_bytes) return LC3_ERROR;
+    } else if (out_stride < b->stride) return LC3_ERROR;
+    if (b->bwf_cap < n) {
+        free(b->bwf); b->bwf_cap = 0;
+        b->bwf = (uint16_t*)malloc(n * sizeof(uint16_t));
+        if (!b->bwf) return LC3_ERROR;
+        b->bwf_cap = n;
+    }
+    int start[256];
+    LC3_Error res = LC3_OK;
+    for (int s0 = 0; s0 < b->n_streams; s0 += 256) {          /* the value in force before the call: the stream's configuration */
+        const int m = IMIN(256, b->n_streams - s0);
+        for (int i = 0; i < m; i++) start[i] = b->chans[(size_t)(s0 + i) * b->g.channels].bandwidth;
+        const LC3_Error e = enc_plan_bandwidths(&b->g, m, start, bandwidths + (size_t)s0 * n_frames, n_frames, b->bwf + (size_t)s0 * n_frames);
+        if (e != LC3_OK && e != LC3_BW_WARNING) return e;
+        if (e) res = e;
+    }
+    if (lc3hip_encode(b->dev, pcm, pcm_on_device, bitdepth, n_frames, out, out_stride, out_on_device, hip_stream, sync, NULL, bitrates ? b->fsz : NULL,
+                      b->bwf)) return LC3_ERROR;
+    if (num_bytes) for (size_t i = 0; i < n; i++) num_bytes[i] = bitrates ? b->fsz[i] : lc3plus_enc_batch_num_bytes(b, (int)(i / n_frames));
+    /* every stream is configured with the bandwidth in force after its last frame, and with its last rate when rates were given; the one-shot
+     * attack-detector resets pending from set_bitrate have been done by this call */
+    int dirty = 0, rate_dirty = 0;
+    for (int i = 0; i < b->n_streams; i++) {
+        lc3d_chan* ch = b->chans + (size_t)i * b->g.channels;
+        for (int c = 0; c < b->g.channels; c++) if (ch[c].reset_attack) { ch[c].reset_attack = 0; rate_dirty = 1; }
+        if (bitrates) {
+            const int br = bitrates[(size_t)i * n_frames + n_frames - 1];
+            if (br != b->bitrates[i]) {
+                if (derive_bitrate(&b->g, br, ch) != LC3_OK) return LC3_ERROR;          /* checked by enc_plan_bitrates */
+                for (int c = 0; c < b->g.channels; c++) ch[c].reset_attack = 0;
+                b->bitrates[i] = br; rate_dirty = 1;
+            }
+        }
+        const int bw = b->bwf[(size_t)i * n_frames + n_frames - 1];
+        if (bw != ch[0].bandwidth) {
+            for (int c = 0; c < b->g.channels; c++) { ch[c].bandwidth = bw; ch[c].bw_cut_bin = lc3d_bw_cut_bin(bw, b->g.dms); ch[c].bw_index = lc3d_bw_index(bw); }
+            dirty = 1;
+        }
+    }
+    if (rate_dirty) batch_restride(b);
+    /* on the call's stream behind its kernels: the call does not wait for them (sync = 0) */
+    if ((dirty || rate_dirty) && lc3hip_upload_chans_async(b->dev, b->chans, 0, b->n_streams * b->g.channels, hip_stream, !rate_dirty)) return LC3_ERROR;
+    return res;
+}
+LC3_Error lc3plus_enc_batch_encode_bandwidths(lc3plus_batch* b, const void* pcm, int pcm_on_device, int bitdepth, const int* bandwidths, const int* bitrates,
+                                              int n_frames, void* out, int out_stride, int out_on_device, int* num_bytes, void* hip_stream, int sync)
+{
+    return batch_encode_bandwidths(b, pcm, pcm_on_device, bitdepth, bandwidths, bitrates, n_frames, out, out_stride, out_on_device, num_bytes, hip_stream, sync);
+}
+int lc3plus_enc_batch_bandwidth(const lc3plus_batch* b, int stream)
+{
+    if (!b || stream < 0 || stream >= b->n_streams) return -1;
+    return b->chans[(size_t)stream * b->g.channels].bandwidth;
+}
+/* the per-frame bandwidth rule for a geometry, without a device: start [n_streams], bandwidths [n_streams * n_frames] -> in_force [n_streams * n_frames].
+ * Returns LC3_OK, LC3_BW_WARNING where a value was refused, or the error of the call. */
+LC3_Error lc3plus_enc_plan_bandwidths(int samplerate, float frame_ms, int hrmode, int n_streams, const int* start, const int* bandwidths, int n_frames,
+                                      int* in_force)
+{
+    if (!start || !bandwidths || !in_force) return LC3_NULL_ERROR;
+    if (n_streams <= 0 || n_frames <= 0) return LC3_ERROR;
+    if (!samplerate_ok(samplerate)) return LC3_SAMPLERATE_ERROR;
+    { int d = (int)ceil(frame_ms * 10); if (d != 25 && d != 50 && d != 100) return LC3_FRAMEMS_ERROR; }
+    if (samplerate < 48000 && hrmode != 0) return LC3_SAMPLERATE_ERROR;
+    geom_t g;
+    geom_init(&g, samplerate, 1);
+    g.dms = (int)(frame_ms * 10); g.frame_ms = frame_ms; g.hrmode = hrmode > 0;
+    geom_update(&g);
+    if (g.hrmode) return LC3_HRMODE_BW_ERROR;
+    const size_t n = (size_t)n_streams * n_frames;
+    for (size_t i = 0; i < n; i++) if (!bw_value_ok(bandwidths[i], g.dms)) return LC3_ERROR;
+    uint16_t* f = (uint16_t*)malloc(n * sizeof(uint16_t));
+    if (!f) return LC3_ERROR;
+    const LC3_Error e = enc_plan_bandwidths(&g, n_streams, start, bandwidths, n_frames, f);
+    if (e == LC3_OK || e == LC3_BW_WARNING) for (size_t i = 0; i < n; i++) in_force[i] = f[i];
+    free(f);
+    return e;
+}
+
 /* test hook: the per-frame bitrate rule for a geometry, without a device.  num_bytes [n_streams * n_frames] out, *max_bytes the largest */
 LC3_Error lc3plus_enc_plan_bitrates(int samplerate, int channels, float frame_ms, int hrmode, int n_streams, const int* bitrates, int n_frames,
                                     int* num_bytes, int* max_bytes)
@@ -769,7 +893,7 @@ LC3_Error lc3_enc_set_bandwidth(LC3_Enc* e, int bandwidth)
         if (bandwidth * 2 > eff) return LC3_BW_WARNING;
         e->bandwidth = bandwidth;
         for (int c = 0; c < e->channels; c++) {
-            e->ch[c].bandwidth = bandwidth; e->ch[c].bw_cut_bin = (bandwidth * e->g.dms) / 5000; e->ch[c].bw_index = IMAX(0, (bandwidth / 4000) - 1);
+            e->ch[c].bandwidth = bandwidth; e->ch[c].bw_cut_bin = lc3d_bw_cut_bin(bandwidth, e->g.dms); e->ch[c].bw_index = lc3d_bw_index(bandwidth);
         }
         if (e->batch) return lc3plus_enc_batch_set_bandwidth(e->batch, 0, bandwidth);
     }

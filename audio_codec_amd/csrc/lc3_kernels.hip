@@ -36,6 +36,9 @@
 /* Two LDS layouts of the same code.  Standard: frames up to 480 samples with an MDCT memory of at most 300 (every operating
  * point except two), 10 KB per wave, 4 waves per SIMD.  Large (-DLC3_BIG, kernel lc3_encode_kernel_big): 96 kHz / 10 ms (N = 960)
  * and 96 kHz / 5 ms (N = 480, MDCT memory 360), 17 KB per wave, 2 waves per SIMD. */
+#if defined(LC3_BIG) && defined(LC3_ENC_VBW)
+#error "per-frame bandwidths have no large-layout kernels: that layout only serves 96 kHz, which is high-resolution and has no bandwidth controller"
+#endif
 #ifdef LC3_BIG
 #define MAXN 960
 #define MEMCAP LC3D_MEMCAP_BIG
@@ -50,8 +53,12 @@
 #define MAXN 480
 #define MEMCAP LC3D_MEMCAP_STD  /* MDCT overlap memory: N - la_zeros <= 300 for every N <= 480 except 96 kHz / 5 ms */
 #define SMW 548
-#ifdef LC3_ENC_VAR
+#if defined(LC3_ENC_VAR) && defined(LC3_ENC_VBW)
+#define KERNEL_NAME lc3_encode_kernel_var_vbw
+#elif defined(LC3_ENC_VAR)
 #define KERNEL_NAME lc3_encode_kernel_var
+#elif defined(LC3_ENC_VBW)
+#define KERNEL_NAME lc3_encode_kernel_vbw
 #else
 #define KERNEL_NAME lc3_encode_kernel
 #endif
@@ -2653,7 +2660,10 @@ template <class LdsT> STAGE void st_bitstream(const lc3d_plan* __restrict__ P, c
  * fixed-rate kernel stays the code it is.  Per frame the wave reloads the rate-derived words of its configuration from etab, the configuration per channel
  * byte count, at the channel's share of fsz[stream][dt0 + t] (the stream-frame's bytes, split over the channels as derive_bitrate does); the bandwidth
  * words stay the stream's (chans).  A frame whose rate disables attack handling clears the detector first (R/setup_enc_lc3.c:297-308).  The in-kernel
- * writer then addresses the output by the call's frames: [stream][dT][out_stride], frame dt0 + t. */
+ * writer then addresses the output by the call's frames: [stream][dT][out_stride], frame dt0 + t.
+ * -DLC3_ENC_VBW: per-frame bandwidths (lc3plus_enc_batch_encode_bandwidths), kernel lc3_encode_kernel_vbw (_var_vbw together with -DLC3_ENC_VAR), standard
+ * layout only, in objects of their own.  The bandwidth controller takes the frame's bandwidth in Hz from bwf[stream][dt0 + t] (the host has resolved every
+ * frame to the value in force, 0 = off) instead of the stream's configuration words, with the formulas of set_bandwidth (lc3d_bw_cut_bin, lc3d_bw_index). */
 extern "C" __global__ void __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(KERNEL_WAVES, KERNEL_WAVES)))
 KERNEL_NAME(const lc3d_plan* __restrict__ P, const lc3d_chan* __restrict__ chans, float* __restrict__ state,
                   const void* __restrict__ pcm, int bitdepth, int T, uint8_t* __restrict__ out, int out_stride, int ncs,
@@ -2666,6 +2676,9 @@ KERNEL_NAME(const lc3d_plan* __restrict__ P, const lc3d_chan* __restrict__ chans
                   const float* __restrict__ xnext /* [cs][MEMCAP] MDCT memory after the last frame */
 #ifdef LC3_ENC_VAR
                   , const uint16_t* __restrict__ fsz /* [stream][dT] bytes of each stream-frame */, const lc3d_chan* __restrict__ etab /* per channel byte count */
+#endif
+#ifdef LC3_ENC_VBW
+                  , const uint16_t* __restrict__ bwf /* [stream][dT] bandwidth in force for each stream-frame, Hz */
 #endif
                   )
 {
@@ -2816,6 +2829,18 @@ KERNEL_NAME(const lc3d_plan* __restrict__ P, const lc3d_chan* __restrict__ chans
         if (tr) { if (lane < 16) tr->scf_q[lane] = L.sm[SM_SCFQ + lane]; if (lane < 7) tr->scf_idx[lane] = L.isc[I_SCF0 + lane];
                   for (int i = lane; i < N; i += WAVE) tr->spec_shaped[i] = L.A[i]; }
         int bw = uni(L.isc[I_BW]);
+#ifdef LC3_ENC_VBW
+        const int fbw = bwf[(size_t)strm * dT + dt0 + t];
+        if (fbw) {                                            /* R/cutoff_bandwidth.c:13-26 */
+            const int bin = lc3d_bw_cut_bin(fbw, PI(dms));
+            if (PI(ylen) > bin) {
+                if (lane < 4) { const float sc4[4] = {0.5f, 0.25f, 0.125f, 0.0625f}; L.A[bin - 1 + lane] = L.A[bin - 1 + lane] * sc4[lane]; }
+                for (int i = bin + 3 + lane; i < PI(ylen); i += WAVE) L.A[i] = 0;
+            }
+            bw = imin(bw, lc3d_bw_index(fbw));
+            if (lane == 0) L.isc[I_BW] = bw;
+        }
+#else
         if (CI(bandwidth)) {                                  /* R/cutoff_bandwidth.c:13-26 */
             const int bin = CI(bw_cut_bin);
             if (PI(ylen) > bin) {
@@ -2825,6 +2850,7 @@ KERNEL_NAME(const lc3d_plan* __restrict__ P, const lc3d_chan* __restrict__ chans
             bw = imin(bw, CI(bw_index));
             if (lane == 0) L.isc[I_BW] = bw;
         }
+#endif
         const int bw_bin = lc3t_bw_bins[PI(bw_cls) * 6 + bw];
         if (lane < 16) L.isc[I_TNS_IDX0 + lane] = 0;
         if (lane < 2) L.isc[I_TNS_ORD0 + lane] = 0;
@@ -2914,7 +2940,11 @@ KERNEL_NAME(const lc3d_plan* __restrict__ P, const lc3d_chan* __restrict__ chans
     if (lane < 16 && !(spec && (lane == I_ATT_POS || lane == I_ATT_FLAG))) ((int*)stp)[LC3D_ST_SCAL(MEMCAP) + 16 + lane] = L.isc[lane];
     (void)ml;
 }
-#ifndef LC3_ENC_VAR             /* the per-frame-bitrate objects hold only that kernel */
+#if defined(LC3_ENC_VBW) && !defined(LC3_ENC_VAR)   /* the per-frame-bandwidth object: besides lc3_encode_kernel_vbw only the two shape kernels */
+#include "lc3_enc_rate.inc"        /* lc3_enc_shape_kernel_vbw */
+#include "lc3_enc_shapel.inc"      /* lc3_enc_shape_lane_kernel_vbw */
+#endif
+#if !defined(LC3_ENC_VAR) && !defined(LC3_ENC_VBW)   /* the per-frame-bitrate and per-frame-bandwidth objects hold only their kernels */
 
 /* ------------------------------------------------------------------------------------------------ */
 /* C-ABI device shim (lc3_shim.h): context, uploads, launch                                          */
@@ -2946,6 +2976,22 @@ extern "C" __global__ void lc3_encode_kernel_big_var(const lc3d_plan* __restrict
                                                      lc3d_trace* __restrict__ trace, int* __restrict__ dump, int dstride, const float* __restrict__ y12,
                                                      uint8_t* __restrict__ status, int dT, int dt0, const float* __restrict__ spec, const float* __restrict__ frec,
                                                      const float* __restrict__ xnext, const uint16_t* __restrict__ fsz, const lc3d_chan* __restrict__ etab);
+/* per-frame bandwidths (-DLC3_ENC_VBW objects): bwf [stream][frames of the call] in Hz, behind the arguments of the kernels they vary */
+extern "C" __global__ void lc3_encode_kernel_vbw(const lc3d_plan* __restrict__ P, const lc3d_chan* __restrict__ chans, float* __restrict__ state,
+                                                 const void* __restrict__ pcm, int bitdepth, int T, uint8_t* __restrict__ out, int out_stride, int ncs,
+                                                 lc3d_trace* __restrict__ trace, int* __restrict__ dump, int dstride, const float* __restrict__ y12,
+                                                 uint8_t* __restrict__ status, int dT, int dt0, const float* __restrict__ spec, const float* __restrict__ frec,
+                                                 const float* __restrict__ xnext, const uint16_t* __restrict__ bwf);
+extern "C" __global__ void lc3_encode_kernel_var_vbw(const lc3d_plan* __restrict__ P, const lc3d_chan* __restrict__ chans, float* __restrict__ state,
+                                                     const void* __restrict__ pcm, int bitdepth, int T, uint8_t* __restrict__ out, int out_stride, int ncs,
+                                                     lc3d_trace* __restrict__ trace, int* __restrict__ dump, int dstride, const float* __restrict__ y12,
+                                                     uint8_t* __restrict__ status, int dT, int dt0, const float* __restrict__ spec, const float* __restrict__ frec,
+                                                     const float* __restrict__ xnext, const uint16_t* __restrict__ fsz, const lc3d_chan* __restrict__ etab,
+                                                     const uint16_t* __restrict__ bwf);
+extern "C" __global__ void lc3_enc_shape_kernel_vbw(const lc3d_plan* __restrict__ P, const lc3d_chan* __restrict__ chans, int T, int tb, int nt, int fpw, int ncs,
+                                                    float* __restrict__ rows, int srow, float* __restrict__ frec, const uint16_t* __restrict__ bwf);
+extern "C" __global__ void lc3_enc_shape_lane_kernel_vbw(const lc3d_plan* __restrict__ P, const lc3d_chan* __restrict__ chans, int RT, int r0, int nt, int ncs,
+                                                         float* __restrict__ rows, int srow, float* __restrict__ frec, const uint16_t* __restrict__ bwf);
 extern "C" __global__ void lc3_enc_front_kernel_big(const lc3d_plan* __restrict__ P, const lc3d_chan* __restrict__ chans, const float* __restrict__ state, const void* __restrict__ pcm,
                                                     int bitdepth, int T, int tb, int nt, int fpw, int ncs, float* __restrict__ spec, int srow, int RT, int r0, float* __restrict__ rec, float* __restrict__ xnext, const float* __restrict__ xprev, int xprev_stride, int do_scf);
 extern "C" __global__ void lc3_enc_shape_kernel_big(const lc3d_plan* __restrict__ P, const lc3d_chan* __restrict__ chans, int T, int tb, int nt, int fpw, int ncs,
@@ -3081,6 +3127,12 @@ struct lc3hip_ctx {
     /* lc3hip_upload_chans_async: the configuration a per-frame-bitrate call leaves, queued on its stream behind its kernels from pinned staging; every later
      * call waits for the copy (ev_chans) on its own stream - and for the last stream-lifecycle call (lc3hip_stream_state), which records the same event */
     lc3d_chan* h_chans; hipEvent_t ev_chans; int chans_armed;
+    /* per-frame bandwidths: per call the words in force, through pinned staging in LC3D_SETS rotating buffers as the sizes above.  The copy of a call goes on
+     * the stream of the first kernel that reads the words (bw_to): on the pipelined path a side stream, so that a call that overlaps its predecessor does not
+     * wait for that call's tail on the caller's stream; kernels on another stream wait for ev_bwcp.  bw_src / bw_bytes / bw_on: the pending call's copy. */
+    int cfg_fresh;      /* a copy of lc3hip_upload_chans_async that the side streams are not yet ordered behind: 1 bandwidth words only, 2 more (enc_launch) */
+    uint16_t* d_bw[LC3D_SETS]; uint16_t* h_bw[LC3D_SETS]; size_t bw_cap; hipEvent_t ev_bw[LC3D_SETS]; int bw_armed[LC3D_SETS], bw_set;
+    const uint16_t* bw_src; size_t bw_bytes; hipStream_t bw_on; hipEvent_t ev_bwcp;
     lc3hip_ss ss;                                   /* lc3hip_set_template, lc3hip_stream_state */
 };
 
@@ -3210,9 +3262,10 @@ extern "C" int lc3hip_set_template(void* ctx, const float* tmpl)
 }
 
 static int chans_host_side(lc3hip_ctx* c, const lc3d_chan* chans, int first, int count);
-extern "C" int lc3hip_upload_chans_async(void* ctx, const lc3d_chan* chans, int first, int count, void* hip_stream)
+extern "C" int lc3hip_upload_chans_async(void* ctx, const lc3d_chan* chans, int first, int count, void* hip_stream, int bw_only)
 {
     lc3hip_ctx* c = (lc3hip_ctx*)ctx;
+    c->cfg_fresh = bw_only ? 1 : 2;
     HIPCHK(hipSetDevice(c->device));
     hipStream_t s = hip_stream ? (hipStream_t)hip_stream : c->stream;
     if (!c->h_chans) HIPCHK(hipHostMalloc((void**)&c->h_chans, sizeof(lc3d_chan) * (size_t)c->ncs, hipHostMallocDefault));
@@ -3280,8 +3333,10 @@ static void launch_resample(lc3hip_ctx* c, hipStream_t st, const void* dpcm, int
     else
         hipLaunchKernelGGL(lc3_enc_resample_kernel, dim3((unsigned)c->ncs * pruns), dim3(WAVE), 0, st, c->d_plan, c->d_state, c->state_words, mc, dpcm, bitdepth, n_frames, hb, hn, c->ncs, dy12, xprev, xprev_stride);
 }
+static int bw_to(lc3hip_ctx* c, hipStream_t st);
 static int enc_launch(lc3hip_ctx* c, const void* dpcm, int bitdepth, int n_frames, uint8_t* dout, int out_stride, hipStream_t s, lc3d_trace* dtr,
-                      int dT, int dt0, bool pack, const uint16_t* dfsz /* per-frame bitrates: [stream][dT] stream-frame bytes, or null */)
+                      int dT, int dt0, bool pack, const uint16_t* dfsz /* per-frame bitrates: [stream][dT] stream-frame bytes, or null */,
+                      const uint16_t* dbw /* per-frame bandwidths: [stream][dT] Hz in force (stage_bw), or null; the path is the one without them */)
 {
     /* two kernels: lc3_encode_kernel (one wave per channel-stream, frames in order) leaves each frame's parameters and quantised
      * spectrum in a record; lc3_enc_pack_kernel (one channel-frame per lane, any frame size) writes the bytes.  With stage traces,
@@ -3326,14 +3381,18 @@ static int enc_launch(lc3hip_ctx* c, const void* dpcm, int bitdepth, int n_frame
     float* rows_for_pack = nullptr; const float* frec_for_pack = nullptr;      /* pipelined path: the bitstream writer starts from the shaped spectra (frame-parallel tail, one frame per lane) */
     const int mc = c->big ? LC3D_MEMCAP_BIG : LC3D_MEMCAP_STD;
     if (!split) {
-        c->ahead_ok = 0; c->last_frec = nullptr; c->last_frec_frames = 0;
+        c->ahead_ok = 0; c->last_frec = nullptr; c->last_frec_frames = 0; c->cfg_fresh = 0;
         /* everything in lc3_encode_kernel (traced, diagnostic and very short launches), behind the 12.8 kHz pre-kernels when they apply */
         if (dy12) {
             launch_resample(c, s, dpcm, bitdepth, n_frames, 0, n_frames, mc, dy12, c->d_state + LC3D_ST_XPREV, c->state_words);
             hipLaunchKernelGGL(lc3_enc_hp50_kernel, dim3((unsigned)((c->ncs + WAVE - 1) / WAVE)), dim3(WAVE), 0, s, c->d_plan, c->d_state, c->state_words, LC3D_ST_SCAL(mc), n_frames, 0, n_frames, c->ncs, dy12);
             HIPCHK(hipGetLastError());
         }
-        if (dfsz && c->big) hipLaunchKernelGGL(lc3_encode_kernel_big_var, dim3(c->ncs), dim3(WAVE), 0, s, c->d_plan, c->d_chans, c->d_state, dpcm, bitdepth, n_frames,
+        if (dbw && bw_to(c, s)) return 1;
+        if (dfsz && dbw) hipLaunchKernelGGL(lc3_encode_kernel_var_vbw, dim3(c->ncs), dim3(WAVE), 0, s, c->d_plan, c->d_chans, c->d_state, dpcm, bitdepth, n_frames,
+                                            dout, out_stride, c->ncs, dtr, ddump, dstride, dy12, c->d_status, dT, dt0, (const float*)nullptr, (const float*)nullptr,
+                                            (const float*)nullptr, dfsz, (const lc3d_chan*)c->d_etab, dbw);
+        else if (dfsz && c->big) hipLaunchKernelGGL(lc3_encode_kernel_big_var, dim3(c->ncs), dim3(WAVE), 0, s, c->d_plan, c->d_chans, c->d_state, dpcm, bitdepth, n_frames,
                                                dout, out_stride, c->ncs, dtr, ddump, dstride, dy12, c->d_status, dT, dt0, (const float*)nullptr, (const float*)nullptr,
                                                (const float*)nullptr, dfsz, (const lc3d_chan*)c->d_etab);
         else if (dfsz) hipLaunchKernelGGL(lc3_encode_kernel_var, dim3(c->ncs), dim3(WAVE), 0, s, c->d_plan, c->d_chans, c->d_state, dpcm, bitdepth, n_frames,
@@ -3341,6 +3400,9 @@ static int enc_launch(lc3hip_ctx* c, const void* dpcm, int bitdepth, int n_frame
                                           (const float*)nullptr, dfsz, (const lc3d_chan*)c->d_etab);
         else if (c->big) hipLaunchKernelGGL(lc3_encode_kernel_big, dim3(c->ncs), dim3(WAVE), 0, s, c->d_plan, c->d_chans, c->d_state, dpcm, bitdepth, n_frames,
                                        dout, out_stride, c->ncs, dtr, ddump, dstride, dy12, c->d_status, dT, dt0, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr);
+        else if (dbw) hipLaunchKernelGGL(lc3_encode_kernel_vbw, dim3(c->ncs), dim3(WAVE), 0, s, c->d_plan, c->d_chans, c->d_state, dpcm, bitdepth, n_frames,
+                                         dout, out_stride, c->ncs, dtr, ddump, dstride, dy12, c->d_status, dT, dt0, (const float*)nullptr, (const float*)nullptr,
+                                         (const float*)nullptr, dbw);
         else hipLaunchKernelGGL(lc3_encode_kernel, dim3(c->ncs), dim3(WAVE), 0, s, c->d_plan, c->d_chans, c->d_state, dpcm, bitdepth, n_frames,
                                 dout, out_stride, c->ncs, dtr, ddump, dstride, dy12, c->d_status, dT, dt0, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr);
     } else {
@@ -3398,7 +3460,12 @@ static int enc_launch(lc3hip_ctx* c, const void* dpcm, int bitdepth, int n_frame
          * the previous one: ev_done); the MDCT memory before frame 0 is read from the previous call's hand-over (two alternating buffers),
          * not from the state that call's last rate kernel is still to update. */
         const int amax = c->opt.ahead_max ? c->opt.ahead_max : LC3D_AHEAD_MAX_FRAMES;
-        const bool ahead = c->input_ready && n_frames <= amax && c->ahead_ok && c->ahead_T == n_frames && c->ahead_R == R && c->last_stream == s && dt0 == 0 && dT == n_frames && pack;
+        /* A configuration copy queued behind the previous call (lc3hip_upload_chans_async) is on s, which a call that overlaps does not wait for: only a
+         * per-frame-bandwidth call overlaps it, and only when that copy changed nothing but the bandwidth words, which its kernels do not read (the other words
+         * are rewritten with their own values).  A call that forks from s is behind the copy, and so is everything after it. */
+        const bool cfg_ok = c->cfg_fresh == 0 || (c->cfg_fresh == 1 && dbw);
+        const bool ahead = c->input_ready && n_frames <= amax && c->ahead_ok && c->ahead_T == n_frames && c->ahead_R == R && c->last_stream == s && dt0 == 0 && dT == n_frames && pack && cfg_ok;
+        if (!ahead) c->cfg_fresh = 0;
         float* xn_w = c->d_xnext[c->xn_par];                         /* written by this call's front kernel */
         /* one buffer more than calls in flight: the one written now was last read by the call LC3D_SETS back (its resampler and front) and by the
          * rate kernel of the call before that, all finished before the bitstream writer this call's side streams have waited for */
@@ -3485,7 +3552,10 @@ static int enc_launch(lc3hip_ctx* c, const void* dpcm, int bitdepth, int n_frame
                 if (son) { HIPCHK(hipEventRecord(c->ev_f[k], c->s_ln)); HIPCHK(hipStreamWaitEvent(s, c->ev_f[k], 0)); }
                 if (sop) { HIPCHK(hipEventRecord(c->ev_v[k], c->s_ln)); HIPCHK(hipStreamWaitEvent(ss, c->ev_v[k], 0)); }
                 const int swave = c->opt.shape_wave;
-                if (!swave) DUPL('a') hipLaunchKernelGGL(lc3_enc_shape_lane_kernel, dim3((unsigned)(((long long)c->ncs * nt + WAVE - 1) / WAVE)), dim3(WAVE), 0, ss, c->d_plan, c->d_chans, dT, dt0 + tb, nt, c->ncs, dspec, c->srow, dfrec);
+                if (dbw && bw_to(c, ss)) return 1;
+                if (dbw && !swave) hipLaunchKernelGGL(lc3_enc_shape_lane_kernel_vbw, dim3((unsigned)(((long long)c->ncs * nt + WAVE - 1) / WAVE)), dim3(WAVE), 0, ss, c->d_plan, c->d_chans, dT, dt0 + tb, nt, c->ncs, dspec, c->srow, dfrec, dbw);
+                else if (dbw) hipLaunchKernelGGL(lc3_enc_shape_kernel_vbw, dim3((unsigned)c->ncs * sruns), dim3(WAVE), 0, ss, c->d_plan, c->d_chans, dT, dt0 + tb, nt, spw, c->ncs, dspec, c->srow, dfrec, dbw);
+                else if (!swave) DUPL('a') hipLaunchKernelGGL(lc3_enc_shape_lane_kernel, dim3((unsigned)(((long long)c->ncs * nt + WAVE - 1) / WAVE)), dim3(WAVE), 0, ss, c->d_plan, c->d_chans, dT, dt0 + tb, nt, c->ncs, dspec, c->srow, dfrec);
                 else if (c->big) hipLaunchKernelGGL(lc3_enc_shape_kernel_big, dim3((unsigned)c->ncs * sruns), dim3(WAVE), 0, ss, c->d_plan, c->d_chans, dT, dt0 + tb, nt, spw, c->ncs, dspec, c->srow, dfrec);
                 else DUPL('a') hipLaunchKernelGGL(lc3_enc_shape_kernel, dim3((unsigned)c->ncs * sruns), dim3(WAVE), 0, ss, c->d_plan, c->d_chans, dT, dt0 + tb, nt, spw, c->ncs, dspec, c->srow, dfrec);
                 HIPCHK(hipGetLastError());
@@ -3573,7 +3643,8 @@ static bool host_ptr_is_pinned(const void* p)
  * overlaps with the GPU work of the previous run.  The bitstream writer runs ONCE behind the last run over all frames of the call (one
  * frame per lane makes it latency bound: per run it would cost as much as for the whole call), then the frames come down in one
  * linear copy.  State stays on the device between runs.  The first run is short so that the kernels start early. */
-static int encode_host(lc3hip_ctx* c, const void* pcm, int bitdepth, int n_frames, void* out, int out_stride, hipStream_t s, const uint16_t* dfsz)
+static int encode_host(lc3hip_ctx* c, const void* pcm, int bitdepth, int n_frames, void* out, int out_stride, hipStream_t s, const uint16_t* dfsz,
+                       const uint16_t* dbw)
 {
     const size_t bps = bitdepth == 16 ? 2 : 4;
     const size_t fr_in = (size_t)c->channels * c->N * bps;                    /* bytes of one stream-frame of PCM */
@@ -3608,7 +3679,7 @@ static int encode_host(lc3hip_ctx* c, const void* pcm, int bitdepth, int n_frame
         }
         HIPCHK(hipEventRecord(c->ev_h2d[i], c->s_h2d));
         HIPCHK(hipStreamWaitEvent(s, c->ev_h2d[i], 0));
-        if (enc_launch(c, c->hp_dpcm[i], bitdepth, tc, c->d_out, out_stride, s, nullptr, n_frames, t0, t0 + tc >= n_frames, dfsz)) return 1;
+        if (enc_launch(c, c->hp_dpcm[i], bitdepth, tc, c->d_out, out_stride, s, nullptr, n_frames, t0, t0 + tc >= n_frames, dfsz, dbw)) return 1;
         HIPCHK(hipEventRecord(c->ev_k[i], s));
         t0 += tc;
     }
@@ -3652,20 +3723,59 @@ static int upload_fsz(lc3hip_ctx* c, const uint16_t* fsz_host, int n_frames, hip
     c->fsz_armed[k] = 1; c->fsz_set = (k + 1) % LC3D_SETS;
     return 0;
 }
+/* the bandwidths in force of a per-frame-bandwidth call into pinned staging, so that the caller's array is free when the call returns (the buffer pair of the
+ * call LC3D_SETS back is waited for before it is written again; sized on first use, a call of equal or smaller size allocates nothing); bw_to queues the copy */
+static int stage_bw(lc3hip_ctx* c, const uint16_t* bw_host, int n_frames, const uint16_t** dbw, hipEvent_t* ev)
+{
+    const size_t fb = sizeof(uint16_t) * (size_t)c->n_streams * n_frames;
+    const int k = c->bw_set;
+    if (c->bw_armed[k]) HIPCHK(hipEventSynchronize(c->ev_bw[k]));
+    if (c->bw_cap < fb) {
+        for (int i = 0; i < LC3D_SETS; i++) if (c->bw_armed[i]) { HIPCHK(hipEventSynchronize(c->ev_bw[i])); c->bw_armed[i] = 0; }      /* no call reads them any more */
+        for (int i = 0; i < LC3D_SETS; i++) {
+            if (c->d_bw[i]) HIPCHK(hipFree(c->d_bw[i])); if (c->h_bw[i]) HIPCHK(hipHostFree(c->h_bw[i])); c->d_bw[i] = nullptr; c->h_bw[i] = nullptr;
+        }
+        c->bw_cap = 0;
+        for (int i = 0; i < LC3D_SETS; i++) { HIPCHK(hipMalloc((void**)&c->d_bw[i], fb)); HIPCHK(hipHostMalloc((void**)&c->h_bw[i], fb, hipHostMallocDefault)); }
+        c->bw_cap = fb;
+    }
+    if (!c->ev_bwcp) {
+        for (int i = 0; i < LC3D_SETS; i++) HIPCHK(hipEventCreateWithFlags(&c->ev_bw[i], hipEventDisableTiming));
+        HIPCHK(hipEventCreateWithFlags(&c->ev_bwcp, hipEventDisableTiming));
+    }
+    memcpy(c->h_bw[k], bw_host, fb);
+    c->bw_src = c->h_bw[k]; c->bw_bytes = fb; c->bw_on = nullptr;
+    *dbw = c->d_bw[k]; *ev = c->ev_bw[k];
+    c->bw_armed[k] = 1; c->bw_set = (k + 1) % LC3D_SETS;
+    return 0;
+}
+static int bw_to(lc3hip_ctx* c, hipStream_t st)
+{
+    const int k = (c->bw_set + LC3D_SETS - 1) % LC3D_SETS;                    /* the slot stage_bw filled for this call */
+    if (!c->bw_on) {
+        HIPCHK(hipMemcpyAsync(c->d_bw[k], c->bw_src, c->bw_bytes, hipMemcpyHostToDevice, st));
+        HIPCHK(hipEventRecord(c->ev_bwcp, st)); c->bw_on = st;
+    } else if (c->bw_on != st) HIPCHK(hipStreamWaitEvent(st, c->ev_bwcp, 0));
+    return 0;
+}
 extern "C" int lc3hip_encode(void* ctx, const void* pcm, int pcm_on_device, int bitdepth, int n_frames, void* out, int out_stride,
-                             int out_on_device, void* hip_stream, int sync, void* trace_host, const uint16_t* fsz_host)
+                             int out_on_device, void* hip_stream, int sync, void* trace_host, const uint16_t* fsz_host, const uint16_t* bw_host)
 {
     lc3hip_ctx* c = (lc3hip_ctx*)ctx;
     HIPCHK(hipSetDevice(c->device));
     if (!hip_stream && !c->stream) HIPCHK(hipStreamCreate(&c->stream));
     hipStream_t s = hip_stream ? (hipStream_t)hip_stream : c->stream;
     const uint16_t* dfsz = nullptr; hipEvent_t ev_fsz = nullptr;
+    const uint16_t* dbw = nullptr; hipEvent_t ev_bw = nullptr;
     if (fsz_host && !c->d_etab) return 1;
+    if (bw_host && c->big) return 1;            /* no large-layout kernels: that layout only serves high-resolution batches, which the host refuses */
     if (!pcm_on_device && !out_on_device && !trace_host) {
         if (c->chans_armed) HIPCHK(hipStreamWaitEvent(s, c->ev_chans, 0));
         if (fsz_host && upload_fsz(c, fsz_host, n_frames, s, &dfsz, &ev_fsz)) return 1;
-        if (encode_host(c, pcm, bitdepth, n_frames, out, out_stride, s, dfsz)) return 1;
+        if (bw_host && stage_bw(c, bw_host, n_frames, &dbw, &ev_bw)) return 1;
+        if (encode_host(c, pcm, bitdepth, n_frames, out, out_stride, s, dfsz, dbw)) return 1;
         if (ev_fsz) HIPCHK(hipEventRecord(ev_fsz, s));
+        if (ev_bw) HIPCHK(hipEventRecord(ev_bw, s));
         return 0;
     }
     const size_t bps = bitdepth == 16 ? 2 : 4;
@@ -3704,10 +3814,12 @@ extern "C" int lc3hip_encode(void* ctx, const void* pcm, int pcm_on_device, int 
     /* behind the LC3PLUS_CHECK_READY test, which must see no copy of ours pending on s */
     if (c->chans_armed) HIPCHK(hipStreamWaitEvent(s, c->ev_chans, 0));
     if (fsz_host && upload_fsz(c, fsz_host, n_frames, s, &dfsz, &ev_fsz)) return 1;
+    if (bw_host && stage_bw(c, bw_host, n_frames, &dbw, &ev_bw)) return 1;
     HIPCHK(hipEventRecord(c->ev0, s));
-    if (enc_launch(c, dpcm, bitdepth, n_frames, dout, out_stride, s, dtr, n_frames, 0, true, dfsz)) return 1;
+    if (enc_launch(c, dpcm, bitdepth, n_frames, dout, out_stride, s, dtr, n_frames, 0, true, dfsz, dbw)) return 1;
     HIPCHK(hipEventRecord(c->ev1, s));
     if (ev_fsz) HIPCHK(hipEventRecord(ev_fsz, s));
+    if (ev_bw) HIPCHK(hipEventRecord(ev_bw, s));      /* the end of the call on s lies behind every kernel that read the words, on whichever stream */
     if (c->opt.check_ready && c->ev_ours) { HIPCHK(hipEventRecord(c->ev_ours, s)); c->ours_armed = 1; }
     if (!out_on_device) HIPCHK(hipMemcpyAsync(out, dout, out_bytes, hipMemcpyDeviceToHost, s));
     if (trace_host) HIPCHK(hipMemcpyAsync(trace_host, dtr, sizeof(lc3d_trace) * (size_t)c->ncs * n_frames, hipMemcpyDeviceToHost, s));
@@ -3824,6 +3936,8 @@ extern "C" int lc3hip_destroy(void* ctx)
     if (c->ev_chans) hipEventDestroy(c->ev_chans);
     ss_free(&c->ss);
     for (int i = 0; i < LC3D_SETS; i++) { if (c->d_fsz[i]) hipFree(c->d_fsz[i]); if (c->h_fsz[i]) hipHostFree(c->h_fsz[i]); if (c->ev_fsz[i]) hipEventDestroy(c->ev_fsz[i]); }
+    for (int i = 0; i < LC3D_SETS; i++) { if (c->d_bw[i]) hipFree(c->d_bw[i]); if (c->h_bw[i]) hipHostFree(c->h_bw[i]); if (c->ev_bw[i]) hipEventDestroy(c->ev_bw[i]); }
+    if (c->ev_bwcp) hipEventDestroy(c->ev_bwcp);
     for (int i = 0; i < 2; i++) {
         if (c->hp_dpcm[i]) hipFree(c->hp_dpcm[i]);
         if (c->hp_pin_in[i]) hipHostFree(c->hp_pin_in[i]);
@@ -4208,4 +4322,4 @@ extern "C" int lc3hip_dec_destroy(void* ctx)
     return 0;
 }
 #endif /* !LC3_BIG */
-#endif  /* LC3_ENC_VAR */
+#endif  /* !LC3_ENC_VAR && !LC3_ENC_VBW */

@@ -135,6 +135,11 @@ static inline LC3D_HD int lc3d_dec_frame_class(int nb, int bfi, int in_stride, c
     return LC3D_FRAME_GOOD;
 }
 
+/* The bandwidth controller's words for a bandwidth of bw Hz (R/lc3.c:199-201, lc3_enc_set_bandwidth): the cut-off line and the cap on the
+ * detected bandwidth index.  The host's set_bandwidth and the per-frame-bandwidth kernels (lc3plus_enc_batch_encode_bandwidths) use these. */
+static inline LC3D_HD int lc3d_bw_cut_bin(int bw, int dms) { return (bw * dms) / 5000; }
+static inline LC3D_HD int lc3d_bw_index(int bw) { const int i = (bw / 4000) - 1; return i > 0 ? i : 0; }
+
 /* decoder state words per channel-stream */
 #define DST_IMEM   0                                   /* 600: IMDCT overlap memory (300 used by the standard layout) */
 #define DST_QPREV  600                                 /* 960: last good spectrum (concealment) */

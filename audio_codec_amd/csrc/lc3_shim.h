@@ -48,12 +48,15 @@ int   lc3hip_dec_destroy(void* ctx);
 int   lc3hip_create(void** ctx, const lc3d_plan* plan, int n_streams, int device);
 int   lc3hip_set_template(void* ctx, const float* tmpl);       /* one channel-stream's fresh state row (init_state): kept on the device, every row reset from it */
 int   lc3hip_upload_chans(void* ctx, const lc3d_chan* chans, int first, int count);
-/* the same, queued on hip_stream (NULL: the context's stream) behind the work already there, without waiting for it; later calls wait for the copy */
-int   lc3hip_upload_chans_async(void* ctx, const lc3d_chan* chans, int first, int count, void* hip_stream);
+/* the same, queued on hip_stream (NULL: the context's stream) behind the work already there, without waiting for it; later calls wait for the copy.
+ * bw_only: the copy changes the bandwidth words alone (a following per-frame-bandwidth call may still overlap the call before it) */
+int   lc3hip_upload_chans_async(void* ctx, const lc3d_chan* chans, int first, int count, void* hip_stream, int bw_only);
 int   lc3hip_upload_enc_table(void* ctx, const lc3d_chan* tab, int n);   /* encoder configuration per channel byte count 0 .. n - 1 (per-frame bitrates) */
-/* fsz_host: null, or [n_streams][n_frames] bytes of every stream-frame (per-frame bitrates; the host has checked them against the table) */
+/* fsz_host: null, or [n_streams][n_frames] bytes of every stream-frame (per-frame bitrates; the host has checked them against the table).
+ * bw_host: null, or [n_streams][n_frames] the bandwidth in force of every stream-frame in Hz (per-frame bandwidths; resolved and checked by the host,
+ * standard layout only); the call takes the path it takes without it */
 int   lc3hip_encode(void* ctx, const void* pcm, int pcm_on_device, int bitdepth, int n_frames, void* out, int out_stride,
-                    int out_on_device, void* hip_stream, int sync, void* trace_host, const uint16_t* fsz_host);
+                    int out_on_device, void* hip_stream, int sync, void* trace_host, const uint16_t* fsz_host, const uint16_t* bw_host);
 float lc3hip_last_ms(void* ctx);
 size_t lc3hip_state_bytes(void* ctx);                             /* checkpoint / resume of the per-stream state (include/lc3plus_batch.h) */
 int   lc3hip_get_state(void* ctx, void* host, size_t bytes);

@@ -62,6 +62,33 @@ LC3_Error lc3plus_enc_batch_encode_bitrates(lc3plus_batch* batch, const void* pc
                                             const int* bitrates, int n_frames, void* out, int out_stride, int out_on_device,
                                             int* num_bytes, void* hip_stream, int sync);
 
+/* Per-frame bandwidths, as the reference takes them (R/codec_exe.c:316-325: lc3_enc_set_bandwidth before every frame of a bandwidth switching file).
+ * Arguments as encode_bitrates(), and
+ *   bandwidths : host pointer, [n_streams][n_frames] bandwidth in Hz for each stream-frame; may be reused when the call returns
+ *   bitrates   : NULL, or as for encode_bitrates()
+ *   num_bytes  : host pointer or NULL, [n_streams][n_frames]; without bitrates every entry is num_bytes(stream)
+ * Frame t of stream s is encoded byte for byte as the reference encodes it right after lc3_enc_set_bitrate(bitrates[s][t]) (when bitrates are given)
+ * and then lc3_enc_set_bandwidth(bandwidths[s][t]): 0 switches the bandwidth controller off for the frame; a value set_bandwidth refuses
+ * (2 * bw > min(samplerate, 40000), R/lc3.c:193-199) keeps the bandwidth in force - the call still does all its work and returns LC3_BW_WARNING
+ * instead of LC3_OK.  Refused calls, checked in this order, queue nothing and leave the batch unchanged: a high-resolution batch
+ * (LC3_HRMODE_BW_ERROR, as set_bandwidth); a negative bandwidth, or a positive one whose cut-off line bw * frame_ms / 500 is below 1 (under 50 Hz at
+ * 10 ms, 100 Hz at 5 ms, 200 Hz at 2.5 ms): LC3_ERROR; NULL pointers, bitdepth and n_frames as encode(); a rate or out_stride as encode_bitrates().
+ * After the call each stream is configured with the bandwidth in force after its last frame (bandwidth(stream)), and with its last rate when
+ * bitrates were given; a following encode() continues from there.  Bandwidths stay configuration, not state: get_state / set_state and the stream
+ * blobs are unchanged.  The new configuration is queued on hip_stream behind the call's kernels, so a call with sync = 0 does not wait for them.
+ * Without bitrates the call takes the path encode() takes for the same n_frames, promise and switches - the pipelined kernels for longer calls, the
+ * overlap of consecutive equal-length calls under set_input_ready - and last_records / last_status report it as they report encode() (FR_BWC holds
+ * each frame's capped bandwidth index); with bitrates it runs the one-wave kernel of encode_bitrates().  The diagnostic switches LC3PLUS_ENC_FUSED,
+ * LC3PLUS_ENC_NO_SPLIT and LC3PLUS_ENC_SHAPE_WAVE select the same kernels as for encode(), each in its per-frame-bandwidth form, with the same bytes. */
+LC3_Error lc3plus_enc_batch_encode_bandwidths(lc3plus_batch* batch, const void* pcm, int pcm_on_device, int bitdepth,
+                                              const int* bandwidths, const int* bitrates, int n_frames, void* out, int out_stride,
+                                              int out_on_device, int* num_bytes, void* hip_stream, int sync);
+int       lc3plus_enc_batch_bandwidth(const lc3plus_batch* batch, int stream);     /* Hz in force, 0 = none; -1 on a bad argument */
+/* The per-frame rule of encode_bandwidths() on the host alone, no device: start [n_streams] the bandwidth in force before the call, bandwidths
+ * [n_streams][n_frames] -> in_force [n_streams][n_frames].  Returns LC3_OK, LC3_BW_WARNING where a value was refused, or the call's error. */
+LC3_Error lc3plus_enc_plan_bandwidths(int samplerate, float frame_ms, int hrmode, int n_streams, const int* start,
+                                      const int* bandwidths, int n_frames, int* in_force);
+
 /* Checkpoint / resume.  The cross-frame state of every channel-stream of the batch (MDCT / resampler memory, pitch and LTPF histories,
  * rate-control and attack-detector words; R/setup_enc_lc3.h:17-62) as one opaque host array of state_size() bytes.  A batch created with
  * the same (n_streams, samplerate, channels, frame_ms, hrmode, bitrates, bandwidths) that is given the state continues the streams

@@ -12,7 +12,8 @@
  *
  * Switching files (R/codec_exe.c:296-326, loopy_read64 :858-866) hold one int64 per frame and wrap around: the bitrate per channel
  * (-swf FILE, or a file name in place of BITRATE) and the audio bandwidth in Hz (-bandwidth FILE).  Frames go through the GPU in blocks of up
- * to 256 with one bitrate per frame (lc3plus_enc_batch_encode_bitrates); a change of bandwidth ends a block.
+ * to 256 with one bitrate per frame (lc3plus_enc_batch_encode_bitrates) and, with a bandwidth file, one bandwidth per frame
+ * (lc3plus_enc_batch_encode_bandwidths).  A bandwidth the reference refuses keeps the one in force, as lc3_enc_set_bandwidth does.
  */
 #include <stdint.h>
 #include <stdio.h>
@@ -131,30 +132,17 @@ int main(int ac, char** av)
     const int wide = w.bits != 16;
     void* pcm = calloc((size_t)CH * C * N, wide ? 4 : 2);
     uint8_t* out = (uint8_t*)malloc((size_t)CH * S);
-    int* rates = (int*)malloc(sizeof(int) * CH); int* sizes = (int*)malloc(sizeof(int) * CH);
-    if (!pcm || !out || !rates || !sizes) die("out of memory");
+    int* rates = (int*)malloc(sizeof(int) * CH); int* bws = (int*)malloc(sizeof(int) * CH); int* sizes = (int*)malloc(sizeof(int) * CH);
+    if (!pcm || !out || !rates || !bws || !sizes) die("out of memory");
     const int bps = w.bits / 8;
-    int cur_bitrate = bitrate, cur_bw = bandwidth;
     uint32_t f0 = 0;
     while (f0 < total_frames) {
-        /* settings of frame f0 (the reference applies them before reading the frame, R/codec_exe.c:296-326) */
-        int64_t nbr = fswf ? loopy_read64(fswf) * C : cur_bitrate, nbw = fbwf ? loopy_read64(fbwf) : cur_bw;
-        if ((int)nbw != cur_bw) {
-            err = lc3plus_enc_batch_set_bandwidth(b, 0, (int)nbw); if (err && err < LC3_WARNING) die("bandwidth error");
-            cur_bw = (int)nbw;
-        }
-        /* a block of up to CH frames with one rate per frame (lc3plus_enc_batch_encode_bitrates, as the reference's lc3_enc_set_bitrate before
-         * every frame); only a bandwidth change ends it */
-        rates[0] = (int)nbr;
-        int T = 1;
-        while (T < CH && f0 + T < total_frames) {
-            if (fbwf) {
-                const long ps = fswf ? ftell(fswf) : 0, pb = ftell(fbwf);
-                const int64_t br2 = fswf ? loopy_read64(fswf) * C : cur_bitrate, bw2 = loopy_read64(fbwf);
-                if ((int)bw2 != cur_bw) { if (fswf) fseek(fswf, ps, SEEK_SET); fseek(fbwf, pb, SEEK_SET); break; }
-                rates[T] = (int)br2;
-            } else rates[T] = fswf ? (int)(loopy_read64(fswf) * C) : cur_bitrate;
-            T++;
+        /* a block of up to CH frames with the settings of every frame (the reference applies them before reading the frame, R/codec_exe.c:296-326:
+         * lc3_enc_set_bitrate, then lc3_enc_set_bandwidth) */
+        const int T = total_frames - f0 < (uint32_t)CH ? (int)(total_frames - f0) : CH;
+        for (int t = 0; t < T; t++) {
+            rates[t] = fswf ? (int)(loopy_read64(fswf) * C) : bitrate;
+            if (fbwf) bws[t] = (int)loopy_read64(fbwf);
         }
         memset(pcm, 0, (size_t)T * C * N * (wide ? 4 : 2));
         for (int t = 0; t < T; t++) for (int n = 0; n < N; n++) {                 /* de-interleave into [frame][channel][N] */
@@ -168,10 +156,12 @@ int main(int ac, char** av)
                 else ((int32_t*)pcm)[o] = ((int32_t)rd32(p)) >> 8;   /* the reference reader narrows 32-bit WAV to 24 bit (R/tinywavein_c.h:528-533) and still calls lc3_enc32 */
             }
         }
-        if (fswf) {
+        if (fbwf) {
+            err = lc3plus_enc_batch_encode_bandwidths(b, pcm, 0, w.bits, bws, fswf ? rates : NULL, T, out, S, 0, sizes, NULL, 1);
+            if (err && err < LC3_WARNING) { fprintf(stderr, "lc3plus_enc_cli: encode failed (LC3_Error %d)\n", (int)err); return 1; }
+        } else if (fswf) {
             err = lc3plus_enc_batch_encode_bitrates(b, pcm, 0, w.bits, rates, T, out, S, 0, sizes, NULL, 1);
             if (err) { fprintf(stderr, "lc3plus_enc_cli: encode failed (LC3_Error %d)\n", (int)err); return 1; }
-            cur_bitrate = rates[T - 1];
         } else {
             err = lc3plus_enc_batch_encode(b, pcm, 0, w.bits, T, out, S, 0, NULL, 1);
             if (err) { fprintf(stderr, "lc3plus_enc_cli: encode failed (LC3_Error %d)\n", (int)err); return 1; }
@@ -199,6 +189,6 @@ int main(int ac, char** av)
     if (!quiet) puts("\nProcessing done!");
     fclose(fo);
     lc3plus_enc_batch_destroy(b);
-    free(pcm); free(out); free(rates); free(sizes);
+    free(pcm); free(out); free(rates); free(bws); free(sizes);
     return 0;
 }
