@@ -32,7 +32,10 @@ EXPORTS = [
     "lc3plus_enc_batch_stream_state_size", "lc3plus_enc_batch_reset_streams", "lc3plus_enc_batch_export_streams", "lc3plus_enc_batch_import_streams",
     "lc3plus_dec_batch_stream_state_size", "lc3plus_dec_batch_reset_streams", "lc3plus_dec_batch_export_streams", "lc3plus_dec_batch_import_streams",
     "lc3plus_enc_batch_encode_bandwidths", "lc3plus_enc_batch_bandwidth", "lc3plus_enc_plan_bandwidths",
+    "lc3plus_enc_batch_encode_rates_device", "lc3plus_enc_plan_rates_lenient",
 ]
+# flag bits of Batch.encode_device_rates (lc3plus_enc_batch_encode_rates_device)
+ENC_FL_RATE, ENC_FL_BW_REFUSED, ENC_FL_BW_RANGE = 1, 2, 4
 LC3_BW_WARNING = 18
 
 
@@ -69,6 +72,10 @@ def load_library():
                                                           C.c_int, C.c_void_p, C.c_void_p, C.c_int]
         L.lc3plus_enc_batch_bandwidth.argtypes = [C.c_void_p, C.c_int]
         L.lc3plus_enc_plan_bandwidths.argtypes = [C.c_int, C.c_float, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        L.lc3plus_enc_batch_encode_rates_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
+                                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+        L.lc3plus_enc_plan_rates_lenient.argtypes = [C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                     C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.lc3plus_enc_batch_last_kernel_ms.restype = C.c_float
         L.lc3plus_enc_batch_last_kernel_ms.argtypes = [C.c_void_p]
         L.lc3plus_enc_batch_last_status.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
@@ -389,6 +396,19 @@ class Batch(_StreamLifecycle):
         if rc:
             raise LC3Error(rc, "lc3plus_enc_batch_encode(device)")
 
+    def encode_device_rates(self, d_pcm_ptr, bitdepth, T, d_out_ptr, out_stride, d_bitrates_ptr=None, d_bandwidths_ptr=None, d_num_bytes_ptr=None,
+                            d_flags_ptr=None, hip_stream=None, sync=False):
+        """Per-frame rates and / or bandwidths in device memory (lc3plus_enc_batch_encode_rates_device): raw device pointers only - pcm
+        [n_streams, T, channels, N], out [n_streams, T, out_stride] uint8, bitrates and bandwidths [n_streams, T] int32 (either may be None, not both),
+        num_bytes [n_streams, T] int32 and flags [n_streams, T] uint8 (None or written).  Queued on hip_stream; returns at once unless sync.  A rate or
+        bandwidth the host forms refuse does not fail the call: the frame keeps the carried value and is flagged (ENC_FL_*)."""
+        def p(x):
+            return C.c_void_p(x) if x else None
+        rc = self.lib.lc3plus_enc_batch_encode_rates_device(self.h, p(d_pcm_ptr), bitdepth, p(d_bitrates_ptr), p(d_bandwidths_ptr), T, p(d_out_ptr),
+                                                            out_stride, p(d_num_bytes_ptr), p(d_flags_ptr), p(hip_stream), 1 if sync else 0)
+        if rc:
+            raise LC3Error(rc, "lc3plus_enc_batch_encode_rates_device")
+
     def last_kernel_ms(self):
         return float(self.lib.lc3plus_enc_batch_last_kernel_ms(self.h))
 
@@ -435,6 +455,23 @@ def enc_plan_bandwidths(samplerate, frame_ms, hrmode, start, bandwidths):
     if rc not in (0, LC3_BW_WARNING):
         raise LC3Error(rc, "lc3plus_enc_plan_bandwidths")
     return f, rc
+
+
+def enc_plan_rates_lenient(samplerate, channels, frame_ms, hrmode, start_rates, start_bw, bitrates=None, bandwidths=None, out_stride=1 << 20):
+    """The per-frame rule of Batch.encode_device_rates on the host (test hook lc3plus_enc_plan_rates_lenient, no device needed): start_rates,
+    start_bw [n_streams] the configuration before the call, bitrates / bandwidths None or [n_streams, n_frames] -> (LC3_Error code, num_bytes int32,
+    bandwidth in force int32, flags uint8 [n_streams, n_frames], last rates int32 [n_streams])."""
+    L = load_library()
+    br = np.ascontiguousarray(np.atleast_2d(np.asarray(bitrates)), dtype=np.int32) if bitrates is not None else None
+    bw = np.ascontiguousarray(np.atleast_2d(np.asarray(bandwidths)), dtype=np.int32) if bandwidths is not None else None
+    S, T = (br if br is not None else bw).shape
+    sr = np.ascontiguousarray(np.broadcast_to(np.asarray(start_rates, dtype=np.int32), (S,)), dtype=np.int32)
+    sb = np.ascontiguousarray(np.broadcast_to(np.asarray(start_bw, dtype=np.int32), (S,)), dtype=np.int32)
+    nb = np.zeros((S, T), np.int32); inf = np.zeros((S, T), np.int32); fl = np.zeros((S, T), np.uint8); end = np.zeros(S, np.int32)
+    rc = L.lc3plus_enc_plan_rates_lenient(samplerate, channels, frame_ms, hrmode, S, sr.ctypes.data, sb.ctypes.data,
+                                          br.ctypes.data if br is not None else None, bw.ctypes.data if bw is not None else None, T, int(out_stride),
+                                          nb.ctypes.data, inf.ctypes.data, fl.ctypes.data, end.ctypes.data)
+    return rc, nb, inf, fl, end
 
 
 class Encoder:

@@ -7,6 +7,7 @@
  * reference evaluates them, and moves buffers.  There is no CPU encode path: without a HIP device every encode
  * call fails with LC3_ERROR.
  */
+#include <limits.h>
 #include <math.h>
 #include <stddef.h>
 #include <stdio.h>
@@ -134,6 +135,7 @@ static LC3_Error derive_bitrate(const geom_t* g, int bitrate, lc3d_chan* ch /* [
     for (int c = 0; c < g->channels; c++) {
         derive_chan(g, totalBytes / g->channels + (c < (totalBytes % g->channels)), &ch[c]);
         ch[c].out_off = off; off += ch[c].nbytes;
+        ch[c].bitrate = bitrate;
     }
     return LC3_OK;
 }
@@ -157,10 +159,8 @@ static LC3_Error enc_plan_bitrates(const geom_t* g, const int* bitrates, size_t 
     LC3_Error e = bitrate_limits(g, &lo, &hi);
     if (e) return e;
     for (size_t i = 0; i < n; i++) {
-        const int br = bitrates[i];
-        if (br <= 0 || br < lo || br > hi) return LC3_BITRATE_ERROR;
-        const int tb = br * g->N / (8 * g->fs_in);
-        if (tb / g->channels < 1 || (tb + g->channels - 1) / g->channels > enc_max_chan_bytes(g)) return LC3_BITRATE_ERROR;   /* inside the table (always, by the limits) */
+        const int tb = lc3d_enc_rate_bytes(bitrates[i], lo, hi, g->N, g->fs_in, g->channels, enc_max_chan_bytes(g), INT_MAX);   /* (inside the table always, by the limits) */
+        if (tb < 0) return LC3_BITRATE_ERROR;
         fsz[i] = (uint16_t)tb;
         if (tb > mx) mx = tb;
     }
@@ -370,7 +370,29 @@ struct lc3plus_batch {
     void* dev;
     uint16_t* fsz; size_t fsz_cap;  /* per-frame bitrates: stream-frame sizes of enc_plan_bitrates, grown as needed */
     uint16_t* bwf; size_t bwf_cap;  /* per-frame bandwidths: the values in force of enc_plan_bandwidths, grown as needed */
+    int chans_stale;                /* a call with rates or bandwidths in device memory has changed the configuration on the device: enc_refresh before reading chans */
+    int stride_bound;               /* while chans is stale: the out_stride an encode() needs (stride() before those calls, raised to the out_stride of each with rates) */
+    int bw_unsafe;                  /* set_bandwidth has installed a value with a cut-off line below 1 since the last read-back */
 };
+
+static void batch_restride(lc3plus_batch* b);
+/* Brings the host copy of the configuration back after calls with rates or bandwidths in device memory: waits for the batch's last call and downloads it, once. */
+static LC3_Error enc_refresh(lc3plus_batch* b)
+{
+    if (!b->chans_stale) return LC3_OK;
+    if (lc3hip_download_chans(b->dev, b->chans)) return LC3_ERROR;
+    const int C = b->g.channels;
+    b->bw_unsafe = 0;
+    for (int i = 0; i < b->n_streams; i++) {
+        b->bitrates[i] = b->chans[(size_t)i * C].bitrate;
+        if (!lc3d_bw_value_ok(b->chans[(size_t)i * C].bandwidth, b->g.dms)) b->bw_unsafe = 1;
+    }
+    batch_restride(b);
+    b->chans_stale = 0;
+    return LC3_OK;
+}
+/* the smallest out_stride encode() accepts: stride(), or while the host's copy is stale the bound those calls have left (no read-back) */
+static int enc_stride_bound(const lc3plus_batch* b) { return b->chans_stale ? b->stride_bound : b->stride; }
 
 static LC3_Error batch_upload(lc3plus_batch* b, int first_stream, int count)
 {
@@ -439,10 +461,12 @@ LC3_Error lc3plus_enc_batch_destroy(lc3plus_batch* b)
 }
 
 int lc3plus_enc_batch_input_samples(const lc3plus_batch* b) { return b ? b->g.N : 0; }
-int lc3plus_enc_batch_stride(const lc3plus_batch* b) { return b ? b->stride : 0; }
+/* (the host copy is a cache of the device's configuration: refreshing it leaves the batch as it was) */
+int lc3plus_enc_batch_stride(const lc3plus_batch* b) { return b && !enc_refresh((lc3plus_batch*)b) ? b->stride : 0; }
 int lc3plus_enc_batch_num_bytes(const lc3plus_batch* b, int stream)
 {
     if (!b || stream < 0 || stream >= b->n_streams) return 0;
+    if (enc_refresh((lc3plus_batch*)b)) return 0;
     int n = 0;
     for (int c = 0; c < b->g.channels; c++) n += b->chans[stream * b->g.channels + c].nbytes;
     return n;
@@ -453,6 +477,7 @@ LC3_Error lc3plus_enc_batch_set_bitrate(lc3plus_batch* b, int stream, int bitrat
     if (!b) return LC3_NULL_ERROR;
     if (stream < 0 || stream >= b->n_streams) return LC3_ERROR;
     if (bitrate <= 0) return LC3_BITRATE_ERROR;
+    if (enc_refresh(b)) return LC3_ERROR;
     lc3d_chan tmp[MAX_CH];
     memcpy(tmp, b->chans + (size_t)stream * b->g.channels, sizeof(lc3d_chan) * b->g.channels);
     for (int c = 0; c < b->g.channels; c++) tmp[c].reset_attack = 0;
@@ -469,6 +494,7 @@ LC3_Error lc3plus_enc_batch_set_bandwidth(lc3plus_batch* b, int stream, int band
     if (!b) return LC3_NULL_ERROR;
     if (stream < 0 || stream >= b->n_streams) return LC3_ERROR;
     if (b->g.hrmode == 1) return LC3_HRMODE_BW_ERROR;
+    if (enc_refresh(b)) return LC3_ERROR;
     lc3d_chan* ch = b->chans + (size_t)stream * b->g.channels;
     int eff = b->g.fs_in;
     if (ch[0].bandwidth != bandwidth) {
@@ -479,6 +505,7 @@ LC3_Error lc3plus_enc_batch_set_bandwidth(lc3plus_batch* b, int stream, int band
             ch[c].bw_cut_bin = lc3d_bw_cut_bin(bandwidth, b->g.dms);
             ch[c].bw_index = lc3d_bw_index(bandwidth);
         }
+        if (!lc3d_bw_value_ok(bandwidth, b->g.dms)) b->bw_unsafe = 1;
         return batch_upload(b, stream, 1);
     }
     return LC3_OK;
@@ -489,9 +516,11 @@ static LC3_Error batch_encode(lc3plus_batch* b, const void* pcm, int pcm_on_devi
 {
     if (!b || !pcm || !out) return LC3_NULL_ERROR;
     if (bitdepth != 16 && bitdepth != 24 && bitdepth != 32) return LC3_ERROR;
-    if (n_frames <= 0 || out_stride < b->stride) return LC3_ERROR;
+    if (n_frames <= 0 || out_stride < enc_stride_bound(b)) return LC3_ERROR;
     if (lc3hip_encode(b->dev, pcm, pcm_on_device, bitdepth, n_frames, out, out_stride, out_on_device, hip_stream, sync, trace, NULL, NULL)) return LC3_ERROR;
-    /* one-shot attack-state reset requests have been consumed by this launch */
+    /* one-shot attack-state reset requests have been consumed by this launch (a stale copy has none: the device-rate calls consume them, and nothing of it
+     * is uploaded) */
+    if (b->chans_stale) return LC3_OK;
     int dirty = 0;
     for (int i = 0; i < b->n_streams * b->g.channels; i++) if (b->chans[i].reset_attack) { b->chans[i].reset_attack = 0; dirty = 1; }
     if (dirty) return batch_upload(b, 0, b->n_streams);
@@ -510,6 +539,7 @@ static LC3_Error batch_encode_bitrates(lc3plus_batch* b, const void* pcm, int pc
     if (!b || !pcm || !out || !bitrates) return LC3_NULL_ERROR;
     if (bitdepth != 16 && bitdepth != 24 && bitdepth != 32) return LC3_ERROR;
     if (n_frames <= 0) return LC3_ERROR;
+    if (enc_refresh(b)) return LC3_ERROR;
     const size_t n = (size_t)b->n_streams * n_frames;
     if (b->fsz_cap < n) {
         free(b->fsz); b->fsz_cap = 0;
@@ -555,7 +585,7 @@ LC3_Error lc3plus_enc_batch_encode_bitrates_traced(lc3plus_batch* b, const void*
 /* ---- per-frame bandwidths (lc3plus_enc_batch_encode_bandwidths) ---- */
 /* The values a call refuses outright: a negative bandwidth, and a positive one whose cut-off line is below 1 (the controller would write in front of the
  * spectrum, R/cutoff_bandwidth.c:17-19).  0 switches the controller off. */
-static int bw_value_ok(int bw, int dms) { return bw == 0 || (bw > 0 && bw >= (5000 + dms - 1) / dms); }      /* lc3d_bw_cut_bin(bw, dms) >= 1, without overflow */
+static int bw_value_ok(int bw, int dms) { return lc3d_bw_value_ok(bw, dms); }      /* lc3d_bw_cut_bin(bw, dms) >= 1, without overflow */
 /* The per-frame rule: frame t of stream s applies lc3_enc_set_bandwidth(bandwidths[s][t]) to the value in force before it (start[s] for frame 0,
  * R/lc3.c:187-208): a new value that 2 * bw > min(fs_in, 40000) refuses keeps the value in force and makes the call's result LC3_BW_WARNING.  Values
  * have been checked with bw_value_ok; start values are what set_bandwidth accepted, and one with a cut-off line below 1 that stays in force is refused
@@ -567,8 +597,9 @@ static LC3_Error enc_plan_bandwidths(const geom_t* g, int n_streams, const int* 
     for (int s = 0; s < n_streams; s++) {
         int cur = start[s];
         for (int t = 0; t < n_frames; t++) {
-            const int v = bandwidths[(size_t)s * n_frames + t];
-            if (v != cur) { if (v > eff / 2) res = LC3_BW_WARNING; else cur = v; }          /* 2 * v > eff: eff is even */
+            const int f = lc3d_enc_bw_step(&cur, bandwidths[(size_t)s * n_frames + t], eff / 2, g->dms);     /* 2 * v > eff: eff is even */
+            if (f & LC3D_ENC_FL_BW_RANGE) return LC3_ERROR;                                                     /* (checked before) */
+            if (f & LC3D_ENC_FL_BW_REFUSED) res = LC3_BW_WARNING;
             if (!bw_value_ok(cur, g->dms) || cur > 0xFFFF) return LC3_ERROR;
             in_force[(size_t)s * n_frames + t] = (uint16_t)cur;
         }
@@ -580,6 +611,7 @@ static LC3_Error batch_encode_bandwidths(lc3plus_batch* b, const void* pcm, int 
 {
     if (!b) return LC3_NULL_ERROR;
     if (b->g.hrmode) return LC3_HRMODE_BW_ERROR;
+    if (enc_refresh(b)) return LC3_ERROR;
     const size_t n = (size_t)b->n_streams * (n_frames > 0 ? n_frames : 0);
     if (bandwidths) for (size_t i = 0; i < n; i++) if (!bw_value_ok(bandwidths[i], b->g.dms)) return LC3_ERROR;
     if (!pcm || !out || !bandwidths) return LC3_NULL_ERROR;
@@ -648,6 +680,7 @@ LC3_Error lc3plus_enc_batch_encode_bandwidths(lc3plus_batch* b, const void* pcm,
 int lc3plus_enc_batch_bandwidth(const lc3plus_batch* b, int stream)
 {
     if (!b || stream < 0 || stream >= b->n_streams) return -1;
+    if (enc_refresh((lc3plus_batch*)b)) return -1;
     return b->chans[(size_t)stream * b->g.channels].bandwidth;
 }
 /* the per-frame bandwidth rule for a geometry, without a device: start [n_streams], bandwidths [n_streams * n_frames] -> in_force [n_streams * n_frames].
@@ -698,6 +731,79 @@ LC3_Error lc3plus_enc_plan_bitrates(int samplerate, int channels, float frame_ms
     return e;
 }
 
+/* ---- per-frame rates and bandwidths in device memory (lc3plus_enc_batch_encode_rates_device) ---- */
+/* the constants of lc3d_enc_frame_step for a geometry; lim: the largest stream-frame the call may write */
+static LC3_Error enc_rate_rule(const geom_t* g, int lim, lc3d_rate_rule* r)
+{
+    LC3_Error e = bitrate_limits(g, &r->lo, &r->hi);
+    if (e) return e;
+    r->N = g->N; r->fs_in = g->fs_in; r->channels = g->channels; r->max_chan = enc_max_chan_bytes(g); r->lim = lim;
+    r->half = (g->fs_in > 40000 ? 40000 : g->fs_in) / 2; r->dms = g->dms;
+    return LC3_OK;
+}
+LC3_Error lc3plus_enc_batch_encode_rates_device(lc3plus_batch* b, const void* pcm, int bitdepth, const int32_t* bitrates, const int32_t* bandwidths,
+                                                int n_frames, void* out, int out_stride, int32_t* num_bytes, uint8_t* flags, void* hip_stream, int sync)
+{
+    if (!b || !pcm || !out || (!bitrates && !bandwidths)) return LC3_NULL_ERROR;
+    if (bitdepth != 16 && bitdepth != 24 && bitdepth != 32) return LC3_ERROR;
+    if (n_frames <= 0 || out_stride < enc_stride_bound(b)) return LC3_ERROR;
+    if (bandwidths && b->g.hrmode) return LC3_HRMODE_BW_ERROR;
+    if (bandwidths && b->bw_unsafe) {           /* a value in force with a cut-off line below 1: refused as encode_bandwidths refuses it (enc_plan_bandwidths) */
+        if (enc_refresh(b)) return LC3_ERROR;
+        b->bw_unsafe = 0;
+        for (int i = 0; i < b->n_streams; i++) if (!bw_value_ok(b->chans[(size_t)i * b->g.channels].bandwidth, b->g.dms)) b->bw_unsafe = 1;
+        if (b->bw_unsafe) return LC3_ERROR;
+    }
+    lc3d_rate_rule r;
+    if (enc_rate_rule(&b->g, out_stride, &r)) return LC3_ERROR;
+    int resets = 0;                             /* one-shot attack-detector resets pending from set_bitrate (a stale copy has none) */
+    if (!b->chans_stale) for (int i = 0; i < b->n_streams * b->g.channels; i++) resets |= b->chans[i].reset_attack != 0;
+    if (lc3hip_encode_rates_device(b->dev, pcm, bitdepth, n_frames, out, out_stride, bitrates, bandwidths, &r, num_bytes, flags, resets, hip_stream, sync))
+        return LC3_ERROR;
+    /* the configuration after the call is on the device only: the host copy is read back by the next host-side reader or writer; until then encode()
+     * checks out_stride against the bound: every stream-frame of this call fits out_stride, and so does each stream's carry */
+    if (!b->chans_stale) b->stride_bound = b->stride;
+    if (bitrates && out_stride > b->stride_bound) b->stride_bound = out_stride;
+    b->chans_stale = 1;
+    return LC3_OK;
+}
+/* test hook: the rule of encode_rates_device on host arrays, without a device.  start_rates, start_bw [n_streams]: the stream's configuration before
+ * the call; bitrates, bandwidths: NULL or [n_streams][n_frames]; out: num_bytes, bw_in_force, flags [n_streams][n_frames], end_rates [n_streams] */
+LC3_Error lc3plus_enc_plan_rates_lenient(int samplerate, int channels, float frame_ms, int hrmode, int n_streams, const int* start_rates, const int* start_bw,
+                                         const int* bitrates, const int* bandwidths, int n_frames, int out_stride, int* num_bytes, int* bw_in_force,
+                                         uint8_t* flags, int* end_rates)
+{
+    if (!start_rates || !start_bw || !num_bytes || !bw_in_force || !flags || !end_rates || (!bitrates && !bandwidths)) return LC3_NULL_ERROR;
+    if (n_streams <= 0 || n_frames <= 0) return LC3_ERROR;
+    if (!samplerate_ok(samplerate)) return LC3_SAMPLERATE_ERROR;
+    if (channels < 1 || channels > MAX_CH) return LC3_CHANNELS_ERROR;
+    { int d = (int)ceil(frame_ms * 10); if (d != 25 && d != 50 && d != 100) return LC3_FRAMEMS_ERROR; }
+    if (samplerate < 48000 && hrmode != 0) return LC3_SAMPLERATE_ERROR;
+    geom_t g;
+    geom_init(&g, samplerate, channels);
+    g.dms = (int)(frame_ms * 10); g.frame_ms = frame_ms; g.hrmode = hrmode > 0;
+    geom_update(&g);
+    if (bandwidths && g.hrmode) return LC3_HRMODE_BW_ERROR;
+    lc3d_rate_rule r;
+    LC3_Error e = enc_rate_rule(&g, out_stride, &r);
+    if (e) return e;
+    for (int s = 0; s < n_streams; s++) {       /* the start: a configuration the batch can hold, and one the call accepts */
+        if (lc3d_enc_rate_bytes(start_rates[s], r.lo, r.hi, r.N, r.fs_in, r.channels, r.max_chan, out_stride) < 0) return LC3_BITRATE_ERROR;
+        if (bandwidths && !bw_value_ok(start_bw[s], g.dms)) return LC3_ERROR;
+    }
+    for (int s = 0; s < n_streams; s++) {
+        int rate = start_rates[s], bytes = lc3d_enc_rate_bytes(rate, r.lo, r.hi, r.N, r.fs_in, r.channels, r.max_chan, out_stride), bw = start_bw[s];
+        for (int t = 0; t < n_frames; t++) {
+            const size_t i = (size_t)s * n_frames + t;
+            flags[i] = (uint8_t)lc3d_enc_frame_step(&r, bitrates != NULL, bitrates ? bitrates[i] : 0, bandwidths != NULL, bandwidths ? bandwidths[i] : 0,
+                                                    &rate, &bytes, &bw);
+            num_bytes[i] = bytes; bw_in_force[i] = bw;
+        }
+        end_rates[s] = rate;
+    }
+    return LC3_OK;
+}
+
 /* debug / stage-parity entry point used by tests: additionally returns one lc3d_trace per channel-frame */
 LC3_Error lc3plus_enc_batch_encode_traced(lc3plus_batch* b, const void* pcm, int bitdepth, int n_frames, void* out, int out_stride, void* traces)
 {
@@ -739,6 +845,7 @@ LC3_Error lc3plus_enc_batch_reset_streams(lc3plus_batch* b, const int* streams, 
     const int C = b->g.channels;
     lc3d_chan* cfg = NULL;
     if (bitrates) {                             /* as set_bitrate configures a stream, every rate checked first; the bandwidth is kept */
+        if (enc_refresh(b)) return LC3_ERROR;
         cfg = (lc3d_chan*)malloc(sizeof(lc3d_chan) * (size_t)n * C);
         if (!cfg) return LC3_ERROR;
         for (int i = 0; i < n && !e; i++) {

@@ -3095,6 +3095,81 @@ extern "C" __global__ void __launch_bounds__(WAVE) lc3_stream_state_kernel(int m
     if (!ok) return;
     for (int k = lane; k < n4; k += WAVE) row[k] = brow[k];
 }
+
+/* ---- per-frame rates and bandwidths from device memory (include/lc3plus_batch.h: lc3plus_enc_batch_encode_rates_device) ----
+ * Plan kernel: one stream per lane walks its T frames in order - the carry is serial per stream, the frames of a stream are not - with the rule of
+ * lc3d_enc_frame_step (lc3_plan.h).  It is the only reader of the caller's rates [stream][T] and bandwidths [stream][T] (either may be null) and writes
+ * what the per-frame kernels take (fsz with rates, bwf with bandwidths: the bytes and the bandwidth in force of every stream-frame), the caller's
+ * num_bytes and flags (null or [stream][T]), and each stream's carry after the call: into carry (for the next plan kernel) and into pend (for this call's
+ * tail kernel).  seed (not null): start from the configuration on the device instead of from carry, after the host has changed it.  Where T is a
+ * multiple of 4 and every array is aligned for it, a lane moves four frames per access (16 bytes of rates / bandwidths / sizes); T is a kernel argument,
+ * so the loop is wave-uniform. */
+extern "C" __global__ void __launch_bounds__(WAVE) lc3_enc_plan_rates_kernel(lc3d_rate_rule r, const int32_t* __restrict__ rates, const int32_t* __restrict__ bws,
+                                                                             int T, int n_streams, int4* __restrict__ carry, const lc3d_chan* __restrict__ seed,
+                                                                             uint16_t* __restrict__ fsz, uint16_t* __restrict__ bwf, int32_t* __restrict__ num_bytes,
+                                                                             uint8_t* __restrict__ flags, int4* __restrict__ pend, int vec4)
+{
+    const int s = (int)(blockIdx.x * WAVE + threadIdx.x);
+    if (s >= n_streams) return;
+    int rate, bytes, bw;
+    if (seed) {
+        const lc3d_chan* ch = seed + (size_t)s * r.channels;
+        rate = ch[0].bitrate; bw = ch[0].bandwidth; bytes = ch[0].nbytes;
+        if (r.channels > 1) bytes += ch[1].nbytes;
+    } else { const int4 c = carry[s]; rate = c.x; bytes = c.y; bw = c.z; }
+    const size_t row = (size_t)s * T;
+    if (vec4) {
+        for (int t = 0; t < T; t += 4) {
+            const size_t i = row + t;
+            const int4 rv = rates ? *(const int4*)(rates + i) : make_int4(0, 0, 0, 0);
+            const int4 bv = bws ? *(const int4*)(bws + i) : make_int4(0, 0, 0, 0);
+            int f0, f1, f2, f3; int z0, z1, z2, z3; int w0, w1, w2, w3;
+            f0 = lc3d_enc_frame_step(&r, rates != nullptr, rv.x, bws != nullptr, bv.x, &rate, &bytes, &bw); z0 = bytes; w0 = bw;
+            f1 = lc3d_enc_frame_step(&r, rates != nullptr, rv.y, bws != nullptr, bv.y, &rate, &bytes, &bw); z1 = bytes; w1 = bw;
+            f2 = lc3d_enc_frame_step(&r, rates != nullptr, rv.z, bws != nullptr, bv.z, &rate, &bytes, &bw); z2 = bytes; w2 = bw;
+            f3 = lc3d_enc_frame_step(&r, rates != nullptr, rv.w, bws != nullptr, bv.w, &rate, &bytes, &bw); z3 = bytes; w3 = bw;
+            if (rates) *(uint2*)(fsz + i) = make_uint2((unsigned)z0 | (unsigned)z1 << 16, (unsigned)z2 | (unsigned)z3 << 16);
+            if (bws) *(uint2*)(bwf + i) = make_uint2((unsigned)w0 | (unsigned)w1 << 16, (unsigned)w2 | (unsigned)w3 << 16);
+            if (num_bytes) *(int4*)(num_bytes + i) = make_int4(z0, z1, z2, z3);
+            if (flags) *(unsigned*)(flags + i) = (unsigned)f0 | (unsigned)f1 << 8 | (unsigned)f2 << 16 | (unsigned)f3 << 24;
+        }
+    } else {
+        for (int t = 0; t < T; t++) {
+            const size_t i = row + t;
+            const int f = lc3d_enc_frame_step(&r, rates != nullptr, rates ? rates[i] : 0, bws != nullptr, bws ? bws[i] : 0, &rate, &bytes, &bw);
+            if (rates) fsz[i] = (uint16_t)bytes;
+            if (bws) bwf[i] = (uint16_t)bw;
+            if (num_bytes) num_bytes[i] = bytes;
+            if (flags) flags[i] = (uint8_t)f;
+        }
+    }
+    const int4 e = make_int4(rate, bytes, bw, 0);
+    carry[s] = e; pend[s] = e;
+}
+/* Tail kernel, behind the call's last kernel: one channel-stream per lane configures its channel from the stream's carry after the call (pend), as the host
+ * configures it after encode_bitrates / encode_bandwidths.  With rates (all): the channel's share of the bytes from etab (derive_chan), its payload
+ * offset, the bandwidth words and the rate.  Without: the bandwidth words alone.  Either way the pending one-shot attack-detector reset is cleared: the
+ * call's kernels have done it. */
+extern "C" __global__ void __launch_bounds__(WAVE) lc3_enc_rates_tail_kernel(const int4* __restrict__ pend, const lc3d_chan* __restrict__ etab, lc3d_chan* __restrict__ chans,
+                                                                             int channels, int ncs, int dms, int all)
+{
+    const int cs = (int)(blockIdx.x * WAVE + threadIdx.x);
+    if (cs >= ncs) return;
+    const int strm = cs / channels, ch = cs - strm * channels;
+    const int4 e = pend[strm];
+    lc3d_chan* d = chans + cs;
+    if (all) {
+        const int fb = e.y;
+        lc3d_chan v = etab[channels == 1 ? fb : ch ? fb >> 1 : (fb + 1) >> 1];
+        v.out_off = ch ? (fb + 1) >> 1 : 0;
+        v.bandwidth = e.z; v.bw_cut_bin = lc3d_bw_cut_bin(e.z, dms); v.bw_index = lc3d_bw_index(e.z);
+        v.reset_attack = 0; v.bitrate = e.x;
+        *d = v;
+    } else {
+        d->bandwidth = e.z; d->bw_cut_bin = lc3d_bw_cut_bin(e.z, dms); d->bw_index = lc3d_bw_index(e.z);
+        d->reset_attack = 0;
+    }
+}
 /* What a batch keeps for those calls: the fresh-row template, and LC3D_SETS staging slots (pinned host memory for the index list, configuration entries and
  * host blobs, and its device copy) used in turn, each guarded by the event recorded behind the call that used it last; ev_done: behind the last call, for
  * later calls on other streams */
@@ -3134,6 +3209,15 @@ struct lc3hip_ctx {
     uint16_t* d_bw[LC3D_SETS]; uint16_t* h_bw[LC3D_SETS]; size_t bw_cap; hipEvent_t ev_bw[LC3D_SETS]; int bw_armed[LC3D_SETS], bw_set;
     const uint16_t* bw_src; size_t bw_bytes; hipStream_t bw_on; hipEvent_t ev_bwcp;
     lc3hip_ss ss;                                   /* lc3hip_set_template, lc3hip_stream_state */
+    /* per-frame rates and bandwidths from device memory (lc3hip_encode_rates_device).  d_carry: each stream's rate, bytes and bandwidth in force, passed
+     * from plan kernel to plan kernel in call order (ev_plan: behind the last one, on whichever stream it ran); carry_seed: the host has written the
+     * configuration since, the next plan kernel starts from d_chans.  Per call, in LC3D_SETS rotating sets: the sizes and bandwidths the plan kernel writes
+     * and the carry after the call (for the tail kernel); a set is written again behind the event of the call that used it last, waited for on the device.
+     * pl: the plan kernel of the pending call, launched by bw_to where the first kernel that reads its words runs. */
+    int4* d_carry; int carry_seed; hipEvent_t ev_plan, ev_pset_prev; int plan_armed;
+    uint16_t* d_pfsz[LC3D_SETS]; uint16_t* d_pbw[LC3D_SETS]; int4* d_pend[LC3D_SETS]; size_t pset_frames; hipEvent_t ev_pset[LC3D_SETS]; int pset_armed[LC3D_SETS], pset;
+    int etab_attack, etab_max;                      /* some byte count of the table has attack handling; the largest channel byte count */
+    struct { int pending, k, T; const int32_t* rates; const int32_t* bws; int32_t* nb; uint8_t* fl; lc3d_rate_rule rule; } pl;
 };
 
 #define LC3D_FUSED_MAX_T 8
@@ -3273,6 +3357,7 @@ extern "C" int lc3hip_upload_chans_async(void* ctx, const lc3d_chan* chans, int 
     if (c->chans_armed) HIPCHK(hipEventSynchronize(c->ev_chans));      /* the staging of the previous copy is free */
     memcpy(c->h_chans + first, chans, sizeof(lc3d_chan) * (size_t)count);
     HIPCHK(hipMemcpyAsync(c->d_chans + first, c->h_chans + first, sizeof(lc3d_chan) * (size_t)count, hipMemcpyHostToDevice, s));
+    c->carry_seed = 1;
     HIPCHK(hipEventRecord(c->ev_chans, s)); c->chans_armed = 1;
     if (c->opt.check_ready && c->ev_ours) { HIPCHK(hipEventRecord(c->ev_ours, s)); c->ours_armed = 1; }      /* the copy is the library's own work */
     return chans_host_side(c, chans, first, count);
@@ -3286,6 +3371,7 @@ extern "C" int lc3hip_upload_chans(void* ctx, const lc3d_chan* chans, int first,
     if (c->last_stream) { HIPCHK(hipStreamSynchronize(c->last_stream)); c->last_stream = nullptr; }
     if (c->chans_armed) HIPCHK(hipEventSynchronize(c->ev_chans));      /* a queued copy of lc3hip_upload_chans_async lands first */
     HIPCHK(hipMemcpy(c->d_chans + first, chans, sizeof(lc3d_chan) * count, hipMemcpyHostToDevice));
+    c->carry_seed = 1;
     return chans_host_side(c, chans, first, count);
 }
 /* what the launch decisions read of the configuration, on the host: channel-streams first ... first + count - 1, or with list the channels of streams list[0 .. count / channels - 1] */
@@ -3698,6 +3784,8 @@ extern "C" int lc3hip_upload_enc_table(void* ctx, const lc3d_chan* tab, int n)
     c->d_etab = nullptr;
     HIPCHK(hipMalloc((void**)&c->d_etab, sizeof(lc3d_chan) * (size_t)n));
     HIPCHK(hipMemcpy(c->d_etab, tab, sizeof(lc3d_chan) * (size_t)n, hipMemcpyHostToDevice));
+    c->etab_attack = 0; c->etab_max = n - 1;
+    for (int i = 1; i < n; i++) c->etab_attack |= tab[i].attack_handling != 0;
     return 0;
 }
 /* the stream-frame sizes of a per-frame-bitrate call to the device, queued on s ahead of its kernels: copied into pinned staging first, so that the caller's
@@ -3744,16 +3832,18 @@ static int stage_bw(lc3hip_ctx* c, const uint16_t* bw_host, int n_frames, const 
         HIPCHK(hipEventCreateWithFlags(&c->ev_bwcp, hipEventDisableTiming));
     }
     memcpy(c->h_bw[k], bw_host, fb);
-    c->bw_src = c->h_bw[k]; c->bw_bytes = fb; c->bw_on = nullptr;
+    c->bw_src = c->h_bw[k]; c->bw_bytes = fb; c->bw_on = nullptr; c->pl.pending = 0;
     *dbw = c->d_bw[k]; *ev = c->ev_bw[k];
     c->bw_armed[k] = 1; c->bw_set = (k + 1) % LC3D_SETS;
     return 0;
 }
+static int plan_launch(lc3hip_ctx* c, hipStream_t st);
 static int bw_to(lc3hip_ctx* c, hipStream_t st)
 {
     const int k = (c->bw_set + LC3D_SETS - 1) % LC3D_SETS;                    /* the slot stage_bw filled for this call */
     if (!c->bw_on) {
-        HIPCHK(hipMemcpyAsync(c->d_bw[k], c->bw_src, c->bw_bytes, hipMemcpyHostToDevice, st));
+        if (c->pl.pending) { if (plan_launch(c, st)) return 1; }             /* words from device memory: the call's plan kernel writes them */
+        else HIPCHK(hipMemcpyAsync(c->d_bw[k], c->bw_src, c->bw_bytes, hipMemcpyHostToDevice, st));
         HIPCHK(hipEventRecord(c->ev_bwcp, st)); c->bw_on = st;
     } else if (c->bw_on != st) HIPCHK(hipStreamWaitEvent(st, c->ev_bwcp, 0));
     return 0;
@@ -3830,6 +3920,99 @@ extern "C" int lc3hip_encode(void* ctx, const void* pcm, int pcm_on_device, int 
     return 0;
 }
 
+/* the pending call's plan kernel on st: behind the previous call's plan kernel (the carry), behind the call that used this set last, and - when it starts
+ * from the configuration the host wrote - behind that write */
+static int plan_launch(lc3hip_ctx* c, hipStream_t st)
+{
+    const int k = c->pl.k, T = c->pl.T;
+    if (c->plan_armed) HIPCHK(hipStreamWaitEvent(st, c->ev_plan, 0));
+    if (c->pset_armed[k]) HIPCHK(hipStreamWaitEvent(st, c->ev_pset[k], 0));
+    if (c->carry_seed && c->chans_armed) HIPCHK(hipStreamWaitEvent(st, c->ev_chans, 0));
+    const size_t al = (size_t)c->pl.rates | (size_t)c->pl.bws | (size_t)c->pl.nb | (size_t)c->pl.fl;
+    const int vec4 = (T & 3) == 0 && (al & 15) == 0 && (((size_t)c->pl.fl) & 3) == 0;
+    hipLaunchKernelGGL(lc3_enc_plan_rates_kernel, dim3((unsigned)((c->n_streams + WAVE - 1) / WAVE)), dim3(WAVE), 0, st, c->pl.rule, c->pl.rates, c->pl.bws, T,
+                       c->n_streams, c->d_carry, c->carry_seed ? (const lc3d_chan*)c->d_chans : (const lc3d_chan*)nullptr, c->d_pfsz[k], c->d_pbw[k], c->pl.nb, c->pl.fl,
+                       c->d_pend[k], vec4);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(c->ev_plan, st)); c->plan_armed = 1;
+    c->carry_seed = 0; c->pl.pending = 0;
+    return 0;
+}
+/* Per-frame rates and / or bandwidths in device memory, as PCM and output: the plan kernel turns them into the words the per-frame kernels read (it runs
+ * where the first of those kernels runs: bw_to), the call takes the path lc3hip_encode takes with the same words from the host, and the tail kernel
+ * configures every stream on s behind it.  Nothing is read back, and the host waits only where a set of plan buffers has to grow. */
+extern "C" int lc3hip_encode_rates_device(void* ctx, const void* pcm, int bitdepth, int n_frames, void* out, int out_stride, const int32_t* rates_dev,
+                                          const int32_t* bws_dev, const lc3d_rate_rule* rule, int32_t* num_bytes_dev, uint8_t* flags_dev, int clear_resets,
+                                          void* hip_stream, int sync)
+{
+    lc3hip_ctx* c = (lc3hip_ctx*)ctx;
+    HIPCHK(hipSetDevice(c->device));
+    if (!c->d_etab || (bws_dev && c->big)) return 1;
+    if (!hip_stream && !c->stream) HIPCHK(hipStreamCreate(&c->stream));
+    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : c->stream;
+    if (!c->ev_plan) {
+        HIPCHK(hipEventCreateWithFlags(&c->ev_plan, hipEventDisableTiming)); HIPCHK(hipEventCreateWithFlags(&c->ev_pset_prev, hipEventDisableTiming));
+        for (int i = 0; i < LC3D_SETS; i++) HIPCHK(hipEventCreateWithFlags(&c->ev_pset[i], hipEventDisableTiming));
+        if (!c->ev_bwcp) HIPCHK(hipEventCreateWithFlags(&c->ev_bwcp, hipEventDisableTiming));
+        HIPCHK(hipMalloc((void**)&c->d_carry, sizeof(int4) * (size_t)c->n_streams));
+        for (int i = 0; i < LC3D_SETS; i++) HIPCHK(hipMalloc((void**)&c->d_pend[i], sizeof(int4) * (size_t)c->n_streams));
+        c->carry_seed = 1;
+    }
+    if (c->pset_frames < (size_t)n_frames) {
+        /* an earlier call that did not wait may still read the smaller sets: growing them waits for the device, once (the first allocation does not) */
+        if (c->d_pfsz[0]) HIPCHK(hipDeviceSynchronize());
+        for (int i = 0; i < LC3D_SETS; i++) {
+            if (c->d_pfsz[i]) HIPCHK(hipFree(c->d_pfsz[i])); if (c->d_pbw[i]) HIPCHK(hipFree(c->d_pbw[i]));
+            c->d_pfsz[i] = nullptr; c->d_pbw[i] = nullptr;
+        }
+        c->pset_frames = 0;
+        const size_t fb = sizeof(uint16_t) * (size_t)c->n_streams * n_frames;
+        for (int i = 0; i < LC3D_SETS; i++) { HIPCHK(hipMalloc((void**)&c->d_pfsz[i], fb)); HIPCHK(hipMalloc((void**)&c->d_pbw[i], fb)); }
+        c->pset_frames = (size_t)n_frames;
+    }
+    const int k = c->pset;
+    c->pl.pending = 1; c->pl.k = k; c->pl.T = n_frames; c->pl.rates = rates_dev; c->pl.bws = bws_dev; c->pl.nb = num_bytes_dev; c->pl.fl = flags_dev; c->pl.rule = *rule;
+    c->bw_on = nullptr;
+    if (c->chans_armed) HIPCHK(hipStreamWaitEvent(s, c->ev_chans, 0));
+    /* behind the batch's last call when that went to another stream (its work there ends on it: writer, rate chain), as a stream-lifecycle call is */
+    if (c->last_stream && c->last_stream != s) { HIPCHK(hipEventRecord(c->ev_pset_prev, c->last_stream)); HIPCHK(hipStreamWaitEvent(s, c->ev_pset_prev, 0)); }
+    HIPCHK(hipEventRecord(c->ev0, s));
+    if (rates_dev && bw_to(c, s)) return 1;                                  /* the one-wave kernels on s read the sizes: the plan kernel in front of them */
+    if (enc_launch(c, pcm, bitdepth, n_frames, (uint8_t*)out, out_stride, s, nullptr, n_frames, 0, true, rates_dev ? c->d_pfsz[k] : nullptr,
+                   bws_dev ? c->d_pbw[k] : nullptr)) return 1;
+    if (c->pl.pending) return 1;                                             /* every path reads the words */
+    hipLaunchKernelGGL(lc3_enc_rates_tail_kernel, dim3((unsigned)((c->ncs + WAVE - 1) / WAVE)), dim3(WAVE), 0, s, (const int4*)c->d_pend[k], (const lc3d_chan*)c->d_etab,
+                       c->d_chans, c->channels, c->ncs, rule->dms, rates_dev ? 1 : 0);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(c->ev1, s));
+    HIPCHK(hipEventRecord(c->ev_pset[k], s)); c->pset_armed[k] = 1; c->pset = (k + 1) % LC3D_SETS;
+    /* the configuration the tail kernel wrote: later calls on other streams wait for it (as for lc3hip_upload_chans_async); a call that overlaps this one may
+     * do so only where the tail changed the bandwidth words alone */
+    if (!c->ev_chans) HIPCHK(hipEventCreateWithFlags(&c->ev_chans, hipEventDisableTiming));
+    HIPCHK(hipEventRecord(c->ev_chans, s)); c->chans_armed = 1;
+    c->cfg_fresh = (rates_dev || clear_resets) ? 2 : 1;
+    /* what the launch decisions know of the configuration until the host reads it back: with rates any stream may now have attack handling, and channel
+     * frames of any size of the table */
+    if (rates_dev) { c->any_attack |= c->etab_attack; c->max_nbytes = c->etab_max; c->min_nbytes = 1; }
+    if (c->opt.check_ready && c->ev_ours) { HIPCHK(hipEventRecord(c->ev_ours, s)); c->ours_armed = 1; }
+    c->last_stream = s;
+    if (sync) {
+        HIPCHK(hipStreamSynchronize(s));
+        float ms = 0; if (hipEventElapsedTime(&ms, c->ev0, c->ev1) == hipSuccess) c->last_ms = ms;
+    }
+    return 0;
+}
+/* waits for the batch's last call and copies the configuration of every channel-stream to chans[ncs] (after lc3hip_encode_rates_device) */
+extern "C" int lc3hip_download_chans(void* ctx, lc3d_chan* chans)
+{
+    lc3hip_ctx* c = (lc3hip_ctx*)ctx;
+    HIPCHK(hipSetDevice(c->device));
+    if (c->last_stream) HIPCHK(hipStreamSynchronize(c->last_stream));
+    if (c->chans_armed) HIPCHK(hipEventSynchronize(c->ev_chans));
+    HIPCHK(hipMemcpy(chans, c->d_chans, sizeof(lc3d_chan) * (size_t)c->ncs, hipMemcpyDeviceToHost));
+    return chans_host_side(c, chans, 0, c->ncs);
+}
+
 /* status bits of the last call, [channel-stream][frame] (n = ncs * frames of that call), to host memory */
 extern "C" int lc3hip_last_status(void* ctx, uint8_t* status_host, int n)
 {
@@ -3895,6 +4078,7 @@ extern "C" int lc3hip_stream_state(void* ctx, int mode, const int* streams, int 
     HIPCHK(hipEventRecord(c->ev_chans, s)); c->chans_armed = 1;
     c->ahead_ok = 0;
     c->last_stream = s;
+    if (cfg) c->carry_seed = 1;
     return cfg ? chans_host_side_list(c, cfg, 0, n * c->channels, streams) : 0;
 }
 
@@ -3938,6 +4122,9 @@ extern "C" int lc3hip_destroy(void* ctx)
     for (int i = 0; i < LC3D_SETS; i++) { if (c->d_fsz[i]) hipFree(c->d_fsz[i]); if (c->h_fsz[i]) hipHostFree(c->h_fsz[i]); if (c->ev_fsz[i]) hipEventDestroy(c->ev_fsz[i]); }
     for (int i = 0; i < LC3D_SETS; i++) { if (c->d_bw[i]) hipFree(c->d_bw[i]); if (c->h_bw[i]) hipHostFree(c->h_bw[i]); if (c->ev_bw[i]) hipEventDestroy(c->ev_bw[i]); }
     if (c->ev_bwcp) hipEventDestroy(c->ev_bwcp);
+    if (c->d_carry) hipFree(c->d_carry);
+    if (c->ev_plan) { hipEventDestroy(c->ev_plan); hipEventDestroy(c->ev_pset_prev); }
+    for (int i = 0; i < LC3D_SETS; i++) { if (c->d_pfsz[i]) hipFree(c->d_pfsz[i]); if (c->d_pbw[i]) hipFree(c->d_pbw[i]); if (c->d_pend[i]) hipFree(c->d_pend[i]); if (c->ev_pset[i]) hipEventDestroy(c->ev_pset[i]); }
     for (int i = 0; i < 2; i++) {
         if (c->hp_dpcm[i]) hipFree(c->hp_dpcm[i]);
         if (c->hp_pin_in[i]) hipHostFree(c->hp_pin_in[i]);

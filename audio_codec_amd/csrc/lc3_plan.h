@@ -57,7 +57,8 @@ typedef struct {
     int32_t out_off;            /* byte offset of this channel's payload inside the stream-frame */
     int32_t bandwidth, bw_cut_bin, bw_index;
     int32_t reset_attack;       /* set by a bitrate change that disables attack handling (R/setup_enc_lc3.c:297-308) */
-    int32_t pad[3];
+    int32_t bitrate;            /* the stream's total bitrate (all channels) these values come from; no kernel reads it: the host reads it back */
+    int32_t pad[2];
 } lc3d_chan;
 
 /* ---- state layout (32-bit words), parametrised by the kernel layout's MDCT-memory slot (300 standard, 600 large) ---- */
@@ -139,6 +140,50 @@ static inline LC3D_HD int lc3d_dec_frame_class(int nb, int bfi, int in_stride, c
  * detected bandwidth index.  The host's set_bandwidth and the per-frame-bandwidth kernels (lc3plus_enc_batch_encode_bandwidths) use these. */
 static inline LC3D_HD int lc3d_bw_cut_bin(int bw, int dms) { return (bw * dms) / 5000; }
 static inline LC3D_HD int lc3d_bw_index(int bw) { const int i = (bw / 4000) - 1; return i > 0 ? i : 0; }
+
+/* The per-frame rules of the encoder's per-frame rates and bandwidths, one stream-frame at a time, on the host (lc3_host.c: enc_plan_bitrates,
+ * enc_plan_bandwidths, the test hook lc3plus_enc_plan_rates_lenient) and on the device (lc3_enc_plan_rates_kernel). */
+#define LC3D_ENC_FL_RATE 1               /* flag bits of lc3plus_enc_batch_encode_rates_device: the rate was refused, the frame keeps the carried rate */
+#define LC3D_ENC_FL_BW_REFUSED 2         /* the bandwidth was refused as set_bandwidth refuses it (2 * bw > min(fs_in, 40000)): the value in force stays */
+#define LC3D_ENC_FL_BW_RANGE 4           /* the bandwidth is negative or its cut-off line is below 1: the value in force stays */
+/* Rate br of a stream-frame -> its bytes (all channels), as derive_bitrate computes them (R/setup_enc_lc3.c:196-240), or -1 where set_bitrate refuses
+ * the rate (outside [lo, hi], the geometry's limits), a channel's share falls outside the table 1 ... max_chan, or the bytes exceed lim.  br is
+ * compared with the limits before it is multiplied: hi * N < 2^31 for every geometry. */
+static inline LC3D_HD int lc3d_enc_rate_bytes(int br, int lo, int hi, int N, int fs_in, int channels, int max_chan, int lim)
+{
+    if (br <= 0 || br < lo || br > hi) return -1;
+    const int tb = br * N / (8 * fs_in);
+    if (tb / channels < 1 || (tb + channels - 1) / channels > max_chan || tb > lim) return -1;
+    return tb;
+}
+/* Bandwidth v for a stream-frame whose bandwidth in force is *cur (lc3_enc_set_bandwidth, R/lc3.c:187-208, with half = min(fs_in, 40000) / 2 and the
+ * frame length in dms): a value equal to *cur changes nothing; a negative one, or one whose cut-off line is below 1, is out of range
+ * (LC3D_ENC_FL_BW_RANGE, lc3d_bw_value_ok); one above half is refused (LC3D_ENC_FL_BW_REFUSED); any other becomes *cur.  Returns the flag bits, 0 for a clean frame. */
+static inline LC3D_HD int lc3d_bw_value_ok(int bw, int dms) { return bw == 0 || (bw > 0 && bw >= (5000 + dms - 1) / dms); }  /* cut-off line >= 1, no overflow */
+static inline LC3D_HD int lc3d_enc_bw_step(int* cur, int v, int half, int dms)
+{
+    if (v == *cur) return 0;
+    if (!lc3d_bw_value_ok(v, dms)) return LC3D_ENC_FL_BW_RANGE;
+    if (v > half) return LC3D_ENC_FL_BW_REFUSED;
+    *cur = v;
+    return 0;
+}
+/* the geometry's constants of both rules (a kernel argument) */
+typedef struct { int32_t lo, hi, N, fs_in, channels, max_chan, lim, half, dms; } lc3d_rate_rule;
+/* One stream-frame of lc3plus_enc_batch_encode_rates_device: the rate br (when has_rate) and then the bandwidth bw (when has_bw), as encode_bandwidths
+ * applies set_bitrate and then set_bandwidth.  The carry (*rate, *bytes: the stream's rate and its bytes; *cur_bw: the bandwidth in force) moves with
+ * every value the rules accept; a refused value leaves it.  Returns the frame's LC3D_ENC_FL_* bits. */
+static inline LC3D_HD int lc3d_enc_frame_step(const lc3d_rate_rule* r, int has_rate, int br, int has_bw, int bw, int* rate, int* bytes, int* cur_bw)
+{
+    int f = 0;
+    if (has_rate) {
+        const int tb = lc3d_enc_rate_bytes(br, r->lo, r->hi, r->N, r->fs_in, r->channels, r->max_chan, r->lim);
+        if (tb < 0) f = LC3D_ENC_FL_RATE;
+        else { *rate = br; *bytes = tb; }
+    }
+    if (has_bw) f |= lc3d_enc_bw_step(cur_bw, bw, r->half, r->dms);
+    return f;
+}
 
 /* decoder state words per channel-stream */
 #define DST_IMEM   0                                   /* 600: IMDCT overlap memory (300 used by the standard layout) */

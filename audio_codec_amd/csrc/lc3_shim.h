@@ -57,8 +57,16 @@ int   lc3hip_upload_enc_table(void* ctx, const lc3d_chan* tab, int n);   /* enco
  * standard layout only); the call takes the path it takes without it */
 int   lc3hip_encode(void* ctx, const void* pcm, int pcm_on_device, int bitdepth, int n_frames, void* out, int out_stride,
                     int out_on_device, void* hip_stream, int sync, void* trace_host, const uint16_t* fsz_host, const uint16_t* bw_host);
+/* per-frame rates_dev and / or bws_dev ([n_streams][n_frames] or null, not both) in device memory, as pcm and out: the rule of lc3d_enc_frame_step on the
+ * device from each stream's carry, num_bytes_dev / flags_dev (null or [n_streams][n_frames]) written there; ordered on hip_stream, does not wait unless sync.
+ * Each stream ends configured on the device with its carry; the host's copy of the configuration is then unknown (lc3hip_download_chans).  clear_resets: the
+ * configuration holds pending one-shot attack-detector resets, which the call consumes */
+int   lc3hip_encode_rates_device(void* ctx, const void* pcm, int bitdepth, int n_frames, void* out, int out_stride, const int32_t* rates_dev,
+                                 const int32_t* bws_dev, const lc3d_rate_rule* rule, int32_t* num_bytes_dev, uint8_t* flags_dev, int clear_resets,
+                                 void* hip_stream, int sync);
+int   lc3hip_download_chans(void* ctx, lc3d_chan* chans);       /* waits for the last call, copies the per-channel-stream configuration to chans[ncs] */
 float lc3hip_last_ms(void* ctx);
-size_t lc3hip_state_bytes(void* ctx);                             /* checkpoint / resume of the per-stream state (include/lc3plus_batch.h) */
+size_t lc3hip_state_bytes(void* ctx);                            /* checkpoint / resume of the per-stream state (include/lc3plus_batch.h) */
 int   lc3hip_get_state(void* ctx, void* host, size_t bytes);
 int   lc3hip_set_state(void* ctx, const void* host, size_t bytes);
 size_t lc3hip_dec_state_bytes(void* ctx);

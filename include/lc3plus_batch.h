@@ -89,6 +89,42 @@ int       lc3plus_enc_batch_bandwidth(const lc3plus_batch* batch, int stream);  
 LC3_Error lc3plus_enc_plan_bandwidths(int samplerate, float frame_ms, int hrmode, int n_streams, const int* start,
                                       const int* bandwidths, int n_frames, int* in_force);
 
+/* Per-frame rates and bandwidths in device memory, for servers whose rate control runs on the GPU.  Every pointer is a device pointer:
+ *   pcm        : [n_streams][n_frames][channels][input_samples], int16_t (bitdepth 16) or int32_t (24/32)
+ *   bitrates   : [n_streams][n_frames] total bitrate of each stream-frame, or NULL
+ *   bandwidths : [n_streams][n_frames] bandwidth in Hz of each stream-frame, or NULL (not both NULL)
+ *   out        : [n_streams][n_frames][out_stride] bytes; each payload at its slot, the bytes behind it and every slot outside the call untouched
+ *   num_bytes  : [n_streams][n_frames] bytes written per stream-frame, or NULL
+ *   flags      : [n_streams][n_frames], or NULL: bit 0 the rate was refused, bit 1 the bandwidth was refused as set_bandwidth refuses it, bit 2 the
+ *                bandwidth was negative or its cut-off line below 1; 0 for a clean frame
+ * The call is queued on hip_stream (NULL = the batch's own stream) in order with the batch's other calls there, and returns at once when sync = 0: it
+ * does not wait, copy synchronously or read anything back - except that a call with more frames than any earlier one, on a batch that already holds
+ * smaller buffers, waits once for the device while it grows them.  Refused calls, checked in this order, queue nothing and leave the batch unchanged:
+ * NULL pcm or out, or both bitrates and bandwidths NULL (LC3_NULL_ERROR); a bad bitdepth, n_frames <= 0, or out_stride below the stride bound (below)
+ * (LC3_ERROR); bandwidths on a high-resolution batch (LC3_HRMODE_BW_ERROR); bandwidths while a stream's bandwidth in force, installed by set_bandwidth,
+ * has a cut-off line below 1 (LC3_ERROR, as encode_bandwidths).  Frame t of stream s applies the rate and then the bandwidth, each with the rule of
+ * encode_bitrates() / encode_bandwidths() and byte for byte as they encode every input they accept, on the device, from the stream's configuration
+ * before the call and carried across frames and calls of every kind.  An entry they would refuse does not fail this call; the frame goes on as the
+ * reference does after a refused setter: a rate outside the limits of set_bitrate, or whose stream-frame exceeds out_stride, encodes the frame at the
+ * carried rate (flag bit 0); a bandwidth set_bandwidth refuses (bit 1), or out of range (bit 2), keeps the bandwidth in force.  The result is LC3_OK
+ * even where frames were flagged; last_status reports the call as for encode_bitrates(), last_records as for encode_bandwidths() without rates.
+ * With bitrates the call runs the kernels of encode_bitrates(); with bandwidths alone it takes the path of encode_bandwidths(), including the overlap
+ * of consecutive calls under set_input_ready, whose promise covers bitrates and bandwidths as it covers the PCM.
+ * After the call each stream is configured on the device with its last valid rate and its last bandwidth in force.  The first host-side reader or writer
+ * of the configuration (num_bytes, stride, bandwidth, set_bitrate, set_bandwidth, encode_bitrates, encode_bandwidths, reset_streams with rates) waits
+ * for the batch's last call and reads it back, once.  encode() and this call do not: they check out_stride against a stride bound, which is stride()
+ * while the host's copy is current and is raised to the out_stride of every call of this kind with bitrates; a caller who wants a smaller out_stride
+ * calls stride() first.  Rates and bandwidths stay configuration, not state: get_state / set_state and the stream blobs are unchanged. */
+LC3_Error lc3plus_enc_batch_encode_rates_device(lc3plus_batch* batch, const void* pcm, int bitdepth, const int32_t* bitrates,
+                                                const int32_t* bandwidths, int n_frames, void* out, int out_stride, int32_t* num_bytes,
+                                                uint8_t* flags, void* hip_stream, int sync);
+/* The per-frame rule of encode_rates_device() on the host alone, no device: start_rates, start_bw [n_streams] the configuration before the call,
+ * bitrates, bandwidths NULL or [n_streams][n_frames] -> num_bytes, bw_in_force, flags [n_streams][n_frames] and end_rates [n_streams].  Returns the
+ * call's error for the arguments (a start rate that is not a valid one fitting out_stride: LC3_BITRATE_ERROR), LC3_OK otherwise. */
+LC3_Error lc3plus_enc_plan_rates_lenient(int samplerate, int channels, float frame_ms, int hrmode, int n_streams, const int* start_rates,
+                                         const int* start_bw, const int* bitrates, const int* bandwidths, int n_frames, int out_stride,
+                                         int* num_bytes, int* bw_in_force, uint8_t* flags, int* end_rates);
+
 /* Checkpoint / resume.  The cross-frame state of every channel-stream of the batch (MDCT / resampler memory, pitch and LTPF histories,
  * rate-control and attack-detector words; R/setup_enc_lc3.h:17-62) as one opaque host array of state_size() bytes.  A batch created with
  * the same (n_streams, samplerate, channels, frame_ms, hrmode, bitrates, bandwidths) that is given the state continues the streams
@@ -130,7 +166,9 @@ LC3_Error lc3plus_enc_batch_import_streams(lc3plus_batch* batch, const int* stre
  * still running (consecutive calls of equal n_frames of up to 256 frames; up to three calls are then in flight); results are identical, and the output of a call is complete in stream order
  * on hip_stream as before.  The promise covers the OUTPUT buffer as well: it must be free to be written when the call is made - not still being read by work
  * queued earlier on hip_stream - because the bitstream writers of consecutive calls may run beside each other (large frames, short calls), each into the
- * buffer of its own call.  Streaming servers that fill their PCM ring ahead of the encode calls and drain their output ring behind them are the use. */
+ * buffer of its own call.  Streaming servers that fill their PCM ring ahead of the encode calls and drain their output ring behind them are the use.
+ * For encode_rates_device() the promise covers its bitrates and bandwidths as well (complete when the call is made), and its num_bytes and flags as
+ * the output buffer (free to be written). */
 LC3_Error lc3plus_enc_batch_set_input_ready(lc3plus_batch* batch, int ready);
 
 /* Kernel-only timing of the last encode() call in milliseconds (HIP events on the launch stream). */
