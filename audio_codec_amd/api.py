@@ -33,9 +33,13 @@ EXPORTS = [
     "lc3plus_dec_batch_stream_state_size", "lc3plus_dec_batch_reset_streams", "lc3plus_dec_batch_export_streams", "lc3plus_dec_batch_import_streams",
     "lc3plus_enc_batch_encode_bandwidths", "lc3plus_enc_batch_bandwidth", "lc3plus_enc_plan_bandwidths",
     "lc3plus_enc_batch_encode_rates_device", "lc3plus_enc_plan_rates_lenient",
+    "lc3plus_enc_batch_encode_packed", "lc3plus_plan_packed", "lc3plus_dec_batch_decode_packed", "lc3plus_dec_plan_packed_lenient",
 ]
 # flag bits of Batch.encode_device_rates (lc3plus_enc_batch_encode_rates_device)
 ENC_FL_RATE, ENC_FL_BW_REFUSED, ENC_FL_BW_RANGE = 1, 2, 4
+# ... and of Batch.encode_device_packed: the frame did not fit the output capacity (encoded, not written); the frame orders of packed output
+ENC_FL_PACK_CAP = 8
+PACK_STREAM_MAJOR, PACK_FRAME_MAJOR = 0, 1
 LC3_BW_WARNING = 18
 
 
@@ -117,6 +121,13 @@ def load_library():
                                                             C.c_void_p, C.c_void_p, C.c_int]
         L.lc3plus_dec_plan_sizes_lenient.argtypes = [C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                                                      C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.lc3plus_enc_batch_encode_packed.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int64,
+                                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+        L.lc3plus_plan_packed.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.lc3plus_dec_batch_decode_packed.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
+                                                      C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int]
+        L.lc3plus_dec_plan_packed_lenient.argtypes = [C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                                      C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.lc3plus_dec_batch_decode_traced.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
                                                       C.c_void_p, C.c_void_p]
         L.lc3plus_dec_batch_last_kernel_ms.restype = C.c_float
@@ -409,6 +420,22 @@ class Batch(_StreamLifecycle):
         if rc:
             raise LC3Error(rc, "lc3plus_enc_batch_encode_rates_device")
 
+    def encode_device_packed(self, d_pcm_ptr, bitdepth, T, d_out_ptr, out_capacity, order=PACK_STREAM_MAJOR, d_bitrates_ptr=None,
+                             d_bandwidths_ptr=None, d_offsets_ptr=None, d_total_ptr=None, d_num_bytes_ptr=None, d_flags_ptr=None, hip_stream=None,
+                             sync=False):
+        """Packed output in device memory (lc3plus_enc_batch_encode_packed): raw device pointers only - pcm [n_streams, T, channels, N], out
+        out_capacity bytes, bitrates and bandwidths [n_streams, T] int32 (either or both may be None), offsets [n_streams, T] int64, total one int64,
+        num_bytes [n_streams, T] int32 and flags [n_streams, T] uint8 (None or written).  Frame (s, t) lies at out + offsets[s, t]; order
+        (PACK_STREAM_MAJOR / PACK_FRAME_MAJOR) says how the frames follow each other.  A frame past out_capacity is encoded, not written, and flagged
+        ENC_FL_PACK_CAP.  Queued on hip_stream; returns at once unless sync."""
+        def p(x):
+            return C.c_void_p(x) if x else None
+        rc = self.lib.lc3plus_enc_batch_encode_packed(self.h, p(d_pcm_ptr), bitdepth, p(d_bitrates_ptr), p(d_bandwidths_ptr), T, order, p(d_out_ptr),
+                                                      int(out_capacity), p(d_offsets_ptr), p(d_total_ptr), p(d_num_bytes_ptr), p(d_flags_ptr),
+                                                      p(hip_stream), 1 if sync else 0)
+        if rc:
+            raise LC3Error(rc, "lc3plus_enc_batch_encode_packed")
+
     def last_kernel_ms(self):
         return float(self.lib.lc3plus_enc_batch_last_kernel_ms(self.h))
 
@@ -455,6 +482,17 @@ def enc_plan_bandwidths(samplerate, frame_ms, hrmode, start, bandwidths):
     if rc not in (0, LC3_BW_WARNING):
         raise LC3Error(rc, "lc3plus_enc_plan_bandwidths")
     return f, rc
+
+
+def plan_packed(sizes, order=PACK_STREAM_MAJOR, capacity=1 << 62):
+    """The offsets of Batch.encode_device_packed on the host (lc3plus_plan_packed, no device needed): sizes [n_streams, n_frames] -> (LC3_Error code,
+    offsets int64 [n_streams, n_frames], total, overflow uint8 [n_streams, n_frames]: ENC_FL_PACK_CAP where the frame does not fit capacity)."""
+    L = load_library()
+    sizes = np.ascontiguousarray(np.atleast_2d(np.asarray(sizes)), dtype=np.int32)
+    S, T = sizes.shape
+    offs = np.zeros((S, T), np.int64); ovf = np.zeros((S, T), np.uint8); tot = C.c_int64(0)
+    rc = L.lc3plus_plan_packed(sizes.ctypes.data, S, T, int(order), int(capacity), offs.ctypes.data, C.byref(tot), ovf.ctypes.data)
+    return rc, offs, tot.value, ovf
 
 
 def enc_plan_rates_lenient(samplerate, channels, frame_ms, hrmode, start_rates, start_bw, bitrates=None, bandwidths=None, out_stride=1 << 20):
@@ -546,6 +584,24 @@ def dec_plan_sizes_lenient(samplerate, channels, frame_ms, hrmode, start, num_by
     return rc, eff, lost, inv, end, mx.value
 
 
+def dec_plan_packed_lenient(samplerate, channels, frame_ms, hrmode, start, num_bytes, offsets, frames_capacity, max_frame_bytes, bfi=None):
+    """The frame rule of DecBatch.decode_device_packed on the host (test hook lc3plus_dec_plan_packed_lenient, no device needed): as
+    dec_plan_sizes_lenient, with each frame's offset, the buffer's capacity and the largest frame in place of in_stride -> (LC3_Error code, effective
+    sizes [S, T] uint16, lost [S, T] uint8, invalid [S, T] uint8, sizes after the call [S], largest channel frame not lost)."""
+    L = load_library()
+    num_bytes = np.ascontiguousarray(num_bytes, dtype=np.int32)
+    S, T = num_bytes.shape
+    offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+    start = np.ascontiguousarray(start, dtype=np.int32)
+    bfi = np.ascontiguousarray(bfi, dtype=np.uint8) if bfi is not None else None
+    eff = np.zeros((S, T), np.uint16); lost = np.zeros((S, T), np.uint8); inv = np.zeros((S, T), np.uint8); end = np.zeros(S, np.int32)
+    mx = C.c_int(0)
+    rc = L.lc3plus_dec_plan_packed_lenient(samplerate, channels, frame_ms, hrmode, S, start.ctypes.data, num_bytes.ctypes.data, offsets.ctypes.data,
+                                           int(frames_capacity), int(max_frame_bytes), bfi.ctypes.data if bfi is not None else None, T,
+                                           eff.ctypes.data, lost.ctypes.data, inv.ctypes.data, end.ctypes.data, C.byref(mx))
+    return rc, eff, lost, inv, end, mx.value
+
+
 class DecBatch(_StreamLifecycle):
     """n_streams independent decoders (lc3plus_dec_batch_*), state resident on the GPU between decode() calls."""
 
@@ -631,6 +687,20 @@ class DecBatch(_StreamLifecycle):
                                                             C.c_void_p(hip_stream) if hip_stream else None, 1 if sync else 0)
         if rc:
             raise LC3Error(rc, "lc3plus_dec_batch_decode_sizes_device")
+
+    def decode_device_packed(self, d_frames_ptr, frames_capacity, d_offsets_ptr, T, d_pcm_ptr, d_num_bytes_ptr, max_frame_bytes, d_bfi_ptr=None,
+                             d_status_ptr=None, bps=16, hip_stream=None, sync=False):
+        """Frames packed back to back in device memory (lc3plus_dec_batch_decode_packed): raw device pointers only - frames frames_capacity bytes,
+        offsets [n_streams, T] int64, num_bytes [n_streams, T] int32 (0 = lost), optional bfi and status [n_streams, T] uint8, pcm [n_streams, T,
+        channels, N].  A frame outside the buffer or above max_frame_bytes is concealed (status bit 1) and never read.  Queued on hip_stream; returns
+        at once unless sync."""
+        def p(x):
+            return C.c_void_p(x) if x else None
+        rc = self.lib.lc3plus_dec_batch_decode_packed(self.h, p(d_frames_ptr), int(frames_capacity), p(d_offsets_ptr), p(d_num_bytes_ptr),
+                                                      int(max_frame_bytes), p(d_bfi_ptr), T, p(d_pcm_ptr), bps, p(d_status_ptr), p(hip_stream),
+                                                      1 if sync else 0)
+        if rc:
+            raise LC3Error(rc, "lc3plus_dec_batch_decode_packed")
 
     def decode_traced(self, frames, bfi=None, bps=16):
         frames, T, stride, bfi, pcm, status = self._prep(frames, bfi, bps)

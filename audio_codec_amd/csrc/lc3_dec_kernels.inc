@@ -283,6 +283,23 @@ lc3_dec_plan_sizes_kernel(const int32_t* __restrict__ num_bytes, const uint8_t* 
     invalid[i] = k >= LC3D_FRAME_BAD_FLAG;
 }
 
+/* The same for frames packed back to back (lc3plus_dec_batch_decode_packed): the rule of lc3d_dec_frame_class_packed, with each frame's offset and the
+ * caller's capacity in place of in_stride.  A frame that breaks it is invalid like a bad size: it is never read and does not move the carry. */
+extern "C" __global__ void __launch_bounds__(256)
+lc3_dec_plan_packed_kernel(const int32_t* __restrict__ num_bytes, const long long* __restrict__ offs, const uint8_t* __restrict__ bfi /* or null */,
+                           const lc3d_dchan* __restrict__ dtab, int tab_n, int channels, long long cap, int max_bytes, long long n, uint16_t* __restrict__ sizes,
+                           uint8_t* __restrict__ lost, uint8_t* __restrict__ invalid)
+{
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int nb = num_bytes[i], fl = bfi ? (int)bfi[i] : 0;
+    const long long off = (fl == 0 && nb != 0) ? offs[i] : 0;        /* a lost frame's offset is not looked at */
+    const int k = lc3d_dec_frame_class_packed(nb, fl, off, cap, max_bytes, dtab, tab_n, channels);
+    sizes[i] = k == LC3D_FRAME_GOOD ? (uint16_t)nb : (uint16_t)0;
+    lost[i] = k != LC3D_FRAME_GOOD;
+    invalid[i] = k >= LC3D_FRAME_BAD_FLAG;
+}
+
 /* ... and after the synthesis: one stream-frame per lane.  An invalid frame's status gets LC3D_DEC_ST_INVALID beside the concealment bit the synthesis
  * wrote.  The lane of a stream's last frame configures the stream with the size of its last good frame of the call (the configuration stays when the
  * call has none): every channel from dtab, with its payload offset, as lc3plus_dec_batch_decode_sizes does on the host.  The concealment kernel of the

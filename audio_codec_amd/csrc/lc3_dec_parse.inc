@@ -126,13 +126,14 @@ template <int OFF, int MMAX> __device__ __forceinline__ void pl_pvq(const unsign
 
 /* Workgroup = up to four waves that share the model tables (7.5 KB); every wave owns a slice of the dynamic LDS.  VAR: per-frame sizes (a kernel of its own,
  * so that the fixed-size kernels stay the code they were). */
-template <bool GLOB, bool VAR> __device__ __forceinline__ void
+template <bool GLOB, bool VAR, bool PKD = false> __device__ __forceinline__ void
 dec_parse_body(const lc3d_plan* __restrict__ P, const lc3d_dchan* __restrict__ chans, const uint8_t* __restrict__ in, int in_stride,
                      const uint8_t* __restrict__ bfi_flags /* [stream][T] or null */,
                      const uint16_t* __restrict__ sizes /* VAR: [stream][T] bytes of each stream-frame, 0 where lost */,
                      const lc3d_dchan* __restrict__ dtab /* VAR: configuration per channel byte count; otherwise chans[channel-stream] */,
                      int T, int n_streams, int nw_max /* LDS words staged per frame; 0: frames are read from global memory */,
-                     int* __restrict__ rec /* [cs][T][PR_WORDS] */, float* __restrict__ ws /* [cs][T][wsr] */, int wsr /* words per spectrum row */)
+                     int* __restrict__ rec /* [cs][T][PR_WORDS] */, float* __restrict__ ws /* [cs][T][wsr] */, int wsr /* words per spectrum row */,
+                     const long long* __restrict__ offs = nullptr /* PKD: [stream][T] byte offset of each stream-frame in `in` (frames packed) */)
 {
     __shared__ ParseLds L;
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, wpg = blockDim.x >> 6, tid = threadIdx.x, nthr = blockDim.x;
@@ -169,7 +170,7 @@ dec_parse_body(const lc3d_plan* __restrict__ P, const lc3d_dchan* __restrict__ c
         const int nbytes = valid ? dc.nbytes : 0;
         /* ---- stage the frame bytes: fw[w][lane], bytes from nbytes on are zero ---- */
         {
-            const uint8_t* src = in + ((size_t)strm * T + t) * in_stride + dc.in_off;
+            const uint8_t* src = (PKD ? in + (nbytes ? offs[(size_t)strm * T + t] : 0) : in + ((size_t)strm * T + t) * in_stride) + dc.in_off;
             const bool al = (((size_t)src) & 3) == 0;
             for (int w = 0; w < nw_max; w++) {             /* (nothing when the frames are read from global memory) */
                 unsigned v = 0;
@@ -184,7 +185,7 @@ dec_parse_body(const lc3d_plan* __restrict__ P, const lc3d_dchan* __restrict__ c
         }
         PLaneT<GLOB> p; p.fw = fw; p.lane = lane; p.nw = nw_max; p.nbytes = nbytes;
         {
-            const uint8_t* src = in + ((size_t)strm * T + t) * in_stride + dc.in_off;
+            const uint8_t* src = (PKD ? in + (nbytes ? offs[(size_t)strm * T + t] : 0) : in + ((size_t)strm * T + t) * in_stride) + dc.in_off;
             p.goff = (int)(((size_t)src) & 3); p.g = (const unsigned*)(src - p.goff); p.fwi = -1; p.bwi = -1; p.fwv = 0; p.bwv = 0;
         }
         int* r = rec + ((size_t)cs * T + t) * PR_WORDS;
@@ -581,3 +582,15 @@ DEC_PARSE_KERNEL(lc3_dec_parse_kernel_g, true, false)
 DEC_PARSE_KERNEL(lc3_dec_parse_kernel_var, false, true)
 DEC_PARSE_KERNEL(lc3_dec_parse_kernel_g_var, true, true)
 #undef DEC_PARSE_KERNEL
+/* frames packed back to back (lc3plus_dec_batch_decode_packed): the per-frame-size kernels addressing each stream-frame through the offset table.  Only good
+ * frames are read (a lost or invalid one has size 0: nbytes 0), and only the aligned words that hold a byte of the frame (the staged read takes whole words
+ * where the source is aligned and the frame has four bytes left, bytes otherwise; pl_gword stops at the last word holding a frame byte). */
+#define DEC_PARSE_KERNEL_PK(name, GLOB) \
+extern "C" __global__ void __launch_bounds__(4 * WAVE) __attribute__((amdgpu_waves_per_eu(DEC_PARSE_EU, DEC_PARSE_EU))) \
+name(const lc3d_plan* __restrict__ P, const lc3d_dchan* __restrict__ chans, const uint8_t* __restrict__ in, const long long* __restrict__ offs, \
+     const uint8_t* __restrict__ bfi_flags, const uint16_t* __restrict__ sizes, const lc3d_dchan* __restrict__ dtab, int T, int n_streams, int nw_max, \
+     int* __restrict__ rec, float* __restrict__ ws, int wsr) \
+{ dec_parse_body<GLOB, true, true>(P, chans, in, 0, bfi_flags, sizes, dtab, T, n_streams, nw_max, rec, ws, wsr, offs); }
+DEC_PARSE_KERNEL_PK(lc3_dec_parse_kernel_var_pk, false)
+DEC_PARSE_KERNEL_PK(lc3_dec_parse_kernel_g_var_pk, true)
+#undef DEC_PARSE_KERNEL_PK

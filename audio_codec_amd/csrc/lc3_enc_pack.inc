@@ -29,7 +29,7 @@ extern __shared__ unsigned pack_fw[];    /* per wave: [16][64]: the lane's curre
 #define PK_XBUF 16
 typedef unsigned __attribute__((aligned(1), may_alias)) pk_u32u;
 
-struct PkW { uint8_t* o; int nbytes; unsigned fw, bw; int q; int bp; unsigned low, range; int cache, carry, carry_count; };
+struct PkW { uint8_t* o; int nbytes; unsigned fw, bw; int q; int bp; unsigned low, range; int cache, carry, carry_count; bool wr; };   /* wr: the frame's bytes are stored (packed output: false where the frame does not fit) */
 /* forward cursor: byte v (whole bytes from the range coder, single bits at finalisation) into byte bp if c, then advance.  Predicated rather than
  * branched: a lane-divergent `if` costs the scalar unit three to four instructions per nesting level, and the coder's renormalisation is four levels deep */
 __device__ __forceinline__ void pk_emit(PkW& w, unsigned v, bool c)
@@ -37,7 +37,7 @@ __device__ __forceinline__ void pk_emit(PkW& w, unsigned v, bool c)
     const bool in = c && w.bp < w.nbytes;
     const unsigned sh = (unsigned)(w.bp & 3) * 8u;
     w.fw |= in ? (v & 255u) << sh : 0u;
-    if (in && sh == 24u) { *(pk_u32u*)(w.o + (w.bp & ~3)) = w.fw; w.fw = 0; }
+    if (in && sh == 24u) { if (w.wr) *(pk_u32u*)(w.o + (w.bp & ~3)) = w.fw; w.fw = 0; }
     w.bp += c ? 1 : 0;
 }
 __device__ __forceinline__ void pk_fwd_or(PkW& w, unsigned v) { if (w.bp < w.nbytes) w.fw |= (v & 255u) << ((w.bp & 3) * 8); }     /* finalisation only: OR without advancing */
@@ -48,7 +48,7 @@ __device__ __forceinline__ void pk_back(PkW& w, unsigned val, int n)
     const unsigned long long acc = (unsigned long long)w.bw | ((unsigned long long)(n >= 32 ? val : val & ((1u << n) - 1u)) << sh);
     if (sh + n >= 32) {
         const int off = w.nbytes - 4 - 4 * (w.q >> 5);
-        if (off >= 0) *(pk_u32u*)(w.o + off) = __builtin_bswap32((unsigned)acc);
+        if (off >= 0 && w.wr) *(pk_u32u*)(w.o + off) = __builtin_bswap32((unsigned)acc);
         w.bw = (unsigned)(acc >> 32);
     } else w.bw = (unsigned)acc;
     w.q += n;
@@ -115,11 +115,12 @@ __device__ __forceinline__ void lane_gain_adjust(const lc3d_plan* __restrict__ P
 /* MODE 0: head and coder in one kernel (lc3_enc_pack_kernel).  MODE 1 / 2: the two halves as kernels of their own (lc3_enc_pack_head_kernel leaves the frame's 56
  * parameters in the head of its scratch row, next to the quantised lines and residual words it leaves there anyway; lc3_enc_pack_code_kernel picks them up) - each half
  * with the registers IT needs: the head's 16-line rounds (lines, quantised lines, the next round in flight) against the coder's per-lane state machine. */
-template <int MODE> __device__ __forceinline__ void
+template <int MODE, bool PK = false> __device__ __forceinline__ void
 pack_body(const lc3d_plan* __restrict__ P, const lc3d_chan* __restrict__ chans, int* __restrict__ dump /* [cs][T][dstride] */, int dstride, int T, int tb, int nt, int ncs,
           uint8_t* __restrict__ out, int out_stride, uint8_t* __restrict__ status /* [cs][T] LC3D_ENC_ST_* bits, or null */,
           float* __restrict__ rows /* [cs][T][srow]: the shaped spectra of the pipelined path, or null: the record is complete (lc3_encode_kernel wrote it) */, int srow,
-          const float* __restrict__ frec /* [cs][T][FR_WORDS] */, int skip_bytes /* channel-streams with frames of this size and more belong to lc3_enc_tailw_kernel; 0: none */)
+          const float* __restrict__ frec /* [cs][T][FR_WORDS] */, int skip_bytes /* channel-streams with frames of this size and more belong to lc3_enc_tailw_kernel; 0: none */,
+          const long long* __restrict__ poff = nullptr /* PK: [stream][T] byte offset of each stream-frame in out, -1: not written (lc3_pack_offsets_kernel) */)
 {
     __shared__ PackLds L;
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, wpg = blockDim.x >> 6, tid = threadIdx.x, nthr = blockDim.x;
@@ -147,7 +148,8 @@ pack_body(const lc3d_plan* __restrict__ P, const lc3d_chan* __restrict__ chans, 
     const int RTd = rows ? T : 1;
     int* r = rows ? LC3D_ROW_BASE(dump, cs, t, T, dstride) : dump + (valid ? row : 0) * dstride;
 #define RP(k_) (&r[LC3D_ROW_OFF((k_), RTd)])
-    PkW w; w.o = out + ((size_t)strm * T + t) * out_stride + (valid ? C->out_off : 0); w.nbytes = nbytes; w.q = 0; w.fw = 0; w.bw = 0;
+    PkW w; w.o = out + ((size_t)strm * T + t) * out_stride + (valid ? C->out_off : 0); w.nbytes = nbytes; w.q = 0; w.fw = 0; w.bw = 0; w.wr = true;
+    if (PK) { const long long po = valid ? poff[(size_t)strm * T + t] : -1; w.o = out + (po < 0 ? 0 : po) + (valid ? C->out_off : 0); w.wr = po >= 0; }
     unsigned* xb = pack_fw + (size_t)wv * PK_XBUF * WAVE;     /* a row is read in 64-byte pieces: each cache line is visited twice, not eight times */
     /* ---- parameters of the frame (isc[] of lc3_encode_kernel): the record head in 16-byte pieces, not one scattered load per field ---- */
     int rc[56];
@@ -584,10 +586,11 @@ pack_body(const lc3d_plan* __restrict__ P, const lc3d_chan* __restrict__ chans, 
          * frame bytes 4 mb ... = frame bytes ... b1) and the unused bytes between them; a byte both cursors hold is OR-ed ---- */
         const int f0 = w.bp & ~3, mb = w.q >> 5, b1 = nbytes - 1 - 4 * mb;
         for (int i = f0; i <= b1; ) {
-            if (i >= f0 + 4 && i + 7 <= b1) { *(pk_u32u*)(w.o + i) = 0u; i += 4; continue; }
+            if (i >= f0 + 4 && i + 7 <= b1) { if (w.wr) *(pk_u32u*)(w.o + i) = 0u; i += 4; continue; }
             const int fj = i - f0, bj = b1 - i;
             const unsigned v = (fj < 4 ? (w.fw >> (8 * fj)) & 255u : 0u) | (bj < 4 ? (w.bw >> (8 * bj)) & 255u : 0u);
-            w.o[i] = (uint8_t)v; i++;
+            if (w.wr) w.o[i] = (uint8_t)v;
+            i++;
         }
     }
 #undef KPI
@@ -605,5 +608,11 @@ extern "C" __global__ void __launch_bounds__(4 * WAVE) __attribute__((amdgpu_wav
 extern "C" __global__ void __launch_bounds__(4 * WAVE) __attribute__((amdgpu_waves_per_eu(5, 5))) lc3_enc_pack_kernel_w5(PK_ARGS) { pack_body<0>(PK_PASS); }
 extern "C" __global__ void __launch_bounds__(4 * WAVE) __attribute__((amdgpu_waves_per_eu(PK_HEAD_EU, PK_HEAD_EU))) lc3_enc_pack_head_kernel(PK_ARGS) { pack_body<1>(PK_PASS); }
 extern "C" __global__ void __launch_bounds__(4 * WAVE) __attribute__((amdgpu_waves_per_eu(PK_CODE_EU, PK_CODE_EU))) lc3_enc_pack_code_kernel(PK_ARGS) { pack_body<2>(PK_PASS); }
+/* packed output (lc3plus_enc_batch_encode_packed): the same four kernels, each frame at its offset of the call's table; every store stays inside the frame's
+ * bytes (forward words at 4k < nbytes, backward words at nbytes - 4 - 4m >= 0, the rest bytewise up to nbytes - 1), so frames back to back do not overlap */
+extern "C" __global__ void __launch_bounds__(4 * WAVE) __attribute__((amdgpu_waves_per_eu(PK_EU, PK_EU))) lc3_enc_pack_kernel_pk(PK_ARGS, const long long* __restrict__ poff) { pack_body<0, true>(PK_PASS, poff); }
+extern "C" __global__ void __launch_bounds__(4 * WAVE) __attribute__((amdgpu_waves_per_eu(5, 5))) lc3_enc_pack_kernel_w5_pk(PK_ARGS, const long long* __restrict__ poff) { pack_body<0, true>(PK_PASS, poff); }
+extern "C" __global__ void __launch_bounds__(4 * WAVE) __attribute__((amdgpu_waves_per_eu(PK_HEAD_EU, PK_HEAD_EU))) lc3_enc_pack_head_kernel_pk(PK_ARGS, const long long* __restrict__ poff) { pack_body<1, true>(PK_PASS, poff); }
+extern "C" __global__ void __launch_bounds__(4 * WAVE) __attribute__((amdgpu_waves_per_eu(PK_CODE_EU, PK_CODE_EU))) lc3_enc_pack_code_kernel_pk(PK_ARGS, const long long* __restrict__ poff) { pack_body<2, true>(PK_PASS, poff); }
 #undef PK_ARGS
 #undef PK_PASS

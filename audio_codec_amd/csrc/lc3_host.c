@@ -804,6 +804,63 @@ LC3_Error lc3plus_enc_plan_rates_lenient(int samplerate, int channels, float fra
     return LC3_OK;
 }
 
+/* ---- packed output in device memory (lc3plus_enc_batch_encode_packed) ---- */
+LC3_Error lc3plus_enc_batch_encode_packed(lc3plus_batch* b, const void* pcm, int bitdepth, const int32_t* bitrates, const int32_t* bandwidths, int n_frames,
+                                          int order, void* out, int64_t out_capacity, int64_t* offsets, int64_t* total, int32_t* num_bytes, uint8_t* flags,
+                                          void* hip_stream, int sync)
+{
+    if (!b || !pcm || !out) return LC3_NULL_ERROR;
+    if (bitdepth != 16 && bitdepth != 24 && bitdepth != 32) return LC3_ERROR;
+    if (n_frames <= 0 || (order != LC3D_PACK_STREAM_MAJOR && order != LC3D_PACK_FRAME_MAJOR) || out_capacity < 0) return LC3_ERROR;
+    if (bandwidths && b->g.hrmode) return LC3_HRMODE_BW_ERROR;
+    if (bandwidths && b->bw_unsafe) {           /* as encode_rates_device */
+        if (enc_refresh(b)) return LC3_ERROR;
+        b->bw_unsafe = 0;
+        for (int i = 0; i < b->n_streams; i++) if (!bw_value_ok(b->chans[(size_t)i * b->g.channels].bandwidth, b->g.dms)) b->bw_unsafe = 1;
+        if (b->bw_unsafe) return LC3_ERROR;
+    }
+    /* no slot: a rate is refused only where set_bitrate refuses it - the bound on the bytes is the geometry's largest stream-frame */
+    const int lim = enc_max_chan_bytes(&b->g) * b->g.channels;
+    lc3d_rate_rule r;
+    if (enc_rate_rule(&b->g, lim, &r)) return LC3_ERROR;
+    const int has = bitrates || bandwidths;
+    int resets = 0;                             /* one-shot attack-detector resets pending from set_bitrate (a stale copy has none) */
+    if (!b->chans_stale) for (int i = 0; i < b->n_streams * b->g.channels; i++) resets |= b->chans[i].reset_attack != 0;
+    if (lc3hip_encode_packed(b->dev, pcm, bitdepth, n_frames, bitrates, bandwidths, &r, order, out, (long long)out_capacity, (long long*)offsets,
+                             (long long*)total, num_bytes, flags, resets, hip_stream, sync)) return LC3_ERROR;
+    if (has) {                                  /* the configuration after the call is on the device only, as after encode_rates_device */
+        if (!b->chans_stale) b->stride_bound = b->stride;
+        if (bitrates && lim > b->stride_bound) b->stride_bound = lim;
+        b->chans_stale = 1;
+        return LC3_OK;
+    }
+    /* as encode(): the one-shot attack-state reset requests have been consumed by this launch */
+    if (b->chans_stale) return LC3_OK;
+    int dirty = 0;
+    for (int i = 0; i < b->n_streams * b->g.channels; i++) if (b->chans[i].reset_attack) { b->chans[i].reset_attack = 0; dirty = 1; }
+    if (dirty) return batch_upload(b, 0, b->n_streams);
+    return LC3_OK;
+}
+/* The offsets of packed output on the host alone (the rule of lc3_pack_offsets_kernel): sizes [n_streams][n_frames] -> offsets [n_streams][n_frames], an
+ * exclusive scan of the sizes in `order`; *total (or NULL) their sum; overflow (or NULL) [n_streams][n_frames] LC3D_ENC_FL_PACK_CAP where the frame does
+ * not fit capacity, 0 elsewhere. */
+LC3_Error lc3plus_plan_packed(const int32_t* sizes, int n_streams, int n_frames, int order, int64_t capacity, int64_t* offsets, int64_t* total, uint8_t* overflow)
+{
+    if (!sizes || !offsets) return LC3_NULL_ERROR;
+    if (n_streams <= 0 || n_frames <= 0 || (order != LC3D_PACK_STREAM_MAJOR && order != LC3D_PACK_FRAME_MAJOR) || capacity < 0) return LC3_ERROR;
+    const long long n = (long long)n_streams * n_frames;
+    long long off = 0;
+    for (long long j = 0; j < n; j++) {
+        const long long s = order ? j % n_streams : j / n_frames, t = order ? j / n_streams : j % n_frames;
+        const size_t i = (size_t)(s * n_frames + t);
+        offsets[i] = off;
+        if (overflow) overflow[i] = lc3d_pack_fits(off, sizes[i], capacity) ? 0 : LC3D_ENC_FL_PACK_CAP;
+        off += sizes[i];
+    }
+    if (total) *total = off;
+    return LC3_OK;
+}
+
 /* debug / stage-parity entry point used by tests: additionally returns one lc3d_trace per channel-frame */
 LC3_Error lc3plus_enc_batch_encode_traced(lc3plus_batch* b, const void* pcm, int bitdepth, int n_frames, void* out, int out_stride, void* traces)
 {
@@ -1187,6 +1244,26 @@ static void dec_plan_sizes_lenient(const geom_t* g, const lc3d_dchan* tab, int t
     *max_chan = mx;
 }
 
+/* The same for lc3plus_dec_batch_decode_packed: offsets, capacity and max_bytes in place of in_stride (lc3d_dec_frame_class_packed). */
+static void dec_plan_packed_lenient(const geom_t* g, const lc3d_dchan* tab, int tab_n, int n_streams, const int* start, const int* num_bytes,
+                                    const int64_t* offsets, int64_t capacity, int max_bytes, const uint8_t* bfi, int n_frames, uint16_t* eff, uint8_t* lost,
+                                    uint8_t* invalid, int* end, int* max_chan)
+{
+    const int C = g->channels;
+    int mx = 0;
+    for (int s = 0; s < n_streams; s++) {
+        int cur = start[s];
+        for (int t = 0; t < n_frames; t++) {
+            const size_t i = (size_t)s * n_frames + t;
+            const int k = lc3d_dec_frame_class_packed(num_bytes[i], bfi ? bfi[i] : 0, (long long)offsets[i], (long long)capacity, max_bytes, tab, tab_n, C);
+            if (k == LC3D_FRAME_GOOD) { cur = num_bytes[i]; if ((cur + C - 1) / C > mx) mx = (cur + C - 1) / C; }
+            eff[i] = (uint16_t)cur; lost[i] = k != LC3D_FRAME_GOOD; invalid[i] = k >= LC3D_FRAME_BAD_FLAG;
+        }
+        end[s] = cur;
+    }
+    *max_chan = mx;
+}
+
 struct lc3plus_dec_batch {
     geom_t g; int n_streams;
     lc3d_dchan* chans;               /* [n_streams * channels] host mirror */
@@ -1355,6 +1432,17 @@ LC3_Error lc3plus_dec_batch_decode_sizes_device(lc3plus_dec_batch* b, const void
     b->chans_stale = 1;
     return LC3_OK;
 }
+LC3_Error lc3plus_dec_batch_decode_packed(lc3plus_dec_batch* b, const void* frames, int64_t frames_capacity, const int64_t* offsets, const int32_t* num_bytes,
+                                          int max_frame_bytes, const uint8_t* bfi, int n_frames, void* pcm, int bps, uint8_t* status, void* hip_stream, int sync)
+{
+    if (!b || !frames || !pcm || !num_bytes || !offsets) return LC3_NULL_ERROR;
+    if (bps != 16 && bps != 24 && bps != 32) return LC3_ERROR;
+    if (n_frames <= 0 || max_frame_bytes <= 0 || frames_capacity < 0) return LC3_ERROR;
+    if (lc3hip_dec_decode_packed(b->dev, frames, (long long)frames_capacity, (const long long*)offsets, num_bytes, max_frame_bytes, bfi, n_frames, pcm, bps,
+                                 status, hip_stream, sync)) return LC3_ERROR;
+    b->chans_stale = 1;
+    return LC3_OK;
+}
 size_t lc3plus_dec_batch_stream_state_size(const lc3plus_dec_batch* b) { return b ? stream_blob_bytes(SS_DEC, &b->g) : 0; }
 LC3_Error lc3plus_dec_batch_reset_streams(lc3plus_dec_batch* b, const int* streams, int n, const int* num_bytes, void* hip_stream, int sync)
 {
@@ -1453,6 +1541,20 @@ LC3_Error lc3plus_dec_plan_sizes_lenient(int samplerate, int channels, float fra
     LC3_Error e = dec_hook_table(samplerate, channels, frame_ms, hrmode, &g, &tab, &tab_n);
     if (e) return e;
     dec_plan_sizes_lenient(&g, tab, tab_n, n_streams, start, num_bytes, bfi, n_frames, in_stride, eff, lost, invalid, end, max_chan);
+    free(tab);
+    return LC3_OK;
+}
+LC3_Error lc3plus_dec_plan_packed_lenient(int samplerate, int channels, float frame_ms, int hrmode, int n_streams, const int* start, const int* num_bytes,
+                                          const int64_t* offsets, int64_t frames_capacity, int max_frame_bytes, const uint8_t* bfi, int n_frames, uint16_t* eff,
+                                          uint8_t* lost, uint8_t* invalid, int* end, int* max_chan)
+{
+    if (!start || !num_bytes || !offsets || !eff || !lost || !invalid || !end || !max_chan) return LC3_NULL_ERROR;
+    if (max_frame_bytes <= 0) return LC3_ERROR;
+    geom_t g; lc3d_dchan* tab = NULL; int tab_n = 0;
+    LC3_Error e = dec_hook_table(samplerate, channels, frame_ms, hrmode, &g, &tab, &tab_n);
+    if (e) return e;
+    dec_plan_packed_lenient(&g, tab, tab_n, n_streams, start, num_bytes, offsets, frames_capacity, max_frame_bytes, bfi, n_frames, eff, lost, invalid, end,
+                            max_chan);
     free(tab);
     return LC3_OK;
 }

@@ -66,6 +66,15 @@
 #define KERNEL_WAVES 4
 #endif
 #endif
+/* -DLC3_ENC_PACKED: the same kernel writing packed output (lc3plus_enc_batch_encode_packed), named with _pk, in objects of its own: frame (stream, t) goes to
+ * out + poff[stream][dT] (lc3_pack_offsets_kernel), or nowhere where poff is -1 (the frame does not fit the caller's capacity) */
+#ifdef LC3_ENC_PACKED
+#define LC3_PK_CAT2(a) a##_pk
+#define LC3_PK_CAT(a) LC3_PK_CAT2(a)
+#define KERNEL_FN LC3_PK_CAT(KERNEL_NAME)
+#else
+#define KERNEL_FN KERNEL_NAME
+#endif
 #define NQL ((MAXN / 4 + 63) / 64)   /* bisection energies (4 bins each) per lane: 2 or 4 */
 #define WAVE 64
 #define LSYNC() __syncthreads()
@@ -2665,7 +2674,7 @@ template <class LdsT> STAGE void st_bitstream(const lc3d_plan* __restrict__ P, c
  * layout only, in objects of their own.  The bandwidth controller takes the frame's bandwidth in Hz from bwf[stream][dt0 + t] (the host has resolved every
  * frame to the value in force, 0 = off) instead of the stream's configuration words, with the formulas of set_bandwidth (lc3d_bw_cut_bin, lc3d_bw_index). */
 extern "C" __global__ void __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(KERNEL_WAVES, KERNEL_WAVES)))
-KERNEL_NAME(const lc3d_plan* __restrict__ P, const lc3d_chan* __restrict__ chans, float* __restrict__ state,
+KERNEL_FN(const lc3d_plan* __restrict__ P, const lc3d_chan* __restrict__ chans, float* __restrict__ state,
                   const void* __restrict__ pcm, int bitdepth, int T, uint8_t* __restrict__ out, int out_stride, int ncs,
                   lc3d_trace* __restrict__ trace, int* __restrict__ dump /* [cs][T][dstride] hand-over to lc3_enc_pack_kernel, or null: write the bytes here */, int dstride,
                   const float* __restrict__ y12 /* [cs][T][128] HP-filtered 12.8 kHz signal from the pre-kernels, or null: resample here */,
@@ -2679,6 +2688,9 @@ KERNEL_NAME(const lc3d_plan* __restrict__ P, const lc3d_chan* __restrict__ chans
 #endif
 #ifdef LC3_ENC_VBW
                   , const uint16_t* __restrict__ bwf /* [stream][dT] bandwidth in force for each stream-frame, Hz */
+#endif
+#ifdef LC3_ENC_PACKED
+                  , const long long* __restrict__ poff /* [stream][dT] byte offset of each stream-frame in out, -1: not written */
 #endif
                   )
 {
@@ -2917,12 +2929,18 @@ KERNEL_NAME(const lc3d_plan* __restrict__ P, const lc3d_chan* __restrict__ chans
         TICK(16);
         if (tr && lane == 0) { tr->n_res_bits = L.isc[I_NRES]; tr->bp_side = L.isc[I_BP_SIDE]; tr->mask_side = L.isc[I_MASK_SIDE]; }
         /* ---- bytes out ---- */
+#if defined(LC3_ENC_PACKED)
+        const long long po = poff[(size_t)strm * dT + dt0 + t];
+        uint8_t* o = out + (po < 0 ? 0 : po) + CI(out_off);
+        const int nby = po < 0 ? 0 : CI(nbytes);
+#else
 #ifdef LC3_ENC_VAR
         uint8_t* o = out + ((size_t)strm * dT + dt0 + t) * out_stride + CI(out_off);
 #else
         uint8_t* o = out + ((size_t)strm * T + t) * out_stride + CI(out_off);
 #endif
         const int nby = CI(nbytes);
+#endif
         if (((nby | (int)(size_t)o) & 3) == 0) { for (int i = lane; i < (nby >> 2); i += WAVE) ((uint32_t*)o)[i] = ((const uint32_t*)BYTES(L))[i]; }
         else for (int i = lane; i < nby; i += WAVE) o[i] = BYTES(L)[i];
         LSYNC();
@@ -2940,11 +2958,11 @@ KERNEL_NAME(const lc3d_plan* __restrict__ P, const lc3d_chan* __restrict__ chans
     if (lane < 16 && !(spec && (lane == I_ATT_POS || lane == I_ATT_FLAG))) ((int*)stp)[LC3D_ST_SCAL(MEMCAP) + 16 + lane] = L.isc[lane];
     (void)ml;
 }
-#if defined(LC3_ENC_VBW) && !defined(LC3_ENC_VAR)   /* the per-frame-bandwidth object: besides lc3_encode_kernel_vbw only the two shape kernels */
+#if defined(LC3_ENC_VBW) && !defined(LC3_ENC_VAR) && !defined(LC3_ENC_PACKED)   /* the per-frame-bandwidth object: besides lc3_encode_kernel_vbw only the two shape kernels */
 #include "lc3_enc_rate.inc"        /* lc3_enc_shape_kernel_vbw */
 #include "lc3_enc_shapel.inc"      /* lc3_enc_shape_lane_kernel_vbw */
 #endif
-#if !defined(LC3_ENC_VAR) && !defined(LC3_ENC_VBW)   /* the per-frame-bitrate and per-frame-bandwidth objects hold only their kernels */
+#if !defined(LC3_ENC_VAR) && !defined(LC3_ENC_VBW) && !defined(LC3_ENC_PACKED)   /* the per-frame-bitrate, per-frame-bandwidth and packed objects hold only their kernels */
 
 /* ------------------------------------------------------------------------------------------------ */
 /* C-ABI device shim (lc3_shim.h): context, uploads, launch                                          */
@@ -3000,6 +3018,18 @@ extern "C" __global__ void lc3_enc_tailw_kernel_big(const lc3d_plan* __restrict_
                                                      const float* __restrict__ frec, uint8_t* __restrict__ out, int out_stride, uint8_t* __restrict__ status, int min_bytes);
 extern "C" __global__ void lc3_enc_rate_kernel_big(const lc3d_plan* __restrict__ P, const lc3d_chan* __restrict__ chans, float* __restrict__ state, int T, int t0, int nt, int ncs,
                                                    const float* __restrict__ rows, int srow, float* __restrict__ frec, const float* __restrict__ xnext, int last);
+/* packed output (-DLC3_ENC_PACKED objects): each one-wave kernel above once more with the table of offsets behind its arguments */
+#define LC3_OW_ARGS const lc3d_plan* __restrict__ P, const lc3d_chan* __restrict__ chans, float* __restrict__ state, const void* __restrict__ pcm, int bitdepth, int T, \
+                    uint8_t* __restrict__ out, int out_stride, int ncs, lc3d_trace* __restrict__ trace, int* __restrict__ dump, int dstride, const float* __restrict__ y12, \
+                    uint8_t* __restrict__ status, int dT, int dt0, const float* __restrict__ spec, const float* __restrict__ frec, const float* __restrict__ xnext
+extern "C" __global__ void lc3_encode_kernel_pk(LC3_OW_ARGS, const long long* __restrict__ poff);
+extern "C" __global__ void lc3_encode_kernel_big_pk(LC3_OW_ARGS, const long long* __restrict__ poff);
+extern "C" __global__ void lc3_encode_kernel_var_pk(LC3_OW_ARGS, const uint16_t* __restrict__ fsz, const lc3d_chan* __restrict__ etab, const long long* __restrict__ poff);
+extern "C" __global__ void lc3_encode_kernel_big_var_pk(LC3_OW_ARGS, const uint16_t* __restrict__ fsz, const lc3d_chan* __restrict__ etab, const long long* __restrict__ poff);
+extern "C" __global__ void lc3_encode_kernel_vbw_pk(LC3_OW_ARGS, const uint16_t* __restrict__ bwf, const long long* __restrict__ poff);
+extern "C" __global__ void lc3_encode_kernel_var_vbw_pk(LC3_OW_ARGS, const uint16_t* __restrict__ fsz, const lc3d_chan* __restrict__ etab, const uint16_t* __restrict__ bwf,
+                                                        const long long* __restrict__ poff);
+#undef LC3_OW_ARGS
 #include "lc3_enc_pack.inc"
 #include "lc3_enc_snsvq.inc"
 #include "lc3_enc_shapel.inc"
@@ -3146,6 +3176,94 @@ extern "C" __global__ void __launch_bounds__(WAVE) lc3_enc_plan_rates_kernel(lc3
     const int4 e = make_int4(rate, bytes, bw, 0);
     carry[s] = e; pend[s] = e;
 }
+/* Packed output (lc3plus_enc_batch_encode_packed): the offsets of the call's frames, an exclusive scan of their sizes in the caller's order (stream-major:
+ * j = s T + t, frame-major: j = t S + s) with 64-bit sums, as a reduce / scan / add chain of three kernels over tiles of PKS_TILE frames.  A frame's size
+ * is fsz[s][t] (per-frame rates: the plan kernel's sizes), else pend[s].y (bandwidths alone: the stream's bytes the plan kernel carried), else the sum of
+ * the stream's channel bytes in chans. */
+#define PKS_THREADS 256
+#define PKS_ITEMS 8
+#define PKS_TILE (PKS_THREADS * PKS_ITEMS)
+struct PkSrc { const uint16_t* fsz; const int4* pend; const lc3d_chan* chans; int channels, order, S, T; };
+__device__ __forceinline__ int pks_size(const PkSrc& q, long long j, size_t* idx)
+{
+    int s, t;
+    if (q.order) { t = (int)(j / q.S); s = (int)(j - (long long)t * q.S); } else { s = (int)(j / q.T); t = (int)(j - (long long)s * q.T); }
+    *idx = (size_t)s * q.T + t;
+    if (q.fsz) return q.fsz[*idx];
+    if (q.pend) return q.pend[s].y;
+    int nb = 0;
+    for (int c = 0; c < q.channels; c++) nb += q.chans[(size_t)s * q.channels + c].nbytes;
+    return nb;
+}
+/* exclusive scan of one value per thread over the workgroup; returns the workgroup's sum in *all */
+__device__ __forceinline__ long long pks_block_scan(long long v, long long* sh, long long* all)
+{
+    const int tid = threadIdx.x;
+    sh[tid] = v;
+    __syncthreads();
+    for (int d = 1; d < PKS_THREADS; d <<= 1) {
+        const long long a = tid >= d ? sh[tid - d] : 0;
+        __syncthreads();
+        sh[tid] += a;
+        __syncthreads();
+    }
+    const long long inc = sh[tid];
+    *all = sh[PKS_THREADS - 1];
+    __syncthreads();
+    return inc - v;
+}
+extern "C" __global__ void __launch_bounds__(PKS_THREADS) lc3_pack_sums_kernel(PkSrc q, long long n, long long* __restrict__ bsum)
+{
+    __shared__ long long sh[PKS_THREADS];
+    const long long j0 = (long long)blockIdx.x * PKS_TILE + (long long)threadIdx.x * PKS_ITEMS;
+    long long v = 0; size_t idx;
+    for (int i = 0; i < PKS_ITEMS; i++) if (j0 + i < n) v += pks_size(q, j0 + i, &idx);
+    long long all;
+    (void)pks_block_scan(v, sh, &all);
+    if (threadIdx.x == 0) bsum[blockIdx.x] = all;
+}
+/* one workgroup: the tile sums -> the tiles' bases (in place), and the call's total */
+extern "C" __global__ void __launch_bounds__(PKS_THREADS) lc3_pack_base_kernel(long long* __restrict__ bsum, long long nb, long long* __restrict__ total)
+{
+    __shared__ long long sh[PKS_THREADS];
+    long long run = 0;
+    for (long long b0 = 0; b0 < nb; b0 += PKS_THREADS) {
+        const long long b = b0 + threadIdx.x;
+        const long long v = b < nb ? bsum[b] : 0;
+        long long all;
+        const long long ex = pks_block_scan(v, sh, &all);
+        if (b < nb) bsum[b] = run + ex;
+        run += all;
+    }
+    if (threadIdx.x == 0 && total) *total = run;
+}
+/* every frame's offset: into the writers' table (-1 where the frame does not fit cap: lc3d_pack_fits) and the caller's offsets; flag bit
+ * LC3D_ENC_FL_PACK_CAP beside the plan kernel's bits (plan_flags) or alone; the sizes into num_bytes when no plan kernel wrote them */
+extern "C" __global__ void __launch_bounds__(PKS_THREADS) lc3_pack_offsets_kernel(PkSrc q, long long n, const long long* __restrict__ base, long long cap,
+                                                                              long long* __restrict__ tab, long long* __restrict__ offsets,
+                                                                              uint8_t* __restrict__ flags, int plan_flags, int32_t* __restrict__ num_bytes)
+{
+    __shared__ long long sh[PKS_THREADS];
+    const long long j0 = (long long)blockIdx.x * PKS_TILE + (long long)threadIdx.x * PKS_ITEMS;
+    int sz[PKS_ITEMS]; size_t ix[PKS_ITEMS];
+    long long v = 0;
+#pragma unroll
+    for (int i = 0; i < PKS_ITEMS; i++) { sz[i] = j0 + i < n ? pks_size(q, j0 + i, &ix[i]) : 0; v += sz[i]; }
+    long long all;
+    long long off = base[blockIdx.x] + pks_block_scan(v, sh, &all);
+#pragma unroll
+    for (int i = 0; i < PKS_ITEMS; i++) {
+        if (j0 + i >= n) break;
+        const size_t k = ix[i];
+        const int fit = lc3d_pack_fits(off, sz[i], cap);
+        tab[k] = fit ? off : -1;
+        if (offsets) offsets[k] = off;
+        if (flags) flags[k] = (uint8_t)((plan_flags ? flags[k] : 0) | (fit ? 0 : LC3D_ENC_FL_PACK_CAP));
+        if (num_bytes) num_bytes[k] = sz[i];
+        off += sz[i];
+    }
+}
+
 /* Tail kernel, behind the call's last kernel: one channel-stream per lane configures its channel from the stream's carry after the call (pend), as the host
  * configures it after encode_bitrates / encode_bandwidths.  With rates (all): the channel's share of the bytes from etab (derive_chan), its payload
  * offset, the bandwidth words and the rate.  Without: the bandwidth words alone.  Either way the pending one-shot attack-detector reset is cleared: the
@@ -3218,6 +3336,10 @@ struct lc3hip_ctx {
     uint16_t* d_pfsz[LC3D_SETS]; uint16_t* d_pbw[LC3D_SETS]; int4* d_pend[LC3D_SETS]; size_t pset_frames; hipEvent_t ev_pset[LC3D_SETS]; int pset_armed[LC3D_SETS], pset;
     int etab_attack, etab_max;                      /* some byte count of the table has attack handling; the largest channel byte count */
     struct { int pending, k, T; const int32_t* rates; const int32_t* bws; int32_t* nb; uint8_t* fl; lc3d_rate_rule rule; } pl;
+    /* packed output (lc3hip_encode_packed), for the call being queued: the scan (pack_scan) writes the table of offsets the writers read - per plan set k
+     * with rates or bandwidths (a set is written again behind the call that used it last, as the plan buffers), one table otherwise (on the launch stream) */
+    struct { int on, order; long long cap; long long* offs; long long* total; int32_t* nb; uint8_t* fl; const long long* tab; } pk;
+    long long* d_poff[LC3D_SETS + 1]; size_t poff_cap; long long* d_pbsum; size_t pbsum_cap /* per slot */; hipEvent_t ev_scan;
 };
 
 #define LC3D_FUSED_MAX_T 8
@@ -3475,6 +3597,25 @@ static int enc_launch(lc3hip_ctx* c, const void* dpcm, int bitdepth, int n_frame
             HIPCHK(hipGetLastError());
         }
         if (dbw && bw_to(c, s)) return 1;
+        const long long* pt = c->pk.on ? c->pk.tab : nullptr;         /* packed output: the _pk kernels, frames at the offsets of the call's table */
+        if (pt) {
+            if (dfsz && dbw) hipLaunchKernelGGL(lc3_encode_kernel_var_vbw_pk, dim3(c->ncs), dim3(WAVE), 0, s, c->d_plan, c->d_chans, c->d_state, dpcm, bitdepth, n_frames,
+                                                dout, 0, c->ncs, dtr, ddump, dstride, dy12, c->d_status, dT, dt0, (const float*)nullptr, (const float*)nullptr,
+                                                (const float*)nullptr, dfsz, (const lc3d_chan*)c->d_etab, dbw, pt);
+            else if (dfsz && c->big) hipLaunchKernelGGL(lc3_encode_kernel_big_var_pk, dim3(c->ncs), dim3(WAVE), 0, s, c->d_plan, c->d_chans, c->d_state, dpcm, bitdepth, n_frames,
+                                                   dout, 0, c->ncs, dtr, ddump, dstride, dy12, c->d_status, dT, dt0, (const float*)nullptr, (const float*)nullptr,
+                                                   (const float*)nullptr, dfsz, (const lc3d_chan*)c->d_etab, pt);
+            else if (dfsz) hipLaunchKernelGGL(lc3_encode_kernel_var_pk, dim3(c->ncs), dim3(WAVE), 0, s, c->d_plan, c->d_chans, c->d_state, dpcm, bitdepth, n_frames,
+                                              dout, 0, c->ncs, dtr, ddump, dstride, dy12, c->d_status, dT, dt0, (const float*)nullptr, (const float*)nullptr,
+                                              (const float*)nullptr, dfsz, (const lc3d_chan*)c->d_etab, pt);
+            else if (c->big) hipLaunchKernelGGL(lc3_encode_kernel_big_pk, dim3(c->ncs), dim3(WAVE), 0, s, c->d_plan, c->d_chans, c->d_state, dpcm, bitdepth, n_frames,
+                                           dout, 0, c->ncs, dtr, ddump, dstride, dy12, c->d_status, dT, dt0, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, pt);
+            else if (dbw) hipLaunchKernelGGL(lc3_encode_kernel_vbw_pk, dim3(c->ncs), dim3(WAVE), 0, s, c->d_plan, c->d_chans, c->d_state, dpcm, bitdepth, n_frames,
+                                             dout, 0, c->ncs, dtr, ddump, dstride, dy12, c->d_status, dT, dt0, (const float*)nullptr, (const float*)nullptr,
+                                             (const float*)nullptr, dbw, pt);
+            else hipLaunchKernelGGL(lc3_encode_kernel_pk, dim3(c->ncs), dim3(WAVE), 0, s, c->d_plan, c->d_chans, c->d_state, dpcm, bitdepth, n_frames,
+                                    dout, 0, c->ncs, dtr, ddump, dstride, dy12, c->d_status, dT, dt0, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, pt);
+        } else
         if (dfsz && dbw) hipLaunchKernelGGL(lc3_encode_kernel_var_vbw, dim3(c->ncs), dim3(WAVE), 0, s, c->d_plan, c->d_chans, c->d_state, dpcm, bitdepth, n_frames,
                                             dout, out_stride, c->ncs, dtr, ddump, dstride, dy12, c->d_status, dT, dt0, (const float*)nullptr, (const float*)nullptr,
                                             (const float*)nullptr, dfsz, (const lc3d_chan*)c->d_etab, dbw);
@@ -3681,9 +3822,10 @@ static int enc_launch(lc3hip_ctx* c, const void* dpcm, int bitdepth, int n_frame
             ps = c->s_pk[c->pk_par];
             HIPCHK(hipStreamWaitEvent(ps, c->ev_rate, 0));
         }
+        if (side && c->pk.on) HIPCHK(hipStreamWaitEvent(ps, c->ev_scan, 0));     /* packed output: behind the call's scan (the table the writers read) */
         if (split) HIPCHK(hipMemsetAsync(c->d_status, 0, (size_t)c->ncs * dT, ps));
         /* large frames: tail + writer a frame per wave (lc3_enc_tailw_kernel, lc3_enc_rate.inc), launched first - its waves are the long ones */
-        const int big_from = (split && c->opt.tailw_bytes && c->max_nbytes >= c->opt.tailw_bytes) ? c->opt.tailw_bytes : 0;
+        const int big_from = (split && c->opt.tailw_bytes && c->max_nbytes >= c->opt.tailw_bytes && !c->pk.on) ? c->opt.tailw_bytes : 0;   /* (no packed form) */
         if (big_from) {
             const int fpw = dT < 4 ? dT : 4;
             const unsigned wruns = (unsigned)((dT + fpw - 1) / fpw);
@@ -3695,14 +3837,20 @@ static int enc_launch(lc3hip_ctx* c, const void* dpcm, int bitdepth, int n_frame
         if (!big_from || c->min_nbytes < big_from) {
             const dim3 grid((unsigned)((tasks + per_wg - 1) / per_wg)), block(wpg * WAVE);
             const size_t dyn = per_wave * wpg + ((size_t)(c->opt.pack_pad_kb > 0 ? c->opt.pack_pad_kb : 0) << 10);
-            if (two) {
+            const long long* pt = c->pk.on ? c->pk.tab : nullptr;
+            if (two && pt) {
+                hipLaunchKernelGGL(lc3_enc_pack_head_kernel_pk, grid, block, 0, ps, c->d_plan, c->d_chans, ddump, dstride, dT, 0, dT, c->ncs, dout, 0, c->d_status, rows_for_pack, c->srow, frec_for_pack, big_from, pt);
+                hipLaunchKernelGGL(lc3_enc_pack_code_kernel_pk, grid, block, dyn, ps, c->d_plan, c->d_chans, ddump, dstride, dT, 0, dT, c->ncs, dout, 0, c->d_status, rows_for_pack, c->srow, frec_for_pack, big_from, pt);
+            } else if (two) {
                 hipLaunchKernelGGL(lc3_enc_pack_head_kernel, grid, block, 0, ps, c->d_plan, c->d_chans, ddump, dstride, dT, 0, dT, c->ncs, dout, out_stride, c->d_status, rows_for_pack, c->srow, frec_for_pack, big_from);
                 hipLaunchKernelGGL(lc3_enc_pack_code_kernel, grid, block, dyn, ps, c->d_plan, c->d_chans, ddump, dstride, dT, 0, dT, c->ncs, dout, out_stride, c->d_status, rows_for_pack, c->srow, frec_for_pack, big_from);
             } else {
                 /* 96 or 128 registers (lc3_enc_pack.inc, the table at lc3_enc_pack_kernel_w5): five waves per SIMD pay for long calls of small 10 ms frames */
                 const bool w5 = c->opt.pack_w5 >= 0 ? c->opt.pack_w5 == 1 : (split && !c->big && !c->hr && c->N == 480 && dT >= 48 && c->max_nbytes <= 100);
                 auto pk = w5 ? lc3_enc_pack_kernel_w5 : lc3_enc_pack_kernel;
-                DUPL('k') hipLaunchKernelGGL(pk, grid, block, dyn, ps, c->d_plan, c->d_chans, ddump, dstride,
+                if (pt) hipLaunchKernelGGL(w5 ? lc3_enc_pack_kernel_w5_pk : lc3_enc_pack_kernel_pk, grid, block, dyn, ps, c->d_plan, c->d_chans, ddump, dstride,
+                                           dT, 0, dT, c->ncs, dout, 0, c->d_status, rows_for_pack, c->srow, frec_for_pack, big_from, pt);
+                else DUPL('k') hipLaunchKernelGGL(pk, grid, block, dyn, ps, c->d_plan, c->d_chans, ddump, dstride,
                                    dT, 0, dT, c->ncs, dout, out_stride, c->d_status, rows_for_pack, c->srow, frec_for_pack, big_from);
             }
         }
@@ -3838,6 +3986,23 @@ static int stage_bw(lc3hip_ctx* c, const uint16_t* bw_host, int n_frames, const 
     return 0;
 }
 static int plan_launch(lc3hip_ctx* c, hipStream_t st);
+/* packed output: the scan of the call's frame sizes on st (lc3_pack_sums_kernel, lc3_pack_base_kernel, lc3_pack_offsets_kernel) into tab, the caller's
+ * offsets, total, flags (plan_flags: the plan kernel has written bits 0 ... 2 there) and num_bytes (where no plan kernel wrote them: plan_nb = 0) */
+static int pack_scan(lc3hip_ctx* c, hipStream_t st, int T, int slot /* the plan set, LC3D_SETS without a plan kernel */, const uint16_t* fsz, const int4* pend,
+                     int plan_flags, int plan_nb)
+{
+    const long long n = (long long)c->n_streams * T, nb = (n + PKS_TILE - 1) / PKS_TILE;
+    long long* tab = c->d_poff[slot]; long long* bsum = c->d_pbsum + (size_t)slot * c->pbsum_cap;
+    PkSrc q; q.fsz = fsz; q.pend = fsz ? nullptr : pend; q.chans = c->d_chans; q.channels = c->channels; q.order = c->pk.order; q.S = c->n_streams; q.T = T;
+    hipLaunchKernelGGL(lc3_pack_sums_kernel, dim3((unsigned)nb), dim3(PKS_THREADS), 0, st, q, n, bsum);
+    hipLaunchKernelGGL(lc3_pack_base_kernel, dim3(1), dim3(PKS_THREADS), 0, st, bsum, nb, c->pk.total);
+    hipLaunchKernelGGL(lc3_pack_offsets_kernel, dim3((unsigned)nb), dim3(PKS_THREADS), 0, st, q, n, (const long long*)bsum, c->pk.cap, tab, c->pk.offs,
+                       c->pk.fl, plan_flags, plan_nb ? (int32_t*)nullptr : c->pk.nb);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(c->ev_scan, st));
+    c->pk.tab = tab;
+    return 0;
+}
 static int bw_to(lc3hip_ctx* c, hipStream_t st)
 {
     const int k = (c->bw_set + LC3D_SETS - 1) % LC3D_SETS;                    /* the slot stage_bw filled for this call */
@@ -3906,6 +4071,7 @@ extern "C" int lc3hip_encode(void* ctx, const void* pcm, int pcm_on_device, int 
     if (fsz_host && upload_fsz(c, fsz_host, n_frames, s, &dfsz, &ev_fsz)) return 1;
     if (bw_host && stage_bw(c, bw_host, n_frames, &dbw, &ev_bw)) return 1;
     HIPCHK(hipEventRecord(c->ev0, s));
+    if (c->pk.on && (fsz_host || bw_host || pack_scan(c, s, n_frames, LC3D_SETS, nullptr, nullptr, 0, 0))) return 1;      /* packed output, no per-frame words */
     if (enc_launch(c, dpcm, bitdepth, n_frames, dout, out_stride, s, dtr, n_frames, 0, true, dfsz, dbw)) return 1;
     HIPCHK(hipEventRecord(c->ev1, s));
     if (ev_fsz) HIPCHK(hipEventRecord(ev_fsz, s));
@@ -3936,6 +4102,8 @@ static int plan_launch(lc3hip_ctx* c, hipStream_t st)
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(c->ev_plan, st)); c->plan_armed = 1;
     c->carry_seed = 0; c->pl.pending = 0;
+    /* packed output: the offsets behind the sizes, on the same stream (the writers, on whichever stream, are behind this one: bw_to, ev_scan) */
+    if (c->pk.on && pack_scan(c, st, T, k, c->pl.rates ? c->d_pfsz[k] : nullptr, c->d_pend[k], c->pl.fl != nullptr, c->pl.nb != nullptr)) return 1;
     return 0;
 }
 /* Per-frame rates and / or bandwidths in device memory, as PCM and output: the plan kernel turns them into the words the per-frame kernels read (it runs
@@ -4001,6 +4169,36 @@ extern "C" int lc3hip_encode_rates_device(void* ctx, const void* pcm, int bitdep
         float ms = 0; if (hipEventElapsedTime(&ms, c->ev0, c->ev1) == hipSuccess) c->last_ms = ms;
     }
     return 0;
+}
+/* Packed output: the call of lc3hip_encode_rates_device (rates_dev or bws_dev given) or of lc3hip_encode with device pointers (neither), with the scan of
+ * the call's frame sizes in front of its writers and the _pk kernels writing each frame at its offset.  The tables grow as the plan sets do: an earlier
+ * call that did not wait may still read the smaller ones, so growing them waits for the device, once. */
+extern "C" int lc3hip_encode_packed(void* ctx, const void* pcm, int bitdepth, int n_frames, const int32_t* rates_dev, const int32_t* bws_dev,
+                                    const lc3d_rate_rule* rule, int order, void* out, long long capacity, long long* offsets_dev, long long* total_dev,
+                                    int32_t* num_bytes_dev, uint8_t* flags_dev, int clear_resets, void* hip_stream, int sync)
+{
+    lc3hip_ctx* c = (lc3hip_ctx*)ctx;
+    HIPCHK(hipSetDevice(c->device));
+    const size_t n = (size_t)c->n_streams * n_frames, nb = (n + PKS_TILE - 1) / PKS_TILE;
+    if (c->poff_cap < n || c->pbsum_cap < nb) {
+        if (c->d_pbsum) HIPCHK(hipDeviceSynchronize());
+        for (int i = 0; i < LC3D_SETS + 1; i++) { if (c->d_poff[i]) HIPCHK(hipFree(c->d_poff[i])); c->d_poff[i] = nullptr; }
+        if (c->d_pbsum) HIPCHK(hipFree(c->d_pbsum));
+        c->d_pbsum = nullptr; c->poff_cap = 0; c->pbsum_cap = 0;
+        for (int i = 0; i < LC3D_SETS + 1; i++) HIPCHK(hipMalloc((void**)&c->d_poff[i], n * sizeof(long long)));
+        HIPCHK(hipMalloc((void**)&c->d_pbsum, (size_t)(LC3D_SETS + 1) * nb * sizeof(long long)));
+        c->poff_cap = n; c->pbsum_cap = nb;
+    }
+    if (!c->ev_scan) HIPCHK(hipEventCreateWithFlags(&c->ev_scan, hipEventDisableTiming));
+    c->pk.on = 1; c->pk.order = order; c->pk.cap = capacity; c->pk.offs = offsets_dev; c->pk.total = total_dev; c->pk.nb = num_bytes_dev; c->pk.fl = flags_dev;
+    c->pk.tab = nullptr;
+    int rc;
+    if (rates_dev || bws_dev)
+        rc = lc3hip_encode_rates_device(ctx, pcm, bitdepth, n_frames, out, 0, rates_dev, bws_dev, rule, num_bytes_dev, flags_dev, clear_resets, hip_stream, sync);
+    else
+        rc = lc3hip_encode(ctx, pcm, 1, bitdepth, n_frames, out, 0, 1, hip_stream, sync, nullptr, nullptr, nullptr);
+    c->pk.on = 0; c->pk.tab = nullptr;
+    return rc;
 }
 /* waits for the batch's last call and copies the configuration of every channel-stream to chans[ncs] (after lc3hip_encode_rates_device) */
 extern "C" int lc3hip_download_chans(void* ctx, lc3d_chan* chans)
@@ -4124,6 +4322,9 @@ extern "C" int lc3hip_destroy(void* ctx)
     if (c->ev_bwcp) hipEventDestroy(c->ev_bwcp);
     if (c->d_carry) hipFree(c->d_carry);
     if (c->ev_plan) { hipEventDestroy(c->ev_plan); hipEventDestroy(c->ev_pset_prev); }
+    for (int i = 0; i < LC3D_SETS + 1; i++) if (c->d_poff[i]) hipFree(c->d_poff[i]);
+    if (c->d_pbsum) hipFree(c->d_pbsum);
+    if (c->ev_scan) hipEventDestroy(c->ev_scan);
     for (int i = 0; i < LC3D_SETS; i++) { if (c->d_pfsz[i]) hipFree(c->d_pfsz[i]); if (c->d_pbw[i]) hipFree(c->d_pbw[i]); if (c->d_pend[i]) hipFree(c->d_pend[i]); if (c->ev_pset[i]) hipEventDestroy(c->ev_pset[i]); }
     for (int i = 0; i < 2; i++) {
         if (c->hp_dpcm[i]) hipFree(c->hp_dpcm[i]);
@@ -4239,7 +4440,8 @@ extern "C" int lc3hip_dec_download_chans(void* ctx, lc3d_dchan* chans)
 /* nb_dev: per-frame sizes in device memory (lc3hip_dec_decode_dsizes) - with bfi_dev (or null) and status_dev (or null), all device pointers like frames and pcm */
 static int dec_decode(lc3hip_dctx* c, const void* frames, int frames_on_device, int in_stride, const uint8_t* bfi_host, const uint16_t* sizes_host,
                       int sizes_max_nbytes, int n_frames, void* pcm, int pcm_on_device, int bps, uint8_t* status_host, void* hip_stream, int sync,
-                      void* trace_host, const int32_t* nb_dev, const uint8_t* bfi_dev, uint8_t* status_dev)
+                      void* trace_host, const int32_t* nb_dev, const uint8_t* bfi_dev, uint8_t* status_dev,
+                      const long long* offs_dev = nullptr /* frames packed (lc3hip_dec_decode_packed): in_stride is then the largest frame */, long long cap = 0)
 {
     HIPCHK(hipSetDevice(c->device));
     hipStream_t s = hip_stream ? (hipStream_t)hip_stream : c->stream;
@@ -4351,6 +4553,9 @@ static int dec_decode(lc3hip_dctx* c, const void* frames, int frames_on_device, 
     HIPCHK(hipEventRecord(c->ev0, s));
     if (nb_dev) {
         const long long n = (long long)c->n_streams * n_frames;
+        if (offs_dev) hipLaunchKernelGGL(lc3_dec_plan_packed_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, nb_dev, offs_dev, bfi_dev, c->d_tab, c->tab_n,
+                                         c->channels, cap, in_stride, n, c->d_sizes, c->d_bfi, c->d_inval);
+        else
         hipLaunchKernelGGL(lc3_dec_plan_sizes_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, nb_dev, bfi_dev, c->d_tab, c->tab_n, c->channels, in_stride, n,
                            c->d_sizes, c->d_bfi, c->d_inval);
         HIPCHK(hipGetLastError());
@@ -4376,6 +4581,10 @@ static int dec_decode(lc3hip_dctx* c, const void* frames, int frames_on_device, 
     const size_t quarter = (160u << 10) / 4, used = sizeof(ParseLds) + per_wave * wpg;
     const size_t pad = c->opt.dec_parse_pad_kb >= 0 ? (size_t)c->opt.dec_parse_pad_kb << 10 : (nw_max || used >= quarter ? 0 : quarter - used);
     auto parse = dsizes ? (nw_max ? lc3_dec_parse_kernel_var : lc3_dec_parse_kernel_g_var) : (nw_max ? lc3_dec_parse_kernel : lc3_dec_parse_kernel_g);
+    if (offs_dev) hipLaunchKernelGGL(nw_max ? lc3_dec_parse_kernel_var_pk : lc3_dec_parse_kernel_g_var_pk, dim3((unsigned)((tasks + per_wg - 1) / per_wg)), dim3(wpg * WAVE),
+                                     per_wave * wpg + pad, sp, c->d_plan, c->d_chans, din, offs_dev, dbfi, dsizes, c->d_tab, n_frames, c->n_streams, nw_max, rec_w, ws_w,
+                                     WS_ROW(c->N));
+    else
     hipLaunchKernelGGL(parse, dim3((unsigned)((tasks + per_wg - 1) / per_wg)), dim3(wpg * WAVE), per_wave * wpg + pad, sp, c->d_plan, c->d_chans, din, in_stride,
                        dbfi, dsizes, c->d_tab, n_frames, c->n_streams, nw_max, rec_w, ws_w, WS_ROW(c->N));
     HIPCHK(hipGetLastError());
@@ -4440,6 +4649,12 @@ extern "C" int lc3hip_dec_decode_dsizes(void* ctx, const void* frames, int in_st
 {
     return dec_decode((lc3hip_dctx*)ctx, frames, 1, in_stride, nullptr, nullptr, 0, n_frames, pcm, 1, bps, nullptr, hip_stream, sync, nullptr,
                       num_bytes_dev, bfi_dev, status_dev);
+}
+extern "C" int lc3hip_dec_decode_packed(void* ctx, const void* frames, long long capacity, const long long* offsets_dev, const int32_t* num_bytes_dev, int max_bytes,
+                                        const uint8_t* bfi_dev, int n_frames, void* pcm, int bps, uint8_t* status_dev, void* hip_stream, int sync)
+{
+    return dec_decode((lc3hip_dctx*)ctx, frames, 1, max_bytes, nullptr, nullptr, 0, n_frames, pcm, 1, bps, nullptr, hip_stream, sync, nullptr,
+                      num_bytes_dev, bfi_dev, status_dev, offsets_dev, capacity);
 }
 extern "C" int lc3hip_dec_stream_state(void* ctx, int mode, const int* streams, int n, const lc3d_dchan* cfg, void* blob, int blob_on_device, const uint32_t* hdr,
                                        uint8_t* status, void* hip_stream, int sync)
@@ -4509,4 +4724,4 @@ extern "C" int lc3hip_dec_destroy(void* ctx)
     return 0;
 }
 #endif /* !LC3_BIG */
-#endif  /* !LC3_ENC_VAR && !LC3_ENC_VBW */
+#endif  /* !LC3_ENC_VAR && !LC3_ENC_VBW && !LC3_ENC_PACKED */

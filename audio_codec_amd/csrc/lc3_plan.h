@@ -136,6 +136,23 @@ static inline LC3D_HD int lc3d_dec_frame_class(int nb, int bfi, int in_stride, c
     return LC3D_FRAME_GOOD;
 }
 
+/* The same rule for frames packed back to back (lc3plus_dec_batch_decode_packed): in place of in_stride, a good frame also lies inside the buffer
+ * (0 <= off, off + nb <= cap) and is at most max_bytes long.  A lost frame's size and offset are not looked at. */
+static inline LC3D_HD int lc3d_dec_frame_class_packed(int nb, int bfi, long long off, long long cap, int max_bytes, const lc3d_dchan* tab, int tab_n,
+                                                      int channels)
+{
+    if (bfi > 1) return LC3D_FRAME_BAD_FLAG;
+    if (bfi == 1 || nb == 0) return LC3D_FRAME_LOST;
+    if (nb < 0 || nb > max_bytes || off < 0 || off > cap - nb) return LC3D_FRAME_BAD_SIZE;
+    return lc3d_dec_frame_class(nb, 0, max_bytes, tab, tab_n, channels);
+}
+/* Packed encoder output (lc3plus_enc_batch_encode_packed): a frame of nb bytes at offset off is written where it fits the caller's capacity; one that does
+ * not is still encoded, but its bytes are not written and it gets LC3D_ENC_FL_PACK_CAP.  The host hook lc3plus_plan_packed and lc3_pack_offsets_kernel. */
+#define LC3D_ENC_FL_PACK_CAP 8
+#define LC3D_PACK_STREAM_MAJOR 0
+#define LC3D_PACK_FRAME_MAJOR 1
+static inline LC3D_HD int lc3d_pack_fits(long long off, int nb, long long cap) { return off >= 0 && nb >= 0 && off <= cap - nb; }
+
 /* The bandwidth controller's words for a bandwidth of bw Hz (R/lc3.c:199-201, lc3_enc_set_bandwidth): the cut-off line and the cap on the
  * detected bandwidth index.  The host's set_bandwidth and the per-frame-bandwidth kernels (lc3plus_enc_batch_encode_bandwidths) use these. */
 static inline LC3D_HD int lc3d_bw_cut_bin(int bw, int dms) { return (bw * dms) / 5000; }

@@ -42,6 +42,9 @@ int   lc3hip_dec_decode(void* ctx, const void* frames, int frames_on_device, int
  * configuration on the device follows each stream's last good frame, the host's copy of it is then unknown (lc3hip_dec_download_chans) */
 int   lc3hip_dec_decode_dsizes(void* ctx, const void* frames, int in_stride, const int32_t* num_bytes_dev, const uint8_t* bfi_dev, int n_frames,
                                void* pcm, int bps, uint8_t* status_dev, void* hip_stream, int sync);
+/* the same with frames packed: frame (s, t) at frames + offsets_dev[s][t], the rule of lc3d_dec_frame_class_packed (capacity, max_bytes) */
+int   lc3hip_dec_decode_packed(void* ctx, const void* frames, long long capacity, const long long* offsets_dev, const int32_t* num_bytes_dev, int max_bytes,
+                               const uint8_t* bfi_dev, int n_frames, void* pcm, int bps, uint8_t* status_dev, void* hip_stream, int sync);
 int   lc3hip_dec_download_chans(void* ctx, lc3d_dchan* chans);    /* waits for the last call, copies the per-channel-stream configuration to chans[ncs] */
 float lc3hip_dec_last_ms(void* ctx);
 int   lc3hip_dec_destroy(void* ctx);
@@ -64,6 +67,12 @@ int   lc3hip_encode(void* ctx, const void* pcm, int pcm_on_device, int bitdepth,
 int   lc3hip_encode_rates_device(void* ctx, const void* pcm, int bitdepth, int n_frames, void* out, int out_stride, const int32_t* rates_dev,
                                  const int32_t* bws_dev, const lc3d_rate_rule* rule, int32_t* num_bytes_dev, uint8_t* flags_dev, int clear_resets,
                                  void* hip_stream, int sync);
+/* packed output (lc3plus_enc_batch_encode_packed): the call of lc3hip_encode_rates_device (rates_dev or bws_dev given) or of lc3hip_encode with device pointers
+ * (neither), each frame written at its offset of an exclusive scan of the frame sizes in `order` (LC3D_PACK_*) where it fits capacity; offsets_dev, total_dev
+ * (null or device) receive the scan, flags_dev bit LC3D_ENC_FL_PACK_CAP the frames that do not fit */
+int   lc3hip_encode_packed(void* ctx, const void* pcm, int bitdepth, int n_frames, const int32_t* rates_dev, const int32_t* bws_dev, const lc3d_rate_rule* rule,
+                           int order, void* out, long long capacity, long long* offsets_dev, long long* total_dev, int32_t* num_bytes_dev, uint8_t* flags_dev,
+                           int clear_resets, void* hip_stream, int sync);
 int   lc3hip_download_chans(void* ctx, lc3d_chan* chans);       /* waits for the last call, copies the per-channel-stream configuration to chans[ncs] */
 float lc3hip_last_ms(void* ctx);
 size_t lc3hip_state_bytes(void* ctx);                            /* checkpoint / resume of the per-stream state (include/lc3plus_batch.h) */

@@ -125,6 +125,36 @@ LC3_Error lc3plus_enc_plan_rates_lenient(int samplerate, int channels, float fra
                                          const int* start_bw, const int* bitrates, const int* bandwidths, int n_frames, int out_stride,
                                          int* num_bytes, int* bw_in_force, uint8_t* flags, int* end_rates);
 
+/* Packed output in device memory, for senders that want their packets back to back (an RTP-style ring) without compacting fixed slots themselves.
+ * Every pointer is a device pointer:
+ *   pcm, bitrates, bandwidths : as encode_rates_device(), except that bitrates and bandwidths may both be NULL (fixed per-stream rates, as encode())
+ *   order        : LC3PLUS_PACK_STREAM_MAJOR (stream 0 frames 0 ... n_frames - 1, then stream 1, ...) or LC3PLUS_PACK_FRAME_MAJOR (frame 0 of streams 0 ...
+ *                  n_streams - 1, then frame 1, ...): how the frames lie in out
+ *   out          : out_capacity bytes; frame (s, t) is written to out + offsets[s * n_frames + t], exactly its num_bytes bytes long
+ *   offsets      : [n_streams][n_frames] int64 (always indexed [s][t]), or NULL: an exclusive scan of the frame sizes in `order`, starting at 0
+ *   total        : one int64, or NULL: the sum of all frame sizes of the call
+ *   num_bytes, flags : as encode_rates_device(), and flag bit 3 (8): the frame did not fit out_capacity (offset + size > out_capacity)
+ * Frame t of stream s is encoded as encode_rates_device() encodes it (as encode() without bitrates and bandwidths), with its per-frame rule and the carry across
+ * calls of every kind - except that there is no out_stride: a rate is refused (flag bit 0) only where set_bitrate refuses it.  A frame that does not fit
+ * out_capacity is still encoded and its stream advances; its bytes are not written.  No byte of out outside [offset, offset + size) of a written frame is
+ * touched, bytes at or past out_capacity included.  Refused calls queue nothing and leave the batch unchanged: NULL pcm or out (LC3_NULL_ERROR); a bad
+ * bitdepth, n_frames <= 0, an order other than 0 / 1, or out_capacity < 0 (LC3_ERROR); then the refusals of encode_rates_device() for bandwidths.  Queueing,
+ * sync = 0, buffer growth, the configuration left on the device and the set_input_ready promise are those of encode_rates_device() (of encode() without
+ * bitrates and bandwidths); the promise covers offsets and total as it covers the output buffer.  The call takes the kernel path encode_rates_device() (or
+ * encode()) takes for the same arguments - the one-wave kernel with its writer inside, the pipelined writer, the large layout, the diagnostic switches - each
+ * in a packed form, behind one scan of the call's frame sizes (three short kernels on the stream of the call's sizes).  The diagnostic large-frame writer
+ * (a frame per wave, off by default) has no packed form: a packed call uses the one-frame-per-lane writer there. */
+#define LC3PLUS_PACK_STREAM_MAJOR 0
+#define LC3PLUS_PACK_FRAME_MAJOR  1
+LC3_Error lc3plus_enc_batch_encode_packed(lc3plus_batch* batch, const void* pcm, int bitdepth, const int32_t* bitrates, const int32_t* bandwidths, int n_frames,
+                                          int order, void* out, int64_t out_capacity, int64_t* offsets, int64_t* total, int32_t* num_bytes, uint8_t* flags,
+                                          void* hip_stream, int sync);
+/* The offsets of encode_packed() on the host alone, no device: sizes [n_streams][n_frames] -> offsets [n_streams][n_frames] (indexed [s][t]), *total (or NULL)
+ * the sum, overflow (or NULL) [n_streams][n_frames] 8 where offset + size > capacity, 0 elsewhere.  LC3_ERROR for n_streams or n_frames <= 0, a bad order
+ * or capacity < 0. */
+LC3_Error lc3plus_plan_packed(const int32_t* sizes, int n_streams, int n_frames, int order, int64_t capacity, int64_t* offsets, int64_t* total,
+                              uint8_t* overflow);
+
 /* Checkpoint / resume.  The cross-frame state of every channel-stream of the batch (MDCT / resampler memory, pitch and LTPF histories,
  * rate-control and attack-detector words; R/setup_enc_lc3.h:17-62) as one opaque host array of state_size() bytes.  A batch created with
  * the same (n_streams, samplerate, channels, frame_ms, hrmode, bitrates, bandwidths) that is given the state continues the streams
@@ -242,6 +272,24 @@ LC3_Error lc3plus_dec_batch_decode_sizes(lc3plus_dec_batch* batch, const void* f
 LC3_Error lc3plus_dec_batch_decode_sizes_device(lc3plus_dec_batch* batch, const void* frames, int in_stride, const int32_t* num_bytes,
                                                 const uint8_t* bfi, int n_frames, void* pcm, int bps, uint8_t* status,
                                                 void* hip_stream, int sync);
+/* Frames packed back to back in device memory, for receivers whose packets land in a receive ring.  As decode_sizes_device(), with
+ *   frames          : frames_capacity bytes; frame (s, t) is read from frames + offsets[s * n_frames + t], num_bytes[s][t] bytes
+ *   offsets         : [n_streams][n_frames] int64 - any offsets: odd, out of order, with gaps (the offsets of encode_packed() fit directly)
+ *   max_frame_bytes : the largest frame the call may hold (> 0)
+ * The frame rule is decode_sizes_device()'s with in_stride replaced: a good frame also needs 0 <= offset, offset + size <= frames_capacity and size <=
+ * max_frame_bytes.  A frame that breaks the rule is concealed with status bit 1, its bytes are never read and it does not move the carried size; a lost
+ * frame's offset is not looked at.  Only the aligned words that hold a byte of a good frame are read.  The parser stages frames in LDS up to
+ * ceil(max_frame_bytes / channels) bytes per channel: a tight max_frame_bytes keeps the staged parser.  Refused calls queue nothing: NULL frames, offsets,
+ * num_bytes or pcm (LC3_NULL_ERROR); a bad bps, n_frames <= 0, max_frame_bytes <= 0 or frames_capacity < 0 (LC3_ERROR).  The call takes the path of
+ * decode_sizes_device() and is queued and ordered the same way. */
+LC3_Error lc3plus_dec_batch_decode_packed(lc3plus_dec_batch* batch, const void* frames, int64_t frames_capacity, const int64_t* offsets, const int32_t* num_bytes,
+                                          int max_frame_bytes, const uint8_t* bfi, int n_frames, void* pcm, int bps, uint8_t* status, void* hip_stream, int sync);
+/* The frame rule of decode_packed() on the host alone, no device: start [n_streams] the sizes before the call, num_bytes, offsets, bfi (or NULL)
+ * [n_streams][n_frames] -> eff (the size in force), lost, invalid [n_streams][n_frames], end [n_streams] the sizes after the call and *max_chan the largest
+ * channel frame not lost.  LC3_ERROR for max_frame_bytes <= 0, the geometry's errors otherwise. */
+LC3_Error lc3plus_dec_plan_packed_lenient(int samplerate, int channels, float frame_ms, int hrmode, int n_streams, const int* start, const int* num_bytes,
+                                          const int64_t* offsets, int64_t frames_capacity, int max_frame_bytes, const uint8_t* bfi, int n_frames,
+                                          uint16_t* eff, uint8_t* lost, uint8_t* invalid, int* end, int* max_chan);
 float     lc3plus_dec_batch_last_kernel_ms(lc3plus_dec_batch* batch);
 /* checkpoint / resume of the decoders' cross-frame state (overlap-add memory, last good spectrum, LTPF histories, concealment words), as
  * for the encoder batch; the frame sizes are configuration (lc3plus_dec_batch_set_num_bytes), not state */
