@@ -34,7 +34,11 @@ EXPORTS = [
     "lc3plus_enc_batch_encode_bandwidths", "lc3plus_enc_batch_bandwidth", "lc3plus_enc_plan_bandwidths",
     "lc3plus_enc_batch_encode_rates_device", "lc3plus_enc_plan_rates_lenient",
     "lc3plus_enc_batch_encode_packed", "lc3plus_plan_packed", "lc3plus_dec_batch_decode_packed", "lc3plus_dec_plan_packed_lenient",
+    "lc3plus_pcm_format_check", "lc3plus_pcm_offset",
 ]
+# the PCM format word of the batch calls (include/lc3plus_batch.h): a sample type - 16, 24, 32 or PCM_FLOAT32 - alone or with one layout
+PCM_FLOAT32, PCM_INTERLEAVED, PCM_CHANNEL_MAJOR = 0x80, 0x100, 0x200
+PCM_LAYOUTS = {None: 0, "default": 0, "interleaved": PCM_INTERLEAVED, "channel_major": PCM_CHANNEL_MAJOR}
 # flag bits of Batch.encode_device_rates (lc3plus_enc_batch_encode_rates_device)
 ENC_FL_RATE, ENC_FL_BW_REFUSED, ENC_FL_BW_RANGE = 1, 2, 4
 # ... and of Batch.encode_device_packed: the frame did not fit the output capacity (encoded, not written); the frame orders of packed output
@@ -137,8 +141,41 @@ def load_library():
         L.lc3plus_dec_batch_num_bytes.argtypes = [C.c_void_p, C.c_int]
         L.lc3plus_dec_batch_set_input_ready.argtypes = [C.c_void_p, C.c_int]
         L.lc3plus_dec_batch_set_num_bytes.argtypes = [C.c_void_p, C.c_int, C.c_int]
+        L.lc3plus_pcm_format_check.argtypes = [C.c_int]
+        L.lc3plus_pcm_offset.argtypes = [C.c_int] * 8
+        L.lc3plus_pcm_offset.restype = C.c_int64
         _LIB = L
     return _LIB
+
+
+def pcm_format(sample, layout=None):
+    """The format word of a sample type (16, 24, 32, PCM_FLOAT32 or a numpy dtype) and a layout (None / "default", "interleaved", "channel_major" or the bit)."""
+    if not isinstance(sample, int):
+        dt = np.dtype(sample)
+        sample = {np.dtype(np.int16): 16, np.dtype(np.float32): PCM_FLOAT32}.get(dt)
+        if sample is None:
+            raise ValueError("no PCM sample type for dtype %s (int32 is 24 or 32: say which)" % dt)
+    word = sample | (layout if isinstance(layout, int) else PCM_LAYOUTS[layout])
+    if load_library().lc3plus_pcm_format_check(word) != 0:
+        raise LC3Error(1, "pcm format %#x" % word)
+    return word
+
+
+def pcm_shape(fmt, S, T, channels, N):
+    """The array shape of one call's PCM in the layout of format word fmt."""
+    if fmt & PCM_INTERLEAVED:
+        return (S, T * N, channels)
+    if fmt & PCM_CHANNEL_MAJOR:
+        return (S, channels, T * N)
+    return (S, T, channels, N)
+
+
+def pcm_dtype(fmt):
+    return {16: np.int16, PCM_FLOAT32: np.float32}.get(fmt & 0xFF, np.int32)
+
+
+def pcm_offset(fmt, channels, n_frames, samples, stream, frame, channel, sample):
+    return int(load_library().lc3plus_pcm_offset(fmt, channels, n_frames, samples, stream, frame, channel, sample))
 
 
 def _stream_list(streams):
@@ -279,14 +316,32 @@ class Batch(_StreamLifecycle):
         self.last_num_bytes = np.zeros((self.n_streams, T), dtype=np.int32)
         return br
 
-    def encode(self, pcm, bitdepth=16, bitrates=None, bandwidths=None):
+    def _pcm_in(self, pcm, bitdepth, layout):
+        """The format word and frame count of a host PCM array: float32 arrays are PCM_FLOAT32 whatever bitdepth says, the shape must be the layout's."""
+        fmt = pcm_format(PCM_FLOAT32 if pcm.dtype == np.float32 else bitdepth & 0xFF, (bitdepth & 0x300) | (layout if isinstance(layout, int) else PCM_LAYOUTS[layout]))
+        if pcm.dtype != pcm_dtype(fmt):
+            raise ValueError("pcm dtype %s does not match format %#x" % (pcm.dtype, fmt))
+        if fmt & (PCM_INTERLEAVED | PCM_CHANNEL_MAJOR):
+            n = pcm.shape[1] if fmt & PCM_INTERLEAVED else pcm.shape[-1]
+            T = n // self.N
+            if pcm.ndim != 3 or n % self.N or pcm.shape != pcm_shape(fmt, self.n_streams, T, self.channels, self.N):
+                raise ValueError("pcm shape %s is not %s" % (pcm.shape, "[n_streams, T * N, channels]" if fmt & PCM_INTERLEAVED else "[n_streams, channels, T * N]"))
+            return fmt, T
+        T = pcm.shape[1]
+        if pcm.shape not in (pcm_shape(fmt, self.n_streams, T, self.channels, self.N), (self.n_streams, T, self.N) if self.channels == 1 else None):
+            raise ValueError("pcm shape %s is not [n_streams, T, channels, N]" % (pcm.shape,))
+        return fmt, T
+
+    def encode(self, pcm, bitdepth=16, bitrates=None, bandwidths=None, layout=None):
         """pcm: host array [n_streams, T, channels, N] (or [n_streams, T, N] for mono) -> uint8 [n_streams, T, stride].
+        A float32 array is taken as PCM_FLOAT32 (full scale 1.0); layout: None, "interleaved" (pcm [n_streams, T * N, channels]) or "channel_major"
+        (pcm [n_streams, channels, T * N]).  bitdepth may also be a whole format word.
         bitrates: None, or [n_streams, T] total bitrate per stream-frame (lc3plus_enc_batch_encode_bitrates): the output is then
         [n_streams, T, largest frame of the call] and last_num_bytes [n_streams, T] holds each frame's size.
         bandwidths: None, or [n_streams, T] bandwidth in Hz per stream-frame, anything that broadcasts to it (lc3plus_enc_batch_encode_bandwidths),
         with or without bitrates; last_result is then 0 or LC3_BW_WARNING (a refused value kept the bandwidth in force)."""
         pcm = np.ascontiguousarray(pcm)
-        T = pcm.shape[1]
+        bitdepth, T = self._pcm_in(pcm, bitdepth, layout)
         if bandwidths is not None:
             stride = max(int(enc_plan_bitrates_for(self, self._bitrates(bitrates, T)).max()), 1) if bitrates is not None else self.stride
             out = np.zeros((self.n_streams, T, stride), dtype=np.uint8)
@@ -642,14 +697,15 @@ class DecBatch(_StreamLifecycle):
         if rc:
             raise LC3Error(rc, "lc3plus_dec_batch_set_state")
 
-    def _prep(self, frames, bfi, bps):
+    def _prep(self, frames, bfi, bps, layout=None):
         frames = np.ascontiguousarray(frames, dtype=np.uint8)
         S, T, stride = frames.shape
         assert S == self.n_streams
         if bfi is not None:
             bfi = np.ascontiguousarray(bfi, dtype=np.uint8)
             assert bfi.shape == (S, T)
-        pcm = np.zeros((S, T, self.channels, self.N), dtype=np.int16 if bps == 16 else np.int32)
+        fmt = pcm_format(bps & 0xFF, (bps & 0x300) | (layout if isinstance(layout, int) else PCM_LAYOUTS[layout]))
+        pcm = np.zeros(pcm_shape(fmt, S, T, self.channels, self.N), dtype=pcm_dtype(fmt))
         status = np.zeros((S, T), dtype=np.uint8)
         return frames, T, stride, bfi, pcm, status
 
@@ -659,9 +715,12 @@ class DecBatch(_StreamLifecycle):
             raise ValueError("num_bytes must have shape %s, not %s" % ((self.n_streams, T), num_bytes.shape))
         return num_bytes
 
-    def decode(self, frames, bfi=None, bps=16, num_bytes=None):
+    def decode(self, frames, bfi=None, bps=16, num_bytes=None, layout=None):
         """frames: uint8 [n_streams, T, stride]; bfi: optional [n_streams, T] -> (pcm [n_streams, T, channels, N], status).
-        num_bytes: optional [n_streams, T] bytes of every stream-frame, 0 = lost (lc3plus_dec_batch_decode_sizes)."""
+        num_bytes: optional [n_streams, T] bytes of every stream-frame, 0 = lost (lc3plus_dec_batch_decode_sizes).
+        bps: 16, 24, 32 or PCM_FLOAT32 (float32 samples, full scale 1.0), or a whole format word; layout: None, "interleaved" (pcm [n_streams, T * N,
+        channels]) or "channel_major" (pcm [n_streams, channels, T * N])."""
+        bps = pcm_format(bps & 0xFF, (bps & 0x300) | (layout if isinstance(layout, int) else PCM_LAYOUTS[layout]))
         frames, T, stride, bfi, pcm, status = self._prep(frames, bfi, bps)
         if num_bytes is not None:
             nb = self._sizes(num_bytes, T)

@@ -556,21 +556,30 @@ DEC_SYNTH_KERNEL(const lc3d_plan* __restrict__ P, float* __restrict__ state,
         DTICK(9);
         /* ---- output R/dec_lc3_fl.c:115-127 ---- */
         {
-            const size_t o = (((size_t)strm * T + t) * channels + ch) * (size_t)N;
-            if (bps == 16) {
+            /* bps is the PCM format word (lc3_plan.h: lc3d_pcm_*): the sample type, and the layout that gives the frame's first element and the step between samples */
+            const size_t o = lc3d_pcm_frame(bps, channels, T, N, strm, t, ch);
+            const int ps = lc3d_pcm_stride(bps, channels), ty = bps & LC3D_PCM_TYPE_MASK;
+            if (ty == 16) {
                 int16_t* op = (int16_t*)pcm + o;
                 for (int i = lane; i < N; i += WAVE) {
                     const float tt = (float)round((double)(0x1p15f * (out[i] * 0x1p-15f)));
-                    op[i] = (int16_t)fmaxf(fminf(tt, 32767.0f), -32768.0f);
+                    op[(size_t)i * ps] = (int16_t)fmaxf(fminf(tt, 32767.0f), -32768.0f);
                 }
+            } else if (ty == LC3D_PCM_FLOAT32) {
+                /* float: the synthesised sample at full scale 1.0, neither rounded nor clipped; 16 bytes per lane where the samples follow each other */
+                float* op = (float*)pcm + o;
+                if (ps == 1 && (N & 3) == 0 && (((size_t)op) & 15) == 0) {
+                    for (int i = lane; i < (N >> 2); i += WAVE)
+                        ((float4*)op)[i] = make_float4(out[4 * i] * 0x1p-15f, out[4 * i + 1] * 0x1p-15f, out[4 * i + 2] * 0x1p-15f, out[4 * i + 3] * 0x1p-15f);
+                } else for (int i = lane; i < N; i += WAVE) op[(size_t)i * ps] = out[i] * 0x1p-15f;
             } else {
                 int32_t* op = (int32_t*)pcm + o;
-                const float sc = bps == 24 ? 0x1p23f : 0x1p31f;
+                const float sc = ty == 24 ? 0x1p23f : 0x1p31f;
                 for (int i = lane; i < N; i += WAVE) {
                     /* the reference converts without clipping (R/dec_lc3_fl.c:123-125); out of range that is undefined in C and yields
                      * INT32_MIN on the x86-64 builds the vectors come from (cvttsd2si), for either sign and for NaN: reproduced here */
                     const double r = round((double)(sc * (out[i] * 0x1p-15f)));
-                    op[i] = (r >= -2147483648.0 && r < 2147483648.0) ? (int32_t)r : (int32_t)0x80000000;
+                    op[(size_t)i * ps] = (r >= -2147483648.0 && r < 2147483648.0) ? (int32_t)r : (int32_t)0x80000000;
                 }
             }
         }

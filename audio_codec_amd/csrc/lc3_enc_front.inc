@@ -8,7 +8,11 @@
  * of a launch at once, a run of `fpw` consecutive frames per wave (the MDCT memory then slides inside LDS as in the sequential
  * kernel; one frame per wave where the launch is a short run of the pipelined path and its latency counts), with the stage functions of lc3_kernels.hip unchanged; the sequential kernel picks the spectrum and the record up from HBM.
  * The wave that owns a stream's last frame hands the MDCT memory for the next launch to the sequential kernel, which stores it in the
- * stream's state (waves of this kernel that start a stream's launch are still reading that state). */
+ * stream's state (waves of this kernel that start a stream's launch are still reading that state).
+ *
+ * FRONT_PCM_FMT 0: everything, the kernel for the reference's three PCM formats (16, 24, 32 in the default layout) token for token what it was before the PCM
+ * format word existed.  FRONT_PCM_FMT 1 (the -DLC3_PCM_FMT objects): the front kernel alone, named with _fmt, for the formats beyond those (float samples, the
+ * interleaved and the channel-major layout, lc3_plan.h: lc3d_pcm_*); the two differ in the PCM load alone. */
 #ifndef FRONT_FPW
 #define FRONT_FPW 4
 #endif
@@ -19,8 +23,13 @@
 #define FRONT_WAVES 5
 #endif
 #endif
-#ifdef LC3_BIG
+#undef FRONT_KERNEL_NAME
+#if defined(LC3_BIG) && FRONT_PCM_FMT
+#define FRONT_KERNEL_NAME lc3_enc_front_kernel_big_fmt
+#elif defined(LC3_BIG)
 #define FRONT_KERNEL_NAME lc3_enc_front_kernel_big
+#elif FRONT_PCM_FMT
+#define FRONT_KERNEL_NAME lc3_enc_front_kernel_fmt
 #else
 #define FRONT_KERNEL_NAME lc3_enc_front_kernel
 #endif
@@ -47,11 +56,19 @@ FRONT_KERNEL_NAME(const lc3d_plan* __restrict__ P, const lc3d_chan* __restrict__
     const float sc = bitdepth == 24 ? 256.0f : 65536.0f;
     /* MDCT memory = the last N - la_zeros samples of the frame before the run (R/mdct.c:111), right-aligned in its slot */
     if (t0 == 0) { for (int i = lane; i < MEMCAP; i += WAVE) L.xbuf[i] = xprev[(size_t)cs * xprev_stride + i]; }
+#if FRONT_PCM_FMT
+    else {
+        const int ps = lc3d_pcm_stride(bitdepth, channels);
+        const size_t pidx = lc3d_pcm_frame(bitdepth, channels, T, N, strm, t0 - 1, ch) + (size_t)(N - ml) * ps;
+        for (int j = lane; j < ml; j += WAVE) L.xbuf[MEMCAP - ml + j] = pcm_in(pcm, bitdepth, pidx + (size_t)j * ps);
+    }
+#else
     else {
         const size_t pidx = (((size_t)strm * T + t0 - 1) * channels + ch) * N + (N - ml);
         for (int j = lane; j < ml; j += WAVE)
             L.xbuf[MEMCAP - ml + j] = bitdepth == 16 ? (float)((const int16_t*)pcm)[pidx + j] : (float)((const int32_t*)pcm)[pidx + j] / sc;
     }
+#endif
     /* attack detector, first half (R/attack_detector.c:26-77): its filter memory entering a frame is the last two 16 kHz samples of the
      * previous frame - the state for the first frame of a launch, a function of the previous frame's PCM otherwise */
     const bool att = CI(attack_handling) != 0;
@@ -68,6 +85,18 @@ FRONT_KERNEL_NAME(const lc3d_plan* __restrict__ P, const lc3d_chan* __restrict__
         }
     }
     for (int t = t0; t < t1; t++) {
+#if FRONT_PCM_FMT
+        {                                                                              /* by the format word: the frame's first element and the step between its samples */
+            const size_t o = lc3d_pcm_frame(bitdepth, channels, T, N, strm, t, ch);
+            if (pcm_f32_wide(pcm, bitdepth, o, N)) {                                   /* float samples one after the other: 16 bytes per lane */
+                const float4* p = (const float4*)((const float*)pcm + o);
+                for (int i = lane; i < (N >> 2); i += WAVE) *(float4*)&XCUR(L)[4 * i] = pcm_f32x4(p[i]);
+            } else {
+                const int ps = lc3d_pcm_stride(bitdepth, channels);
+                for (int i = lane; i < N; i += WAVE) XCUR(L)[i] = pcm_in(pcm, bitdepth, o + (size_t)i * ps);
+            }
+        }
+#else
         const size_t fidx = ((size_t)strm * T + t) * channels + ch;
         if (bitdepth == 16) {
             const int16_t* p = (const int16_t*)pcm + fidx * N;
@@ -85,6 +114,7 @@ FRONT_KERNEL_NAME(const lc3d_plan* __restrict__ P, const lc3d_chan* __restrict__
             const int32_t* p = (const int32_t*)pcm + fidx * N;
             for (int i = lane; i < N; i += WAVE) XCUR(L)[i] = (float)p[i] / sc;
         }
+#endif
         LSYNC();
         float* r = rec + ((size_t)cs * RT + r0 + t) * FR_WORDS;
         if (att) {
@@ -128,7 +158,7 @@ FRONT_KERNEL_NAME(const lc3d_plan* __restrict__ P, const lc3d_chan* __restrict__
     if (t1 == T) for (int i = lane; i < MEMCAP; i += WAVE) xnext[(size_t)cs * MEMCAP + i] = L.xbuf[i];
 }
 
-#ifndef LC3_BIG
+#if !defined(LC3_BIG) && !FRONT_PCM_FMT
 /* attack detector, second half (R/attack_detector.c:79-102): one channel-stream per lane walks the frames of the launch over the block
  * energies the front kernel left in the records and writes each frame's flag back; the detector's state lives in the stream's state
  * words (same words the sequential kernel uses on its own path).  A pending reset (R/setup_enc_lc3.c:297-308) is applied first. */

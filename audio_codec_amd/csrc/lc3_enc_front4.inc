@@ -77,7 +77,12 @@ __device__ __forceinline__ void f4_dft240x4(float* x, const lc3d_plan* __restric
 #define F4_WAVES 4
 #endif
 extern "C" __global__ void __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(F4_WAVES, F4_WAVES)))
-lc3_enc_front4_kernel(const lc3d_plan* __restrict__ P, const lc3d_chan* __restrict__ chans, const float* __restrict__ state, const void* __restrict__ pcm, int bitdepth,
+#ifdef LC3_PCM_FMT               /* the object of the PCM formats beyond 16 / 24 / 32 (float samples, the interleaved and the channel-major layout): the PCM load differs, nothing else */
+lc3_enc_front4_kernel_fmt(
+#else
+lc3_enc_front4_kernel(
+#endif
+                      const lc3d_plan* __restrict__ P, const lc3d_chan* __restrict__ chans, const float* __restrict__ state, const void* __restrict__ pcm, int bitdepth,
                       int T, int tb, int nt /* frames tb ... tb + nt - 1 of the call's T */, int ncs, float* __restrict__ spec, int srow, int RT, int r0, float* __restrict__ rec,
                       float* __restrict__ xnext, const float* __restrict__ xprev, int xprev_stride)
 {
@@ -92,7 +97,37 @@ lc3_enc_front4_kernel(const lc3d_plan* __restrict__ P, const lc3d_chan* __restri
     constexpr int N = F4_N, h = N / 2;
     const int channels = PI(channels);
     const int strm = cs / channels, ch = cs - strm * channels;
+#ifndef LC3_PCM_FMT
     const float sc = bitdepth == 24 ? 256.0f : 65536.0f;
+#endif
+#ifdef LC3_PCM_FMT
+    /* ---- PCM of the run and the MDCT memory in front of it -> x ---- */
+    {   /* by the format word: the run's first element, the step to the next sample and to the channel's next frame.  Float samples that follow each other (480 x 4
+         * bytes per frame from a 16-byte aligned base) take 16 bytes per lane like the 16-bit ones of the kernel without the suffix. */
+        const int ps = lc3d_pcm_stride(bitdepth, channels);
+        const size_t pf0 = lc3d_pcm_frame(bitdepth, channels, T, N, strm, t0, ch), pfst = lc3d_pcm_fstep(bitdepth, channels, N);
+        const bool fastf = pcm_f32_wide(pcm, bitdepth, pf0, N) && ((pfst * 4) & 15) == 0;
+        if (t0 == 0) { for (int i = lane; i < MEMCAP; i += WAVE) L.x[i] = xprev[(size_t)cs * xprev_stride + i]; }
+        else {
+            const size_t pidx = pf0 - pfst + (size_t)(N - MEMCAP) * ps;
+            if (fastf) {
+                const float4* p = (const float4*)((const float*)pcm + pidx);
+                for (int j = lane; j < MEMCAP / 4; j += WAVE) *(float4*)&L.x[4 * j] = pcm_f32x4(p[j]);
+            } else for (int j = lane; j < MEMCAP; j += WAVE) L.x[j] = pcm_in(pcm, bitdepth, pidx + (size_t)j * ps);
+        }
+        if (fastf) {
+            for (int idx = lane; idx < 120 * nf; idx += WAVE) {                          /* 120 x 16 bytes per frame */
+                const int f = idx / 120, j = idx - 120 * f;
+                *(float4*)&L.x[MEMCAP + N * f + 4 * j] = pcm_f32x4(((const float4*)((const float*)pcm + pf0 + (size_t)f * pfst))[j]);
+            }
+        } else {
+            for (int f = 0; f < nf; f++) {
+                const size_t o = pf0 + (size_t)f * pfst;
+                for (int i = lane; i < N; i += WAVE) L.x[MEMCAP + N * f + i] = pcm_in(pcm, bitdepth, o + (size_t)i * ps);
+            }
+        }
+    }
+#else
     /* ---- PCM of the run and the MDCT memory in front of it -> x ---- */
     {
         const size_t f0 = ((size_t)strm * T + t0) * channels + ch;
@@ -132,6 +167,7 @@ lc3_enc_front4_kernel(const lc3d_plan* __restrict__ P, const lc3d_chan* __restri
             }
         }
     }
+#endif
     LSYNC();
     if (t0 + nf == T) for (int i = lane; i < MEMCAP; i += WAVE) xnext[(size_t)cs * MEMCAP + i] = L.x[N * nf + i];     /* the MDCT memory behind the call's last frame */
     float* r = rec + ((size_t)cs * RT + r0 + t0) * FR_WORDS;

@@ -60,7 +60,12 @@ __device__ __forceinline__ void fm_stage(const uint8_t* __restrict__ map, const 
 }
 
 extern "C" __global__ void __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(4, 4)))
-lc3_enc_frontm_kernel(const lc3d_plan* __restrict__ P, const lc3d_chan* __restrict__ chans, const float* __restrict__ state, const void* __restrict__ pcm, int bitdepth,
+#ifdef LC3_PCM_FMT               /* the object of the PCM formats beyond 16 / 24 / 32 (float samples, the interleaved and the channel-major layout): the PCM load differs, nothing else */
+lc3_enc_frontm_kernel_fmt(
+#else
+lc3_enc_frontm_kernel(
+#endif
+                      const lc3d_plan* __restrict__ P, const lc3d_chan* __restrict__ chans, const float* __restrict__ state, const void* __restrict__ pcm, int bitdepth,
                       int T, int tb, int nt /* frames tb ... tb + nt - 1 of the call's T */, int F /* frames per wave: F x N <= FM_CAP, F <= 8 */, int ncs,
                       float* __restrict__ spec, int srow, int RT, int r0, float* __restrict__ rec, float* __restrict__ xnext, const float* __restrict__ xprev, int xprev_stride)
 {
@@ -74,8 +79,34 @@ lc3_enc_frontm_kernel(const lc3d_plan* __restrict__ P, const lc3d_chan* __restri
     LSYNC();
     const int N = PI(N), h = N >> 1, la = PI(la), ml = N - la, channels = PI(channels), fs = PI(fs);
     const int strm = cs / channels, ch = cs - strm * channels;
+#ifndef LC3_PCM_FMT
     const float sc = bitdepth == 24 ? 256.0f : 65536.0f;
     const size_t f0 = ((size_t)strm * T + t0) * channels + ch;
+#endif
+#ifdef LC3_PCM_FMT
+    /* ---- the MDCT memory in front of the run (right-aligned below x[MEMCAP]) and the run's PCM -> x: by the format word - the run's first element, the step to the
+     * next sample and to the channel's next frame; float samples that follow each other take 16 bytes per lane like the 16-bit ones of the kernel without the suffix ---- */
+    const int ps = lc3d_pcm_stride(bitdepth, channels);
+    const size_t pf0 = lc3d_pcm_frame(bitdepth, channels, T, N, strm, t0, ch), pfst = lc3d_pcm_fstep(bitdepth, channels, N);
+    if (t0 == 0) { for (int i = lane; i < MEMCAP; i += WAVE) L.x[i] = xprev[(size_t)cs * xprev_stride + i]; }
+    else {
+        const size_t pidx = pf0 - pfst + (size_t)(N - ml) * ps;
+        for (int j = lane; j < ml; j += WAVE) L.x[MEMCAP - ml + j] = pcm_in(pcm, bitdepth, pidx + (size_t)j * ps);
+    }
+    if (pcm_f32_wide(pcm, bitdepth, pf0, N) && ((pfst * 4) & 15) == 0) {
+        const int per = N >> 2, ntask = nf * per;                 /* 16 bytes per lane */
+        const float rp = 1.0f / (float)per;
+        for (int tk = lane; tk < ntask; tk += WAVE) {
+            const int f = (int)(((float)tk + 0.5f) * rp), j = tk - f * per;
+            *(float4*)&L.x[MEMCAP + N * f + 4 * j] = pcm_f32x4(((const float4*)((const float*)pcm + pf0 + (size_t)f * pfst))[j]);
+        }
+    } else {
+        for (int f = 0; f < nf; f++) {
+            const size_t o = pf0 + (size_t)f * pfst;
+            for (int i = lane; i < N; i += WAVE) L.x[MEMCAP + N * f + i] = pcm_in(pcm, bitdepth, o + (size_t)i * ps);
+        }
+    }
+#else
     /* ---- the MDCT memory in front of the run (right-aligned below x[MEMCAP]) and the run's PCM -> x ---- */
     if (t0 == 0) { for (int i = lane; i < MEMCAP; i += WAVE) L.x[i] = xprev[(size_t)cs * xprev_stride + i]; }
     else {
@@ -100,6 +131,7 @@ lc3_enc_frontm_kernel(const lc3d_plan* __restrict__ P, const lc3d_chan* __restri
                 L.x[MEMCAP + N * f + i] = bitdepth == 16 ? (float)((const int16_t*)pcm)[o + i] : (float)((const int32_t*)pcm)[o + i] / sc;
         }
     }
+#endif
     LSYNC();
     if (t0 + nf == T) for (int i = lane; i < MEMCAP; i += WAVE) xnext[(size_t)cs * MEMCAP + i] = L.x[N * nf + i];     /* the MDCT memory behind the call's last frame */
     float* r = rec + ((size_t)cs * RT + r0 + t0) * FR_WORDS;

@@ -32,86 +32,12 @@ __device__ const uint8_t lc3t_rs48_map[128] = {
     12, 28, 36, 48, 52, 84, 100, 116, 25, 41, 57, 61, 85, 93, 109, 125, 18, 26, 30, 54, 90, 98, 106, 122, 3, 19, 27, 51, 55, 67, 83, 111, 20, 44, 60, 72, 76, 88, 96, 108, 13, 33, 49, 53, 69, 73, 81, 101, 6, 10, 34, 38, 46, 58, 62, 114, 15, 35, 39, 43, 59, 91, 99, 119,
     0, 16, 24, 40, 56, 68, 80, 112, 9, 21, 45, 65, 77, 105, 113, 121, 22, 42, 66, 70, 78, 86, 118, 126, 23, 31, 47, 63, 71, 115, 123, 127, 4, 8, 32, 64, 92, 104, 120, 124, 1, 5, 17, 29, 37, 89, 97, 117, 2, 14, 50, 74, 82, 94, 102, 110, 7, 11, 75, 79, 87, 95, 103, 107};
 
-extern "C" __global__ void __launch_bounds__(WAVE)
-lc3_enc_resample_kernel(const lc3d_plan* __restrict__ P, const float* __restrict__ state, int state_words, int memcap, const void* __restrict__ pcm, int bitdepth,
-                        int T, int tb, int nt, int ncs, float* __restrict__ d12 /* [cs][T][128] */,
-                        const float* __restrict__ xprev /* the MDCT / resampler memory before frame 0 (slot of memcap words per channel-stream) */, int xprev_stride)
-{
-    __shared__ PreLds L;
-    const int lane = threadIdx.x;
-    const int runs = (nt + PRE_FPW - 1) / PRE_FPW;
-    const int cs = blockIdx.x / runs, t0 = tb + (blockIdx.x % runs) * PRE_FPW, t1 = imin(tb + nt, t0 + PRE_FPW);
-    if (cs >= ncs) return;
-    if (lane < LC3D_PLAN_HEAD_WORDS) L.pc[lane] = ((const int*)P)[lane];
-    for (int i = lane; i < 240; i += WAVE) L.taps[i] = P->rs_taps[i];
-    LSYNC();
-    const int mlen = PI(rs_mem_in_len), stride = PI(rs_stride), n12 = PI(n12), N = PI(N), channels = PI(channels);
-    const float sf = PF(rs_scale);
-    const int strm = cs / channels, ch = cs - strm * channels;
-    const int Tt = 240 / stride;
-    int n0 = lane, n1 = lane + 64;                  /* the two outputs of this lane (same filter phase: 15 x 64 is a multiple of every stride) */
-    if (stride == 4 && n12 == 128) { n0 = lc3t_rs48_map[lane]; n1 = lc3t_rs48_map[64 + lane]; }
-    const int i0 = 15 * n0, i1 = 15 * n1, r = i0 % stride, start = r ? stride - r : 0;
-    const float* tp = &L.taps[start * Tt];
-    const bool on0 = n0 < n12, on1 = n1 < n12;
-    float* xs = L.xs;
-    /* the PCM of a frame (16 bytes per lane when the layout allows) is requested one frame ahead: the wave has nothing else to hide the round trip with */
-    const bool fast16 = bitdepth == 16 && (N & 7) == 0 && N <= 8 * WAVE && ((((size_t)pcm) + (((size_t)strm * T) * channels + ch) * N * 2) & 15) == 0 && ((N * 2 * channels) & 15) == 0;
-    uint4 nv = make_uint4(0, 0, 0, 0);
-    if (fast16 && t0 < t1 && lane < (N >> 3)) nv = ((const uint4*)((const int16_t*)pcm + (((size_t)strm * T + t0) * channels + ch) * N))[lane];
-    for (int t = t0; t < t1; t++) {
-        const size_t fidx = ((size_t)strm * T + t) * channels + ch;
-        /* the previous frame's last mlen samples: from the PCM of this launch, or from the stream's MDCT memory for its first frame */
-        if (t > t0 && fast16) {
-            for (int j = lane; j < mlen; j += WAVE) xs[j] = xs[N + j];          /* still in LDS: the tail of the frame before */
-        } else {
-            for (int j = lane; j < mlen; j += WAVE) {
-                float v;
-                if (t > 0) v = pre_pcm(pcm, bitdepth, (fidx - channels) * N + (N - mlen + j));
-                else v = xprev[(size_t)cs * xprev_stride + (memcap - mlen + j)];
-                xs[j] = v * sf;
-            }
-        }
-        if (fast16) {
-            LSYNC();
-            if (lane < (N >> 3)) {
-                const uint4 v = nv;
-                float* d = &xs[mlen + 8 * lane];
-                d[0] = (float)(int16_t)(v.x & 0xffff) * sf; d[1] = (float)(int16_t)(v.x >> 16) * sf;
-                d[2] = (float)(int16_t)(v.y & 0xffff) * sf; d[3] = (float)(int16_t)(v.y >> 16) * sf;
-                d[4] = (float)(int16_t)(v.z & 0xffff) * sf; d[5] = (float)(int16_t)(v.z >> 16) * sf;
-                d[6] = (float)(int16_t)(v.w & 0xffff) * sf; d[7] = (float)(int16_t)(v.w >> 16) * sf;
-            }
-            if (t + 1 < t1 && lane < (N >> 3)) nv = ((const uint4*)((const int16_t*)pcm + (fidx + channels) * N))[lane];
-        } else if (bitdepth == 16 && (N & 7) == 0 && ((((size_t)pcm) + fidx * N * 2) & 15) == 0) {      /* 16 bytes per lane */
-            const uint4* p = (const uint4*)((const int16_t*)pcm + fidx * N);
-            for (int i = lane; i < (N >> 3); i += WAVE) {
-                const uint4 v = p[i];
-                float* d = &xs[mlen + 8 * i];
-                d[0] = (float)(int16_t)(v.x & 0xffff) * sf; d[1] = (float)(int16_t)(v.x >> 16) * sf;
-                d[2] = (float)(int16_t)(v.y & 0xffff) * sf; d[3] = (float)(int16_t)(v.y >> 16) * sf;
-                d[4] = (float)(int16_t)(v.z & 0xffff) * sf; d[5] = (float)(int16_t)(v.z >> 16) * sf;
-                d[6] = (float)(int16_t)(v.w & 0xffff) * sf; d[7] = (float)(int16_t)(v.w >> 16) * sf;
-            }
-        } else for (int j = lane; j < N; j += WAVE) xs[mlen + j] = pre_pcm(pcm, bitdepth, fidx * N + j) * sf;
-        LSYNC();
-        /* polyphase FIR, R/resamp12k8.c:48-57: the taps of a lane's phase 10 at a time, both outputs of the lane share them */
-        const float* b0 = on0 ? xs + (i0 + start) / stride : xs;
-        const float* b1 = on1 ? xs + (i1 + start) / stride : xs;
-        float m0 = 0, m1 = 0;
-        for (int tb = 0; tb < Tt; tb += 10) {
-            float tap[10];
-#pragma unroll
-            for (int m = 0; m < 10; m++) tap[m] = tp[tb + m];
-#pragma unroll
-            for (int m = 0; m < 10; m++) { m0 += b0[tb + m] * tap[m]; m1 += b1[tb + m] * tap[m]; }
-        }
-        float* o = d12 + ((size_t)cs * T + t) * 128;
-        if (on0) o[n0] = m0;
-        if (on1) o[n1] = m1;
-        LSYNC();
-    }
-}
+#ifdef LC3_PCM_FMT                 /* the object of the PCM formats beyond 16 / 24 / 32 holds the two resamplers of those formats alone */
+#define RESAMPLE_PCM_FMT 1
+#else
+#define RESAMPLE_PCM_FMT 0
+#endif
+#include "lc3_enc_resample.inc"    /* lc3_enc_resample_kernel, or lc3_enc_resample_fmt_kernel */
 
 /* ---- 48 kHz / 10 ms (N = 480, one output per 15/4 input samples, 60 taps per output): four outputs per lane --------------------------------------
  * The kernel above reads 2 x 60 words of LDS per output (taps and samples: 61 KB per frame) and is bound by exactly that: 486 LDS-array cycles per
@@ -136,6 +62,82 @@ __device__ __forceinline__ void pre48_put(float* __restrict__ d, const uint4 v, 
     ((float4*)d)[0] = a; ((float4*)d)[1] = b;
 }
 
+#ifdef LC3_PCM_FMT
+/* lc3_enc_resample48_kernel (below) for float samples that follow each other (LC3PLUS_PCM_FLOAT32 in the default or the channel-major layout of the format word
+ * fmt): its tap and LDS scheme unchanged, only the load and convert step differs.  A frame is 120 pieces of 16 bytes instead of 60: a lane loads piece lane and
+ * piece lane + 60 of both frames of its pair and writes each to LDS as one float4 - consecutive lanes, consecutive quad-words. */
+__device__ __forceinline__ void pre48_putf(float* __restrict__ d, const float4 v, const float sf)
+{
+    const float4 c = pcm_f32x4(v);
+    *(float4*)d = make_float4(c.x * sf, c.y * sf, c.z * sf, c.w * sf);
+}
+
+extern "C" __global__ void __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(3, 3)))
+lc3_enc_resample48f_kernel(const lc3d_plan* __restrict__ P, const float* __restrict__ pcm /* 16-byte aligned */, int fmt, int channels, int memcap,
+                           int T, int tb, int nt, int ncs, float* __restrict__ d12 /* [cs][T][128] */, const float* __restrict__ xprev, int xprev_stride)
+{
+    __shared__ Pre48Lds L;
+    const int lane = threadIdx.x;
+    const int runs = (nt + PRE_FPW - 1) / PRE_FPW;
+    const int cs = blockIdx.x / runs, t0 = tb + (blockIdx.x % runs) * PRE_FPW, t1 = imin(tb + nt, t0 + PRE_FPW);
+    if (cs >= ncs) return;
+    const int code = lc3t_rs48_lane4[lane], f = code >> 5, b = (code >> 2) & 7, p = code & 3;
+    const float sf = P->rs_scale;
+    const int strm = cs / channels, ch = cs - strm * channels;
+    float tap[60];
+#pragma unroll
+    for (int m = 0; m < 60; m++) tap[m] = P->rs_taps[p * 60 + m];
+    float* xs = L.xs;
+    const float* fr0 = pcm + lc3d_pcm_frame(fmt, channels, T, 480, strm, t0, ch);          /* frame t0 of this channel-stream; the next one is fstep further */
+    const size_t fstep = lc3d_pcm_fstep(fmt, channels, 480);
+    float4 fa0 = make_float4(0, 0, 0, 0), fa1 = fa0, fb0 = fa0, fb1 = fa0;
+    if (lane < 60) {
+        fa0 = ((const float4*)fr0)[lane]; fa1 = ((const float4*)fr0)[lane + 60];
+        if (t0 + 1 < t1) { fb0 = ((const float4*)(fr0 + fstep))[lane]; fb1 = ((const float4*)(fr0 + fstep))[lane + 60]; }
+    }
+    if (lane < 60) {   /* the 60 samples in front of frame t0: from the PCM of this call, or the stream's MDCT memory for its first frame */
+        float v;
+        if (t0 > 0) v = pcm_f32((fr0 - fstep)[420 + lane]);
+        else v = xprev[(size_t)cs * xprev_stride + (memcap - 60 + lane)];
+        xs[lane] = v * sf;
+    }
+    const float4* xb = (const float4*)(xs + 480 * f + 60 * b + 4 * p);
+    float* o = d12 + ((size_t)cs * T + t0 + f) * 128 + 16 * b + p;
+    for (int t = t0; t < t1; t += 2) {
+        float4 tl = make_float4(0, 0, 0, 0);
+        if (t > t0 && lane < 15) tl = ((const float4*)xs)[240 + lane];       /* the last 60 samples of the pair before */
+        LSYNC();
+        if (t > t0 && lane < 15) ((float4*)xs)[lane] = tl;
+        if (lane < 60) {
+            pre48_putf(xs + 60 + 4 * lane, fa0, sf); pre48_putf(xs + 300 + 4 * lane, fa1, sf); pre48_putf(xs + 540 + 4 * lane, fb0, sf); pre48_putf(xs + 780 + 4 * lane, fb1, sf);
+            const float* fn = fr0 + (size_t)(t + 2 - t0) * fstep;
+            if (t + 2 < t1) { fa0 = ((const float4*)fn)[lane]; fa1 = ((const float4*)fn)[lane + 60]; }
+            if (t + 3 < t1) { fb0 = ((const float4*)(fn + fstep))[lane]; fb1 = ((const float4*)(fn + fstep))[lane + 60]; }
+        }
+        LSYNC();
+        float acc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+        for (int c = 0; c < 27; c++) {
+            const float4 q = xb[c];
+            const float xv[4] = {q.x, q.y, q.z, q.w};
+#pragma unroll
+            for (int e = 0; e < 4; e++) {
+                const int u = 4 * c + e;
+#pragma unroll
+                for (int k = 0; k < 4; k++) {
+                    const int m = u - 15 * k;
+                    if (m >= 0 && m < 60) acc[k] += xv[e] * tap[m];
+                }
+            }
+        }
+        if (f == 0 || t + 1 < t1) {
+#pragma unroll
+            for (int k = 0; k < 4; k++) o[4 * k] = acc[k];
+        }
+        o += 256;
+    }
+}
+#else
 extern "C" __global__ void __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(3, 3)))
 lc3_enc_resample48_kernel(const lc3d_plan* __restrict__ P, const int16_t* __restrict__ pcm /* 16-byte aligned */, int channels, int memcap,
                           int T, int tb, int nt, int ncs, float* __restrict__ d12 /* [cs][T][128] */,
@@ -403,3 +405,4 @@ lc3_enc_hp50_kernel(const lc3d_plan* __restrict__ P, float* __restrict__ state, 
     sc[F_HP0] = (float)u11; sc[F_HP1] = (float)u21;
 }
 #endif
+#endif /* !LC3_PCM_FMT */

@@ -511,11 +511,27 @@ LC3_Error lc3plus_enc_batch_set_bandwidth(lc3plus_batch* b, int stream, int band
     return LC3_OK;
 }
 
+/* The PCM format word of every batch call that takes PCM (include/lc3plus_batch.h: LC3PLUS_PCM_*; the arithmetic is lc3_plan.h's, shared with the kernels):
+ * 16, 24, 32 or LC3PLUS_PCM_FLOAT32, alone or with one of the two layout bits. */
+typedef char pcm_format_words_agree[(LC3PLUS_PCM_FLOAT32 == LC3D_PCM_FLOAT32 && LC3PLUS_PCM_INTERLEAVED == LC3D_PCM_INTERLEAVED &&
+                                    LC3PLUS_PCM_CHANNEL_MAJOR == LC3D_PCM_CHANNEL_MAJOR) ? 1 : -1];
+static int pcm_format_ok(int format) { return lc3d_pcm_format_ok(format); }
+static int pcm_format_plain(int format) { return format == 16 || format == 24 || format == 32; }
+/* Host-only hooks: the format check and the address rule without a GPU (tests/test_pcm_format_cpu.py). */
+LC3_Error lc3plus_pcm_format_check(int format) { return pcm_format_ok(format) ? LC3_OK : LC3_ERROR; }
+int64_t lc3plus_pcm_offset(int format, int channels, int n_frames, int samples, int stream, int frame, int channel, int sample)
+{
+    if (!pcm_format_ok(format) || channels <= 0 || n_frames <= 0 || samples <= 0 || stream < 0 || frame < 0 || frame >= n_frames || channel < 0 ||
+        channel >= channels || sample < 0 || sample >= samples) return -1;
+    return (int64_t)(lc3d_pcm_frame(format, channels, n_frames, samples, stream, frame, channel) + (size_t)sample * lc3d_pcm_stride(format, channels));
+}
+
 static LC3_Error batch_encode(lc3plus_batch* b, const void* pcm, int pcm_on_device, int bitdepth, int n_frames, void* out, int out_stride,
                               int out_on_device, void* hip_stream, int sync, void* trace)
 {
     if (!b || !pcm || !out) return LC3_NULL_ERROR;
-    if (bitdepth != 16 && bitdepth != 24 && bitdepth != 32) return LC3_ERROR;
+    if (!pcm_format_ok(bitdepth)) return LC3_ERROR;
+    if (trace && !pcm_format_plain(bitdepth)) return LC3_ERROR;      /* the traced calls take the integer formats in the default layout only */
     if (n_frames <= 0 || out_stride < enc_stride_bound(b)) return LC3_ERROR;
     if (lc3hip_encode(b->dev, pcm, pcm_on_device, bitdepth, n_frames, out, out_stride, out_on_device, hip_stream, sync, trace, NULL, NULL)) return LC3_ERROR;
     /* one-shot attack-state reset requests have been consumed by this launch (a stale copy has none: the device-rate calls consume them, and nothing of it
@@ -537,7 +553,8 @@ static LC3_Error batch_encode_bitrates(lc3plus_batch* b, const void* pcm, int pc
                                        int out_stride, int out_on_device, int* num_bytes, void* hip_stream, int sync, void* trace)
 {
     if (!b || !pcm || !out || !bitrates) return LC3_NULL_ERROR;
-    if (bitdepth != 16 && bitdepth != 24 && bitdepth != 32) return LC3_ERROR;
+    if (!pcm_format_ok(bitdepth)) return LC3_ERROR;
+    if (trace && !pcm_format_plain(bitdepth)) return LC3_ERROR;
     if (n_frames <= 0) return LC3_ERROR;
     if (enc_refresh(b)) return LC3_ERROR;
     const size_t n = (size_t)b->n_streams * n_frames;
@@ -615,7 +632,7 @@ static LC3_Error batch_encode_bandwidths(lc3plus_batch* b, const void* pcm, int 
     const size_t n = (size_t)b->n_streams * (n_frames > 0 ? n_frames : 0);
     if (bandwidths) for (size_t i = 0; i < n; i++) if (!bw_value_ok(bandwidths[i], b->g.dms)) return LC3_ERROR;
     if (!pcm || !out || !bandwidths) return LC3_NULL_ERROR;
-    if (bitdepth != 16 && bitdepth != 24 && bitdepth != 32) return LC3_ERROR;
+    if (!pcm_format_ok(bitdepth)) return LC3_ERROR;
     if (n_frames <= 0) return LC3_ERROR;
     if (bitrates) {
         if (b->fsz_cap < n) {
@@ -745,7 +762,7 @@ LC3_Error lc3plus_enc_batch_encode_rates_device(lc3plus_batch* b, const void* pc
                                                 int n_frames, void* out, int out_stride, int32_t* num_bytes, uint8_t* flags, void* hip_stream, int sync)
 {
     if (!b || !pcm || !out || (!bitrates && !bandwidths)) return LC3_NULL_ERROR;
-    if (bitdepth != 16 && bitdepth != 24 && bitdepth != 32) return LC3_ERROR;
+    if (!pcm_format_ok(bitdepth)) return LC3_ERROR;
     if (n_frames <= 0 || out_stride < enc_stride_bound(b)) return LC3_ERROR;
     if (bandwidths && b->g.hrmode) return LC3_HRMODE_BW_ERROR;
     if (bandwidths && b->bw_unsafe) {           /* a value in force with a cut-off line below 1: refused as encode_bandwidths refuses it (enc_plan_bandwidths) */
@@ -810,7 +827,7 @@ LC3_Error lc3plus_enc_batch_encode_packed(lc3plus_batch* b, const void* pcm, int
                                           void* hip_stream, int sync)
 {
     if (!b || !pcm || !out) return LC3_NULL_ERROR;
-    if (bitdepth != 16 && bitdepth != 24 && bitdepth != 32) return LC3_ERROR;
+    if (!pcm_format_ok(bitdepth)) return LC3_ERROR;
     if (n_frames <= 0 || (order != LC3D_PACK_STREAM_MAJOR && order != LC3D_PACK_FRAME_MAJOR) || out_capacity < 0) return LC3_ERROR;
     if (bandwidths && b->g.hrmode) return LC3_HRMODE_BW_ERROR;
     if (bandwidths && b->bw_unsafe) {           /* as encode_rates_device */
@@ -1374,7 +1391,8 @@ static LC3_Error dec_batch_decode(lc3plus_dec_batch* b, const void* frames, int 
                                   void* pcm, int pcm_on_device, int bps, uint8_t* status, void* hip_stream, int sync, void* traces)
 {
     if (!b || !frames || !pcm) return LC3_NULL_ERROR;
-    if (bps != 16 && bps != 24 && bps != 32) return LC3_ERROR;
+    if (!pcm_format_ok(bps)) return LC3_ERROR;
+    if (traces && !pcm_format_plain(bps)) return LC3_ERROR;          /* the traced call writes the integer formats in the default layout only */
     if (n_frames <= 0) return LC3_ERROR;
     if (dec_refresh(b)) return LC3_ERROR;
     for (int i = 0; i < b->n_streams; i++) if (lc3plus_dec_batch_num_bytes(b, i) > in_stride) return LC3_NUMBYTES_ERROR;
@@ -1385,7 +1403,7 @@ LC3_Error lc3plus_dec_batch_decode_sizes(lc3plus_dec_batch* b, const void* frame
                                          const uint8_t* bfi, int n_frames, void* pcm, int pcm_on_device, int bps, uint8_t* status, void* hip_stream, int sync)
 {
     if (!b || !frames || !pcm || !num_bytes) return LC3_NULL_ERROR;
-    if (bps != 16 && bps != 24 && bps != 32) return LC3_ERROR;
+    if (!pcm_format_ok(bps)) return LC3_ERROR;
     if (n_frames <= 0) return LC3_ERROR;
     if (dec_refresh(b)) return LC3_ERROR;
     const size_t n = (size_t)b->n_streams * n_frames;
@@ -1425,7 +1443,7 @@ LC3_Error lc3plus_dec_batch_decode_sizes_device(lc3plus_dec_batch* b, const void
                                                 int n_frames, void* pcm, int bps, uint8_t* status, void* hip_stream, int sync)
 {
     if (!b || !frames || !pcm || !num_bytes) return LC3_NULL_ERROR;
-    if (bps != 16 && bps != 24 && bps != 32) return LC3_ERROR;
+    if (!pcm_format_ok(bps)) return LC3_ERROR;
     if (n_frames <= 0 || in_stride <= 0) return LC3_ERROR;
     /* the sizes, the carry and the configuration after the call are on the device only: the host mirror is read back by the next host-side reader */
     if (lc3hip_dec_decode_dsizes(b->dev, frames, in_stride, num_bytes, bfi, n_frames, pcm, bps, status, hip_stream, sync)) return LC3_ERROR;
@@ -1436,7 +1454,7 @@ LC3_Error lc3plus_dec_batch_decode_packed(lc3plus_dec_batch* b, const void* fram
                                           int max_frame_bytes, const uint8_t* bfi, int n_frames, void* pcm, int bps, uint8_t* status, void* hip_stream, int sync)
 {
     if (!b || !frames || !pcm || !num_bytes || !offsets) return LC3_NULL_ERROR;
-    if (bps != 16 && bps != 24 && bps != 32) return LC3_ERROR;
+    if (!pcm_format_ok(bps)) return LC3_ERROR;
     if (n_frames <= 0 || max_frame_bytes <= 0 || frames_capacity < 0) return LC3_ERROR;
     if (lc3hip_dec_decode_packed(b->dev, frames, (long long)frames_capacity, (const long long*)offsets, num_bytes, max_frame_bytes, bfi, n_frames, pcm, bps,
                                  status, hip_stream, sync)) return LC3_ERROR;

@@ -99,6 +99,23 @@
 #define SUB(id) do { } while (0)
 #endif
 
+/* The encoder's input conversion (R/enc_lc3_fl.c:30-42) for the PCM format word (lc3_plan.h: lc3d_pcm_*).  A float sample is x * 32768 with no rounding and no
+ * clipping, like the integers; a NaN or an infinity is taken as 0 so that one bad sample cannot stay in a stream's filter memories for ever. */
+__device__ __forceinline__ float pcm_f32(float x) { return (__float_as_uint(x) & 0x7f800000u) == 0x7f800000u ? 0.0f : x * 32768.0f; }
+__device__ __forceinline__ float4 pcm_f32x4(const float4 v) { return make_float4(pcm_f32(v.x), pcm_f32(v.y), pcm_f32(v.z), pcm_f32(v.w)); }
+__device__ __forceinline__ float pcm_in(const void* __restrict__ pcm, int fmt, size_t idx)
+{
+    const int ty = fmt & LC3D_PCM_TYPE_MASK;
+    if (ty == 16) return (float)((const int16_t*)pcm)[idx];
+    if (ty == LC3D_PCM_FLOAT32) return pcm_f32(((const float*)pcm)[idx]);
+    return (float)((const int32_t*)pcm)[idx] / (ty == 24 ? 256.0f : 65536.0f);
+}
+/* float samples one after the other from element o on (default and channel-major layouts), n of them a multiple of four, 16-byte aligned: 16 bytes per lane */
+__device__ __forceinline__ bool pcm_f32_wide(const void* __restrict__ pcm, int fmt, size_t o, int n)
+{
+    return (fmt & (LC3D_PCM_TYPE_MASK | LC3D_PCM_INTERLEAVED)) == LC3D_PCM_FLOAT32 && (n & 3) == 0 && ((((size_t)pcm) + o * 4) & 15) == 0;
+}
+
 /* ------------------------------------------------------------------------------------------------ */
 /* LDS slice of one wave (~12.8 KB -> 12 waves per CU)                                                */
 /* ------------------------------------------------------------------------------------------------ */
@@ -2673,300 +2690,36 @@ template <class LdsT> STAGE void st_bitstream(const lc3d_plan* __restrict__ P, c
  * -DLC3_ENC_VBW: per-frame bandwidths (lc3plus_enc_batch_encode_bandwidths), kernel lc3_encode_kernel_vbw (_var_vbw together with -DLC3_ENC_VAR), standard
  * layout only, in objects of their own.  The bandwidth controller takes the frame's bandwidth in Hz from bwf[stream][dt0 + t] (the host has resolved every
  * frame to the value in force, 0 = off) instead of the stream's configuration words, with the formulas of set_bandwidth (lc3d_bw_cut_bin, lc3d_bw_index). */
-extern "C" __global__ void __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(KERNEL_WAVES, KERNEL_WAVES)))
-KERNEL_FN(const lc3d_plan* __restrict__ P, const lc3d_chan* __restrict__ chans, float* __restrict__ state,
-                  const void* __restrict__ pcm, int bitdepth, int T, uint8_t* __restrict__ out, int out_stride, int ncs,
-                  lc3d_trace* __restrict__ trace, int* __restrict__ dump /* [cs][T][dstride] hand-over to lc3_enc_pack_kernel, or null: write the bytes here */, int dstride,
-                  const float* __restrict__ y12 /* [cs][T][128] HP-filtered 12.8 kHz signal from the pre-kernels, or null: resample here */,
-                  uint8_t* __restrict__ status /* [cs][dT] LC3D_ENC_ST_* bits (zeroed by the host), or null */,
-                  int dT, int dt0 /* the hand-over and the status rows hold dT frames per channel-stream; this launch's frame t is their frame dt0 + t */,
-                  const float* __restrict__ spec /* [cs][T][N] MDCT spectra from lc3_enc_front_kernel, or null: transform here */,
-                  const float* __restrict__ frec /* [cs][T][FR_WORDS] with the SNS result of lc3_enc_snsvq_kernel */,
-                  const float* __restrict__ xnext /* [cs][MEMCAP] MDCT memory after the last frame */
-#ifdef LC3_ENC_VAR
-                  , const uint16_t* __restrict__ fsz /* [stream][dT] bytes of each stream-frame */, const lc3d_chan* __restrict__ etab /* per channel byte count */
-#endif
-#ifdef LC3_ENC_VBW
-                  , const uint16_t* __restrict__ bwf /* [stream][dT] bandwidth in force for each stream-frame, Hz */
-#endif
-#ifdef LC3_ENC_PACKED
-                  , const long long* __restrict__ poff /* [stream][dT] byte offset of each stream-frame in out, -1: not written */
-#endif
-                  )
-{
-    __shared__ WaveLds L;
-    const int lane = threadIdx.x;
-    const int cs = blockIdx.x;
-    if (cs >= ncs) return;
-    if (lane < LC3D_PLAN_HEAD_WORDS) L.pc[lane] = ((const int*)P)[lane];
-    if (lane < 14) L.cc[lane] = ((const int*)&chans[cs])[lane];
-    LSYNC();
-    const lc3d_chan* __restrict__ C = &chans[cs];
-    const int N = PI(N), channels = PI(channels), ml = N - PI(la);
-    const int strm = cs / channels, ch = cs - strm * channels;
-
-    /* ---- load cross-frame state ---- */
-    float* stp = state + (size_t)cs * LC3D_STATE_WORDS(MEMCAP);
-    for (int i = lane; i < MEMCAP; i += WAVE) L.xbuf[i] = stp[LC3D_ST_XPREV + i];
-    for (int i = lane; i < 384; i += WAVE) L.h12[i] = stp[LC3D_ST_H12(MEMCAP) + i];
-    for (int i = lane; i < 194; i += WAVE) L.h6[i] = stp[LC3D_ST_H6(MEMCAP) + i];
-    if (lane < 12) L.fsc[lane] = stp[LC3D_ST_SCAL(MEMCAP) + lane];
-    if (lane < 16) L.isc[lane] = ((const int*)stp)[LC3D_ST_SCAL(MEMCAP) + 16 + lane];
-    LSYNC();
-    if (CI(reset_attack) && lane == 0) { L.fsc[F_ATT_M0] = 0; L.fsc[F_ATT_M1] = 0; L.fsc[F_ATT_ACC] = 0; L.isc[I_ATT_POS] = 0; L.isc[I_ATT_FLAG] = 0; }
-    LSYNC();
-#ifdef LC3_STAGE_TIMING
-    if (lane < NSTAGE) L.tacc[lane] = 0;
-    LSYNC();
-    long long tlast = clock64();
-#endif
-
-    /* The next frame's PCM (16 bytes per lane when the layout allows) and 12.8 kHz samples are requested one frame ahead and wait
-     * in registers: a wave has nothing else to hide a global-memory round trip with at the top of a frame. */
-    const bool fast16 = bitdepth == 16 && (N & 7) == 0 && N <= 8 * WAVE && ((((size_t)pcm) + (((size_t)strm * T) * channels + ch) * N * 2) & 15) == 0 && ((N * 2 * channels) & 15) == 0;
-    uint4 nv = make_uint4(0, 0, 0, 0); float ny0 = 0, ny1 = 0;
-    constexpr int SPK = (MAXN + WAVE - 1) / WAVE;
-    unsigned bob[4] = {0, 0, 0, 0};                  /* band of this lane's bins (lane + 64 k), one byte each: the table look-up of the SNS shaping, once per launch */
-#pragma unroll
-    for (int k = 0; k < SPK; k++) { const int j = lane + 64 * k; bob[k >> 2] |= (unsigned)(j < N ? P->band_of_bin[j] : 255) << (8 * (k & 3)); }
-    float sp[SPK]; float rq = 0; int ri = 0;
-#pragma unroll
-    for (int k = 0; k < SPK; k++) sp[k] = 0;
-#define SPEC_PREFETCH(t_) do { const float* sr_ = spec + ((size_t)cs * T + (t_)) * N; const float* fr_ = frec + ((size_t)cs * T + (t_)) * FR_WORDS; \
-        _Pragma("unroll") for (int k = 0; k < SPK; k++) sp[k] = lane + 64 * k < N ? sr_[lane + 64 * k] : 0.0f; \
-        if (lane < 16) rq = fr_[FR_SCFQ + lane]; \
-        if (lane < 8) ri = ((const int*)fr_)[FR_IDX + lane];   /* seven indices, then the bandwidth index */ } while (0)
-    if (spec && T > 0) SPEC_PREFETCH(0);
-    if (T > 0) {
-        if (fast16 && lane < (N >> 3)) nv = ((const uint4*)((const int16_t*)pcm + (((size_t)strm * T) * channels + ch) * N))[lane];
-        if (y12) { const float* yp = y12 + ((size_t)cs * T) * 128; ny0 = lane < PI(len12) ? yp[lane] : 0.0f; ny1 = lane + 64 < PI(len12) ? yp[lane + 64] : 0.0f; }
-    }
-    for (int t = 0; t < T; t++) {
-#ifdef LC3_STAGE_TIMING
-        lc3d_trace* tr = nullptr;
+#define LC3_FMT_CAT2(a) a##_fmt
+#define LC3_FMT_CAT(a) LC3_FMT_CAT2(a)
+/* -DLC3_PCM_FMT: the same kernel for the PCM formats beyond the reference's three (float samples, the interleaved and the channel-major layout), named with
+ * _fmt, once more in an object of its own per object above - with the front and the resampler kernel of those formats in the two plain ones - so that the
+ * objects of 16 / 24 / 32 stay as they are (a second kernel beside it in one object already changes how the stage functions are inlined into the first). */
+#ifdef LC3_PCM_FMT
+#define ENC_PCM_FMT 1
 #else
-        lc3d_trace* tr = trace ? &trace[(size_t)cs * T + t] : nullptr;
+#define ENC_PCM_FMT 0
 #endif
-#ifdef LC3_ENC_VAR
-        {                                                /* this frame's configuration (the words before out_off) and the channel's payload offset */
-            const int fb = fsz[(size_t)strm * dT + dt0 + t];
-            const int k = channels == 1 ? fb : ch ? fb >> 1 : (fb + 1) >> 1;
-            if (lane < 8) L.cc[lane] = ((const int*)&etab[k])[lane];
-            if (lane == 8) L.cc[lane] = ch ? (fb + 1) >> 1 : 0;
-            LSYNC();
-            if (!CI(attack_handling) && lane == 0) { L.fsc[F_ATT_M0] = 0; L.fsc[F_ATT_M1] = 0; L.fsc[F_ATT_ACC] = 0; L.isc[I_ATT_POS] = 0; L.isc[I_ATT_FLAG] = 0; }
-            LSYNC();
-        }
-#endif
-        /* ---- PCM in (R/enc_lc3_fl.c:30-42) ---- */
-        const size_t fidx = ((size_t)strm * T + t) * channels + ch;
-        /* the frame's spectrum and SNS record from the frame-parallel front were requested at the end of the previous frame: park them in
-         * LDS (the frame half of xbuf is free until the quantiser needs it) */
-        if (spec) {
-#pragma unroll
-            for (int k = 0; k < SPK; k++) if (lane + 64 * k < N) XCUR(L)[lane + 64 * k] = sp[k];
-            if (lane < 16) L.sm[SM_SCFQ + lane] = rq;
-            if (lane < 7) L.isc[I_SCF0 + lane] = ri;
-            if (lane == 7) L.isc[I_BW] = ri;
-        } else if (fast16) {
-            if (lane < (N >> 3)) {
-                const uint4 v = nv;
-                float* d = &XCUR(L)[8 * lane];
-                d[0] = (float)(int16_t)(v.x & 0xffff); d[1] = (float)(int16_t)(v.x >> 16);
-                d[2] = (float)(int16_t)(v.y & 0xffff); d[3] = (float)(int16_t)(v.y >> 16);
-                d[4] = (float)(int16_t)(v.z & 0xffff); d[5] = (float)(int16_t)(v.z >> 16);
-                d[6] = (float)(int16_t)(v.w & 0xffff); d[7] = (float)(int16_t)(v.w >> 16);
-            }
-            if (t + 1 < T && lane < (N >> 3)) nv = ((const uint4*)((const int16_t*)pcm + (fidx + channels) * N))[lane];
-        } else if (bitdepth == 16) {
-            const int16_t* p = (const int16_t*)pcm + fidx * N;
-            for (int i = lane; i < N; i += WAVE) XCUR(L)[i] = (float)p[i];
-        } else {
-            const int32_t* p = (const int32_t*)pcm + fidx * N;
-            const float sc = bitdepth == 24 ? 256.0f : 65536.0f;
-            for (int i = lane; i < N; i += WAVE) XCUR(L)[i] = (float)p[i] / sc;
-        }
-        LSYNC();
-        TICK(0);
-
-        if (y12) {                                       /* lc3_enc_resample_kernel + lc3_enc_hp50_kernel (lc3_enc_pre.inc) have done the work */
-            const int len12 = PI(len12);
-            const float y0 = ny0, y1 = ny1;
-            if (t + 1 < T) { const float* yp = y12 + ((size_t)cs * T + t + 1) * 128; ny0 = lane < len12 ? yp[lane] : 0.0f; ny1 = lane + 64 < len12 ? yp[lane + 64] : 0.0f; }
-            float keep[6];
-#pragma unroll
-            for (int k = 0; k < 6; k++) { const int i = lane + 64 * k; keep[k] = (i + len12 < 384) ? L.h12[i + len12] : 0.0f; }
-            LSYNC();
-#pragma unroll
-            for (int k = 0; k < 6; k++) { const int i = lane + 64 * k; if (i + len12 < 384) L.h12[i] = keep[k]; }
-            if (lane < len12) L.h12[384 - len12 + lane] = y0;
-            if (lane + 64 < len12) L.h12[384 - len12 + 64 + lane] = y1;
-            LSYNC();
-        } else st_resample(P, L, lane, nullptr);
-        TICK(2);
-        if (tr) for (int i = lane; i < PI(len12) + 1; i += WAVE) tr->s12k8[i] = L.h12[384 - PI(len12) - 24 + i];
-        st_olpa(P, L, lane);
-        TICK(3);
-        st_ltpf(P, C, L, lane);
-        TICK(4);
-        if (spec) {
-            TICK(5); TICK(1); TICK(6); TICK(7); TICK(8);
-        } else {
-        if (CI(attack_handling)) st_attack(P, L, lane);
-        TICK(5);
-        mdct_pre(P, L, lane);
-#ifdef LC3_BIG
-        if (PI(N) == 960) { mdct_dft480_cols(L, lane); mdct_dft480_rows(L, lane); } else
-#endif
-        if (PI(N) == 480) { mdct_dft240_cols(L, lane); mdct_dft240_rows(L, lane); }
-        else if (PI(N) == 120) mdct_dft60(P, L, lane);
-        else { if (PI(N) == 320) mdct_dft160_stage1(P, L, lane); else if (PI(N) == 160) mdct_dft80_stage1(P, L, lane); mdct_dft_pfa(P, L, lane); }
-        mdct_post(P, L, lane);
-        TICK(1);
-        if (tr) for (int i = lane; i < N; i += WAVE) tr->spec_mdct[i] = L.A[i];
-        st_energy_bw(P, L, lane);
-        TICK(6);
-        if (tr) { if (lane == 0) { tr->T0 = L.isc[I_T0]; tr->normcorr = L.fsc[F_NC]; tr->ltpf_param[0] = L.isc[I_LTPF0]; tr->ltpf_param[1] = L.isc[I_LTPF1];
-                                   tr->ltpf_param[2] = L.isc[I_LTPF2]; tr->ltpf_bits = L.isc[I_LTPF_BITS]; tr->attack = L.isc[I_ATT_FLAG]; }
-                  tr->ener[lane] = lane < PI(nbands) ? L.sm[SM_ENER + lane] : 0; }
-        LSYNC();
-        st_sns_scf(P, L, lane);
-        TICK(7);
-        if (tr && lane < 16) tr->scf[lane] = L.sm[SM_SCF + lane];
-        st_sns_vq(P, L, lane);
-        TICK(8);
-        }
-        st_sns_apply(P, L, lane, spec ? XCUR(L) : L.A, bob[0], bob[1], bob[2], bob[3]);
-        TICK(9);
-        if (tr) { if (lane < 16) tr->scf_q[lane] = L.sm[SM_SCFQ + lane]; if (lane < 7) tr->scf_idx[lane] = L.isc[I_SCF0 + lane];
-                  for (int i = lane; i < N; i += WAVE) tr->spec_shaped[i] = L.A[i]; }
-        int bw = uni(L.isc[I_BW]);
-#ifdef LC3_ENC_VBW
-        const int fbw = bwf[(size_t)strm * dT + dt0 + t];
-        if (fbw) {                                            /* R/cutoff_bandwidth.c:13-26 */
-            const int bin = lc3d_bw_cut_bin(fbw, PI(dms));
-            if (PI(ylen) > bin) {
-                if (lane < 4) { const float sc4[4] = {0.5f, 0.25f, 0.125f, 0.0625f}; L.A[bin - 1 + lane] = L.A[bin - 1 + lane] * sc4[lane]; }
-                for (int i = bin + 3 + lane; i < PI(ylen); i += WAVE) L.A[i] = 0;
-            }
-            bw = imin(bw, lc3d_bw_index(fbw));
-            if (lane == 0) L.isc[I_BW] = bw;
-        }
-#else
-        if (CI(bandwidth)) {                                  /* R/cutoff_bandwidth.c:13-26 */
-            const int bin = CI(bw_cut_bin);
-            if (PI(ylen) > bin) {
-                if (lane < 4) { const float sc4[4] = {0.5f, 0.25f, 0.125f, 0.0625f}; L.A[bin - 1 + lane] = L.A[bin - 1 + lane] * sc4[lane]; }
-                for (int i = bin + 3 + lane; i < PI(ylen); i += WAVE) L.A[i] = 0;
-            }
-            bw = imin(bw, CI(bw_index));
-            if (lane == 0) L.isc[I_BW] = bw;
-        }
-#endif
-        const int bw_bin = lc3t_bw_bins[PI(bw_cls) * 6 + bw];
-        if (lane < 16) L.isc[I_TNS_IDX0 + lane] = 0;
-        if (lane < 2) L.isc[I_TNS_ORD0 + lane] = 0;
-        LSYNC();
-        st_tns(P, L, lane, bw, bw_bin);
-        TICK(10);
-        const int tns_bits = uni(L.isc[I_TNS_BITS]);
-        if (tr) { if (lane == 0) { tr->bw_idx = bw; tr->tns_nfilt = L.isc[I_TNS_NF]; tr->tns_order[0] = L.isc[I_TNS_ORD0]; tr->tns_order[1] = L.isc[I_TNS_ORD1]; tr->tns_bits = tns_bits; }
-                  if (lane < 16) tr->tns_rc_idx[lane] = L.isc[I_TNS_IDX0 + lane];
-                  for (int i = lane; i < N; i += WAVE) tr->spec_tns[i] = L.A[i]; }
-        const int tbq = CI(target_bits_init) - (tns_bits + uni(L.isc[I_LTPF_BITS]));
-        st_gain_estimate(P, C, L, lane, tbq);
-        TICK(11);
-        if (tr && lane == 0) { tr->target_bits_quant = tbq; tr->gain0 = L.fsc[F_GAIN]; tr->gg_idx0 = L.isc[I_GG]; tr->gg_min = L.isc[I_GGMIN]; }
-        st_quantize(P, C, L, lane, -1, tbq);
-        TICK(12);
-        {
-            int gg = uni(L.isc[I_GG]), change; float gain = unif(L.fsc[F_GAIN]);
-            const int nbits0 = uni(L.isc[I_NBITS]);
-            if (tr && lane == 0) tr->nbits0 = nbits0;
-            gain_adjust(P, L, gg, uni(L.isc[I_GGMIN]), gain, tbq, nbits0, change);
-            LSYNC();
-            if (lane == 0) { L.isc[I_MEM_SPEC] = nbits0; L.isc[I_GG] = gg; L.fsc[F_GAIN] = gain; L.isc[I_CHANGE] = change; }
-            LSYNC();
-            if (change) st_quantize(P, C, L, lane, 0, tbq);
-        }
-        TICK(13);
-        st_noise_factor(P, L, lane, bw_bin);
-        TICK(14);
-        if (tr) { if (lane == 0) { tr->gain = L.fsc[F_GAIN]; tr->gg_idx = L.isc[I_GG]; tr->gain_change = L.isc[I_CHANGE]; tr->nbits = L.isc[I_NBITS]; tr->nbits2 = L.isc[I_NBITS2];
-                                   tr->lastnz = L.isc[I_LASTNZ]; tr->lsb_mode = L.isc[I_LSB]; tr->fac_ns = L.isc[I_FACNS]; }
-                  for (int i = lane; i < N; i += WAVE) tr->xq[i] = i < PI(ylen) ? XQ(L)[i] : 0; }
-        if (uni(L.isc[I_LSB]) == 0) st_residual(P, L, lane, tbq, uni(L.isc[I_NBITS2]));
-        else { for (int i = lane; i < 160; i += WAVE) ((uint32_t*)RESB(L))[i] = 0; if (lane == 0) L.isc[I_NRES] = 0; LSYNC(); }
-        TICK(15);
-        if (spec && t + 1 < T) SPEC_PREFETCH(t + 1);
-        if (dump) {
-            /* the bitstream of a frame depends on nothing but this: scalars, residual bits, quantised lines up to lastnz.  The
-             * serial writer runs one frame per lane in lc3_enc_pack_kernel. */
-            int* r = dump + ((size_t)cs * dT + dt0 + t) * dstride;
-            if (lane < 56) r[lane] = L.isc[lane];
-            const int lastnz = uni(L.isc[I_LASTNZ]), nresw = uni(L.isc[I_LSB]) == 0 ? (uni(L.isc[I_NRES]) + 31) >> 5 : 0;
-            for (int i = lane; i < nresw; i += WAVE) r[PK_RES + i] = (int)((const uint32_t*)RESB(L))[i];
-            const int* xq = XQ(L);
-            if (PI(hrmode)) { for (int i = lane; i < ((lastnz + 1) & ~1); i += WAVE) r[PK_XQ + i] = xq[i]; }
-            else {
-                /* R/quantize_spec.c:50 asserts that a quantised line fits 16 bits outside the high-resolution mode; here the frame is
-                 * flagged instead (the hand-over keeps the low 16 bits) */
-                bool ovf = false;
-                for (int p = lane; p < ((lastnz + 1) >> 1); p += WAVE) {
-                    const int q0 = xq[2 * p], q1 = xq[2 * p + 1];
-                    ovf |= q0 != (int)(int16_t)q0 || q1 != (int)(int16_t)q1;
-                    r[PK_XQ + p] = (q0 & 0xFFFF) | (q1 << 16);
-                }
-                if (status && __ballot(ovf) && lane == 0) status[(size_t)cs * dT + dt0 + t] |= LC3D_ENC_ST_QUANT_RANGE;
-            }
-            LSYNC();
-            TICK(16);
-            TICK(17);
-            continue;
-        }
-        st_bitstream(P, C, L, lane);
-        LSYNC();
-        TICK(16);
-        if (tr && lane == 0) { tr->n_res_bits = L.isc[I_NRES]; tr->bp_side = L.isc[I_BP_SIDE]; tr->mask_side = L.isc[I_MASK_SIDE]; }
-        /* ---- bytes out ---- */
-#if defined(LC3_ENC_PACKED)
-        const long long po = poff[(size_t)strm * dT + dt0 + t];
-        uint8_t* o = out + (po < 0 ? 0 : po) + CI(out_off);
-        const int nby = po < 0 ? 0 : CI(nbytes);
-#else
-#ifdef LC3_ENC_VAR
-        uint8_t* o = out + ((size_t)strm * dT + dt0 + t) * out_stride + CI(out_off);
-#else
-        uint8_t* o = out + ((size_t)strm * T + t) * out_stride + CI(out_off);
-#endif
-        const int nby = CI(nbytes);
-#endif
-        if (((nby | (int)(size_t)o) & 3) == 0) { for (int i = lane; i < (nby >> 2); i += WAVE) ((uint32_t*)o)[i] = ((const uint32_t*)BYTES(L))[i]; }
-        else for (int i = lane; i < nby; i += WAVE) o[i] = BYTES(L)[i];
-        LSYNC();
-        TICK(17);
-    }
-#ifdef LC3_STAGE_TIMING
-    if (trace && lane < NSTAGE) ((long long*)&trace[(size_t)cs * T])[lane] = L.tacc[lane];
-#endif
-    /* ---- store cross-frame state ---- */
-    for (int i = lane; i < MEMCAP; i += WAVE) stp[LC3D_ST_XPREV + i] = spec ? xnext[(size_t)cs * MEMCAP + i] : L.xbuf[i];
-    for (int i = lane; i < 384; i += WAVE) stp[LC3D_ST_H12(MEMCAP) + i] = L.h12[i];
-    for (int i = lane; i < 194; i += WAVE) stp[LC3D_ST_H6(MEMCAP) + i] = L.h6[i];
-    /* the HP50 state belongs to lc3_enc_hp50_kernel when it runs, the attack detector's to lc3_enc_attack_kernel on the split path */
-    if (lane < 12 && !(y12 && lane < 2) && !(spec && lane >= F_ATT_M0 && lane <= F_ATT_ACC)) stp[LC3D_ST_SCAL(MEMCAP) + lane] = L.fsc[lane];
-    if (lane < 16 && !(spec && (lane == I_ATT_POS || lane == I_ATT_FLAG))) ((int*)stp)[LC3D_ST_SCAL(MEMCAP) + 16 + lane] = L.isc[lane];
-    (void)ml;
-}
-#if defined(LC3_ENC_VBW) && !defined(LC3_ENC_VAR) && !defined(LC3_ENC_PACKED)   /* the per-frame-bandwidth object: besides lc3_encode_kernel_vbw only the two shape kernels */
+#include "lc3_enc_wave.inc"       /* KERNEL_FN, or KERNEL_FN with _fmt */
+#if defined(LC3_ENC_VBW) && !defined(LC3_ENC_VAR) && !defined(LC3_ENC_PACKED) && !defined(LC3_PCM_FMT)   /* the per-frame-bandwidth object: besides lc3_encode_kernel_vbw only the two shape kernels */
 #include "lc3_enc_rate.inc"        /* lc3_enc_shape_kernel_vbw */
 #include "lc3_enc_shapel.inc"      /* lc3_enc_shape_lane_kernel_vbw */
 #endif
-#if !defined(LC3_ENC_VAR) && !defined(LC3_ENC_VBW) && !defined(LC3_ENC_PACKED)   /* the per-frame-bitrate, per-frame-bandwidth and packed objects hold only their kernels */
+#if defined(LC3_PCM_FMT) && !defined(LC3_ENC_VAR) && !defined(LC3_ENC_VBW) && !defined(LC3_ENC_PACKED)
+#define FRONT_PCM_FMT 1
+#include "lc3_enc_front.inc"       /* lc3_enc_front_kernel_fmt (or _big_fmt) */
+#ifndef LC3_BIG
+#include "lc3_enc_front4.inc"      /* lc3_enc_front4_kernel_fmt */
+#include "lc3_enc_frontm.inc"      /* lc3_enc_frontm_kernel_fmt */
+#include "lc3_enc_pre.inc"         /* lc3_enc_resample_fmt_kernel, lc3_enc_resample48f_kernel */
+#endif
+#endif
+#if !defined(LC3_ENC_VAR) && !defined(LC3_ENC_VBW) && !defined(LC3_ENC_PACKED) && !defined(LC3_PCM_FMT)   /* the per-frame-bitrate, per-frame-bandwidth, packed and PCM-format objects hold only their kernels */
 
 /* ------------------------------------------------------------------------------------------------ */
 /* C-ABI device shim (lc3_shim.h): context, uploads, launch                                          */
 /* ------------------------------------------------------------------------------------------------ */
+#define FRONT_PCM_FMT 0
 #include "lc3_enc_front.inc"       /* lc3_enc_front_kernel (or _big): the stateless front, frame-parallel */
 #ifndef LC3_BIG
 #include "lc3_enc_front4.inc"      /* lc3_enc_front4_kernel: the same for N = 480, four frames per wave */
@@ -3029,6 +2782,32 @@ extern "C" __global__ void lc3_encode_kernel_big_var_pk(LC3_OW_ARGS, const uint1
 extern "C" __global__ void lc3_encode_kernel_vbw_pk(LC3_OW_ARGS, const uint16_t* __restrict__ bwf, const long long* __restrict__ poff);
 extern "C" __global__ void lc3_encode_kernel_var_vbw_pk(LC3_OW_ARGS, const uint16_t* __restrict__ fsz, const lc3d_chan* __restrict__ etab, const uint16_t* __restrict__ bwf,
                                                         const long long* __restrict__ poff);
+/* ... and every one-wave kernel once more for the PCM formats beyond 16 / 24 / 32 (float samples, the two other layouts), next to its twin in the same object */
+extern "C" __global__ void lc3_encode_kernel_big_fmt(LC3_OW_ARGS);
+extern "C" __global__ void lc3_encode_kernel_var_fmt(LC3_OW_ARGS, const uint16_t* __restrict__ fsz, const lc3d_chan* __restrict__ etab);
+extern "C" __global__ void lc3_encode_kernel_big_var_fmt(LC3_OW_ARGS, const uint16_t* __restrict__ fsz, const lc3d_chan* __restrict__ etab);
+extern "C" __global__ void lc3_encode_kernel_vbw_fmt(LC3_OW_ARGS, const uint16_t* __restrict__ bwf);
+extern "C" __global__ void lc3_encode_kernel_var_vbw_fmt(LC3_OW_ARGS, const uint16_t* __restrict__ fsz, const lc3d_chan* __restrict__ etab, const uint16_t* __restrict__ bwf);
+extern "C" __global__ void lc3_encode_kernel_pk_fmt(LC3_OW_ARGS, const long long* __restrict__ poff);
+extern "C" __global__ void lc3_encode_kernel_big_pk_fmt(LC3_OW_ARGS, const long long* __restrict__ poff);
+extern "C" __global__ void lc3_encode_kernel_var_pk_fmt(LC3_OW_ARGS, const uint16_t* __restrict__ fsz, const lc3d_chan* __restrict__ etab, const long long* __restrict__ poff);
+extern "C" __global__ void lc3_encode_kernel_big_var_pk_fmt(LC3_OW_ARGS, const uint16_t* __restrict__ fsz, const lc3d_chan* __restrict__ etab, const long long* __restrict__ poff);
+extern "C" __global__ void lc3_encode_kernel_vbw_pk_fmt(LC3_OW_ARGS, const uint16_t* __restrict__ bwf, const long long* __restrict__ poff);
+extern "C" __global__ void lc3_encode_kernel_var_vbw_pk_fmt(LC3_OW_ARGS, const uint16_t* __restrict__ fsz, const lc3d_chan* __restrict__ etab, const uint16_t* __restrict__ bwf,
+                                                            const long long* __restrict__ poff);
+extern "C" __global__ void lc3_encode_kernel_fmt(LC3_OW_ARGS);
+extern "C" __global__ void lc3_enc_front_kernel_fmt(const lc3d_plan* __restrict__ P, const lc3d_chan* __restrict__ chans, const float* __restrict__ state, const void* __restrict__ pcm,
+                                                    int bitdepth, int T, int tb, int nt, int fpw, int ncs, float* __restrict__ spec, int srow, int RT, int r0, float* __restrict__ rec, float* __restrict__ xnext, const float* __restrict__ xprev, int xprev_stride, int do_scf);
+extern "C" __global__ void lc3_enc_front4_kernel_fmt(const lc3d_plan* __restrict__ P, const lc3d_chan* __restrict__ chans, const float* __restrict__ state, const void* __restrict__ pcm, int bitdepth,
+                                                     int T, int tb, int nt, int ncs, float* __restrict__ spec, int srow, int RT, int r0, float* __restrict__ rec, float* __restrict__ xnext, const float* __restrict__ xprev, int xprev_stride);
+extern "C" __global__ void lc3_enc_frontm_kernel_fmt(const lc3d_plan* __restrict__ P, const lc3d_chan* __restrict__ chans, const float* __restrict__ state, const void* __restrict__ pcm, int bitdepth,
+                                                     int T, int tb, int nt, int F, int ncs, float* __restrict__ spec, int srow, int RT, int r0, float* __restrict__ rec, float* __restrict__ xnext, const float* __restrict__ xprev, int xprev_stride);
+extern "C" __global__ void lc3_enc_resample48f_kernel(const lc3d_plan* __restrict__ P, const float* __restrict__ pcm, int fmt, int channels, int memcap, int T, int tb, int nt, int ncs, float* __restrict__ d12,
+                                                      const float* __restrict__ xprev, int xprev_stride);
+extern "C" __global__ void lc3_enc_resample_fmt_kernel(const lc3d_plan* __restrict__ P, const float* __restrict__ state, int state_words, int memcap, const void* __restrict__ pcm, int bitdepth,
+                                                       int T, int tb, int nt, int ncs, float* __restrict__ d12, const float* __restrict__ xprev, int xprev_stride);
+extern "C" __global__ void lc3_enc_front_kernel_big_fmt(const lc3d_plan* __restrict__ P, const lc3d_chan* __restrict__ chans, const float* __restrict__ state, const void* __restrict__ pcm,
+                                                        int bitdepth, int T, int tb, int nt, int fpw, int ncs, float* __restrict__ spec, int srow, int RT, int r0, float* __restrict__ rec, float* __restrict__ xnext, const float* __restrict__ xprev, int xprev_stride, int do_scf);
 #undef LC3_OW_ARGS
 #include "lc3_enc_pack.inc"
 #include "lc3_enc_snsvq.inc"
@@ -3533,13 +3312,15 @@ static void launch_resample(lc3hip_ctx* c, hipStream_t st, const void* dpcm, int
     const unsigned pruns = (unsigned)((hn + PRE_FPW - 1) / PRE_FPW);
     if (c->rs48 && bitdepth == 16 && (((size_t)dpcm) & 15) == 0)
         hipLaunchKernelGGL(lc3_enc_resample48_kernel, dim3((unsigned)c->ncs * pruns), dim3(WAVE), 0, st, c->d_plan, (const int16_t*)dpcm, c->channels, mc, n_frames, hb, hn, c->ncs, dy12, xprev, xprev_stride);
+    else if (c->rs48 && (bitdepth & (LC3D_PCM_TYPE_MASK | LC3D_PCM_INTERLEAVED)) == LC3D_PCM_FLOAT32 && (((size_t)dpcm) & 15) == 0)   /* frames of 480 x 4 bytes: every one 16-byte aligned */
+        hipLaunchKernelGGL(lc3_enc_resample48f_kernel, dim3((unsigned)c->ncs * pruns), dim3(WAVE), 0, st, c->d_plan, (const float*)dpcm, bitdepth, c->channels, mc, n_frames, hb, hn, c->ncs, dy12, xprev, xprev_stride);
     else if (c->rs96 && bitdepth == 16 && (((size_t)dpcm) & 15) == 0) {
         auto k = c->N == 960 ? lc3_enc_resample96_kernel_n960 : c->N == 480 ? lc3_enc_resample96_kernel_n480 : lc3_enc_resample96_kernel_n240;
         const int fpb = (1920 / c->N) * PRE96_ITERS;                       /* frames per workgroup: PRE96_ITERS steps of 1 920 samples */
         hipLaunchKernelGGL(k, dim3((unsigned)c->ncs * (unsigned)((hn + fpb - 1) / fpb)), dim3(WAVE), 0, st, c->d_plan, (const int16_t*)dpcm, c->channels, mc, n_frames, hb, hn, c->ncs, dy12, xprev, xprev_stride);
     }
     else
-        hipLaunchKernelGGL(lc3_enc_resample_kernel, dim3((unsigned)c->ncs * pruns), dim3(WAVE), 0, st, c->d_plan, c->d_state, c->state_words, mc, dpcm, bitdepth, n_frames, hb, hn, c->ncs, dy12, xprev, xprev_stride);
+        hipLaunchKernelGGL((bitdepth == 16 || bitdepth == 24 || bitdepth == 32) ? lc3_enc_resample_kernel : lc3_enc_resample_fmt_kernel, dim3((unsigned)c->ncs * pruns), dim3(WAVE), 0, st, c->d_plan, c->d_state, c->state_words, mc, dpcm, bitdepth, n_frames, hb, hn, c->ncs, dy12, xprev, xprev_stride);
 }
 static int bw_to(lc3hip_ctx* c, hipStream_t st);
 static int enc_launch(lc3hip_ctx* c, const void* dpcm, int bitdepth, int n_frames, uint8_t* dout, int out_stride, hipStream_t s, lc3d_trace* dtr,
@@ -3558,6 +3339,8 @@ static int enc_launch(lc3hip_ctx* c, const void* dpcm, int bitdepth, int n_frame
      * (4096 streams, Mframes/s pipelined / in-kernel writer: 3 frames 31.9 / 36.3, 4: 39.8 / 38.0, 6: 48.6 / 40.2, 8: 53.9 / 41.2; without the
      * promise 8: 40.2 / 41.2) */
     /* (per-frame bitrates: always - lc3_encode_kernel_var reloads the configuration per frame; it is the only kernel that does) */
+    /* the PCM formats beyond the reference's three have kernels of their own (_fmt) wherever the load could not be added without moving the registers of the kernel that is there */
+    const bool fmt_plain = bitdepth == 16 || bitdepth == 24 || bitdepth == 32;
     const bool in_kernel_writer = dtr || c->fused || dfsz || dT <= (c->input_ready ? LC3D_FUSED_MAX_T_READY : LC3D_FUSED_MAX_T);
     if (!in_kernel_writer) {
         dstride = PK_STRIDE(c->N, c->hr);
@@ -3597,40 +3380,41 @@ static int enc_launch(lc3hip_ctx* c, const void* dpcm, int bitdepth, int n_frame
             HIPCHK(hipGetLastError());
         }
         if (dbw && bw_to(c, s)) return 1;
+#define OWK(k) (fmt_plain ? k : k##_fmt)
         const long long* pt = c->pk.on ? c->pk.tab : nullptr;         /* packed output: the _pk kernels, frames at the offsets of the call's table */
         if (pt) {
-            if (dfsz && dbw) hipLaunchKernelGGL(lc3_encode_kernel_var_vbw_pk, dim3(c->ncs), dim3(WAVE), 0, s, c->d_plan, c->d_chans, c->d_state, dpcm, bitdepth, n_frames,
+            if (dfsz && dbw) hipLaunchKernelGGL(OWK(lc3_encode_kernel_var_vbw_pk), dim3(c->ncs), dim3(WAVE), 0, s, c->d_plan, c->d_chans, c->d_state, dpcm, bitdepth, n_frames,
                                                 dout, 0, c->ncs, dtr, ddump, dstride, dy12, c->d_status, dT, dt0, (const float*)nullptr, (const float*)nullptr,
                                                 (const float*)nullptr, dfsz, (const lc3d_chan*)c->d_etab, dbw, pt);
-            else if (dfsz && c->big) hipLaunchKernelGGL(lc3_encode_kernel_big_var_pk, dim3(c->ncs), dim3(WAVE), 0, s, c->d_plan, c->d_chans, c->d_state, dpcm, bitdepth, n_frames,
+            else if (dfsz && c->big) hipLaunchKernelGGL(OWK(lc3_encode_kernel_big_var_pk), dim3(c->ncs), dim3(WAVE), 0, s, c->d_plan, c->d_chans, c->d_state, dpcm, bitdepth, n_frames,
                                                    dout, 0, c->ncs, dtr, ddump, dstride, dy12, c->d_status, dT, dt0, (const float*)nullptr, (const float*)nullptr,
                                                    (const float*)nullptr, dfsz, (const lc3d_chan*)c->d_etab, pt);
-            else if (dfsz) hipLaunchKernelGGL(lc3_encode_kernel_var_pk, dim3(c->ncs), dim3(WAVE), 0, s, c->d_plan, c->d_chans, c->d_state, dpcm, bitdepth, n_frames,
+            else if (dfsz) hipLaunchKernelGGL(OWK(lc3_encode_kernel_var_pk), dim3(c->ncs), dim3(WAVE), 0, s, c->d_plan, c->d_chans, c->d_state, dpcm, bitdepth, n_frames,
                                               dout, 0, c->ncs, dtr, ddump, dstride, dy12, c->d_status, dT, dt0, (const float*)nullptr, (const float*)nullptr,
                                               (const float*)nullptr, dfsz, (const lc3d_chan*)c->d_etab, pt);
-            else if (c->big) hipLaunchKernelGGL(lc3_encode_kernel_big_pk, dim3(c->ncs), dim3(WAVE), 0, s, c->d_plan, c->d_chans, c->d_state, dpcm, bitdepth, n_frames,
+            else if (c->big) hipLaunchKernelGGL(OWK(lc3_encode_kernel_big_pk), dim3(c->ncs), dim3(WAVE), 0, s, c->d_plan, c->d_chans, c->d_state, dpcm, bitdepth, n_frames,
                                            dout, 0, c->ncs, dtr, ddump, dstride, dy12, c->d_status, dT, dt0, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, pt);
-            else if (dbw) hipLaunchKernelGGL(lc3_encode_kernel_vbw_pk, dim3(c->ncs), dim3(WAVE), 0, s, c->d_plan, c->d_chans, c->d_state, dpcm, bitdepth, n_frames,
+            else if (dbw) hipLaunchKernelGGL(OWK(lc3_encode_kernel_vbw_pk), dim3(c->ncs), dim3(WAVE), 0, s, c->d_plan, c->d_chans, c->d_state, dpcm, bitdepth, n_frames,
                                              dout, 0, c->ncs, dtr, ddump, dstride, dy12, c->d_status, dT, dt0, (const float*)nullptr, (const float*)nullptr,
                                              (const float*)nullptr, dbw, pt);
-            else hipLaunchKernelGGL(lc3_encode_kernel_pk, dim3(c->ncs), dim3(WAVE), 0, s, c->d_plan, c->d_chans, c->d_state, dpcm, bitdepth, n_frames,
+            else hipLaunchKernelGGL(OWK(lc3_encode_kernel_pk), dim3(c->ncs), dim3(WAVE), 0, s, c->d_plan, c->d_chans, c->d_state, dpcm, bitdepth, n_frames,
                                     dout, 0, c->ncs, dtr, ddump, dstride, dy12, c->d_status, dT, dt0, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, pt);
         } else
-        if (dfsz && dbw) hipLaunchKernelGGL(lc3_encode_kernel_var_vbw, dim3(c->ncs), dim3(WAVE), 0, s, c->d_plan, c->d_chans, c->d_state, dpcm, bitdepth, n_frames,
+        if (dfsz && dbw) hipLaunchKernelGGL(OWK(lc3_encode_kernel_var_vbw), dim3(c->ncs), dim3(WAVE), 0, s, c->d_plan, c->d_chans, c->d_state, dpcm, bitdepth, n_frames,
                                             dout, out_stride, c->ncs, dtr, ddump, dstride, dy12, c->d_status, dT, dt0, (const float*)nullptr, (const float*)nullptr,
                                             (const float*)nullptr, dfsz, (const lc3d_chan*)c->d_etab, dbw);
-        else if (dfsz && c->big) hipLaunchKernelGGL(lc3_encode_kernel_big_var, dim3(c->ncs), dim3(WAVE), 0, s, c->d_plan, c->d_chans, c->d_state, dpcm, bitdepth, n_frames,
+        else if (dfsz && c->big) hipLaunchKernelGGL(OWK(lc3_encode_kernel_big_var), dim3(c->ncs), dim3(WAVE), 0, s, c->d_plan, c->d_chans, c->d_state, dpcm, bitdepth, n_frames,
                                                dout, out_stride, c->ncs, dtr, ddump, dstride, dy12, c->d_status, dT, dt0, (const float*)nullptr, (const float*)nullptr,
                                                (const float*)nullptr, dfsz, (const lc3d_chan*)c->d_etab);
-        else if (dfsz) hipLaunchKernelGGL(lc3_encode_kernel_var, dim3(c->ncs), dim3(WAVE), 0, s, c->d_plan, c->d_chans, c->d_state, dpcm, bitdepth, n_frames,
+        else if (dfsz) hipLaunchKernelGGL(OWK(lc3_encode_kernel_var), dim3(c->ncs), dim3(WAVE), 0, s, c->d_plan, c->d_chans, c->d_state, dpcm, bitdepth, n_frames,
                                           dout, out_stride, c->ncs, dtr, ddump, dstride, dy12, c->d_status, dT, dt0, (const float*)nullptr, (const float*)nullptr,
                                           (const float*)nullptr, dfsz, (const lc3d_chan*)c->d_etab);
-        else if (c->big) hipLaunchKernelGGL(lc3_encode_kernel_big, dim3(c->ncs), dim3(WAVE), 0, s, c->d_plan, c->d_chans, c->d_state, dpcm, bitdepth, n_frames,
+        else if (c->big) hipLaunchKernelGGL(OWK(lc3_encode_kernel_big), dim3(c->ncs), dim3(WAVE), 0, s, c->d_plan, c->d_chans, c->d_state, dpcm, bitdepth, n_frames,
                                        dout, out_stride, c->ncs, dtr, ddump, dstride, dy12, c->d_status, dT, dt0, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr);
-        else if (dbw) hipLaunchKernelGGL(lc3_encode_kernel_vbw, dim3(c->ncs), dim3(WAVE), 0, s, c->d_plan, c->d_chans, c->d_state, dpcm, bitdepth, n_frames,
+        else if (dbw) hipLaunchKernelGGL(OWK(lc3_encode_kernel_vbw), dim3(c->ncs), dim3(WAVE), 0, s, c->d_plan, c->d_chans, c->d_state, dpcm, bitdepth, n_frames,
                                          dout, out_stride, c->ncs, dtr, ddump, dstride, dy12, c->d_status, dT, dt0, (const float*)nullptr, (const float*)nullptr,
                                          (const float*)nullptr, dbw);
-        else hipLaunchKernelGGL(lc3_encode_kernel, dim3(c->ncs), dim3(WAVE), 0, s, c->d_plan, c->d_chans, c->d_state, dpcm, bitdepth, n_frames,
+        else hipLaunchKernelGGL(OWK(lc3_encode_kernel), dim3(c->ncs), dim3(WAVE), 0, s, c->d_plan, c->d_chans, c->d_state, dpcm, bitdepth, n_frames,
                                 dout, out_stride, c->ncs, dtr, ddump, dstride, dy12, c->d_status, dT, dt0, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr);
     } else {
         /* The pipelined path.  Per run of frames: on one side stream the pitch chain (resampler per frame, HP50 one stream per lane, OLPA +
@@ -3752,11 +3536,11 @@ static int enc_launch(lc3hip_ctx* c, const void* dpcm, int bitdepth, int n_frame
             const unsigned fruns = (unsigned)((nt + fpw - 1) / fpw);
             const int f4 = c->opt.front4;
             if (f4 && !c->big && !scf_wave && c->N == 480 && c->la == 180 && (c->ylen & 15) == 0)
-                DUPL('f') hipLaunchKernelGGL(lc3_enc_front4_kernel, dim3((unsigned)c->ncs * (unsigned)((nt + 3) / 4)), dim3(WAVE), 0, c->s_fr, c->d_plan, c->d_chans, c->d_state, dpcm, bitdepth, n_frames, tb, nt, c->ncs, dspec, c->srow, dT, dt0, dfrec, xn_w, xprev, xprev_stride);
+                DUPL('f') hipLaunchKernelGGL(fmt_plain ? lc3_enc_front4_kernel : lc3_enc_front4_kernel_fmt, dim3((unsigned)c->ncs * (unsigned)((nt + 3) / 4)), dim3(WAVE), 0, c->s_fr, c->d_plan, c->d_chans, c->d_state, dpcm, bitdepth, n_frames, tb, nt, c->ncs, dspec, c->srow, dT, dt0, dfrec, xn_w, xprev, xprev_stride);
             else if (f4 && c->fm_frames && !scf_wave)
-                hipLaunchKernelGGL(lc3_enc_frontm_kernel, dim3((unsigned)c->ncs * (unsigned)((nt + c->fm_frames - 1) / c->fm_frames)), dim3(WAVE), 0, c->s_fr, c->d_plan, c->d_chans, c->d_state, dpcm, bitdepth, n_frames, tb, nt, c->fm_frames, c->ncs, dspec, c->srow, dT, dt0, dfrec, xn_w, xprev, xprev_stride);
-            else if (c->big) hipLaunchKernelGGL(lc3_enc_front_kernel_big, dim3((unsigned)c->ncs * fruns), dim3(WAVE), 0, c->s_fr, c->d_plan, c->d_chans, c->d_state, dpcm, bitdepth, n_frames, tb, nt, fpw, c->ncs, dspec, c->srow, dT, dt0, dfrec, xn_w, xprev, xprev_stride, scf_wave);
-            else DUPL('f') hipLaunchKernelGGL(lc3_enc_front_kernel, dim3((unsigned)c->ncs * fruns), dim3(WAVE), 0, c->s_fr, c->d_plan, c->d_chans, c->d_state, dpcm, bitdepth, n_frames, tb, nt, fpw, c->ncs, dspec, c->srow, dT, dt0, dfrec, xn_w, xprev, xprev_stride, scf_wave);
+                hipLaunchKernelGGL(fmt_plain ? lc3_enc_frontm_kernel : lc3_enc_frontm_kernel_fmt, dim3((unsigned)c->ncs * (unsigned)((nt + c->fm_frames - 1) / c->fm_frames)), dim3(WAVE), 0, c->s_fr, c->d_plan, c->d_chans, c->d_state, dpcm, bitdepth, n_frames, tb, nt, c->fm_frames, c->ncs, dspec, c->srow, dT, dt0, dfrec, xn_w, xprev, xprev_stride);
+            else if (c->big) hipLaunchKernelGGL(fmt_plain ? lc3_enc_front_kernel_big : lc3_enc_front_kernel_big_fmt, dim3((unsigned)c->ncs * fruns), dim3(WAVE), 0, c->s_fr, c->d_plan, c->d_chans, c->d_state, dpcm, bitdepth, n_frames, tb, nt, fpw, c->ncs, dspec, c->srow, dT, dt0, dfrec, xn_w, xprev, xprev_stride, scf_wave);
+            else DUPL('f') hipLaunchKernelGGL(fmt_plain ? lc3_enc_front_kernel : lc3_enc_front_kernel_fmt, dim3((unsigned)c->ncs * fruns), dim3(WAVE), 0, c->s_fr, c->d_plan, c->d_chans, c->d_state, dpcm, bitdepth, n_frames, tb, nt, fpw, c->ncs, dspec, c->srow, dT, dt0, dfrec, xn_w, xprev, xprev_stride, scf_wave);
             HIPCHK(hipEventRecord(c->ev_m[k], c->s_fr));                 /* the MDCT memory hand-over and the spectrum rows of the run are written */
             if (five) HIPCHK(hipStreamWaitEvent(c->s_ln, c->ev_m[k], 0));
             const int fuse_vq = !scf_wave && !c->any_attack && c->opt.fuse_vq;
@@ -3880,11 +3664,12 @@ static bool host_ptr_is_pinned(const void* p)
 static int encode_host(lc3hip_ctx* c, const void* pcm, int bitdepth, int n_frames, void* out, int out_stride, hipStream_t s, const uint16_t* dfsz,
                        const uint16_t* dbw)
 {
-    const size_t bps = bitdepth == 16 ? 2 : 4;
+    const size_t bps = (size_t)lc3d_pcm_elem_bytes(bitdepth);
     const size_t fr_in = (size_t)c->channels * c->N * bps;                    /* bytes of one stream-frame of PCM */
     const size_t pcm_bytes = (size_t)c->n_streams * n_frames * fr_in, out_bytes = (size_t)c->n_streams * n_frames * out_stride;
     int K = (int)(pcm_bytes >> 25);                                           /* ~32 MB of PCM per run */
     if (K < 1) K = 1; if (K > 8) K = 8; if (K > n_frames) K = n_frames;
+    if ((bitdepth & LC3D_PCM_CHANNEL_MAJOR) && c->channels > 1) K = 1;        /* a run of frames is one block per stream in the two other layouts only: this one goes up in one piece */
     if (!dfsz && (c->fused || n_frames <= LC3D_FUSED_MAX_T)) K = 1;                                          /* diagnostic single-kernel path: the first kernel addresses the output by its own frame count (the per-frame-bitrate kernel by the call's) */
     const int Tc = (n_frames + K - 1) / K, T0 = K > 1 ? (Tc + 1) / 2 : Tc;   /* first run: half a run */
     const bool pin_in = host_ptr_is_pinned(pcm);
@@ -4033,7 +3818,7 @@ extern "C" int lc3hip_encode(void* ctx, const void* pcm, int pcm_on_device, int 
         if (ev_bw) HIPCHK(hipEventRecord(ev_bw, s));
         return 0;
     }
-    const size_t bps = bitdepth == 16 ? 2 : 4;
+    const size_t bps = (size_t)lc3d_pcm_elem_bytes(bitdepth);
     const size_t pcm_bytes = (size_t)c->n_streams * n_frames * c->channels * c->N * bps;
     const size_t out_bytes = (size_t)c->n_streams * n_frames * out_stride;
     const void* dpcm = pcm; uint8_t* dout = (uint8_t*)out;
@@ -4447,7 +4232,7 @@ static int dec_decode(lc3hip_dctx* c, const void* frames, int frames_on_device, 
     hipStream_t s = hip_stream ? (hipStream_t)hip_stream : c->stream;
     if (c->ss.done_armed) HIPCHK(hipStreamWaitEvent(s, c->ss.ev_done, 0));      /* behind the last stream-lifecycle call, whichever stream it was queued on */
     const size_t in_bytes = (size_t)c->n_streams * n_frames * in_stride;
-    const size_t pcm_bytes = (size_t)c->ncs * n_frames * c->N * (bps == 16 ? 2 : 4);
+    const size_t pcm_bytes = (size_t)c->ncs * n_frames * c->N * (size_t)lc3d_pcm_elem_bytes(bps);
     const uint8_t* din = (const uint8_t*)frames; void* dpcm = pcm; const uint8_t* dbfi = nullptr; lc3d_dec_trace* dtr = nullptr;
     if (!frames_on_device) {
         if (c->in_cap < in_bytes) { if (c->d_in) HIPCHK(hipFree(c->d_in)); HIPCHK(hipMalloc((void**)&c->d_in, in_bytes)); c->in_cap = in_bytes; }

@@ -10,6 +10,7 @@
  */
 #ifndef LC3_PLAN_H
 #define LC3_PLAN_H
+#include <stddef.h>
 #include <stdint.h>
 
 #define LC3D_MAX_N 960          /* largest frame length (96 kHz / 10 ms); the kernels come in two LDS layouts, see lc3_kernels.hip */
@@ -225,5 +226,32 @@ static inline LC3D_HD int lc3d_enc_frame_step(const lc3d_rate_rule* r, int has_r
 enum { DS_PITCH_INT = 0, DS_PITCH_FR, DS_BETA_IDX, DS_PARAM0, DS_PARAM1, DS_PARAM2, DS_GAIN /* float */, DS_NBLOST, DS_CUM_ALPHA /* float */, DS_PLC_SEED,
        DS_PREV_BFI, DS_PREVPREV_BFI };
 
+/* ---- The PCM format word of the batch calls (include/lc3plus_batch.h: LC3PLUS_PCM_*) --------------------------------------------------------------
+ * Bits 0 ... 7: the sample type - 16, 24, 32 (integers as the reference's bitdepth / bps) or LC3D_PCM_FLOAT32 (IEEE float, full scale 1.0);
+ * bits 8, 9: the layout - none = [stream][frame][channel][sample], LC3D_PCM_INTERLEAVED = [stream][time][channel], LC3D_PCM_CHANNEL_MAJOR =
+ * [stream][channel][time], time = frame * N + sample.  The same arithmetic on the host (lc3plus_pcm_format_check, lc3plus_pcm_offset) and in every kernel
+ * that touches PCM: lc3d_pcm_frame gives the element index of sample 0 of (stream, frame, channel); sample i is lc3d_pcm_stride further per step, and the same
+ * channel's next frame lc3d_pcm_fstep further. */
+#define LC3D_PCM_FLOAT32       0x80
+#define LC3D_PCM_TYPE_MASK     0xff
+#define LC3D_PCM_INTERLEAVED   0x100
+#define LC3D_PCM_CHANNEL_MAJOR 0x200
+#define LC3D_PCM_LAYOUT_MASK   0x300
+static inline LC3D_HD int lc3d_pcm_format_ok(int fmt)
+{
+    const int ty = fmt & LC3D_PCM_TYPE_MASK, lay = fmt & LC3D_PCM_LAYOUT_MASK;
+    if (fmt & ~(LC3D_PCM_TYPE_MASK | LC3D_PCM_LAYOUT_MASK)) return 0;
+    if (ty != 16 && ty != 24 && ty != 32 && ty != LC3D_PCM_FLOAT32) return 0;
+    return lay != LC3D_PCM_LAYOUT_MASK;
+}
+static inline LC3D_HD int lc3d_pcm_elem_bytes(int fmt) { return (fmt & LC3D_PCM_TYPE_MASK) == 16 ? 2 : 4; }
+static inline LC3D_HD int lc3d_pcm_stride(int fmt, int channels) { return (fmt & LC3D_PCM_INTERLEAVED) ? channels : 1; }
+static inline LC3D_HD size_t lc3d_pcm_fstep(int fmt, int channels, int N) { return (fmt & LC3D_PCM_CHANNEL_MAJOR) ? (size_t)N : (size_t)N * channels; }
+static inline LC3D_HD size_t lc3d_pcm_frame(int fmt, int channels, int T, int N, int strm, int t, int ch)
+{
+    if (fmt & LC3D_PCM_CHANNEL_MAJOR) return (((size_t)strm * channels + ch) * T + t) * N;
+    if (fmt & LC3D_PCM_INTERLEAVED) return ((size_t)strm * T + t) * N * channels + ch;
+    return (((size_t)strm * T + t) * channels + ch) * N;
+}
 
 #endif

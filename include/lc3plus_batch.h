@@ -31,8 +31,36 @@ int lc3plus_enc_batch_stride(const lc3plus_batch* batch);           /* max over 
 LC3_Error lc3plus_enc_batch_set_bitrate(lc3plus_batch* batch, int stream, int bitrate);
 LC3_Error lc3plus_enc_batch_set_bandwidth(lc3plus_batch* batch, int stream, int bandwidth);
 
+/* ---- The PCM format word ------------------------------------------------------------------------------------------------------------------
+ * The `bitdepth` argument of every batched encode call and the `bps` argument of every batched decode call is a format word: a sample type, alone or
+ * combined (|) with ONE layout.  16, 24 and 32 alone are what they always were.  Any other value is LC3_ERROR before any work is done.
+ *
+ * Sample type:
+ *   16, 24, 32          : int16_t / int32_t as the reference takes and gives them (lc3_enc_fl bitdepth, lc3_dec_fl bps)
+ *   LC3PLUS_PCM_FLOAT32 : IEEE float, full scale 1.0.  Encoder: the internal sample is x * 32768.0f and nothing else - no rounding and no clipping
+ *                         (the integer formats do not clip either), so float input that lies on the 16-, 24- or 32-bit grid gives the bytes of that
+ *                         integer format.  A NaN or an infinity is taken as 0.0f, so that one bad sample cannot stay in a stream's filter
+ *                         memories for ever.  Decoder: the synthesised sample times 2^-15, neither rounded nor clipped (the integer formats round that
+ *                         same value, R/dec_lc3_fl.c:115-127), so it may exceed [-1, 1).
+ * Layout of one call's n_streams x n_frames x channels x samples elements (N = samples per frame, time = frame * N + sample):
+ *   none                      : [stream][frame][channel][sample]
+ *   LC3PLUS_PCM_INTERLEAVED   : [stream][time][channel]         - capture, WAV and RTP order
+ *   LC3PLUS_PCM_CHANNEL_MAJOR : [stream][channel][time]         - the frame count of THIS call is part of the address
+ * With one channel the three are the same addresses.  A layout changes addresses only, never a byte or a sample.
+ * Every format works with host and with device pointers; the device-pointer calls are the fast ones (float samples one after the other are loaded and
+ * stored 16 bytes per lane like the 16-bit ones; interleaved samples one by one).  With host pointers, the channel-major layout is copied in one piece
+ * instead of in overlapped runs of frames.  The traced calls (*_traced) take 16, 24 and 32 alone.
+ * lc3plus_pcm_format_check and lc3plus_pcm_offset are host-only: the check every call makes, and the element index of one sample (-1 for arguments
+ * out of range) - the arithmetic the kernels use. */
+#define LC3PLUS_PCM_FLOAT32       0x80
+#define LC3PLUS_PCM_INTERLEAVED   0x100
+#define LC3PLUS_PCM_CHANNEL_MAJOR 0x200
+LC3_Error lc3plus_pcm_format_check(int format);
+int64_t lc3plus_pcm_offset(int format, int channels, int n_frames, int samples, int stream, int frame, int channel, int sample);
+
 /* Advances every stream by n_frames.
- *   pcm : [n_streams][n_frames][channels][input_samples] samples, int16_t (bitdepth 16) or int32_t (24/32)
+ *   pcm : [n_streams][n_frames][channels][input_samples] samples, int16_t (bitdepth 16) or int32_t (24/32); or float and / or another layout, as the
+ *         format word in `bitdepth` says (above)
  *   out : [n_streams][n_frames][out_stride] bytes; frame payload = num_bytes(stream) bytes, rest untouched
  *   *_on_device : 0 = host pointer, 1 = device pointer used in place.  With BOTH on the host the call is cut into runs of frames
  *                 whose H2D copy, kernels and D2H copy overlap on three HIP streams; pinned caller memory (hipHostMalloc /

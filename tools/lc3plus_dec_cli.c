@@ -159,15 +159,15 @@ int main(int ac, char** av)
             sizes[t] = lost ? 0 : f->nbytes;
             flags[t] = (uint8_t)lost;                                       /* (bfi_ext 3 of a G.192 file decodes as a good frame in the float codec) */
         }
-        err = lc3plus_dec_batch_decode_sizes(b, in_buf, 0, stride, sizes, flags, T, pcm, 0, bps, status, NULL, 1);
+        err = lc3plus_dec_batch_decode_sizes(b, in_buf, 0, stride, sizes, flags, T, pcm, 0, bps | LC3PLUS_PCM_INTERLEAVED, status, NULL, 1);   /* the file's order, [time][channel] */
         if (err == LC3_NUMBYTES_ERROR) { fprintf(stderr, "lc3plus_dec_cli: frame size rejected (LC3_Error %d)\n", (int)err); return 1; }
         if (err) { fprintf(stderr, "lc3plus_dec_cli: decode failed (LC3_Error %d)\n", (int)err); return 1; }
         for (int t = 0; t < T; t++) {
             if (fed) { const int16_t e = status[t]; fwrite(&e, 2, 1, fed); }
-            /* R/codec_exe.c:430-435: interleave, skip the codec delay at the start, stop at the signal length of the header */
+            /* R/codec_exe.c:430-435: skip the codec delay at the start, stop at the signal length of the header (the library has interleaved) */
             uint32_t n_out = (uint32_t)(N - delay) < n_file ? (uint32_t)(N - delay) : n_file;
             for (uint32_t n = 0; n < n_out; n++) for (int c = 0; c < C; c++) {
-                const size_t o = ((size_t)t * C + c) * N + delay + n;
+                const size_t o = ((size_t)t * N + delay + n) * C + c;
                 if (bps == 16) { const int16_t v = ((const int16_t*)pcm)[o]; fwrite(&v, 2, 1, fo); data_bytes += 2; }
                 else if (bps == 24) {                                       /* R/tinywaveout_c.h:403-424 (clip to 24 bit, 3 bytes) */
                     int32_t v = ((const int32_t*)pcm)[o];

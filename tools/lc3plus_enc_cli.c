@@ -145,25 +145,25 @@ int main(int ac, char** av)
             if (fbwf) bws[t] = (int)loopy_read64(fbwf);
         }
         memset(pcm, 0, (size_t)T * C * N * (wide ? 4 : 2));
-        for (int t = 0; t < T; t++) for (int n = 0; n < N; n++) {                 /* de-interleave into [frame][channel][N] */
+        for (int t = 0; t < T; t++) for (int n = 0; n < N; n++) {                 /* the file's samples in the file's order, [time][channel]: the library takes that layout */
             const uint64_t s = (uint64_t)(f0 + t) * N + n;
             if (s >= w.frames) break;
             for (int c = 0; c < C; c++) {
                 const uint8_t* p = w.data + (s * C + c) * bps;
-                const size_t o = ((size_t)t * C + c) * N + n;
+                const size_t o = ((size_t)t * N + n) * C + c;
                 if (w.bits == 16) ((int16_t*)pcm)[o] = (int16_t)rd16(p);
                 else if (w.bits == 24) ((int32_t*)pcm)[o] = ((int32_t)((uint32_t)p[0] << 8 | (uint32_t)p[1] << 16 | (uint32_t)p[2] << 24)) >> 8;
                 else ((int32_t*)pcm)[o] = ((int32_t)rd32(p)) >> 8;   /* the reference reader narrows 32-bit WAV to 24 bit (R/tinywavein_c.h:528-533) and still calls lc3_enc32 */
             }
         }
         if (fbwf) {
-            err = lc3plus_enc_batch_encode_bandwidths(b, pcm, 0, w.bits, bws, fswf ? rates : NULL, T, out, S, 0, sizes, NULL, 1);
+            err = lc3plus_enc_batch_encode_bandwidths(b, pcm, 0, w.bits | LC3PLUS_PCM_INTERLEAVED, bws, fswf ? rates : NULL, T, out, S, 0, sizes, NULL, 1);
             if (err && err < LC3_WARNING) { fprintf(stderr, "lc3plus_enc_cli: encode failed (LC3_Error %d)\n", (int)err); return 1; }
         } else if (fswf) {
-            err = lc3plus_enc_batch_encode_bitrates(b, pcm, 0, w.bits, rates, T, out, S, 0, sizes, NULL, 1);
+            err = lc3plus_enc_batch_encode_bitrates(b, pcm, 0, w.bits | LC3PLUS_PCM_INTERLEAVED, rates, T, out, S, 0, sizes, NULL, 1);
             if (err) { fprintf(stderr, "lc3plus_enc_cli: encode failed (LC3_Error %d)\n", (int)err); return 1; }
         } else {
-            err = lc3plus_enc_batch_encode(b, pcm, 0, w.bits, T, out, S, 0, NULL, 1);
+            err = lc3plus_enc_batch_encode(b, pcm, 0, w.bits | LC3PLUS_PCM_INTERLEAVED, T, out, S, 0, NULL, 1);
             if (err) { fprintf(stderr, "lc3plus_enc_cli: encode failed (LC3_Error %d)\n", (int)err); return 1; }
             for (int t = 0; t < T; t++) sizes[t] = nbytes;
         }
