@@ -330,7 +330,6 @@ lc3_dec_sizes_tail_kernel(const uint16_t* __restrict__ sizes, const uint8_t* __r
 /* A run of IMDCT_FPW consecutive frames of one channel-stream per wave, every frame on its own: shaped (or concealed) spectrum ->
  * DCT-IV -> window.  The overlap-add needs the previous frame and is left to the synthesis kernel: this kernel is stateless, all
  * runs of a launch are independent (ncs * ceil(T / IMDCT_FPW) waves).  The hand-over of the next frame is fetched during the transform. */
-#define IMDCT_FPW 8
 extern "C" __global__ void __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(DEC_IMDCT_WAVES, DEC_IMDCT_WAVES)))
 DEC_IMDCT_KERNEL(const lc3d_plan* __restrict__ P, const float* __restrict__ state, const int* __restrict__ rec /* [cs][T][PR_WORDS] */,
                  const float* __restrict__ ws /* [cs][T][WS_ROW(N)] */, int T, int ncs, float* __restrict__ ov /* [cs][T][OV_ROW(N)] */,

@@ -20,14 +20,6 @@
 
 /* PR_WORDS / PR_BFI / WS_ROW: lc3_plan.h */
 
-struct __attribute__((aligned(16))) ParseLds {
-    unsigned short cum[64 * 32 + 8];     /* spectral models: cumulative frequencies, 32 per model: 0 ... 1024 in [0, 17], 0xFFFF from there on - the symbol search needs
-                                          * no bound on its probe (in a valid state low < (range >> 10) * 1024, so a probe at 17 or beyond never succeeds) */
-    unsigned short tcum[18 + 144];       /* TNS order (2 x 9) and coefficient (8 x 18) models */
-    unsigned char lut[4096];             /* context -> model */
-    unsigned mpvq[176];                  /* MPVQ offsets A(n, k) */
-    int pc[LC3D_PLAN_HEAD_WORDS];
-};
 extern __shared__ unsigned parse_fw[];   /* per wave: [nw][64] frame words, word-major, then [nlw][64] LSB-mode flags (bit (k / 2) of a lane's row is set when
                                           * tuple k had an escape level > 0) */
 

@@ -13,9 +13,6 @@
  * FRONT_PCM_FMT 0: everything, the kernel for the reference's three PCM formats (16, 24, 32 in the default layout) token for token what it was before the PCM
  * format word existed.  FRONT_PCM_FMT 1 (the -DLC3_PCM_FMT objects): the front kernel alone, named with _fmt, for the formats beyond those (float samples, the
  * interleaved and the channel-major layout, lc3_plan.h: lc3d_pcm_*); the two differ in the PCM load alone. */
-#ifndef FRONT_FPW
-#define FRONT_FPW 4
-#endif
 #ifndef FRONT_WAVES
 #ifdef LC3_BIG
 #define FRONT_WAVES 2

@@ -10,9 +10,6 @@
 #ifndef FM_CAP
 #define FM_CAP 960              /* F x N <= 960 words */
 #endif
-#ifndef FM_F240
-#define FM_F240 4               /* frames per wave at N = 240 (FM_CAP / 240).  Measured on c4 (tools/variants.sh): 2 frames (FM_CAP 480) 130.7, 4 frames 136.4, 8 frames (FM_CAP 1920) 130.1 Mframes/s */
-#endif
 struct __attribute__((aligned(16))) FrontMLds {
     float x[MEMCAP + FM_CAP];
     float b[FM_CAP];

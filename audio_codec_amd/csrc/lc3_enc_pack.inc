@@ -26,7 +26,6 @@ struct __attribute__((aligned(16))) PackLds {
     int pc[LC3D_PLAN_HEAD_WORDS];
 };
 extern __shared__ unsigned pack_fw[];    /* per wave: [16][64]: the lane's current 64-byte piece of its spectrum row */
-#define PK_XBUF 16
 typedef unsigned __attribute__((aligned(1), may_alias)) pk_u32u;
 
 struct PkW { uint8_t* o; int nbytes; unsigned fw, bw; int q; int bp; unsigned low, range; int cache, carry, carry_count; bool wr; };   /* wr: the frame's bytes are stored (packed output: false where the frame does not fit) */

@@ -15,9 +15,6 @@ struct __attribute__((aligned(16))) PreLds {
 #ifndef HP_WAVES
 #define HP_WAVES 1
 #endif
-#ifndef PRE_FPW
-#define PRE_FPW 8                        /* frames per wave of the FIR kernel */
-#endif
 
 __device__ __forceinline__ float pre_pcm(const void* __restrict__ pcm, int bitdepth, size_t idx)   /* the encoder's input conversion (R/enc_lc3_fl.c:30-42) */
 {
@@ -216,7 +213,6 @@ __device__ const uint8_t lc3t_b128_slot[64] = {
     32, 33, 34, 35, 48, 49, 50, 51, 52, 53, 54, 55, 36, 37, 38, 39, 56, 57, 58, 59, 40, 41, 42, 43, 44, 45, 46, 47, 60, 61, 62, 63};
 
 struct __attribute__((aligned(16))) Pre96Lds { float xs[120 + 1920 + 8]; };    /* [the 120 samples in front | 1 920 samples = 2 / 4 / 8 frames], scaled */
-#define PRE96_ITERS 4                    /* steps of 1 920 samples per workgroup: the 120 taps are fetched once per workgroup */
 
 template <int NF> __device__ __forceinline__ void
 resample96_body(Pre96Lds& L, const lc3d_plan* __restrict__ P, const int16_t* __restrict__ pcm /* 16-byte aligned */, int channels, int memcap,

@@ -21,9 +21,6 @@
  *
  * All buffers are rows of T frames (the frames of the call); a launch covers frames t0 ... t0 + nt - 1. */
 
-#ifndef SHAPE_FPW
-#define SHAPE_FPW 4
-#endif
 #ifdef LC3_BIG
 #define SHAPE_KERNEL_NAME lc3_enc_shape_kernel_big
 #define RATE_KERNEL_NAME  lc3_enc_rate_kernel_big
@@ -157,7 +154,6 @@ SHAPE_KERNEL_NAME(const lc3d_plan* __restrict__ P, const lc3d_chan* __restrict__
 /* The bit-count tables live in LDS, shared by the RATE_WG waves (channel-streams) of a workgroup: a gather from global memory would be waited for with
  * vmcnt, which counts in issue order - the wait would also be for the next frame's spectrum row, requested a frame ahead precisely so that nobody waits
  * for it (measured before: 4 750 of the kernel's 6 200 wave-cycles per frame waiting). */
-#define RATE_WG 4
 struct __attribute__((aligned(16))) RateLds {
     uint2    esc[1024];
     uint32_t lut4[1024];

@@ -9,25 +9,7 @@
 #define ENC_WAVE_FN KERNEL_FN
 #endif
 extern "C" __global__ void __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(KERNEL_WAVES, KERNEL_WAVES)))
-ENC_WAVE_FN(const lc3d_plan* __restrict__ P, const lc3d_chan* __restrict__ chans, float* __restrict__ state,
-                  const void* __restrict__ pcm, int bitdepth, int T, uint8_t* __restrict__ out, int out_stride, int ncs,
-                  lc3d_trace* __restrict__ trace, int* __restrict__ dump /* [cs][T][dstride] hand-over to lc3_enc_pack_kernel, or null: write the bytes here */, int dstride,
-                  const float* __restrict__ y12 /* [cs][T][128] HP-filtered 12.8 kHz signal from the pre-kernels, or null: resample here */,
-                  uint8_t* __restrict__ status /* [cs][dT] LC3D_ENC_ST_* bits (zeroed by the host), or null */,
-                  int dT, int dt0 /* the hand-over and the status rows hold dT frames per channel-stream; this launch's frame t is their frame dt0 + t */,
-                  const float* __restrict__ spec /* [cs][T][N] MDCT spectra from lc3_enc_front_kernel, or null: transform here */,
-                  const float* __restrict__ frec /* [cs][T][FR_WORDS] with the SNS result of lc3_enc_snsvq_kernel */,
-                  const float* __restrict__ xnext /* [cs][MEMCAP] MDCT memory after the last frame */
-#ifdef LC3_ENC_VAR
-                  , const uint16_t* __restrict__ fsz /* [stream][dT] bytes of each stream-frame */, const lc3d_chan* __restrict__ etab /* per channel byte count */
-#endif
-#ifdef LC3_ENC_VBW
-                  , const uint16_t* __restrict__ bwf /* [stream][dT] bandwidth in force for each stream-frame, Hz */
-#endif
-#ifdef LC3_ENC_PACKED
-                  , const long long* __restrict__ poff /* [stream][dT] byte offset of each stream-frame in out, -1: not written */
-#endif
-                  )
+ENC_WAVE_FN(LC3_OW_ARGS LC3_OW_OPT(LC3_OW_ARGS_, LC3_TU_VAR, LC3_TU_VBW, LC3_TU_PK))      /* lc3_kernel_decls.h: the parameters, and what each is */
 {
     __shared__ WaveLds L;
     const int lane = threadIdx.x;

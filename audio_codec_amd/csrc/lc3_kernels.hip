@@ -1,9 +1,9 @@
-/* lc3_kernels.hip -- gfx950 (MI355X / CDNA4) LC3plus encode / decode kernels + the C-ABI device shim.
+/* lc3_kernels.hip -- gfx950 (MI355X / CDNA4) LC3plus encode / decode kernels.  Device code only: the host side that launches them is lc3_runtime.hip.
  *
  * This file holds (1) the stage functions of the encoder - one per stage of the reference, each citing its lines - and lc3_encode_kernel, which runs
  * all of them with ONE CHANNEL-STREAM PER WAVEFRONT, frames in time order, everything in that wave's LDS slice: the path of traced launches, of calls of
- * a few frames and of the single-stream lc3_enc_* API; (2) the device shim (contexts, launches, streams, events).  The product path for batches is the
- * PIPELINE of kernels in the lc3_enc_*.inc files included below - resampler, HP50, pitch chain, MDCT front, scale factors, SNS quantiser, shaping + TNS,
+ * a few frames and of the single-stream lc3_enc_* API; (2) at its end the includes that decide which kernels an object holds.  The product path for batches is the
+ * PIPELINE of kernels in the lc3_enc_*.inc files included there - resampler, HP50, pitch chain, MDCT front, scale factors, SNS quantiser, shaping + TNS,
  * rate chain, bitstream writer - each with the unit of work its dependences allow (one frame per lane, four frames per wave, one or two channel-streams
  * per wave), hand-overs in HBM, three HIP streams, up to three calls in flight.  PCM is read from HBM with coalesced loads, bytes are
  * written back coalesced.  No MFMA (nothing here is a dense contraction), no collectives.
@@ -32,10 +32,36 @@
 #include "lc3_tables.h"
 #include "lc3_plan.h"
 #include "lc3_shim.h"
+#include "lc3_launch.h"
+#include "lc3_kernel_decls.h"
 
 /* Two LDS layouts of the same code.  Standard: frames up to 480 samples with an MDCT memory of at most 300 (every operating
  * point except two), 10 KB per wave, 4 waves per SIMD.  Large (-DLC3_BIG, kernel lc3_encode_kernel_big): 96 kHz / 10 ms (N = 960)
  * and 96 kHz / 5 ms (N = 480, MDCT memory 360), 17 KB per wave, 2 waves per SIMD. */
+/* What this object is, from the five -D switches (csrc/Makefile: one object per combination).  Every object holds its one-wave encode kernel
+ * (lc3_enc_wave.inc); three kinds hold more: */
+#if !defined(LC3_ENC_VAR) && !defined(LC3_ENC_VBW) && !defined(LC3_ENC_PACKED) && !defined(LC3_PCM_FMT)
+#define LC3_TU_MAIN 1           /* the plain object (or with -DLC3_BIG the large-layout one): every other kernel of the library */
+#elif defined(LC3_ENC_VBW) && !defined(LC3_ENC_VAR) && !defined(LC3_ENC_PACKED) && !defined(LC3_PCM_FMT)
+#define LC3_TU_VBW_SHAPE 1      /* the per-frame-bandwidth object: the two shape kernels that read the bandwidth words */
+#elif defined(LC3_PCM_FMT) && !defined(LC3_ENC_VAR) && !defined(LC3_ENC_VBW) && !defined(LC3_ENC_PACKED)
+#define LC3_TU_FMT_FRONT 1      /* the plain PCM-format object (or its large-layout twin): the front and resampler kernels of those formats */
+#endif
+#ifdef LC3_ENC_VAR              /* the optional argument groups of this object's one-wave kernel (lc3_kernel_decls.h: LC3_OW_OPT) */
+#define LC3_TU_VAR 1
+#else
+#define LC3_TU_VAR 0
+#endif
+#ifdef LC3_ENC_VBW
+#define LC3_TU_VBW 1
+#else
+#define LC3_TU_VBW 0
+#endif
+#ifdef LC3_ENC_PACKED
+#define LC3_TU_PK 1
+#else
+#define LC3_TU_PK 0
+#endif
 #if defined(LC3_BIG) && defined(LC3_ENC_VBW)
 #error "per-frame bandwidths have no large-layout kernels: that layout only serves 96 kHz, which is high-resolution and has no bandwidth controller"
 #endif
@@ -76,7 +102,6 @@
 #define KERNEL_FN KERNEL_NAME
 #endif
 #define NQL ((MAXN / 4 + 63) / 64)   /* bisection energies (4 bins each) per lane: 2 or 4 */
-#define WAVE 64
 #define LSYNC() __syncthreads()
 #define STAGE __device__ __attribute__((noinline))
 
@@ -2701,11 +2726,11 @@ template <class LdsT> STAGE void st_bitstream(const lc3d_plan* __restrict__ P, c
 #define ENC_PCM_FMT 0
 #endif
 #include "lc3_enc_wave.inc"       /* KERNEL_FN, or KERNEL_FN with _fmt */
-#if defined(LC3_ENC_VBW) && !defined(LC3_ENC_VAR) && !defined(LC3_ENC_PACKED) && !defined(LC3_PCM_FMT)   /* the per-frame-bandwidth object: besides lc3_encode_kernel_vbw only the two shape kernels */
+#ifdef LC3_TU_VBW_SHAPE
 #include "lc3_enc_rate.inc"        /* lc3_enc_shape_kernel_vbw */
 #include "lc3_enc_shapel.inc"      /* lc3_enc_shape_lane_kernel_vbw */
 #endif
-#if defined(LC3_PCM_FMT) && !defined(LC3_ENC_VAR) && !defined(LC3_ENC_VBW) && !defined(LC3_ENC_PACKED)
+#ifdef LC3_TU_FMT_FRONT
 #define FRONT_PCM_FMT 1
 #include "lc3_enc_front.inc"       /* lc3_enc_front_kernel_fmt (or _big_fmt) */
 #ifndef LC3_BIG
@@ -2714,11 +2739,8 @@ template <class LdsT> STAGE void st_bitstream(const lc3d_plan* __restrict__ P, c
 #include "lc3_enc_pre.inc"         /* lc3_enc_resample_fmt_kernel, lc3_enc_resample48f_kernel */
 #endif
 #endif
-#if !defined(LC3_ENC_VAR) && !defined(LC3_ENC_VBW) && !defined(LC3_ENC_PACKED) && !defined(LC3_PCM_FMT)   /* the per-frame-bitrate, per-frame-bandwidth, packed and PCM-format objects hold only their kernels */
-
-/* ------------------------------------------------------------------------------------------------ */
-/* C-ABI device shim (lc3_shim.h): context, uploads, launch                                          */
-/* ------------------------------------------------------------------------------------------------ */
+#ifdef LC3_TU_MAIN
+/* the pipeline's kernels; their order here is their order in the code object */
 #define FRONT_PCM_FMT 0
 #include "lc3_enc_front.inc"       /* lc3_enc_front_kernel (or _big): the stateless front, frame-parallel */
 #ifndef LC3_BIG
@@ -2732,1781 +2754,10 @@ template <class LdsT> STAGE void st_bitstream(const lc3d_plan* __restrict__ P, c
 #ifndef LC3_BIG                 /* the large-layout object holds only its kernels */
 #include "lc3_dec_parse.inc"
 #include "lc3_dec_imdct4.inc"      /* lc3_dec_imdct4_kernel: the decoder's IMDCT for N = 480, four frames per wave */
-extern "C" __global__ void lc3_encode_kernel_big(const lc3d_plan* __restrict__ P, const lc3d_chan* __restrict__ chans, float* __restrict__ state,
-                                                 const void* __restrict__ pcm, int bitdepth, int T, uint8_t* __restrict__ out, int out_stride, int ncs,
-                                                 lc3d_trace* __restrict__ trace, int* __restrict__ dump, int dstride, const float* __restrict__ y12,
-                                                 uint8_t* __restrict__ status, int dT, int dt0, const float* __restrict__ spec, const float* __restrict__ frec,
-                                                 const float* __restrict__ xnext);
-extern "C" __global__ void lc3_encode_kernel_var(const lc3d_plan* __restrict__ P, const lc3d_chan* __restrict__ chans, float* __restrict__ state,
-                                                 const void* __restrict__ pcm, int bitdepth, int T, uint8_t* __restrict__ out, int out_stride, int ncs,
-                                                 lc3d_trace* __restrict__ trace, int* __restrict__ dump, int dstride, const float* __restrict__ y12,
-                                                 uint8_t* __restrict__ status, int dT, int dt0, const float* __restrict__ spec, const float* __restrict__ frec,
-                                                 const float* __restrict__ xnext, const uint16_t* __restrict__ fsz, const lc3d_chan* __restrict__ etab);
-extern "C" __global__ void lc3_encode_kernel_big_var(const lc3d_plan* __restrict__ P, const lc3d_chan* __restrict__ chans, float* __restrict__ state,
-                                                     const void* __restrict__ pcm, int bitdepth, int T, uint8_t* __restrict__ out, int out_stride, int ncs,
-                                                     lc3d_trace* __restrict__ trace, int* __restrict__ dump, int dstride, const float* __restrict__ y12,
-                                                     uint8_t* __restrict__ status, int dT, int dt0, const float* __restrict__ spec, const float* __restrict__ frec,
-                                                     const float* __restrict__ xnext, const uint16_t* __restrict__ fsz, const lc3d_chan* __restrict__ etab);
-/* per-frame bandwidths (-DLC3_ENC_VBW objects): bwf [stream][frames of the call] in Hz, behind the arguments of the kernels they vary */
-extern "C" __global__ void lc3_encode_kernel_vbw(const lc3d_plan* __restrict__ P, const lc3d_chan* __restrict__ chans, float* __restrict__ state,
-                                                 const void* __restrict__ pcm, int bitdepth, int T, uint8_t* __restrict__ out, int out_stride, int ncs,
-                                                 lc3d_trace* __restrict__ trace, int* __restrict__ dump, int dstride, const float* __restrict__ y12,
-                                                 uint8_t* __restrict__ status, int dT, int dt0, const float* __restrict__ spec, const float* __restrict__ frec,
-                                                 const float* __restrict__ xnext, const uint16_t* __restrict__ bwf);
-extern "C" __global__ void lc3_encode_kernel_var_vbw(const lc3d_plan* __restrict__ P, const lc3d_chan* __restrict__ chans, float* __restrict__ state,
-                                                     const void* __restrict__ pcm, int bitdepth, int T, uint8_t* __restrict__ out, int out_stride, int ncs,
-                                                     lc3d_trace* __restrict__ trace, int* __restrict__ dump, int dstride, const float* __restrict__ y12,
-                                                     uint8_t* __restrict__ status, int dT, int dt0, const float* __restrict__ spec, const float* __restrict__ frec,
-                                                     const float* __restrict__ xnext, const uint16_t* __restrict__ fsz, const lc3d_chan* __restrict__ etab,
-                                                     const uint16_t* __restrict__ bwf);
-extern "C" __global__ void lc3_enc_shape_kernel_vbw(const lc3d_plan* __restrict__ P, const lc3d_chan* __restrict__ chans, int T, int tb, int nt, int fpw, int ncs,
-                                                    float* __restrict__ rows, int srow, float* __restrict__ frec, const uint16_t* __restrict__ bwf);
-extern "C" __global__ void lc3_enc_shape_lane_kernel_vbw(const lc3d_plan* __restrict__ P, const lc3d_chan* __restrict__ chans, int RT, int r0, int nt, int ncs,
-                                                         float* __restrict__ rows, int srow, float* __restrict__ frec, const uint16_t* __restrict__ bwf);
-extern "C" __global__ void lc3_enc_front_kernel_big(const lc3d_plan* __restrict__ P, const lc3d_chan* __restrict__ chans, const float* __restrict__ state, const void* __restrict__ pcm,
-                                                    int bitdepth, int T, int tb, int nt, int fpw, int ncs, float* __restrict__ spec, int srow, int RT, int r0, float* __restrict__ rec, float* __restrict__ xnext, const float* __restrict__ xprev, int xprev_stride, int do_scf);
-extern "C" __global__ void lc3_enc_shape_kernel_big(const lc3d_plan* __restrict__ P, const lc3d_chan* __restrict__ chans, int T, int tb, int nt, int fpw, int ncs,
-                                                    float* __restrict__ rows, int srow, float* __restrict__ frec);
-extern "C" __global__ void lc3_enc_tailw_kernel_big(const lc3d_plan* __restrict__ P, const lc3d_chan* __restrict__ chans, int T, int nt, int fpw, int ncs, const float* __restrict__ rows, int srow,
-                                                     const float* __restrict__ frec, uint8_t* __restrict__ out, int out_stride, uint8_t* __restrict__ status, int min_bytes);
-extern "C" __global__ void lc3_enc_rate_kernel_big(const lc3d_plan* __restrict__ P, const lc3d_chan* __restrict__ chans, float* __restrict__ state, int T, int t0, int nt, int ncs,
-                                                   const float* __restrict__ rows, int srow, float* __restrict__ frec, const float* __restrict__ xnext, int last);
-/* packed output (-DLC3_ENC_PACKED objects): each one-wave kernel above once more with the table of offsets behind its arguments */
-#define LC3_OW_ARGS const lc3d_plan* __restrict__ P, const lc3d_chan* __restrict__ chans, float* __restrict__ state, const void* __restrict__ pcm, int bitdepth, int T, \
-                    uint8_t* __restrict__ out, int out_stride, int ncs, lc3d_trace* __restrict__ trace, int* __restrict__ dump, int dstride, const float* __restrict__ y12, \
-                    uint8_t* __restrict__ status, int dT, int dt0, const float* __restrict__ spec, const float* __restrict__ frec, const float* __restrict__ xnext
-extern "C" __global__ void lc3_encode_kernel_pk(LC3_OW_ARGS, const long long* __restrict__ poff);
-extern "C" __global__ void lc3_encode_kernel_big_pk(LC3_OW_ARGS, const long long* __restrict__ poff);
-extern "C" __global__ void lc3_encode_kernel_var_pk(LC3_OW_ARGS, const uint16_t* __restrict__ fsz, const lc3d_chan* __restrict__ etab, const long long* __restrict__ poff);
-extern "C" __global__ void lc3_encode_kernel_big_var_pk(LC3_OW_ARGS, const uint16_t* __restrict__ fsz, const lc3d_chan* __restrict__ etab, const long long* __restrict__ poff);
-extern "C" __global__ void lc3_encode_kernel_vbw_pk(LC3_OW_ARGS, const uint16_t* __restrict__ bwf, const long long* __restrict__ poff);
-extern "C" __global__ void lc3_encode_kernel_var_vbw_pk(LC3_OW_ARGS, const uint16_t* __restrict__ fsz, const lc3d_chan* __restrict__ etab, const uint16_t* __restrict__ bwf,
-                                                        const long long* __restrict__ poff);
-/* ... and every one-wave kernel once more for the PCM formats beyond 16 / 24 / 32 (float samples, the two other layouts), next to its twin in the same object */
-extern "C" __global__ void lc3_encode_kernel_big_fmt(LC3_OW_ARGS);
-extern "C" __global__ void lc3_encode_kernel_var_fmt(LC3_OW_ARGS, const uint16_t* __restrict__ fsz, const lc3d_chan* __restrict__ etab);
-extern "C" __global__ void lc3_encode_kernel_big_var_fmt(LC3_OW_ARGS, const uint16_t* __restrict__ fsz, const lc3d_chan* __restrict__ etab);
-extern "C" __global__ void lc3_encode_kernel_vbw_fmt(LC3_OW_ARGS, const uint16_t* __restrict__ bwf);
-extern "C" __global__ void lc3_encode_kernel_var_vbw_fmt(LC3_OW_ARGS, const uint16_t* __restrict__ fsz, const lc3d_chan* __restrict__ etab, const uint16_t* __restrict__ bwf);
-extern "C" __global__ void lc3_encode_kernel_pk_fmt(LC3_OW_ARGS, const long long* __restrict__ poff);
-extern "C" __global__ void lc3_encode_kernel_big_pk_fmt(LC3_OW_ARGS, const long long* __restrict__ poff);
-extern "C" __global__ void lc3_encode_kernel_var_pk_fmt(LC3_OW_ARGS, const uint16_t* __restrict__ fsz, const lc3d_chan* __restrict__ etab, const long long* __restrict__ poff);
-extern "C" __global__ void lc3_encode_kernel_big_var_pk_fmt(LC3_OW_ARGS, const uint16_t* __restrict__ fsz, const lc3d_chan* __restrict__ etab, const long long* __restrict__ poff);
-extern "C" __global__ void lc3_encode_kernel_vbw_pk_fmt(LC3_OW_ARGS, const uint16_t* __restrict__ bwf, const long long* __restrict__ poff);
-extern "C" __global__ void lc3_encode_kernel_var_vbw_pk_fmt(LC3_OW_ARGS, const uint16_t* __restrict__ fsz, const lc3d_chan* __restrict__ etab, const uint16_t* __restrict__ bwf,
-                                                            const long long* __restrict__ poff);
-extern "C" __global__ void lc3_encode_kernel_fmt(LC3_OW_ARGS);
-extern "C" __global__ void lc3_enc_front_kernel_fmt(const lc3d_plan* __restrict__ P, const lc3d_chan* __restrict__ chans, const float* __restrict__ state, const void* __restrict__ pcm,
-                                                    int bitdepth, int T, int tb, int nt, int fpw, int ncs, float* __restrict__ spec, int srow, int RT, int r0, float* __restrict__ rec, float* __restrict__ xnext, const float* __restrict__ xprev, int xprev_stride, int do_scf);
-extern "C" __global__ void lc3_enc_front4_kernel_fmt(const lc3d_plan* __restrict__ P, const lc3d_chan* __restrict__ chans, const float* __restrict__ state, const void* __restrict__ pcm, int bitdepth,
-                                                     int T, int tb, int nt, int ncs, float* __restrict__ spec, int srow, int RT, int r0, float* __restrict__ rec, float* __restrict__ xnext, const float* __restrict__ xprev, int xprev_stride);
-extern "C" __global__ void lc3_enc_frontm_kernel_fmt(const lc3d_plan* __restrict__ P, const lc3d_chan* __restrict__ chans, const float* __restrict__ state, const void* __restrict__ pcm, int bitdepth,
-                                                     int T, int tb, int nt, int F, int ncs, float* __restrict__ spec, int srow, int RT, int r0, float* __restrict__ rec, float* __restrict__ xnext, const float* __restrict__ xprev, int xprev_stride);
-extern "C" __global__ void lc3_enc_resample48f_kernel(const lc3d_plan* __restrict__ P, const float* __restrict__ pcm, int fmt, int channels, int memcap, int T, int tb, int nt, int ncs, float* __restrict__ d12,
-                                                      const float* __restrict__ xprev, int xprev_stride);
-extern "C" __global__ void lc3_enc_resample_fmt_kernel(const lc3d_plan* __restrict__ P, const float* __restrict__ state, int state_words, int memcap, const void* __restrict__ pcm, int bitdepth,
-                                                       int T, int tb, int nt, int ncs, float* __restrict__ d12, const float* __restrict__ xprev, int xprev_stride);
-extern "C" __global__ void lc3_enc_front_kernel_big_fmt(const lc3d_plan* __restrict__ P, const lc3d_chan* __restrict__ chans, const float* __restrict__ state, const void* __restrict__ pcm,
-                                                        int bitdepth, int T, int tb, int nt, int fpw, int ncs, float* __restrict__ spec, int srow, int RT, int r0, float* __restrict__ rec, float* __restrict__ xnext, const float* __restrict__ xprev, int xprev_stride, int do_scf);
-#undef LC3_OW_ARGS
 #include "lc3_enc_pack.inc"
 #include "lc3_enc_snsvq.inc"
 #include "lc3_enc_shapel.inc"
 #include "lc3_enc_pre.inc"
-#define LC3D_MAX_RUNS 16
-#ifndef LC3D_SETS
-#define LC3D_SETS 3                     /* sets of hand-over buffers under the input-ready promise: that many calls may be in flight */
-#endif
-#define LC3D_AHEAD_MAX_FRAMES 256     /* lc3hip_set_input_ready: calls of up to this many frames overlap with their predecessor */
-#define LC3D_RUN_FRAMES 16            /* frames per run when consecutive calls do not overlap (measured, 4096 streams x 64 frames: 8: 58.1, 16: 64.9, 32: 62.8, 64: 58.6 Mframes/s) */
-#define LC3D_RUN_FRAMES_READY 64      /* under the input-ready promise (calls overlap, a call's own pipeline matters less: 8: 62.4, 16: 70.1, 32: 72.6, 64: 73.0) */
-/* The diagnostic switches (LC3PLUS_* environment variables), read ONCE per context in lc3hip_create / lc3hip_dec_create: no function-local statics, so two threads
- * that drive two batches never race on them, and a context's behaviour does not change under it. */
-struct lc3hip_opts {
-    int fused, no_split, streams5, run_frames, runs, ahead_max, rate_stream /* -1 rule, 0, 1 */, pre_runs, pitch2, scf_wave, front4, shape_fpw, shape_on_s, shape_wave,
-        pack_wpg, pack_stream /* -1 off (default), 0, 1 */, resample48, resample96, dec_imdct4, check_ready, tailw_bytes, dec_parse_pad_kb, pack_pad_kb, pack_split, pack_w5, fuse_vq, stream_order, stream_skip, rate_on, dec_plc_stream, shape_on_pitch, side_prio;
-};
-static int env_int(const char* name, int lo, int hi, int dflt) { const char* e = getenv(name); if (!e || !*e) return dflt; const int v = atoi(e); return v >= lo && v <= hi ? v : dflt; }
-static void read_opts(lc3hip_opts* o)
-{
-    o->fused = env_int("LC3PLUS_ENC_FUSED", 0, 1, 0);                 /* the bitstream writer inside lc3_encode_kernel */
-    o->no_split = env_int("LC3PLUS_ENC_NO_SPLIT", 0, 1, 0);           /* everything in lc3_encode_kernel */
-    o->streams5 = env_int("LC3PLUS_ENC_STREAMS", 0, 8, 0) >= 5;       /* the pitch kernel and the one-frame-per-lane kernels on streams of their own (GPU_MAX_HW_QUEUES >= 6) */
-    o->run_frames = env_int("LC3PLUS_ENC_RUN_FRAMES", 1, 1 << 20, 0);
-    o->runs = env_int("LC3PLUS_ENC_RUNS", 1, 16, 0);
-    o->ahead_max = env_int("LC3PLUS_ENC_AHEAD_MAX", 1, 1 << 20, 0);
-    o->rate_stream = env_int("LC3PLUS_ENC_RATE_STREAM", 0, 1, -1);
-    o->pre_runs = env_int("LC3PLUS_ENC_PRE_RUNS", 1, 64, 3);
-    o->pitch2 = env_int("LC3PLUS_ENC_PITCH2", 0, 1, 1);              /* 0 = one stream per wave */
-    o->scf_wave = env_int("LC3PLUS_ENC_SCF_WAVE", 0, 1, 0);          /* energies / scale factors in the front kernel */
-    o->front4 = env_int("LC3PLUS_ENC_FRONT4", 0, 1, 1);              /* 0 = the one-frame-at-a-time front for every frame length */
-    o->shape_fpw = env_int("LC3PLUS_ENC_SHAPE_FPW", 1, 64, 0);
-    o->shape_on_s = env_int("LC3PLUS_ENC_SHAPE_ON_S", 0, 1, 0);
-    o->shape_wave = env_int("LC3PLUS_ENC_SHAPE_WAVE", 0, 1, 0);      /* the wave-per-frame shape kernel */
-    o->pack_wpg = env_int("LC3PLUS_ENC_PACK_WPG", 1, 4, 4);          /* waves per workgroup of the writer */
-    o->pack_stream = env_int("LC3PLUS_ENC_PACK_STREAM", 0, 1, -1);   /* 1 = the writers of consecutive calls on two side streams (deployment switch, see enc_launch) */
-    o->resample48 = env_int("LC3PLUS_ENC_RESAMPLE48", 0, 1, 1);      /* 0 = the two-outputs-per-lane resampler for 48 kHz / 10 ms too */
-    o->resample96 = env_int("LC3PLUS_ENC_RESAMPLE96", 0, 2, 1);      /* the four-outputs-per-lane resampler for 96 kHz: 0 never, 1 standard kernel layout (2.5 ms frames), 2 every frame length */
-    /* frames of this size and more: tail + writer a frame per wave (lc3_enc_tailw_kernel).  Off (0) by default - measured, Mframes/s: c96 (320-byte frames) 32.5 without,
-     * 27.3 with; c5 (20 ... 400 bytes) 86.5 without, 68.6 / 73.6 / 78.4 from 120 / 200 / 320 bytes: the wave-parallel writer shortens the longest wave of the call but
-     * costs several times the instructions per frame, and the call is bound by instructions, not by that latency. */
-    o->tailw_bytes = env_int("LC3PLUS_ENC_TAILW_BYTES", 0, 1 << 20, 0);
-    o->dec_parse_pad_kb = env_int("LC3PLUS_DEC_PARSE_PAD_KB", 0, 60, -1);  /* LDS padding per parse workgroup = fewer resident parse waves; -1: the rule in lc3hip_dec_decode */
-    o->pack_pad_kb = env_int("LC3PLUS_ENC_PACK_PAD_KB", 0, 60, -1);      /* LDS padding per writer workgroup = fewer resident writer waves; -1: the rule in enc_launch */
-    o->pack_split = env_int("LC3PLUS_ENC_PACK_SPLIT", 0, 1, -1);        /* the writer as two kernels (head, coder); -1: the rule in enc_launch */
-    o->pack_w5 = env_int("LC3PLUS_ENC_PACK_W5", 0, 1, -1);              /* the writer under a 96-register budget; -1: the rule in enc_launch (long calls of small 10 ms frames) */
-    o->fuse_vq = env_int("LC3PLUS_ENC_FUSE_VQ", 0, 1, 0);               /* the SNS quantiser at the tail of the scale-factor kernel where no stream has attack handling */
-    o->stream_order = env_int("LC3PLUS_ENC_STREAM_ORDER", 0, 1, 1);     /* diagnostic: 0 = the pitch stream is created before the front stream */
-    o->stream_skip = env_int("LC3PLUS_ENC_STREAM_SKIP", 0, 8, 0);
-    o->rate_on = env_int("LC3PLUS_ENC_RATE_ON", 0, 1, -1);                /* a rate chain that leaves the caller's stream runs on the front stream (0) / the pitch stream (1); -1: the rule in enc_launch */
-    o->dec_plc_stream = env_int("LC3PLUS_DEC_PLC_STREAM", 0, 1, 1);        /* 0 = the decoder's concealment bookkeeping on the caller's stream (round 3) */
-    o->shape_on_pitch = env_int("LC3PLUS_ENC_SHAPE_ON_PITCH", 0, 1, -1);  /* the shape kernel on the pitch stream; -1: the rule in enc_launch (long calls of 2.5 ms high-resolution frames only) */
-    o->side_prio = env_int("LC3PLUS_ENC_SIDE_PRIO", 0, 2, 0);             /* diagnostic: 1 = the side streams at the lowest HIP stream priority, 2 = at the highest */
-    o->check_ready = env_int("LC3PLUS_CHECK_READY", 0, 1, 0);        /* debug aid for lc3plus_enc_batch_set_input_ready: refuse a call made while foreign work is pending on the caller's stream */
-    o->dec_imdct4 = env_int("LC3PLUS_DEC_IMDCT4", 0, 1, 1);          /* 0 = the one-frame-at-a-time IMDCT for N = 480 too */
-}
-/* ---- stream lifecycle: one kernel for the encoder and the decoder (include/lc3plus_batch.h: lc3plus_{enc,dec}_batch_{reset,export,import}_streams) ----
- * LC3D_SS_RESET : the listed channel-streams' state rows <- the batch's fresh-row template, and with cfg their configuration entries <- cfg [n][channels]
- * LC3D_SS_EXPORT: the listed streams' rows -> blob i (LC3D_SS_HEADER bytes of header h0..h3, then the stream's rows, channel 0 first), back to back in list order
- * LC3D_SS_IMPORT: blob i -> the rows of stream list[i] where its header equals h0..h3; status[i] = 1 and the stream untouched where it does not
- * One wave per channel row.  A row is 240 (encoder), 315 (encoder, large layout) or 614 (decoder) 16-byte chunks: four to ten dwordx4 loads and stores per
- * lane, enough to keep a wave's memory pipeline busy, and the rows of a stereo stream are independent.  A workgroup per stream would only add a barrier for
- * the header decision, which the wave of each row takes from its own lane 0.  list null: stream i (create).  Rows, template and blobs are 16-byte aligned
- * (row lengths are multiples of 4 words; the host checks a device blob's address). */
-extern "C" __global__ void __launch_bounds__(WAVE) lc3_stream_state_kernel(int mode, float* __restrict__ state, int row_words, int channels, const int* __restrict__ list,
-                                                                           int n, const float* __restrict__ tmpl, uint8_t* __restrict__ blob, uint32_t h0, uint32_t h1,
-                                                                           uint32_t h2, uint32_t h3, uint8_t* __restrict__ status, const uint32_t* __restrict__ cfg,
-                                                                           uint32_t* __restrict__ chans, int cfg_words)
-{
-    const int lane = threadIdx.x;
-    const int i = (int)(blockIdx.x / (unsigned)channels), ch = (int)(blockIdx.x % (unsigned)channels);
-    if (i >= n) return;
-    const size_t cs = (size_t)(list ? list[i] : i) * channels + ch;
-    float4* row = (float4*)(state + cs * row_words);
-    const int n4 = row_words >> 2;
-    if (mode == LC3D_SS_RESET) {
-        const float4* t4 = (const float4*)tmpl;
-        for (int k = lane; k < n4; k += WAVE) row[k] = t4[k];
-        if (cfg) for (int k = lane; k < cfg_words; k += WAVE) chans[cs * cfg_words + k] = cfg[((size_t)i * channels + ch) * cfg_words + k];
-        return;
-    }
-    uint8_t* b = blob + (size_t)i * (LC3D_SS_HEADER + (size_t)channels * row_words * 4);
-    float4* brow = (float4*)(b + LC3D_SS_HEADER + (size_t)ch * row_words * 4);
-    if (mode == LC3D_SS_EXPORT) {
-        if (ch == 0 && lane == 0) *(uint4*)b = make_uint4(h0, h1, h2, h3);
-        for (int k = lane; k < n4; k += WAVE) brow[k] = row[k];
-        return;
-    }
-    int ok = 0;                                                       /* import: lane 0 reads the header and decides, the wave follows before it writes */
-    if (lane == 0) { const uint4 h = *(const uint4*)b; ok = h.x == h0 && h.y == h1 && h.z == h2 && h.w == h3; }
-    ok = __builtin_amdgcn_readfirstlane(ok);
-    if (status && ch == 0 && lane == 0) status[i] = ok ? 0 : 1;
-    if (!ok) return;
-    for (int k = lane; k < n4; k += WAVE) row[k] = brow[k];
-}
-
-/* ---- per-frame rates and bandwidths from device memory (include/lc3plus_batch.h: lc3plus_enc_batch_encode_rates_device) ----
- * Plan kernel: one stream per lane walks its T frames in order - the carry is serial per stream, the frames of a stream are not - with the rule of
- * lc3d_enc_frame_step (lc3_plan.h).  It is the only reader of the caller's rates [stream][T] and bandwidths [stream][T] (either may be null) and writes
- * what the per-frame kernels take (fsz with rates, bwf with bandwidths: the bytes and the bandwidth in force of every stream-frame), the caller's
- * num_bytes and flags (null or [stream][T]), and each stream's carry after the call: into carry (for the next plan kernel) and into pend (for this call's
- * tail kernel).  seed (not null): start from the configuration on the device instead of from carry, after the host has changed it.  Where T is a
- * multiple of 4 and every array is aligned for it, a lane moves four frames per access (16 bytes of rates / bandwidths / sizes); T is a kernel argument,
- * so the loop is wave-uniform. */
-extern "C" __global__ void __launch_bounds__(WAVE) lc3_enc_plan_rates_kernel(lc3d_rate_rule r, const int32_t* __restrict__ rates, const int32_t* __restrict__ bws,
-                                                                             int T, int n_streams, int4* __restrict__ carry, const lc3d_chan* __restrict__ seed,
-                                                                             uint16_t* __restrict__ fsz, uint16_t* __restrict__ bwf, int32_t* __restrict__ num_bytes,
-                                                                             uint8_t* __restrict__ flags, int4* __restrict__ pend, int vec4)
-{
-    const int s = (int)(blockIdx.x * WAVE + threadIdx.x);
-    if (s >= n_streams) return;
-    int rate, bytes, bw;
-    if (seed) {
-        const lc3d_chan* ch = seed + (size_t)s * r.channels;
-        rate = ch[0].bitrate; bw = ch[0].bandwidth; bytes = ch[0].nbytes;
-        if (r.channels > 1) bytes += ch[1].nbytes;
-    } else { const int4 c = carry[s]; rate = c.x; bytes = c.y; bw = c.z; }
-    const size_t row = (size_t)s * T;
-    if (vec4) {
-        for (int t = 0; t < T; t += 4) {
-            const size_t i = row + t;
-            const int4 rv = rates ? *(const int4*)(rates + i) : make_int4(0, 0, 0, 0);
-            const int4 bv = bws ? *(const int4*)(bws + i) : make_int4(0, 0, 0, 0);
-            int f0, f1, f2, f3; int z0, z1, z2, z3; int w0, w1, w2, w3;
-            f0 = lc3d_enc_frame_step(&r, rates != nullptr, rv.x, bws != nullptr, bv.x, &rate, &bytes, &bw); z0 = bytes; w0 = bw;
-            f1 = lc3d_enc_frame_step(&r, rates != nullptr, rv.y, bws != nullptr, bv.y, &rate, &bytes, &bw); z1 = bytes; w1 = bw;
-            f2 = lc3d_enc_frame_step(&r, rates != nullptr, rv.z, bws != nullptr, bv.z, &rate, &bytes, &bw); z2 = bytes; w2 = bw;
-            f3 = lc3d_enc_frame_step(&r, rates != nullptr, rv.w, bws != nullptr, bv.w, &rate, &bytes, &bw); z3 = bytes; w3 = bw;
-            if (rates) *(uint2*)(fsz + i) = make_uint2((unsigned)z0 | (unsigned)z1 << 16, (unsigned)z2 | (unsigned)z3 << 16);
-            if (bws) *(uint2*)(bwf + i) = make_uint2((unsigned)w0 | (unsigned)w1 << 16, (unsigned)w2 | (unsigned)w3 << 16);
-            if (num_bytes) *(int4*)(num_bytes + i) = make_int4(z0, z1, z2, z3);
-            if (flags) *(unsigned*)(flags + i) = (unsigned)f0 | (unsigned)f1 << 8 | (unsigned)f2 << 16 | (unsigned)f3 << 24;
-        }
-    } else {
-        for (int t = 0; t < T; t++) {
-            const size_t i = row + t;
-            const int f = lc3d_enc_frame_step(&r, rates != nullptr, rates ? rates[i] : 0, bws != nullptr, bws ? bws[i] : 0, &rate, &bytes, &bw);
-            if (rates) fsz[i] = (uint16_t)bytes;
-            if (bws) bwf[i] = (uint16_t)bw;
-            if (num_bytes) num_bytes[i] = bytes;
-            if (flags) flags[i] = (uint8_t)f;
-        }
-    }
-    const int4 e = make_int4(rate, bytes, bw, 0);
-    carry[s] = e; pend[s] = e;
-}
-/* Packed output (lc3plus_enc_batch_encode_packed): the offsets of the call's frames, an exclusive scan of their sizes in the caller's order (stream-major:
- * j = s T + t, frame-major: j = t S + s) with 64-bit sums, as a reduce / scan / add chain of three kernels over tiles of PKS_TILE frames.  A frame's size
- * is fsz[s][t] (per-frame rates: the plan kernel's sizes), else pend[s].y (bandwidths alone: the stream's bytes the plan kernel carried), else the sum of
- * the stream's channel bytes in chans. */
-#define PKS_THREADS 256
-#define PKS_ITEMS 8
-#define PKS_TILE (PKS_THREADS * PKS_ITEMS)
-struct PkSrc { const uint16_t* fsz; const int4* pend; const lc3d_chan* chans; int channels, order, S, T; };
-__device__ __forceinline__ int pks_size(const PkSrc& q, long long j, size_t* idx)
-{
-    int s, t;
-    if (q.order) { t = (int)(j / q.S); s = (int)(j - (long long)t * q.S); } else { s = (int)(j / q.T); t = (int)(j - (long long)s * q.T); }
-    *idx = (size_t)s * q.T + t;
-    if (q.fsz) return q.fsz[*idx];
-    if (q.pend) return q.pend[s].y;
-    int nb = 0;
-    for (int c = 0; c < q.channels; c++) nb += q.chans[(size_t)s * q.channels + c].nbytes;
-    return nb;
-}
-/* exclusive scan of one value per thread over the workgroup; returns the workgroup's sum in *all */
-__device__ __forceinline__ long long pks_block_scan(long long v, long long* sh, long long* all)
-{
-    const int tid = threadIdx.x;
-    sh[tid] = v;
-    __syncthreads();
-    for (int d = 1; d < PKS_THREADS; d <<= 1) {
-        const long long a = tid >= d ? sh[tid - d] : 0;
-        __syncthreads();
-        sh[tid] += a;
-        __syncthreads();
-    }
-    const long long inc = sh[tid];
-    *all = sh[PKS_THREADS - 1];
-    __syncthreads();
-    return inc - v;
-}
-extern "C" __global__ void __launch_bounds__(PKS_THREADS) lc3_pack_sums_kernel(PkSrc q, long long n, long long* __restrict__ bsum)
-{
-    __shared__ long long sh[PKS_THREADS];
-    const long long j0 = (long long)blockIdx.x * PKS_TILE + (long long)threadIdx.x * PKS_ITEMS;
-    long long v = 0; size_t idx;
-    for (int i = 0; i < PKS_ITEMS; i++) if (j0 + i < n) v += pks_size(q, j0 + i, &idx);
-    long long all;
-    (void)pks_block_scan(v, sh, &all);
-    if (threadIdx.x == 0) bsum[blockIdx.x] = all;
-}
-/* one workgroup: the tile sums -> the tiles' bases (in place), and the call's total */
-extern "C" __global__ void __launch_bounds__(PKS_THREADS) lc3_pack_base_kernel(long long* __restrict__ bsum, long long nb, long long* __restrict__ total)
-{
-    __shared__ long long sh[PKS_THREADS];
-    long long run = 0;
-    for (long long b0 = 0; b0 < nb; b0 += PKS_THREADS) {
-        const long long b = b0 + threadIdx.x;
-        const long long v = b < nb ? bsum[b] : 0;
-        long long all;
-        const long long ex = pks_block_scan(v, sh, &all);
-        if (b < nb) bsum[b] = run + ex;
-        run += all;
-    }
-    if (threadIdx.x == 0 && total) *total = run;
-}
-/* every frame's offset: into the writers' table (-1 where the frame does not fit cap: lc3d_pack_fits) and the caller's offsets; flag bit
- * LC3D_ENC_FL_PACK_CAP beside the plan kernel's bits (plan_flags) or alone; the sizes into num_bytes when no plan kernel wrote them */
-extern "C" __global__ void __launch_bounds__(PKS_THREADS) lc3_pack_offsets_kernel(PkSrc q, long long n, const long long* __restrict__ base, long long cap,
-                                                                              long long* __restrict__ tab, long long* __restrict__ offsets,
-                                                                              uint8_t* __restrict__ flags, int plan_flags, int32_t* __restrict__ num_bytes)
-{
-    __shared__ long long sh[PKS_THREADS];
-    const long long j0 = (long long)blockIdx.x * PKS_TILE + (long long)threadIdx.x * PKS_ITEMS;
-    int sz[PKS_ITEMS]; size_t ix[PKS_ITEMS];
-    long long v = 0;
-#pragma unroll
-    for (int i = 0; i < PKS_ITEMS; i++) { sz[i] = j0 + i < n ? pks_size(q, j0 + i, &ix[i]) : 0; v += sz[i]; }
-    long long all;
-    long long off = base[blockIdx.x] + pks_block_scan(v, sh, &all);
-#pragma unroll
-    for (int i = 0; i < PKS_ITEMS; i++) {
-        if (j0 + i >= n) break;
-        const size_t k = ix[i];
-        const int fit = lc3d_pack_fits(off, sz[i], cap);
-        tab[k] = fit ? off : -1;
-        if (offsets) offsets[k] = off;
-        if (flags) flags[k] = (uint8_t)((plan_flags ? flags[k] : 0) | (fit ? 0 : LC3D_ENC_FL_PACK_CAP));
-        if (num_bytes) num_bytes[k] = sz[i];
-        off += sz[i];
-    }
-}
-
-/* Tail kernel, behind the call's last kernel: one channel-stream per lane configures its channel from the stream's carry after the call (pend), as the host
- * configures it after encode_bitrates / encode_bandwidths.  With rates (all): the channel's share of the bytes from etab (derive_chan), its payload
- * offset, the bandwidth words and the rate.  Without: the bandwidth words alone.  Either way the pending one-shot attack-detector reset is cleared: the
- * call's kernels have done it. */
-extern "C" __global__ void __launch_bounds__(WAVE) lc3_enc_rates_tail_kernel(const int4* __restrict__ pend, const lc3d_chan* __restrict__ etab, lc3d_chan* __restrict__ chans,
-                                                                             int channels, int ncs, int dms, int all)
-{
-    const int cs = (int)(blockIdx.x * WAVE + threadIdx.x);
-    if (cs >= ncs) return;
-    const int strm = cs / channels, ch = cs - strm * channels;
-    const int4 e = pend[strm];
-    lc3d_chan* d = chans + cs;
-    if (all) {
-        const int fb = e.y;
-        lc3d_chan v = etab[channels == 1 ? fb : ch ? fb >> 1 : (fb + 1) >> 1];
-        v.out_off = ch ? (fb + 1) >> 1 : 0;
-        v.bandwidth = e.z; v.bw_cut_bin = lc3d_bw_cut_bin(e.z, dms); v.bw_index = lc3d_bw_index(e.z);
-        v.reset_attack = 0; v.bitrate = e.x;
-        *d = v;
-    } else {
-        d->bandwidth = e.z; d->bw_cut_bin = lc3d_bw_cut_bin(e.z, dms); d->bw_index = lc3d_bw_index(e.z);
-        d->reset_attack = 0;
-    }
-}
-/* What a batch keeps for those calls: the fresh-row template, and LC3D_SETS staging slots (pinned host memory for the index list, configuration entries and
- * host blobs, and its device copy) used in turn, each guarded by the event recorded behind the call that used it last; ev_done: behind the last call, for
- * later calls on other streams */
-struct lc3hip_ss {
-    float* d_tmpl; int row_words;
-    uint8_t* h[LC3D_SETS]; uint8_t* d[LC3D_SETS]; size_t cap[LC3D_SETS]; hipEvent_t ev[LC3D_SETS]; int armed[LC3D_SETS], k;
-    hipEvent_t ev_prev, ev_done; int done_armed;
-};
-struct lc3hip_ctx {
-    lc3hip_opts opt;
-    int device, ncs, n_streams, channels, N, big, state_words, rs48, rs96;
-    lc3d_plan* d_plan; lc3d_chan* d_chans; float* d_state;
-    void* d_pcm; size_t pcm_cap; uint8_t* d_out; size_t out_cap;
-    lc3d_trace* d_trace; size_t trace_cap;
-    int* d_dumpv[LC3D_SETS]; size_t dump_capv[LC3D_SETS]; int hr, fused; float* d_y12[LC3D_SETS]; size_t y12_cap[LC3D_SETS];
-    uint8_t* d_status; uint8_t* d_statusv[LC3D_SETS]; size_t status_capv[LC3D_SETS]; int status_frames;      /* d_status: the set of the last call */
-    hipStream_t s_pk[2]; hipEvent_t ev_pk[2]; int pk_par;       /* the bitstream writers of consecutive calls beside each other (enc_launch) */
-    float* d_spec[LC3D_SETS]; size_t spec_cap[LC3D_SETS]; float* d_frec[LC3D_SETS]; size_t frec_cap[LC3D_SETS]; hipEvent_t ev_done[LC3D_SETS]; float* d_xnext[LC3D_SETS + 1]; int xn_par, row_par; uint8_t* h_attack; int any_attack;
-    int input_ready, ahead_ok, ahead_T, ahead_R;   /* lc3hip_set_input_ready: side kernels of a call beside the previous call's tail */   /* split path (lc3_enc_front.inc) */      /* per channel-frame status bits of the last call (LC3D_ENC_ST_*) */
-    /* host-pointer pipeline (lc3hip_encode_host): two chunk slots, each with device staging and (for pageable callers) pinned staging */
-    void* hp_dpcm[2]; void* hp_pin_in[2]; size_t hp_pcm_cap, hp_pin_in_cap;
-    hipStream_t s_h2d; hipEvent_t ev_h2d[2], ev_k[2];
-    hipStream_t s_pre, s_fr, s_pit, s_ln; hipEvent_t ev_rate; int rate_armed, mean_nbytes, min_nbytes, max_nbytes; int* h_nb; hipEvent_t ev_fork, ev_p[LC3D_MAX_RUNS], ev_f[LC3D_MAX_RUNS], ev_h[LC3D_MAX_RUNS], ev_m[LC3D_MAX_RUNS], ev_v[LC3D_MAX_RUNS];   /* side streams: pitch chain, frame-parallel front, frame-parallel tail */
-    int ylen, srow, la, len12, fm_frames; const float* last_frec; int last_frec_frames;      /* the records of the last pipelined call (lc3hip_last_records) */
-    hipStream_t stream, last_stream; hipEvent_t ev0, ev1; float last_ms;
-    hipEvent_t ev_ours, ev_now; int ours_armed;       /* LC3PLUS_CHECK_READY: the tail of the library's own work on the caller's stream */
-    /* per-frame bitrates: the configuration per channel byte count (lc3hip_upload_enc_table), and per call the stream-frame sizes, through pinned
-     * staging, in LC3D_SETS rotating buffers (a buffer is written again once the call that read it has finished: calls with sync = 0) */
-    lc3d_chan* d_etab; uint16_t* d_fsz[LC3D_SETS]; uint16_t* h_fsz[LC3D_SETS]; size_t fsz_cap; hipEvent_t ev_fsz[LC3D_SETS]; int fsz_armed[LC3D_SETS], fsz_set;
-    /* lc3hip_upload_chans_async: the configuration a per-frame-bitrate call leaves, queued on its stream behind its kernels from pinned staging; every later
-     * call waits for the copy (ev_chans) on its own stream - and for the last stream-lifecycle call (lc3hip_stream_state), which records the same event */
-    lc3d_chan* h_chans; hipEvent_t ev_chans; int chans_armed;
-    /* per-frame bandwidths: per call the words in force, through pinned staging in LC3D_SETS rotating buffers as the sizes above.  The copy of a call goes on
-     * the stream of the first kernel that reads the words (bw_to): on the pipelined path a side stream, so that a call that overlaps its predecessor does not
-     * wait for that call's tail on the caller's stream; kernels on another stream wait for ev_bwcp.  bw_src / bw_bytes / bw_on: the pending call's copy. */
-    int cfg_fresh;      /* a copy of lc3hip_upload_chans_async that the side streams are not yet ordered behind: 1 bandwidth words only, 2 more (enc_launch) */
-    uint16_t* d_bw[LC3D_SETS]; uint16_t* h_bw[LC3D_SETS]; size_t bw_cap; hipEvent_t ev_bw[LC3D_SETS]; int bw_armed[LC3D_SETS], bw_set;
-    const uint16_t* bw_src; size_t bw_bytes; hipStream_t bw_on; hipEvent_t ev_bwcp;
-    lc3hip_ss ss;                                   /* lc3hip_set_template, lc3hip_stream_state */
-    /* per-frame rates and bandwidths from device memory (lc3hip_encode_rates_device).  d_carry: each stream's rate, bytes and bandwidth in force, passed
-     * from plan kernel to plan kernel in call order (ev_plan: behind the last one, on whichever stream it ran); carry_seed: the host has written the
-     * configuration since, the next plan kernel starts from d_chans.  Per call, in LC3D_SETS rotating sets: the sizes and bandwidths the plan kernel writes
-     * and the carry after the call (for the tail kernel); a set is written again behind the event of the call that used it last, waited for on the device.
-     * pl: the plan kernel of the pending call, launched by bw_to where the first kernel that reads its words runs. */
-    int4* d_carry; int carry_seed; hipEvent_t ev_plan, ev_pset_prev; int plan_armed;
-    uint16_t* d_pfsz[LC3D_SETS]; uint16_t* d_pbw[LC3D_SETS]; int4* d_pend[LC3D_SETS]; size_t pset_frames; hipEvent_t ev_pset[LC3D_SETS]; int pset_armed[LC3D_SETS], pset;
-    int etab_attack, etab_max;                      /* some byte count of the table has attack handling; the largest channel byte count */
-    struct { int pending, k, T; const int32_t* rates; const int32_t* bws; int32_t* nb; uint8_t* fl; lc3d_rate_rule rule; } pl;
-    /* packed output (lc3hip_encode_packed), for the call being queued: the scan (pack_scan) writes the table of offsets the writers read - per plan set k
-     * with rates or bandwidths (a set is written again behind the call that used it last, as the plan buffers), one table otherwise (on the launch stream) */
-    struct { int on, order; long long cap; long long* offs; long long* total; int32_t* nb; uint8_t* fl; const long long* tab; } pk;
-    long long* d_poff[LC3D_SETS + 1]; size_t poff_cap; long long* d_pbsum; size_t pbsum_cap /* per slot */; hipEvent_t ev_scan;
-};
-
-#define LC3D_FUSED_MAX_T 8
-#define LC3D_FUSED_MAX_T_READY 5     /* measured under the promise (Mframes/s, pipelined / in-kernel writer): 4 frames 31.6 / 38, 6: 46.2 / 40, 8: 52.4 / 41 */
-#define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { fprintf(stderr, "lc3plus_hip: %s failed: %s (%s:%d)\n", #x, hipGetErrorString(e_), __FILE__, __LINE__); return 1; } } while (0)
-/* inside the create functions: release what has been allocated so far (the caller only sees ctx == NULL) */
-#define HIPCHK_OR(x, cleanup) do { hipError_t e_ = (x); if (e_ != hipSuccess) { fprintf(stderr, "lc3plus_hip: %s failed: %s (%s:%d)\n", #x, hipGetErrorString(e_), __FILE__, __LINE__); cleanup; return 1; } } while (0)
-static size_t ss_up(size_t x) { return (x + 255) & ~(size_t)255; }
-/* the template to the device, and every row of the batch reset from it (create) */
-static int ss_init(lc3hip_ss* q, int device, float* state, int row_words, int ncs, const float* tmpl)
-{
-    HIPCHK(hipSetDevice(device));
-    q->row_words = row_words;
-    HIPCHK(hipMalloc((void**)&q->d_tmpl, sizeof(float) * (size_t)row_words));
-    HIPCHK(hipMemcpy(q->d_tmpl, tmpl, sizeof(float) * (size_t)row_words, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(lc3_stream_state_kernel, dim3((unsigned)ncs), dim3(WAVE), 0, (hipStream_t)0, (int)LC3D_SS_RESET, state, row_words, 1, (const int*)nullptr, ncs,
-                       (const float*)q->d_tmpl, (uint8_t*)nullptr, 0u, 0u, 0u, 0u, (uint8_t*)nullptr, (const uint32_t*)nullptr, (uint32_t*)nullptr, 0);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize((hipStream_t)0));
-    return 0;
-}
-static void ss_free(lc3hip_ss* q)
-{
-    if (q->d_tmpl) hipFree(q->d_tmpl);
-    for (int i = 0; i < LC3D_SETS; i++) { if (q->h[i]) hipHostFree(q->h[i]); if (q->d[i]) hipFree(q->d[i]); if (q->ev[i]) hipEventDestroy(q->ev[i]); }
-    if (q->ev_prev) { hipEventDestroy(q->ev_prev); hipEventDestroy(q->ev_done); }
-}
-/* one lifecycle call on stream s, behind `last` (the stream of the batch's last call); cfg_bytes: bytes of one configuration entry */
-static int ss_run(lc3hip_ss* q, hipStream_t s, hipStream_t last, int mode, float* state, int channels, const int* list, int n, const void* cfg, int cfg_bytes,
-                  void* chans, void* blob, int blob_on_device, const uint32_t* hdr, uint8_t* status, int sync)
-{
-    if (!q->ev_prev) {
-        HIPCHK(hipEventCreateWithFlags(&q->ev_prev, hipEventDisableTiming)); HIPCHK(hipEventCreateWithFlags(&q->ev_done, hipEventDisableTiming));
-        for (int i = 0; i < LC3D_SETS; i++) HIPCHK(hipEventCreateWithFlags(&q->ev[i], hipEventDisableTiming));
-    }
-    const size_t blob_bytes = (size_t)n * (LC3D_SS_HEADER + (size_t)channels * q->row_words * 4);
-    const size_t o_cfg = ss_up(sizeof(int) * (size_t)n), n_cfg = cfg ? (size_t)n * channels * cfg_bytes : 0;
-    const size_t o_blob = o_cfg + ss_up(n_cfg), need = o_blob + (blob_on_device ? 0 : blob_bytes);
-    const int k = q->k;
-    if (q->armed[k]) { HIPCHK(hipEventSynchronize(q->ev[k])); q->armed[k] = 0; }      /* the call LC3D_SETS back has read this slot */
-    if (q->cap[k] < need) {
-        if (q->h[k]) HIPCHK(hipHostFree(q->h[k])); if (q->d[k]) HIPCHK(hipFree(q->d[k]));
-        q->h[k] = nullptr; q->d[k] = nullptr; q->cap[k] = 0;
-        const size_t cap = need < (64u << 10) ? (64u << 10) : need;
-        HIPCHK(hipHostMalloc((void**)&q->h[k], cap, hipHostMallocDefault)); HIPCHK(hipMalloc((void**)&q->d[k], cap));
-        q->cap[k] = cap;
-    }
-    memcpy(q->h[k], list, sizeof(int) * (size_t)n);
-    if (cfg) memcpy(q->h[k] + o_cfg, cfg, n_cfg);
-    if (mode == LC3D_SS_IMPORT && !blob_on_device) memcpy(q->h[k] + o_blob, blob, blob_bytes);
-    if (last && last != s) { HIPCHK(hipEventRecord(q->ev_prev, last)); HIPCHK(hipStreamWaitEvent(s, q->ev_prev, 0)); }
-    HIPCHK(hipMemcpyAsync(q->d[k], q->h[k], mode == LC3D_SS_IMPORT && !blob_on_device ? o_blob + blob_bytes : o_blob, hipMemcpyHostToDevice, s));
-    uint8_t* dblob = blob_on_device ? (uint8_t*)blob : q->d[k] + o_blob;
-    hipLaunchKernelGGL(lc3_stream_state_kernel, dim3((unsigned)((size_t)n * channels)), dim3(WAVE), 0, s, mode, state, q->row_words, channels, (const int*)q->d[k], n,
-                       (const float*)q->d_tmpl, dblob, hdr[0], hdr[1], hdr[2], hdr[3], blob_on_device ? status : (uint8_t*)nullptr,
-                       (const uint32_t*)(cfg ? q->d[k] + o_cfg : nullptr), (uint32_t*)chans, cfg_bytes / 4);
-    HIPCHK(hipGetLastError());
-    if (mode == LC3D_SS_EXPORT && !blob_on_device) HIPCHK(hipMemcpyAsync(q->h[k] + o_blob, dblob, blob_bytes, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipEventRecord(q->ev[k], s)); q->armed[k] = 1; q->k = (k + 1) % LC3D_SETS;
-    HIPCHK(hipEventRecord(q->ev_done, s)); q->done_armed = 1;
-    if (mode == LC3D_SS_EXPORT && !blob_on_device) { HIPCHK(hipStreamSynchronize(s)); memcpy(blob, q->h[k] + o_blob, blob_bytes); }
-    else if (sync) HIPCHK(hipStreamSynchronize(s));
-    return 0;
-}
-
-
-/* test hook (tests/test_gpu_parity.py::test_device_fastmath_equals_host): lc3_fastmath.h as the kernels evaluate it, over an array.  kind 0 log2, 1 log10, 2 2^x */
-extern "C" __global__ void lc3_fastmath_test_kernel(int kind, const float* __restrict__ x, float* __restrict__ y, long long n)
-{
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) y[i] = kind == 0 ? m_log2f(x[i]) : kind == 1 ? m_log10f(x[i]) : m_pow2f(x[i]);
-}
-extern "C" int lc3hip_test_fastmath(int kind, const float* x_host, float* y_host, long long n)
-{
-    float *dx = nullptr, *dy = nullptr;
-    HIPCHK(hipMalloc((void**)&dx, (size_t)n * 4)); HIPCHK(hipMalloc((void**)&dy, (size_t)n * 4));
-    HIPCHK(hipMemcpy(dx, x_host, (size_t)n * 4, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(lc3_fastmath_test_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, kind, dx, dy, n);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpy(y_host, dy, (size_t)n * 4, hipMemcpyDeviceToHost));
-    HIPCHK(hipFree(dx)); HIPCHK(hipFree(dy));
-    return 0;
-}
-extern "C" int lc3hip_destroy(void* ctx);
-extern "C" int lc3hip_create(void** out_ctx, const lc3d_plan* plan, int n_streams, int device)
-{
-    int ndev = 0;
-    *out_ctx = nullptr;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { fprintf(stderr, "lc3plus_hip: no HIP device available (this engine has no CPU fallback)\n"); return 1; }
-    lc3hip_ctx* c = (lc3hip_ctx*)calloc(1, sizeof *c);
-    if (!c) return 1;
-    if (device < 0) { if (hipGetDevice(&device) != hipSuccess) device = 0; }
-    c->device = device;
-    HIPCHK_OR(hipSetDevice(device), free(c));
-    c->n_streams = n_streams; c->channels = plan->channels; c->ncs = n_streams * plan->channels; c->N = plan->N;
-    c->big = LC3D_LAYOUT_BIG(plan->N, plan->la);
-    c->hr = plan->hrmode; c->ylen = plan->ylen; c->la = plan->la; c->len12 = plan->len12;
-    c->fm_frames = (!c->big && plan->pfa_nst >= 2 && plan->pfa_rad[0] <= 8 && plan->pfa_rad[1] <= 8 && (plan->pfa_nst < 3 || plan->pfa_rad[2] <= 8) && plan->N <= 240) ? (plan->N > 120 ? FM_F240 : 8) : 0;      /* lc3_enc_frontm_kernel */
-    c->srow = LC3D_SROW(plan->ylen);
-    c->rs48 = plan->N == 480 && plan->rs_stride == 4 && plan->n12 == 128 && plan->rs_mem_in_len == 60;      /* lc3_enc_resample48_kernel */
-    read_opts(&c->opt);
-    if (!c->opt.resample48) c->rs48 = 0;
-    /* lc3_enc_resample96_kernel_n*: 96 kHz.  By default for the standard kernel layout only (2.5 ms frames): c4 125.0 -> 137.0 Mframes/s; beside the large-layout kernels its
-     * 256 registers per wave cost more than its shorter run gives (c96 36.6 -> 33.4) */
-    c->rs96 = c->opt.resample96 && plan->rs_stride == 2 && plan->rs_mem_in_len == 120 && (plan->N == 960 || plan->N == 480 || plan->N == 240) && plan->n12 * 15 == plan->N * 2
-              && (!c->big || c->opt.resample96 == 2);
-    c->fused = c->opt.fused;
-    c->state_words = LC3D_STATE_WORDS(c->big ? LC3D_MEMCAP_BIG : LC3D_MEMCAP_STD);
-    HIPCHK_OR(hipMalloc((void**)&c->d_plan, sizeof(lc3d_plan)), lc3hip_destroy(c));
-    HIPCHK_OR(hipMemcpy(c->d_plan, plan, sizeof(lc3d_plan), hipMemcpyHostToDevice), lc3hip_destroy(c));
-    HIPCHK_OR(hipMalloc((void**)&c->d_chans, sizeof(lc3d_chan) * c->ncs), lc3hip_destroy(c));
-    HIPCHK_OR(hipMalloc((void**)&c->d_state, sizeof(float) * c->state_words * (size_t)c->ncs), lc3hip_destroy(c));
-    /* the library's own launch stream is created when a call first needs it (a caller that brings its stream never does): HIP maps streams
-     * onto a few hardware queues, and the pipelined path wants its three side streams on queues of their own */
-    HIPCHK_OR(hipEventCreate(&c->ev0), lc3hip_destroy(c)); HIPCHK_OR(hipEventCreate(&c->ev1), lc3hip_destroy(c));
-    *out_ctx = c;
-    return 0;
-}
-
-extern "C" int lc3hip_set_template(void* ctx, const float* tmpl)
-{
-    lc3hip_ctx* c = (lc3hip_ctx*)ctx;
-    if (ss_init(&c->ss, c->device, c->d_state, c->state_words, c->ncs, tmpl)) return 1;
-    c->ahead_ok = 0;                       /* the MDCT memory is in the state again, not in the hand-over of a previous call */
-    return 0;
-}
-
-static int chans_host_side(lc3hip_ctx* c, const lc3d_chan* chans, int first, int count);
-extern "C" int lc3hip_upload_chans_async(void* ctx, const lc3d_chan* chans, int first, int count, void* hip_stream, int bw_only)
-{
-    lc3hip_ctx* c = (lc3hip_ctx*)ctx;
-    c->cfg_fresh = bw_only ? 1 : 2;
-    HIPCHK(hipSetDevice(c->device));
-    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : c->stream;
-    if (!c->h_chans) HIPCHK(hipHostMalloc((void**)&c->h_chans, sizeof(lc3d_chan) * (size_t)c->ncs, hipHostMallocDefault));
-    if (!c->ev_chans) HIPCHK(hipEventCreateWithFlags(&c->ev_chans, hipEventDisableTiming));
-    if (c->chans_armed) HIPCHK(hipEventSynchronize(c->ev_chans));      /* the staging of the previous copy is free */
-    memcpy(c->h_chans + first, chans, sizeof(lc3d_chan) * (size_t)count);
-    HIPCHK(hipMemcpyAsync(c->d_chans + first, c->h_chans + first, sizeof(lc3d_chan) * (size_t)count, hipMemcpyHostToDevice, s));
-    c->carry_seed = 1;
-    HIPCHK(hipEventRecord(c->ev_chans, s)); c->chans_armed = 1;
-    if (c->opt.check_ready && c->ev_ours) { HIPCHK(hipEventRecord(c->ev_ours, s)); c->ours_armed = 1; }      /* the copy is the library's own work */
-    return chans_host_side(c, chans, first, count);
-}
-extern "C" int lc3hip_upload_chans(void* ctx, const lc3d_chan* chans, int first, int count)
-{
-    lc3hip_ctx* c = (lc3hip_ctx*)ctx;
-    HIPCHK(hipSetDevice(c->device));
-    /* a launch with sync = 0 may still be reading d_chans, possibly on a caller's non-blocking stream that a plain hipMemcpy does not
-     * wait for: drain the stream the last launch went to first */
-    if (c->last_stream) { HIPCHK(hipStreamSynchronize(c->last_stream)); c->last_stream = nullptr; }
-    if (c->chans_armed) HIPCHK(hipEventSynchronize(c->ev_chans));      /* a queued copy of lc3hip_upload_chans_async lands first */
-    HIPCHK(hipMemcpy(c->d_chans + first, chans, sizeof(lc3d_chan) * count, hipMemcpyHostToDevice));
-    c->carry_seed = 1;
-    return chans_host_side(c, chans, first, count);
-}
-/* what the launch decisions read of the configuration, on the host: channel-streams first ... first + count - 1, or with list the channels of streams list[0 .. count / channels - 1] */
-static int chans_host_side_list(lc3hip_ctx* c, const lc3d_chan* chans, int first, int count, const int* list)
-{
-    if (!c->h_attack) { c->h_attack = (uint8_t*)calloc((size_t)c->ncs, 1); if (!c->h_attack) return 1; }
-    if (!c->h_nb) { c->h_nb = (int*)calloc((size_t)c->ncs, sizeof(int)); if (!c->h_nb) return 1; }
-    for (int i = 0; i < count; i++) {
-        const int cs = list ? list[i / c->channels] * c->channels + i % c->channels : first + i;
-        c->h_attack[cs] = chans[i].attack_handling != 0 || chans[i].reset_attack != 0;     /* streams with attack handling need lc3_enc_attack_kernel; a pending reset too */
-        c->h_nb[cs] = chans[i].nbytes;
-    }
-    c->any_attack = 0;
-    for (int i = 0; i < c->ncs; i++) c->any_attack |= c->h_attack[i];
-    /* mean frame size: decides where the rate chain runs (enc_launch) */
-    { long long sum = 0; int mn = 1 << 30, mx = 0; for (int i = 0; i < c->ncs; i++) { sum += c->h_nb[i]; if (c->h_nb[i] < mn) mn = c->h_nb[i]; if (c->h_nb[i] > mx) mx = c->h_nb[i]; }
-      c->mean_nbytes = (int)(sum / (c->ncs > 0 ? c->ncs : 1)); c->min_nbytes = mn; c->max_nbytes = mx; }
-    return 0;
-}
-static int chans_host_side(lc3hip_ctx* c, const lc3d_chan* chans, int first, int count) { return chans_host_side_list(c, chans, first, count, nullptr); }
-
-/* the kernels of one call (or of one run of frames of a call) on stream s, PCM and output in device memory.  n_frames frames from
- * dpcm [stream][n_frames][channel][N]; the hand-over records and status bytes are rows of dT frames per channel-stream in which this
- * launch fills frames dt0 ... dt0 + n_frames - 1; with `pack` the bitstream writer then runs over all dT frames into dout [stream][dT][out_stride]. */
-#ifdef LC3_DUP
-/* diagnostic build (tools/variants.sh dup "-DLC3_DUP", tools/dup_run.sh): LC3PLUS_ENC_DUP=<letters> launches the named kernels of the pipelined
- * path twice (r resampler, h HP50, p pitch, f front, v quantiser, s rate, k pack) - what a kernel costs in the co-resident mix.  Output is
- * wrong for the kernels that carry state (h, p, s); never built into the product library. */
-static int dup_of(char k) { static const char* e = nullptr; static bool rd = false; if (!rd) { e = getenv("LC3PLUS_ENC_DUP"); rd = true; } return e && strchr(e, k) ? 2 : 1; }
-#define DUPL(k) for (int dup_ = 0; dup_ < dup_of(k); dup_++)
-#else
-#define DUPL(k)
-#endif
-/* the 12.8 kHz polyphase FIR of frames hb ... hb + hn - 1 of every channel-stream on stream st: four outputs per lane where the shape allows */
-static void launch_resample(lc3hip_ctx* c, hipStream_t st, const void* dpcm, int bitdepth, int n_frames, int hb, int hn, int mc, float* dy12, const float* xprev, int xprev_stride)
-{
-    const unsigned pruns = (unsigned)((hn + PRE_FPW - 1) / PRE_FPW);
-    if (c->rs48 && bitdepth == 16 && (((size_t)dpcm) & 15) == 0)
-        hipLaunchKernelGGL(lc3_enc_resample48_kernel, dim3((unsigned)c->ncs * pruns), dim3(WAVE), 0, st, c->d_plan, (const int16_t*)dpcm, c->channels, mc, n_frames, hb, hn, c->ncs, dy12, xprev, xprev_stride);
-    else if (c->rs48 && (bitdepth & (LC3D_PCM_TYPE_MASK | LC3D_PCM_INTERLEAVED)) == LC3D_PCM_FLOAT32 && (((size_t)dpcm) & 15) == 0)   /* frames of 480 x 4 bytes: every one 16-byte aligned */
-        hipLaunchKernelGGL(lc3_enc_resample48f_kernel, dim3((unsigned)c->ncs * pruns), dim3(WAVE), 0, st, c->d_plan, (const float*)dpcm, bitdepth, c->channels, mc, n_frames, hb, hn, c->ncs, dy12, xprev, xprev_stride);
-    else if (c->rs96 && bitdepth == 16 && (((size_t)dpcm) & 15) == 0) {
-        auto k = c->N == 960 ? lc3_enc_resample96_kernel_n960 : c->N == 480 ? lc3_enc_resample96_kernel_n480 : lc3_enc_resample96_kernel_n240;
-        const int fpb = (1920 / c->N) * PRE96_ITERS;                       /* frames per workgroup: PRE96_ITERS steps of 1 920 samples */
-        hipLaunchKernelGGL(k, dim3((unsigned)c->ncs * (unsigned)((hn + fpb - 1) / fpb)), dim3(WAVE), 0, st, c->d_plan, (const int16_t*)dpcm, c->channels, mc, n_frames, hb, hn, c->ncs, dy12, xprev, xprev_stride);
-    }
-    else
-        hipLaunchKernelGGL((bitdepth == 16 || bitdepth == 24 || bitdepth == 32) ? lc3_enc_resample_kernel : lc3_enc_resample_fmt_kernel, dim3((unsigned)c->ncs * pruns), dim3(WAVE), 0, st, c->d_plan, c->d_state, c->state_words, mc, dpcm, bitdepth, n_frames, hb, hn, c->ncs, dy12, xprev, xprev_stride);
-}
-static int bw_to(lc3hip_ctx* c, hipStream_t st);
-static int enc_launch(lc3hip_ctx* c, const void* dpcm, int bitdepth, int n_frames, uint8_t* dout, int out_stride, hipStream_t s, lc3d_trace* dtr,
-                      int dT, int dt0, bool pack, const uint16_t* dfsz /* per-frame bitrates: [stream][dT] stream-frame bytes, or null */,
-                      const uint16_t* dbw /* per-frame bandwidths: [stream][dT] Hz in force (stage_bw), or null; the path is the one without them */)
-{
-    /* two kernels: lc3_encode_kernel (one wave per channel-stream, frames in order) leaves each frame's parameters and quantised
-     * spectrum in a record; lc3_enc_pack_kernel (one channel-frame per lane, any frame size) writes the bytes.  With stage traces,
-     * or with LC3PLUS_ENC_FUSED=1 (diagnostic), the first kernel writes the bytes itself. */
-    /* A call of very few frames is latency bound and the one-frame-per-lane writer is the longest chain in it (~0.19 ms for a frame of
-     * 80 bytes whatever the batch size): up to LC3D_FUSED_MAX_T frames per call the wave-parallel writer inside the first kernel
-     * (st_bitstream, ~6 us per frame) is used instead - the single-stream lc3_enc_* API and T = 1 batches live here. */
-    int* ddump = nullptr; int dstride = 0;
-    const int set = c->input_ready ? c->row_par : 0;        /* the set of hand-over buffers of this call (rows, records, writer scratch, status bytes) */
-    /* with the input-ready promise consecutive short calls overlap on the pipelined path, which then wins from 4 frames per call
-     * (4096 streams, Mframes/s pipelined / in-kernel writer: 3 frames 31.9 / 36.3, 4: 39.8 / 38.0, 6: 48.6 / 40.2, 8: 53.9 / 41.2; without the
-     * promise 8: 40.2 / 41.2) */
-    /* (per-frame bitrates: always - lc3_encode_kernel_var reloads the configuration per frame; it is the only kernel that does) */
-    /* the PCM formats beyond the reference's three have kernels of their own (_fmt) wherever the load could not be added without moving the registers of the kernel that is there */
-    const bool fmt_plain = bitdepth == 16 || bitdepth == 24 || bitdepth == 32;
-    const bool in_kernel_writer = dtr || c->fused || dfsz || dT <= (c->input_ready ? LC3D_FUSED_MAX_T_READY : LC3D_FUSED_MAX_T);
-    if (!in_kernel_writer) {
-        dstride = PK_STRIDE(c->N, c->hr);
-        const size_t need = (size_t)c->ncs * dT * dstride;
-        /* under the input-ready promise every set is sized on the first call that needs it: no allocation inside a later (timed, overlapped) call */
-        for (int i = c->input_ready ? 0 : set; i < (c->input_ready ? LC3D_SETS : set + 1); i++)
-            if (c->dump_capv[i] < need) { if (c->d_dumpv[i]) HIPCHK(hipFree(c->d_dumpv[i])); c->d_dumpv[i] = nullptr; c->dump_capv[i] = 0; HIPCHK(hipMalloc((void**)&c->d_dumpv[i], need * sizeof(int))); c->dump_capv[i] = need; }
-        ddump = c->d_dumpv[set];
-    }
-    /* ahead of it: the 12.8 kHz resampler of all frames at once and its HP50 recurrence one stream per lane (lc3_enc_pre.inc) */
-    float* dy12 = nullptr;
-    if (!dtr && !c->fused) {
-        const size_t need = (size_t)c->ncs * n_frames * 128;
-        const int yb = c->input_ready ? c->row_par : 0;      /* two buffers under the input-ready promise: the next call's resampler may run beside this call's pitch kernel */
-        for (int i = c->input_ready ? 0 : yb; i < (c->input_ready ? LC3D_SETS : yb + 1); i++)
-            if (c->y12_cap[i] < need) { if (c->d_y12[i]) HIPCHK(hipFree(c->d_y12[i])); c->d_y12[i] = nullptr; c->y12_cap[i] = 0; HIPCHK(hipMalloc((void**)&c->d_y12[i], need * sizeof(float))); c->y12_cap[i] = need; }
-        dy12 = c->d_y12[yb];
-    }
-    const bool split = dy12 && ddump && !c->opt.no_split;
-    if (dt0 == 0) {   /* per channel-frame status bits (LC3D_ENC_ST_*), cleared per call: by the stream that runs the kernel that sets them (the writer's, on the pipelined path) */
-        const size_t need = (size_t)c->ncs * dT;
-        for (int i = c->input_ready ? 0 : set; i < (c->input_ready ? LC3D_SETS : set + 1); i++)
-            if (c->status_capv[i] < need) { if (c->d_statusv[i]) HIPCHK(hipFree(c->d_statusv[i])); c->d_statusv[i] = nullptr; c->status_capv[i] = 0; HIPCHK(hipMalloc((void**)&c->d_statusv[i], need)); c->status_capv[i] = need; }
-        c->d_status = c->d_statusv[set];
-        if (!split) HIPCHK(hipMemsetAsync(c->d_status, 0, need, s));
-        c->status_frames = dT;
-    }
-    bool rate_on_side = false;
-    float* rows_for_pack = nullptr; const float* frec_for_pack = nullptr;      /* pipelined path: the bitstream writer starts from the shaped spectra (frame-parallel tail, one frame per lane) */
-    const int mc = c->big ? LC3D_MEMCAP_BIG : LC3D_MEMCAP_STD;
-    if (!split) {
-        c->ahead_ok = 0; c->last_frec = nullptr; c->last_frec_frames = 0; c->cfg_fresh = 0;
-        /* everything in lc3_encode_kernel (traced, diagnostic and very short launches), behind the 12.8 kHz pre-kernels when they apply */
-        if (dy12) {
-            launch_resample(c, s, dpcm, bitdepth, n_frames, 0, n_frames, mc, dy12, c->d_state + LC3D_ST_XPREV, c->state_words);
-            hipLaunchKernelGGL(lc3_enc_hp50_kernel, dim3((unsigned)((c->ncs + WAVE - 1) / WAVE)), dim3(WAVE), 0, s, c->d_plan, c->d_state, c->state_words, LC3D_ST_SCAL(mc), n_frames, 0, n_frames, c->ncs, dy12);
-            HIPCHK(hipGetLastError());
-        }
-        if (dbw && bw_to(c, s)) return 1;
-#define OWK(k) (fmt_plain ? k : k##_fmt)
-        const long long* pt = c->pk.on ? c->pk.tab : nullptr;         /* packed output: the _pk kernels, frames at the offsets of the call's table */
-        if (pt) {
-            if (dfsz && dbw) hipLaunchKernelGGL(OWK(lc3_encode_kernel_var_vbw_pk), dim3(c->ncs), dim3(WAVE), 0, s, c->d_plan, c->d_chans, c->d_state, dpcm, bitdepth, n_frames,
-                                                dout, 0, c->ncs, dtr, ddump, dstride, dy12, c->d_status, dT, dt0, (const float*)nullptr, (const float*)nullptr,
-                                                (const float*)nullptr, dfsz, (const lc3d_chan*)c->d_etab, dbw, pt);
-            else if (dfsz && c->big) hipLaunchKernelGGL(OWK(lc3_encode_kernel_big_var_pk), dim3(c->ncs), dim3(WAVE), 0, s, c->d_plan, c->d_chans, c->d_state, dpcm, bitdepth, n_frames,
-                                                   dout, 0, c->ncs, dtr, ddump, dstride, dy12, c->d_status, dT, dt0, (const float*)nullptr, (const float*)nullptr,
-                                                   (const float*)nullptr, dfsz, (const lc3d_chan*)c->d_etab, pt);
-            else if (dfsz) hipLaunchKernelGGL(OWK(lc3_encode_kernel_var_pk), dim3(c->ncs), dim3(WAVE), 0, s, c->d_plan, c->d_chans, c->d_state, dpcm, bitdepth, n_frames,
-                                              dout, 0, c->ncs, dtr, ddump, dstride, dy12, c->d_status, dT, dt0, (const float*)nullptr, (const float*)nullptr,
-                                              (const float*)nullptr, dfsz, (const lc3d_chan*)c->d_etab, pt);
-            else if (c->big) hipLaunchKernelGGL(OWK(lc3_encode_kernel_big_pk), dim3(c->ncs), dim3(WAVE), 0, s, c->d_plan, c->d_chans, c->d_state, dpcm, bitdepth, n_frames,
-                                           dout, 0, c->ncs, dtr, ddump, dstride, dy12, c->d_status, dT, dt0, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, pt);
-            else if (dbw) hipLaunchKernelGGL(OWK(lc3_encode_kernel_vbw_pk), dim3(c->ncs), dim3(WAVE), 0, s, c->d_plan, c->d_chans, c->d_state, dpcm, bitdepth, n_frames,
-                                             dout, 0, c->ncs, dtr, ddump, dstride, dy12, c->d_status, dT, dt0, (const float*)nullptr, (const float*)nullptr,
-                                             (const float*)nullptr, dbw, pt);
-            else hipLaunchKernelGGL(OWK(lc3_encode_kernel_pk), dim3(c->ncs), dim3(WAVE), 0, s, c->d_plan, c->d_chans, c->d_state, dpcm, bitdepth, n_frames,
-                                    dout, 0, c->ncs, dtr, ddump, dstride, dy12, c->d_status, dT, dt0, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, pt);
-        } else
-        if (dfsz && dbw) hipLaunchKernelGGL(OWK(lc3_encode_kernel_var_vbw), dim3(c->ncs), dim3(WAVE), 0, s, c->d_plan, c->d_chans, c->d_state, dpcm, bitdepth, n_frames,
-                                            dout, out_stride, c->ncs, dtr, ddump, dstride, dy12, c->d_status, dT, dt0, (const float*)nullptr, (const float*)nullptr,
-                                            (const float*)nullptr, dfsz, (const lc3d_chan*)c->d_etab, dbw);
-        else if (dfsz && c->big) hipLaunchKernelGGL(OWK(lc3_encode_kernel_big_var), dim3(c->ncs), dim3(WAVE), 0, s, c->d_plan, c->d_chans, c->d_state, dpcm, bitdepth, n_frames,
-                                               dout, out_stride, c->ncs, dtr, ddump, dstride, dy12, c->d_status, dT, dt0, (const float*)nullptr, (const float*)nullptr,
-                                               (const float*)nullptr, dfsz, (const lc3d_chan*)c->d_etab);
-        else if (dfsz) hipLaunchKernelGGL(OWK(lc3_encode_kernel_var), dim3(c->ncs), dim3(WAVE), 0, s, c->d_plan, c->d_chans, c->d_state, dpcm, bitdepth, n_frames,
-                                          dout, out_stride, c->ncs, dtr, ddump, dstride, dy12, c->d_status, dT, dt0, (const float*)nullptr, (const float*)nullptr,
-                                          (const float*)nullptr, dfsz, (const lc3d_chan*)c->d_etab);
-        else if (c->big) hipLaunchKernelGGL(OWK(lc3_encode_kernel_big), dim3(c->ncs), dim3(WAVE), 0, s, c->d_plan, c->d_chans, c->d_state, dpcm, bitdepth, n_frames,
-                                       dout, out_stride, c->ncs, dtr, ddump, dstride, dy12, c->d_status, dT, dt0, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr);
-        else if (dbw) hipLaunchKernelGGL(OWK(lc3_encode_kernel_vbw), dim3(c->ncs), dim3(WAVE), 0, s, c->d_plan, c->d_chans, c->d_state, dpcm, bitdepth, n_frames,
-                                         dout, out_stride, c->ncs, dtr, ddump, dstride, dy12, c->d_status, dT, dt0, (const float*)nullptr, (const float*)nullptr,
-                                         (const float*)nullptr, dbw);
-        else hipLaunchKernelGGL(OWK(lc3_encode_kernel), dim3(c->ncs), dim3(WAVE), 0, s, c->d_plan, c->d_chans, c->d_state, dpcm, bitdepth, n_frames,
-                                dout, out_stride, c->ncs, dtr, ddump, dstride, dy12, c->d_status, dT, dt0, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr);
-    } else {
-        /* The pipelined path.  Per run of frames: on one side stream the pitch chain (resampler per frame, HP50 one stream per lane, OLPA +
-         * LTPF one stream per wave); on another the frame-parallel front (MDCT ... scale factors), the attack decision and the SNS quantiser
-         * (one frame per lane); on the launch stream the shape kernel (SNS shaping, TNS, log energies: frame-parallel) and behind it the rate
-         * chain (lc3_enc_rate_kernel: rate loop, bisection, first quantisation), which also waits for the pitch chain.  Everything behind the
-         * chain - gain adjustment, second quantisation, noise level, residual - is frame-parallel again and runs one frame per lane at the head
-         * of the bitstream writer, once per call.  The side kernels of run k+1 are resident beside the launch stream's kernels of run k. */
-        /* spectrum rows and records of all dT frames of the call (a call through host pointers comes in pieces: rows dt0 ...): two sets under
-         * the input-ready promise (consecutive calls overlap: the side kernels of a call write one set while the bitstream writer of the call
-         * before still reads the other), one otherwise */
-        const int hb_ = set;
-        const size_t ns = (size_t)c->ncs * dT * c->srow, nr = (size_t)c->ncs * dT * FR_WORDS;
-        for (int i = c->input_ready ? 0 : hb_; i < (c->input_ready ? LC3D_SETS : hb_ + 1); i++) {
-            if (c->spec_cap[i] < ns) { if (c->d_spec[i]) HIPCHK(hipFree(c->d_spec[i])); c->d_spec[i] = nullptr; c->spec_cap[i] = 0; HIPCHK(hipMalloc((void**)&c->d_spec[i], ns * sizeof(float))); c->spec_cap[i] = ns; }
-            if (c->frec_cap[i] < nr) { if (c->d_frec[i]) HIPCHK(hipFree(c->d_frec[i])); c->d_frec[i] = nullptr; c->frec_cap[i] = 0; HIPCHK(hipMalloc((void**)&c->d_frec[i], nr * sizeof(float))); c->frec_cap[i] = nr; }
-        }
-        for (int i = 0; i < LC3D_SETS + 1; i++) if (!c->d_xnext[i]) HIPCHK(hipMalloc((void**)&c->d_xnext[i], (size_t)c->ncs * mc * sizeof(float)));
-        if (!c->s_pre) {
-            {   /* Two side streams, no third.  HIP (four hardware queues by default) gave the FIRST side stream a batch creates a queue of its own and put all later ones
-                 * together on another - and kernels of two streams on one queue run one after the other.  Round 3's separate rate stream therefore shared the front stream's
-                 * queue (timeline of c5: 2.9 of the call's 3.0 ms on that one queue).  A rate chain that leaves the caller's stream now runs ON one of the two side streams,
-                 * chosen per call (below): the same packets in the same queue, by choice instead of by creation order. */
-                for (int i = 0; i < c->opt.stream_skip; i++) { hipStream_t d; HIPCHK(hipStreamCreateWithFlags(&d, hipStreamNonBlocking)); }      /* diagnostic: shifts the assignment (never destroyed) */
-                int plo = 0, phi = 0; (void)hipDeviceGetStreamPriorityRange(&plo, &phi);       /* least, greatest */
-                const int prio = c->opt.side_prio == 1 ? plo : c->opt.side_prio == 2 ? phi : 0;
-                if (c->opt.stream_order) { HIPCHK(hipStreamCreateWithPriority(&c->s_fr, hipStreamNonBlocking, prio)); HIPCHK(hipStreamCreateWithPriority(&c->s_pre, hipStreamNonBlocking, prio)); }
-                else { HIPCHK(hipStreamCreateWithPriority(&c->s_pre, hipStreamNonBlocking, prio)); HIPCHK(hipStreamCreateWithPriority(&c->s_fr, hipStreamNonBlocking, prio)); }
-            }
-            /* LC3PLUS_ENC_STREAMS=5: the pitch kernel and the one-frame-per-lane kernels on streams of their own (pays only where the HIP runtime has
-             * hardware queues for them: GPU_MAX_HW_QUEUES >= 6) */
-            { c->s_pit = c->s_pre; c->s_ln = c->s_fr;
-              if (c->opt.streams5) { HIPCHK(hipStreamCreateWithFlags(&c->s_pit, hipStreamNonBlocking)); HIPCHK(hipStreamCreateWithFlags(&c->s_ln, hipStreamNonBlocking)); } }
-            for (int i = 0; i < LC3D_MAX_RUNS; i++) { HIPCHK(hipEventCreateWithFlags(&c->ev_h[i], hipEventDisableTiming)); HIPCHK(hipEventCreateWithFlags(&c->ev_m[i], hipEventDisableTiming)); HIPCHK(hipEventCreateWithFlags(&c->ev_v[i], hipEventDisableTiming)); }
-            for (int i = 0; i < 2; i++) { c->s_pk[i] = NULL; HIPCHK(hipEventCreateWithFlags(&c->ev_pk[i], hipEventDisableTiming)); }
-            HIPCHK(hipEventCreateWithFlags(&c->ev_rate, hipEventDisableTiming));
-            HIPCHK(hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
-            for (int i = 0; i < LC3D_SETS; i++) HIPCHK(hipEventCreateWithFlags(&c->ev_done[i], hipEventDisableTiming));
-            for (int i = 0; i < LC3D_MAX_RUNS; i++) { HIPCHK(hipEventCreateWithFlags(&c->ev_p[i], hipEventDisableTiming)); HIPCHK(hipEventCreateWithFlags(&c->ev_f[i], hipEventDisableTiming)); }
-        }
-        float* dspec = c->d_spec[hb_]; float* dfrec = c->d_frec[hb_];
-        rows_for_pack = dspec; frec_for_pack = dfrec;
-        c->last_frec = dfrec; c->last_frec_frames = dT;
-        const int runf = c->opt.run_frames ? c->opt.run_frames : c->input_ready ? LC3D_RUN_FRAMES_READY : LC3D_RUN_FRAMES;
-        int R = (n_frames + runf - 1) / runf;              /* runs of frames */
-        if (R > LC3D_MAX_RUNS) R = LC3D_MAX_RUNS;
-        if (R < 1) R = 1;
-        if (c->opt.runs) R = c->opt.runs;
-        const int Tr = (n_frames + R - 1) / R;
-        /* Where the side kernels of this call may start.  Normally behind everything the caller queued on s before the call (the PCM may
-         * come from there).  With lc3hip_set_input_ready - the PCM of a call is complete when the call is made - and a previous call of
-         * the same shape on the same stream, they need not wait for that call's chain and bitstream writer: their streams carry on in
-         * their own order, writing the other set of rows and records (the set they write now was last read by the writer of the call before
-         * the previous one: ev_done); the MDCT memory before frame 0 is read from the previous call's hand-over (two alternating buffers),
-         * not from the state that call's last rate kernel is still to update. */
-        const int amax = c->opt.ahead_max ? c->opt.ahead_max : LC3D_AHEAD_MAX_FRAMES;
-        /* A configuration copy queued behind the previous call (lc3hip_upload_chans_async) is on s, which a call that overlaps does not wait for: only a
-         * per-frame-bandwidth call overlaps it, and only when that copy changed nothing but the bandwidth words, which its kernels do not read (the other words
-         * are rewritten with their own values).  A call that forks from s is behind the copy, and so is everything after it. */
-        const bool cfg_ok = c->cfg_fresh == 0 || (c->cfg_fresh == 1 && dbw);
-        const bool ahead = c->input_ready && n_frames <= amax && c->ahead_ok && c->ahead_T == n_frames && c->ahead_R == R && c->last_stream == s && dt0 == 0 && dT == n_frames && pack && cfg_ok;
-        if (!ahead) c->cfg_fresh = 0;
-        float* xn_w = c->d_xnext[c->xn_par];                         /* written by this call's front kernel */
-        /* one buffer more than calls in flight: the one written now was last read by the call LC3D_SETS back (its resampler and front) and by the
-         * rate kernel of the call before that, all finished before the bitstream writer this call's side streams have waited for */
-        const float* xprev = ahead ? c->d_xnext[(c->xn_par + LC3D_SETS) % (LC3D_SETS + 1)] : c->d_state + LC3D_ST_XPREV;
-        const int xprev_stride = ahead ? mc : c->state_words;
-        const bool five = c->s_pit != c->s_pre;
-        /* The rate chain on a stream of its own, so that the rate kernel of call k+1 runs beside the bitstream writer of call k (which stays on the
-         * caller's stream: it is what the caller waits for).  It pays where the caller's stream - rate kernel + writer - is the longest of the three:
-         * large frames (the writer's work grows with the bytes: c96 22 -> 32 Mframes/s, c5 77 -> 83) and short calls (c3 +3 %); on 80-byte frames in
-         * calls of 64 (c1) a fourth side stream costs 0 ... 11 % (it shares one of HIP's four hardware queues with another, depending on what else the
-         * process created), and on c4 4 %.  LC3PLUS_ENC_RATE_STREAM=0 / 1 forces the choice (diagnostic). */
-        const int rt_env = c->opt.rate_stream;
-        const bool want_rt = rt_env == 1 || (rt_env < 0 && !c->big && (c->mean_nbytes >= 120 || n_frames <= 32));      /* large layout (c96, with round 4's writer): 36.6 on the caller's stream against 33.9 / 34.5 on the front / pitch stream */
-        /* ... and then on which side stream: behind the pitch kernel (it waits for the shape kernel's event) or behind the shape kernel (it waits for the pitch kernel's).
-         * Measured (Mframes/s, front stream / pitch stream): 48 kHz / 10 ms x 64 frames at 120 bytes 91.6 / 102.5, 160: 88.5 / 98.0, 240: 82.0 / 88.0, 400: 72.8 / 75.2, c5 88.3 / 97.1 (calls of
-         * 32: 82.7 / 88.5); 80-byte frames in calls of 6: 51.3 / 60.4, 8: 62.3 / 68.1, 12: 72.4 / 88.6, 14: 80.6 / 88.4, 18: 85.3 / 90.8, 28: 93.4 / 95.5, 32: 94.6 / 100.9 - but of 16: 94.2 / 92.6 (c3 94.1 / 89.8),
-         * 20: 93.8 / 91.0, 24: 96.4 / 92.9, and c96 32.8 / 30.8.  The pitch stream is the lighter one; behind the shape kernel the rate kernel blocks nothing while it waits, which wins where the
-         * front stream is at its best (calls of 16 ... 24 frames in whole groups of four - lc3_enc_front4_kernel's unit) and in the large layout. */
-        const bool on_pre = c->opt.rate_on >= 0 ? c->opt.rate_on == 1 : !(c->big || (c->mean_nbytes < 120 && n_frames >= 16 && n_frames <= 24 && (n_frames & 3) == 0));
-        hipStream_t rts = want_rt ? (on_pre ? c->s_pit : c->s_ln) : NULL;          /* NULL: the rate kernels run on the caller's stream */
-        if (!ahead) {
-            HIPCHK(hipEventRecord(c->ev_fork, s)); HIPCHK(hipStreamWaitEvent(c->s_pre, c->ev_fork, 0)); HIPCHK(hipStreamWaitEvent(c->s_fr, c->ev_fork, 0));
-            if (five) { HIPCHK(hipStreamWaitEvent(c->s_pit, c->ev_fork, 0)); HIPCHK(hipStreamWaitEvent(c->s_ln, c->ev_fork, 0)); }
-        } else {
-            HIPCHK(hipStreamWaitEvent(c->s_pre, c->ev_m[R - 1], 0));    /* the resampler reads the hand-over the previous call's last front kernel wrote */
-            HIPCHK(hipStreamWaitEvent(c->s_pre, c->ev_done[hb_], 0)); HIPCHK(hipStreamWaitEvent(c->s_fr, c->ev_done[hb_], 0));
-            if (five) { HIPCHK(hipStreamWaitEvent(c->s_pit, c->ev_done[hb_], 0)); HIPCHK(hipStreamWaitEvent(c->s_ln, c->ev_done[hb_], 0));
-                        if (c->any_attack) HIPCHK(hipStreamWaitEvent(c->s_fr, c->ev_f[R - 1], 0)); }      /* the front reads the attack detector's filter memory the previous call's attack kernel leaves */
-        }
-        /* The 12.8 kHz pre-kernels run ahead in larger pieces than the runs: the HP50 kernel (one stream per lane, B / 64 waves) costs ~0.1 ms
-         * per launch whatever the frame count, which per run would make its stream the slowest.  First piece = the first run (the rate
-         * kernel should start early), then three runs at a time, in stream order between the pitch kernels that need them.  (More side
-         * streams than these two do not help: HIP multiplexes streams onto a few hardware queues and kernels of two streams that share
-         * one run back to back.) */
-        hipStream_t rs = s;                                  /* where the rate kernels run */
-        for (int k = 0, tb = 0, hb = 0, hk = 0; tb < n_frames; k++, tb += Tr) {
-            const int nt = n_frames - tb < Tr ? n_frames - tb : Tr;
-            if (tb >= hb) {
-                const int prn = c->opt.pre_runs;
-                const int hn0 = hk == 0 ? Tr : prn * Tr, hn = n_frames - hb < hn0 ? n_frames - hb : hn0;
-                DUPL('r') launch_resample(c, c->s_pre, dpcm, bitdepth, n_frames, hb, hn, mc, dy12, xprev, xprev_stride);
-                DUPL('h') hipLaunchKernelGGL(lc3_enc_hp50_kernel, dim3((unsigned)((c->ncs + WAVE - 1) / WAVE)), dim3(WAVE), 0, c->s_pre, c->d_plan, c->d_state, c->state_words, LC3D_ST_SCAL(mc), n_frames, hb, hn, c->ncs, dy12);
-                HIPCHK(hipGetLastError());
-                hb += hn; hk++;
-                if (five) { HIPCHK(hipEventRecord(c->ev_h[k], c->s_pre)); HIPCHK(hipStreamWaitEvent(c->s_pit, c->ev_h[k], 0)); }
-            }
-            const int p2 = c->opt.pitch2;
-            if (p2 && (c->len12 == 128 || c->len12 == 64 || c->len12 == 32)) {
-                auto pk = c->len12 == 128 ? lc3_enc_pitch2_kernel : c->len12 == 64 ? lc3_enc_pitch2_kernel_l64 : lc3_enc_pitch2_kernel_l32;
-                DUPL('p') hipLaunchKernelGGL(pk, dim3((unsigned)((c->ncs + 1) / 2)), dim3(WAVE), 0, c->s_pit, c->d_plan, c->d_chans, c->d_state, c->state_words, mc, dy12, n_frames, tb, nt, c->ncs, dfrec, dT, dt0);
-            }
-            else DUPL('p') hipLaunchKernelGGL(lc3_enc_pitch_kernel, dim3(c->ncs), dim3(WAVE), 0, c->s_pit, c->d_plan, c->d_chans, c->d_state, c->state_words, mc, dy12, n_frames, tb, nt, c->ncs, dfrec, dT, dt0);
-            HIPCHK(hipGetLastError());
-            HIPCHK(hipEventRecord(c->ev_p[k], c->s_pit));
-            const int scf_wave = c->opt.scf_wave;
-            const int fpw = nt < FRONT_FPW ? nt : FRONT_FPW;
-            const unsigned fruns = (unsigned)((nt + fpw - 1) / fpw);
-            const int f4 = c->opt.front4;
-            if (f4 && !c->big && !scf_wave && c->N == 480 && c->la == 180 && (c->ylen & 15) == 0)
-                DUPL('f') hipLaunchKernelGGL(fmt_plain ? lc3_enc_front4_kernel : lc3_enc_front4_kernel_fmt, dim3((unsigned)c->ncs * (unsigned)((nt + 3) / 4)), dim3(WAVE), 0, c->s_fr, c->d_plan, c->d_chans, c->d_state, dpcm, bitdepth, n_frames, tb, nt, c->ncs, dspec, c->srow, dT, dt0, dfrec, xn_w, xprev, xprev_stride);
-            else if (f4 && c->fm_frames && !scf_wave)
-                hipLaunchKernelGGL(fmt_plain ? lc3_enc_frontm_kernel : lc3_enc_frontm_kernel_fmt, dim3((unsigned)c->ncs * (unsigned)((nt + c->fm_frames - 1) / c->fm_frames)), dim3(WAVE), 0, c->s_fr, c->d_plan, c->d_chans, c->d_state, dpcm, bitdepth, n_frames, tb, nt, c->fm_frames, c->ncs, dspec, c->srow, dT, dt0, dfrec, xn_w, xprev, xprev_stride);
-            else if (c->big) hipLaunchKernelGGL(fmt_plain ? lc3_enc_front_kernel_big : lc3_enc_front_kernel_big_fmt, dim3((unsigned)c->ncs * fruns), dim3(WAVE), 0, c->s_fr, c->d_plan, c->d_chans, c->d_state, dpcm, bitdepth, n_frames, tb, nt, fpw, c->ncs, dspec, c->srow, dT, dt0, dfrec, xn_w, xprev, xprev_stride, scf_wave);
-            else DUPL('f') hipLaunchKernelGGL(fmt_plain ? lc3_enc_front_kernel : lc3_enc_front_kernel_fmt, dim3((unsigned)c->ncs * fruns), dim3(WAVE), 0, c->s_fr, c->d_plan, c->d_chans, c->d_state, dpcm, bitdepth, n_frames, tb, nt, fpw, c->ncs, dspec, c->srow, dT, dt0, dfrec, xn_w, xprev, xprev_stride, scf_wave);
-            HIPCHK(hipEventRecord(c->ev_m[k], c->s_fr));                 /* the MDCT memory hand-over and the spectrum rows of the run are written */
-            if (five) HIPCHK(hipStreamWaitEvent(c->s_ln, c->ev_m[k], 0));
-            const int fuse_vq = !scf_wave && !c->any_attack && c->opt.fuse_vq;
-            if (!scf_wave) DUPL('e') hipLaunchKernelGGL(lc3_enc_scf_lane_kernel, dim3((unsigned)(((long long)c->ncs * nt + WAVE - 1) / WAVE)), dim3(WAVE), 0, c->s_ln, c->d_plan, dT, dt0 + tb, nt, c->ncs, dspec, c->srow, dfrec, fuse_vq);
-            if (c->any_attack)
-                hipLaunchKernelGGL(lc3_enc_attack_kernel, dim3((unsigned)((c->ncs + WAVE - 1) / WAVE)), dim3(WAVE), 0, c->s_ln, c->d_plan, c->d_chans, c->d_state, c->state_words, LC3D_ST_SCAL(mc), dfrec, dT, dt0, tb, nt, c->ncs);
-            const long long nfr = (long long)c->ncs * nt;
-            if (!fuse_vq) DUPL('v') hipLaunchKernelGGL(lc3_enc_snsvq_kernel, dim3((unsigned)((nfr + WAVE - 1) / WAVE)), dim3(WAVE), 0, c->s_ln, c->d_plan, dfrec, dT, dt0, tb, nt, c->ncs, c->any_attack);
-            {   /* shaping, TNS and the stateless half of the gain estimate: frame-parallel, behind the quantiser (LC3PLUS_ENC_SHAPE_ON_S=1, diagnostic: on the
-                 * launch stream in front of the rate kernel instead) */
-                const int sfpw = c->opt.shape_fpw ? c->opt.shape_fpw : SHAPE_FPW, son = c->opt.shape_on_s;
-                const int spw = nt < sfpw ? nt : sfpw;
-                const unsigned sruns = (unsigned)((nt + spw - 1) / spw);
-                /* LC3PLUS_ENC_SHAPE_ON_PITCH=1 (diagnostic): the shape kernel on the pitch stream, behind the pitch kernel, waiting for the quantiser's event.  Tried for c96, whose
-                 * front stream is the longest (3.6 of a 3.6 ms call) and whose pitch stream the lightest (1.4): the next call's pitch chain then queues behind a shape kernel that
-                 * waits for the front stream - 37.3 -> 31.0 Mframes/s; c1 111 -> 101, c5 97 -> 81, c3 93 -> 83; only c4 - long calls of 2.5 ms high-resolution frames, four runs per call, the front stream 8.5 of the 8.6 ms - gains (122.0 -> 126.1): on for that shape only. */
-                const bool sop = !son && (c->opt.shape_on_pitch >= 0 ? c->opt.shape_on_pitch == 1 : (c->hr && c->N == 240 && n_frames >= 128));      /* c4's shape: calls of 128 / 256 frames 123.8 -> 126.0, 122.0 -> 126.1 */
-                hipStream_t ss = son ? s : sop ? c->s_pit : c->s_ln;
-                rs = (son || !rts) ? s : rts;
-                if (son) { HIPCHK(hipEventRecord(c->ev_f[k], c->s_ln)); HIPCHK(hipStreamWaitEvent(s, c->ev_f[k], 0)); }
-                if (sop) { HIPCHK(hipEventRecord(c->ev_v[k], c->s_ln)); HIPCHK(hipStreamWaitEvent(ss, c->ev_v[k], 0)); }
-                const int swave = c->opt.shape_wave;
-                if (dbw && bw_to(c, ss)) return 1;
-                if (dbw && !swave) hipLaunchKernelGGL(lc3_enc_shape_lane_kernel_vbw, dim3((unsigned)(((long long)c->ncs * nt + WAVE - 1) / WAVE)), dim3(WAVE), 0, ss, c->d_plan, c->d_chans, dT, dt0 + tb, nt, c->ncs, dspec, c->srow, dfrec, dbw);
-                else if (dbw) hipLaunchKernelGGL(lc3_enc_shape_kernel_vbw, dim3((unsigned)c->ncs * sruns), dim3(WAVE), 0, ss, c->d_plan, c->d_chans, dT, dt0 + tb, nt, spw, c->ncs, dspec, c->srow, dfrec, dbw);
-                else if (!swave) DUPL('a') hipLaunchKernelGGL(lc3_enc_shape_lane_kernel, dim3((unsigned)(((long long)c->ncs * nt + WAVE - 1) / WAVE)), dim3(WAVE), 0, ss, c->d_plan, c->d_chans, dT, dt0 + tb, nt, c->ncs, dspec, c->srow, dfrec);
-                else if (c->big) hipLaunchKernelGGL(lc3_enc_shape_kernel_big, dim3((unsigned)c->ncs * sruns), dim3(WAVE), 0, ss, c->d_plan, c->d_chans, dT, dt0 + tb, nt, spw, c->ncs, dspec, c->srow, dfrec);
-                else DUPL('a') hipLaunchKernelGGL(lc3_enc_shape_kernel, dim3((unsigned)c->ncs * sruns), dim3(WAVE), 0, ss, c->d_plan, c->d_chans, dT, dt0 + tb, nt, spw, c->ncs, dspec, c->srow, dfrec);
-                HIPCHK(hipGetLastError());
-                if (!son) { HIPCHK(hipEventRecord(c->ev_f[k], ss)); HIPCHK(hipStreamWaitEvent(rs, c->ev_f[k], 0)); }
-            }
-            HIPCHK(hipStreamWaitEvent(rs, c->ev_p[k], 0));
-            if (k == 0 && c->rate_armed) HIPCHK(hipStreamWaitEvent(rs, c->ev_rate, 0));      /* the rate chain is a chain: behind the previous call's, whichever stream that ran on */
-            const int last = tb + nt >= n_frames;            /* behind the last frame of this launch the MDCT memory goes into the state */
-            if (c->big) hipLaunchKernelGGL(lc3_enc_rate_kernel_big, dim3((unsigned)((c->ncs + RATE_WG - 1) / RATE_WG)), dim3(RATE_WG * WAVE), 0, rs, c->d_plan, c->d_chans, c->d_state, dT, dt0 + tb, nt, c->ncs, dspec, c->srow, dfrec, xn_w, last);
-            else DUPL('s') hipLaunchKernelGGL(lc3_enc_rate_kernel, dim3((unsigned)((c->ncs + RATE_WG - 1) / RATE_WG)), dim3(RATE_WG * WAVE), 0, rs, c->d_plan, c->d_chans, c->d_state, dT, dt0 + tb, nt, c->ncs, dspec, c->srow, dfrec, xn_w, last);
-            HIPCHK(hipGetLastError());
-        }
-        HIPCHK(hipEventRecord(c->ev_rate, rs)); c->rate_armed = 1; rate_on_side = rs != s;
-        if (rs != s) HIPCHK(hipStreamWaitEvent(s, c->ev_rate, 0));      /* the writer (and whatever the caller queues next) behind the rate chain */
-        c->ahead_ok = (dt0 == 0 && dT == n_frames && pack) ? 1 : 0; c->ahead_T = n_frames; c->ahead_R = R;
-        c->xn_par = (c->xn_par + 1) % (LC3D_SETS + 1);
-    }
-    if (ddump && pack) {
-        HIPCHK(hipGetLastError());
-        const int wpg = c->opt.pack_wpg;                  /* waves per workgroup of the writer (they share the coder's tables in LDS) */
-        const size_t per_wave = (size_t)PK_XBUF * WAVE * sizeof(unsigned);
-        const long long tasks = (long long)c->ncs * dT, per_wg = (long long)wpg * WAVE;
-        /* The writer codes one frame per lane: its duration is the latency of the LARGEST frame of the batch (c5: 1.7 ms for 400 bytes, c96: 3.2 ms), whatever the
-         * batch size, and on the caller's stream the writers of consecutive calls run one after the other.  Where that is the longest stream (the rule that moves the
-         * rate chain off the caller's stream: large frames, short calls) and calls overlap, the writers CAN alternate between two side streams - writer k + 1 beside
-         * writer k, each with its own set of scratch rows and status bytes, the caller's stream waiting for their events in call order.  Measured (Mframes/s,
-         * off / on): with HIP's default four hardware queues c5 87.0 / 80.0, c96 32.1 / 28.7, c3 85.1 / 73.0 - six streams share four queues and kernels of two
-         * streams on one queue run back to back; with GPU_MAX_HW_QUEUES=8 c5 90.9 / 92.4, c96 28.8 / 33.9, c3 85.5 / 85.8.  So it is a deployment switch
-         * (LC3PLUS_ENC_PACK_STREAM=1 together with GPU_MAX_HW_QUEUES >= 6), off by default. */
-        const int pk_env = c->opt.pack_stream;
-        const bool side = split && rate_on_side && c->input_ready && dt0 == 0 && dT == n_frames && pk_env == 1;
-        hipStream_t ps = s;
-        if (side) {
-            /* behind this call's rate chain only - NOT behind the caller's stream, whose tail is the writer of the call before: under the input-ready promise the
-             * output buffer of a call, like its PCM, is the caller's to have ready (include/lc3plus_batch.h) */
-            if (!c->s_pk[c->pk_par]) HIPCHK(hipStreamCreateWithFlags(&c->s_pk[c->pk_par], hipStreamNonBlocking));
-            ps = c->s_pk[c->pk_par];
-            HIPCHK(hipStreamWaitEvent(ps, c->ev_rate, 0));
-        }
-        if (side && c->pk.on) HIPCHK(hipStreamWaitEvent(ps, c->ev_scan, 0));     /* packed output: behind the call's scan (the table the writers read) */
-        if (split) HIPCHK(hipMemsetAsync(c->d_status, 0, (size_t)c->ncs * dT, ps));
-        /* large frames: tail + writer a frame per wave (lc3_enc_tailw_kernel, lc3_enc_rate.inc), launched first - its waves are the long ones */
-        const int big_from = (split && c->opt.tailw_bytes && c->max_nbytes >= c->opt.tailw_bytes && !c->pk.on) ? c->opt.tailw_bytes : 0;   /* (no packed form) */
-        if (big_from) {
-            const int fpw = dT < 4 ? dT : 4;
-            const unsigned wruns = (unsigned)((dT + fpw - 1) / fpw);
-            if (c->big) hipLaunchKernelGGL(lc3_enc_tailw_kernel_big, dim3((unsigned)c->ncs * wruns), dim3(WAVE), 0, ps, c->d_plan, c->d_chans, dT, dT, fpw, c->ncs, rows_for_pack, c->srow, frec_for_pack, dout, out_stride, c->d_status, big_from);
-            else hipLaunchKernelGGL(lc3_enc_tailw_kernel, dim3((unsigned)c->ncs * wruns), dim3(WAVE), 0, ps, c->d_plan, c->d_chans, dT, dT, fpw, c->ncs, rows_for_pack, c->srow, frec_for_pack, dout, out_stride, c->d_status, big_from);
-            HIPCHK(hipGetLastError());
-        }
-        const bool two = split && c->opt.pack_split == 1;
-        if (!big_from || c->min_nbytes < big_from) {
-            const dim3 grid((unsigned)((tasks + per_wg - 1) / per_wg)), block(wpg * WAVE);
-            const size_t dyn = per_wave * wpg + ((size_t)(c->opt.pack_pad_kb > 0 ? c->opt.pack_pad_kb : 0) << 10);
-            const long long* pt = c->pk.on ? c->pk.tab : nullptr;
-            if (two && pt) {
-                hipLaunchKernelGGL(lc3_enc_pack_head_kernel_pk, grid, block, 0, ps, c->d_plan, c->d_chans, ddump, dstride, dT, 0, dT, c->ncs, dout, 0, c->d_status, rows_for_pack, c->srow, frec_for_pack, big_from, pt);
-                hipLaunchKernelGGL(lc3_enc_pack_code_kernel_pk, grid, block, dyn, ps, c->d_plan, c->d_chans, ddump, dstride, dT, 0, dT, c->ncs, dout, 0, c->d_status, rows_for_pack, c->srow, frec_for_pack, big_from, pt);
-            } else if (two) {
-                hipLaunchKernelGGL(lc3_enc_pack_head_kernel, grid, block, 0, ps, c->d_plan, c->d_chans, ddump, dstride, dT, 0, dT, c->ncs, dout, out_stride, c->d_status, rows_for_pack, c->srow, frec_for_pack, big_from);
-                hipLaunchKernelGGL(lc3_enc_pack_code_kernel, grid, block, dyn, ps, c->d_plan, c->d_chans, ddump, dstride, dT, 0, dT, c->ncs, dout, out_stride, c->d_status, rows_for_pack, c->srow, frec_for_pack, big_from);
-            } else {
-                /* 96 or 128 registers (lc3_enc_pack.inc, the table at lc3_enc_pack_kernel_w5): five waves per SIMD pay for long calls of small 10 ms frames */
-                const bool w5 = c->opt.pack_w5 >= 0 ? c->opt.pack_w5 == 1 : (split && !c->big && !c->hr && c->N == 480 && dT >= 48 && c->max_nbytes <= 100);
-                auto pk = w5 ? lc3_enc_pack_kernel_w5 : lc3_enc_pack_kernel;
-                if (pt) hipLaunchKernelGGL(w5 ? lc3_enc_pack_kernel_w5_pk : lc3_enc_pack_kernel_pk, grid, block, dyn, ps, c->d_plan, c->d_chans, ddump, dstride,
-                                           dT, 0, dT, c->ncs, dout, 0, c->d_status, rows_for_pack, c->srow, frec_for_pack, big_from, pt);
-                else DUPL('k') hipLaunchKernelGGL(pk, grid, block, dyn, ps, c->d_plan, c->d_chans, ddump, dstride,
-                                   dT, 0, dT, c->ncs, dout, out_stride, c->d_status, rows_for_pack, c->srow, frec_for_pack, big_from);
-            }
-        }
-        if (split && c->input_ready) { HIPCHK(hipEventRecord(c->ev_done[c->row_par], ps)); c->row_par = (c->row_par + 1) % LC3D_SETS; }      /* this call's set of rows and records is free again */
-        if (side) { HIPCHK(hipEventRecord(c->ev_pk[c->pk_par], ps)); HIPCHK(hipStreamWaitEvent(s, c->ev_pk[c->pk_par], 0)); c->pk_par ^= 1; }
-    }
-    HIPCHK(hipGetLastError());
-    c->last_stream = s;
-    return 0;
-}
-
-static bool host_ptr_is_pinned(const void* p)
-{
-    hipPointerAttribute_t a;
-    if (hipPointerGetAttributes(&a, p) != hipSuccess) { (void)hipGetLastError(); return false; }
-    return a.type == hipMemoryTypeHost;
-}
-
-/* Host pointers on both sides (SURVEY 8d "wall-clock over the encode() call including H2D of PCM and D2H of bitstreams"): the PCM of a
- * call is cut into runs of frames (all streams advance together, so every run fills the GPU like the whole call would; cutting by
- * streams would not).  Run k+1 goes up on a copy stream while run k is encoded on the launch stream: PCM of a run is a strided block of
- * the caller's [stream][frame][channel][N] array - a 2-D copy (SDMA) straight from the caller's memory when that is pinned
- * (hipHostMalloc / hipHostRegister), otherwise rows are staged through the library's own pinned slots by the calling thread, which
- * overlaps with the GPU work of the previous run.  The bitstream writer runs ONCE behind the last run over all frames of the call (one
- * frame per lane makes it latency bound: per run it would cost as much as for the whole call), then the frames come down in one
- * linear copy.  State stays on the device between runs.  The first run is short so that the kernels start early. */
-static int encode_host(lc3hip_ctx* c, const void* pcm, int bitdepth, int n_frames, void* out, int out_stride, hipStream_t s, const uint16_t* dfsz,
-                       const uint16_t* dbw)
-{
-    const size_t bps = (size_t)lc3d_pcm_elem_bytes(bitdepth);
-    const size_t fr_in = (size_t)c->channels * c->N * bps;                    /* bytes of one stream-frame of PCM */
-    const size_t pcm_bytes = (size_t)c->n_streams * n_frames * fr_in, out_bytes = (size_t)c->n_streams * n_frames * out_stride;
-    int K = (int)(pcm_bytes >> 25);                                           /* ~32 MB of PCM per run */
-    if (K < 1) K = 1; if (K > 8) K = 8; if (K > n_frames) K = n_frames;
-    if ((bitdepth & LC3D_PCM_CHANNEL_MAJOR) && c->channels > 1) K = 1;        /* a run of frames is one block per stream in the two other layouts only: this one goes up in one piece */
-    if (!dfsz && (c->fused || n_frames <= LC3D_FUSED_MAX_T)) K = 1;                                          /* diagnostic single-kernel path: the first kernel addresses the output by its own frame count (the per-frame-bitrate kernel by the call's) */
-    const int Tc = (n_frames + K - 1) / K, T0 = K > 1 ? (Tc + 1) / 2 : Tc;   /* first run: half a run */
-    const bool pin_in = host_ptr_is_pinned(pcm);
-    const size_t cin = (size_t)c->n_streams * Tc * fr_in;
-    if (!c->s_h2d) {
-        HIPCHK(hipStreamCreateWithFlags(&c->s_h2d, hipStreamNonBlocking));
-        for (int i = 0; i < 2; i++) { HIPCHK(hipEventCreateWithFlags(&c->ev_h2d[i], hipEventDisableTiming)); HIPCHK(hipEventCreateWithFlags(&c->ev_k[i], hipEventDisableTiming)); }
-    }
-    if (c->hp_pcm_cap < cin) { for (int i = 0; i < 2; i++) { if (c->hp_dpcm[i]) HIPCHK(hipFree(c->hp_dpcm[i])); c->hp_dpcm[i] = nullptr; } c->hp_pcm_cap = 0;
-                               for (int i = 0; i < 2; i++) HIPCHK(hipMalloc(&c->hp_dpcm[i], cin)); c->hp_pcm_cap = cin; }
-    if (!pin_in && c->hp_pin_in_cap < cin) { for (int i = 0; i < 2; i++) { if (c->hp_pin_in[i]) HIPCHK(hipHostFree(c->hp_pin_in[i])); c->hp_pin_in[i] = nullptr; } c->hp_pin_in_cap = 0;
-                                             for (int i = 0; i < 2; i++) HIPCHK(hipHostMalloc(&c->hp_pin_in[i], cin, hipHostMallocDefault)); c->hp_pin_in_cap = cin; }
-    if (c->out_cap < out_bytes) { if (c->d_out) HIPCHK(hipFree(c->d_out)); c->d_out = nullptr; c->out_cap = 0; HIPCHK(hipMalloc((void**)&c->d_out, out_bytes)); c->out_cap = out_bytes; }
-    const size_t in_pitch = (size_t)n_frames * fr_in;
-    HIPCHK(hipEventRecord(c->ev0, s));
-    HIPCHK(hipMemsetAsync(c->d_out, 0, out_bytes, s));
-    for (int k = 0, t0 = 0; t0 < n_frames; k++) {
-        const int i = k & 1, want = k == 0 ? T0 : Tc, tc = n_frames - t0 < want ? n_frames - t0 : want;
-        const size_t w_in = (size_t)tc * fr_in;
-        if (k >= 2) HIPCHK(hipEventSynchronize(c->ev_k[i]));                   /* run k - 2 has been encoded: its staging slot is free */
-        const uint8_t* src = (const uint8_t*)pcm + (size_t)t0 * fr_in;
-        if (pin_in) HIPCHK(hipMemcpy2DAsync(c->hp_dpcm[i], w_in, src, in_pitch, w_in, (size_t)c->n_streams, hipMemcpyHostToDevice, c->s_h2d));
-        else {
-            for (int st = 0; st < c->n_streams; st++) memcpy((uint8_t*)c->hp_pin_in[i] + st * w_in, src + st * in_pitch, w_in);
-            HIPCHK(hipMemcpyAsync(c->hp_dpcm[i], c->hp_pin_in[i], w_in * c->n_streams, hipMemcpyHostToDevice, c->s_h2d));
-        }
-        HIPCHK(hipEventRecord(c->ev_h2d[i], c->s_h2d));
-        HIPCHK(hipStreamWaitEvent(s, c->ev_h2d[i], 0));
-        if (enc_launch(c, c->hp_dpcm[i], bitdepth, tc, c->d_out, out_stride, s, nullptr, n_frames, t0, t0 + tc >= n_frames, dfsz, dbw)) return 1;
-        HIPCHK(hipEventRecord(c->ev_k[i], s));
-        t0 += tc;
-    }
-    HIPCHK(hipEventRecord(c->ev1, s));
-    HIPCHK(hipMemcpyAsync(out, c->d_out, out_bytes, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    float ms = 0; if (hipEventElapsedTime(&ms, c->ev0, c->ev1) == hipSuccess) c->last_ms = ms;
-    return 0;
-}
-
-extern "C" int lc3hip_upload_enc_table(void* ctx, const lc3d_chan* tab, int n)
-{
-    lc3hip_ctx* c = (lc3hip_ctx*)ctx;
-    HIPCHK(hipSetDevice(c->device));
-    if (c->d_etab) HIPCHK(hipFree(c->d_etab));
-    c->d_etab = nullptr;
-    HIPCHK(hipMalloc((void**)&c->d_etab, sizeof(lc3d_chan) * (size_t)n));
-    HIPCHK(hipMemcpy(c->d_etab, tab, sizeof(lc3d_chan) * (size_t)n, hipMemcpyHostToDevice));
-    c->etab_attack = 0; c->etab_max = n - 1;
-    for (int i = 1; i < n; i++) c->etab_attack |= tab[i].attack_handling != 0;
-    return 0;
-}
-/* the stream-frame sizes of a per-frame-bitrate call to the device, queued on s ahead of its kernels: copied into pinned staging first, so that the caller's
- * array is free when the call returns; the buffer pair of the call LC3D_SETS back is waited for before it is written again */
-static int upload_fsz(lc3hip_ctx* c, const uint16_t* fsz_host, int n_frames, hipStream_t s, const uint16_t** dfsz, hipEvent_t* ev)
-{
-    const size_t fb = sizeof(uint16_t) * (size_t)c->n_streams * n_frames;
-    const int k = c->fsz_set;
-    if (c->fsz_armed[k]) HIPCHK(hipEventSynchronize(c->ev_fsz[k]));
-    if (c->fsz_cap < fb) {
-        for (int i = 0; i < LC3D_SETS; i++) if (c->fsz_armed[i]) { HIPCHK(hipEventSynchronize(c->ev_fsz[i])); c->fsz_armed[i] = 0; }   /* no call reads them any more */
-        for (int i = 0; i < LC3D_SETS; i++) {
-            if (c->d_fsz[i]) HIPCHK(hipFree(c->d_fsz[i])); if (c->h_fsz[i]) HIPCHK(hipHostFree(c->h_fsz[i])); c->d_fsz[i] = nullptr; c->h_fsz[i] = nullptr;
-        }
-        c->fsz_cap = 0;
-        for (int i = 0; i < LC3D_SETS; i++) { HIPCHK(hipMalloc((void**)&c->d_fsz[i], fb)); HIPCHK(hipHostMalloc((void**)&c->h_fsz[i], fb, hipHostMallocDefault)); }
-        c->fsz_cap = fb;
-    }
-    if (!c->ev_fsz[0]) for (int i = 0; i < LC3D_SETS; i++) HIPCHK(hipEventCreateWithFlags(&c->ev_fsz[i], hipEventDisableTiming));
-    memcpy(c->h_fsz[k], fsz_host, fb);
-    HIPCHK(hipMemcpyAsync(c->d_fsz[k], c->h_fsz[k], fb, hipMemcpyHostToDevice, s));
-    *dfsz = c->d_fsz[k]; *ev = c->ev_fsz[k];
-    c->fsz_armed[k] = 1; c->fsz_set = (k + 1) % LC3D_SETS;
-    return 0;
-}
-/* the bandwidths in force of a per-frame-bandwidth call into pinned staging, so that the caller's array is free when the call returns (the buffer pair of the
- * call LC3D_SETS back is waited for before it is written again; sized on first use, a call of equal or smaller size allocates nothing); bw_to queues the copy */
-static int stage_bw(lc3hip_ctx* c, const uint16_t* bw_host, int n_frames, const uint16_t** dbw, hipEvent_t* ev)
-{
-    const size_t fb = sizeof(uint16_t) * (size_t)c->n_streams * n_frames;
-    const int k = c->bw_set;
-    if (c->bw_armed[k]) HIPCHK(hipEventSynchronize(c->ev_bw[k]));
-    if (c->bw_cap < fb) {
-        for (int i = 0; i < LC3D_SETS; i++) if (c->bw_armed[i]) { HIPCHK(hipEventSynchronize(c->ev_bw[i])); c->bw_armed[i] = 0; }      /* no call reads them any more */
-        for (int i = 0; i < LC3D_SETS; i++) {
-            if (c->d_bw[i]) HIPCHK(hipFree(c->d_bw[i])); if (c->h_bw[i]) HIPCHK(hipHostFree(c->h_bw[i])); c->d_bw[i] = nullptr; c->h_bw[i] = nullptr;
-        }
-        c->bw_cap = 0;
-        for (int i = 0; i < LC3D_SETS; i++) { HIPCHK(hipMalloc((void**)&c->d_bw[i], fb)); HIPCHK(hipHostMalloc((void**)&c->h_bw[i], fb, hipHostMallocDefault)); }
-        c->bw_cap = fb;
-    }
-    if (!c->ev_bwcp) {
-        for (int i = 0; i < LC3D_SETS; i++) HIPCHK(hipEventCreateWithFlags(&c->ev_bw[i], hipEventDisableTiming));
-        HIPCHK(hipEventCreateWithFlags(&c->ev_bwcp, hipEventDisableTiming));
-    }
-    memcpy(c->h_bw[k], bw_host, fb);
-    c->bw_src = c->h_bw[k]; c->bw_bytes = fb; c->bw_on = nullptr; c->pl.pending = 0;
-    *dbw = c->d_bw[k]; *ev = c->ev_bw[k];
-    c->bw_armed[k] = 1; c->bw_set = (k + 1) % LC3D_SETS;
-    return 0;
-}
-static int plan_launch(lc3hip_ctx* c, hipStream_t st);
-/* packed output: the scan of the call's frame sizes on st (lc3_pack_sums_kernel, lc3_pack_base_kernel, lc3_pack_offsets_kernel) into tab, the caller's
- * offsets, total, flags (plan_flags: the plan kernel has written bits 0 ... 2 there) and num_bytes (where no plan kernel wrote them: plan_nb = 0) */
-static int pack_scan(lc3hip_ctx* c, hipStream_t st, int T, int slot /* the plan set, LC3D_SETS without a plan kernel */, const uint16_t* fsz, const int4* pend,
-                     int plan_flags, int plan_nb)
-{
-    const long long n = (long long)c->n_streams * T, nb = (n + PKS_TILE - 1) / PKS_TILE;
-    long long* tab = c->d_poff[slot]; long long* bsum = c->d_pbsum + (size_t)slot * c->pbsum_cap;
-    PkSrc q; q.fsz = fsz; q.pend = fsz ? nullptr : pend; q.chans = c->d_chans; q.channels = c->channels; q.order = c->pk.order; q.S = c->n_streams; q.T = T;
-    hipLaunchKernelGGL(lc3_pack_sums_kernel, dim3((unsigned)nb), dim3(PKS_THREADS), 0, st, q, n, bsum);
-    hipLaunchKernelGGL(lc3_pack_base_kernel, dim3(1), dim3(PKS_THREADS), 0, st, bsum, nb, c->pk.total);
-    hipLaunchKernelGGL(lc3_pack_offsets_kernel, dim3((unsigned)nb), dim3(PKS_THREADS), 0, st, q, n, (const long long*)bsum, c->pk.cap, tab, c->pk.offs,
-                       c->pk.fl, plan_flags, plan_nb ? (int32_t*)nullptr : c->pk.nb);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(c->ev_scan, st));
-    c->pk.tab = tab;
-    return 0;
-}
-static int bw_to(lc3hip_ctx* c, hipStream_t st)
-{
-    const int k = (c->bw_set + LC3D_SETS - 1) % LC3D_SETS;                    /* the slot stage_bw filled for this call */
-    if (!c->bw_on) {
-        if (c->pl.pending) { if (plan_launch(c, st)) return 1; }             /* words from device memory: the call's plan kernel writes them */
-        else HIPCHK(hipMemcpyAsync(c->d_bw[k], c->bw_src, c->bw_bytes, hipMemcpyHostToDevice, st));
-        HIPCHK(hipEventRecord(c->ev_bwcp, st)); c->bw_on = st;
-    } else if (c->bw_on != st) HIPCHK(hipStreamWaitEvent(st, c->ev_bwcp, 0));
-    return 0;
-}
-extern "C" int lc3hip_encode(void* ctx, const void* pcm, int pcm_on_device, int bitdepth, int n_frames, void* out, int out_stride,
-                             int out_on_device, void* hip_stream, int sync, void* trace_host, const uint16_t* fsz_host, const uint16_t* bw_host)
-{
-    lc3hip_ctx* c = (lc3hip_ctx*)ctx;
-    HIPCHK(hipSetDevice(c->device));
-    if (!hip_stream && !c->stream) HIPCHK(hipStreamCreate(&c->stream));
-    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : c->stream;
-    const uint16_t* dfsz = nullptr; hipEvent_t ev_fsz = nullptr;
-    const uint16_t* dbw = nullptr; hipEvent_t ev_bw = nullptr;
-    if (fsz_host && !c->d_etab) return 1;
-    if (bw_host && c->big) return 1;            /* no large-layout kernels: that layout only serves high-resolution batches, which the host refuses */
-    if (!pcm_on_device && !out_on_device && !trace_host) {
-        if (c->chans_armed) HIPCHK(hipStreamWaitEvent(s, c->ev_chans, 0));
-        if (fsz_host && upload_fsz(c, fsz_host, n_frames, s, &dfsz, &ev_fsz)) return 1;
-        if (bw_host && stage_bw(c, bw_host, n_frames, &dbw, &ev_bw)) return 1;
-        if (encode_host(c, pcm, bitdepth, n_frames, out, out_stride, s, dfsz, dbw)) return 1;
-        if (ev_fsz) HIPCHK(hipEventRecord(ev_fsz, s));
-        if (ev_bw) HIPCHK(hipEventRecord(ev_bw, s));
-        return 0;
-    }
-    const size_t bps = (size_t)lc3d_pcm_elem_bytes(bitdepth);
-    const size_t pcm_bytes = (size_t)c->n_streams * n_frames * c->channels * c->N * bps;
-    const size_t out_bytes = (size_t)c->n_streams * n_frames * out_stride;
-    const void* dpcm = pcm; uint8_t* dout = (uint8_t*)out;
-    if (!pcm_on_device) {
-        if (c->pcm_cap < pcm_bytes) { if (c->d_pcm) HIPCHK(hipFree(c->d_pcm)); c->d_pcm = nullptr; c->pcm_cap = 0; HIPCHK(hipMalloc(&c->d_pcm, pcm_bytes)); c->pcm_cap = pcm_bytes; }
-        HIPCHK(hipMemcpyAsync(c->d_pcm, pcm, pcm_bytes, hipMemcpyHostToDevice, s));
-        dpcm = c->d_pcm;
-    }
-    if (!out_on_device) {
-        if (c->out_cap < out_bytes) { if (c->d_out) HIPCHK(hipFree(c->d_out)); c->d_out = nullptr; c->out_cap = 0; HIPCHK(hipMalloc((void**)&c->d_out, out_bytes)); c->out_cap = out_bytes; }
-        dout = c->d_out;
-        HIPCHK(hipMemsetAsync(dout, 0, out_bytes, s));
-    }
-    lc3d_trace* dtr = nullptr;
-    if (trace_host) {
-        const size_t tb = sizeof(lc3d_trace) * (size_t)c->ncs * n_frames;
-        if (c->trace_cap < tb) { if (c->d_trace) HIPCHK(hipFree(c->d_trace)); c->d_trace = nullptr; c->trace_cap = 0; HIPCHK(hipMalloc((void**)&c->d_trace, tb)); c->trace_cap = tb; }
-        HIPCHK(hipMemsetAsync(c->d_trace, 0, tb, s));
-        dtr = c->d_trace;
-    }
-    if (c->opt.check_ready && c->input_ready && pcm_on_device) {
-        /* The promise says the PCM is complete NOW.  What can be checked: if everything this library queued on s has finished and s still has work pending, that work is
-         * the caller's - possibly the producer of this PCM.  (While our own work is pending nothing can be told apart; the check is a debug aid, not a proof.) */
-        if (!c->ev_ours) { HIPCHK(hipEventCreateWithFlags(&c->ev_ours, hipEventDisableTiming)); HIPCHK(hipEventCreateWithFlags(&c->ev_now, hipEventDisableTiming)); }
-        if ((!c->ours_armed || c->last_stream != s || hipEventQuery(c->ev_ours) == hipSuccess) && hipStreamQuery(s) == hipErrorNotReady) {
-            fprintf(stderr, "lc3plus_hip: LC3PLUS_CHECK_READY: lc3plus_enc_batch_set_input_ready(1) is in force, but work queued by the caller is still pending on the stream "
-                            "of this call - the PCM (or the output buffer) may not be ready; call refused\n");
-            (void)hipGetLastError();
-            return 1;
-        }
-        (void)hipGetLastError();
-    }
-    /* behind the LC3PLUS_CHECK_READY test, which must see no copy of ours pending on s */
-    if (c->chans_armed) HIPCHK(hipStreamWaitEvent(s, c->ev_chans, 0));
-    if (fsz_host && upload_fsz(c, fsz_host, n_frames, s, &dfsz, &ev_fsz)) return 1;
-    if (bw_host && stage_bw(c, bw_host, n_frames, &dbw, &ev_bw)) return 1;
-    HIPCHK(hipEventRecord(c->ev0, s));
-    if (c->pk.on && (fsz_host || bw_host || pack_scan(c, s, n_frames, LC3D_SETS, nullptr, nullptr, 0, 0))) return 1;      /* packed output, no per-frame words */
-    if (enc_launch(c, dpcm, bitdepth, n_frames, dout, out_stride, s, dtr, n_frames, 0, true, dfsz, dbw)) return 1;
-    HIPCHK(hipEventRecord(c->ev1, s));
-    if (ev_fsz) HIPCHK(hipEventRecord(ev_fsz, s));
-    if (ev_bw) HIPCHK(hipEventRecord(ev_bw, s));      /* the end of the call on s lies behind every kernel that read the words, on whichever stream */
-    if (c->opt.check_ready && c->ev_ours) { HIPCHK(hipEventRecord(c->ev_ours, s)); c->ours_armed = 1; }
-    if (!out_on_device) HIPCHK(hipMemcpyAsync(out, dout, out_bytes, hipMemcpyDeviceToHost, s));
-    if (trace_host) HIPCHK(hipMemcpyAsync(trace_host, dtr, sizeof(lc3d_trace) * (size_t)c->ncs * n_frames, hipMemcpyDeviceToHost, s));
-    if (sync || !out_on_device || trace_host) {
-        HIPCHK(hipStreamSynchronize(s));
-        float ms = 0; if (hipEventElapsedTime(&ms, c->ev0, c->ev1) == hipSuccess) c->last_ms = ms;
-    }
-    return 0;
-}
-
-/* the pending call's plan kernel on st: behind the previous call's plan kernel (the carry), behind the call that used this set last, and - when it starts
- * from the configuration the host wrote - behind that write */
-static int plan_launch(lc3hip_ctx* c, hipStream_t st)
-{
-    const int k = c->pl.k, T = c->pl.T;
-    if (c->plan_armed) HIPCHK(hipStreamWaitEvent(st, c->ev_plan, 0));
-    if (c->pset_armed[k]) HIPCHK(hipStreamWaitEvent(st, c->ev_pset[k], 0));
-    if (c->carry_seed && c->chans_armed) HIPCHK(hipStreamWaitEvent(st, c->ev_chans, 0));
-    const size_t al = (size_t)c->pl.rates | (size_t)c->pl.bws | (size_t)c->pl.nb | (size_t)c->pl.fl;
-    const int vec4 = (T & 3) == 0 && (al & 15) == 0 && (((size_t)c->pl.fl) & 3) == 0;
-    hipLaunchKernelGGL(lc3_enc_plan_rates_kernel, dim3((unsigned)((c->n_streams + WAVE - 1) / WAVE)), dim3(WAVE), 0, st, c->pl.rule, c->pl.rates, c->pl.bws, T,
-                       c->n_streams, c->d_carry, c->carry_seed ? (const lc3d_chan*)c->d_chans : (const lc3d_chan*)nullptr, c->d_pfsz[k], c->d_pbw[k], c->pl.nb, c->pl.fl,
-                       c->d_pend[k], vec4);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(c->ev_plan, st)); c->plan_armed = 1;
-    c->carry_seed = 0; c->pl.pending = 0;
-    /* packed output: the offsets behind the sizes, on the same stream (the writers, on whichever stream, are behind this one: bw_to, ev_scan) */
-    if (c->pk.on && pack_scan(c, st, T, k, c->pl.rates ? c->d_pfsz[k] : nullptr, c->d_pend[k], c->pl.fl != nullptr, c->pl.nb != nullptr)) return 1;
-    return 0;
-}
-/* Per-frame rates and / or bandwidths in device memory, as PCM and output: the plan kernel turns them into the words the per-frame kernels read (it runs
- * where the first of those kernels runs: bw_to), the call takes the path lc3hip_encode takes with the same words from the host, and the tail kernel
- * configures every stream on s behind it.  Nothing is read back, and the host waits only where a set of plan buffers has to grow. */
-extern "C" int lc3hip_encode_rates_device(void* ctx, const void* pcm, int bitdepth, int n_frames, void* out, int out_stride, const int32_t* rates_dev,
-                                          const int32_t* bws_dev, const lc3d_rate_rule* rule, int32_t* num_bytes_dev, uint8_t* flags_dev, int clear_resets,
-                                          void* hip_stream, int sync)
-{
-    lc3hip_ctx* c = (lc3hip_ctx*)ctx;
-    HIPCHK(hipSetDevice(c->device));
-    if (!c->d_etab || (bws_dev && c->big)) return 1;
-    if (!hip_stream && !c->stream) HIPCHK(hipStreamCreate(&c->stream));
-    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : c->stream;
-    if (!c->ev_plan) {
-        HIPCHK(hipEventCreateWithFlags(&c->ev_plan, hipEventDisableTiming)); HIPCHK(hipEventCreateWithFlags(&c->ev_pset_prev, hipEventDisableTiming));
-        for (int i = 0; i < LC3D_SETS; i++) HIPCHK(hipEventCreateWithFlags(&c->ev_pset[i], hipEventDisableTiming));
-        if (!c->ev_bwcp) HIPCHK(hipEventCreateWithFlags(&c->ev_bwcp, hipEventDisableTiming));
-        HIPCHK(hipMalloc((void**)&c->d_carry, sizeof(int4) * (size_t)c->n_streams));
-        for (int i = 0; i < LC3D_SETS; i++) HIPCHK(hipMalloc((void**)&c->d_pend[i], sizeof(int4) * (size_t)c->n_streams));
-        c->carry_seed = 1;
-    }
-    if (c->pset_frames < (size_t)n_frames) {
-        /* an earlier call that did not wait may still read the smaller sets: growing them waits for the device, once (the first allocation does not) */
-        if (c->d_pfsz[0]) HIPCHK(hipDeviceSynchronize());
-        for (int i = 0; i < LC3D_SETS; i++) {
-            if (c->d_pfsz[i]) HIPCHK(hipFree(c->d_pfsz[i])); if (c->d_pbw[i]) HIPCHK(hipFree(c->d_pbw[i]));
-            c->d_pfsz[i] = nullptr; c->d_pbw[i] = nullptr;
-        }
-        c->pset_frames = 0;
-        const size_t fb = sizeof(uint16_t) * (size_t)c->n_streams * n_frames;
-        for (int i = 0; i < LC3D_SETS; i++) { HIPCHK(hipMalloc((void**)&c->d_pfsz[i], fb)); HIPCHK(hipMalloc((void**)&c->d_pbw[i], fb)); }
-        c->pset_frames = (size_t)n_frames;
-    }
-    const int k = c->pset;
-    c->pl.pending = 1; c->pl.k = k; c->pl.T = n_frames; c->pl.rates = rates_dev; c->pl.bws = bws_dev; c->pl.nb = num_bytes_dev; c->pl.fl = flags_dev; c->pl.rule = *rule;
-    c->bw_on = nullptr;
-    if (c->chans_armed) HIPCHK(hipStreamWaitEvent(s, c->ev_chans, 0));
-    /* behind the batch's last call when that went to another stream (its work there ends on it: writer, rate chain), as a stream-lifecycle call is */
-    if (c->last_stream && c->last_stream != s) { HIPCHK(hipEventRecord(c->ev_pset_prev, c->last_stream)); HIPCHK(hipStreamWaitEvent(s, c->ev_pset_prev, 0)); }
-    HIPCHK(hipEventRecord(c->ev0, s));
-    if (rates_dev && bw_to(c, s)) return 1;                                  /* the one-wave kernels on s read the sizes: the plan kernel in front of them */
-    if (enc_launch(c, pcm, bitdepth, n_frames, (uint8_t*)out, out_stride, s, nullptr, n_frames, 0, true, rates_dev ? c->d_pfsz[k] : nullptr,
-                   bws_dev ? c->d_pbw[k] : nullptr)) return 1;
-    if (c->pl.pending) return 1;                                             /* every path reads the words */
-    hipLaunchKernelGGL(lc3_enc_rates_tail_kernel, dim3((unsigned)((c->ncs + WAVE - 1) / WAVE)), dim3(WAVE), 0, s, (const int4*)c->d_pend[k], (const lc3d_chan*)c->d_etab,
-                       c->d_chans, c->channels, c->ncs, rule->dms, rates_dev ? 1 : 0);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(c->ev1, s));
-    HIPCHK(hipEventRecord(c->ev_pset[k], s)); c->pset_armed[k] = 1; c->pset = (k + 1) % LC3D_SETS;
-    /* the configuration the tail kernel wrote: later calls on other streams wait for it (as for lc3hip_upload_chans_async); a call that overlaps this one may
-     * do so only where the tail changed the bandwidth words alone */
-    if (!c->ev_chans) HIPCHK(hipEventCreateWithFlags(&c->ev_chans, hipEventDisableTiming));
-    HIPCHK(hipEventRecord(c->ev_chans, s)); c->chans_armed = 1;
-    c->cfg_fresh = (rates_dev || clear_resets) ? 2 : 1;
-    /* what the launch decisions know of the configuration until the host reads it back: with rates any stream may now have attack handling, and channel
-     * frames of any size of the table */
-    if (rates_dev) { c->any_attack |= c->etab_attack; c->max_nbytes = c->etab_max; c->min_nbytes = 1; }
-    if (c->opt.check_ready && c->ev_ours) { HIPCHK(hipEventRecord(c->ev_ours, s)); c->ours_armed = 1; }
-    c->last_stream = s;
-    if (sync) {
-        HIPCHK(hipStreamSynchronize(s));
-        float ms = 0; if (hipEventElapsedTime(&ms, c->ev0, c->ev1) == hipSuccess) c->last_ms = ms;
-    }
-    return 0;
-}
-/* Packed output: the call of lc3hip_encode_rates_device (rates_dev or bws_dev given) or of lc3hip_encode with device pointers (neither), with the scan of
- * the call's frame sizes in front of its writers and the _pk kernels writing each frame at its offset.  The tables grow as the plan sets do: an earlier
- * call that did not wait may still read the smaller ones, so growing them waits for the device, once. */
-extern "C" int lc3hip_encode_packed(void* ctx, const void* pcm, int bitdepth, int n_frames, const int32_t* rates_dev, const int32_t* bws_dev,
-                                    const lc3d_rate_rule* rule, int order, void* out, long long capacity, long long* offsets_dev, long long* total_dev,
-                                    int32_t* num_bytes_dev, uint8_t* flags_dev, int clear_resets, void* hip_stream, int sync)
-{
-    lc3hip_ctx* c = (lc3hip_ctx*)ctx;
-    HIPCHK(hipSetDevice(c->device));
-    const size_t n = (size_t)c->n_streams * n_frames, nb = (n + PKS_TILE - 1) / PKS_TILE;
-    if (c->poff_cap < n || c->pbsum_cap < nb) {
-        if (c->d_pbsum) HIPCHK(hipDeviceSynchronize());
-        for (int i = 0; i < LC3D_SETS + 1; i++) { if (c->d_poff[i]) HIPCHK(hipFree(c->d_poff[i])); c->d_poff[i] = nullptr; }
-        if (c->d_pbsum) HIPCHK(hipFree(c->d_pbsum));
-        c->d_pbsum = nullptr; c->poff_cap = 0; c->pbsum_cap = 0;
-        for (int i = 0; i < LC3D_SETS + 1; i++) HIPCHK(hipMalloc((void**)&c->d_poff[i], n * sizeof(long long)));
-        HIPCHK(hipMalloc((void**)&c->d_pbsum, (size_t)(LC3D_SETS + 1) * nb * sizeof(long long)));
-        c->poff_cap = n; c->pbsum_cap = nb;
-    }
-    if (!c->ev_scan) HIPCHK(hipEventCreateWithFlags(&c->ev_scan, hipEventDisableTiming));
-    c->pk.on = 1; c->pk.order = order; c->pk.cap = capacity; c->pk.offs = offsets_dev; c->pk.total = total_dev; c->pk.nb = num_bytes_dev; c->pk.fl = flags_dev;
-    c->pk.tab = nullptr;
-    int rc;
-    if (rates_dev || bws_dev)
-        rc = lc3hip_encode_rates_device(ctx, pcm, bitdepth, n_frames, out, 0, rates_dev, bws_dev, rule, num_bytes_dev, flags_dev, clear_resets, hip_stream, sync);
-    else
-        rc = lc3hip_encode(ctx, pcm, 1, bitdepth, n_frames, out, 0, 1, hip_stream, sync, nullptr, nullptr, nullptr);
-    c->pk.on = 0; c->pk.tab = nullptr;
-    return rc;
-}
-/* waits for the batch's last call and copies the configuration of every channel-stream to chans[ncs] (after lc3hip_encode_rates_device) */
-extern "C" int lc3hip_download_chans(void* ctx, lc3d_chan* chans)
-{
-    lc3hip_ctx* c = (lc3hip_ctx*)ctx;
-    HIPCHK(hipSetDevice(c->device));
-    if (c->last_stream) HIPCHK(hipStreamSynchronize(c->last_stream));
-    if (c->chans_armed) HIPCHK(hipEventSynchronize(c->ev_chans));
-    HIPCHK(hipMemcpy(chans, c->d_chans, sizeof(lc3d_chan) * (size_t)c->ncs, hipMemcpyDeviceToHost));
-    return chans_host_side(c, chans, 0, c->ncs);
-}
-
-/* status bits of the last call, [channel-stream][frame] (n = ncs * frames of that call), to host memory */
-extern "C" int lc3hip_last_status(void* ctx, uint8_t* status_host, int n)
-{
-    lc3hip_ctx* c = (lc3hip_ctx*)ctx;
-    HIPCHK(hipSetDevice(c->device));
-    if (n > c->ncs * c->status_frames) n = c->ncs * c->status_frames;
-    if (c->last_stream) HIPCHK(hipStreamSynchronize(c->last_stream));
-    if (n > 0) HIPCHK(hipMemcpy(status_host, c->d_status, (size_t)n, hipMemcpyDeviceToHost));
-    return n;
-}
-
-/* the per-frame records of the last call of the pipelined path (FR_* in lc3_plan.h: scale factors, SNS indices, bandwidth, LTPF and TNS parameters, gain floor,
- * the rate kernel's four words), [channel-stream][frame][FR_WORDS] to host memory: stage-level parity tests of the product path read them */
-extern "C" int lc3hip_last_records(void* ctx, float* rec_host, int max_words)
-{
-    lc3hip_ctx* c = (lc3hip_ctx*)ctx;
-    if (!c || !c->last_frec) return 0;
-    HIPCHK(hipSetDevice(c->device));
-    if (c->last_stream) HIPCHK(hipStreamSynchronize(c->last_stream));
-    long long n = (long long)c->ncs * c->last_frec_frames * FR_WORDS;
-    if (n > max_words) n = max_words;
-    if (n > 0) HIPCHK(hipMemcpy(rec_host, c->last_frec, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
-    return (int)n;
-}
-
-/* checkpoint / resume: the cross-frame state of every channel-stream (LC3D_STATE_WORDS words each, the layout of lc3_plan.h) as one host
- * array; everything else a batch holds is derived from its configuration.  Both wait for the last call to finish. */
-extern "C" size_t lc3hip_state_bytes(void* ctx) { lc3hip_ctx* c = (lc3hip_ctx*)ctx; return c ? sizeof(float) * (size_t)c->state_words * (size_t)c->ncs : 0; }
-extern "C" int lc3hip_get_state(void* ctx, void* host, size_t bytes)
-{
-    lc3hip_ctx* c = (lc3hip_ctx*)ctx;
-    if (!c || !host || bytes != lc3hip_state_bytes(ctx)) return 1;
-    HIPCHK(hipSetDevice(c->device));
-    if (c->last_stream) HIPCHK(hipStreamSynchronize(c->last_stream));
-    HIPCHK(hipMemcpy(host, c->d_state, bytes, hipMemcpyDeviceToHost));
-    return 0;
-}
-extern "C" int lc3hip_set_state(void* ctx, const void* host, size_t bytes)
-{
-    lc3hip_ctx* c = (lc3hip_ctx*)ctx;
-    if (!c || !host || bytes != lc3hip_state_bytes(ctx)) return 1;
-    HIPCHK(hipSetDevice(c->device));
-    if (c->last_stream) HIPCHK(hipStreamSynchronize(c->last_stream));
-    HIPCHK(hipMemcpy(c->d_state, host, bytes, hipMemcpyHostToDevice));
-    c->ahead_ok = 0;                       /* the MDCT memory is in the state, not in a previous call's hand-over */
-    return 0;
-}
-
-extern "C" int lc3hip_stream_state(void* ctx, int mode, const int* streams, int n, const lc3d_chan* cfg, void* blob, int blob_on_device, const uint32_t* hdr,
-                                   uint8_t* status, void* hip_stream, int sync)
-{
-    lc3hip_ctx* c = (lc3hip_ctx*)ctx;
-    HIPCHK(hipSetDevice(c->device));
-    if (!hip_stream && !c->stream) HIPCHK(hipStreamCreate(&c->stream));
-    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : c->stream;
-    /* behind the batch's last call: on its stream the writer, and the rate chain of a pipelined call, whose last rate kernel has written the MDCT memory
-     * into the state (the side streams carry nothing of that call's state work beyond it); behind a configuration copy queued on another stream */
-    if (c->chans_armed) HIPCHK(hipStreamWaitEvent(s, c->ev_chans, 0));
-    if (ss_run(&c->ss, s, c->last_stream, mode, c->d_state, c->channels, streams, n, cfg, (int)sizeof(lc3d_chan), c->d_chans, blob, blob_on_device, hdr, status, sync)) return 1;
-    /* every later call waits for this one on its own stream (ev_chans: encode, the configuration copies); the next call does not read the MDCT memory from a
-     * hand-over, and starts its side streams behind this call */
-    if (!c->ev_chans) HIPCHK(hipEventCreateWithFlags(&c->ev_chans, hipEventDisableTiming));
-    HIPCHK(hipEventRecord(c->ev_chans, s)); c->chans_armed = 1;
-    c->ahead_ok = 0;
-    c->last_stream = s;
-    if (cfg) c->carry_seed = 1;
-    return cfg ? chans_host_side_list(c, cfg, 0, n * c->channels, streams) : 0;
-}
-
-extern "C" int lc3hip_set_input_ready(void* ctx, int ready)
-{
-    lc3hip_ctx* c = (lc3hip_ctx*)ctx;
-    if (!c) return 1;
-    c->input_ready = ready != 0; c->ahead_ok = 0;
-    return 0;
-}
-
-extern "C" float lc3hip_last_ms(void* ctx)
-{
-    lc3hip_ctx* c = (lc3hip_ctx*)ctx;
-    float ms = 0;
-    if (hipEventSynchronize(c->ev1) == hipSuccess && hipEventElapsedTime(&ms, c->ev0, c->ev1) == hipSuccess) c->last_ms = ms;
-    return c->last_ms;
-}
-
-extern "C" int lc3hip_destroy(void* ctx)
-{
-    lc3hip_ctx* c = (lc3hip_ctx*)ctx;
-    if (!c) return 0;
-    hipSetDevice(c->device);
-    hipDeviceSynchronize();
-    if (c->d_plan) hipFree(c->d_plan);
-    if (c->d_chans) hipFree(c->d_chans);
-    if (c->d_state) hipFree(c->d_state);
-    if (c->d_pcm) hipFree(c->d_pcm);
-    if (c->d_out) hipFree(c->d_out);
-    for (int i = 0; i < LC3D_SETS; i++) { if (c->d_dumpv[i]) hipFree(c->d_dumpv[i]); if (c->d_statusv[i]) hipFree(c->d_statusv[i]); }
-    for (int i = 0; i < LC3D_SETS; i++) if (c->d_y12[i]) hipFree(c->d_y12[i]);
-    if (c->d_trace) hipFree(c->d_trace);
-    for (int i = 0; i < LC3D_SETS; i++) { if (c->d_spec[i]) hipFree(c->d_spec[i]); if (c->d_frec[i]) hipFree(c->d_frec[i]); }
-    for (int i = 0; i < LC3D_SETS + 1; i++) if (c->d_xnext[i]) hipFree(c->d_xnext[i]);
-    free(c->h_attack); free(c->h_nb);
-    if (c->d_etab) hipFree(c->d_etab);
-    if (c->h_chans) hipHostFree(c->h_chans);
-    if (c->ev_chans) hipEventDestroy(c->ev_chans);
-    ss_free(&c->ss);
-    for (int i = 0; i < LC3D_SETS; i++) { if (c->d_fsz[i]) hipFree(c->d_fsz[i]); if (c->h_fsz[i]) hipHostFree(c->h_fsz[i]); if (c->ev_fsz[i]) hipEventDestroy(c->ev_fsz[i]); }
-    for (int i = 0; i < LC3D_SETS; i++) { if (c->d_bw[i]) hipFree(c->d_bw[i]); if (c->h_bw[i]) hipHostFree(c->h_bw[i]); if (c->ev_bw[i]) hipEventDestroy(c->ev_bw[i]); }
-    if (c->ev_bwcp) hipEventDestroy(c->ev_bwcp);
-    if (c->d_carry) hipFree(c->d_carry);
-    if (c->ev_plan) { hipEventDestroy(c->ev_plan); hipEventDestroy(c->ev_pset_prev); }
-    for (int i = 0; i < LC3D_SETS + 1; i++) if (c->d_poff[i]) hipFree(c->d_poff[i]);
-    if (c->d_pbsum) hipFree(c->d_pbsum);
-    if (c->ev_scan) hipEventDestroy(c->ev_scan);
-    for (int i = 0; i < LC3D_SETS; i++) { if (c->d_pfsz[i]) hipFree(c->d_pfsz[i]); if (c->d_pbw[i]) hipFree(c->d_pbw[i]); if (c->d_pend[i]) hipFree(c->d_pend[i]); if (c->ev_pset[i]) hipEventDestroy(c->ev_pset[i]); }
-    for (int i = 0; i < 2; i++) {
-        if (c->hp_dpcm[i]) hipFree(c->hp_dpcm[i]);
-        if (c->hp_pin_in[i]) hipHostFree(c->hp_pin_in[i]);
-        if (c->ev_h2d[i]) hipEventDestroy(c->ev_h2d[i]);
-        if (c->ev_k[i]) hipEventDestroy(c->ev_k[i]);
-    }
-    if (c->s_h2d) hipStreamDestroy(c->s_h2d);
-    if (c->s_pre) { if (c->s_pit != c->s_pre) { hipStreamDestroy(c->s_pit); hipStreamDestroy(c->s_ln); } hipStreamDestroy(c->s_pre); hipStreamDestroy(c->s_fr); for (int i = 0; i < 2; i++) { if (c->s_pk[i]) hipStreamDestroy(c->s_pk[i]); hipEventDestroy(c->ev_pk[i]); } hipEventDestroy(c->ev_rate);
-                    for (int i = 0; i < LC3D_MAX_RUNS; i++) { hipEventDestroy(c->ev_h[i]); hipEventDestroy(c->ev_m[i]); hipEventDestroy(c->ev_v[i]); } hipEventDestroy(c->ev_fork); for (int i = 0; i < LC3D_SETS; i++) hipEventDestroy(c->ev_done[i]);
-                    for (int i = 0; i < LC3D_MAX_RUNS; i++) { hipEventDestroy(c->ev_p[i]); hipEventDestroy(c->ev_f[i]); } }
-    if (c->ev0) hipEventDestroy(c->ev0);
-    if (c->ev1) hipEventDestroy(c->ev1);
-    if (c->ev_ours) { hipEventDestroy(c->ev_ours); hipEventDestroy(c->ev_now); }
-    if (c->stream) { hipStreamSynchronize(c->stream); hipStreamDestroy(c->stream); }
-    free(c);
-    return 0;
-}
-/* ---- decoder shim ---- */
-extern "C" __global__ void lc3_dec_imdct_kernel_big(const lc3d_plan* __restrict__ P, const float* __restrict__ state, const int* __restrict__ rec, const float* __restrict__ ws,
-                                                    int T, int ncs, float* __restrict__ ov, lc3d_dec_trace* __restrict__ trace);
-extern "C" __global__ void lc3_dec_synth_kernel_big(const lc3d_plan* __restrict__ P, float* __restrict__ state, const int* __restrict__ rec,
-                                                    const float* __restrict__ ws, const float* __restrict__ ov, int T, void* __restrict__ pcm, int bps, int ncs,
-                                                    uint8_t* __restrict__ status, lc3d_dec_trace* __restrict__ trace);
-#ifndef DEC_SETS
-#define DEC_SETS 3                      /* sets of hand-over buffers (records, spectrum rows) under the decoder's input-ready promise: the parser of call k + 2 may write while call k is synthesised */
-#endif
-struct lc3hip_dctx {
-    lc3hip_opts opt;
-    int device, ncs, n_streams, channels, N, big;
-    lc3d_plan* d_plan; lc3d_dchan* d_chans; float* d_state;
-    uint8_t* d_in; size_t in_cap; void* d_pcm; size_t pcm_cap; uint8_t* d_bfi; size_t bfi_cap;
-    lc3d_dchan* d_tab; int tab_n; uint16_t* d_sizes; size_t sizes_cap;          /* per-frame sizes: configuration per channel byte count, effective size per stream-frame */
-    uint8_t* d_inval; size_t inval_cap;                              /* per-frame sizes from device memory: the frames lost because their size or flag is invalid */
-    lc3d_dec_trace* d_trace; size_t trace_cap; uint8_t* d_status; size_t status_cap;
-    int* d_rec; float* d_ws; float* d_ov; size_t hand_cap; int max_nbytes; int* h_nbytes;
-    hipStream_t stream, last_stream; hipEvent_t ev0, ev1; float last_ms;
-    /* lc3hip_dec_set_input_ready: the parse kernel of a call runs on a stream of its own beside the transform and synthesis of the call before; a
-     * second set of hand-over buffers (records, spectrum rows), alternating */
-    int input_ready, set; int* d_recx[DEC_SETS - 1]; float* d_wsx[DEC_SETS - 1]; size_t handx_cap; hipStream_t s_par, s_plc; hipEvent_t ev_par[DEC_SETS], ev_free[DEC_SETS], ev_plc; int free_armed[DEC_SETS];
-    /* the end of the last ordered call (bad-frame flags, per-frame sizes, status, host pointers) under the promise: the next parse-ahead waits for it */
-    hipEvent_t ev_ord; int ord_pending;
-    lc3hip_ss ss;                                   /* the fresh-row template, lc3hip_dec_stream_state */
-};
-static int dec_side_streams(lc3hip_dctx* c)                       /* the parse-ahead stream, the concealment stream and their events, created once */
-{
-    if (c->s_par) return 0;
-    HIPCHK(hipStreamCreateWithFlags(&c->s_par, hipStreamNonBlocking));
-    for (int i = 0; i < DEC_SETS; i++) { HIPCHK(hipEventCreateWithFlags(&c->ev_par[i], hipEventDisableTiming)); HIPCHK(hipEventCreateWithFlags(&c->ev_free[i], hipEventDisableTiming)); }
-    HIPCHK(hipStreamCreateWithFlags(&c->s_plc, hipStreamNonBlocking)); HIPCHK(hipEventCreateWithFlags(&c->ev_plc, hipEventDisableTiming));
-    HIPCHK(hipEventCreateWithFlags(&c->ev_ord, hipEventDisableTiming));
-    return 0;
-}
-extern "C" int lc3hip_dec_destroy(void* ctx);
-extern "C" int lc3hip_dec_create(void** out_ctx, const lc3d_plan* plan, const float* tmpl, int n_streams, int device)
-{
-    int ndev = 0;
-    *out_ctx = nullptr;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { fprintf(stderr, "lc3plus_hip: no HIP device available (this engine has no CPU fallback)\n"); return 1; }
-    lc3hip_dctx* c = (lc3hip_dctx*)calloc(1, sizeof *c);
-    if (!c) return 1;
-    if (device < 0) { if (hipGetDevice(&device) != hipSuccess) device = 0; }
-    c->device = device;
-    HIPCHK_OR(hipSetDevice(device), free(c));
-    c->n_streams = n_streams; c->channels = plan->channels; c->ncs = n_streams * plan->channels; c->N = plan->N;
-    c->big = LC3D_LAYOUT_BIG(plan->N, plan->la);
-    read_opts(&c->opt);
-    HIPCHK_OR(hipMalloc((void**)&c->d_plan, sizeof(lc3d_plan)), lc3hip_dec_destroy(c));
-    HIPCHK_OR(hipMemcpy(c->d_plan, plan, sizeof(lc3d_plan), hipMemcpyHostToDevice), lc3hip_dec_destroy(c));
-    HIPCHK_OR(hipMalloc((void**)&c->d_chans, sizeof(lc3d_dchan) * c->ncs), lc3hip_dec_destroy(c));
-    HIPCHK_OR(hipMalloc((void**)&c->d_state, sizeof(float) * DST_WORDS * (size_t)c->ncs), lc3hip_dec_destroy(c));
-    if (ss_init(&c->ss, c->device, c->d_state, DST_WORDS, c->ncs, tmpl)) { lc3hip_dec_destroy(c); return 1; }
-    HIPCHK_OR(hipStreamCreate(&c->stream), lc3hip_dec_destroy(c));
-    HIPCHK_OR(hipEventCreate(&c->ev0), lc3hip_dec_destroy(c)); HIPCHK_OR(hipEventCreate(&c->ev1), lc3hip_dec_destroy(c));
-    *out_ctx = c;
-    return 0;
-}
-extern "C" int lc3hip_dec_upload_chans(void* ctx, const lc3d_dchan* chans, int first, int count)
-{
-    lc3hip_dctx* c = (lc3hip_dctx*)ctx;
-    HIPCHK(hipSetDevice(c->device));
-    if (c->last_stream) { HIPCHK(hipStreamSynchronize(c->last_stream)); c->last_stream = nullptr; }
-    HIPCHK(hipMemcpy(c->d_chans + first, chans, sizeof(lc3d_dchan) * count, hipMemcpyHostToDevice));
-    /* the largest frame of the batch selects the parse kernel's staging: keep it exact when sizes shrink again */
-    if (!c->h_nbytes) { c->h_nbytes = (int*)calloc((size_t)c->ncs, sizeof(int)); if (!c->h_nbytes) return 1; }
-    for (int i = 0; i < count; i++) c->h_nbytes[first + i] = chans[i].nbytes;
-    c->max_nbytes = 0;
-    for (int i = 0; i < c->ncs; i++) if (c->h_nbytes[i] > c->max_nbytes) c->max_nbytes = c->h_nbytes[i];
-    return 0;
-}
-extern "C" int lc3hip_dec_upload_table(void* ctx, const lc3d_dchan* tab, int n)
-{
-    lc3hip_dctx* c = (lc3hip_dctx*)ctx;
-    HIPCHK(hipSetDevice(c->device));
-    if (c->d_tab) HIPCHK(hipFree(c->d_tab));
-    c->d_tab = nullptr;
-    HIPCHK(hipMalloc((void**)&c->d_tab, sizeof(lc3d_dchan) * (size_t)n));
-    HIPCHK(hipMemcpy(c->d_tab, tab, sizeof(lc3d_dchan) * (size_t)n, hipMemcpyHostToDevice));
-    c->tab_n = n;
-    return 0;
-}
-extern "C" int lc3hip_dec_download_chans(void* ctx, lc3d_dchan* chans)
-{
-    lc3hip_dctx* c = (lc3hip_dctx*)ctx;
-    HIPCHK(hipSetDevice(c->device));
-    if (c->last_stream) { HIPCHK(hipStreamSynchronize(c->last_stream)); c->last_stream = nullptr; }
-    HIPCHK(hipMemcpy(chans, c->d_chans, sizeof(lc3d_dchan) * c->ncs, hipMemcpyDeviceToHost));
-    if (!c->h_nbytes) { c->h_nbytes = (int*)calloc((size_t)c->ncs, sizeof(int)); if (!c->h_nbytes) return 1; }
-    c->max_nbytes = 0;
-    for (int i = 0; i < c->ncs; i++) { c->h_nbytes[i] = chans[i].nbytes; if (c->h_nbytes[i] > c->max_nbytes) c->max_nbytes = c->h_nbytes[i]; }
-    return 0;
-}
-/* nb_dev: per-frame sizes in device memory (lc3hip_dec_decode_dsizes) - with bfi_dev (or null) and status_dev (or null), all device pointers like frames and pcm */
-static int dec_decode(lc3hip_dctx* c, const void* frames, int frames_on_device, int in_stride, const uint8_t* bfi_host, const uint16_t* sizes_host,
-                      int sizes_max_nbytes, int n_frames, void* pcm, int pcm_on_device, int bps, uint8_t* status_host, void* hip_stream, int sync,
-                      void* trace_host, const int32_t* nb_dev, const uint8_t* bfi_dev, uint8_t* status_dev,
-                      const long long* offs_dev = nullptr /* frames packed (lc3hip_dec_decode_packed): in_stride is then the largest frame */, long long cap = 0)
-{
-    HIPCHK(hipSetDevice(c->device));
-    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : c->stream;
-    if (c->ss.done_armed) HIPCHK(hipStreamWaitEvent(s, c->ss.ev_done, 0));      /* behind the last stream-lifecycle call, whichever stream it was queued on */
-    const size_t in_bytes = (size_t)c->n_streams * n_frames * in_stride;
-    const size_t pcm_bytes = (size_t)c->ncs * n_frames * c->N * (size_t)lc3d_pcm_elem_bytes(bps);
-    const uint8_t* din = (const uint8_t*)frames; void* dpcm = pcm; const uint8_t* dbfi = nullptr; lc3d_dec_trace* dtr = nullptr;
-    if (!frames_on_device) {
-        if (c->in_cap < in_bytes) { if (c->d_in) HIPCHK(hipFree(c->d_in)); HIPCHK(hipMalloc((void**)&c->d_in, in_bytes)); c->in_cap = in_bytes; }
-        HIPCHK(hipMemcpyAsync(c->d_in, frames, in_bytes, hipMemcpyHostToDevice, s));
-        din = c->d_in;
-    }
-    if (!pcm_on_device) {
-        if (c->pcm_cap < pcm_bytes) { if (c->d_pcm) HIPCHK(hipFree(c->d_pcm)); HIPCHK(hipMalloc((void**)&c->d_pcm, pcm_bytes)); c->pcm_cap = pcm_bytes; }
-        dpcm = c->d_pcm;
-    }
-    if (bfi_host) {
-        const size_t fb = (size_t)c->n_streams * n_frames;
-        if (c->bfi_cap < fb) { if (c->d_bfi) HIPCHK(hipFree(c->d_bfi)); HIPCHK(hipMalloc((void**)&c->d_bfi, fb)); c->bfi_cap = fb; }
-        HIPCHK(hipMemcpyAsync(c->d_bfi, bfi_host, fb, hipMemcpyHostToDevice, s));
-        dbfi = c->d_bfi;
-    }
-    const uint16_t* dsizes = nullptr;
-    if (sizes_host) {                                               /* per-frame sizes: the host merged the lost frames into bfi_host, so this call is ordered */
-        if (!bfi_host || !c->d_tab) return 1;
-        const size_t fb = sizeof(uint16_t) * (size_t)c->n_streams * n_frames;
-        if (c->sizes_cap < fb) { if (c->d_sizes) HIPCHK(hipFree(c->d_sizes)); HIPCHK(hipMalloc((void**)&c->d_sizes, fb)); c->sizes_cap = fb; }
-        HIPCHK(hipMemcpyAsync(c->d_sizes, sizes_host, fb, hipMemcpyHostToDevice, s));
-        dsizes = c->d_sizes;
-    }
-    if (trace_host) {
-        const size_t tb = sizeof(lc3d_dec_trace) * (size_t)c->ncs * n_frames;
-        if (c->trace_cap < tb) { if (c->d_trace) HIPCHK(hipFree(c->d_trace)); HIPCHK(hipMalloc((void**)&c->d_trace, tb)); c->trace_cap = tb; }
-        HIPCHK(hipMemsetAsync(c->d_trace, 0, tb, s));
-        dtr = c->d_trace;
-    }
-    uint8_t* dst = nullptr;
-    if (status_host) {
-        const size_t fb = (size_t)c->n_streams * n_frames;
-        if (c->status_cap < fb) { if (c->d_status) HIPCHK(hipFree(c->d_status)); HIPCHK(hipMalloc((void**)&c->d_status, fb)); c->status_cap = fb; }
-        dst = c->d_status;
-    }
-    if (nb_dev) {                                                   /* sizes and flags from device memory: the plan kernel below fills d_sizes / d_bfi / d_inval */
-        if (!c->d_tab) return 1;
-        const size_t fb = (size_t)c->n_streams * n_frames;
-        if (c->sizes_cap < sizeof(uint16_t) * fb || c->bfi_cap < fb || c->inval_cap < fb) {
-            /* a smaller buffer of an earlier call may still be read (calls of this kind do not wait): growing it waits for the device, once; the first
-             * allocation does not */
-            if ((c->d_sizes && c->sizes_cap < sizeof(uint16_t) * fb) || (c->d_bfi && c->bfi_cap < fb) || (c->d_inval && c->inval_cap < fb))
-                HIPCHK(hipDeviceSynchronize());
-            if (c->sizes_cap < sizeof(uint16_t) * fb) { if (c->d_sizes) HIPCHK(hipFree(c->d_sizes)); c->d_sizes = nullptr; c->sizes_cap = 0;
-                                                         HIPCHK(hipMalloc((void**)&c->d_sizes, sizeof(uint16_t) * fb)); c->sizes_cap = sizeof(uint16_t) * fb; }
-            if (c->bfi_cap < fb) { if (c->d_bfi) HIPCHK(hipFree(c->d_bfi)); c->d_bfi = nullptr; c->bfi_cap = 0; HIPCHK(hipMalloc((void**)&c->d_bfi, fb)); c->bfi_cap = fb; }
-            if (c->inval_cap < fb) { if (c->d_inval) HIPCHK(hipFree(c->d_inval)); c->d_inval = nullptr; c->inval_cap = 0; HIPCHK(hipMalloc((void**)&c->d_inval, fb)); c->inval_cap = fb; }
-        }
-        dsizes = c->d_sizes; dbfi = c->d_bfi; dst = status_dev;
-    }
-    {   /* hand-over buffers between the two kernels: records and spectrum rows of every channel-frame of this call */
-        const size_t cf = (size_t)c->ncs * n_frames;
-        if (c->hand_cap < cf) {
-            if (c->d_rec) HIPCHK(hipDeviceSynchronize());            /* an earlier call that did not wait may still read them (not on the first call) */
-            if (c->d_rec) HIPCHK(hipFree(c->d_rec));
-            if (c->d_ws) HIPCHK(hipFree(c->d_ws));
-            if (c->d_ov) HIPCHK(hipFree(c->d_ov));
-            c->d_rec = nullptr; c->d_ws = nullptr; c->d_ov = nullptr; c->hand_cap = 0;
-            HIPCHK(hipMalloc((void**)&c->d_rec, cf * PR_WORDS * sizeof(int)));
-            HIPCHK(hipMalloc((void**)&c->d_ws, cf * WS_ROW(c->N) * sizeof(float)));
-            HIPCHK(hipMalloc((void**)&c->d_ov, cf * (c->big ? OV_ROW_BIG : OV_ROW_STD) * sizeof(float)));
-            c->hand_cap = cf;
-        }
-    }
-    /* Under the input-ready promise (the frames of a call are complete on the device when the call is made) the parse kernel - stateless: a frame's
-     * record and spectrum row depend on that frame's bytes only - does not wait for what is queued on s: it runs on its own stream into the other set of
-     * hand-over buffers while the concealment bookkeeping, transform and synthesis of the call before (the stateful part, in order on s) read theirs. */
-    const bool ahead = c->input_ready && frames_on_device && pcm_on_device && !bfi_host && !trace_host && !status_host && !nb_dev;
-    int* rec_w = c->d_rec; float* ws_w = c->d_ws;
-    if (ahead) {
-        const size_t cf = (size_t)c->ncs * n_frames;
-        if (dec_side_streams(c)) return 1;
-        if (c->handx_cap < cf) {
-            HIPCHK(hipDeviceSynchronize());
-            for (int i = 0; i < DEC_SETS - 1; i++) {
-                if (c->d_recx[i]) HIPCHK(hipFree(c->d_recx[i]));
-                if (c->d_wsx[i]) HIPCHK(hipFree(c->d_wsx[i]));
-                c->d_recx[i] = nullptr; c->d_wsx[i] = nullptr;
-            }
-            c->handx_cap = 0;
-            for (int i = 0; i < DEC_SETS - 1; i++) {
-                HIPCHK(hipMalloc((void**)&c->d_recx[i], cf * PR_WORDS * sizeof(int)));
-                HIPCHK(hipMalloc((void**)&c->d_wsx[i], cf * WS_ROW(c->N) * sizeof(float)));
-            }
-            c->handx_cap = cf;
-        }
-        if (c->set) { rec_w = c->d_recx[c->set - 1]; ws_w = c->d_wsx[c->set - 1]; }
-    }
-    hipStream_t sp = ahead ? c->s_par : s;
-    /* frames of up to 128 bytes are staged in LDS; larger ones would cut the waves per workgroup and are read from global memory */
-    /* (per-frame sizes: the largest channel frame of the call that is not lost - lost frames stage nothing; sizes in device memory are not seen by the
-     * host: the bound it knows, a channel's share of in_stride up to the geometry's largest channel frame - a tight in_stride keeps the staged parser) */
-    const int ch_share = (in_stride + c->channels - 1) / c->channels;
-    const int max_nb = nb_dev ? (ch_share < c->tab_n - 1 ? ch_share : c->tab_n - 1) : dsizes ? sizes_max_nbytes : c->max_nbytes;
-    const int nw_max = max_nb > 128 ? 0 : max_nb > 0 ? (max_nb + 3) / 4 : 1;
-    const int nlw = (WS_ROW(c->N) / 2 + 31) / 32;                          /* >= (ylen / 2 + 31) / 32 of the plan */
-    const size_t per_wave = (size_t)(nw_max + nlw) * WAVE * sizeof(unsigned);
-    int wpg = (int)((64 * 1024 - sizeof(ParseLds)) / per_wave);            /* waves per workgroup: they share the model tables */
-    if (wpg > 4) wpg = 4;
-    if (wpg < 1) { fprintf(stderr, "lc3plus_hip: frame of %d bytes exceeds the parse kernel's LDS staging\n", max_nb); return 1; }
-    const long long tasks = (long long)c->n_streams * n_frames, per_wg = (long long)wpg * WAVE;
-    HIPCHK(hipEventRecord(c->ev0, s));
-    if (nb_dev) {
-        const long long n = (long long)c->n_streams * n_frames;
-        if (offs_dev) hipLaunchKernelGGL(lc3_dec_plan_packed_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, nb_dev, offs_dev, bfi_dev, c->d_tab, c->tab_n,
-                                         c->channels, cap, in_stride, n, c->d_sizes, c->d_bfi, c->d_inval);
-        else
-        hipLaunchKernelGGL(lc3_dec_plan_sizes_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, nb_dev, bfi_dev, c->d_tab, c->tab_n, c->channels, in_stride, n,
-                           c->d_sizes, c->d_bfi, c->d_inval);
-        HIPCHK(hipGetLastError());
-    }
-    /* parse: one stream-frame per lane; concealment bookkeeping: one channel-stream per lane; IMDCT: one channel-frame per wave;
-     * synthesis: one channel-stream per wave (lc3_dec_kernels.inc) */
-    if (ahead && c->free_armed[c->set]) HIPCHK(hipStreamWaitEvent(sp, c->ev_free[c->set], 0));      /* this set was last read by the synthesis of the call DEC_SETS back */
-    /* The first parse-ahead behind an ordered call waits for all of it: that call's transform and synthesis read the first set of hand-over buffers, its
-     * concealment kernel (on s) must not be overtaken by this call's (on s_plc, behind this parser) - both read-modify-write the concealment words
-     * (DS_NBLOST, DS_CUM_ALPHA, DS_PLC_SEED, DS_PREV_BFI) - and with sizes from device memory its tail kernel writes the configuration this parser reads.
-     * Every ordered call made today has completed when this wait is queued: the host-array calls return when they are done, and a call with sizes in
-     * device memory (which returns before its work is done) leaves the host's copy of the configuration stale, so the fixed-size call that makes this
-     * parse-ahead reads it back first (lc3_host.c dec_refresh), waiting for that call on the host.  The event states the order on the device instead of
-     * leaving it to those host waits.  The other direction, an ordered call behind parse-ahead calls, waits on the device for the last of their
-     * concealment kernels (ev_plc, below) - there a device-size call with sync = 0 does rely on it. */
-    if (ahead && c->ord_pending) { HIPCHK(hipStreamWaitEvent(sp, c->ev_ord, 0)); c->ord_pending = 0; }
-    /* How many parse waves a CU holds.  The kernel for frames of more than 128 bytes reads its frames from global memory and needs little LDS, so its 4 096
-     * waves of 128 registers fill every SIMD, and the 64-wave concealment kernel and the transform of the call before wait for parse waves to retire; 24 KB of
-     * padding per workgroup leave room beside them: d5 81.3 -> 88.7 Mframes/s (20 KB: 87.1, 28 KB: 77.1).  The kernel that stages its frames in LDS (d1) loses
-     * with any padding (129 -> 117 at 16 KB): none there. */
-    /* (the rule in bytes: the workgroup's LDS - tables, its waves' slices, padding - is a quarter of the CU's 160 KB, so that exactly four of them fit; that was 24 KB of padding
-     * with the tables of the time) */
-    const size_t quarter = (160u << 10) / 4, used = sizeof(ParseLds) + per_wave * wpg;
-    const size_t pad = c->opt.dec_parse_pad_kb >= 0 ? (size_t)c->opt.dec_parse_pad_kb << 10 : (nw_max || used >= quarter ? 0 : quarter - used);
-    auto parse = dsizes ? (nw_max ? lc3_dec_parse_kernel_var : lc3_dec_parse_kernel_g_var) : (nw_max ? lc3_dec_parse_kernel : lc3_dec_parse_kernel_g);
-    if (offs_dev) hipLaunchKernelGGL(nw_max ? lc3_dec_parse_kernel_var_pk : lc3_dec_parse_kernel_g_var_pk, dim3((unsigned)((tasks + per_wg - 1) / per_wg)), dim3(wpg * WAVE),
-                                     per_wave * wpg + pad, sp, c->d_plan, c->d_chans, din, offs_dev, dbfi, dsizes, c->d_tab, n_frames, c->n_streams, nw_max, rec_w, ws_w,
-                                     WS_ROW(c->N));
-    else
-    hipLaunchKernelGGL(parse, dim3((unsigned)((tasks + per_wg - 1) / per_wg)), dim3(wpg * WAVE), per_wave * wpg + pad, sp, c->d_plan, c->d_chans, din, in_stride,
-                       dbfi, dsizes, c->d_tab, n_frames, c->n_streams, nw_max, rec_w, ws_w, WS_ROW(c->N));
-    HIPCHK(hipGetLastError());
-    /* The concealment bookkeeping needs its call's parser and the bookkeeping of the call before - NOT the transform or the synthesis of the call before.  On the caller's stream it
-     * became runnable at the moment the NEXT call's parser did (both behind the previous synthesis; the parser waits for its set of hand-over buffers), lost the race for the SIMDs to
-     * 4 096 parse waves of 128 registers, and took 0.9 ms for 0.05 ms of work - on the stream that bounds the call (timeline in profiles/experiments/r04_what_bounds.md, section 8).
-     * On a stream of its own it runs the moment its parser ends, while the chip has room. */
-    hipStream_t spl = s;
-    if (ahead && c->opt.dec_plc_stream) {
-        spl = c->s_plc;
-        HIPCHK(hipEventRecord(c->ev_par[c->set], sp)); HIPCHK(hipStreamWaitEvent(spl, c->ev_par[c->set], 0));
-    } else if (ahead) { HIPCHK(hipEventRecord(c->ev_par[c->set], sp)); HIPCHK(hipStreamWaitEvent(s, c->ev_par[c->set], 0)); }
-    else if (c->s_plc) HIPCHK(hipStreamWaitEvent(s, c->ev_plc, 0));      /* an ordered call behind ahead calls: the bookkeeping is a chain (the event of the last one, if any: waiting on a fresh event is a no-op) */
-    hipLaunchKernelGGL(lc3_dec_plc_kernel, dim3((unsigned)((c->ncs + WAVE - 1) / WAVE)), dim3(WAVE), 0, spl, c->d_plan, c->d_chans, dsizes, c->d_tab, c->d_state, rec_w, n_frames, c->ncs);
-    HIPCHK(hipGetLastError());
-    if (spl != s) { HIPCHK(hipEventRecord(c->ev_plc, spl)); HIPCHK(hipStreamWaitEvent(s, c->ev_plc, 0)); }
-    const unsigned ncf = (unsigned)((size_t)c->ncs * ((n_frames + IMDCT_FPW - 1) / IMDCT_FPW));     /* runs of IMDCT_FPW frames */
-    if (c->big) {
-        hipLaunchKernelGGL(lc3_dec_imdct_kernel_big, dim3(ncf), dim3(WAVE), 0, s, c->d_plan, c->d_state, rec_w, ws_w, n_frames, c->ncs, c->d_ov, dtr);
-        hipLaunchKernelGGL(lc3_dec_synth_kernel_big, dim3(c->ncs), dim3(WAVE), 0, s, c->d_plan, c->d_state, rec_w, ws_w, c->d_ov, n_frames, dpcm, bps, c->ncs, dst, dtr);
-    } else {
-        const int i4 = c->opt.dec_imdct4;
-        if (i4 && !dtr && c->N == 480)
-            hipLaunchKernelGGL(lc3_dec_imdct4_kernel, dim3((unsigned)((size_t)c->ncs * ((n_frames + 3) / 4))), dim3(WAVE), 0, s, c->d_plan, c->d_state, rec_w, ws_w, n_frames, c->ncs, c->d_ov);
-        else
-        hipLaunchKernelGGL(lc3_dec_imdct_kernel, dim3(ncf), dim3(WAVE), 0, s, c->d_plan, c->d_state, rec_w, ws_w, n_frames, c->ncs, c->d_ov, dtr);
-        hipLaunchKernelGGL(lc3_dec_synth_kernel, dim3(c->ncs), dim3(WAVE), 0, s, c->d_plan, c->d_state, rec_w, ws_w, c->d_ov, n_frames, dpcm, bps, c->ncs, dst, dtr);
-    }
-    HIPCHK(hipGetLastError());
-    if (nb_dev) {                                                    /* behind the synthesis: the status bits and the stream's configuration for the next call */
-        const long long n = (long long)c->n_streams * n_frames;
-        hipLaunchKernelGGL(lc3_dec_sizes_tail_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, c->d_sizes, c->d_inval, c->d_tab, c->channels,
-                           c->n_streams, n_frames, c->d_chans, dst);
-        HIPCHK(hipGetLastError());
-    }
-    if (ahead) { HIPCHK(hipEventRecord(c->ev_free[c->set], s)); c->free_armed[c->set] = 1; c->set = (c->set + 1) % DEC_SETS; }
-    else if (c->s_par) { HIPCHK(hipEventRecord(c->ev_free[0], s)); c->free_armed[0] = 1; }      /* an ordered call reads the first set: a later parse-ahead into it waits for this one */
-    if (!ahead && c->input_ready) {                                  /* ... and the next parse-ahead waits for the whole call (see above) */
-        if (dec_side_streams(c)) return 1;
-        HIPCHK(hipEventRecord(c->ev_ord, s)); c->ord_pending = 1;
-    }
-    c->last_stream = s;
-    HIPCHK(hipEventRecord(c->ev1, s));
-    if (!pcm_on_device) HIPCHK(hipMemcpyAsync(pcm, dpcm, pcm_bytes, hipMemcpyDeviceToHost, s));
-    if (trace_host) HIPCHK(hipMemcpyAsync(trace_host, dtr, sizeof(lc3d_dec_trace) * (size_t)c->ncs * n_frames, hipMemcpyDeviceToHost, s));
-    if (status_host) HIPCHK(hipMemcpyAsync(status_host, dst, (size_t)c->n_streams * n_frames, hipMemcpyDeviceToHost, s));
-    if (sync || !pcm_on_device || !frames_on_device || trace_host || bfi_host || status_host) {
-        HIPCHK(hipStreamSynchronize(s));
-        float ms = 0; if (hipEventElapsedTime(&ms, c->ev0, c->ev1) == hipSuccess) c->last_ms = ms;
-    }
-    return 0;
-}
-extern "C" int lc3hip_dec_decode(void* ctx, const void* frames, int frames_on_device, int in_stride, const uint8_t* bfi_host, const uint16_t* sizes_host,
-                                 int sizes_max_nbytes, int n_frames, void* pcm, int pcm_on_device, int bps, uint8_t* status_host, void* hip_stream, int sync,
-                                 void* trace_host)
-{
-    return dec_decode((lc3hip_dctx*)ctx, frames, frames_on_device, in_stride, bfi_host, sizes_host, sizes_max_nbytes, n_frames, pcm, pcm_on_device, bps, status_host,
-                      hip_stream, sync, trace_host, nullptr, nullptr, nullptr);
-}
-extern "C" int lc3hip_dec_decode_dsizes(void* ctx, const void* frames, int in_stride, const int32_t* num_bytes_dev, const uint8_t* bfi_dev, int n_frames,
-                                        void* pcm, int bps, uint8_t* status_dev, void* hip_stream, int sync)
-{
-    return dec_decode((lc3hip_dctx*)ctx, frames, 1, in_stride, nullptr, nullptr, 0, n_frames, pcm, 1, bps, nullptr, hip_stream, sync, nullptr,
-                      num_bytes_dev, bfi_dev, status_dev);
-}
-extern "C" int lc3hip_dec_decode_packed(void* ctx, const void* frames, long long capacity, const long long* offsets_dev, const int32_t* num_bytes_dev, int max_bytes,
-                                        const uint8_t* bfi_dev, int n_frames, void* pcm, int bps, uint8_t* status_dev, void* hip_stream, int sync)
-{
-    return dec_decode((lc3hip_dctx*)ctx, frames, 1, max_bytes, nullptr, nullptr, 0, n_frames, pcm, 1, bps, nullptr, hip_stream, sync, nullptr,
-                      num_bytes_dev, bfi_dev, status_dev, offsets_dev, capacity);
-}
-extern "C" int lc3hip_dec_stream_state(void* ctx, int mode, const int* streams, int n, const lc3d_dchan* cfg, void* blob, int blob_on_device, const uint32_t* hdr,
-                                       uint8_t* status, void* hip_stream, int sync)
-{
-    lc3hip_dctx* c = (lc3hip_dctx*)ctx;
-    HIPCHK(hipSetDevice(c->device));
-    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : c->stream;
-    /* behind the batch's last call: a parse-ahead call's concealment kernel (its stream's tail waits for it) and a device-size call's configuration tail included */
-    if (ss_run(&c->ss, s, c->last_stream, mode, c->d_state, c->channels, streams, n, cfg, (int)sizeof(lc3d_dchan), c->d_chans, blob, blob_on_device, hdr, status, sync)) return 1;
-    c->last_stream = s;
-    /* the next parse-ahead reads the configuration and its concealment kernel the state this call writes: it waits for this call, as behind an ordered call */
-    if (c->input_ready) { if (dec_side_streams(c)) return 1; HIPCHK(hipEventRecord(c->ev_ord, s)); c->ord_pending = 1; }
-    if (cfg) {                                  /* the largest frame of the batch selects the parser's staging */
-        if (!c->h_nbytes) { c->h_nbytes = (int*)calloc((size_t)c->ncs, sizeof(int)); if (!c->h_nbytes) return 1; }
-        for (int i = 0; i < n * c->channels; i++) c->h_nbytes[streams[i / c->channels] * c->channels + i % c->channels] = cfg[i].nbytes;
-        c->max_nbytes = 0;
-        for (int i = 0; i < c->ncs; i++) if (c->h_nbytes[i] > c->max_nbytes) c->max_nbytes = c->h_nbytes[i];
-    }
-    return 0;
-}
-extern "C" int lc3hip_dec_set_input_ready(void* ctx, int ready)
-{
-    lc3hip_dctx* c = (lc3hip_dctx*)ctx;
-    if (!c) return 1;
-    /* 0 -> 1: an ordered call made before the promise may still be reading the first set of hand-over buffers, and it recorded no event a parse-ahead
-     * could wait for (the side stream and its events exist from the first ahead call on): drain it once, as the encoder side does by clearing ahead_ok */
-    if (ready && !c->input_ready && c->last_stream) { HIPCHK(hipSetDevice(c->device)); HIPCHK(hipStreamSynchronize(c->last_stream)); }
-    c->input_ready = ready != 0;
-    return 0;
-}
-extern "C" size_t lc3hip_dec_state_bytes(void* ctx) { lc3hip_dctx* c = (lc3hip_dctx*)ctx; return c ? sizeof(float) * (size_t)DST_WORDS * (size_t)c->ncs : 0; }
-extern "C" int lc3hip_dec_get_state(void* ctx, void* host, size_t bytes)
-{
-    lc3hip_dctx* c = (lc3hip_dctx*)ctx;
-    if (!c || !host || bytes != lc3hip_dec_state_bytes(ctx)) return 1;
-    HIPCHK(hipSetDevice(c->device));
-    if (c->last_stream) HIPCHK(hipStreamSynchronize(c->last_stream));
-    HIPCHK(hipMemcpy(host, c->d_state, bytes, hipMemcpyDeviceToHost));
-    return 0;
-}
-extern "C" int lc3hip_dec_set_state(void* ctx, const void* host, size_t bytes)
-{
-    lc3hip_dctx* c = (lc3hip_dctx*)ctx;
-    if (!c || !host || bytes != lc3hip_dec_state_bytes(ctx)) return 1;
-    HIPCHK(hipSetDevice(c->device));
-    if (c->last_stream) HIPCHK(hipStreamSynchronize(c->last_stream));
-    HIPCHK(hipMemcpy(c->d_state, host, bytes, hipMemcpyHostToDevice));
-    return 0;
-}
-extern "C" float lc3hip_dec_last_ms(void* ctx) { return ctx ? ((lc3hip_dctx*)ctx)->last_ms : 0.0f; }
-extern "C" int lc3hip_dec_destroy(void* ctx)
-{
-    lc3hip_dctx* c = (lc3hip_dctx*)ctx;
-    if (!c) return 0;
-    hipSetDevice(c->device);
-    hipDeviceSynchronize();
-    void* bufs[] = {c->d_plan, c->d_chans, c->d_state, c->d_in, c->d_pcm, c->d_bfi, c->d_trace, c->d_status, c->d_rec, c->d_ws, c->d_ov, c->d_tab, c->d_sizes, c->d_inval};
-    for (int i = 0; i < DEC_SETS - 1; i++) { if (c->d_recx[i]) hipFree(c->d_recx[i]); if (c->d_wsx[i]) hipFree(c->d_wsx[i]); }
-    if (c->s_par) { hipStreamDestroy(c->s_par); for (int i = 0; i < DEC_SETS; i++) { hipEventDestroy(c->ev_par[i]); hipEventDestroy(c->ev_free[i]); } hipStreamDestroy(c->s_plc); hipEventDestroy(c->ev_plc); hipEventDestroy(c->ev_ord); }
-    for (void* p : bufs) if (p) hipFree(p);
-    if (c->stream) hipStreamDestroy(c->stream);
-    if (c->ev0) hipEventDestroy(c->ev0);
-    if (c->ev1) hipEventDestroy(c->ev1);
-    ss_free(&c->ss);
-    free(c->h_nbytes);
-    free(c);
-    return 0;
-}
+#include "lc3_util_kernels.inc"
 #endif /* !LC3_BIG */
-#endif  /* !LC3_ENC_VAR && !LC3_ENC_VBW && !LC3_ENC_PACKED */
+#endif /* LC3_TU_MAIN */

@@ -1,4 +1,4 @@
-/* lc3_shim.h -- the thin C-ABI between the host C code (lc3_host.c) and the HIP side (lc3_kernels.hip). */
+/* lc3_shim.h -- the thin C-ABI between the host C code (lc3_host.c) and the HIP side (lc3_runtime.hip, which launches the kernels of lc3_kernels.hip). */
 #ifndef LC3_SHIM_H
 #define LC3_SHIM_H
 #include <stdint.h>

@@ -29,19 +29,24 @@ def readelf():
     sys.exit("llvm-readelf not found (ROCM_PATH/llvm/bin or PATH)")
 
 
-def fatbin(path):
-    """the bytes of the ELF64 section .hip_fatbin"""
-    d = open(path, "rb").read()
+def section(d, want):
+    """the bytes of section `want` of the ELF64 image d, or None"""
     assert d[:4] == b"\x7fELF" and d[4] == 2, "not an ELF64 file"
     shoff, = struct.unpack_from("<Q", d, 0x28)
     shentsize, shnum, shstrndx = struct.unpack_from("<HHH", d, 0x3A)
     sec = [struct.unpack_from("<IIQQQQIIQQ", d, shoff + i * shentsize) for i in range(shnum)]
     stroff = sec[shstrndx][4]
     for s in sec:
-        name = d[stroff + s[0]:d.index(b"\0", stroff + s[0])]
-        if name == b".hip_fatbin":
+        if d[stroff + s[0]:d.index(b"\0", stroff + s[0])] == want:
             return d[s[4]:s[4] + s[5]]
-    sys.exit("no .hip_fatbin section in %s" % path)
+    return None
+
+
+def fatbin(path):
+    fb = section(open(path, "rb").read(), b".hip_fatbin")
+    if fb is None:
+        sys.exit("no .hip_fatbin section in %s" % path)
+    return fb
 
 
 def code_objects(fb, arch):
@@ -58,20 +63,24 @@ def code_objects(fb, arch):
         pos = fb.find(MAGIC, pos + 1)
 
 
+def object_kernels(co, fields=FIELDS):
+    """{kernel name: metadata values} of one code object"""
+    out = {}
+    with tempfile.NamedTemporaryFile(suffix=".co") as f:
+        f.write(co)
+        f.flush()
+        notes = subprocess.run([readelf(), "--notes", f.name], check=True, capture_output=True, text=True).stdout
+    for block in re.split(r"\n\s+- \.", "\n" + notes):          # one list item of amdhsa.kernels per block
+        vals = {m.group(1): m.group(2) for m in re.finditer(r"(\.[a-z_]+):\s+(\S+)", "." + block)}
+        if ".symbol" in vals and ".name" in vals and ".vgpr_count" in vals:
+            out[vals[".name"].strip("'\"")] = tuple(int(vals.get(k, "0")) for k in fields)
+    return out
+
+
 def kernels(path, arch):
     out = {}
-    tool = readelf()
     for co in code_objects(fatbin(path), arch):
-        with tempfile.NamedTemporaryFile(suffix=".co") as f:
-            f.write(co)
-            f.flush()
-            notes = subprocess.run([tool, "--notes", f.name], check=True, capture_output=True, text=True).stdout
-        cur = None
-        for block in re.split(r"\n\s+- \.", "\n" + notes):          # one list item of amdhsa.kernels per block
-            vals = {m.group(1): m.group(2) for m in re.finditer(r"(\.[a-z_]+):\s+(\S+)", "." + block)}
-            if ".symbol" in vals and ".name" in vals and ".vgpr_count" in vals:
-                cur = vals[".name"].strip("'\"")
-                out[cur] = tuple(int(vals.get(k, "0")) for k in FIELDS)
+        out.update(object_kernels(co))
     return out
 
 

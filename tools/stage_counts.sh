@@ -10,7 +10,8 @@ VAR=$SRC/variants
 ORDER="0 2 3 4 5 1 6 7 8 9 10 11 12 13 14 15 16 17"
 if [ "$1" = build ]; then
   mkdir -p $VAR
-  build_one() { k=$1; hipcc -O3 -ffp-contract=off --offload-arch=gfx950 -fPIC -Wno-unused-value -Wno-unused-label -DLC3_STOP_AFTER=$k -c $SRC/lc3_kernels.hip -o $VAR/k$k.o && hipcc --offload-arch=gfx950 -shared -fPIC -o $VAR/stop$k.so $VAR/k$k.o $SRC/lc3_host.o -lm && rm $VAR/k$k.o; }
+  REST=$(make -s -C $SRC print-objs | tr ' ' '\n' | grep -v '/lc3_kernels\.o$')      # the plain kernel object is the variant; every other object is the product's (build it first)
+  build_one() { k=$1; hipcc -O3 -ffp-contract=off --offload-arch=gfx950 -fPIC -Wno-unused-value -Wno-unused-label -DLC3_STOP_AFTER=$k -c $SRC/lc3_kernels.hip -o $VAR/k$k.o && hipcc --offload-arch=gfx950 -shared -fPIC -o $VAR/stop$k.so $VAR/k$k.o $REST -lm && rm $VAR/k$k.o; }
   n=0
   for k in $ORDER; do build_one $k & n=$((n+1)); if [ $((n % 6)) = 0 ]; then wait; fi; done
   wait; ls $VAR
