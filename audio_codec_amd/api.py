@@ -35,6 +35,16 @@ EXPORTS = [
     "lc3plus_enc_batch_encode_rates_device", "lc3plus_enc_plan_rates_lenient",
     "lc3plus_enc_batch_encode_packed", "lc3plus_plan_packed", "lc3plus_dec_batch_decode_packed", "lc3plus_dec_plan_packed_lenient",
     "lc3plus_pcm_format_check", "lc3plus_pcm_offset",
+    "lc3plus_shard_block",
+    "lc3plus_enc_sharded_create", "lc3plus_enc_sharded_destroy", "lc3plus_enc_sharded_shards", "lc3plus_enc_sharded_shard", "lc3plus_enc_sharded_device",
+    "lc3plus_enc_sharded_owner", "lc3plus_enc_sharded_input_samples", "lc3plus_enc_sharded_num_bytes", "lc3plus_enc_sharded_stride",
+    "lc3plus_enc_sharded_set_bitrate", "lc3plus_enc_sharded_set_bandwidth", "lc3plus_enc_sharded_bandwidth", "lc3plus_enc_sharded_encode",
+    "lc3plus_enc_sharded_encode_device", "lc3plus_enc_sharded_state_size", "lc3plus_enc_sharded_get_state", "lc3plus_enc_sharded_set_state",
+    "lc3plus_enc_sharded_last_kernel_ms",
+    "lc3plus_dec_sharded_create", "lc3plus_dec_sharded_destroy", "lc3plus_dec_sharded_shards", "lc3plus_dec_sharded_shard", "lc3plus_dec_sharded_device",
+    "lc3plus_dec_sharded_owner", "lc3plus_dec_sharded_output_samples", "lc3plus_dec_sharded_delay", "lc3plus_dec_sharded_num_bytes",
+    "lc3plus_dec_sharded_set_num_bytes", "lc3plus_dec_sharded_decode", "lc3plus_dec_sharded_decode_device", "lc3plus_dec_sharded_state_size",
+    "lc3plus_dec_sharded_get_state", "lc3plus_dec_sharded_set_state", "lc3plus_dec_sharded_last_kernel_ms",
 ]
 # the PCM format word of the batch calls (include/lc3plus_batch.h): a sample type - 16, 24, 32 or PCM_FLOAT32 - alone or with one layout
 PCM_FLOAT32, PCM_INTERLEAVED, PCM_CHANNEL_MAJOR = 0x80, 0x100, 0x200
@@ -58,6 +68,33 @@ def lib_path():
     return os.environ.get("LC3PLUS_HIP_LIB") or os.path.join(HERE, "liblc3plus_hip.so")
 
 
+def _declare_sharded(L):
+    """argtypes of the sharded-batch section of include/lc3plus_batch.h (also for the stub build of the host code: tests/test_sharded_cpu.py)."""
+    L.lc3plus_shard_block.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    for nm in ("lc3plus_enc_sharded", "lc3plus_dec_sharded"):
+        f = lambda x: getattr(L, nm + x)
+        f("_create").argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_int]
+        f("_destroy").argtypes = [C.c_void_p]
+        f("_shards").argtypes = [C.c_void_p]
+        f("_shard").argtypes = [C.c_void_p, C.c_int]; f("_shard").restype = C.c_void_p
+        f("_device").argtypes = [C.c_void_p, C.c_int]
+        f("_owner").argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        f("_num_bytes").argtypes = [C.c_void_p, C.c_int]
+        f("_state_size").argtypes = [C.c_void_p]; f("_state_size").restype = C.c_size_t
+        f("_get_state").argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+        f("_set_state").argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+        f("_last_kernel_ms").argtypes = [C.c_void_p, C.c_int]; f("_last_kernel_ms").restype = C.c_float
+    for f in ("lc3plus_enc_sharded_input_samples", "lc3plus_enc_sharded_stride", "lc3plus_dec_sharded_output_samples", "lc3plus_dec_sharded_delay"):
+        getattr(L, f).argtypes = [C.c_void_p]
+    for f in ("lc3plus_enc_sharded_set_bitrate", "lc3plus_enc_sharded_set_bandwidth", "lc3plus_dec_sharded_set_num_bytes"):
+        getattr(L, f).argtypes = [C.c_void_p, C.c_int, C.c_int]
+    L.lc3plus_enc_sharded_bandwidth.argtypes = [C.c_void_p, C.c_int]
+    L.lc3plus_enc_sharded_encode.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
+    L.lc3plus_enc_sharded_encode_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int]
+    L.lc3plus_dec_sharded_decode.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
+    L.lc3plus_dec_sharded_decode_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int]
+
+
 def load_library():
     global _LIB
     if _LIB is None:
@@ -66,6 +103,7 @@ def load_library():
             raise ImportError("liblc3plus_hip.so is not built (run `python -c 'import __graft_entry__ as g; g.build()'`); "
                               "there is no fallback implementation")
         L = C.CDLL(p)
+        _declare_sharded(L)
         L.lc3_enc_set_frame_ms.argtypes = [C.c_void_p, C.c_float]
         L.lc3plus_enc_batch_create.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_float, C.c_int,
                                                C.POINTER(C.c_int), C.c_int]
@@ -278,6 +316,17 @@ class Batch(_StreamLifecycle):
         self.last_num_bytes = None
         self.last_result = 0          # LC3_Error of the last per-frame-bandwidth call: 0, or LC3_BW_WARNING where a value was refused (not raised)
         self.N = self.lib.lc3plus_enc_batch_input_samples(self.h)
+
+    @classmethod
+    def _borrowed(cls, lib, handle, n_streams, samplerate, channels, frame_ms, hrmode):
+        """A Batch over a handle somebody else owns (a shard of a ShardedBatch): close() and the destructor leave the handle alone."""
+        b = object.__new__(cls)
+        b.lib, b.h, b.borrowed = lib, C.c_void_p(handle), True
+        b.n_streams, b.channels = n_streams, channels
+        b.samplerate, b.frame_ms, b.hrmode = samplerate, frame_ms, hrmode
+        b.last_num_bytes, b.last_result = None, 0
+        b.N = lib.lc3plus_enc_batch_input_samples(b.h)
+        return b
 
     @property
     def stride(self):
@@ -496,7 +545,8 @@ class Batch(_StreamLifecycle):
 
     def close(self):
         if self.h:
-            self.lib.lc3plus_enc_batch_destroy(self.h)
+            if not getattr(self, "borrowed", False):
+                self.lib.lc3plus_enc_batch_destroy(self.h)
             self.h = None
 
     def __del__(self):
@@ -673,6 +723,15 @@ class DecBatch(_StreamLifecycle):
 
     _ss = "lc3plus_dec_batch"
 
+    @classmethod
+    def _borrowed(cls, lib, handle, n_streams, channels):
+        """A DecBatch over a handle somebody else owns (a shard of a ShardedDecBatch)."""
+        b = object.__new__(cls)
+        b.lib, b.h, b.borrowed = lib, C.c_void_p(handle), True
+        b.n_streams, b.channels = n_streams, channels
+        b.N = lib.lc3plus_dec_batch_output_samples(b.h)
+        return b
+
     def num_bytes(self, stream):
         return self.lib.lc3plus_dec_batch_num_bytes(self.h, stream)
 
@@ -802,7 +861,8 @@ class DecBatch(_StreamLifecycle):
 
     def close(self):
         if self.h:
-            self.lib.lc3plus_dec_batch_destroy(self.h)
+            if not getattr(self, "borrowed", False):
+                self.lib.lc3plus_dec_batch_destroy(self.h)
             self.h = None
 
     def __del__(self):
@@ -810,6 +870,197 @@ class DecBatch(_StreamLifecycle):
             self.close()
         except Exception:
             pass
+
+
+def shard_block(n_streams, n_shards, shard, lib=None):
+    """(first, count) of the streams shard `shard` of `n_shards` owns (lc3plus_shard_block, no device needed); LC3Error for arguments it refuses."""
+    first, count = C.c_int(0), C.c_int(0)
+    rc = (lib or load_library()).lc3plus_shard_block(n_streams, n_shards, shard, C.byref(first), C.byref(count))
+    if rc:
+        raise LC3Error(rc, "lc3plus_shard_block")
+    return first.value, count.value
+
+
+def _ptr_array(ptrs, n):
+    """n raw pointers (ints or None) as a C array of void*; None for no list."""
+    if ptrs is None:
+        return None
+    ptrs = list(ptrs)
+    if len(ptrs) != n:
+        raise ValueError("one pointer per shard (%d), not %d" % (n, len(ptrs)))
+    return (C.c_void_p * n)(*[C.c_void_p(int(p)) if p else None for p in ptrs])
+
+
+class _Sharded:
+    """What ShardedBatch and ShardedDecBatch share: the shards, their blocks and the checkpoint calls (lc3plus_{enc,dec}_sharded_*)."""
+    _sp = None                                                      # C prefix
+
+    def _f(self, name):
+        return getattr(self.lib, self._sp + name)
+
+    def _create(self, n_streams, samplerate, channels, frame_ms, hrmode, config, devices, lib):
+        self.lib = lib or load_library()
+        cfg = np.ascontiguousarray(config, dtype=np.int32) if config is not None else None
+        if cfg is not None and cfg.size != n_streams:
+            raise ValueError("one configuration value per stream")
+        dev = np.ascontiguousarray(devices, dtype=np.int32) if devices is not None else None
+        self.h = C.c_void_p()
+        rc = self._f("_create")(C.byref(self.h), n_streams, samplerate, channels, frame_ms, hrmode, cfg.ctypes.data if cfg is not None else None,
+                                dev.ctypes.data if dev is not None else None, dev.size if dev is not None else 0)
+        if rc:
+            self.h = None
+            raise LC3Error(rc, self._sp + "_create")
+        self.n_streams, self.channels = n_streams, channels
+        self.samplerate, self.frame_ms, self.hrmode = samplerate, frame_ms, hrmode
+        self.n_shards = self._f("_shards")(self.h)
+        self.devices = [self._f("_device")(self.h, i) for i in range(self.n_shards)]
+        self.blocks = [shard_block(n_streams, self.n_shards, i, self.lib) for i in range(self.n_shards)]
+
+    def owner(self, stream):
+        """(shard, local index) of a global stream index."""
+        k, l = C.c_int(0), C.c_int(0)
+        rc = self._f("_owner")(self.h, stream, C.byref(k), C.byref(l))
+        if rc:
+            raise LC3Error(rc, self._sp + "_owner")
+        return k.value, l.value
+
+    def num_bytes(self, stream):
+        return self._f("_num_bytes")(self.h, stream)
+
+    @property
+    def state_size(self):
+        return int(self._f("_state_size")(self.h))
+
+    def get_state(self):
+        """The shards' states one after the other: the state of an unsharded batch of n_streams (and of a sharded one with any number of shards)."""
+        st = np.zeros(self.state_size, dtype=np.uint8)
+        rc = self._f("_get_state")(self.h, st.ctypes.data, st.size)
+        if rc:
+            raise LC3Error(rc, self._sp + "_get_state")
+        return st
+
+    def set_state(self, st):
+        st = np.ascontiguousarray(st, dtype=np.uint8)
+        rc = self._f("_set_state")(self.h, st.ctypes.data, st.size)
+        if rc:
+            raise LC3Error(rc, self._sp + "_set_state")
+
+    def last_kernel_ms(self, shard):
+        return float(self._f("_last_kernel_ms")(self.h, shard))
+
+    def close(self):
+        if getattr(self, "h", None):
+            self._f("_destroy")(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class ShardedBatch(_Sharded):
+    """n_streams encoders in contiguous blocks over devices (lc3plus_enc_sharded_*; one shard per entry of devices, the same device may appear more than
+    once).  Stream indices are global; encode() takes and returns what Batch.encode() does, byte for byte."""
+    _sp = "lc3plus_enc_sharded"
+
+    def __init__(self, n_streams, samplerate, channels, frame_ms, hrmode, bitrates, devices, lib=None):
+        self._create(n_streams, samplerate, channels, frame_ms, hrmode, bitrates, devices, lib)
+        self.last_num_bytes, self.last_result = None, 0
+        self.N = self.lib.lc3plus_enc_sharded_input_samples(self.h)
+
+    _pcm_in = Batch._pcm_in
+    _bitrates = Batch._bitrates
+
+    def shard(self, i):
+        """The shard's Batch, borrowed: local stream indices (owner()); closing it leaves the shard alone."""
+        h = self.lib.lc3plus_enc_sharded_shard(self.h, i)
+        if not h:
+            raise LC3Error(1, "lc3plus_enc_sharded_shard")
+        return Batch._borrowed(self.lib, h, self.blocks[i][1], self.samplerate, self.channels, self.frame_ms, self.hrmode)
+
+    @property
+    def stride(self):
+        return self.lib.lc3plus_enc_sharded_stride(self.h)
+
+    def set_bitrate(self, stream, bitrate):
+        return self.lib.lc3plus_enc_sharded_set_bitrate(self.h, stream, bitrate)
+
+    def set_bandwidth(self, stream, bw):
+        return self.lib.lc3plus_enc_sharded_set_bandwidth(self.h, stream, bw)
+
+    def bandwidth(self, stream):
+        return self.lib.lc3plus_enc_sharded_bandwidth(self.h, stream)
+
+    def encode(self, pcm, bitdepth=16, bitrates=None, bandwidths=None, layout=None):
+        """As Batch.encode: pcm over all n_streams -> uint8 [n_streams, T, stride]; last_num_bytes [n_streams, T]; last_result 0 or LC3_BW_WARNING."""
+        pcm = np.ascontiguousarray(pcm)
+        fmt, T = self._pcm_in(pcm, bitdepth, layout)
+        br = self._bitrates(bitrates, T) if bitrates is not None else None
+        bw = np.ascontiguousarray(np.broadcast_to(np.asarray(bandwidths, dtype=np.int32), (self.n_streams, T)), dtype=np.int32) if bandwidths is not None else None
+        stride = max(int(enc_plan_bitrates_for(self, br).max()), 1) if br is not None else self.stride
+        if br is None:
+            self.last_num_bytes = np.zeros((self.n_streams, T), dtype=np.int32)
+        out = np.zeros((self.n_streams, T, stride), dtype=np.uint8)
+        rc = self.lib.lc3plus_enc_sharded_encode(self.h, pcm.ctypes.data, fmt, bw.ctypes.data if bw is not None else None,
+                                                 br.ctypes.data if br is not None else None, T, out.ctypes.data, stride, self.last_num_bytes.ctypes.data)
+        if rc not in (0, LC3_BW_WARNING):
+            raise LC3Error(rc, "lc3plus_enc_sharded_encode")
+        self.last_result = rc
+        return out
+
+    def encode_device(self, d_pcm_ptrs, bitdepth, T, d_out_ptrs, out_stride, hip_streams=None, sync=False):
+        """Raw device pointers, one per shard, each on its shard's device and holding that shard's block.  Every shard's call is queued before any is
+        waited for; returns after queueing unless sync."""
+        rc = self.lib.lc3plus_enc_sharded_encode_device(self.h, _ptr_array(d_pcm_ptrs, self.n_shards), bitdepth, T, _ptr_array(d_out_ptrs, self.n_shards),
+                                                        out_stride, _ptr_array(hip_streams, self.n_shards), 1 if sync else 0)
+        if rc:
+            raise LC3Error(rc, "lc3plus_enc_sharded_encode_device")
+
+
+class ShardedDecBatch(_Sharded):
+    """n_streams decoders in contiguous blocks over devices (lc3plus_dec_sharded_*); decode() takes and returns what DecBatch.decode() does."""
+    _sp = "lc3plus_dec_sharded"
+
+    def __init__(self, n_streams, samplerate, channels, frame_ms, hrmode, num_bytes, devices, lib=None):
+        self._create(n_streams, samplerate, channels, frame_ms, hrmode, num_bytes, devices, lib)
+        self.N = self.lib.lc3plus_dec_sharded_output_samples(self.h)
+
+    _prep = DecBatch._prep
+    _sizes = DecBatch._sizes
+
+    def shard(self, i):
+        """The shard's DecBatch, borrowed: local stream indices (owner())."""
+        h = self.lib.lc3plus_dec_sharded_shard(self.h, i)
+        if not h:
+            raise LC3Error(1, "lc3plus_dec_sharded_shard")
+        return DecBatch._borrowed(self.lib, h, self.blocks[i][1], self.channels)
+
+    @property
+    def delay(self):
+        return self.lib.lc3plus_dec_sharded_delay(self.h)
+
+    def set_num_bytes(self, stream, nbytes):
+        return self.lib.lc3plus_dec_sharded_set_num_bytes(self.h, stream, nbytes)
+
+    def decode(self, frames, bfi=None, bps=16, num_bytes=None, layout=None):
+        """As DecBatch.decode: frames uint8 [n_streams, T, stride] -> (pcm, status)."""
+        bps = pcm_format(bps & 0xFF, (bps & 0x300) | (layout if isinstance(layout, int) else PCM_LAYOUTS[layout]))
+        frames, T, stride, bfi, pcm, status = self._prep(frames, bfi, bps)
+        nb = self._sizes(num_bytes, T) if num_bytes is not None else None
+        rc = self.lib.lc3plus_dec_sharded_decode(self.h, frames.ctypes.data, stride, nb.ctypes.data if nb is not None else None,
+                                                 bfi.ctypes.data if bfi is not None else None, T, pcm.ctypes.data, bps, status.ctypes.data)
+        if rc:
+            raise LC3Error(rc, "lc3plus_dec_sharded_decode")
+        return pcm, status
+
+    def decode_device(self, d_frames_ptrs, in_stride, T, d_pcm_ptrs, bps=16, hip_streams=None, sync=False):
+        """Raw device pointers, one per shard, as ShardedBatch.encode_device."""
+        rc = self.lib.lc3plus_dec_sharded_decode_device(self.h, _ptr_array(d_frames_ptrs, self.n_shards), in_stride, T, _ptr_array(d_pcm_ptrs, self.n_shards),
+                                                        bps, _ptr_array(hip_streams, self.n_shards), 1 if sync else 0)
+        if rc:
+            raise LC3Error(rc, "lc3plus_dec_sharded_decode_device")
 
 
 class Decoder:

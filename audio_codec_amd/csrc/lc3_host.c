@@ -9,6 +9,7 @@
  */
 #include <limits.h>
 #include <math.h>
+#include <pthread.h>
 #include <stddef.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -373,8 +374,14 @@ struct lc3plus_batch {
     int chans_stale;                /* a call with rates or bandwidths in device memory has changed the configuration on the device: enc_refresh before reading chans */
     int stride_bound;               /* while chans is stale: the out_stride an encode() needs (stride() before those calls, raised to the out_stride of each with rates) */
     int bw_unsafe;                  /* set_bandwidth has installed a value with a cut-off line below 1 since the last read-back */
+    int dry;                        /* DRY_*: the call checks its arguments as always and returns before it touches the device (sharded batches) */
 };
 
+/* A sharded batch checks a call on every shard before any shard runs it: the per-batch call itself, stopped behind its checks.  The checks of a call come in
+ * the order bandwidth values, rate values, everything else; DRY_BW and DRY_RATES stop behind the first and the second, so that the shards can be walked
+ * once per step and the first refusal is the one an unsharded batch of all the streams gives. */
+enum { DRY_BW = 1, DRY_RATES = 2, DRY_ALL = 3 };
+#define DRY_STOP(b, level, res) do { if ((b)->dry && (b)->dry <= (level)) return (res); } while (0)
 static void batch_restride(lc3plus_batch* b);
 /* Brings the host copy of the configuration back after calls with rates or bandwidths in device memory: waits for the batch's last call and downloads it, once. */
 static LC3_Error enc_refresh(lc3plus_batch* b)
@@ -408,25 +415,34 @@ static void batch_restride(lc3plus_batch* b)
     b->stride = s;
 }
 
-LC3_Error lc3plus_enc_batch_create(lc3plus_batch** out, int n_streams, int samplerate, int channels, float frame_ms, int hrmode,
-                                   const int* bitrates, int device)
+/* the geometry of an encoder batch, or the error create gives for it; no device */
+static LC3_Error enc_batch_geometry(geom_t* g, int n_streams, int samplerate, int channels, float frame_ms, int hrmode)
 {
-    if (!out || !bitrates) return LC3_NULL_ERROR;
-    *out = NULL;
     if (n_streams <= 0) return LC3_ERROR;
     if (!samplerate_ok(samplerate)) return LC3_SAMPLERATE_ERROR;
     if (channels < 1 || channels > MAX_CH) return LC3_CHANNELS_ERROR;
     { int d = (int)ceil(frame_ms * 10); if (d != 25 && d != 50 && d != 100) return LC3_FRAMEMS_ERROR; }
     if (samplerate < 48000 && hrmode != 0) return LC3_SAMPLERATE_ERROR;
+    geom_init(g, samplerate, channels);
+    g->dms = (int)(frame_ms * 10); g->frame_ms = frame_ms; g->hrmode = hrmode > 0;
+    geom_update(g);
+    if (!geom_supported(g)) {
+        fprintf(stderr, "lc3plus_hip: %d Hz / %.1f ms%s is not built into the gfx950 kernels yet\n", samplerate, frame_ms, hrmode ? " hr" : "");
+        return LC3_ERROR;
+    }
+    return LC3_OK;
+}
+
+LC3_Error lc3plus_enc_batch_create(lc3plus_batch** out, int n_streams, int samplerate, int channels, float frame_ms, int hrmode,
+                                   const int* bitrates, int device)
+{
+    if (!out || !bitrates) return LC3_NULL_ERROR;
+    *out = NULL;
+    geom_t g;
+    { LC3_Error e = enc_batch_geometry(&g, n_streams, samplerate, channels, frame_ms, hrmode); if (e) return e; }
     lc3plus_batch* b = (lc3plus_batch*)calloc(1, sizeof *b);
     if (!b) return LC3_ERROR;
-    geom_init(&b->g, samplerate, channels);
-    b->g.dms = (int)(frame_ms * 10); b->g.frame_ms = frame_ms; b->g.hrmode = hrmode > 0;
-    geom_update(&b->g);
-    if (!geom_supported(&b->g)) {
-        fprintf(stderr, "lc3plus_hip: %d Hz / %.1f ms%s is not built into the gfx950 kernels yet\n", samplerate, frame_ms, hrmode ? " hr" : "");
-        free(b); return LC3_ERROR;
-    }
+    b->g = g;
     b->n_streams = n_streams;
     b->chans = (lc3d_chan*)calloc((size_t)n_streams * channels, sizeof(lc3d_chan));
     b->bitrates = (int*)calloc(n_streams, sizeof(int));
@@ -533,6 +549,7 @@ static LC3_Error batch_encode(lc3plus_batch* b, const void* pcm, int pcm_on_devi
     if (!pcm_format_ok(bitdepth)) return LC3_ERROR;
     if (trace && !pcm_format_plain(bitdepth)) return LC3_ERROR;      /* the traced calls take the integer formats in the default layout only */
     if (n_frames <= 0 || out_stride < enc_stride_bound(b)) return LC3_ERROR;
+    DRY_STOP(b, DRY_ALL, LC3_OK);
     if (lc3hip_encode(b->dev, pcm, pcm_on_device, bitdepth, n_frames, out, out_stride, out_on_device, hip_stream, sync, trace, NULL, NULL)) return LC3_ERROR;
     /* one-shot attack-state reset requests have been consumed by this launch (a stale copy has none: the device-rate calls consume them, and nothing of it
      * is uploaded) */
@@ -567,7 +584,9 @@ static LC3_Error batch_encode_bitrates(lc3plus_batch* b, const void* pcm, int pc
     int max_bytes = 0;
     LC3_Error e = enc_plan_bitrates(&b->g, bitrates, n, b->fsz, &max_bytes);
     if (e) return e;
+    DRY_STOP(b, DRY_RATES, LC3_OK);
     if (out_stride < max_bytes) return LC3_ERROR;
+    DRY_STOP(b, DRY_ALL, LC3_OK);
     if (lc3hip_encode(b->dev, pcm, pcm_on_device, bitdepth, n_frames, out, out_stride, out_on_device, hip_stream, sync, trace, b->fsz, NULL)) return LC3_ERROR;
     if (num_bytes) for (size_t i = 0; i < n; i++) num_bytes[i] = b->fsz[i];
     /* every stream is configured with its last frame's rate; the kernel has done every attack-detector reset the call asked for, and the one-shot
@@ -631,6 +650,7 @@ static LC3_Error batch_encode_bandwidths(lc3plus_batch* b, const void* pcm, int 
     if (enc_refresh(b)) return LC3_ERROR;
     const size_t n = (size_t)b->n_streams * (n_frames > 0 ? n_frames : 0);
     if (bandwidths) for (size_t i = 0; i < n; i++) if (!bw_value_ok(bandwidths[i], b->g.dms)) return LC3_ERROR;
+    DRY_STOP(b, DRY_BW, LC3_OK);
     if (!pcm || !out || !bandwidths) return LC3_NULL_ERROR;
     if (!pcm_format_ok(bitdepth)) return LC3_ERROR;
     if (n_frames <= 0) return LC3_ERROR;
@@ -644,6 +664,7 @@ static LC3_Error batch_encode_bandwidths(lc3plus_batch* b, const void* pcm, int 
         int max_bytes = 0;
         LC3_Error e = enc_plan_bitrates(&b->g, bitrates, n, b->fsz, &max_bytes);
         if (e) return e;
+        DRY_STOP(b, DRY_RATES, LC3_OK);
         if (out_stride < max_bytes) return LC3_ERROR;
     } else if (out_stride < b->stride) return LC3_ERROR;
     if (b->bwf_cap < n) {
@@ -661,6 +682,7 @@ static LC3_Error batch_encode_bandwidths(lc3plus_batch* b, const void* pcm, int 
         if (e != LC3_OK && e != LC3_BW_WARNING) return e;
         if (e) res = e;
     }
+    DRY_STOP(b, DRY_ALL, res);
     if (lc3hip_encode(b->dev, pcm, pcm_on_device, bitdepth, n_frames, out, out_stride, out_on_device, hip_stream, sync, NULL, bitrates ? b->fsz : NULL,
                       b->bwf)) return LC3_ERROR;
     if (num_bytes) for (size_t i = 0; i < n; i++) num_bytes[i] = bitrates ? b->fsz[i] : lc3plus_enc_batch_num_bytes(b, (int)(i / n_frames));
@@ -1288,28 +1310,38 @@ struct lc3plus_dec_batch {
     void* dev;
     lc3d_dchan* tab; int tab_n;      /* dec_build_table, also on the device */
     uint16_t* eff; uint8_t* lost; int* sz; size_t plan_cap;          /* per-frame sizes: host buffers of dec_plan_sizes, grown as needed */
+    int dry;                         /* as lc3plus_batch.dry: the call returns behind its checks */
 };
+
+/* the geometry of a decoder batch, or the error create gives for it; no device */
+static LC3_Error dec_batch_geometry(geom_t* g, int n_streams, int samplerate, int channels, float frame_ms, int hrmode)
+{
+    if (n_streams <= 0) return LC3_ERROR;
+    if (!samplerate_ok(samplerate)) return LC3_SAMPLERATE_ERROR;
+    if (channels < 1 || channels > MAX_CH) return LC3_CHANNELS_ERROR;
+    { int d = (int)ceil(frame_ms * 10); if (d != 25 && d != 50 && d != 100) return LC3_FRAMEMS_ERROR; }
+    geom_init(g, samplerate, channels);
+    if (g->fs_idx < 4 && hrmode != 0) return LC3_SAMPLERATE_ERROR;          /* R/lc3.c:350 */
+    if (g->fs_idx == 5 && hrmode == 0) return LC3_HRMODE_ERROR;             /* R/lc3.c:351 */
+    g->dms = (int)(frame_ms * 10); g->frame_ms = frame_ms; g->hrmode = hrmode > 0;
+    geom_update_ex(g, 1);
+    if (!dec_geom_supported(g)) {
+        fprintf(stderr, "lc3plus_hip: decoding %d Hz / %.1f ms%s is not built into the gfx950 kernels yet\n", samplerate, frame_ms, hrmode ? " hr" : "");
+        return LC3_ERROR;
+    }
+    return LC3_OK;
+}
 
 LC3_Error lc3plus_dec_batch_create(lc3plus_dec_batch** out, int n_streams, int samplerate, int channels, float frame_ms, int hrmode,
                                    const int* num_bytes, int device)
 {
     if (!out) return LC3_NULL_ERROR;
     *out = NULL;
-    if (n_streams <= 0) return LC3_ERROR;
-    if (!samplerate_ok(samplerate)) return LC3_SAMPLERATE_ERROR;
-    if (channels < 1 || channels > MAX_CH) return LC3_CHANNELS_ERROR;
-    { int d = (int)ceil(frame_ms * 10); if (d != 25 && d != 50 && d != 100) return LC3_FRAMEMS_ERROR; }
+    geom_t g;
+    { LC3_Error e = dec_batch_geometry(&g, n_streams, samplerate, channels, frame_ms, hrmode); if (e) return e; }
     lc3plus_dec_batch* b = (lc3plus_dec_batch*)calloc(1, sizeof *b);
     if (!b) return LC3_ERROR;
-    geom_init(&b->g, samplerate, channels);
-    if (b->g.fs_idx < 4 && hrmode != 0) { free(b); return LC3_SAMPLERATE_ERROR; }          /* R/lc3.c:350 */
-    if (b->g.fs_idx == 5 && hrmode == 0) { free(b); return LC3_HRMODE_ERROR; }             /* R/lc3.c:351 */
-    b->g.dms = (int)(frame_ms * 10); b->g.frame_ms = frame_ms; b->g.hrmode = hrmode > 0;
-    geom_update_ex(&b->g, 1);
-    if (!dec_geom_supported(&b->g)) {
-        fprintf(stderr, "lc3plus_hip: decoding %d Hz / %.1f ms%s is not built into the gfx950 kernels yet\n", samplerate, frame_ms, hrmode ? " hr" : "");
-        free(b); return LC3_ERROR;
-    }
+    b->g = g;
     b->n_streams = n_streams;
     b->chans = (lc3d_dchan*)calloc((size_t)n_streams * channels, sizeof(lc3d_dchan));
     if (!b->chans) { free(b); return LC3_ERROR; }
@@ -1396,6 +1428,7 @@ static LC3_Error dec_batch_decode(lc3plus_dec_batch* b, const void* frames, int 
     if (n_frames <= 0) return LC3_ERROR;
     if (dec_refresh(b)) return LC3_ERROR;
     for (int i = 0; i < b->n_streams; i++) if (lc3plus_dec_batch_num_bytes(b, i) > in_stride) return LC3_NUMBYTES_ERROR;
+    DRY_STOP(b, DRY_ALL, LC3_OK);
     return lc3hip_dec_decode(b->dev, frames, frames_on_device, in_stride, bfi, NULL, 0, n_frames, pcm, pcm_on_device, bps, status, hip_stream, sync, traces)
                ? LC3_ERROR : LC3_OK;
 }
@@ -1419,6 +1452,7 @@ LC3_Error lc3plus_dec_batch_decode_sizes(lc3plus_dec_batch* b, const void* frame
     int max_chan = 0;
     LC3_Error e = dec_plan_sizes(&b->g, b->tab, b->tab_n, b->n_streams, start, num_bytes, bfi, n_frames, in_stride, b->eff, b->lost, end, &max_chan);
     if (e) return e;
+    DRY_STOP(b, DRY_ALL, LC3_OK);
     /* the kernels take the size of every good frame and 0 for a lost one: the parser reads nothing of a lost frame's slot, and the concealment kernel
      * carries the last good configuration from frame to frame (from the stream's configuration before the call), as dec_plan_sizes does here */
     for (size_t i = 0; i < n; i++) if (b->lost[i]) b->eff[i] = 0;
@@ -1724,4 +1758,431 @@ LC3_Error lc3_dec_free_memory(LC3_Dec* d)
     lc3_free_decoder_structs(d);
     free(d);
     return LC3_OK;
+}
+
+/* ------------------------------------------------------------------------------------------------ */
+/* sharded batches (include/lc3plus_batch.h): N ordinary batches, each with a contiguous block of the  */
+/* streams on a device of its own, driven by one call.  Streams never exchange anything, so a sharded   */
+/* call is the per-batch call of every shard on its slice of the arguments.                             */
+/* ------------------------------------------------------------------------------------------------ */
+LC3_Error lc3plus_shard_block(int n_streams, int n_shards, int shard, int* first, int* count)
+{
+    if (!first || !count) return LC3_NULL_ERROR;
+    if (n_streams < 0 || n_shards <= 0 || shard < 0 || shard >= n_shards) return LC3_ERROR;
+    const int base = n_streams / n_shards, rem = n_streams % n_shards;
+    *first = shard * base + IMIN(shard, rem);
+    *count = base + (shard < rem);
+    return LC3_OK;
+}
+/* the owner of a stream under that rule */
+static void shard_owner(int n_streams, int n_shards, int stream, int* shard, int* local)
+{
+    const int base = n_streams / n_shards, rem = n_streams % n_shards, cut = rem * (base + 1);
+    const int k = stream < cut ? stream / (base + 1) : rem + (stream - cut) / IMAX(base, 1);
+    *shard = k; *local = stream - (k * base + IMIN(k, rem));
+}
+static LC3_Error shard_devices_check(int n_streams, const int* devices, int n_devices)
+{
+    if (!devices) return LC3_NULL_ERROR;
+    if (n_devices <= 0) return LC3_ERROR;
+    for (int i = 0; i < n_devices; i++) if (devices[i] < 0) return LC3_ERROR;
+    return n_streams > 0 && n_devices > n_streams ? LC3_ERROR : LC3_OK;
+}
+
+/* One worker thread per shard, alive from create to destroy.  run() hands every worker the same job function and returns when all have finished it; a
+ * worker calls fn(owner, its shard).  One mutex guards gen / pending / quit; what a job reads was written before run() took it, what it writes is read
+ * after run() has seen pending reach 0 under it. */
+typedef struct shard_pool shard_pool;
+typedef struct { shard_pool* pool; int shard; } shard_worker;
+struct shard_pool {
+    pthread_mutex_t mu; pthread_cond_t go, done;
+    int n, started, gen, pending, quit;
+    pthread_t* th; shard_worker* w;
+    void (*fn)(void* owner, int shard); void* owner;
+};
+static void* shard_worker_main(void* arg)
+{
+    shard_worker* w = (shard_worker*)arg;
+    shard_pool* p = w->pool;
+    int seen = 0;
+    pthread_mutex_lock(&p->mu);
+    for (;;) {
+        while (p->gen == seen && !p->quit) pthread_cond_wait(&p->go, &p->mu);
+        if (p->quit) break;
+        seen = p->gen;
+        void (*fn)(void*, int) = p->fn; void* owner = p->owner;
+        pthread_mutex_unlock(&p->mu);
+        fn(owner, w->shard);
+        pthread_mutex_lock(&p->mu);
+        if (--p->pending == 0) pthread_cond_signal(&p->done);
+    }
+    pthread_mutex_unlock(&p->mu);
+    return NULL;
+}
+static void shard_pool_stop(shard_pool* p)
+{
+    pthread_mutex_lock(&p->mu); p->quit = 1; pthread_cond_broadcast(&p->go); pthread_mutex_unlock(&p->mu);
+    for (int i = 0; i < p->started; i++) pthread_join(p->th[i], NULL);
+    pthread_cond_destroy(&p->go); pthread_cond_destroy(&p->done); pthread_mutex_destroy(&p->mu);
+    free(p->th); free(p->w);
+}
+static int shard_pool_start(shard_pool* p, int n, void* owner)
+{
+    memset(p, 0, sizeof *p);
+    p->n = n; p->owner = owner;
+    p->th = (pthread_t*)calloc((size_t)n, sizeof(pthread_t)); p->w = (shard_worker*)calloc((size_t)n, sizeof(shard_worker));
+    if (!p->th || !p->w) { free(p->th); free(p->w); return 1; }
+    pthread_mutex_init(&p->mu, NULL); pthread_cond_init(&p->go, NULL); pthread_cond_init(&p->done, NULL);
+    for (int i = 0; i < n; i++) {
+        p->w[i].pool = p; p->w[i].shard = i;
+        if (pthread_create(&p->th[i], NULL, shard_worker_main, &p->w[i])) { shard_pool_stop(p); return 1; }
+        p->started++;
+    }
+    return 0;
+}
+static void shard_pool_run(shard_pool* p, void (*fn)(void*, int))
+{
+    pthread_mutex_lock(&p->mu);
+    p->fn = fn; p->pending = p->n; p->gen++;
+    pthread_cond_broadcast(&p->go);
+    while (p->pending) pthread_cond_wait(&p->done, &p->mu);
+    pthread_mutex_unlock(&p->mu);
+}
+/* LC3_OK if every shard returned it, otherwise the first other code in shard order */
+static LC3_Error shard_result(const LC3_Error* res, int n)
+{
+    for (int i = 0; i < n; i++) if (res[i] != LC3_OK) return res[i];
+    return LC3_OK;
+}
+
+/* ---- encoders ---- */
+struct lc3plus_sharded {
+    int n_streams, n_shards, channels, N;
+    lc3plus_batch** sh; int* first; int* count; int* dev; LC3_Error* res;
+    shard_pool pool;
+    /* the arguments of the host-pointer call the workers are running */
+    struct { const char* pcm; int fmt; const int* bw; const int* br; int T; uint8_t* out; int stride; int* nb; } a;
+};
+
+static void enc_sharded_free(lc3plus_sharded* s, int created)
+{
+    for (int i = 0; i < created; i++) lc3plus_enc_batch_destroy(s->sh[i]);
+    free(s->sh); free(s->first); free(s->count); free(s->dev); free(s->res); free(s);
+}
+LC3_Error lc3plus_enc_sharded_create(lc3plus_sharded** out, int n_streams, int samplerate, int channels, float frame_ms, int hrmode, const int* bitrates,
+                                     const int* devices, int n_devices)
+{
+    if (!out || !bitrates) return LC3_NULL_ERROR;
+    *out = NULL;
+    LC3_Error e = shard_devices_check(n_streams, devices, n_devices);
+    if (e) return e;
+    geom_t g;
+    e = enc_batch_geometry(&g, n_streams, samplerate, channels, frame_ms, hrmode);
+    if (e) return e;
+    for (int i = 0; i < n_streams; i++) { lc3d_chan tmp[MAX_CH]; e = derive_bitrate(&g, bitrates[i], tmp); if (e) return e; }      /* before any device is touched */
+    lc3plus_sharded* s = (lc3plus_sharded*)calloc(1, sizeof *s);
+    if (!s) return LC3_ERROR;
+    s->n_streams = n_streams; s->n_shards = n_devices; s->channels = channels; s->N = g.N;
+    s->sh = (lc3plus_batch**)calloc((size_t)n_devices, sizeof *s->sh);
+    s->first = (int*)calloc((size_t)n_devices, sizeof(int)); s->count = (int*)calloc((size_t)n_devices, sizeof(int));
+    s->dev = (int*)calloc((size_t)n_devices, sizeof(int)); s->res = (LC3_Error*)calloc((size_t)n_devices, sizeof(LC3_Error));
+    if (!s->sh || !s->first || !s->count || !s->dev || !s->res) { enc_sharded_free(s, 0); return LC3_ERROR; }
+    for (int k = 0; k < n_devices; k++) {
+        lc3plus_shard_block(n_streams, n_devices, k, &s->first[k], &s->count[k]);
+        s->dev[k] = devices[k];
+        e = lc3plus_enc_batch_create(&s->sh[k], s->count[k], samplerate, channels, frame_ms, hrmode, bitrates + s->first[k], devices[k]);
+        if (e) { enc_sharded_free(s, k); return e; }
+    }
+    if (shard_pool_start(&s->pool, n_devices, s)) { enc_sharded_free(s, n_devices); return LC3_ERROR; }
+    *out = s;
+    return LC3_OK;
+}
+LC3_Error lc3plus_enc_sharded_destroy(lc3plus_sharded* s)
+{
+    if (!s) return LC3_NULL_ERROR;
+    shard_pool_stop(&s->pool);
+    enc_sharded_free(s, s->n_shards);
+    return LC3_OK;
+}
+int lc3plus_enc_sharded_shards(const lc3plus_sharded* s) { return s ? s->n_shards : 0; }
+lc3plus_batch* lc3plus_enc_sharded_shard(lc3plus_sharded* s, int shard) { return s && shard >= 0 && shard < s->n_shards ? s->sh[shard] : NULL; }
+int lc3plus_enc_sharded_device(const lc3plus_sharded* s, int shard) { return s && shard >= 0 && shard < s->n_shards ? s->dev[shard] : -1; }
+LC3_Error lc3plus_enc_sharded_owner(const lc3plus_sharded* s, int stream, int* shard, int* local)
+{
+    if (!s || !shard || !local) return LC3_NULL_ERROR;
+    if (stream < 0 || stream >= s->n_streams) return LC3_ERROR;
+    shard_owner(s->n_streams, s->n_shards, stream, shard, local);
+    return LC3_OK;
+}
+/* the shard and the local index of a global stream, NULL where there is none */
+static lc3plus_batch* enc_sharded_at(const lc3plus_sharded* s, int stream, int* local)
+{
+    int k = 0;
+    if (!s || stream < 0 || stream >= s->n_streams) return NULL;
+    shard_owner(s->n_streams, s->n_shards, stream, &k, local);
+    return s->sh[k];
+}
+int lc3plus_enc_sharded_input_samples(const lc3plus_sharded* s) { return s ? s->N : 0; }
+int lc3plus_enc_sharded_num_bytes(const lc3plus_sharded* s, int stream)
+{
+    int l = 0; lc3plus_batch* b = enc_sharded_at(s, stream, &l);
+    return b ? lc3plus_enc_batch_num_bytes(b, l) : 0;
+}
+int lc3plus_enc_sharded_stride(const lc3plus_sharded* s)
+{
+    int m = 0;
+    if (!s) return 0;
+    for (int k = 0; k < s->n_shards; k++) { const int v = lc3plus_enc_batch_stride(s->sh[k]); if (v <= 0) return 0; m = IMAX(m, v); }
+    return m;
+}
+LC3_Error lc3plus_enc_sharded_set_bitrate(lc3plus_sharded* s, int stream, int bitrate)
+{
+    if (!s) return LC3_NULL_ERROR;
+    int l = 0; lc3plus_batch* b = enc_sharded_at(s, stream, &l);
+    return b ? lc3plus_enc_batch_set_bitrate(b, l, bitrate) : LC3_ERROR;
+}
+LC3_Error lc3plus_enc_sharded_set_bandwidth(lc3plus_sharded* s, int stream, int bandwidth)
+{
+    if (!s) return LC3_NULL_ERROR;
+    int l = 0; lc3plus_batch* b = enc_sharded_at(s, stream, &l);
+    return b ? lc3plus_enc_batch_set_bandwidth(b, l, bandwidth) : LC3_ERROR;
+}
+int lc3plus_enc_sharded_bandwidth(const lc3plus_sharded* s, int stream)
+{
+    int l = 0; lc3plus_batch* b = enc_sharded_at(s, stream, &l);
+    return b ? lc3plus_enc_batch_bandwidth(b, l) : -1;
+}
+
+/* shard k's call of the host-pointer encode: the call an unsharded batch would be given for the same arguments, on the shard's slice of every array.  In
+ * all three layouts the stream index is the outermost one, so the slice of the PCM is an offset */
+static LC3_Error enc_shard_call(lc3plus_sharded* s, int k)
+{
+    const size_t f = (size_t)s->first[k], row = f * (size_t)(s->a.T > 0 ? s->a.T : 0);
+    const int64_t po = s->a.pcm && s->a.T > 0 && pcm_format_ok(s->a.fmt) ? lc3plus_pcm_offset(s->a.fmt, s->channels, s->a.T, s->N, (int)f, 0, 0, 0) : 0;
+    const char* pcm = s->a.pcm ? s->a.pcm + (size_t)lc3d_pcm_elem_bytes(s->a.fmt) * (size_t)po : NULL;
+    uint8_t* out = s->a.out ? s->a.out + row * (size_t)(s->a.stride > 0 ? s->a.stride : 0) : NULL;
+    const int* br = s->a.br ? s->a.br + row : NULL;
+    int* nb = s->a.nb ? s->a.nb + row : NULL;
+    lc3plus_batch* b = s->sh[k];
+    if (s->a.bw) return batch_encode_bandwidths(b, pcm, 0, s->a.fmt, s->a.bw + row, br, s->a.T, out, s->a.stride, 0, nb, NULL, 1);
+    if (s->a.br) return batch_encode_bitrates(b, pcm, 0, s->a.fmt, br, s->a.T, out, s->a.stride, 0, nb, NULL, 1, NULL);
+    const LC3_Error e = batch_encode(b, pcm, 0, s->a.fmt, s->a.T, out, s->a.stride, 0, NULL, 1, NULL);
+    if (!e && nb && !b->dry) for (size_t i = 0; i < (size_t)s->count[k] * s->a.T; i++) nb[i] = lc3plus_enc_batch_num_bytes(b, (int)(i / s->a.T));
+    return e;
+}
+static void enc_shard_job(void* owner, int k) { lc3plus_sharded* s = (lc3plus_sharded*)owner; s->res[k] = enc_shard_call(s, k); }
+/* Every check of the call on every shard, on the calling thread, nothing run: step by step over all shards, so that the code is the one an unsharded batch
+ * gives (DRY_*).  LC3_OK and LC3_BW_WARNING let the call go on. */
+static LC3_Error enc_sharded_check(lc3plus_sharded* s)
+{
+    LC3_Error res = LC3_OK;
+    for (int step = s->a.bw ? DRY_BW : s->a.br ? DRY_RATES : DRY_ALL; step <= DRY_ALL && (res == LC3_OK || res == LC3_BW_WARNING); step++) {
+        if (step == DRY_RATES && !s->a.br) continue;
+        for (int k = 0; k < s->n_shards && (res == LC3_OK || res == LC3_BW_WARNING); k++) {
+            s->sh[k]->dry = step;
+            const LC3_Error e = enc_shard_call(s, k);
+            s->sh[k]->dry = 0;
+            if (e) res = e;
+        }
+    }
+    return res;
+}
+LC3_Error lc3plus_enc_sharded_encode(lc3plus_sharded* s, const void* pcm, int bitdepth, const int* bandwidths, const int* bitrates, int n_frames, void* out,
+                                     int out_stride, int* num_bytes)
+{
+    if (!s) return LC3_NULL_ERROR;
+    s->a.pcm = (const char*)pcm; s->a.fmt = bitdepth; s->a.bw = bandwidths; s->a.br = bitrates; s->a.T = n_frames; s->a.out = (uint8_t*)out;
+    s->a.stride = out_stride; s->a.nb = num_bytes;
+    const LC3_Error e = enc_sharded_check(s);
+    if (e != LC3_OK && e != LC3_BW_WARNING) return e;
+    shard_pool_run(&s->pool, enc_shard_job);
+    return shard_result(s->res, s->n_shards);
+}
+LC3_Error lc3plus_enc_sharded_encode_device(lc3plus_sharded* s, const void* const* pcm, int bitdepth, int n_frames, void* const* out, int out_stride,
+                                            void* const* hip_streams, int sync)
+{
+    if (!s || !pcm || !out) return LC3_NULL_ERROR;
+    for (int k = 0; k < s->n_shards; k++) {
+        s->sh[k]->dry = DRY_ALL;
+        const LC3_Error e = batch_encode(s->sh[k], pcm[k], 1, bitdepth, n_frames, out[k], out_stride, 1, NULL, 0, NULL);
+        s->sh[k]->dry = 0;
+        if (e) return e;
+    }
+    /* every shard's call is queued before any is waited for */
+    for (int k = 0; k < s->n_shards; k++)
+        s->res[k] = batch_encode(s->sh[k], pcm[k], 1, bitdepth, n_frames, out[k], out_stride, 1, hip_streams ? hip_streams[k] : NULL, 0, NULL);
+    if (sync) for (int k = 0; k < s->n_shards; k++) if (lc3hip_wait(s->sh[k]->dev) && !s->res[k]) s->res[k] = LC3_ERROR;
+    return shard_result(s->res, s->n_shards);
+}
+/* the shards' states one after the other: [channel-stream][state words] over all the streams, which is the state of an unsharded batch of n_streams */
+size_t lc3plus_enc_sharded_state_size(const lc3plus_sharded* s)
+{
+    size_t n = 0;
+    if (s) for (int k = 0; k < s->n_shards; k++) n += lc3plus_enc_batch_state_size(s->sh[k]);
+    return n;
+}
+LC3_Error lc3plus_enc_sharded_get_state(lc3plus_sharded* s, void* state, size_t size)
+{
+    if (!s || !state) return LC3_NULL_ERROR;
+    if (size != lc3plus_enc_sharded_state_size(s)) return LC3_ERROR;
+    uint8_t* p = (uint8_t*)state;
+    for (int k = 0; k < s->n_shards; k++) { const size_t n = lc3plus_enc_batch_state_size(s->sh[k]); s->res[k] = lc3plus_enc_batch_get_state(s->sh[k], p, n); p += n; }
+    return shard_result(s->res, s->n_shards);
+}
+LC3_Error lc3plus_enc_sharded_set_state(lc3plus_sharded* s, const void* state, size_t size)
+{
+    if (!s || !state) return LC3_NULL_ERROR;
+    if (size != lc3plus_enc_sharded_state_size(s)) return LC3_ERROR;
+    const uint8_t* p = (const uint8_t*)state;
+    for (int k = 0; k < s->n_shards; k++) { const size_t n = lc3plus_enc_batch_state_size(s->sh[k]); s->res[k] = lc3plus_enc_batch_set_state(s->sh[k], p, n); p += n; }
+    return shard_result(s->res, s->n_shards);
+}
+float lc3plus_enc_sharded_last_kernel_ms(lc3plus_sharded* s, int shard)
+{
+    return s && shard >= 0 && shard < s->n_shards ? lc3plus_enc_batch_last_kernel_ms(s->sh[shard]) : 0.0f;
+}
+
+/* ---- decoders ---- */
+struct lc3plus_dec_sharded {
+    int n_streams, n_shards, channels, N, delay;
+    lc3plus_dec_batch** sh; int* first; int* count; int* dev; LC3_Error* res;
+    shard_pool pool;
+    struct { const uint8_t* frames; int in_stride; const int* nb; const uint8_t* bfi; int T; char* pcm; int fmt; uint8_t* status; } a;
+};
+static void dec_sharded_free(lc3plus_dec_sharded* s, int created)
+{
+    for (int i = 0; i < created; i++) lc3plus_dec_batch_destroy(s->sh[i]);
+    free(s->sh); free(s->first); free(s->count); free(s->dev); free(s->res); free(s);
+}
+LC3_Error lc3plus_dec_sharded_create(lc3plus_dec_sharded** out, int n_streams, int samplerate, int channels, float frame_ms, int hrmode, const int* num_bytes,
+                                     const int* devices, int n_devices)
+{
+    if (!out) return LC3_NULL_ERROR;
+    *out = NULL;
+    LC3_Error e = shard_devices_check(n_streams, devices, n_devices);
+    if (e) return e;
+    geom_t g;
+    e = dec_batch_geometry(&g, n_streams, samplerate, channels, frame_ms, hrmode);
+    if (e) return e;
+    if (num_bytes) for (int i = 0; i < n_streams; i++) { lc3d_dchan tmp[MAX_CH]; memset(tmp, 0, sizeof tmp); e = derive_dstream(&g, num_bytes[i], tmp); if (e) return e; }
+    lc3plus_dec_sharded* s = (lc3plus_dec_sharded*)calloc(1, sizeof *s);
+    if (!s) return LC3_ERROR;
+    s->n_streams = n_streams; s->n_shards = n_devices; s->channels = channels; s->N = g.N; s->delay = g.N - 2 * g.la;
+    s->sh = (lc3plus_dec_batch**)calloc((size_t)n_devices, sizeof *s->sh);
+    s->first = (int*)calloc((size_t)n_devices, sizeof(int)); s->count = (int*)calloc((size_t)n_devices, sizeof(int));
+    s->dev = (int*)calloc((size_t)n_devices, sizeof(int)); s->res = (LC3_Error*)calloc((size_t)n_devices, sizeof(LC3_Error));
+    if (!s->sh || !s->first || !s->count || !s->dev || !s->res) { dec_sharded_free(s, 0); return LC3_ERROR; }
+    for (int k = 0; k < n_devices; k++) {
+        lc3plus_shard_block(n_streams, n_devices, k, &s->first[k], &s->count[k]);
+        s->dev[k] = devices[k];
+        e = lc3plus_dec_batch_create(&s->sh[k], s->count[k], samplerate, channels, frame_ms, hrmode, num_bytes ? num_bytes + s->first[k] : NULL, devices[k]);
+        if (e) { dec_sharded_free(s, k); return e; }
+    }
+    if (shard_pool_start(&s->pool, n_devices, s)) { dec_sharded_free(s, n_devices); return LC3_ERROR; }
+    *out = s;
+    return LC3_OK;
+}
+LC3_Error lc3plus_dec_sharded_destroy(lc3plus_dec_sharded* s)
+{
+    if (!s) return LC3_NULL_ERROR;
+    shard_pool_stop(&s->pool);
+    dec_sharded_free(s, s->n_shards);
+    return LC3_OK;
+}
+int lc3plus_dec_sharded_shards(const lc3plus_dec_sharded* s) { return s ? s->n_shards : 0; }
+lc3plus_dec_batch* lc3plus_dec_sharded_shard(lc3plus_dec_sharded* s, int shard) { return s && shard >= 0 && shard < s->n_shards ? s->sh[shard] : NULL; }
+int lc3plus_dec_sharded_device(const lc3plus_dec_sharded* s, int shard) { return s && shard >= 0 && shard < s->n_shards ? s->dev[shard] : -1; }
+LC3_Error lc3plus_dec_sharded_owner(const lc3plus_dec_sharded* s, int stream, int* shard, int* local)
+{
+    if (!s || !shard || !local) return LC3_NULL_ERROR;
+    if (stream < 0 || stream >= s->n_streams) return LC3_ERROR;
+    shard_owner(s->n_streams, s->n_shards, stream, shard, local);
+    return LC3_OK;
+}
+int lc3plus_dec_sharded_output_samples(const lc3plus_dec_sharded* s) { return s ? s->N : 0; }
+int lc3plus_dec_sharded_delay(const lc3plus_dec_sharded* s) { return s ? s->delay : 0; }
+int lc3plus_dec_sharded_num_bytes(const lc3plus_dec_sharded* s, int stream)
+{
+    int k = 0, l = 0;
+    if (!s || stream < 0 || stream >= s->n_streams) return 0;
+    shard_owner(s->n_streams, s->n_shards, stream, &k, &l);
+    return lc3plus_dec_batch_num_bytes(s->sh[k], l);
+}
+LC3_Error lc3plus_dec_sharded_set_num_bytes(lc3plus_dec_sharded* s, int stream, int num_bytes)
+{
+    int k = 0, l = 0;
+    if (!s) return LC3_NULL_ERROR;
+    if (stream < 0 || stream >= s->n_streams) return LC3_ERROR;
+    shard_owner(s->n_streams, s->n_shards, stream, &k, &l);
+    return lc3plus_dec_batch_set_num_bytes(s->sh[k], l, num_bytes);
+}
+static LC3_Error dec_shard_call(lc3plus_dec_sharded* s, int k)
+{
+    const size_t f = (size_t)s->first[k], row = f * (size_t)(s->a.T > 0 ? s->a.T : 0);
+    const int64_t po = s->a.pcm && s->a.T > 0 && pcm_format_ok(s->a.fmt) ? lc3plus_pcm_offset(s->a.fmt, s->channels, s->a.T, s->N, (int)f, 0, 0, 0) : 0;
+    char* pcm = s->a.pcm ? s->a.pcm + (size_t)lc3d_pcm_elem_bytes(s->a.fmt) * (size_t)po : NULL;
+    const uint8_t* frames = s->a.frames ? s->a.frames + row * (size_t)(s->a.in_stride > 0 ? s->a.in_stride : 0) : NULL;
+    const uint8_t* bfi = s->a.bfi ? s->a.bfi + row : NULL;
+    uint8_t* status = s->a.status ? s->a.status + row : NULL;
+    if (s->a.nb) return lc3plus_dec_batch_decode_sizes(s->sh[k], frames, 0, s->a.in_stride, s->a.nb + row, bfi, s->a.T, pcm, 0, s->a.fmt, status, NULL, 1);
+    return dec_batch_decode(s->sh[k], frames, 0, s->a.in_stride, bfi, s->a.T, pcm, 0, s->a.fmt, status, NULL, 1, NULL);
+}
+static void dec_shard_job(void* owner, int k) { lc3plus_dec_sharded* s = (lc3plus_dec_sharded*)owner; s->res[k] = dec_shard_call(s, k); }
+LC3_Error lc3plus_dec_sharded_decode(lc3plus_dec_sharded* s, const void* frames, int in_stride, const int* num_bytes, const uint8_t* bfi, int n_frames, void* pcm,
+                                     int bps, uint8_t* status)
+{
+    if (!s) return LC3_NULL_ERROR;
+    s->a.frames = (const uint8_t*)frames; s->a.in_stride = in_stride; s->a.nb = num_bytes; s->a.bfi = bfi; s->a.T = n_frames; s->a.pcm = (char*)pcm;
+    s->a.fmt = bps; s->a.status = status;
+    /* every check on every shard first, nothing run: shards are blocks of streams in order, and the checks walk the streams in order, so the first refusal
+     * is the unsharded batch's */
+    for (int k = 0; k < s->n_shards; k++) {
+        s->sh[k]->dry = DRY_ALL;
+        const LC3_Error e = dec_shard_call(s, k);
+        s->sh[k]->dry = 0;
+        if (e) return e;
+    }
+    shard_pool_run(&s->pool, dec_shard_job);
+    return shard_result(s->res, s->n_shards);
+}
+LC3_Error lc3plus_dec_sharded_decode_device(lc3plus_dec_sharded* s, const void* const* frames, int in_stride, int n_frames, void* const* pcm, int bps,
+                                            void* const* hip_streams, int sync)
+{
+    if (!s || !frames || !pcm) return LC3_NULL_ERROR;
+    for (int k = 0; k < s->n_shards; k++) {
+        s->sh[k]->dry = DRY_ALL;
+        const LC3_Error e = dec_batch_decode(s->sh[k], frames[k], 1, in_stride, NULL, n_frames, pcm[k], 1, bps, NULL, NULL, 0, NULL);
+        s->sh[k]->dry = 0;
+        if (e) return e;
+    }
+    for (int k = 0; k < s->n_shards; k++)
+        s->res[k] = dec_batch_decode(s->sh[k], frames[k], 1, in_stride, NULL, n_frames, pcm[k], 1, bps, NULL, hip_streams ? hip_streams[k] : NULL, 0, NULL);
+    if (sync) for (int k = 0; k < s->n_shards; k++) if (lc3hip_dec_wait(s->sh[k]->dev) && !s->res[k]) s->res[k] = LC3_ERROR;
+    return shard_result(s->res, s->n_shards);
+}
+size_t lc3plus_dec_sharded_state_size(const lc3plus_dec_sharded* s)
+{
+    size_t n = 0;
+    if (s) for (int k = 0; k < s->n_shards; k++) n += lc3plus_dec_batch_state_size(s->sh[k]);
+    return n;
+}
+LC3_Error lc3plus_dec_sharded_get_state(lc3plus_dec_sharded* s, void* state, size_t size)
+{
+    if (!s || !state) return LC3_NULL_ERROR;
+    if (size != lc3plus_dec_sharded_state_size(s)) return LC3_ERROR;
+    uint8_t* p = (uint8_t*)state;
+    for (int k = 0; k < s->n_shards; k++) { const size_t n = lc3plus_dec_batch_state_size(s->sh[k]); s->res[k] = lc3plus_dec_batch_get_state(s->sh[k], p, n); p += n; }
+    return shard_result(s->res, s->n_shards);
+}
+LC3_Error lc3plus_dec_sharded_set_state(lc3plus_dec_sharded* s, const void* state, size_t size)
+{
+    if (!s || !state) return LC3_NULL_ERROR;
+    if (size != lc3plus_dec_sharded_state_size(s)) return LC3_ERROR;
+    const uint8_t* p = (const uint8_t*)state;
+    for (int k = 0; k < s->n_shards; k++) { const size_t n = lc3plus_dec_batch_state_size(s->sh[k]); s->res[k] = lc3plus_dec_batch_set_state(s->sh[k], p, n); p += n; }
+    return shard_result(s->res, s->n_shards);
+}
+float lc3plus_dec_sharded_last_kernel_ms(lc3plus_dec_sharded* s, int shard)
+{
+    return s && shard >= 0 && shard < s->n_shards ? lc3plus_dec_batch_last_kernel_ms(s->sh[shard]) : 0.0f;
 }

@@ -971,6 +971,15 @@ extern "C" int lc3hip_download_chans(void* ctx, lc3d_chan* chans)
     return chans_host_side(c, chans, 0, c->ncs);
 }
 
+/* waits for the batch's last call (a call made with sync = 0) */
+extern "C" int lc3hip_wait(void* ctx)
+{
+    lc3hip_ctx* c = (lc3hip_ctx*)ctx;
+    HIPCHK(hipSetDevice(c->device));
+    if (c->last_stream) HIPCHK(hipStreamSynchronize(c->last_stream));
+    return 0;
+}
+
 /* status bits of the last call, [channel-stream][frame] (n = ncs * frames of that call), to host memory */
 extern "C" int lc3hip_last_status(void* ctx, uint8_t* status_host, int n)
 {
@@ -1179,6 +1188,13 @@ extern "C" int lc3hip_dec_upload_table(void* ctx, const lc3d_dchan* tab, int n)
     HIPCHK(hipMalloc((void**)&c->d_tab, sizeof(lc3d_dchan) * (size_t)n));
     HIPCHK(hipMemcpy(c->d_tab, tab, sizeof(lc3d_dchan) * (size_t)n, hipMemcpyHostToDevice));
     c->tab_n = n;
+    return 0;
+}
+extern "C" int lc3hip_dec_wait(void* ctx)            /* as lc3hip_wait */
+{
+    lc3hip_dctx* c = (lc3hip_dctx*)ctx;
+    HIPCHK(hipSetDevice(c->device));
+    if (c->last_stream) HIPCHK(hipStreamSynchronize(c->last_stream));
     return 0;
 }
 extern "C" int lc3hip_dec_download_chans(void* ctx, lc3d_dchan* chans)

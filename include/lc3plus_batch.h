@@ -339,6 +339,86 @@ LC3_Error lc3plus_dec_batch_import_streams(lc3plus_dec_batch* batch, const int* 
  * are identical, and the PCM of a call is complete in stream order on hip_stream as before.  Off by default. */
 LC3_Error lc3plus_dec_batch_set_input_ready(lc3plus_dec_batch* batch, int ready);
 
+/* ---- Sharded batches: one call drives encoders or decoders on several GPUs ------------------------------------------------------------------
+ * Streams are independent, so a sharded batch is n_devices ordinary batches, each owning a contiguous block of the n_streams streams on a device of its
+ * own; nothing is exchanged between devices.  Stream indices are GLOBAL (0 ... n_streams - 1) and arrays are laid out over all n_streams exactly as the
+ * per-batch calls lay them out over theirs; a sharded call gives byte for byte what one unsharded batch of n_streams gives.
+ *
+ * The split, on the host alone (no device): shard `shard` of `n_shards` owns *count streams from *first.  Contiguous blocks in shard order, sizes differ by
+ * at most one, the larger blocks first.  LC3_ERROR for n_streams < 0, n_shards <= 0 or a shard out of range. */
+LC3_Error lc3plus_shard_block(int n_streams, int n_shards, int shard, int* first, int* count);
+
+typedef struct lc3plus_sharded     lc3plus_sharded;      /* encoders */
+typedef struct lc3plus_dec_sharded lc3plus_dec_sharded;  /* decoders */
+
+/* devices[n_devices]: one shard per entry, in order.  An entry is a HIP device index; the same index may appear more than once (two shards, two contexts,
+ * one device).  Everything is checked before a device is touched: NULL devices (LC3_NULL_ERROR); n_devices <= 0, a negative entry or more devices than
+ * streams (LC3_ERROR); then the geometry and every rate, with the codes of lc3plus_enc_batch_create.  If a shard cannot be created the ones before it are
+ * destroyed; on every error *s is NULL.  One worker thread per shard is started here and joined in destroy; no call starts a thread.
+ * A sharded batch is used from one thread at a time, as a batch is; distinct sharded batches (and distinct batches) may be used from different threads at
+ * the same time. */
+LC3_Error lc3plus_enc_sharded_create(lc3plus_sharded** s, int n_streams, int samplerate, int channels, float frame_ms, int hrmode, const int* bitrates,
+                                     const int* devices, int n_devices);
+LC3_Error lc3plus_enc_sharded_destroy(lc3plus_sharded* s);
+int            lc3plus_enc_sharded_shards(const lc3plus_sharded* s);
+/* The shard's batch, borrowed (never destroy it), with LOCAL stream indices (owner()).  Everything a batch can do beyond the calls below - rates and sizes in
+ * device memory, packed frames, the stream lifecycle, set_input_ready, last_status, last_records - is reached through it.  A sharded call is complete when
+ * it returns (or queued on each shard's stream with sync = 0), so calls on a borrowed batch order with it as they order with that batch's own calls. */
+lc3plus_batch* lc3plus_enc_sharded_shard(lc3plus_sharded* s, int shard);
+int            lc3plus_enc_sharded_device(const lc3plus_sharded* s, int shard);          /* -1 for a bad argument */
+LC3_Error      lc3plus_enc_sharded_owner(const lc3plus_sharded* s, int stream, int* shard, int* local);
+int       lc3plus_enc_sharded_input_samples(const lc3plus_sharded* s);
+int       lc3plus_enc_sharded_num_bytes(const lc3plus_sharded* s, int stream);
+int       lc3plus_enc_sharded_stride(const lc3plus_sharded* s);                          /* max over the shards */
+LC3_Error lc3plus_enc_sharded_set_bitrate(lc3plus_sharded* s, int stream, int bitrate);
+LC3_Error lc3plus_enc_sharded_set_bandwidth(lc3plus_sharded* s, int stream, int bandwidth);
+int       lc3plus_enc_sharded_bandwidth(const lc3plus_sharded* s, int stream);
+/* Host pointers.  pcm, bitdepth (the format word, every sample type and layout), n_frames, out and out_stride as lc3plus_enc_batch_encode over n_streams;
+ * bandwidths, bitrates, num_bytes: NULL or host [n_streams][n_frames].  Each shard makes the call an unsharded batch would be given for these arguments -
+ * encode() without bitrates and bandwidths (num_bytes, if given, is then filled with num_bytes(stream)), encode_bitrates() with bitrates alone,
+ * encode_bandwidths() with bandwidths - on its block of every array; the shards' calls run at the same time, one host thread per shard, and the call
+ * returns when all are done.  Every check of those calls is made for all shards on the calling thread before any shard is touched: a refused call returns
+ * the code the unsharded call gives and changes nothing on any device.  Otherwise the result is LC3_OK if every shard returned it, else the first other code
+ * in shard order (LC3_BW_WARNING among them); a failure inside one shard does not stop the others from finishing their call. */
+LC3_Error lc3plus_enc_sharded_encode(lc3plus_sharded* s, const void* pcm, int bitdepth, const int* bandwidths, const int* bitrates, int n_frames, void* out,
+                                     int out_stride, int* num_bytes);
+/* Device pointers: pcm[n_shards] and out[n_shards], each on its shard's device and holding that shard's block (pcm[k]: [count_k][n_frames]..., out[k]:
+ * [count_k][n_frames][out_stride]); hip_streams: NULL, or [n_shards] streams (an entry may be NULL: the shard's own stream).  Checked for all shards first,
+ * as above; then every shard's call is queued before any is waited for.  sync = 0 returns after queueing, sync != 0 when every shard has finished. */
+LC3_Error lc3plus_enc_sharded_encode_device(lc3plus_sharded* s, const void* const* pcm, int bitdepth, int n_frames, void* const* out, int out_stride,
+                                            void* const* hip_streams, int sync);
+/* Checkpoint / resume: the shards' states one after the other in shard order.  A batch's state is [channel-stream][state words], so this IS the state of an
+ * unsharded batch of n_streams (state_size() is equal): a checkpoint moves between a sharded batch, an unsharded batch and a sharded batch with another
+ * number of shards.  size must be state_size() (LC3_ERROR, nothing written). */
+size_t    lc3plus_enc_sharded_state_size(const lc3plus_sharded* s);
+LC3_Error lc3plus_enc_sharded_get_state(lc3plus_sharded* s, void* state, size_t size);
+LC3_Error lc3plus_enc_sharded_set_state(lc3plus_sharded* s, const void* state, size_t size);
+float     lc3plus_enc_sharded_last_kernel_ms(lc3plus_sharded* s, int shard);
+
+/* The decoder twin, with the codes of lc3plus_dec_batch_create (num_bytes may be NULL). */
+LC3_Error lc3plus_dec_sharded_create(lc3plus_dec_sharded** s, int n_streams, int samplerate, int channels, float frame_ms, int hrmode, const int* num_bytes,
+                                     const int* devices, int n_devices);
+LC3_Error lc3plus_dec_sharded_destroy(lc3plus_dec_sharded* s);
+int                lc3plus_dec_sharded_shards(const lc3plus_dec_sharded* s);
+lc3plus_dec_batch* lc3plus_dec_sharded_shard(lc3plus_dec_sharded* s, int shard);         /* borrowed; local stream indices */
+int                lc3plus_dec_sharded_device(const lc3plus_dec_sharded* s, int shard);
+LC3_Error          lc3plus_dec_sharded_owner(const lc3plus_dec_sharded* s, int stream, int* shard, int* local);
+int       lc3plus_dec_sharded_output_samples(const lc3plus_dec_sharded* s);
+int       lc3plus_dec_sharded_delay(const lc3plus_dec_sharded* s);
+int       lc3plus_dec_sharded_num_bytes(const lc3plus_dec_sharded* s, int stream);
+LC3_Error lc3plus_dec_sharded_set_num_bytes(lc3plus_dec_sharded* s, int stream, int num_bytes);
+/* Host pointers, over n_streams: num_bytes NULL -> each shard calls lc3plus_dec_batch_decode, else lc3plus_dec_batch_decode_sizes; bfi and status NULL or
+ * [n_streams][n_frames].  Checks, threads and result as lc3plus_enc_sharded_encode. */
+LC3_Error lc3plus_dec_sharded_decode(lc3plus_dec_sharded* s, const void* frames, int in_stride, const int* num_bytes, const uint8_t* bfi, int n_frames, void* pcm,
+                                     int bps, uint8_t* status);
+/* Device pointers, one per shard (frames[k]: [count_k][n_frames][in_stride], pcm[k]: that shard's block), as lc3plus_enc_sharded_encode_device. */
+LC3_Error lc3plus_dec_sharded_decode_device(lc3plus_dec_sharded* s, const void* const* frames, int in_stride, int n_frames, void* const* pcm, int bps,
+                                            void* const* hip_streams, int sync);
+size_t    lc3plus_dec_sharded_state_size(const lc3plus_dec_sharded* s);
+LC3_Error lc3plus_dec_sharded_get_state(lc3plus_dec_sharded* s, void* state, size_t size);
+LC3_Error lc3plus_dec_sharded_set_state(lc3plus_dec_sharded* s, const void* state, size_t size);
+float     lc3plus_dec_sharded_last_kernel_ms(lc3plus_dec_sharded* s, int shard);
+
 /* lc3plus_enc_* spellings of the single-stream API (north-star wording); thin aliases. */
 LC3_Error lc3plus_enc_init(LC3_Enc* e, int samplerate, int channels);
 LC3_Error lc3plus_enc_set_frame_ms(LC3_Enc* e, float frame_ms);

@@ -1,0 +1,155 @@
+/* stub_shim.c -- every lc3hip_* symbol of audio_codec_amd/csrc/lc3_shim.h as a function that touches no GPU.
+ *
+ * Linked with lc3_host.c in place of lc3_runtime.hip and the kernels (csrc/Makefile, target stub), it lets the host logic - which pointer, which slice of
+ * which array, which result, which thread - be tested on a machine without a device: every create succeeds, every call returns success and appends one
+ * record to a log that lc3stub_log() returns; lc3stub_fail_ctx() makes the encode / decode / state calls of one context fail.  Contexts are numbered in
+ * the order they are created, from 0 after lc3stub_reset().  Never part of the product library. */
+#include <pthread.h>
+#include <stdint.h>
+#include <stdlib.h>
+#include <string.h>
+#include "../audio_codec_amd/csrc/lc3_shim.h"
+
+enum { STUB_ENCODE = 1, STUB_DECODE = 2, STUB_GET_STATE = 3, STUB_SET_STATE = 4, STUB_WAIT = 5 };
+#define STUB_STATE_BYTES 32          /* per channel-stream */
+
+/* p: encode pcm, out; decode frames, pcm, status, bfi; state: the host pointer.  a / b: the first two words and the last one of the two per-frame arrays
+ * the call was given (encode: frame sizes, bandwidths in force; decode: sizes, loss flags), -1 where there is none.  sync / on_device as passed. */
+typedef struct {
+    int32_t ctx, kind, dec, n_frames, stride, fmt, on_device, sync;
+    uint64_t p[4];
+    int64_t a[3], b[3];
+    uint64_t bytes, hip_stream;
+} lc3stub_rec;
+
+typedef struct { int id, dec, n_streams, channels; } stub_ctx;
+
+static pthread_mutex_t g_mu = PTHREAD_MUTEX_INITIALIZER;
+static lc3stub_rec* g_log; static int g_n, g_cap, g_next_ctx, g_fail = -1;
+
+void lc3stub_reset(void)
+{
+    pthread_mutex_lock(&g_mu);
+    g_n = 0; g_next_ctx = 0; g_fail = -1;
+    pthread_mutex_unlock(&g_mu);
+}
+void lc3stub_fail_ctx(int ctx) { pthread_mutex_lock(&g_mu); g_fail = ctx; pthread_mutex_unlock(&g_mu); }
+int lc3stub_rec_sizeof(void) { return (int)sizeof(lc3stub_rec); }
+/* copies up to max records, oldest first; returns how many the log holds */
+int lc3stub_log(lc3stub_rec* out, int max)
+{
+    pthread_mutex_lock(&g_mu);
+    const int n = g_n;
+    if (out) memcpy(out, g_log, sizeof(lc3stub_rec) * (size_t)(n < max ? n : max));
+    pthread_mutex_unlock(&g_mu);
+    return n;
+}
+/* appends the record; returns 1 where the context is the one chosen to fail */
+static int stub_append(const stub_ctx* c, lc3stub_rec* r)
+{
+    r->ctx = c->id; r->dec = c->dec;
+    pthread_mutex_lock(&g_mu);
+    if (g_n == g_cap) {
+        const int cap = g_cap ? 2 * g_cap : 256;
+        lc3stub_rec* q = (lc3stub_rec*)realloc(g_log, sizeof(lc3stub_rec) * (size_t)cap);
+        if (q) { g_log = q; g_cap = cap; }
+    }
+    if (g_n < g_cap) g_log[g_n++] = *r;
+    const int fail = g_fail == c->id;
+    pthread_mutex_unlock(&g_mu);
+    return fail;
+}
+static stub_ctx* stub_new(int dec, int n_streams, int channels)
+{
+    stub_ctx* c = (stub_ctx*)calloc(1, sizeof *c);
+    if (!c) return NULL;
+    c->dec = dec; c->n_streams = n_streams; c->channels = channels;
+    pthread_mutex_lock(&g_mu); c->id = g_next_ctx++; pthread_mutex_unlock(&g_mu);
+    return c;
+}
+static void words16(const uint16_t* w, size_t n, int64_t* o) { o[0] = w && n > 0 ? w[0] : -1; o[1] = w && n > 1 ? w[1] : -1; o[2] = w && n > 0 ? w[n - 1] : -1; }
+static void words8(const uint8_t* w, size_t n, int64_t* o) { o[0] = w && n > 0 ? w[0] : -1; o[1] = w && n > 1 ? w[1] : -1; o[2] = w && n > 0 ? w[n - 1] : -1; }
+
+int lc3hip_create(void** ctx, const lc3d_plan* plan, int n_streams, int device) { *ctx = stub_new(0, n_streams, plan->channels); return *ctx ? 0 : 1; }
+int lc3hip_dec_create(void** ctx, const lc3d_plan* plan, const float* tmpl, int n_streams, int device) { *ctx = stub_new(1, n_streams, plan->channels); return *ctx ? 0 : 1; }
+int lc3hip_destroy(void* ctx) { free(ctx); return 0; }
+int lc3hip_dec_destroy(void* ctx) { free(ctx); return 0; }
+int lc3hip_set_template(void* ctx, const float* tmpl) { return 0; }
+int lc3hip_upload_chans(void* ctx, const lc3d_chan* chans, int first, int count) { return 0; }
+int lc3hip_upload_chans_async(void* ctx, const lc3d_chan* chans, int first, int count, void* hip_stream, int bw_only) { return 0; }
+int lc3hip_upload_enc_table(void* ctx, const lc3d_chan* tab, int n) { return 0; }
+int lc3hip_dec_upload_chans(void* ctx, const lc3d_dchan* chans, int first, int count) { return 0; }
+int lc3hip_dec_upload_table(void* ctx, const lc3d_dchan* tab, int n) { return 0; }
+int lc3hip_download_chans(void* ctx, lc3d_chan* chans) { return 0; }
+int lc3hip_dec_download_chans(void* ctx, lc3d_dchan* chans) { return 0; }
+float lc3hip_last_ms(void* ctx) { return 0.0f; }
+float lc3hip_dec_last_ms(void* ctx) { return 0.0f; }
+int lc3hip_set_input_ready(void* ctx, int ready) { return 0; }
+int lc3hip_dec_set_input_ready(void* ctx, int ready) { return 0; }
+int lc3hip_last_status(void* ctx, uint8_t* status_host, int n) { return 0; }
+int lc3hip_last_records(void* ctx, float* rec_host, int max_words) { return 0; }
+int lc3hip_test_fastmath(int kind, const float* x_host, float* y_host, long long n) { return 1; }
+
+int lc3hip_encode(void* ctx, const void* pcm, int pcm_on_device, int bitdepth, int n_frames, void* out, int out_stride, int out_on_device, void* hip_stream,
+                  int sync, void* trace_host, const uint16_t* fsz_host, const uint16_t* bw_host)
+{
+    const stub_ctx* c = (const stub_ctx*)ctx;
+    lc3stub_rec r; memset(&r, 0, sizeof r);
+    r.kind = STUB_ENCODE; r.n_frames = n_frames; r.stride = out_stride; r.fmt = bitdepth; r.on_device = pcm_on_device; r.sync = sync;
+    r.p[0] = (uint64_t)(uintptr_t)pcm; r.p[1] = (uint64_t)(uintptr_t)out; r.hip_stream = (uint64_t)(uintptr_t)hip_stream;
+    words16(fsz_host, (size_t)c->n_streams * n_frames, r.a); words16(bw_host, (size_t)c->n_streams * n_frames, r.b);
+    return stub_append(c, &r);
+}
+int lc3hip_encode_rates_device(void* ctx, const void* pcm, int bitdepth, int n_frames, void* out, int out_stride, const int32_t* rates_dev, const int32_t* bws_dev,
+                               const lc3d_rate_rule* rule, int32_t* num_bytes_dev, uint8_t* flags_dev, int clear_resets, void* hip_stream, int sync) { return 0; }
+int lc3hip_encode_packed(void* ctx, const void* pcm, int bitdepth, int n_frames, const int32_t* rates_dev, const int32_t* bws_dev, const lc3d_rate_rule* rule,
+                         int order, void* out, long long capacity, long long* offsets_dev, long long* total_dev, int32_t* num_bytes_dev, uint8_t* flags_dev,
+                         int clear_resets, void* hip_stream, int sync) { return 0; }
+int lc3hip_dec_decode(void* ctx, const void* frames, int frames_on_device, int in_stride, const uint8_t* bfi_flags_host, const uint16_t* sizes_host,
+                      int sizes_max_nbytes, int n_frames, void* pcm, int pcm_on_device, int bps, uint8_t* status_host, void* hip_stream, int sync, void* trace_host)
+{
+    const stub_ctx* c = (const stub_ctx*)ctx;
+    lc3stub_rec r; memset(&r, 0, sizeof r);
+    r.kind = STUB_DECODE; r.n_frames = n_frames; r.stride = in_stride; r.fmt = bps; r.on_device = pcm_on_device; r.sync = sync;
+    r.p[0] = (uint64_t)(uintptr_t)frames; r.p[1] = (uint64_t)(uintptr_t)pcm; r.p[2] = (uint64_t)(uintptr_t)status_host; r.p[3] = (uint64_t)(uintptr_t)bfi_flags_host;
+    r.hip_stream = (uint64_t)(uintptr_t)hip_stream;
+    words16(sizes_host, (size_t)c->n_streams * n_frames, r.a); words8(bfi_flags_host, (size_t)c->n_streams * n_frames, r.b);
+    return stub_append(c, &r);
+}
+int lc3hip_dec_decode_dsizes(void* ctx, const void* frames, int in_stride, const int32_t* num_bytes_dev, const uint8_t* bfi_dev, int n_frames, void* pcm, int bps,
+                             uint8_t* status_dev, void* hip_stream, int sync) { return 0; }
+int lc3hip_dec_decode_packed(void* ctx, const void* frames, long long capacity, const long long* offsets_dev, const int32_t* num_bytes_dev, int max_bytes,
+                             const uint8_t* bfi_dev, int n_frames, void* pcm, int bps, uint8_t* status_dev, void* hip_stream, int sync) { return 0; }
+
+static size_t stub_state_bytes(const void* ctx) { const stub_ctx* c = (const stub_ctx*)ctx; return c ? (size_t)STUB_STATE_BYTES * c->n_streams * c->channels : 0; }
+/* get: every byte is the context's number, so that a test sees which shard wrote which slice */
+static int stub_state(void* ctx, int kind, void* host, size_t bytes)
+{
+    const stub_ctx* c = (const stub_ctx*)ctx;
+    lc3stub_rec r; memset(&r, 0, sizeof r);
+    r.kind = kind; r.p[0] = (uint64_t)(uintptr_t)host; r.bytes = bytes;
+    r.a[0] = r.a[1] = r.a[2] = r.b[0] = r.b[1] = r.b[2] = -1;
+    if (kind == STUB_SET_STATE && bytes) { r.a[0] = ((const uint8_t*)host)[0]; r.a[2] = ((const uint8_t*)host)[bytes - 1]; }
+    const int fail = stub_append(c, &r);
+    if (fail || bytes != stub_state_bytes(ctx)) return 1;
+    if (kind == STUB_GET_STATE) memset(host, c->id, bytes);
+    return 0;
+}
+size_t lc3hip_state_bytes(void* ctx) { return stub_state_bytes(ctx); }
+int lc3hip_get_state(void* ctx, void* host, size_t bytes) { return stub_state(ctx, STUB_GET_STATE, host, bytes); }
+int lc3hip_set_state(void* ctx, const void* host, size_t bytes) { return stub_state(ctx, STUB_SET_STATE, (void*)host, bytes); }
+size_t lc3hip_dec_state_bytes(void* ctx) { return stub_state_bytes(ctx); }
+int lc3hip_dec_get_state(void* ctx, void* host, size_t bytes) { return stub_state(ctx, STUB_GET_STATE, host, bytes); }
+int lc3hip_dec_set_state(void* ctx, const void* host, size_t bytes) { return stub_state(ctx, STUB_SET_STATE, (void*)host, bytes); }
+static int stub_wait(void* ctx)
+{
+    lc3stub_rec r; memset(&r, 0, sizeof r);
+    r.kind = STUB_WAIT;
+    return stub_append((const stub_ctx*)ctx, &r);
+}
+int lc3hip_wait(void* ctx) { return stub_wait(ctx); }
+int lc3hip_dec_wait(void* ctx) { return stub_wait(ctx); }
+int lc3hip_stream_state(void* ctx, int mode, const int* streams, int n, const lc3d_chan* cfg, void* blob, int blob_on_device, const uint32_t* hdr, uint8_t* status,
+                        void* hip_stream, int sync) { return 0; }
+int lc3hip_dec_stream_state(void* ctx, int mode, const int* streams, int n, const lc3d_dchan* cfg, void* blob, int blob_on_device, const uint32_t* hdr,
+                            uint8_t* status, void* hip_stream, int sync) { return 0; }
