@@ -34,7 +34,7 @@ EXPORTS = [
     "lc3plus_enc_batch_encode_bandwidths", "lc3plus_enc_batch_bandwidth", "lc3plus_enc_plan_bandwidths",
     "lc3plus_enc_batch_encode_rates_device", "lc3plus_enc_plan_rates_lenient",
     "lc3plus_enc_batch_encode_packed", "lc3plus_plan_packed", "lc3plus_dec_batch_decode_packed", "lc3plus_dec_plan_packed_lenient",
-    "lc3plus_pcm_format_check", "lc3plus_pcm_offset",
+    "lc3plus_pcm_format_check", "lc3plus_pcm_offset", "lc3plus_pcm_elem_bytes", "lc3plus_pcm_to_native", "lc3plus_pcm_from_native",
     "lc3plus_shard_block",
     "lc3plus_enc_sharded_create", "lc3plus_enc_sharded_destroy", "lc3plus_enc_sharded_shards", "lc3plus_enc_sharded_shard", "lc3plus_enc_sharded_device",
     "lc3plus_enc_sharded_owner", "lc3plus_enc_sharded_input_samples", "lc3plus_enc_sharded_num_bytes", "lc3plus_enc_sharded_stride",
@@ -48,6 +48,9 @@ EXPORTS = [
 ]
 # the PCM format word of the batch calls (include/lc3plus_batch.h): a sample type - 16, 24, 32 or PCM_FLOAT32 - alone or with one layout
 PCM_FLOAT32, PCM_INTERLEAVED, PCM_CHANNEL_MAJOR = 0x80, 0x100, 0x200
+# the wire sample types: an element of 1, 2 or 3 bytes that stands for the 16- or the 24-bit integer format (big-endian, packed 24 bits, G.711)
+PCM_S16_BE, PCM_S24_3LE, PCM_S24_3BE, PCM_ULAW, PCM_ALAW = 0x81, 0x82, 0x83, 0x84, 0x85
+PCM_NAMES = {"s16be": PCM_S16_BE, "s24_3le": PCM_S24_3LE, "s24_3be": PCM_S24_3BE, "ulaw": PCM_ULAW, "alaw": PCM_ALAW}
 PCM_LAYOUTS = {None: 0, "default": 0, "interleaved": PCM_INTERLEAVED, "channel_major": PCM_CHANNEL_MAJOR}
 # flag bits of Batch.encode_device_rates (lc3plus_enc_batch_encode_rates_device)
 ENC_FL_RATE, ENC_FL_BW_REFUSED, ENC_FL_BW_RANGE = 1, 2, 4
@@ -182,12 +185,18 @@ def load_library():
         L.lc3plus_pcm_format_check.argtypes = [C.c_int]
         L.lc3plus_pcm_offset.argtypes = [C.c_int] * 8
         L.lc3plus_pcm_offset.restype = C.c_int64
+        L.lc3plus_pcm_elem_bytes.argtypes = [C.c_int]
+        for f in (L.lc3plus_pcm_to_native, L.lc3plus_pcm_from_native):
+            f.argtypes = [C.c_int, C.c_void_p, C.c_int64, C.c_void_p]
         _LIB = L
     return _LIB
 
 
 def pcm_format(sample, layout=None):
-    """The format word of a sample type (16, 24, 32, PCM_FLOAT32 or a numpy dtype) and a layout (None / "default", "interleaved", "channel_major" or the bit)."""
+    """The format word of a sample type (16, 24, 32, PCM_FLOAT32, a wire type or its name - "s16be", "s24_3le", "s24_3be", "ulaw", "alaw" - or a numpy dtype)
+    and a layout (None / "default", "interleaved", "channel_major" or the bit)."""
+    if isinstance(sample, str) and sample in PCM_NAMES:
+        sample = PCM_NAMES[sample]
     if not isinstance(sample, int):
         dt = np.dtype(sample)
         sample = {np.dtype(np.int16): 16, np.dtype(np.float32): PCM_FLOAT32}.get(dt)
@@ -201,15 +210,43 @@ def pcm_format(sample, layout=None):
 
 def pcm_shape(fmt, S, T, channels, N):
     """The array shape of one call's PCM in the layout of format word fmt."""
+    tail = (3,) if (fmt & 0xFF) in (PCM_S24_3LE, PCM_S24_3BE) else ()       # packed 24 bits: uint8 with a trailing axis of the three bytes
     if fmt & PCM_INTERLEAVED:
-        return (S, T * N, channels)
+        return (S, T * N, channels) + tail
     if fmt & PCM_CHANNEL_MAJOR:
-        return (S, channels, T * N)
-    return (S, T, channels, N)
+        return (S, channels, T * N) + tail
+    return (S, T, channels, N) + tail
 
 
 def pcm_dtype(fmt):
-    return {16: np.int16, PCM_FLOAT32: np.float32}.get(fmt & 0xFF, np.int32)
+    return {16: np.int16, PCM_FLOAT32: np.float32, PCM_S16_BE: np.dtype(">i2"), PCM_S24_3LE: np.uint8, PCM_S24_3BE: np.uint8, PCM_ULAW: np.uint8,
+            PCM_ALAW: np.uint8}.get(fmt & 0xFF, np.int32)
+
+
+def pcm_to_native(fmt, wire):
+    """Wire elements (an array of pcm_dtype(fmt); packed 24 bits with a trailing axis of 3) -> the int16 / int32 they stand for (lc3plus_pcm_to_native)."""
+    fmt = pcm_format(fmt & 0xFF, fmt & 0x300) if isinstance(fmt, int) else pcm_format(fmt)
+    wire = np.ascontiguousarray(wire, dtype=pcm_dtype(fmt))
+    p24 = (fmt & 0xFF) in (PCM_S24_3LE, PCM_S24_3BE)
+    if p24 and wire.shape[-1:] != (3,):
+        raise ValueError("packed 24-bit samples need a trailing axis of 3, not shape %s" % (wire.shape,))
+    out = np.zeros(wire.shape[:-1] if p24 else wire.shape, dtype=np.int32 if p24 else np.int16)
+    rc = load_library().lc3plus_pcm_to_native(fmt, wire.ctypes.data, out.size, out.ctypes.data) if out.size else 0
+    if rc:
+        raise LC3Error(rc, "lc3plus_pcm_to_native")
+    return out
+
+
+def pcm_from_native(fmt, native):
+    """int16 (int32 for packed 24 bits) -> the wire elements the decoder would write for them, saturation included (lc3plus_pcm_from_native)."""
+    fmt = pcm_format(fmt & 0xFF, fmt & 0x300) if isinstance(fmt, int) else pcm_format(fmt)
+    p24 = (fmt & 0xFF) in (PCM_S24_3LE, PCM_S24_3BE)
+    native = np.ascontiguousarray(native, dtype=np.int32 if p24 else np.int16)
+    out = np.zeros(native.shape + ((3,) if p24 else ()), dtype=pcm_dtype(fmt))
+    rc = load_library().lc3plus_pcm_from_native(fmt, native.ctypes.data, native.size, out.ctypes.data) if native.size else 0
+    if rc:
+        raise LC3Error(rc, "lc3plus_pcm_from_native")
+    return out
 
 
 def pcm_offset(fmt, channels, n_frames, samples, stream, frame, channel, sample):
@@ -370,14 +407,17 @@ class Batch(_StreamLifecycle):
         fmt = pcm_format(PCM_FLOAT32 if pcm.dtype == np.float32 else bitdepth & 0xFF, (bitdepth & 0x300) | (layout if isinstance(layout, int) else PCM_LAYOUTS[layout]))
         if pcm.dtype != pcm_dtype(fmt):
             raise ValueError("pcm dtype %s does not match format %#x" % (pcm.dtype, fmt))
+        tail = (3,) if (fmt & 0xFF) in (PCM_S24_3LE, PCM_S24_3BE) else ()      # packed 24 bits: the three bytes of a sample
+        if tail and pcm.shape[-1:] != tail:
+            raise ValueError("packed 24-bit pcm needs a trailing axis of 3, not shape %s" % (pcm.shape,))
         if fmt & (PCM_INTERLEAVED | PCM_CHANNEL_MAJOR):
-            n = pcm.shape[1] if fmt & PCM_INTERLEAVED else pcm.shape[-1]
+            n = pcm.shape[1] if fmt & PCM_INTERLEAVED else pcm.shape[2]
             T = n // self.N
-            if pcm.ndim != 3 or n % self.N or pcm.shape != pcm_shape(fmt, self.n_streams, T, self.channels, self.N):
+            if pcm.ndim != 3 + len(tail) or n % self.N or pcm.shape != pcm_shape(fmt, self.n_streams, T, self.channels, self.N):
                 raise ValueError("pcm shape %s is not %s" % (pcm.shape, "[n_streams, T * N, channels]" if fmt & PCM_INTERLEAVED else "[n_streams, channels, T * N]"))
             return fmt, T
         T = pcm.shape[1]
-        if pcm.shape not in (pcm_shape(fmt, self.n_streams, T, self.channels, self.N), (self.n_streams, T, self.N) if self.channels == 1 else None):
+        if pcm.shape not in (pcm_shape(fmt, self.n_streams, T, self.channels, self.N), (self.n_streams, T, self.N) + tail if self.channels == 1 else None):
             raise ValueError("pcm shape %s is not [n_streams, T, channels, N]" % (pcm.shape,))
         return fmt, T
 

@@ -571,6 +571,43 @@ DEC_SYNTH_KERNEL(const lc3d_plan* __restrict__ P, float* __restrict__ state,
                     for (int i = lane; i < (N >> 2); i += WAVE)
                         ((float4*)op)[i] = make_float4(out[4 * i] * 0x1p-15f, out[4 * i + 1] * 0x1p-15f, out[4 * i + 2] * 0x1p-15f, out[4 * i + 3] * 0x1p-15f);
                 } else for (int i = lane; i < N; i += WAVE) op[(size_t)i * ps] = out[i] * 0x1p-15f;
+            } else if (lc3d_pcm_type_wire(ty)) {
+                /* the wire types (lc3_plan.h): the 16- or 24-bit integer result of the branches around this one, then bytes swapped, saturated to 24 bits or
+                 * compressed by G.711.  Exactly N elements of 1, 2 or 3 bytes are written: one, two or three whole dwords (four samples) per lane where the samples
+                 * follow each other and the frame's first byte is on a dword, the rest byte by byte. */
+                const int eb = lc3d_pcm_elem_bytes(ty);
+                uint8_t* op = (uint8_t*)pcm + o * eb;
+                const bool w24 = eb == 3, be = ty == LC3D_PCM_S16_BE || ty == LC3D_PCM_S24_3BE, al = ty == LC3D_PCM_ALAW;
+                /* sample i as the bytes it is stored as, the first byte lowest */
+                auto wire = [&](int i) -> unsigned {
+                    if (w24) {
+                        const double r = round((double)(0x1p23f * (out[i] * 0x1p-15f)));
+                        const unsigned v = (unsigned)lc3d_pcm_sat24((r >= -2147483648.0 && r < 2147483648.0) ? (int32_t)r : (int32_t)0x80000000) & 0xffffffu;
+                        return be ? __builtin_bswap32(v) >> 8 : v;
+                    }
+                    const float tt = (float)round((double)(0x1p15f * (out[i] * 0x1p-15f)));
+                    const int x = (int)fmaxf(fminf(tt, 32767.0f), -32768.0f);
+                    if (eb == 1) return (unsigned)lc3d_g711_compress(x, al);
+                    return be ? __builtin_bswap32((unsigned)x) >> 16 : (unsigned)x & 0xffffu;
+                };
+                int done = 0;
+                if (ps == 1 && (((size_t)op) & 3) == 0) {            /* four samples per lane, like the float output: 4, 8 or 12 bytes of whole dwords, consecutive lanes consecutive bytes */
+                    for (int i = lane; i < (N >> 2); i += WAVE) {
+                        const unsigned a = wire(4 * i), b = wire(4 * i + 1), c = wire(4 * i + 2), e = wire(4 * i + 3);
+                        unsigned* q = (unsigned*)op + eb * i;
+                        if (eb == 1) q[0] = a | b << 8 | c << 16 | e << 24;
+                        else if (eb == 2) { q[0] = a | b << 16; q[1] = c | e << 16; }
+                        else { q[0] = a | b << 24; q[1] = b >> 8 | c << 16; q[2] = c >> 16 | e << 8; }
+                    }
+                    done = N & ~3;
+                }
+                for (int i = done + lane; i < N; i += WAVE) {
+                    const unsigned v = wire(i);
+                    uint8_t* q = op + (size_t)i * ps * eb;
+                    q[0] = (uint8_t)v;
+                    if (eb > 1) q[1] = (uint8_t)(v >> 8);
+                    if (eb > 2) q[2] = (uint8_t)(v >> 16);
+                }
             } else {
                 int32_t* op = (int32_t*)pcm + o;
                 const float sc = ty == 24 ? 0x1p23f : 0x1p31f;

@@ -22,11 +22,11 @@
 #endif
 #undef FRONT_KERNEL_NAME
 #if defined(LC3_BIG) && FRONT_PCM_FMT
-#define FRONT_KERNEL_NAME lc3_enc_front_kernel_big_fmt
+#define FRONT_KERNEL_NAME LC3_FMT_CAT(lc3_enc_front_kernel_big)
 #elif defined(LC3_BIG)
 #define FRONT_KERNEL_NAME lc3_enc_front_kernel_big
 #elif FRONT_PCM_FMT
-#define FRONT_KERNEL_NAME lc3_enc_front_kernel_fmt
+#define FRONT_KERNEL_NAME LC3_FMT_CAT(lc3_enc_front_kernel)
 #else
 #define FRONT_KERNEL_NAME lc3_enc_front_kernel
 #endif
@@ -57,7 +57,7 @@ FRONT_KERNEL_NAME(const lc3d_plan* __restrict__ P, const lc3d_chan* __restrict__
     else {
         const int ps = lc3d_pcm_stride(bitdepth, channels);
         const size_t pidx = lc3d_pcm_frame(bitdepth, channels, T, N, strm, t0 - 1, ch) + (size_t)(N - ml) * ps;
-        for (int j = lane; j < ml; j += WAVE) L.xbuf[MEMCAP - ml + j] = pcm_in(pcm, bitdepth, pidx + (size_t)j * ps);
+        for (int j = lane; j < ml; j += WAVE) L.xbuf[MEMCAP - ml + j] = PCM_IN(pcm, bitdepth, pidx + (size_t)j * ps);
     }
 #else
     else {
@@ -85,12 +85,12 @@ FRONT_KERNEL_NAME(const lc3d_plan* __restrict__ P, const lc3d_chan* __restrict__
 #if FRONT_PCM_FMT
         {                                                                              /* by the format word: the frame's first element and the step between its samples */
             const size_t o = lc3d_pcm_frame(bitdepth, channels, T, N, strm, t, ch);
-            if (pcm_f32_wide(pcm, bitdepth, o, N)) {                                   /* float samples one after the other: 16 bytes per lane */
+            if (PCM_F32_WIDE(pcm, bitdepth, o, N)) {                                   /* float samples one after the other: 16 bytes per lane */
                 const float4* p = (const float4*)((const float*)pcm + o);
                 for (int i = lane; i < (N >> 2); i += WAVE) *(float4*)&XCUR(L)[4 * i] = pcm_f32x4(p[i]);
             } else {
                 const int ps = lc3d_pcm_stride(bitdepth, channels);
-                for (int i = lane; i < N; i += WAVE) XCUR(L)[i] = pcm_in(pcm, bitdepth, o + (size_t)i * ps);
+                for (int i = PCM_RUN(true, pcm, bitdepth, o, N, XCUR(L), lane, 1.0f) + lane; i < N; i += WAVE) XCUR(L)[i] = PCM_IN(pcm, bitdepth, o + (size_t)i * ps);
             }
         }
 #else

@@ -78,7 +78,7 @@ __device__ __forceinline__ void f4_dft240x4(float* x, const lc3d_plan* __restric
 #endif
 extern "C" __global__ void __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(F4_WAVES, F4_WAVES)))
 #ifdef LC3_PCM_FMT               /* the object of the PCM formats beyond 16 / 24 / 32 (float samples, the interleaved and the channel-major layout): the PCM load differs, nothing else */
-lc3_enc_front4_kernel_fmt(
+LC3_FMT_CAT(lc3_enc_front4_kernel)(
 #else
 lc3_enc_front4_kernel(
 #endif
@@ -106,14 +106,14 @@ lc3_enc_front4_kernel(
          * bytes per frame from a 16-byte aligned base) take 16 bytes per lane like the 16-bit ones of the kernel without the suffix. */
         const int ps = lc3d_pcm_stride(bitdepth, channels);
         const size_t pf0 = lc3d_pcm_frame(bitdepth, channels, T, N, strm, t0, ch), pfst = lc3d_pcm_fstep(bitdepth, channels, N);
-        const bool fastf = pcm_f32_wide(pcm, bitdepth, pf0, N) && ((pfst * 4) & 15) == 0;
+        const bool fastf = PCM_F32_WIDE(pcm, bitdepth, pf0, N) && ((pfst * 4) & 15) == 0;
         if (t0 == 0) { for (int i = lane; i < MEMCAP; i += WAVE) L.x[i] = xprev[(size_t)cs * xprev_stride + i]; }
         else {
             const size_t pidx = pf0 - pfst + (size_t)(N - MEMCAP) * ps;
             if (fastf) {
                 const float4* p = (const float4*)((const float*)pcm + pidx);
                 for (int j = lane; j < MEMCAP / 4; j += WAVE) *(float4*)&L.x[4 * j] = pcm_f32x4(p[j]);
-            } else for (int j = lane; j < MEMCAP; j += WAVE) L.x[j] = pcm_in(pcm, bitdepth, pidx + (size_t)j * ps);
+            } else for (int j = PCM_RUN(true, pcm, bitdepth, pidx, MEMCAP, L.x, lane, 1.0f) + lane; j < MEMCAP; j += WAVE) L.x[j] = PCM_IN(pcm, bitdepth, pidx + (size_t)j * ps);
         }
         if (fastf) {
             for (int idx = lane; idx < 120 * nf; idx += WAVE) {                          /* 120 x 16 bytes per frame */
@@ -123,7 +123,7 @@ lc3_enc_front4_kernel(
         } else {
             for (int f = 0; f < nf; f++) {
                 const size_t o = pf0 + (size_t)f * pfst;
-                for (int i = lane; i < N; i += WAVE) L.x[MEMCAP + N * f + i] = pcm_in(pcm, bitdepth, o + (size_t)i * ps);
+                for (int i = PCM_RUN(true, pcm, bitdepth, o, N, &L.x[MEMCAP + N * f], lane, 1.0f) + lane; i < N; i += WAVE) L.x[MEMCAP + N * f + i] = PCM_IN(pcm, bitdepth, o + (size_t)i * ps);
             }
         }
     }

@@ -58,7 +58,7 @@ __device__ __forceinline__ void fm_stage(const uint8_t* __restrict__ map, const 
 
 extern "C" __global__ void __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(4, 4)))
 #ifdef LC3_PCM_FMT               /* the object of the PCM formats beyond 16 / 24 / 32 (float samples, the interleaved and the channel-major layout): the PCM load differs, nothing else */
-lc3_enc_frontm_kernel_fmt(
+LC3_FMT_CAT(lc3_enc_frontm_kernel)(
 #else
 lc3_enc_frontm_kernel(
 #endif
@@ -88,9 +88,9 @@ lc3_enc_frontm_kernel(
     if (t0 == 0) { for (int i = lane; i < MEMCAP; i += WAVE) L.x[i] = xprev[(size_t)cs * xprev_stride + i]; }
     else {
         const size_t pidx = pf0 - pfst + (size_t)(N - ml) * ps;
-        for (int j = lane; j < ml; j += WAVE) L.x[MEMCAP - ml + j] = pcm_in(pcm, bitdepth, pidx + (size_t)j * ps);
+        for (int j = lane; j < ml; j += WAVE) L.x[MEMCAP - ml + j] = PCM_IN(pcm, bitdepth, pidx + (size_t)j * ps);
     }
-    if (pcm_f32_wide(pcm, bitdepth, pf0, N) && ((pfst * 4) & 15) == 0) {
+    if (PCM_F32_WIDE(pcm, bitdepth, pf0, N) && ((pfst * 4) & 15) == 0) {
         const int per = N >> 2, ntask = nf * per;                 /* 16 bytes per lane */
         const float rp = 1.0f / (float)per;
         for (int tk = lane; tk < ntask; tk += WAVE) {
@@ -100,7 +100,7 @@ lc3_enc_frontm_kernel(
     } else {
         for (int f = 0; f < nf; f++) {
             const size_t o = pf0 + (size_t)f * pfst;
-            for (int i = lane; i < N; i += WAVE) L.x[MEMCAP + N * f + i] = pcm_in(pcm, bitdepth, o + (size_t)i * ps);
+            for (int i = PCM_RUN(true, pcm, bitdepth, o, N, &L.x[MEMCAP + N * f], lane, 1.0f) + lane; i < N; i += WAVE) L.x[MEMCAP + N * f + i] = PCM_IN(pcm, bitdepth, o + (size_t)i * ps);
         }
     }
 #else

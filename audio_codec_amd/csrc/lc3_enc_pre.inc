@@ -60,18 +60,48 @@ __device__ __forceinline__ void pre48_put(float* __restrict__ d, const uint4 v, 
 }
 
 #ifdef LC3_PCM_FMT
-/* lc3_enc_resample48_kernel (below) for float samples that follow each other (LC3PLUS_PCM_FLOAT32 in the default or the channel-major layout of the format word
- * fmt): its tap and LDS scheme unchanged, only the load and convert step differs.  A frame is 120 pieces of 16 bytes instead of 60: a lane loads piece lane and
- * piece lane + 60 of both frames of its pair and writes each to LDS as one float4 - consecutive lanes, consecutive quad-words. */
-__device__ __forceinline__ void pre48_putf(float* __restrict__ d, const float4 v, const float sf)
+/* lc3_enc_resample48_kernel (below) for samples that follow each other in the default or the channel-major layout of the format word fmt: its tap and LDS scheme
+ * unchanged, only the load and convert step differs.  A frame is 120 pieces of four samples instead of 60 of eight: a lane loads piece lane and piece lane + 60 of
+ * both frames of its pair, keeps them as loaded, and writes each to LDS as one float4 - consecutive lanes, consecutive quad-words.  One text, two kernels:
+ *   lc3_enc_resample48f_kernel (the _fmt object): float samples, a piece is 16 bytes of a 16-byte aligned frame;
+ *   lc3_enc_resample48w_kernel (the _wire object): the five wire types (lc3_plan.h: LC3D_PCM_S16_BE ... LC3D_PCM_ALAW), a piece is one, two or three whole dwords
+ *   by the element size of a dword-aligned frame (12 registers for the four pieces, the float kernel has 16), converted by pcm_wire_x4. */
+#ifdef LC3_PCM_WIRE
+struct Pre48Raw { unsigned a, b, c; };
+typedef Pre48Raw pre48_piece;
+typedef unsigned pre48_word;                 /* what the frame pointer counts in */
+#define PRE48_FN lc3_enc_resample48w_kernel
+#define PRE48_WORDS(elems) ((elems) * nd / 4)            /* elements -> words of the frame pointer */
+#define PRE48_ZERO {0, 0, 0}
+__device__ __forceinline__ pre48_piece pre48_ld(const unsigned* __restrict__ fr, int nd, int piece)
+{
+    Pre48Raw r = {0, 0, 0};
+    const unsigned* p = fr + piece * nd;
+    r.a = p[0]; if (nd > 1) r.b = p[1]; if (nd > 2) r.c = p[2];
+    return r;
+}
+__device__ __forceinline__ void pre48_putx(float* __restrict__ d, int ty, const pre48_piece r, const float sf)
+{
+    const float4 c = pcm_wire_x4(ty, r.a, r.b, r.c);
+    *(float4*)d = make_float4(c.x * sf, c.y * sf, c.z * sf, c.w * sf);
+}
+#else
+typedef float4 pre48_piece;
+typedef float pre48_word;
+#define PRE48_FN lc3_enc_resample48f_kernel
+#define PRE48_WORDS(elems) (elems)
+#define PRE48_ZERO make_float4(0, 0, 0, 0)
+__device__ __forceinline__ pre48_piece pre48_ld(const float* __restrict__ fr, int, int piece) { return ((const float4*)fr)[piece]; }
+__device__ __forceinline__ void pre48_putx(float* __restrict__ d, int, const float4 v, const float sf)
 {
     const float4 c = pcm_f32x4(v);
     *(float4*)d = make_float4(c.x * sf, c.y * sf, c.z * sf, c.w * sf);
 }
+#endif
 
 extern "C" __global__ void __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(3, 3)))
-lc3_enc_resample48f_kernel(const lc3d_plan* __restrict__ P, const float* __restrict__ pcm /* 16-byte aligned */, int fmt, int channels, int memcap,
-                           int T, int tb, int nt, int ncs, float* __restrict__ d12 /* [cs][T][128] */, const float* __restrict__ xprev, int xprev_stride)
+PRE48_FN(const lc3d_plan* __restrict__ P, const pre48_word* __restrict__ pcm /* 16-byte (float) or 4-byte (wire) aligned */, int fmt, int channels, int memcap,
+         int T, int tb, int nt, int ncs, float* __restrict__ d12 /* [cs][T][128] */, const float* __restrict__ xprev, int xprev_stride)
 {
     __shared__ Pre48Lds L;
     const int lane = threadIdx.x;
@@ -85,16 +115,22 @@ lc3_enc_resample48f_kernel(const lc3d_plan* __restrict__ P, const float* __restr
 #pragma unroll
     for (int m = 0; m < 60; m++) tap[m] = P->rs_taps[p * 60 + m];
     float* xs = L.xs;
-    const float* fr0 = pcm + lc3d_pcm_frame(fmt, channels, T, 480, strm, t0, ch);          /* frame t0 of this channel-stream; the next one is fstep further */
-    const size_t fstep = lc3d_pcm_fstep(fmt, channels, 480);
-    float4 fa0 = make_float4(0, 0, 0, 0), fa1 = fa0, fb0 = fa0, fb1 = fa0;
+    const int ty = fmt & LC3D_PCM_TYPE_MASK, nd = lc3d_pcm_elem_bytes(ty);         /* (wire) dwords per piece of four samples = bytes per element */
+    const size_t e0 = lc3d_pcm_frame(fmt, channels, T, 480, strm, t0, ch);         /* frame t0 of this channel-stream, in elements; the next one is fstep further */
+    const pre48_word* fr0 = pcm + PRE48_WORDS(e0);
+    const size_t fstep = PRE48_WORDS(lc3d_pcm_fstep(fmt, channels, 480));
+    pre48_piece fa0 = PRE48_ZERO, fa1 = fa0, fb0 = fa0, fb1 = fa0;
     if (lane < 60) {
-        fa0 = ((const float4*)fr0)[lane]; fa1 = ((const float4*)fr0)[lane + 60];
-        if (t0 + 1 < t1) { fb0 = ((const float4*)(fr0 + fstep))[lane]; fb1 = ((const float4*)(fr0 + fstep))[lane + 60]; }
+        fa0 = pre48_ld(fr0, nd, lane); fa1 = pre48_ld(fr0, nd, lane + 60);
+        if (t0 + 1 < t1) { fb0 = pre48_ld(fr0 + fstep, nd, lane); fb1 = pre48_ld(fr0 + fstep, nd, lane + 60); }
     }
     if (lane < 60) {   /* the 60 samples in front of frame t0: from the PCM of this call, or the stream's MDCT memory for its first frame */
         float v;
+#ifdef LC3_PCM_WIRE
+        if (t0 > 0) v = pcm_wire(pcm, ty, e0 - lc3d_pcm_fstep(fmt, channels, 480) + 420 + lane);
+#else
         if (t0 > 0) v = pcm_f32((fr0 - fstep)[420 + lane]);
+#endif
         else v = xprev[(size_t)cs * xprev_stride + (memcap - 60 + lane)];
         xs[lane] = v * sf;
     }
@@ -106,10 +142,10 @@ lc3_enc_resample48f_kernel(const lc3d_plan* __restrict__ P, const float* __restr
         LSYNC();
         if (t > t0 && lane < 15) ((float4*)xs)[lane] = tl;
         if (lane < 60) {
-            pre48_putf(xs + 60 + 4 * lane, fa0, sf); pre48_putf(xs + 300 + 4 * lane, fa1, sf); pre48_putf(xs + 540 + 4 * lane, fb0, sf); pre48_putf(xs + 780 + 4 * lane, fb1, sf);
-            const float* fn = fr0 + (size_t)(t + 2 - t0) * fstep;
-            if (t + 2 < t1) { fa0 = ((const float4*)fn)[lane]; fa1 = ((const float4*)fn)[lane + 60]; }
-            if (t + 3 < t1) { fb0 = ((const float4*)(fn + fstep))[lane]; fb1 = ((const float4*)(fn + fstep))[lane + 60]; }
+            pre48_putx(xs + 60 + 4 * lane, ty, fa0, sf); pre48_putx(xs + 300 + 4 * lane, ty, fa1, sf); pre48_putx(xs + 540 + 4 * lane, ty, fb0, sf); pre48_putx(xs + 780 + 4 * lane, ty, fb1, sf);
+            const pre48_word* fn = fr0 + (size_t)(t + 2 - t0) * fstep;
+            if (t + 2 < t1) { fa0 = pre48_ld(fn, nd, lane); fa1 = pre48_ld(fn, nd, lane + 60); }
+            if (t + 3 < t1) { fb0 = pre48_ld(fn + fstep, nd, lane); fb1 = pre48_ld(fn + fstep, nd, lane + 60); }
         }
         LSYNC();
         float acc[4] = {0.0f, 0.0f, 0.0f, 0.0f};

@@ -4,7 +4,7 @@
  * format word existed.  RESAMPLE_PCM_FMT 1 (the -DLC3_PCM_FMT object): lc3_enc_resample_fmt_kernel for the formats beyond those (float samples, the interleaved and the channel-major layout,
  * lc3_plan.h: lc3d_pcm_*); the two differ in the PCM load alone. */
 #if RESAMPLE_PCM_FMT
-#define RESAMPLE_FN lc3_enc_resample_fmt_kernel
+#define RESAMPLE_FN LC3_RESAMPLE_FMT_FN
 #else
 #define RESAMPLE_FN lc3_enc_resample_kernel
 #endif
@@ -48,18 +48,18 @@ RESAMPLE_FN(const lc3d_plan* __restrict__ P, const float* __restrict__ state, in
             const size_t pf = lc3d_pcm_frame(bitdepth, channels, T, N, strm, t, ch), pp = t > 0 ? lc3d_pcm_frame(bitdepth, channels, T, N, strm, t - 1, ch) : 0;
             for (int j = lane; j < mlen; j += WAVE) {
                 float v;
-                if (t > 0) v = pcm_in(pcm, bitdepth, pp + (size_t)(N - mlen + j) * ps);
+                if (t > 0) v = PCM_IN(pcm, bitdepth, pp + (size_t)(N - mlen + j) * ps);
                 else v = xprev[(size_t)cs * xprev_stride + (memcap - mlen + j)];
                 xs[j] = v * sf;
             }
-            if (pcm_f32_wide(pcm, bitdepth, pf, N)) {              /* float samples one after the other: 16 bytes per lane */
+            if (PCM_F32_WIDE(pcm, bitdepth, pf, N)) {              /* float samples one after the other: 16 bytes per lane */
                 const float4* p = (const float4*)((const float*)pcm + pf);
                 for (int i = lane; i < (N >> 2); i += WAVE) {
                     const float4 v = pcm_f32x4(p[i]);
                     float* d = &xs[mlen + 4 * i];
                     d[0] = v.x * sf; d[1] = v.y * sf; d[2] = v.z * sf; d[3] = v.w * sf;
                 }
-            } else for (int j = lane; j < N; j += WAVE) xs[mlen + j] = pcm_in(pcm, bitdepth, pf + (size_t)j * ps) * sf;
+            } else for (int j = PCM_RUN(false, pcm, bitdepth, pf, N, xs + mlen, lane, sf) + lane; j < N; j += WAVE) xs[mlen + j] = PCM_IN(pcm, bitdepth, pf + (size_t)j * ps) * sf;
         }
 #else
         if (t > t0 && fast16) {

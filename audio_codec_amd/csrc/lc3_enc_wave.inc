@@ -94,12 +94,12 @@ ENC_WAVE_FN(LC3_OW_ARGS LC3_OW_OPT(LC3_OW_ARGS_, LC3_TU_VAR, LC3_TU_VBW, LC3_TU_
 #if ENC_PCM_FMT
         else {                                           /* by the format word: the frame's first element and the step between its samples */
             const size_t o = lc3d_pcm_frame(bitdepth, channels, T, N, strm, t, ch);
-            if (pcm_f32_wide(pcm, bitdepth, o, N)) {     /* float samples one after the other: 16 bytes per lane */
+            if (PCM_F32_WIDE(pcm, bitdepth, o, N)) {     /* float samples one after the other: 16 bytes per lane */
                 const float4* p = (const float4*)((const float*)pcm + o);
                 for (int i = lane; i < (N >> 2); i += WAVE) *(float4*)&XCUR(L)[4 * i] = pcm_f32x4(p[i]);
             } else {
                 const int ps = lc3d_pcm_stride(bitdepth, channels);
-                for (int i = lane; i < N; i += WAVE) XCUR(L)[i] = pcm_in(pcm, bitdepth, o + (size_t)i * ps);
+                for (int i = PCM_RUN(true, pcm, bitdepth, o, N, XCUR(L), lane, 1.0f) + lane; i < N; i += WAVE) XCUR(L)[i] = PCM_IN(pcm, bitdepth, o + (size_t)i * ps);
             }
         }
 #else

@@ -530,7 +530,9 @@ LC3_Error lc3plus_enc_batch_set_bandwidth(lc3plus_batch* b, int stream, int band
 /* The PCM format word of every batch call that takes PCM (include/lc3plus_batch.h: LC3PLUS_PCM_*; the arithmetic is lc3_plan.h's, shared with the kernels):
  * 16, 24, 32 or LC3PLUS_PCM_FLOAT32, alone or with one of the two layout bits. */
 typedef char pcm_format_words_agree[(LC3PLUS_PCM_FLOAT32 == LC3D_PCM_FLOAT32 && LC3PLUS_PCM_INTERLEAVED == LC3D_PCM_INTERLEAVED &&
-                                    LC3PLUS_PCM_CHANNEL_MAJOR == LC3D_PCM_CHANNEL_MAJOR) ? 1 : -1];
+                                    LC3PLUS_PCM_CHANNEL_MAJOR == LC3D_PCM_CHANNEL_MAJOR && LC3PLUS_PCM_S16_BE == LC3D_PCM_S16_BE &&
+                                    LC3PLUS_PCM_S24_3LE == LC3D_PCM_S24_3LE && LC3PLUS_PCM_S24_3BE == LC3D_PCM_S24_3BE &&
+                                    LC3PLUS_PCM_ULAW == LC3D_PCM_ULAW && LC3PLUS_PCM_ALAW == LC3D_PCM_ALAW) ? 1 : -1];
 static int pcm_format_ok(int format) { return lc3d_pcm_format_ok(format); }
 static int pcm_format_plain(int format) { return format == 16 || format == 24 || format == 32; }
 /* Host-only hooks: the format check and the address rule without a GPU (tests/test_pcm_format_cpu.py). */
@@ -540,6 +542,42 @@ int64_t lc3plus_pcm_offset(int format, int channels, int n_frames, int samples, 
     if (!pcm_format_ok(format) || channels <= 0 || n_frames <= 0 || samples <= 0 || stream < 0 || frame < 0 || frame >= n_frames || channel < 0 ||
         channel >= channels || sample < 0 || sample >= samples) return -1;
     return (int64_t)(lc3d_pcm_frame(format, channels, n_frames, samples, stream, frame, channel) + (size_t)sample * lc3d_pcm_stride(format, channels));
+}
+
+int lc3plus_pcm_elem_bytes(int format) { return pcm_format_ok(format) ? lc3d_pcm_elem_bytes(format) : -1; }
+/* The wire types' conversion rule on the host (lc3_plan.h: the text the kernels compile too), element by element, byte by byte: no alignment needed on the wire side. */
+LC3_Error lc3plus_pcm_to_native(int format, const void* src, int64_t n, void* dst)
+{
+    const int ty = format & LC3D_PCM_TYPE_MASK;
+    if (!src || !dst) return LC3_NULL_ERROR;
+    if ((format & ~(LC3D_PCM_TYPE_MASK | LC3D_PCM_LAYOUT_MASK)) || !lc3d_pcm_type_wire(ty) || n < 0) return LC3_ERROR;
+    const uint8_t* s = (const uint8_t*)src;
+    for (int64_t i = 0; i < n; i++) {
+        if (ty == LC3D_PCM_ULAW || ty == LC3D_PCM_ALAW) ((int16_t*)dst)[i] = (int16_t)lc3d_g711_expand(s[i], ty == LC3D_PCM_ALAW);
+        else if (ty == LC3D_PCM_S16_BE) ((int16_t*)dst)[i] = (int16_t)((s[2 * i] << 8) | s[2 * i + 1]);
+        else {
+            const int lo = ty == LC3D_PCM_S24_3LE ? 0 : 2;
+            ((int32_t*)dst)[i] = (int32_t)(int8_t)s[3 * i + 2 - lo] * 65536 + ((s[3 * i + 1] << 8) | s[3 * i + lo]);
+        }
+    }
+    return LC3_OK;
+}
+LC3_Error lc3plus_pcm_from_native(int format, const void* src, int64_t n, void* dst)
+{
+    const int ty = format & LC3D_PCM_TYPE_MASK;
+    if (!src || !dst) return LC3_NULL_ERROR;
+    if ((format & ~(LC3D_PCM_TYPE_MASK | LC3D_PCM_LAYOUT_MASK)) || !lc3d_pcm_type_wire(ty) || n < 0) return LC3_ERROR;
+    uint8_t* d = (uint8_t*)dst;
+    for (int64_t i = 0; i < n; i++) {
+        if (ty == LC3D_PCM_ULAW || ty == LC3D_PCM_ALAW) d[i] = (uint8_t)lc3d_g711_compress(((const int16_t*)src)[i], ty == LC3D_PCM_ALAW);
+        else if (ty == LC3D_PCM_S16_BE) { const uint16_t v = (uint16_t)((const int16_t*)src)[i]; d[2 * i] = (uint8_t)(v >> 8); d[2 * i + 1] = (uint8_t)v; }
+        else {
+            const uint32_t v = (uint32_t)lc3d_pcm_sat24(((const int32_t*)src)[i]);
+            const int lo = ty == LC3D_PCM_S24_3LE ? 0 : 2;
+            d[3 * i + lo] = (uint8_t)v; d[3 * i + 1] = (uint8_t)(v >> 8); d[3 * i + 2 - lo] = (uint8_t)(v >> 16);
+        }
+    }
+    return LC3_OK;
 }
 
 static LC3_Error batch_encode(lc3plus_batch* b, const void* pcm, int pcm_on_device, int bitdepth, int n_frames, void* out, int out_stride,

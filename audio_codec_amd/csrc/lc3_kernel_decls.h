@@ -27,7 +27,7 @@
 #define LC3_OW_ARGS_PK_1 , const long long* __restrict__ poff /* [stream][dT] byte offset of each stream-frame in out, -1: not written */
 #define LC3_OW_OPT_(G, var, vbw, pk) G##VAR_##var G##VBW_##vbw G##PK_##pk
 #define LC3_OW_OPT(G, var, vbw, pk) LC3_OW_OPT_(G, var, vbw, pk)
-/* The variants: X(name, large layout, var, vbw, pk), each once more named name_fmt for the PCM formats beyond 16 / 24 / 32.  There is no large-layout kernel
+/* The variants: X(name, large layout, var, vbw, pk), each once more named name_fmt for the PCM formats beyond 16 / 24 / 32 and name_wire for the wire sample types.  There is no large-layout kernel
  * with per-frame bandwidths: that layout only serves 96 kHz, which is high-resolution and has no bandwidth controller. */
 #define LC3_OW_KERNELS(X) \
     X(lc3_encode_kernel,            0, 0, 0, 0) X(lc3_encode_kernel_pk,            0, 0, 0, 1) \
@@ -37,7 +37,8 @@
     X(lc3_encode_kernel_vbw,        0, 0, 1, 0) X(lc3_encode_kernel_vbw_pk,        0, 0, 1, 1) \
     X(lc3_encode_kernel_var_vbw,    0, 1, 1, 0) X(lc3_encode_kernel_var_vbw_pk,    0, 1, 1, 1)
 #define LC3_OW_DECL(name, big, var, vbw, pk) \
-    extern "C" __global__ void name(LC3_OW_ARGS LC3_OW_OPT(LC3_OW_ARGS_, var, vbw, pk)), name##_fmt(LC3_OW_ARGS LC3_OW_OPT(LC3_OW_ARGS_, var, vbw, pk));
+    extern "C" __global__ void name(LC3_OW_ARGS LC3_OW_OPT(LC3_OW_ARGS_, var, vbw, pk)), name##_fmt(LC3_OW_ARGS LC3_OW_OPT(LC3_OW_ARGS_, var, vbw, pk)), \
+        name##_wire(LC3_OW_ARGS LC3_OW_OPT(LC3_OW_ARGS_, var, vbw, pk));
 LC3_OW_KERNELS(LC3_OW_DECL)
 #undef LC3_OW_DECL
 
@@ -48,16 +49,16 @@ __global__ void lc3_enc_attack_kernel(const lc3d_plan* __restrict__ P, const lc3
 #define LC3_FRONT4_ARGS const lc3d_plan* __restrict__ P, const lc3d_chan* __restrict__ chans, const float* __restrict__ state, const void* __restrict__ pcm, int bitdepth, \
     int T, int tb, int nt, int ncs, float* __restrict__ spec, int srow, int RT, int r0, float* __restrict__ rec, float* __restrict__ xnext, \
     const float* __restrict__ xprev, int xprev_stride
-__global__ void lc3_enc_front4_kernel(LC3_FRONT4_ARGS), lc3_enc_front4_kernel_fmt(LC3_FRONT4_ARGS);
+__global__ void lc3_enc_front4_kernel(LC3_FRONT4_ARGS), lc3_enc_front4_kernel_fmt(LC3_FRONT4_ARGS), lc3_enc_front4_kernel_wire(LC3_FRONT4_ARGS);
 #define LC3_FRONT_ARGS const lc3d_plan* __restrict__ P, const lc3d_chan* __restrict__ chans, const float* __restrict__ state, const void* __restrict__ pcm, int bitdepth, \
     int T, int tb, int nt, int fpw, int ncs, float* __restrict__ spec, int srow, int RT, int r0, float* __restrict__ rec, float* __restrict__ xnext, \
     const float* __restrict__ xprev, int xprev_stride, int do_scf
 __global__ void lc3_enc_front_kernel(LC3_FRONT_ARGS), lc3_enc_front_kernel_big(LC3_FRONT_ARGS), lc3_enc_front_kernel_big_fmt(LC3_FRONT_ARGS),
-    lc3_enc_front_kernel_fmt(LC3_FRONT_ARGS);
+    lc3_enc_front_kernel_fmt(LC3_FRONT_ARGS), lc3_enc_front_kernel_wire(LC3_FRONT_ARGS), lc3_enc_front_kernel_big_wire(LC3_FRONT_ARGS);
 #define LC3_FRONTM_ARGS const lc3d_plan* __restrict__ P, const lc3d_chan* __restrict__ chans, const float* __restrict__ state, const void* __restrict__ pcm, int bitdepth, \
     int T, int tb, int nt, int F, int ncs, float* __restrict__ spec, int srow, int RT, int r0, float* __restrict__ rec, float* __restrict__ xnext, \
     const float* __restrict__ xprev, int xprev_stride
-__global__ void lc3_enc_frontm_kernel(LC3_FRONTM_ARGS), lc3_enc_frontm_kernel_fmt(LC3_FRONTM_ARGS);
+__global__ void lc3_enc_frontm_kernel(LC3_FRONTM_ARGS), lc3_enc_frontm_kernel_fmt(LC3_FRONTM_ARGS), lc3_enc_frontm_kernel_wire(LC3_FRONTM_ARGS);
 __global__ void lc3_enc_hp50_kernel(const lc3d_plan* __restrict__ P, float* __restrict__ state, int state_words, int scal_off, int T, int tb, int nt, int ncs,
     float* __restrict__ d12);
 #define LC3_PACK_ARGS const lc3d_plan* __restrict__ P, const lc3d_chan* __restrict__ chans, int* __restrict__ dump, int dstride, int T, int tb, int nt, int ncs, \
@@ -80,13 +81,15 @@ __global__ void lc3_enc_resample48_kernel(const lc3d_plan* __restrict__ P, const
     float* __restrict__ d12, const float* __restrict__ xprev, int xprev_stride);
 __global__ void lc3_enc_resample48f_kernel(const lc3d_plan* __restrict__ P, const float* __restrict__ pcm, int fmt, int channels, int memcap, int T, int tb, int nt,
     int ncs, float* __restrict__ d12, const float* __restrict__ xprev, int xprev_stride);
+__global__ void lc3_enc_resample48w_kernel(const lc3d_plan* __restrict__ P, const unsigned* __restrict__ pcm, int fmt, int channels, int memcap, int T, int tb, int nt,
+    int ncs, float* __restrict__ d12, const float* __restrict__ xprev, int xprev_stride);
 #define LC3_RESAMPLE96_ARGS const lc3d_plan* __restrict__ P, const int16_t* __restrict__ pcm, int channels, int memcap, int T, int tb, int nt, int ncs, \
     float* __restrict__ d12, const float* __restrict__ xprev, int xprev_stride
 __global__ void lc3_enc_resample96_kernel_n240(LC3_RESAMPLE96_ARGS), lc3_enc_resample96_kernel_n480(LC3_RESAMPLE96_ARGS),
     lc3_enc_resample96_kernel_n960(LC3_RESAMPLE96_ARGS);
 #define LC3_RESAMPLE_ARGS const lc3d_plan* __restrict__ P, const float* __restrict__ state, int state_words, int memcap, const void* __restrict__ pcm, int bitdepth, \
     int T, int tb, int nt, int ncs, float* __restrict__ d12, const float* __restrict__ xprev, int xprev_stride
-__global__ void lc3_enc_resample_fmt_kernel(LC3_RESAMPLE_ARGS), lc3_enc_resample_kernel(LC3_RESAMPLE_ARGS);
+__global__ void lc3_enc_resample_fmt_kernel(LC3_RESAMPLE_ARGS), lc3_enc_resample_kernel(LC3_RESAMPLE_ARGS), lc3_enc_resample_wire_kernel(LC3_RESAMPLE_ARGS);
 __global__ void lc3_enc_scf_lane_kernel(const lc3d_plan* __restrict__ P, int RT, int r0, int nt, int ncs, const float* __restrict__ rows, int srow,
     float* __restrict__ frec, int with_vq);
 #define LC3_SHAPE_ARGS const lc3d_plan* __restrict__ P, const lc3d_chan* __restrict__ chans, int T, int tb, int nt, int fpw, int ncs, float* __restrict__ rows, int srow, \

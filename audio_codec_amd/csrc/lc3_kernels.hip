@@ -141,6 +141,91 @@ __device__ __forceinline__ bool pcm_f32_wide(const void* __restrict__ pcm, int f
     return (fmt & (LC3D_PCM_TYPE_MASK | LC3D_PCM_INTERLEAVED)) == LC3D_PCM_FLOAT32 && (n & 3) == 0 && ((((size_t)pcm) + o * 4) & 15) == 0;
 }
 
+#ifdef LC3_PCM_WIRE
+/* The wire types (lc3_plan.h: LC3D_PCM_S16_BE ... LC3D_PCM_ALAW): element idx byte by byte - any layout, any alignment - as the integer the type stands for,
+ * converted as that depth is */
+__device__ __forceinline__ float pcm_wire(const void* __restrict__ pcm, int ty, size_t idx)
+{
+    const uint8_t* b = (const uint8_t*)pcm;
+    if (ty == LC3D_PCM_ULAW || ty == LC3D_PCM_ALAW) return (float)lc3d_g711_expand(b[idx], ty == LC3D_PCM_ALAW);
+    if (ty == LC3D_PCM_S16_BE) return (float)(int16_t)((b[2 * idx] << 8) | b[2 * idx + 1]);
+    const int lo = ty == LC3D_PCM_S24_3LE ? 0 : 2;
+    return (float)((int)(int8_t)b[3 * idx + 2 - lo] * 65536 + ((b[3 * idx + 1] << 8) | b[3 * idx + lo])) / 256.0f;
+}
+/* Four wire samples that follow each other, from the 4, 8 or 12 bytes they occupy, as whole little-endian dwords a, b, c (b, c unused by the shorter types) */
+__device__ __forceinline__ float4 pcm_wire_x4(int ty, unsigned a, unsigned b, unsigned c)
+{
+    if (ty == LC3D_PCM_ULAW || ty == LC3D_PCM_ALAW) {
+        const int al = ty == LC3D_PCM_ALAW;
+        return make_float4((float)lc3d_g711_expand(a & 0xff, al), (float)lc3d_g711_expand((a >> 8) & 0xff, al), (float)lc3d_g711_expand((a >> 16) & 0xff, al),
+                           (float)lc3d_g711_expand(a >> 24, al));
+    }
+    if (ty == LC3D_PCM_S16_BE) {                                /* the swapped dword holds the first sample in its high half */
+        const unsigned x = __builtin_bswap32(a), y = __builtin_bswap32(b);
+        return make_float4((float)(int16_t)(x >> 16), (float)(int16_t)(x & 0xffff), (float)(int16_t)(y >> 16), (float)(int16_t)(y & 0xffff));
+    }
+    int s0, s1, s2, s3;                                         /* each sample in the upper three bytes of a word, then an arithmetic shift */
+    if (ty == LC3D_PCM_S24_3LE) { s0 = (int)(a << 8); s1 = (int)((b << 16) | ((a >> 24) << 8)); s2 = (int)((c << 24) | ((b >> 16) << 8)); s3 = (int)(c & 0xffffff00u); }
+    else {
+        const unsigned x = __builtin_bswap32(a), y = __builtin_bswap32(b), z = __builtin_bswap32(c);
+        s0 = (int)(x & 0xffffff00u); s1 = (int)((x << 24) | (y >> 8)); s2 = (int)((y << 16) | (z >> 16)); s3 = (int)(z << 8);
+    }
+    return make_float4((float)(s0 >> 8) / 256.0f, (float)(s1 >> 8) / 256.0f, (float)(s2 >> 8) / 256.0f, (float)(s3 >> 8) / 256.0f);
+}
+/* n wire samples that follow each other from element o on (default and channel-major layouts) -> dst[0 .. n), times sf, by the whole wave: the pieces that lie
+ * entirely inside the run are loaded wide - G.711: 16 bytes = 16 samples per lane, S16_BE: 16 bytes = 8 samples, packed 24 bits: three dwords = 4 samples - where
+ * the run's first byte is aligned for that load (16, 16, 4); returns the number of samples done, the caller's per-sample loop takes the rest.  No byte outside the
+ * run is read.  QW: dst is 16-byte aligned (LDS) and gets one float4 per four samples. */
+template <bool QW> __device__ __forceinline__ void pcm_wire_put(float* __restrict__ d, const float4 v, const float sf)
+{
+    if (QW) *(float4*)d = make_float4(v.x * sf, v.y * sf, v.z * sf, v.w * sf);
+    else { d[0] = v.x * sf; d[1] = v.y * sf; d[2] = v.z * sf; d[3] = v.w * sf; }
+}
+template <bool QW> __device__ __forceinline__ int pcm_wire_run(const void* __restrict__ pcm, int fmt, size_t o, int n, float* __restrict__ dst, int lane, float sf)
+{
+    const int ty = fmt & LC3D_PCM_TYPE_MASK;
+    if (!lc3d_pcm_type_wire(ty) || (fmt & LC3D_PCM_INTERLEAVED) || (QW && (n & 3))) return 0;
+    const size_t at = (size_t)pcm + o * (size_t)lc3d_pcm_elem_bytes(ty);
+    if (ty == LC3D_PCM_ULAW || ty == LC3D_PCM_ALAW) {
+        if (at & 15) return 0;
+        for (int i = lane; i < (n >> 4); i += WAVE) {
+            const uint4 v = ((const uint4*)at)[i];
+            float* d = dst + 16 * i;
+            pcm_wire_put<QW>(d, pcm_wire_x4(ty, v.x, 0, 0), sf); pcm_wire_put<QW>(d + 4, pcm_wire_x4(ty, v.y, 0, 0), sf);
+            pcm_wire_put<QW>(d + 8, pcm_wire_x4(ty, v.z, 0, 0), sf); pcm_wire_put<QW>(d + 12, pcm_wire_x4(ty, v.w, 0, 0), sf);
+        }
+        return n & ~15;
+    }
+    if (ty == LC3D_PCM_S16_BE) {
+        if (at & 15) return 0;
+        for (int i = lane; i < (n >> 3); i += WAVE) {
+            const uint4 v = ((const uint4*)at)[i];
+            pcm_wire_put<QW>(dst + 8 * i, pcm_wire_x4(ty, v.x, v.y, 0), sf); pcm_wire_put<QW>(dst + 8 * i + 4, pcm_wire_x4(ty, v.z, v.w, 0), sf);
+        }
+        return n & ~7;
+    }
+    if (at & 3) return 0;
+    for (int i = lane; i < (n >> 2); i += WAVE) {
+        const unsigned* p = (const unsigned*)at + 3 * i;
+        pcm_wire_put<QW>(dst + 4 * i, pcm_wire_x4(ty, p[0], p[1], p[2]), sf);
+    }
+    return n & ~3;
+}
+#endif
+/* What the loaders of the -DLC3_PCM_FMT objects call.  Those objects come twice: _fmt for float samples and the two layouts, whose text is what it was before the
+ * wire types existed (PCM_RUN is 0 there, PCM_IN is pcm_in), and -DLC3_PCM_WIRE, named _wire, for the five wire types alone in any layout: the same kernels with
+ * the wire loaders in place of the float ones.  Kernels of their own for the reason the _fmt objects exist: a branch more in a loader moved the registers and the
+ * speed of the kernels that were there. */
+#ifdef LC3_PCM_WIRE
+#define PCM_IN(pcm, fmt, idx) pcm_wire(pcm, (fmt) & LC3D_PCM_TYPE_MASK, idx)
+#define PCM_RUN(QW, pcm, fmt, o, n, dst, lane, sf) pcm_wire_run<QW>(pcm, fmt, o, n, dst, lane, sf)
+#define PCM_F32_WIDE(pcm, fmt, o, n) false
+#else
+#define PCM_IN(pcm, fmt, idx) pcm_in(pcm, fmt, idx)
+#define PCM_RUN(QW, pcm, fmt, o, n, dst, lane, sf) 0
+#define PCM_F32_WIDE(pcm, fmt, o, n) pcm_f32_wide(pcm, fmt, o, n)
+#endif
+
 /* ------------------------------------------------------------------------------------------------ */
 /* LDS slice of one wave (~12.8 KB -> 12 waves per CU)                                                */
 /* ------------------------------------------------------------------------------------------------ */
@@ -2715,7 +2800,13 @@ template <class LdsT> STAGE void st_bitstream(const lc3d_plan* __restrict__ P, c
  * -DLC3_ENC_VBW: per-frame bandwidths (lc3plus_enc_batch_encode_bandwidths), kernel lc3_encode_kernel_vbw (_var_vbw together with -DLC3_ENC_VAR), standard
  * layout only, in objects of their own.  The bandwidth controller takes the frame's bandwidth in Hz from bwf[stream][dt0 + t] (the host has resolved every
  * frame to the value in force, 0 = off) instead of the stream's configuration words, with the formulas of set_bandwidth (lc3d_bw_cut_bin, lc3d_bw_index). */
+#ifdef LC3_PCM_WIRE
+#define LC3_FMT_CAT2(a) a##_wire
+#define LC3_RESAMPLE_FMT_FN lc3_enc_resample_wire_kernel
+#else
 #define LC3_FMT_CAT2(a) a##_fmt
+#define LC3_RESAMPLE_FMT_FN lc3_enc_resample_fmt_kernel
+#endif
 #define LC3_FMT_CAT(a) LC3_FMT_CAT2(a)
 /* -DLC3_PCM_FMT: the same kernel for the PCM formats beyond the reference's three (float samples, the interleaved and the channel-major layout), named with
  * _fmt, once more in an object of its own per object above - with the front and the resampler kernel of those formats in the two plain ones - so that the
@@ -2736,7 +2827,7 @@ template <class LdsT> STAGE void st_bitstream(const lc3d_plan* __restrict__ P, c
 #ifndef LC3_BIG
 #include "lc3_enc_front4.inc"      /* lc3_enc_front4_kernel_fmt */
 #include "lc3_enc_frontm.inc"      /* lc3_enc_frontm_kernel_fmt */
-#include "lc3_enc_pre.inc"         /* lc3_enc_resample_fmt_kernel, lc3_enc_resample48f_kernel */
+#include "lc3_enc_pre.inc"         /* lc3_enc_resample_fmt_kernel, lc3_enc_resample48f_kernel, lc3_enc_resample48w_kernel */
 #endif
 #endif
 #ifdef LC3_TU_MAIN

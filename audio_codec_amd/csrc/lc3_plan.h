@@ -227,24 +227,61 @@ enum { DS_PITCH_INT = 0, DS_PITCH_FR, DS_BETA_IDX, DS_PARAM0, DS_PARAM1, DS_PARA
        DS_PREV_BFI, DS_PREVPREV_BFI };
 
 /* ---- The PCM format word of the batch calls (include/lc3plus_batch.h: LC3PLUS_PCM_*) --------------------------------------------------------------
- * Bits 0 ... 7: the sample type - 16, 24, 32 (integers as the reference's bitdepth / bps) or LC3D_PCM_FLOAT32 (IEEE float, full scale 1.0);
- * bits 8, 9: the layout - none = [stream][frame][channel][sample], LC3D_PCM_INTERLEAVED = [stream][time][channel], LC3D_PCM_CHANNEL_MAJOR =
- * [stream][channel][time], time = frame * N + sample.  The same arithmetic on the host (lc3plus_pcm_format_check, lc3plus_pcm_offset) and in every kernel
- * that touches PCM: lc3d_pcm_frame gives the element index of sample 0 of (stream, frame, channel); sample i is lc3d_pcm_stride further per step, and the same
- * channel's next frame lc3d_pcm_fstep further. */
+ * Bits 0 ... 7: the sample type - 16, 24, 32 (integers as the reference's bitdepth / bps), LC3D_PCM_FLOAT32 (IEEE float, full scale 1.0) or one of the five
+ * wire types LC3D_PCM_S16_BE ... LC3D_PCM_ALAW (below); bits 8, 9: the layout - none = [stream][frame][channel][sample], LC3D_PCM_INTERLEAVED =
+ * [stream][time][channel], LC3D_PCM_CHANNEL_MAJOR = [stream][channel][time], time = frame * N + sample.  The same arithmetic on the host
+ * (lc3plus_pcm_format_check, lc3plus_pcm_offset) and in every kernel that touches PCM: lc3d_pcm_frame gives the element index of sample 0 of (stream, frame,
+ * channel); sample i is lc3d_pcm_stride further per step, and the same channel's next frame lc3d_pcm_fstep further.  An element is lc3d_pcm_elem_bytes bytes. */
 #define LC3D_PCM_FLOAT32       0x80
+#define LC3D_PCM_S16_BE        0x81      /* 2 bytes, big-endian: stands for 16 */
+#define LC3D_PCM_S24_3LE       0x82      /* 3 bytes, little-endian two's complement: stands for 24 */
+#define LC3D_PCM_S24_3BE       0x83      /* 3 bytes, big-endian: stands for 24 */
+#define LC3D_PCM_ULAW          0x84      /* 1 byte, G.711 mu-law: stands for 16 */
+#define LC3D_PCM_ALAW          0x85      /* 1 byte, G.711 A-law: stands for 16 */
 #define LC3D_PCM_TYPE_MASK     0xff
 #define LC3D_PCM_INTERLEAVED   0x100
 #define LC3D_PCM_CHANNEL_MAJOR 0x200
 #define LC3D_PCM_LAYOUT_MASK   0x300
+static inline LC3D_HD int lc3d_pcm_type_wire(int ty) { return ty >= LC3D_PCM_S16_BE && ty <= LC3D_PCM_ALAW; }
 static inline LC3D_HD int lc3d_pcm_format_ok(int fmt)
 {
     const int ty = fmt & LC3D_PCM_TYPE_MASK, lay = fmt & LC3D_PCM_LAYOUT_MASK;
     if (fmt & ~(LC3D_PCM_TYPE_MASK | LC3D_PCM_LAYOUT_MASK)) return 0;
-    if (ty != 16 && ty != 24 && ty != 32 && ty != LC3D_PCM_FLOAT32) return 0;
+    if (ty != 16 && ty != 24 && ty != 32 && ty != LC3D_PCM_FLOAT32 && !lc3d_pcm_type_wire(ty)) return 0;
     return lay != LC3D_PCM_LAYOUT_MASK;
 }
-static inline LC3D_HD int lc3d_pcm_elem_bytes(int fmt) { return (fmt & LC3D_PCM_TYPE_MASK) == 16 ? 2 : 4; }
+static inline LC3D_HD int lc3d_pcm_elem_bytes(int fmt)
+{
+    const int ty = fmt & LC3D_PCM_TYPE_MASK;
+    return ty == LC3D_PCM_ULAW || ty == LC3D_PCM_ALAW ? 1 : ty == 16 || ty == LC3D_PCM_S16_BE ? 2 : ty == LC3D_PCM_S24_3LE || ty == LC3D_PCM_S24_3BE ? 3 : 4;
+}
+/* The wire types' conversion rule, one text for the host functions (lc3plus_pcm_to_native / _from_native) and the kernels.  Into the encoder a wire sample
+ * becomes the integer its type stands for (then R/enc_lc3_fl.c:30-42 for that depth); out of the decoder the integer output of that depth (R/dec_lc3_fl.c:115-127)
+ * becomes the wire sample: bytes swapped, the 24-bit value saturated as R/tinywaveout_c.h:403-424 clips it, or compressed by G.711.
+ * G.711: code c -> sample (ITU-T G.711 tables 1a / 2a at 16 bits), and sample x -> code with the magnitude taken by one's complement (y = x < 0 ? ~x : x), so that
+ * -1 has magnitude 0 and both signs quantise alike. */
+static inline LC3D_HD int lc3d_g711_expand(int c, int alaw)
+{
+    const int k = alaw ? (c ^ 0x55) : (~c & 0xff), e = (k >> 4) & 7, q = k & 15;
+    if (alaw) { const int m = e == 0 ? (2 * q + 1) << 3 : ((2 * q + 33) << (e - 1)) << 3; return (k & 0x80) ? m : -m; }
+    const int m = ((2 * q + 33) << (e + 2)) - 132;
+    return (c & 0x80) ? m : -m;
+}
+static inline LC3D_HD int lc3d_g711_compress(int x /* int16 */, int alaw)
+{
+    const int s = x < 0, y = s ? ~x : x;
+    if (alaw) {
+        const int m = y >> 4;
+        int c7 = m;
+        if (m > 15) { const int e = 28 - __builtin_clz((unsigned)m); c7 = (e << 4) | ((m >> (e - 1)) & 15); }
+        return (c7 | (s ? 0 : 0x80)) ^ 0x55;
+    }
+    int a = (y >> 2) + 33;
+    if (a > 8191) a = 8191;
+    const int e = 26 - __builtin_clz((unsigned)a), q = (a >> (e + 1)) & 15;
+    return (s ? 0 : 0x80) | ((7 - e) << 4) | (15 - q);
+}
+static inline LC3D_HD int32_t lc3d_pcm_sat24(int32_t v) { return v > 8388607 ? 8388607 : v < -8388608 ? -8388608 : v; }
 static inline LC3D_HD int lc3d_pcm_stride(int fmt, int channels) { return (fmt & LC3D_PCM_INTERLEAVED) ? channels : 1; }
 static inline LC3D_HD size_t lc3d_pcm_fstep(int fmt, int channels, int N) { return (fmt & LC3D_PCM_CHANNEL_MAJOR) ? (size_t)N : (size_t)N * channels; }
 static inline LC3D_HD size_t lc3d_pcm_frame(int fmt, int channels, int T, int N, int strm, int t, int ch)

@@ -305,13 +305,15 @@ static void launch_resample(lc3hip_ctx* c, hipStream_t st, const void* dpcm, int
         hipLaunchKernelGGL(lc3_enc_resample48_kernel, dim3((unsigned)c->ncs * pruns), dim3(WAVE), 0, st, c->d_plan, (const int16_t*)dpcm, c->channels, mc, n_frames, hb, hn, c->ncs, dy12, xprev, xprev_stride);
     else if (c->rs48 && (bitdepth & (LC3D_PCM_TYPE_MASK | LC3D_PCM_INTERLEAVED)) == LC3D_PCM_FLOAT32 && (((size_t)dpcm) & 15) == 0)   /* frames of 480 x 4 bytes: every one 16-byte aligned */
         hipLaunchKernelGGL(lc3_enc_resample48f_kernel, dim3((unsigned)c->ncs * pruns), dim3(WAVE), 0, st, c->d_plan, (const float*)dpcm, bitdepth, c->channels, mc, n_frames, hb, hn, c->ncs, dy12, xprev, xprev_stride);
+    else if (c->rs48 && lc3d_pcm_type_wire(bitdepth & LC3D_PCM_TYPE_MASK) && !(bitdepth & LC3D_PCM_INTERLEAVED) && (((size_t)dpcm) & 3) == 0)   /* wire samples that follow each other, frames of 480 elements: every one starts on a dword */
+        hipLaunchKernelGGL(lc3_enc_resample48w_kernel, dim3((unsigned)c->ncs * pruns), dim3(WAVE), 0, st, c->d_plan, (const unsigned*)dpcm, bitdepth, c->channels, mc, n_frames, hb, hn, c->ncs, dy12, xprev, xprev_stride);
     else if (c->rs96 && bitdepth == 16 && (((size_t)dpcm) & 15) == 0) {
         auto k = c->N == 960 ? lc3_enc_resample96_kernel_n960 : c->N == 480 ? lc3_enc_resample96_kernel_n480 : lc3_enc_resample96_kernel_n240;
         const int fpb = (1920 / c->N) * PRE96_ITERS;                       /* frames per workgroup: PRE96_ITERS steps of 1 920 samples */
         hipLaunchKernelGGL(k, dim3((unsigned)c->ncs * (unsigned)((hn + fpb - 1) / fpb)), dim3(WAVE), 0, st, c->d_plan, (const int16_t*)dpcm, c->channels, mc, n_frames, hb, hn, c->ncs, dy12, xprev, xprev_stride);
     }
     else
-        hipLaunchKernelGGL((bitdepth == 16 || bitdepth == 24 || bitdepth == 32) ? lc3_enc_resample_kernel : lc3_enc_resample_fmt_kernel, dim3((unsigned)c->ncs * pruns), dim3(WAVE), 0, st, c->d_plan, c->d_state, c->state_words, mc, dpcm, bitdepth, n_frames, hb, hn, c->ncs, dy12, xprev, xprev_stride);
+        hipLaunchKernelGGL((bitdepth == 16 || bitdepth == 24 || bitdepth == 32) ? lc3_enc_resample_kernel : lc3d_pcm_type_wire(bitdepth & LC3D_PCM_TYPE_MASK) ? lc3_enc_resample_wire_kernel : lc3_enc_resample_fmt_kernel, dim3((unsigned)c->ncs * pruns), dim3(WAVE), 0, st, c->d_plan, c->d_state, c->state_words, mc, dpcm, bitdepth, n_frames, hb, hn, c->ncs, dy12, xprev, xprev_stride);
 }
 static int bw_to(lc3hip_ctx* c, hipStream_t st);
 /* what enc_launch passes for the optional argument groups of the one-wave kernels (lc3_kernel_decls.h: LC3_OW_OPT orders them) */
@@ -340,6 +342,7 @@ static int enc_launch(lc3hip_ctx* c, const void* dpcm, int bitdepth, int n_frame
     /* (per-frame bitrates: always - lc3_encode_kernel_var reloads the configuration per frame; it is the only kernel that does) */
     /* the PCM formats beyond the reference's three have kernels of their own (_fmt) wherever the load could not be added without moving the registers of the kernel that is there */
     const bool fmt_plain = bitdepth == 16 || bitdepth == 24 || bitdepth == 32;
+    const bool fmt_wire = lc3d_pcm_type_wire(bitdepth & LC3D_PCM_TYPE_MASK) != 0;           /* the wire sample types: the _wire twins, so that the _fmt kernels stay what they were */
     const bool in_kernel_writer = dtr || c->fused || dfsz || dT <= (c->input_ready ? LC3D_FUSED_MAX_T_READY : LC3D_FUSED_MAX_T);
     if (!in_kernel_writer) {
         dstride = PK_STRIDE(c->N, c->hr);
@@ -385,7 +388,7 @@ static int enc_launch(lc3hip_ctx* c, const void* dpcm, int bitdepth, int n_frame
         const int key = OW_KEY(c->big != 0, dfsz != nullptr, dbw != nullptr, pt != nullptr);
 #define OW_LAUNCH(name, big, var, vbw, pk) \
         if (key == OW_KEY(big, var, vbw, pk)) \
-            hipLaunchKernelGGL(fmt_plain ? name : name##_fmt, dim3(c->ncs), dim3(WAVE), 0, s, c->d_plan, c->d_chans, c->d_state, dpcm, bitdepth, n_frames, \
+            hipLaunchKernelGGL(fmt_plain ? name : fmt_wire ? name##_wire : name##_fmt, dim3(c->ncs), dim3(WAVE), 0, s, c->d_plan, c->d_chans, c->d_state, dpcm, bitdepth, n_frames, \
                                dout, pt ? 0 : out_stride, c->ncs, dtr, ddump, dstride, dy12, c->d_status, dT, dt0, (const float*)nullptr, (const float*)nullptr, \
                                (const float*)nullptr LC3_OW_OPT(LC3_OW_VALS_, var, vbw, pk)); \
         else
@@ -511,11 +514,11 @@ static int enc_launch(lc3hip_ctx* c, const void* dpcm, int bitdepth, int n_frame
             const unsigned fruns = (unsigned)((nt + fpw - 1) / fpw);
             const int f4 = c->opt.front4;
             if (f4 && !c->big && !scf_wave && c->N == 480 && c->la == 180 && (c->ylen & 15) == 0)
-                DUPL('f') hipLaunchKernelGGL(fmt_plain ? lc3_enc_front4_kernel : lc3_enc_front4_kernel_fmt, dim3((unsigned)c->ncs * (unsigned)((nt + 3) / 4)), dim3(WAVE), 0, c->s_fr, c->d_plan, c->d_chans, c->d_state, dpcm, bitdepth, n_frames, tb, nt, c->ncs, dspec, c->srow, dT, dt0, dfrec, xn_w, xprev, xprev_stride);
+                DUPL('f') hipLaunchKernelGGL(fmt_plain ? lc3_enc_front4_kernel : fmt_wire ? lc3_enc_front4_kernel_wire : lc3_enc_front4_kernel_fmt, dim3((unsigned)c->ncs * (unsigned)((nt + 3) / 4)), dim3(WAVE), 0, c->s_fr, c->d_plan, c->d_chans, c->d_state, dpcm, bitdepth, n_frames, tb, nt, c->ncs, dspec, c->srow, dT, dt0, dfrec, xn_w, xprev, xprev_stride);
             else if (f4 && c->fm_frames && !scf_wave)
-                hipLaunchKernelGGL(fmt_plain ? lc3_enc_frontm_kernel : lc3_enc_frontm_kernel_fmt, dim3((unsigned)c->ncs * (unsigned)((nt + c->fm_frames - 1) / c->fm_frames)), dim3(WAVE), 0, c->s_fr, c->d_plan, c->d_chans, c->d_state, dpcm, bitdepth, n_frames, tb, nt, c->fm_frames, c->ncs, dspec, c->srow, dT, dt0, dfrec, xn_w, xprev, xprev_stride);
-            else if (c->big) hipLaunchKernelGGL(fmt_plain ? lc3_enc_front_kernel_big : lc3_enc_front_kernel_big_fmt, dim3((unsigned)c->ncs * fruns), dim3(WAVE), 0, c->s_fr, c->d_plan, c->d_chans, c->d_state, dpcm, bitdepth, n_frames, tb, nt, fpw, c->ncs, dspec, c->srow, dT, dt0, dfrec, xn_w, xprev, xprev_stride, scf_wave);
-            else DUPL('f') hipLaunchKernelGGL(fmt_plain ? lc3_enc_front_kernel : lc3_enc_front_kernel_fmt, dim3((unsigned)c->ncs * fruns), dim3(WAVE), 0, c->s_fr, c->d_plan, c->d_chans, c->d_state, dpcm, bitdepth, n_frames, tb, nt, fpw, c->ncs, dspec, c->srow, dT, dt0, dfrec, xn_w, xprev, xprev_stride, scf_wave);
+                hipLaunchKernelGGL(fmt_plain ? lc3_enc_frontm_kernel : fmt_wire ? lc3_enc_frontm_kernel_wire : lc3_enc_frontm_kernel_fmt, dim3((unsigned)c->ncs * (unsigned)((nt + c->fm_frames - 1) / c->fm_frames)), dim3(WAVE), 0, c->s_fr, c->d_plan, c->d_chans, c->d_state, dpcm, bitdepth, n_frames, tb, nt, c->fm_frames, c->ncs, dspec, c->srow, dT, dt0, dfrec, xn_w, xprev, xprev_stride);
+            else if (c->big) hipLaunchKernelGGL(fmt_plain ? lc3_enc_front_kernel_big : fmt_wire ? lc3_enc_front_kernel_big_wire : lc3_enc_front_kernel_big_fmt, dim3((unsigned)c->ncs * fruns), dim3(WAVE), 0, c->s_fr, c->d_plan, c->d_chans, c->d_state, dpcm, bitdepth, n_frames, tb, nt, fpw, c->ncs, dspec, c->srow, dT, dt0, dfrec, xn_w, xprev, xprev_stride, scf_wave);
+            else DUPL('f') hipLaunchKernelGGL(fmt_plain ? lc3_enc_front_kernel : fmt_wire ? lc3_enc_front_kernel_wire : lc3_enc_front_kernel_fmt, dim3((unsigned)c->ncs * fruns), dim3(WAVE), 0, c->s_fr, c->d_plan, c->d_chans, c->d_state, dpcm, bitdepth, n_frames, tb, nt, fpw, c->ncs, dspec, c->srow, dT, dt0, dfrec, xn_w, xprev, xprev_stride, scf_wave);
             HIPCHK(hipEventRecord(c->ev_m[k], c->s_fr));                 /* the MDCT memory hand-over and the spectrum rows of the run are written */
             if (five) HIPCHK(hipStreamWaitEvent(c->s_ln, c->ev_m[k], 0));
             const int fuse_vq = !scf_wave && !c->any_attack && c->opt.fuse_vq;

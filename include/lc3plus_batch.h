@@ -42,6 +42,22 @@ LC3_Error lc3plus_enc_batch_set_bandwidth(lc3plus_batch* batch, int stream, int 
  *                         integer format.  A NaN or an infinity is taken as 0.0f, so that one bad sample cannot stay in a stream's filter
  *                         memories for ever.  Decoder: the synthesised sample times 2^-15, neither rounded nor clipped (the integer formats round that
  *                         same value, R/dec_lc3_fl.c:115-127), so it may exceed [-1, 1).
+ *   Five wire types, each an element of 1, 2 or 3 bytes that stands for one of the integer depths.  Encoder: the element becomes that integer and is then
+ *   converted as that depth is, so a call in a wire type gives, byte for byte, what the same call gives for the converted int16_t / int32_t array.
+ *   Decoder: the result of that depth for the same frame, then the step named here.  No alignment is required: any byte address is a valid pointer.
+ *   LC3PLUS_PCM_S16_BE  : 2 bytes, big-endian (RTP L16), for 16: the bytes swapped.
+ *   LC3PLUS_PCM_S24_3LE : 3 bytes, little-endian two's complement (the body of a 24-bit WAV file), for 24: sign-extended on the way in; on the way out
+ *                         the 24-bit result saturated to [-8388608, 8388607] as R/tinywaveout_c.h:403-424 clips it (the int32_t format does not clip: a
+ *                         sample it gives as INT32_MIN comes out as -8388608), then its low three bytes.
+ *   LC3PLUS_PCM_S24_3BE : the same, big-endian (RTP L24, AES67).
+ *   LC3PLUS_PCM_ULAW    : 1 byte, G.711 mu-law (PCMU), for 16.  Code c -> sample: k = ~c & 0xff, e = (k >> 4) & 7, q = k & 15, magnitude
+ *                         ((2q + 33) << (e + 2)) - 132, negative when bit 7 of c is clear.  Sample x -> code: s = x < 0, y = s ? ~x : x (one's complement:
+ *                         -1 has magnitude 0), a = min((y >> 2) + 33, 8191), e = floor(log2 a) - 5, q = (a >> (e + 1)) & 15,
+ *                         code (s ? 0 : 0x80) | (7 - e) << 4 | (15 - q).
+ *   LC3PLUS_PCM_ALAW    : 1 byte, G.711 A-law (PCMA), for 16.  Code c -> sample: k = c ^ 0x55, e, q as above, magnitude (2q + 1) << 3 for e == 0, else
+ *                         ((2q + 33) << (e - 1)) << 3, negative when bit 7 of k is clear.  Sample x -> code: s, y as above, m = y >> 4, c7 = m for m <= 15,
+ *                         else e = floor(log2 m) - 3, c7 = e << 4 | ((m >> (e - 1)) & 15); code (c7 | (s ? 0 : 0x80)) ^ 0x55.
+ *                         Both expansions are the ITU-T G.711 tables at 16 bits; every A-law code and every mu-law code but 0x7f (negative zero) round-trips.
  * Layout of one call's n_streams x n_frames x channels x samples elements (N = samples per frame, time = frame * N + sample):
  *   none                      : [stream][frame][channel][sample]
  *   LC3PLUS_PCM_INTERLEAVED   : [stream][time][channel]         - capture, WAV and RTP order
@@ -51,12 +67,23 @@ LC3_Error lc3plus_enc_batch_set_bandwidth(lc3plus_batch* batch, int stream, int 
  * stored 16 bytes per lane like the 16-bit ones; interleaved samples one by one).  With host pointers, the channel-major layout is copied in one piece
  * instead of in overlapped runs of frames.  The traced calls (*_traced) take 16, 24 and 32 alone.
  * lc3plus_pcm_format_check and lc3plus_pcm_offset are host-only: the check every call makes, and the element index of one sample (-1 for arguments
- * out of range) - the arithmetic the kernels use. */
+ * out of range) - the arithmetic the kernels use.  The byte address of an element is its index times lc3plus_pcm_elem_bytes(format): 1, 2, 3 or 4, -1 for a
+ * word the check refuses.  lc3plus_pcm_to_native converts n elements of a wire type to the int16_t / int32_t it stands for, lc3plus_pcm_from_native applies the
+ * decoder's output step (saturation included) to n int16_t / int32_t: the rule above on the host, no device needed.  A layout bit in `format` is ignored; a type
+ * that is not one of the five is LC3_ERROR, a null pointer LC3_NULL_ERROR. */
 #define LC3PLUS_PCM_FLOAT32       0x80
+#define LC3PLUS_PCM_S16_BE        0x81
+#define LC3PLUS_PCM_S24_3LE       0x82
+#define LC3PLUS_PCM_S24_3BE       0x83
+#define LC3PLUS_PCM_ULAW          0x84
+#define LC3PLUS_PCM_ALAW          0x85
 #define LC3PLUS_PCM_INTERLEAVED   0x100
 #define LC3PLUS_PCM_CHANNEL_MAJOR 0x200
 LC3_Error lc3plus_pcm_format_check(int format);
 int64_t lc3plus_pcm_offset(int format, int channels, int n_frames, int samples, int stream, int frame, int channel, int sample);
+int lc3plus_pcm_elem_bytes(int format);
+LC3_Error lc3plus_pcm_to_native(int format, const void* src, int64_t n, void* dst);
+LC3_Error lc3plus_pcm_from_native(int format, const void* src, int64_t n, void* dst);
 
 /* Advances every stream by n_frames.
  *   pcm : [n_streams][n_frames][channels][input_samples] samples, int16_t (bitdepth 16) or int32_t (24/32); or float and / or another layout, as the

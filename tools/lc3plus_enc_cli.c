@@ -135,6 +135,7 @@ int main(int ac, char** av)
     int* rates = (int*)malloc(sizeof(int) * CH); int* bws = (int*)malloc(sizeof(int) * CH); int* sizes = (int*)malloc(sizeof(int) * CH);
     if (!pcm || !out || !rates || !bws || !sizes) die("out of memory");
     const int bps = w.bits / 8;
+    const int fmt = (w.bits == 24 ? LC3PLUS_PCM_S24_3LE : w.bits) | LC3PLUS_PCM_INTERLEAVED;
     uint32_t f0 = 0;
     while (f0 < total_frames) {
         /* a block of up to CH frames with the settings of every frame (the reference applies them before reading the frame, R/codec_exe.c:296-326:
@@ -145,6 +146,10 @@ int main(int ac, char** av)
             if (fbwf) bws[t] = (int)loopy_read64(fbwf);
         }
         memset(pcm, 0, (size_t)T * C * N * (wide ? 4 : 2));
+        if (w.bits == 24) {                               /* the body of a 24-bit WAV file is LC3PLUS_PCM_S24_3LE in the interleaved layout as it stands: the library unpacks it */
+            const uint64_t s0 = (uint64_t)f0 * N, left = w.frames - s0, want = (uint64_t)T * N;
+            memcpy(pcm, w.data + s0 * C * 3, (size_t)((left < want ? left : want) * C * 3));
+        } else
         for (int t = 0; t < T; t++) for (int n = 0; n < N; n++) {                 /* the file's samples in the file's order, [time][channel]: the library takes that layout */
             const uint64_t s = (uint64_t)(f0 + t) * N + n;
             if (s >= w.frames) break;
@@ -152,18 +157,17 @@ int main(int ac, char** av)
                 const uint8_t* p = w.data + (s * C + c) * bps;
                 const size_t o = ((size_t)t * N + n) * C + c;
                 if (w.bits == 16) ((int16_t*)pcm)[o] = (int16_t)rd16(p);
-                else if (w.bits == 24) ((int32_t*)pcm)[o] = ((int32_t)((uint32_t)p[0] << 8 | (uint32_t)p[1] << 16 | (uint32_t)p[2] << 24)) >> 8;
                 else ((int32_t*)pcm)[o] = ((int32_t)rd32(p)) >> 8;   /* the reference reader narrows 32-bit WAV to 24 bit (R/tinywavein_c.h:528-533) and still calls lc3_enc32 */
             }
         }
         if (fbwf) {
-            err = lc3plus_enc_batch_encode_bandwidths(b, pcm, 0, w.bits | LC3PLUS_PCM_INTERLEAVED, bws, fswf ? rates : NULL, T, out, S, 0, sizes, NULL, 1);
+            err = lc3plus_enc_batch_encode_bandwidths(b, pcm, 0, fmt, bws, fswf ? rates : NULL, T, out, S, 0, sizes, NULL, 1);
             if (err && err < LC3_WARNING) { fprintf(stderr, "lc3plus_enc_cli: encode failed (LC3_Error %d)\n", (int)err); return 1; }
         } else if (fswf) {
-            err = lc3plus_enc_batch_encode_bitrates(b, pcm, 0, w.bits | LC3PLUS_PCM_INTERLEAVED, rates, T, out, S, 0, sizes, NULL, 1);
+            err = lc3plus_enc_batch_encode_bitrates(b, pcm, 0, fmt, rates, T, out, S, 0, sizes, NULL, 1);
             if (err) { fprintf(stderr, "lc3plus_enc_cli: encode failed (LC3_Error %d)\n", (int)err); return 1; }
         } else {
-            err = lc3plus_enc_batch_encode(b, pcm, 0, w.bits | LC3PLUS_PCM_INTERLEAVED, T, out, S, 0, NULL, 1);
+            err = lc3plus_enc_batch_encode(b, pcm, 0, fmt, T, out, S, 0, NULL, 1);
             if (err) { fprintf(stderr, "lc3plus_enc_cli: encode failed (LC3_Error %d)\n", (int)err); return 1; }
             for (int t = 0; t < T; t++) sizes[t] = nbytes;
         }
