@@ -35,6 +35,7 @@ EXPORTS = [
     "lc3plus_enc_batch_encode_rates_device", "lc3plus_enc_plan_rates_lenient",
     "lc3plus_enc_batch_encode_packed", "lc3plus_plan_packed", "lc3plus_dec_batch_decode_packed", "lc3plus_dec_plan_packed_lenient",
     "lc3plus_pcm_format_check", "lc3plus_pcm_offset", "lc3plus_pcm_elem_bytes", "lc3plus_pcm_to_native", "lc3plus_pcm_from_native",
+    "lc3plus_enc_batch_set_pcm_placement", "lc3plus_dec_batch_set_pcm_placement", "lc3plus_pcm_placed_offset", "lc3plus_plan_placed",
     "lc3plus_shard_block",
     "lc3plus_enc_sharded_create", "lc3plus_enc_sharded_destroy", "lc3plus_enc_sharded_shards", "lc3plus_enc_sharded_shard", "lc3plus_enc_sharded_device",
     "lc3plus_enc_sharded_owner", "lc3plus_enc_sharded_input_samples", "lc3plus_enc_sharded_num_bytes", "lc3plus_enc_sharded_stride",
@@ -56,6 +57,8 @@ PCM_LAYOUTS = {None: 0, "default": 0, "interleaved": PCM_INTERLEAVED, "channel_m
 ENC_FL_RATE, ENC_FL_BW_REFUSED, ENC_FL_BW_RANGE = 1, 2, 4
 # ... and of Batch.encode_device_packed: the frame did not fit the output capacity (encoded, not written); the frame orders of packed output
 ENC_FL_PACK_CAP = 8
+# placed PCM (set_pcm_placement): the frame's PCM offset is invalid - the encoder took silence (device flags), the decoder wrote nothing (device status)
+ENC_FL_PCM_PLACE, DEC_ST_PCM_PLACE = 16, 4
 PACK_STREAM_MAJOR, PACK_FRAME_MAJOR = 0, 1
 LC3_BW_WARNING = 18
 
@@ -188,6 +191,11 @@ def load_library():
         L.lc3plus_pcm_elem_bytes.argtypes = [C.c_int]
         for f in (L.lc3plus_pcm_to_native, L.lc3plus_pcm_from_native):
             f.argtypes = [C.c_int, C.c_void_p, C.c_int64, C.c_void_p]
+        for f in (L.lc3plus_enc_batch_set_pcm_placement, L.lc3plus_dec_batch_set_pcm_placement):
+            f.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
+        L.lc3plus_pcm_placed_offset.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int]
+        L.lc3plus_pcm_placed_offset.restype = C.c_int64
+        L.lc3plus_plan_placed.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]
         _LIB = L
     return _LIB
 
@@ -251,6 +259,38 @@ def pcm_from_native(fmt, native):
 
 def pcm_offset(fmt, channels, n_frames, samples, stream, frame, channel, sample):
     return int(load_library().lc3plus_pcm_offset(fmt, channels, n_frames, samples, stream, frame, channel, sample))
+
+
+def pcm_placed_offset(fmt, channels, samples, frame_offset, channel, sample):
+    """lc3plus_pcm_placed_offset: the element index of one sample of a frame placed at frame_offset, -1 for what the rule refuses."""
+    return int(load_library().lc3plus_pcm_placed_offset(fmt, channels, samples, int(frame_offset), channel, sample))
+
+
+def plan_placed(fmt, channels, samples, offsets, capacity):
+    """lc3plus_plan_placed: uint8 array of the shape of offsets, 1 where a frame of channels * samples elements at that offset does not lie inside
+    [0, capacity) - the rule the placed kernels apply to every frame."""
+    off = np.ascontiguousarray(offsets, dtype=np.int64)
+    inv = np.zeros(off.shape, dtype=np.uint8)
+    rc = load_library().lc3plus_plan_placed(fmt, channels, samples, off.ctypes.data if off.size else None, off.size, int(capacity),
+                                            inv.ctypes.data if off.size else None)
+    if rc:
+        raise LC3Error(rc, "lc3plus_plan_placed")
+    return inv
+
+
+def ring_offsets(starts, n_frames, ring_frames, frame_elems, ring_stride):
+    """Offsets for set_pcm_placement of per-stream rings in one arena: stream s owns ring_frames slots of frame_elems elements from element
+    s * ring_stride on, and the call's frame t lies in slot (starts[s] + t) % ring_frames.  int64 [n_streams, n_frames]."""
+    starts = np.asarray(starts, dtype=np.int64)
+    s = np.arange(starts.size, dtype=np.int64)[:, None]
+    t = np.arange(n_frames, dtype=np.int64)[None, :]
+    return starts[:, None] * 0 + s * int(ring_stride) + ((starts[:, None] + t) % int(ring_frames)) * int(frame_elems)
+
+
+def _set_pcm_placement(obj, name, d_offsets_ptr, capacity):
+    rc = getattr(obj.lib, name)(obj.h, C.c_void_p(d_offsets_ptr) if d_offsets_ptr else None, int(capacity) if d_offsets_ptr else 0)
+    if rc:
+        raise LC3Error(rc, name)
 
 
 def _stream_list(streams):
@@ -469,6 +509,11 @@ class Batch(_StreamLifecycle):
         rc = self.lib.lc3plus_enc_batch_set_input_ready(self.h, 1 if ready else 0)
         if rc:
             raise LC3Error(rc, "lc3plus_enc_batch_set_input_ready")
+
+    def set_pcm_placement(self, d_offsets_ptr, capacity=0):
+        """lc3plus_enc_batch_set_pcm_placement: frame (s, t) of every following device-pointer call is read at element d_offsets[s, t] (int64
+        [n_streams, T] in device memory) of the call's pcm pointer, a buffer of `capacity` elements; None switches placement off."""
+        _set_pcm_placement(self, "lc3plus_enc_batch_set_pcm_placement", d_offsets_ptr, capacity)
 
     _ss = "lc3plus_enc_batch"
 
@@ -875,6 +920,11 @@ class DecBatch(_StreamLifecycle):
         rc = self.lib.lc3plus_dec_batch_set_input_ready(self.h, 1 if ready else 0)
         if rc:
             raise LC3Error(rc, "lc3plus_dec_batch_set_input_ready")
+
+    def set_pcm_placement(self, d_offsets_ptr, capacity=0):
+        """lc3plus_dec_batch_set_pcm_placement: frame (s, t) of every following device-pointer call is written at element d_offsets[s, t] (int64
+        [n_streams, T] in device memory) of the call's pcm pointer, a buffer of `capacity` elements; None switches placement off."""
+        _set_pcm_placement(self, "lc3plus_dec_batch_set_pcm_placement", d_offsets_ptr, capacity)
 
     def decode_device(self, d_frames_ptr, in_stride, T, d_pcm_ptr, bps=16, hip_stream=None, sync=False, num_bytes=None, bfi=None):
         """Device-resident variant: raw device pointers.  Without num_bytes no bad-frame flags; with num_bytes ([n_streams, T] host ints, 0 = lost)

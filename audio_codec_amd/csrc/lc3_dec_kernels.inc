@@ -14,11 +14,18 @@
 #ifdef LC3_BIG
 #define DEC_IMDCT_KERNEL lc3_dec_imdct_kernel_big
 #define DEC_IMDCT_WAVES 3
-#define DEC_SYNTH_KERNEL lc3_dec_synth_kernel_big
+#define DEC_SYNTH_NAME lc3_dec_synth_kernel_big
 #else
 #define DEC_IMDCT_KERNEL lc3_dec_imdct_kernel
 #define DEC_IMDCT_WAVES 4
-#define DEC_SYNTH_KERNEL lc3_dec_synth_kernel
+#define DEC_SYNTH_NAME lc3_dec_synth_kernel
+#endif
+/* -DLC3_PCM_PLACED (the two plain _plc objects): the synthesis kernel alone, named with _plc, writing each frame at its offset (lc3_plan.h: lc3d_pcm_placed_*) or,
+ * where that is invalid, not at all; nothing else of the frame's decoding differs. */
+#ifdef LC3_PCM_PLACED
+#define DEC_SYNTH_KERNEL LC3_FMT_CAT(DEC_SYNTH_NAME)
+#else
+#define DEC_SYNTH_KERNEL DEC_SYNTH_NAME
 #endif
 #define NR ((MAXN + 63) / 64)                        /* spectrum / time samples per lane */
 #define NH ((MAXN / 2 + 63) / 64)                    /* complex DFT points per lane */
@@ -219,7 +226,7 @@ __device__ __noinline__ const float* dec_ltpf(const lc3d_plan* __restrict__ P, S
 }
 
 /* ------------------------------------------------------------------------------------------------ */
-#ifndef LC3_BIG
+#if !defined(LC3_BIG) && !defined(LC3_PCM_PLACED)
 /* Concealment bookkeeping: one channel-stream per lane, frames in order.  nbLostCmpt, the cumulative attenuation and the sign
  * generator's seed (R/plc_main.c, R/plc_noise_substitution0.c:13-40, R/plc_update.c:13-30) depend only on which frames are bad; a
  * lost frame gets (count, attenuation, first seed, index of the last good frame of this launch or -1) into its record.
@@ -326,6 +333,7 @@ lc3_dec_sizes_tail_kernel(const uint16_t* __restrict__ sizes, const uint8_t* __r
 }
 #endif
 
+#ifndef LC3_PCM_PLACED
 /* ------------------------------------------------------------------------------------------------ */
 /* A run of IMDCT_FPW consecutive frames of one channel-stream per wave, every frame on its own: shaped (or concealed) spectrum ->
  * DCT-IV -> window.  The overlap-add needs the previous frame and is left to the synthesis kernel: this kernel is stateless, all
@@ -468,6 +476,7 @@ DEC_IMDCT_KERNEL(const lc3d_plan* __restrict__ P, const float* __restrict__ stat
     }
 #undef PREFETCH
 }
+#endif /* !LC3_PCM_PLACED */
 
 /* ------------------------------------------------------------------------------------------------ */
 /* One channel-stream per wave, frames in order: overlap-add, LTPF synthesis, output.  The overlap memory lives in registers. */
@@ -477,7 +486,7 @@ DEC_IMDCT_KERNEL(const lc3d_plan* __restrict__ P, const float* __restrict__ stat
 extern "C" __global__ void __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(DEC_SYNTH_EU, DEC_SYNTH_EU)))
 DEC_SYNTH_KERNEL(const lc3d_plan* __restrict__ P, float* __restrict__ state,
                  const int* __restrict__ rec, const float* __restrict__ ws, const float* __restrict__ ov /* [cs][T][OV_ROW(N)] */, int T,
-                 void* __restrict__ pcm, int bps, int ncs, uint8_t* __restrict__ status /* [stream][T] or null */, lc3d_dec_trace* __restrict__ trace)
+                 void* __restrict__ pcm, int bps, int ncs, uint8_t* __restrict__ status /* [stream][T] or null */, lc3d_dec_trace* __restrict__ trace LC3_PLACED_OPT)
 {
     __shared__ SynLds L;
     const int lane = threadIdx.x, cs = blockIdx.x;
@@ -556,8 +565,17 @@ DEC_SYNTH_KERNEL(const lc3d_plan* __restrict__ P, float* __restrict__ state,
         /* ---- output R/dec_lc3_fl.c:115-127 ---- */
         {
             /* bps is the PCM format word (lc3_plan.h: lc3d_pcm_*): the sample type, and the layout that gives the frame's first element and the step between samples */
+#ifdef LC3_PCM_PLACED
+            const long long poff = plo[(size_t)strm * T + t];
+            const bool pok = lc3d_pcm_placed_ok(poff, channels, N, plcap) != 0;                /* an invalid frame is decoded like any other and written nowhere */
+            const size_t o = pok ? lc3d_pcm_placed_frame(bps, channels, N, poff, ch) : 0;
+            const int ps = lc3d_pcm_stride(bps, channels), ty = bps & LC3D_PCM_TYPE_MASK;
+            if (!pok) { }
+            else
+#else
             const size_t o = lc3d_pcm_frame(bps, channels, T, N, strm, t, ch);
             const int ps = lc3d_pcm_stride(bps, channels), ty = bps & LC3D_PCM_TYPE_MASK;
+#endif
             if (ty == 16) {
                 int16_t* op = (int16_t*)pcm + o;
                 for (int i = lane; i < N; i += WAVE) {

@@ -36,7 +36,7 @@ FRONT_KERNEL_NAME(const lc3d_plan* __restrict__ P, const lc3d_chan* __restrict__
                      int T, int tb, int nt /* frames tb ... tb + nt - 1 of the call's T */, int fpw /* consecutive frames per wave */, int ncs, float* __restrict__ spec /* [cs][RT][srow]: the first ylen lines (the coded ones); frame t of this launch is row r0 + t */, int srow, int RT, int r0, float* __restrict__ rec /* [cs][RT][FR_WORDS] */,
                      float* __restrict__ xnext /* [cs][MEMCAP]: the MDCT memory after the last frame (the sequential kernel moves it into the state) */,
                      const float* __restrict__ xprev /* the MDCT memory before frame 0: the state's slot, or the previous call's xnext */, int xprev_stride,
-                     int do_scf /* band energies, bandwidth detector and scale factors here (0: lc3_enc_scf_lane_kernel does them, one frame per lane) */)
+                     int do_scf /* band energies, bandwidth detector and scale factors here (0: lc3_enc_scf_lane_kernel does them, one frame per lane) */ LC3_PLACED_OPT)
 {
     __shared__ FrontLds L;
     const int lane = threadIdx.x;
@@ -53,7 +53,9 @@ FRONT_KERNEL_NAME(const lc3d_plan* __restrict__ P, const lc3d_chan* __restrict__
     const float sc = bitdepth == 24 ? 256.0f : 65536.0f;
     /* MDCT memory = the last N - la_zeros samples of the frame before the run (R/mdct.c:111), right-aligned in its slot */
     if (t0 == 0) { for (int i = lane; i < MEMCAP; i += WAVE) L.xbuf[i] = xprev[(size_t)cs * xprev_stride + i]; }
-#if FRONT_PCM_FMT
+#ifdef LC3_PCM_PLACED
+    else pcm_placed_load<false>(pcm, bitdepth, plo, plcap, channels, N, (size_t)strm * T + t0 - 1, ch, N - ml, ml, &L.xbuf[MEMCAP - ml], lane, 1.0f);
+#elif FRONT_PCM_FMT
     else {
         const int ps = lc3d_pcm_stride(bitdepth, channels);
         const size_t pidx = lc3d_pcm_frame(bitdepth, channels, T, N, strm, t0 - 1, ch) + (size_t)(N - ml) * ps;
@@ -82,7 +84,9 @@ FRONT_KERNEL_NAME(const lc3d_plan* __restrict__ P, const lc3d_chan* __restrict__
         }
     }
     for (int t = t0; t < t1; t++) {
-#if FRONT_PCM_FMT
+#ifdef LC3_PCM_PLACED
+        pcm_placed_load<true>(pcm, bitdepth, plo, plcap, channels, N, (size_t)strm * T + t, ch, 0, N, XCUR(L), lane, 1.0f);
+#elif FRONT_PCM_FMT
         {                                                                              /* by the format word: the frame's first element and the step between its samples */
             const size_t o = lc3d_pcm_frame(bitdepth, channels, T, N, strm, t, ch);
             if (PCM_F32_WIDE(pcm, bitdepth, o, N)) {                                   /* float samples one after the other: 16 bytes per lane */

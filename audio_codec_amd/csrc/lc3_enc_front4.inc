@@ -84,7 +84,7 @@ lc3_enc_front4_kernel(
 #endif
                       const lc3d_plan* __restrict__ P, const lc3d_chan* __restrict__ chans, const float* __restrict__ state, const void* __restrict__ pcm, int bitdepth,
                       int T, int tb, int nt /* frames tb ... tb + nt - 1 of the call's T */, int ncs, float* __restrict__ spec, int srow, int RT, int r0, float* __restrict__ rec,
-                      float* __restrict__ xnext, const float* __restrict__ xprev, int xprev_stride)
+                      float* __restrict__ xnext, const float* __restrict__ xprev, int xprev_stride LC3_PLACED_OPT)
 {
     __shared__ Front4Lds L;
     const int lane = threadIdx.x;
@@ -100,7 +100,12 @@ lc3_enc_front4_kernel(
 #ifndef LC3_PCM_FMT
     const float sc = bitdepth == 24 ? 256.0f : 65536.0f;
 #endif
-#ifdef LC3_PCM_FMT
+#ifdef LC3_PCM_PLACED
+    /* ---- PCM of the run and the MDCT memory in front of it -> x: every frame at its own offset ---- */
+    if (t0 == 0) { for (int i = lane; i < MEMCAP; i += WAVE) L.x[i] = xprev[(size_t)cs * xprev_stride + i]; }
+    else pcm_placed_load<true>(pcm, bitdepth, plo, plcap, channels, N, (size_t)strm * T + t0 - 1, ch, N - MEMCAP, MEMCAP, L.x, lane, 1.0f);
+    for (int f = 0; f < nf; f++) pcm_placed_load<true>(pcm, bitdepth, plo, plcap, channels, N, (size_t)strm * T + t0 + f, ch, 0, N, &L.x[MEMCAP + N * f], lane, 1.0f);
+#elif defined(LC3_PCM_FMT)
     /* ---- PCM of the run and the MDCT memory in front of it -> x ---- */
     {   /* by the format word: the run's first element, the step to the next sample and to the channel's next frame.  Float samples that follow each other (480 x 4
          * bytes per frame from a 16-byte aligned base) take 16 bytes per lane like the 16-bit ones of the kernel without the suffix. */

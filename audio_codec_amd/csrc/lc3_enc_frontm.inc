@@ -64,7 +64,7 @@ lc3_enc_frontm_kernel(
 #endif
                       const lc3d_plan* __restrict__ P, const lc3d_chan* __restrict__ chans, const float* __restrict__ state, const void* __restrict__ pcm, int bitdepth,
                       int T, int tb, int nt /* frames tb ... tb + nt - 1 of the call's T */, int F /* frames per wave: F x N <= FM_CAP, F <= 8 */, int ncs,
-                      float* __restrict__ spec, int srow, int RT, int r0, float* __restrict__ rec, float* __restrict__ xnext, const float* __restrict__ xprev, int xprev_stride)
+                      float* __restrict__ spec, int srow, int RT, int r0, float* __restrict__ rec, float* __restrict__ xnext, const float* __restrict__ xprev, int xprev_stride LC3_PLACED_OPT)
 {
     __shared__ FrontMLds L;
     const int lane = threadIdx.x;
@@ -80,7 +80,12 @@ lc3_enc_frontm_kernel(
     const float sc = bitdepth == 24 ? 256.0f : 65536.0f;
     const size_t f0 = ((size_t)strm * T + t0) * channels + ch;
 #endif
-#ifdef LC3_PCM_FMT
+#ifdef LC3_PCM_PLACED
+    /* ---- the MDCT memory in front of the run (right-aligned below x[MEMCAP]) and the run's PCM -> x: every frame at its own offset ---- */
+    if (t0 == 0) { for (int i = lane; i < MEMCAP; i += WAVE) L.x[i] = xprev[(size_t)cs * xprev_stride + i]; }
+    else pcm_placed_load<false>(pcm, bitdepth, plo, plcap, channels, N, (size_t)strm * T + t0 - 1, ch, N - ml, ml, &L.x[MEMCAP - ml], lane, 1.0f);
+    for (int f = 0; f < nf; f++) pcm_placed_load<true>(pcm, bitdepth, plo, plcap, channels, N, (size_t)strm * T + t0 + f, ch, 0, N, &L.x[MEMCAP + N * f], lane, 1.0f);
+#elif defined(LC3_PCM_FMT)
     /* ---- the MDCT memory in front of the run (right-aligned below x[MEMCAP]) and the run's PCM -> x: by the format word - the run's first element, the step to the
      * next sample and to the channel's next frame; float samples that follow each other take 16 bytes per lane like the 16-bit ones of the kernel without the suffix ---- */
     const int ps = lc3d_pcm_stride(bitdepth, channels);

@@ -59,7 +59,8 @@ __device__ __forceinline__ void pre48_put(float* __restrict__ d, const uint4 v, 
     ((float4*)d)[0] = a; ((float4*)d)[1] = b;
 }
 
-#ifdef LC3_PCM_FMT
+#ifdef LC3_PCM_PLACED               /* the placed object holds lc3_enc_resample_plc_kernel alone: a placed call always takes the resampler for every shape */
+#elif defined(LC3_PCM_FMT)
 /* lc3_enc_resample48_kernel (below) for samples that follow each other in the default or the channel-major layout of the format word fmt: its tap and LDS scheme
  * unchanged, only the load and convert step differs.  A frame is 120 pieces of four samples instead of 60 of eight: a lane loads piece lane and piece lane + 60 of
  * both frames of its pair, keeps them as loaded, and writes each to LDS as one float4 - consecutive lanes, consecutive quad-words.  One text, two kernels:

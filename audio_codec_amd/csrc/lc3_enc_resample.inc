@@ -11,7 +11,7 @@
 extern "C" __global__ void __launch_bounds__(WAVE)
 RESAMPLE_FN(const lc3d_plan* __restrict__ P, const float* __restrict__ state, int state_words, int memcap, const void* __restrict__ pcm, int bitdepth,
                         int T, int tb, int nt, int ncs, float* __restrict__ d12 /* [cs][T][128] */,
-                        const float* __restrict__ xprev /* the MDCT / resampler memory before frame 0 (slot of memcap words per channel-stream) */, int xprev_stride)
+                        const float* __restrict__ xprev /* the MDCT / resampler memory before frame 0 (slot of memcap words per channel-stream) */, int xprev_stride LC3_PLACED_OPT)
 {
     __shared__ PreLds L;
     const int lane = threadIdx.x;
@@ -42,7 +42,11 @@ RESAMPLE_FN(const lc3d_plan* __restrict__ P, const float* __restrict__ state, in
         const size_t fidx = ((size_t)strm * T + t) * channels + ch;
 #endif
         /* the previous frame's last mlen samples: from the PCM of this launch, or from the stream's MDCT memory for its first frame */
-#if RESAMPLE_PCM_FMT
+#ifdef LC3_PCM_PLACED
+        if (t > 0) pcm_placed_load<false>(pcm, bitdepth, plo, plcap, channels, N, (size_t)strm * T + t - 1, ch, N - mlen, mlen, xs, lane, sf);
+        else for (int j = lane; j < mlen; j += WAVE) xs[j] = xprev[(size_t)cs * xprev_stride + (memcap - mlen + j)] * sf;
+        pcm_placed_load<false>(pcm, bitdepth, plo, plcap, channels, N, (size_t)strm * T + t, ch, 0, N, xs + mlen, lane, sf);
+#elif RESAMPLE_PCM_FMT
         {                                                          /* by the format word (lc3_plan.h): a frame's first element and the step between its samples */
             const int ps = lc3d_pcm_stride(bitdepth, channels);
             const size_t pf = lc3d_pcm_frame(bitdepth, channels, T, N, strm, t, ch), pp = t > 0 ? lc3d_pcm_frame(bitdepth, channels, T, N, strm, t - 1, ch) : 0;

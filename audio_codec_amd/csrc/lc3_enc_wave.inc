@@ -2,14 +2,15 @@
  *
  * ENC_PCM_FMT 0: the kernel KERNEL_FN for the reference's three PCM formats (16, 24, 32 in the default layout), token for token what it was before the PCM format
  * word existed: it sits at its register limit, and any branch more moves its spills.  ENC_PCM_FMT 1 (the -DLC3_PCM_FMT objects): the same kernel named with _fmt
- * for the formats beyond those (float samples, the interleaved and the channel-major layout, lc3_plan.h: lc3d_pcm_*).  The two differ in the PCM load alone. */
+ * for the formats beyond those (float samples, the interleaved and the channel-major layout, lc3_plan.h: lc3d_pcm_*).  The two differ in the PCM load alone.
+ * -DLC3_PCM_PLACED: named with _plc, every sample type from per-frame offsets (lc3_kernels.hip: pcm_placed_load). */
 #if ENC_PCM_FMT
 #define ENC_WAVE_FN LC3_FMT_CAT(KERNEL_FN)
 #else
 #define ENC_WAVE_FN KERNEL_FN
 #endif
 extern "C" __global__ void __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(KERNEL_WAVES, KERNEL_WAVES)))
-ENC_WAVE_FN(LC3_OW_ARGS LC3_OW_OPT(LC3_OW_ARGS_, LC3_TU_VAR, LC3_TU_VBW, LC3_TU_PK))      /* lc3_kernel_decls.h: the parameters, and what each is */
+ENC_WAVE_FN(LC3_OW_ARGS LC3_OW_OPT(LC3_OW_ARGS_, LC3_TU_VAR, LC3_TU_VBW, LC3_TU_PK) LC3_PLACED_OPT)      /* lc3_kernel_decls.h: the parameters, and what each is */
 {
     __shared__ WaveLds L;
     const int lane = threadIdx.x;
@@ -91,7 +92,9 @@ ENC_WAVE_FN(LC3_OW_ARGS LC3_OW_OPT(LC3_OW_ARGS_, LC3_TU_VAR, LC3_TU_VBW, LC3_TU_
             if (lane < 7) L.isc[I_SCF0 + lane] = ri;
             if (lane == 7) L.isc[I_BW] = ri;
         }
-#if ENC_PCM_FMT
+#ifdef LC3_PCM_PLACED                                    /* placed: the frame at its offset, zeros where that is invalid */
+        else pcm_placed_load<true>(pcm, bitdepth, plo, plcap, channels, N, (size_t)strm * T + t, ch, 0, N, XCUR(L), lane, 1.0f);
+#elif ENC_PCM_FMT
         else {                                           /* by the format word: the frame's first element and the step between its samples */
             const size_t o = lc3d_pcm_frame(bitdepth, channels, T, N, strm, t, ch);
             if (PCM_F32_WIDE(pcm, bitdepth, o, N)) {     /* float samples one after the other: 16 bytes per lane */

@@ -375,6 +375,7 @@ struct lc3plus_batch {
     int stride_bound;               /* while chans is stale: the out_stride an encode() needs (stride() before those calls, raised to the out_stride of each with rates) */
     int bw_unsafe;                  /* set_bandwidth has installed a value with a cut-off line below 1 since the last read-back */
     int dry;                        /* DRY_*: the call checks its arguments as always and returns before it touches the device (sharded batches) */
+    int placed;                     /* lc3plus_enc_batch_set_pcm_placement is on: the calls below refuse host PCM, traces and the channel-major layout */
 };
 
 /* A sharded batch checks a call on every shard before any shard runs it: the per-batch call itself, stopped behind its checks.  The checks of a call come in
@@ -545,6 +546,35 @@ int64_t lc3plus_pcm_offset(int format, int channels, int n_frames, int samples, 
 }
 
 int lc3plus_pcm_elem_bytes(int format) { return pcm_format_ok(format) ? lc3d_pcm_elem_bytes(format) : -1; }
+/* Placed PCM (lc3_plan.h: lc3d_pcm_placed_*, the text the _plc kernels compile too).  Host-only hooks: the address rule and the validity rule without a GPU
+ * (tests/test_pcm_placed_cpu.py). */
+int64_t lc3plus_pcm_placed_offset(int format, int channels, int samples, int64_t frame_offset, int channel, int sample)
+{
+    if (!pcm_format_ok(format) || (format & LC3D_PCM_CHANNEL_MAJOR) || channels <= 0 || samples <= 0 || frame_offset < 0 || channel < 0 || channel >= channels ||
+        sample < 0 || sample >= samples) return -1;
+    if (frame_offset > INT64_MAX - (int64_t)channels * samples) return -1;
+    return (int64_t)(lc3d_pcm_placed_frame(format, channels, samples, (long long)frame_offset, channel) + (size_t)sample * lc3d_pcm_stride(format, channels));
+}
+LC3_Error lc3plus_plan_placed(int format, int channels, int samples, const int64_t* offsets, int64_t n, int64_t capacity, uint8_t* invalid)
+{
+    if (n < 0 || capacity < 0 || channels <= 0 || samples <= 0 || !pcm_format_ok(format) || (format & LC3D_PCM_CHANNEL_MAJOR)) return LC3_ERROR;
+    if (n > 0 && (!offsets || !invalid)) return LC3_NULL_ERROR;
+    for (int64_t i = 0; i < n; i++) invalid[i] = (uint8_t)!lc3d_pcm_placed_ok((long long)offsets[i], channels, samples, (long long)capacity);
+    return LC3_OK;
+}
+/* while placement is on: a call with host PCM, a traced call and the channel-major layout are refused before anything else of the call is looked at */
+static int placed_refuses(int placed, int pcm_on_device, int format, const void* trace)
+{
+    return placed && (!pcm_on_device || trace || (format & LC3D_PCM_CHANNEL_MAJOR));
+}
+LC3_Error lc3plus_enc_batch_set_pcm_placement(lc3plus_batch* b, const int64_t* offsets, int64_t capacity)
+{
+    if (!b) return LC3_NULL_ERROR;
+    if (capacity < 0) return LC3_ERROR;
+    if (lc3hip_set_pcm_placement(b->dev, (const long long*)offsets, (long long)capacity)) return LC3_ERROR;
+    b->placed = offsets != NULL;
+    return LC3_OK;
+}
 /* The wire types' conversion rule on the host (lc3_plan.h: the text the kernels compile too), element by element, byte by byte: no alignment needed on the wire side. */
 LC3_Error lc3plus_pcm_to_native(int format, const void* src, int64_t n, void* dst)
 {
@@ -585,6 +615,7 @@ static LC3_Error batch_encode(lc3plus_batch* b, const void* pcm, int pcm_on_devi
 {
     if (!b || !pcm || !out) return LC3_NULL_ERROR;
     if (!pcm_format_ok(bitdepth)) return LC3_ERROR;
+    if (placed_refuses(b->placed, pcm_on_device, bitdepth, trace)) return LC3_ERROR;
     if (trace && !pcm_format_plain(bitdepth)) return LC3_ERROR;      /* the traced calls take the integer formats in the default layout only */
     if (n_frames <= 0 || out_stride < enc_stride_bound(b)) return LC3_ERROR;
     DRY_STOP(b, DRY_ALL, LC3_OK);
@@ -609,6 +640,7 @@ static LC3_Error batch_encode_bitrates(lc3plus_batch* b, const void* pcm, int pc
 {
     if (!b || !pcm || !out || !bitrates) return LC3_NULL_ERROR;
     if (!pcm_format_ok(bitdepth)) return LC3_ERROR;
+    if (placed_refuses(b->placed, pcm_on_device, bitdepth, trace)) return LC3_ERROR;
     if (trace && !pcm_format_plain(bitdepth)) return LC3_ERROR;
     if (n_frames <= 0) return LC3_ERROR;
     if (enc_refresh(b)) return LC3_ERROR;
@@ -684,6 +716,7 @@ static LC3_Error batch_encode_bandwidths(lc3plus_batch* b, const void* pcm, int 
                                          int n_frames, void* out, int out_stride, int out_on_device, int* num_bytes, void* hip_stream, int sync)
 {
     if (!b) return LC3_NULL_ERROR;
+    if (placed_refuses(b->placed, pcm_on_device, pcm_format_ok(bitdepth) ? bitdepth : 0, NULL)) return LC3_ERROR;
     if (b->g.hrmode) return LC3_HRMODE_BW_ERROR;
     if (enc_refresh(b)) return LC3_ERROR;
     const size_t n = (size_t)b->n_streams * (n_frames > 0 ? n_frames : 0);
@@ -823,6 +856,7 @@ LC3_Error lc3plus_enc_batch_encode_rates_device(lc3plus_batch* b, const void* pc
 {
     if (!b || !pcm || !out || (!bitrates && !bandwidths)) return LC3_NULL_ERROR;
     if (!pcm_format_ok(bitdepth)) return LC3_ERROR;
+    if (placed_refuses(b->placed, 1, bitdepth, NULL)) return LC3_ERROR;
     if (n_frames <= 0 || out_stride < enc_stride_bound(b)) return LC3_ERROR;
     if (bandwidths && b->g.hrmode) return LC3_HRMODE_BW_ERROR;
     if (bandwidths && b->bw_unsafe) {           /* a value in force with a cut-off line below 1: refused as encode_bandwidths refuses it (enc_plan_bandwidths) */
@@ -888,6 +922,7 @@ LC3_Error lc3plus_enc_batch_encode_packed(lc3plus_batch* b, const void* pcm, int
 {
     if (!b || !pcm || !out) return LC3_NULL_ERROR;
     if (!pcm_format_ok(bitdepth)) return LC3_ERROR;
+    if (placed_refuses(b->placed, 1, bitdepth, NULL)) return LC3_ERROR;
     if (n_frames <= 0 || (order != LC3D_PACK_STREAM_MAJOR && order != LC3D_PACK_FRAME_MAJOR) || out_capacity < 0) return LC3_ERROR;
     if (bandwidths && b->g.hrmode) return LC3_HRMODE_BW_ERROR;
     if (bandwidths && b->bw_unsafe) {           /* as encode_rates_device */
@@ -1349,6 +1384,7 @@ struct lc3plus_dec_batch {
     lc3d_dchan* tab; int tab_n;      /* dec_build_table, also on the device */
     uint16_t* eff; uint8_t* lost; int* sz; size_t plan_cap;          /* per-frame sizes: host buffers of dec_plan_sizes, grown as needed */
     int dry;                         /* as lc3plus_batch.dry: the call returns behind its checks */
+    int placed;                      /* as lc3plus_batch.placed (lc3plus_dec_batch_set_pcm_placement) */
 };
 
 /* the geometry of a decoder batch, or the error create gives for it; no device */
@@ -1462,6 +1498,7 @@ static LC3_Error dec_batch_decode(lc3plus_dec_batch* b, const void* frames, int 
 {
     if (!b || !frames || !pcm) return LC3_NULL_ERROR;
     if (!pcm_format_ok(bps)) return LC3_ERROR;
+    if (placed_refuses(b->placed, pcm_on_device, bps, traces)) return LC3_ERROR;
     if (traces && !pcm_format_plain(bps)) return LC3_ERROR;          /* the traced call writes the integer formats in the default layout only */
     if (n_frames <= 0) return LC3_ERROR;
     if (dec_refresh(b)) return LC3_ERROR;
@@ -1475,6 +1512,7 @@ LC3_Error lc3plus_dec_batch_decode_sizes(lc3plus_dec_batch* b, const void* frame
 {
     if (!b || !frames || !pcm || !num_bytes) return LC3_NULL_ERROR;
     if (!pcm_format_ok(bps)) return LC3_ERROR;
+    if (placed_refuses(b->placed, pcm_on_device, bps, NULL)) return LC3_ERROR;
     if (n_frames <= 0) return LC3_ERROR;
     if (dec_refresh(b)) return LC3_ERROR;
     const size_t n = (size_t)b->n_streams * n_frames;
@@ -1516,6 +1554,7 @@ LC3_Error lc3plus_dec_batch_decode_sizes_device(lc3plus_dec_batch* b, const void
 {
     if (!b || !frames || !pcm || !num_bytes) return LC3_NULL_ERROR;
     if (!pcm_format_ok(bps)) return LC3_ERROR;
+    if (placed_refuses(b->placed, 1, bps, NULL)) return LC3_ERROR;
     if (n_frames <= 0 || in_stride <= 0) return LC3_ERROR;
     /* the sizes, the carry and the configuration after the call are on the device only: the host mirror is read back by the next host-side reader */
     if (lc3hip_dec_decode_dsizes(b->dev, frames, in_stride, num_bytes, bfi, n_frames, pcm, bps, status, hip_stream, sync)) return LC3_ERROR;
@@ -1527,6 +1566,7 @@ LC3_Error lc3plus_dec_batch_decode_packed(lc3plus_dec_batch* b, const void* fram
 {
     if (!b || !frames || !pcm || !num_bytes || !offsets) return LC3_NULL_ERROR;
     if (!pcm_format_ok(bps)) return LC3_ERROR;
+    if (placed_refuses(b->placed, 1, bps, NULL)) return LC3_ERROR;
     if (n_frames <= 0 || max_frame_bytes <= 0 || frames_capacity < 0) return LC3_ERROR;
     if (lc3hip_dec_decode_packed(b->dev, frames, (long long)frames_capacity, (const long long*)offsets, num_bytes, max_frame_bytes, bfi, n_frames, pcm, bps,
                                  status, hip_stream, sync)) return LC3_ERROR;
@@ -1661,6 +1701,14 @@ LC3_Error lc3plus_dec_batch_decode_traced(lc3plus_dec_batch* b, const void* fram
 }
 int lc3plus_dec_trace_sizeof(void) { return (int)sizeof(lc3d_dec_trace); }
 float lc3plus_dec_batch_last_kernel_ms(lc3plus_dec_batch* b) { return b ? lc3hip_dec_last_ms(b->dev) : 0.0f; }
+LC3_Error lc3plus_dec_batch_set_pcm_placement(lc3plus_dec_batch* b, const int64_t* offsets, int64_t capacity)
+{
+    if (!b) return LC3_NULL_ERROR;
+    if (capacity < 0) return LC3_ERROR;
+    if (lc3hip_dec_set_pcm_placement(b->dev, (const long long*)offsets, (long long)capacity)) return LC3_ERROR;
+    b->placed = offsets != NULL;
+    return LC3_OK;
+}
 LC3_Error lc3plus_dec_batch_set_input_ready(lc3plus_dec_batch* b, int ready)
 {
     if (!b) return LC3_NULL_ERROR;

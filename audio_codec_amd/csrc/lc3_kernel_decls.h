@@ -25,9 +25,11 @@
 #define LC3_OW_ARGS_VBW_1 , const uint16_t* __restrict__ bwf /* [stream][dT] bandwidth in force for each stream-frame, Hz */
 #define LC3_OW_ARGS_PK_0
 #define LC3_OW_ARGS_PK_1 , const long long* __restrict__ poff /* [stream][dT] byte offset of each stream-frame in out, -1: not written */
+/* the two parameters every placed kernel (_plc: lc3_plan.h lc3d_pcm_placed_*, lc3_kernels.hip pcm_placed_load) takes behind those of its dense twin */
+#define LC3_PLACED_ARGS , const long long* __restrict__ plo /* [stream][T] element offset of each stream-frame's PCM */, long long plcap /* length of the PCM buffer, elements */
 #define LC3_OW_OPT_(G, var, vbw, pk) G##VAR_##var G##VBW_##vbw G##PK_##pk
 #define LC3_OW_OPT(G, var, vbw, pk) LC3_OW_OPT_(G, var, vbw, pk)
-/* The variants: X(name, large layout, var, vbw, pk), each once more named name_fmt for the PCM formats beyond 16 / 24 / 32 and name_wire for the wire sample types.  There is no large-layout kernel
+/* The variants: X(name, large layout, var, vbw, pk), each once more named name_fmt for the PCM formats beyond 16 / 24 / 32, name_wire for the wire sample types and name_plc for placed PCM.  There is no large-layout kernel
  * with per-frame bandwidths: that layout only serves 96 kHz, which is high-resolution and has no bandwidth controller. */
 #define LC3_OW_KERNELS(X) \
     X(lc3_encode_kernel,            0, 0, 0, 0) X(lc3_encode_kernel_pk,            0, 0, 0, 1) \
@@ -38,7 +40,7 @@
     X(lc3_encode_kernel_var_vbw,    0, 1, 1, 0) X(lc3_encode_kernel_var_vbw_pk,    0, 1, 1, 1)
 #define LC3_OW_DECL(name, big, var, vbw, pk) \
     extern "C" __global__ void name(LC3_OW_ARGS LC3_OW_OPT(LC3_OW_ARGS_, var, vbw, pk)), name##_fmt(LC3_OW_ARGS LC3_OW_OPT(LC3_OW_ARGS_, var, vbw, pk)), \
-        name##_wire(LC3_OW_ARGS LC3_OW_OPT(LC3_OW_ARGS_, var, vbw, pk));
+        name##_wire(LC3_OW_ARGS LC3_OW_OPT(LC3_OW_ARGS_, var, vbw, pk)), name##_plc(LC3_OW_ARGS LC3_OW_OPT(LC3_OW_ARGS_, var, vbw, pk) LC3_PLACED_ARGS);
 LC3_OW_KERNELS(LC3_OW_DECL)
 #undef LC3_OW_DECL
 
@@ -49,16 +51,19 @@ __global__ void lc3_enc_attack_kernel(const lc3d_plan* __restrict__ P, const lc3
 #define LC3_FRONT4_ARGS const lc3d_plan* __restrict__ P, const lc3d_chan* __restrict__ chans, const float* __restrict__ state, const void* __restrict__ pcm, int bitdepth, \
     int T, int tb, int nt, int ncs, float* __restrict__ spec, int srow, int RT, int r0, float* __restrict__ rec, float* __restrict__ xnext, \
     const float* __restrict__ xprev, int xprev_stride
-__global__ void lc3_enc_front4_kernel(LC3_FRONT4_ARGS), lc3_enc_front4_kernel_fmt(LC3_FRONT4_ARGS), lc3_enc_front4_kernel_wire(LC3_FRONT4_ARGS);
+__global__ void lc3_enc_front4_kernel(LC3_FRONT4_ARGS), lc3_enc_front4_kernel_fmt(LC3_FRONT4_ARGS), lc3_enc_front4_kernel_wire(LC3_FRONT4_ARGS),
+    lc3_enc_front4_kernel_plc(LC3_FRONT4_ARGS LC3_PLACED_ARGS);
 #define LC3_FRONT_ARGS const lc3d_plan* __restrict__ P, const lc3d_chan* __restrict__ chans, const float* __restrict__ state, const void* __restrict__ pcm, int bitdepth, \
     int T, int tb, int nt, int fpw, int ncs, float* __restrict__ spec, int srow, int RT, int r0, float* __restrict__ rec, float* __restrict__ xnext, \
     const float* __restrict__ xprev, int xprev_stride, int do_scf
 __global__ void lc3_enc_front_kernel(LC3_FRONT_ARGS), lc3_enc_front_kernel_big(LC3_FRONT_ARGS), lc3_enc_front_kernel_big_fmt(LC3_FRONT_ARGS),
-    lc3_enc_front_kernel_fmt(LC3_FRONT_ARGS), lc3_enc_front_kernel_wire(LC3_FRONT_ARGS), lc3_enc_front_kernel_big_wire(LC3_FRONT_ARGS);
+    lc3_enc_front_kernel_fmt(LC3_FRONT_ARGS), lc3_enc_front_kernel_wire(LC3_FRONT_ARGS), lc3_enc_front_kernel_big_wire(LC3_FRONT_ARGS),
+    lc3_enc_front_kernel_plc(LC3_FRONT_ARGS LC3_PLACED_ARGS), lc3_enc_front_kernel_big_plc(LC3_FRONT_ARGS LC3_PLACED_ARGS);
 #define LC3_FRONTM_ARGS const lc3d_plan* __restrict__ P, const lc3d_chan* __restrict__ chans, const float* __restrict__ state, const void* __restrict__ pcm, int bitdepth, \
     int T, int tb, int nt, int F, int ncs, float* __restrict__ spec, int srow, int RT, int r0, float* __restrict__ rec, float* __restrict__ xnext, \
     const float* __restrict__ xprev, int xprev_stride
-__global__ void lc3_enc_frontm_kernel(LC3_FRONTM_ARGS), lc3_enc_frontm_kernel_fmt(LC3_FRONTM_ARGS), lc3_enc_frontm_kernel_wire(LC3_FRONTM_ARGS);
+__global__ void lc3_enc_frontm_kernel(LC3_FRONTM_ARGS), lc3_enc_frontm_kernel_fmt(LC3_FRONTM_ARGS), lc3_enc_frontm_kernel_wire(LC3_FRONTM_ARGS),
+    lc3_enc_frontm_kernel_plc(LC3_FRONTM_ARGS LC3_PLACED_ARGS);
 __global__ void lc3_enc_hp50_kernel(const lc3d_plan* __restrict__ P, float* __restrict__ state, int state_words, int scal_off, int T, int tb, int nt, int ncs,
     float* __restrict__ d12);
 #define LC3_PACK_ARGS const lc3d_plan* __restrict__ P, const lc3d_chan* __restrict__ chans, int* __restrict__ dump, int dstride, int T, int tb, int nt, int ncs, \
@@ -89,7 +94,8 @@ __global__ void lc3_enc_resample96_kernel_n240(LC3_RESAMPLE96_ARGS), lc3_enc_res
     lc3_enc_resample96_kernel_n960(LC3_RESAMPLE96_ARGS);
 #define LC3_RESAMPLE_ARGS const lc3d_plan* __restrict__ P, const float* __restrict__ state, int state_words, int memcap, const void* __restrict__ pcm, int bitdepth, \
     int T, int tb, int nt, int ncs, float* __restrict__ d12, const float* __restrict__ xprev, int xprev_stride
-__global__ void lc3_enc_resample_fmt_kernel(LC3_RESAMPLE_ARGS), lc3_enc_resample_kernel(LC3_RESAMPLE_ARGS), lc3_enc_resample_wire_kernel(LC3_RESAMPLE_ARGS);
+__global__ void lc3_enc_resample_fmt_kernel(LC3_RESAMPLE_ARGS), lc3_enc_resample_kernel(LC3_RESAMPLE_ARGS), lc3_enc_resample_wire_kernel(LC3_RESAMPLE_ARGS),
+    lc3_enc_resample_plc_kernel(LC3_RESAMPLE_ARGS LC3_PLACED_ARGS);
 __global__ void lc3_enc_scf_lane_kernel(const lc3d_plan* __restrict__ P, int RT, int r0, int nt, int ncs, const float* __restrict__ rows, int srow,
     float* __restrict__ frec, int with_vq);
 #define LC3_SHAPE_ARGS const lc3d_plan* __restrict__ P, const lc3d_chan* __restrict__ chans, int T, int tb, int nt, int fpw, int ncs, float* __restrict__ rows, int srow, \
@@ -131,7 +137,8 @@ __global__ void lc3_dec_sizes_tail_kernel(const uint16_t* __restrict__ sizes, co
     int n_streams, int T, lc3d_dchan* __restrict__ chans, uint8_t* __restrict__ status);
 #define LC3_DEC_SYNTH_ARGS const lc3d_plan* __restrict__ P, float* __restrict__ state, const int* __restrict__ rec, const float* __restrict__ ws, \
     const float* __restrict__ ov, int T, void* __restrict__ pcm, int bps, int ncs, uint8_t* __restrict__ status, lc3d_dec_trace* __restrict__ trace
-__global__ void lc3_dec_synth_kernel(LC3_DEC_SYNTH_ARGS), lc3_dec_synth_kernel_big(LC3_DEC_SYNTH_ARGS);
+__global__ void lc3_dec_synth_kernel(LC3_DEC_SYNTH_ARGS), lc3_dec_synth_kernel_big(LC3_DEC_SYNTH_ARGS), lc3_dec_synth_kernel_plc(LC3_DEC_SYNTH_ARGS LC3_PLACED_ARGS),
+    lc3_dec_synth_kernel_big_plc(LC3_DEC_SYNTH_ARGS LC3_PLACED_ARGS);
 /* ---- stream lifecycle, per-frame plans, packed offsets, test hook (lc3_util_kernels.inc) ---- */
 __global__ void lc3_enc_plan_rates_kernel(lc3d_rate_rule r, const int32_t* __restrict__ rates, const int32_t* __restrict__ bws, int T, int n_streams,
     int4* __restrict__ carry, const lc3d_chan* __restrict__ seed, uint16_t* __restrict__ fsz, uint16_t* __restrict__ bwf, int32_t* __restrict__ num_bytes,
@@ -139,6 +146,7 @@ __global__ void lc3_enc_plan_rates_kernel(lc3d_rate_rule r, const int32_t* __res
 __global__ void lc3_enc_rates_tail_kernel(const int4* __restrict__ pend, const lc3d_chan* __restrict__ etab, lc3d_chan* __restrict__ chans, int channels, int ncs,
     int dms, int all);
 __global__ void lc3_fastmath_test_kernel(int kind, const float* __restrict__ x, float* __restrict__ y, long long n);
+__global__ void lc3_pcm_placed_mark_kernel(const long long* __restrict__ plo, long long plcap, int channels, int N, long long n, uint8_t* __restrict__ out, int bit);
 __global__ void lc3_pack_base_kernel(long long* __restrict__ bsum, long long nb, long long* __restrict__ total);
 __global__ void lc3_pack_offsets_kernel(PkSrc q, long long n, const long long* __restrict__ base, long long cap, long long* __restrict__ tab,
     long long* __restrict__ offsets, uint8_t* __restrict__ flags, int plan_flags, int32_t* __restrict__ num_bytes);

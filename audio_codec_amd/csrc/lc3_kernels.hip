@@ -226,6 +226,60 @@ template <bool QW> __device__ __forceinline__ int pcm_wire_run(const void* __res
 #define PCM_F32_WIDE(pcm, fmt, o, n) pcm_f32_wide(pcm, fmt, o, n)
 #endif
 
+/* -DLC3_PCM_PLACED (with -DLC3_PCM_FMT -DLC3_PCM_WIRE, the objects and kernels named _plc): placed PCM (lc3_plan.h: lc3d_pcm_placed_*).  Every kernel that touches the
+ * caller's PCM once more, taking two parameters behind its own - plo [stream][T], the element offset of each frame, and plcap, the length of the buffer in elements -
+ * and loading through pcm_placed_load: one form for every sample type, chosen per frame, as the offsets are only known on the device. */
+#ifdef LC3_PCM_PLACED
+#define LC3_PLACED_OPT LC3_PLACED_ARGS
+__device__ __forceinline__ float pcm_any(const void* __restrict__ pcm, int fmt, size_t idx)
+{
+    const int ty = fmt & LC3D_PCM_TYPE_MASK;
+    return lc3d_pcm_type_wire(ty) ? pcm_wire(pcm, ty, idx) : pcm_in(pcm, fmt, idx);
+}
+/* pcm_wire_run for the four native types: n samples that follow each other from element o on, 16 bytes per lane where the run's first byte is 16-byte aligned;
+ * returns the number of samples done.  No byte outside the run is read. */
+template <bool QW> __device__ __forceinline__ int pcm_native_run(const void* __restrict__ pcm, int fmt, size_t o, int n, float* __restrict__ dst, int lane, float sf)
+{
+    const int ty = fmt & LC3D_PCM_TYPE_MASK;
+    const size_t at = (size_t)pcm + o * (size_t)lc3d_pcm_elem_bytes(ty);
+    if ((QW && (n & 3)) || (at & 15)) return 0;
+    if (ty == 16) {
+        for (int i = lane; i < (n >> 3); i += WAVE) {
+            const uint4 v = ((const uint4*)at)[i];
+            pcm_wire_put<QW>(dst + 8 * i, make_float4((float)(int16_t)(v.x & 0xffff), (float)(int16_t)(v.x >> 16), (float)(int16_t)(v.y & 0xffff), (float)(int16_t)(v.y >> 16)), sf);
+            pcm_wire_put<QW>(dst + 8 * i + 4, make_float4((float)(int16_t)(v.z & 0xffff), (float)(int16_t)(v.z >> 16), (float)(int16_t)(v.w & 0xffff), (float)(int16_t)(v.w >> 16)), sf);
+        }
+        return n & ~7;
+    }
+    if (ty == LC3D_PCM_FLOAT32) {
+        for (int i = lane; i < (n >> 2); i += WAVE) pcm_wire_put<QW>(dst + 4 * i, pcm_f32x4(((const float4*)at)[i]), sf);
+        return n & ~3;
+    }
+    const float sc = ty == 24 ? 256.0f : 65536.0f;
+    for (int i = lane; i < (n >> 2); i += WAVE) {
+        const int4 v = ((const int4*)at)[i];
+        pcm_wire_put<QW>(dst + 4 * i, make_float4((float)v.x / sc, (float)v.y / sc, (float)v.z / sc, (float)v.w / sc), sf);
+    }
+    return n & ~3;
+}
+/* Samples first ... first + n - 1 of channel ch of the frame whose offset is plo[fi] (fi = stream * T + frame) -> dst[0 .. n), times sf, by the whole wave: zeros
+ * where the frame is invalid; wide loads where the samples follow each other and the run starts on the boundary its type's wide load needs, element by element
+ * otherwise.  QW: dst is 16-byte aligned (LDS). */
+template <bool QW> __device__ __forceinline__ void pcm_placed_load(const void* __restrict__ pcm, int fmt, const long long* __restrict__ plo, long long plcap, int channels,
+                                                                   int N, size_t fi, int ch, int first, int n, float* __restrict__ dst, int lane, float sf)
+{
+    const long long off = plo[fi];
+    if (!lc3d_pcm_placed_ok(off, channels, N, plcap)) { for (int i = lane; i < n; i += WAVE) dst[i] = 0.0f; return; }
+    const int ps = lc3d_pcm_stride(fmt, channels);
+    const size_t o = lc3d_pcm_placed_frame(fmt, channels, N, off, ch) + (size_t)first * ps;
+    int done = 0;
+    if (ps == 1) done = lc3d_pcm_type_wire(fmt & LC3D_PCM_TYPE_MASK) ? pcm_wire_run<QW>(pcm, fmt & ~LC3D_PCM_INTERLEAVED, o, n, dst, lane, sf) : pcm_native_run<QW>(pcm, fmt, o, n, dst, lane, sf);
+    for (int i = done + lane; i < n; i += WAVE) dst[i] = pcm_any(pcm, fmt, o + (size_t)i * ps) * sf;
+}
+#else
+#define LC3_PLACED_OPT
+#endif
+
 /* ------------------------------------------------------------------------------------------------ */
 /* LDS slice of one wave (~12.8 KB -> 12 waves per CU)                                                */
 /* ------------------------------------------------------------------------------------------------ */
@@ -2800,7 +2854,10 @@ template <class LdsT> STAGE void st_bitstream(const lc3d_plan* __restrict__ P, c
  * -DLC3_ENC_VBW: per-frame bandwidths (lc3plus_enc_batch_encode_bandwidths), kernel lc3_encode_kernel_vbw (_var_vbw together with -DLC3_ENC_VAR), standard
  * layout only, in objects of their own.  The bandwidth controller takes the frame's bandwidth in Hz from bwf[stream][dt0 + t] (the host has resolved every
  * frame to the value in force, 0 = off) instead of the stream's configuration words, with the formulas of set_bandwidth (lc3d_bw_cut_bin, lc3d_bw_index). */
-#ifdef LC3_PCM_WIRE
+#ifdef LC3_PCM_PLACED
+#define LC3_FMT_CAT2(a) a##_plc
+#define LC3_RESAMPLE_FMT_FN lc3_enc_resample_plc_kernel
+#elif defined(LC3_PCM_WIRE)
 #define LC3_FMT_CAT2(a) a##_wire
 #define LC3_RESAMPLE_FMT_FN lc3_enc_resample_wire_kernel
 #else
@@ -2828,6 +2885,20 @@ template <class LdsT> STAGE void st_bitstream(const lc3d_plan* __restrict__ P, c
 #include "lc3_enc_front4.inc"      /* lc3_enc_front4_kernel_fmt */
 #include "lc3_enc_frontm.inc"      /* lc3_enc_frontm_kernel_fmt */
 #include "lc3_enc_pre.inc"         /* lc3_enc_resample_fmt_kernel, lc3_enc_resample48f_kernel, lc3_enc_resample48w_kernel */
+#endif
+#ifdef LC3_PCM_PLACED              /* the two plain placed objects: the decoder's synthesis kernel with placed output, and the kernel that marks invalid frames */
+#include "lc3_dec_kernels.inc"     /* lc3_dec_synth_kernel_plc (or _big_plc) alone */
+#ifndef LC3_BIG
+/* One stream-frame per lane behind a placed call that reports per frame in device memory: the frames whose offset is invalid get `bit` (LC3D_ENC_FL_PCM_PLACE into
+ * the encoder's flags, LC3D_DEC_ST_PCM_PLACE into the decoder's status) beside what the call's own kernels wrote there. */
+extern "C" __global__ void __launch_bounds__(256)
+lc3_pcm_placed_mark_kernel(const long long* __restrict__ plo, long long plcap, int channels, int N, long long n, uint8_t* __restrict__ out, int bit)
+{
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    if (!lc3d_pcm_placed_ok(plo[i], channels, N, plcap)) out[i] |= (uint8_t)bit;
+}
+#endif
 #endif
 #endif
 #ifdef LC3_TU_MAIN

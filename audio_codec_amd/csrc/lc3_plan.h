@@ -291,4 +291,23 @@ static inline LC3D_HD size_t lc3d_pcm_frame(int fmt, int channels, int T, int N,
     return (((size_t)strm * T + t) * channels + ch) * N;
 }
 
+/* ---- Placed PCM (lc3plus_{enc,dec}_batch_set_pcm_placement) --------------------------------------------------------------------------------------
+ * In place of lc3d_pcm_frame: frame (stream, t) of a call lies at the element offset off = offsets[stream * T + t], read from device memory when the call's
+ * kernels run.  off is sample 0 of channel 0; the frame's channels * N elements follow each other - channel after channel with no layout bit, sample by sample
+ * with LC3D_PCM_INTERLEAVED (there is no channel-major placement: that layout's channel distance belongs to a dense call).  A frame is valid where it lies
+ * inside [0, cap); nothing of an invalid frame is touched: the encoder reads zeros for it, the decoder does not write it.  The same text on the host
+ * (lc3plus_pcm_placed_offset, lc3plus_plan_placed) and in the _plc kernels. */
+#define LC3D_ENC_FL_PCM_PLACE 16         /* flag bit of the encoder's device flags: the frame's PCM offset is invalid, the frame was encoded as silence */
+#define LC3D_DEC_ST_PCM_PLACE 4          /* status bit of the decoder's device status: the frame's PCM offset is invalid, its PCM was not written */
+static inline LC3D_HD int lc3d_pcm_placed_ok(long long off, int channels, int N, long long cap)
+{
+    const long long fe = (long long)channels * N;
+    return off >= 0 && cap >= fe && off <= cap - fe;         /* no overflow: cap - fe >= 0 */
+}
+static inline LC3D_HD size_t lc3d_pcm_placed_frame(int fmt, int channels, int N, long long off, int ch)
+{
+    (void)channels;
+    return (size_t)off + ((fmt & LC3D_PCM_INTERLEAVED) ? (size_t)ch : (size_t)ch * (size_t)N);
+}
+
 #endif

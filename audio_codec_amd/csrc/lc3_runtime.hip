@@ -83,6 +83,7 @@ struct lc3hip_ctx {
     uint8_t* d_status; uint8_t* d_statusv[LC3D_SETS]; size_t status_capv[LC3D_SETS]; int status_frames;      /* d_status: the set of the last call */
     hipStream_t s_pk[2]; hipEvent_t ev_pk[2]; int pk_par;       /* the bitstream writers of consecutive calls beside each other (enc_launch) */
     float* d_spec[LC3D_SETS]; size_t spec_cap[LC3D_SETS]; float* d_frec[LC3D_SETS]; size_t frec_cap[LC3D_SETS]; hipEvent_t ev_done[LC3D_SETS]; float* d_xnext[LC3D_SETS + 1]; int xn_par, row_par; uint8_t* h_attack; int any_attack;
+    const long long* plo; long long plcap;         /* lc3hip_set_pcm_placement: per-frame PCM offsets in device memory (null: off) and the buffer's length in elements */
     int input_ready, ahead_ok, ahead_T, ahead_R;   /* lc3hip_set_input_ready: side kernels of a call beside the previous call's tail */   /* split path (lc3_enc_front.inc) */      /* per channel-frame status bits of the last call (LC3D_ENC_ST_*) */
     /* host-pointer pipeline (lc3hip_encode_host): two chunk slots, each with device staging and (for pageable callers) pinned staging */
     void* hp_dpcm[2]; void* hp_pin_in[2]; size_t hp_pcm_cap, hp_pin_in_cap;
@@ -297,11 +298,22 @@ static int dup_of(char k) { static const char* e = nullptr; static bool rd = fal
 #else
 #define DUPL(k)
 #endif
+/* Placed PCM, calls that report per frame in device memory: behind the call's own kernels on s - every one of them that writes `out` (the encoder's flags, the
+ * decoder's status) has finished or is joined to s by then - the frames whose offset is invalid get `bit`.  Nothing to do without placement or without `out`. */
+static int placed_mark(const long long* plo, long long plcap, int channels, int N, long long n, uint8_t* out, int bit, hipStream_t s)
+{
+    if (!plo || !out || n <= 0) return 0;
+    hipLaunchKernelGGL(lc3_pcm_placed_mark_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, plo, plcap, channels, N, n, out, bit);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
 /* the 12.8 kHz polyphase FIR of frames hb ... hb + hn - 1 of every channel-stream on stream st: four outputs per lane where the shape allows */
 static void launch_resample(lc3hip_ctx* c, hipStream_t st, const void* dpcm, int bitdepth, int n_frames, int hb, int hn, int mc, float* dy12, const float* xprev, int xprev_stride)
 {
     const unsigned pruns = (unsigned)((hn + PRE_FPW - 1) / PRE_FPW);
-    if (c->rs48 && bitdepth == 16 && (((size_t)dpcm) & 15) == 0)
+    if (c->plo)                                  /* placed PCM: the resampler for every shape (the specialised ones take typed dense pointers) */
+        hipLaunchKernelGGL(lc3_enc_resample_plc_kernel, dim3((unsigned)c->ncs * pruns), dim3(WAVE), 0, st, c->d_plan, c->d_state, c->state_words, mc, dpcm, bitdepth, n_frames, hb, hn, c->ncs, dy12, xprev, xprev_stride, c->plo, c->plcap);
+    else if (c->rs48 && bitdepth == 16 && (((size_t)dpcm) & 15) == 0)
         hipLaunchKernelGGL(lc3_enc_resample48_kernel, dim3((unsigned)c->ncs * pruns), dim3(WAVE), 0, st, c->d_plan, (const int16_t*)dpcm, c->channels, mc, n_frames, hb, hn, c->ncs, dy12, xprev, xprev_stride);
     else if (c->rs48 && (bitdepth & (LC3D_PCM_TYPE_MASK | LC3D_PCM_INTERLEAVED)) == LC3D_PCM_FLOAT32 && (((size_t)dpcm) & 15) == 0)   /* frames of 480 x 4 bytes: every one 16-byte aligned */
         hipLaunchKernelGGL(lc3_enc_resample48f_kernel, dim3((unsigned)c->ncs * pruns), dim3(WAVE), 0, st, c->d_plan, (const float*)dpcm, bitdepth, c->channels, mc, n_frames, hb, hn, c->ncs, dy12, xprev, xprev_stride);
@@ -343,6 +355,8 @@ static int enc_launch(lc3hip_ctx* c, const void* dpcm, int bitdepth, int n_frame
     /* the PCM formats beyond the reference's three have kernels of their own (_fmt) wherever the load could not be added without moving the registers of the kernel that is there */
     const bool fmt_plain = bitdepth == 16 || bitdepth == 24 || bitdepth == 32;
     const bool fmt_wire = lc3d_pcm_type_wire(bitdepth & LC3D_PCM_TYPE_MASK) != 0;           /* the wire sample types: the _wire twins, so that the _fmt kernels stay what they were */
+    const bool placed = c->plo != nullptr;                                                  /* placed PCM: the _plc twins, one form for every sample type */
+    if (placed && (dt0 != 0 || dT != n_frames || (bitdepth & LC3D_PCM_CHANNEL_MAJOR))) return 1;    /* the offsets are indexed by the call's frames; the host refuses the rest */
     const bool in_kernel_writer = dtr || c->fused || dfsz || dT <= (c->input_ready ? LC3D_FUSED_MAX_T_READY : LC3D_FUSED_MAX_T);
     if (!in_kernel_writer) {
         dstride = PK_STRIDE(c->N, c->hr);
@@ -387,7 +401,11 @@ static int enc_launch(lc3hip_ctx* c, const void* dpcm, int bitdepth, int n_frame
         const long long* pt = c->pk.on ? c->pk.tab : nullptr;         /* packed output: the _pk kernels, frames at the offsets of the call's table */
         const int key = OW_KEY(c->big != 0, dfsz != nullptr, dbw != nullptr, pt != nullptr);
 #define OW_LAUNCH(name, big, var, vbw, pk) \
-        if (key == OW_KEY(big, var, vbw, pk)) \
+        if (key == OW_KEY(big, var, vbw, pk) && placed) \
+            hipLaunchKernelGGL(name##_plc, dim3(c->ncs), dim3(WAVE), 0, s, c->d_plan, c->d_chans, c->d_state, dpcm, bitdepth, n_frames, \
+                               dout, pt ? 0 : out_stride, c->ncs, dtr, ddump, dstride, dy12, c->d_status, dT, dt0, (const float*)nullptr, (const float*)nullptr, \
+                               (const float*)nullptr LC3_OW_OPT(LC3_OW_VALS_, var, vbw, pk), c->plo, c->plcap); \
+        else if (key == OW_KEY(big, var, vbw, pk)) \
             hipLaunchKernelGGL(fmt_plain ? name : fmt_wire ? name##_wire : name##_fmt, dim3(c->ncs), dim3(WAVE), 0, s, c->d_plan, c->d_chans, c->d_state, dpcm, bitdepth, n_frames, \
                                dout, pt ? 0 : out_stride, c->ncs, dtr, ddump, dstride, dy12, c->d_status, dT, dt0, (const float*)nullptr, (const float*)nullptr, \
                                (const float*)nullptr LC3_OW_OPT(LC3_OW_VALS_, var, vbw, pk)); \
@@ -513,10 +531,14 @@ static int enc_launch(lc3hip_ctx* c, const void* dpcm, int bitdepth, int n_frame
             const int fpw = nt < FRONT_FPW ? nt : FRONT_FPW;
             const unsigned fruns = (unsigned)((nt + fpw - 1) / fpw);
             const int f4 = c->opt.front4;
-            if (f4 && !c->big && !scf_wave && c->N == 480 && c->la == 180 && (c->ylen & 15) == 0)
-                DUPL('f') hipLaunchKernelGGL(fmt_plain ? lc3_enc_front4_kernel : fmt_wire ? lc3_enc_front4_kernel_wire : lc3_enc_front4_kernel_fmt, dim3((unsigned)c->ncs * (unsigned)((nt + 3) / 4)), dim3(WAVE), 0, c->s_fr, c->d_plan, c->d_chans, c->d_state, dpcm, bitdepth, n_frames, tb, nt, c->ncs, dspec, c->srow, dT, dt0, dfrec, xn_w, xprev, xprev_stride);
-            else if (f4 && c->fm_frames && !scf_wave)
-                hipLaunchKernelGGL(fmt_plain ? lc3_enc_frontm_kernel : fmt_wire ? lc3_enc_frontm_kernel_wire : lc3_enc_frontm_kernel_fmt, dim3((unsigned)c->ncs * (unsigned)((nt + c->fm_frames - 1) / c->fm_frames)), dim3(WAVE), 0, c->s_fr, c->d_plan, c->d_chans, c->d_state, dpcm, bitdepth, n_frames, tb, nt, c->fm_frames, c->ncs, dspec, c->srow, dT, dt0, dfrec, xn_w, xprev, xprev_stride);
+            if (f4 && !c->big && !scf_wave && c->N == 480 && c->la == 180 && (c->ylen & 15) == 0) {
+                if (placed) hipLaunchKernelGGL(lc3_enc_front4_kernel_plc, dim3((unsigned)c->ncs * (unsigned)((nt + 3) / 4)), dim3(WAVE), 0, c->s_fr, c->d_plan, c->d_chans, c->d_state, dpcm, bitdepth, n_frames, tb, nt, c->ncs, dspec, c->srow, dT, dt0, dfrec, xn_w, xprev, xprev_stride, c->plo, c->plcap);
+                else DUPL('f') hipLaunchKernelGGL(fmt_plain ? lc3_enc_front4_kernel : fmt_wire ? lc3_enc_front4_kernel_wire : lc3_enc_front4_kernel_fmt, dim3((unsigned)c->ncs * (unsigned)((nt + 3) / 4)), dim3(WAVE), 0, c->s_fr, c->d_plan, c->d_chans, c->d_state, dpcm, bitdepth, n_frames, tb, nt, c->ncs, dspec, c->srow, dT, dt0, dfrec, xn_w, xprev, xprev_stride);
+            } else if (f4 && c->fm_frames && !scf_wave) {
+                if (placed) hipLaunchKernelGGL(lc3_enc_frontm_kernel_plc, dim3((unsigned)c->ncs * (unsigned)((nt + c->fm_frames - 1) / c->fm_frames)), dim3(WAVE), 0, c->s_fr, c->d_plan, c->d_chans, c->d_state, dpcm, bitdepth, n_frames, tb, nt, c->fm_frames, c->ncs, dspec, c->srow, dT, dt0, dfrec, xn_w, xprev, xprev_stride, c->plo, c->plcap);
+                else hipLaunchKernelGGL(fmt_plain ? lc3_enc_frontm_kernel : fmt_wire ? lc3_enc_frontm_kernel_wire : lc3_enc_frontm_kernel_fmt, dim3((unsigned)c->ncs * (unsigned)((nt + c->fm_frames - 1) / c->fm_frames)), dim3(WAVE), 0, c->s_fr, c->d_plan, c->d_chans, c->d_state, dpcm, bitdepth, n_frames, tb, nt, c->fm_frames, c->ncs, dspec, c->srow, dT, dt0, dfrec, xn_w, xprev, xprev_stride);
+            }
+            else if (placed) hipLaunchKernelGGL(c->big ? lc3_enc_front_kernel_big_plc : lc3_enc_front_kernel_plc, dim3((unsigned)c->ncs * fruns), dim3(WAVE), 0, c->s_fr, c->d_plan, c->d_chans, c->d_state, dpcm, bitdepth, n_frames, tb, nt, fpw, c->ncs, dspec, c->srow, dT, dt0, dfrec, xn_w, xprev, xprev_stride, scf_wave, c->plo, c->plcap);
             else if (c->big) hipLaunchKernelGGL(fmt_plain ? lc3_enc_front_kernel_big : fmt_wire ? lc3_enc_front_kernel_big_wire : lc3_enc_front_kernel_big_fmt, dim3((unsigned)c->ncs * fruns), dim3(WAVE), 0, c->s_fr, c->d_plan, c->d_chans, c->d_state, dpcm, bitdepth, n_frames, tb, nt, fpw, c->ncs, dspec, c->srow, dT, dt0, dfrec, xn_w, xprev, xprev_stride, scf_wave);
             else DUPL('f') hipLaunchKernelGGL(fmt_plain ? lc3_enc_front_kernel : fmt_wire ? lc3_enc_front_kernel_wire : lc3_enc_front_kernel_fmt, dim3((unsigned)c->ncs * fruns), dim3(WAVE), 0, c->s_fr, c->d_plan, c->d_chans, c->d_state, dpcm, bitdepth, n_frames, tb, nt, fpw, c->ncs, dspec, c->srow, dT, dt0, dfrec, xn_w, xprev, xprev_stride, scf_wave);
             HIPCHK(hipEventRecord(c->ev_m[k], c->s_fr));                 /* the MDCT memory hand-over and the spectrum rows of the run are written */
@@ -787,6 +809,7 @@ extern "C" int lc3hip_encode(void* ctx, const void* pcm, int pcm_on_device, int 
     const uint16_t* dbw = nullptr; hipEvent_t ev_bw = nullptr;
     if (fsz_host && !c->d_etab) return 1;
     if (bw_host && c->big) return 1;            /* no large-layout kernels: that layout only serves high-resolution batches, which the host refuses */
+    if (c->plo && (!pcm_on_device || trace_host)) return 1;      /* placed PCM: device-pointer calls without traces (the host refuses the others) */
     if (!pcm_on_device && !out_on_device && !trace_host) {
         if (c->chans_armed) HIPCHK(hipStreamWaitEvent(s, c->ev_chans, 0));
         if (fsz_host && upload_fsz(c, fsz_host, n_frames, s, &dfsz, &ev_fsz)) return 1;
@@ -836,6 +859,7 @@ extern "C" int lc3hip_encode(void* ctx, const void* pcm, int pcm_on_device, int 
     HIPCHK(hipEventRecord(c->ev0, s));
     if (c->pk.on && (fsz_host || bw_host || pack_scan(c, s, n_frames, LC3D_SETS, nullptr, nullptr, 0, 0))) return 1;      /* packed output, no per-frame words */
     if (enc_launch(c, dpcm, bitdepth, n_frames, dout, out_stride, s, dtr, n_frames, 0, true, dfsz, dbw)) return 1;
+    if (c->pk.on && placed_mark(c->plo, c->plcap, c->channels, c->N, (long long)c->n_streams * n_frames, c->pk.fl, LC3D_ENC_FL_PCM_PLACE, s)) return 1;
     HIPCHK(hipEventRecord(c->ev1, s));
     if (ev_fsz) HIPCHK(hipEventRecord(ev_fsz, s));
     if (ev_bw) HIPCHK(hipEventRecord(ev_bw, s));      /* the end of the call on s lies behind every kernel that read the words, on whichever stream */
@@ -915,6 +939,7 @@ extern "C" int lc3hip_encode_rates_device(void* ctx, const void* pcm, int bitdep
     hipLaunchKernelGGL(lc3_enc_rates_tail_kernel, dim3((unsigned)((c->ncs + WAVE - 1) / WAVE)), dim3(WAVE), 0, s, (const int4*)c->d_pend[k], (const lc3d_chan*)c->d_etab,
                        c->d_chans, c->channels, c->ncs, rule->dms, rates_dev ? 1 : 0);
     HIPCHK(hipGetLastError());
+    if (placed_mark(c->plo, c->plcap, c->channels, c->N, (long long)c->n_streams * n_frames, flags_dev, LC3D_ENC_FL_PCM_PLACE, s)) return 1;
     HIPCHK(hipEventRecord(c->ev1, s));
     HIPCHK(hipEventRecord(c->ev_pset[k], s)); c->pset_armed[k] = 1; c->pset = (k + 1) % LC3D_SETS;
     /* the configuration the tail kernel wrote: later calls on other streams wait for it (as for lc3hip_upload_chans_async); a call that overlaps this one may
@@ -1052,6 +1077,14 @@ extern "C" int lc3hip_stream_state(void* ctx, int mode, const int* streams, int 
     return cfg ? chans_host_side_list(c, cfg, 0, n * c->channels, streams) : 0;
 }
 
+/* records the pair: every later call reads it (enc_launch, launch_resample); nothing is queued */
+extern "C" int lc3hip_set_pcm_placement(void* ctx, const long long* offsets_dev, long long capacity)
+{
+    lc3hip_ctx* c = (lc3hip_ctx*)ctx;
+    if (!c || capacity < 0) return 1;
+    c->plo = offsets_dev; c->plcap = offsets_dev ? capacity : 0;
+    return 0;
+}
 extern "C" int lc3hip_set_input_ready(void* ctx, int ready)
 {
     lc3hip_ctx* c = (lc3hip_ctx*)ctx;
@@ -1131,6 +1164,7 @@ struct lc3hip_dctx {
     hipStream_t stream, last_stream; hipEvent_t ev0, ev1; float last_ms;
     /* lc3hip_dec_set_input_ready: the parse kernel of a call runs on a stream of its own beside the transform and synthesis of the call before; a
      * second set of hand-over buffers (records, spectrum rows), alternating */
+    const long long* plo; long long plcap;         /* lc3hip_dec_set_pcm_placement */
     int input_ready, set; int* d_recx[DEC_SETS - 1]; float* d_wsx[DEC_SETS - 1]; size_t handx_cap; hipStream_t s_par, s_plc; hipEvent_t ev_par[DEC_SETS], ev_free[DEC_SETS], ev_plc; int free_armed[DEC_SETS];
     /* the end of the last ordered call (bad-frame flags, per-frame sizes, status, host pointers) under the promise: the next parse-ahead waits for it */
     hipEvent_t ev_ord; int ord_pending;
@@ -1218,6 +1252,7 @@ static int dec_decode(lc3hip_dctx* c, const void* frames, int frames_on_device, 
                       const long long* offs_dev = nullptr /* frames packed (lc3hip_dec_decode_packed): in_stride is then the largest frame */, long long cap = 0)
 {
     HIPCHK(hipSetDevice(c->device));
+    if (c->plo && (!pcm_on_device || trace_host || (bps & LC3D_PCM_CHANNEL_MAJOR))) return 1;      /* placed PCM: device-pointer calls without traces (the host refuses the others) */
     hipStream_t s = hip_stream ? (hipStream_t)hip_stream : c->stream;
     if (c->ss.done_armed) HIPCHK(hipStreamWaitEvent(s, c->ss.ev_done, 0));      /* behind the last stream-lifecycle call, whichever stream it was queued on */
     const size_t in_bytes = (size_t)c->n_streams * n_frames * in_stride;
@@ -1378,14 +1413,16 @@ static int dec_decode(lc3hip_dctx* c, const void* frames, int frames_on_device, 
     const unsigned ncf = (unsigned)((size_t)c->ncs * ((n_frames + IMDCT_FPW - 1) / IMDCT_FPW));     /* runs of IMDCT_FPW frames */
     if (c->big) {
         hipLaunchKernelGGL(lc3_dec_imdct_kernel_big, dim3(ncf), dim3(WAVE), 0, s, c->d_plan, c->d_state, rec_w, ws_w, n_frames, c->ncs, c->d_ov, dtr);
-        hipLaunchKernelGGL(lc3_dec_synth_kernel_big, dim3(c->ncs), dim3(WAVE), 0, s, c->d_plan, c->d_state, rec_w, ws_w, c->d_ov, n_frames, dpcm, bps, c->ncs, dst, dtr);
+        if (c->plo) hipLaunchKernelGGL(lc3_dec_synth_kernel_big_plc, dim3(c->ncs), dim3(WAVE), 0, s, c->d_plan, c->d_state, rec_w, ws_w, c->d_ov, n_frames, dpcm, bps, c->ncs, dst, dtr, c->plo, c->plcap);
+        else hipLaunchKernelGGL(lc3_dec_synth_kernel_big, dim3(c->ncs), dim3(WAVE), 0, s, c->d_plan, c->d_state, rec_w, ws_w, c->d_ov, n_frames, dpcm, bps, c->ncs, dst, dtr);
     } else {
         const int i4 = c->opt.dec_imdct4;
         if (i4 && !dtr && c->N == 480)
             hipLaunchKernelGGL(lc3_dec_imdct4_kernel, dim3((unsigned)((size_t)c->ncs * ((n_frames + 3) / 4))), dim3(WAVE), 0, s, c->d_plan, c->d_state, rec_w, ws_w, n_frames, c->ncs, c->d_ov);
         else
         hipLaunchKernelGGL(lc3_dec_imdct_kernel, dim3(ncf), dim3(WAVE), 0, s, c->d_plan, c->d_state, rec_w, ws_w, n_frames, c->ncs, c->d_ov, dtr);
-        hipLaunchKernelGGL(lc3_dec_synth_kernel, dim3(c->ncs), dim3(WAVE), 0, s, c->d_plan, c->d_state, rec_w, ws_w, c->d_ov, n_frames, dpcm, bps, c->ncs, dst, dtr);
+        if (c->plo) hipLaunchKernelGGL(lc3_dec_synth_kernel_plc, dim3(c->ncs), dim3(WAVE), 0, s, c->d_plan, c->d_state, rec_w, ws_w, c->d_ov, n_frames, dpcm, bps, c->ncs, dst, dtr, c->plo, c->plcap);
+        else hipLaunchKernelGGL(lc3_dec_synth_kernel, dim3(c->ncs), dim3(WAVE), 0, s, c->d_plan, c->d_state, rec_w, ws_w, c->d_ov, n_frames, dpcm, bps, c->ncs, dst, dtr);
     }
     HIPCHK(hipGetLastError());
     if (nb_dev) {                                                    /* behind the synthesis: the status bits and the stream's configuration for the next call */
@@ -1393,6 +1430,7 @@ static int dec_decode(lc3hip_dctx* c, const void* frames, int frames_on_device, 
         hipLaunchKernelGGL(lc3_dec_sizes_tail_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, c->d_sizes, c->d_inval, c->d_tab, c->channels,
                            c->n_streams, n_frames, c->d_chans, dst);
         HIPCHK(hipGetLastError());
+        if (placed_mark(c->plo, c->plcap, c->channels, c->N, n, dst, LC3D_DEC_ST_PCM_PLACE, s)) return 1;
     }
     if (ahead) { HIPCHK(hipEventRecord(c->ev_free[c->set], s)); c->free_armed[c->set] = 1; c->set = (c->set + 1) % DEC_SETS; }
     else if (c->s_par) { HIPCHK(hipEventRecord(c->ev_free[0], s)); c->free_armed[0] = 1; }      /* an ordered call reads the first set: a later parse-ahead into it waits for this one */
@@ -1447,6 +1485,13 @@ extern "C" int lc3hip_dec_stream_state(void* ctx, int mode, const int* streams, 
         c->max_nbytes = 0;
         for (int i = 0; i < c->ncs; i++) if (c->h_nbytes[i] > c->max_nbytes) c->max_nbytes = c->h_nbytes[i];
     }
+    return 0;
+}
+extern "C" int lc3hip_dec_set_pcm_placement(void* ctx, const long long* offsets_dev, long long capacity)
+{
+    lc3hip_dctx* c = (lc3hip_dctx*)ctx;
+    if (!c || capacity < 0) return 1;
+    c->plo = offsets_dev; c->plcap = offsets_dev ? capacity : 0;
     return 0;
 }
 extern "C" int lc3hip_dec_set_input_ready(void* ctx, int ready)

@@ -91,6 +91,11 @@ int   lc3hip_stream_state(void* ctx, int mode, const int* streams, int n, const 
                           uint8_t* status, void* hip_stream, int sync);
 int   lc3hip_dec_stream_state(void* ctx, int mode, const int* streams, int n, const lc3d_dchan* cfg, void* blob, int blob_on_device, const uint32_t* hdr,
                               uint8_t* status, void* hip_stream, int sync);
+/* placed PCM (include/lc3plus_batch.h: lc3plus_{enc,dec}_batch_set_pcm_placement; lc3_plan.h: lc3d_pcm_placed_*): offsets_dev [n_streams][n_frames of each call] in
+ * device memory, or null: off; capacity in elements.  Kept in the context and read by every later call that takes device PCM - those calls refuse host PCM, traces
+ * and the channel-major layout while it is on.  Queues nothing, waits for nothing. */
+int   lc3hip_set_pcm_placement(void* ctx, const long long* offsets_dev, long long capacity);
+int   lc3hip_dec_set_pcm_placement(void* ctx, const long long* offsets_dev, long long capacity);
 int   lc3hip_dec_set_input_ready(void* ctx, int ready);          /* see lc3plus_dec_batch_set_input_ready (include/lc3plus_batch.h) */
 int   lc3hip_set_input_ready(void* ctx, int ready);              /* see lc3plus_enc_batch_set_input_ready (include/lc3plus_batch.h) */
 int   lc3hip_last_status(void* ctx, uint8_t* status_host, int n);        /* LC3D_ENC_ST_* bits per channel-frame of the last call; returns the count copied */

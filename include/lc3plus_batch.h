@@ -85,6 +85,40 @@ int lc3plus_pcm_elem_bytes(int format);
 LC3_Error lc3plus_pcm_to_native(int format, const void* src, int64_t n, void* dst);
 LC3_Error lc3plus_pcm_from_native(int format, const void* src, int64_t n, void* dst);
 
+/* ---- Placed PCM: every frame of a call at an offset read from device memory (per-session rings, simulcast) ----
+ * lc3plus_enc_batch_set_pcm_placement / lc3plus_dec_batch_set_pcm_placement (below, with the batches) make the PLACEMENT of the PCM free as the format word makes its
+ * element free: frame (s, t) of a call lies where offsets[s * n_frames + t] says, so that an encoder reads straight out of capture rings, a decoder writes
+ * straight into playout rings, and several streams encode one signal at several rates without a copy.
+ *   offsets  : device pointer to int64 [n_streams][n_frames], indexed [s * n_frames + t] with the n_frames of each call.  NULL switches placement off: off is the
+ *              default, and every call then behaves as without it.
+ *   capacity : the length of the PCM buffer in elements, >= 0.
+ * The setter only records the pair; it queues nothing and waits for nothing.  LC3_NULL_ERROR for a null batch, LC3_ERROR for capacity < 0.  Placement is
+ * configuration, not state: get_state, set_state and the stream blobs do not carry it.
+ * It applies to every later call of the batch that takes its PCM through a device pointer - encode / decode with *_on_device = 1, encode_bitrates /
+ * encode_bandwidths with device PCM, encode_rates_device, encode_packed, decode_sizes, decode_sizes_device, decode_packed - and to the shards of a sharded batch
+ * through the handle lc3plus_{enc,dec}_sharded_shard returns.  The array is read on the device when the call's kernels run: a kernel of the caller's may advance
+ * ring positions between calls.  The set_input_ready promise covers `offsets` as it covers the PCM.
+ * The address rule: offsets[s][t] is the element index, in the `pcm` argument of the call, of sample 0 of channel 0 of frame (s, t).  With no layout bit channel c
+ * starts c * N elements further and its samples follow each other; with LC3PLUS_PCM_INTERLEAVED sample i of channel c is at + i * channels + c.  Either way a
+ * frame occupies channels * N consecutive elements.  lc3plus_pcm_placed_offset is this arithmetic on the host: the element index of one sample, or -1 for
+ * arguments out of range, a refused format word, or LC3PLUS_PCM_CHANNEL_MAJOR.  Every sample type of the format word works; the byte address is the index times
+ * lc3plus_pcm_elem_bytes, and no alignment is needed beyond what the dense call of that type needs for its pointer.  Any element offset is exact; frames whose
+ * byte address is a multiple of 16 keep the wide loads and stores.
+ * While placement is on, a call with host PCM, a traced call, and a call with LC3PLUS_PCM_CHANNEL_MAJOR (its channel distance is a property of a dense call)
+ * return LC3_ERROR, queue nothing and leave the batch unchanged.
+ * A frame is VALID when 0 <= offset and offset + channels * N <= capacity, computed without overflow; lc3plus_plan_placed is that rule on the host (invalid[i] = 1
+ * where offsets[i] is not valid; LC3_ERROR for a negative n or capacity, channels or samples below 1, a refused format word or channel-major, LC3_NULL_ERROR for
+ * a null array with n > 0).  The host cannot see the offsets, so an invalid one does not fail the call, and memory outside [0, capacity) is never touched:
+ *   encoder : all samples of an invalid frame are 0 wherever they are read - as the previous frame of the MDCT overlap, the resampler history and the attack
+ *             detector as well.  The frame is encoded and its stream advances: the result equals a dense call in which that frame is silence.  The calls that
+ *             return `flags` in device memory (encode_rates_device, encode_packed) set flag bit 4 (16) for it; the other calls stay silent.
+ *   decoder : an invalid frame is decoded or concealed and its stream advances exactly as otherwise; its PCM is not written.  The calls with a device `status`
+ *             (decode_sizes_device, decode_packed) set status bit 2 (4) for it; host status arrays keep their 0 / 1 meaning.
+ * Input frames may coincide or overlap: several streams may read the same PCM (simulcast), and the hop may be shorter than a frame.  Output frames that overlap
+ * are the caller's error: each is written whole, in no defined order.  No byte outside a written frame's channels * N elements is modified. */
+int64_t lc3plus_pcm_placed_offset(int format, int channels, int samples, int64_t frame_offset, int channel, int sample);
+LC3_Error lc3plus_plan_placed(int format, int channels, int samples, const int64_t* offsets, int64_t n, int64_t capacity, uint8_t* invalid);
+
 /* Advances every stream by n_frames.
  *   pcm : [n_streams][n_frames][channels][input_samples] samples, int16_t (bitdepth 16) or int32_t (24/32); or float and / or another layout, as the
  *         format word in `bitdepth` says (above)
@@ -255,6 +289,8 @@ LC3_Error lc3plus_enc_batch_import_streams(lc3plus_batch* batch, const int* stre
  * For encode_rates_device() the promise covers its bitrates and bandwidths as well (complete when the call is made), and its num_bytes and flags as
  * the output buffer (free to be written). */
 LC3_Error lc3plus_enc_batch_set_input_ready(lc3plus_batch* batch, int ready);
+/* Placed PCM for the encoder's input ("Placed PCM" above): offsets NULL = off. */
+LC3_Error lc3plus_enc_batch_set_pcm_placement(lc3plus_batch* batch, const int64_t* offsets, int64_t capacity);
 
 /* Kernel-only timing of the last encode() call in milliseconds (HIP events on the launch stream). */
 float lc3plus_enc_batch_last_kernel_ms(lc3plus_batch* batch);
@@ -365,6 +401,8 @@ LC3_Error lc3plus_dec_batch_import_streams(lc3plus_dec_batch* batch, const int* 
  * bitstream parser of a call - stateless - then runs on a stream of the batch beside the transform and synthesis of the call before; results
  * are identical, and the PCM of a call is complete in stream order on hip_stream as before.  Off by default. */
 LC3_Error lc3plus_dec_batch_set_input_ready(lc3plus_dec_batch* batch, int ready);
+/* Placed PCM for the decoder's output ("Placed PCM" above): offsets NULL = off. */
+LC3_Error lc3plus_dec_batch_set_pcm_placement(lc3plus_dec_batch* batch, const int64_t* offsets, int64_t capacity);
 
 /* ---- Sharded batches: one call drives encoders or decoders on several GPUs ------------------------------------------------------------------
  * Streams are independent, so a sharded batch is n_devices ordinary batches, each owning a contiguous block of the n_streams streams on a device of its

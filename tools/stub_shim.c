@@ -10,11 +10,12 @@
 #include <string.h>
 #include "../audio_codec_amd/csrc/lc3_shim.h"
 
-enum { STUB_ENCODE = 1, STUB_DECODE = 2, STUB_GET_STATE = 3, STUB_SET_STATE = 4, STUB_WAIT = 5 };
+enum { STUB_ENCODE = 1, STUB_DECODE = 2, STUB_GET_STATE = 3, STUB_SET_STATE = 4, STUB_WAIT = 5, STUB_PLACEMENT = 6 };
 #define STUB_STATE_BYTES 32          /* per channel-stream */
 
 /* p: encode pcm, out; decode frames, pcm, status, bfi; state: the host pointer.  a / b: the first two words and the last one of the two per-frame arrays
- * the call was given (encode: frame sizes, bandwidths in force; decode: sizes, loss flags), -1 where there is none.  sync / on_device as passed. */
+ * the call was given (encode: frame sizes, bandwidths in force; decode: sizes, loss flags), -1 where there is none.  sync / on_device as passed.
+ * STUB_PLACEMENT (lc3hip_set_pcm_placement, lc3hip_dec_set_pcm_placement): p[0] the offsets pointer, a[0] the capacity. */
 typedef struct {
     int32_t ctx, kind, dec, n_frames, stride, fmt, on_device, sync;
     uint64_t p[4];
@@ -86,6 +87,16 @@ float lc3hip_last_ms(void* ctx) { return 0.0f; }
 float lc3hip_dec_last_ms(void* ctx) { return 0.0f; }
 int lc3hip_set_input_ready(void* ctx, int ready) { return 0; }
 int lc3hip_dec_set_input_ready(void* ctx, int ready) { return 0; }
+static int stub_placement(void* ctx, const long long* offsets_dev, long long capacity)
+{
+    lc3stub_rec r; memset(&r, 0, sizeof r);
+    r.kind = STUB_PLACEMENT; r.p[0] = (uint64_t)(uintptr_t)offsets_dev;
+    r.a[0] = capacity; r.a[1] = r.a[2] = r.b[0] = r.b[1] = r.b[2] = -1;
+    (void)stub_append((const stub_ctx*)ctx, &r);
+    return capacity < 0;
+}
+int lc3hip_set_pcm_placement(void* ctx, const long long* offsets_dev, long long capacity) { return stub_placement(ctx, offsets_dev, capacity); }
+int lc3hip_dec_set_pcm_placement(void* ctx, const long long* offsets_dev, long long capacity) { return stub_placement(ctx, offsets_dev, capacity); }
 int lc3hip_last_status(void* ctx, uint8_t* status_host, int n) { return 0; }
 int lc3hip_last_records(void* ctx, float* rec_host, int max_words) { return 0; }
 int lc3hip_test_fastmath(int kind, const float* x_host, float* y_host, long long n) { return 1; }
