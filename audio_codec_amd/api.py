@@ -36,6 +36,7 @@ EXPORTS = [
     "lc3plus_enc_batch_encode_packed", "lc3plus_plan_packed", "lc3plus_dec_batch_decode_packed", "lc3plus_dec_plan_packed_lenient",
     "lc3plus_pcm_format_check", "lc3plus_pcm_offset", "lc3plus_pcm_elem_bytes", "lc3plus_pcm_to_native", "lc3plus_pcm_from_native",
     "lc3plus_enc_batch_set_pcm_placement", "lc3plus_dec_batch_set_pcm_placement", "lc3plus_pcm_placed_offset", "lc3plus_plan_placed",
+    "lc3plus_dec_batch_set_frame_counts", "lc3plus_dec_plan_counts",
     "lc3plus_shard_block",
     "lc3plus_enc_sharded_create", "lc3plus_enc_sharded_destroy", "lc3plus_enc_sharded_shards", "lc3plus_enc_sharded_shard", "lc3plus_enc_sharded_device",
     "lc3plus_enc_sharded_owner", "lc3plus_enc_sharded_input_samples", "lc3plus_enc_sharded_num_bytes", "lc3plus_enc_sharded_stride",
@@ -59,6 +60,8 @@ ENC_FL_RATE, ENC_FL_BW_REFUSED, ENC_FL_BW_RANGE = 1, 2, 4
 ENC_FL_PACK_CAP = 8
 # placed PCM (set_pcm_placement): the frame's PCM offset is invalid - the encoder took silence (device flags), the decoder wrote nothing (device status)
 ENC_FL_PCM_PLACE, DEC_ST_PCM_PLACE = 16, 4
+# per-stream frame counts (DecBatch.set_frame_counts): the frame is absent - behind its stream's count; status exactly this value, nothing decoded or written
+DEC_ST_ABSENT = 8
 PACK_STREAM_MAJOR, PACK_FRAME_MAJOR = 0, 1
 LC3_BW_WARNING = 18
 
@@ -196,6 +199,8 @@ def load_library():
         L.lc3plus_pcm_placed_offset.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int]
         L.lc3plus_pcm_placed_offset.restype = C.c_int64
         L.lc3plus_plan_placed.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]
+        L.lc3plus_dec_batch_set_frame_counts.argtypes = [C.c_void_p, C.c_void_p]
+        L.lc3plus_dec_plan_counts.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
         _LIB = L
     return _LIB
 
@@ -792,6 +797,17 @@ def dec_plan_packed_lenient(samplerate, channels, frame_ms, hrmode, start, num_b
     return rc, eff, lost, inv, end, mx.value
 
 
+def dec_plan_counts(counts, n_frames):
+    """The clamp of DecBatch.set_frame_counts on the host (lc3plus_dec_plan_counts, no device needed): counts [S] -> the frames of each stream present in a
+    call of n_frames, int32 [S]; LC3Error for arguments the C call refuses."""
+    counts = np.ascontiguousarray(counts, dtype=np.int32)
+    eff = np.zeros(counts.shape, np.int32)
+    rc = load_library().lc3plus_dec_plan_counts(counts.ctypes.data, counts.size, int(n_frames), eff.ctypes.data)
+    if rc:
+        raise LC3Error(rc, "lc3plus_dec_plan_counts")
+    return eff
+
+
 class DecBatch(_StreamLifecycle):
     """n_streams independent decoders (lc3plus_dec_batch_*), state resident on the GPU between decode() calls."""
 
@@ -925,6 +941,15 @@ class DecBatch(_StreamLifecycle):
         """lc3plus_dec_batch_set_pcm_placement: frame (s, t) of every following device-pointer call is written at element d_offsets[s, t] (int64
         [n_streams, T] in device memory) of the call's pcm pointer, a buffer of `capacity` elements; None switches placement off."""
         _set_pcm_placement(self, "lc3plus_dec_batch_set_pcm_placement", d_offsets_ptr, capacity)
+
+    def set_frame_counts(self, d_counts_ptr):
+        """lc3plus_dec_batch_set_frame_counts: of every following decode_device_sizes / decode_device_packed call stream s holds its first
+        min(max(d_counts[s], 0), T) frames (int32 [n_streams] in device memory, read when the call runs); the frames behind them are absent - nothing read,
+        decoded, concealed or written, status DEC_ST_ABSENT - and the stream's state stops at its last present frame.  The other decode calls refuse while
+        counts are set; None switches them off."""
+        rc = self.lib.lc3plus_dec_batch_set_frame_counts(self.h, C.c_void_p(d_counts_ptr) if d_counts_ptr else None)
+        if rc:
+            raise LC3Error(rc, "lc3plus_dec_batch_set_frame_counts")
 
     def decode_device(self, d_frames_ptr, in_stride, T, d_pcm_ptr, bps=16, hip_stream=None, sync=False, num_bytes=None, bfi=None):
         """Device-resident variant: raw device pointers.  Without num_bytes no bad-frame flags; with num_bytes ([n_streams, T] host ints, 0 = lost)

@@ -18,14 +18,18 @@ struct __attribute__((aligned(16))) Imd4Lds {
 #define DEC_IMDCT4_EU 4
 #endif
 extern "C" __global__ void __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(DEC_IMDCT4_EU, DEC_IMDCT4_EU)))
-lc3_dec_imdct4_kernel(const lc3d_plan* __restrict__ P, const float* __restrict__ state, const int* __restrict__ rec /* [cs][T][PR_WORDS] */,
-                      const float* __restrict__ ws /* [cs][T][WS_ROW(N)], tiled */, int T, int ncs, float* __restrict__ ov /* [cs][T][OV_ROW(N)] */)
+DEC_RAG(lc3_dec_imdct4_kernel)(const lc3d_plan* __restrict__ P, const float* __restrict__ state, const int* __restrict__ rec /* [cs][T][PR_WORDS] */,
+                      const float* __restrict__ ws /* [cs][T][WS_ROW(N)], tiled */, int T, int ncs, float* __restrict__ ov /* [cs][T][OV_ROW(N)] */ LC3_RAGGED_OPT)
 {
     __shared__ Imd4Lds L;
     const int lane = threadIdx.x;
     const int runs = (T + F4_FR - 1) / F4_FR;
-    const int cs = blockIdx.x / runs, t0 = (blockIdx.x % runs) * F4_FR, nf = imin(F4_FR, T - t0);
+    const int cs = blockIdx.x / runs, t0 = (blockIdx.x % runs) * F4_FR;
     if (cs >= ncs) return;
+    const int nf = imin(F4_FR, DEC_TC(cs / P->channels) - t0);
+#ifdef LC3_DEC_RAGGED
+    if (nf <= 0) return;                              /* a group wholly past the stream's count (lc3_dec_kernels.inc: DEC_TC); one that straddles it holds nf frames */
+#endif
     if (lane < LC3D_PLAN_HEAD_WORDS) L.pc[lane] = ((const int*)P)[lane];
     constexpr int N = F4_N, wsr = WS_ROW(F4_N), ovr = OV_ROW_STD;
     const size_t cf0 = (size_t)cs * T + t0;

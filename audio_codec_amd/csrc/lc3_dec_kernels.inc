@@ -11,14 +11,24 @@
  *   lc3_dec_synth_kernel   one channel-stream per WAVE, frames in order: overlap-add, LTPF synthesis (R/ltpf_decoder.c), output
  * Records, spectra and windowed frames travel through HBM between them. */
 
-#ifdef LC3_BIG
-#define DEC_IMDCT_KERNEL lc3_dec_imdct_kernel_big
-#define DEC_IMDCT_WAVES 3
-#define DEC_SYNTH_NAME lc3_dec_synth_kernel_big
+/* -DLC3_DEC_RAGGED (the four _rag objects): per-stream frame counts (lc3plus_dec_batch_set_frame_counts).  The stateful and the transform kernels once more, named
+ * with _rag, taking cnt [stream] behind their own parameters - the frames of stream s present in this call, clamped to 0 ... T by the ragged plan kernel: where the
+ * dense kernel's frame loop ends at T, theirs ends at cnt[s] (DEC_TC).  Rows and records keep the call's T as their layout. */
+#ifdef LC3_DEC_RAGGED
+#define DEC_RAG(a) a##_rag
+#define DEC_TC(strm_) cnt[strm_]
 #else
-#define DEC_IMDCT_KERNEL lc3_dec_imdct_kernel
+#define DEC_RAG(a) a
+#define DEC_TC(strm_) T
+#endif
+#ifdef LC3_BIG
+#define DEC_IMDCT_KERNEL DEC_RAG(lc3_dec_imdct_kernel_big)
+#define DEC_IMDCT_WAVES 3
+#define DEC_SYNTH_NAME DEC_RAG(lc3_dec_synth_kernel_big)
+#else
+#define DEC_IMDCT_KERNEL DEC_RAG(lc3_dec_imdct_kernel)
 #define DEC_IMDCT_WAVES 4
-#define DEC_SYNTH_NAME lc3_dec_synth_kernel
+#define DEC_SYNTH_NAME DEC_RAG(lc3_dec_synth_kernel)
 #endif
 /* -DLC3_PCM_PLACED (the two plain _plc objects): the synthesis kernel alone, named with _plc, writing each frame at its offset (lc3_plan.h: lc3d_pcm_placed_*) or,
  * where that is invalid, not at all; nothing else of the frame's decoding differs. */
@@ -232,9 +242,12 @@ __device__ __noinline__ const float* dec_ltpf(const lc3d_plan* __restrict__ P, S
  * lost frame gets (count, attenuation, first seed, index of the last good frame of this launch or -1) into its record.
  * Every frame also gets its LTPF configuration (PR_LTPF): the channel's configuration, or with per-frame sizes (0 = lost) that of the frame's
  * size, a lost frame keeping the one of the last good frame (R/dec_lc3_fl.c:146-155) - the channel's configuration before the call at first. */
+/* _rag: a lane's frames end at its stream's count; the lanes of a wave end at different frames, so the wave walks to the largest count among them and a lane
+ * past its own takes no part (it is not `live`: never lost, so the seed loop under __any leaves its seed alone).  The scalars are written back from the
+ * count's frame; with count 0 nothing is written. */
 extern "C" __global__ void __launch_bounds__(WAVE)
-lc3_dec_plc_kernel(const lc3d_plan* __restrict__ P, const lc3d_dchan* __restrict__ chans, const uint16_t* __restrict__ sizes /* [stream][T] or null */,
-                   const lc3d_dchan* __restrict__ dtab, float* __restrict__ state, int* __restrict__ rec, int T, int ncs)
+DEC_RAG(lc3_dec_plc_kernel)(const lc3d_plan* __restrict__ P, const lc3d_dchan* __restrict__ chans, const uint16_t* __restrict__ sizes /* [stream][T] or null */,
+                   const lc3d_dchan* __restrict__ dtab, float* __restrict__ state, int* __restrict__ rec, int T, int ncs LC3_RAGGED_OPT)
 {
     const int cs = blockIdx.x * WAVE + threadIdx.x;
     const bool valid = cs < ncs;
@@ -244,11 +257,21 @@ lc3_dec_plc_kernel(const lc3d_plan* __restrict__ P, const lc3d_dchan* __restrict
     int nbl = valid ? sc[DS_NBLOST] : 0, seed = valid ? sc[DS_PLC_SEED] : 0, prev = valid ? sc[DS_PREV_BFI] : 0, pprev = valid ? sc[DS_PREVPREV_BFI] : 0;
     float ca = valid ? __int_as_float(sc[DS_CUM_ALPHA]) : 1.0f;
     int last_good = -1;
-    for (int t = 0; t < T; t++) {
+#ifdef LC3_DEC_RAGGED
+    const int Tc = valid ? DEC_TC(strm) : 0;
+    int Tw = Tc;
+    for (int o = WAVE / 2; o > 0; o >>= 1) Tw = imax(Tw, __shfl_xor(Tw, o));
+#define PLC_END Tw
+#define PLC_LIVE(t_) (valid && (t_) < Tc)
+#else                                    /* the dense kernel's tokens, so that it stays the code it was */
+#define PLC_END T
+#define PLC_LIVE(t_) valid
+#endif
+    for (int t = 0; t < PLC_END; t++) {
         int* r = rec + ((size_t)(valid ? cs : 0) * T + t) * PR_WORDS;
-        const int bfi = valid ? r[PR_BFI] : 0;
-        const bool lost = valid && bfi == 1;
-        if (valid) {
+        const int bfi = PLC_LIVE(t) ? r[PR_BFI] : 0;
+        const bool lost = PLC_LIVE(t) && bfi == 1;
+        if (PLC_LIVE(t)) {
             const int fsz = sizes ? (int)sizes[(size_t)strm * T + t] : 0;
             if (fsz) { const lc3d_dchan* d = &dtab[fsz / channels + (ch < fsz % channels)]; beta = d->ltpf_beta; beta_idx = d->ltpf_beta_idx; }
             r[PR_LTPF] = __float_as_int(beta); r[PR_LTPF + 1] = beta_idx;
@@ -267,12 +290,19 @@ lc3_dec_plc_kernel(const lc3d_plan* __restrict__ P, const lc3d_dchan* __restrict
                 if (lost) seed = s2;
             }
         }
-        if (valid && !lost) { last_good = t; nbl = 0; ca = 1.0f; }
+        if (PLC_LIVE(t) && !lost) { last_good = t; nbl = 0; ca = 1.0f; }
+#ifdef LC3_DEC_RAGGED
+        if (PLC_LIVE(t)) { pprev = prev; prev = bfi; }
+#else
         pprev = prev; prev = bfi;
+#endif
     }
-    if (valid) { sc[DS_NBLOST] = nbl; sc[DS_CUM_ALPHA] = __float_as_int(ca); sc[DS_PLC_SEED] = seed; sc[DS_PREV_BFI] = prev; sc[DS_PREVPREV_BFI] = pprev; }
+    if (PLC_LIVE(0)) { sc[DS_NBLOST] = nbl; sc[DS_CUM_ALPHA] = __float_as_int(ca); sc[DS_PLC_SEED] = seed; sc[DS_PREV_BFI] = prev; sc[DS_PREVPREV_BFI] = pprev; }
+#undef PLC_LIVE
+#undef PLC_END
 }
 
+#ifndef LC3_DEC_RAGGED
 /* Per-frame sizes and flags in device memory (lc3plus_dec_batch_decode_sizes_device), before the parser: one stream-frame per lane, the rule of
  * lc3d_dec_frame_class (lc3_plan.h).  Writes what the per-frame-size kernels take - the size of every good frame and 0 where the frame is lost, and the
  * lost flag - and marks the frames lost because their size or flag is invalid. */
@@ -331,6 +361,76 @@ lc3_dec_sizes_tail_kernel(const uint16_t* __restrict__ sizes, const uint8_t* __r
         chans[s * channels + c] = d;
     }
 }
+#else /* LC3_DEC_RAGGED */
+/* The three kernels above with per-stream frame counts.  The plan kernels clamp the caller's count into cnt [stream] (the lane of a stream's first frame writes it;
+ * every later kernel of the call reads that copy) and give an absent frame - t >= count - size 0, lost 1, invalid 0 without reading any of its entries: that is
+ * what the per-frame-size parser takes for a frame it stages and reads nothing of, so the parser has no ragged form. */
+extern "C" __global__ void __launch_bounds__(256)
+lc3_dec_plan_sizes_kernel_rag(const int32_t* __restrict__ num_bytes, const uint8_t* __restrict__ bfi /* or null */, const lc3d_dchan* __restrict__ dtab,
+                              int tab_n, int channels, int in_stride, long long n, uint16_t* __restrict__ sizes, uint8_t* __restrict__ lost,
+                              uint8_t* __restrict__ invalid, const int32_t* __restrict__ counts, int T, int32_t* __restrict__ cnt)
+{
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int t = (int)(i % T), c = lc3d_dec_count_clamp(counts[i / T], T);
+    if (t == 0) cnt[i / T] = c;
+    if (t >= c) { sizes[i] = 0; lost[i] = 1; invalid[i] = 0; return; }
+    const int nb = num_bytes[i];
+    const int k = lc3d_dec_frame_class(nb, bfi ? (int)bfi[i] : 0, in_stride, dtab, tab_n, channels);
+    sizes[i] = k == LC3D_FRAME_GOOD ? (uint16_t)nb : (uint16_t)0;
+    lost[i] = k != LC3D_FRAME_GOOD;
+    invalid[i] = k >= LC3D_FRAME_BAD_FLAG;
+}
+extern "C" __global__ void __launch_bounds__(256)
+lc3_dec_plan_packed_kernel_rag(const int32_t* __restrict__ num_bytes, const long long* __restrict__ offs, const uint8_t* __restrict__ bfi /* or null */,
+                               const lc3d_dchan* __restrict__ dtab, int tab_n, int channels, long long cap, int max_bytes, long long n, uint16_t* __restrict__ sizes,
+                               uint8_t* __restrict__ lost, uint8_t* __restrict__ invalid, const int32_t* __restrict__ counts, int T, int32_t* __restrict__ cnt)
+{
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int t = (int)(i % T), c = lc3d_dec_count_clamp(counts[i / T], T);
+    if (t == 0) cnt[i / T] = c;
+    if (t >= c) { sizes[i] = 0; lost[i] = 1; invalid[i] = 0; return; }
+    const int nb = num_bytes[i], fl = bfi ? (int)bfi[i] : 0;
+    const long long off = (fl == 0 && nb != 0) ? offs[i] : 0;        /* a lost frame's offset is not looked at */
+    const int k = lc3d_dec_frame_class_packed(nb, fl, off, cap, max_bytes, dtab, tab_n, channels);
+    sizes[i] = k == LC3D_FRAME_GOOD ? (uint16_t)nb : (uint16_t)0;
+    lost[i] = k != LC3D_FRAME_GOOD;
+    invalid[i] = k >= LC3D_FRAME_BAD_FLAG;
+}
+/* ... and behind the synthesis.  An absent frame's status is LC3D_DEC_ST_ABSENT by store - no kernel of the call has written it, and the caller's buffer is not
+ * initialised - and neither the invalid bit nor the placement bit looks at it; a present frame gets both as in the dense call (plo null: no placement; the marking
+ * of lc3_pcm_placed_mark_kernel is done here, it would OR into the absent frames).  The last good size is searched among the present frames. */
+extern "C" __global__ void __launch_bounds__(256)
+lc3_dec_sizes_tail_kernel_rag(const uint16_t* __restrict__ sizes, const uint8_t* __restrict__ invalid, const lc3d_dchan* __restrict__ dtab, int channels,
+                              int n_streams, int T, lc3d_dchan* __restrict__ chans, uint8_t* __restrict__ status /* [stream][T] or null */,
+                              const int32_t* __restrict__ cnt, const long long* __restrict__ plo /* or null */, long long plcap, int N)
+{
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (long long)n_streams * T) return;
+    const long long s = i / T;
+    const int c = cnt[s];
+    if (status) {
+        if (i % T >= c) status[i] = LC3D_DEC_ST_ABSENT;
+        else {
+            int b = invalid[i] ? LC3D_DEC_ST_INVALID : 0;
+            if (plo && !lc3d_pcm_placed_ok(plo[i], channels, N, plcap)) b |= LC3D_DEC_ST_PCM_PLACE;
+            if (b) status[i] |= (uint8_t)b;
+        }
+    }
+    if (i % T != T - 1) return;
+    const uint16_t* z = sizes + s * T;
+    int t = c - 1;
+    while (t >= 0 && z[t] == 0) t--;
+    if (t < 0) return;
+    const int fsz = z[t];
+    for (int k = 0, off = 0; k < channels; k++) {
+        lc3d_dchan d = dtab[fsz / channels + (k < fsz % channels)];
+        d.in_off = off; off += d.nbytes;
+        chans[s * channels + k] = d;
+    }
+}
+#endif /* LC3_DEC_RAGGED */
 #endif
 
 #ifndef LC3_PCM_PLACED
@@ -341,13 +441,17 @@ lc3_dec_sizes_tail_kernel(const uint16_t* __restrict__ sizes, const uint8_t* __r
 extern "C" __global__ void __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(DEC_IMDCT_WAVES, DEC_IMDCT_WAVES)))
 DEC_IMDCT_KERNEL(const lc3d_plan* __restrict__ P, const float* __restrict__ state, const int* __restrict__ rec /* [cs][T][PR_WORDS] */,
                  const float* __restrict__ ws /* [cs][T][WS_ROW(N)] */, int T, int ncs, float* __restrict__ ov /* [cs][T][OV_ROW(N)] */,
-                 lc3d_dec_trace* __restrict__ trace)
+                 lc3d_dec_trace* __restrict__ trace LC3_RAGGED_OPT)
 {
     __shared__ ImdLds L;
     const int lane = threadIdx.x;
     const int runs = (T + IMDCT_FPW - 1) / IMDCT_FPW;
-    const int cs = blockIdx.x / runs, t0 = (blockIdx.x % runs) * IMDCT_FPW, t1 = imin(T, t0 + IMDCT_FPW);
+    const int cs = blockIdx.x / runs, t0 = (blockIdx.x % runs) * IMDCT_FPW;
     if (cs >= ncs) return;
+    const int t1 = imin(DEC_TC(cs / P->channels), t0 + IMDCT_FPW);
+#ifdef LC3_DEC_RAGGED
+    if (t0 >= t1) return;                            /* a run wholly past the stream's count; one that straddles it stops there (t1) */
+#endif
     if (lane < LC3D_PLAN_HEAD_WORDS) L.pc[lane] = ((const int*)P)[lane];
     LSYNC();
     const int N = DPI(N), Lspec = DPI(ylen), la = DPI(la), h = N >> 1, wsr = WS_ROW(N);
@@ -486,11 +590,15 @@ DEC_IMDCT_KERNEL(const lc3d_plan* __restrict__ P, const float* __restrict__ stat
 extern "C" __global__ void __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(DEC_SYNTH_EU, DEC_SYNTH_EU)))
 DEC_SYNTH_KERNEL(const lc3d_plan* __restrict__ P, float* __restrict__ state,
                  const int* __restrict__ rec, const float* __restrict__ ws, const float* __restrict__ ov /* [cs][T][OV_ROW(N)] */, int T,
-                 void* __restrict__ pcm, int bps, int ncs, uint8_t* __restrict__ status /* [stream][T] or null */, lc3d_dec_trace* __restrict__ trace LC3_PLACED_OPT)
+                 void* __restrict__ pcm, int bps, int ncs, uint8_t* __restrict__ status /* [stream][T] or null */, lc3d_dec_trace* __restrict__ trace LC3_PLACED_OPT LC3_RAGGED_OPT)
 {
     __shared__ SynLds L;
     const int lane = threadIdx.x, cs = blockIdx.x;
     if (cs >= ncs) return;
+    const int Tc = DEC_TC(cs / P->channels);         /* the frames of this stream in the call: T, or with _rag the stream's count */
+#ifdef LC3_DEC_RAGGED
+    if (Tc <= 0) return;                              /* no present frame: the state rows stay untouched */
+#endif
     if (lane < LC3D_PLAN_HEAD_WORDS) L.pc[lane] = ((const int*)P)[lane];
     float* stp = state + (size_t)cs * DST_WORDS;
 #ifndef LC3_BIG
@@ -532,7 +640,7 @@ DEC_SYNTH_KERNEL(const lc3d_plan* __restrict__ P, float* __restrict__ state,
     long long tlast = clock64();
 #endif
     const int lane0 = lane;
-    for (int t = 0; t < T; t++) {
+    for (int t = 0; t < Tc; t++) {
         int lane = lane0;
         asm volatile("" : "+v"(lane));             /* keeps per-lane address arithmetic inside the iteration instead of in spilled registers */
 #ifdef LC3_STAGE_TIMING
@@ -554,7 +662,7 @@ DEC_SYNTH_KERNEL(const lc3d_plan* __restrict__ P, float* __restrict__ state,
         LSYNC();
         const int bfi = uni(L.isc[PR_BFI]);
         if (bfi != 1) last_good = t;
-        if (t + 1 < T) PREFETCH(t + 1);
+        if (t + 1 < Tc) PREFETCH(t + 1);
         DTICK(0);
         if (tr) for (int i = lane; i < N; i += WAVE) tr->x_imdct[i] = L.A[i];
         /* ---- LTPF synthesis R/ltpf_decoder.c:13-316 ---- */

@@ -73,6 +73,7 @@ __device__ __forceinline__ void f4_dft240x4(float* x, const lc3d_plan* __restric
     LSYNC();
 }
 
+#ifndef LC3_TU_DEC_RAGGED         /* the decoder's ragged object takes the transform above and no encoder kernel */
 #ifndef F4_WAVES
 #define F4_WAVES 4
 #endif
@@ -243,3 +244,4 @@ lc3_enc_front4_kernel(
         }
     }
 }
+#endif /* !LC3_TU_DEC_RAGGED */

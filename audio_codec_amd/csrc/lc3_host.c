@@ -1385,6 +1385,7 @@ struct lc3plus_dec_batch {
     uint16_t* eff; uint8_t* lost; int* sz; size_t plan_cap;          /* per-frame sizes: host buffers of dec_plan_sizes, grown as needed */
     int dry;                         /* as lc3plus_batch.dry: the call returns behind its checks */
     int placed;                      /* as lc3plus_batch.placed (lc3plus_dec_batch_set_pcm_placement) */
+    int ragged;                      /* lc3plus_dec_batch_set_frame_counts is on: only the calls with sizes in device memory decode, the others refuse */
 };
 
 /* the geometry of a decoder batch, or the error create gives for it; no device */
@@ -1499,6 +1500,7 @@ static LC3_Error dec_batch_decode(lc3plus_dec_batch* b, const void* frames, int 
     if (!b || !frames || !pcm) return LC3_NULL_ERROR;
     if (!pcm_format_ok(bps)) return LC3_ERROR;
     if (placed_refuses(b->placed, pcm_on_device, bps, traces)) return LC3_ERROR;
+    if (b->ragged) return LC3_ERROR;                                 /* per-stream frame counts are read by the device-size calls alone; nothing is touched here */
     if (traces && !pcm_format_plain(bps)) return LC3_ERROR;          /* the traced call writes the integer formats in the default layout only */
     if (n_frames <= 0) return LC3_ERROR;
     if (dec_refresh(b)) return LC3_ERROR;
@@ -1513,6 +1515,7 @@ LC3_Error lc3plus_dec_batch_decode_sizes(lc3plus_dec_batch* b, const void* frame
     if (!b || !frames || !pcm || !num_bytes) return LC3_NULL_ERROR;
     if (!pcm_format_ok(bps)) return LC3_ERROR;
     if (placed_refuses(b->placed, pcm_on_device, bps, NULL)) return LC3_ERROR;
+    if (b->ragged) return LC3_ERROR;                                 /* as in dec_batch_decode */
     if (n_frames <= 0) return LC3_ERROR;
     if (dec_refresh(b)) return LC3_ERROR;
     const size_t n = (size_t)b->n_streams * n_frames;
@@ -1707,6 +1710,20 @@ LC3_Error lc3plus_dec_batch_set_pcm_placement(lc3plus_dec_batch* b, const int64_
     if (capacity < 0) return LC3_ERROR;
     if (lc3hip_dec_set_pcm_placement(b->dev, (const long long*)offsets, (long long)capacity)) return LC3_ERROR;
     b->placed = offsets != NULL;
+    return LC3_OK;
+}
+LC3_Error lc3plus_dec_batch_set_frame_counts(lc3plus_dec_batch* b, const int32_t* counts)
+{
+    if (!b) return LC3_NULL_ERROR;
+    if (lc3hip_dec_set_frame_counts(b->dev, counts)) return LC3_ERROR;
+    b->ragged = counts != NULL;
+    return LC3_OK;
+}
+LC3_Error lc3plus_dec_plan_counts(const int32_t* counts, int n_streams, int n_frames, int32_t* effective)
+{
+    if (n_streams < 0 || n_frames <= 0) return LC3_ERROR;
+    if (n_streams > 0 && (!counts || !effective)) return LC3_NULL_ERROR;
+    for (int s = 0; s < n_streams; s++) effective[s] = lc3d_dec_count_clamp(counts[s], n_frames);
     return LC3_OK;
 }
 LC3_Error lc3plus_dec_batch_set_input_ready(lc3plus_dec_batch* b, int ready)

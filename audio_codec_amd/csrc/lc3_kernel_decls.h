@@ -27,6 +27,8 @@
 #define LC3_OW_ARGS_PK_1 , const long long* __restrict__ poff /* [stream][dT] byte offset of each stream-frame in out, -1: not written */
 /* the two parameters every placed kernel (_plc: lc3_plan.h lc3d_pcm_placed_*, lc3_kernels.hip pcm_placed_load) takes behind those of its dense twin */
 #define LC3_PLACED_ARGS , const long long* __restrict__ plo /* [stream][T] element offset of each stream-frame's PCM */, long long plcap /* length of the PCM buffer, elements */
+/* the parameter every ragged decoder kernel (_rag: lc3_dec_kernels.inc DEC_TC) takes behind those of its dense twin, behind the placed ones where it has both */
+#define LC3_RAGGED_ARGS , const int32_t* __restrict__ cnt /* [stream] frames of each stream present in this call, clamped to 0 ... T */
 #define LC3_OW_OPT_(G, var, vbw, pk) G##VAR_##var G##VBW_##vbw G##PK_##pk
 #define LC3_OW_OPT(G, var, vbw, pk) LC3_OW_OPT_(G, var, vbw, pk)
 /* The variants: X(name, large layout, var, vbw, pk), each once more named name_fmt for the PCM formats beyond 16 / 24 / 32, name_wire for the wire sample types and name_plc for placed PCM.  There is no large-layout kernel
@@ -139,6 +141,23 @@ __global__ void lc3_dec_sizes_tail_kernel(const uint16_t* __restrict__ sizes, co
     const float* __restrict__ ov, int T, void* __restrict__ pcm, int bps, int ncs, uint8_t* __restrict__ status, lc3d_dec_trace* __restrict__ trace
 __global__ void lc3_dec_synth_kernel(LC3_DEC_SYNTH_ARGS), lc3_dec_synth_kernel_big(LC3_DEC_SYNTH_ARGS), lc3_dec_synth_kernel_plc(LC3_DEC_SYNTH_ARGS LC3_PLACED_ARGS),
     lc3_dec_synth_kernel_big_plc(LC3_DEC_SYNTH_ARGS LC3_PLACED_ARGS);
+/* the ragged forms (per-stream frame counts, lc3plus_dec_batch_set_frame_counts), in objects of their own; the parser has none (a frame of size 0 is read by no parser) */
+__global__ void lc3_dec_imdct4_kernel_rag(const lc3d_plan* __restrict__ P, const float* __restrict__ state, const int* __restrict__ rec, const float* __restrict__ ws, int T,
+    int ncs, float* __restrict__ ov LC3_RAGGED_ARGS);
+__global__ void lc3_dec_imdct_kernel_rag(LC3_DEC_IMDCT_ARGS LC3_RAGGED_ARGS), lc3_dec_imdct_kernel_big_rag(LC3_DEC_IMDCT_ARGS LC3_RAGGED_ARGS);
+__global__ void lc3_dec_plan_packed_kernel_rag(const int32_t* __restrict__ num_bytes, const long long* __restrict__ offs, const uint8_t* __restrict__ bfi,
+    const lc3d_dchan* __restrict__ dtab, int tab_n, int channels, long long cap, int max_bytes, long long n, uint16_t* __restrict__ sizes, uint8_t* __restrict__ lost,
+    uint8_t* __restrict__ invalid, const int32_t* __restrict__ counts, int T, int32_t* __restrict__ cnt);
+__global__ void lc3_dec_plan_sizes_kernel_rag(const int32_t* __restrict__ num_bytes, const uint8_t* __restrict__ bfi, const lc3d_dchan* __restrict__ dtab, int tab_n,
+    int channels, int in_stride, long long n, uint16_t* __restrict__ sizes, uint8_t* __restrict__ lost, uint8_t* __restrict__ invalid,
+    const int32_t* __restrict__ counts, int T, int32_t* __restrict__ cnt);
+__global__ void lc3_dec_plc_kernel_rag(const lc3d_plan* __restrict__ P, const lc3d_dchan* __restrict__ chans, const uint16_t* __restrict__ sizes,
+    const lc3d_dchan* __restrict__ dtab, float* __restrict__ state, int* __restrict__ rec, int T, int ncs LC3_RAGGED_ARGS);
+__global__ void lc3_dec_sizes_tail_kernel_rag(const uint16_t* __restrict__ sizes, const uint8_t* __restrict__ invalid, const lc3d_dchan* __restrict__ dtab, int channels,
+    int n_streams, int T, lc3d_dchan* __restrict__ chans, uint8_t* __restrict__ status, const int32_t* __restrict__ cnt, const long long* __restrict__ plo,
+    long long plcap, int N);
+__global__ void lc3_dec_synth_kernel_rag(LC3_DEC_SYNTH_ARGS LC3_RAGGED_ARGS), lc3_dec_synth_kernel_big_rag(LC3_DEC_SYNTH_ARGS LC3_RAGGED_ARGS),
+    lc3_dec_synth_kernel_rag_plc(LC3_DEC_SYNTH_ARGS LC3_PLACED_ARGS LC3_RAGGED_ARGS), lc3_dec_synth_kernel_big_rag_plc(LC3_DEC_SYNTH_ARGS LC3_PLACED_ARGS LC3_RAGGED_ARGS);
 /* ---- stream lifecycle, per-frame plans, packed offsets, test hook (lc3_util_kernels.inc) ---- */
 __global__ void lc3_enc_plan_rates_kernel(lc3d_rate_rule r, const int32_t* __restrict__ rates, const int32_t* __restrict__ bws, int T, int n_streams,
     int4* __restrict__ carry, const lc3d_chan* __restrict__ seed, uint16_t* __restrict__ fsz, uint16_t* __restrict__ bwf, int32_t* __restrict__ num_bytes,

@@ -40,7 +40,9 @@
  * and 96 kHz / 5 ms (N = 480, MDCT memory 360), 17 KB per wave, 2 waves per SIMD. */
 /* What this object is, from the five -D switches (csrc/Makefile: one object per combination).  Every object holds its one-wave encode kernel
  * (lc3_enc_wave.inc); three kinds hold more: */
-#if !defined(LC3_ENC_VAR) && !defined(LC3_ENC_VBW) && !defined(LC3_ENC_PACKED) && !defined(LC3_PCM_FMT)
+#ifdef LC3_DEC_RAGGED
+#define LC3_TU_DEC_RAGGED 1     /* the four _rag objects (with -DLC3_BIG and / or the _plc switches): the decoder's ragged kernels and nothing else, no one-wave kernel either */
+#elif !defined(LC3_ENC_VAR) && !defined(LC3_ENC_VBW) && !defined(LC3_ENC_PACKED) && !defined(LC3_PCM_FMT)
 #define LC3_TU_MAIN 1           /* the plain object (or with -DLC3_BIG the large-layout one): every other kernel of the library */
 #elif defined(LC3_ENC_VBW) && !defined(LC3_ENC_VAR) && !defined(LC3_ENC_PACKED) && !defined(LC3_PCM_FMT)
 #define LC3_TU_VBW_SHAPE 1      /* the per-frame-bandwidth object: the two shape kernels that read the bandwidth words */
@@ -278,6 +280,11 @@ template <bool QW> __device__ __forceinline__ void pcm_placed_load(const void* _
 }
 #else
 #define LC3_PLACED_OPT
+#endif
+#ifdef LC3_DEC_RAGGED
+#define LC3_RAGGED_OPT LC3_RAGGED_ARGS
+#else
+#define LC3_RAGGED_OPT
 #endif
 
 /* ------------------------------------------------------------------------------------------------ */
@@ -2873,7 +2880,19 @@ template <class LdsT> STAGE void st_bitstream(const lc3d_plan* __restrict__ P, c
 #else
 #define ENC_PCM_FMT 0
 #endif
+#ifdef LC3_TU_DEC_RAGGED
+/* per-stream frame counts: lc3_dec_{plan_sizes,plan_packed,plc,imdct,synth,sizes_tail}_kernel_rag and lc3_dec_imdct4_kernel_rag in the plain object, the imdct and
+ * synth kernels _big_rag in the large-layout one, the synthesis kernel alone (_rag_plc, _big_rag_plc) in the two placed ones */
+#if !defined(LC3_BIG) && !defined(LC3_PCM_PLACED)
+#include "lc3_enc_front4.inc"      /* f4_dft240x4 alone */
+#endif
+#include "lc3_dec_kernels.inc"
+#if !defined(LC3_BIG) && !defined(LC3_PCM_PLACED)
+#include "lc3_dec_imdct4.inc"
+#endif
+#else
 #include "lc3_enc_wave.inc"       /* KERNEL_FN, or KERNEL_FN with _fmt */
+#endif
 #ifdef LC3_TU_VBW_SHAPE
 #include "lc3_enc_rate.inc"        /* lc3_enc_shape_kernel_vbw */
 #include "lc3_enc_shapel.inc"      /* lc3_enc_shape_lane_kernel_vbw */

@@ -147,6 +147,11 @@ static inline LC3D_HD int lc3d_dec_frame_class_packed(int nb, int bfi, long long
     if (nb < 0 || nb > max_bytes || off < 0 || off > cap - nb) return LC3D_FRAME_BAD_SIZE;
     return lc3d_dec_frame_class(nb, 0, max_bytes, tab, tab_n, channels);
 }
+/* Per-stream frame counts (lc3plus_dec_batch_set_frame_counts): of a call's n_frames, stream s holds the first min(max(counts[s], 0), n_frames); the frames behind
+ * them are absent - not looked at, not read, neither decoded nor concealed, no PCM written, status exactly LC3D_DEC_ST_ABSENT.  On the host in
+ * lc3plus_dec_plan_counts, on the device in the ragged plan kernels (lc3_dec_kernels.inc). */
+#define LC3D_DEC_ST_ABSENT 8
+static inline LC3D_HD int lc3d_dec_count_clamp(int count, int n_frames) { return count < 0 ? 0 : count > n_frames ? n_frames : count; }
 /* Packed encoder output (lc3plus_enc_batch_encode_packed): a frame of nb bytes at offset off is written where it fits the caller's capacity; one that does
  * not is still encoded, but its bytes are not written and it gets LC3D_ENC_FL_PACK_CAP.  The host hook lc3plus_plan_packed and lc3_pack_offsets_kernel. */
 #define LC3D_ENC_FL_PACK_CAP 8

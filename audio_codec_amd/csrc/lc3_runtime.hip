@@ -1165,6 +1165,7 @@ struct lc3hip_dctx {
     /* lc3hip_dec_set_input_ready: the parse kernel of a call runs on a stream of its own beside the transform and synthesis of the call before; a
      * second set of hand-over buffers (records, spectrum rows), alternating */
     const long long* plo; long long plcap;         /* lc3hip_dec_set_pcm_placement */
+    const int32_t* counts; int32_t* d_cnt;         /* lc3hip_dec_set_frame_counts: the caller's per-stream frame counts (null: off), and the clamped copy [n_streams] the ragged kernels of a call read */
     int input_ready, set; int* d_recx[DEC_SETS - 1]; float* d_wsx[DEC_SETS - 1]; size_t handx_cap; hipStream_t s_par, s_plc; hipEvent_t ev_par[DEC_SETS], ev_free[DEC_SETS], ev_plc; int free_armed[DEC_SETS];
     /* the end of the last ordered call (bad-frame flags, per-frame sizes, status, host pointers) under the promise: the next parse-ahead waits for it */
     hipEvent_t ev_ord; int ord_pending;
@@ -1197,6 +1198,7 @@ extern "C" int lc3hip_dec_create(void** out_ctx, const lc3d_plan* plan, const fl
     HIPCHK_OR(hipMemcpy(c->d_plan, plan, sizeof(lc3d_plan), hipMemcpyHostToDevice), lc3hip_dec_destroy(c));
     HIPCHK_OR(hipMalloc((void**)&c->d_chans, sizeof(lc3d_dchan) * c->ncs), lc3hip_dec_destroy(c));
     HIPCHK_OR(hipMalloc((void**)&c->d_state, sizeof(float) * DST_WORDS * (size_t)c->ncs), lc3hip_dec_destroy(c));
+    HIPCHK_OR(hipMalloc((void**)&c->d_cnt, sizeof(int32_t) * (size_t)n_streams), lc3hip_dec_destroy(c));
     if (ss_init(&c->ss, c->device, c->d_state, DST_WORDS, c->ncs, tmpl)) { lc3hip_dec_destroy(c); return 1; }
     HIPCHK_OR(hipStreamCreate(&c->stream), lc3hip_dec_destroy(c));
     HIPCHK_OR(hipEventCreate(&c->ev0), lc3hip_dec_destroy(c)); HIPCHK_OR(hipEventCreate(&c->ev1), lc3hip_dec_destroy(c));
@@ -1253,6 +1255,8 @@ static int dec_decode(lc3hip_dctx* c, const void* frames, int frames_on_device, 
 {
     HIPCHK(hipSetDevice(c->device));
     if (c->plo && (!pcm_on_device || trace_host || (bps & LC3D_PCM_CHANNEL_MAJOR))) return 1;      /* placed PCM: device-pointer calls without traces (the host refuses the others) */
+    const int32_t* cnt = c->counts ? c->d_cnt : nullptr;           /* per-stream frame counts: the _rag kernels below, every one behind the plan kernel that clamps them into d_cnt */
+    if (cnt && !nb_dev) return 1;                                   /* ... on the calls with sizes in device memory only (the host refuses the others) */
     hipStream_t s = hip_stream ? (hipStream_t)hip_stream : c->stream;
     if (c->ss.done_armed) HIPCHK(hipStreamWaitEvent(s, c->ss.ev_done, 0));      /* behind the last stream-lifecycle call, whichever stream it was queued on */
     const size_t in_bytes = (size_t)c->n_streams * n_frames * in_stride;
@@ -1362,6 +1366,11 @@ static int dec_decode(lc3hip_dctx* c, const void* frames, int frames_on_device, 
     HIPCHK(hipEventRecord(c->ev0, s));
     if (nb_dev) {
         const long long n = (long long)c->n_streams * n_frames;
+        if (cnt && offs_dev) hipLaunchKernelGGL(lc3_dec_plan_packed_kernel_rag, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, nb_dev, offs_dev, bfi_dev, c->d_tab,
+                                                c->tab_n, c->channels, cap, in_stride, n, c->d_sizes, c->d_bfi, c->d_inval, c->counts, n_frames, c->d_cnt);
+        else if (cnt) hipLaunchKernelGGL(lc3_dec_plan_sizes_kernel_rag, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, nb_dev, bfi_dev, c->d_tab, c->tab_n, c->channels,
+                                         in_stride, n, c->d_sizes, c->d_bfi, c->d_inval, c->counts, n_frames, c->d_cnt);
+        else
         if (offs_dev) hipLaunchKernelGGL(lc3_dec_plan_packed_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, nb_dev, offs_dev, bfi_dev, c->d_tab, c->tab_n,
                                          c->channels, cap, in_stride, n, c->d_sizes, c->d_bfi, c->d_inval);
         else
@@ -1407,10 +1416,27 @@ static int dec_decode(lc3hip_dctx* c, const void* frames, int frames_on_device, 
         HIPCHK(hipEventRecord(c->ev_par[c->set], sp)); HIPCHK(hipStreamWaitEvent(spl, c->ev_par[c->set], 0));
     } else if (ahead) { HIPCHK(hipEventRecord(c->ev_par[c->set], sp)); HIPCHK(hipStreamWaitEvent(s, c->ev_par[c->set], 0)); }
     else if (c->s_plc) HIPCHK(hipStreamWaitEvent(s, c->ev_plc, 0));      /* an ordered call behind ahead calls: the bookkeeping is a chain (the event of the last one, if any: waiting on a fresh event is a no-op) */
+    if (cnt) hipLaunchKernelGGL(lc3_dec_plc_kernel_rag, dim3((unsigned)((c->ncs + WAVE - 1) / WAVE)), dim3(WAVE), 0, spl, c->d_plan, c->d_chans, dsizes, c->d_tab, c->d_state, rec_w, n_frames, c->ncs, cnt);
+    else
     hipLaunchKernelGGL(lc3_dec_plc_kernel, dim3((unsigned)((c->ncs + WAVE - 1) / WAVE)), dim3(WAVE), 0, spl, c->d_plan, c->d_chans, dsizes, c->d_tab, c->d_state, rec_w, n_frames, c->ncs);
     HIPCHK(hipGetLastError());
     if (spl != s) { HIPCHK(hipEventRecord(c->ev_plc, spl)); HIPCHK(hipStreamWaitEvent(s, c->ev_plc, 0)); }
     const unsigned ncf = (unsigned)((size_t)c->ncs * ((n_frames + IMDCT_FPW - 1) / IMDCT_FPW));     /* runs of IMDCT_FPW frames */
+    if (cnt) {
+        /* the same grids as the dense call: a wave whose run of frames lies past its stream's count returns at once, a stream without a present frame before touching its state */
+        if (c->big) {
+            hipLaunchKernelGGL(lc3_dec_imdct_kernel_big_rag, dim3(ncf), dim3(WAVE), 0, s, c->d_plan, c->d_state, rec_w, ws_w, n_frames, c->ncs, c->d_ov, dtr, cnt);
+            if (c->plo) hipLaunchKernelGGL(lc3_dec_synth_kernel_big_rag_plc, dim3(c->ncs), dim3(WAVE), 0, s, c->d_plan, c->d_state, rec_w, ws_w, c->d_ov, n_frames, dpcm, bps, c->ncs, dst, dtr, c->plo, c->plcap, cnt);
+            else hipLaunchKernelGGL(lc3_dec_synth_kernel_big_rag, dim3(c->ncs), dim3(WAVE), 0, s, c->d_plan, c->d_state, rec_w, ws_w, c->d_ov, n_frames, dpcm, bps, c->ncs, dst, dtr, cnt);
+        } else {
+            if (c->opt.dec_imdct4 && c->N == 480)
+                hipLaunchKernelGGL(lc3_dec_imdct4_kernel_rag, dim3((unsigned)((size_t)c->ncs * ((n_frames + 3) / 4))), dim3(WAVE), 0, s, c->d_plan, c->d_state, rec_w, ws_w, n_frames, c->ncs, c->d_ov, cnt);
+            else
+            hipLaunchKernelGGL(lc3_dec_imdct_kernel_rag, dim3(ncf), dim3(WAVE), 0, s, c->d_plan, c->d_state, rec_w, ws_w, n_frames, c->ncs, c->d_ov, dtr, cnt);
+            if (c->plo) hipLaunchKernelGGL(lc3_dec_synth_kernel_rag_plc, dim3(c->ncs), dim3(WAVE), 0, s, c->d_plan, c->d_state, rec_w, ws_w, c->d_ov, n_frames, dpcm, bps, c->ncs, dst, dtr, c->plo, c->plcap, cnt);
+            else hipLaunchKernelGGL(lc3_dec_synth_kernel_rag, dim3(c->ncs), dim3(WAVE), 0, s, c->d_plan, c->d_state, rec_w, ws_w, c->d_ov, n_frames, dpcm, bps, c->ncs, dst, dtr, cnt);
+        }
+    } else
     if (c->big) {
         hipLaunchKernelGGL(lc3_dec_imdct_kernel_big, dim3(ncf), dim3(WAVE), 0, s, c->d_plan, c->d_state, rec_w, ws_w, n_frames, c->ncs, c->d_ov, dtr);
         if (c->plo) hipLaunchKernelGGL(lc3_dec_synth_kernel_big_plc, dim3(c->ncs), dim3(WAVE), 0, s, c->d_plan, c->d_state, rec_w, ws_w, c->d_ov, n_frames, dpcm, bps, c->ncs, dst, dtr, c->plo, c->plcap);
@@ -1427,10 +1453,16 @@ static int dec_decode(lc3hip_dctx* c, const void* frames, int frames_on_device, 
     HIPCHK(hipGetLastError());
     if (nb_dev) {                                                    /* behind the synthesis: the status bits and the stream's configuration for the next call */
         const long long n = (long long)c->n_streams * n_frames;
+        if (cnt) {                                                   /* the ragged tail also marks the invalid placements, among the present frames only */
+            hipLaunchKernelGGL(lc3_dec_sizes_tail_kernel_rag, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, c->d_sizes, c->d_inval, c->d_tab, c->channels,
+                               c->n_streams, n_frames, c->d_chans, dst, cnt, c->plo, c->plcap, c->N);
+            HIPCHK(hipGetLastError());
+        } else {
         hipLaunchKernelGGL(lc3_dec_sizes_tail_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, c->d_sizes, c->d_inval, c->d_tab, c->channels,
                            c->n_streams, n_frames, c->d_chans, dst);
         HIPCHK(hipGetLastError());
-        if (placed_mark(c->plo, c->plcap, c->channels, c->N, n, dst, LC3D_DEC_ST_PCM_PLACE, s)) return 1;
+        }
+        if (!cnt && placed_mark(c->plo, c->plcap, c->channels, c->N, n, dst, LC3D_DEC_ST_PCM_PLACE, s)) return 1;
     }
     if (ahead) { HIPCHK(hipEventRecord(c->ev_free[c->set], s)); c->free_armed[c->set] = 1; c->set = (c->set + 1) % DEC_SETS; }
     else if (c->s_par) { HIPCHK(hipEventRecord(c->ev_free[0], s)); c->free_armed[0] = 1; }      /* an ordered call reads the first set: a later parse-ahead into it waits for this one */
@@ -1494,6 +1526,13 @@ extern "C" int lc3hip_dec_set_pcm_placement(void* ctx, const long long* offsets_
     c->plo = offsets_dev; c->plcap = offsets_dev ? capacity : 0;
     return 0;
 }
+extern "C" int lc3hip_dec_set_frame_counts(void* ctx, const int32_t* counts_dev)
+{
+    lc3hip_dctx* c = (lc3hip_dctx*)ctx;
+    if (!c) return 1;
+    c->counts = counts_dev;
+    return 0;
+}
 extern "C" int lc3hip_dec_set_input_ready(void* ctx, int ready)
 {
     lc3hip_dctx* c = (lc3hip_dctx*)ctx;
@@ -1530,7 +1569,7 @@ extern "C" int lc3hip_dec_destroy(void* ctx)
     if (!c) return 0;
     hipSetDevice(c->device);
     hipDeviceSynchronize();
-    void* bufs[] = {c->d_plan, c->d_chans, c->d_state, c->d_in, c->d_pcm, c->d_bfi, c->d_trace, c->d_status, c->d_rec, c->d_ws, c->d_ov, c->d_tab, c->d_sizes, c->d_inval};
+    void* bufs[] = {c->d_plan, c->d_chans, c->d_state, c->d_in, c->d_pcm, c->d_bfi, c->d_trace, c->d_status, c->d_rec, c->d_ws, c->d_ov, c->d_tab, c->d_sizes, c->d_inval, c->d_cnt};
     for (int i = 0; i < DEC_SETS - 1; i++) { if (c->d_recx[i]) hipFree(c->d_recx[i]); if (c->d_wsx[i]) hipFree(c->d_wsx[i]); }
     if (c->s_par) { hipStreamDestroy(c->s_par); for (int i = 0; i < DEC_SETS; i++) { hipEventDestroy(c->ev_par[i]); hipEventDestroy(c->ev_free[i]); } hipStreamDestroy(c->s_plc); hipEventDestroy(c->ev_plc); hipEventDestroy(c->ev_ord); }
     for (void* p : bufs) if (p) hipFree(p);

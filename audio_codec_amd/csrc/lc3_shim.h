@@ -96,6 +96,10 @@ int   lc3hip_dec_stream_state(void* ctx, int mode, const int* streams, int n, co
  * and the channel-major layout while it is on.  Queues nothing, waits for nothing. */
 int   lc3hip_set_pcm_placement(void* ctx, const long long* offsets_dev, long long capacity);
 int   lc3hip_dec_set_pcm_placement(void* ctx, const long long* offsets_dev, long long capacity);
+/* per-stream frame counts (include/lc3plus_batch.h: lc3plus_dec_batch_set_frame_counts; lc3_plan.h: lc3d_dec_count_clamp): counts_dev [n_streams] in device memory,
+ * or null: off.  Kept in the context; read on the device by lc3hip_dec_decode_dsizes and lc3hip_dec_decode_packed, which then launch the ragged kernels;
+ * lc3hip_dec_decode fails while it is on (the host refuses first).  Queues nothing, waits for nothing. */
+int   lc3hip_dec_set_frame_counts(void* ctx, const int32_t* counts_dev);
 int   lc3hip_dec_set_input_ready(void* ctx, int ready);          /* see lc3plus_dec_batch_set_input_ready (include/lc3plus_batch.h) */
 int   lc3hip_set_input_ready(void* ctx, int ready);              /* see lc3plus_enc_batch_set_input_ready (include/lc3plus_batch.h) */
 int   lc3hip_last_status(void* ctx, uint8_t* status_host, int n);        /* LC3D_ENC_ST_* bits per channel-frame of the last call; returns the count copied */

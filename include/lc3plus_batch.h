@@ -350,6 +350,7 @@ LC3_Error lc3plus_dec_batch_decode_sizes(lc3plus_dec_batch* batch, const void* f
  *   bfi       : [n_streams][n_frames] flags, or NULL
  *   pcm       : [n_streams][n_frames][channels][output_samples], int16_t (bps 16) or int32_t (24/32)
  *   status    : [n_streams][n_frames], or NULL: bit 0 the frame was concealed, bit 1 it was concealed because its size or flag was invalid
+ *               (bit 2: placed PCM, the frame's offset is invalid; bit 3: the frame is absent, lc3plus_dec_batch_set_frame_counts below)
  * The call is queued on hip_stream (NULL = the batch's own stream) in order with the batch's other calls there, and returns at once when sync = 0: it
  * does not wait, copy synchronously or read anything back.  The arguments are checked on the host before any work - NULL frames, pcm or num_bytes:
  * LC3_NULL_ERROR; a bad bps, n_frames <= 0 or in_stride <= 0: LC3_ERROR; nothing is queued then.  The frame rule of decode_sizes() holds per stream,
@@ -403,6 +404,28 @@ LC3_Error lc3plus_dec_batch_import_streams(lc3plus_dec_batch* batch, const int* 
 LC3_Error lc3plus_dec_batch_set_input_ready(lc3plus_dec_batch* batch, int ready);
 /* Placed PCM for the decoder's output ("Placed PCM" above): offsets NULL = off. */
 LC3_Error lc3plus_dec_batch_set_pcm_placement(lc3plus_dec_batch* batch, const int64_t* offsets, int64_t capacity);
+/* Per-stream frame counts for the decoder (jitter: at one tick a stream has three frames waiting, another one, a third none).
+ *   counts : device pointer to int32 [n_streams], or NULL = off (the default; every call then behaves as without this function)
+ * The setter only records the pointer: it queues nothing and waits for nothing (LC3_NULL_ERROR for a NULL batch).  Counts are configuration, not state:
+ * get_state / set_state and the stream blobs do not carry them.  Through lc3plus_dec_sharded_shard() they apply to that shard, with its local stream indices.
+ * While counts are set they apply to decode_sizes_device() and decode_packed(); the array is read on the device when the call's kernels run, so a kernel or
+ * copy queued earlier on the same hip_stream may produce it (these calls are ordered; no promise is involved).  Every other decode call of the batch -
+ * decode(), decode_sizes(), the traced call - returns LC3_ERROR, queues nothing and leaves the batch unchanged; the sharded lc3plus_dec_sharded_decode() and
+ * _decode_device() make that check for all shards before any shard is touched.
+ *
+ * The rule.  With c = min(max(counts[s], 0), n_frames) for a call of n_frames, of stream s
+ *   frames t < c are PRESENT: exactly as in the same call without counts - the frame rule with its carry of the last good size and the invalid entries,
+ *     concealment, placed PCM with its status bit 2, every PCM format word and layout (LC3PLUS_PCM_CHANNEL_MAJOR: the channel distance stays n_frames);
+ *   frames t >= c are ABSENT: their num_bytes, bfi, offsets and placement entries are not looked at, their frame bytes are never read, they are neither
+ *     decoded nor concealed, no byte of their PCM is written, and status[s][t] (where status is given) is exactly 8 - bit 3, "absent", and no other bit.
+ * After the call the stream's state (overlap memory, LTPF histories, concealment words, last good spectrum) is the state after its c present frames, and its
+ * configured size that of its last good present frame, or unchanged where there is none; with c = 0 both are bit for bit what they were.  So a sequence of
+ * ragged calls gives each stream the PCM and status that one dense sequence of that stream's present frames gives, and counts that all equal n_frames give
+ * the bytes, status and state of the call without counts.  Only a tail can be absent: a count skips no frame in the middle of a call. */
+LC3_Error lc3plus_dec_batch_set_frame_counts(lc3plus_dec_batch* batch, const int32_t* counts);
+/* The clamp of that rule on the host alone, no device: effective[s] = min(max(counts[s], 0), n_frames).  LC3_NULL_ERROR for a NULL array with n_streams > 0,
+ * LC3_ERROR for n_streams < 0 or n_frames <= 0. */
+LC3_Error lc3plus_dec_plan_counts(const int32_t* counts, int n_streams, int n_frames, int32_t* effective);
 
 /* ---- Sharded batches: one call drives encoders or decoders on several GPUs ------------------------------------------------------------------
  * Streams are independent, so a sharded batch is n_devices ordinary batches, each owning a contiguous block of the n_streams streams on a device of its

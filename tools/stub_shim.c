@@ -10,12 +10,13 @@
 #include <string.h>
 #include "../audio_codec_amd/csrc/lc3_shim.h"
 
-enum { STUB_ENCODE = 1, STUB_DECODE = 2, STUB_GET_STATE = 3, STUB_SET_STATE = 4, STUB_WAIT = 5, STUB_PLACEMENT = 6 };
+enum { STUB_ENCODE = 1, STUB_DECODE = 2, STUB_GET_STATE = 3, STUB_SET_STATE = 4, STUB_WAIT = 5, STUB_PLACEMENT = 6, STUB_COUNTS = 7 };
 #define STUB_STATE_BYTES 32          /* per channel-stream */
 
 /* p: encode pcm, out; decode frames, pcm, status, bfi; state: the host pointer.  a / b: the first two words and the last one of the two per-frame arrays
  * the call was given (encode: frame sizes, bandwidths in force; decode: sizes, loss flags), -1 where there is none.  sync / on_device as passed.
- * STUB_PLACEMENT (lc3hip_set_pcm_placement, lc3hip_dec_set_pcm_placement): p[0] the offsets pointer, a[0] the capacity. */
+ * STUB_PLACEMENT (lc3hip_set_pcm_placement, lc3hip_dec_set_pcm_placement): p[0] the offsets pointer, a[0] the capacity.
+ * STUB_COUNTS (lc3hip_dec_set_frame_counts): p[0] the counts pointer. */
 typedef struct {
     int32_t ctx, kind, dec, n_frames, stride, fmt, on_device, sync;
     uint64_t p[4];
@@ -97,6 +98,14 @@ static int stub_placement(void* ctx, const long long* offsets_dev, long long cap
 }
 int lc3hip_set_pcm_placement(void* ctx, const long long* offsets_dev, long long capacity) { return stub_placement(ctx, offsets_dev, capacity); }
 int lc3hip_dec_set_pcm_placement(void* ctx, const long long* offsets_dev, long long capacity) { return stub_placement(ctx, offsets_dev, capacity); }
+int lc3hip_dec_set_frame_counts(void* ctx, const int32_t* counts_dev)
+{
+    lc3stub_rec r; memset(&r, 0, sizeof r);
+    r.kind = STUB_COUNTS; r.p[0] = (uint64_t)(uintptr_t)counts_dev;
+    r.a[0] = r.a[1] = r.a[2] = r.b[0] = r.b[1] = r.b[2] = -1;
+    (void)stub_append((const stub_ctx*)ctx, &r);
+    return 0;
+}
 int lc3hip_last_status(void* ctx, uint8_t* status_host, int n) { return 0; }
 int lc3hip_last_records(void* ctx, float* rec_host, int max_words) { return 0; }
 int lc3hip_test_fastmath(int kind, const float* x_host, float* y_host, long long n) { return 1; }
