@@ -1,6 +1,6 @@
 /* lc3_runtime.hip -- the C-ABI device shim (lc3_shim.h): the host side of the gfx950 library.  Contexts, uploads, streams and events, and every launch of the
- * kernels in lc3_kernels.hip: lc3hip_* for the encoder (enc_launch: the one-wave path and the pipelined path), lc3hip_dec_* for the
- * decoder (dec_decode).  No device code here: the kernels are declared in lc3_kernel_decls.h, and what a launch is sized by is in lc3_launch.h and lc3_plan.h.
+ * kernels in lc3_kernels.hip: lc3hip_* for the encoder (enc_launch: enc_one_wave or enc_pipelined, then enc_writer), lc3hip_dec_* for the
+ * decoder (dec_decode: dec_stage, dec_plan, dec_parse, dec_chain, dec_tail).  No device code here: the kernels are declared in lc3_kernel_decls.h, and what a launch is sized by is in lc3_launch.h and lc3_plan.h.
  * Compiled once; the build-time diagnostic switches that act on host code (LC3_DUP, LC3D_SETS, DEC_SETS) are this file's. */
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -14,6 +14,7 @@
 #include "lc3_kernel_decls.h"
 
 #define LC3D_MAX_RUNS 16
+#define PKS_SUMS(n) (((size_t)(n) + PKS_TILE - 1) / PKS_TILE)      /* packed output: tile sums of the scan over n frames */
 #ifndef LC3D_SETS
 #define LC3D_SETS 3                     /* sets of hand-over buffers under the input-ready promise: that many calls may be in flight */
 #endif
@@ -44,23 +45,23 @@ static void read_opts(lc3hip_opts* o)
     o->shape_on_s = env_int("LC3PLUS_ENC_SHAPE_ON_S", 0, 1, 0);
     o->shape_wave = env_int("LC3PLUS_ENC_SHAPE_WAVE", 0, 1, 0);      /* the wave-per-frame shape kernel */
     o->pack_wpg = env_int("LC3PLUS_ENC_PACK_WPG", 1, 4, 4);          /* waves per workgroup of the writer */
-    o->pack_stream = env_int("LC3PLUS_ENC_PACK_STREAM", 0, 1, -1);   /* 1 = the writers of consecutive calls on two side streams (deployment switch, see enc_launch) */
+    o->pack_stream = env_int("LC3PLUS_ENC_PACK_STREAM", 0, 1, -1);   /* 1 = the writers of consecutive calls on two side streams (deployment switch, see enc_writer) */
     o->resample48 = env_int("LC3PLUS_ENC_RESAMPLE48", 0, 1, 1);      /* 0 = the two-outputs-per-lane resampler for 48 kHz / 10 ms too */
     o->resample96 = env_int("LC3PLUS_ENC_RESAMPLE96", 0, 2, 1);      /* the four-outputs-per-lane resampler for 96 kHz: 0 never, 1 standard kernel layout (2.5 ms frames), 2 every frame length */
     /* frames of this size and more: tail + writer a frame per wave (lc3_enc_tailw_kernel).  Off (0) by default - measured, Mframes/s: c96 (320-byte frames) 32.5 without,
      * 27.3 with; c5 (20 ... 400 bytes) 86.5 without, 68.6 / 73.6 / 78.4 from 120 / 200 / 320 bytes: the wave-parallel writer shortens the longest wave of the call but
      * costs several times the instructions per frame, and the call is bound by instructions, not by that latency. */
     o->tailw_bytes = env_int("LC3PLUS_ENC_TAILW_BYTES", 0, 1 << 20, 0);
-    o->dec_parse_pad_kb = env_int("LC3PLUS_DEC_PARSE_PAD_KB", 0, 60, -1);  /* LDS padding per parse workgroup = fewer resident parse waves; -1: the rule in lc3hip_dec_decode */
-    o->pack_pad_kb = env_int("LC3PLUS_ENC_PACK_PAD_KB", 0, 60, -1);      /* LDS padding per writer workgroup = fewer resident writer waves; -1: the rule in enc_launch */
-    o->pack_split = env_int("LC3PLUS_ENC_PACK_SPLIT", 0, 1, -1);        /* the writer as two kernels (head, coder); -1: the rule in enc_launch */
-    o->pack_w5 = env_int("LC3PLUS_ENC_PACK_W5", 0, 1, -1);              /* the writer under a 96-register budget; -1: the rule in enc_launch (long calls of small 10 ms frames) */
+    o->dec_parse_pad_kb = env_int("LC3PLUS_DEC_PARSE_PAD_KB", 0, 60, -1);  /* LDS padding per parse workgroup = fewer resident parse waves; -1: the rule in dec_parse */
+    o->pack_pad_kb = env_int("LC3PLUS_ENC_PACK_PAD_KB", 0, 60, -1);      /* LDS padding per writer workgroup = fewer resident writer waves; -1: the rule in enc_writer */
+    o->pack_split = env_int("LC3PLUS_ENC_PACK_SPLIT", 0, 1, -1);        /* the writer as two kernels (head, coder); -1: the rule in enc_writer */
+    o->pack_w5 = env_int("LC3PLUS_ENC_PACK_W5", 0, 1, -1);              /* the writer under a 96-register budget; -1: the rule in enc_writer (long calls of small 10 ms frames) */
     o->fuse_vq = env_int("LC3PLUS_ENC_FUSE_VQ", 0, 1, 0);               /* the SNS quantiser at the tail of the scale-factor kernel where no stream has attack handling */
     o->stream_order = env_int("LC3PLUS_ENC_STREAM_ORDER", 0, 1, 1);     /* diagnostic: 0 = the pitch stream is created before the front stream */
     o->stream_skip = env_int("LC3PLUS_ENC_STREAM_SKIP", 0, 8, 0);
-    o->rate_on = env_int("LC3PLUS_ENC_RATE_ON", 0, 1, -1);                /* a rate chain that leaves the caller's stream runs on the front stream (0) / the pitch stream (1); -1: the rule in enc_launch */
+    o->rate_on = env_int("LC3PLUS_ENC_RATE_ON", 0, 1, -1);                /* a rate chain that leaves the caller's stream runs on the front stream (0) / the pitch stream (1); -1: the rule in enc_pipelined */
     o->dec_plc_stream = env_int("LC3PLUS_DEC_PLC_STREAM", 0, 1, 1);        /* 0 = the decoder's concealment bookkeeping on the caller's stream (round 3) */
-    o->shape_on_pitch = env_int("LC3PLUS_ENC_SHAPE_ON_PITCH", 0, 1, -1);  /* the shape kernel on the pitch stream; -1: the rule in enc_launch (long calls of 2.5 ms high-resolution frames only) */
+    o->shape_on_pitch = env_int("LC3PLUS_ENC_SHAPE_ON_PITCH", 0, 1, -1);  /* the shape kernel on the pitch stream; -1: the rule in enc_run (long calls of 2.5 ms high-resolution frames only) */
     o->side_prio = env_int("LC3PLUS_ENC_SIDE_PRIO", 0, 2, 0);             /* diagnostic: 1 = the side streams at the lowest HIP stream priority, 2 = at the highest */
     o->check_ready = env_int("LC3PLUS_CHECK_READY", 0, 1, 0);        /* debug aid for lc3plus_enc_batch_set_input_ready: refuse a call made while foreign work is pending on the caller's stream */
     o->dec_imdct4 = env_int("LC3PLUS_DEC_IMDCT4", 0, 1, 1);          /* 0 = the one-frame-at-a-time IMDCT for N = 480 too */
@@ -73,6 +74,9 @@ struct lc3hip_ss {
     uint8_t* h[LC3D_SETS]; uint8_t* d[LC3D_SETS]; size_t cap[LC3D_SETS]; hipEvent_t ev[LC3D_SETS]; int armed[LC3D_SETS], k;
     hipEvent_t ev_prev, ev_done; int done_armed;
 };
+/* Words of a call through pinned staging to the device, in LC3D_SETS rotating sets: the caller's array is free when the call returns, and a set is written again
+ * once the call that read it has finished (calls with sync = 0) - its event is recorded by the caller behind the last kernel that reads the words. */
+struct lc3hip_stage { uint16_t* d[LC3D_SETS]; uint16_t* h[LC3D_SETS]; size_t cap; hipEvent_t ev[LC3D_SETS]; int armed[LC3D_SETS], k; };
 struct lc3hip_ctx {
     lc3hip_opts opt;
     int device, ncs, n_streams, channels, N, big, state_words, rs48, rs96;
@@ -81,7 +85,7 @@ struct lc3hip_ctx {
     lc3d_trace* d_trace; size_t trace_cap;
     int* d_dumpv[LC3D_SETS]; size_t dump_capv[LC3D_SETS]; int hr, fused; float* d_y12[LC3D_SETS]; size_t y12_cap[LC3D_SETS];
     uint8_t* d_status; uint8_t* d_statusv[LC3D_SETS]; size_t status_capv[LC3D_SETS]; int status_frames;      /* d_status: the set of the last call */
-    hipStream_t s_pk[2]; hipEvent_t ev_pk[2]; int pk_par;       /* the bitstream writers of consecutive calls beside each other (enc_launch) */
+    hipStream_t s_pk[2]; hipEvent_t ev_pk[2]; int pk_par;       /* the bitstream writers of consecutive calls beside each other (enc_writer) */
     float* d_spec[LC3D_SETS]; size_t spec_cap[LC3D_SETS]; float* d_frec[LC3D_SETS]; size_t frec_cap[LC3D_SETS]; hipEvent_t ev_done[LC3D_SETS]; float* d_xnext[LC3D_SETS + 1]; int xn_par, row_par; uint8_t* h_attack; int any_attack;
     const long long* plo; long long plcap;         /* lc3hip_set_pcm_placement: per-frame PCM offsets in device memory (null: off) and the buffer's length in elements */
     int input_ready, ahead_ok, ahead_T, ahead_R;   /* lc3hip_set_input_ready: side kernels of a call beside the previous call's tail */   /* split path (lc3_enc_front.inc) */      /* per channel-frame status bits of the last call (LC3D_ENC_ST_*) */
@@ -94,15 +98,15 @@ struct lc3hip_ctx {
     hipEvent_t ev_ours, ev_now; int ours_armed;       /* LC3PLUS_CHECK_READY: the tail of the library's own work on the caller's stream */
     /* per-frame bitrates: the configuration per channel byte count (lc3hip_upload_enc_table), and per call the stream-frame sizes, through pinned
      * staging, in LC3D_SETS rotating buffers (a buffer is written again once the call that read it has finished: calls with sync = 0) */
-    lc3d_chan* d_etab; uint16_t* d_fsz[LC3D_SETS]; uint16_t* h_fsz[LC3D_SETS]; size_t fsz_cap; hipEvent_t ev_fsz[LC3D_SETS]; int fsz_armed[LC3D_SETS], fsz_set;
+    lc3d_chan* d_etab; lc3hip_stage fsz;
     /* lc3hip_upload_chans_async: the configuration a per-frame-bitrate call leaves, queued on its stream behind its kernels from pinned staging; every later
      * call waits for the copy (ev_chans) on its own stream - and for the last stream-lifecycle call (lc3hip_stream_state), which records the same event */
     lc3d_chan* h_chans; hipEvent_t ev_chans; int chans_armed;
     /* per-frame bandwidths: per call the words in force, through pinned staging in LC3D_SETS rotating buffers as the sizes above.  The copy of a call goes on
      * the stream of the first kernel that reads the words (bw_to): on the pipelined path a side stream, so that a call that overlaps its predecessor does not
      * wait for that call's tail on the caller's stream; kernels on another stream wait for ev_bwcp.  bw_src / bw_bytes / bw_on: the pending call's copy. */
-    int cfg_fresh;      /* a copy of lc3hip_upload_chans_async that the side streams are not yet ordered behind: 1 bandwidth words only, 2 more (enc_launch) */
-    uint16_t* d_bw[LC3D_SETS]; uint16_t* h_bw[LC3D_SETS]; size_t bw_cap; hipEvent_t ev_bw[LC3D_SETS]; int bw_armed[LC3D_SETS], bw_set;
+    int cfg_fresh;      /* a copy of lc3hip_upload_chans_async that the side streams are not yet ordered behind: 1 bandwidth words only, 2 more (enc_pipelined) */
+    lc3hip_stage bw;
     const uint16_t* bw_src; size_t bw_bytes; hipStream_t bw_on; hipEvent_t ev_bwcp;
     lc3hip_ss ss;                                   /* lc3hip_set_template, lc3hip_stream_state */
     /* per-frame rates and bandwidths from device memory (lc3hip_encode_rates_device).  d_carry: each stream's rate, bytes and bandwidth in force, passed
@@ -117,7 +121,7 @@ struct lc3hip_ctx {
     /* packed output (lc3hip_encode_packed), for the call being queued: the scan (pack_scan) writes the table of offsets the writers read - per plan set k
      * with rates or bandwidths (a set is written again behind the call that used it last, as the plan buffers), one table otherwise (on the launch stream) */
     struct { int on, order; long long cap; long long* offs; long long* total; int32_t* nb; uint8_t* fl; const long long* tab; } pk;
-    long long* d_poff[LC3D_SETS + 1]; size_t poff_cap; long long* d_pbsum; size_t pbsum_cap /* per slot */; hipEvent_t ev_scan;
+    long long* d_poff[LC3D_SETS + 1]; size_t poff_cap /* frames; d_pbsum: a slot of PKS_SUMS(poff_cap) sums per table */; long long* d_pbsum; hipEvent_t ev_scan;
 };
 
 #define LC3D_FUSED_MAX_T 8
@@ -125,13 +129,53 @@ struct lc3hip_ctx {
 #define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { fprintf(stderr, "lc3plus_hip: %s failed: %s (%s:%d)\n", #x, hipGetErrorString(e_), __FILE__, __LINE__); return 1; } } while (0)
 /* inside the create functions: release what has been allocated so far (the caller only sees ctx == NULL) */
 #define HIPCHK_OR(x, cleanup) do { hipError_t e_ = (x); if (e_ != hipSuccess) { fprintf(stderr, "lc3plus_hip: %s failed: %s (%s:%d)\n", #x, hipGetErrorString(e_), __FILE__, __LINE__); cleanup; return 1; } } while (0)
+/* waits for the call on s and keeps its kernel time (ev0 ... ev1) */
+#define SYNC_TIMED(c, s) do { HIPCHK(hipStreamSynchronize(s)); float ms_ = 0; if (hipEventElapsedTime(&ms_, (c)->ev0, (c)->ev1) == hipSuccess) (c)->last_ms = ms_; } while (0)
 static size_t ss_up(size_t x) { return (x + 255) & ~(size_t)255; }
+/* The one place a buffer grows.  n buffers (device memory, or pinned host memory) share the capacity *cap, in the caller's unit: where it is below `need` they are
+ * freed and allocated again, b[i].bytes each.  wait: an earlier call that did not wait may still read them - wait for the device before freeing, unless this is the
+ * first allocation.  (hipFree drains the device too; the flag states where the order is the library's to keep.)  The pointers are null and the capacity is 0 before
+ * anything is allocated, so a failed allocation leaves nothing in the context to write through or to free twice. */
+struct lc3hip_buf { void** p; size_t bytes; bool pinned; };
+static int grow_group(size_t* cap, size_t need, const lc3hip_buf* b, int n, bool wait)
+{
+    if (*cap >= need) return 0;
+    bool first = true;
+    for (int i = 0; i < n; i++) first = first && !*b[i].p;
+    if (wait && !first) HIPCHK(hipDeviceSynchronize());
+    *cap = 0;
+    for (int i = 0; i < n; i++) { void* old = *b[i].p; *b[i].p = nullptr; if (old) HIPCHK(b[i].pinned ? hipHostFree(old) : hipFree(old)); }
+    for (int i = 0; i < n; i++) HIPCHK(b[i].pinned ? hipHostMalloc(b[i].p, b[i].bytes, hipHostMallocDefault) : hipMalloc(b[i].p, b[i].bytes));
+    *cap = need;
+    return 0;
+}
+template <typename T> static int grow(T** p, size_t* cap, size_t need, size_t bytes, bool wait) { const lc3hip_buf b = {(void**)p, bytes, false}; return grow_group(cap, need, &b, 1, wait); }
+/* two plain forms: grow_once, a buffer whose size never changes, allocated on first use (capacity 1 once it exists); replace, a buffer allocated anew whatever its size (capacity 0) */
+template <typename T> static int grow_once(T** p, size_t bytes, bool pinned = false) { size_t cap = *p != nullptr; const lc3hip_buf b = {(void**)p, bytes, pinned}; return grow_group(&cap, 1, &b, 1, false); }
+template <typename T> static int replace(T** p, size_t bytes) { size_t cap = 0; const lc3hip_buf b = {(void**)p, bytes, false}; return grow_group(&cap, 1, &b, 1, false); }
+/* src into the set whose turn it is (returned in *set, armed); the copy h -> d is the caller's to queue.  Sized on first use, a call of equal or smaller size allocates nothing. */
+static int stage_words(lc3hip_stage* q, const uint16_t* src, size_t bytes, int* set)
+{
+    const int k = q->k;
+    if (q->armed[k]) HIPCHK(hipEventSynchronize(q->ev[k]));       /* the set of the call LC3D_SETS back */
+    if (q->cap < bytes) {
+        for (int i = 0; i < LC3D_SETS; i++) if (q->armed[i]) { HIPCHK(hipEventSynchronize(q->ev[i])); q->armed[i] = 0; }      /* no call reads them any more: no wait for the device */
+        lc3hip_buf b[2 * LC3D_SETS];
+        for (int i = 0; i < LC3D_SETS; i++) { b[2 * i] = {(void**)&q->d[i], bytes, false}; b[2 * i + 1] = {(void**)&q->h[i], bytes, true}; }
+        if (grow_group(&q->cap, bytes, b, 2 * LC3D_SETS, false)) return 1;
+    }
+    if (!q->ev[0]) for (int i = 0; i < LC3D_SETS; i++) HIPCHK(hipEventCreateWithFlags(&q->ev[i], hipEventDisableTiming));
+    memcpy(q->h[k], src, bytes);
+    q->armed[k] = 1; q->k = (k + 1) % LC3D_SETS; *set = k;
+    return 0;
+}
+static void stage_free(lc3hip_stage* q) { for (int i = 0; i < LC3D_SETS; i++) { if (q->d[i]) hipFree(q->d[i]); if (q->h[i]) hipHostFree(q->h[i]); if (q->ev[i]) hipEventDestroy(q->ev[i]); } }
 /* the template to the device, and every row of the batch reset from it (create) */
 static int ss_init(lc3hip_ss* q, int device, float* state, int row_words, int ncs, const float* tmpl)
 {
     HIPCHK(hipSetDevice(device));
     q->row_words = row_words;
-    HIPCHK(hipMalloc((void**)&q->d_tmpl, sizeof(float) * (size_t)row_words));
+    if (grow_once(&q->d_tmpl, sizeof(float) * (size_t)row_words)) return 1;
     HIPCHK(hipMemcpy(q->d_tmpl, tmpl, sizeof(float) * (size_t)row_words, hipMemcpyHostToDevice));
     hipLaunchKernelGGL(lc3_stream_state_kernel, dim3((unsigned)ncs), dim3(WAVE), 0, (hipStream_t)0, (int)LC3D_SS_RESET, state, row_words, 1, (const int*)nullptr, ncs,
                        (const float*)q->d_tmpl, (uint8_t*)nullptr, 0u, 0u, 0u, 0u, (uint8_t*)nullptr, (const uint32_t*)nullptr, (uint32_t*)nullptr, 0);
@@ -158,13 +202,10 @@ static int ss_run(lc3hip_ss* q, hipStream_t s, hipStream_t last, int mode, float
     const size_t o_blob = o_cfg + ss_up(n_cfg), need = o_blob + (blob_on_device ? 0 : blob_bytes);
     const int k = q->k;
     if (q->armed[k]) { HIPCHK(hipEventSynchronize(q->ev[k])); q->armed[k] = 0; }      /* the call LC3D_SETS back has read this slot */
-    if (q->cap[k] < need) {
-        if (q->h[k]) HIPCHK(hipHostFree(q->h[k])); if (q->d[k]) HIPCHK(hipFree(q->d[k]));
-        q->h[k] = nullptr; q->d[k] = nullptr; q->cap[k] = 0;
-        const size_t cap = need < (64u << 10) ? (64u << 10) : need;
-        HIPCHK(hipHostMalloc((void**)&q->h[k], cap, hipHostMallocDefault)); HIPCHK(hipMalloc((void**)&q->d[k], cap));
-        q->cap[k] = cap;
-    }
+    /* at least 64 KB; no wait for the device: the event above says the slot's last reader has finished */
+    const size_t cap = need < (64u << 10) ? (64u << 10) : need;
+    const lc3hip_buf b[] = {{(void**)&q->h[k], cap, true}, {(void**)&q->d[k], cap, false}};
+    if (need && grow_group(&q->cap[k], cap, b, 2, false)) return 1;
     memcpy(q->h[k], list, sizeof(int) * (size_t)n);
     if (cfg) memcpy(q->h[k] + o_cfg, cfg, n_cfg);
     if (mode == LC3D_SS_IMPORT && !blob_on_device) memcpy(q->h[k] + o_blob, blob, blob_bytes);
@@ -245,7 +286,7 @@ extern "C" int lc3hip_upload_chans_async(void* ctx, const lc3d_chan* chans, int 
     c->cfg_fresh = bw_only ? 1 : 2;
     HIPCHK(hipSetDevice(c->device));
     hipStream_t s = hip_stream ? (hipStream_t)hip_stream : c->stream;
-    if (!c->h_chans) HIPCHK(hipHostMalloc((void**)&c->h_chans, sizeof(lc3d_chan) * (size_t)c->ncs, hipHostMallocDefault));
+    if (grow_once(&c->h_chans, sizeof(lc3d_chan) * (size_t)c->ncs, true)) return 1;
     if (!c->ev_chans) HIPCHK(hipEventCreateWithFlags(&c->ev_chans, hipEventDisableTiming));
     if (c->chans_armed) HIPCHK(hipEventSynchronize(c->ev_chans));      /* the staging of the previous copy is free */
     memcpy(c->h_chans + first, chans, sizeof(lc3d_chan) * (size_t)count);
@@ -279,7 +320,7 @@ static int chans_host_side_list(lc3hip_ctx* c, const lc3d_chan* chans, int first
     }
     c->any_attack = 0;
     for (int i = 0; i < c->ncs; i++) c->any_attack |= c->h_attack[i];
-    /* mean frame size: decides where the rate chain runs (enc_launch) */
+    /* mean frame size: decides where the rate chain runs (enc_pipelined) */
     { long long sum = 0; int mn = 1 << 30, mx = 0; for (int i = 0; i < c->ncs; i++) { sum += c->h_nb[i]; if (c->h_nb[i] < mn) mn = c->h_nb[i]; if (c->h_nb[i] > mx) mx = c->h_nb[i]; }
       c->mean_nbytes = (int)(sum / (c->ncs > 0 ? c->ncs : 1)); c->min_nbytes = mn; c->max_nbytes = mx; }
     return 0;
@@ -298,6 +339,14 @@ static int dup_of(char k) { static const char* e = nullptr; static bool rd = fal
 #else
 #define DUPL(k)
 #endif
+/* How a launch picks its twin.  Every step of a path is launched at ONE place: a generic lambda that holds the grid, the stream and the
+ * step's dense argument list, and takes the kernel and that kernel's trailing arguments - `go(kernel, trailing ...)`.  The variant is chosen beside it: the
+ * kernel's name (plain, _fmt, _wire, _big, _w5, _l32 ...) by a conditional, a twin with more parameters (_plc: LC3_PLACED_ARGS, _rag: LC3_RAGGED_ARGS, _pk, _vbw)
+ * by a call of the same lambda with those values appended.  The declaration of lc3_kernel_decls.h checks count and types of what arrives. */
+/* the twin of `name` by sample type: the reference's three depths, the wire types, the other formats */
+#define BY_FMT(q, name) ((q)->fmt_plain ? name : (q)->fmt_wire ? name##_wire : name##_fmt)
+/* PCM for the kernels that declare it as a typed pointer (the specialised resamplers): converts to whichever sample type the chosen kernel takes */
+struct pcm_as { const void* p; template <typename T> operator const T*() const { return (const T*)p; } };
 /* Placed PCM, calls that report per frame in device memory: behind the call's own kernels on s - every one of them that writes `out` (the encoder's flags, the
  * decoder's status) has finished or is joined to s by then - the frames whose offset is invalid get `bit`.  Nothing to do without placement or without `out`. */
 static int placed_mark(const long long* plo, long long plcap, int channels, int N, long long n, uint8_t* out, int bit, hipStream_t s)
@@ -311,34 +360,358 @@ static int placed_mark(const long long* plo, long long plcap, int channels, int 
 static void launch_resample(lc3hip_ctx* c, hipStream_t st, const void* dpcm, int bitdepth, int n_frames, int hb, int hn, int mc, float* dy12, const float* xprev, int xprev_stride)
 {
     const unsigned pruns = (unsigned)((hn + PRE_FPW - 1) / PRE_FPW);
-    if (c->plo)                                  /* placed PCM: the resampler for every shape (the specialised ones take typed dense pointers) */
-        hipLaunchKernelGGL(lc3_enc_resample_plc_kernel, dim3((unsigned)c->ncs * pruns), dim3(WAVE), 0, st, c->d_plan, c->d_state, c->state_words, mc, dpcm, bitdepth, n_frames, hb, hn, c->ncs, dy12, xprev, xprev_stride, c->plo, c->plcap);
-    else if (c->rs48 && bitdepth == 16 && (((size_t)dpcm) & 15) == 0)
-        hipLaunchKernelGGL(lc3_enc_resample48_kernel, dim3((unsigned)c->ncs * pruns), dim3(WAVE), 0, st, c->d_plan, (const int16_t*)dpcm, c->channels, mc, n_frames, hb, hn, c->ncs, dy12, xprev, xprev_stride);
-    else if (c->rs48 && (bitdepth & (LC3D_PCM_TYPE_MASK | LC3D_PCM_INTERLEAVED)) == LC3D_PCM_FLOAT32 && (((size_t)dpcm) & 15) == 0)   /* frames of 480 x 4 bytes: every one 16-byte aligned */
-        hipLaunchKernelGGL(lc3_enc_resample48f_kernel, dim3((unsigned)c->ncs * pruns), dim3(WAVE), 0, st, c->d_plan, (const float*)dpcm, bitdepth, c->channels, mc, n_frames, hb, hn, c->ncs, dy12, xprev, xprev_stride);
-    else if (c->rs48 && lc3d_pcm_type_wire(bitdepth & LC3D_PCM_TYPE_MASK) && !(bitdepth & LC3D_PCM_INTERLEAVED) && (((size_t)dpcm) & 3) == 0)   /* wire samples that follow each other, frames of 480 elements: every one starts on a dword */
-        hipLaunchKernelGGL(lc3_enc_resample48w_kernel, dim3((unsigned)c->ncs * pruns), dim3(WAVE), 0, st, c->d_plan, (const unsigned*)dpcm, bitdepth, c->channels, mc, n_frames, hb, hn, c->ncs, dy12, xprev, xprev_stride);
-    else if (c->rs96 && bitdepth == 16 && (((size_t)dpcm) & 15) == 0) {
-        auto k = c->N == 960 ? lc3_enc_resample96_kernel_n960 : c->N == 480 ? lc3_enc_resample96_kernel_n480 : lc3_enc_resample96_kernel_n240;
+    const bool a16 = (((size_t)dpcm) & 15) == 0;
+    /* the resampler for every shape, and its twins by sample type */
+    auto any = [&](auto k, auto... placed) { hipLaunchKernelGGL(k, dim3((unsigned)c->ncs * pruns), dim3(WAVE), 0, st, c->d_plan, c->d_state, c->state_words, mc, dpcm, bitdepth, n_frames, hb, hn, c->ncs, dy12, xprev, xprev_stride, placed...); };
+    /* the specialised ones take typed dense pointers: 16-bit samples ... */
+    auto s16 = [&](auto k, unsigned runs) { hipLaunchKernelGGL(k, dim3((unsigned)c->ncs * runs), dim3(WAVE), 0, st, c->d_plan, (const int16_t*)dpcm, c->channels, mc, n_frames, hb, hn, c->ncs, dy12, xprev, xprev_stride); };
+    /* ... and float32 or wire samples, which also take the format word */
+    auto typed = [&](auto k) { hipLaunchKernelGGL(k, dim3((unsigned)c->ncs * pruns), dim3(WAVE), 0, st, c->d_plan, pcm_as{dpcm}, bitdepth, c->channels, mc, n_frames, hb, hn, c->ncs, dy12, xprev, xprev_stride); };
+    if (c->plo) any(lc3_enc_resample_plc_kernel, c->plo, c->plcap);      /* placed PCM: the resampler for every shape (the specialised ones take typed dense pointers) */
+    else if (c->rs48 && bitdepth == 16 && a16) s16(lc3_enc_resample48_kernel, pruns);
+    else if (c->rs48 && (bitdepth & (LC3D_PCM_TYPE_MASK | LC3D_PCM_INTERLEAVED)) == LC3D_PCM_FLOAT32 && a16) typed(lc3_enc_resample48f_kernel);   /* frames of 480 x 4 bytes: every one 16-byte aligned */
+    else if (c->rs48 && lc3d_pcm_type_wire(bitdepth & LC3D_PCM_TYPE_MASK) && !(bitdepth & LC3D_PCM_INTERLEAVED) && (((size_t)dpcm) & 3) == 0) typed(lc3_enc_resample48w_kernel);   /* wire samples that follow each other, frames of 480 elements: every one starts on a dword */
+    else if (c->rs96 && bitdepth == 16 && a16) {
         const int fpb = (1920 / c->N) * PRE96_ITERS;                       /* frames per workgroup: PRE96_ITERS steps of 1 920 samples */
-        hipLaunchKernelGGL(k, dim3((unsigned)c->ncs * (unsigned)((hn + fpb - 1) / fpb)), dim3(WAVE), 0, st, c->d_plan, (const int16_t*)dpcm, c->channels, mc, n_frames, hb, hn, c->ncs, dy12, xprev, xprev_stride);
+        s16(c->N == 960 ? lc3_enc_resample96_kernel_n960 : c->N == 480 ? lc3_enc_resample96_kernel_n480 : lc3_enc_resample96_kernel_n240, (unsigned)((hn + fpb - 1) / fpb));
     }
-    else
-        hipLaunchKernelGGL((bitdepth == 16 || bitdepth == 24 || bitdepth == 32) ? lc3_enc_resample_kernel : lc3d_pcm_type_wire(bitdepth & LC3D_PCM_TYPE_MASK) ? lc3_enc_resample_wire_kernel : lc3_enc_resample_fmt_kernel, dim3((unsigned)c->ncs * pruns), dim3(WAVE), 0, st, c->d_plan, c->d_state, c->state_words, mc, dpcm, bitdepth, n_frames, hb, hn, c->ncs, dy12, xprev, xprev_stride);
+    else any((bitdepth == 16 || bitdepth == 24 || bitdepth == 32) ? lc3_enc_resample_kernel : lc3d_pcm_type_wire(bitdepth & LC3D_PCM_TYPE_MASK) ? lc3_enc_resample_wire_kernel : lc3_enc_resample_fmt_kernel);
+}
+/* behind it the HP50 recurrence of the same frames, one stream per lane */
+static void launch_hp50(lc3hip_ctx* c, hipStream_t st, int n_frames, int hb, int hn, int mc, float* dy12)
+{
+    hipLaunchKernelGGL(lc3_enc_hp50_kernel, dim3((unsigned)((c->ncs + WAVE - 1) / WAVE)), dim3(WAVE), 0, st, c->d_plan, c->d_state, c->state_words, LC3D_ST_SCAL(mc), n_frames, hb, hn, c->ncs, dy12);
 }
 static int bw_to(lc3hip_ctx* c, hipStream_t st);
-/* what enc_launch passes for the optional argument groups of the one-wave kernels (lc3_kernel_decls.h: LC3_OW_OPT orders them) */
+/* what enc_one_wave passes for the optional argument groups of the one-wave kernels (lc3_kernel_decls.h: LC3_OW_OPT orders them) */
 #define LC3_OW_VALS_VAR_0
-#define LC3_OW_VALS_VAR_1 , dfsz, (const lc3d_chan*)c->d_etab
+#define LC3_OW_VALS_VAR_1 , q->dfsz, (const lc3d_chan*)c->d_etab
 #define LC3_OW_VALS_VBW_0
-#define LC3_OW_VALS_VBW_1 , dbw
+#define LC3_OW_VALS_VBW_1 , q->dbw
 #define LC3_OW_VALS_PK_0
 #define LC3_OW_VALS_PK_1 , pt
 #define OW_KEY(big, var, vbw, pk) ((big) | (var) << 1 | (vbw) << 2 | (pk) << 3)
+/* one call of enc_launch: its arguments, and what the functions it is cut into hand to each other */
+struct enc_call {
+    const void* dpcm; int bitdepth, n_frames; uint8_t* dout; int out_stride; hipStream_t s; lc3d_trace* dtr; int dT, dt0; bool pack;
+    const uint16_t* dfsz;       /* per-frame bitrates: [stream][dT] stream-frame bytes, or null */
+    const uint16_t* dbw;        /* per-frame bandwidths: [stream][dT] Hz in force (stage_bw), or null; the path is the one without them */
+    bool fmt_plain, fmt_wire, placed;       /* which twin by sample type */
+    int set, mc, dstride; int* ddump; float* dy12; bool split;      /* enc_size_set: the call's set of hand-over buffers, and the path they select */
+    bool rate_on_side;                      /* enc_pipelined: the rate chain left the caller's stream */
+};
+/* the call's set of hand-over buffers (rows, records, writer scratch, status bytes), sized.  No site here waits for the device itself: under the input-ready
+ * promise every set is sized by the first call that needs it, and without it hipFree waits for the device's pending work before it releases a buffer that a
+ * call with sync = 0 may still read. */
+static int enc_size_set(lc3hip_ctx* c, enc_call* q, bool in_kernel_writer)
+{
+    const int set = q->set;
+    /* under the input-ready promise every set is sized on the first call that needs it: no allocation inside a later (timed, overlapped) call */
+    const int i0 = c->input_ready ? 0 : set, i1 = c->input_ready ? LC3D_SETS : set + 1;
+    if (!in_kernel_writer) {
+        q->dstride = PK_STRIDE(c->N, c->hr);
+        const size_t need = (size_t)c->ncs * q->dT * q->dstride;
+        for (int i = i0; i < i1; i++) if (grow(&c->d_dumpv[i], &c->dump_capv[i], need, need * sizeof(int), false)) return 1;
+        q->ddump = c->d_dumpv[set];
+    }
+    /* ahead of it: the 12.8 kHz resampler of all frames at once and its HP50 recurrence one stream per lane (lc3_enc_pre.inc) */
+    if (!q->dtr && !c->fused) {
+        const size_t need = (size_t)c->ncs * q->n_frames * 128;
+        /* two buffers under the input-ready promise: the next call's resampler may run beside this call's pitch kernel */
+        for (int i = i0; i < i1; i++) if (grow(&c->d_y12[i], &c->y12_cap[i], need, need * sizeof(float), false)) return 1;
+        q->dy12 = c->d_y12[set];
+    }
+    q->split = q->dy12 && q->ddump && !c->opt.no_split;
+    if (q->dt0 == 0) {   /* per channel-frame status bits (LC3D_ENC_ST_*), cleared per call: by the stream that runs the kernel that sets them (the writer's, on the pipelined path) */
+        const size_t need = (size_t)c->ncs * q->dT;
+        for (int i = i0; i < i1; i++) if (grow(&c->d_statusv[i], &c->status_capv[i], need, need, false)) return 1;
+        c->d_status = c->d_statusv[set];
+        if (!q->split) HIPCHK(hipMemsetAsync(c->d_status, 0, need, q->s));
+        c->status_frames = q->dT;
+    }
+    if (q->split) {
+        /* spectrum rows and records of all dT frames of the call (a call through host pointers comes in pieces: rows dt0 ...): two sets under
+         * the input-ready promise (consecutive calls overlap: the side kernels of a call write one set while the bitstream writer of the call
+         * before still reads the other), one otherwise */
+        const size_t ns = (size_t)c->ncs * q->dT * c->srow, nr = (size_t)c->ncs * q->dT * FR_WORDS;
+        for (int i = i0; i < i1; i++)
+            if (grow(&c->d_spec[i], &c->spec_cap[i], ns, ns * sizeof(float), false) || grow(&c->d_frec[i], &c->frec_cap[i], nr, nr * sizeof(float), false)) return 1;
+        for (int i = 0; i < LC3D_SETS + 1; i++) if (grow_once(&c->d_xnext[i], (size_t)c->ncs * q->mc * sizeof(float))) return 1;
+    }
+    return 0;
+}
+/* everything in lc3_encode_kernel (traced, diagnostic and very short launches), behind the 12.8 kHz pre-kernels when they apply */
+static int enc_one_wave(lc3hip_ctx* c, const enc_call* q)
+{
+    hipStream_t s = q->s;
+    if (c->big && q->dbw) return 1;                          /* no such kernel (LC3_OW_KERNELS) */
+    c->ahead_ok = 0; c->last_frec = nullptr; c->last_frec_frames = 0; c->cfg_fresh = 0;
+    if (q->dy12) {
+        launch_resample(c, s, q->dpcm, q->bitdepth, q->n_frames, 0, q->n_frames, q->mc, q->dy12, c->d_state + LC3D_ST_XPREV, c->state_words);
+        launch_hp50(c, s, q->n_frames, 0, q->n_frames, q->mc, q->dy12);
+        HIPCHK(hipGetLastError());
+    }
+    if (q->dbw && bw_to(c, s)) return 1;
+    /* the one-wave kernel of this call by layout and optional argument groups (lc3_kernel_decls.h: LC3_OW_KERNELS), or its _fmt, _wire or _plc twin */
+    const long long* pt = c->pk.on ? c->pk.tab : nullptr;         /* packed output: the _pk kernels, frames at the offsets of the call's table */
+    const int key = OW_KEY(c->big != 0, q->dfsz != nullptr, q->dbw != nullptr, pt != nullptr);
+    auto ow = [&](auto k, auto... groups) { hipLaunchKernelGGL(k, dim3(c->ncs), dim3(WAVE), 0, s, c->d_plan, c->d_chans, c->d_state, q->dpcm, q->bitdepth, q->n_frames, q->dout, pt ? 0 : q->out_stride, c->ncs, q->dtr, q->ddump, q->dstride, q->dy12, c->d_status, q->dT, q->dt0, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, groups...); };
+#define OW_LAUNCH(name, big, var, vbw, pk) \
+    if (key == OW_KEY(big, var, vbw, pk)) { \
+        if (q->placed) ow(name##_plc LC3_OW_OPT(LC3_OW_VALS_, var, vbw, pk), c->plo, c->plcap); \
+        else ow(BY_FMT(q, name) LC3_OW_OPT(LC3_OW_VALS_, var, vbw, pk)); \
+    } else
+    LC3_OW_KERNELS(OW_LAUNCH) return 1;
+#undef OW_LAUNCH
+    return 0;
+}
+/* the side streams of the pipelined path and their events, created on first use */
+static int enc_side_streams(lc3hip_ctx* c)
+{
+    if (c->s_pre) return 0;
+    /* Two side streams, no third.  HIP (four hardware queues by default) gave the FIRST side stream a batch creates a queue of its own and put all later ones
+     * together on another - and kernels of two streams on one queue run one after the other.  Round 3's separate rate stream therefore shared the front stream's
+     * queue (timeline of c5: 2.9 of the call's 3.0 ms on that one queue).  A rate chain that leaves the caller's stream now runs ON one of the two side streams,
+     * chosen per call (enc_pipelined): the same packets in the same queue, by choice instead of by creation order. */
+    for (int i = 0; i < c->opt.stream_skip; i++) { hipStream_t d; HIPCHK(hipStreamCreateWithFlags(&d, hipStreamNonBlocking)); }      /* diagnostic: shifts the assignment (never destroyed) */
+    int plo = 0, phi = 0; (void)hipDeviceGetStreamPriorityRange(&plo, &phi);       /* least, greatest */
+    const int prio = c->opt.side_prio == 1 ? plo : c->opt.side_prio == 2 ? phi : 0;
+    if (c->opt.stream_order) { HIPCHK(hipStreamCreateWithPriority(&c->s_fr, hipStreamNonBlocking, prio)); HIPCHK(hipStreamCreateWithPriority(&c->s_pre, hipStreamNonBlocking, prio)); }
+    else { HIPCHK(hipStreamCreateWithPriority(&c->s_pre, hipStreamNonBlocking, prio)); HIPCHK(hipStreamCreateWithPriority(&c->s_fr, hipStreamNonBlocking, prio)); }
+    /* LC3PLUS_ENC_STREAMS=5: the pitch kernel and the one-frame-per-lane kernels on streams of their own (pays only where the HIP runtime has
+     * hardware queues for them: GPU_MAX_HW_QUEUES >= 6) */
+    c->s_pit = c->s_pre; c->s_ln = c->s_fr;
+    if (c->opt.streams5) { HIPCHK(hipStreamCreateWithFlags(&c->s_pit, hipStreamNonBlocking)); HIPCHK(hipStreamCreateWithFlags(&c->s_ln, hipStreamNonBlocking)); }
+    for (int i = 0; i < LC3D_MAX_RUNS; i++) { HIPCHK(hipEventCreateWithFlags(&c->ev_h[i], hipEventDisableTiming)); HIPCHK(hipEventCreateWithFlags(&c->ev_m[i], hipEventDisableTiming)); HIPCHK(hipEventCreateWithFlags(&c->ev_v[i], hipEventDisableTiming)); }
+    for (int i = 0; i < 2; i++) { c->s_pk[i] = NULL; HIPCHK(hipEventCreateWithFlags(&c->ev_pk[i], hipEventDisableTiming)); }
+    HIPCHK(hipEventCreateWithFlags(&c->ev_rate, hipEventDisableTiming));
+    HIPCHK(hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
+    for (int i = 0; i < LC3D_SETS; i++) HIPCHK(hipEventCreateWithFlags(&c->ev_done[i], hipEventDisableTiming));
+    for (int i = 0; i < LC3D_MAX_RUNS; i++) { HIPCHK(hipEventCreateWithFlags(&c->ev_p[i], hipEventDisableTiming)); HIPCHK(hipEventCreateWithFlags(&c->ev_f[i], hipEventDisableTiming)); }
+    return 0;
+}
+/* what enc_pipelined decides once per call for its runs */
+struct enc_runs {
+    float* dspec; float* dfrec; float* xn_w; const float* xprev; int xprev_stride; bool five;
+    hipStream_t rts, rs; int hb, hk;      /* rts: the side stream of the rate chain (NULL: the caller's stream), rs: where the last rate kernel ran; the pre-kernels have run up to frame hb, in hk pieces */
+};
+/* run k of the pipelined path: frames tb ... tb + nt - 1 of the launch, Tr frames to a run */
+static int enc_run(lc3hip_ctx* c, const enc_call* q, enc_runs* r, int k, int tb, int nt, int Tr)
+{
+    hipStream_t s = q->s;
+    const int n_frames = q->n_frames, dT = q->dT, dt0 = q->dt0, mc = q->mc;
+    float* dspec = r->dspec; float* dfrec = r->dfrec;
+    /* The 12.8 kHz pre-kernels run ahead in larger pieces than the runs: the HP50 kernel (one stream per lane, B / 64 waves) costs ~0.1 ms
+     * per launch whatever the frame count, which per run would make its stream the slowest.  First piece = the first run (the rate
+     * kernel should start early), then three runs at a time, in stream order between the pitch kernels that need them.  (More side
+     * streams than these two do not help: HIP multiplexes streams onto a few hardware queues and kernels of two streams that share
+     * one run back to back.) */
+    if (tb >= r->hb) {
+        const int prn = c->opt.pre_runs;
+        const int hn0 = r->hk == 0 ? Tr : prn * Tr, hn = n_frames - r->hb < hn0 ? n_frames - r->hb : hn0;
+        DUPL('r') launch_resample(c, c->s_pre, q->dpcm, q->bitdepth, n_frames, r->hb, hn, mc, q->dy12, r->xprev, r->xprev_stride);
+        DUPL('h') launch_hp50(c, c->s_pre, n_frames, r->hb, hn, mc, q->dy12);
+        HIPCHK(hipGetLastError());
+        r->hb += hn; r->hk++;
+        if (r->five) { HIPCHK(hipEventRecord(c->ev_h[k], c->s_pre)); HIPCHK(hipStreamWaitEvent(c->s_pit, c->ev_h[k], 0)); }
+    }
+    /* OLPA + LTPF: two streams per wave where the 12.8 kHz frame length has such a kernel (LC3PLUS_ENC_PITCH2=0: one stream per wave) */
+    const bool p2 = c->opt.pitch2 && (c->len12 == 128 || c->len12 == 64 || c->len12 == 32);
+    auto pk = !p2 ? lc3_enc_pitch_kernel : c->len12 == 128 ? lc3_enc_pitch2_kernel : c->len12 == 64 ? lc3_enc_pitch2_kernel_l64 : lc3_enc_pitch2_kernel_l32;
+    DUPL('p') hipLaunchKernelGGL(pk, dim3((unsigned)(p2 ? (c->ncs + 1) / 2 : c->ncs)), dim3(WAVE), 0, c->s_pit, c->d_plan, c->d_chans, c->d_state, c->state_words, mc, q->dy12, n_frames, tb, nt, c->ncs, dfrec, dT, dt0);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(c->ev_p[k], c->s_pit));
+    const int scf_wave = c->opt.scf_wave;
+    {   /* the front: four frames a wave at 48 kHz / 10 ms, fm_frames a wave for the short frame lengths, else fpw frames a wave */
+        const int fpw = nt < FRONT_FPW ? nt : FRONT_FPW;
+        const int f4 = c->opt.front4;
+        auto front4 = [&](auto kern, auto... placed) { hipLaunchKernelGGL(kern, dim3((unsigned)c->ncs * (unsigned)((nt + 3) / 4)), dim3(WAVE), 0, c->s_fr, c->d_plan, c->d_chans, c->d_state, q->dpcm, q->bitdepth, n_frames, tb, nt, c->ncs, dspec, c->srow, dT, dt0, dfrec, r->xn_w, r->xprev, r->xprev_stride, placed...); };
+        auto frontm = [&](auto kern, auto... placed) { hipLaunchKernelGGL(kern, dim3((unsigned)c->ncs * (unsigned)((nt + c->fm_frames - 1) / c->fm_frames)), dim3(WAVE), 0, c->s_fr, c->d_plan, c->d_chans, c->d_state, q->dpcm, q->bitdepth, n_frames, tb, nt, c->fm_frames, c->ncs, dspec, c->srow, dT, dt0, dfrec, r->xn_w, r->xprev, r->xprev_stride, placed...); };
+        auto front = [&](auto kern, auto... placed) { hipLaunchKernelGGL(kern, dim3((unsigned)c->ncs * (unsigned)((nt + fpw - 1) / fpw)), dim3(WAVE), 0, c->s_fr, c->d_plan, c->d_chans, c->d_state, q->dpcm, q->bitdepth, n_frames, tb, nt, fpw, c->ncs, dspec, c->srow, dT, dt0, dfrec, r->xn_w, r->xprev, r->xprev_stride, scf_wave, placed...); };
+        if (f4 && !c->big && !scf_wave && c->N == 480 && c->la == 180 && (c->ylen & 15) == 0) {
+            if (q->placed) front4(lc3_enc_front4_kernel_plc, c->plo, c->plcap); else DUPL('f') front4(BY_FMT(q, lc3_enc_front4_kernel));
+        } else if (f4 && c->fm_frames && !scf_wave) {
+            if (q->placed) frontm(lc3_enc_frontm_kernel_plc, c->plo, c->plcap); else frontm(BY_FMT(q, lc3_enc_frontm_kernel));
+        }
+        else if (q->placed) front(c->big ? lc3_enc_front_kernel_big_plc : lc3_enc_front_kernel_plc, c->plo, c->plcap);
+        else if (c->big) front(BY_FMT(q, lc3_enc_front_kernel_big));
+        else DUPL('f') front(BY_FMT(q, lc3_enc_front_kernel));
+    }
+    HIPCHK(hipEventRecord(c->ev_m[k], c->s_fr));                 /* the MDCT memory hand-over and the spectrum rows of the run are written */
+    if (r->five) HIPCHK(hipStreamWaitEvent(c->s_ln, c->ev_m[k], 0));
+    const int fuse_vq = !scf_wave && !c->any_attack && c->opt.fuse_vq;
+    const unsigned lanes = (unsigned)(((long long)c->ncs * nt + WAVE - 1) / WAVE);      /* waves of a kernel that takes one frame per lane */
+    if (!scf_wave) DUPL('e') hipLaunchKernelGGL(lc3_enc_scf_lane_kernel, dim3(lanes), dim3(WAVE), 0, c->s_ln, c->d_plan, dT, dt0 + tb, nt, c->ncs, dspec, c->srow, dfrec, fuse_vq);
+    if (c->any_attack)
+        hipLaunchKernelGGL(lc3_enc_attack_kernel, dim3((unsigned)((c->ncs + WAVE - 1) / WAVE)), dim3(WAVE), 0, c->s_ln, c->d_plan, c->d_chans, c->d_state, c->state_words, LC3D_ST_SCAL(mc), dfrec, dT, dt0, tb, nt, c->ncs);
+    if (!fuse_vq) DUPL('v') hipLaunchKernelGGL(lc3_enc_snsvq_kernel, dim3(lanes), dim3(WAVE), 0, c->s_ln, c->d_plan, dfrec, dT, dt0, tb, nt, c->ncs, c->any_attack);
+    hipStream_t rs;
+    {   /* shaping, TNS and the stateless half of the gain estimate: frame-parallel, behind the quantiser (LC3PLUS_ENC_SHAPE_ON_S=1, diagnostic: on the
+         * launch stream in front of the rate kernel instead) */
+        const int sfpw = c->opt.shape_fpw ? c->opt.shape_fpw : SHAPE_FPW, son = c->opt.shape_on_s;
+        const int spw = nt < sfpw ? nt : sfpw;
+        const unsigned sruns = (unsigned)((nt + spw - 1) / spw);
+        /* LC3PLUS_ENC_SHAPE_ON_PITCH=1 (diagnostic): the shape kernel on the pitch stream, behind the pitch kernel, waiting for the quantiser's event.  Tried for c96, whose
+         * front stream is the longest (3.6 of a 3.6 ms call) and whose pitch stream the lightest (1.4): the next call's pitch chain then queues behind a shape kernel that
+         * waits for the front stream - 37.3 -> 31.0 Mframes/s; c1 111 -> 101, c5 97 -> 81, c3 93 -> 83; only c4 - long calls of 2.5 ms high-resolution frames, four runs per call, the front stream 8.5 of the 8.6 ms - gains (122.0 -> 126.1): on for that shape only. */
+        const bool sop = !son && (c->opt.shape_on_pitch >= 0 ? c->opt.shape_on_pitch == 1 : (c->hr && c->N == 240 && n_frames >= 128));      /* c4's shape: calls of 128 / 256 frames 123.8 -> 126.0, 122.0 -> 126.1 */
+        hipStream_t ss = son ? s : sop ? c->s_pit : c->s_ln;
+        rs = (son || !r->rts) ? s : r->rts;
+        if (son) { HIPCHK(hipEventRecord(c->ev_f[k], c->s_ln)); HIPCHK(hipStreamWaitEvent(s, c->ev_f[k], 0)); }
+        if (sop) { HIPCHK(hipEventRecord(c->ev_v[k], c->s_ln)); HIPCHK(hipStreamWaitEvent(ss, c->ev_v[k], 0)); }
+        const int swave = c->opt.shape_wave;
+        if (q->dbw && bw_to(c, ss)) return 1;
+        /* one frame per lane, or (LC3PLUS_ENC_SHAPE_WAVE=1) spw frames per wave; with per-frame bandwidths the _vbw twin of either */
+        auto lane = [&](auto kern, auto... bw) { hipLaunchKernelGGL(kern, dim3(lanes), dim3(WAVE), 0, ss, c->d_plan, c->d_chans, dT, dt0 + tb, nt, c->ncs, dspec, c->srow, dfrec, bw...); };
+        auto wave = [&](auto kern, auto... bw) { hipLaunchKernelGGL(kern, dim3((unsigned)c->ncs * sruns), dim3(WAVE), 0, ss, c->d_plan, c->d_chans, dT, dt0 + tb, nt, spw, c->ncs, dspec, c->srow, dfrec, bw...); };
+        if (!swave) { if (q->dbw) lane(lc3_enc_shape_lane_kernel_vbw, q->dbw); else DUPL('a') lane(lc3_enc_shape_lane_kernel); }
+        else if (q->dbw) wave(lc3_enc_shape_kernel_vbw, q->dbw);
+        else if (c->big) wave(lc3_enc_shape_kernel_big);
+        else DUPL('a') wave(lc3_enc_shape_kernel);
+        HIPCHK(hipGetLastError());
+        if (!son) { HIPCHK(hipEventRecord(c->ev_f[k], ss)); HIPCHK(hipStreamWaitEvent(rs, c->ev_f[k], 0)); }
+    }
+    HIPCHK(hipStreamWaitEvent(rs, c->ev_p[k], 0));
+    if (k == 0 && c->rate_armed) HIPCHK(hipStreamWaitEvent(rs, c->ev_rate, 0));      /* the rate chain is a chain: behind the previous call's, whichever stream that ran on */
+    const int last = tb + nt >= n_frames;            /* behind the last frame of this launch the MDCT memory goes into the state */
+    auto rate = [&](auto kern) { hipLaunchKernelGGL(kern, dim3((unsigned)((c->ncs + RATE_WG - 1) / RATE_WG)), dim3(RATE_WG * WAVE), 0, rs, c->d_plan, c->d_chans, c->d_state, dT, dt0 + tb, nt, c->ncs, dspec, c->srow, dfrec, r->xn_w, last); };
+    if (c->big) rate(lc3_enc_rate_kernel_big); else DUPL('s') rate(lc3_enc_rate_kernel);
+    HIPCHK(hipGetLastError());
+    r->rs = rs;
+    return 0;
+}
+/* The pipelined path.  Per run of frames: on one side stream the pitch chain (resampler per frame, HP50 one stream per lane, OLPA +
+ * LTPF one stream per wave); on another the frame-parallel front (MDCT ... scale factors), the attack decision and the SNS quantiser
+ * (one frame per lane); on the launch stream the shape kernel (SNS shaping, TNS, log energies: frame-parallel) and behind it the rate
+ * chain (lc3_enc_rate_kernel: rate loop, bisection, first quantisation), which also waits for the pitch chain.  Everything behind the
+ * chain - gain adjustment, second quantisation, noise level, residual - is frame-parallel again and runs one frame per lane at the head
+ * of the bitstream writer, once per call.  The side kernels of run k+1 are resident beside the launch stream's kernels of run k. */
+static int enc_pipelined(lc3hip_ctx* c, enc_call* q)
+{
+    hipStream_t s = q->s;
+    const int n_frames = q->n_frames, dT = q->dT, dt0 = q->dt0, hb_ = q->set;
+    if (enc_side_streams(c)) return 1;
+    enc_runs r;
+    r.dspec = c->d_spec[hb_]; r.dfrec = c->d_frec[hb_];
+    c->last_frec = r.dfrec; c->last_frec_frames = dT;
+    const int runf = c->opt.run_frames ? c->opt.run_frames : c->input_ready ? LC3D_RUN_FRAMES_READY : LC3D_RUN_FRAMES;
+    int R = (n_frames + runf - 1) / runf;              /* runs of frames */
+    if (R > LC3D_MAX_RUNS) R = LC3D_MAX_RUNS;
+    if (R < 1) R = 1;
+    if (c->opt.runs) R = c->opt.runs;
+    const int Tr = (n_frames + R - 1) / R;
+    /* Where the side kernels of this call may start.  Normally behind everything the caller queued on s before the call (the PCM may
+     * come from there).  With lc3hip_set_input_ready - the PCM of a call is complete when the call is made - and a previous call of
+     * the same shape on the same stream, they need not wait for that call's chain and bitstream writer: their streams carry on in
+     * their own order, writing the other set of rows and records (the set they write now was last read by the writer of the call before
+     * the previous one: ev_done); the MDCT memory before frame 0 is read from the previous call's hand-over (two alternating buffers),
+     * not from the state that call's last rate kernel is still to update. */
+    const int amax = c->opt.ahead_max ? c->opt.ahead_max : LC3D_AHEAD_MAX_FRAMES;
+    /* A configuration copy queued behind the previous call (lc3hip_upload_chans_async) is on s, which a call that overlaps does not wait for: only a
+     * per-frame-bandwidth call overlaps it, and only when that copy changed nothing but the bandwidth words, which its kernels do not read (the other words
+     * are rewritten with their own values).  A call that forks from s is behind the copy, and so is everything after it. */
+    const bool cfg_ok = c->cfg_fresh == 0 || (c->cfg_fresh == 1 && q->dbw);
+    const bool ahead = c->input_ready && n_frames <= amax && c->ahead_ok && c->ahead_T == n_frames && c->ahead_R == R && c->last_stream == s && dt0 == 0 && dT == n_frames && q->pack && cfg_ok;
+    if (!ahead) c->cfg_fresh = 0;
+    r.xn_w = c->d_xnext[c->xn_par];                         /* written by this call's front kernel */
+    /* one buffer more than calls in flight: the one written now was last read by the call LC3D_SETS back (its resampler and front) and by the
+     * rate kernel of the call before that, all finished before the bitstream writer this call's side streams have waited for */
+    r.xprev = ahead ? c->d_xnext[(c->xn_par + LC3D_SETS) % (LC3D_SETS + 1)] : c->d_state + LC3D_ST_XPREV;
+    r.xprev_stride = ahead ? q->mc : c->state_words;
+    const bool five = r.five = c->s_pit != c->s_pre;
+    /* The rate chain on a stream of its own, so that the rate kernel of call k+1 runs beside the bitstream writer of call k (which stays on the
+     * caller's stream: it is what the caller waits for).  It pays where the caller's stream - rate kernel + writer - is the longest of the three:
+     * large frames (the writer's work grows with the bytes: c96 22 -> 32 Mframes/s, c5 77 -> 83) and short calls (c3 +3 %); on 80-byte frames in
+     * calls of 64 (c1) a fourth side stream costs 0 ... 11 % (it shares one of HIP's four hardware queues with another, depending on what else the
+     * process created), and on c4 4 %.  LC3PLUS_ENC_RATE_STREAM=0 / 1 forces the choice (diagnostic). */
+    const int rt_env = c->opt.rate_stream;
+    const bool want_rt = rt_env == 1 || (rt_env < 0 && !c->big && (c->mean_nbytes >= 120 || n_frames <= 32));      /* large layout (c96, with round 4's writer): 36.6 on the caller's stream against 33.9 / 34.5 on the front / pitch stream */
+    /* ... and then on which side stream: behind the pitch kernel (it waits for the shape kernel's event) or behind the shape kernel (it waits for the pitch kernel's).
+     * Measured (Mframes/s, front stream / pitch stream): 48 kHz / 10 ms x 64 frames at 120 bytes 91.6 / 102.5, 160: 88.5 / 98.0, 240: 82.0 / 88.0, 400: 72.8 / 75.2, c5 88.3 / 97.1 (calls of
+     * 32: 82.7 / 88.5); 80-byte frames in calls of 6: 51.3 / 60.4, 8: 62.3 / 68.1, 12: 72.4 / 88.6, 14: 80.6 / 88.4, 18: 85.3 / 90.8, 28: 93.4 / 95.5, 32: 94.6 / 100.9 - but of 16: 94.2 / 92.6 (c3 94.1 / 89.8),
+     * 20: 93.8 / 91.0, 24: 96.4 / 92.9, and c96 32.8 / 30.8.  The pitch stream is the lighter one; behind the shape kernel the rate kernel blocks nothing while it waits, which wins where the
+     * front stream is at its best (calls of 16 ... 24 frames in whole groups of four - lc3_enc_front4_kernel's unit) and in the large layout. */
+    const bool on_pre = c->opt.rate_on >= 0 ? c->opt.rate_on == 1 : !(c->big || (c->mean_nbytes < 120 && n_frames >= 16 && n_frames <= 24 && (n_frames & 3) == 0));
+    r.rts = want_rt ? (on_pre ? c->s_pit : c->s_ln) : NULL;          /* NULL: the rate kernels run on the caller's stream */
+    if (!ahead) {
+        HIPCHK(hipEventRecord(c->ev_fork, s)); HIPCHK(hipStreamWaitEvent(c->s_pre, c->ev_fork, 0)); HIPCHK(hipStreamWaitEvent(c->s_fr, c->ev_fork, 0));
+        if (five) { HIPCHK(hipStreamWaitEvent(c->s_pit, c->ev_fork, 0)); HIPCHK(hipStreamWaitEvent(c->s_ln, c->ev_fork, 0)); }
+    } else {
+        HIPCHK(hipStreamWaitEvent(c->s_pre, c->ev_m[R - 1], 0));    /* the resampler reads the hand-over the previous call's last front kernel wrote */
+        HIPCHK(hipStreamWaitEvent(c->s_pre, c->ev_done[hb_], 0)); HIPCHK(hipStreamWaitEvent(c->s_fr, c->ev_done[hb_], 0));
+        if (five) { HIPCHK(hipStreamWaitEvent(c->s_pit, c->ev_done[hb_], 0)); HIPCHK(hipStreamWaitEvent(c->s_ln, c->ev_done[hb_], 0));
+                    if (c->any_attack) HIPCHK(hipStreamWaitEvent(c->s_fr, c->ev_f[R - 1], 0)); }      /* the front reads the attack detector's filter memory the previous call's attack kernel leaves */
+    }
+    r.rs = s; r.hb = 0; r.hk = 0;                         /* rs: where the rate kernels run */
+    for (int k = 0, tb = 0; tb < n_frames; k++, tb += Tr)
+        if (enc_run(c, q, &r, k, tb, n_frames - tb < Tr ? n_frames - tb : Tr, Tr)) return 1;
+    HIPCHK(hipEventRecord(c->ev_rate, r.rs)); c->rate_armed = 1; q->rate_on_side = r.rs != s;
+    if (r.rs != s) HIPCHK(hipStreamWaitEvent(s, c->ev_rate, 0));      /* the writer (and whatever the caller queues next) behind the rate chain */
+    c->ahead_ok = (dt0 == 0 && dT == n_frames && q->pack) ? 1 : 0; c->ahead_T = n_frames; c->ahead_R = R;
+    c->xn_par = (c->xn_par + 1) % (LC3D_SETS + 1);
+    return 0;
+}
+/* the bitstream writer over all dT frames of the call, once the last launch of the call has filled the hand-over; on the pipelined path it starts from the shaped
+ * spectra (frame-parallel tail, one frame per lane) */
+static int enc_writer(lc3hip_ctx* c, const enc_call* q)
+{
+    hipStream_t s = q->s;
+    const int dT = q->dT; const bool split = q->split;
+    float* rows_for_pack = split ? c->d_spec[q->set] : nullptr; const float* frec_for_pack = split ? c->d_frec[q->set] : nullptr;
+    HIPCHK(hipGetLastError());
+    const int wpg = c->opt.pack_wpg;                  /* waves per workgroup of the writer (they share the coder's tables in LDS) */
+    const size_t per_wave = (size_t)PK_XBUF * WAVE * sizeof(unsigned);
+    const long long tasks = (long long)c->ncs * dT, per_wg = (long long)wpg * WAVE;
+    /* The writer codes one frame per lane: its duration is the latency of the LARGEST frame of the batch (c5: 1.7 ms for 400 bytes, c96: 3.2 ms), whatever the
+     * batch size, and on the caller's stream the writers of consecutive calls run one after the other.  Where that is the longest stream (the rule that moves the
+     * rate chain off the caller's stream: large frames, short calls) and calls overlap, the writers CAN alternate between two side streams - writer k + 1 beside
+     * writer k, each with its own set of scratch rows and status bytes, the caller's stream waiting for their events in call order.  Measured (Mframes/s,
+     * off / on): with HIP's default four hardware queues c5 87.0 / 80.0, c96 32.1 / 28.7, c3 85.1 / 73.0 - six streams share four queues and kernels of two
+     * streams on one queue run back to back; with GPU_MAX_HW_QUEUES=8 c5 90.9 / 92.4, c96 28.8 / 33.9, c3 85.5 / 85.8.  So it is a deployment switch
+     * (LC3PLUS_ENC_PACK_STREAM=1 together with GPU_MAX_HW_QUEUES >= 6), off by default. */
+    const int pk_env = c->opt.pack_stream;
+    const bool side = split && q->rate_on_side && c->input_ready && q->dt0 == 0 && dT == q->n_frames && pk_env == 1;
+    hipStream_t ps = s;
+    if (side) {
+        /* behind this call's rate chain only - NOT behind the caller's stream, whose tail is the writer of the call before: under the input-ready promise the
+         * output buffer of a call, like its PCM, is the caller's to have ready (include/lc3plus_batch.h) */
+        if (!c->s_pk[c->pk_par]) HIPCHK(hipStreamCreateWithFlags(&c->s_pk[c->pk_par], hipStreamNonBlocking));
+        ps = c->s_pk[c->pk_par];
+        HIPCHK(hipStreamWaitEvent(ps, c->ev_rate, 0));
+    }
+    if (side && c->pk.on) HIPCHK(hipStreamWaitEvent(ps, c->ev_scan, 0));     /* packed output: behind the call's scan (the table the writers read) */
+    if (split) HIPCHK(hipMemsetAsync(c->d_status, 0, (size_t)c->ncs * dT, ps));
+    /* large frames: tail + writer a frame per wave (lc3_enc_tailw_kernel, lc3_enc_rate.inc), launched first - its waves are the long ones */
+    const int big_from = (split && c->opt.tailw_bytes && c->max_nbytes >= c->opt.tailw_bytes && !c->pk.on) ? c->opt.tailw_bytes : 0;   /* (no packed form) */
+    if (big_from) {
+        const int fpw = dT < 4 ? dT : 4;
+        const unsigned wruns = (unsigned)((dT + fpw - 1) / fpw);
+        hipLaunchKernelGGL(c->big ? lc3_enc_tailw_kernel_big : lc3_enc_tailw_kernel, dim3((unsigned)c->ncs * wruns), dim3(WAVE), 0, ps, c->d_plan, c->d_chans, dT, dT, fpw, c->ncs, rows_for_pack, c->srow, frec_for_pack, q->dout,
+                           q->out_stride, c->d_status, big_from);
+        HIPCHK(hipGetLastError());
+    }
+    const bool two = split && c->opt.pack_split == 1;
+    if (!big_from || c->min_nbytes < big_from) {
+        const dim3 grid((unsigned)((tasks + per_wg - 1) / per_wg)), block(wpg * WAVE);
+        const size_t dyn = per_wave * wpg + ((size_t)(c->opt.pack_pad_kb > 0 ? c->opt.pack_pad_kb : 0) << 10);
+        const long long* pt = c->pk.on ? c->pk.tab : nullptr;      /* packed output: the _pk twins write each frame at its offset of the call's table */
+        auto writer = [&](auto kern, size_t lds, auto... poff) { hipLaunchKernelGGL(kern, grid, block, lds, ps, c->d_plan, c->d_chans, q->ddump, q->dstride, dT, 0, dT, c->ncs, q->dout, pt ? 0 : q->out_stride, c->d_status, rows_for_pack, c->srow, frec_for_pack, big_from, poff...); };
+        if (two) {       /* LC3PLUS_ENC_PACK_SPLIT=1: the writer as two kernels (head, coder) */
+            if (pt) { writer(lc3_enc_pack_head_kernel_pk, 0, pt); writer(lc3_enc_pack_code_kernel_pk, dyn, pt); }
+            else { writer(lc3_enc_pack_head_kernel, 0); writer(lc3_enc_pack_code_kernel, dyn); }
+        } else {
+            /* 96 or 128 registers (lc3_enc_pack.inc, the table at lc3_enc_pack_kernel_w5): five waves per SIMD pay for long calls of small 10 ms frames */
+            const bool w5 = c->opt.pack_w5 >= 0 ? c->opt.pack_w5 == 1 : (split && !c->big && !c->hr && c->N == 480 && dT >= 48 && c->max_nbytes <= 100);
+            if (pt) writer(w5 ? lc3_enc_pack_kernel_w5_pk : lc3_enc_pack_kernel_pk, dyn, pt);
+            else DUPL('k') writer(w5 ? lc3_enc_pack_kernel_w5 : lc3_enc_pack_kernel, dyn);
+        }
+    }
+    if (split && c->input_ready) { HIPCHK(hipEventRecord(c->ev_done[c->row_par], ps)); c->row_par = (c->row_par + 1) % LC3D_SETS; }      /* this call's set of rows and records is free again */
+    if (side) { HIPCHK(hipEventRecord(c->ev_pk[c->pk_par], ps)); HIPCHK(hipStreamWaitEvent(s, c->ev_pk[c->pk_par], 0)); c->pk_par ^= 1; }
+    return 0;
+}
 static int enc_launch(lc3hip_ctx* c, const void* dpcm, int bitdepth, int n_frames, uint8_t* dout, int out_stride, hipStream_t s, lc3d_trace* dtr,
-                      int dT, int dt0, bool pack, const uint16_t* dfsz /* per-frame bitrates: [stream][dT] stream-frame bytes, or null */,
-                      const uint16_t* dbw /* per-frame bandwidths: [stream][dT] Hz in force (stage_bw), or null; the path is the one without them */)
+                      int dT, int dt0, bool pack, const uint16_t* dfsz, const uint16_t* dbw)
 {
     /* two kernels: lc3_encode_kernel (one wave per channel-stream, frames in order) leaves each frame's parameters and quantised
      * spectrum in a record; lc3_enc_pack_kernel (one channel-frame per lane, any frame size) writes the bytes.  With stage traces,
@@ -346,301 +719,22 @@ static int enc_launch(lc3hip_ctx* c, const void* dpcm, int bitdepth, int n_frame
     /* A call of very few frames is latency bound and the one-frame-per-lane writer is the longest chain in it (~0.19 ms for a frame of
      * 80 bytes whatever the batch size): up to LC3D_FUSED_MAX_T frames per call the wave-parallel writer inside the first kernel
      * (st_bitstream, ~6 us per frame) is used instead - the single-stream lc3_enc_* API and T = 1 batches live here. */
-    int* ddump = nullptr; int dstride = 0;
-    const int set = c->input_ready ? c->row_par : 0;        /* the set of hand-over buffers of this call (rows, records, writer scratch, status bytes) */
+    enc_call q = {dpcm, bitdepth, n_frames, dout, out_stride, s, dtr, dT, dt0, pack, dfsz, dbw};
+    q.set = c->input_ready ? c->row_par : 0;        /* the set of hand-over buffers of this call (rows, records, writer scratch, status bytes) */
     /* with the input-ready promise consecutive short calls overlap on the pipelined path, which then wins from 4 frames per call
      * (4096 streams, Mframes/s pipelined / in-kernel writer: 3 frames 31.9 / 36.3, 4: 39.8 / 38.0, 6: 48.6 / 40.2, 8: 53.9 / 41.2; without the
      * promise 8: 40.2 / 41.2) */
     /* (per-frame bitrates: always - lc3_encode_kernel_var reloads the configuration per frame; it is the only kernel that does) */
     /* the PCM formats beyond the reference's three have kernels of their own (_fmt) wherever the load could not be added without moving the registers of the kernel that is there */
-    const bool fmt_plain = bitdepth == 16 || bitdepth == 24 || bitdepth == 32;
-    const bool fmt_wire = lc3d_pcm_type_wire(bitdepth & LC3D_PCM_TYPE_MASK) != 0;           /* the wire sample types: the _wire twins, so that the _fmt kernels stay what they were */
-    const bool placed = c->plo != nullptr;                                                  /* placed PCM: the _plc twins, one form for every sample type */
-    if (placed && (dt0 != 0 || dT != n_frames || (bitdepth & LC3D_PCM_CHANNEL_MAJOR))) return 1;    /* the offsets are indexed by the call's frames; the host refuses the rest */
+    q.fmt_plain = bitdepth == 16 || bitdepth == 24 || bitdepth == 32;
+    q.fmt_wire = lc3d_pcm_type_wire(bitdepth & LC3D_PCM_TYPE_MASK) != 0;           /* the wire sample types: the _wire twins, so that the _fmt kernels stay what they were */
+    q.placed = c->plo != nullptr;                                                  /* placed PCM: the _plc twins, one form for every sample type */
+    if (q.placed && (dt0 != 0 || dT != n_frames || (bitdepth & LC3D_PCM_CHANNEL_MAJOR))) return 1;    /* the offsets are indexed by the call's frames; the host refuses the rest */
     const bool in_kernel_writer = dtr || c->fused || dfsz || dT <= (c->input_ready ? LC3D_FUSED_MAX_T_READY : LC3D_FUSED_MAX_T);
-    if (!in_kernel_writer) {
-        dstride = PK_STRIDE(c->N, c->hr);
-        const size_t need = (size_t)c->ncs * dT * dstride;
-        /* under the input-ready promise every set is sized on the first call that needs it: no allocation inside a later (timed, overlapped) call */
-        for (int i = c->input_ready ? 0 : set; i < (c->input_ready ? LC3D_SETS : set + 1); i++)
-            if (c->dump_capv[i] < need) { if (c->d_dumpv[i]) HIPCHK(hipFree(c->d_dumpv[i])); c->d_dumpv[i] = nullptr; c->dump_capv[i] = 0; HIPCHK(hipMalloc((void**)&c->d_dumpv[i], need * sizeof(int))); c->dump_capv[i] = need; }
-        ddump = c->d_dumpv[set];
-    }
-    /* ahead of it: the 12.8 kHz resampler of all frames at once and its HP50 recurrence one stream per lane (lc3_enc_pre.inc) */
-    float* dy12 = nullptr;
-    if (!dtr && !c->fused) {
-        const size_t need = (size_t)c->ncs * n_frames * 128;
-        const int yb = c->input_ready ? c->row_par : 0;      /* two buffers under the input-ready promise: the next call's resampler may run beside this call's pitch kernel */
-        for (int i = c->input_ready ? 0 : yb; i < (c->input_ready ? LC3D_SETS : yb + 1); i++)
-            if (c->y12_cap[i] < need) { if (c->d_y12[i]) HIPCHK(hipFree(c->d_y12[i])); c->d_y12[i] = nullptr; c->y12_cap[i] = 0; HIPCHK(hipMalloc((void**)&c->d_y12[i], need * sizeof(float))); c->y12_cap[i] = need; }
-        dy12 = c->d_y12[yb];
-    }
-    const bool split = dy12 && ddump && !c->opt.no_split;
-    if (dt0 == 0) {   /* per channel-frame status bits (LC3D_ENC_ST_*), cleared per call: by the stream that runs the kernel that sets them (the writer's, on the pipelined path) */
-        const size_t need = (size_t)c->ncs * dT;
-        for (int i = c->input_ready ? 0 : set; i < (c->input_ready ? LC3D_SETS : set + 1); i++)
-            if (c->status_capv[i] < need) { if (c->d_statusv[i]) HIPCHK(hipFree(c->d_statusv[i])); c->d_statusv[i] = nullptr; c->status_capv[i] = 0; HIPCHK(hipMalloc((void**)&c->d_statusv[i], need)); c->status_capv[i] = need; }
-        c->d_status = c->d_statusv[set];
-        if (!split) HIPCHK(hipMemsetAsync(c->d_status, 0, need, s));
-        c->status_frames = dT;
-    }
-    bool rate_on_side = false;
-    float* rows_for_pack = nullptr; const float* frec_for_pack = nullptr;      /* pipelined path: the bitstream writer starts from the shaped spectra (frame-parallel tail, one frame per lane) */
-    const int mc = c->big ? LC3D_MEMCAP_BIG : LC3D_MEMCAP_STD;
-    if (!split) {
-        if (c->big && dbw) return 1;                          /* no such kernel (LC3_OW_KERNELS) */
-        c->ahead_ok = 0; c->last_frec = nullptr; c->last_frec_frames = 0; c->cfg_fresh = 0;
-        /* everything in lc3_encode_kernel (traced, diagnostic and very short launches), behind the 12.8 kHz pre-kernels when they apply */
-        if (dy12) {
-            launch_resample(c, s, dpcm, bitdepth, n_frames, 0, n_frames, mc, dy12, c->d_state + LC3D_ST_XPREV, c->state_words);
-            hipLaunchKernelGGL(lc3_enc_hp50_kernel, dim3((unsigned)((c->ncs + WAVE - 1) / WAVE)), dim3(WAVE), 0, s, c->d_plan, c->d_state, c->state_words, LC3D_ST_SCAL(mc), n_frames, 0, n_frames, c->ncs, dy12);
-            HIPCHK(hipGetLastError());
-        }
-        if (dbw && bw_to(c, s)) return 1;
-        /* the one-wave kernel of this call by layout and optional argument groups (lc3_kernel_decls.h: LC3_OW_KERNELS), or its _fmt twin */
-        const long long* pt = c->pk.on ? c->pk.tab : nullptr;         /* packed output: the _pk kernels, frames at the offsets of the call's table */
-        const int key = OW_KEY(c->big != 0, dfsz != nullptr, dbw != nullptr, pt != nullptr);
-#define OW_LAUNCH(name, big, var, vbw, pk) \
-        if (key == OW_KEY(big, var, vbw, pk) && placed) \
-            hipLaunchKernelGGL(name##_plc, dim3(c->ncs), dim3(WAVE), 0, s, c->d_plan, c->d_chans, c->d_state, dpcm, bitdepth, n_frames, \
-                               dout, pt ? 0 : out_stride, c->ncs, dtr, ddump, dstride, dy12, c->d_status, dT, dt0, (const float*)nullptr, (const float*)nullptr, \
-                               (const float*)nullptr LC3_OW_OPT(LC3_OW_VALS_, var, vbw, pk), c->plo, c->plcap); \
-        else if (key == OW_KEY(big, var, vbw, pk)) \
-            hipLaunchKernelGGL(fmt_plain ? name : fmt_wire ? name##_wire : name##_fmt, dim3(c->ncs), dim3(WAVE), 0, s, c->d_plan, c->d_chans, c->d_state, dpcm, bitdepth, n_frames, \
-                               dout, pt ? 0 : out_stride, c->ncs, dtr, ddump, dstride, dy12, c->d_status, dT, dt0, (const float*)nullptr, (const float*)nullptr, \
-                               (const float*)nullptr LC3_OW_OPT(LC3_OW_VALS_, var, vbw, pk)); \
-        else
-        LC3_OW_KERNELS(OW_LAUNCH) return 1;
-#undef OW_LAUNCH
-    } else {
-        /* The pipelined path.  Per run of frames: on one side stream the pitch chain (resampler per frame, HP50 one stream per lane, OLPA +
-         * LTPF one stream per wave); on another the frame-parallel front (MDCT ... scale factors), the attack decision and the SNS quantiser
-         * (one frame per lane); on the launch stream the shape kernel (SNS shaping, TNS, log energies: frame-parallel) and behind it the rate
-         * chain (lc3_enc_rate_kernel: rate loop, bisection, first quantisation), which also waits for the pitch chain.  Everything behind the
-         * chain - gain adjustment, second quantisation, noise level, residual - is frame-parallel again and runs one frame per lane at the head
-         * of the bitstream writer, once per call.  The side kernels of run k+1 are resident beside the launch stream's kernels of run k. */
-        /* spectrum rows and records of all dT frames of the call (a call through host pointers comes in pieces: rows dt0 ...): two sets under
-         * the input-ready promise (consecutive calls overlap: the side kernels of a call write one set while the bitstream writer of the call
-         * before still reads the other), one otherwise */
-        const int hb_ = set;
-        const size_t ns = (size_t)c->ncs * dT * c->srow, nr = (size_t)c->ncs * dT * FR_WORDS;
-        for (int i = c->input_ready ? 0 : hb_; i < (c->input_ready ? LC3D_SETS : hb_ + 1); i++) {
-            if (c->spec_cap[i] < ns) { if (c->d_spec[i]) HIPCHK(hipFree(c->d_spec[i])); c->d_spec[i] = nullptr; c->spec_cap[i] = 0; HIPCHK(hipMalloc((void**)&c->d_spec[i], ns * sizeof(float))); c->spec_cap[i] = ns; }
-            if (c->frec_cap[i] < nr) { if (c->d_frec[i]) HIPCHK(hipFree(c->d_frec[i])); c->d_frec[i] = nullptr; c->frec_cap[i] = 0; HIPCHK(hipMalloc((void**)&c->d_frec[i], nr * sizeof(float))); c->frec_cap[i] = nr; }
-        }
-        for (int i = 0; i < LC3D_SETS + 1; i++) if (!c->d_xnext[i]) HIPCHK(hipMalloc((void**)&c->d_xnext[i], (size_t)c->ncs * mc * sizeof(float)));
-        if (!c->s_pre) {
-            {   /* Two side streams, no third.  HIP (four hardware queues by default) gave the FIRST side stream a batch creates a queue of its own and put all later ones
-                 * together on another - and kernels of two streams on one queue run one after the other.  Round 3's separate rate stream therefore shared the front stream's
-                 * queue (timeline of c5: 2.9 of the call's 3.0 ms on that one queue).  A rate chain that leaves the caller's stream now runs ON one of the two side streams,
-                 * chosen per call (below): the same packets in the same queue, by choice instead of by creation order. */
-                for (int i = 0; i < c->opt.stream_skip; i++) { hipStream_t d; HIPCHK(hipStreamCreateWithFlags(&d, hipStreamNonBlocking)); }      /* diagnostic: shifts the assignment (never destroyed) */
-                int plo = 0, phi = 0; (void)hipDeviceGetStreamPriorityRange(&plo, &phi);       /* least, greatest */
-                const int prio = c->opt.side_prio == 1 ? plo : c->opt.side_prio == 2 ? phi : 0;
-                if (c->opt.stream_order) { HIPCHK(hipStreamCreateWithPriority(&c->s_fr, hipStreamNonBlocking, prio)); HIPCHK(hipStreamCreateWithPriority(&c->s_pre, hipStreamNonBlocking, prio)); }
-                else { HIPCHK(hipStreamCreateWithPriority(&c->s_pre, hipStreamNonBlocking, prio)); HIPCHK(hipStreamCreateWithPriority(&c->s_fr, hipStreamNonBlocking, prio)); }
-            }
-            /* LC3PLUS_ENC_STREAMS=5: the pitch kernel and the one-frame-per-lane kernels on streams of their own (pays only where the HIP runtime has
-             * hardware queues for them: GPU_MAX_HW_QUEUES >= 6) */
-            { c->s_pit = c->s_pre; c->s_ln = c->s_fr;
-              if (c->opt.streams5) { HIPCHK(hipStreamCreateWithFlags(&c->s_pit, hipStreamNonBlocking)); HIPCHK(hipStreamCreateWithFlags(&c->s_ln, hipStreamNonBlocking)); } }
-            for (int i = 0; i < LC3D_MAX_RUNS; i++) { HIPCHK(hipEventCreateWithFlags(&c->ev_h[i], hipEventDisableTiming)); HIPCHK(hipEventCreateWithFlags(&c->ev_m[i], hipEventDisableTiming)); HIPCHK(hipEventCreateWithFlags(&c->ev_v[i], hipEventDisableTiming)); }
-            for (int i = 0; i < 2; i++) { c->s_pk[i] = NULL; HIPCHK(hipEventCreateWithFlags(&c->ev_pk[i], hipEventDisableTiming)); }
-            HIPCHK(hipEventCreateWithFlags(&c->ev_rate, hipEventDisableTiming));
-            HIPCHK(hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
-            for (int i = 0; i < LC3D_SETS; i++) HIPCHK(hipEventCreateWithFlags(&c->ev_done[i], hipEventDisableTiming));
-            for (int i = 0; i < LC3D_MAX_RUNS; i++) { HIPCHK(hipEventCreateWithFlags(&c->ev_p[i], hipEventDisableTiming)); HIPCHK(hipEventCreateWithFlags(&c->ev_f[i], hipEventDisableTiming)); }
-        }
-        float* dspec = c->d_spec[hb_]; float* dfrec = c->d_frec[hb_];
-        rows_for_pack = dspec; frec_for_pack = dfrec;
-        c->last_frec = dfrec; c->last_frec_frames = dT;
-        const int runf = c->opt.run_frames ? c->opt.run_frames : c->input_ready ? LC3D_RUN_FRAMES_READY : LC3D_RUN_FRAMES;
-        int R = (n_frames + runf - 1) / runf;              /* runs of frames */
-        if (R > LC3D_MAX_RUNS) R = LC3D_MAX_RUNS;
-        if (R < 1) R = 1;
-        if (c->opt.runs) R = c->opt.runs;
-        const int Tr = (n_frames + R - 1) / R;
-        /* Where the side kernels of this call may start.  Normally behind everything the caller queued on s before the call (the PCM may
-         * come from there).  With lc3hip_set_input_ready - the PCM of a call is complete when the call is made - and a previous call of
-         * the same shape on the same stream, they need not wait for that call's chain and bitstream writer: their streams carry on in
-         * their own order, writing the other set of rows and records (the set they write now was last read by the writer of the call before
-         * the previous one: ev_done); the MDCT memory before frame 0 is read from the previous call's hand-over (two alternating buffers),
-         * not from the state that call's last rate kernel is still to update. */
-        const int amax = c->opt.ahead_max ? c->opt.ahead_max : LC3D_AHEAD_MAX_FRAMES;
-        /* A configuration copy queued behind the previous call (lc3hip_upload_chans_async) is on s, which a call that overlaps does not wait for: only a
-         * per-frame-bandwidth call overlaps it, and only when that copy changed nothing but the bandwidth words, which its kernels do not read (the other words
-         * are rewritten with their own values).  A call that forks from s is behind the copy, and so is everything after it. */
-        const bool cfg_ok = c->cfg_fresh == 0 || (c->cfg_fresh == 1 && dbw);
-        const bool ahead = c->input_ready && n_frames <= amax && c->ahead_ok && c->ahead_T == n_frames && c->ahead_R == R && c->last_stream == s && dt0 == 0 && dT == n_frames && pack && cfg_ok;
-        if (!ahead) c->cfg_fresh = 0;
-        float* xn_w = c->d_xnext[c->xn_par];                         /* written by this call's front kernel */
-        /* one buffer more than calls in flight: the one written now was last read by the call LC3D_SETS back (its resampler and front) and by the
-         * rate kernel of the call before that, all finished before the bitstream writer this call's side streams have waited for */
-        const float* xprev = ahead ? c->d_xnext[(c->xn_par + LC3D_SETS) % (LC3D_SETS + 1)] : c->d_state + LC3D_ST_XPREV;
-        const int xprev_stride = ahead ? mc : c->state_words;
-        const bool five = c->s_pit != c->s_pre;
-        /* The rate chain on a stream of its own, so that the rate kernel of call k+1 runs beside the bitstream writer of call k (which stays on the
-         * caller's stream: it is what the caller waits for).  It pays where the caller's stream - rate kernel + writer - is the longest of the three:
-         * large frames (the writer's work grows with the bytes: c96 22 -> 32 Mframes/s, c5 77 -> 83) and short calls (c3 +3 %); on 80-byte frames in
-         * calls of 64 (c1) a fourth side stream costs 0 ... 11 % (it shares one of HIP's four hardware queues with another, depending on what else the
-         * process created), and on c4 4 %.  LC3PLUS_ENC_RATE_STREAM=0 / 1 forces the choice (diagnostic). */
-        const int rt_env = c->opt.rate_stream;
-        const bool want_rt = rt_env == 1 || (rt_env < 0 && !c->big && (c->mean_nbytes >= 120 || n_frames <= 32));      /* large layout (c96, with round 4's writer): 36.6 on the caller's stream against 33.9 / 34.5 on the front / pitch stream */
-        /* ... and then on which side stream: behind the pitch kernel (it waits for the shape kernel's event) or behind the shape kernel (it waits for the pitch kernel's).
-         * Measured (Mframes/s, front stream / pitch stream): 48 kHz / 10 ms x 64 frames at 120 bytes 91.6 / 102.5, 160: 88.5 / 98.0, 240: 82.0 / 88.0, 400: 72.8 / 75.2, c5 88.3 / 97.1 (calls of
-         * 32: 82.7 / 88.5); 80-byte frames in calls of 6: 51.3 / 60.4, 8: 62.3 / 68.1, 12: 72.4 / 88.6, 14: 80.6 / 88.4, 18: 85.3 / 90.8, 28: 93.4 / 95.5, 32: 94.6 / 100.9 - but of 16: 94.2 / 92.6 (c3 94.1 / 89.8),
-         * 20: 93.8 / 91.0, 24: 96.4 / 92.9, and c96 32.8 / 30.8.  The pitch stream is the lighter one; behind the shape kernel the rate kernel blocks nothing while it waits, which wins where the
-         * front stream is at its best (calls of 16 ... 24 frames in whole groups of four - lc3_enc_front4_kernel's unit) and in the large layout. */
-        const bool on_pre = c->opt.rate_on >= 0 ? c->opt.rate_on == 1 : !(c->big || (c->mean_nbytes < 120 && n_frames >= 16 && n_frames <= 24 && (n_frames & 3) == 0));
-        hipStream_t rts = want_rt ? (on_pre ? c->s_pit : c->s_ln) : NULL;          /* NULL: the rate kernels run on the caller's stream */
-        if (!ahead) {
-            HIPCHK(hipEventRecord(c->ev_fork, s)); HIPCHK(hipStreamWaitEvent(c->s_pre, c->ev_fork, 0)); HIPCHK(hipStreamWaitEvent(c->s_fr, c->ev_fork, 0));
-            if (five) { HIPCHK(hipStreamWaitEvent(c->s_pit, c->ev_fork, 0)); HIPCHK(hipStreamWaitEvent(c->s_ln, c->ev_fork, 0)); }
-        } else {
-            HIPCHK(hipStreamWaitEvent(c->s_pre, c->ev_m[R - 1], 0));    /* the resampler reads the hand-over the previous call's last front kernel wrote */
-            HIPCHK(hipStreamWaitEvent(c->s_pre, c->ev_done[hb_], 0)); HIPCHK(hipStreamWaitEvent(c->s_fr, c->ev_done[hb_], 0));
-            if (five) { HIPCHK(hipStreamWaitEvent(c->s_pit, c->ev_done[hb_], 0)); HIPCHK(hipStreamWaitEvent(c->s_ln, c->ev_done[hb_], 0));
-                        if (c->any_attack) HIPCHK(hipStreamWaitEvent(c->s_fr, c->ev_f[R - 1], 0)); }      /* the front reads the attack detector's filter memory the previous call's attack kernel leaves */
-        }
-        /* The 12.8 kHz pre-kernels run ahead in larger pieces than the runs: the HP50 kernel (one stream per lane, B / 64 waves) costs ~0.1 ms
-         * per launch whatever the frame count, which per run would make its stream the slowest.  First piece = the first run (the rate
-         * kernel should start early), then three runs at a time, in stream order between the pitch kernels that need them.  (More side
-         * streams than these two do not help: HIP multiplexes streams onto a few hardware queues and kernels of two streams that share
-         * one run back to back.) */
-        hipStream_t rs = s;                                  /* where the rate kernels run */
-        for (int k = 0, tb = 0, hb = 0, hk = 0; tb < n_frames; k++, tb += Tr) {
-            const int nt = n_frames - tb < Tr ? n_frames - tb : Tr;
-            if (tb >= hb) {
-                const int prn = c->opt.pre_runs;
-                const int hn0 = hk == 0 ? Tr : prn * Tr, hn = n_frames - hb < hn0 ? n_frames - hb : hn0;
-                DUPL('r') launch_resample(c, c->s_pre, dpcm, bitdepth, n_frames, hb, hn, mc, dy12, xprev, xprev_stride);
-                DUPL('h') hipLaunchKernelGGL(lc3_enc_hp50_kernel, dim3((unsigned)((c->ncs + WAVE - 1) / WAVE)), dim3(WAVE), 0, c->s_pre, c->d_plan, c->d_state, c->state_words, LC3D_ST_SCAL(mc), n_frames, hb, hn, c->ncs, dy12);
-                HIPCHK(hipGetLastError());
-                hb += hn; hk++;
-                if (five) { HIPCHK(hipEventRecord(c->ev_h[k], c->s_pre)); HIPCHK(hipStreamWaitEvent(c->s_pit, c->ev_h[k], 0)); }
-            }
-            const int p2 = c->opt.pitch2;
-            if (p2 && (c->len12 == 128 || c->len12 == 64 || c->len12 == 32)) {
-                auto pk = c->len12 == 128 ? lc3_enc_pitch2_kernel : c->len12 == 64 ? lc3_enc_pitch2_kernel_l64 : lc3_enc_pitch2_kernel_l32;
-                DUPL('p') hipLaunchKernelGGL(pk, dim3((unsigned)((c->ncs + 1) / 2)), dim3(WAVE), 0, c->s_pit, c->d_plan, c->d_chans, c->d_state, c->state_words, mc, dy12, n_frames, tb, nt, c->ncs, dfrec, dT, dt0);
-            }
-            else DUPL('p') hipLaunchKernelGGL(lc3_enc_pitch_kernel, dim3(c->ncs), dim3(WAVE), 0, c->s_pit, c->d_plan, c->d_chans, c->d_state, c->state_words, mc, dy12, n_frames, tb, nt, c->ncs, dfrec, dT, dt0);
-            HIPCHK(hipGetLastError());
-            HIPCHK(hipEventRecord(c->ev_p[k], c->s_pit));
-            const int scf_wave = c->opt.scf_wave;
-            const int fpw = nt < FRONT_FPW ? nt : FRONT_FPW;
-            const unsigned fruns = (unsigned)((nt + fpw - 1) / fpw);
-            const int f4 = c->opt.front4;
-            if (f4 && !c->big && !scf_wave && c->N == 480 && c->la == 180 && (c->ylen & 15) == 0) {
-                if (placed) hipLaunchKernelGGL(lc3_enc_front4_kernel_plc, dim3((unsigned)c->ncs * (unsigned)((nt + 3) / 4)), dim3(WAVE), 0, c->s_fr, c->d_plan, c->d_chans, c->d_state, dpcm, bitdepth, n_frames, tb, nt, c->ncs, dspec, c->srow, dT, dt0, dfrec, xn_w, xprev, xprev_stride, c->plo, c->plcap);
-                else DUPL('f') hipLaunchKernelGGL(fmt_plain ? lc3_enc_front4_kernel : fmt_wire ? lc3_enc_front4_kernel_wire : lc3_enc_front4_kernel_fmt, dim3((unsigned)c->ncs * (unsigned)((nt + 3) / 4)), dim3(WAVE), 0, c->s_fr, c->d_plan, c->d_chans, c->d_state, dpcm, bitdepth, n_frames, tb, nt, c->ncs, dspec, c->srow, dT, dt0, dfrec, xn_w, xprev, xprev_stride);
-            } else if (f4 && c->fm_frames && !scf_wave) {
-                if (placed) hipLaunchKernelGGL(lc3_enc_frontm_kernel_plc, dim3((unsigned)c->ncs * (unsigned)((nt + c->fm_frames - 1) / c->fm_frames)), dim3(WAVE), 0, c->s_fr, c->d_plan, c->d_chans, c->d_state, dpcm, bitdepth, n_frames, tb, nt, c->fm_frames, c->ncs, dspec, c->srow, dT, dt0, dfrec, xn_w, xprev, xprev_stride, c->plo, c->plcap);
-                else hipLaunchKernelGGL(fmt_plain ? lc3_enc_frontm_kernel : fmt_wire ? lc3_enc_frontm_kernel_wire : lc3_enc_frontm_kernel_fmt, dim3((unsigned)c->ncs * (unsigned)((nt + c->fm_frames - 1) / c->fm_frames)), dim3(WAVE), 0, c->s_fr, c->d_plan, c->d_chans, c->d_state, dpcm, bitdepth, n_frames, tb, nt, c->fm_frames, c->ncs, dspec, c->srow, dT, dt0, dfrec, xn_w, xprev, xprev_stride);
-            }
-            else if (placed) hipLaunchKernelGGL(c->big ? lc3_enc_front_kernel_big_plc : lc3_enc_front_kernel_plc, dim3((unsigned)c->ncs * fruns), dim3(WAVE), 0, c->s_fr, c->d_plan, c->d_chans, c->d_state, dpcm, bitdepth, n_frames, tb, nt, fpw, c->ncs, dspec, c->srow, dT, dt0, dfrec, xn_w, xprev, xprev_stride, scf_wave, c->plo, c->plcap);
-            else if (c->big) hipLaunchKernelGGL(fmt_plain ? lc3_enc_front_kernel_big : fmt_wire ? lc3_enc_front_kernel_big_wire : lc3_enc_front_kernel_big_fmt, dim3((unsigned)c->ncs * fruns), dim3(WAVE), 0, c->s_fr, c->d_plan, c->d_chans, c->d_state, dpcm, bitdepth, n_frames, tb, nt, fpw, c->ncs, dspec, c->srow, dT, dt0, dfrec, xn_w, xprev, xprev_stride, scf_wave);
-            else DUPL('f') hipLaunchKernelGGL(fmt_plain ? lc3_enc_front_kernel : fmt_wire ? lc3_enc_front_kernel_wire : lc3_enc_front_kernel_fmt, dim3((unsigned)c->ncs * fruns), dim3(WAVE), 0, c->s_fr, c->d_plan, c->d_chans, c->d_state, dpcm, bitdepth, n_frames, tb, nt, fpw, c->ncs, dspec, c->srow, dT, dt0, dfrec, xn_w, xprev, xprev_stride, scf_wave);
-            HIPCHK(hipEventRecord(c->ev_m[k], c->s_fr));                 /* the MDCT memory hand-over and the spectrum rows of the run are written */
-            if (five) HIPCHK(hipStreamWaitEvent(c->s_ln, c->ev_m[k], 0));
-            const int fuse_vq = !scf_wave && !c->any_attack && c->opt.fuse_vq;
-            if (!scf_wave) DUPL('e') hipLaunchKernelGGL(lc3_enc_scf_lane_kernel, dim3((unsigned)(((long long)c->ncs * nt + WAVE - 1) / WAVE)), dim3(WAVE), 0, c->s_ln, c->d_plan, dT, dt0 + tb, nt, c->ncs, dspec, c->srow, dfrec, fuse_vq);
-            if (c->any_attack)
-                hipLaunchKernelGGL(lc3_enc_attack_kernel, dim3((unsigned)((c->ncs + WAVE - 1) / WAVE)), dim3(WAVE), 0, c->s_ln, c->d_plan, c->d_chans, c->d_state, c->state_words, LC3D_ST_SCAL(mc), dfrec, dT, dt0, tb, nt, c->ncs);
-            const long long nfr = (long long)c->ncs * nt;
-            if (!fuse_vq) DUPL('v') hipLaunchKernelGGL(lc3_enc_snsvq_kernel, dim3((unsigned)((nfr + WAVE - 1) / WAVE)), dim3(WAVE), 0, c->s_ln, c->d_plan, dfrec, dT, dt0, tb, nt, c->ncs, c->any_attack);
-            {   /* shaping, TNS and the stateless half of the gain estimate: frame-parallel, behind the quantiser (LC3PLUS_ENC_SHAPE_ON_S=1, diagnostic: on the
-                 * launch stream in front of the rate kernel instead) */
-                const int sfpw = c->opt.shape_fpw ? c->opt.shape_fpw : SHAPE_FPW, son = c->opt.shape_on_s;
-                const int spw = nt < sfpw ? nt : sfpw;
-                const unsigned sruns = (unsigned)((nt + spw - 1) / spw);
-                /* LC3PLUS_ENC_SHAPE_ON_PITCH=1 (diagnostic): the shape kernel on the pitch stream, behind the pitch kernel, waiting for the quantiser's event.  Tried for c96, whose
-                 * front stream is the longest (3.6 of a 3.6 ms call) and whose pitch stream the lightest (1.4): the next call's pitch chain then queues behind a shape kernel that
-                 * waits for the front stream - 37.3 -> 31.0 Mframes/s; c1 111 -> 101, c5 97 -> 81, c3 93 -> 83; only c4 - long calls of 2.5 ms high-resolution frames, four runs per call, the front stream 8.5 of the 8.6 ms - gains (122.0 -> 126.1): on for that shape only. */
-                const bool sop = !son && (c->opt.shape_on_pitch >= 0 ? c->opt.shape_on_pitch == 1 : (c->hr && c->N == 240 && n_frames >= 128));      /* c4's shape: calls of 128 / 256 frames 123.8 -> 126.0, 122.0 -> 126.1 */
-                hipStream_t ss = son ? s : sop ? c->s_pit : c->s_ln;
-                rs = (son || !rts) ? s : rts;
-                if (son) { HIPCHK(hipEventRecord(c->ev_f[k], c->s_ln)); HIPCHK(hipStreamWaitEvent(s, c->ev_f[k], 0)); }
-                if (sop) { HIPCHK(hipEventRecord(c->ev_v[k], c->s_ln)); HIPCHK(hipStreamWaitEvent(ss, c->ev_v[k], 0)); }
-                const int swave = c->opt.shape_wave;
-                if (dbw && bw_to(c, ss)) return 1;
-                if (dbw && !swave) hipLaunchKernelGGL(lc3_enc_shape_lane_kernel_vbw, dim3((unsigned)(((long long)c->ncs * nt + WAVE - 1) / WAVE)), dim3(WAVE), 0, ss, c->d_plan, c->d_chans, dT, dt0 + tb, nt, c->ncs, dspec, c->srow, dfrec, dbw);
-                else if (dbw) hipLaunchKernelGGL(lc3_enc_shape_kernel_vbw, dim3((unsigned)c->ncs * sruns), dim3(WAVE), 0, ss, c->d_plan, c->d_chans, dT, dt0 + tb, nt, spw, c->ncs, dspec, c->srow, dfrec, dbw);
-                else if (!swave) DUPL('a') hipLaunchKernelGGL(lc3_enc_shape_lane_kernel, dim3((unsigned)(((long long)c->ncs * nt + WAVE - 1) / WAVE)), dim3(WAVE), 0, ss, c->d_plan, c->d_chans, dT, dt0 + tb, nt, c->ncs, dspec, c->srow, dfrec);
-                else if (c->big) hipLaunchKernelGGL(lc3_enc_shape_kernel_big, dim3((unsigned)c->ncs * sruns), dim3(WAVE), 0, ss, c->d_plan, c->d_chans, dT, dt0 + tb, nt, spw, c->ncs, dspec, c->srow, dfrec);
-                else DUPL('a') hipLaunchKernelGGL(lc3_enc_shape_kernel, dim3((unsigned)c->ncs * sruns), dim3(WAVE), 0, ss, c->d_plan, c->d_chans, dT, dt0 + tb, nt, spw, c->ncs, dspec, c->srow, dfrec);
-                HIPCHK(hipGetLastError());
-                if (!son) { HIPCHK(hipEventRecord(c->ev_f[k], ss)); HIPCHK(hipStreamWaitEvent(rs, c->ev_f[k], 0)); }
-            }
-            HIPCHK(hipStreamWaitEvent(rs, c->ev_p[k], 0));
-            if (k == 0 && c->rate_armed) HIPCHK(hipStreamWaitEvent(rs, c->ev_rate, 0));      /* the rate chain is a chain: behind the previous call's, whichever stream that ran on */
-            const int last = tb + nt >= n_frames;            /* behind the last frame of this launch the MDCT memory goes into the state */
-            if (c->big) hipLaunchKernelGGL(lc3_enc_rate_kernel_big, dim3((unsigned)((c->ncs + RATE_WG - 1) / RATE_WG)), dim3(RATE_WG * WAVE), 0, rs, c->d_plan, c->d_chans, c->d_state, dT, dt0 + tb, nt, c->ncs, dspec, c->srow, dfrec, xn_w, last);
-            else DUPL('s') hipLaunchKernelGGL(lc3_enc_rate_kernel, dim3((unsigned)((c->ncs + RATE_WG - 1) / RATE_WG)), dim3(RATE_WG * WAVE), 0, rs, c->d_plan, c->d_chans, c->d_state, dT, dt0 + tb, nt, c->ncs, dspec, c->srow, dfrec, xn_w, last);
-            HIPCHK(hipGetLastError());
-        }
-        HIPCHK(hipEventRecord(c->ev_rate, rs)); c->rate_armed = 1; rate_on_side = rs != s;
-        if (rs != s) HIPCHK(hipStreamWaitEvent(s, c->ev_rate, 0));      /* the writer (and whatever the caller queues next) behind the rate chain */
-        c->ahead_ok = (dt0 == 0 && dT == n_frames && pack) ? 1 : 0; c->ahead_T = n_frames; c->ahead_R = R;
-        c->xn_par = (c->xn_par + 1) % (LC3D_SETS + 1);
-    }
-    if (ddump && pack) {
-        HIPCHK(hipGetLastError());
-        const int wpg = c->opt.pack_wpg;                  /* waves per workgroup of the writer (they share the coder's tables in LDS) */
-        const size_t per_wave = (size_t)PK_XBUF * WAVE * sizeof(unsigned);
-        const long long tasks = (long long)c->ncs * dT, per_wg = (long long)wpg * WAVE;
-        /* The writer codes one frame per lane: its duration is the latency of the LARGEST frame of the batch (c5: 1.7 ms for 400 bytes, c96: 3.2 ms), whatever the
-         * batch size, and on the caller's stream the writers of consecutive calls run one after the other.  Where that is the longest stream (the rule that moves the
-         * rate chain off the caller's stream: large frames, short calls) and calls overlap, the writers CAN alternate between two side streams - writer k + 1 beside
-         * writer k, each with its own set of scratch rows and status bytes, the caller's stream waiting for their events in call order.  Measured (Mframes/s,
-         * off / on): with HIP's default four hardware queues c5 87.0 / 80.0, c96 32.1 / 28.7, c3 85.1 / 73.0 - six streams share four queues and kernels of two
-         * streams on one queue run back to back; with GPU_MAX_HW_QUEUES=8 c5 90.9 / 92.4, c96 28.8 / 33.9, c3 85.5 / 85.8.  So it is a deployment switch
-         * (LC3PLUS_ENC_PACK_STREAM=1 together with GPU_MAX_HW_QUEUES >= 6), off by default. */
-        const int pk_env = c->opt.pack_stream;
-        const bool side = split && rate_on_side && c->input_ready && dt0 == 0 && dT == n_frames && pk_env == 1;
-        hipStream_t ps = s;
-        if (side) {
-            /* behind this call's rate chain only - NOT behind the caller's stream, whose tail is the writer of the call before: under the input-ready promise the
-             * output buffer of a call, like its PCM, is the caller's to have ready (include/lc3plus_batch.h) */
-            if (!c->s_pk[c->pk_par]) HIPCHK(hipStreamCreateWithFlags(&c->s_pk[c->pk_par], hipStreamNonBlocking));
-            ps = c->s_pk[c->pk_par];
-            HIPCHK(hipStreamWaitEvent(ps, c->ev_rate, 0));
-        }
-        if (side && c->pk.on) HIPCHK(hipStreamWaitEvent(ps, c->ev_scan, 0));     /* packed output: behind the call's scan (the table the writers read) */
-        if (split) HIPCHK(hipMemsetAsync(c->d_status, 0, (size_t)c->ncs * dT, ps));
-        /* large frames: tail + writer a frame per wave (lc3_enc_tailw_kernel, lc3_enc_rate.inc), launched first - its waves are the long ones */
-        const int big_from = (split && c->opt.tailw_bytes && c->max_nbytes >= c->opt.tailw_bytes && !c->pk.on) ? c->opt.tailw_bytes : 0;   /* (no packed form) */
-        if (big_from) {
-            const int fpw = dT < 4 ? dT : 4;
-            const unsigned wruns = (unsigned)((dT + fpw - 1) / fpw);
-            if (c->big) hipLaunchKernelGGL(lc3_enc_tailw_kernel_big, dim3((unsigned)c->ncs * wruns), dim3(WAVE), 0, ps, c->d_plan, c->d_chans, dT, dT, fpw, c->ncs, rows_for_pack, c->srow, frec_for_pack, dout, out_stride, c->d_status, big_from);
-            else hipLaunchKernelGGL(lc3_enc_tailw_kernel, dim3((unsigned)c->ncs * wruns), dim3(WAVE), 0, ps, c->d_plan, c->d_chans, dT, dT, fpw, c->ncs, rows_for_pack, c->srow, frec_for_pack, dout, out_stride, c->d_status, big_from);
-            HIPCHK(hipGetLastError());
-        }
-        const bool two = split && c->opt.pack_split == 1;
-        if (!big_from || c->min_nbytes < big_from) {
-            const dim3 grid((unsigned)((tasks + per_wg - 1) / per_wg)), block(wpg * WAVE);
-            const size_t dyn = per_wave * wpg + ((size_t)(c->opt.pack_pad_kb > 0 ? c->opt.pack_pad_kb : 0) << 10);
-            const long long* pt = c->pk.on ? c->pk.tab : nullptr;
-            if (two && pt) {
-                hipLaunchKernelGGL(lc3_enc_pack_head_kernel_pk, grid, block, 0, ps, c->d_plan, c->d_chans, ddump, dstride, dT, 0, dT, c->ncs, dout, 0, c->d_status, rows_for_pack, c->srow, frec_for_pack, big_from, pt);
-                hipLaunchKernelGGL(lc3_enc_pack_code_kernel_pk, grid, block, dyn, ps, c->d_plan, c->d_chans, ddump, dstride, dT, 0, dT, c->ncs, dout, 0, c->d_status, rows_for_pack, c->srow, frec_for_pack, big_from, pt);
-            } else if (two) {
-                hipLaunchKernelGGL(lc3_enc_pack_head_kernel, grid, block, 0, ps, c->d_plan, c->d_chans, ddump, dstride, dT, 0, dT, c->ncs, dout, out_stride, c->d_status, rows_for_pack, c->srow, frec_for_pack, big_from);
-                hipLaunchKernelGGL(lc3_enc_pack_code_kernel, grid, block, dyn, ps, c->d_plan, c->d_chans, ddump, dstride, dT, 0, dT, c->ncs, dout, out_stride, c->d_status, rows_for_pack, c->srow, frec_for_pack, big_from);
-            } else {
-                /* 96 or 128 registers (lc3_enc_pack.inc, the table at lc3_enc_pack_kernel_w5): five waves per SIMD pay for long calls of small 10 ms frames */
-                const bool w5 = c->opt.pack_w5 >= 0 ? c->opt.pack_w5 == 1 : (split && !c->big && !c->hr && c->N == 480 && dT >= 48 && c->max_nbytes <= 100);
-                auto pk = w5 ? lc3_enc_pack_kernel_w5 : lc3_enc_pack_kernel;
-                if (pt) hipLaunchKernelGGL(w5 ? lc3_enc_pack_kernel_w5_pk : lc3_enc_pack_kernel_pk, grid, block, dyn, ps, c->d_plan, c->d_chans, ddump, dstride,
-                                           dT, 0, dT, c->ncs, dout, 0, c->d_status, rows_for_pack, c->srow, frec_for_pack, big_from, pt);
-                else DUPL('k') hipLaunchKernelGGL(pk, grid, block, dyn, ps, c->d_plan, c->d_chans, ddump, dstride,
-                                   dT, 0, dT, c->ncs, dout, out_stride, c->d_status, rows_for_pack, c->srow, frec_for_pack, big_from);
-            }
-        }
-        if (split && c->input_ready) { HIPCHK(hipEventRecord(c->ev_done[c->row_par], ps)); c->row_par = (c->row_par + 1) % LC3D_SETS; }      /* this call's set of rows and records is free again */
-        if (side) { HIPCHK(hipEventRecord(c->ev_pk[c->pk_par], ps)); HIPCHK(hipStreamWaitEvent(s, c->ev_pk[c->pk_par], 0)); c->pk_par ^= 1; }
-    }
+    q.mc = c->big ? LC3D_MEMCAP_BIG : LC3D_MEMCAP_STD;
+    if (enc_size_set(c, &q, in_kernel_writer)) return 1;
+    if (q.split ? enc_pipelined(c, &q) : enc_one_wave(c, &q)) return 1;
+    if (q.ddump && pack && enc_writer(c, &q)) return 1;
     HIPCHK(hipGetLastError());
     c->last_stream = s;
     return 0;
@@ -678,11 +772,9 @@ static int encode_host(lc3hip_ctx* c, const void* pcm, int bitdepth, int n_frame
         HIPCHK(hipStreamCreateWithFlags(&c->s_h2d, hipStreamNonBlocking));
         for (int i = 0; i < 2; i++) { HIPCHK(hipEventCreateWithFlags(&c->ev_h2d[i], hipEventDisableTiming)); HIPCHK(hipEventCreateWithFlags(&c->ev_k[i], hipEventDisableTiming)); }
     }
-    if (c->hp_pcm_cap < cin) { for (int i = 0; i < 2; i++) { if (c->hp_dpcm[i]) HIPCHK(hipFree(c->hp_dpcm[i])); c->hp_dpcm[i] = nullptr; } c->hp_pcm_cap = 0;
-                               for (int i = 0; i < 2; i++) HIPCHK(hipMalloc(&c->hp_dpcm[i], cin)); c->hp_pcm_cap = cin; }
-    if (!pin_in && c->hp_pin_in_cap < cin) { for (int i = 0; i < 2; i++) { if (c->hp_pin_in[i]) HIPCHK(hipHostFree(c->hp_pin_in[i])); c->hp_pin_in[i] = nullptr; } c->hp_pin_in_cap = 0;
-                                             for (int i = 0; i < 2; i++) HIPCHK(hipHostMalloc(&c->hp_pin_in[i], cin, hipHostMallocDefault)); c->hp_pin_in_cap = cin; }
-    if (c->out_cap < out_bytes) { if (c->d_out) HIPCHK(hipFree(c->d_out)); c->d_out = nullptr; c->out_cap = 0; HIPCHK(hipMalloc((void**)&c->d_out, out_bytes)); c->out_cap = out_bytes; }
+    /* the two chunk slots and the output: no wait for the device - a call through host pointers returns when its work is done */
+    const lc3hip_buf dev[] = {{&c->hp_dpcm[0], cin, false}, {&c->hp_dpcm[1], cin, false}}, pin[] = {{&c->hp_pin_in[0], cin, true}, {&c->hp_pin_in[1], cin, true}};
+    if (grow_group(&c->hp_pcm_cap, cin, dev, 2, false) || (!pin_in && grow_group(&c->hp_pin_in_cap, cin, pin, 2, false)) || grow(&c->d_out, &c->out_cap, out_bytes, out_bytes, false)) return 1;
     const size_t in_pitch = (size_t)n_frames * fr_in;
     HIPCHK(hipEventRecord(c->ev0, s));
     HIPCHK(hipMemsetAsync(c->d_out, 0, out_bytes, s));
@@ -704,8 +796,7 @@ static int encode_host(lc3hip_ctx* c, const void* pcm, int bitdepth, int n_frame
     }
     HIPCHK(hipEventRecord(c->ev1, s));
     HIPCHK(hipMemcpyAsync(out, c->d_out, out_bytes, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    float ms = 0; if (hipEventElapsedTime(&ms, c->ev0, c->ev1) == hipSuccess) c->last_ms = ms;
+    SYNC_TIMED(c, s);
     return 0;
 }
 
@@ -713,61 +804,31 @@ extern "C" int lc3hip_upload_enc_table(void* ctx, const lc3d_chan* tab, int n)
 {
     lc3hip_ctx* c = (lc3hip_ctx*)ctx;
     HIPCHK(hipSetDevice(c->device));
-    if (c->d_etab) HIPCHK(hipFree(c->d_etab));
-    c->d_etab = nullptr;
-    HIPCHK(hipMalloc((void**)&c->d_etab, sizeof(lc3d_chan) * (size_t)n));
+    if (replace(&c->d_etab, sizeof(lc3d_chan) * (size_t)n)) return 1;      /* no wait of its own: lc3_host.c uploads the table once, before the first call that reads it */
     HIPCHK(hipMemcpy(c->d_etab, tab, sizeof(lc3d_chan) * (size_t)n, hipMemcpyHostToDevice));
     c->etab_attack = 0; c->etab_max = n - 1;
     for (int i = 1; i < n; i++) c->etab_attack |= tab[i].attack_handling != 0;
     return 0;
 }
-/* the stream-frame sizes of a per-frame-bitrate call to the device, queued on s ahead of its kernels: copied into pinned staging first, so that the caller's
- * array is free when the call returns; the buffer pair of the call LC3D_SETS back is waited for before it is written again */
+/* the stream-frame sizes of a per-frame-bitrate call through pinned staging (stage_words) to the device, queued on s ahead of its kernels */
 static int upload_fsz(lc3hip_ctx* c, const uint16_t* fsz_host, int n_frames, hipStream_t s, const uint16_t** dfsz, hipEvent_t* ev)
 {
     const size_t fb = sizeof(uint16_t) * (size_t)c->n_streams * n_frames;
-    const int k = c->fsz_set;
-    if (c->fsz_armed[k]) HIPCHK(hipEventSynchronize(c->ev_fsz[k]));
-    if (c->fsz_cap < fb) {
-        for (int i = 0; i < LC3D_SETS; i++) if (c->fsz_armed[i]) { HIPCHK(hipEventSynchronize(c->ev_fsz[i])); c->fsz_armed[i] = 0; }   /* no call reads them any more */
-        for (int i = 0; i < LC3D_SETS; i++) {
-            if (c->d_fsz[i]) HIPCHK(hipFree(c->d_fsz[i])); if (c->h_fsz[i]) HIPCHK(hipHostFree(c->h_fsz[i])); c->d_fsz[i] = nullptr; c->h_fsz[i] = nullptr;
-        }
-        c->fsz_cap = 0;
-        for (int i = 0; i < LC3D_SETS; i++) { HIPCHK(hipMalloc((void**)&c->d_fsz[i], fb)); HIPCHK(hipHostMalloc((void**)&c->h_fsz[i], fb, hipHostMallocDefault)); }
-        c->fsz_cap = fb;
-    }
-    if (!c->ev_fsz[0]) for (int i = 0; i < LC3D_SETS; i++) HIPCHK(hipEventCreateWithFlags(&c->ev_fsz[i], hipEventDisableTiming));
-    memcpy(c->h_fsz[k], fsz_host, fb);
-    HIPCHK(hipMemcpyAsync(c->d_fsz[k], c->h_fsz[k], fb, hipMemcpyHostToDevice, s));
-    *dfsz = c->d_fsz[k]; *ev = c->ev_fsz[k];
-    c->fsz_armed[k] = 1; c->fsz_set = (k + 1) % LC3D_SETS;
+    int k;
+    if (stage_words(&c->fsz, fsz_host, fb, &k)) return 1;
+    HIPCHK(hipMemcpyAsync(c->fsz.d[k], c->fsz.h[k], fb, hipMemcpyHostToDevice, s));
+    *dfsz = c->fsz.d[k]; *ev = c->fsz.ev[k];
     return 0;
 }
-/* the bandwidths in force of a per-frame-bandwidth call into pinned staging, so that the caller's array is free when the call returns (the buffer pair of the
- * call LC3D_SETS back is waited for before it is written again; sized on first use, a call of equal or smaller size allocates nothing); bw_to queues the copy */
+/* the bandwidths in force of a per-frame-bandwidth call into pinned staging (stage_words); bw_to queues the copy */
 static int stage_bw(lc3hip_ctx* c, const uint16_t* bw_host, int n_frames, const uint16_t** dbw, hipEvent_t* ev)
 {
     const size_t fb = sizeof(uint16_t) * (size_t)c->n_streams * n_frames;
-    const int k = c->bw_set;
-    if (c->bw_armed[k]) HIPCHK(hipEventSynchronize(c->ev_bw[k]));
-    if (c->bw_cap < fb) {
-        for (int i = 0; i < LC3D_SETS; i++) if (c->bw_armed[i]) { HIPCHK(hipEventSynchronize(c->ev_bw[i])); c->bw_armed[i] = 0; }      /* no call reads them any more */
-        for (int i = 0; i < LC3D_SETS; i++) {
-            if (c->d_bw[i]) HIPCHK(hipFree(c->d_bw[i])); if (c->h_bw[i]) HIPCHK(hipHostFree(c->h_bw[i])); c->d_bw[i] = nullptr; c->h_bw[i] = nullptr;
-        }
-        c->bw_cap = 0;
-        for (int i = 0; i < LC3D_SETS; i++) { HIPCHK(hipMalloc((void**)&c->d_bw[i], fb)); HIPCHK(hipHostMalloc((void**)&c->h_bw[i], fb, hipHostMallocDefault)); }
-        c->bw_cap = fb;
-    }
-    if (!c->ev_bwcp) {
-        for (int i = 0; i < LC3D_SETS; i++) HIPCHK(hipEventCreateWithFlags(&c->ev_bw[i], hipEventDisableTiming));
-        HIPCHK(hipEventCreateWithFlags(&c->ev_bwcp, hipEventDisableTiming));
-    }
-    memcpy(c->h_bw[k], bw_host, fb);
-    c->bw_src = c->h_bw[k]; c->bw_bytes = fb; c->bw_on = nullptr; c->pl.pending = 0;
-    *dbw = c->d_bw[k]; *ev = c->ev_bw[k];
-    c->bw_armed[k] = 1; c->bw_set = (k + 1) % LC3D_SETS;
+    int k;
+    if (stage_words(&c->bw, bw_host, fb, &k)) return 1;
+    if (!c->ev_bwcp) HIPCHK(hipEventCreateWithFlags(&c->ev_bwcp, hipEventDisableTiming));
+    c->bw_src = c->bw.h[k]; c->bw_bytes = fb; c->bw_on = nullptr; c->pl.pending = 0;
+    *dbw = c->bw.d[k]; *ev = c->bw.ev[k];
     return 0;
 }
 static int plan_launch(lc3hip_ctx* c, hipStream_t st);
@@ -777,7 +838,7 @@ static int pack_scan(lc3hip_ctx* c, hipStream_t st, int T, int slot /* the plan 
                      int plan_flags, int plan_nb)
 {
     const long long n = (long long)c->n_streams * T, nb = (n + PKS_TILE - 1) / PKS_TILE;
-    long long* tab = c->d_poff[slot]; long long* bsum = c->d_pbsum + (size_t)slot * c->pbsum_cap;
+    long long* tab = c->d_poff[slot]; long long* bsum = c->d_pbsum + (size_t)slot * PKS_SUMS(c->poff_cap);
     PkSrc q; q.fsz = fsz; q.pend = fsz ? nullptr : pend; q.chans = c->d_chans; q.channels = c->channels; q.order = c->pk.order; q.S = c->n_streams; q.T = T;
     hipLaunchKernelGGL(lc3_pack_sums_kernel, dim3((unsigned)nb), dim3(PKS_THREADS), 0, st, q, n, bsum);
     hipLaunchKernelGGL(lc3_pack_base_kernel, dim3(1), dim3(PKS_THREADS), 0, st, bsum, nb, c->pk.total);
@@ -790,10 +851,10 @@ static int pack_scan(lc3hip_ctx* c, hipStream_t st, int T, int slot /* the plan 
 }
 static int bw_to(lc3hip_ctx* c, hipStream_t st)
 {
-    const int k = (c->bw_set + LC3D_SETS - 1) % LC3D_SETS;                    /* the slot stage_bw filled for this call */
+    const int k = (c->bw.k + LC3D_SETS - 1) % LC3D_SETS;                      /* the slot stage_bw filled for this call */
     if (!c->bw_on) {
         if (c->pl.pending) { if (plan_launch(c, st)) return 1; }             /* words from device memory: the call's plan kernel writes them */
-        else HIPCHK(hipMemcpyAsync(c->d_bw[k], c->bw_src, c->bw_bytes, hipMemcpyHostToDevice, st));
+        else HIPCHK(hipMemcpyAsync(c->bw.d[k], c->bw_src, c->bw_bytes, hipMemcpyHostToDevice, st));
         HIPCHK(hipEventRecord(c->ev_bwcp, st)); c->bw_on = st;
     } else if (c->bw_on != st) HIPCHK(hipStreamWaitEvent(st, c->ev_bwcp, 0));
     return 0;
@@ -824,19 +885,19 @@ extern "C" int lc3hip_encode(void* ctx, const void* pcm, int pcm_on_device, int 
     const size_t out_bytes = (size_t)c->n_streams * n_frames * out_stride;
     const void* dpcm = pcm; uint8_t* dout = (uint8_t*)out;
     if (!pcm_on_device) {
-        if (c->pcm_cap < pcm_bytes) { if (c->d_pcm) HIPCHK(hipFree(c->d_pcm)); c->d_pcm = nullptr; c->pcm_cap = 0; HIPCHK(hipMalloc(&c->d_pcm, pcm_bytes)); c->pcm_cap = pcm_bytes; }
+        if (grow(&c->d_pcm, &c->pcm_cap, pcm_bytes, pcm_bytes, false)) return 1;      /* staging of host arrays (d_pcm, d_out, d_trace): no wait of its own, as in encode_host */
         HIPCHK(hipMemcpyAsync(c->d_pcm, pcm, pcm_bytes, hipMemcpyHostToDevice, s));
         dpcm = c->d_pcm;
     }
     if (!out_on_device) {
-        if (c->out_cap < out_bytes) { if (c->d_out) HIPCHK(hipFree(c->d_out)); c->d_out = nullptr; c->out_cap = 0; HIPCHK(hipMalloc((void**)&c->d_out, out_bytes)); c->out_cap = out_bytes; }
+        if (grow(&c->d_out, &c->out_cap, out_bytes, out_bytes, false)) return 1;
         dout = c->d_out;
         HIPCHK(hipMemsetAsync(dout, 0, out_bytes, s));
     }
     lc3d_trace* dtr = nullptr;
     if (trace_host) {
         const size_t tb = sizeof(lc3d_trace) * (size_t)c->ncs * n_frames;
-        if (c->trace_cap < tb) { if (c->d_trace) HIPCHK(hipFree(c->d_trace)); c->d_trace = nullptr; c->trace_cap = 0; HIPCHK(hipMalloc((void**)&c->d_trace, tb)); c->trace_cap = tb; }
+        if (grow(&c->d_trace, &c->trace_cap, tb, tb, false)) return 1;
         HIPCHK(hipMemsetAsync(c->d_trace, 0, tb, s));
         dtr = c->d_trace;
     }
@@ -866,10 +927,7 @@ extern "C" int lc3hip_encode(void* ctx, const void* pcm, int pcm_on_device, int 
     if (c->opt.check_ready && c->ev_ours) { HIPCHK(hipEventRecord(c->ev_ours, s)); c->ours_armed = 1; }
     if (!out_on_device) HIPCHK(hipMemcpyAsync(out, dout, out_bytes, hipMemcpyDeviceToHost, s));
     if (trace_host) HIPCHK(hipMemcpyAsync(trace_host, dtr, sizeof(lc3d_trace) * (size_t)c->ncs * n_frames, hipMemcpyDeviceToHost, s));
-    if (sync || !out_on_device || trace_host) {
-        HIPCHK(hipStreamSynchronize(s));
-        float ms = 0; if (hipEventElapsedTime(&ms, c->ev0, c->ev1) == hipSuccess) c->last_ms = ms;
-    }
+    if (sync || !out_on_device || trace_host) SYNC_TIMED(c, s);
     return 0;
 }
 
@@ -909,22 +967,15 @@ extern "C" int lc3hip_encode_rates_device(void* ctx, const void* pcm, int bitdep
         HIPCHK(hipEventCreateWithFlags(&c->ev_plan, hipEventDisableTiming)); HIPCHK(hipEventCreateWithFlags(&c->ev_pset_prev, hipEventDisableTiming));
         for (int i = 0; i < LC3D_SETS; i++) HIPCHK(hipEventCreateWithFlags(&c->ev_pset[i], hipEventDisableTiming));
         if (!c->ev_bwcp) HIPCHK(hipEventCreateWithFlags(&c->ev_bwcp, hipEventDisableTiming));
-        HIPCHK(hipMalloc((void**)&c->d_carry, sizeof(int4) * (size_t)c->n_streams));
-        for (int i = 0; i < LC3D_SETS; i++) HIPCHK(hipMalloc((void**)&c->d_pend[i], sizeof(int4) * (size_t)c->n_streams));
         c->carry_seed = 1;
     }
-    if (c->pset_frames < (size_t)n_frames) {
-        /* an earlier call that did not wait may still read the smaller sets: growing them waits for the device, once (the first allocation does not) */
-        if (c->d_pfsz[0]) HIPCHK(hipDeviceSynchronize());
-        for (int i = 0; i < LC3D_SETS; i++) {
-            if (c->d_pfsz[i]) HIPCHK(hipFree(c->d_pfsz[i])); if (c->d_pbw[i]) HIPCHK(hipFree(c->d_pbw[i]));
-            c->d_pfsz[i] = nullptr; c->d_pbw[i] = nullptr;
-        }
-        c->pset_frames = 0;
-        const size_t fb = sizeof(uint16_t) * (size_t)c->n_streams * n_frames;
-        for (int i = 0; i < LC3D_SETS; i++) { HIPCHK(hipMalloc((void**)&c->d_pfsz[i], fb)); HIPCHK(hipMalloc((void**)&c->d_pbw[i], fb)); }
-        c->pset_frames = (size_t)n_frames;
-    }
+    if (grow_once(&c->d_carry, sizeof(int4) * (size_t)c->n_streams)) return 1;      /* outside the block above: a call after a failed allocation tries again */
+    for (int i = 0; i < LC3D_SETS; i++) if (grow_once(&c->d_pend[i], sizeof(int4) * (size_t)c->n_streams)) return 1;
+    /* an earlier call that did not wait may still read the smaller sets: growing them waits for the device, once (the first allocation does not) */
+    const size_t fb = sizeof(uint16_t) * (size_t)c->n_streams * n_frames;
+    lc3hip_buf b[2 * LC3D_SETS];
+    for (int i = 0; i < LC3D_SETS; i++) { b[2 * i] = {(void**)&c->d_pfsz[i], fb, false}; b[2 * i + 1] = {(void**)&c->d_pbw[i], fb, false}; }
+    if (grow_group(&c->pset_frames, (size_t)n_frames, b, 2 * LC3D_SETS, true)) return 1;
     const int k = c->pset;
     c->pl.pending = 1; c->pl.k = k; c->pl.T = n_frames; c->pl.rates = rates_dev; c->pl.bws = bws_dev; c->pl.nb = num_bytes_dev; c->pl.fl = flags_dev; c->pl.rule = *rule;
     c->bw_on = nullptr;
@@ -952,10 +1003,7 @@ extern "C" int lc3hip_encode_rates_device(void* ctx, const void* pcm, int bitdep
     if (rates_dev) { c->any_attack |= c->etab_attack; c->max_nbytes = c->etab_max; c->min_nbytes = 1; }
     if (c->opt.check_ready && c->ev_ours) { HIPCHK(hipEventRecord(c->ev_ours, s)); c->ours_armed = 1; }
     c->last_stream = s;
-    if (sync) {
-        HIPCHK(hipStreamSynchronize(s));
-        float ms = 0; if (hipEventElapsedTime(&ms, c->ev0, c->ev1) == hipSuccess) c->last_ms = ms;
-    }
+    if (sync) SYNC_TIMED(c, s);
     return 0;
 }
 /* Packed output: the call of lc3hip_encode_rates_device (rates_dev or bws_dev given) or of lc3hip_encode with device pointers (neither), with the scan of
@@ -967,16 +1015,13 @@ extern "C" int lc3hip_encode_packed(void* ctx, const void* pcm, int bitdepth, in
 {
     lc3hip_ctx* c = (lc3hip_ctx*)ctx;
     HIPCHK(hipSetDevice(c->device));
-    const size_t n = (size_t)c->n_streams * n_frames, nb = (n + PKS_TILE - 1) / PKS_TILE;
-    if (c->poff_cap < n || c->pbsum_cap < nb) {
-        if (c->d_pbsum) HIPCHK(hipDeviceSynchronize());
-        for (int i = 0; i < LC3D_SETS + 1; i++) { if (c->d_poff[i]) HIPCHK(hipFree(c->d_poff[i])); c->d_poff[i] = nullptr; }
-        if (c->d_pbsum) HIPCHK(hipFree(c->d_pbsum));
-        c->d_pbsum = nullptr; c->poff_cap = 0; c->pbsum_cap = 0;
-        for (int i = 0; i < LC3D_SETS + 1; i++) HIPCHK(hipMalloc((void**)&c->d_poff[i], n * sizeof(long long)));
-        HIPCHK(hipMalloc((void**)&c->d_pbsum, (size_t)(LC3D_SETS + 1) * nb * sizeof(long long)));
-        c->poff_cap = n; c->pbsum_cap = nb;
-    }
+    /* one table of offsets per slot and, in one buffer, a slot of tile sums for each; an earlier call that did not wait may still read the smaller tables, so
+     * growing them waits for the device, once (the first allocation does not) */
+    const size_t n = (size_t)c->n_streams * n_frames;
+    lc3hip_buf b[LC3D_SETS + 2];
+    for (int i = 0; i < LC3D_SETS + 1; i++) b[i] = {(void**)&c->d_poff[i], n * sizeof(long long), false};
+    b[LC3D_SETS + 1] = {(void**)&c->d_pbsum, (size_t)(LC3D_SETS + 1) * PKS_SUMS(n) * sizeof(long long), false};
+    if (grow_group(&c->poff_cap, n, b, LC3D_SETS + 2, true)) return 1;
     if (!c->ev_scan) HIPCHK(hipEventCreateWithFlags(&c->ev_scan, hipEventDisableTiming));
     c->pk.on = 1; c->pk.order = order; c->pk.cap = capacity; c->pk.offs = offsets_dev; c->pk.total = total_dev; c->pk.nb = num_bytes_dev; c->pk.fl = flags_dev;
     c->pk.tab = nullptr;
@@ -1107,36 +1152,23 @@ extern "C" int lc3hip_destroy(void* ctx)
     if (!c) return 0;
     hipSetDevice(c->device);
     hipDeviceSynchronize();
-    if (c->d_plan) hipFree(c->d_plan);
-    if (c->d_chans) hipFree(c->d_chans);
-    if (c->d_state) hipFree(c->d_state);
-    if (c->d_pcm) hipFree(c->d_pcm);
-    if (c->d_out) hipFree(c->d_out);
-    for (int i = 0; i < LC3D_SETS; i++) { if (c->d_dumpv[i]) hipFree(c->d_dumpv[i]); if (c->d_statusv[i]) hipFree(c->d_statusv[i]); }
-    for (int i = 0; i < LC3D_SETS; i++) if (c->d_y12[i]) hipFree(c->d_y12[i]);
-    if (c->d_trace) hipFree(c->d_trace);
-    for (int i = 0; i < LC3D_SETS; i++) { if (c->d_spec[i]) hipFree(c->d_spec[i]); if (c->d_frec[i]) hipFree(c->d_frec[i]); }
-    for (int i = 0; i < LC3D_SETS + 1; i++) if (c->d_xnext[i]) hipFree(c->d_xnext[i]);
+    void* bufs[] = {c->d_plan, c->d_chans, c->d_state, c->d_pcm, c->d_out, c->d_trace, c->d_etab, c->d_carry, c->d_pbsum, c->hp_dpcm[0], c->hp_dpcm[1]};
+    for (void* p : bufs) if (p) hipFree(p);
+    for (int i = 0; i < LC3D_SETS; i++) {      /* what a set holds: hand-over buffers, plan buffers */
+        void* set[] = {c->d_dumpv[i], c->d_statusv[i], c->d_y12[i], c->d_spec[i], c->d_frec[i], c->d_pfsz[i], c->d_pbw[i], c->d_pend[i]};
+        for (void* p : set) if (p) hipFree(p);
+        if (c->ev_pset[i]) hipEventDestroy(c->ev_pset[i]);
+    }
+    for (int i = 0; i < LC3D_SETS + 1; i++) { if (c->d_xnext[i]) hipFree(c->d_xnext[i]); if (c->d_poff[i]) hipFree(c->d_poff[i]); }
     free(c->h_attack); free(c->h_nb);
-    if (c->d_etab) hipFree(c->d_etab);
     if (c->h_chans) hipHostFree(c->h_chans);
     if (c->ev_chans) hipEventDestroy(c->ev_chans);
     ss_free(&c->ss);
-    for (int i = 0; i < LC3D_SETS; i++) { if (c->d_fsz[i]) hipFree(c->d_fsz[i]); if (c->h_fsz[i]) hipHostFree(c->h_fsz[i]); if (c->ev_fsz[i]) hipEventDestroy(c->ev_fsz[i]); }
-    for (int i = 0; i < LC3D_SETS; i++) { if (c->d_bw[i]) hipFree(c->d_bw[i]); if (c->h_bw[i]) hipHostFree(c->h_bw[i]); if (c->ev_bw[i]) hipEventDestroy(c->ev_bw[i]); }
+    stage_free(&c->fsz); stage_free(&c->bw);
     if (c->ev_bwcp) hipEventDestroy(c->ev_bwcp);
-    if (c->d_carry) hipFree(c->d_carry);
     if (c->ev_plan) { hipEventDestroy(c->ev_plan); hipEventDestroy(c->ev_pset_prev); }
-    for (int i = 0; i < LC3D_SETS + 1; i++) if (c->d_poff[i]) hipFree(c->d_poff[i]);
-    if (c->d_pbsum) hipFree(c->d_pbsum);
     if (c->ev_scan) hipEventDestroy(c->ev_scan);
-    for (int i = 0; i < LC3D_SETS; i++) { if (c->d_pfsz[i]) hipFree(c->d_pfsz[i]); if (c->d_pbw[i]) hipFree(c->d_pbw[i]); if (c->d_pend[i]) hipFree(c->d_pend[i]); if (c->ev_pset[i]) hipEventDestroy(c->ev_pset[i]); }
-    for (int i = 0; i < 2; i++) {
-        if (c->hp_dpcm[i]) hipFree(c->hp_dpcm[i]);
-        if (c->hp_pin_in[i]) hipHostFree(c->hp_pin_in[i]);
-        if (c->ev_h2d[i]) hipEventDestroy(c->ev_h2d[i]);
-        if (c->ev_k[i]) hipEventDestroy(c->ev_k[i]);
-    }
+    for (int i = 0; i < 2; i++) { if (c->hp_pin_in[i]) hipHostFree(c->hp_pin_in[i]); if (c->ev_h2d[i]) hipEventDestroy(c->ev_h2d[i]); if (c->ev_k[i]) hipEventDestroy(c->ev_k[i]); }
     if (c->s_h2d) hipStreamDestroy(c->s_h2d);
     if (c->s_pre) { if (c->s_pit != c->s_pre) { hipStreamDestroy(c->s_pit); hipStreamDestroy(c->s_ln); } hipStreamDestroy(c->s_pre); hipStreamDestroy(c->s_fr); for (int i = 0; i < 2; i++) { if (c->s_pk[i]) hipStreamDestroy(c->s_pk[i]); hipEventDestroy(c->ev_pk[i]); } hipEventDestroy(c->ev_rate);
                     for (int i = 0; i < LC3D_MAX_RUNS; i++) { hipEventDestroy(c->ev_h[i]); hipEventDestroy(c->ev_m[i]); hipEventDestroy(c->ev_v[i]); } hipEventDestroy(c->ev_fork); for (int i = 0; i < LC3D_SETS; i++) hipEventDestroy(c->ev_done[i]);
@@ -1205,26 +1237,29 @@ extern "C" int lc3hip_dec_create(void** out_ctx, const lc3d_plan* plan, const fl
     *out_ctx = c;
     return 0;
 }
+/* the largest frame of the batch selects the parse kernel's staging: kept exact when sizes shrink again.  Channel-streams first ... first + count - 1, or with
+ * list the channels of streams list[0 .. count / channels - 1] */
+static int dec_note_nbytes(lc3hip_dctx* c, const lc3d_dchan* chans, int first, int count, const int* list)
+{
+    if (!c->h_nbytes) { c->h_nbytes = (int*)calloc((size_t)c->ncs, sizeof(int)); if (!c->h_nbytes) return 1; }
+    for (int i = 0; i < count; i++) c->h_nbytes[list ? list[i / c->channels] * c->channels + i % c->channels : first + i] = chans[i].nbytes;
+    c->max_nbytes = 0;
+    for (int i = 0; i < c->ncs; i++) if (c->h_nbytes[i] > c->max_nbytes) c->max_nbytes = c->h_nbytes[i];
+    return 0;
+}
 extern "C" int lc3hip_dec_upload_chans(void* ctx, const lc3d_dchan* chans, int first, int count)
 {
     lc3hip_dctx* c = (lc3hip_dctx*)ctx;
     HIPCHK(hipSetDevice(c->device));
     if (c->last_stream) { HIPCHK(hipStreamSynchronize(c->last_stream)); c->last_stream = nullptr; }
     HIPCHK(hipMemcpy(c->d_chans + first, chans, sizeof(lc3d_dchan) * count, hipMemcpyHostToDevice));
-    /* the largest frame of the batch selects the parse kernel's staging: keep it exact when sizes shrink again */
-    if (!c->h_nbytes) { c->h_nbytes = (int*)calloc((size_t)c->ncs, sizeof(int)); if (!c->h_nbytes) return 1; }
-    for (int i = 0; i < count; i++) c->h_nbytes[first + i] = chans[i].nbytes;
-    c->max_nbytes = 0;
-    for (int i = 0; i < c->ncs; i++) if (c->h_nbytes[i] > c->max_nbytes) c->max_nbytes = c->h_nbytes[i];
-    return 0;
+    return dec_note_nbytes(c, chans, first, count, nullptr);
 }
 extern "C" int lc3hip_dec_upload_table(void* ctx, const lc3d_dchan* tab, int n)
 {
     lc3hip_dctx* c = (lc3hip_dctx*)ctx;
     HIPCHK(hipSetDevice(c->device));
-    if (c->d_tab) HIPCHK(hipFree(c->d_tab));
-    c->d_tab = nullptr;
-    HIPCHK(hipMalloc((void**)&c->d_tab, sizeof(lc3d_dchan) * (size_t)n));
+    if (replace(&c->d_tab, sizeof(lc3d_dchan) * (size_t)n)) return 1;      /* as the encoder's table */
     HIPCHK(hipMemcpy(c->d_tab, tab, sizeof(lc3d_dchan) * (size_t)n, hipMemcpyHostToDevice));
     c->tab_n = n;
     return 0;
@@ -1242,145 +1277,111 @@ extern "C" int lc3hip_dec_download_chans(void* ctx, lc3d_dchan* chans)
     HIPCHK(hipSetDevice(c->device));
     if (c->last_stream) { HIPCHK(hipStreamSynchronize(c->last_stream)); c->last_stream = nullptr; }
     HIPCHK(hipMemcpy(chans, c->d_chans, sizeof(lc3d_dchan) * c->ncs, hipMemcpyDeviceToHost));
-    if (!c->h_nbytes) { c->h_nbytes = (int*)calloc((size_t)c->ncs, sizeof(int)); if (!c->h_nbytes) return 1; }
-    c->max_nbytes = 0;
-    for (int i = 0; i < c->ncs; i++) { c->h_nbytes[i] = chans[i].nbytes; if (c->h_nbytes[i] > c->max_nbytes) c->max_nbytes = c->h_nbytes[i]; }
-    return 0;
+    return dec_note_nbytes(c, chans, 0, c->ncs, nullptr);
 }
-/* nb_dev: per-frame sizes in device memory (lc3hip_dec_decode_dsizes) - with bfi_dev (or null) and status_dev (or null), all device pointers like frames and pcm */
-static int dec_decode(lc3hip_dctx* c, const void* frames, int frames_on_device, int in_stride, const uint8_t* bfi_host, const uint16_t* sizes_host,
-                      int sizes_max_nbytes, int n_frames, void* pcm, int pcm_on_device, int bps, uint8_t* status_host, void* hip_stream, int sync,
-                      void* trace_host, const int32_t* nb_dev, const uint8_t* bfi_dev, uint8_t* status_dev,
-                      const long long* offs_dev = nullptr /* frames packed (lc3hip_dec_decode_packed): in_stride is then the largest frame */, long long cap = 0)
+/* one call of dec_decode: its arguments, and what the functions it is cut into hand to each other.
+ * nb_dev: per-frame sizes in device memory (lc3hip_dec_decode_dsizes) - with bfi_dev (or null) and status_dev (or null), all device pointers like frames and pcm */
+struct dec_call {
+    const void* frames; int frames_on_device, in_stride; const uint8_t* bfi_host; const uint16_t* sizes_host; int sizes_max_nbytes, n_frames; void* pcm; int pcm_on_device, bps;
+    uint8_t* status_host; int sync; void* trace_host; const int32_t* nb_dev; const uint8_t* bfi_dev; uint8_t* status_dev;
+    const long long* offs_dev;      /* frames packed (lc3hip_dec_decode_packed): in_stride is then the largest frame */
+    long long cap;
+    hipStream_t s; const int32_t* cnt;
+    const uint8_t* din; void* dpcm; const uint8_t* dbfi; const uint16_t* dsizes; lc3d_dec_trace* dtr; uint8_t* dst; size_t pcm_bytes;      /* dec_stage: what the kernels read and write */
+    bool ahead; int* rec_w; float* ws_w;                                                                                               /* dec_stage: the set of hand-over buffers the parser writes */
+    int max_nb, nw_max, wpg; size_t per_wave;                                                                                          /* dec_parse_lds */
+};
+/* staging host arrays: what the call brings in host memory goes to the device on s, and every buffer of the call is sized.  The host-array buffers (d_in, d_pcm,
+ * d_bfi, d_sizes, d_trace, d_status) grow without a wait of their own: a call that uses one returns when its work is done, and hipFree waits for the device's
+ * pending work before it releases anything. */
+static int dec_stage(lc3hip_dctx* c, dec_call* q)
 {
-    HIPCHK(hipSetDevice(c->device));
-    if (c->plo && (!pcm_on_device || trace_host || (bps & LC3D_PCM_CHANNEL_MAJOR))) return 1;      /* placed PCM: device-pointer calls without traces (the host refuses the others) */
-    const int32_t* cnt = c->counts ? c->d_cnt : nullptr;           /* per-stream frame counts: the _rag kernels below, every one behind the plan kernel that clamps them into d_cnt */
-    if (cnt && !nb_dev) return 1;                                   /* ... on the calls with sizes in device memory only (the host refuses the others) */
-    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : c->stream;
-    if (c->ss.done_armed) HIPCHK(hipStreamWaitEvent(s, c->ss.ev_done, 0));      /* behind the last stream-lifecycle call, whichever stream it was queued on */
-    const size_t in_bytes = (size_t)c->n_streams * n_frames * in_stride;
-    const size_t pcm_bytes = (size_t)c->ncs * n_frames * c->N * (size_t)lc3d_pcm_elem_bytes(bps);
-    const uint8_t* din = (const uint8_t*)frames; void* dpcm = pcm; const uint8_t* dbfi = nullptr; lc3d_dec_trace* dtr = nullptr;
-    if (!frames_on_device) {
-        if (c->in_cap < in_bytes) { if (c->d_in) HIPCHK(hipFree(c->d_in)); HIPCHK(hipMalloc((void**)&c->d_in, in_bytes)); c->in_cap = in_bytes; }
-        HIPCHK(hipMemcpyAsync(c->d_in, frames, in_bytes, hipMemcpyHostToDevice, s));
-        din = c->d_in;
+    hipStream_t s = q->s;
+    const int n_frames = q->n_frames;
+    const size_t in_bytes = (size_t)c->n_streams * n_frames * q->in_stride;
+    q->pcm_bytes = (size_t)c->ncs * n_frames * c->N * (size_t)lc3d_pcm_elem_bytes(q->bps);
+    q->din = (const uint8_t*)q->frames; q->dpcm = q->pcm;
+    /* a device buffer of `bytes` for a host array of the call, and the array (if any: h) copied into it on s */
+    auto up = [&](auto** d, size_t* cap, const void* h, size_t bytes) -> int { if (grow(d, cap, bytes, bytes, false)) return 1; if (h) HIPCHK(hipMemcpyAsync(*d, h, bytes, hipMemcpyHostToDevice, s)); return 0; };
+    const size_t fb = (size_t)c->n_streams * n_frames;            /* a byte per stream-frame */
+    if (!q->frames_on_device) { if (up(&c->d_in, &c->in_cap, q->frames, in_bytes)) return 1; q->din = c->d_in; }
+    if (!q->pcm_on_device) { if (up(&c->d_pcm, &c->pcm_cap, nullptr, q->pcm_bytes)) return 1; q->dpcm = c->d_pcm; }
+    if (q->bfi_host) { if (up(&c->d_bfi, &c->bfi_cap, q->bfi_host, fb)) return 1; q->dbfi = c->d_bfi; }
+    if (q->sizes_host) {                                            /* per-frame sizes: the host merged the lost frames into bfi_host, so this call is ordered */
+        if (!q->bfi_host || !c->d_tab || up(&c->d_sizes, &c->sizes_cap, q->sizes_host, sizeof(uint16_t) * fb)) return 1;
+        q->dsizes = c->d_sizes;
     }
-    if (!pcm_on_device) {
-        if (c->pcm_cap < pcm_bytes) { if (c->d_pcm) HIPCHK(hipFree(c->d_pcm)); HIPCHK(hipMalloc((void**)&c->d_pcm, pcm_bytes)); c->pcm_cap = pcm_bytes; }
-        dpcm = c->d_pcm;
-    }
-    if (bfi_host) {
-        const size_t fb = (size_t)c->n_streams * n_frames;
-        if (c->bfi_cap < fb) { if (c->d_bfi) HIPCHK(hipFree(c->d_bfi)); HIPCHK(hipMalloc((void**)&c->d_bfi, fb)); c->bfi_cap = fb; }
-        HIPCHK(hipMemcpyAsync(c->d_bfi, bfi_host, fb, hipMemcpyHostToDevice, s));
-        dbfi = c->d_bfi;
-    }
-    const uint16_t* dsizes = nullptr;
-    if (sizes_host) {                                               /* per-frame sizes: the host merged the lost frames into bfi_host, so this call is ordered */
-        if (!bfi_host || !c->d_tab) return 1;
-        const size_t fb = sizeof(uint16_t) * (size_t)c->n_streams * n_frames;
-        if (c->sizes_cap < fb) { if (c->d_sizes) HIPCHK(hipFree(c->d_sizes)); HIPCHK(hipMalloc((void**)&c->d_sizes, fb)); c->sizes_cap = fb; }
-        HIPCHK(hipMemcpyAsync(c->d_sizes, sizes_host, fb, hipMemcpyHostToDevice, s));
-        dsizes = c->d_sizes;
-    }
-    if (trace_host) {
+    if (q->trace_host) {
         const size_t tb = sizeof(lc3d_dec_trace) * (size_t)c->ncs * n_frames;
-        if (c->trace_cap < tb) { if (c->d_trace) HIPCHK(hipFree(c->d_trace)); HIPCHK(hipMalloc((void**)&c->d_trace, tb)); c->trace_cap = tb; }
+        if (up(&c->d_trace, &c->trace_cap, nullptr, tb)) return 1;
         HIPCHK(hipMemsetAsync(c->d_trace, 0, tb, s));
-        dtr = c->d_trace;
+        q->dtr = c->d_trace;
     }
-    uint8_t* dst = nullptr;
-    if (status_host) {
-        const size_t fb = (size_t)c->n_streams * n_frames;
-        if (c->status_cap < fb) { if (c->d_status) HIPCHK(hipFree(c->d_status)); HIPCHK(hipMalloc((void**)&c->d_status, fb)); c->status_cap = fb; }
-        dst = c->d_status;
-    }
-    if (nb_dev) {                                                   /* sizes and flags from device memory: the plan kernel below fills d_sizes / d_bfi / d_inval */
+    if (q->status_host) { if (up(&c->d_status, &c->status_cap, nullptr, fb)) return 1; q->dst = c->d_status; }
+    if (q->nb_dev) {                                                /* sizes and flags from device memory: the plan kernel fills d_sizes / d_bfi / d_inval */
         if (!c->d_tab) return 1;
-        const size_t fb = (size_t)c->n_streams * n_frames;
-        if (c->sizes_cap < sizeof(uint16_t) * fb || c->bfi_cap < fb || c->inval_cap < fb) {
-            /* a smaller buffer of an earlier call may still be read (calls of this kind do not wait): growing it waits for the device, once; the first
-             * allocation does not */
-            if ((c->d_sizes && c->sizes_cap < sizeof(uint16_t) * fb) || (c->d_bfi && c->bfi_cap < fb) || (c->d_inval && c->inval_cap < fb))
-                HIPCHK(hipDeviceSynchronize());
-            if (c->sizes_cap < sizeof(uint16_t) * fb) { if (c->d_sizes) HIPCHK(hipFree(c->d_sizes)); c->d_sizes = nullptr; c->sizes_cap = 0;
-                                                         HIPCHK(hipMalloc((void**)&c->d_sizes, sizeof(uint16_t) * fb)); c->sizes_cap = sizeof(uint16_t) * fb; }
-            if (c->bfi_cap < fb) { if (c->d_bfi) HIPCHK(hipFree(c->d_bfi)); c->d_bfi = nullptr; c->bfi_cap = 0; HIPCHK(hipMalloc((void**)&c->d_bfi, fb)); c->bfi_cap = fb; }
-            if (c->inval_cap < fb) { if (c->d_inval) HIPCHK(hipFree(c->d_inval)); c->d_inval = nullptr; c->inval_cap = 0; HIPCHK(hipMalloc((void**)&c->d_inval, fb)); c->inval_cap = fb; }
-        }
-        dsizes = c->d_sizes; dbfi = c->d_bfi; dst = status_dev;
+        /* a smaller buffer of an earlier call may still be read (calls of this kind do not wait): growing it waits for the device; the first allocation does not.
+         * (Three capacities - the host-array calls above grow two of the buffers on their own: each that grows waits, and behind the first wait the device is idle.) */
+        if (grow(&c->d_sizes, &c->sizes_cap, sizeof(uint16_t) * fb, sizeof(uint16_t) * fb, true) || grow(&c->d_bfi, &c->bfi_cap, fb, fb, true) || grow(&c->d_inval, &c->inval_cap, fb, fb, true)) return 1;
+        q->dsizes = c->d_sizes; q->dbfi = c->d_bfi; q->dst = q->status_dev;
     }
-    {   /* hand-over buffers between the two kernels: records and spectrum rows of every channel-frame of this call */
-        const size_t cf = (size_t)c->ncs * n_frames;
-        if (c->hand_cap < cf) {
-            if (c->d_rec) HIPCHK(hipDeviceSynchronize());            /* an earlier call that did not wait may still read them (not on the first call) */
-            if (c->d_rec) HIPCHK(hipFree(c->d_rec));
-            if (c->d_ws) HIPCHK(hipFree(c->d_ws));
-            if (c->d_ov) HIPCHK(hipFree(c->d_ov));
-            c->d_rec = nullptr; c->d_ws = nullptr; c->d_ov = nullptr; c->hand_cap = 0;
-            HIPCHK(hipMalloc((void**)&c->d_rec, cf * PR_WORDS * sizeof(int)));
-            HIPCHK(hipMalloc((void**)&c->d_ws, cf * WS_ROW(c->N) * sizeof(float)));
-            HIPCHK(hipMalloc((void**)&c->d_ov, cf * (c->big ? OV_ROW_BIG : OV_ROW_STD) * sizeof(float)));
-            c->hand_cap = cf;
-        }
-    }
+    const size_t cf = (size_t)c->ncs * n_frames;
+    /* hand-over buffers between the two kernels: records and spectrum rows of every channel-frame of this call; an earlier call that did not wait may still read them (not on the first call) */
+    const lc3hip_buf hand[] = {{(void**)&c->d_rec, cf * PR_WORDS * sizeof(int), false}, {(void**)&c->d_ws, cf * WS_ROW(c->N) * sizeof(float), false},
+                               {(void**)&c->d_ov, cf * (c->big ? OV_ROW_BIG : OV_ROW_STD) * sizeof(float), false}};
+    if (grow_group(&c->hand_cap, cf, hand, 3, true)) return 1;
     /* Under the input-ready promise (the frames of a call are complete on the device when the call is made) the parse kernel - stateless: a frame's
      * record and spectrum row depend on that frame's bytes only - does not wait for what is queued on s: it runs on its own stream into the other set of
      * hand-over buffers while the concealment bookkeeping, transform and synthesis of the call before (the stateful part, in order on s) read theirs. */
-    const bool ahead = c->input_ready && frames_on_device && pcm_on_device && !bfi_host && !trace_host && !status_host && !nb_dev;
-    int* rec_w = c->d_rec; float* ws_w = c->d_ws;
-    if (ahead) {
-        const size_t cf = (size_t)c->ncs * n_frames;
+    q->ahead = c->input_ready && q->frames_on_device && q->pcm_on_device && !q->bfi_host && !q->trace_host && !q->status_host && !q->nb_dev;
+    q->rec_w = c->d_rec; q->ws_w = c->d_ws;
+    if (q->ahead) {
         if (dec_side_streams(c)) return 1;
-        if (c->handx_cap < cf) {
-            HIPCHK(hipDeviceSynchronize());
-            for (int i = 0; i < DEC_SETS - 1; i++) {
-                if (c->d_recx[i]) HIPCHK(hipFree(c->d_recx[i]));
-                if (c->d_wsx[i]) HIPCHK(hipFree(c->d_wsx[i]));
-                c->d_recx[i] = nullptr; c->d_wsx[i] = nullptr;
-            }
-            c->handx_cap = 0;
-            for (int i = 0; i < DEC_SETS - 1; i++) {
-                HIPCHK(hipMalloc((void**)&c->d_recx[i], cf * PR_WORDS * sizeof(int)));
-                HIPCHK(hipMalloc((void**)&c->d_wsx[i], cf * WS_ROW(c->N) * sizeof(float)));
-            }
-            c->handx_cap = cf;
+        lc3hip_buf handx[2 * (DEC_SETS - 1)];      /* the other sets: calls in flight read them, so growing them waits for the device (not before the first allocation: nothing reads buffers that do not exist) */
+        for (int i = 0; i < DEC_SETS - 1; i++) {
+            handx[2 * i] = {(void**)&c->d_recx[i], cf * PR_WORDS * sizeof(int), false};
+            handx[2 * i + 1] = {(void**)&c->d_wsx[i], cf * WS_ROW(c->N) * sizeof(float), false};
         }
-        if (c->set) { rec_w = c->d_recx[c->set - 1]; ws_w = c->d_wsx[c->set - 1]; }
+        if (grow_group(&c->handx_cap, cf, handx, 2 * (DEC_SETS - 1), true)) return 1;
+        if (c->set) { q->rec_w = c->d_recx[c->set - 1]; q->ws_w = c->d_wsx[c->set - 1]; }
     }
-    hipStream_t sp = ahead ? c->s_par : s;
+    return 0;
+}
+/* the parser's LDS: how many words of a frame a lane stages, and how many waves share a workgroup's tables */
+static int dec_parse_lds(lc3hip_dctx* c, dec_call* q)
+{
     /* frames of up to 128 bytes are staged in LDS; larger ones would cut the waves per workgroup and are read from global memory */
     /* (per-frame sizes: the largest channel frame of the call that is not lost - lost frames stage nothing; sizes in device memory are not seen by the
      * host: the bound it knows, a channel's share of in_stride up to the geometry's largest channel frame - a tight in_stride keeps the staged parser) */
-    const int ch_share = (in_stride + c->channels - 1) / c->channels;
-    const int max_nb = nb_dev ? (ch_share < c->tab_n - 1 ? ch_share : c->tab_n - 1) : dsizes ? sizes_max_nbytes : c->max_nbytes;
-    const int nw_max = max_nb > 128 ? 0 : max_nb > 0 ? (max_nb + 3) / 4 : 1;
+    const int ch_share = (q->in_stride + c->channels - 1) / c->channels;
+    q->max_nb = q->nb_dev ? (ch_share < c->tab_n - 1 ? ch_share : c->tab_n - 1) : q->dsizes ? q->sizes_max_nbytes : c->max_nbytes;
+    q->nw_max = q->max_nb > 128 ? 0 : q->max_nb > 0 ? (q->max_nb + 3) / 4 : 1;
     const int nlw = (WS_ROW(c->N) / 2 + 31) / 32;                          /* >= (ylen / 2 + 31) / 32 of the plan */
-    const size_t per_wave = (size_t)(nw_max + nlw) * WAVE * sizeof(unsigned);
-    int wpg = (int)((64 * 1024 - sizeof(ParseLds)) / per_wave);            /* waves per workgroup: they share the model tables */
-    if (wpg > 4) wpg = 4;
-    if (wpg < 1) { fprintf(stderr, "lc3plus_hip: frame of %d bytes exceeds the parse kernel's LDS staging\n", max_nb); return 1; }
-    const long long tasks = (long long)c->n_streams * n_frames, per_wg = (long long)wpg * WAVE;
-    HIPCHK(hipEventRecord(c->ev0, s));
-    if (nb_dev) {
-        const long long n = (long long)c->n_streams * n_frames;
-        if (cnt && offs_dev) hipLaunchKernelGGL(lc3_dec_plan_packed_kernel_rag, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, nb_dev, offs_dev, bfi_dev, c->d_tab,
-                                                c->tab_n, c->channels, cap, in_stride, n, c->d_sizes, c->d_bfi, c->d_inval, c->counts, n_frames, c->d_cnt);
-        else if (cnt) hipLaunchKernelGGL(lc3_dec_plan_sizes_kernel_rag, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, nb_dev, bfi_dev, c->d_tab, c->tab_n, c->channels,
-                                         in_stride, n, c->d_sizes, c->d_bfi, c->d_inval, c->counts, n_frames, c->d_cnt);
-        else
-        if (offs_dev) hipLaunchKernelGGL(lc3_dec_plan_packed_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, nb_dev, offs_dev, bfi_dev, c->d_tab, c->tab_n,
-                                         c->channels, cap, in_stride, n, c->d_sizes, c->d_bfi, c->d_inval);
-        else
-        hipLaunchKernelGGL(lc3_dec_plan_sizes_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, nb_dev, bfi_dev, c->d_tab, c->tab_n, c->channels, in_stride, n,
-                           c->d_sizes, c->d_bfi, c->d_inval);
-        HIPCHK(hipGetLastError());
-    }
-    /* parse: one stream-frame per lane; concealment bookkeeping: one channel-stream per lane; IMDCT: one channel-frame per wave;
-     * synthesis: one channel-stream per wave (lc3_dec_kernels.inc) */
-    if (ahead && c->free_armed[c->set]) HIPCHK(hipStreamWaitEvent(sp, c->ev_free[c->set], 0));      /* this set was last read by the synthesis of the call DEC_SETS back */
+    q->per_wave = (size_t)(q->nw_max + nlw) * WAVE * sizeof(unsigned);
+    q->wpg = (int)((64 * 1024 - sizeof(ParseLds)) / q->per_wave);          /* waves per workgroup: they share the model tables */
+    if (q->wpg > 4) q->wpg = 4;
+    if (q->wpg < 1) { fprintf(stderr, "lc3plus_hip: frame of %d bytes exceeds the parse kernel's LDS staging\n", q->max_nb); return 1; }
+    return 0;
+}
+/* the plan kernel of a call with sizes in device memory, on s: the sizes, loss flags and invalid flags the other kernels read; ragged, also the clamped counts */
+static int dec_plan(lc3hip_dctx* c, const dec_call* q)
+{
+    const long long n = (long long)c->n_streams * q->n_frames;
+    const dim3 grid((unsigned)((n + 255) / 256)), block(256);
+    auto packed = [&](auto kern, auto... ragged) { hipLaunchKernelGGL(kern, grid, block, 0, q->s, q->nb_dev, q->offs_dev, q->bfi_dev, c->d_tab, c->tab_n, c->channels, q->cap, q->in_stride, n, c->d_sizes, c->d_bfi, c->d_inval, ragged...); };
+    auto sizes = [&](auto kern, auto... ragged) { hipLaunchKernelGGL(kern, grid, block, 0, q->s, q->nb_dev, q->bfi_dev, c->d_tab, c->tab_n, c->channels, q->in_stride, n, c->d_sizes, c->d_bfi, c->d_inval, ragged...); };
+    if (q->offs_dev) { if (q->cnt) packed(lc3_dec_plan_packed_kernel_rag, c->counts, q->n_frames, c->d_cnt); else packed(lc3_dec_plan_packed_kernel); }
+    else if (q->cnt) sizes(lc3_dec_plan_sizes_kernel_rag, c->counts, q->n_frames, c->d_cnt);
+    else sizes(lc3_dec_plan_sizes_kernel);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+/* parse: one stream-frame per lane, on sp */
+static int dec_parse(lc3hip_dctx* c, const dec_call* q, hipStream_t sp)
+{
+    const int nw_max = q->nw_max, wpg = q->wpg;
+    const long long tasks = (long long)c->n_streams * q->n_frames, per_wg = (long long)wpg * WAVE;
+    if (q->ahead && c->free_armed[c->set]) HIPCHK(hipStreamWaitEvent(sp, c->ev_free[c->set], 0));      /* this set was last read by the synthesis of the call DEC_SETS back */
     /* The first parse-ahead behind an ordered call waits for all of it: that call's transform and synthesis read the first set of hand-over buffers, its
      * concealment kernel (on s) must not be overtaken by this call's (on s_plc, behind this parser) - both read-modify-write the concealment words
      * (DS_NBLOST, DS_CUM_ALPHA, DS_PLC_SEED, DS_PREV_BFI) - and with sizes from device memory its tail kernel writes the configuration this parser reads.
@@ -1388,117 +1389,119 @@ static int dec_decode(lc3hip_dctx* c, const void* frames, int frames_on_device, 
      * device memory (which returns before its work is done) leaves the host's copy of the configuration stale, so the fixed-size call that makes this
      * parse-ahead reads it back first (lc3_host.c dec_refresh), waiting for that call on the host.  The event states the order on the device instead of
      * leaving it to those host waits.  The other direction, an ordered call behind parse-ahead calls, waits on the device for the last of their
-     * concealment kernels (ev_plc, below) - there a device-size call with sync = 0 does rely on it. */
-    if (ahead && c->ord_pending) { HIPCHK(hipStreamWaitEvent(sp, c->ev_ord, 0)); c->ord_pending = 0; }
+     * concealment kernels (ev_plc, dec_chain) - there a device-size call with sync = 0 does rely on it. */
+    if (q->ahead && c->ord_pending) { HIPCHK(hipStreamWaitEvent(sp, c->ev_ord, 0)); c->ord_pending = 0; }
     /* How many parse waves a CU holds.  The kernel for frames of more than 128 bytes reads its frames from global memory and needs little LDS, so its 4 096
      * waves of 128 registers fill every SIMD, and the 64-wave concealment kernel and the transform of the call before wait for parse waves to retire; 24 KB of
      * padding per workgroup leave room beside them: d5 81.3 -> 88.7 Mframes/s (20 KB: 87.1, 28 KB: 77.1).  The kernel that stages its frames in LDS (d1) loses
      * with any padding (129 -> 117 at 16 KB): none there. */
     /* (the rule in bytes: the workgroup's LDS - tables, its waves' slices, padding - is a quarter of the CU's 160 KB, so that exactly four of them fit; that was 24 KB of padding
      * with the tables of the time) */
-    const size_t quarter = (160u << 10) / 4, used = sizeof(ParseLds) + per_wave * wpg;
+    const size_t quarter = (160u << 10) / 4, used = sizeof(ParseLds) + q->per_wave * wpg;
     const size_t pad = c->opt.dec_parse_pad_kb >= 0 ? (size_t)c->opt.dec_parse_pad_kb << 10 : (nw_max || used >= quarter ? 0 : quarter - used);
-    auto parse = dsizes ? (nw_max ? lc3_dec_parse_kernel_var : lc3_dec_parse_kernel_g_var) : (nw_max ? lc3_dec_parse_kernel : lc3_dec_parse_kernel_g);
-    if (offs_dev) hipLaunchKernelGGL(nw_max ? lc3_dec_parse_kernel_var_pk : lc3_dec_parse_kernel_g_var_pk, dim3((unsigned)((tasks + per_wg - 1) / per_wg)), dim3(wpg * WAVE),
-                                     per_wave * wpg + pad, sp, c->d_plan, c->d_chans, din, offs_dev, dbfi, dsizes, c->d_tab, n_frames, c->n_streams, nw_max, rec_w, ws_w,
-                                     WS_ROW(c->N));
-    else
-    hipLaunchKernelGGL(parse, dim3((unsigned)((tasks + per_wg - 1) / per_wg)), dim3(wpg * WAVE), per_wave * wpg + pad, sp, c->d_plan, c->d_chans, din, in_stride,
-                       dbfi, dsizes, c->d_tab, n_frames, c->n_streams, nw_max, rec_w, ws_w, WS_ROW(c->N));
+    /* `at`: where a stream's frames lie - the stride of the dense array, or (the _pk twins) the offsets of packed frames */
+    auto parse = [&](auto kern, auto at) { hipLaunchKernelGGL(kern, dim3((unsigned)((tasks + per_wg - 1) / per_wg)), dim3(wpg * WAVE), q->per_wave * wpg + pad, sp, c->d_plan, c->d_chans, q->din, at, q->dbfi, q->dsizes, c->d_tab, q->n_frames, c->n_streams, nw_max, q->rec_w, q->ws_w, WS_ROW(c->N)); };
+    if (q->offs_dev) parse(nw_max ? lc3_dec_parse_kernel_var_pk : lc3_dec_parse_kernel_g_var_pk, q->offs_dev);
+    else parse(q->dsizes ? (nw_max ? lc3_dec_parse_kernel_var : lc3_dec_parse_kernel_g_var) : (nw_max ? lc3_dec_parse_kernel : lc3_dec_parse_kernel_g), q->in_stride);
     HIPCHK(hipGetLastError());
+    return 0;
+}
+/* the stateful chain behind the parser (on sp).  Concealment bookkeeping: one channel-stream per lane; IMDCT: one channel-frame per wave; synthesis: one
+ * channel-stream per wave (lc3_dec_kernels.inc).  With per-stream frame counts the _rag twins on the same grids as the dense call: a wave whose run of frames lies
+ * past its stream's count returns at once, a stream without a present frame before touching its state */
+static int dec_chain(lc3hip_dctx* c, const dec_call* q, hipStream_t sp)
+{
+    hipStream_t s = q->s;
+    const int n_frames = q->n_frames; const int32_t* cnt = q->cnt;
+    int* rec_w = q->rec_w; float* ws_w = q->ws_w; lc3d_dec_trace* dtr = q->dtr;
     /* The concealment bookkeeping needs its call's parser and the bookkeeping of the call before - NOT the transform or the synthesis of the call before.  On the caller's stream it
      * became runnable at the moment the NEXT call's parser did (both behind the previous synthesis; the parser waits for its set of hand-over buffers), lost the race for the SIMDs to
      * 4 096 parse waves of 128 registers, and took 0.9 ms for 0.05 ms of work - on the stream that bounds the call (timeline in profiles/experiments/r04_what_bounds.md, section 8).
      * On a stream of its own it runs the moment its parser ends, while the chip has room. */
     hipStream_t spl = s;
-    if (ahead && c->opt.dec_plc_stream) {
+    if (q->ahead && c->opt.dec_plc_stream) {
         spl = c->s_plc;
         HIPCHK(hipEventRecord(c->ev_par[c->set], sp)); HIPCHK(hipStreamWaitEvent(spl, c->ev_par[c->set], 0));
-    } else if (ahead) { HIPCHK(hipEventRecord(c->ev_par[c->set], sp)); HIPCHK(hipStreamWaitEvent(s, c->ev_par[c->set], 0)); }
+    } else if (q->ahead) { HIPCHK(hipEventRecord(c->ev_par[c->set], sp)); HIPCHK(hipStreamWaitEvent(s, c->ev_par[c->set], 0)); }
     else if (c->s_plc) HIPCHK(hipStreamWaitEvent(s, c->ev_plc, 0));      /* an ordered call behind ahead calls: the bookkeeping is a chain (the event of the last one, if any: waiting on a fresh event is a no-op) */
-    if (cnt) hipLaunchKernelGGL(lc3_dec_plc_kernel_rag, dim3((unsigned)((c->ncs + WAVE - 1) / WAVE)), dim3(WAVE), 0, spl, c->d_plan, c->d_chans, dsizes, c->d_tab, c->d_state, rec_w, n_frames, c->ncs, cnt);
-    else
-    hipLaunchKernelGGL(lc3_dec_plc_kernel, dim3((unsigned)((c->ncs + WAVE - 1) / WAVE)), dim3(WAVE), 0, spl, c->d_plan, c->d_chans, dsizes, c->d_tab, c->d_state, rec_w, n_frames, c->ncs);
+    auto plc = [&](auto kern, auto... ragged) { hipLaunchKernelGGL(kern, dim3((unsigned)((c->ncs + WAVE - 1) / WAVE)), dim3(WAVE), 0, spl, c->d_plan, c->d_chans, q->dsizes, c->d_tab, c->d_state, rec_w, n_frames, c->ncs, ragged...); };
+    if (cnt) plc(lc3_dec_plc_kernel_rag, cnt); else plc(lc3_dec_plc_kernel);
     HIPCHK(hipGetLastError());
     if (spl != s) { HIPCHK(hipEventRecord(c->ev_plc, spl)); HIPCHK(hipStreamWaitEvent(s, c->ev_plc, 0)); }
-    const unsigned ncf = (unsigned)((size_t)c->ncs * ((n_frames + IMDCT_FPW - 1) / IMDCT_FPW));     /* runs of IMDCT_FPW frames */
-    if (cnt) {
-        /* the same grids as the dense call: a wave whose run of frames lies past its stream's count returns at once, a stream without a present frame before touching its state */
-        if (c->big) {
-            hipLaunchKernelGGL(lc3_dec_imdct_kernel_big_rag, dim3(ncf), dim3(WAVE), 0, s, c->d_plan, c->d_state, rec_w, ws_w, n_frames, c->ncs, c->d_ov, dtr, cnt);
-            if (c->plo) hipLaunchKernelGGL(lc3_dec_synth_kernel_big_rag_plc, dim3(c->ncs), dim3(WAVE), 0, s, c->d_plan, c->d_state, rec_w, ws_w, c->d_ov, n_frames, dpcm, bps, c->ncs, dst, dtr, c->plo, c->plcap, cnt);
-            else hipLaunchKernelGGL(lc3_dec_synth_kernel_big_rag, dim3(c->ncs), dim3(WAVE), 0, s, c->d_plan, c->d_state, rec_w, ws_w, c->d_ov, n_frames, dpcm, bps, c->ncs, dst, dtr, cnt);
-        } else {
-            if (c->opt.dec_imdct4 && c->N == 480)
-                hipLaunchKernelGGL(lc3_dec_imdct4_kernel_rag, dim3((unsigned)((size_t)c->ncs * ((n_frames + 3) / 4))), dim3(WAVE), 0, s, c->d_plan, c->d_state, rec_w, ws_w, n_frames, c->ncs, c->d_ov, cnt);
-            else
-            hipLaunchKernelGGL(lc3_dec_imdct_kernel_rag, dim3(ncf), dim3(WAVE), 0, s, c->d_plan, c->d_state, rec_w, ws_w, n_frames, c->ncs, c->d_ov, dtr, cnt);
-            if (c->plo) hipLaunchKernelGGL(lc3_dec_synth_kernel_rag_plc, dim3(c->ncs), dim3(WAVE), 0, s, c->d_plan, c->d_state, rec_w, ws_w, c->d_ov, n_frames, dpcm, bps, c->ncs, dst, dtr, c->plo, c->plcap, cnt);
-            else hipLaunchKernelGGL(lc3_dec_synth_kernel_rag, dim3(c->ncs), dim3(WAVE), 0, s, c->d_plan, c->d_state, rec_w, ws_w, c->d_ov, n_frames, dpcm, bps, c->ncs, dst, dtr, cnt);
-        }
-    } else
-    if (c->big) {
-        hipLaunchKernelGGL(lc3_dec_imdct_kernel_big, dim3(ncf), dim3(WAVE), 0, s, c->d_plan, c->d_state, rec_w, ws_w, n_frames, c->ncs, c->d_ov, dtr);
-        if (c->plo) hipLaunchKernelGGL(lc3_dec_synth_kernel_big_plc, dim3(c->ncs), dim3(WAVE), 0, s, c->d_plan, c->d_state, rec_w, ws_w, c->d_ov, n_frames, dpcm, bps, c->ncs, dst, dtr, c->plo, c->plcap);
-        else hipLaunchKernelGGL(lc3_dec_synth_kernel_big, dim3(c->ncs), dim3(WAVE), 0, s, c->d_plan, c->d_state, rec_w, ws_w, c->d_ov, n_frames, dpcm, bps, c->ncs, dst, dtr);
-    } else {
-        const int i4 = c->opt.dec_imdct4;
-        if (i4 && !dtr && c->N == 480)
-            hipLaunchKernelGGL(lc3_dec_imdct4_kernel, dim3((unsigned)((size_t)c->ncs * ((n_frames + 3) / 4))), dim3(WAVE), 0, s, c->d_plan, c->d_state, rec_w, ws_w, n_frames, c->ncs, c->d_ov);
-        else
-        hipLaunchKernelGGL(lc3_dec_imdct_kernel, dim3(ncf), dim3(WAVE), 0, s, c->d_plan, c->d_state, rec_w, ws_w, n_frames, c->ncs, c->d_ov, dtr);
-        if (c->plo) hipLaunchKernelGGL(lc3_dec_synth_kernel_plc, dim3(c->ncs), dim3(WAVE), 0, s, c->d_plan, c->d_state, rec_w, ws_w, c->d_ov, n_frames, dpcm, bps, c->ncs, dst, dtr, c->plo, c->plcap);
-        else hipLaunchKernelGGL(lc3_dec_synth_kernel, dim3(c->ncs), dim3(WAVE), 0, s, c->d_plan, c->d_state, rec_w, ws_w, c->d_ov, n_frames, dpcm, bps, c->ncs, dst, dtr);
-    }
+    /* the IMDCT: four frames a wave at N = 480 in the standard layout (LC3PLUS_DEC_IMDCT4=0, or a traced call: the kernel below; a ragged call never carries a trace), else runs of IMDCT_FPW frames */
+    auto imdct4 = [&](auto kern, auto... ragged) { hipLaunchKernelGGL(kern, dim3((unsigned)((size_t)c->ncs * ((n_frames + 3) / 4))), dim3(WAVE), 0, s, c->d_plan, c->d_state, rec_w, ws_w, n_frames, c->ncs, c->d_ov, ragged...); };
+    auto imdct = [&](auto kern, auto... ragged) { hipLaunchKernelGGL(kern, dim3((unsigned)((size_t)c->ncs * ((n_frames + IMDCT_FPW - 1) / IMDCT_FPW))), dim3(WAVE), 0, s, c->d_plan, c->d_state, rec_w, ws_w, n_frames, c->ncs, c->d_ov, dtr, ragged...); };
+    if (!c->big && c->opt.dec_imdct4 && !dtr && c->N == 480) { if (cnt) imdct4(lc3_dec_imdct4_kernel_rag, cnt); else imdct4(lc3_dec_imdct4_kernel); }
+    else if (cnt) imdct(c->big ? lc3_dec_imdct_kernel_big_rag : lc3_dec_imdct_kernel_rag, cnt);
+    else imdct(c->big ? lc3_dec_imdct_kernel_big : lc3_dec_imdct_kernel);
+    /* the synthesis; placed PCM: the _plc twins */
+    auto synth = [&](auto kern, auto... placed_ragged) { hipLaunchKernelGGL(kern, dim3(c->ncs), dim3(WAVE), 0, s, c->d_plan, c->d_state, rec_w, ws_w, c->d_ov, n_frames, q->dpcm, q->bps, c->ncs, q->dst, dtr, placed_ragged...); };
+    if (cnt && c->plo) synth(c->big ? lc3_dec_synth_kernel_big_rag_plc : lc3_dec_synth_kernel_rag_plc, c->plo, c->plcap, cnt);
+    else if (cnt) synth(c->big ? lc3_dec_synth_kernel_big_rag : lc3_dec_synth_kernel_rag, cnt);
+    else if (c->plo) synth(c->big ? lc3_dec_synth_kernel_big_plc : lc3_dec_synth_kernel_plc, c->plo, c->plcap);
+    else synth(c->big ? lc3_dec_synth_kernel_big : lc3_dec_synth_kernel);
     HIPCHK(hipGetLastError());
-    if (nb_dev) {                                                    /* behind the synthesis: the status bits and the stream's configuration for the next call */
+    return 0;
+}
+/* the tail of a call with sizes in device memory, the events later calls wait for, and what goes back to the host */
+static int dec_tail(lc3hip_dctx* c, const dec_call* q)
+{
+    hipStream_t s = q->s;
+    const int n_frames = q->n_frames;
+    if (q->nb_dev) {                                                 /* behind the synthesis: the status bits and the stream's configuration for the next call */
         const long long n = (long long)c->n_streams * n_frames;
-        if (cnt) {                                                   /* the ragged tail also marks the invalid placements, among the present frames only */
-            hipLaunchKernelGGL(lc3_dec_sizes_tail_kernel_rag, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, c->d_sizes, c->d_inval, c->d_tab, c->channels,
-                               c->n_streams, n_frames, c->d_chans, dst, cnt, c->plo, c->plcap, c->N);
-            HIPCHK(hipGetLastError());
-        } else {
-        hipLaunchKernelGGL(lc3_dec_sizes_tail_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, c->d_sizes, c->d_inval, c->d_tab, c->channels,
-                           c->n_streams, n_frames, c->d_chans, dst);
+        auto tail = [&](auto kern, auto... ragged) { hipLaunchKernelGGL(kern, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, c->d_sizes, c->d_inval, c->d_tab, c->channels, c->n_streams, n_frames, c->d_chans, q->dst, ragged...); };
+        /* the ragged tail also marks the invalid placements, among the present frames only */
+        if (q->cnt) tail(lc3_dec_sizes_tail_kernel_rag, q->cnt, c->plo, c->plcap, c->N); else tail(lc3_dec_sizes_tail_kernel);
         HIPCHK(hipGetLastError());
-        }
-        if (!cnt && placed_mark(c->plo, c->plcap, c->channels, c->N, n, dst, LC3D_DEC_ST_PCM_PLACE, s)) return 1;
+        if (!q->cnt && placed_mark(c->plo, c->plcap, c->channels, c->N, n, q->dst, LC3D_DEC_ST_PCM_PLACE, s)) return 1;
     }
-    if (ahead) { HIPCHK(hipEventRecord(c->ev_free[c->set], s)); c->free_armed[c->set] = 1; c->set = (c->set + 1) % DEC_SETS; }
+    if (q->ahead) { HIPCHK(hipEventRecord(c->ev_free[c->set], s)); c->free_armed[c->set] = 1; c->set = (c->set + 1) % DEC_SETS; }
     else if (c->s_par) { HIPCHK(hipEventRecord(c->ev_free[0], s)); c->free_armed[0] = 1; }      /* an ordered call reads the first set: a later parse-ahead into it waits for this one */
-    if (!ahead && c->input_ready) {                                  /* ... and the next parse-ahead waits for the whole call (see above) */
+    if (!q->ahead && c->input_ready) {                               /* ... and the next parse-ahead waits for the whole call (dec_parse) */
         if (dec_side_streams(c)) return 1;
         HIPCHK(hipEventRecord(c->ev_ord, s)); c->ord_pending = 1;
     }
     c->last_stream = s;
     HIPCHK(hipEventRecord(c->ev1, s));
-    if (!pcm_on_device) HIPCHK(hipMemcpyAsync(pcm, dpcm, pcm_bytes, hipMemcpyDeviceToHost, s));
-    if (trace_host) HIPCHK(hipMemcpyAsync(trace_host, dtr, sizeof(lc3d_dec_trace) * (size_t)c->ncs * n_frames, hipMemcpyDeviceToHost, s));
-    if (status_host) HIPCHK(hipMemcpyAsync(status_host, dst, (size_t)c->n_streams * n_frames, hipMemcpyDeviceToHost, s));
-    if (sync || !pcm_on_device || !frames_on_device || trace_host || bfi_host || status_host) {
-        HIPCHK(hipStreamSynchronize(s));
-        float ms = 0; if (hipEventElapsedTime(&ms, c->ev0, c->ev1) == hipSuccess) c->last_ms = ms;
-    }
+    if (!q->pcm_on_device) HIPCHK(hipMemcpyAsync(q->pcm, q->dpcm, q->pcm_bytes, hipMemcpyDeviceToHost, s));
+    if (q->trace_host) HIPCHK(hipMemcpyAsync(q->trace_host, q->dtr, sizeof(lc3d_dec_trace) * (size_t)c->ncs * n_frames, hipMemcpyDeviceToHost, s));
+    if (q->status_host) HIPCHK(hipMemcpyAsync(q->status_host, q->dst, (size_t)c->n_streams * n_frames, hipMemcpyDeviceToHost, s));
+    if (q->sync || !q->pcm_on_device || !q->frames_on_device || q->trace_host || q->bfi_host || q->status_host) SYNC_TIMED(c, s);
     return 0;
+}
+static int dec_decode(lc3hip_dctx* c, dec_call* q, void* hip_stream)
+{
+    HIPCHK(hipSetDevice(c->device));
+    if (c->plo && (!q->pcm_on_device || q->trace_host || (q->bps & LC3D_PCM_CHANNEL_MAJOR))) return 1;      /* placed PCM: device-pointer calls without traces (the host refuses the others) */
+    q->cnt = c->counts ? c->d_cnt : nullptr;                       /* per-stream frame counts: the _rag kernels, every one behind the plan kernel that clamps them into d_cnt */
+    if (q->cnt && !q->nb_dev) return 1;                             /* ... on the calls with sizes in device memory only (the host refuses the others) */
+    hipStream_t s = q->s = hip_stream ? (hipStream_t)hip_stream : c->stream;
+    if (c->ss.done_armed) HIPCHK(hipStreamWaitEvent(s, c->ss.ev_done, 0));      /* behind the last stream-lifecycle call, whichever stream it was queued on */
+    if (dec_stage(c, q) || dec_parse_lds(c, q)) return 1;
+    hipStream_t sp = q->ahead ? c->s_par : s;
+    HIPCHK(hipEventRecord(c->ev0, s));
+    if (q->nb_dev && dec_plan(c, q)) return 1;
+    return dec_parse(c, q, sp) || dec_chain(c, q, sp) || dec_tail(c, q);
 }
 extern "C" int lc3hip_dec_decode(void* ctx, const void* frames, int frames_on_device, int in_stride, const uint8_t* bfi_host, const uint16_t* sizes_host,
                                  int sizes_max_nbytes, int n_frames, void* pcm, int pcm_on_device, int bps, uint8_t* status_host, void* hip_stream, int sync,
                                  void* trace_host)
 {
-    return dec_decode((lc3hip_dctx*)ctx, frames, frames_on_device, in_stride, bfi_host, sizes_host, sizes_max_nbytes, n_frames, pcm, pcm_on_device, bps, status_host,
-                      hip_stream, sync, trace_host, nullptr, nullptr, nullptr);
+    dec_call q = {frames, frames_on_device, in_stride, bfi_host, sizes_host, sizes_max_nbytes, n_frames, pcm, pcm_on_device, bps, status_host, sync, trace_host};
+    return dec_decode((lc3hip_dctx*)ctx, &q, hip_stream);
 }
 extern "C" int lc3hip_dec_decode_dsizes(void* ctx, const void* frames, int in_stride, const int32_t* num_bytes_dev, const uint8_t* bfi_dev, int n_frames,
                                         void* pcm, int bps, uint8_t* status_dev, void* hip_stream, int sync)
 {
-    return dec_decode((lc3hip_dctx*)ctx, frames, 1, in_stride, nullptr, nullptr, 0, n_frames, pcm, 1, bps, nullptr, hip_stream, sync, nullptr,
-                      num_bytes_dev, bfi_dev, status_dev);
+    dec_call q = {frames, 1, in_stride, nullptr, nullptr, 0, n_frames, pcm, 1, bps, nullptr, sync, nullptr, num_bytes_dev, bfi_dev, status_dev};
+    return dec_decode((lc3hip_dctx*)ctx, &q, hip_stream);
 }
 extern "C" int lc3hip_dec_decode_packed(void* ctx, const void* frames, long long capacity, const long long* offsets_dev, const int32_t* num_bytes_dev, int max_bytes,
                                         const uint8_t* bfi_dev, int n_frames, void* pcm, int bps, uint8_t* status_dev, void* hip_stream, int sync)
 {
-    return dec_decode((lc3hip_dctx*)ctx, frames, 1, max_bytes, nullptr, nullptr, 0, n_frames, pcm, 1, bps, nullptr, hip_stream, sync, nullptr,
-                      num_bytes_dev, bfi_dev, status_dev, offsets_dev, capacity);
+    dec_call q = {frames, 1, max_bytes, nullptr, nullptr, 0, n_frames, pcm, 1, bps, nullptr, sync, nullptr, num_bytes_dev, bfi_dev, status_dev, offsets_dev, capacity};
+    return dec_decode((lc3hip_dctx*)ctx, &q, hip_stream);
 }
 extern "C" int lc3hip_dec_stream_state(void* ctx, int mode, const int* streams, int n, const lc3d_dchan* cfg, void* blob, int blob_on_device, const uint32_t* hdr,
                                        uint8_t* status, void* hip_stream, int sync)
@@ -1511,13 +1514,7 @@ extern "C" int lc3hip_dec_stream_state(void* ctx, int mode, const int* streams, 
     c->last_stream = s;
     /* the next parse-ahead reads the configuration and its concealment kernel the state this call writes: it waits for this call, as behind an ordered call */
     if (c->input_ready) { if (dec_side_streams(c)) return 1; HIPCHK(hipEventRecord(c->ev_ord, s)); c->ord_pending = 1; }
-    if (cfg) {                                  /* the largest frame of the batch selects the parser's staging */
-        if (!c->h_nbytes) { c->h_nbytes = (int*)calloc((size_t)c->ncs, sizeof(int)); if (!c->h_nbytes) return 1; }
-        for (int i = 0; i < n * c->channels; i++) c->h_nbytes[streams[i / c->channels] * c->channels + i % c->channels] = cfg[i].nbytes;
-        c->max_nbytes = 0;
-        for (int i = 0; i < c->ncs; i++) if (c->h_nbytes[i] > c->max_nbytes) c->max_nbytes = c->h_nbytes[i];
-    }
-    return 0;
+    return cfg ? dec_note_nbytes(c, cfg, 0, n * c->channels, streams) : 0;
 }
 extern "C" int lc3hip_dec_set_pcm_placement(void* ctx, const long long* offsets_dev, long long capacity)
 {
