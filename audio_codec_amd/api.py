@@ -37,6 +37,7 @@ EXPORTS = [
     "lc3plus_pcm_format_check", "lc3plus_pcm_offset", "lc3plus_pcm_elem_bytes", "lc3plus_pcm_to_native", "lc3plus_pcm_from_native",
     "lc3plus_enc_batch_set_pcm_placement", "lc3plus_dec_batch_set_pcm_placement", "lc3plus_pcm_placed_offset", "lc3plus_plan_placed",
     "lc3plus_dec_batch_set_frame_counts", "lc3plus_dec_plan_counts",
+    "lc3plus_enc_batch_set_frame_counts", "lc3plus_enc_plan_rates_ragged",
     "lc3plus_shard_block",
     "lc3plus_enc_sharded_create", "lc3plus_enc_sharded_destroy", "lc3plus_enc_sharded_shards", "lc3plus_enc_sharded_shard", "lc3plus_enc_sharded_device",
     "lc3plus_enc_sharded_owner", "lc3plus_enc_sharded_input_samples", "lc3plus_enc_sharded_num_bytes", "lc3plus_enc_sharded_stride",
@@ -62,6 +63,8 @@ ENC_FL_PACK_CAP = 8
 ENC_FL_PCM_PLACE, DEC_ST_PCM_PLACE = 16, 4
 # per-stream frame counts (DecBatch.set_frame_counts): the frame is absent - behind its stream's count; status exactly this value, nothing decoded or written
 DEC_ST_ABSENT = 8
+# ... and Batch.set_frame_counts: the encoder's device flags of an absent frame are exactly this value; nothing read, encoded or written, num_bytes 0
+ENC_FL_ABSENT = 32
 PACK_STREAM_MAJOR, PACK_FRAME_MAJOR = 0, 1
 LC3_BW_WARNING = 18
 
@@ -131,6 +134,9 @@ def load_library():
                                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
         L.lc3plus_enc_plan_rates_lenient.argtypes = [C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                      C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.lc3plus_enc_batch_set_frame_counts.argtypes = [C.c_void_p, C.c_void_p]
+        L.lc3plus_enc_plan_rates_ragged.argtypes = [C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                    C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.lc3plus_enc_batch_last_kernel_ms.restype = C.c_float
         L.lc3plus_enc_batch_last_kernel_ms.argtypes = [C.c_void_p]
         L.lc3plus_enc_batch_last_status.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
@@ -630,6 +636,15 @@ class Batch(_StreamLifecycle):
         if rc:
             raise LC3Error(rc, "lc3plus_enc_batch_encode_packed")
 
+    def set_frame_counts(self, d_counts_ptr):
+        """lc3plus_enc_batch_set_frame_counts: of every following encode_device_rates / encode_device_packed call stream s holds its first
+        min(max(counts[s], 0), T) frames, counts an int32 [n_streams] array in device memory read when the call runs.  The frames behind them are absent -
+        nothing read, encoded or written, num_bytes 0, flags ENC_FL_ABSENT - and the stream's state and configuration stop at its last present frame.  The
+        other encode calls refuse while counts are set.  0 / None: off.  Only records the pointer."""
+        rc = self.lib.lc3plus_enc_batch_set_frame_counts(self.h, C.c_void_p(d_counts_ptr) if d_counts_ptr else None)
+        if rc:
+            raise LC3Error(rc, "lc3plus_enc_batch_set_frame_counts")
+
     def last_kernel_ms(self):
         return float(self.lib.lc3plus_enc_batch_last_kernel_ms(self.h))
 
@@ -704,6 +719,26 @@ def enc_plan_rates_lenient(samplerate, channels, frame_ms, hrmode, start_rates, 
     rc = L.lc3plus_enc_plan_rates_lenient(samplerate, channels, frame_ms, hrmode, S, sr.ctypes.data, sb.ctypes.data,
                                           br.ctypes.data if br is not None else None, bw.ctypes.data if bw is not None else None, T, int(out_stride),
                                           nb.ctypes.data, inf.ctypes.data, fl.ctypes.data, end.ctypes.data)
+    return rc, nb, inf, fl, end
+
+
+def enc_plan_rates_ragged(samplerate, channels, frame_ms, hrmode, start_rates, start_bw, bitrates=None, bandwidths=None, out_stride=1 << 20, counts=None,
+                          n_frames=None):
+    """enc_plan_rates_lenient with per-stream frame counts (lc3plus_enc_plan_rates_ragged, no device needed): counts None (dense) or [n_streams]; bitrates
+    and bandwidths may both be None, n_frames then says how long the call is.  Absent entries: num_bytes 0, bandwidth in force 0, flags ENC_FL_ABSENT; the
+    last rates are those after each stream's last present frame.  Same return as enc_plan_rates_lenient."""
+    L = load_library()
+    br = np.ascontiguousarray(np.atleast_2d(np.asarray(bitrates)), dtype=np.int32) if bitrates is not None else None
+    bw = np.ascontiguousarray(np.atleast_2d(np.asarray(bandwidths)), dtype=np.int32) if bandwidths is not None else None
+    words = br if br is not None else bw
+    S, T = words.shape if words is not None else (np.asarray(start_rates).size, int(n_frames))
+    sr = np.ascontiguousarray(np.broadcast_to(np.asarray(start_rates, dtype=np.int32), (S,)), dtype=np.int32)
+    sb = np.ascontiguousarray(np.broadcast_to(np.asarray(start_bw, dtype=np.int32), (S,)), dtype=np.int32)
+    cn = np.ascontiguousarray(np.broadcast_to(np.asarray(counts, dtype=np.int32), (S,)), dtype=np.int32) if counts is not None else None
+    nb = np.zeros((S, T), np.int32); inf = np.zeros((S, T), np.int32); fl = np.zeros((S, T), np.uint8); end = np.zeros(S, np.int32)
+    rc = L.lc3plus_enc_plan_rates_ragged(samplerate, channels, frame_ms, hrmode, S, sr.ctypes.data, sb.ctypes.data,
+                                         br.ctypes.data if br is not None else None, bw.ctypes.data if bw is not None else None, T, int(out_stride),
+                                         nb.ctypes.data, inf.ctypes.data, fl.ctypes.data, end.ctypes.data, cn.ctypes.data if cn is not None else None)
     return rc, nb, inf, fl, end
 
 

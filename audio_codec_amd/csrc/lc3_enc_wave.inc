@@ -3,19 +3,30 @@
  * ENC_PCM_FMT 0: the kernel KERNEL_FN for the reference's three PCM formats (16, 24, 32 in the default layout), token for token what it was before the PCM format
  * word existed: it sits at its register limit, and any branch more moves its spills.  ENC_PCM_FMT 1 (the -DLC3_PCM_FMT objects): the same kernel named with _fmt
  * for the formats beyond those (float samples, the interleaved and the channel-major layout, lc3_plan.h: lc3d_pcm_*).  The two differ in the PCM load alone.
- * -DLC3_PCM_PLACED: named with _plc, every sample type from per-frame offsets (lc3_kernels.hip: pcm_placed_load). */
+ * -DLC3_PCM_PLACED: named with _plc, every sample type from per-frame offsets (lc3_kernels.hip: pcm_placed_load).
+ * -DLC3_ENC_RAGGED (objects of their own, csrc/Makefile: _erag; the kernels are named with _rag behind _pk, lc3_encode_kernel_var_pk_rag ...): per-stream frame counts (lc3plus_enc_batch_set_frame_counts).  The wave reads its stream's count once
+ * (cnt[strm], clamped to 0 ... T by the ragged plan kernel; the channels of a stereo stream share it), returns before it touches anything where that is 0, and runs
+ * its frame loop and its one-frame-ahead requests to the count (ENC_TC) instead of T.  T stays the call's frame count: every array is indexed with it.  Without
+ * the switch ENC_TC is T, and the kernels are token for token what they were. */
 #if ENC_PCM_FMT
 #define ENC_WAVE_FN LC3_FMT_CAT(KERNEL_FN)
 #else
 #define ENC_WAVE_FN KERNEL_FN
 #endif
 extern "C" __global__ void __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(KERNEL_WAVES, KERNEL_WAVES)))
-ENC_WAVE_FN(LC3_OW_ARGS LC3_OW_OPT(LC3_OW_ARGS_, LC3_TU_VAR, LC3_TU_VBW, LC3_TU_PK) LC3_PLACED_OPT)      /* lc3_kernel_decls.h: the parameters, and what each is */
+ENC_WAVE_FN(LC3_OW_ARGS LC3_OW_OPT(LC3_OW_ARGS_, LC3_TU_VAR, LC3_TU_VBW, LC3_TU_PK) LC3_PLACED_OPT LC3_ENC_RAGGED_OPT)      /* lc3_kernel_decls.h: the parameters, and what each is */
 {
     __shared__ WaveLds L;
     const int lane = threadIdx.x;
     const int cs = blockIdx.x;
     if (cs >= ncs) return;
+#ifdef LC3_ENC_RAGGED
+    const int Tc = uni(cnt[cs / P->channels]);
+    if (Tc <= 0) return;                                 /* nothing of this stream in the call: state, configuration and output stay what they are */
+#define ENC_TC Tc
+#else
+#define ENC_TC T
+#endif
     if (lane < LC3D_PLAN_HEAD_WORDS) L.pc[lane] = ((const int*)P)[lane];
     if (lane < 14) L.cc[lane] = ((const int*)&chans[cs])[lane];
     LSYNC();
@@ -57,14 +68,14 @@ ENC_WAVE_FN(LC3_OW_ARGS LC3_OW_OPT(LC3_OW_ARGS_, LC3_TU_VAR, LC3_TU_VBW, LC3_TU_
         _Pragma("unroll") for (int k = 0; k < SPK; k++) sp[k] = lane + 64 * k < N ? sr_[lane + 64 * k] : 0.0f; \
         if (lane < 16) rq = fr_[FR_SCFQ + lane]; \
         if (lane < 8) ri = ((const int*)fr_)[FR_IDX + lane];   /* seven indices, then the bandwidth index */ } while (0)
-    if (spec && T > 0) SPEC_PREFETCH(0);
-    if (T > 0) {
+    if (spec && ENC_TC > 0) SPEC_PREFETCH(0);
+    if (ENC_TC > 0) {
 #if !ENC_PCM_FMT
         if (fast16 && lane < (N >> 3)) nv = ((const uint4*)((const int16_t*)pcm + (((size_t)strm * T) * channels + ch) * N))[lane];
 #endif
         if (y12) { const float* yp = y12 + ((size_t)cs * T) * 128; ny0 = lane < PI(len12) ? yp[lane] : 0.0f; ny1 = lane + 64 < PI(len12) ? yp[lane + 64] : 0.0f; }
     }
-    for (int t = 0; t < T; t++) {
+    for (int t = 0; t < ENC_TC; t++) {
 #ifdef LC3_STAGE_TIMING
         lc3d_trace* tr = nullptr;
 #else
@@ -115,7 +126,7 @@ ENC_WAVE_FN(LC3_OW_ARGS LC3_OW_OPT(LC3_OW_ARGS_, LC3_TU_VAR, LC3_TU_VBW, LC3_TU_
                 d[4] = (float)(int16_t)(v.z & 0xffff); d[5] = (float)(int16_t)(v.z >> 16);
                 d[6] = (float)(int16_t)(v.w & 0xffff); d[7] = (float)(int16_t)(v.w >> 16);
             }
-            if (t + 1 < T && lane < (N >> 3)) nv = ((const uint4*)((const int16_t*)pcm + (fidx + channels) * N))[lane];
+            if (t + 1 < ENC_TC && lane < (N >> 3)) nv = ((const uint4*)((const int16_t*)pcm + (fidx + channels) * N))[lane];
         } else if (bitdepth == 16) {
             const int16_t* p = (const int16_t*)pcm + fidx * N;
             for (int i = lane; i < N; i += WAVE) XCUR(L)[i] = (float)p[i];
@@ -131,7 +142,7 @@ ENC_WAVE_FN(LC3_OW_ARGS LC3_OW_OPT(LC3_OW_ARGS_, LC3_TU_VAR, LC3_TU_VBW, LC3_TU_
         if (y12) {                                       /* lc3_enc_resample_kernel + lc3_enc_hp50_kernel (lc3_enc_pre.inc) have done the work */
             const int len12 = PI(len12);
             const float y0 = ny0, y1 = ny1;
-            if (t + 1 < T) { const float* yp = y12 + ((size_t)cs * T + t + 1) * 128; ny0 = lane < len12 ? yp[lane] : 0.0f; ny1 = lane + 64 < len12 ? yp[lane + 64] : 0.0f; }
+            if (t + 1 < ENC_TC) { const float* yp = y12 + ((size_t)cs * T + t + 1) * 128; ny0 = lane < len12 ? yp[lane] : 0.0f; ny1 = lane + 64 < len12 ? yp[lane + 64] : 0.0f; }
             float keep[6];
 #pragma unroll
             for (int k = 0; k < 6; k++) { const int i = lane + 64 * k; keep[k] = (i + len12 < 384) ? L.h12[i + len12] : 0.0f; }
@@ -237,7 +248,7 @@ ENC_WAVE_FN(LC3_OW_ARGS LC3_OW_OPT(LC3_OW_ARGS_, LC3_TU_VAR, LC3_TU_VBW, LC3_TU_
         if (uni(L.isc[I_LSB]) == 0) st_residual(P, L, lane, tbq, uni(L.isc[I_NBITS2]));
         else { for (int i = lane; i < 160; i += WAVE) ((uint32_t*)RESB(L))[i] = 0; if (lane == 0) L.isc[I_NRES] = 0; LSYNC(); }
         TICK(15);
-        if (spec && t + 1 < T) SPEC_PREFETCH(t + 1);
+        if (spec && t + 1 < ENC_TC) SPEC_PREFETCH(t + 1);
         if (dump) {
             /* the bitstream of a frame depends on nothing but this: scalars, residual bits, quantised lines up to lastnz.  The
              * serial writer runs one frame per lane in lc3_enc_pack_kernel. */
@@ -297,3 +308,4 @@ ENC_WAVE_FN(LC3_OW_ARGS LC3_OW_OPT(LC3_OW_ARGS_, LC3_TU_VAR, LC3_TU_VBW, LC3_TU_
     if (lane < 16 && !(spec && (lane == I_ATT_POS || lane == I_ATT_FLAG))) ((int*)stp)[LC3D_ST_SCAL(MEMCAP) + 16 + lane] = L.isc[lane];
     (void)ml;
 }
+#undef ENC_TC

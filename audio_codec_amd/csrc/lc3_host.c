@@ -376,6 +376,12 @@ struct lc3plus_batch {
     int bw_unsafe;                  /* set_bandwidth has installed a value with a cut-off line below 1 since the last read-back */
     int dry;                        /* DRY_*: the call checks its arguments as always and returns before it touches the device (sharded batches) */
     int placed;                     /* lc3plus_enc_batch_set_pcm_placement is on: the calls below refuse host PCM, traces and the channel-major layout */
+    int ragged;                     /* lc3plus_enc_batch_set_frame_counts is on: only encode_rates_device and encode_packed encode, the others refuse */
+    /* a ragged call has left the copy stale: a stream that was absent from it may still hold a one-shot attack-detector reset in its device configuration
+     * (lc3_enc_rates_tail_kernel_rag leaves such a stream alone), which the stale copy does not show.  Until the copy is read back (enc_refresh) or a dense
+     * call with words has run (its tail kernel clears every stream's), a call treats resets as pending: the fixed-rate calls read the copy back before they
+     * launch, so that they clear and upload as ever instead of leaving the word for their next launch to act on again. */
+    int resets_unknown;
 };
 
 /* A sharded batch checks a call on every shard before any shard runs it: the per-batch call itself, stopped behind its checks.  The checks of a call come in
@@ -396,7 +402,7 @@ static LC3_Error enc_refresh(lc3plus_batch* b)
         if (!lc3d_bw_value_ok(b->chans[(size_t)i * C].bandwidth, b->g.dms)) b->bw_unsafe = 1;
     }
     batch_restride(b);
-    b->chans_stale = 0;
+    b->chans_stale = 0; b->resets_unknown = 0;
     return LC3_OK;
 }
 /* the smallest out_stride encode() accepts: stride(), or while the host's copy is stale the bound those calls have left (no read-back) */
@@ -497,7 +503,8 @@ LC3_Error lc3plus_enc_batch_set_bitrate(lc3plus_batch* b, int stream, int bitrat
     if (enc_refresh(b)) return LC3_ERROR;
     lc3d_chan tmp[MAX_CH];
     memcpy(tmp, b->chans + (size_t)stream * b->g.channels, sizeof(lc3d_chan) * b->g.channels);
-    for (int c = 0; c < b->g.channels; c++) tmp[c].reset_attack = 0;
+    /* a one-shot reset that is still pending - no frame of the stream has run since the rate that asked for it (a stream absent from ragged calls) - stays pending:
+     * the reference clears the detector at that set_bitrate, whatever rate follows */
     LC3_Error e = derive_bitrate(&b->g, bitrate, tmp);
     if (e) return e;
     memcpy(b->chans + (size_t)stream * b->g.channels, tmp, sizeof(lc3d_chan) * b->g.channels);
@@ -575,6 +582,14 @@ LC3_Error lc3plus_enc_batch_set_pcm_placement(lc3plus_batch* b, const int64_t* o
     b->placed = offsets != NULL;
     return LC3_OK;
 }
+/* records the pointer (the runtime keeps it); from here on the host-pointer, fixed-rate and host-array calls refuse (batch_encode ...) */
+LC3_Error lc3plus_enc_batch_set_frame_counts(lc3plus_batch* b, const int32_t* counts)
+{
+    if (!b) return LC3_NULL_ERROR;
+    if (lc3hip_set_frame_counts(b->dev, counts)) return LC3_ERROR;
+    b->ragged = counts != NULL;
+    return LC3_OK;
+}
 /* The wire types' conversion rule on the host (lc3_plan.h: the text the kernels compile too), element by element, byte by byte: no alignment needed on the wire side. */
 LC3_Error lc3plus_pcm_to_native(int format, const void* src, int64_t n, void* dst)
 {
@@ -616,12 +631,14 @@ static LC3_Error batch_encode(lc3plus_batch* b, const void* pcm, int pcm_on_devi
     if (!b || !pcm || !out) return LC3_NULL_ERROR;
     if (!pcm_format_ok(bitdepth)) return LC3_ERROR;
     if (placed_refuses(b->placed, pcm_on_device, bitdepth, trace)) return LC3_ERROR;
+    if (b->ragged) return LC3_ERROR;                                 /* per-stream frame counts are read by the calls with flags in device memory alone; nothing is touched here */
     if (trace && !pcm_format_plain(bitdepth)) return LC3_ERROR;      /* the traced calls take the integer formats in the default layout only */
     if (n_frames <= 0 || out_stride < enc_stride_bound(b)) return LC3_ERROR;
     DRY_STOP(b, DRY_ALL, LC3_OK);
+    if (b->resets_unknown && enc_refresh(b)) return LC3_ERROR;      /* behind ragged calls: the resets this launch consumes are cleared below, once */
     if (lc3hip_encode(b->dev, pcm, pcm_on_device, bitdepth, n_frames, out, out_stride, out_on_device, hip_stream, sync, trace, NULL, NULL)) return LC3_ERROR;
-    /* one-shot attack-state reset requests have been consumed by this launch (a stale copy has none: the device-rate calls consume them, and nothing of it
-     * is uploaded) */
+    /* one-shot attack-state reset requests have been consumed by this launch (a stale copy has none: the dense device-rate calls consume them, a copy left
+     * stale by ragged calls was read back above, and nothing of a stale copy is uploaded) */
     if (b->chans_stale) return LC3_OK;
     int dirty = 0;
     for (int i = 0; i < b->n_streams * b->g.channels; i++) if (b->chans[i].reset_attack) { b->chans[i].reset_attack = 0; dirty = 1; }
@@ -641,6 +658,7 @@ static LC3_Error batch_encode_bitrates(lc3plus_batch* b, const void* pcm, int pc
     if (!b || !pcm || !out || !bitrates) return LC3_NULL_ERROR;
     if (!pcm_format_ok(bitdepth)) return LC3_ERROR;
     if (placed_refuses(b->placed, pcm_on_device, bitdepth, trace)) return LC3_ERROR;
+    if (b->ragged) return LC3_ERROR;                                 /* as in batch_encode */
     if (trace && !pcm_format_plain(bitdepth)) return LC3_ERROR;
     if (n_frames <= 0) return LC3_ERROR;
     if (enc_refresh(b)) return LC3_ERROR;
@@ -717,6 +735,7 @@ static LC3_Error batch_encode_bandwidths(lc3plus_batch* b, const void* pcm, int 
 {
     if (!b) return LC3_NULL_ERROR;
     if (placed_refuses(b->placed, pcm_on_device, pcm_format_ok(bitdepth) ? bitdepth : 0, NULL)) return LC3_ERROR;
+    if (b->ragged) return LC3_ERROR;                                 /* as in batch_encode */
     if (b->g.hrmode) return LC3_HRMODE_BW_ERROR;
     if (enc_refresh(b)) return LC3_ERROR;
     const size_t n = (size_t)b->n_streams * (n_frames > 0 ? n_frames : 0);
@@ -869,6 +888,7 @@ LC3_Error lc3plus_enc_batch_encode_rates_device(lc3plus_batch* b, const void* pc
     if (enc_rate_rule(&b->g, out_stride, &r)) return LC3_ERROR;
     int resets = 0;                             /* one-shot attack-detector resets pending from set_bitrate (a stale copy has none) */
     if (!b->chans_stale) for (int i = 0; i < b->n_streams * b->g.channels; i++) resets |= b->chans[i].reset_attack != 0;
+    resets |= b->resets_unknown;                /* (a stale copy behind ragged calls may have some) */
     if (lc3hip_encode_rates_device(b->dev, pcm, bitdepth, n_frames, out, out_stride, bitrates, bandwidths, &r, num_bytes, flags, resets, hip_stream, sync))
         return LC3_ERROR;
     /* the configuration after the call is on the device only: the host copy is read back by the next host-side reader or writer; until then encode()
@@ -876,15 +896,16 @@ LC3_Error lc3plus_enc_batch_encode_rates_device(lc3plus_batch* b, const void* pc
     if (!b->chans_stale) b->stride_bound = b->stride;
     if (bitrates && out_stride > b->stride_bound) b->stride_bound = out_stride;
     b->chans_stale = 1;
+    b->resets_unknown = b->ragged;              /* a dense call's tail kernel has cleared every stream's reset; a ragged one's only those of the streams that ran */
     return LC3_OK;
 }
 /* test hook: the rule of encode_rates_device on host arrays, without a device.  start_rates, start_bw [n_streams]: the stream's configuration before
  * the call; bitrates, bandwidths: NULL or [n_streams][n_frames]; out: num_bytes, bw_in_force, flags [n_streams][n_frames], end_rates [n_streams] */
-LC3_Error lc3plus_enc_plan_rates_lenient(int samplerate, int channels, float frame_ms, int hrmode, int n_streams, const int* start_rates, const int* start_bw,
-                                         const int* bitrates, const int* bandwidths, int n_frames, int out_stride, int* num_bytes, int* bw_in_force,
-                                         uint8_t* flags, int* end_rates)
+static LC3_Error enc_plan_rates_host(int samplerate, int channels, float frame_ms, int hrmode, int n_streams, const int* start_rates, const int* start_bw,
+                                     const int* bitrates, const int* bandwidths, int n_frames, int out_stride, int* num_bytes, int* bw_in_force,
+                                     uint8_t* flags, int* end_rates, const int32_t* counts, int need_words)
 {
-    if (!start_rates || !start_bw || !num_bytes || !bw_in_force || !flags || !end_rates || (!bitrates && !bandwidths)) return LC3_NULL_ERROR;
+    if (!start_rates || !start_bw || !num_bytes || !bw_in_force || !flags || !end_rates || (need_words && !bitrates && !bandwidths)) return LC3_NULL_ERROR;
     if (n_streams <= 0 || n_frames <= 0) return LC3_ERROR;
     if (!samplerate_ok(samplerate)) return LC3_SAMPLERATE_ERROR;
     if (channels < 1 || channels > MAX_CH) return LC3_CHANNELS_ERROR;
@@ -904,15 +925,33 @@ LC3_Error lc3plus_enc_plan_rates_lenient(int samplerate, int channels, float fra
     }
     for (int s = 0; s < n_streams; s++) {
         int rate = start_rates[s], bytes = lc3d_enc_rate_bytes(rate, r.lo, r.hi, r.N, r.fs_in, r.channels, r.max_chan, out_stride), bw = start_bw[s];
-        for (int t = 0; t < n_frames; t++) {
+        const int c = counts ? lc3d_dec_count_clamp(counts[s], n_frames) : n_frames;       /* the frames present; the rest are absent and not looked at */
+        for (int t = 0; t < c; t++) {
             const size_t i = (size_t)s * n_frames + t;
             flags[i] = (uint8_t)lc3d_enc_frame_step(&r, bitrates != NULL, bitrates ? bitrates[i] : 0, bandwidths != NULL, bandwidths ? bandwidths[i] : 0,
                                                     &rate, &bytes, &bw);
             num_bytes[i] = bytes; bw_in_force[i] = bw;
         }
+        for (int t = c; t < n_frames; t++) { const size_t i = (size_t)s * n_frames + t; flags[i] = LC3D_ENC_FL_ABSENT; num_bytes[i] = 0; bw_in_force[i] = 0; }
         end_rates[s] = rate;
     }
     return LC3_OK;
+}
+LC3_Error lc3plus_enc_plan_rates_lenient(int samplerate, int channels, float frame_ms, int hrmode, int n_streams, const int* start_rates, const int* start_bw,
+                                         const int* bitrates, const int* bandwidths, int n_frames, int out_stride, int* num_bytes, int* bw_in_force,
+                                         uint8_t* flags, int* end_rates)
+{
+    return enc_plan_rates_host(samplerate, channels, frame_ms, hrmode, n_streams, start_rates, start_bw, bitrates, bandwidths, n_frames, out_stride, num_bytes,
+                               bw_in_force, flags, end_rates, NULL, 1);
+}
+/* test hook: the same rule with per-stream frame counts (lc3plus_enc_batch_set_frame_counts): counts NULL or host [n_streams]; bitrates and bandwidths may both
+ * be NULL (a ragged encode_packed call with neither: every present frame has the carried size) */
+LC3_Error lc3plus_enc_plan_rates_ragged(int samplerate, int channels, float frame_ms, int hrmode, int n_streams, const int* start_rates, const int* start_bw,
+                                        const int* bitrates, const int* bandwidths, int n_frames, int out_stride, int* num_bytes, int* bw_in_force,
+                                        uint8_t* flags, int* end_rates, const int32_t* counts)
+{
+    return enc_plan_rates_host(samplerate, channels, frame_ms, hrmode, n_streams, start_rates, start_bw, bitrates, bandwidths, n_frames, out_stride, num_bytes,
+                               bw_in_force, flags, end_rates, counts, 0);
 }
 
 /* ---- packed output in device memory (lc3plus_enc_batch_encode_packed) ---- */
@@ -935,8 +974,9 @@ LC3_Error lc3plus_enc_batch_encode_packed(lc3plus_batch* b, const void* pcm, int
     const int lim = enc_max_chan_bytes(&b->g) * b->g.channels;
     lc3d_rate_rule r;
     if (enc_rate_rule(&b->g, lim, &r)) return LC3_ERROR;
-    const int has = bitrates || bandwidths;
-    int resets = 0;                             /* one-shot attack-detector resets pending from set_bitrate (a stale copy has none) */
+    const int has = bitrates || bandwidths || b->ragged;      /* (ragged: the plan and tail kernels run whatever the call has, and a stream that did not run keeps a pending reset) */
+    if (!has && b->resets_unknown && enc_refresh(b)) return LC3_ERROR;      /* as batch_encode */
+    int resets = b->resets_unknown;             /* one-shot attack-detector resets pending from set_bitrate (a stale copy has none, unless ragged calls left it) */
     if (!b->chans_stale) for (int i = 0; i < b->n_streams * b->g.channels; i++) resets |= b->chans[i].reset_attack != 0;
     if (lc3hip_encode_packed(b->dev, pcm, bitdepth, n_frames, bitrates, bandwidths, &r, order, out, (long long)out_capacity, (long long*)offsets,
                              (long long*)total, num_bytes, flags, resets, hip_stream, sync)) return LC3_ERROR;
@@ -944,6 +984,7 @@ LC3_Error lc3plus_enc_batch_encode_packed(lc3plus_batch* b, const void* pcm, int
         if (!b->chans_stale) b->stride_bound = b->stride;
         if (bitrates && lim > b->stride_bound) b->stride_bound = lim;
         b->chans_stale = 1;
+        b->resets_unknown = b->ragged;
         return LC3_OK;
     }
     /* as encode(): the one-shot attack-state reset requests have been consumed by this launch */

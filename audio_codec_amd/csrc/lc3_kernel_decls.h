@@ -27,7 +27,7 @@
 #define LC3_OW_ARGS_PK_1 , const long long* __restrict__ poff /* [stream][dT] byte offset of each stream-frame in out, -1: not written */
 /* the two parameters every placed kernel (_plc: lc3_plan.h lc3d_pcm_placed_*, lc3_kernels.hip pcm_placed_load) takes behind those of its dense twin */
 #define LC3_PLACED_ARGS , const long long* __restrict__ plo /* [stream][T] element offset of each stream-frame's PCM */, long long plcap /* length of the PCM buffer, elements */
-/* the parameter every ragged decoder kernel (_rag: lc3_dec_kernels.inc DEC_TC) takes behind those of its dense twin, behind the placed ones where it has both */
+/* the parameter every ragged kernel (_rag: lc3_dec_kernels.inc DEC_TC, lc3_enc_wave.inc ENC_TC) takes behind those of its dense twin, behind the placed ones where it has both */
 #define LC3_RAGGED_ARGS , const int32_t* __restrict__ cnt /* [stream] frames of each stream present in this call, clamped to 0 ... T */
 #define LC3_OW_OPT_(G, var, vbw, pk) G##VAR_##var G##VBW_##vbw G##PK_##pk
 #define LC3_OW_OPT(G, var, vbw, pk) LC3_OW_OPT_(G, var, vbw, pk)
@@ -45,6 +45,14 @@
         name##_wire(LC3_OW_ARGS LC3_OW_OPT(LC3_OW_ARGS_, var, vbw, pk)), name##_plc(LC3_OW_ARGS LC3_OW_OPT(LC3_OW_ARGS_, var, vbw, pk) LC3_PLACED_ARGS);
 LC3_OW_KERNELS(LC3_OW_DECL)
 #undef LC3_OW_DECL
+/* The ragged forms (per-stream frame counts, lc3plus_enc_batch_set_frame_counts), in objects of their own.  A ragged call always has per-frame sizes and an offset
+ * table - lc3_enc_plan_rates_kernel_rag writes both - so var and pk are 1 in every one: X(dense twin, large layout, var, vbw, pk), named twin_rag, twin_rag_fmt ... */
+#define LC3_OW_RAG_KERNELS(X) X(lc3_encode_kernel_var_pk, 0, 1, 0, 1) X(lc3_encode_kernel_big_var_pk, 1, 1, 0, 1) X(lc3_encode_kernel_var_vbw_pk, 0, 1, 1, 1)
+#define LC3_OW_RAG_DECL(name, big, var, vbw, pk) \
+    extern "C" __global__ void name##_rag(LC3_OW_ARGS LC3_OW_OPT(LC3_OW_ARGS_, var, vbw, pk) LC3_RAGGED_ARGS), name##_rag_fmt(LC3_OW_ARGS LC3_OW_OPT(LC3_OW_ARGS_, var, vbw, pk) LC3_RAGGED_ARGS), \
+        name##_rag_wire(LC3_OW_ARGS LC3_OW_OPT(LC3_OW_ARGS_, var, vbw, pk) LC3_RAGGED_ARGS), name##_rag_plc(LC3_OW_ARGS LC3_OW_OPT(LC3_OW_ARGS_, var, vbw, pk) LC3_PLACED_ARGS LC3_RAGGED_ARGS);
+LC3_OW_RAG_KERNELS(LC3_OW_RAG_DECL)
+#undef LC3_OW_RAG_DECL
 
 extern "C" {
 /* ---- the encoder's pipeline (lc3_enc_*.inc), in alphabetical order ---- */
@@ -164,6 +172,14 @@ __global__ void lc3_enc_plan_rates_kernel(lc3d_rate_rule r, const int32_t* __res
     uint8_t* __restrict__ flags, int4* __restrict__ pend, int vec4);
 __global__ void lc3_enc_rates_tail_kernel(const int4* __restrict__ pend, const lc3d_chan* __restrict__ etab, lc3d_chan* __restrict__ chans, int channels, int ncs,
     int dms, int all);
+/* the encoder's ragged calls (lc3_enc_ragged.inc) */
+__global__ void lc3_enc_plan_rates_kernel_rag(lc3d_rate_rule r, const int32_t* __restrict__ rates, const int32_t* __restrict__ bws, int T, int n_streams,
+    int4* __restrict__ carry, const lc3d_chan* __restrict__ seed, uint16_t* __restrict__ fsz, uint16_t* __restrict__ bwf, int32_t* __restrict__ num_bytes,
+    uint8_t* __restrict__ flags, int4* __restrict__ pend, int vec4, const int32_t* __restrict__ counts, int32_t* __restrict__ cnt, long long* __restrict__ tab,
+    int out_stride);
+__global__ void lc3_enc_rates_tail_kernel_rag(const int4* __restrict__ pend, const lc3d_chan* __restrict__ etab, lc3d_chan* __restrict__ chans, int channels, int ncs,
+    int dms, int all, const int32_t* __restrict__ cnt);
+__global__ void lc3_enc_absent_kernel(const int32_t* __restrict__ cnt, int T, long long n, uint8_t* __restrict__ flags);
 __global__ void lc3_fastmath_test_kernel(int kind, const float* __restrict__ x, float* __restrict__ y, long long n);
 __global__ void lc3_pcm_placed_mark_kernel(const long long* __restrict__ plo, long long plcap, int channels, int N, long long n, uint8_t* __restrict__ out, int bit);
 __global__ void lc3_pack_base_kernel(long long* __restrict__ bsum, long long nb, long long* __restrict__ total);

@@ -42,6 +42,8 @@
  * (lc3_enc_wave.inc); three kinds hold more: */
 #ifdef LC3_DEC_RAGGED
 #define LC3_TU_DEC_RAGGED 1     /* the four _rag objects (with -DLC3_BIG and / or the _plc switches): the decoder's ragged kernels and nothing else, no one-wave kernel either */
+#elif defined(LC3_ENC_RAGGED_PLAN)
+#define LC3_TU_ENC_RAGGED_PLAN 1 /* the _eplan object: the plan, tail and absent-flag kernels of the encoder's ragged calls (lc3_enc_ragged.inc) and nothing else */
 #elif !defined(LC3_ENC_VAR) && !defined(LC3_ENC_VBW) && !defined(LC3_ENC_PACKED) && !defined(LC3_PCM_FMT)
 #define LC3_TU_MAIN 1           /* the plain object (or with -DLC3_BIG the large-layout one): every other kernel of the library */
 #elif defined(LC3_ENC_VBW) && !defined(LC3_ENC_VAR) && !defined(LC3_ENC_PACKED) && !defined(LC3_PCM_FMT)
@@ -96,12 +98,25 @@
 #endif
 /* -DLC3_ENC_PACKED: the same kernel writing packed output (lc3plus_enc_batch_encode_packed), named with _pk, in objects of its own: frame (stream, t) goes to
  * out + poff[stream][dT] (lc3_pack_offsets_kernel), or nowhere where poff is -1 (the frame does not fit the caller's capacity) */
-#ifdef LC3_ENC_PACKED
+/* -DLC3_ENC_RAGGED (with -DLC3_ENC_VAR -DLC3_ENC_PACKED, the _erag objects): the same kernel once more with per-stream frame counts (lc3plus_enc_batch_set_frame_counts,
+ * lc3_enc_wave.inc: ENC_TC), named with _rag behind _pk.  A ragged call always has per-frame sizes and a table of offsets (the ragged plan kernel writes both), so
+ * these three - standard, standard with bandwidths, large - times the PCM forms are all there are. */
+#ifdef LC3_ENC_RAGGED
+#if !defined(LC3_ENC_VAR) || !defined(LC3_ENC_PACKED)
+#error "the ragged one-wave kernels are built with per-frame sizes and an offset table"
+#endif
+#define LC3_PK_CAT2(a) a##_pk_rag
+#define LC3_PK_CAT(a) LC3_PK_CAT2(a)
+#define KERNEL_FN LC3_PK_CAT(KERNEL_NAME)
+#define LC3_ENC_RAGGED_OPT LC3_RAGGED_ARGS
+#elif defined(LC3_ENC_PACKED)
 #define LC3_PK_CAT2(a) a##_pk
 #define LC3_PK_CAT(a) LC3_PK_CAT2(a)
 #define KERNEL_FN LC3_PK_CAT(KERNEL_NAME)
+#define LC3_ENC_RAGGED_OPT
 #else
 #define KERNEL_FN KERNEL_NAME
+#define LC3_ENC_RAGGED_OPT
 #endif
 #define NQL ((MAXN / 4 + 63) / 64)   /* bisection energies (4 bins each) per lane: 2 or 4 */
 #define LSYNC() __syncthreads()
@@ -2890,6 +2905,8 @@ template <class LdsT> STAGE void st_bitstream(const lc3d_plan* __restrict__ P, c
 #if !defined(LC3_BIG) && !defined(LC3_PCM_PLACED)
 #include "lc3_dec_imdct4.inc"
 #endif
+#elif defined(LC3_TU_ENC_RAGGED_PLAN)
+#include "lc3_enc_ragged.inc"     /* lc3_enc_plan_rates_kernel_rag, lc3_enc_rates_tail_kernel_rag, lc3_enc_absent_kernel */
 #else
 #include "lc3_enc_wave.inc"       /* KERNEL_FN, or KERNEL_FN with _fmt */
 #endif

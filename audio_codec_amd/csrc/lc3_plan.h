@@ -152,6 +152,10 @@ static inline LC3D_HD int lc3d_dec_frame_class_packed(int nb, int bfi, long long
  * lc3plus_dec_plan_counts, on the device in the ragged plan kernels (lc3_dec_kernels.inc). */
 #define LC3D_DEC_ST_ABSENT 8
 static inline LC3D_HD int lc3d_dec_count_clamp(int count, int n_frames) { return count < 0 ? 0 : count > n_frames ? n_frames : count; }
+/* The encoder's counterpart (lc3plus_enc_batch_set_frame_counts), with the same clamp: an absent frame's rate, bandwidth and placement entries are not looked at,
+ * no sample of its PCM is read, it is not encoded, no byte of out is written, its num_bytes is 0 and its flags are exactly LC3D_ENC_FL_ABSENT.  On the host in
+ * lc3plus_enc_plan_rates_ragged, on the device in lc3_enc_plan_rates_kernel_rag (lc3_enc_ragged.inc). */
+#define LC3D_ENC_FL_ABSENT 32
 /* Packed encoder output (lc3plus_enc_batch_encode_packed): a frame of nb bytes at offset off is written where it fits the caller's capacity; one that does
  * not is still encoded, but its bytes are not written and it gets LC3D_ENC_FL_PACK_CAP.  The host hook lc3plus_plan_packed and lc3_pack_offsets_kernel. */
 #define LC3D_ENC_FL_PACK_CAP 8

@@ -88,6 +88,9 @@ struct lc3hip_ctx {
     hipStream_t s_pk[2]; hipEvent_t ev_pk[2]; int pk_par;       /* the bitstream writers of consecutive calls beside each other (enc_writer) */
     float* d_spec[LC3D_SETS]; size_t spec_cap[LC3D_SETS]; float* d_frec[LC3D_SETS]; size_t frec_cap[LC3D_SETS]; hipEvent_t ev_done[LC3D_SETS]; float* d_xnext[LC3D_SETS + 1]; int xn_par, row_par; uint8_t* h_attack; int any_attack;
     const long long* plo; long long plcap;         /* lc3hip_set_pcm_placement: per-frame PCM offsets in device memory (null: off) and the buffer's length in elements */
+    /* lc3hip_set_frame_counts: the caller's per-stream frame counts in device memory (null: off), and the clamped copy [n_streams] that the ragged plan kernel of a
+     * call writes and its other kernels read.  One buffer: ragged calls are ordered on the caller's stream, none overlaps another.  rag: the call being queued is one. */
+    const int32_t* counts; int32_t* d_cnt; int rag;
     int input_ready, ahead_ok, ahead_T, ahead_R;   /* lc3hip_set_input_ready: side kernels of a call beside the previous call's tail */   /* split path (lc3_enc_front.inc) */      /* per channel-frame status bits of the last call (LC3D_ENC_ST_*) */
     /* host-pointer pipeline (lc3hip_encode_host): two chunk slots, each with device staging and (for pageable callers) pinned staging */
     void* hp_dpcm[2]; void* hp_pin_in[2]; size_t hp_pcm_cap, hp_pin_in_cap;
@@ -117,7 +120,7 @@ struct lc3hip_ctx {
     int4* d_carry; int carry_seed; hipEvent_t ev_plan, ev_pset_prev; int plan_armed;
     uint16_t* d_pfsz[LC3D_SETS]; uint16_t* d_pbw[LC3D_SETS]; int4* d_pend[LC3D_SETS]; size_t pset_frames; hipEvent_t ev_pset[LC3D_SETS]; int pset_armed[LC3D_SETS], pset;
     int etab_attack, etab_max;                      /* some byte count of the table has attack handling; the largest channel byte count */
-    struct { int pending, k, T; const int32_t* rates; const int32_t* bws; int32_t* nb; uint8_t* fl; lc3d_rate_rule rule; } pl;
+    struct { int pending, k, T; const int32_t* rates; const int32_t* bws; int32_t* nb; uint8_t* fl; lc3d_rate_rule rule; int stride; } pl;
     /* packed output (lc3hip_encode_packed), for the call being queued: the scan (pack_scan) writes the table of offsets the writers read - per plan set k
      * with rates or bandwidths (a set is written again behind the call that used it last, as the plan buffers), one table otherwise (on the launch stream) */
     struct { int on, order; long long cap; long long* offs; long long* total; int32_t* nb; uint8_t* fl; const long long* tab; } pk;
@@ -264,6 +267,7 @@ extern "C" int lc3hip_create(void** out_ctx, const lc3d_plan* plan, int n_stream
     HIPCHK_OR(hipMemcpy(c->d_plan, plan, sizeof(lc3d_plan), hipMemcpyHostToDevice), lc3hip_destroy(c));
     HIPCHK_OR(hipMalloc((void**)&c->d_chans, sizeof(lc3d_chan) * c->ncs), lc3hip_destroy(c));
     HIPCHK_OR(hipMalloc((void**)&c->d_state, sizeof(float) * c->state_words * (size_t)c->ncs), lc3hip_destroy(c));
+    HIPCHK_OR(hipMalloc((void**)&c->d_cnt, sizeof(int32_t) * (size_t)n_streams), lc3hip_destroy(c));
     /* the library's own launch stream is created when a call first needs it (a caller that brings its stream never does): HIP maps streams
      * onto a few hardware queues, and the pipelined path wants its three side streams on queues of their own */
     HIPCHK_OR(hipEventCreate(&c->ev0), lc3hip_destroy(c)); HIPCHK_OR(hipEventCreate(&c->ev1), lc3hip_destroy(c));
@@ -397,6 +401,7 @@ struct enc_call {
     const uint16_t* dfsz;       /* per-frame bitrates: [stream][dT] stream-frame bytes, or null */
     const uint16_t* dbw;        /* per-frame bandwidths: [stream][dT] Hz in force (stage_bw), or null; the path is the one without them */
     bool fmt_plain, fmt_wire, placed;       /* which twin by sample type */
+    const int32_t* cnt;         /* a ragged call: [stream] clamped frame counts (the one-wave path with the _rag twins, no pre-kernels), or null */
     int set, mc, dstride; int* ddump; float* dy12; bool split;      /* enc_size_set: the call's set of hand-over buffers, and the path they select */
     bool rate_on_side;                      /* enc_pipelined: the rate chain left the caller's stream */
 };
@@ -415,7 +420,7 @@ static int enc_size_set(lc3hip_ctx* c, enc_call* q, bool in_kernel_writer)
         q->ddump = c->d_dumpv[set];
     }
     /* ahead of it: the 12.8 kHz resampler of all frames at once and its HP50 recurrence one stream per lane (lc3_enc_pre.inc) */
-    if (!q->dtr && !c->fused) {
+    if (!q->dtr && !c->fused && !q->cnt) {      /* (a ragged call resamples in its one kernel, as a traced one: the pre-kernels read every frame's PCM) */
         const size_t need = (size_t)c->ncs * q->n_frames * 128;
         /* two buffers under the input-ready promise: the next call's resampler may run beside this call's pitch kernel */
         for (int i = i0; i < i1; i++) if (grow(&c->d_y12[i], &c->y12_cap[i], need, need * sizeof(float), false)) return 1;
@@ -453,7 +458,7 @@ static int enc_one_wave(lc3hip_ctx* c, const enc_call* q)
     }
     if (q->dbw && bw_to(c, s)) return 1;
     /* the one-wave kernel of this call by layout and optional argument groups (lc3_kernel_decls.h: LC3_OW_KERNELS), or its _fmt, _wire or _plc twin */
-    const long long* pt = c->pk.on ? c->pk.tab : nullptr;         /* packed output: the _pk kernels, frames at the offsets of the call's table */
+    const long long* pt = c->pk.on || q->cnt ? c->pk.tab : nullptr;         /* packed output: the _pk kernels, frames at the offsets of the call's table (a ragged call always has one) */
     const int key = OW_KEY(c->big != 0, q->dfsz != nullptr, q->dbw != nullptr, pt != nullptr);
     auto ow = [&](auto k, auto... groups) { hipLaunchKernelGGL(k, dim3(c->ncs), dim3(WAVE), 0, s, c->d_plan, c->d_chans, c->d_state, q->dpcm, q->bitdepth, q->n_frames, q->dout, pt ? 0 : q->out_stride, c->ncs, q->dtr, q->ddump, q->dstride, q->dy12, c->d_status, q->dT, q->dt0, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, groups...); };
 #define OW_LAUNCH(name, big, var, vbw, pk) \
@@ -461,7 +466,14 @@ static int enc_one_wave(lc3hip_ctx* c, const enc_call* q)
         if (q->placed) ow(name##_plc LC3_OW_OPT(LC3_OW_VALS_, var, vbw, pk), c->plo, c->plcap); \
         else ow(BY_FMT(q, name) LC3_OW_OPT(LC3_OW_VALS_, var, vbw, pk)); \
     } else
-    LC3_OW_KERNELS(OW_LAUNCH) return 1;
+#define OW_LAUNCH_RAG(name, big, var, vbw, pk) \
+    if (key == OW_KEY(big, var, vbw, pk)) { \
+        if (q->placed) ow(name##_rag_plc LC3_OW_OPT(LC3_OW_VALS_, var, vbw, pk), c->plo, c->plcap, q->cnt); \
+        else ow((q->fmt_plain ? name##_rag : q->fmt_wire ? name##_rag_wire : name##_rag_fmt) LC3_OW_OPT(LC3_OW_VALS_, var, vbw, pk), q->cnt); \
+    } else
+    if (q->cnt) { LC3_OW_RAG_KERNELS(OW_LAUNCH_RAG) return 1; }      /* ragged: per-frame sizes and a table, or no such kernel */
+    else LC3_OW_KERNELS(OW_LAUNCH) return 1;
+#undef OW_LAUNCH_RAG
 #undef OW_LAUNCH
     return 0;
 }
@@ -729,6 +741,8 @@ static int enc_launch(lc3hip_ctx* c, const void* dpcm, int bitdepth, int n_frame
     q.fmt_plain = bitdepth == 16 || bitdepth == 24 || bitdepth == 32;
     q.fmt_wire = lc3d_pcm_type_wire(bitdepth & LC3D_PCM_TYPE_MASK) != 0;           /* the wire sample types: the _wire twins, so that the _fmt kernels stay what they were */
     q.placed = c->plo != nullptr;                                                  /* placed PCM: the _plc twins, one form for every sample type */
+    q.cnt = c->rag ? c->d_cnt : nullptr;                                           /* ragged (lc3hip_encode_rates_device): sizes always, so the one-wave path whatever n_frames */
+    if (q.cnt && (!dfsz || dtr || dt0 != 0 || dT != n_frames)) return 1;
     if (q.placed && (dt0 != 0 || dT != n_frames || (bitdepth & LC3D_PCM_CHANNEL_MAJOR))) return 1;    /* the offsets are indexed by the call's frames; the host refuses the rest */
     const bool in_kernel_writer = dtr || c->fused || dfsz || dT <= (c->input_ready ? LC3D_FUSED_MAX_T_READY : LC3D_FUSED_MAX_T);
     q.mc = c->big ? LC3D_MEMCAP_BIG : LC3D_MEMCAP_STD;
@@ -868,6 +882,7 @@ extern "C" int lc3hip_encode(void* ctx, const void* pcm, int pcm_on_device, int 
     hipStream_t s = hip_stream ? (hipStream_t)hip_stream : c->stream;
     const uint16_t* dfsz = nullptr; hipEvent_t ev_fsz = nullptr;
     const uint16_t* dbw = nullptr; hipEvent_t ev_bw = nullptr;
+    if (c->counts) return 1;                   /* per-stream frame counts: the calls with flags in device memory alone (the host refuses the others) */
     if (fsz_host && !c->d_etab) return 1;
     if (bw_host && c->big) return 1;            /* no large-layout kernels: that layout only serves high-resolution batches, which the host refuses */
     if (c->plo && (!pcm_on_device || trace_host)) return 1;      /* placed PCM: device-pointer calls without traces (the host refuses the others) */
@@ -931,6 +946,14 @@ extern "C" int lc3hip_encode(void* ctx, const void* pcm, int pcm_on_device, int 
     return 0;
 }
 
+/* the offset tables (one per plan set and one more) and, in one buffer, a slot of tile sums for each, for n frames */
+static int pk_tables(lc3hip_ctx* c, size_t n)
+{
+    lc3hip_buf b[LC3D_SETS + 2];
+    for (int i = 0; i < LC3D_SETS + 1; i++) b[i] = {(void**)&c->d_poff[i], n * sizeof(long long), false};
+    b[LC3D_SETS + 1] = {(void**)&c->d_pbsum, (size_t)(LC3D_SETS + 1) * PKS_SUMS(n) * sizeof(long long), false};
+    return grow_group(&c->poff_cap, n, b, LC3D_SETS + 2, true);
+}
 /* the pending call's plan kernel on st: behind the previous call's plan kernel (the carry), behind the call that used this set last, and - when it starts
  * from the configuration the host wrote - behind that write */
 static int plan_launch(lc3hip_ctx* c, hipStream_t st)
@@ -941,14 +964,17 @@ static int plan_launch(lc3hip_ctx* c, hipStream_t st)
     if (c->carry_seed && c->chans_armed) HIPCHK(hipStreamWaitEvent(st, c->ev_chans, 0));
     const size_t al = (size_t)c->pl.rates | (size_t)c->pl.bws | (size_t)c->pl.nb | (size_t)c->pl.fl;
     const int vec4 = (T & 3) == 0 && (al & 15) == 0 && (((size_t)c->pl.fl) & 3) == 0;
-    hipLaunchKernelGGL(lc3_enc_plan_rates_kernel, dim3((unsigned)((c->n_streams + WAVE - 1) / WAVE)), dim3(WAVE), 0, st, c->pl.rule, c->pl.rates, c->pl.bws, T,
+    auto plan = [&](auto kern, auto... ragged) { hipLaunchKernelGGL(kern, dim3((unsigned)((c->n_streams + WAVE - 1) / WAVE)), dim3(WAVE), 0, st, c->pl.rule, c->pl.rates, c->pl.bws, T,
                        c->n_streams, c->d_carry, c->carry_seed ? (const lc3d_chan*)c->d_chans : (const lc3d_chan*)nullptr, c->d_pfsz[k], c->d_pbw[k], c->pl.nb, c->pl.fl,
-                       c->d_pend[k], vec4);
+                       c->d_pend[k], vec4, ragged...); };
+    /* ragged: the clamped counts, and for slotted output the table of slots in this set's offset table (a packed call's scan fills it below) */
+    if (c->rag) { plan(lc3_enc_plan_rates_kernel_rag, c->counts, c->d_cnt, c->pk.on ? (long long*)nullptr : c->d_poff[k], c->pl.stride); if (!c->pk.on) c->pk.tab = c->d_poff[k]; }
+    else plan(lc3_enc_plan_rates_kernel);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(c->ev_plan, st)); c->plan_armed = 1;
     c->carry_seed = 0; c->pl.pending = 0;
     /* packed output: the offsets behind the sizes, on the same stream (the writers, on whichever stream, are behind this one: bw_to, ev_scan) */
-    if (c->pk.on && pack_scan(c, st, T, k, c->pl.rates ? c->d_pfsz[k] : nullptr, c->d_pend[k], c->pl.fl != nullptr, c->pl.nb != nullptr)) return 1;
+    if (c->pk.on && pack_scan(c, st, T, k, c->pl.rates || c->rag ? c->d_pfsz[k] : nullptr, c->d_pend[k], c->pl.fl != nullptr, c->pl.nb != nullptr)) return 1;
     return 0;
 }
 /* Per-frame rates and / or bandwidths in device memory, as PCM and output: the plan kernel turns them into the words the per-frame kernels read (it runs
@@ -976,6 +1002,13 @@ extern "C" int lc3hip_encode_rates_device(void* ctx, const void* pcm, int bitdep
     lc3hip_buf b[2 * LC3D_SETS];
     for (int i = 0; i < LC3D_SETS; i++) { b[2 * i] = {(void**)&c->d_pfsz[i], fb, false}; b[2 * i + 1] = {(void**)&c->d_pbw[i], fb, false}; }
     if (grow_group(&c->pset_frames, (size_t)n_frames, b, 2 * LC3D_SETS, true)) return 1;
+    /* Ragged (lc3hip_set_frame_counts): the call of this function with the _rag kernels.  Its plan kernel always writes sizes - the carried ones where the caller
+     * gave no rates - and an offset table (slotted output: every frame's slot), so the call takes the one-wave path whatever its length, ordered on s: that path
+     * ends every overlap (enc_one_wave), and the call after it forks from s again. */
+    const int rag = c->counts != nullptr;
+    if (rag && !c->pk.on && pk_tables(c, (size_t)c->n_streams * n_frames)) return 1;
+    c->rag = rag; c->pl.stride = out_stride;
+    struct rag_off { lc3hip_ctx* c; ~rag_off() { if (c->rag && !c->pk.on) c->pk.tab = nullptr; c->rag = 0; } } rag_end = {c};      /* however the call ends */
     const int k = c->pset;
     c->pl.pending = 1; c->pl.k = k; c->pl.T = n_frames; c->pl.rates = rates_dev; c->pl.bws = bws_dev; c->pl.nb = num_bytes_dev; c->pl.fl = flags_dev; c->pl.rule = *rule;
     c->bw_on = nullptr;
@@ -983,14 +1016,20 @@ extern "C" int lc3hip_encode_rates_device(void* ctx, const void* pcm, int bitdep
     /* behind the batch's last call when that went to another stream (its work there ends on it: writer, rate chain), as a stream-lifecycle call is */
     if (c->last_stream && c->last_stream != s) { HIPCHK(hipEventRecord(c->ev_pset_prev, c->last_stream)); HIPCHK(hipStreamWaitEvent(s, c->ev_pset_prev, 0)); }
     HIPCHK(hipEventRecord(c->ev0, s));
-    if (rates_dev && bw_to(c, s)) return 1;                                  /* the one-wave kernels on s read the sizes: the plan kernel in front of them */
-    if (enc_launch(c, pcm, bitdepth, n_frames, (uint8_t*)out, out_stride, s, nullptr, n_frames, 0, true, rates_dev ? c->d_pfsz[k] : nullptr,
+    if ((rates_dev || rag) && bw_to(c, s)) return 1;                         /* the one-wave kernels on s read the sizes: the plan kernel in front of them */
+    if (enc_launch(c, pcm, bitdepth, n_frames, (uint8_t*)out, out_stride, s, nullptr, n_frames, 0, true, rates_dev || rag ? c->d_pfsz[k] : nullptr,
                    bws_dev ? c->d_pbw[k] : nullptr)) return 1;
     if (c->pl.pending) return 1;                                             /* every path reads the words */
-    hipLaunchKernelGGL(lc3_enc_rates_tail_kernel, dim3((unsigned)((c->ncs + WAVE - 1) / WAVE)), dim3(WAVE), 0, s, (const int4*)c->d_pend[k], (const lc3d_chan*)c->d_etab,
-                       c->d_chans, c->channels, c->ncs, rule->dms, rates_dev ? 1 : 0);
+    auto tail = [&](auto kern, auto... ragged) { hipLaunchKernelGGL(kern, dim3((unsigned)((c->ncs + WAVE - 1) / WAVE)), dim3(WAVE), 0, s, (const int4*)c->d_pend[k], (const lc3d_chan*)c->d_etab,
+                       c->d_chans, c->channels, c->ncs, rule->dms, rates_dev ? 1 : 0, ragged...); };
+    if (rag) tail(lc3_enc_rates_tail_kernel_rag, (const int32_t*)c->d_cnt); else tail(lc3_enc_rates_tail_kernel);
     HIPCHK(hipGetLastError());
     if (placed_mark(c->plo, c->plcap, c->channels, c->N, (long long)c->n_streams * n_frames, flags_dev, LC3D_ENC_FL_PCM_PLACE, s)) return 1;
+    if (rag && flags_dev) {      /* last: an absent frame's flags are exactly LC3D_ENC_FL_ABSENT, whatever the scan and the mark above put beside it */
+        const long long n = (long long)c->n_streams * n_frames;
+        hipLaunchKernelGGL(lc3_enc_absent_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (const int32_t*)c->d_cnt, n_frames, n, flags_dev);
+        HIPCHK(hipGetLastError());
+    }
     HIPCHK(hipEventRecord(c->ev1, s));
     HIPCHK(hipEventRecord(c->ev_pset[k], s)); c->pset_armed[k] = 1; c->pset = (k + 1) % LC3D_SETS;
     /* the configuration the tail kernel wrote: later calls on other streams wait for it (as for lc3hip_upload_chans_async); a call that overlaps this one may
@@ -1017,16 +1056,12 @@ extern "C" int lc3hip_encode_packed(void* ctx, const void* pcm, int bitdepth, in
     HIPCHK(hipSetDevice(c->device));
     /* one table of offsets per slot and, in one buffer, a slot of tile sums for each; an earlier call that did not wait may still read the smaller tables, so
      * growing them waits for the device, once (the first allocation does not) */
-    const size_t n = (size_t)c->n_streams * n_frames;
-    lc3hip_buf b[LC3D_SETS + 2];
-    for (int i = 0; i < LC3D_SETS + 1; i++) b[i] = {(void**)&c->d_poff[i], n * sizeof(long long), false};
-    b[LC3D_SETS + 1] = {(void**)&c->d_pbsum, (size_t)(LC3D_SETS + 1) * PKS_SUMS(n) * sizeof(long long), false};
-    if (grow_group(&c->poff_cap, n, b, LC3D_SETS + 2, true)) return 1;
+    if (pk_tables(c, (size_t)c->n_streams * n_frames)) return 1;
     if (!c->ev_scan) HIPCHK(hipEventCreateWithFlags(&c->ev_scan, hipEventDisableTiming));
     c->pk.on = 1; c->pk.order = order; c->pk.cap = capacity; c->pk.offs = offsets_dev; c->pk.total = total_dev; c->pk.nb = num_bytes_dev; c->pk.fl = flags_dev;
     c->pk.tab = nullptr;
     int rc;
-    if (rates_dev || bws_dev)
+    if (rates_dev || bws_dev || c->counts)      /* (ragged with neither: the plan kernel still runs, on the carried sizes) */
         rc = lc3hip_encode_rates_device(ctx, pcm, bitdepth, n_frames, out, 0, rates_dev, bws_dev, rule, num_bytes_dev, flags_dev, clear_resets, hip_stream, sync);
     else
         rc = lc3hip_encode(ctx, pcm, 1, bitdepth, n_frames, out, 0, 1, hip_stream, sync, nullptr, nullptr, nullptr);
@@ -1130,6 +1165,14 @@ extern "C" int lc3hip_set_pcm_placement(void* ctx, const long long* offsets_dev,
     c->plo = offsets_dev; c->plcap = offsets_dev ? capacity : 0;
     return 0;
 }
+/* records the pointer: lc3hip_encode_rates_device and lc3hip_encode_packed read it when they are called, their plan kernel reads the array when it runs */
+extern "C" int lc3hip_set_frame_counts(void* ctx, const int32_t* counts_dev)
+{
+    lc3hip_ctx* c = (lc3hip_ctx*)ctx;
+    if (!c) return 1;
+    c->counts = counts_dev;
+    return 0;
+}
 extern "C" int lc3hip_set_input_ready(void* ctx, int ready)
 {
     lc3hip_ctx* c = (lc3hip_ctx*)ctx;
@@ -1152,7 +1195,7 @@ extern "C" int lc3hip_destroy(void* ctx)
     if (!c) return 0;
     hipSetDevice(c->device);
     hipDeviceSynchronize();
-    void* bufs[] = {c->d_plan, c->d_chans, c->d_state, c->d_pcm, c->d_out, c->d_trace, c->d_etab, c->d_carry, c->d_pbsum, c->hp_dpcm[0], c->hp_dpcm[1]};
+    void* bufs[] = {c->d_plan, c->d_chans, c->d_state, c->d_pcm, c->d_out, c->d_trace, c->d_etab, c->d_carry, c->d_pbsum, c->hp_dpcm[0], c->hp_dpcm[1], c->d_cnt};
     for (void* p : bufs) if (p) hipFree(p);
     for (int i = 0; i < LC3D_SETS; i++) {      /* what a set holds: hand-over buffers, plan buffers */
         void* set[] = {c->d_dumpv[i], c->d_statusv[i], c->d_y12[i], c->d_spec[i], c->d_frec[i], c->d_pfsz[i], c->d_pbw[i], c->d_pend[i]};

@@ -100,6 +100,10 @@ int   lc3hip_dec_set_pcm_placement(void* ctx, const long long* offsets_dev, long
  * or null: off.  Kept in the context; read on the device by lc3hip_dec_decode_dsizes and lc3hip_dec_decode_packed, which then launch the ragged kernels;
  * lc3hip_dec_decode fails while it is on (the host refuses first).  Queues nothing, waits for nothing. */
 int   lc3hip_dec_set_frame_counts(void* ctx, const int32_t* counts_dev);
+/* the encoder's counterpart (lc3plus_enc_batch_set_frame_counts; lc3_plan.h: LC3D_ENC_FL_ABSENT): read on the device by lc3hip_encode_rates_device and
+ * lc3hip_encode_packed (rates_dev and bws_dev may then both be null), which launch the ragged kernels on the one-wave path; lc3hip_encode fails while it is on (the
+ * host refuses first).  Queues nothing, waits for nothing. */
+int   lc3hip_set_frame_counts(void* ctx, const int32_t* counts_dev);
 int   lc3hip_dec_set_input_ready(void* ctx, int ready);          /* see lc3plus_dec_batch_set_input_ready (include/lc3plus_batch.h) */
 int   lc3hip_set_input_ready(void* ctx, int ready);              /* see lc3plus_enc_batch_set_input_ready (include/lc3plus_batch.h) */
 int   lc3hip_last_status(void* ctx, uint8_t* status_host, int n);        /* LC3D_ENC_ST_* bits per channel-frame of the last call; returns the count copied */

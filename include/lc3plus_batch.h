@@ -291,6 +291,47 @@ LC3_Error lc3plus_enc_batch_import_streams(lc3plus_batch* batch, const int* stre
 LC3_Error lc3plus_enc_batch_set_input_ready(lc3plus_batch* batch, int ready);
 /* Placed PCM for the encoder's input ("Placed PCM" above): offsets NULL = off. */
 LC3_Error lc3plus_enc_batch_set_pcm_placement(lc3plus_batch* batch, const int64_t* offsets, int64_t capacity);
+/* Per-stream frame counts for the encoder (the counterpart of lc3plus_dec_batch_set_frame_counts below: a transcoder that decoded a jittery tick raggedly has PCM
+ * for three frames of one stream, one of another and none of a third, and hands exactly that on).
+ *   counts : device pointer to int32 [n_streams], or NULL = off (the default; every call then behaves as without this function)
+ * The setter only records the pointer: it queues nothing and waits for nothing (LC3_NULL_ERROR for a NULL batch).  Counts are configuration, not state:
+ * get_state / set_state and the stream blobs do not carry them.  Through lc3plus_enc_sharded_shard() they apply to that shard, with its local stream indices.
+ * While counts are set they apply to encode_rates_device() and encode_packed(), the calls that return num_bytes / flags in device memory; the array is read on
+ * the device when the call's kernels run, so a kernel or copy queued earlier on the same hip_stream may produce it - the decoder batch's counts array can be
+ * handed over as it is.  A ragged call is ordered on hip_stream like a stream-lifecycle call: it does not overlap the previous call under set_input_ready(),
+ * and the call after it runs ordered too.  Every other encode call of the batch - encode(), encode_bitrates(), encode_bandwidths(), the traced calls -
+ * returns LC3_ERROR, queues nothing and leaves the batch unchanged; lc3plus_enc_sharded_encode() and _encode_device() make that check for all shards before
+ * any shard is touched.
+ *
+ * The rule.  With c = min(max(counts[s], 0), n_frames) for a call of n_frames, of stream s
+ *   frames t < c are PRESENT: exactly as in the same call without counts - the lenient rate / bandwidth rule with its carry and flag bits 0 ... 2, placed PCM
+ *     with flag bit 4, packed output with flag bit 3, every PCM format word and layout (LC3PLUS_PCM_CHANNEL_MAJOR: the channel distance stays n_frames);
+ *   frames t >= c are ABSENT: their bitrates, bandwidths and placement entries are not looked at - no result depends on their values, which may be left
+ *     uninitialised; the arrays still hold n_frames entries per stream, and a kernel may load an absent entry with its neighbours (a group of four rates, a
+ *     placement entry) without using it - no sample of their PCM is read, not as the "next" or "previous" frame of a present one either, they are not encoded, no byte of out is written for them, num_bytes[s][t] is 0, flags[s][t] is exactly 32
+ *     (bit 5, "absent", LC3PLUS_ENC_FL_ABSENT, and no other bit) and their last_status entries are 0.
+ * Packed output: an absent frame has size 0 in the scan - offsets[s][t] is the running offset at its place in `order`, total the sum over the present frames
+ * (what lc3plus_plan_packed gives for sizes with zeros in them).
+ * After the call the stream's state (MDCT overlap, pitch and LTPF histories, attack detector, rate loop) is the state after its c present frames, and its
+ * configured rate and bandwidth those after its last present frame; with c = 0 state and configuration are bit for bit what they were - a one-shot
+ * attack-detector reset pending from set_bitrate() included, which takes effect at the stream's first present frame, whenever that comes.  So a sequence of
+ * ragged calls gives each stream the bytes, sizes and flags that one dense sequence of its present frames gives, and counts that all equal n_frames give the
+ * bytes, sizes, flags and state of the call without counts.  ("State": every word a later frame reads.  get_state() also returns per-frame scalars that the
+ * one-wave kernels store and the pipelined kernels leave alone, and unused words in front of the MDCT memory; where the dense call runs pipelined - long calls
+ * without per-frame bitrates - those bytes differ, as they do between a short and a long dense call, and the batches carry on alike.)  Only a tail can be
+ * absent: a count skips no frame in the middle of a call.
+ * Changed with this function: lc3plus_enc_batch_set_bitrate() no longer drops a one-shot reset that is still pending.  A rate that disables attack handling
+ * followed, with no frame of the stream between, by one that enables it now clears the detector, as the reference does at the disabling call
+ * (setup_enc_lc3.c:297-308); before, the second call cancelled the first one's reset.
+ * A ragged call of any length runs one channel-stream per wavefront (the path of short calls: ragged ticks are short); the pipelined kernels that long dense
+ * calls use have no ragged form yet. */
+#define LC3PLUS_ENC_FL_ABSENT 32
+LC3_Error lc3plus_enc_batch_set_frame_counts(lc3plus_batch* batch, const int32_t* counts);
+/* That rule on the host alone, no device: lc3plus_enc_plan_rates_lenient with counts, host int32 [n_streams] or NULL = dense; bitrates and bandwidths may both
+ * be NULL (encode_packed with neither).  Absent entries: num_bytes 0, bw_in_force 0, flags 32; end_rates is taken after the last present frame. */
+LC3_Error lc3plus_enc_plan_rates_ragged(int samplerate, int channels, float frame_ms, int hrmode, int n_streams, const int* start_rates,
+                                        const int* start_bw, const int* bitrates, const int* bandwidths, int n_frames, int out_stride,
+                                        int* num_bytes, int* bw_in_force, uint8_t* flags, int* end_rates, const int32_t* counts);
 
 /* Kernel-only timing of the last encode() call in milliseconds (HIP events on the launch stream). */
 float lc3plus_enc_batch_last_kernel_ms(lc3plus_batch* batch);

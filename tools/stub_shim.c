@@ -16,7 +16,7 @@ enum { STUB_ENCODE = 1, STUB_DECODE = 2, STUB_GET_STATE = 3, STUB_SET_STATE = 4,
 /* p: encode pcm, out; decode frames, pcm, status, bfi; state: the host pointer.  a / b: the first two words and the last one of the two per-frame arrays
  * the call was given (encode: frame sizes, bandwidths in force; decode: sizes, loss flags), -1 where there is none.  sync / on_device as passed.
  * STUB_PLACEMENT (lc3hip_set_pcm_placement, lc3hip_dec_set_pcm_placement): p[0] the offsets pointer, a[0] the capacity.
- * STUB_COUNTS (lc3hip_dec_set_frame_counts): p[0] the counts pointer. */
+ * STUB_COUNTS (lc3hip_set_frame_counts, lc3hip_dec_set_frame_counts): p[0] the counts pointer. */
 typedef struct {
     int32_t ctx, kind, dec, n_frames, stride, fmt, on_device, sync;
     uint64_t p[4];
@@ -98,7 +98,7 @@ static int stub_placement(void* ctx, const long long* offsets_dev, long long cap
 }
 int lc3hip_set_pcm_placement(void* ctx, const long long* offsets_dev, long long capacity) { return stub_placement(ctx, offsets_dev, capacity); }
 int lc3hip_dec_set_pcm_placement(void* ctx, const long long* offsets_dev, long long capacity) { return stub_placement(ctx, offsets_dev, capacity); }
-int lc3hip_dec_set_frame_counts(void* ctx, const int32_t* counts_dev)
+static int stub_counts(void* ctx, const int32_t* counts_dev)
 {
     lc3stub_rec r; memset(&r, 0, sizeof r);
     r.kind = STUB_COUNTS; r.p[0] = (uint64_t)(uintptr_t)counts_dev;
@@ -106,6 +106,8 @@ int lc3hip_dec_set_frame_counts(void* ctx, const int32_t* counts_dev)
     (void)stub_append((const stub_ctx*)ctx, &r);
     return 0;
 }
+int lc3hip_set_frame_counts(void* ctx, const int32_t* counts_dev) { return stub_counts(ctx, counts_dev); }
+int lc3hip_dec_set_frame_counts(void* ctx, const int32_t* counts_dev) { return stub_counts(ctx, counts_dev); }
 int lc3hip_last_status(void* ctx, uint8_t* status_host, int n) { return 0; }
 int lc3hip_last_records(void* ctx, float* rec_host, int max_words) { return 0; }
 int lc3hip_test_fastmath(int kind, const float* x_host, float* y_host, long long n) { return 1; }
