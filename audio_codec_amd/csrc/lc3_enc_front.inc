@@ -26,9 +26,9 @@
 #elif defined(LC3_BIG)
 #define FRONT_KERNEL_NAME lc3_enc_front_kernel_big
 #elif FRONT_PCM_FMT
-#define FRONT_KERNEL_NAME LC3_FMT_CAT(lc3_enc_front_kernel)
+#define FRONT_KERNEL_NAME ERP_FN(LC3_FMT_CAT(lc3_enc_front_kernel))
 #else
-#define FRONT_KERNEL_NAME lc3_enc_front_kernel
+#define FRONT_KERNEL_NAME ERP_FN(lc3_enc_front_kernel)
 #endif
 
 extern "C" __global__ void __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(FRONT_WAVES, FRONT_WAVES)))
@@ -36,13 +36,20 @@ FRONT_KERNEL_NAME(const lc3d_plan* __restrict__ P, const lc3d_chan* __restrict__
                      int T, int tb, int nt /* frames tb ... tb + nt - 1 of the call's T */, int fpw /* consecutive frames per wave */, int ncs, float* __restrict__ spec /* [cs][RT][srow]: the first ylen lines (the coded ones); frame t of this launch is row r0 + t */, int srow, int RT, int r0, float* __restrict__ rec /* [cs][RT][FR_WORDS] */,
                      float* __restrict__ xnext /* [cs][MEMCAP]: the MDCT memory after the last frame (the sequential kernel moves it into the state) */,
                      const float* __restrict__ xprev /* the MDCT memory before frame 0: the state's slot, or the previous call's xnext */, int xprev_stride,
-                     int do_scf /* band energies, bandwidth detector and scale factors here (0: lc3_enc_scf_lane_kernel does them, one frame per lane) */ LC3_PLACED_OPT)
+                     int do_scf /* band energies, bandwidth detector and scale factors here (0: lc3_enc_scf_lane_kernel does them, one frame per lane) */ LC3_PLACED_OPT LC3_ERP_OPT)
 {
     __shared__ FrontLds L;
     const int lane = threadIdx.x;
     const int runs = (nt + fpw - 1) / fpw;
-    const int cs = blockIdx.x / runs, t0 = tb + (blockIdx.x % runs) * fpw, t1 = imin(tb + nt, t0 + fpw);
+#ifdef LC3_ENC_RPIPE                /* ragged: the run ends at the stream's count tend, and the wave that holds frame tend - 1 hands the MDCT memory over */
+    const int cs = blockIdx.x / runs, t0 = tb + (blockIdx.x % runs) * fpw;
     if (cs >= ncs) return;
+    const int tend = cnt[cs / P->channels], t1 = imin(imin(tb + nt, t0 + fpw), tend);
+    if (t0 >= t1) return;
+#else
+    const int cs = blockIdx.x / runs, t0 = tb + (blockIdx.x % runs) * fpw, t1 = imin(tb + nt, t0 + fpw), tend = T;
+    if (cs >= ncs) return;
+#endif
     if (lane < LC3D_PLAN_HEAD_WORDS) L.pc[lane] = ((const int*)P)[lane];
     if (lane < 14) L.cc[lane] = ((const int*)&chans[cs])[lane];
     if (lane < 56) L.isc[lane] = 0;                                        /* I_ATT_FLAG = 0: the smoothing is applied later (lc3_enc_snsvq_kernel) */
@@ -156,7 +163,7 @@ FRONT_KERNEL_NAME(const lc3d_plan* __restrict__ P, const lc3d_chan* __restrict__
         if (lane == 0) ((int*)r)[FR_ATTFLAG] = 0;   /* lc3_enc_attack_kernel sets the flag where the detector runs */
         LSYNC();
     }
-    if (t1 == T) for (int i = lane; i < MEMCAP; i += WAVE) xnext[(size_t)cs * MEMCAP + i] = L.xbuf[i];
+    if (t1 == tend) for (int i = lane; i < MEMCAP; i += WAVE) xnext[(size_t)cs * MEMCAP + i] = L.xbuf[i];
 }
 
 #if !defined(LC3_BIG) && !FRONT_PCM_FMT
@@ -164,13 +171,21 @@ FRONT_KERNEL_NAME(const lc3d_plan* __restrict__ P, const lc3d_chan* __restrict__
  * energies the front kernel left in the records and writes each frame's flag back; the detector's state lives in the stream's state
  * words (same words the sequential kernel uses on its own path).  A pending reset (R/setup_enc_lc3.c:297-308) is applied first. */
 extern "C" __global__ void __launch_bounds__(WAVE)
-lc3_enc_attack_kernel(const lc3d_plan* __restrict__ P, const lc3d_chan* __restrict__ chans, float* __restrict__ state, int state_words, int scal_off,
-                      float* __restrict__ rec /* [cs][RT][FR_WORDS], frame t = row r0 + t */, int RT, int r0, int tb, int nt, int ncs)
+ERP_FN(lc3_enc_attack_kernel)(const lc3d_plan* __restrict__ P, const lc3d_chan* __restrict__ chans, float* __restrict__ state, int state_words, int scal_off,
+                      float* __restrict__ rec /* [cs][RT][FR_WORDS], frame t = row r0 + t */, int RT, int r0, int tb, int nt, int ncs LC3_ERP_OPT)
 {
     const int cs = blockIdx.x * WAVE + threadIdx.x;
     if (cs >= ncs) return;
     float* sc = state + (size_t)cs * state_words + scal_off; int* isc = (int*)sc + 16;
-    if (chans[cs].reset_attack) { sc[F_ATT_M0] = 0; sc[F_ATT_M1] = 0; sc[F_ATT_ACC] = 0; isc[I_ATT_POS] = 0; isc[I_ATT_FLAG] = 0; }
+#ifdef LC3_ENC_RPIPE                /* ragged: the stream's present frames of this launch (none: nothing at all), the state from the record of the last of them; a pending reset
+                                     * belongs to the stream's first present frame - the launch that holds frame 0 - and stays pending for a stream with no frame (the tail kernel) */
+    nt = imin(nt, cnt[cs / P->channels] - tb);
+    if (nt <= 0) return;
+    if (tb == 0 && chans[cs].reset_attack)
+#else
+    if (chans[cs].reset_attack)
+#endif
+    { sc[F_ATT_M0] = 0; sc[F_ATT_M1] = 0; sc[F_ATT_ACC] = 0; isc[I_ATT_POS] = 0; isc[I_ATT_FLAG] = 0; }
     if (!chans[cs].attack_handling || nt <= 0) return;
     float acc = sc[F_ATT_ACC]; int pos = isc[I_ATT_POS], flag = 0;
     const int nb = P->att_nblocks, hang = P->att_hang; const float mval = P->fs == 96000 ? 1e-5f : 0.0f;

@@ -79,19 +79,26 @@ __device__ __forceinline__ void f4_dft240x4(float* x, const lc3d_plan* __restric
 #endif
 extern "C" __global__ void __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(F4_WAVES, F4_WAVES)))
 #ifdef LC3_PCM_FMT               /* the object of the PCM formats beyond 16 / 24 / 32 (float samples, the interleaved and the channel-major layout): the PCM load differs, nothing else */
-LC3_FMT_CAT(lc3_enc_front4_kernel)(
+ERP_FN(LC3_FMT_CAT(lc3_enc_front4_kernel))(
 #else
-lc3_enc_front4_kernel(
+ERP_FN(lc3_enc_front4_kernel)(
 #endif
                       const lc3d_plan* __restrict__ P, const lc3d_chan* __restrict__ chans, const float* __restrict__ state, const void* __restrict__ pcm, int bitdepth,
                       int T, int tb, int nt /* frames tb ... tb + nt - 1 of the call's T */, int ncs, float* __restrict__ spec, int srow, int RT, int r0, float* __restrict__ rec,
-                      float* __restrict__ xnext, const float* __restrict__ xprev, int xprev_stride LC3_PLACED_OPT)
+                      float* __restrict__ xnext, const float* __restrict__ xprev, int xprev_stride LC3_PLACED_OPT LC3_ERP_OPT)
 {
     __shared__ Front4Lds L;
     const int lane = threadIdx.x;
     const int runs = (nt + F4_FR - 1) / F4_FR;
-    const int cs = blockIdx.x / runs, t0 = tb + (blockIdx.x % runs) * F4_FR, nf = imin(F4_FR, tb + nt - t0);
+#ifdef LC3_ENC_RPIPE                /* ragged: the group ends at the stream's count tend, and the wave that holds frame tend - 1 hands the MDCT memory over */
+    const int cs = blockIdx.x / runs, t0 = tb + (blockIdx.x % runs) * F4_FR;
     if (cs >= ncs) return;
+    const int tend = cnt[cs / P->channels], nf = imin(imin(F4_FR, tb + nt - t0), tend - t0);
+    if (nf <= 0) return;
+#else
+    const int cs = blockIdx.x / runs, t0 = tb + (blockIdx.x % runs) * F4_FR, nf = imin(F4_FR, tb + nt - t0), tend = T;
+    if (cs >= ncs) return;
+#endif
     if (lane < LC3D_PLAN_HEAD_WORDS) L.pc[lane] = ((const int*)P)[lane];
     if (lane < 14) L.cc[lane] = ((const int*)&chans[cs])[lane];
     LSYNC();
@@ -175,7 +182,7 @@ lc3_enc_front4_kernel(
     }
 #endif
     LSYNC();
-    if (t0 + nf == T) for (int i = lane; i < MEMCAP; i += WAVE) xnext[(size_t)cs * MEMCAP + i] = L.x[N * nf + i];     /* the MDCT memory behind the call's last frame */
+    if (t0 + nf == tend) for (int i = lane; i < MEMCAP; i += WAVE) xnext[(size_t)cs * MEMCAP + i] = L.x[N * nf + i];     /* the MDCT memory behind the call's last frame */
     float* r = rec + ((size_t)cs * RT + r0 + t0) * FR_WORDS;
     if (lane < nf) ((int*)r)[(size_t)lane * FR_WORDS + FR_ATTFLAG] = 0;   /* lc3_enc_attack_kernel sets the flag where the detector runs */
     /* ---- attack detector, first half: frame by frame (its filter memory entering a frame = the last two 16 kHz samples before it) ---- */

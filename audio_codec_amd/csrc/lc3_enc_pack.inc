@@ -119,7 +119,11 @@ pack_body(const lc3d_plan* __restrict__ P, const lc3d_chan* __restrict__ chans, 
           uint8_t* __restrict__ out, int out_stride, uint8_t* __restrict__ status /* [cs][T] LC3D_ENC_ST_* bits, or null */,
           float* __restrict__ rows /* [cs][T][srow]: the shaped spectra of the pipelined path, or null: the record is complete (lc3_encode_kernel wrote it) */, int srow,
           const float* __restrict__ frec /* [cs][T][FR_WORDS] */, int skip_bytes /* channel-streams with frames of this size and more belong to lc3_enc_tailw_kernel; 0: none */,
-          const long long* __restrict__ poff = nullptr /* PK: [stream][T] byte offset of each stream-frame in out, -1: not written (lc3_pack_offsets_kernel) */)
+          const long long* __restrict__ poff = nullptr /* PK: [stream][T] byte offset of each stream-frame in out, -1: not written (lc3_pack_offsets_kernel) */
+#ifdef LC3_ENC_RPIPE
+          , const int32_t* __restrict__ cnt = nullptr /* [stream] frames of each stream present in this call */
+#endif
+          )
 {
     __shared__ PackLds L;
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, wpg = blockDim.x >> 6, tid = threadIdx.x, nthr = blockDim.x;
@@ -136,16 +140,30 @@ pack_body(const lc3d_plan* __restrict__ P, const lc3d_chan* __restrict__ chans, 
     const int Lspec = KPI(ylen), channels = KPI(channels), fs = KPI(fs), hr = KPI(hrmode), bwb = KPI(bw_bits);
     const long long cf = ((long long)blockIdx.x * wpg + wv) * WAVE + lane;
     const bool inside = cf < (long long)ncs * nt;                                /* frames tb ... tb + nt - 1 of every channel-stream */
+#ifdef LC3_ENC_RPIPE
+    const bool valid_dense = inside && !(skip_bytes && chans[(int)(cf / nt)].nbytes >= skip_bytes);
+#else
     const bool valid = inside && !(skip_bytes && chans[(int)(cf / nt)].nbytes >= skip_bytes);
+#endif
+#ifdef LC3_ENC_RPIPE                /* ragged: a lane whose frame is absent is not valid and shadows the wave's first present frame (lc3_kernels.hip: erp_shadow) - not frame
+                                     * (0, tb), whose rows and records no kernel of this call may have written; a wave with no present frame is done */
+    int cs = inside ? (int)(cf / nt) : 0, t = inside ? tb + (int)(cf % nt) : 0;
+    const bool valid = valid_dense && t < cnt[cs / channels];
+    if (!erp_shadow(valid, cs, t)) return;                                       /* (no barrier below) */
+    const long long row = (long long)cs * T + t;
+#define PK_ROW row
+#else
     if (!__any(valid)) return;                                                   /* (no barrier below) */
     const int cs = valid ? (int)(cf / nt) : 0, t = valid ? tb + (int)(cf % nt) : 0;
     const long long row = (long long)cs * T + t;
+#define PK_ROW (valid ? row : 0)
+#endif
     const int strm = cs / channels;
     const lc3d_chan* C = &chans[cs];
     const int nbytes = valid ? C->nbytes : 0, total = C->total_bits, lpcw = C->lpc_weighting & 1;
     /* the frame's row of `dump`: plain rows when lc3_encode_kernel filled them, tiled like the spectrum rows (lc3_plan.h) when this kernel is its only user */
     const int RTd = rows ? T : 1;
-    int* r = rows ? LC3D_ROW_BASE(dump, cs, t, T, dstride) : dump + (valid ? row : 0) * dstride;
+    int* r = rows ? LC3D_ROW_BASE(dump, cs, t, T, dstride) : dump + PK_ROW * dstride;
 #define RP(k_) (&r[LC3D_ROW_OFF((k_), RTd)])
     PkW w; w.o = out + ((size_t)strm * T + t) * out_stride + (valid ? C->out_off : 0); w.nbytes = nbytes; w.q = 0; w.fw = 0; w.bw = 0; w.wr = true;
     if (PK) { const long long po = valid ? poff[(size_t)strm * T + t] : -1; w.o = out + (po < 0 ? 0 : po) + (valid ? C->out_off : 0); w.wr = po >= 0; }
@@ -164,7 +182,7 @@ pack_body(const lc3d_plan* __restrict__ P, const lc3d_chan* __restrict__ chans, 
         for (int i = 0; i < 56; i++) rc[i] = 0;
         float* xr = LC3D_ROW_BASE(rows, cs, t, T, srow);                        /* this frame's spectrum (tiled rows, lc3_plan.h) */
 #define XP(k_) (&xr[LC3D_ROW_OFF((k_), T)])
-        const int* fi = (const int*)(frec + (valid ? row : 0) * FR_WORDS);
+        const int* fi = (const int*)(frec + PK_ROW * FR_WORDS);
         {   /* what the tail needs of the record: bandwidth, TNS / LTPF side bits, the rate kernel's four words; the coder's fields are fetched behind it */
             const int4 v = *(const int4*)&fi[FR_RATE];
             rc[I_GG] = v.x; rc[I_CHANGE] = v.y /* the gain's bits for a moment */; rc[I_NBITS] = v.z;
@@ -595,10 +613,15 @@ pack_body(const lc3d_plan* __restrict__ P, const lc3d_chan* __restrict__ chans, 
 #undef KPI
 #undef RP
 #undef XW
+#undef PK_ROW
 }
 #define PK_ARGS const lc3d_plan* __restrict__ P, const lc3d_chan* __restrict__ chans, int* __restrict__ dump, int dstride, int T, int tb, int nt, int ncs, uint8_t* __restrict__ out, int out_stride, \
                 uint8_t* __restrict__ status, float* __restrict__ rows, int srow, const float* __restrict__ frec, int skip_bytes
 #define PK_PASS P, chans, dump, dstride, T, tb, nt, ncs, out, out_stride, status, rows, srow, frec, skip_bytes
+#ifdef LC3_ENC_RPIPE      /* the ragged object: the two writers of the pipelined path's ragged calls, always with a table of offsets (the ragged plan kernel's slots, or the scan's) */
+extern "C" __global__ void __launch_bounds__(4 * WAVE) __attribute__((amdgpu_waves_per_eu(PK_EU, PK_EU))) lc3_enc_pack_kernel_pk_rag(PK_ARGS, const long long* __restrict__ poff LC3_ERP_OPT) { pack_body<0, true>(PK_PASS, poff, cnt); }
+extern "C" __global__ void __launch_bounds__(4 * WAVE) __attribute__((amdgpu_waves_per_eu(5, 5))) lc3_enc_pack_kernel_w5_pk_rag(PK_ARGS, const long long* __restrict__ poff LC3_ERP_OPT) { pack_body<0, true>(PK_PASS, poff, cnt); }
+#else
 extern "C" __global__ void __launch_bounds__(4 * WAVE) __attribute__((amdgpu_waves_per_eu(PK_EU, PK_EU))) lc3_enc_pack_kernel(PK_ARGS) { pack_body<0>(PK_PASS); }
 /* The same kernel under a 96-register budget (five waves per SIMD; 36 registers go to scratch).  The register file is what the call's kernels compete for (DESIGN.md
  * section 5), and 96-register waves pack with the rate kernel's: measured at 48 kHz / 10 ms, 4096 streams x 64 frames, Mframes/s with 128 / 96 registers - 40-byte frames
@@ -613,5 +636,6 @@ extern "C" __global__ void __launch_bounds__(4 * WAVE) __attribute__((amdgpu_wav
 extern "C" __global__ void __launch_bounds__(4 * WAVE) __attribute__((amdgpu_waves_per_eu(5, 5))) lc3_enc_pack_kernel_w5_pk(PK_ARGS, const long long* __restrict__ poff) { pack_body<0, true>(PK_PASS, poff); }
 extern "C" __global__ void __launch_bounds__(4 * WAVE) __attribute__((amdgpu_waves_per_eu(PK_HEAD_EU, PK_HEAD_EU))) lc3_enc_pack_head_kernel_pk(PK_ARGS, const long long* __restrict__ poff) { pack_body<1, true>(PK_PASS, poff); }
 extern "C" __global__ void __launch_bounds__(4 * WAVE) __attribute__((amdgpu_waves_per_eu(PK_CODE_EU, PK_CODE_EU))) lc3_enc_pack_code_kernel_pk(PK_ARGS, const long long* __restrict__ poff) { pack_body<2, true>(PK_PASS, poff); }
+#endif
 #undef PK_ARGS
 #undef PK_PASS

@@ -59,7 +59,7 @@ __device__ __forceinline__ void pre48_put(float* __restrict__ d, const uint4 v, 
     ((float4*)d)[0] = a; ((float4*)d)[1] = b;
 }
 
-#ifdef LC3_PCM_PLACED               /* the placed object holds lc3_enc_resample_plc_kernel alone: a placed call always takes the resampler for every shape */
+#if defined(LC3_PCM_PLACED) || (defined(LC3_ENC_RPIPE) && defined(LC3_PCM_FMT))      /* the placed object holds lc3_enc_resample_plc_kernel alone: a placed call always takes the resampler for every shape; so does a ragged call (the typed resamplers have no ragged forms) */
 #elif defined(LC3_PCM_FMT)
 /* lc3_enc_resample48_kernel (below) for samples that follow each other in the default or the channel-major layout of the format word fmt: its tap and LDS scheme
  * unchanged, only the load and convert step differs.  A frame is 120 pieces of four samples instead of 60 of eight: a lane loads piece lane and piece lane + 60 of
@@ -172,6 +172,7 @@ PRE48_FN(const lc3d_plan* __restrict__ P, const pre48_word* __restrict__ pcm /* 
     }
 }
 #else
+#ifndef LC3_ENC_RPIPE
 extern "C" __global__ void __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(3, 3)))
 lc3_enc_resample48_kernel(const lc3d_plan* __restrict__ P, const int16_t* __restrict__ pcm /* 16-byte aligned */, int channels, int memcap,
                           int T, int tb, int nt, int ncs, float* __restrict__ d12 /* [cs][T][128] */,
@@ -331,6 +332,7 @@ NAME(const lc3d_plan* __restrict__ P, const int16_t* __restrict__ pcm, int chann
 RESAMPLE96_KERNEL(lc3_enc_resample96_kernel_n960, 960)
 RESAMPLE96_KERNEL(lc3_enc_resample96_kernel_n480, 480)
 RESAMPLE96_KERNEL(lc3_enc_resample96_kernel_n240, 240)
+#endif /* !LC3_ENC_RPIPE */
 
 /* One channel-stream per lane, all frames of the launch: y = HP50(d), in place.  R/resamp12k8.c:60-74 in the transposed direct form
  * the frame-wise code uses: y1 = b0 x + u11; u11' = (b1 x + u21) - a1 y1; u21' = b2 x - a2 y1. */
@@ -340,13 +342,17 @@ RESAMPLE96_KERNEL(lc3_enc_resample96_kernel_n240, 240)
  * hides a load as well as a whole frame did; but a wave that wants half a SIMD's registers waits for two one-frame-per-lane waves of another kernel to retire
  * before it can even start, and this kernel sits on the pitch stream's critical path (0.28 ms alone, 0.6 ... 1.5 ms beside the others in round 3's form). */
 extern "C" __global__ void __launch_bounds__(WAVE)
-lc3_enc_hp50_kernel(const lc3d_plan* __restrict__ P, float* __restrict__ state, int state_words, int scal_off, int T, int tb, int nt, int ncs, float* __restrict__ d12 /* [cs][T][128] */)
+ERP_FN(lc3_enc_hp50_kernel)(const lc3d_plan* __restrict__ P, float* __restrict__ state, int state_words, int scal_off, int T, int tb, int nt, int ncs, float* __restrict__ d12 /* [cs][T][128] */ LC3_ERP_OPT)
 {
 #ifdef HP_PRIO
     __builtin_amdgcn_s_setprio(HP_PRIO);
 #endif
     const int cs = blockIdx.x * WAVE + threadIdx.x;
     if (cs >= ncs) return;
+#ifdef LC3_ENC_RPIPE                /* ragged: the stream's frames of this launch that are present; none - nothing of the stream is read or written */
+    nt = imin(nt, cnt[cs / P->channels] - tb);
+    if (nt <= 0) return;
+#endif
     const int cpf = P->len12 >> 5;                                         /* chunks of 8 float4 (32 samples) per frame: 4, 2 or 1 */
     const double b0 = lc3t_hp50_b[0], b1 = lc3t_hp50_b[1], b2 = lc3t_hp50_b[2], a1 = lc3t_hp50_a[1], a2 = lc3t_hp50_a[2];
     float* sc = state + (size_t)cs * state_words + scal_off;
@@ -388,13 +394,17 @@ lc3_enc_hp50_kernel(const lc3d_plan* __restrict__ P, float* __restrict__ state, 
 }
 #else
 extern "C" __global__ void __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(HP_WAVES, HP_WAVES)))
-lc3_enc_hp50_kernel(const lc3d_plan* __restrict__ P, float* __restrict__ state, int state_words, int scal_off, int T, int tb, int nt, int ncs, float* __restrict__ d12 /* [cs][T][128] */)
+ERP_FN(lc3_enc_hp50_kernel)(const lc3d_plan* __restrict__ P, float* __restrict__ state, int state_words, int scal_off, int T, int tb, int nt, int ncs, float* __restrict__ d12 /* [cs][T][128] */ LC3_ERP_OPT)
 {
 #ifdef HP_PRIO
     __builtin_amdgcn_s_setprio(HP_PRIO);
 #endif
     const int cs = blockIdx.x * WAVE + threadIdx.x;
     if (cs >= ncs) return;
+#ifdef LC3_ENC_RPIPE                /* ragged: the stream's frames of this launch that are present; none - nothing of the stream is read or written */
+    nt = imin(nt, cnt[cs / P->channels] - tb);
+    if (nt <= 0) return;
+#endif
     const int ng = P->len12 >> 2;                                          /* float4 groups per frame: 8, 16 or 32 */
     const double b0 = lc3t_hp50_b[0], b1 = lc3t_hp50_b[1], b2 = lc3t_hp50_b[2], a1 = lc3t_hp50_a[1], a2 = lc3t_hp50_a[2];
     float* sc = state + (size_t)cs * state_words + scal_off;

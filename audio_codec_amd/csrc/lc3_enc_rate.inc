@@ -37,7 +37,7 @@
 #else
 #define SHAPE_KERNEL_NAME lc3_enc_shape_kernel
 #endif
-#define RATE_KERNEL_NAME  lc3_enc_rate_kernel
+#define RATE_KERNEL_NAME  ERP_FN(lc3_enc_rate_kernel)
 #define TAILW_KERNEL_NAME lc3_enc_tailw_kernel
 #ifndef SHAPE_WAVES
 #define SHAPE_WAVES 4          /* 128 registers: under a smaller budget the TNS functions spill (measured: 6 waves 50.6, 5: 52.6, 4: 65.3, 3: 65.2 Mframes/s) */
@@ -47,6 +47,7 @@
 #endif
 #endif
 
+#ifndef LC3_ENC_RPIPE       /* (the ragged object takes the rate kernel alone: the wave-per-frame shape kernel and the frame-per-wave writer are diagnostic variants without ragged forms) */
 /* ------------------------------------------------------------------------------------------------------------------------------ */
 struct __attribute__((aligned(16))) ShapeLds {
     static constexpr int MISC = 0;
@@ -148,6 +149,7 @@ SHAPE_KERNEL_NAME(const lc3d_plan* __restrict__ P, const lc3d_chan* __restrict__
     }
 #undef SHAPE_PREFETCH
 }
+#endif  /* !LC3_ENC_RPIPE */
 #ifndef LC3_ENC_VBW
 
 /* ------------------------------------------------------------------------------------------------------------------------------ */
@@ -165,7 +167,7 @@ struct __attribute__((aligned(16))) RateLds {
 extern "C" __global__ void __launch_bounds__(RATE_WG * WAVE) __attribute__((amdgpu_waves_per_eu(RATE_WAVES, RATE_WAVES)))
 RATE_KERNEL_NAME(const lc3d_plan* __restrict__ P, const lc3d_chan* __restrict__ chans, float* __restrict__ state, int T, int t0, int nt, int ncs,
                  const float* __restrict__ rows /* [cs][T][srow]: shaped spectrum | en[] */, int srow, float* __restrict__ frec /* [cs][T][FR_WORDS] */,
-                 const float* __restrict__ xnext /* [cs][MEMCAP]: stored into the state behind the launch's last frame */, int last)
+                 const float* __restrict__ xnext /* [cs][MEMCAP]: stored into the state behind the launch's last frame */, int last LC3_ERP_OPT)
 {
 #ifdef RATE_PRIO
     __builtin_amdgcn_s_setprio(RATE_PRIO);
@@ -178,6 +180,9 @@ RATE_KERNEL_NAME(const lc3d_plan* __restrict__ P, const lc3d_chan* __restrict__ 
     if (lane < 14 && cs < ncs) LL.cc[wv][lane] = ((const int*)&chans[cs])[lane];
     LSYNC();
     if (cs >= ncs) return;
+#ifdef LC3_ENC_RPIPE                /* ragged: the stream's present frames of this launch; a stream with no frame in the call is left alone - the hand-over buffer holds another call's data */
+    { const int c = cnt[cs / P->channels]; if (c == 0) return; nt = imax(imin(nt, c - t0), 0); }
+#endif
     struct { const int* pc; const int* cc; } L = { LL.pc, LL.cc[wv] };      /* what PI() / CI() name */
     float* stp = state + (size_t)cs * LC3D_STATE_WORDS(MEMCAP);
     /* the three words of the rate loop (R/setup_enc_lc3.h: targetBitsOff, mem_targetBits, mem_specBits), wave-uniform */
@@ -350,6 +355,7 @@ RATE_KERNEL_NAME(const lc3d_plan* __restrict__ P, const lc3d_chan* __restrict__ 
  * latency; the two kernels split the streams of a batch by frame size.  MEASURED AND NOT THE DEFAULT (lc3hip_opts::tailw_bytes = 0): byte-identical, but c96
  * 32.5 -> 27.3 and c5 86.5 -> 73.6 Mframes/s with it - the extra instructions cost more than the shorter tail of the call gains.  Kept as a switch
  * (LC3PLUS_ENC_TAILW_BYTES) and as the second user of the stage functions.  in: the shaped, TNS-filtered row and the frame's record; out: the frame's bytes. */
+#ifndef LC3_ENC_RPIPE
 #ifndef TAILW_WAVES
 #define TAILW_WAVES 4
 #endif
@@ -445,4 +451,5 @@ TAILW_KERNEL_NAME(const lc3d_plan* __restrict__ P, const lc3d_chan* __restrict__
     }
 #undef TAILW_PREFETCH
 }
+#endif  /* !LC3_ENC_RPIPE */
 #endif  /* !LC3_ENC_VBW */

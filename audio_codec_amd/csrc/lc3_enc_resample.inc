@@ -4,20 +4,27 @@
  * format word existed.  RESAMPLE_PCM_FMT 1 (the -DLC3_PCM_FMT object): lc3_enc_resample_fmt_kernel for the formats beyond those (float samples, the interleaved and the channel-major layout,
  * lc3_plan.h: lc3d_pcm_*); the two differ in the PCM load alone. */
 #if RESAMPLE_PCM_FMT
-#define RESAMPLE_FN LC3_RESAMPLE_FMT_FN
+#define RESAMPLE_FN ERP_FN(LC3_RESAMPLE_FMT_FN)
 #else
-#define RESAMPLE_FN lc3_enc_resample_kernel
+#define RESAMPLE_FN ERP_FN(lc3_enc_resample_kernel)
 #endif
 extern "C" __global__ void __launch_bounds__(WAVE)
 RESAMPLE_FN(const lc3d_plan* __restrict__ P, const float* __restrict__ state, int state_words, int memcap, const void* __restrict__ pcm, int bitdepth,
                         int T, int tb, int nt, int ncs, float* __restrict__ d12 /* [cs][T][128] */,
-                        const float* __restrict__ xprev /* the MDCT / resampler memory before frame 0 (slot of memcap words per channel-stream) */, int xprev_stride LC3_PLACED_OPT)
+                        const float* __restrict__ xprev /* the MDCT / resampler memory before frame 0 (slot of memcap words per channel-stream) */, int xprev_stride LC3_PLACED_OPT LC3_ERP_OPT)
 {
     __shared__ PreLds L;
     const int lane = threadIdx.x;
     const int runs = (nt + PRE_FPW - 1) / PRE_FPW;
+#ifdef LC3_ENC_RPIPE                /* ragged: the run ends at the stream's count; a wave with nothing left loads nothing */
+    const int cs = blockIdx.x / runs, t0 = tb + (blockIdx.x % runs) * PRE_FPW;
+    if (cs >= ncs) return;
+    const int t1 = imin(imin(tb + nt, t0 + PRE_FPW), cnt[cs / P->channels]);
+    if (t0 >= t1) return;
+#else
     const int cs = blockIdx.x / runs, t0 = tb + (blockIdx.x % runs) * PRE_FPW, t1 = imin(tb + nt, t0 + PRE_FPW);
     if (cs >= ncs) return;
+#endif
     if (lane < LC3D_PLAN_HEAD_WORDS) L.pc[lane] = ((const int*)P)[lane];
     for (int i = lane; i < 240; i += WAVE) L.taps[i] = P->rs_taps[i];
     LSYNC();

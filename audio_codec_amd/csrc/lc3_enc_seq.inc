@@ -36,8 +36,8 @@ struct __attribute__((aligned(16))) PitchLds {
 };
 
 extern "C" __global__ void __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(8, 8)))
-lc3_enc_pitch_kernel(const lc3d_plan* __restrict__ P, const lc3d_chan* __restrict__ chans, float* __restrict__ state, int state_words, int memcap,
-                     const float* __restrict__ y12 /* [cs][T][128] */, int T, int t0, int nt, int ncs, float* __restrict__ frec /* [cs][RT][FR_WORDS], frame t = row r0 + t */, int RT, int r0)
+ERP_FN(lc3_enc_pitch_kernel)(const lc3d_plan* __restrict__ P, const lc3d_chan* __restrict__ chans, float* __restrict__ state, int state_words, int memcap,
+                     const float* __restrict__ y12 /* [cs][T][128] */, int T, int t0, int nt, int ncs, float* __restrict__ frec /* [cs][RT][FR_WORDS], frame t = row r0 + t */, int RT, int r0 LC3_ERP_OPT)
 {
 #ifdef PITCH_PRIO
     __builtin_amdgcn_s_setprio(PITCH_PRIO);
@@ -45,6 +45,10 @@ lc3_enc_pitch_kernel(const lc3d_plan* __restrict__ P, const lc3d_chan* __restric
     __shared__ PitchLds L;
     const int lane = threadIdx.x, cs = blockIdx.x;
     if (cs >= ncs) return;
+#ifdef LC3_ENC_RPIPE                /* ragged: the stream's frames of this launch that are present; none - the stream's histories stay what they are */
+    nt = imin(nt, cnt[cs / P->channels] - t0);
+    if (nt <= 0) return;
+#endif
     if (lane < LC3D_PLAN_HEAD_WORDS) L.pc[lane] = ((const int*)P)[lane];
     if (lane < 14) L.cc[lane] = ((const int*)&chans[cs])[lane];
     const lc3d_chan* __restrict__ C = &chans[cs];

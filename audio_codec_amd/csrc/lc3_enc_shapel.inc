@@ -62,9 +62,9 @@ __device__ __attribute__((noinline)) void shl_lpc_weight(const float* a_in, cons
 #define SHL_ATTR __attribute__((amdgpu_waves_per_eu(SHL_WAVES, SHL_WAVES)))
 #endif
 #ifdef LC3_ENC_VBW
-#define SHL_KERNEL_NAME lc3_enc_shape_lane_kernel_vbw   /* per-frame bandwidths (lc3_kernels.hip, -DLC3_ENC_VBW): only this kernel of the file */
+#define SHL_KERNEL_NAME ERP_FN(lc3_enc_shape_lane_kernel_vbw)   /* per-frame bandwidths (lc3_kernels.hip, -DLC3_ENC_VBW): only this kernel of the file */
 #else
-#define SHL_KERNEL_NAME lc3_enc_shape_lane_kernel
+#define SHL_KERNEL_NAME ERP_FN(lc3_enc_shape_lane_kernel)
 #endif
 extern "C" __global__ void __launch_bounds__(WAVE) SHL_ATTR
 SHL_KERNEL_NAME(const lc3d_plan* __restrict__ P, const lc3d_chan* __restrict__ chans, int RT /* rows per channel-stream */, int r0 /* first row of this launch */, int nt, int ncs,
@@ -72,10 +72,11 @@ SHL_KERNEL_NAME(const lc3d_plan* __restrict__ P, const lc3d_chan* __restrict__ c
 #ifdef LC3_ENC_VBW
                           , const uint16_t* __restrict__ bwf /* [stream][RT] bandwidth in force for each stream-frame, Hz */
 #endif
-                          )
+                          LC3_ERP_OPT)
 {
     __shared__ ShlLds L;
     const int lane = threadIdx.x;
+    ERP_LANE_FRAME(r0, nt)
     if (lane < LC3D_PLAN_HEAD_WORDS) L.pc[lane] = ((const int*)P)[lane];
     for (int i = lane; i < LC3D_MAX_N; i += WAVE) ((uint8_t*)L.bob)[i] = P->band_of_bin[i];
     for (int i = lane; i < 128 * 3; i += WAVE) L.l10[i] = lc3m_log10_tab[i];
@@ -85,9 +86,11 @@ SHL_KERNEL_NAME(const lc3d_plan* __restrict__ P, const lc3d_chan* __restrict__ c
 #define m_log10f(x_) lc3m_log10f((x_), L.l10)
 #define m_pow2f(x_) lc3m_exp2f((x_), L.ex2)
 #endif
+#ifndef LC3_ENC_RPIPE
     const long long cf = (long long)blockIdx.x * WAVE + lane;
     const bool valid = cf < (long long)ncs * nt;
     const int cs = valid ? (int)(cf / nt) : 0, t = valid ? r0 + (int)(cf % nt) : r0;
+#endif
     float* xr = LC3D_ROW_BASE(rows, cs, t, RT, srow);
 #define XP(k_) (&xr[LC3D_ROW_OFF((k_), RT)])
     float* rec = frec + ((size_t)cs * RT + t) * FR_WORDS;
@@ -535,19 +538,22 @@ struct __attribute__((aligned(16))) ScfLds {
 #define SCF_WAVES 3
 #endif
 extern "C" __global__ void __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(SCF_WAVES, SCF_WAVES)))
-lc3_enc_scf_lane_kernel(const lc3d_plan* __restrict__ P, int RT, int r0, int nt, int ncs, const float* __restrict__ rows /* [cs][RT][srow] */, int srow, float* __restrict__ frec,
-                        int with_vq /* the SNS quantiser of the frame behind its scale factors (no stream of the batch has attack handling: nothing sits between the two) */)
+ERP_FN(lc3_enc_scf_lane_kernel)(const lc3d_plan* __restrict__ P, int RT, int r0, int nt, int ncs, const float* __restrict__ rows /* [cs][RT][srow] */, int srow, float* __restrict__ frec,
+                        int with_vq /* the SNS quantiser of the frame behind its scale factors (no stream of the batch has attack handling: nothing sits between the two) */ LC3_ERP_OPT)
 {
     __shared__ ScfLds L;
     const int lane = threadIdx.x;
+    ERP_LANE_FRAME(r0, nt)
     if (lane < LC3D_PLAN_HEAD_WORDS) L.pc[lane] = ((const int*)P)[lane];
     LSYNC();
     const int nb0 = PI(nbands), ylen = PI(ylen);
     for (int i = lane; i < 68; i += WAVE) L.be[i] = i <= nb0 ? (int)lc3t_band_pool[PI(band_off) + i] : 0x7fffffff;
     LSYNC();
+#ifndef LC3_ENC_RPIPE
     const long long cf = (long long)blockIdx.x * WAVE + lane;
     const bool valid = cf < (long long)ncs * nt;
     const int cs = valid ? (int)(cf / nt) : 0, t = valid ? r0 + (int)(cf % nt) : r0;
+#endif
     const float* xr = LC3D_ROW_BASE(rows, cs, t, RT, srow);
 #define XP(k_) (&xr[LC3D_ROW_OFF((k_), RT)])
     float* rec = frec + ((size_t)cs * RT + t) * FR_WORDS;

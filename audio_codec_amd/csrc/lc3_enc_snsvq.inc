@@ -224,10 +224,13 @@ __device__ __forceinline__ void snsvq_frame(const lc3d_plan* __restrict__ P, con
 }
 
 extern "C" __global__ void __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(VQ_WAVES, VQ_WAVES)))
-lc3_enc_snsvq_kernel(const lc3d_plan* __restrict__ P, float* __restrict__ rec /* [cs][RT][FR_WORDS], frame t = row r0 + t */, int RT, int r0, int tb, int nt, int ncs, int with_attack)
+ERP_FN(lc3_enc_snsvq_kernel)(const lc3d_plan* __restrict__ P, float* __restrict__ rec /* [cs][RT][FR_WORDS], frame t = row r0 + t */, int RT, int r0, int tb, int nt, int ncs, int with_attack LC3_ERP_OPT)
 {
     const long long cf = (long long)blockIdx.x * WAVE + threadIdx.x;          /* frames tb ... tb + nt - 1 of every channel-stream */
     if (cf >= (long long)ncs * nt) return;
+#ifdef LC3_ENC_RPIPE                /* ragged: a lane whose frame is absent has nothing to do (every lane is on its own here) */
+    if (tb + (int)(cf % nt) >= cnt[(int)(cf / nt) / P->channels]) return;
+#endif
     float* r = rec + ((cf / nt) * RT + r0 + tb + cf % nt) * FR_WORDS;
     float env[16];
 #pragma unroll

@@ -121,6 +121,31 @@ __global__ void lc3_enc_snsvq_kernel(const lc3d_plan* __restrict__ P, float* __r
 #define LC3_TAILW_ARGS const lc3d_plan* __restrict__ P, const lc3d_chan* __restrict__ chans, int T, int nt, int fpw, int ncs, const float* __restrict__ rows, int srow, \
     const float* __restrict__ frec, uint8_t* __restrict__ out, int out_stride, uint8_t* __restrict__ status, int min_bytes
 __global__ void lc3_enc_tailw_kernel(LC3_TAILW_ARGS), lc3_enc_tailw_kernel_big(LC3_TAILW_ARGS);
+/* the ragged forms of the pipelined path (per-stream frame counts, lc3plus_enc_batch_set_frame_counts; standard layout), in objects of their own: every step's twin
+ * with LC3_RAGGED_ARGS behind the twin's parameters.  The writers are the _pk forms (a ragged call always has a table of offsets); the typed resamplers, pitch2, the
+ * wave-per-frame shape kernel, the split and frame-per-wave writers and the large layout have none. */
+__global__ void lc3_enc_attack_kernel_rag(const lc3d_plan* __restrict__ P, const lc3d_chan* __restrict__ chans, float* __restrict__ state, int state_words, int scal_off,
+    float* __restrict__ rec, int RT, int r0, int tb, int nt, int ncs LC3_RAGGED_ARGS);
+__global__ void lc3_enc_front4_kernel_rag(LC3_FRONT4_ARGS LC3_RAGGED_ARGS), lc3_enc_front4_kernel_fmt_rag(LC3_FRONT4_ARGS LC3_RAGGED_ARGS),
+    lc3_enc_front4_kernel_wire_rag(LC3_FRONT4_ARGS LC3_RAGGED_ARGS), lc3_enc_front4_kernel_plc_rag(LC3_FRONT4_ARGS LC3_PLACED_ARGS LC3_RAGGED_ARGS);
+__global__ void lc3_enc_front_kernel_rag(LC3_FRONT_ARGS LC3_RAGGED_ARGS), lc3_enc_front_kernel_fmt_rag(LC3_FRONT_ARGS LC3_RAGGED_ARGS),
+    lc3_enc_front_kernel_wire_rag(LC3_FRONT_ARGS LC3_RAGGED_ARGS), lc3_enc_front_kernel_plc_rag(LC3_FRONT_ARGS LC3_PLACED_ARGS LC3_RAGGED_ARGS);
+__global__ void lc3_enc_frontm_kernel_rag(LC3_FRONTM_ARGS LC3_RAGGED_ARGS), lc3_enc_frontm_kernel_fmt_rag(LC3_FRONTM_ARGS LC3_RAGGED_ARGS),
+    lc3_enc_frontm_kernel_wire_rag(LC3_FRONTM_ARGS LC3_RAGGED_ARGS), lc3_enc_frontm_kernel_plc_rag(LC3_FRONTM_ARGS LC3_PLACED_ARGS LC3_RAGGED_ARGS);
+__global__ void lc3_enc_hp50_kernel_rag(const lc3d_plan* __restrict__ P, float* __restrict__ state, int state_words, int scal_off, int T, int tb, int nt, int ncs,
+    float* __restrict__ d12 LC3_RAGGED_ARGS);
+__global__ void lc3_enc_pack_kernel_pk_rag(LC3_PACK_PK_ARGS LC3_RAGGED_ARGS), lc3_enc_pack_kernel_w5_pk_rag(LC3_PACK_PK_ARGS LC3_RAGGED_ARGS);
+__global__ void lc3_enc_pitch_kernel_rag(LC3_PITCH_ARGS LC3_RAGGED_ARGS);
+__global__ void lc3_enc_rate_kernel_rag(LC3_RATE_ARGS LC3_RAGGED_ARGS);
+__global__ void lc3_enc_resample_fmt_kernel_rag(LC3_RESAMPLE_ARGS LC3_RAGGED_ARGS), lc3_enc_resample_kernel_rag(LC3_RESAMPLE_ARGS LC3_RAGGED_ARGS),
+    lc3_enc_resample_wire_kernel_rag(LC3_RESAMPLE_ARGS LC3_RAGGED_ARGS), lc3_enc_resample_plc_kernel_rag(LC3_RESAMPLE_ARGS LC3_PLACED_ARGS LC3_RAGGED_ARGS);
+__global__ void lc3_enc_scf_lane_kernel_rag(const lc3d_plan* __restrict__ P, int RT, int r0, int nt, int ncs, const float* __restrict__ rows, int srow,
+    float* __restrict__ frec, int with_vq LC3_RAGGED_ARGS);
+__global__ void lc3_enc_shape_lane_kernel_rag(const lc3d_plan* __restrict__ P, const lc3d_chan* __restrict__ chans, int RT, int r0, int nt, int ncs, float* __restrict__ rows,
+    int srow, float* __restrict__ frec LC3_RAGGED_ARGS);
+__global__ void lc3_enc_shape_lane_kernel_vbw_rag(const lc3d_plan* __restrict__ P, const lc3d_chan* __restrict__ chans, int RT, int r0, int nt, int ncs,
+    float* __restrict__ rows, int srow, float* __restrict__ frec, const uint16_t* __restrict__ bwf LC3_RAGGED_ARGS);
+__global__ void lc3_enc_snsvq_kernel_rag(const lc3d_plan* __restrict__ P, float* __restrict__ rec, int RT, int r0, int tb, int nt, int ncs, int with_attack LC3_RAGGED_ARGS);
 /* ---- the decoder (lc3_dec_*.inc) ---- */
 __global__ void lc3_dec_imdct4_kernel(const lc3d_plan* __restrict__ P, const float* __restrict__ state, const int* __restrict__ rec, const float* __restrict__ ws, int T,
     int ncs, float* __restrict__ ov);

@@ -42,6 +42,8 @@
  * (lc3_enc_wave.inc); three kinds hold more: */
 #ifdef LC3_DEC_RAGGED
 #define LC3_TU_DEC_RAGGED 1     /* the four _rag objects (with -DLC3_BIG and / or the _plc switches): the decoder's ragged kernels and nothing else, no one-wave kernel either */
+#elif defined(LC3_ENC_RPIPE)
+#define LC3_TU_ENC_RPIPE 1      /* the four _epipe objects (plain, _vbw, and the PCM forms): the ragged forms of the pipelined path's kernels and nothing else, no one-wave kernel either */
 #elif defined(LC3_ENC_RAGGED_PLAN)
 #define LC3_TU_ENC_RAGGED_PLAN 1 /* the _eplan object: the plan, tail and absent-flag kernels of the encoder's ragged calls (lc3_enc_ragged.inc) and nothing else */
 #elif !defined(LC3_ENC_VAR) && !defined(LC3_ENC_VBW) && !defined(LC3_ENC_PACKED) && !defined(LC3_PCM_FMT)
@@ -301,6 +303,19 @@ template <bool QW> __device__ __forceinline__ void pcm_placed_load(const void* _
 #else
 #define LC3_RAGGED_OPT
 #endif
+/* -DLC3_ENC_RPIPE (the _epipe objects): the kernels of the encoder's pipelined path once more with per-stream frame counts (lc3plus_enc_batch_set_frame_counts), each
+ * compiled from the body of its dense twin, named with _rag behind the twin's name and taking LC3_RAGGED_ARGS behind the twin's parameters.  T stays the call's frame
+ * count in every index; c = cnt[cs / channels] is where the stream ends.  A wave that owns a run of frames clamps the run to c and returns before it loads anything
+ * when nothing is left; a chain (one stream per lane or per wave) runs the stream's present frames of the launch; a lane that owns one frame is not `valid` when the
+ * frame is absent. */
+#ifdef LC3_ENC_RPIPE
+#define ERP_FN2(a) a##_rag
+#define ERP_FN(a) ERP_FN2(a)
+#define LC3_ERP_OPT LC3_RAGGED_ARGS
+#else
+#define ERP_FN(a) a
+#define LC3_ERP_OPT
+#endif
 
 /* ------------------------------------------------------------------------------------------------ */
 /* LDS slice of one wave (~12.8 KB -> 12 waves per CU)                                                */
@@ -396,6 +411,31 @@ __device__ __forceinline__ int imax(int a, int b) { return a > b ? a : b; }
 __device__ __forceinline__ int ilog2(unsigned v) { return 31 - __clz((int)v); }
 /* wave-uniform value -> scalar register (lets the compiler use SALU + scalar branches for serial code) */
 __device__ __forceinline__ int uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
+#ifdef LC3_ENC_RPIPE
+/* The one-frame-per-lane kernels of a ragged call.  Their dense twins let a lane without a frame shadow frame (0, r0), which a dense call always has; in a ragged
+ * call no kernel may have written that frame's row and record, and no lane may run the reference's data-dependent loops or index a table with such words.  So a
+ * lane that is not valid takes (cs, t) of the wave's first valid lane - a present frame, whose words this call wrote - and stores nothing, as in the twin.
+ * Returns false where the wave has no present frame at all: it is done (such a wave reaches no barrier it shares with another). */
+__device__ __forceinline__ bool erp_shadow(bool valid, int& cs, int& t)
+{
+    const unsigned long long m = __ballot(valid);
+    if (!m) return false;
+    const int src = uni(__ffsll((long long)m) - 1);
+    const int cs0 = __builtin_amdgcn_readlane(cs, src), t0 = __builtin_amdgcn_readlane(t, src);
+    if (!valid) { cs = cs0; t = t0; }
+    return true;
+}
+/* at the top of such a kernel, before it loads its tables: the lane's frame - row r0_ + cf % nt_ of channel-stream cf / nt_, and the frame of that number: a ragged
+ * call's rows are its frames - or the shadowed one */
+#define ERP_LANE_FRAME(r0_, nt_) \
+    const long long cf = (long long)blockIdx.x * WAVE + lane; \
+    bool valid = cf < (long long)ncs * (nt_); \
+    int cs = valid ? (int)(cf / (nt_)) : 0, t = valid ? (r0_) + (int)(cf % (nt_)) : (r0_); \
+    valid = valid && t < cnt[cs / P->channels]; \
+    if (!erp_shadow(valid, cs, t)) return;
+#else
+#define ERP_LANE_FRAME(r0_, nt_)
+#endif
 
 /* floor(log2f((float)v)) as glibc evaluates it: log2f rounds to an integer for the few v just below 2^b
  * (SURVEY 9): 2^21-1, 2^22-{1,2}, 2^23-{1..5}, 2^24-{1..11}. */
@@ -2907,6 +2947,28 @@ template <class LdsT> STAGE void st_bitstream(const lc3d_plan* __restrict__ P, c
 #endif
 #elif defined(LC3_TU_ENC_RAGGED_PLAN)
 #include "lc3_enc_ragged.inc"     /* lc3_enc_plan_rates_kernel_rag, lc3_enc_rates_tail_kernel_rag, lc3_enc_absent_kernel */
+#elif defined(LC3_TU_ENC_RPIPE)
+/* per-stream frame counts on the pipelined path, standard layout: in the plain object every step's _rag form but the PCM forms' and the shape kernel's with
+ * bandwidths; that one alone in the _vbw object; the resampler and the three fronts of a PCM form in that form's object */
+#if defined(LC3_BIG) || defined(LC3_ENC_VAR) || defined(LC3_ENC_PACKED)
+#error "the ragged pipeline kernels: standard layout, no per-frame sizes (the writers always take a table of offsets)"
+#endif
+#if defined(LC3_ENC_VBW)
+#include "lc3_enc_shapel.inc"      /* lc3_enc_shape_lane_kernel_vbw_rag */
+#else
+#define FRONT_PCM_FMT ENC_PCM_FMT
+#include "lc3_enc_front.inc"       /* lc3_enc_front_kernel_rag (and lc3_enc_attack_kernel_rag), or the PCM form's front */
+#include "lc3_enc_front4.inc"
+#include "lc3_enc_frontm.inc"
+#if !ENC_PCM_FMT
+#include "lc3_enc_seq.inc"         /* lc3_enc_pitch_kernel_rag */
+#include "lc3_enc_rate.inc"        /* lc3_enc_rate_kernel_rag */
+#include "lc3_enc_pack.inc"        /* lc3_enc_pack_kernel_pk_rag, lc3_enc_pack_kernel_w5_pk_rag */
+#include "lc3_enc_snsvq.inc"       /* lc3_enc_snsvq_kernel_rag */
+#include "lc3_enc_shapel.inc"      /* lc3_enc_shape_lane_kernel_rag, lc3_enc_scf_lane_kernel_rag */
+#endif
+#include "lc3_enc_pre.inc"         /* lc3_enc_resample_kernel_rag and lc3_enc_hp50_kernel_rag, or the PCM form's resampler */
+#endif
 #else
 #include "lc3_enc_wave.inc"       /* KERNEL_FN, or KERNEL_FN with _fmt */
 #endif

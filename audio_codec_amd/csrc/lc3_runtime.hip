@@ -25,7 +25,7 @@
  * that drive two batches never race on them, and a context's behaviour does not change under it. */
 struct lc3hip_opts {
     int fused, no_split, streams5, run_frames, runs, ahead_max, rate_stream /* -1 rule, 0, 1 */, pre_runs, pitch2, scf_wave, front4, shape_fpw, shape_on_s, shape_wave,
-        pack_wpg, pack_stream /* -1 off (default), 0, 1 */, resample48, resample96, dec_imdct4, check_ready, tailw_bytes, dec_parse_pad_kb, pack_pad_kb, pack_split, pack_w5, fuse_vq, stream_order, stream_skip, rate_on, dec_plc_stream, shape_on_pitch, side_prio;
+        pack_wpg, pack_stream /* -1 off (default), 0, 1 */, resample48, resample96, dec_imdct4, check_ready, tailw_bytes, dec_parse_pad_kb, pack_pad_kb, pack_split, pack_w5, fuse_vq, stream_order, stream_skip, rate_on, dec_plc_stream, shape_on_pitch, side_prio, ragged_pipe;
 };
 static int env_int(const char* name, int lo, int hi, int dflt) { const char* e = getenv(name); if (!e || !*e) return dflt; const int v = atoi(e); return v >= lo && v <= hi ? v : dflt; }
 static void read_opts(lc3hip_opts* o)
@@ -63,6 +63,7 @@ static void read_opts(lc3hip_opts* o)
     o->dec_plc_stream = env_int("LC3PLUS_DEC_PLC_STREAM", 0, 1, 1);        /* 0 = the decoder's concealment bookkeeping on the caller's stream (round 3) */
     o->shape_on_pitch = env_int("LC3PLUS_ENC_SHAPE_ON_PITCH", 0, 1, -1);  /* the shape kernel on the pitch stream; -1: the rule in enc_run (long calls of 2.5 ms high-resolution frames only) */
     o->side_prio = env_int("LC3PLUS_ENC_SIDE_PRIO", 0, 2, 0);             /* diagnostic: 1 = the side streams at the lowest HIP stream priority, 2 = at the highest */
+    o->ragged_pipe = env_int("LC3PLUS_ENC_RAGGED_PIPE", 0, 1, 1);         /* 0 = every ragged encode call on the one-wave kernels, whatever its length (enc_launch: the A/B handle and a deployment's fallback) */
     o->check_ready = env_int("LC3PLUS_CHECK_READY", 0, 1, 0);        /* debug aid for lc3plus_enc_batch_set_input_ready: refuse a call made while foreign work is pending on the caller's stream */
     o->dec_imdct4 = env_int("LC3PLUS_DEC_IMDCT4", 0, 1, 1);          /* 0 = the one-frame-at-a-time IMDCT for N = 480 too */
 }
@@ -89,7 +90,8 @@ struct lc3hip_ctx {
     float* d_spec[LC3D_SETS]; size_t spec_cap[LC3D_SETS]; float* d_frec[LC3D_SETS]; size_t frec_cap[LC3D_SETS]; hipEvent_t ev_done[LC3D_SETS]; float* d_xnext[LC3D_SETS + 1]; int xn_par, row_par; uint8_t* h_attack; int any_attack;
     const long long* plo; long long plcap;         /* lc3hip_set_pcm_placement: per-frame PCM offsets in device memory (null: off) and the buffer's length in elements */
     /* lc3hip_set_frame_counts: the caller's per-stream frame counts in device memory (null: off), and the clamped copy [n_streams] that the ragged plan kernel of a
-     * call writes and its other kernels read.  One buffer: ragged calls are ordered on the caller's stream, none overlaps another.  rag: the call being queued is one. */
+     * call writes and its other kernels read.  One buffer: ragged calls are ordered on the caller's stream, none overlaps another.  rag: the call being queued is one - 1 with
+     * per-frame bitrates, 2 without (its sizes are the carried ones: every frame of a stream has the bytes of the stream's configuration). */
     const int32_t* counts; int32_t* d_cnt; int rag;
     int input_ready, ahead_ok, ahead_T, ahead_R;   /* lc3hip_set_input_ready: side kernels of a call beside the previous call's tail */   /* split path (lc3_enc_front.inc) */      /* per channel-frame status bits of the last call (LC3D_ENC_ST_*) */
     /* host-pointer pipeline (lc3hip_encode_host): two chunk slots, each with device staging and (for pageable callers) pinned staging */
@@ -349,6 +351,7 @@ static int dup_of(char k) { static const char* e = nullptr; static bool rd = fal
  * by a call of the same lambda with those values appended.  The declaration of lc3_kernel_decls.h checks count and types of what arrives. */
 /* the twin of `name` by sample type: the reference's three depths, the wire types, the other formats */
 #define BY_FMT(q, name) ((q)->fmt_plain ? name : (q)->fmt_wire ? name##_wire : name##_fmt)
+#define BY_FMT_RAG(q, name) ((q)->fmt_plain ? name##_rag : (q)->fmt_wire ? name##_wire_rag : name##_fmt_rag)      /* the ragged forms of the pipelined path */
 /* PCM for the kernels that declare it as a typed pointer (the specialised resamplers): converts to whichever sample type the chosen kernel takes */
 struct pcm_as { const void* p; template <typename T> operator const T*() const { return (const T*)p; } };
 /* Placed PCM, calls that report per frame in device memory: behind the call's own kernels on s - every one of them that writes `out` (the encoder's flags, the
@@ -361,7 +364,8 @@ static int placed_mark(const long long* plo, long long plcap, int channels, int 
     return 0;
 }
 /* the 12.8 kHz polyphase FIR of frames hb ... hb + hn - 1 of every channel-stream on stream st: four outputs per lane where the shape allows */
-static void launch_resample(lc3hip_ctx* c, hipStream_t st, const void* dpcm, int bitdepth, int n_frames, int hb, int hn, int mc, float* dy12, const float* xprev, int xprev_stride)
+static void launch_resample(lc3hip_ctx* c, hipStream_t st, const void* dpcm, int bitdepth, int n_frames, int hb, int hn, int mc, float* dy12, const float* xprev, int xprev_stride,
+                            const int32_t* cnt = nullptr /* a ragged call: always the resampler for every shape, in its _rag form */)
 {
     const unsigned pruns = (unsigned)((hn + PRE_FPW - 1) / PRE_FPW);
     const bool a16 = (((size_t)dpcm) & 15) == 0;
@@ -371,7 +375,11 @@ static void launch_resample(lc3hip_ctx* c, hipStream_t st, const void* dpcm, int
     auto s16 = [&](auto k, unsigned runs) { hipLaunchKernelGGL(k, dim3((unsigned)c->ncs * runs), dim3(WAVE), 0, st, c->d_plan, (const int16_t*)dpcm, c->channels, mc, n_frames, hb, hn, c->ncs, dy12, xprev, xprev_stride); };
     /* ... and float32 or wire samples, which also take the format word */
     auto typed = [&](auto k) { hipLaunchKernelGGL(k, dim3((unsigned)c->ncs * pruns), dim3(WAVE), 0, st, c->d_plan, pcm_as{dpcm}, bitdepth, c->channels, mc, n_frames, hb, hn, c->ncs, dy12, xprev, xprev_stride); };
-    if (c->plo) any(lc3_enc_resample_plc_kernel, c->plo, c->plcap);      /* placed PCM: the resampler for every shape (the specialised ones take typed dense pointers) */
+    if (cnt) {
+        if (c->plo) any(lc3_enc_resample_plc_kernel_rag, c->plo, c->plcap, cnt);
+        else any((bitdepth == 16 || bitdepth == 24 || bitdepth == 32) ? lc3_enc_resample_kernel_rag : lc3d_pcm_type_wire(bitdepth & LC3D_PCM_TYPE_MASK) ? lc3_enc_resample_wire_kernel_rag : lc3_enc_resample_fmt_kernel_rag, cnt);
+    }
+    else if (c->plo) any(lc3_enc_resample_plc_kernel, c->plo, c->plcap);      /* placed PCM: the resampler for every shape (the specialised ones take typed dense pointers) */
     else if (c->rs48 && bitdepth == 16 && a16) s16(lc3_enc_resample48_kernel, pruns);
     else if (c->rs48 && (bitdepth & (LC3D_PCM_TYPE_MASK | LC3D_PCM_INTERLEAVED)) == LC3D_PCM_FLOAT32 && a16) typed(lc3_enc_resample48f_kernel);   /* frames of 480 x 4 bytes: every one 16-byte aligned */
     else if (c->rs48 && lc3d_pcm_type_wire(bitdepth & LC3D_PCM_TYPE_MASK) && !(bitdepth & LC3D_PCM_INTERLEAVED) && (((size_t)dpcm) & 3) == 0) typed(lc3_enc_resample48w_kernel);   /* wire samples that follow each other, frames of 480 elements: every one starts on a dword */
@@ -382,9 +390,10 @@ static void launch_resample(lc3hip_ctx* c, hipStream_t st, const void* dpcm, int
     else any((bitdepth == 16 || bitdepth == 24 || bitdepth == 32) ? lc3_enc_resample_kernel : lc3d_pcm_type_wire(bitdepth & LC3D_PCM_TYPE_MASK) ? lc3_enc_resample_wire_kernel : lc3_enc_resample_fmt_kernel);
 }
 /* behind it the HP50 recurrence of the same frames, one stream per lane */
-static void launch_hp50(lc3hip_ctx* c, hipStream_t st, int n_frames, int hb, int hn, int mc, float* dy12)
+static void launch_hp50(lc3hip_ctx* c, hipStream_t st, int n_frames, int hb, int hn, int mc, float* dy12, const int32_t* cnt = nullptr)
 {
-    hipLaunchKernelGGL(lc3_enc_hp50_kernel, dim3((unsigned)((c->ncs + WAVE - 1) / WAVE)), dim3(WAVE), 0, st, c->d_plan, c->d_state, c->state_words, LC3D_ST_SCAL(mc), n_frames, hb, hn, c->ncs, dy12);
+    auto hp = [&](auto k, auto... ragged) { hipLaunchKernelGGL(k, dim3((unsigned)((c->ncs + WAVE - 1) / WAVE)), dim3(WAVE), 0, st, c->d_plan, c->d_state, c->state_words, LC3D_ST_SCAL(mc), n_frames, hb, hn, c->ncs, dy12, ragged...); };
+    if (cnt) hp(lc3_enc_hp50_kernel_rag, cnt); else hp(lc3_enc_hp50_kernel);
 }
 static int bw_to(lc3hip_ctx* c, hipStream_t st);
 /* what enc_one_wave passes for the optional argument groups of the one-wave kernels (lc3_kernel_decls.h: LC3_OW_OPT orders them) */
@@ -401,7 +410,8 @@ struct enc_call {
     const uint16_t* dfsz;       /* per-frame bitrates: [stream][dT] stream-frame bytes, or null */
     const uint16_t* dbw;        /* per-frame bandwidths: [stream][dT] Hz in force (stage_bw), or null; the path is the one without them */
     bool fmt_plain, fmt_wire, placed;       /* which twin by sample type */
-    const int32_t* cnt;         /* a ragged call: [stream] clamped frame counts (the one-wave path with the _rag twins, no pre-kernels), or null */
+    const int32_t* cnt;         /* a ragged call: [stream] clamped frame counts, or null */
+    bool rag_pipe;              /* ... on the pipelined path (the _rag form of every step); else the one-wave path with the _rag twins, no pre-kernels (enc_launch decides) */
     int set, mc, dstride; int* ddump; float* dy12; bool split;      /* enc_size_set: the call's set of hand-over buffers, and the path they select */
     bool rate_on_side;                      /* enc_pipelined: the rate chain left the caller's stream */
 };
@@ -420,7 +430,7 @@ static int enc_size_set(lc3hip_ctx* c, enc_call* q, bool in_kernel_writer)
         q->ddump = c->d_dumpv[set];
     }
     /* ahead of it: the 12.8 kHz resampler of all frames at once and its HP50 recurrence one stream per lane (lc3_enc_pre.inc) */
-    if (!q->dtr && !c->fused && !q->cnt) {      /* (a ragged call resamples in its one kernel, as a traced one: the pre-kernels read every frame's PCM) */
+    if (!q->dtr && !c->fused && (!q->cnt || q->rag_pipe)) {      /* (a ragged call on the one-wave path resamples in its one kernel, as a traced one: the dense pre-kernels read every frame's PCM) */
         const size_t need = (size_t)c->ncs * q->n_frames * 128;
         /* two buffers under the input-ready promise: the next call's resampler may run beside this call's pitch kernel */
         for (int i = i0; i < i1; i++) if (grow(&c->d_y12[i], &c->y12_cap[i], need, need * sizeof(float), false)) return 1;
@@ -439,8 +449,13 @@ static int enc_size_set(lc3hip_ctx* c, enc_call* q, bool in_kernel_writer)
          * the input-ready promise (consecutive calls overlap: the side kernels of a call write one set while the bitstream writer of the call
          * before still reads the other), one otherwise */
         const size_t ns = (size_t)c->ncs * q->dT * c->srow, nr = (size_t)c->ncs * q->dT * FR_WORDS;
-        for (int i = i0; i < i1; i++)
+        for (int i = i0; i < i1; i++) {
+            const size_t had = c->frec_cap[i];
             if (grow(&c->d_spec[i], &c->spec_cap[i], ns, ns * sizeof(float), false) || grow(&c->d_frec[i], &c->frec_cap[i], nr, nr * sizeof(float), false)) return 1;
+            /* new records start as zeros, on s in front of the fork (a call that allocates never overlaps its predecessor): a record has padding words that no kernel
+             * writes, and lc3hip_last_records reports the same words for the same call on two batches */
+            if (c->frec_cap[i] != had) HIPCHK(hipMemsetAsync(c->d_frec[i], 0, nr * sizeof(float), q->s));
+        }
         for (int i = 0; i < LC3D_SETS + 1; i++) if (grow_once(&c->d_xnext[i], (size_t)c->ncs * q->mc * sizeof(float))) return 1;
     }
     return 0;
@@ -521,16 +536,18 @@ static int enc_run(lc3hip_ctx* c, const enc_call* q, enc_runs* r, int k, int tb,
     if (tb >= r->hb) {
         const int prn = c->opt.pre_runs;
         const int hn0 = r->hk == 0 ? Tr : prn * Tr, hn = n_frames - r->hb < hn0 ? n_frames - r->hb : hn0;
-        DUPL('r') launch_resample(c, c->s_pre, q->dpcm, q->bitdepth, n_frames, r->hb, hn, mc, q->dy12, r->xprev, r->xprev_stride);
-        DUPL('h') launch_hp50(c, c->s_pre, n_frames, r->hb, hn, mc, q->dy12);
+        DUPL('r') launch_resample(c, c->s_pre, q->dpcm, q->bitdepth, n_frames, r->hb, hn, mc, q->dy12, r->xprev, r->xprev_stride, q->cnt);
+        DUPL('h') launch_hp50(c, c->s_pre, n_frames, r->hb, hn, mc, q->dy12, q->cnt);
         HIPCHK(hipGetLastError());
         r->hb += hn; r->hk++;
         if (r->five) { HIPCHK(hipEventRecord(c->ev_h[k], c->s_pre)); HIPCHK(hipStreamWaitEvent(c->s_pit, c->ev_h[k], 0)); }
     }
     /* OLPA + LTPF: two streams per wave where the 12.8 kHz frame length has such a kernel (LC3PLUS_ENC_PITCH2=0: one stream per wave) */
-    const bool p2 = c->opt.pitch2 && (c->len12 == 128 || c->len12 == 64 || c->len12 == 32);
+    /* (a ragged call: one stream per wave - the two streams of a pitch2 wave share barriers and have counts of their own) */
+    const bool p2 = c->opt.pitch2 && (c->len12 == 128 || c->len12 == 64 || c->len12 == 32) && !q->cnt;
     auto pk = !p2 ? lc3_enc_pitch_kernel : c->len12 == 128 ? lc3_enc_pitch2_kernel : c->len12 == 64 ? lc3_enc_pitch2_kernel_l64 : lc3_enc_pitch2_kernel_l32;
-    DUPL('p') hipLaunchKernelGGL(pk, dim3((unsigned)(p2 ? (c->ncs + 1) / 2 : c->ncs)), dim3(WAVE), 0, c->s_pit, c->d_plan, c->d_chans, c->d_state, c->state_words, mc, q->dy12, n_frames, tb, nt, c->ncs, dfrec, dT, dt0);
+    auto pitch = [&](auto kern, auto... ragged) { hipLaunchKernelGGL(kern, dim3((unsigned)(p2 ? (c->ncs + 1) / 2 : c->ncs)), dim3(WAVE), 0, c->s_pit, c->d_plan, c->d_chans, c->d_state, c->state_words, mc, q->dy12, n_frames, tb, nt, c->ncs, dfrec, dT, dt0, ragged...); };
+    if (q->cnt) pitch(lc3_enc_pitch_kernel_rag, q->cnt); else DUPL('p') pitch(pk);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(c->ev_p[k], c->s_pit));
     const int scf_wave = c->opt.scf_wave;
@@ -541,10 +558,13 @@ static int enc_run(lc3hip_ctx* c, const enc_call* q, enc_runs* r, int k, int tb,
         auto frontm = [&](auto kern, auto... placed) { hipLaunchKernelGGL(kern, dim3((unsigned)c->ncs * (unsigned)((nt + c->fm_frames - 1) / c->fm_frames)), dim3(WAVE), 0, c->s_fr, c->d_plan, c->d_chans, c->d_state, q->dpcm, q->bitdepth, n_frames, tb, nt, c->fm_frames, c->ncs, dspec, c->srow, dT, dt0, dfrec, r->xn_w, r->xprev, r->xprev_stride, placed...); };
         auto front = [&](auto kern, auto... placed) { hipLaunchKernelGGL(kern, dim3((unsigned)c->ncs * (unsigned)((nt + fpw - 1) / fpw)), dim3(WAVE), 0, c->s_fr, c->d_plan, c->d_chans, c->d_state, q->dpcm, q->bitdepth, n_frames, tb, nt, fpw, c->ncs, dspec, c->srow, dT, dt0, dfrec, r->xn_w, r->xprev, r->xprev_stride, scf_wave, placed...); };
         if (f4 && !c->big && !scf_wave && c->N == 480 && c->la == 180 && (c->ylen & 15) == 0) {
-            if (q->placed) front4(lc3_enc_front4_kernel_plc, c->plo, c->plcap); else DUPL('f') front4(BY_FMT(q, lc3_enc_front4_kernel));
+            if (q->cnt) { if (q->placed) front4(lc3_enc_front4_kernel_plc_rag, c->plo, c->plcap, q->cnt); else front4(BY_FMT_RAG(q, lc3_enc_front4_kernel), q->cnt); }
+            else if (q->placed) front4(lc3_enc_front4_kernel_plc, c->plo, c->plcap); else DUPL('f') front4(BY_FMT(q, lc3_enc_front4_kernel));
         } else if (f4 && c->fm_frames && !scf_wave) {
-            if (q->placed) frontm(lc3_enc_frontm_kernel_plc, c->plo, c->plcap); else frontm(BY_FMT(q, lc3_enc_frontm_kernel));
+            if (q->cnt) { if (q->placed) frontm(lc3_enc_frontm_kernel_plc_rag, c->plo, c->plcap, q->cnt); else frontm(BY_FMT_RAG(q, lc3_enc_frontm_kernel), q->cnt); }
+            else if (q->placed) frontm(lc3_enc_frontm_kernel_plc, c->plo, c->plcap); else frontm(BY_FMT(q, lc3_enc_frontm_kernel));
         }
+        else if (q->cnt) { if (q->placed) front(lc3_enc_front_kernel_plc_rag, c->plo, c->plcap, q->cnt); else front(BY_FMT_RAG(q, lc3_enc_front_kernel), q->cnt); }      /* (standard layout: enc_launch) */
         else if (q->placed) front(c->big ? lc3_enc_front_kernel_big_plc : lc3_enc_front_kernel_plc, c->plo, c->plcap);
         else if (c->big) front(BY_FMT(q, lc3_enc_front_kernel_big));
         else DUPL('f') front(BY_FMT(q, lc3_enc_front_kernel));
@@ -553,10 +573,12 @@ static int enc_run(lc3hip_ctx* c, const enc_call* q, enc_runs* r, int k, int tb,
     if (r->five) HIPCHK(hipStreamWaitEvent(c->s_ln, c->ev_m[k], 0));
     const int fuse_vq = !scf_wave && !c->any_attack && c->opt.fuse_vq;
     const unsigned lanes = (unsigned)(((long long)c->ncs * nt + WAVE - 1) / WAVE);      /* waves of a kernel that takes one frame per lane */
-    if (!scf_wave) DUPL('e') hipLaunchKernelGGL(lc3_enc_scf_lane_kernel, dim3(lanes), dim3(WAVE), 0, c->s_ln, c->d_plan, dT, dt0 + tb, nt, c->ncs, dspec, c->srow, dfrec, fuse_vq);
-    if (c->any_attack)
-        hipLaunchKernelGGL(lc3_enc_attack_kernel, dim3((unsigned)((c->ncs + WAVE - 1) / WAVE)), dim3(WAVE), 0, c->s_ln, c->d_plan, c->d_chans, c->d_state, c->state_words, LC3D_ST_SCAL(mc), dfrec, dT, dt0, tb, nt, c->ncs);
-    if (!fuse_vq) DUPL('v') hipLaunchKernelGGL(lc3_enc_snsvq_kernel, dim3(lanes), dim3(WAVE), 0, c->s_ln, c->d_plan, dfrec, dT, dt0, tb, nt, c->ncs, c->any_attack);
+    auto scf = [&](auto kern, auto... ragged) { hipLaunchKernelGGL(kern, dim3(lanes), dim3(WAVE), 0, c->s_ln, c->d_plan, dT, dt0 + tb, nt, c->ncs, dspec, c->srow, dfrec, fuse_vq, ragged...); };
+    auto attack = [&](auto kern, auto... ragged) { hipLaunchKernelGGL(kern, dim3((unsigned)((c->ncs + WAVE - 1) / WAVE)), dim3(WAVE), 0, c->s_ln, c->d_plan, c->d_chans, c->d_state, c->state_words, LC3D_ST_SCAL(mc), dfrec, dT, dt0, tb, nt, c->ncs, ragged...); };
+    auto snsvq = [&](auto kern, auto... ragged) { hipLaunchKernelGGL(kern, dim3(lanes), dim3(WAVE), 0, c->s_ln, c->d_plan, dfrec, dT, dt0, tb, nt, c->ncs, c->any_attack, ragged...); };
+    if (!scf_wave) { if (q->cnt) scf(lc3_enc_scf_lane_kernel_rag, q->cnt); else DUPL('e') scf(lc3_enc_scf_lane_kernel); }
+    if (c->any_attack) { if (q->cnt) attack(lc3_enc_attack_kernel_rag, q->cnt); else attack(lc3_enc_attack_kernel); }
+    if (!fuse_vq) { if (q->cnt) snsvq(lc3_enc_snsvq_kernel_rag, q->cnt); else DUPL('v') snsvq(lc3_enc_snsvq_kernel); }
     hipStream_t rs;
     {   /* shaping, TNS and the stateless half of the gain estimate: frame-parallel, behind the quantiser (LC3PLUS_ENC_SHAPE_ON_S=1, diagnostic: on the
          * launch stream in front of the rate kernel instead) */
@@ -576,7 +598,8 @@ static int enc_run(lc3hip_ctx* c, const enc_call* q, enc_runs* r, int k, int tb,
         /* one frame per lane, or (LC3PLUS_ENC_SHAPE_WAVE=1) spw frames per wave; with per-frame bandwidths the _vbw twin of either */
         auto lane = [&](auto kern, auto... bw) { hipLaunchKernelGGL(kern, dim3(lanes), dim3(WAVE), 0, ss, c->d_plan, c->d_chans, dT, dt0 + tb, nt, c->ncs, dspec, c->srow, dfrec, bw...); };
         auto wave = [&](auto kern, auto... bw) { hipLaunchKernelGGL(kern, dim3((unsigned)c->ncs * sruns), dim3(WAVE), 0, ss, c->d_plan, c->d_chans, dT, dt0 + tb, nt, spw, c->ncs, dspec, c->srow, dfrec, bw...); };
-        if (!swave) { if (q->dbw) lane(lc3_enc_shape_lane_kernel_vbw, q->dbw); else DUPL('a') lane(lc3_enc_shape_lane_kernel); }
+        if (q->cnt) { if (q->dbw) lane(lc3_enc_shape_lane_kernel_vbw_rag, q->dbw, q->cnt); else lane(lc3_enc_shape_lane_kernel_rag, q->cnt); }      /* (never with LC3PLUS_ENC_SHAPE_WAVE: enc_launch) */
+        else if (!swave) { if (q->dbw) lane(lc3_enc_shape_lane_kernel_vbw, q->dbw); else DUPL('a') lane(lc3_enc_shape_lane_kernel); }
         else if (q->dbw) wave(lc3_enc_shape_kernel_vbw, q->dbw);
         else if (c->big) wave(lc3_enc_shape_kernel_big);
         else DUPL('a') wave(lc3_enc_shape_kernel);
@@ -586,8 +609,8 @@ static int enc_run(lc3hip_ctx* c, const enc_call* q, enc_runs* r, int k, int tb,
     HIPCHK(hipStreamWaitEvent(rs, c->ev_p[k], 0));
     if (k == 0 && c->rate_armed) HIPCHK(hipStreamWaitEvent(rs, c->ev_rate, 0));      /* the rate chain is a chain: behind the previous call's, whichever stream that ran on */
     const int last = tb + nt >= n_frames;            /* behind the last frame of this launch the MDCT memory goes into the state */
-    auto rate = [&](auto kern) { hipLaunchKernelGGL(kern, dim3((unsigned)((c->ncs + RATE_WG - 1) / RATE_WG)), dim3(RATE_WG * WAVE), 0, rs, c->d_plan, c->d_chans, c->d_state, dT, dt0 + tb, nt, c->ncs, dspec, c->srow, dfrec, r->xn_w, last); };
-    if (c->big) rate(lc3_enc_rate_kernel_big); else DUPL('s') rate(lc3_enc_rate_kernel);
+    auto rate = [&](auto kern, auto... ragged) { hipLaunchKernelGGL(kern, dim3((unsigned)((c->ncs + RATE_WG - 1) / RATE_WG)), dim3(RATE_WG * WAVE), 0, rs, c->d_plan, c->d_chans, c->d_state, dT, dt0 + tb, nt, c->ncs, dspec, c->srow, dfrec, r->xn_w, last, ragged...); };
+    if (q->cnt) rate(lc3_enc_rate_kernel_rag, q->cnt); else if (c->big) rate(lc3_enc_rate_kernel_big); else DUPL('s') rate(lc3_enc_rate_kernel);
     HIPCHK(hipGetLastError());
     r->rs = rs;
     return 0;
@@ -623,7 +646,7 @@ static int enc_pipelined(lc3hip_ctx* c, enc_call* q)
      * per-frame-bandwidth call overlaps it, and only when that copy changed nothing but the bandwidth words, which its kernels do not read (the other words
      * are rewritten with their own values).  A call that forks from s is behind the copy, and so is everything after it. */
     const bool cfg_ok = c->cfg_fresh == 0 || (c->cfg_fresh == 1 && q->dbw);
-    const bool ahead = c->input_ready && n_frames <= amax && c->ahead_ok && c->ahead_T == n_frames && c->ahead_R == R && c->last_stream == s && dt0 == 0 && dT == n_frames && q->pack && cfg_ok;
+    const bool ahead = c->input_ready && n_frames <= amax && c->ahead_ok && c->ahead_T == n_frames && c->ahead_R == R && c->last_stream == s && dt0 == 0 && dT == n_frames && q->pack && cfg_ok && !q->cnt;
     if (!ahead) c->cfg_fresh = 0;
     r.xn_w = c->d_xnext[c->xn_par];                         /* written by this call's front kernel */
     /* one buffer more than calls in flight: the one written now was last read by the call LC3D_SETS back (its resampler and front) and by the
@@ -659,7 +682,8 @@ static int enc_pipelined(lc3hip_ctx* c, enc_call* q)
         if (enc_run(c, q, &r, k, tb, n_frames - tb < Tr ? n_frames - tb : Tr, Tr)) return 1;
     HIPCHK(hipEventRecord(c->ev_rate, r.rs)); c->rate_armed = 1; q->rate_on_side = r.rs != s;
     if (r.rs != s) HIPCHK(hipStreamWaitEvent(s, c->ev_rate, 0));      /* the writer (and whatever the caller queues next) behind the rate chain */
-    c->ahead_ok = (dt0 == 0 && dT == n_frames && q->pack) ? 1 : 0; c->ahead_T = n_frames; c->ahead_R = R;
+    /* a ragged call forks from s and lets nothing overlap it: it fills the hand-over only for the streams that had a frame, so the call behind it reads the MDCT memory from the state */
+    c->ahead_ok = (dt0 == 0 && dT == n_frames && q->pack && !q->cnt) ? 1 : 0; c->ahead_T = n_frames; c->ahead_R = R;
     c->xn_par = (c->xn_par + 1) % (LC3D_SETS + 1);
     return 0;
 }
@@ -706,7 +730,7 @@ static int enc_writer(lc3hip_ctx* c, const enc_call* q)
     if (!big_from || c->min_nbytes < big_from) {
         const dim3 grid((unsigned)((tasks + per_wg - 1) / per_wg)), block(wpg * WAVE);
         const size_t dyn = per_wave * wpg + ((size_t)(c->opt.pack_pad_kb > 0 ? c->opt.pack_pad_kb : 0) << 10);
-        const long long* pt = c->pk.on ? c->pk.tab : nullptr;      /* packed output: the _pk twins write each frame at its offset of the call's table */
+        const long long* pt = c->pk.on || q->cnt ? c->pk.tab : nullptr;      /* packed output: the _pk twins write each frame at its offset of the call's table (a ragged call always has one: the scan's, or the plan kernel's slots) */
         auto writer = [&](auto kern, size_t lds, auto... poff) { hipLaunchKernelGGL(kern, grid, block, lds, ps, c->d_plan, c->d_chans, q->ddump, q->dstride, dT, 0, dT, c->ncs, q->dout, pt ? 0 : q->out_stride, c->d_status, rows_for_pack, c->srow, frec_for_pack, big_from, poff...); };
         if (two) {       /* LC3PLUS_ENC_PACK_SPLIT=1: the writer as two kernels (head, coder) */
             if (pt) { writer(lc3_enc_pack_head_kernel_pk, 0, pt); writer(lc3_enc_pack_code_kernel_pk, dyn, pt); }
@@ -714,7 +738,8 @@ static int enc_writer(lc3hip_ctx* c, const enc_call* q)
         } else {
             /* 96 or 128 registers (lc3_enc_pack.inc, the table at lc3_enc_pack_kernel_w5): five waves per SIMD pay for long calls of small 10 ms frames */
             const bool w5 = c->opt.pack_w5 >= 0 ? c->opt.pack_w5 == 1 : (split && !c->big && !c->hr && c->N == 480 && dT >= 48 && c->max_nbytes <= 100);
-            if (pt) writer(w5 ? lc3_enc_pack_kernel_w5_pk : lc3_enc_pack_kernel_pk, dyn, pt);
+            if (q->cnt) { if (w5) writer(lc3_enc_pack_kernel_w5_pk_rag, dyn, pt, q->cnt); else writer(lc3_enc_pack_kernel_pk_rag, dyn, pt, q->cnt); }
+            else if (pt) writer(w5 ? lc3_enc_pack_kernel_w5_pk : lc3_enc_pack_kernel_pk, dyn, pt);
             else DUPL('k') writer(w5 ? lc3_enc_pack_kernel_w5 : lc3_enc_pack_kernel, dyn);
         }
     }
@@ -741,8 +766,15 @@ static int enc_launch(lc3hip_ctx* c, const void* dpcm, int bitdepth, int n_frame
     q.fmt_plain = bitdepth == 16 || bitdepth == 24 || bitdepth == 32;
     q.fmt_wire = lc3d_pcm_type_wire(bitdepth & LC3D_PCM_TYPE_MASK) != 0;           /* the wire sample types: the _wire twins, so that the _fmt kernels stay what they were */
     q.placed = c->plo != nullptr;                                                  /* placed PCM: the _plc twins, one form for every sample type */
-    q.cnt = c->rag ? c->d_cnt : nullptr;                                           /* ragged (lc3hip_encode_rates_device): sizes always, so the one-wave path whatever n_frames */
+    q.cnt = c->rag ? c->d_cnt : nullptr;                                           /* ragged (lc3hip_encode_rates_device): its plan kernel always writes sizes and a table of offsets */
     if (q.cnt && (!dfsz || dtr || dt0 != 0 || dT != n_frames)) return 1;
+    /* A ragged call takes the pipelined path where the dense call without the input-ready promise does: no per-frame bitrates (with them the dense call runs the
+     * one-wave kernel too; without them the sizes are the configuration's, which is what the pipeline's kernels read), standard layout, more than LC3D_FUSED_MAX_T
+     * frames - with or without the promise, whose lower threshold exists because calls overlap there, and a ragged call does not - and none of the diagnostic kernel
+     * variants, which have no ragged forms.  Every other ragged call: the one-wave _rag kernels.  LC3PLUS_ENC_RAGGED_PIPE=0: all of them. */
+    q.rag_pipe = q.cnt && c->rag == 2 && c->opt.ragged_pipe && !c->big && n_frames > LC3D_FUSED_MAX_T && !c->fused && !c->opt.no_split && !c->opt.shape_wave &&
+                 c->opt.pack_split != 1 && !c->opt.tailw_bytes && !c->opt.scf_wave;
+    if (q.rag_pipe) q.dfsz = dfsz = nullptr;
     if (q.placed && (dt0 != 0 || dT != n_frames || (bitdepth & LC3D_PCM_CHANNEL_MAJOR))) return 1;    /* the offsets are indexed by the call's frames; the host refuses the rest */
     const bool in_kernel_writer = dtr || c->fused || dfsz || dT <= (c->input_ready ? LC3D_FUSED_MAX_T_READY : LC3D_FUSED_MAX_T);
     q.mc = c->big ? LC3D_MEMCAP_BIG : LC3D_MEMCAP_STD;
@@ -1003,11 +1035,12 @@ extern "C" int lc3hip_encode_rates_device(void* ctx, const void* pcm, int bitdep
     for (int i = 0; i < LC3D_SETS; i++) { b[2 * i] = {(void**)&c->d_pfsz[i], fb, false}; b[2 * i + 1] = {(void**)&c->d_pbw[i], fb, false}; }
     if (grow_group(&c->pset_frames, (size_t)n_frames, b, 2 * LC3D_SETS, true)) return 1;
     /* Ragged (lc3hip_set_frame_counts): the call of this function with the _rag kernels.  Its plan kernel always writes sizes - the carried ones where the caller
-     * gave no rates - and an offset table (slotted output: every frame's slot), so the call takes the one-wave path whatever its length, ordered on s: that path
-     * ends every overlap (enc_one_wave), and the call after it forks from s again. */
+     * gave no rates - and an offset table (slotted output: every frame's slot), on s in front of everything else of the call (bw_to below): every other kernel reads
+     * the clamped counts it leaves, and on the pipelined path (enc_launch: long calls without rates in the standard layout) the side streams fork from s behind it.
+     * Either path ends every overlap (enc_one_wave, enc_pipelined), and the call after it forks from s again. */
     const int rag = c->counts != nullptr;
     if (rag && !c->pk.on && pk_tables(c, (size_t)c->n_streams * n_frames)) return 1;
-    c->rag = rag; c->pl.stride = out_stride;
+    c->rag = rag ? (rates_dev ? 1 : 2) : 0; c->pl.stride = out_stride;
     struct rag_off { lc3hip_ctx* c; ~rag_off() { if (c->rag && !c->pk.on) c->pk.tab = nullptr; c->rag = 0; } } rag_end = {c};      /* however the call ends */
     const int k = c->pset;
     c->pl.pending = 1; c->pl.k = k; c->pl.T = n_frames; c->pl.rates = rates_dev; c->pl.bws = bws_dev; c->pl.nb = num_bytes_dev; c->pl.fl = flags_dev; c->pl.rule = *rule;

@@ -317,14 +317,21 @@ LC3_Error lc3plus_enc_batch_set_pcm_placement(lc3plus_batch* batch, const int64_
  * attack-detector reset pending from set_bitrate() included, which takes effect at the stream's first present frame, whenever that comes.  So a sequence of
  * ragged calls gives each stream the bytes, sizes and flags that one dense sequence of its present frames gives, and counts that all equal n_frames give the
  * bytes, sizes, flags and state of the call without counts.  ("State": every word a later frame reads.  get_state() also returns per-frame scalars that the
- * one-wave kernels store and the pipelined kernels leave alone, and unused words in front of the MDCT memory; where the dense call runs pipelined - long calls
- * without per-frame bitrates - those bytes differ, as they do between a short and a long dense call, and the batches carry on alike.)  Only a tail can be
- * absent: a count skips no frame in the middle of a call.
+ * one-wave kernels store and the pipelined kernels leave alone, and unused words in front of the MDCT memory; counts that all equal n_frames give the
+ * get_state() bytes of the dense call wherever both take the same path - which includes long calls without per-frame bitrates, see the last paragraph - and
+ * where they do not, those bytes differ as they do between a short and a long dense call, and the batches carry on alike.)  Only a tail can be absent: a
+ * count skips no frame in the middle of a call.
  * Changed with this function: lc3plus_enc_batch_set_bitrate() no longer drops a one-shot reset that is still pending.  A rate that disables attack handling
  * followed, with no frame of the stream between, by one that enables it now clears the detector, as the reference does at the disabling call
  * (setup_enc_lc3.c:297-308); before, the second call cancelled the first one's reset.
- * A ragged call of any length runs one channel-stream per wavefront (the path of short calls: ragged ticks are short); the pipelined kernels that long dense
- * calls use have no ragged form yet. */
+ * Which kernels carry a ragged call out.  It takes the pipelined path - a ragged form of every step, absent frames costing close to nothing - when all of
+ * these hold: it has no per-frame bitrates (with them the dense call runs the one-wave kernel too); the batch uses the standard kernel layout (every operating
+ * point but 96 kHz at 10 and 5 ms); n_frames > 8, with or without set_input_ready() - the lower threshold under the promise exists because calls overlap there,
+ * and a ragged call does not; and none of the diagnostic kernel switches is set (LC3PLUS_ENC_FUSED, _NO_SPLIT, _SHAPE_WAVE, _SCF_WAVE, _PACK_SPLIT,
+ * _TAILW_BYTES).  Every other ragged call runs one channel-stream per wavefront, the path of short calls: the large layout and the diagnostic writer variants
+ * (head / code split, frame per wave) have no ragged forms.  LC3PLUS_ENC_RAGGED_PIPE=0, read when the batch is created, sends every ragged call down the
+ * one-wave path: the results are the same.  last_status and last_records report a ragged pipelined call as they report a dense one; an absent frame's status
+ * is 0, and the record words of an absent frame are unspecified. */
 #define LC3PLUS_ENC_FL_ABSENT 32
 LC3_Error lc3plus_enc_batch_set_frame_counts(lc3plus_batch* batch, const int32_t* counts);
 /* That rule on the host alone, no device: lc3plus_enc_plan_rates_lenient with counts, host int32 [n_streams] or NULL = dense; bitrates and bandwidths may both
@@ -343,8 +350,8 @@ float lc3plus_enc_batch_last_kernel_ms(lc3plus_batch* batch);
 int lc3plus_enc_batch_last_status(lc3plus_batch* batch, uint8_t* status, int max_entries);
 
 /* Diagnostics: the per channel-frame records the kernels of the pipelined path hand to each other, of the last encode() call that took that path
- * (calls of more than 8 frames - more than 5 under the input-ready promise - that are neither traced nor run with LC3PLUS_ENC_FUSED / _NO_SPLIT; 0 words when
- * the last call did not take it): host array [n_streams * channels][n_frames][lc3plus_enc_batch_record_words()] of 32-bit words
+ * (calls of more than 8 frames - more than 5 under the input-ready promise - that are neither traced nor run with LC3PLUS_ENC_FUSED / _NO_SPLIT, and the ragged
+ * calls that take it, lc3plus_enc_batch_set_frame_counts above: the words of their absent frames are unspecified; 0 words when the last call did not take it): host array [n_streams * channels][n_frames][lc3plus_enc_batch_record_words()] of 32-bit words
  * - 16 scale factors, 16 quantised scale factors, 7 SNS indices, bandwidth index, attack-detector words, 4 LTPF words, 20 TNS words (filters,
  * orders, bits, coefficient indices), gain floor, all-zero flag, bandwidth behind the controller, and gain index / gain / bit count / last
  * non-zero line of the first quantisation (layout: FR_* in audio_codec_amd/csrc/lc3_plan.h).  The stage-level parity tests compare them with the
