@@ -303,9 +303,11 @@ ENC_WAVE_FN(LC3_OW_ARGS LC3_OW_OPT(LC3_OW_ARGS_, LC3_TU_VAR, LC3_TU_VBW, LC3_TU_
     for (int i = lane; i < MEMCAP; i += WAVE) stp[LC3D_ST_XPREV + i] = spec ? xnext[(size_t)cs * MEMCAP + i] : L.xbuf[i];
     for (int i = lane; i < 384; i += WAVE) stp[LC3D_ST_H12(MEMCAP) + i] = L.h12[i];
     for (int i = lane; i < 194; i += WAVE) stp[LC3D_ST_H6(MEMCAP) + i] = L.h6[i];
-    /* the HP50 state belongs to lc3_enc_hp50_kernel when it runs, the attack detector's to lc3_enc_attack_kernel on the split path */
-    if (lane < 12 && !(y12 && lane < 2) && !(spec && lane >= F_ATT_M0 && lane <= F_ATT_ACC)) stp[LC3D_ST_SCAL(MEMCAP) + lane] = L.fsc[lane];
-    if (lane < 16 && !(spec && (lane == I_ATT_POS || lane == I_ATT_FLAG))) ((int*)stp)[LC3D_ST_SCAL(MEMCAP) + 16 + lane] = L.isc[lane];
+    /* the HP50 state belongs to lc3_enc_hp50_kernel when it runs, the attack detector's to lc3_enc_attack_kernel on the split path.  Only the scalars that cross a
+     * frame are stored (fsc up to F_TBITS_OFF, isc up to I_MEM_SPEC): the ones behind them are every frame's own (F_NC, F_GAIN, I_T0 ..., written before they are read),
+     * the pipelined kernels never store them, and get_state() of two batches that encoded the same frames in calls of different shapes must give the same words */
+    if (lane <= F_TBITS_OFF && !(y12 && lane < 2) && !(spec && lane >= F_ATT_M0 && lane <= F_ATT_ACC)) stp[LC3D_ST_SCAL(MEMCAP) + lane] = L.fsc[lane];
+    if (lane <= I_MEM_SPEC && !(spec && (lane == I_ATT_POS || lane == I_ATT_FLAG))) ((int*)stp)[LC3D_ST_SCAL(MEMCAP) + 16 + lane] = L.isc[lane];
     (void)ml;
 }
 #undef ENC_TC

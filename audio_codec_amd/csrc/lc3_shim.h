@@ -111,7 +111,7 @@ int   lc3hip_last_records(void* ctx, float* rec_host, int max_words);   /* the p
 int   lc3hip_wait(void* ctx);                                      /* waits for the batch's last call (sync = 0 calls of a sharded batch) */
 int   lc3hip_dec_wait(void* ctx);
 int   lc3hip_destroy(void* ctx);
-int   lc3hip_test_fastmath(int kind, const float* x_host, float* y_host, long long n);   /* test hook: lc3_fastmath.h on the device over an array (0 log2, 1 log10, 2 2^x) */
+int   lc3hip_test_fastmath(int kind, const float* x_host, float* y_host, long long n);   /* test hook: the device's math over an array (0 log2, 1 log10, 2 2^x through lc3_fastmath.h; 3 pow(2, x), 4 pow(x, i mod 9) through the device library) */
 #ifdef __cplusplus
 }
 #endif

@@ -199,9 +199,14 @@ extern "C" __global__ void __launch_bounds__(WAVE) lc3_enc_rates_tail_kernel(con
         d->reset_attack = 0;
     }
 }
-/* test hook (tests/test_gpu_parity.py::test_device_fastmath_equals_host): lc3_fastmath.h as the kernels evaluate it, over an array.  kind 0 log2, 1 log10, 2 2^x */
+/* test hook (tests/test_gpu_parity.py::test_device_fastmath_equals_host): lc3_fastmath.h as the kernels evaluate it, over an array.  kind 0 log2, 1 log10, 2 2^x;
+ * and the calls that go through the device library's pow: kind 3 m_powf(2, x) (the regulariser, the decoder's SNS gains), kind 4 m_powf(x, k) with k = i mod 9 (the
+ * LPC weighting's alpha^k: the array holds every x nine times) */
 extern "C" __global__ void lc3_fastmath_test_kernel(int kind, const float* __restrict__ x, float* __restrict__ y, long long n)
 {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) y[i] = kind == 0 ? m_log2f(x[i]) : kind == 1 ? m_log10f(x[i]) : m_pow2f(x[i]);
+    if (i >= n) return;
+    if (kind == 3) y[i] = m_powf(2.0f, x[i]);
+    else if (kind == 4) y[i] = m_powf(x[i], (float)(int)(i % 9));
+    else y[i] = kind == 0 ? m_log2f(x[i]) : kind == 1 ? m_log10f(x[i]) : m_pow2f(x[i]);
 }

@@ -833,8 +833,10 @@ static void poly_to_rc(float* a, float* out, int len)
 }
 
 /* R/tns_coder.c:170-362 */
-static void stage_tns(const lc3o_enc* e, const chan_t* s, float* x, int bw_idx, int bw_bin, int* order_out, int* rc_idx, int* nfilt_out, int* bits_out)
+static void stage_tns(const lc3o_enc* e, const chan_t* s, float* x, int bw_idx, int bw_bin, int* order_out, int* rc_idx, int* nfilt_out, int* bits_out,
+                      int* weighted_out /* filters whose LPC went through the weighting */)
 {
+    *weighted_out = 0;
     int fs = e->fs, N = e->N, nBits = s->total_bits, dms = e->dms;
     int numfilters = (fs >= 32000 && dms >= 50) ? 2 : 1;
     int start[2] = {0}, stop[2] = {0};
@@ -876,6 +878,7 @@ static void stage_tns(const lc3o_enc* e, const chan_t* s, float* x, int bw_idx, 
                 float alpha = (maxPG - predGain) * (minPGfac - 1.0) / (maxPG - minPG) + 1.0;
                 for (int i = 0; i <= maxOrder; i++) a[i] = a[i] * m_powf(alpha, i);
                 poly_to_rc(a, rcu, maxOrder + 1);
+                (*weighted_out)++;
             }
             for (int i = 0; i < maxOrder; i++) {
                 int ret = 0;
@@ -910,7 +913,7 @@ static void stage_tns(const lc3o_enc* e, const chan_t* s, float* x, int bw_idx, 
 }
 
 /* R/estimate_global_gain.c:30-137 */
-static void stage_gain_estimate(const lc3o_enc* e, chan_t* s, const float* x, int nbitsSQ, float* gain, int* qgain, int* qmin)
+static void stage_gain_estimate(const lc3o_enc* e, chan_t* s, const float* x, int nbitsSQ, float* gain, int* qgain, int* qmin, int* reg_nonzero)
 {
     const int lg = e->ylen, off = s->gg_off;
     float en[LC3O_MAX_N / 4] = {0}, reg_val = 0, ind = 0, ind_min = 0;
@@ -931,6 +934,7 @@ static void stage_gain_estimate(const lc3o_enc* e, chan_t* s, const float* x, in
         float rB = 8 * (1 - (q < thresh ? q : thresh) / thresh);
         reg_val = x_max * m_powf(2, -s->reg_bits - rB);
     }
+    *reg_nonzero = reg_val != 0;
     if (x_max == 0) { ind_min = off; ind = 0; s->mem_target_bits = -1; }
     else {
         float g_min = e->hrmode == 1 ? x_max / (32768 * 256 - 2) : x_max / (32768 - 0.375);
@@ -1273,14 +1277,14 @@ static void encode_channel(lc3o_enc* e, int chn, const void* pcm, int bps, uint8
         bw = IMIN(bw, e->bw_index);
     }
     if (tr) tr->bw_idx = bw;
-    int nfilt = 0, tns_bits = 0;
-    stage_tns(e, s, d, bw, e->cut_bins[bw], tns_order, tns_idx, &nfilt, &tns_bits);
+    int nfilt = 0, tns_bits = 0, tns_weighted = 0, reg_nonzero = 0;
+    stage_tns(e, s, d, bw, e->cut_bins[bw], tns_order, tns_idx, &nfilt, &tns_bits, &tns_weighted);
     if (tr) { tr->tns_nfilt = nfilt; memcpy(tr->tns_order, tns_order, sizeof tns_order); memcpy(tr->tns_rc_idx, tns_idx, sizeof tns_idx);
               tr->tns_bits = tns_bits; memcpy(tr->spec_tns, d, sizeof(float) * N); }
     int tbq = s->target_bits_init - (tns_bits + ltpf_bits);
     float gain = 0; int gg = 0, ggmin = 0, nbits = 0, nbits2 = 0, lastnz = 0, lsb = 0, change = 0;
-    stage_gain_estimate(e, s, d, tbq, &gain, &gg, &ggmin);
-    if (tr) { tr->target_bits_quant = tbq; tr->gain0 = gain; tr->gg_idx0 = gg; tr->gg_min = ggmin; }
+    stage_gain_estimate(e, s, d, tbq, &gain, &gg, &ggmin, &reg_nonzero);
+    if (tr) { tr->tns_lpc_weighted = tns_weighted; tr->reg_nonzero = reg_nonzero; tr->target_bits_quant = tbq; tr->gain0 = gain; tr->gg_idx0 = gg; tr->gg_min = ggmin; }
     stage_quantize(e, s, d, gain, q, &nbits, &nbits2, &lastnz, cdata, &lsb, -1, tbq);
     s->mem_spec_bits = nbits;
     if (tr) tr->nbits0 = nbits;

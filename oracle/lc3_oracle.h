@@ -48,6 +48,9 @@ typedef struct {
     int   fac_ns;
     int   n_res_bits;
     int   bp_side, mask_side;       /* after side info */
+    /* the oracle's own: the device's lc3d_trace ends above */
+    int   tns_lpc_weighted;         /* TNS filters of the frame whose LPC ran the weighting (total bits < 480 and the prediction gain inside its window) */
+    int   reg_nonzero;              /* the high-resolution regulariser of the gain estimate was not zero */
 } lc3o_trace;
 
 typedef struct lc3o_enc lc3o_enc;

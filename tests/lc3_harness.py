@@ -75,6 +75,11 @@ class Trace(C.Structure):
     ]
 
 
+class OracleTrace(Trace):
+    """lc3o_trace (oracle/lc3_oracle.h): Trace, whose layout the device's lc3d_trace shares, and behind it what only the oracle records."""
+    _fields_ = [("tns_lpc_weighted", C.c_int), ("reg_nonzero", C.c_int)]
+
+
 class Oracle:
     """One multi-channel encoder instance of the CPU restatement."""
 
@@ -105,7 +110,7 @@ class Oracle:
         self.trace = None
 
     def enable_trace(self):
-        self.trace = (Trace * self.channels)()
+        self.trace = (OracleTrace * self.channels)()
         self.lib.lc3o_enc_set_trace.argtypes = [C.c_void_p, C.c_void_p]
         self.lib.lc3o_enc_set_trace(self.p, C.cast(self.trace, C.c_void_p))
         return self.trace

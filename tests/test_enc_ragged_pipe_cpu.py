@@ -47,6 +47,10 @@ def test_ragged_form_needs_no_more_than_its_twin(kernels, rag):
 def test_every_kernel_of_the_parent_keeps_its_figures(kernels):
     parent = kr.read_table(os.path.join(ROOT, "profiles", "enc_ragged_resources.txt"))
     assert len(parent) == 150
+    # the test hook of lc3_fastmath.h got two kinds since that table was written (m_powf(2, x), m_powf(x, k): tests/test_gpu_parity.py::
+    # test_device_fastmath_equals_host); it is no kernel of the product, and its figures are pinned here in the table's place
+    assert parent["lc3_fastmath_test_kernel"] == (34, 0, 20, 0, 0)
+    parent["lc3_fastmath_test_kernel"] = (32, 0, 22, 0, 0)
     changed = {k: (v, kernels.get(k)) for k, v in parent.items() if kernels.get(k) != v}
     assert not changed, changed
     assert sorted(set(kernels) - set(parent)) == sorted(TWINS)            # objects are added, nothing else

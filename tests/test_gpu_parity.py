@@ -1075,7 +1075,10 @@ def test_wave_per_frame_tail_writer_switch(tmp_path):
 
 def test_device_fastmath_equals_host(tmp_path):
     """lc3_fastmath.h gives the same bits on the device as on the host (which tools/fastmath_check.c pins to glibc for every float argument): half a million
-    arguments per function - every binade, the neighbourhood of 1 and of the powers of two, subnormals, the special arguments - through the library's test hook."""
+    arguments per function - every binade, the neighbourhood of 1 and of the powers of two, subnormals, the special arguments - through the library's test hook.
+    And the calls that stay with the device library's pow against glibc's (float)pow((double), (double)): m_powf(2, v) on the same exponents, m_powf(alpha, k),
+    k = 0 ... 8, on every 64th float of [0.85, 1], both ends and their neighbours (tools/pow_boundary_check.py is the exhaustive form,
+    profiles/pow_boundary_check.txt its result)."""
     import ctypes as C
     sys_path = os.path.join(os.path.dirname(os.path.abspath(__file__)))
     import importlib.util
@@ -1093,3 +1096,12 @@ def test_device_fastmath_equals_host(tmp_path):
         H.lc3m_host_eval(kind, x.ctypes.data, host.ctypes.data, x.size)
         same = (dev.view(np.uint32) == host.view(np.uint32)) | (np.isnan(dev) & np.isnan(host))
         assert same.all(), (kind, x[~same][:6], dev[~same][:6], host[~same][:6])
+    lo, hi = (int(np.array(v, np.float32).view(np.uint32)) for v in (0.85, 1.0))
+    alpha = np.unique(np.concatenate([np.arange(lo, hi + 1, 64), [lo - 1, lo, lo + 1, hi - 1, hi, hi + 1]]).astype(np.uint32)).view(np.float32)
+    for kind, host_kind, x in ((3, 6, ex), (4, 7, np.repeat(alpha, 9))):
+        x = np.ascontiguousarray(x)
+        dev = np.zeros_like(x); host = np.zeros_like(x)
+        assert L.lc3hip_test_fastmath(kind, x.ctypes.data, dev.ctypes.data, x.size) == 0
+        H.lc3m_host_eval(host_kind, x.ctypes.data, host.ctypes.data, x.size)
+        same = dev.view(np.uint32) == host.view(np.uint32)
+        assert same.all(), (kind, int((~same).sum()), x[~same][:6], np.flatnonzero(~same)[:6] % 9, dev[~same][:6], host[~same][:6])

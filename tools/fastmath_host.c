@@ -1,5 +1,6 @@
 /* tools/fastmath_host.c -- TEST INFRASTRUCTURE: audio_codec_amd/csrc/lc3_fastmath.h compiled for the host as array functions (tests/test_fastmath.py,
- * tests/test_gpu_parity.py::test_device_fastmath_equals_host): kind 0 = log2, 1 = log10, 2 = 2^x through the header, 3 / 4 / 5 the same through glibc.
+ * tests/test_gpu_parity.py::test_device_fastmath_equals_host): kind 0 = log2, 1 = log10, 2 = 2^x through the header, 3 / 4 / 5 the same through glibc;
+ * 6 = glibc's (float)pow(2.0, (double)x), what the device's m_powf(2, x) has to give, 7 = (float)pow((double)x, (double)(i mod 9)) for m_powf(alpha, k).
  *   gcc -O2 -ffp-contract=off -mfma -shared -fPIC -Iaudio_codec_amd/csrc tools/fastmath_host.c -o <out>.so -lm */
 #include "lc3_fastmath.h"
 void lc3m_host_eval(int kind, const float* x, float* y, long n)
@@ -11,7 +12,8 @@ void lc3m_host_eval(int kind, const float* x, float* y, long n)
         case 2: y[i] = lc3m_exp2f(x[i], lc3m_exp2_tab); break;
         case 3: y[i] = (float)log2((double)x[i]); break;
         case 4: y[i] = (float)log10((double)x[i]); break;
-        default: y[i] = (float)pow(2.0, (double)x[i]); break;
+        case 7: y[i] = (float)pow((double)x[i], (double)(float)(int)(i % 9)); break;
+        default: y[i] = (float)pow(2.0, (double)x[i]); break;          /* 5 and 6 */
         }
     }
 }
