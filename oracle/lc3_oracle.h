@@ -92,6 +92,25 @@ int  lc3o_dec_set_frame_ms(lc3o_dec* d, float frame_ms);
 int  lc3o_dec_set_hrmode(lc3o_dec* d, int hrmode);
 int  lc3o_dec_get_output_samples(const lc3o_dec* d);
 int  lc3o_dec_frame(lc3o_dec* d, const uint8_t* input, int num_bytes, void** output, int bps, int bfi_ext);   /* 0, LC3O_DECODE_ERROR (concealed) or an error */
+/* why the decoder refused the bitstream of channel ch's last frame (R/dec_entropy.c:120-270, R/ari_codec.c:204-509): 0 for a decoded frame and for one
+ * concealed because it was flagged, empty, or behind a refused first channel; else the decision that returned - for the three returns on the range decoder's
+ * ber flag, what set the flag first */
+enum { LC3O_REJ_NONE = 0,
+       LC3O_REJ_BANDWIDTH = 1,      /* bandwidth index above fs_idx */
+       LC3O_REJ_LASTNZ = 2,         /* lastnz > ylen */
+       LC3O_REJ_SNS_INDEX_25 = 3,   /* SNS joint index >= 33460056 (25-bit form, msb == 0) */
+       LC3O_REJ_SNS_INDEX_24 = 4,   /* SNS joint index >= 16708096 (24-bit form, msb == 1) */
+       LC3O_REJ_TNS_ORDER = 5,      /* TNS order above maxlag */
+       LC3O_REJ_TNS_READER = 6,     /* backward reader behind the forward one inside the TNS coefficients */
+       LC3O_REJ_TNS_SYMBOL = 7,     /* range-decoder state invalid on a TNS symbol */
+       LC3O_REJ_OVERLAP = 8,        /* forward and backward readers overlap by more than 3 bytes (tuple loop) */
+       LC3O_REJ_SPEC_SYMBOL = 9,    /* range-decoder state invalid inside the spectrum */
+       LC3O_REJ_ESCAPE_14 = 10,     /* escape at level 14 */
+       LC3O_REJ_NRES = 11,          /* nres < 0 */
+       LC3O_REJ_COUNT = 12 };
+int  lc3o_dec_last_reject(const lc3o_dec* d, int ch);
+int  lc3o_dec_reject_count(void);                 /* LC3O_REJ_COUNT */
+const char* lc3o_dec_reject_name(int code);       /* "none", "bandwidth", ... : what tools and tests print */
 int  lc3o_dft(float* x, int n);      /* test hook: forward complex DFT of length n in place (interleaved re, im); 0 = no kernel */
 int  lc3o_encode_batch16_ch(int samplerate, float frame_ms, int hrmode, int channels, int B, int T, const int* bitrate,
                             const int16_t* pcm, uint8_t* out, int stride);

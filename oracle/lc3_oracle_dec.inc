@@ -15,6 +15,7 @@ typedef struct {
     float ltpf_mem_x[16], ltpf_mem_y[LC3O_LTPF_Y];
     int ltpf_mem_pitch_int, ltpf_mem_pitch_fr, ltpf_mem_beta_idx, ltpf_param_mem[3]; float ltpf_mem_gain;
     float q_d_prev[LC3O_MAX_N]; int nbLost, prevBfi, prevprevBfi, plc_seed; float cum_alpha;
+    int last_reject;                    /* LC3O_REJ_* of the last frame: why the bitstream was refused, 0 for a decoded or flagged frame */
 } dchan_t;
 
 struct lc3o_dec {
@@ -88,6 +89,17 @@ int lc3o_dec_set_hrmode(lc3o_dec* d, int hr)                            /* R/lc3
     return 0;
 }
 int lc3o_dec_get_output_samples(const lc3o_dec* d) { return d ? d->N : 0; }
+int lc3o_dec_last_reject(const lc3o_dec* d, int ch) { return d && ch >= 0 && ch < d->channels ? d->ch[ch].last_reject : 0; }
+int lc3o_dec_reject_count(void) { return LC3O_REJ_COUNT; }
+const char* lc3o_dec_reject_name(int code)
+{
+    static const char* const names[LC3O_REJ_COUNT] = {"none", "bandwidth", "lastnz", "sns_index_25", "sns_index_24", "tns_order", "tns_reader", "tns_symbol",
+                                                      "overlap", "spec_symbol", "escape_14", "nres"};
+    return code >= 0 && code < LC3O_REJ_COUNT ? names[code] : "";
+}
+/* a `return 1` records its own code; one that follows the range decoder's ber flag records what set the flag first (BER) */
+#define LC3O_REJECT(code) do { *why = (code); } while (0)
+#define LC3O_BER(code) do { if (!ber_why) ber_why = (code); } while (0)
 
 /* R/setup_dec_lc3.c:188-299 update_dec_bitrate */
 static int dec_bitrate(lc3o_dec* d, dchan_t* s, int nbytes)
@@ -125,13 +137,13 @@ static int rd_uint(bitr* r, int n) { int v = rd_bit(r); for (int i = 1; i < n; i
 
 /* R/dec_entropy.c:120-270.  Returns 1 when the frame has to be concealed. */
 static int dec_side(const lc3o_dec* d, const uint8_t* bytes, int nbytes, bitr* r, int* gg, int* scf_idx, int* fac_ns, int* nfilt, int* tns_order,
-                    int* ltpf, int* bw, int* lastnz, int* lsb)
+                    int* ltpf, int* bw, int* lastnz, int* lsb, int* why)
 {
     r->p = bytes; r->bp = nbytes - 1; r->mask = 1;
-    if (d->bw_bits > 0) { *bw = rd_uint(r, d->bw_bits); if (d->fs_idx < *bw) return 1; } else *bw = d->fs_idx;
+    if (d->bw_bits > 0) { *bw = rd_uint(r, d->bw_bits); if (d->fs_idx < *bw) { LC3O_REJECT(LC3O_REJ_BANDWIDTH); return 1; } } else *bw = d->fs_idx;
     *nfilt = (*bw < 3 || d->dms == 25) ? 1 : 2;
     *lastnz = (rd_uint(r, (int)ceil(m_log2f(d->ylen / 2))) + 1) * 2;
-    if (*lastnz > d->ylen) return 1;
+    if (*lastnz > d->ylen) { LC3O_REJECT(LC3O_REJ_LASTNZ); return 1; }
     *lsb = rd_bit(r);
     *gg = rd_uint(r, 8);
     for (int i = 0; i < *nfilt; i++) tns_order[i] = rd_bit(r);
@@ -145,13 +157,13 @@ static int dec_side(const lc3o_dec* d, const uint8_t* bytes, int nbytes, bitr* r
     int lsbm = 0;
     if (msb == 0) {
         const int t = rd_uint(r, 25);
-        if (t >= 33460056) return 1;
+        if (t >= 33460056) { LC3O_REJECT(LC3O_REJ_SNS_INDEX_25); return 1; }
         const int ind = t / 2390004;
         scf_idx[5] = t - ind * 2390004;
         if (ind < 2) { lsbm = 1; scf_idx[3] = scf_idx[3] * 2 + ind; scf_idx[6] = -2; } else { lsbm = 0; scf_idx[6] = ind - 2; }
     } else {
         const int t = rd_uint(r, 24);
-        if (t >= 16708096) return 1;
+        if (t >= 16708096) { LC3O_REJECT(LC3O_REJ_SNS_INDEX_24); return 1; }
         if (t >= 15158272) { lsbm = 1; scf_idx[3] = scf_idx[3] * 2 + ((t - 15158272) & 1); scf_idx[5] = (t - 15158272) / 2; scf_idx[6] = -2; }
         else { lsbm = 0; scf_idx[5] = t; scf_idx[6] = -1; }
     }
@@ -177,7 +189,7 @@ static int ad_decode(adec* st, const uint16_t* cum /* cum[0..n], cum[n] = 1024 *
 
 /* R/ari_codec.c:204-509.  Returns 1 when the frame has to be concealed. */
 static int dec_spectrum(const lc3o_dec* d, const dchan_t* s, const uint8_t* bytes, bitr* r, int nfilt, int lsbMode, int lastnz, int* tns_order, int fac_ns,
-                        int gg, uint8_t* resBits, int* x, int* nf_seed, int* tns_idx, int* zero_frame, int* nres, int* res_present)
+                        int gg, uint8_t* resBits, int* x, int* nf_seed, int* tns_idx, int* zero_frame, int* nres, int* res_present, int* why)
 {
     const int L = d->ylen, total_bits = 8 * s->targetBytes;
     int rate = 0;
@@ -185,15 +197,18 @@ static int dec_spectrum(const lc3o_dec* d, const dchan_t* s, const uint8_t* byte
     adec st; st.p = bytes; st.low = 0; st.range = 0xFFFFFF; st.bp = 0; st.ber = 0;
     for (int i = 0; i < 3; i++) { st.low = (int)((unsigned)st.low << 8) + bytes[st.bp]; st.bp++; }
     int maxlag = 8; if (d->dms == 25) maxlag /= 2; if (d->dms == 50) maxlag /= 2;
+    int ber_why = 0;
     for (int n = 0; n < nfilt; n++) if (tns_order[n] > 0) {
         tns_order[n] = ad_decode(&st, &lc3t_tns_order_cum[s->lpc_weighting * 9], 8) + 1;
-        if (tns_order[n] > maxlag) st.ber = 1;
+        if (st.ber) LC3O_BER(LC3O_REJ_TNS_SYMBOL);
+        if (tns_order[n] > maxlag) { st.ber = 1; LC3O_BER(LC3O_REJ_TNS_ORDER); }
         for (int k = 0; k < tns_order[n]; k++) {
-            if (r->bp < st.bp) return 1;
+            if (r->bp < st.bp) { LC3O_REJECT(LC3O_REJ_TNS_READER); return 1; }
             tns_idx[n * 8 + k] = ad_decode(&st, &lc3t_tns_coef_cum[k * 18], 17);
+            if (st.ber) LC3O_BER(LC3O_REJ_TNS_SYMBOL);
         }
     }
-    if (st.ber > 0) return 1;
+    if (st.ber > 0) { LC3O_REJECT(ber_why); return 1; }
     int c = 0, save_lev[LC3O_MAX_N];
     memset(save_lev, 0, sizeof save_lev);
     for (int k = 0; k < lastnz; k += 2) {
@@ -205,10 +220,11 @@ static int dec_spectrum(const lc3o_dec* d, const dchan_t* s, const uint8_t* byte
         for (lev = 0; lev <= max_lev; lev++) {
             const int pki = lc3t_ac_ctx_lut[t + IMIN(lev, 3) * 1024];
             sym = ad_decode(&st, &lc3t_ac_cum[pki * 18], 17);
+            if (st.ber) LC3O_BER(LC3O_REJ_SPEC_SYMBOL);
             if (sym < 16) break;
             if (lsbMode == 0 || lev > 0) { x[k] += rd_bit(r) << lev; x[k + 1] += rd_bit(r) << lev; }
         }
-        if ((lev - 1) == 13 && sym == 16) st.ber = 1;
+        if ((lev - 1) == 13 && sym == 16) { st.ber = 1; LC3O_BER(LC3O_REJ_ESCAPE_14); }
         if (d->hrmode == 0) lev = IMIN(lev, 13);
         if (lsbMode == 1) save_lev[k] = lev;
         const int a = sym & 3, b = sym >> 2;
@@ -218,13 +234,13 @@ static int dec_spectrum(const lc3o_dec* d, const dchan_t* s, const uint8_t* byte
         const int lev1 = IMIN(lev, 3);
         t = lev1 <= 1 ? 1 + (a + b) * (lev1 + 1) : 12 + lev1;
         c = (c & 15) * 16 + t;
-        if (st.bp - r->bp > 3) return 1;
-        if (st.ber > 0) return 1;
+        if (st.bp - r->bp > 3) { LC3O_REJECT(LC3O_REJ_OVERLAP); return 1; }
+        if (st.ber > 0) { LC3O_REJECT(ber_why); return 1; }
     }
     const int nbits_side = total_bits - (8 * (r->bp + 1) + 8 - flog2_of(r->mask));
     const int nbits_ari = (st.bp + 1 - 3) * 8 + 25 - flog2_of((int)st.range);      /* floor(log2f(.)) with glibc's float log2 in both oracle builds, as in the encoder */
     *nres = total_bits - (nbits_side + nbits_ari);
-    if (*nres < 0) return 1;
+    if (*nres < 0) { LC3O_REJECT(LC3O_REJ_NRES); return 1; }
     *res_present = 0;
     if (lsbMode == 0) {
         int nnz = 0;
@@ -458,10 +474,11 @@ static int dec_channel(lc3o_dec* d, dchan_t* s, const uint8_t* bs, void* out, in
     float q[LC3O_MAX_N], xo[LC3O_MAX_N], scf_q[16];
     memset(q, 0, sizeof q);
     bitr r;
-    if (bfi != 1) bfi = dec_side(d, bs, s->targetBytes, &r, &gg, scf_idx, &fac_ns, &nfilt, tns_order, ltpf, &bw, &lastnz, &lsb) ? 1 : bfi;
+    s->last_reject = 0;
+    if (bfi != 1) bfi = dec_side(d, bs, s->targetBytes, &r, &gg, scf_idx, &fac_ns, &nfilt, tns_order, ltpf, &bw, &lastnz, &lsb, &s->last_reject) ? 1 : bfi;
     if (bfi != 1) {
         memset(xq, 0, sizeof xq);
-        if (dec_spectrum(d, s, bs, &r, nfilt, lsb, lastnz, tns_order, fac_ns, gg, resBits, xq, &nf_seed, tns_idx, &zero_frame, &nres, &res_present)) bfi = 1;
+        if (dec_spectrum(d, s, bs, &r, nfilt, lsb, lastnz, tns_order, fac_ns, gg, resBits, xq, &nf_seed, tns_idx, &zero_frame, &nres, &res_present, &s->last_reject)) bfi = 1;
         for (int i = 0; i < L; i++) q[i] = (float)xq[i];
         if (tr) { tr->bw_idx = bw; tr->lastnz = lastnz; tr->lsb_mode = lsb; tr->gg_idx = gg; tr->fac_ns = fac_ns; tr->nfilt = nfilt; tr->nf_seed = nf_seed;
                   tr->zero_frame = zero_frame; tr->nres = nres; memcpy(tr->tns_order, tns_order, sizeof tns_order); memcpy(tr->tns_idx, tns_idx, sizeof tns_idx);
@@ -578,3 +595,5 @@ int lc3o_dec_frame(lc3o_dec* d, const uint8_t* input, int num_bytes, void** outp
     }
     return bfi == 1 ? LC3O_DECODE_ERROR : 0;
 }
+#undef LC3O_REJECT
+#undef LC3O_BER

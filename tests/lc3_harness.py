@@ -247,6 +247,17 @@ class OracleDecoder:
         rc = self.lib.lc3o_dec_frame(self.p, frame_bytes.ctypes.data, int(frame_bytes.size) if num_bytes is None else num_bytes, ptrs, bps, bfi)
         return rc, out
 
+    def last_reject(self, ch=0):
+        """why the decoder refused channel ch's last frame: one of LC3O_REJ_* (oracle/lc3_oracle.h, reject_names() below), 0 for a decoded or flagged frame"""
+        return int(self.lib.lc3o_dec_last_reject(self.p, int(ch)))
+
+
+def reject_names():
+    """the names of LC3O_REJ_* by code, as the oracle library gives them (lc3o_dec_reject_name, lc3o_dec_reject_count): ("none", "bandwidth", ...)"""
+    L = C.CDLL(os.path.join(ORACLE_DIR, "liblc3_oracle_pm.so"))
+    L.lc3o_dec_reject_name.restype = C.c_char_p
+    return tuple(L.lc3o_dec_reject_name(i).decode() for i in range(L.lc3o_dec_reject_count()))
+
 
 class RefDecoder:
     """ETSI float decoder (tool use only: turns bitstreams back into PCM for distance metrics)."""

@@ -1,21 +1,48 @@
 """Differential soak of the DECODER (GPU box): every operating point x seeds x channel counts.  Bitstreams come from the GPU encoder,
 get damaged (frames marked lost, bytes flipped in unmarked frames), are decoded on the GPU in two launches and by the CPU oracle
 decoder (same math); PCM and the concealment status must be identical.
-Usage: python tools/dec_soak.py [seeds] [streams] [frames]  -> one line per differing configuration and a total; exit code 1 on any difference."""
-import os, sys, time
+Usage: python tools/dec_soak.py [seeds] [streams] [frames]  -> one line per differing configuration, a total and the tally of the oracle's last_reject() over
+what was decoded (which refusals of the bitstream the soak reached); exit code 1 on any difference."""
+import collections, os, sys, time
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
 import audio_codec_amd
-from lc3_harness import synth_pcm, oracle_decode_streams
+from lc3_harness import synth_pcm, oracle_decode_streams, OracleDecoder
 import importlib.util
 _spec = importlib.util.spec_from_file_location("soak", os.path.join(ROOT, "tools", "soak.py"))
 _soak = importlib.util.module_from_spec(_spec); _spec.loader.exec_module(_soak)
 configurations = _soak.configurations
 
 
-def run(NS, B, T, verbose=True):
-    """returns (channel-frames compared, channel-frames that differ)"""
+def reject_names():
+    """LC3O_REJ_* by code, from the oracle library itself (this tool also has to load beside a tests/ directory older than OracleDecoder.last_reject)"""
+    import ctypes
+    L = OracleDecoder(48000, 1, 10.0, 0, portable_math=True).lib
+    L.lc3o_dec_reject_name.restype = ctypes.c_char_p
+    return tuple(L.lc3o_dec_reject_name(i).decode() for i in range(L.lc3o_dec_reject_count()))
+
+
+def _oracle_decode_tallied(frames, nb, bfi, fs, ms, hr, ch, bps, tally):
+    """oracle_decode_streams, counting lc3o_dec_last_reject of every channel-frame into tally"""
+    B, T = frames.shape[:2]
+    out = status = None
+    for b in range(B):
+        o = OracleDecoder(fs, ch, ms, hr, portable_math=True)
+        if out is None:
+            out = np.zeros((B, T, ch, o.N), dtype=np.int16 if bps == 16 else np.int32)
+            status = np.zeros((B, T), dtype=np.uint8)
+        for t in range(T):
+            rc, pcm = o.decode(frames[b, t, :nb[b]], int(bfi[b, t]), bps)
+            assert rc in (0, 2), rc
+            out[b, t] = pcm
+            status[b, t] = rc == 2
+            tally.update(int(o.lib.lc3o_dec_last_reject(o.p, c)) for c in range(ch))
+    return out, status
+
+
+def run(NS, B, T, verbose=True, tally=None):
+    """returns (channel-frames compared, channel-frames that differ); tally: a Counter for the oracle's last_reject() of every channel-frame"""
     tot = bad = 0
     for ci, (fs, ms, hr, rates) in enumerate(configurations()):
         N = int(round((48000 if fs == 44100 else fs) * ms / 1000))
@@ -38,7 +65,10 @@ def run(NS, B, T, verbose=True):
             a, sa = dec.decode(frames[:, :cut], bfi[:, :cut], bps)
             c, sc = dec.decode(frames[:, cut:], bfi[:, cut:], bps)
             got, status = np.concatenate([a, c], axis=1), np.concatenate([sa, sc], axis=1)
-            want, wstatus = oracle_decode_streams(frames, nb, bfi, fs, ms, hr, ch, bps)
+            if tally is None:
+                want, wstatus = oracle_decode_streams(frames, nb, bfi, fs, ms, hr, ch, bps)
+            else:
+                want, wstatus = _oracle_decode_tallied(frames, nb, bfi, fs, ms, hr, ch, bps, tally)
             d = int((got != want).any(axis=3).sum()) + int((status != wstatus).sum())
             tot += B * T * ch; bad += d
             if d and verbose: print("%6d Hz %4.1f ms hr%d ch%d bps%d seed %d: %d of %d channel-frames differ" % (fs, ms, hr, ch, bps, seed, d, B * T * ch))
@@ -50,6 +80,8 @@ if __name__ == "__main__":
     B = int(sys.argv[2]) if len(sys.argv) > 2 else 32
     T = int(sys.argv[3]) if len(sys.argv) > 3 else 48
     t0 = time.time()
-    tot, bad = run(NS, B, T)
+    tally = collections.Counter()
+    tot, bad = run(NS, B, T, tally=tally)
     print("decoder soak: %d channel-frames over %d configurations x %d seeds, %d differ, %.0f s" % (tot, len(configurations()), NS, bad, time.time() - t0))
+    print("refused for:", ", ".join("%s %d" % (name, tally[r]) for r, name in enumerate(reject_names()) if r))
     sys.exit(1 if bad else 0)
