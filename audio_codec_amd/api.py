@@ -2,6 +2,7 @@
 
 Nothing here computes anything: every call goes to liblc3plus_hip.so.  If the library has not been built the
 import of a symbol fails loudly -- there is no Python or CPU fallback path."""
+import contextlib
 import ctypes as C
 import os
 
@@ -209,6 +210,42 @@ def load_library():
         L.lc3plus_dec_plan_counts.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
         _LIB = L
     return _LIB
+
+
+@contextlib.contextmanager
+def launch_census():
+    """The kernel launches made inside the block, as {kernel symbol name: count}: the dictionary the block receives is filled when the block ends.  A launch is
+    counted on the host when the call that makes it is made, so the result is complete once the calls have returned, with sync=0 too.  Process-wide (every batch,
+    every host thread): the result is the difference of the library's counts between the two ends of the block, so blocks may nest and a census of the whole
+    process (LC3PLUS_LAUNCH_CENSUS) goes on undisturbed; without that switch the census is off again behind the block."""
+    L = load_library()
+    L.lc3hip_launch_census_read.restype = C.c_size_t
+    L.lc3hip_launch_census_read.argtypes = [C.c_char_p, C.c_size_t]
+    L.lc3hip_launch_census_enable.argtypes = [C.c_int]
+    out = {}
+    was_on = bool(os.environ.get("LC3PLUS_LAUNCH_CENSUS")) or getattr(launch_census, "depth", 0) > 0
+    launch_census.depth = getattr(launch_census, "depth", 0) + 1
+    L.lc3hip_launch_census_enable(1)
+    before = _census_counts(L)
+    try:
+        yield out
+    finally:
+        launch_census.depth -= 1
+        after = _census_counts(L)
+        if not was_on:
+            L.lc3hip_launch_census_enable(0)
+        out.update({k: n - before.get(k, 0) for k, n in after.items() if n > before.get(k, 0)})
+
+
+def _census_counts(L):
+    return {name: int(n) for name, n in (line.split() for line in _census_text(L).splitlines())}
+
+
+def _census_text(L):
+    n = L.lc3hip_launch_census_read(None, 0)
+    buf = C.create_string_buffer(n)
+    L.lc3hip_launch_census_read(buf, n)
+    return buf.value.decode()
 
 
 def pcm_format(sample, layout=None):

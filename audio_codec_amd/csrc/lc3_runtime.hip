@@ -7,11 +7,69 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <dlfcn.h>
+#include <fcntl.h>
+#include <unistd.h>
+#include <atomic>
+#include <mutex>
+#include <string>
+#include <vector>
 
 #include "lc3_plan.h"
 #include "lc3_shim.h"
 #include "lc3_launch.h"
 #include "lc3_kernel_decls.h"
+
+/* The launch census (lc3_shim.h: lc3hip_launch_census_*; LC3PLUS_LAUNCH_CENSUS=<path>): which kernel entry points this process has launched, and how often.  Every
+ * launch of this file goes through LC3_LAUNCH.  Off - the default - a launch reads one process-wide flag; on, it takes a lock (the sharded batches launch from one
+ * host thread per shard) and counts under the kernel's host handle.  A handle's name is resolved when it is first seen: the handle of an extern "C" kernel is an
+ * exported object of this library whose symbol is the kernel's name in the code object, so dladdr gives it; hipKernelNameRefByPtr is asked where dladdr has no answer.
+ * With the environment switch (read once, when the library is loaded) the census is on from the start and its lines are appended to <path>, in one write, when the
+ * library is unloaded or the process exits: no HIP call is made that late. */
+struct census_entry { const void* fn; unsigned long long n; std::string name; };
+static std::atomic<int> g_census_on{0};
+static std::mutex g_census_mu;
+static std::vector<census_entry> g_census;
+static void census_note(const void* fn)
+{
+    std::lock_guard<std::mutex> lk(g_census_mu);
+    for (census_entry& e : g_census) if (e.fn == fn) { e.n++; return; }
+    Dl_info di; const char* nm = nullptr;
+    if (dladdr(fn, &di) && di.dli_sname && di.dli_saddr == fn) nm = di.dli_sname;
+    if (!nm) { nm = hipKernelNameRefByPtr(fn, (hipStream_t)0); (void)hipGetLastError(); }
+    char buf[32];
+    if (!nm || !*nm) { snprintf(buf, sizeof buf, "kernel@%p", fn); nm = buf; }
+    g_census.push_back({fn, 1ull, std::string(nm)});
+}
+static std::string census_text()
+{
+    std::lock_guard<std::mutex> lk(g_census_mu);
+    std::string t;
+    for (const census_entry& e : g_census) if (e.n) t += e.name + " " + std::to_string(e.n) + "\n";
+    return t;
+}
+#define LC3_LAUNCH(k, ...) do { auto k_ = (k); if (g_census_on.load(std::memory_order_relaxed)) census_note((const void*)k_); hipLaunchKernelGGL(k_, __VA_ARGS__); } while (0)
+extern "C" void lc3hip_launch_census_enable(int on) { g_census_on.store(on != 0, std::memory_order_relaxed); }
+extern "C" void lc3hip_launch_census_reset(void) { std::lock_guard<std::mutex> lk(g_census_mu); for (census_entry& e : g_census) e.n = 0; }
+extern "C" size_t lc3hip_launch_census_read(char* buf, size_t cap)
+{
+    const std::string t = census_text();
+    if (buf && cap) { const size_t m = t.size() < cap - 1 ? t.size() : cap - 1; memcpy(buf, t.data(), m); buf[m] = 0; }
+    return t.size() + 1;
+}
+static struct census_env {
+    std::string path;
+    census_env() { const char* e = getenv("LC3PLUS_LAUNCH_CENSUS"); if (e && *e) { path = e; g_census_on.store(1, std::memory_order_relaxed); } }
+    ~census_env()
+    {
+        if (path.empty()) return;
+        const std::string t = census_text();
+        const int fd = open(path.c_str(), O_WRONLY | O_CREAT | O_APPEND, 0644);
+        if (fd < 0) return;
+        if (!t.empty() && write(fd, t.data(), t.size()) < 0) {}
+        close(fd);
+    }
+} g_census_env;      /* defined behind what its destructor reads: destroyed first */
 
 #define LC3D_MAX_RUNS 16
 #define PKS_SUMS(n) (((size_t)(n) + PKS_TILE - 1) / PKS_TILE)      /* packed output: tile sums of the scan over n frames */
@@ -182,7 +240,7 @@ static int ss_init(lc3hip_ss* q, int device, float* state, int row_words, int nc
     q->row_words = row_words;
     if (grow_once(&q->d_tmpl, sizeof(float) * (size_t)row_words)) return 1;
     HIPCHK(hipMemcpy(q->d_tmpl, tmpl, sizeof(float) * (size_t)row_words, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(lc3_stream_state_kernel, dim3((unsigned)ncs), dim3(WAVE), 0, (hipStream_t)0, (int)LC3D_SS_RESET, state, row_words, 1, (const int*)nullptr, ncs,
+    LC3_LAUNCH(lc3_stream_state_kernel, dim3((unsigned)ncs), dim3(WAVE), 0, (hipStream_t)0, (int)LC3D_SS_RESET, state, row_words, 1, (const int*)nullptr, ncs,
                        (const float*)q->d_tmpl, (uint8_t*)nullptr, 0u, 0u, 0u, 0u, (uint8_t*)nullptr, (const uint32_t*)nullptr, (uint32_t*)nullptr, 0);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize((hipStream_t)0));
@@ -217,7 +275,7 @@ static int ss_run(lc3hip_ss* q, hipStream_t s, hipStream_t last, int mode, float
     if (last && last != s) { HIPCHK(hipEventRecord(q->ev_prev, last)); HIPCHK(hipStreamWaitEvent(s, q->ev_prev, 0)); }
     HIPCHK(hipMemcpyAsync(q->d[k], q->h[k], mode == LC3D_SS_IMPORT && !blob_on_device ? o_blob + blob_bytes : o_blob, hipMemcpyHostToDevice, s));
     uint8_t* dblob = blob_on_device ? (uint8_t*)blob : q->d[k] + o_blob;
-    hipLaunchKernelGGL(lc3_stream_state_kernel, dim3((unsigned)((size_t)n * channels)), dim3(WAVE), 0, s, mode, state, q->row_words, channels, (const int*)q->d[k], n,
+    LC3_LAUNCH(lc3_stream_state_kernel, dim3((unsigned)((size_t)n * channels)), dim3(WAVE), 0, s, mode, state, q->row_words, channels, (const int*)q->d[k], n,
                        (const float*)q->d_tmpl, dblob, hdr[0], hdr[1], hdr[2], hdr[3], blob_on_device ? status : (uint8_t*)nullptr,
                        (const uint32_t*)(cfg ? q->d[k] + o_cfg : nullptr), (uint32_t*)chans, cfg_bytes / 4);
     HIPCHK(hipGetLastError());
@@ -234,7 +292,7 @@ extern "C" int lc3hip_test_fastmath(int kind, const float* x_host, float* y_host
     float *dx = nullptr, *dy = nullptr;
     HIPCHK(hipMalloc((void**)&dx, (size_t)n * 4)); HIPCHK(hipMalloc((void**)&dy, (size_t)n * 4));
     HIPCHK(hipMemcpy(dx, x_host, (size_t)n * 4, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(lc3_fastmath_test_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, kind, dx, dy, n);
+    LC3_LAUNCH(lc3_fastmath_test_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, kind, dx, dy, n);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpy(y_host, dy, (size_t)n * 4, hipMemcpyDeviceToHost));
     HIPCHK(hipFree(dx)); HIPCHK(hipFree(dy));
@@ -359,7 +417,7 @@ struct pcm_as { const void* p; template <typename T> operator const T*() const {
 static int placed_mark(const long long* plo, long long plcap, int channels, int N, long long n, uint8_t* out, int bit, hipStream_t s)
 {
     if (!plo || !out || n <= 0) return 0;
-    hipLaunchKernelGGL(lc3_pcm_placed_mark_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, plo, plcap, channels, N, n, out, bit);
+    LC3_LAUNCH(lc3_pcm_placed_mark_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, plo, plcap, channels, N, n, out, bit);
     HIPCHK(hipGetLastError());
     return 0;
 }
@@ -370,11 +428,11 @@ static void launch_resample(lc3hip_ctx* c, hipStream_t st, const void* dpcm, int
     const unsigned pruns = (unsigned)((hn + PRE_FPW - 1) / PRE_FPW);
     const bool a16 = (((size_t)dpcm) & 15) == 0;
     /* the resampler for every shape, and its twins by sample type */
-    auto any = [&](auto k, auto... placed) { hipLaunchKernelGGL(k, dim3((unsigned)c->ncs * pruns), dim3(WAVE), 0, st, c->d_plan, c->d_state, c->state_words, mc, dpcm, bitdepth, n_frames, hb, hn, c->ncs, dy12, xprev, xprev_stride, placed...); };
+    auto any = [&](auto k, auto... placed) { LC3_LAUNCH(k, dim3((unsigned)c->ncs * pruns), dim3(WAVE), 0, st, c->d_plan, c->d_state, c->state_words, mc, dpcm, bitdepth, n_frames, hb, hn, c->ncs, dy12, xprev, xprev_stride, placed...); };
     /* the specialised ones take typed dense pointers: 16-bit samples ... */
-    auto s16 = [&](auto k, unsigned runs) { hipLaunchKernelGGL(k, dim3((unsigned)c->ncs * runs), dim3(WAVE), 0, st, c->d_plan, (const int16_t*)dpcm, c->channels, mc, n_frames, hb, hn, c->ncs, dy12, xprev, xprev_stride); };
+    auto s16 = [&](auto k, unsigned runs) { LC3_LAUNCH(k, dim3((unsigned)c->ncs * runs), dim3(WAVE), 0, st, c->d_plan, (const int16_t*)dpcm, c->channels, mc, n_frames, hb, hn, c->ncs, dy12, xprev, xprev_stride); };
     /* ... and float32 or wire samples, which also take the format word */
-    auto typed = [&](auto k) { hipLaunchKernelGGL(k, dim3((unsigned)c->ncs * pruns), dim3(WAVE), 0, st, c->d_plan, pcm_as{dpcm}, bitdepth, c->channels, mc, n_frames, hb, hn, c->ncs, dy12, xprev, xprev_stride); };
+    auto typed = [&](auto k) { LC3_LAUNCH(k, dim3((unsigned)c->ncs * pruns), dim3(WAVE), 0, st, c->d_plan, pcm_as{dpcm}, bitdepth, c->channels, mc, n_frames, hb, hn, c->ncs, dy12, xprev, xprev_stride); };
     if (cnt) {
         if (c->plo) any(lc3_enc_resample_plc_kernel_rag, c->plo, c->plcap, cnt);
         else any((bitdepth == 16 || bitdepth == 24 || bitdepth == 32) ? lc3_enc_resample_kernel_rag : lc3d_pcm_type_wire(bitdepth & LC3D_PCM_TYPE_MASK) ? lc3_enc_resample_wire_kernel_rag : lc3_enc_resample_fmt_kernel_rag, cnt);
@@ -392,7 +450,7 @@ static void launch_resample(lc3hip_ctx* c, hipStream_t st, const void* dpcm, int
 /* behind it the HP50 recurrence of the same frames, one stream per lane */
 static void launch_hp50(lc3hip_ctx* c, hipStream_t st, int n_frames, int hb, int hn, int mc, float* dy12, const int32_t* cnt = nullptr)
 {
-    auto hp = [&](auto k, auto... ragged) { hipLaunchKernelGGL(k, dim3((unsigned)((c->ncs + WAVE - 1) / WAVE)), dim3(WAVE), 0, st, c->d_plan, c->d_state, c->state_words, LC3D_ST_SCAL(mc), n_frames, hb, hn, c->ncs, dy12, ragged...); };
+    auto hp = [&](auto k, auto... ragged) { LC3_LAUNCH(k, dim3((unsigned)((c->ncs + WAVE - 1) / WAVE)), dim3(WAVE), 0, st, c->d_plan, c->d_state, c->state_words, LC3D_ST_SCAL(mc), n_frames, hb, hn, c->ncs, dy12, ragged...); };
     if (cnt) hp(lc3_enc_hp50_kernel_rag, cnt); else hp(lc3_enc_hp50_kernel);
 }
 static int bw_to(lc3hip_ctx* c, hipStream_t st);
@@ -475,7 +533,7 @@ static int enc_one_wave(lc3hip_ctx* c, const enc_call* q)
     /* the one-wave kernel of this call by layout and optional argument groups (lc3_kernel_decls.h: LC3_OW_KERNELS), or its _fmt, _wire or _plc twin */
     const long long* pt = c->pk.on || q->cnt ? c->pk.tab : nullptr;         /* packed output: the _pk kernels, frames at the offsets of the call's table (a ragged call always has one) */
     const int key = OW_KEY(c->big != 0, q->dfsz != nullptr, q->dbw != nullptr, pt != nullptr);
-    auto ow = [&](auto k, auto... groups) { hipLaunchKernelGGL(k, dim3(c->ncs), dim3(WAVE), 0, s, c->d_plan, c->d_chans, c->d_state, q->dpcm, q->bitdepth, q->n_frames, q->dout, pt ? 0 : q->out_stride, c->ncs, q->dtr, q->ddump, q->dstride, q->dy12, c->d_status, q->dT, q->dt0, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, groups...); };
+    auto ow = [&](auto k, auto... groups) { LC3_LAUNCH(k, dim3(c->ncs), dim3(WAVE), 0, s, c->d_plan, c->d_chans, c->d_state, q->dpcm, q->bitdepth, q->n_frames, q->dout, pt ? 0 : q->out_stride, c->ncs, q->dtr, q->ddump, q->dstride, q->dy12, c->d_status, q->dT, q->dt0, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, groups...); };
 #define OW_LAUNCH(name, big, var, vbw, pk) \
     if (key == OW_KEY(big, var, vbw, pk)) { \
         if (q->placed) ow(name##_plc LC3_OW_OPT(LC3_OW_VALS_, var, vbw, pk), c->plo, c->plcap); \
@@ -546,7 +604,7 @@ static int enc_run(lc3hip_ctx* c, const enc_call* q, enc_runs* r, int k, int tb,
     /* (a ragged call: one stream per wave - the two streams of a pitch2 wave share barriers and have counts of their own) */
     const bool p2 = c->opt.pitch2 && (c->len12 == 128 || c->len12 == 64 || c->len12 == 32) && !q->cnt;
     auto pk = !p2 ? lc3_enc_pitch_kernel : c->len12 == 128 ? lc3_enc_pitch2_kernel : c->len12 == 64 ? lc3_enc_pitch2_kernel_l64 : lc3_enc_pitch2_kernel_l32;
-    auto pitch = [&](auto kern, auto... ragged) { hipLaunchKernelGGL(kern, dim3((unsigned)(p2 ? (c->ncs + 1) / 2 : c->ncs)), dim3(WAVE), 0, c->s_pit, c->d_plan, c->d_chans, c->d_state, c->state_words, mc, q->dy12, n_frames, tb, nt, c->ncs, dfrec, dT, dt0, ragged...); };
+    auto pitch = [&](auto kern, auto... ragged) { LC3_LAUNCH(kern, dim3((unsigned)(p2 ? (c->ncs + 1) / 2 : c->ncs)), dim3(WAVE), 0, c->s_pit, c->d_plan, c->d_chans, c->d_state, c->state_words, mc, q->dy12, n_frames, tb, nt, c->ncs, dfrec, dT, dt0, ragged...); };
     if (q->cnt) pitch(lc3_enc_pitch_kernel_rag, q->cnt); else DUPL('p') pitch(pk);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(c->ev_p[k], c->s_pit));
@@ -554,9 +612,9 @@ static int enc_run(lc3hip_ctx* c, const enc_call* q, enc_runs* r, int k, int tb,
     {   /* the front: four frames a wave at 48 kHz / 10 ms, fm_frames a wave for the short frame lengths, else fpw frames a wave */
         const int fpw = nt < FRONT_FPW ? nt : FRONT_FPW;
         const int f4 = c->opt.front4;
-        auto front4 = [&](auto kern, auto... placed) { hipLaunchKernelGGL(kern, dim3((unsigned)c->ncs * (unsigned)((nt + 3) / 4)), dim3(WAVE), 0, c->s_fr, c->d_plan, c->d_chans, c->d_state, q->dpcm, q->bitdepth, n_frames, tb, nt, c->ncs, dspec, c->srow, dT, dt0, dfrec, r->xn_w, r->xprev, r->xprev_stride, placed...); };
-        auto frontm = [&](auto kern, auto... placed) { hipLaunchKernelGGL(kern, dim3((unsigned)c->ncs * (unsigned)((nt + c->fm_frames - 1) / c->fm_frames)), dim3(WAVE), 0, c->s_fr, c->d_plan, c->d_chans, c->d_state, q->dpcm, q->bitdepth, n_frames, tb, nt, c->fm_frames, c->ncs, dspec, c->srow, dT, dt0, dfrec, r->xn_w, r->xprev, r->xprev_stride, placed...); };
-        auto front = [&](auto kern, auto... placed) { hipLaunchKernelGGL(kern, dim3((unsigned)c->ncs * (unsigned)((nt + fpw - 1) / fpw)), dim3(WAVE), 0, c->s_fr, c->d_plan, c->d_chans, c->d_state, q->dpcm, q->bitdepth, n_frames, tb, nt, fpw, c->ncs, dspec, c->srow, dT, dt0, dfrec, r->xn_w, r->xprev, r->xprev_stride, scf_wave, placed...); };
+        auto front4 = [&](auto kern, auto... placed) { LC3_LAUNCH(kern, dim3((unsigned)c->ncs * (unsigned)((nt + 3) / 4)), dim3(WAVE), 0, c->s_fr, c->d_plan, c->d_chans, c->d_state, q->dpcm, q->bitdepth, n_frames, tb, nt, c->ncs, dspec, c->srow, dT, dt0, dfrec, r->xn_w, r->xprev, r->xprev_stride, placed...); };
+        auto frontm = [&](auto kern, auto... placed) { LC3_LAUNCH(kern, dim3((unsigned)c->ncs * (unsigned)((nt + c->fm_frames - 1) / c->fm_frames)), dim3(WAVE), 0, c->s_fr, c->d_plan, c->d_chans, c->d_state, q->dpcm, q->bitdepth, n_frames, tb, nt, c->fm_frames, c->ncs, dspec, c->srow, dT, dt0, dfrec, r->xn_w, r->xprev, r->xprev_stride, placed...); };
+        auto front = [&](auto kern, auto... placed) { LC3_LAUNCH(kern, dim3((unsigned)c->ncs * (unsigned)((nt + fpw - 1) / fpw)), dim3(WAVE), 0, c->s_fr, c->d_plan, c->d_chans, c->d_state, q->dpcm, q->bitdepth, n_frames, tb, nt, fpw, c->ncs, dspec, c->srow, dT, dt0, dfrec, r->xn_w, r->xprev, r->xprev_stride, scf_wave, placed...); };
         if (f4 && !c->big && !scf_wave && c->N == 480 && c->la == 180 && (c->ylen & 15) == 0) {
             if (q->cnt) { if (q->placed) front4(lc3_enc_front4_kernel_plc_rag, c->plo, c->plcap, q->cnt); else front4(BY_FMT_RAG(q, lc3_enc_front4_kernel), q->cnt); }
             else if (q->placed) front4(lc3_enc_front4_kernel_plc, c->plo, c->plcap); else DUPL('f') front4(BY_FMT(q, lc3_enc_front4_kernel));
@@ -573,9 +631,9 @@ static int enc_run(lc3hip_ctx* c, const enc_call* q, enc_runs* r, int k, int tb,
     if (r->five) HIPCHK(hipStreamWaitEvent(c->s_ln, c->ev_m[k], 0));
     const int fuse_vq = !scf_wave && !c->any_attack && c->opt.fuse_vq;
     const unsigned lanes = (unsigned)(((long long)c->ncs * nt + WAVE - 1) / WAVE);      /* waves of a kernel that takes one frame per lane */
-    auto scf = [&](auto kern, auto... ragged) { hipLaunchKernelGGL(kern, dim3(lanes), dim3(WAVE), 0, c->s_ln, c->d_plan, dT, dt0 + tb, nt, c->ncs, dspec, c->srow, dfrec, fuse_vq, ragged...); };
-    auto attack = [&](auto kern, auto... ragged) { hipLaunchKernelGGL(kern, dim3((unsigned)((c->ncs + WAVE - 1) / WAVE)), dim3(WAVE), 0, c->s_ln, c->d_plan, c->d_chans, c->d_state, c->state_words, LC3D_ST_SCAL(mc), dfrec, dT, dt0, tb, nt, c->ncs, ragged...); };
-    auto snsvq = [&](auto kern, auto... ragged) { hipLaunchKernelGGL(kern, dim3(lanes), dim3(WAVE), 0, c->s_ln, c->d_plan, dfrec, dT, dt0, tb, nt, c->ncs, c->any_attack, ragged...); };
+    auto scf = [&](auto kern, auto... ragged) { LC3_LAUNCH(kern, dim3(lanes), dim3(WAVE), 0, c->s_ln, c->d_plan, dT, dt0 + tb, nt, c->ncs, dspec, c->srow, dfrec, fuse_vq, ragged...); };
+    auto attack = [&](auto kern, auto... ragged) { LC3_LAUNCH(kern, dim3((unsigned)((c->ncs + WAVE - 1) / WAVE)), dim3(WAVE), 0, c->s_ln, c->d_plan, c->d_chans, c->d_state, c->state_words, LC3D_ST_SCAL(mc), dfrec, dT, dt0, tb, nt, c->ncs, ragged...); };
+    auto snsvq = [&](auto kern, auto... ragged) { LC3_LAUNCH(kern, dim3(lanes), dim3(WAVE), 0, c->s_ln, c->d_plan, dfrec, dT, dt0, tb, nt, c->ncs, c->any_attack, ragged...); };
     if (!scf_wave) { if (q->cnt) scf(lc3_enc_scf_lane_kernel_rag, q->cnt); else DUPL('e') scf(lc3_enc_scf_lane_kernel); }
     if (c->any_attack) { if (q->cnt) attack(lc3_enc_attack_kernel_rag, q->cnt); else attack(lc3_enc_attack_kernel); }
     if (!fuse_vq) { if (q->cnt) snsvq(lc3_enc_snsvq_kernel_rag, q->cnt); else DUPL('v') snsvq(lc3_enc_snsvq_kernel); }
@@ -596,8 +654,8 @@ static int enc_run(lc3hip_ctx* c, const enc_call* q, enc_runs* r, int k, int tb,
         const int swave = c->opt.shape_wave;
         if (q->dbw && bw_to(c, ss)) return 1;
         /* one frame per lane, or (LC3PLUS_ENC_SHAPE_WAVE=1) spw frames per wave; with per-frame bandwidths the _vbw twin of either */
-        auto lane = [&](auto kern, auto... bw) { hipLaunchKernelGGL(kern, dim3(lanes), dim3(WAVE), 0, ss, c->d_plan, c->d_chans, dT, dt0 + tb, nt, c->ncs, dspec, c->srow, dfrec, bw...); };
-        auto wave = [&](auto kern, auto... bw) { hipLaunchKernelGGL(kern, dim3((unsigned)c->ncs * sruns), dim3(WAVE), 0, ss, c->d_plan, c->d_chans, dT, dt0 + tb, nt, spw, c->ncs, dspec, c->srow, dfrec, bw...); };
+        auto lane = [&](auto kern, auto... bw) { LC3_LAUNCH(kern, dim3(lanes), dim3(WAVE), 0, ss, c->d_plan, c->d_chans, dT, dt0 + tb, nt, c->ncs, dspec, c->srow, dfrec, bw...); };
+        auto wave = [&](auto kern, auto... bw) { LC3_LAUNCH(kern, dim3((unsigned)c->ncs * sruns), dim3(WAVE), 0, ss, c->d_plan, c->d_chans, dT, dt0 + tb, nt, spw, c->ncs, dspec, c->srow, dfrec, bw...); };
         if (q->cnt) { if (q->dbw) lane(lc3_enc_shape_lane_kernel_vbw_rag, q->dbw, q->cnt); else lane(lc3_enc_shape_lane_kernel_rag, q->cnt); }      /* (never with LC3PLUS_ENC_SHAPE_WAVE: enc_launch) */
         else if (!swave) { if (q->dbw) lane(lc3_enc_shape_lane_kernel_vbw, q->dbw); else DUPL('a') lane(lc3_enc_shape_lane_kernel); }
         else if (q->dbw) wave(lc3_enc_shape_kernel_vbw, q->dbw);
@@ -609,7 +667,7 @@ static int enc_run(lc3hip_ctx* c, const enc_call* q, enc_runs* r, int k, int tb,
     HIPCHK(hipStreamWaitEvent(rs, c->ev_p[k], 0));
     if (k == 0 && c->rate_armed) HIPCHK(hipStreamWaitEvent(rs, c->ev_rate, 0));      /* the rate chain is a chain: behind the previous call's, whichever stream that ran on */
     const int last = tb + nt >= n_frames;            /* behind the last frame of this launch the MDCT memory goes into the state */
-    auto rate = [&](auto kern, auto... ragged) { hipLaunchKernelGGL(kern, dim3((unsigned)((c->ncs + RATE_WG - 1) / RATE_WG)), dim3(RATE_WG * WAVE), 0, rs, c->d_plan, c->d_chans, c->d_state, dT, dt0 + tb, nt, c->ncs, dspec, c->srow, dfrec, r->xn_w, last, ragged...); };
+    auto rate = [&](auto kern, auto... ragged) { LC3_LAUNCH(kern, dim3((unsigned)((c->ncs + RATE_WG - 1) / RATE_WG)), dim3(RATE_WG * WAVE), 0, rs, c->d_plan, c->d_chans, c->d_state, dT, dt0 + tb, nt, c->ncs, dspec, c->srow, dfrec, r->xn_w, last, ragged...); };
     if (q->cnt) rate(lc3_enc_rate_kernel_rag, q->cnt); else if (c->big) rate(lc3_enc_rate_kernel_big); else DUPL('s') rate(lc3_enc_rate_kernel);
     HIPCHK(hipGetLastError());
     r->rs = rs;
@@ -722,7 +780,7 @@ static int enc_writer(lc3hip_ctx* c, const enc_call* q)
     if (big_from) {
         const int fpw = dT < 4 ? dT : 4;
         const unsigned wruns = (unsigned)((dT + fpw - 1) / fpw);
-        hipLaunchKernelGGL(c->big ? lc3_enc_tailw_kernel_big : lc3_enc_tailw_kernel, dim3((unsigned)c->ncs * wruns), dim3(WAVE), 0, ps, c->d_plan, c->d_chans, dT, dT, fpw, c->ncs, rows_for_pack, c->srow, frec_for_pack, q->dout,
+        LC3_LAUNCH(c->big ? lc3_enc_tailw_kernel_big : lc3_enc_tailw_kernel, dim3((unsigned)c->ncs * wruns), dim3(WAVE), 0, ps, c->d_plan, c->d_chans, dT, dT, fpw, c->ncs, rows_for_pack, c->srow, frec_for_pack, q->dout,
                            q->out_stride, c->d_status, big_from);
         HIPCHK(hipGetLastError());
     }
@@ -731,7 +789,7 @@ static int enc_writer(lc3hip_ctx* c, const enc_call* q)
         const dim3 grid((unsigned)((tasks + per_wg - 1) / per_wg)), block(wpg * WAVE);
         const size_t dyn = per_wave * wpg + ((size_t)(c->opt.pack_pad_kb > 0 ? c->opt.pack_pad_kb : 0) << 10);
         const long long* pt = c->pk.on || q->cnt ? c->pk.tab : nullptr;      /* packed output: the _pk twins write each frame at its offset of the call's table (a ragged call always has one: the scan's, or the plan kernel's slots) */
-        auto writer = [&](auto kern, size_t lds, auto... poff) { hipLaunchKernelGGL(kern, grid, block, lds, ps, c->d_plan, c->d_chans, q->ddump, q->dstride, dT, 0, dT, c->ncs, q->dout, pt ? 0 : q->out_stride, c->d_status, rows_for_pack, c->srow, frec_for_pack, big_from, poff...); };
+        auto writer = [&](auto kern, size_t lds, auto... poff) { LC3_LAUNCH(kern, grid, block, lds, ps, c->d_plan, c->d_chans, q->ddump, q->dstride, dT, 0, dT, c->ncs, q->dout, pt ? 0 : q->out_stride, c->d_status, rows_for_pack, c->srow, frec_for_pack, big_from, poff...); };
         if (two) {       /* LC3PLUS_ENC_PACK_SPLIT=1: the writer as two kernels (head, coder) */
             if (pt) { writer(lc3_enc_pack_head_kernel_pk, 0, pt); writer(lc3_enc_pack_code_kernel_pk, dyn, pt); }
             else { writer(lc3_enc_pack_head_kernel, 0); writer(lc3_enc_pack_code_kernel, dyn); }
@@ -886,9 +944,9 @@ static int pack_scan(lc3hip_ctx* c, hipStream_t st, int T, int slot /* the plan 
     const long long n = (long long)c->n_streams * T, nb = (n + PKS_TILE - 1) / PKS_TILE;
     long long* tab = c->d_poff[slot]; long long* bsum = c->d_pbsum + (size_t)slot * PKS_SUMS(c->poff_cap);
     PkSrc q; q.fsz = fsz; q.pend = fsz ? nullptr : pend; q.chans = c->d_chans; q.channels = c->channels; q.order = c->pk.order; q.S = c->n_streams; q.T = T;
-    hipLaunchKernelGGL(lc3_pack_sums_kernel, dim3((unsigned)nb), dim3(PKS_THREADS), 0, st, q, n, bsum);
-    hipLaunchKernelGGL(lc3_pack_base_kernel, dim3(1), dim3(PKS_THREADS), 0, st, bsum, nb, c->pk.total);
-    hipLaunchKernelGGL(lc3_pack_offsets_kernel, dim3((unsigned)nb), dim3(PKS_THREADS), 0, st, q, n, (const long long*)bsum, c->pk.cap, tab, c->pk.offs,
+    LC3_LAUNCH(lc3_pack_sums_kernel, dim3((unsigned)nb), dim3(PKS_THREADS), 0, st, q, n, bsum);
+    LC3_LAUNCH(lc3_pack_base_kernel, dim3(1), dim3(PKS_THREADS), 0, st, bsum, nb, c->pk.total);
+    LC3_LAUNCH(lc3_pack_offsets_kernel, dim3((unsigned)nb), dim3(PKS_THREADS), 0, st, q, n, (const long long*)bsum, c->pk.cap, tab, c->pk.offs,
                        c->pk.fl, plan_flags, plan_nb ? (int32_t*)nullptr : c->pk.nb);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(c->ev_scan, st));
@@ -996,7 +1054,7 @@ static int plan_launch(lc3hip_ctx* c, hipStream_t st)
     if (c->carry_seed && c->chans_armed) HIPCHK(hipStreamWaitEvent(st, c->ev_chans, 0));
     const size_t al = (size_t)c->pl.rates | (size_t)c->pl.bws | (size_t)c->pl.nb | (size_t)c->pl.fl;
     const int vec4 = (T & 3) == 0 && (al & 15) == 0 && (((size_t)c->pl.fl) & 3) == 0;
-    auto plan = [&](auto kern, auto... ragged) { hipLaunchKernelGGL(kern, dim3((unsigned)((c->n_streams + WAVE - 1) / WAVE)), dim3(WAVE), 0, st, c->pl.rule, c->pl.rates, c->pl.bws, T,
+    auto plan = [&](auto kern, auto... ragged) { LC3_LAUNCH(kern, dim3((unsigned)((c->n_streams + WAVE - 1) / WAVE)), dim3(WAVE), 0, st, c->pl.rule, c->pl.rates, c->pl.bws, T,
                        c->n_streams, c->d_carry, c->carry_seed ? (const lc3d_chan*)c->d_chans : (const lc3d_chan*)nullptr, c->d_pfsz[k], c->d_pbw[k], c->pl.nb, c->pl.fl,
                        c->d_pend[k], vec4, ragged...); };
     /* ragged: the clamped counts, and for slotted output the table of slots in this set's offset table (a packed call's scan fills it below) */
@@ -1053,14 +1111,14 @@ extern "C" int lc3hip_encode_rates_device(void* ctx, const void* pcm, int bitdep
     if (enc_launch(c, pcm, bitdepth, n_frames, (uint8_t*)out, out_stride, s, nullptr, n_frames, 0, true, rates_dev || rag ? c->d_pfsz[k] : nullptr,
                    bws_dev ? c->d_pbw[k] : nullptr)) return 1;
     if (c->pl.pending) return 1;                                             /* every path reads the words */
-    auto tail = [&](auto kern, auto... ragged) { hipLaunchKernelGGL(kern, dim3((unsigned)((c->ncs + WAVE - 1) / WAVE)), dim3(WAVE), 0, s, (const int4*)c->d_pend[k], (const lc3d_chan*)c->d_etab,
+    auto tail = [&](auto kern, auto... ragged) { LC3_LAUNCH(kern, dim3((unsigned)((c->ncs + WAVE - 1) / WAVE)), dim3(WAVE), 0, s, (const int4*)c->d_pend[k], (const lc3d_chan*)c->d_etab,
                        c->d_chans, c->channels, c->ncs, rule->dms, rates_dev ? 1 : 0, ragged...); };
     if (rag) tail(lc3_enc_rates_tail_kernel_rag, (const int32_t*)c->d_cnt); else tail(lc3_enc_rates_tail_kernel);
     HIPCHK(hipGetLastError());
     if (placed_mark(c->plo, c->plcap, c->channels, c->N, (long long)c->n_streams * n_frames, flags_dev, LC3D_ENC_FL_PCM_PLACE, s)) return 1;
     if (rag && flags_dev) {      /* last: an absent frame's flags are exactly LC3D_ENC_FL_ABSENT, whatever the scan and the mark above put beside it */
         const long long n = (long long)c->n_streams * n_frames;
-        hipLaunchKernelGGL(lc3_enc_absent_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (const int32_t*)c->d_cnt, n_frames, n, flags_dev);
+        LC3_LAUNCH(lc3_enc_absent_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (const int32_t*)c->d_cnt, n_frames, n, flags_dev);
         HIPCHK(hipGetLastError());
     }
     HIPCHK(hipEventRecord(c->ev1, s));
@@ -1444,8 +1502,8 @@ static int dec_plan(lc3hip_dctx* c, const dec_call* q)
 {
     const long long n = (long long)c->n_streams * q->n_frames;
     const dim3 grid((unsigned)((n + 255) / 256)), block(256);
-    auto packed = [&](auto kern, auto... ragged) { hipLaunchKernelGGL(kern, grid, block, 0, q->s, q->nb_dev, q->offs_dev, q->bfi_dev, c->d_tab, c->tab_n, c->channels, q->cap, q->in_stride, n, c->d_sizes, c->d_bfi, c->d_inval, ragged...); };
-    auto sizes = [&](auto kern, auto... ragged) { hipLaunchKernelGGL(kern, grid, block, 0, q->s, q->nb_dev, q->bfi_dev, c->d_tab, c->tab_n, c->channels, q->in_stride, n, c->d_sizes, c->d_bfi, c->d_inval, ragged...); };
+    auto packed = [&](auto kern, auto... ragged) { LC3_LAUNCH(kern, grid, block, 0, q->s, q->nb_dev, q->offs_dev, q->bfi_dev, c->d_tab, c->tab_n, c->channels, q->cap, q->in_stride, n, c->d_sizes, c->d_bfi, c->d_inval, ragged...); };
+    auto sizes = [&](auto kern, auto... ragged) { LC3_LAUNCH(kern, grid, block, 0, q->s, q->nb_dev, q->bfi_dev, c->d_tab, c->tab_n, c->channels, q->in_stride, n, c->d_sizes, c->d_bfi, c->d_inval, ragged...); };
     if (q->offs_dev) { if (q->cnt) packed(lc3_dec_plan_packed_kernel_rag, c->counts, q->n_frames, c->d_cnt); else packed(lc3_dec_plan_packed_kernel); }
     else if (q->cnt) sizes(lc3_dec_plan_sizes_kernel_rag, c->counts, q->n_frames, c->d_cnt);
     else sizes(lc3_dec_plan_sizes_kernel);
@@ -1476,7 +1534,7 @@ static int dec_parse(lc3hip_dctx* c, const dec_call* q, hipStream_t sp)
     const size_t quarter = (160u << 10) / 4, used = sizeof(ParseLds) + q->per_wave * wpg;
     const size_t pad = c->opt.dec_parse_pad_kb >= 0 ? (size_t)c->opt.dec_parse_pad_kb << 10 : (nw_max || used >= quarter ? 0 : quarter - used);
     /* `at`: where a stream's frames lie - the stride of the dense array, or (the _pk twins) the offsets of packed frames */
-    auto parse = [&](auto kern, auto at) { hipLaunchKernelGGL(kern, dim3((unsigned)((tasks + per_wg - 1) / per_wg)), dim3(wpg * WAVE), q->per_wave * wpg + pad, sp, c->d_plan, c->d_chans, q->din, at, q->dbfi, q->dsizes, c->d_tab, q->n_frames, c->n_streams, nw_max, q->rec_w, q->ws_w, WS_ROW(c->N)); };
+    auto parse = [&](auto kern, auto at) { LC3_LAUNCH(kern, dim3((unsigned)((tasks + per_wg - 1) / per_wg)), dim3(wpg * WAVE), q->per_wave * wpg + pad, sp, c->d_plan, c->d_chans, q->din, at, q->dbfi, q->dsizes, c->d_tab, q->n_frames, c->n_streams, nw_max, q->rec_w, q->ws_w, WS_ROW(c->N)); };
     if (q->offs_dev) parse(nw_max ? lc3_dec_parse_kernel_var_pk : lc3_dec_parse_kernel_g_var_pk, q->offs_dev);
     else parse(q->dsizes ? (nw_max ? lc3_dec_parse_kernel_var : lc3_dec_parse_kernel_g_var) : (nw_max ? lc3_dec_parse_kernel : lc3_dec_parse_kernel_g), q->in_stride);
     HIPCHK(hipGetLastError());
@@ -1500,18 +1558,18 @@ static int dec_chain(lc3hip_dctx* c, const dec_call* q, hipStream_t sp)
         HIPCHK(hipEventRecord(c->ev_par[c->set], sp)); HIPCHK(hipStreamWaitEvent(spl, c->ev_par[c->set], 0));
     } else if (q->ahead) { HIPCHK(hipEventRecord(c->ev_par[c->set], sp)); HIPCHK(hipStreamWaitEvent(s, c->ev_par[c->set], 0)); }
     else if (c->s_plc) HIPCHK(hipStreamWaitEvent(s, c->ev_plc, 0));      /* an ordered call behind ahead calls: the bookkeeping is a chain (the event of the last one, if any: waiting on a fresh event is a no-op) */
-    auto plc = [&](auto kern, auto... ragged) { hipLaunchKernelGGL(kern, dim3((unsigned)((c->ncs + WAVE - 1) / WAVE)), dim3(WAVE), 0, spl, c->d_plan, c->d_chans, q->dsizes, c->d_tab, c->d_state, rec_w, n_frames, c->ncs, ragged...); };
+    auto plc = [&](auto kern, auto... ragged) { LC3_LAUNCH(kern, dim3((unsigned)((c->ncs + WAVE - 1) / WAVE)), dim3(WAVE), 0, spl, c->d_plan, c->d_chans, q->dsizes, c->d_tab, c->d_state, rec_w, n_frames, c->ncs, ragged...); };
     if (cnt) plc(lc3_dec_plc_kernel_rag, cnt); else plc(lc3_dec_plc_kernel);
     HIPCHK(hipGetLastError());
     if (spl != s) { HIPCHK(hipEventRecord(c->ev_plc, spl)); HIPCHK(hipStreamWaitEvent(s, c->ev_plc, 0)); }
     /* the IMDCT: four frames a wave at N = 480 in the standard layout (LC3PLUS_DEC_IMDCT4=0, or a traced call: the kernel below; a ragged call never carries a trace), else runs of IMDCT_FPW frames */
-    auto imdct4 = [&](auto kern, auto... ragged) { hipLaunchKernelGGL(kern, dim3((unsigned)((size_t)c->ncs * ((n_frames + 3) / 4))), dim3(WAVE), 0, s, c->d_plan, c->d_state, rec_w, ws_w, n_frames, c->ncs, c->d_ov, ragged...); };
-    auto imdct = [&](auto kern, auto... ragged) { hipLaunchKernelGGL(kern, dim3((unsigned)((size_t)c->ncs * ((n_frames + IMDCT_FPW - 1) / IMDCT_FPW))), dim3(WAVE), 0, s, c->d_plan, c->d_state, rec_w, ws_w, n_frames, c->ncs, c->d_ov, dtr, ragged...); };
+    auto imdct4 = [&](auto kern, auto... ragged) { LC3_LAUNCH(kern, dim3((unsigned)((size_t)c->ncs * ((n_frames + 3) / 4))), dim3(WAVE), 0, s, c->d_plan, c->d_state, rec_w, ws_w, n_frames, c->ncs, c->d_ov, ragged...); };
+    auto imdct = [&](auto kern, auto... ragged) { LC3_LAUNCH(kern, dim3((unsigned)((size_t)c->ncs * ((n_frames + IMDCT_FPW - 1) / IMDCT_FPW))), dim3(WAVE), 0, s, c->d_plan, c->d_state, rec_w, ws_w, n_frames, c->ncs, c->d_ov, dtr, ragged...); };
     if (!c->big && c->opt.dec_imdct4 && !dtr && c->N == 480) { if (cnt) imdct4(lc3_dec_imdct4_kernel_rag, cnt); else imdct4(lc3_dec_imdct4_kernel); }
     else if (cnt) imdct(c->big ? lc3_dec_imdct_kernel_big_rag : lc3_dec_imdct_kernel_rag, cnt);
     else imdct(c->big ? lc3_dec_imdct_kernel_big : lc3_dec_imdct_kernel);
     /* the synthesis; placed PCM: the _plc twins */
-    auto synth = [&](auto kern, auto... placed_ragged) { hipLaunchKernelGGL(kern, dim3(c->ncs), dim3(WAVE), 0, s, c->d_plan, c->d_state, rec_w, ws_w, c->d_ov, n_frames, q->dpcm, q->bps, c->ncs, q->dst, dtr, placed_ragged...); };
+    auto synth = [&](auto kern, auto... placed_ragged) { LC3_LAUNCH(kern, dim3(c->ncs), dim3(WAVE), 0, s, c->d_plan, c->d_state, rec_w, ws_w, c->d_ov, n_frames, q->dpcm, q->bps, c->ncs, q->dst, dtr, placed_ragged...); };
     if (cnt && c->plo) synth(c->big ? lc3_dec_synth_kernel_big_rag_plc : lc3_dec_synth_kernel_rag_plc, c->plo, c->plcap, cnt);
     else if (cnt) synth(c->big ? lc3_dec_synth_kernel_big_rag : lc3_dec_synth_kernel_rag, cnt);
     else if (c->plo) synth(c->big ? lc3_dec_synth_kernel_big_plc : lc3_dec_synth_kernel_plc, c->plo, c->plcap);
@@ -1526,7 +1584,7 @@ static int dec_tail(lc3hip_dctx* c, const dec_call* q)
     const int n_frames = q->n_frames;
     if (q->nb_dev) {                                                 /* behind the synthesis: the status bits and the stream's configuration for the next call */
         const long long n = (long long)c->n_streams * n_frames;
-        auto tail = [&](auto kern, auto... ragged) { hipLaunchKernelGGL(kern, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, c->d_sizes, c->d_inval, c->d_tab, c->channels, c->n_streams, n_frames, c->d_chans, q->dst, ragged...); };
+        auto tail = [&](auto kern, auto... ragged) { LC3_LAUNCH(kern, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, c->d_sizes, c->d_inval, c->d_tab, c->channels, c->n_streams, n_frames, c->d_chans, q->dst, ragged...); };
         /* the ragged tail also marks the invalid placements, among the present frames only */
         if (q->cnt) tail(lc3_dec_sizes_tail_kernel_rag, q->cnt, c->plo, c->plcap, c->N); else tail(lc3_dec_sizes_tail_kernel);
         HIPCHK(hipGetLastError());

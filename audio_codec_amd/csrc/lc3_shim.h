@@ -112,6 +112,13 @@ int   lc3hip_wait(void* ctx);                                      /* waits for 
 int   lc3hip_dec_wait(void* ctx);
 int   lc3hip_destroy(void* ctx);
 int   lc3hip_test_fastmath(int kind, const float* x_host, float* y_host, long long n);   /* test hook: the device's math over an array (0 log2, 1 log10, 2 2^x through lc3_fastmath.h; 3 pow(2, x), 4 pow(x, i mod 9) through the device library) */
+/* The launch census: which kernel entry points this process has launched through lc3_runtime.hip, and how often.  Process-wide, off by default (a launch then reads
+ * one flag); safe from several host threads.  enable: on != 0 counts from now on; reset: every count to 0; read: the launched kernels as "name count" lines (name: the
+ * kernel's symbol in the code object) into buf, at most cap bytes with the terminating 0, and returns the bytes the whole text needs.  LC3PLUS_LAUNCH_CENSUS=<path>,
+ * read once when the library is loaded, enables it and appends the same lines to <path> when the library is unloaded or the process exits. */
+void  lc3hip_launch_census_enable(int on);
+void  lc3hip_launch_census_reset(void);
+size_t lc3hip_launch_census_read(char* buf, size_t cap);
 #ifdef __cplusplus
 }
 #endif

@@ -324,6 +324,18 @@ def test_soak_every_operating_point():
     assert tot == 24 * 2 * 32 * 36 and bad == 0, (tot, bad)
 
 
+def test_soak_every_operating_point_stereo():
+    """The 24 families in stereo x 1 seed x 16 streams x 20 frames against the oracle's stereo batch entry (tools/soak.py, channels=2): a call of 8 frames and one
+    of 12, so every family - the two of the large layout included - runs the one-wave and the pipelined kernels with two channels; every second stream has an odd
+    stream-frame size in each of the 18 families that are not high-resolution."""
+    import importlib.util
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("soak", os.path.join(root, "tools", "soak.py"))
+    soak = importlib.util.module_from_spec(spec); spec.loader.exec_module(soak)
+    tot, bad = soak.run(1, 16, 20, verbose=False, channels=2)
+    assert tot == 24 * 1 * 16 * 20 and bad == 0, (tot, bad)
+
+
 def test_golden_other_operating_points():
     """the reference's own vectors (tests/golden/c6, generated by make_golden.py) for every family outside 48 kHz / 10 ms"""
     g = np.load(os.path.join(G, "c6_other_operating_points.npz"))

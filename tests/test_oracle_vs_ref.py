@@ -220,6 +220,40 @@ def test_soak_every_operating_point_against_the_reference():
         assert _soak(oracle_encode_streams, fs, ms, hr, rates) == want, (fs, ms, hr)
 
 
+def _stereo_rates(fs, ms, rates):
+    """a stereo stream's total bitrate for each of the first four mono rates: twice the rate, or the next lower one in steps of 800 bit/s whose stream-frame
+    has an even number of bytes (the reference asserts on odd stereo sizes) - twice 500 kbit/s at 5 ms is 625 bytes, and at 44.1 kHz a frame lasts 480 / 441
+    of its nominal length"""
+    N = int(round(48000 * ms / 1000))
+    out = []
+    for r in rates[:4]:
+        r *= 2
+        while (r * N // ((44100 if fs == 44100 else 48000) * 8)) % 2:
+            r -= 800
+        out.append(r)
+    return out
+
+
+def _soak_stereo(Enc, fs, ms, hr, rates):
+    N = int(round((48000 if fs == 44100 else fs) * ms / 1000))
+    pcm = synth_pcm(8, 12, N, fs, seed=4100).reshape(4, 2, 12, N)
+    out = []
+    for s, br in enumerate(_stereo_rates(fs, ms, rates)):
+        e = Enc(fs, 2, ms, hr, br)
+        frames = [e.encode(pcm[s, :, t]) for t in range(12)]
+        assert all(f.size == e.nbytes and f.size % 2 == 0 for f in frames), (fs, ms, hr, br, e.nbytes)
+        out.append(md5(*frames))
+    return out
+
+
+def test_soak_every_operating_point_stereo_against_the_reference():
+    """The restatement's stereo encoder in all 24 families x 4 streams x 12 frames: == the compiled reference, byte for byte.  Even stream-frame sizes only (the
+    reference asserts on odd ones); the odd sizes are the restatement's own split, which the decoder pin above (dec_stereo_size_switch) reads back."""
+    for fs, ms, hr, rates in _soak_every_operating_point_cfgs():
+        want = reference("soak_stereo/%d/%g/%d" % (fs, ms, hr), lambda: _soak_stereo(Ref, fs, ms, hr, rates))
+        assert _soak_stereo(Oracle, fs, ms, hr, rates) == want, (fs, ms, hr)
+
+
 # ----------------------------------------------------------------------------------------------------------------------------------
 # decoder: the chain encoder -> decoder; the restatement's (Oracle, OracleDecoder) against the reference's (Ref, RefDecoder).  The
 # digests cover the frames that went in, the return codes and the PCM that came out.
@@ -410,6 +444,8 @@ def reference_cases():
         yield "dft/%d" % n, _ref_dft(n)
     for fs, ms, hr, rates in _soak_every_operating_point_cfgs():
         yield "soak/%d/%g/%d" % (fs, ms, hr), _soak(ref_encode_streams, fs, ms, hr, rates)
+    for fs, ms, hr, rates in _soak_every_operating_point_cfgs():
+        yield "soak_stereo/%d/%g/%d" % (fs, ms, hr), _soak_stereo(Ref, fs, ms, hr, rates)
     for fs, ms, hr, rates in _soak_cfgs():
         for bi, br in enumerate(rates):
             yield "dec_chain/%d/%g/%d/%d/%d" % (fs, ms, hr, bi, br), _dec_chain(Ref, RefDecoder, fs, ms, hr, bi, br)

@@ -1,5 +1,8 @@
 """Differential soak (GPU box): every operating point x several seeds, GPU frames against the oracle's batch entry (same math).
-Usage: [SOAK_READY=frames_per_call] python tools/soak.py [seeds] [streams] [frames]   -> prints one line per configuration and a total; exit code 1 on any difference."""
+Usage: [SOAK_READY=frames_per_call] python tools/soak.py [seeds] [streams] [frames] [channels]   -> prints one line per configuration and a total; exit code 1 on any
+difference.  channels = 2: stereo streams against the oracle's lc3o_encode_batch16_ch, no bandwidth plan (that entry has none), every second stream at a rate whose
+stream-frame has an odd number of bytes where the family has one (the channels then differ in bytes and channel 1's payload starts at an odd address); calls of 8
+frames and of the rest (one-wave kernels, then the pipelined ones).  No SOAK_READY variant in stereo."""
 import ctypes as C, os, sys, time
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -10,6 +13,7 @@ from lc3_harness import synth_pcm, ORACLE_DIR
 L = C.CDLL(os.path.join(ORACLE_DIR, "liblc3_oracle_pm.so"))
 L.lc3o_encode_batch16.argtypes = [C.c_int, C.c_float, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
 L.lc3o_encode_batch16_bw.argtypes = [C.c_int, C.c_float, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+L.lc3o_encode_batch16_ch.argtypes = [C.c_int, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
 BW = int(os.environ.get("SOAK_BW", "1"))                  # the bandwidth column (E/conformance/lc3_conformance.py:803-817,850-862): band-limited input, set and switched bandwidths
 READY = int(os.environ.get("SOAK_READY", "0"))            # frames per call of the overlapped variant (0: host-pointer calls)
 HIP = C.CDLL("libamdhip64.so") if READY else None
@@ -75,8 +79,47 @@ def configurations():
     return cfg
 
 
-def run(NS, B, T, verbose=True):
-    """returns (frames compared, frames that differ)"""
+def stereo_rate(fs, ms, hr, rate, odd):
+    """the stereo stream's total bitrate for the mono rate of configurations(): twice it, and with odd the next higher rate (steps of 800 bit/s) whose
+    stream-frame has an odd number of bytes by the host rule (api.enc_plan_bitrates, no device); twice the rate again where the family has none in reach"""
+    from audio_codec_amd.api import enc_plan_bitrates, LC3Error
+    if odd:
+        for r in range(2 * rate, 2 * rate + 16000, 800):
+            try:
+                if int(enc_plan_bitrates(fs, 2, ms, hr, [[r]])[0][0, 0]) % 2:
+                    return r
+            except LC3Error:
+                pass
+    return 2 * rate
+
+
+def run_stereo(NS, B, T, verbose=True):
+    """run() for stereo streams: returns (stream-frames compared, stream-frames that differ, families with an odd stream-frame size among their streams)"""
+    tot = bad = odd_families = 0
+    cut = 8 if T > 8 else T // 2
+    for fs, ms, hr, rates in configurations():
+        N = int(round((48000 if fs == 44100 else fs) * ms / 1000))
+        for seed in range(NS):
+            br = np.array([stereo_rate(fs, ms, hr, rates[(i + seed) % len(rates)], i % 2 == 1) for i in range(B)], np.int32)
+            pcm = np.ascontiguousarray(synth_pcm(2 * B, T, N, fs, seed=5000 + 17 * seed).reshape(B, 2, T, N).transpose(0, 2, 1, 3))
+            b = audio_codec_amd.Batch(B, fs, 2, ms, hr, list(map(int, br)), device=0)
+            got = np.concatenate([b.encode(pcm[:, :cut]), b.encode(pcm[:, cut:])], axis=1)
+            want = np.zeros_like(got)
+            rc = L.lc3o_encode_batch16_ch(fs, ms, hr, 2, B, T, br.ctypes.data, pcm.ctypes.data, want.ctypes.data, b.stride)
+            assert rc == 0, rc
+            nb = np.array([b.num_bytes(i) for i in range(B)])
+            odd_families += seed == 0 and bool((nb % 2).any())
+            d = sum(int((got[i, :, :nb[i]] != want[i, :, :nb[i]]).any(axis=1).sum()) for i in range(B))
+            tot += B * T; bad += d
+            if d and verbose: print("%6d Hz %4.1f ms hr%d stereo seed %d: %d of %d frames differ" % (fs, ms, hr, seed, d, B * T))
+            b.close()
+    return tot, bad, odd_families
+
+
+def run(NS, B, T, verbose=True, channels=1):
+    """returns (frames compared, frames that differ); channels = 2: stereo stream-frames (run_stereo)"""
+    if channels == 2:
+        return run_stereo(NS, B, T, verbose)[:2]
     tot = bad = 0
     for fs, ms, hr, rates in configurations():
         N = int(round((48000 if fs == 44100 else fs) * ms / 1000))
@@ -110,7 +153,8 @@ if __name__ == "__main__":
     NS = int(sys.argv[1]) if len(sys.argv) > 1 else 2
     B = int(sys.argv[2]) if len(sys.argv) > 2 else 64
     T = int(sys.argv[3]) if len(sys.argv) > 3 else 48
+    CH = int(sys.argv[4]) if len(sys.argv) > 4 else 1
     t0 = time.time()
-    tot, bad = run(NS, B, T)
+    tot, bad = run(NS, B, T, channels=CH)
     print("soak: %d frames over %d configurations x %d seeds, %d differ, %.0f s" % (tot, len(configurations()), NS, bad, time.time() - t0))
     sys.exit(1 if bad else 0)
