@@ -39,6 +39,7 @@ EXPORTS = [
     "lc3plus_enc_batch_set_pcm_placement", "lc3plus_dec_batch_set_pcm_placement", "lc3plus_pcm_placed_offset", "lc3plus_plan_placed",
     "lc3plus_dec_batch_set_frame_counts", "lc3plus_dec_plan_counts",
     "lc3plus_enc_batch_set_frame_counts", "lc3plus_enc_plan_rates_ragged",
+    "lc3plus_dec_batch_probe", "lc3plus_frame_info_side", "lc3plus_reject_name",
     "lc3plus_shard_block",
     "lc3plus_enc_sharded_create", "lc3plus_enc_sharded_destroy", "lc3plus_enc_sharded_shards", "lc3plus_enc_sharded_shard", "lc3plus_enc_sharded_device",
     "lc3plus_enc_sharded_owner", "lc3plus_enc_sharded_input_samples", "lc3plus_enc_sharded_num_bytes", "lc3plus_enc_sharded_stride",
@@ -67,6 +68,15 @@ DEC_ST_ABSENT = 8
 # ... and Batch.set_frame_counts: the encoder's device flags of an absent frame are exactly this value; nothing read, encoded or written, num_bytes 0
 ENC_FL_ABSENT = 32
 PACK_STREAM_MAJOR, PACK_FRAME_MAJOR = 0, 1
+# the frame probe (DecBatch.probe, frame_info_side; include/lc3plus_batch.h "Frame probe"): depths, the record's words and status bits, the reject reasons
+PROBE_SIDE, PROBE_FULL = 0, 1
+FRAME_INFO_WORDS = 48
+FI_STATUS, FI_REASON, FI_NUM_BYTES, FI_BW_IDX, FI_LASTNZ, FI_LSB_MODE, FI_GG_IDX, FI_FAC_NS, FI_NFILT = range(9)
+FI_TNS_ORDER, FI_TNS_IDX, FI_SCF_IDX, FI_LTPF, FI_NRES = 9, 11, 27, 34, 37
+FI_ST_CONCEALED, FI_ST_INVALID, FI_ST_LOST, FI_ST_SKIPPED = 1, 2, 4, 8
+(REJ_NONE, REJ_BANDWIDTH, REJ_LASTNZ, REJ_SNS_INDEX_25, REJ_SNS_INDEX_24, REJ_TNS_ORDER, REJ_TNS_READER, REJ_TNS_SYMBOL, REJ_OVERLAP, REJ_SPEC_SYMBOL,
+ REJ_ESCAPE_14, REJ_NRES) = range(12)
+REJ_COUNT = 12
 LC3_BW_WARNING = 18
 
 
@@ -208,6 +218,9 @@ def load_library():
         L.lc3plus_plan_placed.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]
         L.lc3plus_dec_batch_set_frame_counts.argtypes = [C.c_void_p, C.c_void_p]
         L.lc3plus_dec_plan_counts.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+        L.lc3plus_dec_batch_probe.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_int]
+        L.lc3plus_frame_info_side.argtypes = [C.c_int, C.c_int, C.c_float, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
+        L.lc3plus_reject_name.argtypes = [C.c_int]; L.lc3plus_reject_name.restype = C.c_char_p
         _LIB = L
     return _LIB
 
@@ -880,6 +893,24 @@ def dec_plan_counts(counts, n_frames):
     return eff
 
 
+def reject_names():
+    """the names of REJ_* by code, as the library gives them (lc3plus_reject_name): ("none", "bandwidth", ...)"""
+    L = load_library()
+    return tuple(L.lc3plus_reject_name(i).decode() for i in range(REJ_COUNT))
+
+
+def frame_info_side(samplerate, channels, frame_ms, hrmode, frame):
+    """The SIDE depth of DecBatch.probe on the host (lc3plus_frame_info_side, no device needed): one stream-frame (bytes, all channels; empty = lost) ->
+    int32 [channels, FRAME_INFO_WORDS]; LC3Error for a geometry the C call refuses."""
+    frame = np.ascontiguousarray(frame, dtype=np.uint8).reshape(-1)
+    info = np.zeros((channels, FRAME_INFO_WORDS), np.int32)
+    rc = load_library().lc3plus_frame_info_side(samplerate, channels, frame_ms, hrmode, frame.ctypes.data if frame.size else None, int(frame.size),
+                                                info.ctypes.data)
+    if rc:
+        raise LC3Error(rc, "lc3plus_frame_info_side")
+    return info
+
+
 class DecBatch(_StreamLifecycle):
     """n_streams independent decoders (lc3plus_dec_batch_*), state resident on the GPU between decode() calls."""
 
@@ -992,6 +1023,46 @@ class DecBatch(_StreamLifecycle):
                                                       1 if sync else 0)
         if rc:
             raise LC3Error(rc, "lc3plus_dec_batch_decode_packed")
+
+    def probe_device(self, d_frames_ptr, frames_capacity, d_offsets_ptr, d_num_bytes_ptr, max_frame_bytes, n_items, d_info_ptr, depth=PROBE_FULL,
+                     hip_stream=None, sync=False):
+        """The frame probe (lc3plus_dec_batch_probe): raw device pointers only - frames frames_capacity bytes, offsets [n_items] int64, num_bytes [n_items]
+        int32, info [n_items, channels, FRAME_INFO_WORDS] int32.  Stateless: nothing of the batch's streams is read or written.  Queued on hip_stream; returns
+        at once unless sync."""
+        def p(x):
+            return C.c_void_p(x) if x else None
+        rc = self.lib.lc3plus_dec_batch_probe(self.h, p(d_frames_ptr), int(frames_capacity), p(d_offsets_ptr), p(d_num_bytes_ptr), int(max_frame_bytes),
+                                              int(n_items), int(depth), p(d_info_ptr), p(hip_stream), 1 if sync else 0)
+        if rc:
+            raise LC3Error(rc, "lc3plus_dec_batch_probe")
+
+    def probe(self, payloads, depth=PROBE_FULL):
+        """Host convenience: a list of stream-frames (bytes or uint8 arrays, all channels; empty = lost) packed back to back, uploaded, probed ->
+        int32 [n, channels, FRAME_INFO_WORDS].  Device memory through the HIP runtime (hipMalloc / hipMemcpy on the current device: the batch's, unless the
+        caller has switched), freed before it returns."""
+        pl = [np.frombuffer(x, np.uint8) if isinstance(x, (bytes, bytearray, memoryview)) else np.ascontiguousarray(x, dtype=np.uint8).reshape(-1)
+              for x in payloads]
+        nb = np.array([x.size for x in pl], np.int32)
+        offs = (np.cumsum(nb, dtype=np.int64) - nb).astype(np.int64)
+        buf = np.concatenate(pl + [np.zeros(4, np.uint8)])            # (never empty)
+        info = np.zeros((len(pl), self.channels, FRAME_INFO_WORDS), np.int32)
+        hip = C.CDLL("libamdhip64.so")
+        ptrs = []
+        try:
+            for a in (buf, offs, nb, info):
+                d = C.c_void_p()
+                if hip.hipMalloc(C.byref(d), C.c_size_t(a.nbytes)) != 0:
+                    raise LC3Error(1, "hipMalloc")
+                ptrs.append(d)
+                if hip.hipMemcpy(d, C.c_void_p(a.ctypes.data), C.c_size_t(a.nbytes), C.c_int(1)) != 0:
+                    raise LC3Error(1, "hipMemcpy")
+            self.probe_device(ptrs[0].value, buf.size - 4, ptrs[1].value, ptrs[2].value, max(int(nb.max()), 1), len(pl), ptrs[3].value, depth, sync=True)
+            if hip.hipMemcpy(C.c_void_p(info.ctypes.data), ptrs[3], C.c_size_t(info.nbytes), C.c_int(2)) != 0:
+                raise LC3Error(1, "hipMemcpy")
+        finally:
+            for d in ptrs:
+                hip.hipFree(d)
+        return info
 
     def decode_traced(self, frames, bfi=None, bps=16):
         frames, T, stride, bfi, pcm, status = self._prep(frames, bfi, bps)

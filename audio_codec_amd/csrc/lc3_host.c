@@ -7,6 +7,10 @@
  * reference evaluates them, and moves buffers.  There is no CPU encode path: without a HIP device every encode
  * call fails with LC3_ERROR.
  */
+#ifndef _GNU_SOURCE
+#define _GNU_SOURCE                 /* dladdr: the frame probe's library is loaded from this library's directory */
+#endif
+#include <dlfcn.h>
 #include <limits.h>
 #include <math.h>
 #include <pthread.h>
@@ -18,6 +22,7 @@
 #include "../../include/lc3plus_batch.h"
 #include "lc3_tables.h"
 #include "lc3_shim.h"
+#include "lc3_probe_shim.h"
 
 #ifndef M_PI
 #define M_PI 3.14159265358979323846
@@ -1766,6 +1771,75 @@ LC3_Error lc3plus_dec_plan_counts(const int32_t* counts, int n_streams, int n_fr
     if (n_streams > 0 && (!counts || !effective)) return LC3_NULL_ERROR;
     for (int s = 0; s < n_streams; s++) effective[s] = lc3d_dec_count_clamp(counts[s], n_frames);
     return LC3_OK;
+}
+/* ---- the frame probe (include/lc3plus_batch.h "Frame probe"; lc3_probe_shim.h) ---- */
+const char* lc3plus_reject_name(int code)
+{
+    static const char* const names[LC3P_REJ_COUNT] = {"none", "bandwidth", "lastnz", "sns_index_25", "sns_index_24", "tns_order", "tns_reader", "tns_symbol",
+                                                      "overlap", "spec_symbol", "escape_14", "nres"};
+    return code >= 0 && code < LC3P_REJ_COUNT ? names[code] : "";
+}
+/* the SIDE depth of the probe on the host: the item rule and lc3p_side, the text the kernels run */
+LC3_Error lc3plus_frame_info_side(int samplerate, int channels, float frame_ms, int hrmode, const uint8_t* frame, int num_bytes, int32_t* info)
+{
+    if (!info || (!frame && num_bytes > 0)) return LC3_NULL_ERROR;
+    geom_t g; lc3d_dchan* tab = NULL; int tab_n = 0;
+    LC3_Error e = dec_hook_table(samplerate, channels, frame_ms, hrmode, &g, &tab, &tab_n);
+    if (e) return e;
+    const int cls = lc3p_item_class(num_bytes, 0, num_bytes > 0 ? num_bytes : 0, num_bytes > 0 ? num_bytes : 1, tab, tab_n, channels);
+    free(tab);
+    memset(info, 0, sizeof(int32_t) * LC3P_WORDS * (size_t)channels);
+    int refused = 0;
+    for (int ch = 0; ch < channels; ch++) {
+        int32_t* r = info + (size_t)ch * LC3P_WORDS;
+        if (cls != LC3D_FRAME_GOOD) { r[LC3P_STATUS] = LC3P_ST_CONCEALED | (cls == LC3D_FRAME_LOST ? LC3P_ST_LOST : LC3P_ST_INVALID); continue; }
+        const int nb = lc3p_chan_bytes(num_bytes, channels, ch);
+        r[LC3P_NBYTES] = nb;
+        if (refused) { r[LC3P_STATUS] = LC3P_ST_CONCEALED | LC3P_ST_SKIPPED; continue; }
+        const uint8_t* end = frame + lc3p_chan_off(num_bytes, ch) + nb;
+        uint32_t v[3] = {0, 0, 0};
+        for (int j = 0; j < LC3P_TAIL_BYTES; j++) v[j >> 2] |= (uint32_t)end[-1 - j] << (8 * (j & 3));
+        int Q = 0;
+        r[LC3P_REASON] = lc3p_side(v[0], v[1], v[2], g.fs_idx, g.bw_bits, g.ylen, g.dms, r, &Q);
+        if (r[LC3P_REASON]) { r[LC3P_STATUS] = LC3P_ST_CONCEALED; refused = 1; }
+    }
+    return LC3_OK;
+}
+/* the sibling library with the probe kernels, loaded once from the directory this library lies in; NULL where it is missing */
+typedef int (*probe_run_fn)(const lc3probe_call*);
+static pthread_once_t probe_once = PTHREAD_ONCE_INIT;
+static probe_run_fn probe_run;
+static void probe_load(void)
+{
+    Dl_info di;
+    char path[4096];
+    if (!dladdr((void*)&probe_load, &di) || !di.dli_fname) return;
+    const char* slash = strrchr(di.dli_fname, '/');
+    const size_t dir = slash ? (size_t)(slash - di.dli_fname) + 1 : 0;
+    static const char name[] = "liblc3plus_probe_hip.so";
+    if (dir + sizeof name > sizeof path) return;
+    memcpy(path, di.dli_fname, dir);
+    memcpy(path + dir, name, sizeof name);
+    void* h = dlopen(path, RTLD_NOW | RTLD_LOCAL);
+    if (!h) { fprintf(stderr, "lc3plus_hip: the frame probe's library is missing: %s\n", dlerror()); return; }
+    probe_run = (probe_run_fn)dlsym(h, "lc3probe_run");
+}
+LC3_Error lc3plus_dec_batch_probe(lc3plus_dec_batch* b, const void* frames, int64_t frames_capacity, const int64_t* offsets, const int32_t* num_bytes,
+                                  int max_frame_bytes, int64_t n_items, int depth, int32_t* info, void* hip_stream, int sync)
+{
+    if (!b || !frames || !offsets || !num_bytes || !info) return LC3_NULL_ERROR;
+    if (n_items <= 0 || max_frame_bytes <= 0 || frames_capacity < 0 || (depth != LC3P_DEPTH_SIDE && depth != LC3P_DEPTH_FULL)) return LC3_ERROR;
+    /* nothing of the batch but these: no stream state, no configuration, no hand-over buffer, and not the record of its last call */
+    lc3probe_call q;
+    memset(&q, 0, sizeof q);
+    void* own = NULL;
+    if (lc3hip_dec_probe_args(b->dev, &q.device, &q.plan, &q.tab, &q.tab_n, &own)) return LC3_ERROR;
+    pthread_once(&probe_once, probe_load);
+    if (!probe_run) return LC3_ERROR;
+    q.channels = b->g.channels; q.ylen = b->g.ylen;
+    q.frames = frames; q.capacity = (long long)frames_capacity; q.offsets = (const long long*)offsets; q.num_bytes = num_bytes; q.max_bytes = max_frame_bytes;
+    q.depth = depth; q.n_items = (long long)n_items; q.info = info; q.stream = hip_stream ? hip_stream : own; q.sync = sync;
+    return probe_run(&q) ? LC3_ERROR : LC3_OK;
 }
 LC3_Error lc3plus_dec_batch_set_input_ready(lc3plus_dec_batch* b, int ready)
 {

@@ -1694,6 +1694,13 @@ extern "C" int lc3hip_dec_set_state(void* ctx, const void* host, size_t bytes)
     return 0;
 }
 extern "C" float lc3hip_dec_last_ms(void* ctx) { return ctx ? ((lc3hip_dctx*)ctx)->last_ms : 0.0f; }
+extern "C" int lc3hip_dec_probe_args(void* ctx, int* device, const lc3d_plan** plan_dev, const lc3d_dchan** tab_dev, int* tab_n, void** stream)
+{
+    lc3hip_dctx* c = (lc3hip_dctx*)ctx;
+    if (!c || !c->d_plan || !c->d_tab) return 1;
+    *device = c->device; *plan_dev = c->d_plan; *tab_dev = c->d_tab; *tab_n = c->tab_n; *stream = (void*)c->stream;
+    return 0;
+}
 extern "C" int lc3hip_dec_destroy(void* ctx)
 {
     lc3hip_dctx* c = (lc3hip_dctx*)ctx;

@@ -47,6 +47,9 @@ int   lc3hip_dec_decode_packed(void* ctx, const void* frames, long long capacity
                                const uint8_t* bfi_dev, int n_frames, void* pcm, int bps, uint8_t* status_dev, void* hip_stream, int sync);
 int   lc3hip_dec_download_chans(void* ctx, lc3d_dchan* chans);    /* waits for the last call, copies the per-channel-stream configuration to chans[ncs] */
 float lc3hip_dec_last_ms(void* ctx);
+/* what the frame probe borrows of a decoder context (lc3_probe_shim.h): its device, the plan and the per-size channel table in device memory - both written once, at
+ * creation - and the context's stream.  Touches nothing. */
+int   lc3hip_dec_probe_args(void* ctx, int* device, const lc3d_plan** plan_dev, const lc3d_dchan** tab_dev, int* tab_n, void** stream);
 int   lc3hip_dec_destroy(void* ctx);
 int   lc3hip_create(void** ctx, const lc3d_plan* plan, int n_streams, int device);
 int   lc3hip_set_template(void* ctx, const float* tmpl);       /* one channel-stream's fresh state row (init_state): kept on the device, every row reset from it */

@@ -475,6 +475,82 @@ LC3_Error lc3plus_dec_batch_set_frame_counts(lc3plus_dec_batch* batch, const int
  * LC3_ERROR for n_streams < 0 or n_frames <= 0. */
 LC3_Error lc3plus_dec_plan_counts(const int32_t* counts, int n_streams, int n_frames, int32_t* effective);
 
+/* ---- Frame probe: what the decoder would do with a frame, and the frame's side information, without decoding ----------------------------------------
+ * A receiver that holds two copies of a packet must pick the one that parses before it commits either to a stream - the decoder is stateful and conceals what
+ * it refuses; a forwarding server that never decodes wants to drop corrupt packets and to read the per-frame side information (bandwidth, global gain as an
+ * activity measure, the LTPF flags, the noise factor).  All of that is in a frame's own bytes.  The probe is a STATELESS call on a decoder batch: it borrows
+ * the batch's device, geometry and per-size channel table and nothing else.  It reads and writes no stream state, no configuration and none of the batch's
+ * buffers: get_state(), num_bytes(stream) and the PCM and status of every later decode call are bit for bit what they are without it.  It is queued on
+ * hip_stream (NULL: the batch's stream), returns at once unless sync, never waits for the device otherwise, and may run on another stream beside a decode call
+ * of the same batch.
+ *
+ *   frames, offsets, num_bytes, info : device pointers.  An ITEM is one stream-frame, all channels; the n_items items are a flat list that has nothing to do with
+ *                     the batch's n_streams.  Item i is read from frames + offsets[i] (int64), num_bytes[i] bytes (int32).
+ *   info            : [n_items][channels][LC3PLUS_FRAME_INFO_WORDS] int32, one record per channel-frame; no byte behind the n_items records is written
+ *   depth           : LC3PLUS_PROBE_SIDE - the side information alone (R/dec_entropy.c:120-270): a few words per channel from the end of its bytes.  Only the
+ *                     side information's own checks can refuse (reasons 1 - 4); a frame whose first failure lies in the coded part READS AS ACCEPTED at this
+ *                     depth.  tns_order holds the two filter flags (0 / 1), tns_idx and nres are 0.
+ *                     LC3PLUS_PROBE_FULL - also the TNS symbols and the whole walk over the spectrum's tuples (R/ari_codec.c:204-509): the verdict is the
+ *                     decoder's, the reason any of the eleven, tns_order the decoded orders, nres the residual bits the decoder ends with.
+ * The item rule is decode_packed()'s frame rule without flags and without a carry: size 0 is LOST; INVALID is a size outside the geometry's limits for any
+ * channel of the split, a size above max_frame_bytes, a negative offset, or offset + size > frames_capacity.  A lost or invalid item is never read; of a good
+ * item only the aligned words that hold one of its bytes are read.  A good item's channels are split from its own size as the decoder splits them.
+ *
+ * The record of a channel-frame (LC3PLUS_FI_*):
+ *   [0] status: 0 = the decoder decodes this channel-frame.  Bit 0 (1): it conceals it - set with every other bit, alone where the bitstream is refused; bit 1
+ *       (2): the item is invalid; bit 2 (4): the item is lost; bit 3 (8): skipped - a later channel behind a refused earlier one, concealed unparsed
+ *       (R/dec_lc3_fl.c:146-160)
+ *   [1] the reason LC3PLUS_REJ_* where the status is exactly 1: the first check that fails in the reference's order (for its three returns on the range
+ *       decoder's error flag: what set the flag first); 0 otherwise.  lc3plus_reject_name() gives the names.
+ *   [2] this channel's byte count (0 for a lost or invalid item)
+ *   [3 ...] bw_idx, lastnz, lsb_mode, gg_idx, fac_ns, nfilt, tns_order[2], tns_idx[16], scf_idx[7], ltpf[3], nres - every word 0 where the status is not 0
+ *   the rest: 0.
+ * Refused calls queue nothing: a NULL batch, frames, offsets, num_bytes or info (LC3_NULL_ERROR); n_items <= 0, max_frame_bytes <= 0, frames_capacity < 0 or a
+ * depth other than the two (LC3_ERROR) - checked in that order, before anything of the batch or the device is touched.  The kernels live in
+ * liblc3plus_probe_hip.so, which this library loads from its own directory on the first probe call: where that file is missing the call returns LC3_ERROR and
+ * nothing else changes.  FULL stages channels of up to 128 bytes in LDS, bounded by ceil(max_frame_bytes / channels): a tight max_frame_bytes keeps that kernel. */
+#define LC3PLUS_PROBE_SIDE 0
+#define LC3PLUS_PROBE_FULL 1
+#define LC3PLUS_FRAME_INFO_WORDS 48
+#define LC3PLUS_FI_STATUS     0
+#define LC3PLUS_FI_REASON     1
+#define LC3PLUS_FI_NUM_BYTES  2
+#define LC3PLUS_FI_BW_IDX     3
+#define LC3PLUS_FI_LASTNZ     4
+#define LC3PLUS_FI_LSB_MODE   5
+#define LC3PLUS_FI_GG_IDX     6
+#define LC3PLUS_FI_FAC_NS     7
+#define LC3PLUS_FI_NFILT      8
+#define LC3PLUS_FI_TNS_ORDER  9       /* 2 words */
+#define LC3PLUS_FI_TNS_IDX    11      /* 16 words */
+#define LC3PLUS_FI_SCF_IDX    27      /* 7 words */
+#define LC3PLUS_FI_LTPF       34      /* 3 words: active flag, pitch present, pitch index */
+#define LC3PLUS_FI_NRES       37
+#define LC3PLUS_FI_ST_CONCEALED 1
+#define LC3PLUS_FI_ST_INVALID   2
+#define LC3PLUS_FI_ST_LOST      4
+#define LC3PLUS_FI_ST_SKIPPED   8
+#define LC3PLUS_REJ_NONE          0
+#define LC3PLUS_REJ_BANDWIDTH     1   /* bandwidth index above the sampling rate's */
+#define LC3PLUS_REJ_LASTNZ        2   /* last non-zero line beyond the coded lines */
+#define LC3PLUS_REJ_SNS_INDEX_25  3   /* SNS joint index out of range, 25-bit form */
+#define LC3PLUS_REJ_SNS_INDEX_24  4   /* SNS joint index out of range, 24-bit form */
+#define LC3PLUS_REJ_TNS_ORDER     5   /* TNS order above the frame length's maximum */
+#define LC3PLUS_REJ_TNS_READER    6   /* the backward reader behind the forward one inside the TNS coefficients */
+#define LC3PLUS_REJ_TNS_SYMBOL    7   /* range-decoder state invalid on a TNS symbol */
+#define LC3PLUS_REJ_OVERLAP       8   /* the two readers overlap by more than 3 bytes inside the spectrum */
+#define LC3PLUS_REJ_SPEC_SYMBOL   9   /* range-decoder state invalid inside the spectrum */
+#define LC3PLUS_REJ_ESCAPE_14     10  /* escape at level 14 */
+#define LC3PLUS_REJ_NRES          11  /* negative residual budget */
+#define LC3PLUS_REJ_COUNT         12
+LC3_Error lc3plus_dec_batch_probe(lc3plus_dec_batch* batch, const void* frames, int64_t frames_capacity, const int64_t* offsets, const int32_t* num_bytes,
+                                  int max_frame_bytes, int64_t n_items, int depth, int32_t* info, void* hip_stream, int sync);
+const char* lc3plus_reject_name(int code);      /* "none", "bandwidth", ... for LC3PLUS_REJ_* 0 .. 11, "" otherwise */
+/* The SIDE depth on the host alone, no device: the same record rule on one stream-frame in host memory (frame: num_bytes bytes; size 0 is lost, a size the
+ * geometry refuses invalid) -> info [channels][LC3PLUS_FRAME_INFO_WORDS].  LC3_NULL_ERROR for a NULL info, or a NULL frame with num_bytes > 0; the geometry's
+ * errors otherwise. */
+LC3_Error lc3plus_frame_info_side(int samplerate, int channels, float frame_ms, int hrmode, const uint8_t* frame, int num_bytes, int32_t* info);
+
 /* ---- Sharded batches: one call drives encoders or decoders on several GPUs ------------------------------------------------------------------
  * Streams are independent, so a sharded batch is n_devices ordinary batches, each owning a contiguous block of the n_streams streams on a device of its
  * own; nothing is exchanged between devices.  Stream indices are GLOBAL (0 ... n_streams - 1) and arrays are laid out over all n_streams exactly as the
