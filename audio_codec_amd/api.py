@@ -40,6 +40,7 @@ EXPORTS = [
     "lc3plus_dec_batch_set_frame_counts", "lc3plus_dec_plan_counts",
     "lc3plus_enc_batch_set_frame_counts", "lc3plus_enc_plan_rates_ragged",
     "lc3plus_dec_batch_probe", "lc3plus_frame_info_side", "lc3plus_reject_name",
+    "lc3plus_dec_batch_ingest", "lc3plus_plan_ingest",
     "lc3plus_shard_block",
     "lc3plus_enc_sharded_create", "lc3plus_enc_sharded_destroy", "lc3plus_enc_sharded_shards", "lc3plus_enc_sharded_shard", "lc3plus_enc_sharded_device",
     "lc3plus_enc_sharded_owner", "lc3plus_enc_sharded_input_samples", "lc3plus_enc_sharded_num_bytes", "lc3plus_enc_sharded_stride",
@@ -77,6 +78,9 @@ FI_ST_CONCEALED, FI_ST_INVALID, FI_ST_LOST, FI_ST_SKIPPED = 1, 2, 4, 8
 (REJ_NONE, REJ_BANDWIDTH, REJ_LASTNZ, REJ_SNS_INDEX_25, REJ_SNS_INDEX_24, REJ_TNS_ORDER, REJ_TNS_READER, REJ_TNS_SYMBOL, REJ_OVERLAP, REJ_SPEC_SYMBOL,
  REJ_ESCAPE_14, REJ_NRES) = range(12)
 REJ_COUNT = 12
+# packet ingest (DecBatch.ingest, plan_ingest; include/lc3plus_batch.h "Packet ingest"): the bits of item_status and the words of a stream's stats
+ING_USED, ING_DUPLICATE, ING_LATE, ING_EARLY, ING_BAD_STREAM, ING_EMPTY, ING_REFUSED, ING_INVALID = 1, 2, 4, 8, 16, 32, 64, 128
+ING_STATS_WORDS = 4
 LC3_BW_WARNING = 18
 
 
@@ -221,6 +225,8 @@ def load_library():
         L.lc3plus_dec_batch_probe.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_int]
         L.lc3plus_frame_info_side.argtypes = [C.c_int, C.c_int, C.c_float, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
         L.lc3plus_reject_name.argtypes = [C.c_int]; L.lc3plus_reject_name.restype = C.c_char_p
+        L.lc3plus_dec_batch_ingest.argtypes = [C.c_void_p, C.c_int64] + [C.c_void_p] * 7 + [C.c_int, C.c_int] + [C.c_void_p] * 7 + [C.c_void_p, C.c_int]
+        L.lc3plus_plan_ingest.argtypes = [C.c_int, C.c_int, C.c_int64] + [C.c_void_p] * 7 + [C.c_int, C.c_int] + [C.c_void_p] * 7
         _LIB = L
     return _LIB
 
@@ -911,6 +917,53 @@ def frame_info_side(samplerate, channels, frame_ms, hrmode, frame):
     return info
 
 
+ING_OPTIONAL = ("next_base", "stats", "item_status")
+
+
+def _ingest_arrays(n_streams, channels, stream, seq, offsets, num_bytes, base, info, floor, n_frames, optional):
+    """the arrays of an ingest call as the C calls take them: (inputs in argument order with None for a NULL one, outputs in argument order likewise)"""
+    stream = np.ascontiguousarray(stream, dtype=np.int32).reshape(-1)
+    n = stream.size
+    def seq32(x):                                                   # sequence numbers as 32-bit words: 0 ... 2^32 - 1 and negative values both fit
+        return (np.asarray(x).astype(np.int64).reshape(-1) & 0xFFFFFFFF).astype(np.uint32).view(np.int32)
+    seq, base = seq32(seq), seq32(base)
+    offsets = np.ascontiguousarray(offsets, dtype=np.int64).reshape(-1)
+    num_bytes = np.ascontiguousarray(num_bytes, dtype=np.int32).reshape(-1)
+    if not (seq.size == offsets.size == num_bytes.size == n) or base.size != n_streams:
+        raise ValueError("stream, seq, offsets and num_bytes hold one entry per item, base one per stream")
+    if info is not None:
+        info = np.ascontiguousarray(info, dtype=np.int32)
+        if info.shape != (n, channels, FRAME_INFO_WORDS):
+            raise ValueError("info must have shape %s, not %s" % ((n, channels, FRAME_INFO_WORDS), info.shape))
+    if floor is not None:
+        floor = np.ascontiguousarray(floor, dtype=np.int32).reshape(-1)
+        if floor.size != n_streams:
+            raise ValueError("floor holds one entry per stream")
+    cells = (max(n_streams, 0), max(int(n_frames), 0))
+    outs = [np.zeros(cells, np.int64), np.zeros(cells, np.int32), np.zeros(cells, np.int32), np.zeros(cells[0], np.int32),
+            np.zeros(cells[0], np.int32) if "next_base" in optional else None,
+            np.zeros((cells[0], ING_STATS_WORDS), np.int32) if "stats" in optional else None,
+            np.zeros(n, np.uint8) if "item_status" in optional else None]
+    return [stream, seq, offsets, num_bytes, info, base, floor], outs
+
+
+ING_OUTPUTS = ("offsets", "num_bytes", "cell_item", "counts", "next_base", "stats", "item_status")
+
+
+def plan_ingest(n_streams, channels, stream, seq, offsets, num_bytes, base, n_frames, seq_bits=16, info=None, floor=None, optional=ING_OPTIONAL):
+    """The rule of DecBatch.ingest on the host (lc3plus_plan_ingest, no device needed): the item list stream / seq / offsets / num_bytes [n], base [n_streams],
+    optional probe records info [n, channels, FRAME_INFO_WORDS] and floor [n_streams] -> dict of offsets (int64), num_bytes, cell_item [n_streams, n_frames],
+    counts, next_base [n_streams], stats [n_streams, ING_STATS_WORDS] and item_status [n] (uint8); those of next_base, stats and item_status not named in
+    `optional` are passed as NULL and come back as None.  LC3Error for arguments the C call refuses."""
+    ins, outs = _ingest_arrays(n_streams, channels, stream, seq, offsets, num_bytes, base, info, floor, n_frames, optional)
+    ptr = lambda a: a.ctypes.data if a is not None and a.size else None
+    rc = load_library().lc3plus_plan_ingest(int(n_streams), int(channels), ins[0].size, *[ptr(a) for a in ins], int(seq_bits), int(n_frames),
+                                            *[ptr(a) for a in outs])
+    if rc:
+        raise LC3Error(rc, "lc3plus_plan_ingest")
+    return dict(zip(ING_OUTPUTS, outs))
+
+
 class DecBatch(_StreamLifecycle):
     """n_streams independent decoders (lc3plus_dec_batch_*), state resident on the GPU between decode() calls."""
 
@@ -1063,6 +1116,50 @@ class DecBatch(_StreamLifecycle):
             for d in ptrs:
                 hip.hipFree(d)
         return info
+
+    def ingest_device(self, n_items, d_stream_ptr, d_seq_ptr, d_offsets_ptr, d_num_bytes_ptr, d_base_ptr, n_frames, d_out_offsets_ptr, d_out_num_bytes_ptr,
+                      d_cell_item_ptr, d_counts_ptr, seq_bits=16, d_info_ptr=None, d_floor_ptr=None, d_next_base_ptr=None, d_stats_ptr=None,
+                      d_item_status_ptr=None, hip_stream=None, sync=False):
+        """Packet ingest (lc3plus_dec_batch_ingest): raw device pointers only - the item list stream, seq, num_bytes [n_items] int32 and offsets [n_items]
+        int64, optional probe records info [n_items, channels, FRAME_INFO_WORDS], base and optional floor [n_streams] int32 -> out_offsets (int64),
+        out_num_bytes, cell_item [n_streams, n_frames], counts [n_streams] and the optional next_base [n_streams], stats [n_streams, ING_STATS_WORDS] and
+        item_status [n_items] uint8.  The tables are what decode_device_packed and set_frame_counts take.  Stateless: nothing of the batch's streams is read
+        or written.  Queued on hip_stream; returns at once unless sync."""
+        def p(x):
+            return C.c_void_p(x) if x else None
+        rc = self.lib.lc3plus_dec_batch_ingest(self.h, int(n_items), p(d_stream_ptr), p(d_seq_ptr), p(d_offsets_ptr), p(d_num_bytes_ptr), p(d_info_ptr),
+                                               p(d_base_ptr), p(d_floor_ptr), int(seq_bits), int(n_frames), p(d_out_offsets_ptr), p(d_out_num_bytes_ptr),
+                                               p(d_cell_item_ptr), p(d_counts_ptr), p(d_next_base_ptr), p(d_stats_ptr), p(d_item_status_ptr), p(hip_stream),
+                                               1 if sync else 0)
+        if rc:
+            raise LC3Error(rc, "lc3plus_dec_batch_ingest")
+
+    def ingest(self, stream, seq, offsets, num_bytes, base, n_frames, seq_bits=16, info=None, floor=None, optional=ING_OPTIONAL):
+        """Host convenience: the arrays of plan_ingest uploaded, ingested on the device and downloaded -> the dict plan_ingest gives.  Device memory through the
+        HIP runtime as in probe(), freed before it returns."""
+        ins, outs = _ingest_arrays(self.n_streams, self.channels, stream, seq, offsets, num_bytes, base, info, floor, n_frames, optional)
+        hip = C.CDLL("libamdhip64.so")
+        ptrs = []
+        try:
+            for a in ins + outs:
+                d = C.c_void_p()                                    # stays NULL for an argument that is None
+                ptrs.append(d)
+                if a is None:
+                    continue
+                if hip.hipMalloc(C.byref(d), C.c_size_t(max(a.nbytes, 4))) != 0:
+                    raise LC3Error(1, "hipMalloc")
+                if hip.hipMemcpy(d, C.c_void_p(a.ctypes.data), C.c_size_t(a.nbytes), C.c_int(1)) != 0:
+                    raise LC3Error(1, "hipMemcpy")
+            v = [d.value for d in ptrs]
+            self.ingest_device(ins[0].size, v[0], v[1], v[2], v[3], v[5], n_frames, v[7], v[8], v[9], v[10], seq_bits, v[4], v[6], v[11], v[12], v[13], sync=True)
+            for a, d in zip(outs, ptrs[7:]):
+                if a is not None and hip.hipMemcpy(C.c_void_p(a.ctypes.data), d, C.c_size_t(a.nbytes), C.c_int(2)) != 0:
+                    raise LC3Error(1, "hipMemcpy")
+        finally:
+            for d in ptrs:
+                if d.value:
+                    hip.hipFree(d)
+        return dict(zip(ING_OUTPUTS, outs))
 
     def decode_traced(self, frames, bfi=None, bps=16):
         frames, T, stride, bfi, pcm, status = self._prep(frames, bfi, bps)

@@ -23,6 +23,7 @@
 #include "lc3_tables.h"
 #include "lc3_shim.h"
 #include "lc3_probe_shim.h"
+#include "lc3_ingest_shim.h"
 
 #ifndef M_PI
 #define M_PI 3.14159265358979323846
@@ -1840,6 +1841,97 @@ LC3_Error lc3plus_dec_batch_probe(lc3plus_dec_batch* b, const void* frames, int6
     q.frames = frames; q.capacity = (long long)frames_capacity; q.offsets = (const long long*)offsets; q.num_bytes = num_bytes; q.max_bytes = max_frame_bytes;
     q.depth = depth; q.n_items = (long long)n_items; q.info = info; q.stream = hip_stream ? hip_stream : own; q.sync = sync;
     return probe_run(&q) ? LC3_ERROR : LC3_OK;
+}
+/* ---- packet ingest (include/lc3plus_batch.h "Packet ingest"; lc3_ingest_shim.h) ---- */
+/* the checks both calls make first, in the header's order */
+static LC3_Error ingest_check(int64_t n_items, const void* stream, const void* seq, const void* offsets, const void* num_bytes, const void* base, int seq_bits,
+                              int n_frames, const void* out_offsets, const void* out_num_bytes, const void* cell_item, const void* counts)
+{
+    if (!stream || !seq || !offsets || !num_bytes || !base || !out_offsets || !out_num_bytes || !cell_item || !counts) return LC3_NULL_ERROR;
+    if (n_items <= 0 || n_items >= LC3I_MAX_ITEMS || n_frames <= 0 || (seq_bits != 16 && seq_bits != 32)) return LC3_ERROR;
+    return LC3_OK;
+}
+/* the rule on the host: the steps of the kernels (lc3_ingest.inc) one after the other, on the text they run */
+LC3_Error lc3plus_plan_ingest(int n_streams, int channels, int64_t n_items, const int32_t* stream, const int32_t* seq, const int64_t* offsets,
+                              const int32_t* num_bytes, const int32_t* info, const int32_t* base, const int32_t* floor, int seq_bits, int n_frames,
+                              int64_t* out_offsets, int32_t* out_num_bytes, int32_t* cell_item, int32_t* counts, int32_t* next_base, int32_t* stats,
+                              uint8_t* item_status)
+{
+    LC3_Error e = ingest_check(n_items, stream, seq, offsets, num_bytes, base, seq_bits, n_frames, out_offsets, out_num_bytes, cell_item, counts);
+    if (e) return e;
+    if (n_streams <= 0 || channels < 1) return LC3_ERROR;
+    uint32_t* key = (uint32_t*)cell_item;
+    for (size_t c = 0; c < (size_t)n_streams * n_frames; c++) key[c] = LC3I_NO_KEY;
+    if (stats) memset(stats, 0, sizeof(int32_t) * LC3I_STATS_WORDS * (size_t)n_streams);
+    for (int64_t i = 0; i < n_items; i++) {
+        int t = 0, rank = 0;
+        const int cls = lc3i_item(stream[i], seq[i], num_bytes[i], info ? info + (size_t)i * channels * LC3I_INFO_WORDS : NULL, channels, n_streams, base, seq_bits,
+                                  n_frames, &t, &rank);
+        if (cls == 0) { uint32_t* k = key + (size_t)stream[i] * n_frames + t; if (lc3i_key(rank, i) < *k) *k = lc3i_key(rank, i); }
+        else if (stats && (cls == LC3I_LATE || cls == LC3I_EARLY)) stats[(size_t)stream[i] * LC3I_STATS_WORDS + (cls == LC3I_LATE ? LC3I_ST_LATE : LC3I_ST_EARLY)]++;
+    }
+    for (int s = 0; s < n_streams; s++) {
+        int top = -1, won = 0;
+        for (int t = 0; t < n_frames; t++) {
+            const size_t c = (size_t)s * n_frames + t;
+            const int32_t w = key[c] == LC3I_NO_KEY ? -1 : (int32_t)(key[c] & LC3I_ITEM_MASK);
+            if (w >= 0) { top = t; won++; }
+            out_offsets[c] = w >= 0 ? offsets[w] : 0; out_num_bytes[c] = w >= 0 ? num_bytes[w] : 0; cell_item[c] = w;
+        }
+        counts[s] = lc3i_count(floor ? floor[s] : 0, n_frames, top);
+        if (next_base) next_base[s] = lc3i_next_base(base[s], counts[s], seq_bits);
+        if (stats) { stats[(size_t)s * LC3I_STATS_WORDS + LC3I_ST_COUNT] = counts[s]; stats[(size_t)s * LC3I_STATS_WORDS + LC3I_ST_GAPS] = counts[s] - won; }
+    }
+    if (item_status)
+        for (int64_t i = 0; i < n_items; i++) {
+            int t = 0, rank = 0;
+            int st = lc3i_item(stream[i], seq[i], num_bytes[i], info ? info + (size_t)i * channels * LC3I_INFO_WORDS : NULL, channels, n_streams, base, seq_bits,
+                               n_frames, &t, &rank);
+            if (st == 0) st = lc3i_candidate_status(rank, i, cell_item[(size_t)stream[i] * n_frames + t]);
+            item_status[i] = (uint8_t)st;
+        }
+    return LC3_OK;
+}
+/* the sibling library with the ingest kernels, loaded as the probe's is; NULL where it is missing */
+typedef int (*ingest_run_fn)(const lc3ingest_call*);
+static pthread_once_t ingest_once = PTHREAD_ONCE_INIT;
+static ingest_run_fn ingest_run;
+static void ingest_load(void)
+{
+    Dl_info di;
+    char path[4096];
+    if (!dladdr((void*)&ingest_load, &di) || !di.dli_fname) return;
+    const char* slash = strrchr(di.dli_fname, '/');
+    const size_t dir = slash ? (size_t)(slash - di.dli_fname) + 1 : 0;
+    static const char name[] = "liblc3plus_ingest_hip.so";
+    if (dir + sizeof name > sizeof path) return;
+    memcpy(path, di.dli_fname, dir);
+    memcpy(path + dir, name, sizeof name);
+    void* h = dlopen(path, RTLD_NOW | RTLD_LOCAL);
+    if (!h) { fprintf(stderr, "lc3plus_hip: the packet ingest's library is missing: %s\n", dlerror()); return; }
+    ingest_run = (ingest_run_fn)dlsym(h, "lc3ingest_run");
+}
+LC3_Error lc3plus_dec_batch_ingest(lc3plus_dec_batch* b, int64_t n_items, const int32_t* stream, const int32_t* seq, const int64_t* offsets,
+                                   const int32_t* num_bytes, const int32_t* info, const int32_t* base, const int32_t* floor, int seq_bits, int n_frames,
+                                   int64_t* out_offsets, int32_t* out_num_bytes, int32_t* cell_item, int32_t* counts, int32_t* next_base, int32_t* stats,
+                                   uint8_t* item_status, void* hip_stream, int sync)
+{
+    if (!b) return LC3_NULL_ERROR;
+    LC3_Error e = ingest_check(n_items, stream, seq, offsets, num_bytes, base, seq_bits, n_frames, out_offsets, out_num_bytes, cell_item, counts);
+    if (e) return e;
+    /* of the batch: its device and stream, n_streams and channels.  No stream state, no configuration, no buffer */
+    lc3ingest_call q;
+    memset(&q, 0, sizeof q);
+    const lc3d_plan* plan = NULL; const lc3d_dchan* tab = NULL; int tab_n = 0;
+    void* own = NULL;
+    if (lc3hip_dec_probe_args(b->dev, &q.device, &plan, &tab, &tab_n, &own)) return LC3_ERROR;
+    pthread_once(&ingest_once, ingest_load);
+    if (!ingest_run) return LC3_ERROR;
+    q.n_streams = b->n_streams; q.channels = b->g.channels; q.seq_bits = seq_bits; q.n_frames = n_frames; q.sync = sync; q.n_items = (long long)n_items;
+    q.stream = stream; q.seq = seq; q.offsets = (const long long*)offsets; q.num_bytes = num_bytes; q.info = info; q.base = base; q.floor = floor;
+    q.out_offsets = (long long*)out_offsets; q.out_num_bytes = out_num_bytes; q.cell_item = cell_item; q.counts = counts; q.next_base = next_base; q.stats = stats;
+    q.item_status = item_status; q.hip_stream = hip_stream ? hip_stream : own;
+    return ingest_run(&q) ? LC3_ERROR : LC3_OK;
 }
 LC3_Error lc3plus_dec_batch_set_input_ready(lc3plus_dec_batch* b, int ready)
 {

@@ -551,6 +551,66 @@ const char* lc3plus_reject_name(int code);      /* "none", "bandwidth", ... for 
  * errors otherwise. */
 LC3_Error lc3plus_frame_info_side(int samplerate, int channels, float frame_ms, int hrmode, const uint8_t* frame, int num_bytes, int32_t* info);
 
+/* ---- Packet ingest: order, de-duplicate and gap-mark packets on the device -----------------------------------------------------------------------------
+ * The probe takes a flat list of items in arrival order - any offsets, any order, duplicates, copies of one packet; decode_packed() takes tables indexed
+ * [stream][frame], size 0 for a lost frame, and a count per stream (set_frame_counts).  The ingest call turns the first into the second in device memory, so
+ * that probe -> ingest -> set_frame_counts + decode_packed runs on one HIP stream with no host wait in between.
+ *
+ * Every pointer but `batch` is a device pointer; the inputs are read when the kernels run, so the probe call queued before on the same stream may produce `info`.
+ * The call is STATELESS, like the probe: it borrows the batch's device, n_streams and channels and nothing else.  No stream state, configuration or buffer of
+ * the batch is read or written, it allocates nothing, and it may run beside a decode call.  It is queued on hip_stream (NULL: the batch's stream) and returns
+ * at once unless sync.  No output may overlap an input or another output (next_base must not overlap base).  On a shard's batch
+ * (lc3plus_dec_sharded_shard) the call works as on any batch, with that shard's n_streams and LOCAL stream indices; nothing else is needed for sharded batches.
+ *
+ *   stream, seq, offsets, num_bytes : [n_items] the stream index, sequence number, byte offset (int64, as the probe takes it) and size of each item
+ *   info      : the probe's records of the same items [n_items][channels][LC3PLUS_FRAME_INFO_WORDS], or NULL; only each record's status word is read
+ *   base      : [n_streams] the sequence number of frame 0 of the coming decode call
+ *   floor     : [n_streams] or NULL: frames the stream must advance by at least (a play-out deadline: what has not arrived by now is lost)
+ *   seq_bits  : 16 (RTP) or 32: sequence numbers wrap at 2^seq_bits
+ *   out_offsets, out_num_bytes, cell_item : [n_streams][n_frames]; the first two are decode_packed()'s offsets and num_bytes.  cell_item is also the call's
+ *               workspace
+ *   counts    : [n_streams], what set_frame_counts takes
+ *   next_base, stats [n_streams][4], item_status [n_items] : each may be NULL
+ *
+ * Per item i, in this order:
+ *   1. stream[i] outside [0, n_streams): BAD_STREAM.
+ *   2. num_bytes[i] == 0: EMPTY.  With info, an item also counts as EMPTY if any of its channels' status has LC3PLUS_FI_ST_LOST.
+ *   3. The slot distance d = sign_extend((seq[i] - base[s]) mod 2^seq_bits, seq_bits).  d < 0: LATE.  d >= n_frames: EARLY.  Otherwise the item is a candidate
+ *      for cell (s, t = d) with a rank: without info 0; with info 0 if every channel's status word is 0 (the decoder decodes it), 2 if any channel has
+ *      LC3PLUS_FI_ST_INVALID, 1 otherwise (refused by the bitstream checks).
+ * Per cell: the winner is the candidate with the smallest (rank, i) - an accepted copy beats a refused one wherever it sits in the list, among equals the
+ *   earliest item wins, and the result is deterministic.  A cell with a winner w gets out_offsets = offsets[w], out_num_bytes = num_bytes[w], cell_item = w: a
+ *   refused or invalid sole copy is handed to the decoder as it is, which then does with it exactly what decode_packed() does today.  A cell without a winner
+ *   gets out_offsets = 0, out_num_bytes = 0 (lost) and cell_item = -1.
+ * Per stream: counts[s] = max(min(max(floor[s], 0), n_frames), 1 + highest t with a winner) - 0 where there is neither a floor nor a winner;
+ *   next_base[s] = (base[s] + counts[s]) mod 2^seq_bits; stats[s] = {counts[s], cells t < counts[s] without a winner, LATE items, EARLY items}.
+ * item_status[i] carries exactly one of USED, DUPLICATE (a candidate whose cell another item won), LATE, EARLY, BAD_STREAM, EMPTY, and on a USED or DUPLICATE
+ *   item also REFUSED (rank 1) or INVALID (rank 2).
+ *
+ * Refused calls queue nothing, checked in this order before anything of the batch or the device is touched: a NULL batch, stream, seq, offsets, num_bytes,
+ * base, out_offsets, out_num_bytes, cell_item or counts (LC3_NULL_ERROR); n_items <= 0, n_items >= 2^29, n_frames <= 0 or a seq_bits other than 16 and 32
+ * (LC3_ERROR).  The kernels live in liblc3plus_ingest_hip.so, which this library loads from its own directory on the first ingest call: where that file is
+ * missing the call returns LC3_ERROR and nothing else changes. */
+#define LC3PLUS_ING_USED        1
+#define LC3PLUS_ING_DUPLICATE   2
+#define LC3PLUS_ING_LATE        4
+#define LC3PLUS_ING_EARLY       8
+#define LC3PLUS_ING_BAD_STREAM  16
+#define LC3PLUS_ING_EMPTY       32
+#define LC3PLUS_ING_REFUSED     64
+#define LC3PLUS_ING_INVALID     128
+#define LC3PLUS_ING_STATS_WORDS 4
+LC3_Error lc3plus_dec_batch_ingest(lc3plus_dec_batch* batch, int64_t n_items, const int32_t* stream, const int32_t* seq, const int64_t* offsets,
+                                   const int32_t* num_bytes, const int32_t* info, const int32_t* base, const int32_t* floor, int seq_bits, int n_frames,
+                                   int64_t* out_offsets, int32_t* out_num_bytes, int32_t* cell_item, int32_t* counts, int32_t* next_base, int32_t* stats,
+                                   uint8_t* item_status, void* hip_stream, int sync);
+/* The same rule on the host alone, no device: the same arrays in host memory, n_streams and channels given instead of a batch.  The refusals of the call above
+ * in its order, then LC3_ERROR for n_streams <= 0 or channels < 1. */
+LC3_Error lc3plus_plan_ingest(int n_streams, int channels, int64_t n_items, const int32_t* stream, const int32_t* seq, const int64_t* offsets,
+                              const int32_t* num_bytes, const int32_t* info, const int32_t* base, const int32_t* floor, int seq_bits, int n_frames,
+                              int64_t* out_offsets, int32_t* out_num_bytes, int32_t* cell_item, int32_t* counts, int32_t* next_base, int32_t* stats,
+                              uint8_t* item_status);
+
 /* ---- Sharded batches: one call drives encoders or decoders on several GPUs ------------------------------------------------------------------
  * Streams are independent, so a sharded batch is n_devices ordinary batches, each owning a contiguous block of the n_streams streams on a device of its
  * own; nothing is exchanged between devices.  Stream indices are GLOBAL (0 ... n_streams - 1) and arrays are laid out over all n_streams exactly as the
