@@ -735,6 +735,22 @@ def enc_plan_bitrates_for(batch, bitrates):
     return enc_plan_bitrates(batch.samplerate, batch.channels, batch.frame_ms, batch.hrmode, bitrates)[0]
 
 
+PLAN_CHAN_WORDS = ("total_bits", "target_bits_init", "lpc_weighting", "ltpf_enable", "gg_off", "attack_handling", "reg_bits",
+                   "dec_lpc_weighting", "dec_gg_off", "dec_ltpf_beta_idx")
+
+
+def plan_chan(samplerate, frame_ms, hrmode, nbytes):
+    """What a channel of nbytes bytes is configured with (test hook lc3plus_plan_chan, no device needed): {word: value} for PLAN_CHAN_WORDS - the encoder's
+    derive_chan and the decoder's derive_dchan, the rules behind every size threshold.  Raises LC3Error (LC3_NUMBYTES_ERROR) for a size outside the range."""
+    L = load_library()
+    L.lc3plus_plan_chan.argtypes = [C.c_int, C.c_float, C.c_int, C.c_int, C.c_void_p]
+    out = np.zeros(len(PLAN_CHAN_WORDS), dtype=np.int32)
+    rc = L.lc3plus_plan_chan(samplerate, frame_ms, hrmode, int(nbytes), out.ctypes.data)
+    if rc:
+        raise LC3Error(rc, "lc3plus_plan_chan")
+    return dict(zip(PLAN_CHAN_WORDS, (int(x) for x in out)))
+
+
 def enc_plan_bandwidths(samplerate, frame_ms, hrmode, start, bandwidths):
     """The per-frame bandwidth rule of Batch.encode(bandwidths=...) on the host (lc3plus_enc_plan_bandwidths, no device needed): start [n_streams]
     the bandwidth in force before the call, bandwidths [n_streams, n_frames] (or [n_frames] for one stream) -> (in_force int32 [n_streams, n_frames],

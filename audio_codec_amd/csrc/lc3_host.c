@@ -1339,6 +1339,30 @@ static LC3_Error derive_dstream(const geom_t* g, int num_bytes, lc3d_dchan* d /*
     return LC3_OK;
 }
 
+/* test hook: what a channel of nbytes bytes is configured with, without a device - derive_chan's words (encoder) and derive_dchan's (decoder), the rules
+ * every kernel's per-size behaviour comes from.  out[10]: total_bits, target_bits_init, lpc_weighting, ltpf_enable, gg_off, attack_handling, reg_bits,
+ * and the decoder's lpc_weighting, gg_off, ltpf_beta_idx.  LC3_NUMBYTES_ERROR for a size the decoder refuses. */
+LC3_Error lc3plus_plan_chan(int samplerate, float frame_ms, int hrmode, int nbytes, int* out)
+{
+    if (!out) return LC3_NULL_ERROR;
+    if (!samplerate_ok(samplerate)) return LC3_SAMPLERATE_ERROR;
+    { int d = (int)ceil(frame_ms * 10); if (d != 25 && d != 50 && d != 100) return LC3_FRAMEMS_ERROR; }
+    if (samplerate < 48000 && hrmode != 0) return LC3_SAMPLERATE_ERROR;
+    geom_t g;
+    geom_init(&g, samplerate, 1);
+    g.dms = (int)(frame_ms * 10); g.frame_ms = frame_ms; g.hrmode = hrmode > 0;
+    geom_update(&g);
+    lc3d_chan s; lc3d_dchan d;
+    memset(&s, 0, sizeof s); memset(&d, 0, sizeof d);
+    const LC3_Error e = derive_dchan(&g, nbytes, &d);
+    if (e) return e;
+    derive_chan(&g, nbytes, &s);
+    const int v[10] = {s.total_bits, s.target_bits_init, s.lpc_weighting, s.ltpf_enable, s.gg_off, s.attack_handling, s.reg_bits,
+                       d.lpc_weighting, d.gg_off, d.ltpf_beta_idx};
+    memcpy(out, v, sizeof v);
+    return LC3_OK;
+}
+
 /* per-frame sizes: the configuration of every channel byte count 0 .. max, from derive_dchan (entry 0 and the sizes it rejects: zeroed, which is what a
  * channel created without a size has).  An entry is valid where its nbytes equals its index and is not 0. */
 static int dec_max_chan_bytes(const geom_t* g) { return g->hrmode ? (g->dms == 25 ? 210 : g->dms == 50 ? 375 : 625) : 400; }

@@ -67,15 +67,18 @@ def encode_ready(b, pcm, tc):
 
 
 def configurations():
+    def top(fs, ms):                                      # the family's largest bitrate: 400 bytes a frame (bitrate_limits in lc3_host.c, R/setup_enc_lc3.c:196-230)
+        return 3200 * int(round(1000 / ms)) * (441 if fs == 44100 else 480) // 480
     cfg = []
     for fs in (8000, 16000, 24000, 32000, 44100, 48000):
         for ms in (10.0, 5.0, 2.5):
             lo = {10.0: 16000 if fs != 44100 else 32000, 5.0: 32000, 2.5: 64000}[ms]
-            cfg.append((fs, ms, 0, [lo, 2 * lo, 3 * lo, 4 * lo, 6 * lo, 320000 if fs != 44100 else 256000]))
+            old = 320000 if fs != 44100 else 256000
+            cfg.append((fs, ms, 0, [lo, 2 * lo, 3 * lo, 4 * lo, 6 * lo, old] + [top(fs, ms)] * (top(fs, ms) != old)))
     for ms, lo in ((10.0, 124800), (5.0, 148800), (2.5, 172800)):
-        cfg.append((48000, ms, 1, [lo, 256000, 400000, 500000]))
+        cfg.append((48000, ms, 1, [lo, 256000, 400000, 500000] + {10.0: [], 5.0: [600000], 2.5: [672000]}[ms]))
     for ms, lo in ((10.0, 149600), (5.0, 174400), (2.5, 198400)):
-        cfg.append((96000, ms, 1, [lo, 256000, 400000, 500000]))
+        cfg.append((96000, ms, 1, [lo, 256000, 400000, 500000] + {10.0: [], 5.0: [600000], 2.5: [672000]}[ms]))
     return cfg
 
 
