@@ -41,6 +41,7 @@ EXPORTS = [
     "lc3plus_enc_batch_set_frame_counts", "lc3plus_enc_plan_rates_ragged",
     "lc3plus_dec_batch_probe", "lc3plus_frame_info_side", "lc3plus_reject_name",
     "lc3plus_dec_batch_ingest", "lc3plus_plan_ingest",
+    "lc3plus_enc_batch_egress", "lc3plus_dec_batch_egress", "lc3plus_plan_egress", "lc3plus_egress_work_bytes",
     "lc3plus_shard_block",
     "lc3plus_enc_sharded_create", "lc3plus_enc_sharded_destroy", "lc3plus_enc_sharded_shards", "lc3plus_enc_sharded_shard", "lc3plus_enc_sharded_device",
     "lc3plus_enc_sharded_owner", "lc3plus_enc_sharded_input_samples", "lc3plus_enc_sharded_num_bytes", "lc3plus_enc_sharded_stride",
@@ -81,6 +82,10 @@ REJ_COUNT = 12
 # packet ingest (DecBatch.ingest, plan_ingest; include/lc3plus_batch.h "Packet ingest"): the bits of item_status and the words of a stream's stats
 ING_USED, ING_DUPLICATE, ING_LATE, ING_EARLY, ING_BAD_STREAM, ING_EMPTY, ING_REFUSED, ING_INVALID = 1, 2, 4, 8, 16, 32, 64, 128
 ING_STATS_WORDS = 4
+# packet egress (Batch.egress, DecBatch.egress, plan_egress; include/lc3plus_batch.h "Packet egress"): the bits of cell_status, of pkt_flags, the words of a route's stats
+EGR_SENT, EGR_LOST, EGR_INVALID, EGR_SKIPPED, EGR_ABSENT, EGR_BAD_ROUTE, EGR_OVERFLOW = 1, 2, 4, 8, 16, 32, 64
+EGR_PKT_OVERFLOW = 1
+EGR_STATS_WORDS = 4
 LC3_BW_WARNING = 18
 
 
@@ -227,6 +232,12 @@ def load_library():
         L.lc3plus_reject_name.argtypes = [C.c_int]; L.lc3plus_reject_name.restype = C.c_char_p
         L.lc3plus_dec_batch_ingest.argtypes = [C.c_void_p, C.c_int64] + [C.c_void_p] * 7 + [C.c_int, C.c_int] + [C.c_void_p] * 7 + [C.c_void_p, C.c_int]
         L.lc3plus_plan_ingest.argtypes = [C.c_int, C.c_int, C.c_int64] + [C.c_void_p] * 7 + [C.c_int, C.c_int] + [C.c_void_p] * 7
+        egr = ([C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                C.c_void_p, C.c_int64, C.c_int, C.c_int] + [C.c_void_p] * 11 + [C.c_void_p, C.c_void_p, C.c_int])
+        L.lc3plus_enc_batch_egress.argtypes = [C.c_void_p] + egr
+        L.lc3plus_dec_batch_egress.argtypes = [C.c_void_p] + egr
+        L.lc3plus_plan_egress.argtypes = [C.c_int] + egr
+        L.lc3plus_egress_work_bytes.argtypes = [C.c_int, C.c_int]; L.lc3plus_egress_work_bytes.restype = C.c_int64
         _LIB = L
     return _LIB
 
@@ -364,6 +375,138 @@ def _stream_list(streams):
     return np.ascontiguousarray(np.atleast_1d(np.asarray(streams)), dtype=np.int32)
 
 
+EGR_OPTIONAL = ("pkt_flags", "wire_total", "next_seq", "stats", "cell_status")
+EGR_OUTPUTS = ("pkt_route", "pkt_seq", "pkt_frame", "pkt_offset", "pkt_size", "pkt_flags", "n_packets", "wire_total", "next_seq", "stats", "cell_status")
+
+
+def egress_work_bytes(n_routes, n_frames):
+    """bytes of the workspace of an egress call (lc3plus_egress_work_bytes); 0 for a shape the calls refuse"""
+    return int(load_library().lc3plus_egress_work_bytes(int(n_routes), int(n_frames)))
+
+
+def _egress_arrays(n_streams, frames, offsets, num_bytes, seq_base, flags, counts, route_src, wire, optional):
+    """the arrays of an egress call as the C calls take them: (inputs by name, None for a NULL one; outputs in EGR_OUTPUTS order likewise; work)"""
+    frames = np.ascontiguousarray(frames, dtype=np.uint8).reshape(-1)
+    offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+    num_bytes = np.ascontiguousarray(num_bytes, dtype=np.int32)
+    if offsets.ndim != 2 or offsets.shape != num_bytes.shape or offsets.shape[0] != n_streams:
+        raise ValueError("offsets and num_bytes must have shape [n_streams, n_frames]")
+    T = offsets.shape[1]
+    seq_base = (np.asarray(seq_base).astype(np.int64).reshape(-1) & 0xFFFFFFFF).astype(np.uint32).view(np.int32)       # 0 ... 2^32 - 1 and negative values both fit
+    R = seq_base.size
+    if flags is not None:
+        flags = np.ascontiguousarray(flags, dtype=np.uint8)
+        if flags.shape != offsets.shape:
+            raise ValueError("flags must have the shape of offsets")
+    if counts is not None:
+        counts = np.ascontiguousarray(counts, dtype=np.int32).reshape(-1)
+        if counts.size != n_streams:
+            raise ValueError("counts holds one entry per stream")
+    if route_src is not None:
+        route_src = np.ascontiguousarray(route_src, dtype=np.int32).reshape(-1)
+        if route_src.size != R:
+            raise ValueError("route_src and seq_base hold one entry per route")
+    if wire is not None:
+        wire = np.array(wire, dtype=np.uint8).reshape(-1)             # a copy: the call's wire buffer starts with these contents
+    n = R * T
+    ins = dict(frames=frames, offsets=offsets, num_bytes=num_bytes, flags=flags, counts=counts, route_src=route_src, seq_base=seq_base, wire=wire)
+    outs = [np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros(n, np.int64), np.zeros(n, np.int32),
+            np.zeros(n, np.uint8) if "pkt_flags" in optional else None, np.zeros(1, np.int64), np.zeros(1, np.int64) if "wire_total" in optional else None,
+            np.zeros(R, np.int32) if "next_seq" in optional else None, np.zeros((R, EGR_STATS_WORDS), np.int32) if "stats" in optional else None,
+            np.zeros((R, T), np.uint8) if "cell_status" in optional else None]
+    work = np.zeros(max(egress_work_bytes(R, T), 8) // 8, np.int64)
+    return ins, outs, work
+
+
+def _egress_result(ins, outs):
+    r = dict(zip(EGR_OUTPUTS, outs))
+    r["n_packets"] = int(r["n_packets"][0])
+    r["wire_total"] = int(r["wire_total"][0]) if r["wire_total"] is not None else None
+    r["wire"] = ins["wire"]
+    return r
+
+
+def plan_egress(n_streams, frames, offsets, num_bytes, seq_base, max_frame_bytes, flags=None, skip_mask=0, counts=None, route_src=None, seq_bits=16,
+                order=PACK_STREAM_MAJOR, wire=None, wire_capacity=None, header_room=0, align=1, optional=EGR_OPTIONAL, frames_capacity=None):
+    """The rule of Batch.egress / DecBatch.egress on the host (lc3plus_plan_egress, no device needed): frames (uint8, frames_capacity bytes of it: all by
+    default), offsets (int64) / num_bytes [n_streams, n_frames], seq_base [n_routes]; optional flags [n_streams, n_frames] with skip_mask, counts [n_streams],
+    route_src [n_routes]; wire: None (in place) or the wire buffer's contents before the call (uint8; wire_capacity bytes of it: all by default).
+    -> dict of the list arrays pkt_route, pkt_seq, pkt_frame, pkt_offset (int64), pkt_size, pkt_flags (uint8) [n_routes * n_frames] (zero behind n_packets),
+    n_packets, wire_total (ints), next_seq [n_routes], stats [n_routes, EGR_STATS_WORDS], cell_status [n_routes, n_frames] (uint8) and wire (the buffer after
+    the call, or None); the outputs of EGR_OPTIONAL not named in `optional` are passed as NULL and come back as None.  LC3Error for arguments the C call
+    refuses."""
+    ins, outs, work = _egress_arrays(n_streams, frames, offsets, num_bytes, seq_base, flags, counts, route_src, wire, optional)
+    ptr = lambda a: a.ctypes.data if a is not None else None
+    fcap = ins["frames"].size if frames_capacity is None else int(frames_capacity)
+    wcap = (ins["wire"].size if ins["wire"] is not None else 0) if wire_capacity is None else int(wire_capacity)
+    pad = np.zeros(8, np.uint8)                                       # an empty array still has to be a pointer
+    rc = load_library().lc3plus_plan_egress(
+        int(n_streams), ins["offsets"].shape[1], ptr(ins["frames"] if ins["frames"].size else pad), fcap, ptr(ins["offsets"]), ptr(ins["num_bytes"]),
+        int(max_frame_bytes), ptr(ins["flags"]), int(skip_mask), ptr(ins["counts"]), ins["seq_base"].size, ptr(ins["route_src"]), ptr(ins["seq_base"]),
+        int(seq_bits), int(order), ptr(ins["wire"]), wcap, int(header_room), int(align), *[ptr(a) for a in outs], ptr(work), None, 0)
+    if rc:
+        raise LC3Error(rc, "lc3plus_plan_egress")
+    return _egress_result(ins, outs)
+
+
+class _Egress:
+    """Packet egress of both batch kinds (lc3plus_{enc,dec}_batch_egress; include/lc3plus_batch.h "Packet egress")."""
+
+    def egress_device(self, n_frames, d_frames_ptr, frames_capacity, d_offsets_ptr, d_num_bytes_ptr, max_frame_bytes, n_routes, d_seq_base_ptr, d_pkt_route_ptr,
+                      d_pkt_seq_ptr, d_pkt_frame_ptr, d_pkt_offset_ptr, d_pkt_size_ptr, d_n_packets_ptr, d_work_ptr, d_flags_ptr=None, skip_mask=0,
+                      d_counts_ptr=None, d_route_src_ptr=None, seq_bits=16, order=PACK_STREAM_MAJOR, d_wire_ptr=None, wire_capacity=0, header_room=0, align=1,
+                      d_pkt_flags_ptr=None, d_wire_total_ptr=None, d_next_seq_ptr=None, d_stats_ptr=None, d_cell_status_ptr=None, hip_stream=None, sync=False):
+        """Raw device pointers only - the tables offsets (int64), num_bytes, optional flags [n_streams, n_frames] and counts [n_streams] of the frames in `frames`,
+        the routes seq_base and optional route_src [n_routes] -> the packet list pkt_* [n_routes * n_frames], n_packets and the optional wire_total (one int64
+        each), next_seq [n_routes], stats [n_routes, EGR_STATS_WORDS], cell_status [n_routes, n_frames]; with d_wire_ptr the frames are copied there behind
+        header_room bytes each.  work: egress_work_bytes(n_routes, n_frames) bytes.  Stateless: nothing of the batch's streams is read or written.  Queued on
+        hip_stream; returns at once unless sync."""
+        def p(x):
+            return C.c_void_p(x) if x else None
+        rc = self._ssf("_egress")(self.h, int(n_frames), p(d_frames_ptr), int(frames_capacity), p(d_offsets_ptr), p(d_num_bytes_ptr), int(max_frame_bytes),
+                                  p(d_flags_ptr), int(skip_mask), p(d_counts_ptr), int(n_routes), p(d_route_src_ptr), p(d_seq_base_ptr), int(seq_bits), int(order),
+                                  p(d_wire_ptr), int(wire_capacity), int(header_room), int(align), p(d_pkt_route_ptr), p(d_pkt_seq_ptr), p(d_pkt_frame_ptr),
+                                  p(d_pkt_offset_ptr), p(d_pkt_size_ptr), p(d_pkt_flags_ptr), p(d_n_packets_ptr), p(d_wire_total_ptr), p(d_next_seq_ptr),
+                                  p(d_stats_ptr), p(d_cell_status_ptr), p(d_work_ptr), p(hip_stream), 1 if sync else 0)
+        if rc:
+            raise LC3Error(rc, self._ss + "_egress")
+
+    def egress(self, frames, offsets, num_bytes, seq_base, max_frame_bytes, flags=None, skip_mask=0, counts=None, route_src=None, seq_bits=16,
+               order=PACK_STREAM_MAJOR, wire=None, wire_capacity=None, header_room=0, align=1, optional=EGR_OPTIONAL, frames_capacity=None):
+        """Host convenience: the arrays of plan_egress uploaded, the egress run on the device and downloaded -> the dict plan_egress gives.  Device memory through
+        the HIP runtime (hipMalloc / hipMemcpy on the current device: the batch's, unless the caller has switched), freed before it returns."""
+        ins, outs, work = _egress_arrays(self.n_streams, frames, offsets, num_bytes, seq_base, flags, counts, route_src, wire, optional)
+        fcap = ins["frames"].size if frames_capacity is None else int(frames_capacity)
+        wcap = (ins["wire"].size if ins["wire"] is not None else 0) if wire_capacity is None else int(wire_capacity)
+        hip = C.CDLL("libamdhip64.so")
+        names = ("frames", "offsets", "num_bytes", "flags", "counts", "route_src", "seq_base", "wire")
+        arrays = [ins[k] for k in names] + outs + [work]
+        ptrs = []
+        try:
+            for a in arrays:
+                d = C.c_void_p()                                    # stays NULL for an argument that is None
+                ptrs.append(d)
+                if a is None:
+                    continue
+                if hip.hipMalloc(C.byref(d), C.c_size_t(max(a.nbytes, 8))) != 0:
+                    raise LC3Error(1, "hipMalloc")
+                if a.nbytes and hip.hipMemcpy(d, C.c_void_p(a.ctypes.data), C.c_size_t(a.nbytes), C.c_int(1)) != 0:
+                    raise LC3Error(1, "hipMemcpy")
+            v = dict(zip(names + EGR_OUTPUTS + ("work",), [d.value for d in ptrs]))
+            self.egress_device(ins["offsets"].shape[1], v["frames"], fcap, v["offsets"], v["num_bytes"], max_frame_bytes, ins["seq_base"].size, v["seq_base"],
+                               v["pkt_route"], v["pkt_seq"], v["pkt_frame"], v["pkt_offset"], v["pkt_size"], v["n_packets"], v["work"], v["flags"], skip_mask,
+                               v["counts"], v["route_src"], seq_bits, order, v["wire"], wcap, header_room, align, v["pkt_flags"], v["wire_total"], v["next_seq"],
+                               v["stats"], v["cell_status"], sync=True)
+            for a, d in zip([ins["wire"]] + outs, ptrs[7:8] + ptrs[8:8 + len(outs)]):
+                if a is not None and a.nbytes and hip.hipMemcpy(C.c_void_p(a.ctypes.data), d, C.c_size_t(a.nbytes), C.c_int(2)) != 0:
+                    raise LC3Error(1, "hipMemcpy")
+        finally:
+            for d in ptrs:
+                if d.value:
+                    hip.hipFree(d)
+        return _egress_result(ins, outs)
+
+
 class _StreamLifecycle:
     """Reset, export and import single streams (lc3plus_{enc,dec}_batch_{reset,export,import}_streams; include/lc3plus_batch.h).  Stream lists are host
     sequences of indices; blobs are stream_state_size bytes per stream."""
@@ -445,7 +588,7 @@ def stream_header_ok(header, blob):
     return bool(load_library().lc3plus_stream_header_ok(h.ctypes.data, b.ctypes.data))
 
 
-class Batch(_StreamLifecycle):
+class Batch(_StreamLifecycle, _Egress):
     """n_streams independent encoders (lc3plus_enc_batch_*), state resident on the GPU between encode() calls."""
 
     def __init__(self, n_streams, samplerate, channels, frame_ms, hrmode, bitrates, device=-1):
@@ -980,7 +1123,7 @@ def plan_ingest(n_streams, channels, stream, seq, offsets, num_bytes, base, n_fr
     return dict(zip(ING_OUTPUTS, outs))
 
 
-class DecBatch(_StreamLifecycle):
+class DecBatch(_StreamLifecycle, _Egress):
     """n_streams independent decoders (lc3plus_dec_batch_*), state resident on the GPU between decode() calls."""
 
     def __init__(self, n_streams, samplerate, channels, frame_ms, hrmode, num_bytes, device=-1):

@@ -24,6 +24,7 @@
 #include "lc3_shim.h"
 #include "lc3_probe_shim.h"
 #include "lc3_ingest_shim.h"
+#include "lc3_egress_shim.h"
 
 #ifndef M_PI
 #define M_PI 3.14159265358979323846
@@ -1956,6 +1957,199 @@ LC3_Error lc3plus_dec_batch_ingest(lc3plus_dec_batch* b, int64_t n_items, const 
     q.out_offsets = (long long*)out_offsets; q.out_num_bytes = out_num_bytes; q.cell_item = cell_item; q.counts = counts; q.next_base = next_base; q.stats = stats;
     q.item_status = item_status; q.hip_stream = hip_stream ? hip_stream : own;
     return ingest_run(&q) ? LC3_ERROR : LC3_OK;
+}
+/* ---- packet egress (include/lc3plus_batch.h "Packet egress"; lc3_egress_shim.h) ---- */
+/* what every egress call takes behind its batch, in the header's order */
+typedef struct {
+    int n_frames; const void* frames; int64_t frames_capacity; const int64_t* offsets; const int32_t* num_bytes; int max_frame_bytes;
+    const uint8_t* flags; int skip_mask; const int32_t* counts;
+    int n_routes; const int32_t* route_src; const int32_t* seq_base; int seq_bits; int order;
+    void* wire; int64_t wire_capacity; int header_room; int align;
+    int32_t* pkt_route; int32_t* pkt_seq; int32_t* pkt_frame; int64_t* pkt_offset; int32_t* pkt_size; uint8_t* pkt_flags;
+    int64_t* n_packets; int64_t* wire_total; int32_t* next_seq; int32_t* stats; uint8_t* cell_status;
+    void* work;
+} egress_args;
+/* the checks every call makes first, in the header's order; n_streams < 0: not known yet (the batch is looked at behind them) */
+static LC3_Error egress_check(const egress_args* a, int n_streams)
+{
+    if (!a->frames || !a->offsets || !a->num_bytes || !a->seq_base || !a->pkt_route || !a->pkt_seq || !a->pkt_frame || !a->pkt_offset || !a->pkt_size ||
+        !a->n_packets || !a->work)
+        return LC3_NULL_ERROR;
+    if (a->n_frames <= 0 || a->n_routes <= 0 || (int64_t)a->n_routes * a->n_frames >= LC3E_MAX_CELLS || a->max_frame_bytes <= 0 || a->frames_capacity < 0 ||
+        a->wire_capacity < 0)
+        return LC3_ERROR;
+    if ((a->order != LC3E_STREAM_MAJOR && a->order != LC3E_FRAME_MAJOR) || (a->seq_bits != 16 && a->seq_bits != 32)) return LC3_ERROR;
+    if (a->header_room < 0 || a->header_room > INT32_MAX - LC3E_MAX_ALIGN - a->max_frame_bytes) return LC3_ERROR;
+    if (a->align < 1 || a->align > LC3E_MAX_ALIGN || (a->align & (a->align - 1))) return LC3_ERROR;
+    if (!a->wire && (a->header_room != 0 || a->align != 1)) return LC3_ERROR;
+    if (n_streams >= 0 && !a->route_src && a->n_routes != n_streams) return LC3_ERROR;
+    if ((uintptr_t)a->work & 7) return LC3_ERROR;
+    return LC3_OK;
+}
+int64_t lc3plus_egress_work_bytes(int n_routes, int n_frames)
+{
+    if (n_routes <= 0 || n_frames <= 0 || (int64_t)n_routes * n_frames >= LC3E_MAX_CELLS) return 0;
+    return lc3e_work_bytes((long long)n_routes * n_frames);
+}
+/* the copy kernel's runs on the host, one after the other */
+static void egress_copy(uint8_t* dst, const uint8_t* src, int n)
+{
+    const lc3e_copy_plan c = lc3e_copy_layout((uintptr_t)dst, n);
+    const int runs[5] = {c.hb, 4 * c.hd, 16 * c.pieces, 4 * c.td, c.tb};
+    for (int k = 0, at = 0; k < 5; at += runs[k++]) memcpy(dst + at, src + at, (size_t)runs[k]);
+}
+/* the rule on the host: the steps of the kernels (lc3_egress.inc) one after the other, on the text they run and over the same workspace */
+LC3_Error lc3plus_plan_egress(int n_streams,
+    int n_frames, const void* frames, int64_t frames_capacity, const int64_t* offsets, const int32_t* num_bytes, int max_frame_bytes,
+    const uint8_t* flags, int skip_mask, const int32_t* counts,
+    int n_routes, const int32_t* route_src, const int32_t* seq_base, int seq_bits, int order,
+    void* wire, int64_t wire_capacity, int header_room, int align,
+    int32_t* pkt_route, int32_t* pkt_seq, int32_t* pkt_frame, int64_t* pkt_offset, int32_t* pkt_size, uint8_t* pkt_flags,
+    int64_t* n_packets, int64_t* wire_total, int32_t* next_seq, int32_t* stats, uint8_t* cell_status,
+    void* work, void* hip_stream, int sync)
+{
+    const egress_args a = {n_frames, frames, frames_capacity, offsets, num_bytes, max_frame_bytes, flags, skip_mask, counts, n_routes, route_src, seq_base, seq_bits, order,
+                           wire, wire_capacity, header_room, align, pkt_route, pkt_seq, pkt_frame, pkt_offset, pkt_size, pkt_flags, n_packets, wire_total, next_seq,
+                           stats, cell_status, work};
+    LC3_Error e = egress_check(&a, -1);
+    if (e) return e;
+    if (n_streams <= 0) return LC3_ERROR;
+    e = egress_check(&a, n_streams);
+    if (e) return e;
+    const long long n_cells = (long long)n_routes * n_frames, n_tiles = lc3e_tiles(n_cells);
+    const int wire_mode = wire != NULL;
+    int32_t* word = (int32_t*)work;
+    long long* sums = (long long*)((char*)work + lc3e_work_sums(n_cells));
+    lc3e_list L = {pkt_route, pkt_seq, pkt_frame, (long long*)pkt_offset, pkt_size, pkt_flags, cell_status, NULL};
+    if (!L.status && stats) L.status = (uint8_t*)work + lc3e_work_status(n_cells);
+    if (wire_mode) L.from = (long long*)((char*)work + lc3e_work_from(n_cells));
+    /* classify */
+    for (long long i = 0; i < n_cells; i++) {
+        int r, t;
+        lc3e_cell_rt(i, n_routes, n_frames, order, &r, &t);
+        word[i] = lc3e_cell_word(r, t, n_streams, route_src, counts, n_frames, (const long long*)offsets, num_bytes, flags, max_frame_bytes, frames_capacity, skip_mask);
+    }
+    /* the tiles' sums, then their bases and the totals */
+    for (long long b = 0; b < n_tiles; b++) {
+        long long cnt = 0, bytes = 0;
+        for (long long i = b * LC3E_TILE; i < n_cells && i < (b + 1) * LC3E_TILE; i++) { cnt += word[i] > 0; bytes += lc3e_advance(word[i], wire_mode, header_room, align); }
+        sums[2 * b] = cnt; sums[2 * b + 1] = bytes;
+    }
+    long long run_c = 0, run_b = 0;
+    for (long long b = 0; b < n_tiles; b++) {
+        const long long cnt = sums[2 * b], bytes = sums[2 * b + 1];
+        sums[2 * b] = run_c; sums[2 * b + 1] = run_b;
+        run_c += cnt; run_b += bytes;
+    }
+    *n_packets = run_c;
+    if (wire_total) *wire_total = run_b;
+    /* scatter, and the copy of each packet that fits */
+    for (long long b = 0; b < n_tiles; b++) {
+        long long p = sums[2 * b], run = sums[2 * b + 1];
+        for (long long i = b * LC3E_TILE; i < n_cells && i < (b + 1) * LC3E_TILE; i++) {
+            int r, t;
+            lc3e_cell_rt(i, n_routes, n_frames, order, &r, &t);
+            int st = -word[i];
+            if (word[i] > 0) {
+                const int s = route_src ? route_src[r] : r;
+                st = lc3e_emit(&L, p, r, t, s, word[i], run, seq_base, seq_bits, n_frames, (const long long*)offsets, wire_mode, header_room, wire_capacity);
+                if (wire_mode && !(st & LC3E_OVERFLOW)) egress_copy((uint8_t*)wire + run + header_room, (const uint8_t*)frames + L.from[p], word[i]);
+                p++; run += lc3e_advance(word[i], wire_mode, header_room, align);
+            }
+            if (L.status) L.status[(size_t)r * n_frames + t] = (uint8_t)st;
+        }
+    }
+    /* the routes */
+    if (next_seq || stats)
+        for (int r = 0; r < n_routes; r++) {
+            int s = 0, sent = 0, holes = 0, over = 0;
+            const int c = lc3e_route(route_src, r, n_streams, counts, n_frames, &s);
+            if (stats)
+                for (int t = 0; t < c; t++) {
+                    const int st = L.status[(size_t)r * n_frames + t];
+                    sent += (st & LC3E_SENT) != 0; over += (st & LC3E_OVERFLOW) != 0; holes += (st & (LC3E_LOST | LC3E_INVALID | LC3E_SKIPPED)) != 0;
+                }
+            lc3e_route_out(r, c, sent, holes, over, seq_base, seq_bits, next_seq, stats);
+        }
+    return LC3_OK;
+}
+/* the sibling library with the egress kernels, loaded as the ingest's is; NULL where it is missing */
+typedef int (*egress_run_fn)(const lc3egress_call*);
+static pthread_once_t egress_once = PTHREAD_ONCE_INIT;
+static egress_run_fn egress_run;
+static void egress_load(void)
+{
+    Dl_info di;
+    char path[4096];
+    if (!dladdr((void*)&egress_load, &di) || !di.dli_fname) return;
+    const char* slash = strrchr(di.dli_fname, '/');
+    const size_t dir = slash ? (size_t)(slash - di.dli_fname) + 1 : 0;
+    static const char name[] = "liblc3plus_egress_hip.so";
+    if (dir + sizeof name > sizeof path) return;
+    memcpy(path, di.dli_fname, dir);
+    memcpy(path + dir, name, sizeof name);
+    void* h = dlopen(path, RTLD_NOW | RTLD_LOCAL);
+    if (!h) { fprintf(stderr, "lc3plus_hip: the packet egress's library is missing: %s\n", dlerror()); return; }
+    egress_run = (egress_run_fn)dlsym(h, "lc3egress_run");
+}
+/* both entry points end here.  Of the batch: its device and stream (dev; decoder: which kind of context it is) and n_streams.  No stream state, no configuration,
+ * no buffer */
+static LC3_Error egress_queue(void* dev, int decoder, int n_streams, const egress_args* a, void* hip_stream, int sync)
+{
+    if (!a->route_src && a->n_routes != n_streams) return LC3_ERROR;
+    lc3egress_call q;
+    memset(&q, 0, sizeof q);
+    void* own = NULL;
+    if (decoder) {
+        const lc3d_plan* plan = NULL; const lc3d_dchan* tab = NULL; int tab_n = 0;
+        if (lc3hip_dec_probe_args(dev, &q.device, &plan, &tab, &tab_n, &own)) return LC3_ERROR;
+    } else if (lc3hip_stream_args(dev, !hip_stream, &q.device, &own)) return LC3_ERROR;
+    pthread_once(&egress_once, egress_load);
+    if (!egress_run) return LC3_ERROR;
+    q.n_streams = n_streams; q.n_frames = a->n_frames; q.max_frame_bytes = a->max_frame_bytes; q.skip_mask = a->skip_mask; q.n_routes = a->n_routes;
+    q.seq_bits = a->seq_bits; q.order = a->order; q.header_room = a->header_room; q.align = a->align; q.sync = sync;
+    q.frames_capacity = (long long)a->frames_capacity; q.wire_capacity = (long long)a->wire_capacity;
+    q.frames = a->frames; q.offsets = (const long long*)a->offsets; q.num_bytes = a->num_bytes; q.flags = a->flags; q.counts = a->counts; q.route_src = a->route_src;
+    q.seq_base = a->seq_base; q.wire = a->wire;
+    q.list.route = a->pkt_route; q.list.seq = a->pkt_seq; q.list.frame = a->pkt_frame; q.list.offset = (long long*)a->pkt_offset; q.list.size = a->pkt_size;
+    q.list.flags = a->pkt_flags; q.list.status = a->cell_status;
+    q.n_packets = (long long*)a->n_packets; q.wire_total = (long long*)a->wire_total; q.next_seq = a->next_seq; q.stats = a->stats; q.work = a->work;
+    q.hip_stream = hip_stream ? hip_stream : own;
+    return egress_run(&q) ? LC3_ERROR : LC3_OK;
+}
+LC3_Error lc3plus_enc_batch_egress(lc3plus_batch* b,
+    int n_frames, const void* frames, int64_t frames_capacity, const int64_t* offsets, const int32_t* num_bytes, int max_frame_bytes,
+    const uint8_t* flags, int skip_mask, const int32_t* counts,
+    int n_routes, const int32_t* route_src, const int32_t* seq_base, int seq_bits, int order,
+    void* wire, int64_t wire_capacity, int header_room, int align,
+    int32_t* pkt_route, int32_t* pkt_seq, int32_t* pkt_frame, int64_t* pkt_offset, int32_t* pkt_size, uint8_t* pkt_flags,
+    int64_t* n_packets, int64_t* wire_total, int32_t* next_seq, int32_t* stats, uint8_t* cell_status,
+    void* work, void* hip_stream, int sync)
+{
+    if (!b) return LC3_NULL_ERROR;
+    const egress_args a = {n_frames, frames, frames_capacity, offsets, num_bytes, max_frame_bytes, flags, skip_mask, counts, n_routes, route_src, seq_base, seq_bits, order,
+                           wire, wire_capacity, header_room, align, pkt_route, pkt_seq, pkt_frame, pkt_offset, pkt_size, pkt_flags, n_packets, wire_total, next_seq,
+                           stats, cell_status, work};
+    LC3_Error e = egress_check(&a, -1);
+    if (e) return e;
+    return egress_queue(b->dev, 0, b->n_streams, &a, hip_stream, sync);
+}
+LC3_Error lc3plus_dec_batch_egress(lc3plus_dec_batch* b,
+    int n_frames, const void* frames, int64_t frames_capacity, const int64_t* offsets, const int32_t* num_bytes, int max_frame_bytes,
+    const uint8_t* flags, int skip_mask, const int32_t* counts,
+    int n_routes, const int32_t* route_src, const int32_t* seq_base, int seq_bits, int order,
+    void* wire, int64_t wire_capacity, int header_room, int align,
+    int32_t* pkt_route, int32_t* pkt_seq, int32_t* pkt_frame, int64_t* pkt_offset, int32_t* pkt_size, uint8_t* pkt_flags,
+    int64_t* n_packets, int64_t* wire_total, int32_t* next_seq, int32_t* stats, uint8_t* cell_status,
+    void* work, void* hip_stream, int sync)
+{
+    if (!b) return LC3_NULL_ERROR;
+    const egress_args a = {n_frames, frames, frames_capacity, offsets, num_bytes, max_frame_bytes, flags, skip_mask, counts, n_routes, route_src, seq_base, seq_bits, order,
+                           wire, wire_capacity, header_room, align, pkt_route, pkt_seq, pkt_frame, pkt_offset, pkt_size, pkt_flags, n_packets, wire_total, next_seq,
+                           stats, cell_status, work};
+    LC3_Error e = egress_check(&a, -1);
+    if (e) return e;
+    return egress_queue(b->dev, 1, b->n_streams, &a, hip_stream, sync);
 }
 LC3_Error lc3plus_dec_batch_set_input_ready(lc3plus_dec_batch* b, int ready)
 {

@@ -335,6 +335,15 @@ extern "C" int lc3hip_create(void** out_ctx, const lc3d_plan* plan, int n_stream
     return 0;
 }
 
+extern "C" int lc3hip_stream_args(void* ctx, int want_stream, int* device, void** stream)
+{
+    lc3hip_ctx* c = (lc3hip_ctx*)ctx;
+    if (!c) return 1;
+    if (want_stream && !c->stream) { HIPCHK(hipSetDevice(c->device)); HIPCHK(hipStreamCreate(&c->stream)); }
+    *device = c->device; *stream = (void*)c->stream;
+    return 0;
+}
+
 extern "C" int lc3hip_set_template(void* ctx, const float* tmpl)
 {
     lc3hip_ctx* c = (lc3hip_ctx*)ctx;

@@ -51,6 +51,9 @@ float lc3hip_dec_last_ms(void* ctx);
  * creation - and the context's stream.  Touches nothing. */
 int   lc3hip_dec_probe_args(void* ctx, int* device, const lc3d_plan** plan_dev, const lc3d_dchan** tab_dev, int* tab_n, void** stream);
 int   lc3hip_dec_destroy(void* ctx);
+/* what the packet egress borrows of an encoder context (lc3_egress_shim.h): its device and, with want_stream, the context's own stream (created here where no
+ * call has needed it yet).  Touches nothing else. */
+int   lc3hip_stream_args(void* ctx, int want_stream, int* device, void** stream);
 int   lc3hip_create(void** ctx, const lc3d_plan* plan, int n_streams, int device);
 int   lc3hip_set_template(void* ctx, const float* tmpl);       /* one channel-stream's fresh state row (init_state): kept on the device, every row reset from it */
 int   lc3hip_upload_chans(void* ctx, const lc3d_chan* chans, int first, int count);

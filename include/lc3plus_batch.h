@@ -611,6 +611,102 @@ LC3_Error lc3plus_plan_ingest(int n_streams, int channels, int64_t n_items, cons
                               int64_t* out_offsets, int32_t* out_num_bytes, int32_t* cell_item, int32_t* counts, int32_t* next_base, int32_t* stats,
                               uint8_t* item_status);
 
+/* ---- Packet egress: frame tables to packet lists and send buffers on the device ------------------------------------------------------------------------
+ * The mirror image of the ingest.  encode_packed() leaves tables indexed [stream][frame] in device memory - offsets, num_bytes, flags - and so does the ingest
+ * (out_offsets, out_num_bytes, counts); a sender needs a flat list of packets, each with a sequence number, and a forwarding or simulcast server needs every
+ * frame once per receiver behind that receiver's header.  The egress call turns the first into the second in device memory, so that
+ * set_frame_counts + encode_packed -> egress (a sender) and probe -> ingest -> egress (a forwarder, which never decodes) run on one HIP stream with no host
+ * wait in between.  Its list is the item format the probe and the ingest take: egress -> ingest is a closed loop.
+ *
+ * Every pointer but `batch` is a device pointer; the inputs are read when the kernels run, so the encode_packed or ingest call queued before on the same stream
+ * may produce them.  The call is STATELESS, like the probe and the ingest: lc3plus_enc_batch_egress borrows an encoder batch's device and n_streams,
+ * lc3plus_dec_batch_egress a decoder batch's, and nothing else.  No stream state, configuration or buffer of the batch is read or written, nothing is
+ * allocated - `work` is the only scratch - and the call may run beside an encode or decode call of the same batch.  It is queued on hip_stream (NULL: the
+ * batch's stream) and returns at once unless sync.  No output may overlap an input or another output; wire must not overlap frames.  On a shard's batch the
+ * call works as on any batch, with that shard's n_streams and LOCAL stream indices.
+ *
+ *   frames, frames_capacity : the buffer the frames lie in and its size in bytes
+ *   offsets, num_bytes : [n_streams][n_frames] each frame's byte offset in frames (int64) and its size; max_frame_bytes: the largest size a frame may have
+ *   flags, skip_mask   : [n_streams][n_frames] or NULL; a frame whose flags have a bit of skip_mask is not sent.  A sender passes encode_packed's flags and
+ *                        8, its bit for a frame that did not fit out_capacity: that frame's bytes were never written
+ *   counts     : [n_streams] or NULL: the frames each stream has in this call (set_frame_counts' array, or the ingest's counts)
+ *   route_src  : [n_routes] the source stream of each route, or NULL: route r sends stream r, and n_routes must equal n_streams
+ *   seq_base   : [n_routes] the sequence number of frame 0 on each route; seq_bits: 16 (RTP) or 32
+ *   order      : LC3PLUS_PACK_STREAM_MAJOR (the list sorted by route, then frame) or LC3PLUS_PACK_FRAME_MAJOR (by frame, then route: time order, for pacing)
+ *   wire, wire_capacity, header_room, align : the send buffer, or NULL: in-place mode
+ *   pkt_route, pkt_seq, pkt_frame, pkt_offset (int64), pkt_size, pkt_flags (uint8) : the list, n_routes * n_frames entries each
+ *   n_packets, wire_total : one int64 each
+ *   next_seq [n_routes], stats [n_routes][LC3PLUS_EGR_STATS_WORDS], cell_status [n_routes][n_frames] (uint8)
+ *   work       : lc3plus_egress_work_bytes(n_routes, n_frames) bytes, 8-byte aligned; its contents mean nothing before or after the call
+ *   pkt_flags, wire_total, next_seq, stats and cell_status may each be NULL.
+ *
+ * Routes.  A route is one outgoing flow with a sequence space of its own.  Several routes may name one stream (fan-out, simulcast); a stream may have no
+ *   route.  A route whose route_src[r] lies outside [0, n_streams) is BAD: it sends nothing, every cell of it has status BAD_ROUTE, next_seq[r] = seq_base[r]
+ *   and its stats are 0.
+ * Cells.  For s = route_src[r] let c = min(max(counts[s], 0), n_frames), n_frames where counts is NULL.  Cell (r, t) with t >= c is ABSENT: none of its table
+ *   entries is looked at.  A cell with t < c is, in this order: LOST where num_bytes[s][t] == 0; INVALID for a negative size, a size above max_frame_bytes, a
+ *   negative offset or offset + size > frames_capacity (computed without overflow); SKIPPED where flags is given and flags[s][t] & skip_mask; SENT otherwise.
+ *   Only the bytes of SENT cells are ever read.
+ * Sequence numbers follow position, not a running count: cell (r, t) has seq = (seq_base[r] + t) mod 2^seq_bits, and next_seq[r] = (seq_base[r] + c) mod
+ *   2^seq_bits.  A LOST, INVALID or SKIPPED frame in front of c therefore leaves a hole in the numbers, which the receiver conceals - exactly what the encoder's
+ *   stream did, which advanced over the frame, and what makes the egress the inverse of the ingest.
+ * The list holds the SENT cells only, compacted, in `order`.  Packet p carries pkt_route, pkt_seq, pkt_frame = t, pkt_offset, pkt_size and pkt_flags;
+ *   *n_packets is the list's length, and entries at or behind it are not written.
+ * In-place mode, wire == NULL (header_room must be 0 and align 1): pkt_offset = offsets[s][t] and pkt_size the frame's size - the packet is the frame where it
+ *   lies; *wire_total is the sum of the sizes; pkt_flags are 0.  No byte is copied.
+ * Wire mode: header_room >= 0 (header_room + max_frame_bytes + 4096 must fit an int32) and align a power of two in [1, 4096].  pkt_size = header_room + size;
+ *   pkt_offset is the exclusive scan, in list order and from 0, of pkt_size rounded up to align, and *wire_total that scan's end.  A packet fits when
+ *   pkt_offset + pkt_size <= wire_capacity: then the frame's bytes are copied to wire + pkt_offset + header_room, and the header_room bytes in front are left to
+ *   the caller.  A packet that does not fit stays in the list with pkt_flags = LC3PLUS_EGR_PKT_OVERFLOW (its cell: SENT | OVERFLOW), keeps its number and copies
+ *   nothing.  No byte of wire outside [pkt_offset + header_room, pkt_offset + pkt_size) of a fitting packet is modified.  Of frames, only aligned 32-bit words
+ *   that hold a byte of a SENT frame are read, as decode_packed() reads them.
+ * stats[r] = {c, SENT cells, LOST + INVALID + SKIPPED cells in front of c, SENT cells that overflowed}.  cell_status holds exactly one of SENT, LOST, INVALID,
+ *   SKIPPED, ABSENT and BAD_ROUTE, and OVERFLOW beside SENT.
+ *
+ * Refused calls queue nothing, checked in this order before anything of the batch or the device is touched: a NULL batch, frames, offsets, num_bytes, seq_base,
+ * pkt_route, pkt_seq, pkt_frame, pkt_offset, pkt_size, n_packets or work (LC3_NULL_ERROR); then n_frames <= 0, n_routes <= 0, n_routes * n_frames >= 2^31,
+ * max_frame_bytes <= 0, frames_capacity < 0, wire_capacity < 0, a bad order, seq_bits, header_room or align, a NULL route_src with n_routes != n_streams, or a
+ * work that is not 8-byte aligned (LC3_ERROR).  The kernels live in liblc3plus_egress_hip.so, which this library loads from its own directory on the first
+ * egress call: where that file is missing the call returns LC3_ERROR and nothing else changes. */
+#define LC3PLUS_EGR_SENT         1
+#define LC3PLUS_EGR_LOST         2
+#define LC3PLUS_EGR_INVALID      4
+#define LC3PLUS_EGR_SKIPPED      8
+#define LC3PLUS_EGR_ABSENT       16
+#define LC3PLUS_EGR_BAD_ROUTE    32
+#define LC3PLUS_EGR_OVERFLOW     64
+#define LC3PLUS_EGR_PKT_OVERFLOW 1
+#define LC3PLUS_EGR_STATS_WORDS  4
+LC3_Error lc3plus_enc_batch_egress(lc3plus_batch* batch,
+    int n_frames, const void* frames, int64_t frames_capacity, const int64_t* offsets, const int32_t* num_bytes, int max_frame_bytes,
+    const uint8_t* flags, int skip_mask, const int32_t* counts,
+    int n_routes, const int32_t* route_src, const int32_t* seq_base, int seq_bits, int order,
+    void* wire, int64_t wire_capacity, int header_room, int align,
+    int32_t* pkt_route, int32_t* pkt_seq, int32_t* pkt_frame, int64_t* pkt_offset, int32_t* pkt_size, uint8_t* pkt_flags,
+    int64_t* n_packets, int64_t* wire_total, int32_t* next_seq, int32_t* stats, uint8_t* cell_status,
+    void* work, void* hip_stream, int sync);
+LC3_Error lc3plus_dec_batch_egress(lc3plus_dec_batch* batch,
+    int n_frames, const void* frames, int64_t frames_capacity, const int64_t* offsets, const int32_t* num_bytes, int max_frame_bytes,
+    const uint8_t* flags, int skip_mask, const int32_t* counts,
+    int n_routes, const int32_t* route_src, const int32_t* seq_base, int seq_bits, int order,
+    void* wire, int64_t wire_capacity, int header_room, int align,
+    int32_t* pkt_route, int32_t* pkt_seq, int32_t* pkt_frame, int64_t* pkt_offset, int32_t* pkt_size, uint8_t* pkt_flags,
+    int64_t* n_packets, int64_t* wire_total, int32_t* next_seq, int32_t* stats, uint8_t* cell_status,
+    void* work, void* hip_stream, int sync);
+/* The same rule on the host alone, no device: the same arrays in host memory (work too), n_streams given instead of a batch; in wire mode the frames are
+ * copied as the copy kernel copies them.  hip_stream and sync are ignored.  The refusals of the calls above in their order, with n_streams <= 0 (LC3_ERROR)
+ * in front of the route_src check. */
+LC3_Error lc3plus_plan_egress(int n_streams,
+    int n_frames, const void* frames, int64_t frames_capacity, const int64_t* offsets, const int32_t* num_bytes, int max_frame_bytes,
+    const uint8_t* flags, int skip_mask, const int32_t* counts,
+    int n_routes, const int32_t* route_src, const int32_t* seq_base, int seq_bits, int order,
+    void* wire, int64_t wire_capacity, int header_room, int align,
+    int32_t* pkt_route, int32_t* pkt_seq, int32_t* pkt_frame, int64_t* pkt_offset, int32_t* pkt_size, uint8_t* pkt_flags,
+    int64_t* n_packets, int64_t* wire_total, int32_t* next_seq, int32_t* stats, uint8_t* cell_status,
+    void* work, void* hip_stream, int sync);
+/* the bytes of `work` for such a call; 0 for arguments the calls refuse */
+int64_t lc3plus_egress_work_bytes(int n_routes, int n_frames);
+
 /* ---- Sharded batches: one call drives encoders or decoders on several GPUs ------------------------------------------------------------------
  * Streams are independent, so a sharded batch is n_devices ordinary batches, each owning a contiguous block of the n_streams streams on a device of its
  * own; nothing is exchanged between devices.  Stream indices are GLOBAL (0 ... n_streams - 1) and arrays are laid out over all n_streams exactly as the

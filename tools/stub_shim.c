@@ -87,6 +87,7 @@ int lc3hip_dec_download_chans(void* ctx, lc3d_dchan* chans) { return 0; }
 float lc3hip_last_ms(void* ctx) { return 0.0f; }
 float lc3hip_dec_last_ms(void* ctx) { return 0.0f; }
 int lc3hip_dec_probe_args(void* ctx, int* device, const lc3d_plan** plan_dev, const lc3d_dchan** tab_dev, int* tab_n, void** stream) { return 1; }   /* no device: a probe fails behind its checks */
+int lc3hip_stream_args(void* ctx, int want_stream, int* device, void** stream) { return 1; }   /* no device: an egress call fails behind its checks */
 int lc3hip_set_input_ready(void* ctx, int ready) { return 0; }
 int lc3hip_dec_set_input_ready(void* ctx, int ready) { return 0; }
 static int stub_placement(void* ctx, const long long* offsets_dev, long long capacity)
