@@ -42,6 +42,8 @@ EXPORTS = [
     "lc3plus_dec_batch_probe", "lc3plus_frame_info_side", "lc3plus_reject_name",
     "lc3plus_dec_batch_ingest", "lc3plus_plan_ingest",
     "lc3plus_enc_batch_egress", "lc3plus_dec_batch_egress", "lc3plus_plan_egress", "lc3plus_egress_work_bytes",
+    "lc3plus_dec_batch_rtp_parse", "lc3plus_plan_rtp_parse", "lc3plus_rtp_sort_ssrc", "lc3plus_enc_batch_rtp_stamp", "lc3plus_dec_batch_rtp_stamp",
+    "lc3plus_plan_rtp_stamp",
     "lc3plus_shard_block",
     "lc3plus_enc_sharded_create", "lc3plus_enc_sharded_destroy", "lc3plus_enc_sharded_shards", "lc3plus_enc_sharded_shard", "lc3plus_enc_sharded_device",
     "lc3plus_enc_sharded_owner", "lc3plus_enc_sharded_input_samples", "lc3plus_enc_sharded_num_bytes", "lc3plus_enc_sharded_stride",
@@ -86,6 +88,12 @@ ING_STATS_WORDS = 4
 EGR_SENT, EGR_LOST, EGR_INVALID, EGR_SKIPPED, EGR_ABSENT, EGR_BAD_ROUTE, EGR_OVERFLOW = 1, 2, 4, 8, 16, 32, 64
 EGR_PKT_OVERFLOW = 1
 EGR_STATS_WORDS = 4
+# RTP framing (DecBatch.rtp_parse, Batch.rtp_stamp, DecBatch.rtp_stamp, plan_rtp_parse, plan_rtp_stamp; include/lc3plus_batch.h "RTP framing"): an item's status
+# (also its word in stats), the bits of pkt_status, the marker modes
+(RTP_OK, RTP_RANGE, RTP_SHORT, RTP_VERSION, RTP_RTCP, RTP_HEADER, RTP_PADDING, RTP_PAYLOAD_ROOM, RTP_UNKNOWN_SSRC, RTP_PAYLOAD_TYPE) = range(10)
+RTP_STATS_WORDS = 16
+RTP_STAMPED, RTP_ST_BAD_ROUTE, RTP_ST_OVERFLOW, RTP_ST_RANGE = 1, 2, 4, 8
+RTP_MARKER_NEVER, RTP_MARKER_AFTER_HOLE = 0, 1
 LC3_BW_WARNING = 18
 
 
@@ -238,6 +246,15 @@ def load_library():
         L.lc3plus_dec_batch_egress.argtypes = [C.c_void_p] + egr
         L.lc3plus_plan_egress.argtypes = [C.c_int] + egr
         L.lc3plus_egress_work_bytes.argtypes = [C.c_int, C.c_int]; L.lc3plus_egress_work_bytes.restype = C.c_int64
+        parse = [C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 8 + [C.c_void_p, C.c_int]
+        L.lc3plus_dec_batch_rtp_parse.argtypes = [C.c_void_p] + parse
+        L.lc3plus_plan_rtp_parse.argtypes = [C.c_int] + parse
+        L.lc3plus_rtp_sort_ssrc.argtypes = [C.c_int, C.c_void_p, C.c_void_p]
+        stamp = ([C.c_int64] + [C.c_void_p] * 7 + [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                 C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int])
+        L.lc3plus_enc_batch_rtp_stamp.argtypes = [C.c_void_p] + stamp
+        L.lc3plus_dec_batch_rtp_stamp.argtypes = [C.c_void_p] + stamp
+        L.lc3plus_plan_rtp_stamp.argtypes = stamp
         _LIB = L
     return _LIB
 
@@ -507,6 +524,190 @@ class _Egress:
         return _egress_result(ins, outs)
 
 
+def _u32(x):
+    """32-bit words however they are given: 0 ... 2^32 - 1 and negative values both fit"""
+    return (np.asarray(x).astype(np.int64).reshape(-1) & 0xFFFFFFFF).astype(np.uint32).view(np.int32)
+
+
+@contextlib.contextmanager
+def _on_device(arrays):
+    """the arrays (None: a NULL pointer) in device memory through the HIP runtime (hipMalloc / hipMemcpy on the current device) -> (their pointers, a function
+    that copies a device array back into its host array); everything is freed at the end"""
+    hip = C.CDLL("libamdhip64.so")
+    ptrs = []
+
+    def back(k):
+        a = arrays[k]
+        if a is not None and a.nbytes and hip.hipMemcpy(C.c_void_p(a.ctypes.data), ptrs[k], C.c_size_t(a.nbytes), C.c_int(2)) != 0:
+            raise LC3Error(1, "hipMemcpy")
+    try:
+        for a in arrays:
+            d = C.c_void_p()                                        # stays NULL for an argument that is None
+            ptrs.append(d)
+            if a is None:
+                continue
+            if hip.hipMalloc(C.byref(d), C.c_size_t(max(a.nbytes, 8))) != 0:
+                raise LC3Error(1, "hipMalloc")
+            if a.nbytes and hip.hipMemcpy(d, C.c_void_p(a.ctypes.data), C.c_size_t(a.nbytes), C.c_int(1)) != 0:
+                raise LC3Error(1, "hipMemcpy")
+        yield [d.value for d in ptrs], back
+    finally:
+        for d in ptrs:
+            if d.value:
+                hip.hipFree(d)
+
+
+RTP_PARSE_OPTIONAL = ("timestamp", "marker", "status", "stats")
+RTP_PARSE_OUTPUTS = ("stream", "seq", "offsets", "num_bytes", "timestamp", "marker", "status", "stats")
+RTP_STAMP_OPTIONAL = ("pkt_status", "next_ts", "next_resume")
+
+
+def rtp_sort_ssrc(ssrc_key, ssrc_stream):
+    """An SSRC table in the order rtp_parse needs (lc3plus_rtp_sort_ssrc): -> (keys ascending as uint32, as int32 words; each key's stream).  LC3Error for an
+    empty table and for a key that occurs twice."""
+    key, stream = _u32(ssrc_key).copy(), np.array(ssrc_stream, dtype=np.int32).reshape(-1)
+    if key.size != stream.size:
+        raise ValueError("ssrc_key and ssrc_stream hold one entry per sender")
+    rc = load_library().lc3plus_rtp_sort_ssrc(key.size, key.ctypes.data if key.size else None, stream.ctypes.data if stream.size else None)
+    if rc:
+        raise LC3Error(rc, "lc3plus_rtp_sort_ssrc")
+    return key, stream
+
+
+def _rtp_parse_arrays(n_streams, ring, dg_offsets, dg_sizes, ssrc_key, ssrc_stream, payload_type, optional):
+    """the arrays of a parse call as the C calls take them: (inputs ring, dg_offsets, dg_sizes, ssrc_key, ssrc_stream, payload_type - None for NULL; outputs in
+    RTP_PARSE_OUTPUTS order likewise)"""
+    ring = np.ascontiguousarray(ring, dtype=np.uint8).reshape(-1)
+    dg_offsets = np.ascontiguousarray(dg_offsets, dtype=np.int64).reshape(-1)
+    dg_sizes = np.ascontiguousarray(dg_sizes, dtype=np.int32).reshape(-1)
+    key, stream = _u32(ssrc_key), np.ascontiguousarray(ssrc_stream, dtype=np.int32).reshape(-1)
+    if dg_offsets.size != dg_sizes.size or key.size != stream.size:
+        raise ValueError("dg_offsets and dg_sizes hold one entry per datagram, ssrc_key and ssrc_stream one per sender")
+    if payload_type is not None:
+        payload_type = np.ascontiguousarray(payload_type, dtype=np.int32).reshape(-1)
+        if payload_type.size != n_streams:
+            raise ValueError("payload_type holds one entry per stream")
+    n = dg_offsets.size
+    outs = [np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros(n, np.int64), np.zeros(n, np.int32),
+            np.zeros(n, np.int32) if "timestamp" in optional else None, np.zeros(n, np.uint8) if "marker" in optional else None,
+            np.zeros(n, np.uint8) if "status" in optional else None, np.zeros(RTP_STATS_WORDS, np.int32) if "stats" in optional else None]
+    return [ring, dg_offsets, dg_sizes, key, stream, payload_type], outs
+
+
+def plan_rtp_parse(n_streams, ring, dg_offsets, dg_sizes, ssrc_key, ssrc_stream, payload_type=None, payload_room=0, optional=RTP_PARSE_OPTIONAL,
+                   ring_capacity=None):
+    """The rule of DecBatch.rtp_parse on the host (lc3plus_plan_rtp_parse, no device needed): ring (uint8, ring_capacity bytes of it: all by default), the
+    datagrams dg_offsets (int64) / dg_sizes [n], the senders ssrc_key (ascending as uint32: rtp_sort_ssrc) / ssrc_stream, optional payload_type [n_streams]
+    -> dict of stream, seq, offsets (int64), num_bytes [n] - the item arrays of ingest and probe - and timestamp [n], marker, status (uint8) [n] and stats
+    [RTP_STATS_WORDS]; those of RTP_PARSE_OPTIONAL not named in `optional` are passed as NULL and come back as None.  LC3Error for arguments the C call
+    refuses."""
+    ins, outs = _rtp_parse_arrays(n_streams, ring, dg_offsets, dg_sizes, ssrc_key, ssrc_stream, payload_type, optional)
+    pad = np.zeros(8, np.uint8)                                       # an empty array still has to be a pointer
+    ptr = lambda a: (a if a.size else pad).ctypes.data if a is not None else None
+    cap = ins[0].size if ring_capacity is None else int(ring_capacity)
+    rc = load_library().lc3plus_plan_rtp_parse(int(n_streams), ins[1].size, ptr(ins[0]), cap, ptr(ins[1]), ptr(ins[2]), ins[3].size, ptr(ins[3]), ptr(ins[4]),
+                                               ptr(ins[5]), int(payload_room), *[ptr(a) for a in outs], None, 0)
+    if rc:
+        raise LC3Error(rc, "lc3plus_plan_rtp_parse")
+    return dict(zip(RTP_PARSE_OUTPUTS, outs))
+
+
+def _rtp_stamp_arrays(pkt_route, pkt_seq, pkt_frame, pkt_offset, pkt_size, pkt_flags, n_packets, ssrc, ts_base, payload_type, n_frames, cell_status, resume,
+                      route_stats, wire, optional):
+    """the arrays of a stamp call as the C calls take them: (inputs in the header's order, None for NULL; wire, a copy; outputs pkt_status, next_ts,
+    next_resume likewise)"""
+    route = np.ascontiguousarray(pkt_route, dtype=np.int32).reshape(-1)
+    m = route.size
+    seq, frame = _u32(pkt_seq), np.ascontiguousarray(pkt_frame, dtype=np.int32).reshape(-1)
+    off, size = np.ascontiguousarray(pkt_offset, dtype=np.int64).reshape(-1), np.ascontiguousarray(pkt_size, dtype=np.int32).reshape(-1)
+    if not (seq.size == frame.size == off.size == size.size == m):
+        raise ValueError("the list arrays hold one entry per packet")
+    flags = np.ascontiguousarray(pkt_flags, dtype=np.uint8).reshape(-1) if pkt_flags is not None else None
+    if flags is not None and flags.size != m:
+        raise ValueError("pkt_flags holds one entry per packet")
+    ssrc, ts_base, payload_type = _u32(ssrc), _u32(ts_base), np.ascontiguousarray(payload_type, dtype=np.int32).reshape(-1)
+    R = ssrc.size
+    if ts_base.size != R or payload_type.size != R:
+        raise ValueError("ssrc, ts_base and payload_type hold one entry per route")
+    if cell_status is not None:
+        cell_status = np.ascontiguousarray(cell_status, dtype=np.uint8)
+        if cell_status.shape != (R, int(n_frames)):
+            raise ValueError("cell_status must have shape [n_routes, n_frames]")
+    if resume is not None:
+        resume = np.ascontiguousarray(resume, dtype=np.uint8).reshape(-1)
+        if resume.size != R:
+            raise ValueError("resume holds one entry per route")
+    if route_stats is not None:
+        route_stats = np.ascontiguousarray(route_stats, dtype=np.int32)
+        if route_stats.shape != (R, EGR_STATS_WORDS):
+            raise ValueError("route_stats must have shape [n_routes, EGR_STATS_WORDS]")
+    count = np.array([m if n_packets is None else int(n_packets)], np.int64)
+    wire = np.array(wire, dtype=np.uint8).reshape(-1)                 # a copy: the call's wire buffer starts with these contents
+    outs = [np.zeros(m, np.uint8) if "pkt_status" in optional else None, np.zeros(R, np.int32) if "next_ts" in optional else None,
+            np.zeros(R, np.uint8) if "next_resume" in optional else None]
+    return [count, route, seq, frame, off, size, flags, ssrc, ts_base, payload_type, cell_status, resume, route_stats], wire, outs
+
+
+def plan_rtp_stamp(pkt_route, pkt_seq, pkt_frame, pkt_offset, pkt_size, ssrc, ts_base, payload_type, ts_step, n_frames, wire, header_room=12, payload_room=0,
+                   pkt_flags=None, n_packets=None, marker_mode=RTP_MARKER_NEVER, cell_status=None, resume=None, route_stats=None, wire_capacity=None,
+                   optional=RTP_STAMP_OPTIONAL):
+    """The rule of Batch.rtp_stamp / DecBatch.rtp_stamp on the host (lc3plus_plan_rtp_stamp, no device needed): the egress's packet list pkt_* [max_packets]
+    (n_packets of it: all by default), per route ssrc, ts_base, payload_type [n_routes], optional cell_status [n_routes, n_frames], resume [n_routes] and
+    route_stats [n_routes, EGR_STATS_WORDS] (the egress's stats); wire: the wire buffer's contents before the call (uint8; wire_capacity bytes of it: all by
+    default) -> dict of wire (the buffer after the call), pkt_status (uint8) [max_packets] (zero behind n_packets), next_ts [n_routes] and next_resume (uint8)
+    [n_routes]; those of RTP_STAMP_OPTIONAL not named in `optional` are passed as NULL and come back as None.  LC3Error for arguments the C call refuses."""
+    ins, wire, outs = _rtp_stamp_arrays(pkt_route, pkt_seq, pkt_frame, pkt_offset, pkt_size, pkt_flags, n_packets, ssrc, ts_base, payload_type, n_frames,
+                                        cell_status, resume, route_stats, wire, optional)
+    pad = np.zeros(8, np.uint8)
+    ptr = lambda a: (a if a.size else pad).ctypes.data if a is not None else None
+    wcap = wire.size if wire_capacity is None else int(wire_capacity)
+    rc = load_library().lc3plus_plan_rtp_stamp(ins[1].size, *[ptr(a) for a in ins[:7]], ins[7].size, int(n_frames), ptr(ins[7]), ptr(ins[8]), ptr(ins[9]),
+                                               int(ts_step), int(marker_mode), ptr(ins[10]), ptr(ins[11]), ptr(ins[12]), ptr(wire), wcap, int(header_room),
+                                               int(payload_room), *[ptr(a) for a in outs], None, 0)
+    if rc:
+        raise LC3Error(rc, "lc3plus_plan_rtp_stamp")
+    return dict(zip(RTP_STAMP_OPTIONAL, outs), wire=wire)
+
+
+class _RtpStamp:
+    """The send side of the RTP framing for both batch kinds (lc3plus_{enc,dec}_batch_rtp_stamp; include/lc3plus_batch.h "RTP framing")."""
+
+    def rtp_stamp_device(self, max_packets, d_n_packets_ptr, d_pkt_route_ptr, d_pkt_seq_ptr, d_pkt_frame_ptr, d_pkt_offset_ptr, d_pkt_size_ptr, n_routes, n_frames,
+                         d_ssrc_ptr, d_ts_base_ptr, d_payload_type_ptr, ts_step, d_wire_ptr, wire_capacity, header_room=12, payload_room=0, d_pkt_flags_ptr=None,
+                         marker_mode=RTP_MARKER_NEVER, d_cell_status_ptr=None, d_resume_ptr=None, d_route_stats_ptr=None, d_pkt_status_ptr=None,
+                         d_next_ts_ptr=None, d_next_resume_ptr=None, hip_stream=None, sync=False):
+        """Raw device pointers only - the egress's packet list pkt_* [max_packets] with its length n_packets (one int64, read when the kernel runs), per route
+        ssrc, ts_base, payload_type [n_routes] and the optional cell_status [n_routes, n_frames], resume [n_routes] (uint8) and route_stats (the egress's
+        stats) -> an RTP header in the header room of every packet of the egress's wire buffer, payload_room bytes in front of the frame, and the optional
+        pkt_status [max_packets] (uint8), next_ts [n_routes], next_resume [n_routes] (uint8).  Stateless: nothing of the batch's streams is read or written.
+        Queued on hip_stream; returns at once unless sync."""
+        def p(x):
+            return C.c_void_p(x) if x else None
+        rc = self._ssf("_rtp_stamp")(self.h, int(max_packets), p(d_n_packets_ptr), p(d_pkt_route_ptr), p(d_pkt_seq_ptr), p(d_pkt_frame_ptr), p(d_pkt_offset_ptr),
+                                     p(d_pkt_size_ptr), p(d_pkt_flags_ptr), int(n_routes), int(n_frames), p(d_ssrc_ptr), p(d_ts_base_ptr), p(d_payload_type_ptr),
+                                     int(ts_step), int(marker_mode), p(d_cell_status_ptr), p(d_resume_ptr), p(d_route_stats_ptr), p(d_wire_ptr), int(wire_capacity),
+                                     int(header_room), int(payload_room), p(d_pkt_status_ptr), p(d_next_ts_ptr), p(d_next_resume_ptr), p(hip_stream),
+                                     1 if sync else 0)
+        if rc:
+            raise LC3Error(rc, self._ss + "_rtp_stamp")
+
+    def rtp_stamp(self, pkt_route, pkt_seq, pkt_frame, pkt_offset, pkt_size, ssrc, ts_base, payload_type, ts_step, n_frames, wire, header_room=12, payload_room=0,
+                  pkt_flags=None, n_packets=None, marker_mode=RTP_MARKER_NEVER, cell_status=None, resume=None, route_stats=None, wire_capacity=None,
+                  optional=RTP_STAMP_OPTIONAL):
+        """Host convenience: the arrays of plan_rtp_stamp uploaded, stamped on the device and downloaded -> the dict plan_rtp_stamp gives.  Device memory through
+        the HIP runtime (on the current device: the batch's, unless the caller has switched), freed before it returns."""
+        ins, wire, outs = _rtp_stamp_arrays(pkt_route, pkt_seq, pkt_frame, pkt_offset, pkt_size, pkt_flags, n_packets, ssrc, ts_base, payload_type, n_frames,
+                                            cell_status, resume, route_stats, wire, optional)
+        wcap = wire.size if wire_capacity is None else int(wire_capacity)
+        arrays = ins + [wire] + outs
+        with _on_device(arrays) as (v, back):
+            self.rtp_stamp_device(ins[1].size, v[0], v[1], v[2], v[3], v[4], v[5], ins[7].size, n_frames, v[7], v[8], v[9], ts_step, v[13], wcap, header_room,
+                                  payload_room, v[6], marker_mode, v[10], v[11], v[12], v[14], v[15], v[16], sync=True)
+            for k in range(13, 17):
+                back(k)
+        return dict(zip(RTP_STAMP_OPTIONAL, outs), wire=wire)
+
+
 class _StreamLifecycle:
     """Reset, export and import single streams (lc3plus_{enc,dec}_batch_{reset,export,import}_streams; include/lc3plus_batch.h).  Stream lists are host
     sequences of indices; blobs are stream_state_size bytes per stream."""
@@ -588,7 +789,7 @@ def stream_header_ok(header, blob):
     return bool(load_library().lc3plus_stream_header_ok(h.ctypes.data, b.ctypes.data))
 
 
-class Batch(_StreamLifecycle, _Egress):
+class Batch(_StreamLifecycle, _Egress, _RtpStamp):
     """n_streams independent encoders (lc3plus_enc_batch_*), state resident on the GPU between encode() calls."""
 
     def __init__(self, n_streams, samplerate, channels, frame_ms, hrmode, bitrates, device=-1):
@@ -1123,7 +1324,7 @@ def plan_ingest(n_streams, channels, stream, seq, offsets, num_bytes, base, n_fr
     return dict(zip(ING_OUTPUTS, outs))
 
 
-class DecBatch(_StreamLifecycle, _Egress):
+class DecBatch(_StreamLifecycle, _Egress, _RtpStamp):
     """n_streams independent decoders (lc3plus_dec_batch_*), state resident on the GPU between decode() calls."""
 
     def __init__(self, n_streams, samplerate, channels, frame_ms, hrmode, num_bytes, device=-1):
@@ -1319,6 +1520,35 @@ class DecBatch(_StreamLifecycle, _Egress):
                 if d.value:
                     hip.hipFree(d)
         return dict(zip(ING_OUTPUTS, outs))
+
+    def rtp_parse_device(self, n_items, d_ring_ptr, ring_capacity, d_dg_offsets_ptr, d_dg_sizes_ptr, n_ssrc, d_ssrc_key_ptr, d_ssrc_stream_ptr, d_stream_ptr,
+                         d_seq_ptr, d_offsets_ptr, d_num_bytes_ptr, d_payload_type_ptr=None, payload_room=0, d_timestamp_ptr=None, d_marker_ptr=None,
+                         d_status_ptr=None, d_stats_ptr=None, hip_stream=None, sync=False):
+        """The receive side of the RTP framing (lc3plus_dec_batch_rtp_parse): raw device pointers only - the datagrams dg_offsets (int64) / dg_sizes [n_items] in
+        ring, the senders ssrc_key (ascending as uint32) / ssrc_stream [n_ssrc], optional payload_type [n_streams] -> stream, seq, offsets (int64), num_bytes
+        [n_items], as ingest_device and probe_device take them (frames = ring, seq_bits = 16), and the optional timestamp [n_items], marker, status (uint8)
+        [n_items] and stats [RTP_STATS_WORDS].  Stateless: nothing of the batch's streams is read or written.  Queued on hip_stream; returns at once unless
+        sync."""
+        def p(x):
+            return C.c_void_p(x) if x else None
+        rc = self.lib.lc3plus_dec_batch_rtp_parse(self.h, int(n_items), p(d_ring_ptr), int(ring_capacity), p(d_dg_offsets_ptr), p(d_dg_sizes_ptr), int(n_ssrc),
+                                                  p(d_ssrc_key_ptr), p(d_ssrc_stream_ptr), p(d_payload_type_ptr), int(payload_room), p(d_stream_ptr), p(d_seq_ptr),
+                                                  p(d_offsets_ptr), p(d_num_bytes_ptr), p(d_timestamp_ptr), p(d_marker_ptr), p(d_status_ptr), p(d_stats_ptr),
+                                                  p(hip_stream), 1 if sync else 0)
+        if rc:
+            raise LC3Error(rc, "lc3plus_dec_batch_rtp_parse")
+
+    def rtp_parse(self, ring, dg_offsets, dg_sizes, ssrc_key, ssrc_stream, payload_type=None, payload_room=0, optional=RTP_PARSE_OPTIONAL, ring_capacity=None):
+        """Host convenience: the arrays of plan_rtp_parse uploaded, parsed on the device and downloaded -> the dict plan_rtp_parse gives.  Device memory through
+        the HIP runtime as in probe(), freed before it returns."""
+        ins, outs = _rtp_parse_arrays(self.n_streams, ring, dg_offsets, dg_sizes, ssrc_key, ssrc_stream, payload_type, optional)
+        cap = ins[0].size if ring_capacity is None else int(ring_capacity)
+        with _on_device(ins + outs) as (v, back):
+            self.rtp_parse_device(ins[1].size, v[0], cap, v[1], v[2], ins[3].size, v[3], v[4], v[6], v[7], v[8], v[9], v[5], payload_room, v[10], v[11], v[12],
+                                  v[13], sync=True)
+            for k in range(6, 14):
+                back(k)
+        return dict(zip(RTP_PARSE_OUTPUTS, outs))
 
     def decode_traced(self, frames, bfi=None, bps=16):
         frames, T, stride, bfi, pcm, status = self._prep(frames, bfi, bps)

@@ -25,6 +25,7 @@
 #include "lc3_probe_shim.h"
 #include "lc3_ingest_shim.h"
 #include "lc3_egress_shim.h"
+#include "lc3_rtp_shim.h"
 
 #ifndef M_PI
 #define M_PI 3.14159265358979323846
@@ -2150,6 +2151,205 @@ LC3_Error lc3plus_dec_batch_egress(lc3plus_dec_batch* b,
     LC3_Error e = egress_check(&a, -1);
     if (e) return e;
     return egress_queue(b->dev, 1, b->n_streams, &a, hip_stream, sync);
+}
+/* ---- RTP framing (include/lc3plus_batch.h "RTP framing"; lc3_rtp_shim.h) ---- */
+/* what a parse call takes behind its batch, in the header's order */
+typedef struct {
+    int64_t n_items; const void* ring; int64_t ring_capacity; const int64_t* dg_offsets; const int32_t* dg_sizes;
+    int n_ssrc; const int32_t* ssrc_key; const int32_t* ssrc_stream; const int32_t* payload_type; int payload_room;
+    int32_t* stream; int32_t* seq; int64_t* offsets; int32_t* num_bytes; int32_t* timestamp; uint8_t* marker; uint8_t* status; int32_t* stats;
+} rtp_parse_args;
+/* the checks every parse call makes first, in the header's order */
+static LC3_Error rtp_parse_check(const rtp_parse_args* a)
+{
+    if (!a->ring || !a->dg_offsets || !a->dg_sizes || !a->ssrc_key || !a->ssrc_stream || !a->stream || !a->seq || !a->offsets || !a->num_bytes) return LC3_NULL_ERROR;
+    if (a->n_items <= 0 || a->n_items >= LC3R_MAX_ITEMS || a->ring_capacity < 0 || a->n_ssrc <= 0 || a->payload_room < 0 || a->payload_room > LC3R_MAX_PAYLOAD_ROOM)
+        return LC3_ERROR;
+    return LC3_OK;
+}
+/* the rule on the host: the kernels' steps (lc3_rtp.inc) on the text they run */
+LC3_Error lc3plus_plan_rtp_parse(int n_streams, int64_t n_items,
+    const void* ring, int64_t ring_capacity, const int64_t* dg_offsets, const int32_t* dg_sizes,
+    int n_ssrc, const int32_t* ssrc_key, const int32_t* ssrc_stream, const int32_t* payload_type, int payload_room,
+    int32_t* stream, int32_t* seq, int64_t* offsets, int32_t* num_bytes, int32_t* timestamp, uint8_t* marker, uint8_t* status, int32_t* stats,
+    void* hip_stream, int sync)
+{
+    const rtp_parse_args a = {n_items, ring, ring_capacity, dg_offsets, dg_sizes, n_ssrc, ssrc_key, ssrc_stream, payload_type, payload_room,
+                              stream, seq, offsets, num_bytes, timestamp, marker, status, stats};
+    const LC3_Error e = rtp_parse_check(&a);
+    if (e) return e;
+    if (n_streams <= 0) return LC3_ERROR;
+    const lc3r_items out = {stream, seq, (long long*)offsets, num_bytes, timestamp, marker, status};
+    if (stats) memset(stats, 0, sizeof(int32_t) * LC3R_STATS_WORDS);
+    for (int64_t i = 0; i < n_items; i++) {
+        const lc3r_item it = lc3r_parse((const uint8_t*)ring, ring_capacity, dg_offsets[i], dg_sizes[i], ssrc_key, ssrc_stream, n_ssrc, n_streams, payload_type,
+                                        payload_room);
+        lc3r_item_out(&out, i, &it);
+        if (stats) stats[it.status]++;
+    }
+    return LC3_OK;
+}
+/* the SSRC table in the order the search needs: keys ascending as uint32, each with its stream (an insertion sort: tables are built once and are short) */
+LC3_Error lc3plus_rtp_sort_ssrc(int n, int32_t* ssrc_key, int32_t* ssrc_stream)
+{
+    if (!ssrc_key || !ssrc_stream) return LC3_NULL_ERROR;
+    if (n <= 0) return LC3_ERROR;
+    for (int i = 1; i < n; i++) {
+        const int32_t k = ssrc_key[i], v = ssrc_stream[i];
+        int j = i;
+        for (; j > 0 && (uint32_t)ssrc_key[j - 1] > (uint32_t)k; j--) { ssrc_key[j] = ssrc_key[j - 1]; ssrc_stream[j] = ssrc_stream[j - 1]; }
+        ssrc_key[j] = k; ssrc_stream[j] = v;
+    }
+    for (int i = 1; i < n; i++) if (ssrc_key[i] == ssrc_key[i - 1]) return LC3_ERROR;
+    return LC3_OK;
+}
+/* what a stamp call takes behind its batch, in the header's order */
+typedef struct {
+    int64_t max_packets; const int64_t* n_packets;
+    const int32_t* pkt_route; const int32_t* pkt_seq; const int32_t* pkt_frame; const int64_t* pkt_offset; const int32_t* pkt_size; const uint8_t* pkt_flags;
+    int n_routes; int n_frames; const int32_t* ssrc; const int32_t* ts_base; const int32_t* payload_type; int ts_step;
+    int marker_mode; const uint8_t* cell_status; const uint8_t* resume; const int32_t* route_stats;
+    void* wire; int64_t wire_capacity; int header_room; int payload_room;
+    uint8_t* pkt_status; int32_t* next_ts; uint8_t* next_resume;
+} rtp_stamp_args;
+/* the checks every stamp call makes first, in the header's order */
+static LC3_Error rtp_stamp_check(const rtp_stamp_args* a)
+{
+    if (!a->n_packets || !a->pkt_route || !a->pkt_seq || !a->pkt_frame || !a->pkt_offset || !a->pkt_size || !a->ssrc || !a->ts_base || !a->payload_type || !a->wire)
+        return LC3_NULL_ERROR;
+    if (a->max_packets <= 0 || a->n_routes <= 0 || a->n_frames <= 0 || a->wire_capacity < 0 || a->payload_room < 0 || a->header_room < LC3R_FIXED ||
+        a->header_room - LC3R_FIXED < a->payload_room)
+        return LC3_ERROR;
+    if (a->marker_mode != LC3R_MARKER_NEVER && a->marker_mode != LC3R_MARKER_AFTER_HOLE) return LC3_ERROR;
+    if ((a->marker_mode == LC3R_MARKER_AFTER_HOLE || a->next_resume) && !a->cell_status) return LC3_ERROR;
+    return LC3_OK;
+}
+static lc3r_stamp_in rtp_stamp_in(const rtp_stamp_args* a)
+{
+    const lc3r_stamp_in q = {a->pkt_route, a->pkt_seq, a->pkt_frame, (const long long*)a->pkt_offset, a->pkt_size, a->pkt_flags, a->ssrc, a->ts_base, a->payload_type,
+                             a->cell_status, a->resume, a->route_stats, a->n_routes, a->n_frames, a->ts_step, a->marker_mode, a->header_room, a->payload_room,
+                             (long long)a->wire_capacity};
+    return q;
+}
+LC3_Error lc3plus_plan_rtp_stamp(int64_t max_packets, const int64_t* n_packets,
+    const int32_t* pkt_route, const int32_t* pkt_seq, const int32_t* pkt_frame, const int64_t* pkt_offset, const int32_t* pkt_size, const uint8_t* pkt_flags,
+    int n_routes, int n_frames, const int32_t* ssrc, const int32_t* ts_base, const int32_t* payload_type, int ts_step,
+    int marker_mode, const uint8_t* cell_status, const uint8_t* resume, const int32_t* route_stats,
+    void* wire, int64_t wire_capacity, int header_room, int payload_room,
+    uint8_t* pkt_status, int32_t* next_ts, uint8_t* next_resume, void* hip_stream, int sync)
+{
+    const rtp_stamp_args a = {max_packets, n_packets, pkt_route, pkt_seq, pkt_frame, pkt_offset, pkt_size, pkt_flags, n_routes, n_frames, ssrc, ts_base, payload_type,
+                              ts_step, marker_mode, cell_status, resume, route_stats, wire, wire_capacity, header_room, payload_room, pkt_status, next_ts, next_resume};
+    const LC3_Error e = rtp_stamp_check(&a);
+    if (e) return e;
+    const lc3r_stamp_in q = rtp_stamp_in(&a);
+    const int64_t n = *n_packets < max_packets ? *n_packets : max_packets;
+    for (int64_t p = 0; p < n; p++) {
+        uint32_t hdr[3];
+        long long at = 0;
+        const int st = lc3r_stamp(&q, p, hdr, &at);
+        if (st == LC3R_STAMPED) lc3r_header_out((uint8_t*)wire, at, hdr);
+        if (pkt_status) pkt_status[p] = (uint8_t)st;
+    }
+    if (next_ts || next_resume)
+        for (int r = 0; r < n_routes; r++) lc3r_route_out(&q, r, next_ts, next_resume);
+    return LC3_OK;
+}
+/* the sibling library with the RTP kernels, loaded as the egress's is; NULL where it is missing */
+typedef int (*rtp_parse_fn)(const lc3rtp_parse_call*);
+typedef int (*rtp_stamp_fn)(const lc3rtp_stamp_call*);
+static pthread_once_t rtp_once = PTHREAD_ONCE_INIT;
+static rtp_parse_fn rtp_parse_run;
+static rtp_stamp_fn rtp_stamp_run;
+static void rtp_load(void)
+{
+    Dl_info di;
+    char path[4096];
+    if (!dladdr((void*)&rtp_load, &di) || !di.dli_fname) return;
+    const char* slash = strrchr(di.dli_fname, '/');
+    const size_t dir = slash ? (size_t)(slash - di.dli_fname) + 1 : 0;
+    static const char name[] = "liblc3plus_rtp_hip.so";
+    if (dir + sizeof name > sizeof path) return;
+    memcpy(path, di.dli_fname, dir);
+    memcpy(path + dir, name, sizeof name);
+    void* h = dlopen(path, RTLD_NOW | RTLD_LOCAL);
+    if (!h) { fprintf(stderr, "lc3plus_hip: the RTP framing's library is missing: %s\n", dlerror()); return; }
+    rtp_parse_fn parse = (rtp_parse_fn)dlsym(h, "lc3rtp_parse_run");
+    rtp_stamp_fn stamp = (rtp_stamp_fn)dlsym(h, "lc3rtp_stamp_run");
+    if (parse && stamp) { rtp_parse_run = parse; rtp_stamp_run = stamp; }
+}
+/* of a batch: its device and stream (dev; decoder: which kind of context it is).  No stream state, no configuration, no buffer */
+static int rtp_device(void* dev, int decoder, int want_stream, int32_t* device, void** own)
+{
+    if (decoder) {
+        const lc3d_plan* plan = NULL; const lc3d_dchan* tab = NULL; int tab_n = 0;
+        return lc3hip_dec_probe_args(dev, device, &plan, &tab, &tab_n, own);
+    }
+    return lc3hip_stream_args(dev, want_stream, device, own);
+}
+LC3_Error lc3plus_dec_batch_rtp_parse(lc3plus_dec_batch* b, int64_t n_items,
+    const void* ring, int64_t ring_capacity, const int64_t* dg_offsets, const int32_t* dg_sizes,
+    int n_ssrc, const int32_t* ssrc_key, const int32_t* ssrc_stream, const int32_t* payload_type, int payload_room,
+    int32_t* stream, int32_t* seq, int64_t* offsets, int32_t* num_bytes, int32_t* timestamp, uint8_t* marker, uint8_t* status, int32_t* stats,
+    void* hip_stream, int sync)
+{
+    if (!b) return LC3_NULL_ERROR;
+    const rtp_parse_args a = {n_items, ring, ring_capacity, dg_offsets, dg_sizes, n_ssrc, ssrc_key, ssrc_stream, payload_type, payload_room,
+                              stream, seq, offsets, num_bytes, timestamp, marker, status, stats};
+    const LC3_Error e = rtp_parse_check(&a);
+    if (e) return e;
+    lc3rtp_parse_call q;
+    memset(&q, 0, sizeof q);
+    void* own = NULL;
+    if (rtp_device(b->dev, 1, 0, &q.device, &own)) return LC3_ERROR;
+    pthread_once(&rtp_once, rtp_load);
+    if (!rtp_parse_run) return LC3_ERROR;
+    q.n_streams = b->n_streams; q.n_ssrc = n_ssrc; q.payload_room = payload_room; q.sync = sync; q.n_items = (long long)n_items; q.ring_capacity = (long long)ring_capacity;
+    q.ring = ring; q.dg_offsets = (const long long*)dg_offsets; q.dg_sizes = dg_sizes; q.ssrc_key = ssrc_key; q.ssrc_stream = ssrc_stream; q.payload_type = payload_type;
+    q.out.stream = stream; q.out.seq = seq; q.out.offsets = (long long*)offsets; q.out.num_bytes = num_bytes; q.out.timestamp = timestamp; q.out.marker = marker;
+    q.out.status = status; q.stats = stats; q.hip_stream = hip_stream ? hip_stream : own;
+    return rtp_parse_run(&q) ? LC3_ERROR : LC3_OK;
+}
+/* both stamp entry points end here */
+static LC3_Error rtp_stamp_queue(void* dev, int decoder, const rtp_stamp_args* a, void* hip_stream, int sync)
+{
+    lc3rtp_stamp_call q;
+    memset(&q, 0, sizeof q);
+    void* own = NULL;
+    if (rtp_device(dev, decoder, !hip_stream, &q.device, &own)) return LC3_ERROR;
+    pthread_once(&rtp_once, rtp_load);
+    if (!rtp_stamp_run) return LC3_ERROR;
+    q.sync = sync; q.max_packets = (long long)a->max_packets; q.n_packets = (const long long*)a->n_packets; q.in = rtp_stamp_in(a);
+    q.wire = a->wire; q.pkt_status = a->pkt_status; q.next_ts = a->next_ts; q.next_resume = a->next_resume; q.hip_stream = hip_stream ? hip_stream : own;
+    return rtp_stamp_run(&q) ? LC3_ERROR : LC3_OK;
+}
+LC3_Error lc3plus_enc_batch_rtp_stamp(lc3plus_batch* b, int64_t max_packets, const int64_t* n_packets,
+    const int32_t* pkt_route, const int32_t* pkt_seq, const int32_t* pkt_frame, const int64_t* pkt_offset, const int32_t* pkt_size, const uint8_t* pkt_flags,
+    int n_routes, int n_frames, const int32_t* ssrc, const int32_t* ts_base, const int32_t* payload_type, int ts_step,
+    int marker_mode, const uint8_t* cell_status, const uint8_t* resume, const int32_t* route_stats,
+    void* wire, int64_t wire_capacity, int header_room, int payload_room,
+    uint8_t* pkt_status, int32_t* next_ts, uint8_t* next_resume, void* hip_stream, int sync)
+{
+    if (!b) return LC3_NULL_ERROR;
+    const rtp_stamp_args a = {max_packets, n_packets, pkt_route, pkt_seq, pkt_frame, pkt_offset, pkt_size, pkt_flags, n_routes, n_frames, ssrc, ts_base, payload_type,
+                              ts_step, marker_mode, cell_status, resume, route_stats, wire, wire_capacity, header_room, payload_room, pkt_status, next_ts, next_resume};
+    const LC3_Error e = rtp_stamp_check(&a);
+    if (e) return e;
+    return rtp_stamp_queue(b->dev, 0, &a, hip_stream, sync);
+}
+LC3_Error lc3plus_dec_batch_rtp_stamp(lc3plus_dec_batch* b, int64_t max_packets, const int64_t* n_packets,
+    const int32_t* pkt_route, const int32_t* pkt_seq, const int32_t* pkt_frame, const int64_t* pkt_offset, const int32_t* pkt_size, const uint8_t* pkt_flags,
+    int n_routes, int n_frames, const int32_t* ssrc, const int32_t* ts_base, const int32_t* payload_type, int ts_step,
+    int marker_mode, const uint8_t* cell_status, const uint8_t* resume, const int32_t* route_stats,
+    void* wire, int64_t wire_capacity, int header_room, int payload_room,
+    uint8_t* pkt_status, int32_t* next_ts, uint8_t* next_resume, void* hip_stream, int sync)
+{
+    if (!b) return LC3_NULL_ERROR;
+    const rtp_stamp_args a = {max_packets, n_packets, pkt_route, pkt_seq, pkt_frame, pkt_offset, pkt_size, pkt_flags, n_routes, n_frames, ssrc, ts_base, payload_type,
+                              ts_step, marker_mode, cell_status, resume, route_stats, wire, wire_capacity, header_room, payload_room, pkt_status, next_ts, next_resume};
+    const LC3_Error e = rtp_stamp_check(&a);
+    if (e) return e;
+    return rtp_stamp_queue(b->dev, 1, &a, hip_stream, sync);
 }
 LC3_Error lc3plus_dec_batch_set_input_ready(lc3plus_dec_batch* b, int ready)
 {

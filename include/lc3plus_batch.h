@@ -707,6 +707,129 @@ LC3_Error lc3plus_plan_egress(int n_streams,
 /* the bytes of `work` for such a call; 0 for arguments the calls refuse */
 int64_t lc3plus_egress_work_bytes(int n_routes, int n_frames);
 
+/* ---- RTP framing: parse received datagrams, stamp sent packets, on the device ------------------------------------------------------------------------------
+ * The last step to the wire on both sides.  The ingest takes a flat item list of stream index, sequence number, payload offset and payload size; what a NIC
+ * path leaves in device memory is datagrams, each an RTP header (RFC 3550 5.1: the fixed header, a CSRC list, a header extension with 5.3.1's length, padding)
+ * in front of its payload, from senders known by their SSRC.  The egress leaves header_room bytes in front of every frame of its wire buffer; what goes out
+ * is an RTP header there.  lc3plus_dec_batch_rtp_parse turns the first into the second and lc3plus_*_batch_rtp_stamp fills the third, so that
+ * datagrams -> parse -> probe -> ingest -> set_frame_counts + decode_packed and encode_packed -> egress -> stamp run on one HIP stream with no host wait.
+ * A payload format's own payload header (the LC3plus table of contents is one) stays with the caller: the stamp leaves payload_room untouched bytes between
+ * the RTP header and the frame, and the parse skips payload_room bytes.  SRTP, the contents of RTCP packets and several frames per packet are not handled.
+ *
+ * Every pointer but `batch` is a device pointer and is read when the kernels run, so the call queued before on the same stream may produce it.  Both calls are
+ * STATELESS and allocate nothing: they borrow the batch's device and n_streams and nothing else, no stream state, configuration or buffer of the batch is read
+ * or written, and either may run beside an encode or decode call of the same batch.  They are queued on hip_stream (NULL: the batch's stream) and return at
+ * once unless sync.  No output may overlap an input or another output.  On a shard's batch they work as on any batch, with that shard's n_streams and LOCAL
+ * stream indices.
+ *
+ * PARSE.  Item i is the datagram ring[dg_offsets[i] .. dg_offsets[i] + dg_sizes[i]); multi-byte fields are big-endian.
+ *   ring, ring_capacity   : the buffer the datagrams lie in and its size in bytes
+ *   dg_offsets, dg_sizes  : [n_items] each datagram's byte offset in ring (int64) and its size
+ *   ssrc_key, ssrc_stream : [n_ssrc] the senders: an SSRC and the stream it feeds, the keys ascending as uint32 (lc3plus_rtp_sort_ssrc brings a table into
+ *                           that order)
+ *   payload_type          : [n_streams] the payload type each stream accepts, < 0: any; or NULL: any for all
+ *   payload_room          : bytes of payload header behind the RTP header that belong to the caller, 0 ... 4096
+ *   stream, seq, offsets (int64), num_bytes : [n_items] the item arrays of the ingest and the probe
+ *   timestamp [n_items], marker, status (uint8) [n_items], stats [LC3PLUS_RTP_STATS_WORDS] : each may be NULL
+ * The first check that fails gives the item's status:
+ *   1 RANGE        dg_offsets[i] < 0, dg_sizes[i] < 0 or offset + size > ring_capacity (computed without overflow); such a datagram is never read
+ *   2 SHORT        size < 12
+ *   3 VERSION      byte 0 >> 6 != 2
+ *   4 RTCP         byte 1 in 192 ... 223: an RTCP packet on the same port (RFC 5761 4)
+ *   5 HEADER       with h = 12 + 4 * (byte 0 & 15), the CSRC list: h > size; with the X bit (byte 0 & 16) also h + 4 > size, and then, with
+ *                  h += 4 + 4 * BE16(at h + 2), the extension: h > size
+ *   6 PADDING      with the P bit (byte 0 & 32) pad is the datagram's last byte, else 0: pad == 0 or h + pad > size
+ *   7 PAYLOAD_ROOM size - h - pad < payload_room
+ *   8 UNKNOWN_SSRC the lower bound of the SSRC (bytes 8 ... 11 as uint32) in ssrc_key is no equal key, or ssrc_stream there lies outside [0, n_streams).  Host
+ *                  and device run one search, so a table that is not sorted gives the same answer on both, whatever it is
+ *   9 PAYLOAD_TYPE payload_type is given, payload_type[s] >= 0 and it differs from byte 1 & 127
+ * An OK item gets stream = s, seq = BE16(bytes 2 .. 3), offsets = dg_offsets[i] + h + payload_room, num_bytes = size - h - pad - payload_room (0 is possible: the
+ * ingest calls it EMPTY), timestamp = BE32(bytes 4 .. 7) and marker = byte 1 >> 7.  Every other item gets stream = -1 and 0 everywhere else: the ingest drops it
+ * as BAD_STREAM and the probe reads it as lost, so the arrays go to both as they are, with frames = ring and seq_bits = 16.  stats[k] is the number of items
+ * with status k; the call zeroes it, and words 10 ... 15 stay 0.  Of a datagram only bytes 0 ... 11, the two bytes of the extension's length and, with the P bit,
+ * the last byte are read, and of the ring only aligned 32-bit words that hold such a byte.
+ * Refused calls queue nothing, checked in this order before anything of the batch or the device is touched: a NULL batch, ring, dg_offsets, dg_sizes, ssrc_key,
+ * ssrc_stream, stream, seq, offsets or num_bytes (LC3_NULL_ERROR); then n_items <= 0, n_items >= 2^29, ring_capacity < 0, n_ssrc <= 0 or a payload_room outside
+ * [0, 4096] (LC3_ERROR).
+ *
+ * STAMP.  For an encoder batch (a sender) or a decoder batch (a forwarder), as the egress has it.  The packet list is the egress's, its wire buffer the egress's
+ * wire buffer, header_room the egress's header_room.
+ *   max_packets, n_packets : the list arrays' length, and one int64 in device memory: the list's length, read when the kernel runs
+ *   pkt_route, pkt_seq, pkt_frame, pkt_offset (int64), pkt_size, pkt_flags (uint8, may be NULL) : the list
+ *   ssrc, ts_base, payload_type : [n_routes] each route's SSRC, the timestamp of its frame 0 and its payload type; ts_step: a frame's samples on the RTP clock
+ *   marker_mode, cell_status [n_routes][n_frames], resume [n_routes] (uint8), route_stats [n_routes][LC3PLUS_EGR_STATS_WORDS] : see below; the last three may
+ *                           be NULL
+ *   wire, wire_capacity, header_room, payload_room : header_room >= 12 + payload_room
+ *   pkt_status [max_packets] (uint8), next_ts [n_routes], next_resume [n_routes] (uint8) : each may be NULL
+ * For each packet p < min(*n_packets, max_packets), with r = pkt_route[p] and t = pkt_frame[p], in this order: ST_BAD_ROUTE where r lies outside [0, n_routes);
+ * ST_OVERFLOW where pkt_flags is given and has LC3PLUS_EGR_PKT_OVERFLOW; ST_RANGE where pkt_offset < 0, pkt_size < header_room, pkt_offset + pkt_size >
+ * wire_capacity or t lies outside [0, n_frames).  Such a packet writes nothing.  Every other is STAMPED: the 12 bytes at
+ * wire + pkt_offset + header_room - payload_room - 12 become 0x80, M << 7 | (payload_type[r] & 127), BE16(pkt_seq & 0xFFFF),
+ * BE32(ts_base[r] + t * ts_step mod 2^32), BE32(ssrc[r]).  No other byte of wire is modified: not the payload_room bytes, not the rest of the header room, not the
+ * payload.  Entries of pkt_status at or behind *n_packets are not written.
+ * M is 0 under LC3PLUS_RTP_MARKER_NEVER.  Under LC3PLUS_RTP_MARKER_AFTER_HOLE, which needs cell_status (the egress's), M is 1 where the packet starts a
+ * talkspurt: at t > 0 where cell_status[r][t - 1] lacks LC3PLUS_EGR_SENT, at t == 0 where resume is given and resume[r] != 0.
+ * Per route, with c = route_stats[r][0] (the egress's stats) clamped to [0, n_frames], n_frames where route_stats is NULL: next_ts[r] = ts_base[r] + c * ts_step;
+ * next_resume[r] = resume[r] (0 for NULL) where c == 0, otherwise 1 where cell (r, c - 1) is not SENT and else 0 - the resume of the next call.
+ * Refused calls queue nothing, checked in this order: a NULL batch, n_packets, pkt_route, pkt_seq, pkt_frame, pkt_offset, pkt_size, ssrc, ts_base, payload_type
+ * or wire (LC3_NULL_ERROR); then max_packets <= 0, n_routes <= 0, n_frames <= 0, wire_capacity < 0, payload_room < 0, header_room < 12 + payload_room, a bad
+ * marker_mode, MARKER_AFTER_HOLE without cell_status, or next_resume without cell_status (LC3_ERROR).
+ *
+ * The kernels live in liblc3plus_rtp_hip.so, which this library loads from its own directory on the first RTP call: where that file is missing the call
+ * returns LC3_ERROR and nothing else changes. */
+#define LC3PLUS_RTP_OK            0
+#define LC3PLUS_RTP_RANGE         1
+#define LC3PLUS_RTP_SHORT         2
+#define LC3PLUS_RTP_VERSION       3
+#define LC3PLUS_RTP_RTCP          4
+#define LC3PLUS_RTP_HEADER        5
+#define LC3PLUS_RTP_PADDING       6
+#define LC3PLUS_RTP_PAYLOAD_ROOM  7
+#define LC3PLUS_RTP_UNKNOWN_SSRC  8
+#define LC3PLUS_RTP_PAYLOAD_TYPE  9
+#define LC3PLUS_RTP_STATS_WORDS   16
+#define LC3PLUS_RTP_STAMPED       1
+#define LC3PLUS_RTP_ST_BAD_ROUTE  2
+#define LC3PLUS_RTP_ST_OVERFLOW   4
+#define LC3PLUS_RTP_ST_RANGE      8
+#define LC3PLUS_RTP_MARKER_NEVER      0
+#define LC3PLUS_RTP_MARKER_AFTER_HOLE 1
+LC3_Error lc3plus_dec_batch_rtp_parse(lc3plus_dec_batch* batch, int64_t n_items,
+    const void* ring, int64_t ring_capacity, const int64_t* dg_offsets, const int32_t* dg_sizes,
+    int n_ssrc, const int32_t* ssrc_key, const int32_t* ssrc_stream, const int32_t* payload_type, int payload_room,
+    int32_t* stream, int32_t* seq, int64_t* offsets, int32_t* num_bytes, int32_t* timestamp, uint8_t* marker, uint8_t* status, int32_t* stats,
+    void* hip_stream, int sync);
+/* The same rule on the host alone, no device: the same arrays in host memory, n_streams given instead of a batch; the datagrams are read byte by byte.
+ * hip_stream and sync are ignored.  The refusals of the call above in their order, then n_streams <= 0 (LC3_ERROR). */
+LC3_Error lc3plus_plan_rtp_parse(int n_streams, int64_t n_items,
+    const void* ring, int64_t ring_capacity, const int64_t* dg_offsets, const int32_t* dg_sizes,
+    int n_ssrc, const int32_t* ssrc_key, const int32_t* ssrc_stream, const int32_t* payload_type, int payload_room,
+    int32_t* stream, int32_t* seq, int64_t* offsets, int32_t* num_bytes, int32_t* timestamp, uint8_t* marker, uint8_t* status, int32_t* stats,
+    void* hip_stream, int sync);
+/* Host: sorts an SSRC table of n entries in place, keys ascending as uint32, each key's stream with it.  LC3_NULL_ERROR for a NULL array, LC3_ERROR for
+ * n <= 0 and for a key that occurs twice (the table is sorted all the same). */
+LC3_Error lc3plus_rtp_sort_ssrc(int n, int32_t* ssrc_key, int32_t* ssrc_stream);
+LC3_Error lc3plus_enc_batch_rtp_stamp(lc3plus_batch* batch, int64_t max_packets, const int64_t* n_packets,
+    const int32_t* pkt_route, const int32_t* pkt_seq, const int32_t* pkt_frame, const int64_t* pkt_offset, const int32_t* pkt_size, const uint8_t* pkt_flags,
+    int n_routes, int n_frames, const int32_t* ssrc, const int32_t* ts_base, const int32_t* payload_type, int ts_step,
+    int marker_mode, const uint8_t* cell_status, const uint8_t* resume, const int32_t* route_stats,
+    void* wire, int64_t wire_capacity, int header_room, int payload_room,
+    uint8_t* pkt_status, int32_t* next_ts, uint8_t* next_resume, void* hip_stream, int sync);
+LC3_Error lc3plus_dec_batch_rtp_stamp(lc3plus_dec_batch* batch, int64_t max_packets, const int64_t* n_packets,
+    const int32_t* pkt_route, const int32_t* pkt_seq, const int32_t* pkt_frame, const int64_t* pkt_offset, const int32_t* pkt_size, const uint8_t* pkt_flags,
+    int n_routes, int n_frames, const int32_t* ssrc, const int32_t* ts_base, const int32_t* payload_type, int ts_step,
+    int marker_mode, const uint8_t* cell_status, const uint8_t* resume, const int32_t* route_stats,
+    void* wire, int64_t wire_capacity, int header_room, int payload_room,
+    uint8_t* pkt_status, int32_t* next_ts, uint8_t* next_resume, void* hip_stream, int sync);
+/* The same rule on the host alone: the same arrays in host memory (n_packets too), no batch.  hip_stream and sync are ignored.  The refusals of the calls above
+ * in their order. */
+LC3_Error lc3plus_plan_rtp_stamp(int64_t max_packets, const int64_t* n_packets,
+    const int32_t* pkt_route, const int32_t* pkt_seq, const int32_t* pkt_frame, const int64_t* pkt_offset, const int32_t* pkt_size, const uint8_t* pkt_flags,
+    int n_routes, int n_frames, const int32_t* ssrc, const int32_t* ts_base, const int32_t* payload_type, int ts_step,
+    int marker_mode, const uint8_t* cell_status, const uint8_t* resume, const int32_t* route_stats,
+    void* wire, int64_t wire_capacity, int header_room, int payload_room,
+    uint8_t* pkt_status, int32_t* next_ts, uint8_t* next_resume, void* hip_stream, int sync);
+
 /* ---- Sharded batches: one call drives encoders or decoders on several GPUs ------------------------------------------------------------------
  * Streams are independent, so a sharded batch is n_devices ordinary batches, each owning a contiguous block of the n_streams streams on a device of its
  * own; nothing is exchanged between devices.  Stream indices are GLOBAL (0 ... n_streams - 1) and arrays are laid out over all n_streams exactly as the
