@@ -151,6 +151,8 @@ struct lc3hip_ctx {
      * call writes and its other kernels read.  One buffer: ragged calls are ordered on the caller's stream, none overlaps another.  rag: the call being queued is one - 1 with
      * per-frame bitrates, 2 without (its sizes are the carried ones: every frame of a stream has the bytes of the stream's configuration). */
     const int32_t* counts; int32_t* d_cnt; int rag;
+    /* the index of the last run the previous pipelined call made (its ev_m / ev_f): what a call that overlaps it waits on; set with ahead_ok, read only while that is set */
+    int ahead_last;
     int input_ready, ahead_ok, ahead_T, ahead_R;   /* lc3hip_set_input_ready: side kernels of a call beside the previous call's tail */   /* split path (lc3_enc_front.inc) */      /* per channel-frame status bits of the last call (LC3D_ENC_ST_*) */
     /* host-pointer pipeline (lc3hip_encode_host): two chunk slots, each with device staging and (for pageable callers) pinned staging */
     void* hp_dpcm[2]; void* hp_pin_in[2]; size_t hp_pcm_cap, hp_pin_in_cap;
@@ -739,18 +741,22 @@ static int enc_pipelined(lc3hip_ctx* c, enc_call* q)
         HIPCHK(hipEventRecord(c->ev_fork, s)); HIPCHK(hipStreamWaitEvent(c->s_pre, c->ev_fork, 0)); HIPCHK(hipStreamWaitEvent(c->s_fr, c->ev_fork, 0));
         if (five) { HIPCHK(hipStreamWaitEvent(c->s_pit, c->ev_fork, 0)); HIPCHK(hipStreamWaitEvent(c->s_ln, c->ev_fork, 0)); }
     } else {
-        HIPCHK(hipStreamWaitEvent(c->s_pre, c->ev_m[R - 1], 0));    /* the resampler reads the hand-over the previous call's last front kernel wrote */
+        /* The previous call's last run: the index it made last (ahead_last), not R - 1.  A call makes ceil(n / Tr) runs, which equals R for every n with the default
+         * run lengths (tests/test_call_shapes_cpu.py: the run invariant) - the two indices are then the same - but not with LC3PLUS_ENC_RUN_FRAMES or LC3PLUS_ENC_RUNS
+         * (run length 1, n = 20: R = 16, Tr = 2, ten runs), where ev_m[R - 1] is an event of some earlier call or of none. */
+        HIPCHK(hipStreamWaitEvent(c->s_pre, c->ev_m[c->ahead_last], 0));    /* the resampler reads the hand-over the previous call's last front kernel wrote */
         HIPCHK(hipStreamWaitEvent(c->s_pre, c->ev_done[hb_], 0)); HIPCHK(hipStreamWaitEvent(c->s_fr, c->ev_done[hb_], 0));
         if (five) { HIPCHK(hipStreamWaitEvent(c->s_pit, c->ev_done[hb_], 0)); HIPCHK(hipStreamWaitEvent(c->s_ln, c->ev_done[hb_], 0));
-                    if (c->any_attack) HIPCHK(hipStreamWaitEvent(c->s_fr, c->ev_f[R - 1], 0)); }      /* the front reads the attack detector's filter memory the previous call's attack kernel leaves */
+                    if (c->any_attack) HIPCHK(hipStreamWaitEvent(c->s_fr, c->ev_f[c->ahead_last], 0)); }      /* the front reads the attack detector's filter memory the previous call's attack kernel leaves */
     }
     r.rs = s; r.hb = 0; r.hk = 0;                         /* rs: where the rate kernels run */
-    for (int k = 0, tb = 0; tb < n_frames; k++, tb += Tr)
-        if (enc_run(c, q, &r, k, tb, n_frames - tb < Tr ? n_frames - tb : Tr, Tr)) return 1;
+    int made = 0;                                         /* runs made: ceil(n_frames / Tr), at most R */
+    for (int tb = 0; tb < n_frames; made++, tb += Tr)
+        if (enc_run(c, q, &r, made, tb, n_frames - tb < Tr ? n_frames - tb : Tr, Tr)) return 1;
     HIPCHK(hipEventRecord(c->ev_rate, r.rs)); c->rate_armed = 1; q->rate_on_side = r.rs != s;
     if (r.rs != s) HIPCHK(hipStreamWaitEvent(s, c->ev_rate, 0));      /* the writer (and whatever the caller queues next) behind the rate chain */
     /* a ragged call forks from s and lets nothing overlap it: it fills the hand-over only for the streams that had a frame, so the call behind it reads the MDCT memory from the state */
-    c->ahead_ok = (dt0 == 0 && dT == n_frames && q->pack && !q->cnt) ? 1 : 0; c->ahead_T = n_frames; c->ahead_R = R;
+    c->ahead_ok = (dt0 == 0 && dT == n_frames && q->pack && !q->cnt) ? 1 : 0; c->ahead_T = n_frames; c->ahead_R = R; c->ahead_last = made - 1;
     c->xn_par = (c->xn_par + 1) % (LC3D_SETS + 1);
     return 0;
 }
