@@ -44,6 +44,7 @@ EXPORTS = [
     "lc3plus_enc_batch_egress", "lc3plus_dec_batch_egress", "lc3plus_plan_egress", "lc3plus_egress_work_bytes",
     "lc3plus_dec_batch_rtp_parse", "lc3plus_plan_rtp_parse", "lc3plus_rtp_sort_ssrc", "lc3plus_enc_batch_rtp_stamp", "lc3plus_dec_batch_rtp_stamp",
     "lc3plus_plan_rtp_stamp",
+    "lc3plus_dec_batch_rtcp_stats", "lc3plus_plan_rtcp_stats", "lc3plus_rtcp_workspace_bytes",
     "lc3plus_shard_block",
     "lc3plus_enc_sharded_create", "lc3plus_enc_sharded_destroy", "lc3plus_enc_sharded_shards", "lc3plus_enc_sharded_shard", "lc3plus_enc_sharded_device",
     "lc3plus_enc_sharded_owner", "lc3plus_enc_sharded_input_samples", "lc3plus_enc_sharded_num_bytes", "lc3plus_enc_sharded_stride",
@@ -94,6 +95,16 @@ EGR_STATS_WORDS = 4
 RTP_STATS_WORDS = 16
 RTP_STAMPED, RTP_ST_BAD_ROUTE, RTP_ST_OVERFLOW, RTP_ST_RANGE = 1, 2, 4, 8
 RTP_MARKER_NEVER, RTP_MARKER_AFTER_HOLE = 0, 1
+# Reception reports (DecBatch.rtcp_stats, plan_rtcp_stats; include/lc3plus_batch.h "Reception reports"): the words of a stream's state, an item's status, the
+# words of a stream's stats, a report block's bytes
+(RR_FLAGS, RR_BASE_SEQ, RR_MAX_SEQ, RR_CYCLES, RR_BAD_SEQ, RR_RECEIVED, RR_EXPECTED_PRIOR, RR_RECEIVED_PRIOR, RR_TRANSIT, RR_JITTER) = range(10)
+RR_STATE_WORDS = 10
+RR_STARTED = 1
+RR_DROPPED, RR_COUNTED, RR_JUMP, RR_RESTART, RR_REORDERED = range(5)
+RR_ST_COUNTED, RR_ST_JUMP, RR_ST_RESTART, RR_ST_REORDERED = range(4)
+RR_STATS_WORDS = 4
+RR_BLOCK_BYTES = 24
+RR_MAX_DROPOUT, RR_MAX_MISORDER = 3000, 100
 LC3_BW_WARNING = 18
 
 
@@ -255,6 +266,10 @@ def load_library():
         L.lc3plus_enc_batch_rtp_stamp.argtypes = [C.c_void_p] + stamp
         L.lc3plus_dec_batch_rtp_stamp.argtypes = [C.c_void_p] + stamp
         L.lc3plus_plan_rtp_stamp.argtypes = stamp
+        rr = [C.c_int64] + [C.c_void_p] * 4 + [C.c_int, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 7
+        L.lc3plus_dec_batch_rtcp_stats.argtypes = [C.c_void_p] + rr + [C.c_void_p, C.c_int64, C.c_void_p, C.c_int]
+        L.lc3plus_plan_rtcp_stats.argtypes = rr
+        L.lc3plus_rtcp_workspace_bytes.argtypes = [C.c_int64, C.c_int]; L.lc3plus_rtcp_workspace_bytes.restype = C.c_int64
         _LIB = L
     return _LIB
 
@@ -706,6 +721,53 @@ class _RtpStamp:
             for k in range(13, 17):
                 back(k)
         return dict(zip(RTP_STAMP_OPTIONAL, outs), wire=wire)
+
+
+RR_OPTIONAL = ("ext_seq", "item_status", "stream_stats")
+RR_OUTPUTS = ("state", "blocks", "ext_seq", "item_status", "stream_stats")
+
+
+def rtcp_workspace_bytes(n_items, n_streams):
+    """the bytes of the workspace a DecBatch.rtcp_stats_device call over n_items items and n_streams streams needs (lc3plus_rtcp_workspace_bytes); 0 for
+    arguments the call refuses"""
+    return int(load_library().lc3plus_rtcp_workspace_bytes(int(n_items), int(n_streams)))
+
+
+def _rtcp_arrays(stream, seq, timestamp, arrival, state, make_report, ssrc, lsr, dlsr, optional):
+    """the arrays of a stats call as the C calls take them: (inputs stream, seq, timestamp, arrival, state_in, ssrc, lsr, dlsr - None for NULL; outputs in
+    RR_OUTPUTS order likewise)"""
+    stream = np.ascontiguousarray(stream, dtype=np.int32).reshape(-1)
+    n = stream.size
+    seq, timestamp, arrival = _u32(seq), _u32(timestamp), _u32(arrival)
+    if not (seq.size == timestamp.size == arrival.size == n):
+        raise ValueError("stream, seq, timestamp and arrival hold one entry per item")
+    state = _u32(state).reshape(-1, RR_STATE_WORDS) if np.asarray(state).size % RR_STATE_WORDS == 0 else None
+    if state is None:
+        raise ValueError("state must have shape [n_streams, RR_STATE_WORDS]")
+    S = state.shape[0]
+    per = [None if a is None else _u32(a) for a in (ssrc, lsr, dlsr)]
+    if any(a is not None and a.size != S for a in per):
+        raise ValueError("ssrc, lsr and dlsr hold one entry per stream")
+    outs = [np.zeros((S, RR_STATE_WORDS), np.int32), np.zeros((S, RR_BLOCK_BYTES), np.uint8) if make_report else None,
+            np.zeros(n, np.int32) if "ext_seq" in optional else None, np.zeros(n, np.uint8) if "item_status" in optional else None,
+            np.zeros((S, RR_STATS_WORDS), np.int32) if "stream_stats" in optional else None]
+    return [stream, seq, timestamp, arrival, np.ascontiguousarray(state)] + per, outs
+
+
+def plan_rtcp_stats(stream, seq, timestamp, arrival, state, make_report=False, ssrc=None, lsr=None, dlsr=None, optional=RR_OPTIONAL):
+    """The rule of DecBatch.rtcp_stats on the host (lc3plus_plan_rtcp_stats, no device needed): the parse's item arrays stream / seq / timestamp [n] and the
+    arrival time of each item on its stream's RTP clock, state [n_streams, RR_STATE_WORDS] (zeros: a source that has not started), with make_report ssrc and
+    optionally lsr, dlsr [n_streams] -> dict of state (the advanced state), blocks [n_streams, RR_BLOCK_BYTES] (uint8; None without make_report), ext_seq [n],
+    item_status (uint8) [n] and stream_stats [n_streams, RR_STATS_WORDS]; those of RR_OPTIONAL not named in `optional` are passed as NULL and come back as
+    None.  LC3Error for arguments the C call refuses."""
+    ins, outs = _rtcp_arrays(stream, seq, timestamp, arrival, state, make_report, ssrc, lsr, dlsr, optional)
+    pad = np.zeros(8, np.uint8)                                       # an empty array still has to be a pointer
+    ptr = lambda a: (a if a.size else pad).ctypes.data if a is not None else None
+    rc = load_library().lc3plus_plan_rtcp_stats(ins[0].size, *[ptr(a) for a in ins[:4]], ins[4].shape[0], ptr(ins[4]), ptr(outs[0]), 1 if make_report else 0,
+                                                ptr(ins[5]), ptr(ins[6]), ptr(ins[7]), *[ptr(a) for a in outs[1:]])
+    if rc:
+        raise LC3Error(rc, "lc3plus_plan_rtcp_stats")
+    return dict(zip(RR_OUTPUTS, outs))
 
 
 class _StreamLifecycle:
@@ -1549,6 +1611,35 @@ class DecBatch(_StreamLifecycle, _Egress, _RtpStamp):
             for k in range(6, 14):
                 back(k)
         return dict(zip(RTP_PARSE_OUTPUTS, outs))
+
+    def rtcp_stats_device(self, n_items, d_stream_ptr, d_seq_ptr, d_timestamp_ptr, d_arrival_ptr, n_streams, d_state_in_ptr, d_state_out_ptr, d_workspace_ptr,
+                          workspace_bytes, make_report=False, d_ssrc_ptr=None, d_lsr_ptr=None, d_dlsr_ptr=None, d_blocks_ptr=None, d_ext_seq_ptr=None,
+                          d_item_status_ptr=None, d_stream_stats_ptr=None, hip_stream=None, sync=False):
+        """Reception reports (lc3plus_dec_batch_rtcp_stats): raw device pointers only - rtp_parse_device's stream, seq and timestamp [n_items] as they stand, the
+        arrival time of each item, state_in / state_out [n_streams, RR_STATE_WORDS] (they may be one array), a workspace of rtcp_workspace_bytes(n_items,
+        n_streams) bytes -> the advanced state, with make_report the report blocks [n_streams, RR_BLOCK_BYTES] (needs ssrc; lsr, dlsr optional), and the optional
+        ext_seq [n_items], item_status (uint8) [n_items] and stream_stats [n_streams, RR_STATS_WORDS].  Stateless: nothing of the batch's streams is read or
+        written.  Queued on hip_stream; returns at once unless sync."""
+        def p(x):
+            return C.c_void_p(x) if x else None
+        rc = self.lib.lc3plus_dec_batch_rtcp_stats(self.h, int(n_items), p(d_stream_ptr), p(d_seq_ptr), p(d_timestamp_ptr), p(d_arrival_ptr), int(n_streams),
+                                                   p(d_state_in_ptr), p(d_state_out_ptr), 1 if make_report is True else int(make_report), p(d_ssrc_ptr),
+                                                   p(d_lsr_ptr), p(d_dlsr_ptr), p(d_blocks_ptr), p(d_ext_seq_ptr), p(d_item_status_ptr), p(d_stream_stats_ptr),
+                                                   p(d_workspace_ptr), int(workspace_bytes), p(hip_stream), 1 if sync else 0)
+        if rc:
+            raise LC3Error(rc, "lc3plus_dec_batch_rtcp_stats")
+
+    def rtcp_stats(self, stream, seq, timestamp, arrival, state, make_report=False, ssrc=None, lsr=None, dlsr=None, optional=RR_OPTIONAL):
+        """Host convenience: the arrays of plan_rtcp_stats uploaded, run on the device and downloaded -> the dict plan_rtcp_stats gives.  Device memory through
+        the HIP runtime as in probe(), the workspace too, freed before it returns."""
+        ins, outs = _rtcp_arrays(stream, seq, timestamp, arrival, state, make_report, ssrc, lsr, dlsr, optional)
+        n, S = ins[0].size, ins[4].shape[0]
+        work = np.zeros(max(rtcp_workspace_bytes(n, S), 8), np.uint8)
+        with _on_device(ins + outs + [work]) as (v, back):
+            self.rtcp_stats_device(n, v[0], v[1], v[2], v[3], S, v[4], v[8], v[13], work.size, make_report, v[5], v[6], v[7], v[9], v[10], v[11], v[12], sync=True)
+            for k in range(8, 13):
+                back(k)
+        return dict(zip(RR_OUTPUTS, outs))
 
     def decode_traced(self, frames, bfi=None, bps=16):
         frames, T, stride, bfi, pcm, status = self._prep(frames, bfi, bps)

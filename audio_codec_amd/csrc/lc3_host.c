@@ -26,6 +26,7 @@
 #include "lc3_ingest_shim.h"
 #include "lc3_egress_shim.h"
 #include "lc3_rtp_shim.h"
+#include "lc3_rtcp_shim.h"
 
 #ifndef M_PI
 #define M_PI 3.14159265358979323846
@@ -2350,6 +2351,113 @@ LC3_Error lc3plus_dec_batch_rtp_stamp(lc3plus_dec_batch* b, int64_t max_packets,
     const LC3_Error e = rtp_stamp_check(&a);
     if (e) return e;
     return rtp_stamp_queue(b->dev, 1, &a, hip_stream, sync);
+}
+/* ---- reception reports (include/lc3plus_batch.h "Reception reports"; lc3_rtcp_shim.h) ---- */
+/* what a stats call takes behind its batch, in the header's order */
+typedef struct {
+    int64_t n_items; const int32_t* stream; const int32_t* seq; const int32_t* timestamp; const int32_t* arrival;
+    int n_streams; const int32_t* state_in; int32_t* state_out;
+    int make_report; const int32_t* ssrc; const int32_t* lsr; const int32_t* dlsr; uint8_t* blocks;
+    int32_t* ext_seq; uint8_t* item_status; int32_t* stream_stats;
+} rtcp_stats_args;
+/* the checks every stats call makes first, in the header's order */
+static LC3_Error rtcp_stats_check(const rtcp_stats_args* a)
+{
+    if (!a->stream || !a->seq || !a->timestamp || !a->arrival || !a->state_in || !a->state_out) return LC3_NULL_ERROR;
+    if (a->make_report && (!a->ssrc || !a->blocks)) return LC3_NULL_ERROR;
+    if (a->n_items <= 0 || a->n_items >= LC3Q_MAX_ITEMS || a->n_streams <= 0 || (a->make_report != 0 && a->make_report != 1)) return LC3_ERROR;
+    return LC3_OK;
+}
+int64_t lc3plus_rtcp_workspace_bytes(int64_t n_items, int n_streams)
+{
+    return (int64_t)lc3q_workspace_bytes((long long)n_items, n_streams);
+}
+/* the rule on the host: the list once in its order, every item on its stream's state, then the reports */
+LC3_Error lc3plus_plan_rtcp_stats(int64_t n_items,
+    const int32_t* stream, const int32_t* seq, const int32_t* timestamp, const int32_t* arrival,
+    int n_streams, const int32_t* state_in, int32_t* state_out,
+    int make_report, const int32_t* ssrc, const int32_t* lsr, const int32_t* dlsr, uint8_t* blocks,
+    int32_t* ext_seq, uint8_t* item_status, int32_t* stream_stats)
+{
+    const rtcp_stats_args a = {n_items, stream, seq, timestamp, arrival, n_streams, state_in, state_out, make_report, ssrc, lsr, dlsr, blocks, ext_seq, item_status,
+                               stream_stats};
+    const LC3_Error e = rtcp_stats_check(&a);
+    if (e) return e;
+    if (state_out != state_in) memmove(state_out, state_in, sizeof(int32_t) * LC3Q_STATE_WORDS * (size_t)n_streams);
+    if (stream_stats) memset(stream_stats, 0, sizeof(int32_t) * LC3Q_STATS_WORDS * (size_t)n_streams);
+    for (int64_t i = 0; i < n_items; i++) {
+        const int s = stream[i];
+        uint32_t ext = 0;
+        int st = LC3Q_DROPPED;
+        if (s >= 0 && s < n_streams) {
+            lc3q_state v;
+            memcpy(v.w, state_out + (size_t)s * LC3Q_STATE_WORDS, sizeof v.w);
+            st = lc3q_step(&v, (uint32_t)seq[i], (uint32_t)arrival[i] - (uint32_t)timestamp[i], &ext);
+            memcpy(state_out + (size_t)s * LC3Q_STATE_WORDS, v.w, sizeof v.w);
+            if (stream_stats) {
+                int32_t* t = stream_stats + (size_t)s * LC3Q_STATS_WORDS;
+                t[LC3Q_ST_COUNTED] += st != LC3Q_JUMP; t[LC3Q_ST_JUMP] += st == LC3Q_JUMP; t[LC3Q_ST_RESTART] += st == LC3Q_RESTART;
+                t[LC3Q_ST_REORDERED] += st == LC3Q_REORDERED;
+            }
+        }
+        if (item_status) item_status[i] = (uint8_t)st;
+        if (ext_seq) ext_seq[i] = (int32_t)ext;
+    }
+    if (make_report)
+        for (int s = 0; s < n_streams; s++) {
+            lc3q_state v;
+            uint32_t blk[LC3Q_BLOCK_WORDS];
+            memcpy(v.w, state_out + (size_t)s * LC3Q_STATE_WORDS, sizeof v.w);
+            lc3q_report(&v, (uint32_t)ssrc[s], lsr ? (uint32_t)lsr[s] : 0u, dlsr ? (uint32_t)dlsr[s] : 0u, blk);
+            memcpy(state_out + (size_t)s * LC3Q_STATE_WORDS, v.w, sizeof v.w);
+            lc3q_block_out(blocks + (size_t)s * LC3Q_BLOCK_BYTES, blk);
+        }
+    return LC3_OK;
+}
+/* the sibling library with the reception reports' kernels, loaded as the RTP framing's is; NULL where it is missing */
+typedef int (*rtcp_stats_fn)(const lc3rtcp_stats_call*);
+static pthread_once_t rtcp_once = PTHREAD_ONCE_INIT;
+static rtcp_stats_fn rtcp_stats_run;
+static void rtcp_load(void)
+{
+    Dl_info di;
+    char path[4096];
+    if (!dladdr((void*)&rtcp_load, &di) || !di.dli_fname) return;
+    const char* slash = strrchr(di.dli_fname, '/');
+    const size_t dir = slash ? (size_t)(slash - di.dli_fname) + 1 : 0;
+    static const char name[] = "liblc3plus_rtcp_hip.so";
+    if (dir + sizeof name > sizeof path) return;
+    memcpy(path, di.dli_fname, dir);
+    memcpy(path + dir, name, sizeof name);
+    void* h = dlopen(path, RTLD_NOW | RTLD_LOCAL);
+    if (!h) { fprintf(stderr, "lc3plus_hip: the reception reports' library is missing: %s\n", dlerror()); return; }
+    rtcp_stats_run = (rtcp_stats_fn)dlsym(h, "lc3rtcp_stats_run");
+}
+LC3_Error lc3plus_dec_batch_rtcp_stats(lc3plus_dec_batch* b, int64_t n_items,
+    const int32_t* stream, const int32_t* seq, const int32_t* timestamp, const int32_t* arrival,
+    int n_streams, const int32_t* state_in, int32_t* state_out,
+    int make_report, const int32_t* ssrc, const int32_t* lsr, const int32_t* dlsr, uint8_t* blocks,
+    int32_t* ext_seq, uint8_t* item_status, int32_t* stream_stats,
+    void* workspace, int64_t workspace_bytes, void* hip_stream, int sync)
+{
+    if (!b) return LC3_NULL_ERROR;
+    const rtcp_stats_args a = {n_items, stream, seq, timestamp, arrival, n_streams, state_in, state_out, make_report, ssrc, lsr, dlsr, blocks, ext_seq, item_status,
+                               stream_stats};
+    if (!workspace) return LC3_NULL_ERROR;
+    const LC3_Error e = rtcp_stats_check(&a);
+    if (e) return e;
+    if (workspace_bytes < lc3plus_rtcp_workspace_bytes(n_items, n_streams)) return LC3_ERROR;
+    lc3rtcp_stats_call q;
+    memset(&q, 0, sizeof q);
+    void* own = NULL;
+    if (rtp_device(b->dev, 1, 0, &q.device, &own)) return LC3_ERROR;
+    pthread_once(&rtcp_once, rtcp_load);
+    if (!rtcp_stats_run) return LC3_ERROR;
+    q.n_streams = n_streams; q.make_report = make_report; q.sync = sync; q.n_items = (long long)n_items;
+    q.stream = stream; q.seq = seq; q.timestamp = timestamp; q.arrival = arrival; q.state_in = state_in; q.state_out = state_out;
+    q.ssrc = ssrc; q.lsr = lsr; q.dlsr = dlsr; q.blocks = blocks; q.ext_seq = ext_seq; q.item_status = item_status; q.stream_stats = stream_stats;
+    q.workspace = workspace; q.workspace_bytes = (long long)workspace_bytes; q.hip_stream = hip_stream ? hip_stream : own;
+    return rtcp_stats_run(&q) ? LC3_ERROR : LC3_OK;
 }
 LC3_Error lc3plus_dec_batch_set_input_ready(lc3plus_dec_batch* b, int ready)
 {

@@ -830,6 +830,109 @@ LC3_Error lc3plus_plan_rtp_stamp(int64_t max_packets, const int64_t* n_packets,
     void* wire, int64_t wire_capacity, int header_room, int payload_room,
     uint8_t* pkt_status, int32_t* next_ts, uint8_t* next_resume, void* hip_stream, int sync);
 
+/* ---- Reception reports: per-stream RTP statistics and RR report blocks, on the device ----------------------------------------------------------------------
+ * A receiver owes its senders RTCP reception reports (RFC 3550 6.4): per source the extended highest sequence number, the cumulative loss, the loss fraction
+ * of the last interval and the interarrival jitter.  All four follow from what lc3plus_dec_batch_rtp_parse leaves in device memory - stream, seq, timestamp -
+ * and the time each datagram arrived.  lc3plus_dec_batch_rtcp_stats takes those arrays as they stand and a state block per stream and gives the advanced state,
+ * the 24-byte report blocks in wire order and a status per item, so that datagrams -> parse -> stats runs on one HIP stream with no host wait; the jitter it
+ * keeps is also what sizes a jitter buffer, the ingest's floor.  Sender reports, the RR header in front of the blocks, compound packets, SDES and BYE stay with
+ * the caller.
+ *
+ * Every pointer but `batch` is a device pointer and is read when the kernels run.  The call is STATELESS and allocates nothing: it borrows the batch's device
+ * and nothing else, no stream state, configuration or buffer of the batch is read or written, and it may run beside a decode call of the same batch.  It is
+ * queued on hip_stream (NULL: the batch's stream) and returns at once unless sync.  No output may overlap an input, another output or the workspace, but
+ * state_out may BE state_in.
+ *   n_items                       : the list's length
+ *   stream, seq, timestamp        : [n_items] the parse's arrays.  A stream outside [0, n_streams) (the parse's -1: a refused datagram) is no source's item
+ *   arrival                       : [n_items] when datagram i arrived, in the units of its stream's RTP clock, mod 2^32
+ *   n_streams, state_in, state_out: [n_streams][LC3PLUS_RR_STATE_WORDS] each source's state before and after.  A zero-filled block is a source that has not
+ *                                   started.  n_streams is the call's own: it need not be the batch's
+ *   make_report, ssrc, lsr, dlsr  : 0 or 1; with 1, [n_streams] each source's SSRC and the LSR and DLSR words of its block (lsr, dlsr: NULL for 0 everywhere)
+ *   blocks                        : [n_streams][LC3PLUS_RR_BLOCK_BYTES] the report blocks, with make_report
+ *   ext_seq [n_items], item_status (uint8) [n_items], stream_stats [n_streams][LC3PLUS_RR_STATS_WORDS] : each may be NULL
+ *   workspace, workspace_bytes    : scratch of at least lc3plus_rtcp_workspace_bytes(n_items, n_streams) bytes, at any alignment; its contents mean nothing
+ *                                   before or after the call
+ *
+ * THE RULE.  All arithmetic is on uint32 mod 2^32 unless a cast is written.  A state block's words are FLAGS (bit 0, LC3PLUS_RR_STARTED: the source has
+ * started; the other bits are kept as they are), BASE_SEQ, MAX_SEQ, CYCLES, BAD_SEQ, RECEIVED, EXPECTED_PRIOR, RECEIVED_PRIOR, TRANSIT, JITTER (LC3PLUS_RR_FLAGS
+ * ... LC3PLUS_RR_JITTER = 0 ... 9).  The items of a stream are taken in list order, which is arrival order: the jitter depends on it.  Streams do not touch each
+ * other.
+ * 1. stream[i] < 0 or >= n_streams: item_status[i] = LC3PLUS_RR_DROPPED (0), ext_seq[i] = 0, and nothing else happens.
+ * 2. Otherwise let s = stream[i], q = seq[i] & 0xFFFF, and init_seq(q) be: BASE_SEQ = MAX_SEQ = q, BAD_SEQ = 65537, CYCLES = RECEIVED = RECEIVED_PRIOR =
+ *    EXPECTED_PRIOR = 0, bit STARTED set.
+ *    - s has not started: init_seq(q).  The item is `first`; its status is LC3PLUS_RR_COUNTED (1).
+ *    - Otherwise RFC 3550 A.1 update_seq without probation (a source the caller put into its table is valid from its first packet), with
+ *      udelta = (q - MAX_SEQ) & 0xFFFF:
+ *        udelta < 3000 (MAX_DROPOUT)        in order: if q < MAX_SEQ then CYCLES += 65536; MAX_SEQ = q.  Status COUNTED.
+ *        else udelta <= 65536 - 100         a large jump (100: MAX_MISORDER).  If q == BAD_SEQ: init_seq(q), the item is `first`, status LC3PLUS_RR_RESTART (3).
+ *                                           Otherwise BAD_SEQ = (q + 1) & 0xFFFF, status LC3PLUS_RR_JUMP (2), ext_seq[i] = 0, and the item ends here: it is not
+ *                                           counted and does not touch the jitter.
+ *        else                               a duplicate or a reordered packet: status LC3PLUS_RR_REORDERED (4).
+ *    - Every item that did not end as a JUMP is counted: RECEIVED += 1.
+ * 3. Jitter (A.8), for counted items: transit = arrival[i] - timestamp[i].  A `first` item - a start or a restart - sets TRANSIT = transit and JITTER = 0.
+ *    Every other counted item: d = transit - TRANSIT; TRANSIT = transit; ad = (int32)d < 0 ? 0 - d : d; JITTER += ad - ((JITTER + 8) >> 4).
+ * 4. ext_seq[i] of a counted item is CYCLES + q, with the values after step 2, less 65536 where q > MAX_SEQ (a reordered packet from before the wrap).
+ * 5. stream_stats[s] is four words, counted from zero in every call: the items counted (LC3PLUS_RR_ST_COUNTED = 0: every status but DROPPED and JUMP), the JUMP
+ *    items (1), the RESTART items (2) and the REORDERED items (3) of stream s.  A stream without items gets zeros.
+ * 6. With make_report == 1, for every stream after its items (A.3).  A stream that has not started gets 24 zero bytes, and its state stays as it is.
+ *    Otherwise
+ *        expected = CYCLES + MAX_SEQ - BASE_SEQ + 1
+ *        lost     = (int32)(expected - RECEIVED), clamped to [-0x800000, 0x7FFFFF]
+ *        ei       = (int32)(expected - EXPECTED_PRIOR);  li = (int32)((expected - EXPECTED_PRIOR) - (RECEIVED - RECEIVED_PRIOR))
+ *        fraction = (ei == 0 || li <= 0) ? 0 : min(255, ((int64)li << 8) / ei), the division truncating towards zero as C's; the block holds its low 8 bits
+ *        then EXPECTED_PRIOR = expected and RECEIVED_PRIOR = RECEIVED.
+ *    RFC 3550's text gives 256 where nothing of an interval arrived, which does not fit the byte: the fraction is capped at 255 here.
+ *    The block is 24 bytes, every field big-endian: ssrc[s] (4 bytes); fraction (1); lost as 24 bits, two's complement (3); CYCLES + MAX_SEQ (4);
+ *    JITTER >> 4 (4); lsr[s] (4); dlsr[s] (4).  Where blocks is 4-aligned the device writes a block as six aligned words.
+ * 7. With make_report == 0 blocks is not written and EXPECTED_PRIOR / RECEIVED_PRIOR stay as they are, so a run split into several calls with the state
+ *    carried from each to the next and a report only in the last equals one call over the whole list.
+ * Refused calls queue nothing, checked in this order before anything of the batch or the device is touched: a NULL batch, workspace, stream, seq, timestamp,
+ * arrival, state_in or state_out, and with make_report != 0 a NULL ssrc or blocks (LC3_NULL_ERROR); then n_items <= 0, n_items >= 2^29, n_streams <= 0, a
+ * make_report other than 0 or 1, and workspace_bytes below what lc3plus_rtcp_workspace_bytes answers (LC3_ERROR).
+ *
+ * The kernels live in liblc3plus_rtcp_hip.so, which this library loads from its own directory on the first call: where that file is missing the call returns
+ * LC3_ERROR and nothing else changes. */
+#define LC3PLUS_RR_FLAGS           0
+#define LC3PLUS_RR_BASE_SEQ        1
+#define LC3PLUS_RR_MAX_SEQ         2
+#define LC3PLUS_RR_CYCLES          3
+#define LC3PLUS_RR_BAD_SEQ         4
+#define LC3PLUS_RR_RECEIVED        5
+#define LC3PLUS_RR_EXPECTED_PRIOR  6
+#define LC3PLUS_RR_RECEIVED_PRIOR  7
+#define LC3PLUS_RR_TRANSIT         8
+#define LC3PLUS_RR_JITTER          9
+#define LC3PLUS_RR_STATE_WORDS     10
+#define LC3PLUS_RR_STARTED         1
+#define LC3PLUS_RR_DROPPED         0
+#define LC3PLUS_RR_COUNTED         1
+#define LC3PLUS_RR_JUMP            2
+#define LC3PLUS_RR_RESTART         3
+#define LC3PLUS_RR_REORDERED       4
+#define LC3PLUS_RR_ST_COUNTED      0
+#define LC3PLUS_RR_ST_JUMP         1
+#define LC3PLUS_RR_ST_RESTART      2
+#define LC3PLUS_RR_ST_REORDERED    3
+#define LC3PLUS_RR_STATS_WORDS     4
+#define LC3PLUS_RR_BLOCK_BYTES     24
+#define LC3PLUS_RR_MAX_DROPOUT     3000
+#define LC3PLUS_RR_MAX_MISORDER    100
+LC3_Error lc3plus_dec_batch_rtcp_stats(lc3plus_dec_batch* batch, int64_t n_items,
+    const int32_t* stream, const int32_t* seq, const int32_t* timestamp, const int32_t* arrival,
+    int n_streams, const int32_t* state_in, int32_t* state_out,
+    int make_report, const int32_t* ssrc, const int32_t* lsr, const int32_t* dlsr, uint8_t* blocks,
+    int32_t* ext_seq, uint8_t* item_status, int32_t* stream_stats,
+    void* workspace, int64_t workspace_bytes, void* hip_stream, int sync);
+/* the bytes of `workspace` for such a call; 0 for an n_items or n_streams the call refuses */
+int64_t lc3plus_rtcp_workspace_bytes(int64_t n_items, int n_streams);
+/* The same rule on the host alone, no device: the same arrays in host memory, no batch, no workspace, no stream.  The refusals of the call above in their
+ * order, less those of the batch and the workspace. */
+LC3_Error lc3plus_plan_rtcp_stats(int64_t n_items,
+    const int32_t* stream, const int32_t* seq, const int32_t* timestamp, const int32_t* arrival,
+    int n_streams, const int32_t* state_in, int32_t* state_out,
+    int make_report, const int32_t* ssrc, const int32_t* lsr, const int32_t* dlsr, uint8_t* blocks,
+    int32_t* ext_seq, uint8_t* item_status, int32_t* stream_stats);
+
 /* ---- Sharded batches: one call drives encoders or decoders on several GPUs ------------------------------------------------------------------
  * Streams are independent, so a sharded batch is n_devices ordinary batches, each owning a contiguous block of the n_streams streams on a device of its
  * own; nothing is exchanged between devices.  Stream indices are GLOBAL (0 ... n_streams - 1) and arrays are laid out over all n_streams exactly as the
