@@ -45,6 +45,8 @@ EXPORTS = [
     "lc3plus_dec_batch_rtp_parse", "lc3plus_plan_rtp_parse", "lc3plus_rtp_sort_ssrc", "lc3plus_enc_batch_rtp_stamp", "lc3plus_dec_batch_rtp_stamp",
     "lc3plus_plan_rtp_stamp",
     "lc3plus_dec_batch_rtcp_stats", "lc3plus_plan_rtcp_stats", "lc3plus_rtcp_workspace_bytes",
+    "lc3plus_srtp_make_context", "lc3plus_enc_batch_srtp_protect", "lc3plus_dec_batch_srtp_protect", "lc3plus_plan_srtp_protect",
+    "lc3plus_dec_batch_srtp_unprotect", "lc3plus_plan_srtp_unprotect", "lc3plus_srtp_workspace_bytes",
     "lc3plus_shard_block",
     "lc3plus_enc_sharded_create", "lc3plus_enc_sharded_destroy", "lc3plus_enc_sharded_shards", "lc3plus_enc_sharded_shard", "lc3plus_enc_sharded_device",
     "lc3plus_enc_sharded_owner", "lc3plus_enc_sharded_input_samples", "lc3plus_enc_sharded_num_bytes", "lc3plus_enc_sharded_stride",
@@ -105,6 +107,15 @@ RR_ST_COUNTED, RR_ST_JUMP, RR_ST_RESTART, RR_ST_REORDERED = range(4)
 RR_STATS_WORDS = 4
 RR_BLOCK_BYTES = 24
 RR_MAX_DROPOUT, RR_MAX_MISORDER = 3000, 100
+# Secure RTP (srtp_make_context, Batch.srtp_protect_device, DecBatch.srtp_unprotect, plan_srtp_protect, plan_srtp_unprotect; include/lc3plus_batch.h "Secure
+# RTP"): the words of a context, the bits of a protected packet's status, the words of a source's state, an item's status (also its word in stats)
+SRTP_CTX_WORDS = 64
+SRTP_PROTECTED, SRTP_NOT_STAMPED, SRTP_BAD_ROUTE, SRTP_RANGE, SRTP_OVERFLOW = 1, 2, 4, 8, 16
+SRTP_STATE_WORDS = 8
+SRTP_FLAGS, SRTP_ROC, SRTP_S_L, SRTP_WIN_LO, SRTP_WIN_HI = range(5)
+SRTP_STARTED = 1
+(SRTP_OK, SRTP_UN_RANGE, SRTP_SHORT, SRTP_VERSION, SRTP_RTCP, SRTP_HEADER, SRTP_UNKNOWN_SSRC, SRTP_REPLAY_OLD, SRTP_REPLAYED, SRTP_AUTH) = range(10)
+SRTP_STATS_WORDS = 16
 LC3_BW_WARNING = 18
 
 
@@ -270,6 +281,15 @@ def load_library():
         L.lc3plus_dec_batch_rtcp_stats.argtypes = [C.c_void_p] + rr + [C.c_void_p, C.c_int64, C.c_void_p, C.c_int]
         L.lc3plus_plan_rtcp_stats.argtypes = rr
         L.lc3plus_rtcp_workspace_bytes.argtypes = [C.c_int64, C.c_int]; L.lc3plus_rtcp_workspace_bytes.restype = C.c_int64
+        L.lc3plus_srtp_make_context.argtypes = [C.c_void_p] * 3
+        prot = ([C.c_int64] + [C.c_void_p] * 6 + [C.c_int64, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 5 + [C.c_int64, C.c_int64, C.c_int] + [C.c_void_p] * 4)
+        L.lc3plus_enc_batch_srtp_protect.argtypes = [C.c_void_p] + prot + [C.c_void_p, C.c_int]
+        L.lc3plus_dec_batch_srtp_protect.argtypes = [C.c_void_p] + prot + [C.c_void_p, C.c_int]
+        L.lc3plus_plan_srtp_protect.argtypes = prot
+        unp = [C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 4 + [C.c_int] + [C.c_void_p] * 4
+        L.lc3plus_dec_batch_srtp_unprotect.argtypes = [C.c_void_p] + unp + [C.c_void_p, C.c_int64, C.c_void_p, C.c_int]
+        L.lc3plus_plan_srtp_unprotect.argtypes = unp
+        L.lc3plus_srtp_workspace_bytes.argtypes = [C.c_int64, C.c_int]; L.lc3plus_srtp_workspace_bytes.restype = C.c_int64
         _LIB = L
     return _LIB
 
@@ -770,6 +790,121 @@ def plan_rtcp_stats(stream, seq, timestamp, arrival, state, make_report=False, s
     return dict(zip(RR_OUTPUTS, outs))
 
 
+SRTP_PROTECT_OUTPUTS = ("out_offset", "out_size", "out_status", "next_roc")
+SRTP_UNPROTECT_OPTIONAL = ("status", "index", "stats")
+SRTP_UNPROTECT_OUTPUTS = ("state", "sizes", "status", "index", "stats")
+
+
+def srtp_make_context(master_key, master_salt):
+    """An SRTP crypto context (lc3plus_srtp_make_context, host only): master_key (16 bytes) and master_salt (14 bytes) -> SRTP_CTX_WORDS int32 words - the
+    round keys of the session cipher key, the session salt and the two SHA-1 midstates of the HMAC under the session authentication key (RFC 3711 4.3.1,
+    key derivation rate 0) - as the device reads them; the caller stacks contexts into [n, SRTP_CTX_WORDS] and copies them to device memory."""
+    key, salt = np.frombuffer(bytes(master_key), np.uint8), np.frombuffer(bytes(master_salt), np.uint8)
+    if key.size != 16 or salt.size != 14:
+        raise ValueError("master_key holds 16 bytes, master_salt 14")
+    ctx = np.zeros(SRTP_CTX_WORDS, np.int32)
+    rc = load_library().lc3plus_srtp_make_context(key.ctypes.data, salt.ctypes.data, ctx.ctypes.data)
+    if rc:
+        raise LC3Error(rc, "lc3plus_srtp_make_context")
+    return ctx
+
+
+def srtp_workspace_bytes(n_items, n_ssrc):
+    """the bytes of the workspace a DecBatch.srtp_unprotect_device call over n_items datagrams and n_ssrc sources needs (lc3plus_srtp_workspace_bytes); 0 for
+    arguments the call refuses"""
+    return int(load_library().lc3plus_srtp_workspace_bytes(int(n_items), int(n_ssrc)))
+
+
+def plan_srtp_protect(pkt_route, pkt_offset, pkt_size, pkt_status, wire, ctx, roc, seq_base, dst, dst_stride, tag_len=10, header_room=12, payload_room=0,
+                      next_seq=None, n_packets=None, wire_capacity=None, dst_capacity=None):
+    """The rule of Batch.srtp_protect_device / DecBatch.srtp_protect_device on the host (lc3plus_plan_srtp_protect, no device needed): the stamp's view of the
+    egress's packet list pkt_route, pkt_offset (int64), pkt_size, pkt_status (uint8) [max_packets] (n_packets of it: all by default), the stamped wire buffer
+    (uint8; wire_capacity bytes of it), per route ctx [n_routes, SRTP_CTX_WORDS], roc, seq_base and optionally next_seq [n_routes]; dst: the destination's
+    contents before the call (uint8; dst_capacity bytes of it) -> dict of dst (the buffer after the call), out_offset (int64), out_size, out_status (uint8)
+    [max_packets] (zero behind n_packets) and next_roc [n_routes] (None without next_seq).  LC3Error for arguments the C call refuses."""
+    route = np.ascontiguousarray(pkt_route, dtype=np.int32).reshape(-1)
+    m = route.size
+    off, size = np.ascontiguousarray(pkt_offset, dtype=np.int64).reshape(-1), np.ascontiguousarray(pkt_size, dtype=np.int32).reshape(-1)
+    pst = np.ascontiguousarray(pkt_status, dtype=np.uint8).reshape(-1)
+    if not (off.size == size.size == pst.size == m):
+        raise ValueError("the list arrays hold one entry per packet")
+    ctx = np.ascontiguousarray(_u32(ctx)).reshape(-1, SRTP_CTX_WORDS)
+    R = ctx.shape[0]
+    roc, seq_base = _u32(roc), _u32(seq_base)
+    next_seq = _u32(next_seq) if next_seq is not None else None
+    if roc.size != R or seq_base.size != R or (next_seq is not None and next_seq.size != R):
+        raise ValueError("ctx, roc, seq_base and next_seq hold one entry per route")
+    wire = np.ascontiguousarray(wire, dtype=np.uint8).reshape(-1)
+    dst = np.array(dst, dtype=np.uint8).reshape(-1)                   # a copy: the call's destination starts with these contents
+    count = np.array([m if n_packets is None else int(n_packets)], np.int64)
+    outs = [np.zeros(m, np.int64), np.zeros(m, np.int32), np.zeros(m, np.uint8), np.zeros(R, np.int32) if next_seq is not None else None]
+    pad = np.zeros(8, np.uint8)
+    ptr = lambda a: (a if a.size else pad).ctypes.data if a is not None else None
+    rc = load_library().lc3plus_plan_srtp_protect(m, ptr(count), ptr(route), ptr(off), ptr(size), ptr(pst), ptr(wire),
+                                                  wire.size if wire_capacity is None else int(wire_capacity), int(header_room), int(payload_room), R, ptr(ctx),
+                                                  ptr(roc), ptr(seq_base), ptr(next_seq), ptr(dst), dst.size if dst_capacity is None else int(dst_capacity),
+                                                  int(dst_stride), int(tag_len), *[ptr(a) for a in outs])
+    if rc:
+        raise LC3Error(rc, "lc3plus_plan_srtp_protect")
+    return dict(zip(SRTP_PROTECT_OUTPUTS, outs), dst=dst)
+
+
+def _srtp_unprotect_arrays(ring, dg_offsets, dg_sizes, ssrc_key, ctx, state, optional):
+    """the arrays of an unprotect call as the C calls take them: (ring - a copy -, dg_offsets, dg_sizes, ssrc_key, ctx, state_in; outputs in
+    SRTP_UNPROTECT_OUTPUTS order, None for NULL)"""
+    ring = np.array(ring, dtype=np.uint8).reshape(-1)                 # a copy: the call decrypts in place
+    dg_offsets = np.ascontiguousarray(dg_offsets, dtype=np.int64).reshape(-1)
+    dg_sizes = np.ascontiguousarray(dg_sizes, dtype=np.int32).reshape(-1)
+    key = _u32(ssrc_key)
+    if dg_offsets.size != dg_sizes.size:
+        raise ValueError("dg_offsets and dg_sizes hold one entry per datagram")
+    ctx = np.ascontiguousarray(_u32(ctx)).reshape(-1, SRTP_CTX_WORDS)
+    state = np.ascontiguousarray(_u32(state)).reshape(-1, SRTP_STATE_WORDS)
+    if ctx.shape[0] != key.size or state.shape[0] != key.size:
+        raise ValueError("ssrc_key, ctx and state hold one entry per source")
+    n = dg_offsets.size
+    outs = [np.zeros((key.size, SRTP_STATE_WORDS), np.int32), np.zeros(n, np.int32), np.zeros(n, np.uint8) if "status" in optional else None,
+            np.zeros(n, np.int64) if "index" in optional else None, np.zeros(SRTP_STATS_WORDS, np.int32) if "stats" in optional else None]
+    return [ring, dg_offsets, dg_sizes, key, ctx, state], outs
+
+
+def plan_srtp_unprotect(ring, dg_offsets, dg_sizes, ssrc_key, ctx, state, tag_len=10, optional=SRTP_UNPROTECT_OPTIONAL, ring_capacity=None):
+    """The rule of DecBatch.srtp_unprotect on the host (lc3plus_plan_srtp_unprotect, no device needed): ring (uint8, ring_capacity bytes of it: all by default),
+    the datagrams dg_offsets (int64) / dg_sizes [n], the sources ssrc_key (ascending as uint32) with ctx [n_ssrc, SRTP_CTX_WORDS] and state [n_ssrc,
+    SRTP_STATE_WORDS] (zeros: a source that has not started) -> dict of ring (the buffer after the call: accepted payloads decrypted), state (the advanced
+    state), sizes [n] (rtp_parse's dg_sizes), status (uint8) [n], index (int64) [n] and stats [SRTP_STATS_WORDS]; those of SRTP_UNPROTECT_OPTIONAL not named in
+    `optional` are passed as NULL and come back as None.  LC3Error for arguments the C call refuses."""
+    ins, outs = _srtp_unprotect_arrays(ring, dg_offsets, dg_sizes, ssrc_key, ctx, state, optional)
+    pad = np.zeros(8, np.uint8)
+    ptr = lambda a: (a if a.size else pad).ctypes.data if a is not None else None
+    cap = ins[0].size if ring_capacity is None else int(ring_capacity)
+    rc = load_library().lc3plus_plan_srtp_unprotect(ins[1].size, ptr(ins[0]), cap, ptr(ins[1]), ptr(ins[2]), ins[3].size, ptr(ins[3]), ptr(ins[4]), ptr(ins[5]),
+                                                    ptr(outs[0]), int(tag_len), *[ptr(a) for a in outs[1:]])
+    if rc:
+        raise LC3Error(rc, "lc3plus_plan_srtp_unprotect")
+    return dict(zip(SRTP_UNPROTECT_OUTPUTS, outs), ring=ins[0])
+
+
+class _SrtpProtect:
+    """The send side of Secure RTP for both batch kinds (lc3plus_{enc,dec}_batch_srtp_protect; include/lc3plus_batch.h "Secure RTP")."""
+
+    def srtp_protect_device(self, max_packets, d_n_packets_ptr, d_pkt_route_ptr, d_pkt_offset_ptr, d_pkt_size_ptr, d_pkt_status_ptr, d_wire_ptr, wire_capacity,
+                            n_routes, d_ctx_ptr, d_roc_ptr, d_seq_base_ptr, d_dst_ptr, dst_capacity, dst_stride, d_out_offset_ptr, d_out_size_ptr,
+                            d_out_status_ptr, tag_len=10, header_room=12, payload_room=0, d_next_seq_ptr=None, d_next_roc_ptr=None, hip_stream=None, sync=False):
+        """Raw device pointers only - the egress's packet list as rtp_stamp_device took it with the stamp's pkt_status, the stamped wire buffer, per route ctx
+        [n_routes, SRTP_CTX_WORDS], roc, seq_base and optionally next_seq -> every stamped packet as an SRTP packet (header, encrypted payload, tag of tag_len
+        bytes) at dst + p * dst_stride, out_offset (int64), out_size, out_status (uint8) [max_packets] and the optional next_roc [n_routes].  Stateless: nothing
+        of the batch's streams is read or written.  Queued on hip_stream; returns at once unless sync."""
+        def p(x):
+            return C.c_void_p(x) if x else None
+        rc = self._ssf("_srtp_protect")(self.h, int(max_packets), p(d_n_packets_ptr), p(d_pkt_route_ptr), p(d_pkt_offset_ptr), p(d_pkt_size_ptr), p(d_pkt_status_ptr),
+                                        p(d_wire_ptr), int(wire_capacity), int(header_room), int(payload_room), int(n_routes), p(d_ctx_ptr), p(d_roc_ptr),
+                                        p(d_seq_base_ptr), p(d_next_seq_ptr), p(d_dst_ptr), int(dst_capacity), int(dst_stride), int(tag_len), p(d_out_offset_ptr),
+                                        p(d_out_size_ptr), p(d_out_status_ptr), p(d_next_roc_ptr), p(hip_stream), 1 if sync else 0)
+        if rc:
+            raise LC3Error(rc, self._ss + "_srtp_protect")
+
+
 class _StreamLifecycle:
     """Reset, export and import single streams (lc3plus_{enc,dec}_batch_{reset,export,import}_streams; include/lc3plus_batch.h).  Stream lists are host
     sequences of indices; blobs are stream_state_size bytes per stream."""
@@ -851,7 +986,7 @@ def stream_header_ok(header, blob):
     return bool(load_library().lc3plus_stream_header_ok(h.ctypes.data, b.ctypes.data))
 
 
-class Batch(_StreamLifecycle, _Egress, _RtpStamp):
+class Batch(_StreamLifecycle, _Egress, _RtpStamp, _SrtpProtect):
     """n_streams independent encoders (lc3plus_enc_batch_*), state resident on the GPU between encode() calls."""
 
     def __init__(self, n_streams, samplerate, channels, frame_ms, hrmode, bitrates, device=-1):
@@ -1386,7 +1521,7 @@ def plan_ingest(n_streams, channels, stream, seq, offsets, num_bytes, base, n_fr
     return dict(zip(ING_OUTPUTS, outs))
 
 
-class DecBatch(_StreamLifecycle, _Egress, _RtpStamp):
+class DecBatch(_StreamLifecycle, _Egress, _RtpStamp, _SrtpProtect):
     """n_streams independent decoders (lc3plus_dec_batch_*), state resident on the GPU between decode() calls."""
 
     def __init__(self, n_streams, samplerate, channels, frame_ms, hrmode, num_bytes, device=-1):
@@ -1640,6 +1775,36 @@ class DecBatch(_StreamLifecycle, _Egress, _RtpStamp):
             for k in range(8, 13):
                 back(k)
         return dict(zip(RR_OUTPUTS, outs))
+
+    def srtp_unprotect_device(self, n_items, d_ring_ptr, ring_capacity, d_dg_offsets_ptr, d_dg_sizes_ptr, n_ssrc, d_ssrc_key_ptr, d_ctx_ptr, d_state_in_ptr,
+                              d_state_out_ptr, d_sizes_out_ptr, d_workspace_ptr, workspace_bytes, tag_len=10, d_status_ptr=None, d_index_ptr=None, d_stats_ptr=None,
+                              hip_stream=None, sync=False):
+        """The receive side of Secure RTP (lc3plus_dec_batch_srtp_unprotect), in front of rtp_parse_device on the same datagram list: raw device pointers only -
+        the datagrams in ring, the sources ssrc_key (ascending as uint32) with ctx [n_ssrc, SRTP_CTX_WORDS], state_in / state_out [n_ssrc, SRTP_STATE_WORDS]
+        (they may be one array), a workspace of srtp_workspace_bytes(n_items, n_ssrc) bytes -> the accepted datagrams decrypted in place, sizes_out [n_items]
+        (rtp_parse_device's dg_sizes), the advanced state and the optional status (uint8), index (int64) [n_items] and stats [SRTP_STATS_WORDS].  Stateless:
+        nothing of the batch's streams is read or written.  Queued on hip_stream; returns at once unless sync."""
+        def p(x):
+            return C.c_void_p(x) if x else None
+        rc = self.lib.lc3plus_dec_batch_srtp_unprotect(self.h, int(n_items), p(d_ring_ptr), int(ring_capacity), p(d_dg_offsets_ptr), p(d_dg_sizes_ptr), int(n_ssrc),
+                                                       p(d_ssrc_key_ptr), p(d_ctx_ptr), p(d_state_in_ptr), p(d_state_out_ptr), int(tag_len), p(d_sizes_out_ptr),
+                                                       p(d_status_ptr), p(d_index_ptr), p(d_stats_ptr), p(d_workspace_ptr), int(workspace_bytes), p(hip_stream),
+                                                       1 if sync else 0)
+        if rc:
+            raise LC3Error(rc, "lc3plus_dec_batch_srtp_unprotect")
+
+    def srtp_unprotect(self, ring, dg_offsets, dg_sizes, ssrc_key, ctx, state, tag_len=10, optional=SRTP_UNPROTECT_OPTIONAL, ring_capacity=None):
+        """Host convenience: the arrays of plan_srtp_unprotect uploaded, run on the device and downloaded -> the dict plan_srtp_unprotect gives.  Device memory
+        through the HIP runtime as in probe(), the workspace too, freed before it returns."""
+        ins, outs = _srtp_unprotect_arrays(ring, dg_offsets, dg_sizes, ssrc_key, ctx, state, optional)
+        n, S = ins[1].size, ins[3].size
+        cap = ins[0].size if ring_capacity is None else int(ring_capacity)
+        work = np.zeros(max(srtp_workspace_bytes(n, S), 8), np.uint8)
+        with _on_device(ins + outs + [work]) as (v, back):
+            self.srtp_unprotect_device(n, v[0], cap, v[1], v[2], S, v[3], v[4], v[5], v[6], v[7], v[11], work.size, tag_len, v[8], v[9], v[10], sync=True)
+            for k in [0] + list(range(6, 11)):
+                back(k)
+        return dict(zip(SRTP_UNPROTECT_OUTPUTS, outs), ring=ins[0])
 
     def decode_traced(self, frames, bfi=None, bps=16):
         frames, T, stride, bfi, pcm, status = self._prep(frames, bfi, bps)

@@ -27,6 +27,7 @@
 #include "lc3_egress_shim.h"
 #include "lc3_rtp_shim.h"
 #include "lc3_rtcp_shim.h"
+#include "lc3_srtp_shim.h"
 
 #ifndef M_PI
 #define M_PI 3.14159265358979323846
@@ -2458,6 +2459,226 @@ LC3_Error lc3plus_dec_batch_rtcp_stats(lc3plus_dec_batch* b, int64_t n_items,
     q.ssrc = ssrc; q.lsr = lsr; q.dlsr = dlsr; q.blocks = blocks; q.ext_seq = ext_seq; q.item_status = item_status; q.stream_stats = stream_stats;
     q.workspace = workspace; q.workspace_bytes = (long long)workspace_bytes; q.hip_stream = hip_stream ? hip_stream : own;
     return rtcp_stats_run(&q) ? LC3_ERROR : LC3_OK;
+}
+/* ---- Secure RTP (include/lc3plus_batch.h "Secure RTP"; lc3_srtp_shim.h) ---- */
+LC3_Error lc3plus_srtp_make_context(const uint8_t* master_key, const uint8_t* master_salt, int32_t* ctx)
+{
+    if (!master_key || !master_salt || !ctx) return LC3_NULL_ERROR;
+    lc3s_make_context(master_key, master_salt, ctx);
+    return LC3_OK;
+}
+/* what a protect call takes behind its batch, in the header's order */
+typedef struct {
+    int64_t max_packets; const int64_t* n_packets;
+    const int32_t* pkt_route; const int64_t* pkt_offset; const int32_t* pkt_size; const uint8_t* pkt_status;
+    const void* wire; int64_t wire_capacity; int header_room; int payload_room;
+    int n_routes; const int32_t* ctx; const int32_t* roc; const int32_t* seq_base; const int32_t* next_seq;
+    void* dst; int64_t dst_capacity; int64_t dst_stride; int tag_len;
+    int64_t* out_offset; int32_t* out_size; uint8_t* out_status; int32_t* next_roc;
+} srtp_protect_args;
+/* the checks every protect call makes first, in the header's order */
+static LC3_Error srtp_protect_check(const srtp_protect_args* a)
+{
+    if (!a->n_packets || !a->pkt_route || !a->pkt_offset || !a->pkt_size || !a->pkt_status || !a->wire || !a->ctx || !a->roc || !a->seq_base || !a->dst ||
+        !a->out_offset || !a->out_size || !a->out_status)
+        return LC3_NULL_ERROR;
+    if (a->next_roc && !a->next_seq) return LC3_NULL_ERROR;
+    if (a->max_packets <= 0 || a->max_packets >= LC3S_MAX_ITEMS || a->wire_capacity < 0 || a->payload_room < 0 || a->header_room < LC3R_FIXED ||
+        a->header_room - LC3R_FIXED < a->payload_room || a->n_routes <= 0)
+        return LC3_ERROR;
+    if (a->dst_capacity < 0 || a->dst_stride <= 0 || a->dst_stride > LC3S_MAX_STRIDE || (a->tag_len != 4 && a->tag_len != 10)) return LC3_ERROR;
+    const uintptr_t w0 = (uintptr_t)a->wire, d0 = (uintptr_t)a->dst;
+    if (d0 < w0 + (uintptr_t)a->wire_capacity && w0 < d0 + (uintptr_t)a->dst_capacity) return LC3_ERROR;          /* out of place only */
+    return LC3_OK;
+}
+static lc3s_protect_in srtp_protect_in(const srtp_protect_args* a)
+{
+    const lc3s_protect_in q = {a->pkt_route, (const long long*)a->pkt_offset, a->pkt_size, a->pkt_status, (const uint8_t*)a->wire, a->ctx, a->roc, a->seq_base,
+                               a->next_seq, (uint8_t*)a->dst, (long long)a->wire_capacity, (long long)a->dst_capacity, (long long)a->dst_stride, a->header_room,
+                               a->payload_room, a->n_routes, a->tag_len};
+    return q;
+}
+/* the rule on the host: the kernels' steps (lc3_srtp.inc) on the text they run */
+LC3_Error lc3plus_plan_srtp_protect(int64_t max_packets, const int64_t* n_packets,
+    const int32_t* pkt_route, const int64_t* pkt_offset, const int32_t* pkt_size, const uint8_t* pkt_status,
+    const void* wire, int64_t wire_capacity, int header_room, int payload_room,
+    int n_routes, const int32_t* ctx, const int32_t* roc, const int32_t* seq_base, const int32_t* next_seq,
+    void* dst, int64_t dst_capacity, int64_t dst_stride, int tag_len,
+    int64_t* out_offset, int32_t* out_size, uint8_t* out_status, int32_t* next_roc)
+{
+    const srtp_protect_args a = {max_packets, n_packets, pkt_route, pkt_offset, pkt_size, pkt_status, wire, wire_capacity, header_room, payload_room, n_routes, ctx,
+                                 roc, seq_base, next_seq, dst, dst_capacity, dst_stride, tag_len, out_offset, out_size, out_status, next_roc};
+    const LC3_Error e = srtp_protect_check(&a);
+    if (e) return e;
+    const lc3s_protect_in q = srtp_protect_in(&a);
+    uint32_t te[LC3S_TE_WORDS];
+    for (uint32_t x = 0; x < LC3S_TE_WORDS; x++) te[x] = lc3s_te0(x);
+    const int64_t n = *n_packets < max_packets ? *n_packets : max_packets;
+    for (int64_t p = 0; p < n; p++) {
+        int32_t size = 0;
+        const int st = lc3s_protect(&q, p, te, 1, &size);
+        out_offset[p] = p * dst_stride; out_size[p] = size; out_status[p] = (uint8_t)st;
+    }
+    if (next_roc)
+        for (int r = 0; r < n_routes; r++) lc3s_route_out(&q, r, next_roc);
+    return LC3_OK;
+}
+/* what an unprotect call takes behind its batch, in the header's order */
+typedef struct {
+    int64_t n_items; void* ring; int64_t ring_capacity; const int64_t* dg_offsets; const int32_t* dg_sizes;
+    int n_ssrc; const int32_t* ssrc_key; const int32_t* ctx; const int32_t* state_in; int32_t* state_out; int tag_len;
+    int32_t* sizes_out; uint8_t* status; int64_t* index; int32_t* stats;
+} srtp_unprotect_args;
+static LC3_Error srtp_unprotect_check(const srtp_unprotect_args* a)
+{
+    if (!a->ring || !a->dg_offsets || !a->dg_sizes || !a->ssrc_key || !a->ctx || !a->state_in || !a->state_out || !a->sizes_out) return LC3_NULL_ERROR;
+    if (a->n_items <= 0 || a->n_items >= LC3S_MAX_ITEMS || a->ring_capacity < 0 || a->n_ssrc <= 0 || (a->tag_len != 4 && a->tag_len != 10)) return LC3_ERROR;
+    return LC3_OK;
+}
+int64_t lc3plus_srtp_workspace_bytes(int64_t n_items, int n_ssrc)
+{
+    return (int64_t)lc3s_workspace_bytes((long long)n_items, n_ssrc);
+}
+/* the rule on the host: the kernels' passes one after the other - the first items, the items against state_in, the window bits against the new tops, the state */
+LC3_Error lc3plus_plan_srtp_unprotect(int64_t n_items,
+    void* ring, int64_t ring_capacity, const int64_t* dg_offsets, const int32_t* dg_sizes,
+    int n_ssrc, const int32_t* ssrc_key, const int32_t* ctx, const int32_t* state_in, int32_t* state_out, int tag_len,
+    int32_t* sizes_out, uint8_t* status, int64_t* index, int32_t* stats)
+{
+    const srtp_unprotect_args a = {n_items, ring, ring_capacity, dg_offsets, dg_sizes, n_ssrc, ssrc_key, ctx, state_in, state_out, tag_len, sizes_out, status, index, stats};
+    const LC3_Error e = srtp_unprotect_check(&a);
+    if (e) return e;
+    uint32_t te[LC3S_TE_WORDS];
+    for (uint32_t x = 0; x < LC3S_TE_WORDS; x++) te[x] = lc3s_te0(x);
+    unsigned long long* top1 = calloc((size_t)n_ssrc, sizeof *top1);
+    unsigned long long* bits = calloc((size_t)n_ssrc, sizeof *bits);
+    int64_t* first = malloc(sizeof *first * (size_t)n_ssrc);
+    int64_t* accepted = malloc(sizeof *accepted * (size_t)n_items);
+    lc3s_item* items = malloc(sizeof *items * (size_t)n_items);
+    if (!top1 || !bits || !first || !accepted || !items) { free(top1); free(bits); free(first); free(accepted); free(items); return LC3_ERROR; }
+    uint8_t* r8 = (uint8_t*)ring;
+    for (int s = 0; s < n_ssrc; s++) first[s] = -1;
+    if (stats) memset(stats, 0, sizeof(int32_t) * LC3S_STATS_WORDS);
+    for (int64_t i = 0; i < n_items; i++) {
+        items[i] = lc3s_check(r8, ring_capacity, dg_offsets[i], dg_sizes[i], tag_len, ssrc_key, n_ssrc);
+        if (items[i].status == LC3S_OK && first[items[i].src] < 0) first[items[i].src] = i;
+    }
+    for (int64_t i = 0; i < n_items; i++) {
+        int st = items[i].status;
+        long long idx = 0;
+        accepted[i] = -1;
+        sizes_out[i] = 0;
+        if (st == LC3S_OK) {
+            const int s = items[i].src;
+            const int32_t* state = state_in + (size_t)s * LC3S_STATE_WORDS;
+            const uint32_t s_l_first = lc3s_seq_at(r8, dg_offsets[first[s]]);
+            st = lc3s_unprotect(r8, dg_offsets[i], dg_sizes[i], tag_len, &items[i], state, s_l_first, (const uint32_t*)ctx + (size_t)s * LC3S_CTX_WORDS, te, 1, &idx);
+            if (st == LC3S_OK) {
+                accepted[i] = idx; sizes_out[i] = dg_sizes[i] - tag_len;
+                if ((unsigned long long)idx + 1 > top1[s]) top1[s] = (unsigned long long)idx + 1;
+            }
+        }
+        if (status) status[i] = (uint8_t)st;
+        if (index) index[i] = idx;
+        if (stats) stats[st]++;
+    }
+    for (int64_t i = 0; i < n_items; i++)
+        if (accepted[i] >= 0) {
+            const int s = items[i].src;
+            bits[s] |= lc3s_window_bit(state_in + (size_t)s * LC3S_STATE_WORDS, top1[s], accepted[i]);
+        }
+    for (int s = 0; s < n_ssrc; s++) lc3s_state_out(state_in + (size_t)s * LC3S_STATE_WORDS, state_out + (size_t)s * LC3S_STATE_WORDS, top1[s], bits[s]);
+    free(top1); free(bits); free(first); free(accepted); free(items);
+    return LC3_OK;
+}
+/* the sibling library with the SRTP kernels, loaded as the RTP framing's is; NULL where it is missing */
+typedef int (*srtp_protect_fn)(const lc3srtp_protect_call*);
+typedef int (*srtp_unprotect_fn)(const lc3srtp_unprotect_call*);
+static pthread_once_t srtp_once = PTHREAD_ONCE_INIT;
+static srtp_protect_fn srtp_protect_run;
+static srtp_unprotect_fn srtp_unprotect_run;
+static void srtp_load(void)
+{
+    Dl_info di;
+    char path[4096];
+    if (!dladdr((void*)&srtp_load, &di) || !di.dli_fname) return;
+    const char* slash = strrchr(di.dli_fname, '/');
+    const size_t dir = slash ? (size_t)(slash - di.dli_fname) + 1 : 0;
+    static const char name[] = "liblc3plus_srtp_hip.so";
+    if (dir + sizeof name > sizeof path) return;
+    memcpy(path, di.dli_fname, dir);
+    memcpy(path + dir, name, sizeof name);
+    void* h = dlopen(path, RTLD_NOW | RTLD_LOCAL);
+    if (!h) { fprintf(stderr, "lc3plus_hip: the Secure RTP library is missing: %s\n", dlerror()); return; }
+    srtp_protect_fn protect = (srtp_protect_fn)dlsym(h, "lc3srtp_protect_run");
+    srtp_unprotect_fn unprotect = (srtp_unprotect_fn)dlsym(h, "lc3srtp_unprotect_run");
+    if (protect && unprotect) { srtp_protect_run = protect; srtp_unprotect_run = unprotect; }
+}
+/* both protect entry points end here */
+static LC3_Error srtp_protect_queue(void* dev, int decoder, const srtp_protect_args* a, void* hip_stream, int sync)
+{
+    lc3srtp_protect_call q;
+    memset(&q, 0, sizeof q);
+    void* own = NULL;
+    if (rtp_device(dev, decoder, !hip_stream, &q.device, &own)) return LC3_ERROR;
+    pthread_once(&srtp_once, srtp_load);
+    if (!srtp_protect_run) return LC3_ERROR;
+    q.sync = sync; q.max_packets = (long long)a->max_packets; q.n_packets = (const long long*)a->n_packets; q.in = srtp_protect_in(a);
+    q.out_offset = (long long*)a->out_offset; q.out_size = a->out_size; q.out_status = a->out_status; q.next_roc = a->next_roc;
+    q.hip_stream = hip_stream ? hip_stream : own;
+    return srtp_protect_run(&q) ? LC3_ERROR : LC3_OK;
+}
+LC3_Error lc3plus_enc_batch_srtp_protect(lc3plus_batch* b, int64_t max_packets, const int64_t* n_packets,
+    const int32_t* pkt_route, const int64_t* pkt_offset, const int32_t* pkt_size, const uint8_t* pkt_status,
+    const void* wire, int64_t wire_capacity, int header_room, int payload_room,
+    int n_routes, const int32_t* ctx, const int32_t* roc, const int32_t* seq_base, const int32_t* next_seq,
+    void* dst, int64_t dst_capacity, int64_t dst_stride, int tag_len,
+    int64_t* out_offset, int32_t* out_size, uint8_t* out_status, int32_t* next_roc, void* hip_stream, int sync)
+{
+    if (!b) return LC3_NULL_ERROR;
+    const srtp_protect_args a = {max_packets, n_packets, pkt_route, pkt_offset, pkt_size, pkt_status, wire, wire_capacity, header_room, payload_room, n_routes, ctx,
+                                 roc, seq_base, next_seq, dst, dst_capacity, dst_stride, tag_len, out_offset, out_size, out_status, next_roc};
+    const LC3_Error e = srtp_protect_check(&a);
+    if (e) return e;
+    return srtp_protect_queue(b->dev, 0, &a, hip_stream, sync);
+}
+LC3_Error lc3plus_dec_batch_srtp_protect(lc3plus_dec_batch* b, int64_t max_packets, const int64_t* n_packets,
+    const int32_t* pkt_route, const int64_t* pkt_offset, const int32_t* pkt_size, const uint8_t* pkt_status,
+    const void* wire, int64_t wire_capacity, int header_room, int payload_room,
+    int n_routes, const int32_t* ctx, const int32_t* roc, const int32_t* seq_base, const int32_t* next_seq,
+    void* dst, int64_t dst_capacity, int64_t dst_stride, int tag_len,
+    int64_t* out_offset, int32_t* out_size, uint8_t* out_status, int32_t* next_roc, void* hip_stream, int sync)
+{
+    if (!b) return LC3_NULL_ERROR;
+    const srtp_protect_args a = {max_packets, n_packets, pkt_route, pkt_offset, pkt_size, pkt_status, wire, wire_capacity, header_room, payload_room, n_routes, ctx,
+                                 roc, seq_base, next_seq, dst, dst_capacity, dst_stride, tag_len, out_offset, out_size, out_status, next_roc};
+    const LC3_Error e = srtp_protect_check(&a);
+    if (e) return e;
+    return srtp_protect_queue(b->dev, 1, &a, hip_stream, sync);
+}
+LC3_Error lc3plus_dec_batch_srtp_unprotect(lc3plus_dec_batch* b, int64_t n_items,
+    void* ring, int64_t ring_capacity, const int64_t* dg_offsets, const int32_t* dg_sizes,
+    int n_ssrc, const int32_t* ssrc_key, const int32_t* ctx, const int32_t* state_in, int32_t* state_out, int tag_len,
+    int32_t* sizes_out, uint8_t* status, int64_t* index, int32_t* stats,
+    void* workspace, int64_t workspace_bytes, void* hip_stream, int sync)
+{
+    if (!b) return LC3_NULL_ERROR;
+    const srtp_unprotect_args a = {n_items, ring, ring_capacity, dg_offsets, dg_sizes, n_ssrc, ssrc_key, ctx, state_in, state_out, tag_len, sizes_out, status, index, stats};
+    if (!workspace) return LC3_NULL_ERROR;
+    const LC3_Error e = srtp_unprotect_check(&a);
+    if (e) return e;
+    if (workspace_bytes < lc3plus_srtp_workspace_bytes(n_items, n_ssrc)) return LC3_ERROR;
+    lc3srtp_unprotect_call q;
+    memset(&q, 0, sizeof q);
+    void* own = NULL;
+    if (rtp_device(b->dev, 1, 0, &q.device, &own)) return LC3_ERROR;
+    pthread_once(&srtp_once, srtp_load);
+    if (!srtp_unprotect_run) return LC3_ERROR;
+    q.sync = sync; q.n_ssrc = n_ssrc; q.tag_len = tag_len; q.n_items = (long long)n_items; q.ring_capacity = (long long)ring_capacity;
+    q.ring = ring; q.dg_offsets = (const long long*)dg_offsets; q.dg_sizes = dg_sizes; q.ssrc_key = ssrc_key; q.ctx = ctx; q.state_in = state_in; q.state_out = state_out;
+    q.sizes_out = sizes_out; q.status = status; q.index = (long long*)index; q.stats = stats;
+    q.workspace = workspace; q.workspace_bytes = (long long)workspace_bytes; q.hip_stream = hip_stream ? hip_stream : own;
+    return srtp_unprotect_run(&q) ? LC3_ERROR : LC3_OK;
 }
 LC3_Error lc3plus_dec_batch_set_input_ready(lc3plus_dec_batch* b, int ready)
 {

@@ -714,7 +714,8 @@ int64_t lc3plus_egress_work_bytes(int n_routes, int n_frames);
  * is an RTP header there.  lc3plus_dec_batch_rtp_parse turns the first into the second and lc3plus_*_batch_rtp_stamp fills the third, so that
  * datagrams -> parse -> probe -> ingest -> set_frame_counts + decode_packed and encode_packed -> egress -> stamp run on one HIP stream with no host wait.
  * A payload format's own payload header (the LC3plus table of contents is one) stays with the caller: the stamp leaves payload_room untouched bytes between
- * the RTP header and the frame, and the parse skips payload_room bytes.  SRTP, the contents of RTCP packets and several frames per packet are not handled.
+ * the RTP header and the frame, and the parse skips payload_room bytes.  SRTP is the block "Secure RTP" below; the contents of RTCP packets (SRTCP with them) and
+ * several frames per packet are not handled.
  *
  * Every pointer but `batch` is a device pointer and is read when the kernels run, so the call queued before on the same stream may produce it.  Both calls are
  * STATELESS and allocate nothing: they borrow the batch's device and n_streams and nothing else, no stream state, configuration or buffer of the batch is read
@@ -932,6 +933,153 @@ LC3_Error lc3plus_plan_rtcp_stats(int64_t n_items,
     int n_streams, const int32_t* state_in, int32_t* state_out,
     int make_report, const int32_t* ssrc, const int32_t* lsr, const int32_t* dlsr, uint8_t* blocks,
     int32_t* ext_seq, uint8_t* item_status, int32_t* stream_stats);
+
+/* ---- Secure RTP: protect stamped packets, unprotect received datagrams, on the device -------------------------------------------------------------------------
+ * RFC 3711 with its default transform, AES_CM_128_HMAC_SHA1_80, and the _32 variant: AES-128 in counter mode over every payload byte, HMAC-SHA1 over every
+ * packet, the tag's length (tag_len: 10 or 4 bytes) a parameter.  lc3plus_*_batch_srtp_protect stands behind the stamp and lc3plus_dec_batch_srtp_unprotect in
+ * front of the parse, so that encode_packed -> egress -> stamp -> protect and datagrams -> unprotect -> parse -> probe -> ingest run on one HIP stream with no
+ * host wait.  NOT HANDLED: a key derivation rate other than 0, the MKI (master key identifier), SRTCP, the AEAD suites of RFC 7714, header-extension
+ * encryption (RFC 6904) and re-keying (a new master key is a new context, made and uploaded by the caller between calls).
+ *
+ * THE CONTEXT, host only.  lc3plus_srtp_make_context derives the session keys from a master key (16 bytes) and a master salt (14 bytes) by RFC 3711 4.3.1 with
+ * key derivation rate 0 - the AES-CM keystream under the master key from the IV (master_salt ^ label << 48) << 16: label 0 the cipher key (16 bytes), label 1
+ * the authentication key (20 bytes), label 2 the session salt (14 bytes) - and lays them out as the device reads them, LC3PLUS_SRTP_CTX_WORDS (64) words:
+ *   0 .. 43   the 44 round key words of the cipher key (FIPS-197 5.2), each big-endian
+ *   44 .. 47  the session salt << 16 as four big-endian words (the fourth ends in 16 zero bits)
+ *   48 .. 52  the SHA-1 state behind the block auth_key ^ 36 36 .. (the HMAC's ipad block), 53 .. 57 the state behind auth_key ^ 5C 5C .. (opad): with them a
+ *             packet costs its own compressions and one more, not three more
+ *   58 .. 63  zero
+ * The caller copies contexts to device memory ([n][64] words, one per route or per source).  The library keeps no copy of any key.  LC3_NULL_ERROR for a NULL
+ * argument. */
+#define LC3PLUS_SRTP_CTX_WORDS     64
+LC3_Error lc3plus_srtp_make_context(const uint8_t* master_key, const uint8_t* master_salt, int32_t* ctx);
+/* PROTECT.  Every pointer but `batch` is a device pointer and is read when the kernels run.  The call is STATELESS and allocates nothing; it borrows the batch's
+ * device and nothing else (the encoder form serves a sender, the decoder form a forwarder, as the stamp has it), is queued on hip_stream (NULL: the batch's
+ * stream) and returns at once unless sync.  No output may overlap an input or another output.
+ *   max_packets, n_packets (one int64 in device memory), pkt_route, pkt_offset, pkt_size : the egress's packet list as the stamp took it
+ *   pkt_status                    : [max_packets] the stamp's output
+ *   wire, wire_capacity, header_room, payload_room : as the stamp took them.  wire is not modified
+ *   n_routes; ctx [n_routes][64]; roc [n_routes] each route's rollover counter at seq_base[r]; seq_base [n_routes] the egress's; next_seq [n_routes] the
+ *                                   egress's output, or NULL
+ *   dst, dst_capacity, dst_stride : the destination: packet p goes to dst + p * dst_stride (the egress leaves no room behind a frame, so the call is out of place)
+ *   tag_len                       : 10 or 4
+ *   out_offset (int64), out_size, out_status (uint8) : [max_packets], written for the packets in front of n_packets
+ *   next_roc                      : [n_routes] each route's rollover counter at next_seq[r]; may be NULL, and needs next_seq
+ * THE RULE for packet p.  Its RTP packet is wire[a .. pkt_offset + pkt_size) with a = pkt_offset + header_room - payload_room - 12, the address the stamp wrote
+ * to, L bytes.  out_offset[p] = p * dst_stride.  The status is the first that applies:
+ *   LC3PLUS_SRTP_NOT_STAMPED  pkt_status[p] lacks LC3PLUS_RTP_STAMPED
+ *   LC3PLUS_SRTP_BAD_ROUTE    pkt_route[p] outside [0, n_routes)
+ *   LC3PLUS_SRTP_RANGE        pkt_offset < 0, pkt_size < header_room, pkt_size > 2^20 or pkt_offset + pkt_size > wire_capacity
+ *   LC3PLUS_SRTP_OVERFLOW     L + tag_len > dst_stride, or the slot ends past dst_capacity: (p + 1) * dst_stride > dst_capacity
+ *   LC3PLUS_SRTP_PROTECTED    the packet stands at dst + out_offset[p]: the header (12 bytes: the stamp writes CC = 0 and X = 0), the encrypted payload (the
+ *                             payload_room bytes and the frame) and the tag; out_size[p] = L + tag_len
+ * A packet that is not PROTECTED writes nothing and has out_size 0.  Of dst only the out_size bytes of protected packets are written; the rest of every slot
+ * keeps its contents.  SEQ and SSRC are the header's own bytes: what is on the wire is what the IV uses.  With r the route, b = seq_base[r] & 0xFFFF and
+ * d = (SEQ - b) & 0xFFFF the packet's rollover counter is ROC_p = roc[r] + ((b + d) >> 16) in 32-bit arithmetic, and
+ * next_roc[r] = roc[r] + ((b + ((next_seq[r] - seq_base[r]) & 0xFFFF)) >> 16).  THE CALLER'S CONDITION: a route sends fewer than 65 536 sequence numbers per call.
+ * Keystream block j is AES_k(IV + j) with IV = (salt << 16) ^ (SSRC << 64) ^ (index << 16) and index = ROC_p << 16 | SEQ (RFC 3711 4.1.1); the tag is the leftmost
+ * tag_len bytes of HMAC-SHA1(k_a, header || ciphertext || ROC_p as 4 big-endian bytes) (4.2).
+ * Refused calls queue nothing, checked in this order before anything of the batch or the device is touched: a NULL batch, n_packets, pkt_route, pkt_offset,
+ * pkt_size, pkt_status, wire, ctx, roc, seq_base, dst, out_offset, out_size or out_status, a next_roc without next_seq (LC3_NULL_ERROR); then max_packets <= 0
+ * or >= 2^29, wire_capacity < 0, payload_room < 0, header_room < 12 + payload_room, n_routes <= 0, dst_capacity < 0, dst_stride <= 0 or > 2^30, a tag_len other
+ * than 4 or 10, and a dst range [dst, dst + dst_capacity) that intersects the wire range (LC3_ERROR). */
+#define LC3PLUS_SRTP_PROTECTED     1
+#define LC3PLUS_SRTP_NOT_STAMPED   2
+#define LC3PLUS_SRTP_BAD_ROUTE     4
+#define LC3PLUS_SRTP_RANGE         8
+#define LC3PLUS_SRTP_OVERFLOW      16
+LC3_Error lc3plus_enc_batch_srtp_protect(lc3plus_batch* batch, int64_t max_packets, const int64_t* n_packets,
+    const int32_t* pkt_route, const int64_t* pkt_offset, const int32_t* pkt_size, const uint8_t* pkt_status,
+    const void* wire, int64_t wire_capacity, int header_room, int payload_room,
+    int n_routes, const int32_t* ctx, const int32_t* roc, const int32_t* seq_base, const int32_t* next_seq,
+    void* dst, int64_t dst_capacity, int64_t dst_stride, int tag_len,
+    int64_t* out_offset, int32_t* out_size, uint8_t* out_status, int32_t* next_roc, void* hip_stream, int sync);
+LC3_Error lc3plus_dec_batch_srtp_protect(lc3plus_dec_batch* batch, int64_t max_packets, const int64_t* n_packets,
+    const int32_t* pkt_route, const int64_t* pkt_offset, const int32_t* pkt_size, const uint8_t* pkt_status,
+    const void* wire, int64_t wire_capacity, int header_room, int payload_room,
+    int n_routes, const int32_t* ctx, const int32_t* roc, const int32_t* seq_base, const int32_t* next_seq,
+    void* dst, int64_t dst_capacity, int64_t dst_stride, int tag_len,
+    int64_t* out_offset, int32_t* out_size, uint8_t* out_status, int32_t* next_roc, void* hip_stream, int sync);
+/* The same rule on the host alone, no device: the same arrays in host memory, no batch, no stream.  The refusals of the calls above in their order, less that
+ * of the batch. */
+LC3_Error lc3plus_plan_srtp_protect(int64_t max_packets, const int64_t* n_packets,
+    const int32_t* pkt_route, const int64_t* pkt_offset, const int32_t* pkt_size, const uint8_t* pkt_status,
+    const void* wire, int64_t wire_capacity, int header_room, int payload_room,
+    int n_routes, const int32_t* ctx, const int32_t* roc, const int32_t* seq_base, const int32_t* next_seq,
+    void* dst, int64_t dst_capacity, int64_t dst_stride, int tag_len,
+    int64_t* out_offset, int32_t* out_size, uint8_t* out_status, int32_t* next_roc);
+/* UNPROTECT runs in front of lc3plus_dec_batch_rtp_parse on the same datagram list: it authenticates every datagram, decrypts the accepted ones IN PLACE in the
+ * ring and gives the sizes without the tags, which go to the parse as its dg_sizes.  Device pointers, stateless, allocation-free and queued as above; no
+ * output may overlap an input, another output or the workspace, but state_out may BE state_in.  THE CALLER'S CONDITION: the datagrams of one list do not overlap
+ * each other in the ring.
+ *   n_items, ring, ring_capacity, dg_offsets (int64), dg_sizes : the datagrams, as the parse takes them
+ *   n_ssrc, ssrc_key              : [n_ssrc] the sources, ascending as uint32 as for the parse (lc3plus_rtp_sort_ssrc) and searched by its rule
+ *   ctx [n_ssrc][64]; state_in, state_out [n_ssrc][LC3PLUS_SRTP_STATE_WORDS] : each source's context and its replay state before and after
+ *   tag_len                       : 10 or 4
+ *   sizes_out                     : [n_items]
+ *   status (uint8) [n_items], index (int64) [n_items], stats [LC3PLUS_SRTP_STATS_WORDS] : each may be NULL
+ *   workspace, workspace_bytes    : scratch of at least lc3plus_srtp_workspace_bytes(n_items, n_ssrc) bytes, at any alignment
+ * A source's state is 8 words: FLAGS (bit 0, LC3PLUS_SRTP_STARTED; the other bits are kept), ROC, S_L, WIN_LO, WIN_HI and three words kept as they are (zero).
+ * top = ROC << 16 | S_L is the highest index accepted so far; bit k of the window WIN_HI << 32 | WIN_LO is set where index top - k was accepted.  A zero-filled
+ * block is a source that has not started; the caller may preset its ROC word (a late joiner).
+ * THE RULE for item i, the first failing check giving its status (the status is also the index of its word in stats, which counts the items per status):
+ * 1. LC3PLUS_SRTP_UN_RANGE, _SHORT (size < 12 + tag_len), _VERSION, _RTCP and _HEADER are the parse's checks with size - tag_len in the size's place.  The P
+ *    bit is not looked at: the padding is encrypted.  A size above 2^20 is UN_RANGE as well: keystream block j is AES_k(IV + j) with j in the IV's low 16 bits,
+ *    which are zero, so a payload has at most 2^16 blocks (a datagram over UDP has fewer than 2^12).
+ * 2. LC3PLUS_SRTP_UNKNOWN_SSRC: the parse's search of ssrc_key.
+ * 3. The index estimate of RFC 3711 3.3.1 and Appendix A against the source's state AS IT STOOD WHEN THE CALL BEGAN: v = ROC - 1 where S_L < 32768 and
+ *    SEQ - S_L > 32768, v = ROC + 1 where S_L >= 32768 and S_L - 32768 > SEQ, else v = ROC; index = v << 16 | SEQ.  For a source that has not started S_L is
+ *    the SEQ of its first item in list order that passed checks 1 and 2, and ROC is the state's ROC word.  A guess of ROC - 1 at ROC == 0 is refused as
+ *    LC3PLUS_SRTP_REPLAY_OLD without authentication.
+ * 4. For a started source: LC3PLUS_SRTP_REPLAY_OLD where top - index >= 64, LC3PLUS_SRTP_REPLAYED where 0 <= top - index and that bit of the window is set.
+ * 5. LC3PLUS_SRTP_AUTH: the datagram's last tag_len bytes do not equal the tag (as in PROTECT) over the bytes in front of them followed by v.  All tag_len bytes
+ *    are compared.
+ * 6. LC3PLUS_SRTP_OK (0): the payload bytes [h, size - tag_len), h the header's length with CSRCs and extension, are decrypted in place;
+ *    sizes_out[i] = size - tag_len; index[i] is the 48-bit index.
+ * Every other item has sizes_out[i] = 0, which the parse refuses as SHORT, and index[i] = 0, and not one byte of it is changed.
+ * THE STATE AFTER THE CALL.  top' is the largest accepted index of the source where that exceeds top (or the source had not started), else top.  The new window
+ * is the old one shifted left by top' - top (zero at 64 or more), ORed with bit top' - index of every accepted item of this call that lies within 64.  Maximum
+ * and OR commute, so the result does not depend on the order the items are taken in.  A source with no accepted item keeps its state word for word.
+ * THE ONE DEVIATION FROM RFC 3711 3.3.2: the call is stateless inside itself - every item is checked against the state the call began with - so two authentic
+ * copies of one packet inside one call are both OK; a copy in a later call is REPLAYED.  This is what lets every item run in a lane of its own, and it costs
+ * nothing: the ingest behind the parse keeps one copy per cell.
+ * Refused calls queue nothing, checked in this order before anything of the batch or the device is touched: a NULL batch, workspace, ring, dg_offsets,
+ * dg_sizes, ssrc_key, ctx, state_in, state_out or sizes_out (LC3_NULL_ERROR); then n_items <= 0 or >= 2^29, ring_capacity < 0, n_ssrc <= 0, a tag_len other
+ * than 4 or 10, and workspace_bytes below what lc3plus_srtp_workspace_bytes answers (LC3_ERROR).
+ *
+ * The kernels live in liblc3plus_srtp_hip.so, which this library loads from its own directory on the first protect or unprotect call: where that file is
+ * missing the call returns LC3_ERROR and nothing else changes. */
+#define LC3PLUS_SRTP_STATE_WORDS   8
+#define LC3PLUS_SRTP_FLAGS         0
+#define LC3PLUS_SRTP_ROC           1
+#define LC3PLUS_SRTP_S_L           2
+#define LC3PLUS_SRTP_WIN_LO        3
+#define LC3PLUS_SRTP_WIN_HI        4
+#define LC3PLUS_SRTP_STARTED       1
+#define LC3PLUS_SRTP_OK            0
+#define LC3PLUS_SRTP_UN_RANGE      1
+#define LC3PLUS_SRTP_SHORT         2
+#define LC3PLUS_SRTP_VERSION       3
+#define LC3PLUS_SRTP_RTCP          4
+#define LC3PLUS_SRTP_HEADER        5
+#define LC3PLUS_SRTP_UNKNOWN_SSRC  6
+#define LC3PLUS_SRTP_REPLAY_OLD    7
+#define LC3PLUS_SRTP_REPLAYED      8
+#define LC3PLUS_SRTP_AUTH          9
+#define LC3PLUS_SRTP_STATS_WORDS   16
+LC3_Error lc3plus_dec_batch_srtp_unprotect(lc3plus_dec_batch* batch, int64_t n_items,
+    void* ring, int64_t ring_capacity, const int64_t* dg_offsets, const int32_t* dg_sizes,
+    int n_ssrc, const int32_t* ssrc_key, const int32_t* ctx, const int32_t* state_in, int32_t* state_out, int tag_len,
+    int32_t* sizes_out, uint8_t* status, int64_t* index, int32_t* stats,
+    void* workspace, int64_t workspace_bytes, void* hip_stream, int sync);
+/* the bytes of `workspace` for such a call; 0 for an n_items or n_ssrc the call refuses */
+int64_t lc3plus_srtp_workspace_bytes(int64_t n_items, int n_ssrc);
+/* The same rule on the host alone, no device: the same arrays in host memory (the ring is decrypted in place there), no batch, no workspace, no stream.  The
+ * refusals of the call above in their order, less those of the batch and the workspace. */
+LC3_Error lc3plus_plan_srtp_unprotect(int64_t n_items,
+    void* ring, int64_t ring_capacity, const int64_t* dg_offsets, const int32_t* dg_sizes,
+    int n_ssrc, const int32_t* ssrc_key, const int32_t* ctx, const int32_t* state_in, int32_t* state_out, int tag_len,
+    int32_t* sizes_out, uint8_t* status, int64_t* index, int32_t* stats);
 
 /* ---- Sharded batches: one call drives encoders or decoders on several GPUs ------------------------------------------------------------------
  * Streams are independent, so a sharded batch is n_devices ordinary batches, each owning a contiguous block of the n_streams streams on a device of its
