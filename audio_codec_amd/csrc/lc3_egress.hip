@@ -1,13 +1,9 @@
 /* lc3_egress.hip -- the packet egress's library (liblc3plus_egress_hip.so): the gfx950 kernels of lc3_egress.inc and the host code that launches them, behind
- * the C ABI of lc3_egress_shim.h.  A fourth library beside liblc3plus_hip.so, liblc3plus_probe_hip.so and liblc3plus_ingest_hip.so, so that the code objects of
- * those three stay what they are; lc3_host.c loads it on the first egress call and hands it the batch's device and stream count.  It keeps no state but its
- * launch counts and allocates nothing. */
+ * the C ABI of lc3_egress_shim.h.  A sibling library (DESIGN.md "Sibling libraries"): lc3_host.c loads it on the first egress call and hands it the batch's device
+ * and stream count.  It keeps no state but its launch counts and allocates nothing. */
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <stdio.h>
-#include <string.h>
 #include <stddef.h>
-#include <atomic>
 
 #include "lc3_egress_shim.h"
 
@@ -15,19 +11,11 @@
 #include "lc3_egress.inc"
 
 /* ---- host ---- */
-enum { K_CLASSIFY = 0, K_SUMS, K_BASE, K_SCATTER, K_ROUTE, K_COPY, K_COUNT };
-static const char* const k_names[K_COUNT] = {"lc3_egress_classify_kernel", "lc3_egress_sums_kernel", "lc3_egress_base_kernel", "lc3_egress_scatter_kernel",
-                                             "lc3_egress_route_kernel", "lc3_egress_copy_kernel"};
-static std::atomic<long long> k_launches[K_COUNT];
-
-extern "C" long long lc3egress_launch_count(const char* kernel)
-{
-    if (!kernel) return -1;
-    for (int i = 0; i < K_COUNT; i++) if (!strcmp(kernel, k_names[i])) return k_launches[i].load(std::memory_order_relaxed);
-    return -1;
-}
-
-#define ECHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { fprintf(stderr, "lc3plus_egress: %s: %s\n", #x, hipGetErrorString(e_)); return 1; } } while (0)
+#define SIB_NAME "lc3plus_egress"
+#include "lc3_sibling.h"
+static const sib_kernel k_table[] = {SIB_KERNEL(lc3_egress_classify_kernel), SIB_KERNEL(lc3_egress_sums_kernel), SIB_KERNEL(lc3_egress_base_kernel),
+                                     SIB_KERNEL(lc3_egress_scatter_kernel), SIB_KERNEL(lc3_egress_route_kernel), SIB_KERNEL(lc3_egress_copy_kernel)};
+extern "C" long long lc3egress_launch_count(const char* kernel) { return sib_launch_count(k_table, kernel); }
 
 extern "C" int lc3egress_run(const lc3egress_call* q)
 {
@@ -40,7 +28,7 @@ extern "C" int lc3egress_run(const lc3egress_call* q)
     if (!q->frames || !q->offsets || !q->num_bytes || !q->seq_base || !q->list.route || !q->list.seq || !q->list.frame || !q->list.offset || !q->list.size ||
         !q->n_packets || !q->work || ((uintptr_t)q->work & 7))
         return 1;
-    ECHK(hipSetDevice(q->device));
+    SIB_CHK(hipSetDevice(q->device));
     hipStream_t s = (hipStream_t)q->hip_stream;
     const long long n_cells = (long long)q->n_routes * q->n_frames, n_tiles = lc3e_tiles(n_cells);
     const int wire_mode = q->wire != nullptr;
@@ -49,35 +37,23 @@ extern "C" int lc3egress_run(const lc3egress_call* q)
     lc3e_list L = q->list;                                            /* status: the caller's array, or the workspace's where the route kernel needs one */
     if (!L.status && q->stats) L.status = (uint8_t*)q->work + lc3e_work_status(n_cells);
     L.from = wire_mode ? (long long*)((char*)q->work + lc3e_work_from(n_cells)) : nullptr;
-    hipLaunchKernelGGL(lc3_egress_classify_kernel, dim3((unsigned)((n_cells + LC3E_THREADS - 1) / LC3E_THREADS)), dim3(LC3E_THREADS), 0, s, n_cells, q->n_streams,
-                       q->n_routes, q->n_frames, q->order, q->route_src, q->counts, q->offsets, q->num_bytes, q->flags, q->max_frame_bytes, q->frames_capacity,
-                       q->skip_mask, word);
-    ECHK(hipGetLastError());
-    k_launches[K_CLASSIFY]++;
-    hipLaunchKernelGGL(lc3_egress_sums_kernel, dim3((unsigned)n_tiles), dim3(LC3E_THREADS), 0, s, (const int32_t*)word, n_cells, wire_mode, q->header_room, q->align, sums);
-    ECHK(hipGetLastError());
-    k_launches[K_SUMS]++;
-    hipLaunchKernelGGL(lc3_egress_base_kernel, dim3(1), dim3(LC3E_THREADS), 0, s, sums, n_tiles, q->n_packets, q->wire_total);
-    ECHK(hipGetLastError());
-    k_launches[K_BASE]++;
-    hipLaunchKernelGGL(lc3_egress_scatter_kernel, dim3((unsigned)n_tiles), dim3(LC3E_THREADS), 0, s, (const int32_t*)word, n_cells, (const long long*)sums, q->n_routes,
-                       q->n_frames, q->order, q->route_src, q->seq_base, q->seq_bits, q->offsets, wire_mode, q->header_room, q->align, q->wire_capacity, L);
-    ECHK(hipGetLastError());
-    k_launches[K_SCATTER]++;
+    SIB_LAUNCH(lc3_egress_classify_kernel, dim3((unsigned)((n_cells + LC3E_THREADS - 1) / LC3E_THREADS)), dim3(LC3E_THREADS), 0, s, n_cells, q->n_streams,
+               q->n_routes, q->n_frames, q->order, q->route_src, q->counts, q->offsets, q->num_bytes, q->flags, q->max_frame_bytes, q->frames_capacity,
+               q->skip_mask, word);
+    SIB_LAUNCH(lc3_egress_sums_kernel, dim3((unsigned)n_tiles), dim3(LC3E_THREADS), 0, s, (const int32_t*)word, n_cells, wire_mode, q->header_room, q->align, sums);
+    SIB_LAUNCH(lc3_egress_base_kernel, dim3(1), dim3(LC3E_THREADS), 0, s, sums, n_tiles, q->n_packets, q->wire_total);
+    SIB_LAUNCH(lc3_egress_scatter_kernel, dim3((unsigned)n_tiles), dim3(LC3E_THREADS), 0, s, (const int32_t*)word, n_cells, (const long long*)sums, q->n_routes,
+               q->n_frames, q->order, q->route_src, q->seq_base, q->seq_bits, q->offsets, wire_mode, q->header_room, q->align, q->wire_capacity, L);
     if (q->next_seq || q->stats) {
-        hipLaunchKernelGGL(lc3_egress_route_kernel, dim3((unsigned)((q->n_routes + LC3E_THREADS / WAVE - 1) / (LC3E_THREADS / WAVE))), dim3(LC3E_THREADS), 0, s,
-                           q->n_streams, q->n_routes, q->n_frames, q->route_src, q->counts, q->seq_base, q->seq_bits, (const uint8_t*)L.status, q->next_seq, q->stats);
-        ECHK(hipGetLastError());
-        k_launches[K_ROUTE]++;
+        SIB_LAUNCH(lc3_egress_route_kernel, dim3((unsigned)((q->n_routes + LC3E_THREADS / WAVE - 1) / (LC3E_THREADS / WAVE))), dim3(LC3E_THREADS), 0, s,
+                   q->n_streams, q->n_routes, q->n_frames, q->route_src, q->counts, q->seq_base, q->seq_bits, (const uint8_t*)L.status, q->next_seq, q->stats);
     }
     if (wire_mode) {
         const int per = LC3E_THREADS / LC3E_COPY_LANES;              /* sized for every cell SENT: the workgroups behind *n_packets leave at once */
-        hipLaunchKernelGGL(lc3_egress_copy_kernel, dim3((unsigned)((n_cells + per - 1) / per)), dim3(LC3E_THREADS), 0, s, (const uint8_t*)q->frames, q->frames_capacity,
-                           (const long long*)q->n_packets, (const long long*)L.from, (const long long*)L.offset, (const int32_t*)L.size, q->header_room,
-                           (uint8_t*)q->wire, q->wire_capacity);
-        ECHK(hipGetLastError());
-        k_launches[K_COPY]++;
+        SIB_LAUNCH(lc3_egress_copy_kernel, dim3((unsigned)((n_cells + per - 1) / per)), dim3(LC3E_THREADS), 0, s, (const uint8_t*)q->frames, q->frames_capacity,
+                   (const long long*)q->n_packets, (const long long*)L.from, (const long long*)L.offset, (const int32_t*)L.size, q->header_room,
+                   (uint8_t*)q->wire, q->wire_capacity);
     }
-    if (q->sync) ECHK(hipStreamSynchronize(s));
+    if (q->sync) SIB_CHK(hipStreamSynchronize(s));
     return 0;
 }

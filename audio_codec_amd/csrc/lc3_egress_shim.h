@@ -2,7 +2,7 @@
  * host C code (lc3_host.c) and the sibling library that holds the egress kernels (lc3_egress.hip -> liblc3plus_egress_hip.so) share.  The route rule, the cell
  * rule, the sequence numbers, the packet's advance in the wire buffer and the packet record are one text for the host function and the kernels; the
  * lc3egress_* functions are the sibling's whole C ABI.  lc3_host.c loads the sibling from its own directory on the first egress call; the code objects of the
- * codec library, the probe library and the ingest library hold none of this. */
+ * other libraries hold none of this. */
 #ifndef LC3_EGRESS_SHIM_H
 #define LC3_EGRESS_SHIM_H
 #include <stdint.h>

@@ -8,7 +8,7 @@
  * call fails with LC3_ERROR.
  */
 #ifndef _GNU_SOURCE
-#define _GNU_SOURCE                 /* dladdr: the frame probe's library is loaded from this library's directory */
+#define _GNU_SOURCE                 /* dladdr: the sibling libraries are loaded from this library's directory */
 #endif
 #include <dlfcn.h>
 #include <limits.h>
@@ -1834,24 +1834,68 @@ LC3_Error lc3plus_frame_info_side(int samplerate, int channels, float frame_ms, 
     }
     return LC3_OK;
 }
-/* the sibling library with the probe kernels, loaded once from the directory this library lies in; NULL where it is missing */
-typedef int (*probe_run_fn)(const lc3probe_call*);
-static pthread_once_t probe_once = PTHREAD_ONCE_INIT;
-static probe_run_fn probe_run;
-static void probe_load(void)
+/* ---- the sibling libraries (DESIGN.md "Sibling libraries"): the kernels of every call below lie in a library of their own beside this one ---- */
+enum { SIB_PROBE, SIB_INGEST, SIB_EGRESS, SIB_RTP, SIB_RTCP, SIB_SRTP, SIB_COUNT };
+/* a row: the file, its one or two entry points, and where they go.  fn holds either all of them or none */
+static struct { const char* file; const char* sym[2]; int tried; void* fn[2]; } siblings[SIB_COUNT] = {
+    [SIB_PROBE] = {"liblc3plus_probe_hip.so", {"lc3probe_run", NULL}, 0, {NULL, NULL}},
+    [SIB_INGEST] = {"liblc3plus_ingest_hip.so", {"lc3ingest_run", NULL}, 0, {NULL, NULL}},
+    [SIB_EGRESS] = {"liblc3plus_egress_hip.so", {"lc3egress_run", NULL}, 0, {NULL, NULL}},
+    [SIB_RTP] = {"liblc3plus_rtp_hip.so", {"lc3rtp_parse_run", "lc3rtp_stamp_run"}, 0, {NULL, NULL}},
+    [SIB_RTCP] = {"liblc3plus_rtcp_hip.so", {"lc3rtcp_stats_run", NULL}, 0, {NULL, NULL}},
+    [SIB_SRTP] = {"liblc3plus_srtp_hip.so", {"lc3srtp_protect_run", "lc3srtp_unprotect_run"}, 0, {NULL, NULL}},
+};
+static pthread_mutex_t sibling_mu = PTHREAD_MUTEX_INITIALIZER;
+/* The entry points of a sibling, or NULL where the library is missing or lacks one of them.  The file is looked for once per process, on the first call that needs
+ * it, in the directory this library lies in; the first failure says so on stderr, every later call fails silently. */
+static void* const* sibling_load(int which)
 {
-    Dl_info di;
-    char path[4096];
-    if (!dladdr((void*)&probe_load, &di) || !di.dli_fname) return;
-    const char* slash = strrchr(di.dli_fname, '/');
-    const size_t dir = slash ? (size_t)(slash - di.dli_fname) + 1 : 0;
-    static const char name[] = "liblc3plus_probe_hip.so";
-    if (dir + sizeof name > sizeof path) return;
-    memcpy(path, di.dli_fname, dir);
-    memcpy(path + dir, name, sizeof name);
-    void* h = dlopen(path, RTLD_NOW | RTLD_LOCAL);
-    if (!h) { fprintf(stderr, "lc3plus_hip: the frame probe's library is missing: %s\n", dlerror()); return; }
-    probe_run = (probe_run_fn)dlsym(h, "lc3probe_run");
+    pthread_mutex_lock(&sibling_mu);
+    if (!siblings[which].tried) {
+        siblings[which].tried = 1;
+        const char* const file = siblings[which].file;
+        Dl_info di;
+        char path[4096];
+        const char* why = "this library's own path is unknown or too long";
+        void* h = NULL;
+        if (dladdr((void*)&sibling_load, &di) && di.dli_fname) {
+            const char* slash = strrchr(di.dli_fname, '/');
+            const size_t dir = slash ? (size_t)(slash - di.dli_fname) + 1 : 0;
+            if (dir + strlen(file) < sizeof path) {
+                memcpy(path, di.dli_fname, dir);
+                strcpy(path + dir, file);
+                h = dlopen(path, RTLD_NOW | RTLD_LOCAL);
+                if (!h) why = dlerror();
+            }
+        }
+        void* fn[2] = {NULL, NULL};
+        int ok = h != NULL;
+        for (int k = 0; ok && k < 2 && siblings[which].sym[k]; k++) { fn[k] = dlsym(h, siblings[which].sym[k]); if (!fn[k]) { ok = 0; why = dlerror(); } }
+        if (ok) memcpy(siblings[which].fn, fn, sizeof fn);
+        else fprintf(stderr, "lc3plus_hip: the sibling library %s cannot be used: %s\n", file, why ? why : "an entry point is missing");
+    }
+    void* const* fn = siblings[which].fn[0] ? siblings[which].fn : NULL;
+    pthread_mutex_unlock(&sibling_mu);
+    return fn;
+}
+/* of a batch: its device and stream (dev; decoder: which kind of context it is; want_stream: an encoder's own stream is created where no call has needed it yet).
+ * No stream state, no configuration, no buffer */
+static int batch_device(void* dev, int decoder, int want_stream, int32_t* device, void** own)
+{
+    if (decoder) {
+        const lc3d_plan* plan = NULL; const lc3d_dchan* tab = NULL; int tab_n = 0;
+        return lc3hip_dec_probe_args(dev, device, &plan, &tab, &tab_n, own);
+    }
+    return lc3hip_stream_args(dev, want_stream, device, own);
+}
+/* How every call into a sibling begins, behind its argument checks: the batch's device, the stream the call runs on - the caller's, or the batch's own - and then
+ * the library's entry points; NULL where either is refused */
+static void* const* sibling_call(int which, void* dev, int decoder, void* hip_stream, int32_t* device, void** stream)
+{
+    void* own = NULL;
+    if (batch_device(dev, decoder, !hip_stream, device, &own)) return NULL;
+    *stream = hip_stream ? hip_stream : own;
+    return sibling_load(which);
 }
 LC3_Error lc3plus_dec_batch_probe(lc3plus_dec_batch* b, const void* frames, int64_t frames_capacity, const int64_t* offsets, const int32_t* num_bytes,
                                   int max_frame_bytes, int64_t n_items, int depth, int32_t* info, void* hip_stream, int sync)
@@ -1863,12 +1907,12 @@ LC3_Error lc3plus_dec_batch_probe(lc3plus_dec_batch* b, const void* frames, int6
     memset(&q, 0, sizeof q);
     void* own = NULL;
     if (lc3hip_dec_probe_args(b->dev, &q.device, &q.plan, &q.tab, &q.tab_n, &own)) return LC3_ERROR;
-    pthread_once(&probe_once, probe_load);
-    if (!probe_run) return LC3_ERROR;
+    void* const* fn = sibling_call(SIB_PROBE, b->dev, 1, hip_stream, &q.device, &q.stream);
+    if (!fn) return LC3_ERROR;
     q.channels = b->g.channels; q.ylen = b->g.ylen;
     q.frames = frames; q.capacity = (long long)frames_capacity; q.offsets = (const long long*)offsets; q.num_bytes = num_bytes; q.max_bytes = max_frame_bytes;
-    q.depth = depth; q.n_items = (long long)n_items; q.info = info; q.stream = hip_stream ? hip_stream : own; q.sync = sync;
-    return probe_run(&q) ? LC3_ERROR : LC3_OK;
+    q.depth = depth; q.n_items = (long long)n_items; q.info = info; q.sync = sync;
+    return ((int (*)(const lc3probe_call*))fn[0])(&q) ? LC3_ERROR : LC3_OK;
 }
 /* ---- packet ingest (include/lc3plus_batch.h "Packet ingest"; lc3_ingest_shim.h) ---- */
 /* the checks both calls make first, in the header's order */
@@ -1920,25 +1964,6 @@ LC3_Error lc3plus_plan_ingest(int n_streams, int channels, int64_t n_items, cons
         }
     return LC3_OK;
 }
-/* the sibling library with the ingest kernels, loaded as the probe's is; NULL where it is missing */
-typedef int (*ingest_run_fn)(const lc3ingest_call*);
-static pthread_once_t ingest_once = PTHREAD_ONCE_INIT;
-static ingest_run_fn ingest_run;
-static void ingest_load(void)
-{
-    Dl_info di;
-    char path[4096];
-    if (!dladdr((void*)&ingest_load, &di) || !di.dli_fname) return;
-    const char* slash = strrchr(di.dli_fname, '/');
-    const size_t dir = slash ? (size_t)(slash - di.dli_fname) + 1 : 0;
-    static const char name[] = "liblc3plus_ingest_hip.so";
-    if (dir + sizeof name > sizeof path) return;
-    memcpy(path, di.dli_fname, dir);
-    memcpy(path + dir, name, sizeof name);
-    void* h = dlopen(path, RTLD_NOW | RTLD_LOCAL);
-    if (!h) { fprintf(stderr, "lc3plus_hip: the packet ingest's library is missing: %s\n", dlerror()); return; }
-    ingest_run = (ingest_run_fn)dlsym(h, "lc3ingest_run");
-}
 LC3_Error lc3plus_dec_batch_ingest(lc3plus_dec_batch* b, int64_t n_items, const int32_t* stream, const int32_t* seq, const int64_t* offsets,
                                    const int32_t* num_bytes, const int32_t* info, const int32_t* base, const int32_t* floor, int seq_bits, int n_frames,
                                    int64_t* out_offsets, int32_t* out_num_bytes, int32_t* cell_item, int32_t* counts, int32_t* next_base, int32_t* stats,
@@ -1950,16 +1975,13 @@ LC3_Error lc3plus_dec_batch_ingest(lc3plus_dec_batch* b, int64_t n_items, const 
     /* of the batch: its device and stream, n_streams and channels.  No stream state, no configuration, no buffer */
     lc3ingest_call q;
     memset(&q, 0, sizeof q);
-    const lc3d_plan* plan = NULL; const lc3d_dchan* tab = NULL; int tab_n = 0;
-    void* own = NULL;
-    if (lc3hip_dec_probe_args(b->dev, &q.device, &plan, &tab, &tab_n, &own)) return LC3_ERROR;
-    pthread_once(&ingest_once, ingest_load);
-    if (!ingest_run) return LC3_ERROR;
+    void* const* fn = sibling_call(SIB_INGEST, b->dev, 1, hip_stream, &q.device, &q.hip_stream);
+    if (!fn) return LC3_ERROR;
     q.n_streams = b->n_streams; q.channels = b->g.channels; q.seq_bits = seq_bits; q.n_frames = n_frames; q.sync = sync; q.n_items = (long long)n_items;
     q.stream = stream; q.seq = seq; q.offsets = (const long long*)offsets; q.num_bytes = num_bytes; q.info = info; q.base = base; q.floor = floor;
     q.out_offsets = (long long*)out_offsets; q.out_num_bytes = out_num_bytes; q.cell_item = cell_item; q.counts = counts; q.next_base = next_base; q.stats = stats;
-    q.item_status = item_status; q.hip_stream = hip_stream ? hip_stream : own;
-    return ingest_run(&q) ? LC3_ERROR : LC3_OK;
+    q.item_status = item_status;
+    return ((int (*)(const lc3ingest_call*))fn[0])(&q) ? LC3_ERROR : LC3_OK;
 }
 /* ---- packet egress (include/lc3plus_batch.h "Packet egress"; lc3_egress_shim.h) ---- */
 /* what every egress call takes behind its batch, in the header's order */
@@ -2076,25 +2098,6 @@ LC3_Error lc3plus_plan_egress(int n_streams,
         }
     return LC3_OK;
 }
-/* the sibling library with the egress kernels, loaded as the ingest's is; NULL where it is missing */
-typedef int (*egress_run_fn)(const lc3egress_call*);
-static pthread_once_t egress_once = PTHREAD_ONCE_INIT;
-static egress_run_fn egress_run;
-static void egress_load(void)
-{
-    Dl_info di;
-    char path[4096];
-    if (!dladdr((void*)&egress_load, &di) || !di.dli_fname) return;
-    const char* slash = strrchr(di.dli_fname, '/');
-    const size_t dir = slash ? (size_t)(slash - di.dli_fname) + 1 : 0;
-    static const char name[] = "liblc3plus_egress_hip.so";
-    if (dir + sizeof name > sizeof path) return;
-    memcpy(path, di.dli_fname, dir);
-    memcpy(path + dir, name, sizeof name);
-    void* h = dlopen(path, RTLD_NOW | RTLD_LOCAL);
-    if (!h) { fprintf(stderr, "lc3plus_hip: the packet egress's library is missing: %s\n", dlerror()); return; }
-    egress_run = (egress_run_fn)dlsym(h, "lc3egress_run");
-}
 /* both entry points end here.  Of the batch: its device and stream (dev; decoder: which kind of context it is) and n_streams.  No stream state, no configuration,
  * no buffer */
 static LC3_Error egress_queue(void* dev, int decoder, int n_streams, const egress_args* a, void* hip_stream, int sync)
@@ -2102,13 +2105,8 @@ static LC3_Error egress_queue(void* dev, int decoder, int n_streams, const egres
     if (!a->route_src && a->n_routes != n_streams) return LC3_ERROR;
     lc3egress_call q;
     memset(&q, 0, sizeof q);
-    void* own = NULL;
-    if (decoder) {
-        const lc3d_plan* plan = NULL; const lc3d_dchan* tab = NULL; int tab_n = 0;
-        if (lc3hip_dec_probe_args(dev, &q.device, &plan, &tab, &tab_n, &own)) return LC3_ERROR;
-    } else if (lc3hip_stream_args(dev, !hip_stream, &q.device, &own)) return LC3_ERROR;
-    pthread_once(&egress_once, egress_load);
-    if (!egress_run) return LC3_ERROR;
+    void* const* fn = sibling_call(SIB_EGRESS, dev, decoder, hip_stream, &q.device, &q.hip_stream);
+    if (!fn) return LC3_ERROR;
     q.n_streams = n_streams; q.n_frames = a->n_frames; q.max_frame_bytes = a->max_frame_bytes; q.skip_mask = a->skip_mask; q.n_routes = a->n_routes;
     q.seq_bits = a->seq_bits; q.order = a->order; q.header_room = a->header_room; q.align = a->align; q.sync = sync;
     q.frames_capacity = (long long)a->frames_capacity; q.wire_capacity = (long long)a->wire_capacity;
@@ -2117,8 +2115,7 @@ static LC3_Error egress_queue(void* dev, int decoder, int n_streams, const egres
     q.list.route = a->pkt_route; q.list.seq = a->pkt_seq; q.list.frame = a->pkt_frame; q.list.offset = (long long*)a->pkt_offset; q.list.size = a->pkt_size;
     q.list.flags = a->pkt_flags; q.list.status = a->cell_status;
     q.n_packets = (long long*)a->n_packets; q.wire_total = (long long*)a->wire_total; q.next_seq = a->next_seq; q.stats = a->stats; q.work = a->work;
-    q.hip_stream = hip_stream ? hip_stream : own;
-    return egress_run(&q) ? LC3_ERROR : LC3_OK;
+    return ((int (*)(const lc3egress_call*))fn[0])(&q) ? LC3_ERROR : LC3_OK;
 }
 LC3_Error lc3plus_enc_batch_egress(lc3plus_batch* b,
     int n_frames, const void* frames, int64_t frames_capacity, const int64_t* offsets, const int32_t* num_bytes, int max_frame_bytes,
@@ -2257,38 +2254,6 @@ LC3_Error lc3plus_plan_rtp_stamp(int64_t max_packets, const int64_t* n_packets,
         for (int r = 0; r < n_routes; r++) lc3r_route_out(&q, r, next_ts, next_resume);
     return LC3_OK;
 }
-/* the sibling library with the RTP kernels, loaded as the egress's is; NULL where it is missing */
-typedef int (*rtp_parse_fn)(const lc3rtp_parse_call*);
-typedef int (*rtp_stamp_fn)(const lc3rtp_stamp_call*);
-static pthread_once_t rtp_once = PTHREAD_ONCE_INIT;
-static rtp_parse_fn rtp_parse_run;
-static rtp_stamp_fn rtp_stamp_run;
-static void rtp_load(void)
-{
-    Dl_info di;
-    char path[4096];
-    if (!dladdr((void*)&rtp_load, &di) || !di.dli_fname) return;
-    const char* slash = strrchr(di.dli_fname, '/');
-    const size_t dir = slash ? (size_t)(slash - di.dli_fname) + 1 : 0;
-    static const char name[] = "liblc3plus_rtp_hip.so";
-    if (dir + sizeof name > sizeof path) return;
-    memcpy(path, di.dli_fname, dir);
-    memcpy(path + dir, name, sizeof name);
-    void* h = dlopen(path, RTLD_NOW | RTLD_LOCAL);
-    if (!h) { fprintf(stderr, "lc3plus_hip: the RTP framing's library is missing: %s\n", dlerror()); return; }
-    rtp_parse_fn parse = (rtp_parse_fn)dlsym(h, "lc3rtp_parse_run");
-    rtp_stamp_fn stamp = (rtp_stamp_fn)dlsym(h, "lc3rtp_stamp_run");
-    if (parse && stamp) { rtp_parse_run = parse; rtp_stamp_run = stamp; }
-}
-/* of a batch: its device and stream (dev; decoder: which kind of context it is).  No stream state, no configuration, no buffer */
-static int rtp_device(void* dev, int decoder, int want_stream, int32_t* device, void** own)
-{
-    if (decoder) {
-        const lc3d_plan* plan = NULL; const lc3d_dchan* tab = NULL; int tab_n = 0;
-        return lc3hip_dec_probe_args(dev, device, &plan, &tab, &tab_n, own);
-    }
-    return lc3hip_stream_args(dev, want_stream, device, own);
-}
 LC3_Error lc3plus_dec_batch_rtp_parse(lc3plus_dec_batch* b, int64_t n_items,
     const void* ring, int64_t ring_capacity, const int64_t* dg_offsets, const int32_t* dg_sizes,
     int n_ssrc, const int32_t* ssrc_key, const int32_t* ssrc_stream, const int32_t* payload_type, int payload_room,
@@ -2302,28 +2267,24 @@ LC3_Error lc3plus_dec_batch_rtp_parse(lc3plus_dec_batch* b, int64_t n_items,
     if (e) return e;
     lc3rtp_parse_call q;
     memset(&q, 0, sizeof q);
-    void* own = NULL;
-    if (rtp_device(b->dev, 1, 0, &q.device, &own)) return LC3_ERROR;
-    pthread_once(&rtp_once, rtp_load);
-    if (!rtp_parse_run) return LC3_ERROR;
+    void* const* fn = sibling_call(SIB_RTP, b->dev, 1, hip_stream, &q.device, &q.hip_stream);
+    if (!fn) return LC3_ERROR;
     q.n_streams = b->n_streams; q.n_ssrc = n_ssrc; q.payload_room = payload_room; q.sync = sync; q.n_items = (long long)n_items; q.ring_capacity = (long long)ring_capacity;
     q.ring = ring; q.dg_offsets = (const long long*)dg_offsets; q.dg_sizes = dg_sizes; q.ssrc_key = ssrc_key; q.ssrc_stream = ssrc_stream; q.payload_type = payload_type;
     q.out.stream = stream; q.out.seq = seq; q.out.offsets = (long long*)offsets; q.out.num_bytes = num_bytes; q.out.timestamp = timestamp; q.out.marker = marker;
-    q.out.status = status; q.stats = stats; q.hip_stream = hip_stream ? hip_stream : own;
-    return rtp_parse_run(&q) ? LC3_ERROR : LC3_OK;
+    q.out.status = status; q.stats = stats;
+    return ((int (*)(const lc3rtp_parse_call*))fn[0])(&q) ? LC3_ERROR : LC3_OK;
 }
 /* both stamp entry points end here */
 static LC3_Error rtp_stamp_queue(void* dev, int decoder, const rtp_stamp_args* a, void* hip_stream, int sync)
 {
     lc3rtp_stamp_call q;
     memset(&q, 0, sizeof q);
-    void* own = NULL;
-    if (rtp_device(dev, decoder, !hip_stream, &q.device, &own)) return LC3_ERROR;
-    pthread_once(&rtp_once, rtp_load);
-    if (!rtp_stamp_run) return LC3_ERROR;
+    void* const* fn = sibling_call(SIB_RTP, dev, decoder, hip_stream, &q.device, &q.hip_stream);
+    if (!fn) return LC3_ERROR;
     q.sync = sync; q.max_packets = (long long)a->max_packets; q.n_packets = (const long long*)a->n_packets; q.in = rtp_stamp_in(a);
-    q.wire = a->wire; q.pkt_status = a->pkt_status; q.next_ts = a->next_ts; q.next_resume = a->next_resume; q.hip_stream = hip_stream ? hip_stream : own;
-    return rtp_stamp_run(&q) ? LC3_ERROR : LC3_OK;
+    q.wire = a->wire; q.pkt_status = a->pkt_status; q.next_ts = a->next_ts; q.next_resume = a->next_resume;
+    return ((int (*)(const lc3rtp_stamp_call*))fn[1])(&q) ? LC3_ERROR : LC3_OK;
 }
 LC3_Error lc3plus_enc_batch_rtp_stamp(lc3plus_batch* b, int64_t max_packets, const int64_t* n_packets,
     const int32_t* pkt_route, const int32_t* pkt_seq, const int32_t* pkt_frame, const int64_t* pkt_offset, const int32_t* pkt_size, const uint8_t* pkt_flags,
@@ -2415,25 +2376,6 @@ LC3_Error lc3plus_plan_rtcp_stats(int64_t n_items,
         }
     return LC3_OK;
 }
-/* the sibling library with the reception reports' kernels, loaded as the RTP framing's is; NULL where it is missing */
-typedef int (*rtcp_stats_fn)(const lc3rtcp_stats_call*);
-static pthread_once_t rtcp_once = PTHREAD_ONCE_INIT;
-static rtcp_stats_fn rtcp_stats_run;
-static void rtcp_load(void)
-{
-    Dl_info di;
-    char path[4096];
-    if (!dladdr((void*)&rtcp_load, &di) || !di.dli_fname) return;
-    const char* slash = strrchr(di.dli_fname, '/');
-    const size_t dir = slash ? (size_t)(slash - di.dli_fname) + 1 : 0;
-    static const char name[] = "liblc3plus_rtcp_hip.so";
-    if (dir + sizeof name > sizeof path) return;
-    memcpy(path, di.dli_fname, dir);
-    memcpy(path + dir, name, sizeof name);
-    void* h = dlopen(path, RTLD_NOW | RTLD_LOCAL);
-    if (!h) { fprintf(stderr, "lc3plus_hip: the reception reports' library is missing: %s\n", dlerror()); return; }
-    rtcp_stats_run = (rtcp_stats_fn)dlsym(h, "lc3rtcp_stats_run");
-}
 LC3_Error lc3plus_dec_batch_rtcp_stats(lc3plus_dec_batch* b, int64_t n_items,
     const int32_t* stream, const int32_t* seq, const int32_t* timestamp, const int32_t* arrival,
     int n_streams, const int32_t* state_in, int32_t* state_out,
@@ -2450,15 +2392,13 @@ LC3_Error lc3plus_dec_batch_rtcp_stats(lc3plus_dec_batch* b, int64_t n_items,
     if (workspace_bytes < lc3plus_rtcp_workspace_bytes(n_items, n_streams)) return LC3_ERROR;
     lc3rtcp_stats_call q;
     memset(&q, 0, sizeof q);
-    void* own = NULL;
-    if (rtp_device(b->dev, 1, 0, &q.device, &own)) return LC3_ERROR;
-    pthread_once(&rtcp_once, rtcp_load);
-    if (!rtcp_stats_run) return LC3_ERROR;
+    void* const* fn = sibling_call(SIB_RTCP, b->dev, 1, hip_stream, &q.device, &q.hip_stream);
+    if (!fn) return LC3_ERROR;
     q.n_streams = n_streams; q.make_report = make_report; q.sync = sync; q.n_items = (long long)n_items;
     q.stream = stream; q.seq = seq; q.timestamp = timestamp; q.arrival = arrival; q.state_in = state_in; q.state_out = state_out;
     q.ssrc = ssrc; q.lsr = lsr; q.dlsr = dlsr; q.blocks = blocks; q.ext_seq = ext_seq; q.item_status = item_status; q.stream_stats = stream_stats;
-    q.workspace = workspace; q.workspace_bytes = (long long)workspace_bytes; q.hip_stream = hip_stream ? hip_stream : own;
-    return rtcp_stats_run(&q) ? LC3_ERROR : LC3_OK;
+    q.workspace = workspace; q.workspace_bytes = (long long)workspace_bytes;
+    return ((int (*)(const lc3rtcp_stats_call*))fn[0])(&q) ? LC3_ERROR : LC3_OK;
 }
 /* ---- Secure RTP (include/lc3plus_batch.h "Secure RTP"; lc3_srtp_shim.h) ---- */
 LC3_Error lc3plus_srtp_make_context(const uint8_t* master_key, const uint8_t* master_salt, int32_t* ctx)
@@ -2591,42 +2531,16 @@ LC3_Error lc3plus_plan_srtp_unprotect(int64_t n_items,
     free(top1); free(bits); free(first); free(accepted); free(items);
     return LC3_OK;
 }
-/* the sibling library with the SRTP kernels, loaded as the RTP framing's is; NULL where it is missing */
-typedef int (*srtp_protect_fn)(const lc3srtp_protect_call*);
-typedef int (*srtp_unprotect_fn)(const lc3srtp_unprotect_call*);
-static pthread_once_t srtp_once = PTHREAD_ONCE_INIT;
-static srtp_protect_fn srtp_protect_run;
-static srtp_unprotect_fn srtp_unprotect_run;
-static void srtp_load(void)
-{
-    Dl_info di;
-    char path[4096];
-    if (!dladdr((void*)&srtp_load, &di) || !di.dli_fname) return;
-    const char* slash = strrchr(di.dli_fname, '/');
-    const size_t dir = slash ? (size_t)(slash - di.dli_fname) + 1 : 0;
-    static const char name[] = "liblc3plus_srtp_hip.so";
-    if (dir + sizeof name > sizeof path) return;
-    memcpy(path, di.dli_fname, dir);
-    memcpy(path + dir, name, sizeof name);
-    void* h = dlopen(path, RTLD_NOW | RTLD_LOCAL);
-    if (!h) { fprintf(stderr, "lc3plus_hip: the Secure RTP library is missing: %s\n", dlerror()); return; }
-    srtp_protect_fn protect = (srtp_protect_fn)dlsym(h, "lc3srtp_protect_run");
-    srtp_unprotect_fn unprotect = (srtp_unprotect_fn)dlsym(h, "lc3srtp_unprotect_run");
-    if (protect && unprotect) { srtp_protect_run = protect; srtp_unprotect_run = unprotect; }
-}
 /* both protect entry points end here */
 static LC3_Error srtp_protect_queue(void* dev, int decoder, const srtp_protect_args* a, void* hip_stream, int sync)
 {
     lc3srtp_protect_call q;
     memset(&q, 0, sizeof q);
-    void* own = NULL;
-    if (rtp_device(dev, decoder, !hip_stream, &q.device, &own)) return LC3_ERROR;
-    pthread_once(&srtp_once, srtp_load);
-    if (!srtp_protect_run) return LC3_ERROR;
+    void* const* fn = sibling_call(SIB_SRTP, dev, decoder, hip_stream, &q.device, &q.hip_stream);
+    if (!fn) return LC3_ERROR;
     q.sync = sync; q.max_packets = (long long)a->max_packets; q.n_packets = (const long long*)a->n_packets; q.in = srtp_protect_in(a);
     q.out_offset = (long long*)a->out_offset; q.out_size = a->out_size; q.out_status = a->out_status; q.next_roc = a->next_roc;
-    q.hip_stream = hip_stream ? hip_stream : own;
-    return srtp_protect_run(&q) ? LC3_ERROR : LC3_OK;
+    return ((int (*)(const lc3srtp_protect_call*))fn[0])(&q) ? LC3_ERROR : LC3_OK;
 }
 LC3_Error lc3plus_enc_batch_srtp_protect(lc3plus_batch* b, int64_t max_packets, const int64_t* n_packets,
     const int32_t* pkt_route, const int64_t* pkt_offset, const int32_t* pkt_size, const uint8_t* pkt_status,
@@ -2670,15 +2584,13 @@ LC3_Error lc3plus_dec_batch_srtp_unprotect(lc3plus_dec_batch* b, int64_t n_items
     if (workspace_bytes < lc3plus_srtp_workspace_bytes(n_items, n_ssrc)) return LC3_ERROR;
     lc3srtp_unprotect_call q;
     memset(&q, 0, sizeof q);
-    void* own = NULL;
-    if (rtp_device(b->dev, 1, 0, &q.device, &own)) return LC3_ERROR;
-    pthread_once(&srtp_once, srtp_load);
-    if (!srtp_unprotect_run) return LC3_ERROR;
+    void* const* fn = sibling_call(SIB_SRTP, b->dev, 1, hip_stream, &q.device, &q.hip_stream);
+    if (!fn) return LC3_ERROR;
     q.sync = sync; q.n_ssrc = n_ssrc; q.tag_len = tag_len; q.n_items = (long long)n_items; q.ring_capacity = (long long)ring_capacity;
     q.ring = ring; q.dg_offsets = (const long long*)dg_offsets; q.dg_sizes = dg_sizes; q.ssrc_key = ssrc_key; q.ctx = ctx; q.state_in = state_in; q.state_out = state_out;
     q.sizes_out = sizes_out; q.status = status; q.index = (long long*)index; q.stats = stats;
-    q.workspace = workspace; q.workspace_bytes = (long long)workspace_bytes; q.hip_stream = hip_stream ? hip_stream : own;
-    return srtp_unprotect_run(&q) ? LC3_ERROR : LC3_OK;
+    q.workspace = workspace; q.workspace_bytes = (long long)workspace_bytes;
+    return ((int (*)(const lc3srtp_unprotect_call*))fn[1])(&q) ? LC3_ERROR : LC3_OK;
 }
 LC3_Error lc3plus_dec_batch_set_input_ready(lc3plus_dec_batch* b, int ready)
 {

@@ -1,12 +1,9 @@
 /* lc3_probe.hip -- the frame probe's library (liblc3plus_probe_hip.so): the gfx950 kernels of lc3_probe.inc and the host code that launches them, behind the
- * C ABI of lc3_probe_shim.h.  A library of its own beside liblc3plus_hip.so, so that the codec library's code object stays what it is; lc3_host.c loads it on
- * the first lc3plus_dec_batch_probe call and hands it the batch's device, plan and per-size channel table.  It keeps no state but its launch counts. */
+ * C ABI of lc3_probe_shim.h.  A sibling library (DESIGN.md "Sibling libraries"): lc3_host.c loads it on the first lc3plus_dec_batch_probe call and hands it the
+ * batch's device, plan and per-size channel table.  It keeps no state but its launch counts. */
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <stdio.h>
-#include <string.h>
 #include <stddef.h>
-#include <atomic>
 
 #define LC3T_QUAL static __device__ const
 #include "lc3_tables.h"
@@ -33,32 +30,22 @@ __device__ __forceinline__ int flog2f_int(unsigned v)
 #include "lc3_probe.inc"
 
 /* ---- host ---- */
-enum { K_SIDE = 0, K_FULL, K_FULL_G, K_COUNT };
-static const char* const k_names[K_COUNT] = {"lc3_probe_side_kernel", "lc3_probe_full_kernel", "lc3_probe_full_kernel_g"};
-static std::atomic<long long> k_launches[K_COUNT];
-
-extern "C" long long lc3probe_launch_count(const char* kernel)
-{
-    if (!kernel) return -1;
-    for (int i = 0; i < K_COUNT; i++) if (!strcmp(kernel, k_names[i])) return k_launches[i].load(std::memory_order_relaxed);
-    return -1;
-}
-
-#define PCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { fprintf(stderr, "lc3plus_probe: %s: %s\n", #x, hipGetErrorString(e_)); return 1; } } while (0)
+#define SIB_NAME "lc3plus_probe"
+#include "lc3_sibling.h"
+static const sib_kernel k_table[] = {SIB_KERNEL(lc3_probe_side_kernel), SIB_KERNEL(lc3_probe_full_kernel), SIB_KERNEL(lc3_probe_full_kernel_g)};
+extern "C" long long lc3probe_launch_count(const char* kernel) { return sib_launch_count(k_table, kernel); }
 
 extern "C" int lc3probe_run(const lc3probe_call* q)
 {
     if (!q || !q->plan || !q->tab || q->n_items <= 0 || q->channels < 1 || q->tab_n < 2) return 1;
-    PCHK(hipSetDevice(q->device));
+    SIB_CHK(hipSetDevice(q->device));
     hipStream_t s = (hipStream_t)q->stream;
     const uint8_t* in = (const uint8_t*)q->frames;
-    int which;
     if (q->depth == LC3P_DEPTH_SIDE) {
         const long long blocks = (q->n_items + 255) / 256;
         if (blocks > 0x7fffffffLL) return 1;
-        hipLaunchKernelGGL(lc3_probe_side_kernel, dim3((unsigned)blocks), dim3(256), 0, s, q->plan, q->tab, q->tab_n, in, q->capacity, q->offsets, q->num_bytes,
-                           q->max_bytes, q->n_items, q->info);
-        which = K_SIDE;
+        SIB_LAUNCH(lc3_probe_side_kernel, dim3((unsigned)blocks), dim3(256), 0, s, q->plan, q->tab, q->tab_n, in, q->capacity, q->offsets, q->num_bytes,
+                   q->max_bytes, q->n_items, q->info);
     } else {
         /* the host does not see the sizes: a channel holds at most its share of max_bytes, and at most the geometry's largest channel frame (as the parser of
          * decode_packed bounds them).  Up to 128 bytes the channel is staged in LDS; above that four waves' worth would not fit beside the tables */
@@ -72,13 +59,12 @@ extern "C" int lc3probe_run(const lc3probe_call* q)
         if (wpg < 1) return 1;
         const long long per_wg = (long long)wpg * WAVE, blocks = (q->n_items + per_wg - 1) / per_wg;
         if (blocks > 0x7fffffffLL) return 1;
-        auto k = nw_max ? lc3_probe_full_kernel : lc3_probe_full_kernel_g;
-        hipLaunchKernelGGL(k, dim3((unsigned)blocks), dim3(wpg * WAVE), per_wave * wpg, s, q->plan, q->tab, q->tab_n, in, q->capacity, q->offsets, q->num_bytes,
-                           q->max_bytes, q->n_items, nw_max, nzw, q->info);
-        which = nw_max ? K_FULL : K_FULL_G;
+#define FULL_ARGS dim3((unsigned)blocks), dim3(wpg * WAVE), per_wave * wpg, s, q->plan, q->tab, q->tab_n, in, q->capacity, q->offsets, q->num_bytes, q->max_bytes, q->n_items, \
+                  nw_max, nzw, q->info
+        if (nw_max) SIB_LAUNCH(lc3_probe_full_kernel, FULL_ARGS);
+        else SIB_LAUNCH(lc3_probe_full_kernel_g, FULL_ARGS);
+#undef FULL_ARGS
     }
-    PCHK(hipGetLastError());
-    k_launches[which]++;
-    if (q->sync) PCHK(hipStreamSynchronize(s));
+    if (q->sync) SIB_CHK(hipStreamSynchronize(s));
     return 0;
 }

@@ -1,13 +1,9 @@
 /* lc3_rtcp.hip -- the reception reports' library (liblc3plus_rtcp_hip.so): the gfx950 kernels of lc3_rtcp.inc and the host code that launches them, behind the
- * C ABI of lc3_rtcp_shim.h.  A sixth library beside liblc3plus_hip.so, liblc3plus_probe_hip.so, liblc3plus_ingest_hip.so, liblc3plus_egress_hip.so and
- * liblc3plus_rtp_hip.so, so that the code objects of those five stay what they are; lc3_host.c loads it on the first call and hands it the batch's device.  It
- * keeps no state but its launch counts and allocates nothing: all scratch lies in the caller's workspace. */
+ * C ABI of lc3_rtcp_shim.h.  A sibling library (DESIGN.md "Sibling libraries"): lc3_host.c loads it on the first call and hands it the batch's device.  It keeps no
+ * state but its launch counts and allocates nothing: all scratch lies in the caller's workspace. */
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <stdio.h>
-#include <string.h>
 #include <stddef.h>
-#include <atomic>
 
 #include "lc3_rtcp_shim.h"
 
@@ -15,26 +11,11 @@
 #include "lc3_rtcp.inc"
 
 /* ---- host ---- */
-enum { K_FILL = 0, K_COUNT_ITEMS, K_SCAN, K_SCATTER, K_PLACE, K_WALK, K_COUNT };
-static const char* const k_names[K_COUNT] = {"lc3_rtcp_fill_kernel", "lc3_rtcp_count_kernel", "lc3_rtcp_scan_kernel", "lc3_rtcp_scatter_kernel", "lc3_rtcp_place_kernel",
-                                             "lc3_rtcp_walk_kernel"};
-static std::atomic<long long> k_launches[K_COUNT];
-
-extern "C" long long lc3rtcp_launch_count(const char* kernel)
-{
-    if (!kernel) return -1;
-    for (int i = 0; i < K_COUNT; i++) if (!strcmp(kernel, k_names[i])) return k_launches[i].load(std::memory_order_relaxed);
-    return -1;
-}
-
-#define QCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { fprintf(stderr, "lc3plus_rtcp: %s: %s\n", #x, hipGetErrorString(e_)); return 1; } } while (0)
-
-/* workgroups of LC3Q_THREADS for n lanes of work, at most `most`: the kernels walk the rest grid-stride */
-static unsigned blocks_for(long long n, long long most)
-{
-    const long long b = (n + LC3Q_THREADS - 1) / LC3Q_THREADS;
-    return (unsigned)(b < 1 ? 1 : b > most ? most : b);
-}
+#define SIB_NAME "lc3plus_rtcp"
+#include "lc3_sibling.h"
+static const sib_kernel k_table[] = {SIB_KERNEL(lc3_rtcp_fill_kernel), SIB_KERNEL(lc3_rtcp_count_kernel), SIB_KERNEL(lc3_rtcp_scan_kernel),
+                                     SIB_KERNEL(lc3_rtcp_scatter_kernel), SIB_KERNEL(lc3_rtcp_place_kernel), SIB_KERNEL(lc3_rtcp_walk_kernel)};
+extern "C" long long lc3rtcp_launch_count(const char* kernel) { return sib_launch_count(k_table, kernel); }
 
 extern "C" int lc3rtcp_stats_run(const lc3rtcp_stats_call* q)
 {
@@ -42,7 +23,7 @@ extern "C" int lc3rtcp_stats_run(const lc3rtcp_stats_call* q)
     if (!q->stream || !q->seq || !q->timestamp || !q->arrival || !q->state_in || !q->state_out || !q->workspace) return 1;
     if (q->make_report && (!q->ssrc || !q->blocks)) return 1;
     if (q->workspace_bytes < lc3q_workspace_bytes(q->n_items, q->n_streams)) return 1;
-    QCHK(hipSetDevice(q->device));
+    SIB_CHK(hipSetDevice(q->device));
     hipStream_t s = (hipStream_t)q->hip_stream;
     /* the workspace's words (lc3_rtcp_shim.h) */
     const int most_big = (int)lc3q_most_big(q->n_items, q->n_streams);
@@ -51,28 +32,16 @@ extern "C" int lc3rtcp_stats_run(const lc3rtcp_stats_call* q)
     int32_t* nbig = cur + q->n_streams;
     int32_t* big = nbig + 1;
     int32_t* idx = big + most_big;
-    hipLaunchKernelGGL(lc3_rtcp_fill_kernel, dim3(blocks_for((long long)q->n_streams + 1, 1024)), dim3(LC3Q_THREADS), 0, s, cur, (long long)q->n_streams + 1);
-    QCHK(hipGetLastError());
-    k_launches[K_FILL]++;
-    hipLaunchKernelGGL(lc3_rtcp_count_kernel, dim3(blocks_for(q->n_items, 1 << 16)), dim3(LC3Q_THREADS), 0, s, q->stream, q->n_items, q->n_streams, cur);
-    QCHK(hipGetLastError());
-    k_launches[K_COUNT_ITEMS]++;
-    hipLaunchKernelGGL(lc3_rtcp_scan_kernel, dim3(1), dim3(LC3Q_SCAN_THREADS), 0, s, off, cur, nbig, big, q->n_streams, most_big);
-    QCHK(hipGetLastError());
-    k_launches[K_SCAN]++;
-    hipLaunchKernelGGL(lc3_rtcp_scatter_kernel, dim3(blocks_for(q->n_items, 1 << 16)), dim3(LC3Q_THREADS), 0, s, q->stream, q->n_items, q->n_streams, off, cur, idx,
-                       q->ext_seq, q->item_status);
-    QCHK(hipGetLastError());
-    k_launches[K_SCATTER]++;
+    SIB_LAUNCH(lc3_rtcp_fill_kernel, dim3(sib_blocks_for((long long)q->n_streams + 1, LC3Q_THREADS, 1024)), dim3(LC3Q_THREADS), 0, s, cur, (long long)q->n_streams + 1);
+    SIB_LAUNCH(lc3_rtcp_count_kernel, dim3(sib_blocks_for(q->n_items, LC3Q_THREADS, 1 << 16)), dim3(LC3Q_THREADS), 0, s, q->stream, q->n_items, q->n_streams, cur);
+    SIB_LAUNCH(lc3_rtcp_scan_kernel, dim3(1), dim3(LC3Q_SCAN_THREADS), 0, s, off, cur, nbig, big, q->n_streams, most_big);
+    SIB_LAUNCH(lc3_rtcp_scatter_kernel, dim3(sib_blocks_for(q->n_items, LC3Q_THREADS, 1 << 16)), dim3(LC3Q_THREADS), 0, s, q->stream, q->n_items, q->n_streams, off, cur, idx,
+               q->ext_seq, q->item_status);
     if (most_big > 0) {                                              /* no stream can be long in a list of at most LC3Q_LDS_ITEMS items */
-        hipLaunchKernelGGL(lc3_rtcp_place_kernel, dim3((unsigned)(most_big < 256 ? most_big : 256)), dim3(LC3Q_PLACE_THREADS), 0, s, q->stream, q->n_items, off, nbig, big,
-                           most_big, idx);
-        QCHK(hipGetLastError());
-        k_launches[K_PLACE]++;
+        SIB_LAUNCH(lc3_rtcp_place_kernel, dim3((unsigned)(most_big < 256 ? most_big : 256)), dim3(LC3Q_PLACE_THREADS), 0, s, q->stream, q->n_items, off, nbig, big,
+                   most_big, idx);
     }
-    hipLaunchKernelGGL(lc3_rtcp_walk_kernel, dim3((unsigned)(q->n_streams < (1 << 20) ? q->n_streams : 1 << 20)), dim3(LC3Q_WALK_THREADS), 0, s, *q, off, idx);
-    QCHK(hipGetLastError());
-    k_launches[K_WALK]++;
-    if (q->sync) QCHK(hipStreamSynchronize(s));
+    SIB_LAUNCH(lc3_rtcp_walk_kernel, dim3((unsigned)(q->n_streams < (1 << 20) ? q->n_streams : 1 << 20)), dim3(LC3Q_WALK_THREADS), 0, s, *q, off, idx);
+    if (q->sync) SIB_CHK(hipStreamSynchronize(s));
     return 0;
 }

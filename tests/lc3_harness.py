@@ -19,6 +19,13 @@ def have_ref():
     return os.path.exists(REF_SO)
 
 
+def sibling_launches(sibling, kernel):
+    """Launches of `kernel` so far in this process by the sibling library liblc3plus_<sibling>_hip.so (its lc3<sibling>_launch_count); -1 for a kernel that is not its own."""
+    f = getattr(C.CDLL(os.path.join(ROOT, "audio_codec_amd", "liblc3plus_%s_hip.so" % sibling)), "lc3%s_launch_count" % sibling)
+    f.restype, f.argtypes = C.c_longlong, [C.c_char_p]
+    return f(kernel.encode())
+
+
 # ---------------------------------------------------------------------------------------------
 # synthetic PCM (int16): sinusoids + coloured noise + transients; some silent / full-scale streams
 # ---------------------------------------------------------------------------------------------

@@ -14,7 +14,7 @@ import pytest
 
 import egress_ref as ref
 import hostile_frames as hf
-from lc3_harness import Oracle, synth_pcm
+from lc3_harness import Oracle, sibling_launches, synth_pcm
 from test_gpu_dec_varsize_device import _Hip
 
 pytestmark = pytest.mark.gpu
@@ -40,10 +40,7 @@ def dev():
 
 
 def _launches(name):
-    L = C.CDLL(LIB)
-    L.lc3egress_launch_count.restype = C.c_longlong
-    L.lc3egress_launch_count.argtypes = [C.c_char_p]
-    return L.lc3egress_launch_count(name.encode())
+    return sibling_launches("egress", name)
 
 
 def _shapes(c):

@@ -4,7 +4,6 @@ api.frame_info_side of the same payloads; the items are the stream-frames of hos
 odd offsets with gaps and duplicates.  Then the edge items, the bytes around info, statelessness against a twin batch, and the sibling library's own launch
 counts.  Device buffers through ctypes (test_gpu_dec_varsize_device._Hip)."""
 import collections
-import ctypes as C
 import functools
 import os
 import sys
@@ -14,6 +13,7 @@ import pytest
 
 import frame_probe_ref as ref
 import hostile_frames as hf
+from lc3_harness import sibling_launches
 from test_gpu_dec_varsize_device import _Hip
 
 pytestmark = pytest.mark.gpu
@@ -220,9 +220,6 @@ def test_every_probe_kernel_ran_under_a_comparison(dev):
         for depth in (ref.FULL, ref.SIDE):
             _same(_probe(dev, d, d_buf, buf.size, offs, sizes, int(sizes.max()), depth), want[depth][item], (geom, depth))
         d.close()
-    L = C.CDLL(lib)
-    L.lc3probe_launch_count.restype = C.c_longlong
-    L.lc3probe_launch_count.argtypes = [C.c_char_p]
     for n in names:
-        assert L.lc3probe_launch_count(n.encode()) > 0, n
-    assert L.lc3probe_launch_count(b"lc3_dec_parse_kernel") == -1
+        assert sibling_launches("probe", n) > 0, n
+    assert sibling_launches("probe", "lc3_dec_parse_kernel") == -1

@@ -3,7 +3,6 @@ the host plan (api.plan_ingest, itself held to the numpy rule in test_ingest_cpu
 behind every output; then probe -> ingest -> set_frame_counts + decode_packed queued on one HIP stream with a single wait at the end, PCM and status against
 the CPU oracle decoder run over the sequence each stream is expected to see; statelessness; and the sibling library's own launch counts.  Device buffers through
 ctypes (test_gpu_dec_varsize_device._Hip)."""
-import ctypes as C
 import functools
 import os
 import sys
@@ -13,6 +12,7 @@ import pytest
 
 import hostile_frames as hf
 import ingest_ref as ref
+from lc3_harness import sibling_launches
 from test_gpu_dec_varsize_device import _Hip
 
 pytestmark = pytest.mark.gpu
@@ -273,9 +273,6 @@ def test_every_ingest_kernel_ran_under_a_comparison(dev):
     d = _batch(c["n_streams"], c["channels"])
     _same(_run(dev, d, c), _plan(c), "3x4_16_info")
     d.close()
-    L = C.CDLL(lib)
-    L.lc3ingest_launch_count.restype = C.c_longlong
-    L.lc3ingest_launch_count.argtypes = [C.c_char_p]
     for n in names:
-        assert L.lc3ingest_launch_count(n.encode()) > 0, n
-    assert L.lc3ingest_launch_count(b"lc3_probe_side_kernel") == -1
+        assert sibling_launches("ingest", n) > 0, n
+    assert sibling_launches("ingest", "lc3_probe_side_kernel") == -1

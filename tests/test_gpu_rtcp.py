@@ -14,6 +14,7 @@ import pytest
 
 import rtcp_ref as ref
 import rtp_ref
+from lc3_harness import sibling_launches
 from test_gpu_dec_varsize_device import _Hip
 
 pytestmark = pytest.mark.gpu
@@ -45,10 +46,7 @@ def bat():
 
 
 def _launches(name):
-    L = C.CDLL(LIB)
-    L.lc3rtcp_launch_count.restype = C.c_longlong
-    L.lc3rtcp_launch_count.argtypes = [C.c_char_p]
-    return L.lc3rtcp_launch_count(name.encode())
+    return sibling_launches("rtcp", name)
 
 
 def _u32(a):

@@ -13,7 +13,7 @@ import pytest
 
 import hostile_frames as hf
 import rtp_ref as ref
-from lc3_harness import synth_pcm
+from lc3_harness import sibling_launches, synth_pcm
 from test_gpu_dec_varsize_device import _Hip
 
 pytestmark = pytest.mark.gpu
@@ -40,10 +40,7 @@ def dev():
 
 
 def _launches(name):
-    L = C.CDLL(LIB)
-    L.lc3rtp_launch_count.restype = C.c_longlong
-    L.lc3rtp_launch_count.argtypes = [C.c_char_p]
-    return L.lc3rtp_launch_count(name.encode())
+    return sibling_launches("rtp", name)
 
 
 def _dec(S, ch=1):

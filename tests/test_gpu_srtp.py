@@ -7,7 +7,6 @@ flipped bits, 65 items of one source and one item each of 65 sources.  The SSRC 
 another path.  The protect list has its own payloads for the padding boundary (its payload_room shifts it) and slots that hold its 400-byte payloads.  Then both
 chains on one HIP stream without a wait between the calls, the host convenience, and the sibling library's own launch counts.  Device buffers through ctypes
 (test_gpu_dec_varsize_device._Hip)."""
-import ctypes as C
 import os
 
 import numpy as np
@@ -16,11 +15,11 @@ import pytest
 import hostile_frames as hf
 import srtp_cases as cases
 import srtp_ref as ref
+from lc3_harness import sibling_launches
 from test_gpu_dec_varsize_device import _Hip
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIB = os.path.join(ROOT, "audio_codec_amd", "liblc3plus_srtp_hip.so")
 GUARD = 16                                             # elements behind every output array
 SENTINEL = {np.int64: 0x5A5A5A5A5A5A5A5A, np.int32: 0x5A5A5A5A, np.uint8: 0x5A}
 KERNELS = ["lc3_srtp_protect_kernel", "lc3_srtp_route_kernel", "lc3_srtp_init_kernel", "lc3_srtp_scan_kernel", "lc3_srtp_auth_kernel", "lc3_srtp_window_kernel",
@@ -40,10 +39,7 @@ def dev():
 
 
 def _launches(name):
-    L = C.CDLL(LIB)
-    L.lc3srtp_launch_count.restype = C.c_longlong
-    L.lc3srtp_launch_count.argtypes = [C.c_char_p]
-    return L.lc3srtp_launch_count(name.encode())
+    return sibling_launches("srtp", name)
 
 
 def _dec(S=1):

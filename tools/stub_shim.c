@@ -27,15 +27,16 @@ typedef struct {
 typedef struct { int id, dec, n_streams, channels; } stub_ctx;
 
 static pthread_mutex_t g_mu = PTHREAD_MUTEX_INITIALIZER;
-static lc3stub_rec* g_log; static int g_n, g_cap, g_next_ctx, g_fail = -1;
+static lc3stub_rec* g_log; static int g_n, g_cap, g_next_ctx, g_fail = -1, g_device_args;
 
 void lc3stub_reset(void)
 {
     pthread_mutex_lock(&g_mu);
-    g_n = 0; g_next_ctx = 0; g_fail = -1;
+    g_n = 0; g_next_ctx = 0; g_fail = -1; g_device_args = 0;
     pthread_mutex_unlock(&g_mu);
 }
 void lc3stub_fail_ctx(int ctx) { pthread_mutex_lock(&g_mu); g_fail = ctx; pthread_mutex_unlock(&g_mu); }
+void lc3stub_device_args(int on) { pthread_mutex_lock(&g_mu); g_device_args = on; pthread_mutex_unlock(&g_mu); }
 int lc3stub_rec_sizeof(void) { return (int)sizeof(lc3stub_rec); }
 /* copies up to max records, oldest first; returns how many the log holds */
 int lc3stub_log(lc3stub_rec* out, int max)
@@ -86,8 +87,14 @@ int lc3hip_download_chans(void* ctx, lc3d_chan* chans) { return 0; }
 int lc3hip_dec_download_chans(void* ctx, lc3d_dchan* chans) { return 0; }
 float lc3hip_last_ms(void* ctx) { return 0.0f; }
 float lc3hip_dec_last_ms(void* ctx) { return 0.0f; }
-int lc3hip_dec_probe_args(void* ctx, int* device, const lc3d_plan** plan_dev, const lc3d_dchan** tab_dev, int* tab_n, void** stream) { return 1; }   /* no device: a probe fails behind its checks */
-int lc3hip_stream_args(void* ctx, int want_stream, int* device, void** stream) { return 1; }   /* no device: an egress call fails behind its checks */
+/* no device: a probe or an egress call fails behind its checks.  With lc3stub_device_args(1) the two calls succeed instead (device 0, no stream, no tables), so that
+ * a call gets as far as looking for its sibling library, of which the stub build has none (tests/test_sibling_missing_cpu.py) */
+int lc3hip_dec_probe_args(void* ctx, int* device, const lc3d_plan** plan_dev, const lc3d_dchan** tab_dev, int* tab_n, void** stream)
+{
+    *device = 0; *plan_dev = NULL; *tab_dev = NULL; *tab_n = 0; *stream = NULL;
+    return !g_device_args;
+}
+int lc3hip_stream_args(void* ctx, int want_stream, int* device, void** stream) { *device = 0; *stream = NULL; return !g_device_args; }
 int lc3hip_set_input_ready(void* ctx, int ready) { return 0; }
 int lc3hip_dec_set_input_ready(void* ctx, int ready) { return 0; }
 static int stub_placement(void* ctx, const long long* offsets_dev, long long capacity)
