@@ -47,6 +47,8 @@ EXPORTS = [
     "lc3plus_dec_batch_rtcp_stats", "lc3plus_plan_rtcp_stats", "lc3plus_rtcp_workspace_bytes",
     "lc3plus_srtp_make_context", "lc3plus_enc_batch_srtp_protect", "lc3plus_dec_batch_srtp_protect", "lc3plus_plan_srtp_protect",
     "lc3plus_dec_batch_srtp_unprotect", "lc3plus_plan_srtp_unprotect", "lc3plus_srtp_workspace_bytes",
+    "lc3plus_srtp_gcm_make_context", "lc3plus_enc_batch_srtp_gcm_protect", "lc3plus_dec_batch_srtp_gcm_protect", "lc3plus_plan_srtp_gcm_protect",
+    "lc3plus_dec_batch_srtp_gcm_unprotect", "lc3plus_plan_srtp_gcm_unprotect",
     "lc3plus_shard_block",
     "lc3plus_enc_sharded_create", "lc3plus_enc_sharded_destroy", "lc3plus_enc_sharded_shards", "lc3plus_enc_sharded_shard", "lc3plus_enc_sharded_device",
     "lc3plus_enc_sharded_owner", "lc3plus_enc_sharded_input_samples", "lc3plus_enc_sharded_num_bytes", "lc3plus_enc_sharded_stride",
@@ -116,6 +118,10 @@ SRTP_FLAGS, SRTP_ROC, SRTP_S_L, SRTP_WIN_LO, SRTP_WIN_HI = range(5)
 SRTP_STARTED = 1
 (SRTP_OK, SRTP_UN_RANGE, SRTP_SHORT, SRTP_VERSION, SRTP_RTCP, SRTP_HEADER, SRTP_UNKNOWN_SSRC, SRTP_REPLAY_OLD, SRTP_REPLAYED, SRTP_AUTH) = range(10)
 SRTP_STATS_WORDS = 16
+# Secure RTP, AEAD (srtp_gcm_make_context, Batch.srtp_gcm_protect_device, DecBatch.srtp_gcm_unprotect, plan_srtp_gcm_protect, plan_srtp_gcm_unprotect;
+# include/lc3plus_batch.h "Secure RTP, AEAD"): the context's words and the tag's bytes; every other constant is SRTP_*'s
+SRTP_GCM_CTX_WORDS = 128
+SRTP_GCM_TAG_BYTES = 16
 LC3_BW_WARNING = 18
 
 
@@ -290,6 +296,13 @@ def load_library():
         L.lc3plus_dec_batch_srtp_unprotect.argtypes = [C.c_void_p] + unp + [C.c_void_p, C.c_int64, C.c_void_p, C.c_int]
         L.lc3plus_plan_srtp_unprotect.argtypes = unp
         L.lc3plus_srtp_workspace_bytes.argtypes = [C.c_int64, C.c_int]; L.lc3plus_srtp_workspace_bytes.restype = C.c_int64
+        L.lc3plus_srtp_gcm_make_context.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        gprot, gunp = prot[:18] + prot[19:], unp[:10] + unp[11:]         # the AEAD calls: the same lists without tag_len
+        L.lc3plus_enc_batch_srtp_gcm_protect.argtypes = [C.c_void_p] + gprot + [C.c_void_p, C.c_int]
+        L.lc3plus_dec_batch_srtp_gcm_protect.argtypes = [C.c_void_p] + gprot + [C.c_void_p, C.c_int]
+        L.lc3plus_plan_srtp_gcm_protect.argtypes = gprot
+        L.lc3plus_dec_batch_srtp_gcm_unprotect.argtypes = [C.c_void_p] + gunp + [C.c_void_p, C.c_int64, C.c_void_p, C.c_int]
+        L.lc3plus_plan_srtp_gcm_unprotect.argtypes = gunp
         _LIB = L
     return _LIB
 
@@ -816,7 +829,7 @@ def srtp_workspace_bytes(n_items, n_ssrc):
 
 
 def plan_srtp_protect(pkt_route, pkt_offset, pkt_size, pkt_status, wire, ctx, roc, seq_base, dst, dst_stride, tag_len=10, header_room=12, payload_room=0,
-                      next_seq=None, n_packets=None, wire_capacity=None, dst_capacity=None):
+                      next_seq=None, n_packets=None, wire_capacity=None, dst_capacity=None, _gcm=False):
     """The rule of Batch.srtp_protect_device / DecBatch.srtp_protect_device on the host (lc3plus_plan_srtp_protect, no device needed): the stamp's view of the
     egress's packet list pkt_route, pkt_offset (int64), pkt_size, pkt_status (uint8) [max_packets] (n_packets of it: all by default), the stamped wire buffer
     (uint8; wire_capacity bytes of it), per route ctx [n_routes, SRTP_CTX_WORDS], roc, seq_base and optionally next_seq [n_routes]; dst: the destination's
@@ -828,7 +841,7 @@ def plan_srtp_protect(pkt_route, pkt_offset, pkt_size, pkt_status, wire, ctx, ro
     pst = np.ascontiguousarray(pkt_status, dtype=np.uint8).reshape(-1)
     if not (off.size == size.size == pst.size == m):
         raise ValueError("the list arrays hold one entry per packet")
-    ctx = np.ascontiguousarray(_u32(ctx)).reshape(-1, SRTP_CTX_WORDS)
+    ctx = np.ascontiguousarray(_u32(ctx)).reshape(-1, SRTP_GCM_CTX_WORDS if _gcm else SRTP_CTX_WORDS)
     R = ctx.shape[0]
     roc, seq_base = _u32(roc), _u32(seq_base)
     next_seq = _u32(next_seq) if next_seq is not None else None
@@ -840,16 +853,17 @@ def plan_srtp_protect(pkt_route, pkt_offset, pkt_size, pkt_status, wire, ctx, ro
     outs = [np.zeros(m, np.int64), np.zeros(m, np.int32), np.zeros(m, np.uint8), np.zeros(R, np.int32) if next_seq is not None else None]
     pad = np.zeros(8, np.uint8)
     ptr = lambda a: (a if a.size else pad).ctypes.data if a is not None else None
-    rc = load_library().lc3plus_plan_srtp_protect(m, ptr(count), ptr(route), ptr(off), ptr(size), ptr(pst), ptr(wire),
-                                                  wire.size if wire_capacity is None else int(wire_capacity), int(header_room), int(payload_room), R, ptr(ctx),
-                                                  ptr(roc), ptr(seq_base), ptr(next_seq), ptr(dst), dst.size if dst_capacity is None else int(dst_capacity),
-                                                  int(dst_stride), int(tag_len), *[ptr(a) for a in outs])
+    name = "lc3plus_plan_srtp_gcm_protect" if _gcm else "lc3plus_plan_srtp_protect"
+    rc = getattr(load_library(), name)(m, ptr(count), ptr(route), ptr(off), ptr(size), ptr(pst), ptr(wire),
+                                       wire.size if wire_capacity is None else int(wire_capacity), int(header_room), int(payload_room), R, ptr(ctx),
+                                       ptr(roc), ptr(seq_base), ptr(next_seq), ptr(dst), dst.size if dst_capacity is None else int(dst_capacity),
+                                       int(dst_stride), *([] if _gcm else [int(tag_len)]), *[ptr(a) for a in outs])
     if rc:
-        raise LC3Error(rc, "lc3plus_plan_srtp_protect")
+        raise LC3Error(rc, name)
     return dict(zip(SRTP_PROTECT_OUTPUTS, outs), dst=dst)
 
 
-def _srtp_unprotect_arrays(ring, dg_offsets, dg_sizes, ssrc_key, ctx, state, optional):
+def _srtp_unprotect_arrays(ring, dg_offsets, dg_sizes, ssrc_key, ctx, state, optional, ctx_words=SRTP_CTX_WORDS):
     """the arrays of an unprotect call as the C calls take them: (ring - a copy -, dg_offsets, dg_sizes, ssrc_key, ctx, state_in; outputs in
     SRTP_UNPROTECT_OUTPUTS order, None for NULL)"""
     ring = np.array(ring, dtype=np.uint8).reshape(-1)                 # a copy: the call decrypts in place
@@ -858,7 +872,7 @@ def _srtp_unprotect_arrays(ring, dg_offsets, dg_sizes, ssrc_key, ctx, state, opt
     key = _u32(ssrc_key)
     if dg_offsets.size != dg_sizes.size:
         raise ValueError("dg_offsets and dg_sizes hold one entry per datagram")
-    ctx = np.ascontiguousarray(_u32(ctx)).reshape(-1, SRTP_CTX_WORDS)
+    ctx = np.ascontiguousarray(_u32(ctx)).reshape(-1, ctx_words)
     state = np.ascontiguousarray(_u32(state)).reshape(-1, SRTP_STATE_WORDS)
     if ctx.shape[0] != key.size or state.shape[0] != key.size:
         raise ValueError("ssrc_key, ctx and state hold one entry per source")
@@ -885,6 +899,43 @@ def plan_srtp_unprotect(ring, dg_offsets, dg_sizes, ssrc_key, ctx, state, tag_le
     return dict(zip(SRTP_UNPROTECT_OUTPUTS, outs), ring=ins[0])
 
 
+def srtp_gcm_make_context(master_key, master_salt):
+    """An SRTP AES-GCM crypto context (lc3plus_srtp_gcm_make_context, host only): master_key (16 bytes: AEAD_AES_128_GCM; 32 bytes: AEAD_AES_256_GCM) and
+    master_salt (12 bytes) -> SRTP_GCM_CTX_WORDS int32 words - the round keys of the session key, the number of rounds, the session salt and the GHASH table
+    (RFC 7714 11, key derivation rate 0) - as the device reads them; the caller stacks contexts, of both key sizes where it likes, into
+    [n, SRTP_GCM_CTX_WORDS] and copies them to device memory."""
+    key, salt = np.frombuffer(bytes(master_key), np.uint8), np.frombuffer(bytes(master_salt), np.uint8)
+    if key.size not in (16, 32) or salt.size != 12:
+        raise ValueError("master_key holds 16 or 32 bytes, master_salt 12")
+    ctx = np.zeros(SRTP_GCM_CTX_WORDS, np.int32)
+    rc = load_library().lc3plus_srtp_gcm_make_context(key.ctypes.data, key.size, salt.ctypes.data, ctx.ctypes.data)
+    if rc:
+        raise LC3Error(rc, "lc3plus_srtp_gcm_make_context")
+    return ctx
+
+
+def plan_srtp_gcm_protect(pkt_route, pkt_offset, pkt_size, pkt_status, wire, ctx, roc, seq_base, dst, dst_stride, header_room=12, payload_room=0, next_seq=None,
+                          n_packets=None, wire_capacity=None, dst_capacity=None):
+    """plan_srtp_protect for the AEAD suites (lc3plus_plan_srtp_gcm_protect): the same arguments without tag_len, ctx [n_routes, SRTP_GCM_CTX_WORDS] -> the same
+    dict; a protected packet is SRTP_GCM_TAG_BYTES longer than its RTP packet."""
+    return plan_srtp_protect(pkt_route, pkt_offset, pkt_size, pkt_status, wire, ctx, roc, seq_base, dst, dst_stride, SRTP_GCM_TAG_BYTES, header_room, payload_room,
+                             next_seq, n_packets, wire_capacity, dst_capacity, _gcm=True)
+
+
+def plan_srtp_gcm_unprotect(ring, dg_offsets, dg_sizes, ssrc_key, ctx, state, optional=SRTP_UNPROTECT_OPTIONAL, ring_capacity=None):
+    """plan_srtp_unprotect for the AEAD suites (lc3plus_plan_srtp_gcm_unprotect): the same arguments without tag_len, ctx [n_ssrc, SRTP_GCM_CTX_WORDS] -> the
+    same dict."""
+    ins, outs = _srtp_unprotect_arrays(ring, dg_offsets, dg_sizes, ssrc_key, ctx, state, optional, SRTP_GCM_CTX_WORDS)
+    pad = np.zeros(8, np.uint8)
+    ptr = lambda a: (a if a.size else pad).ctypes.data if a is not None else None
+    cap = ins[0].size if ring_capacity is None else int(ring_capacity)
+    rc = load_library().lc3plus_plan_srtp_gcm_unprotect(ins[1].size, ptr(ins[0]), cap, ptr(ins[1]), ptr(ins[2]), ins[3].size, ptr(ins[3]), ptr(ins[4]), ptr(ins[5]),
+                                                        ptr(outs[0]), *[ptr(a) for a in outs[1:]])
+    if rc:
+        raise LC3Error(rc, "lc3plus_plan_srtp_gcm_unprotect")
+    return dict(zip(SRTP_UNPROTECT_OUTPUTS, outs), ring=ins[0])
+
+
 class _SrtpProtect:
     """The send side of Secure RTP for both batch kinds (lc3plus_{enc,dec}_batch_srtp_protect; include/lc3plus_batch.h "Secure RTP")."""
 
@@ -903,6 +954,21 @@ class _SrtpProtect:
                                         p(d_out_size_ptr), p(d_out_status_ptr), p(d_next_roc_ptr), p(hip_stream), 1 if sync else 0)
         if rc:
             raise LC3Error(rc, self._ss + "_srtp_protect")
+
+    def srtp_gcm_protect_device(self, max_packets, d_n_packets_ptr, d_pkt_route_ptr, d_pkt_offset_ptr, d_pkt_size_ptr, d_pkt_status_ptr, d_wire_ptr, wire_capacity,
+                                n_routes, d_ctx_ptr, d_roc_ptr, d_seq_base_ptr, d_dst_ptr, dst_capacity, dst_stride, d_out_offset_ptr, d_out_size_ptr,
+                                d_out_status_ptr, header_room=12, payload_room=0, d_next_seq_ptr=None, d_next_roc_ptr=None, hip_stream=None, sync=False):
+        """srtp_protect_device for the AEAD suites (lc3plus_{enc,dec}_batch_srtp_gcm_protect): the same arguments without tag_len, ctx [n_routes,
+        SRTP_GCM_CTX_WORDS], routes of 16- and 32-byte keys side by side -> header, AES-GCM ciphertext and a tag of SRTP_GCM_TAG_BYTES bytes at
+        dst + p * dst_stride."""
+        def p(x):
+            return C.c_void_p(x) if x else None
+        rc = self._ssf("_srtp_gcm_protect")(self.h, int(max_packets), p(d_n_packets_ptr), p(d_pkt_route_ptr), p(d_pkt_offset_ptr), p(d_pkt_size_ptr),
+                                            p(d_pkt_status_ptr), p(d_wire_ptr), int(wire_capacity), int(header_room), int(payload_room), int(n_routes), p(d_ctx_ptr),
+                                            p(d_roc_ptr), p(d_seq_base_ptr), p(d_next_seq_ptr), p(d_dst_ptr), int(dst_capacity), int(dst_stride), p(d_out_offset_ptr),
+                                            p(d_out_size_ptr), p(d_out_status_ptr), p(d_next_roc_ptr), p(hip_stream), 1 if sync else 0)
+        if rc:
+            raise LC3Error(rc, self._ss + "_srtp_gcm_protect")
 
 
 class _StreamLifecycle:
@@ -1802,6 +1868,32 @@ class DecBatch(_StreamLifecycle, _Egress, _RtpStamp, _SrtpProtect):
         work = np.zeros(max(srtp_workspace_bytes(n, S), 8), np.uint8)
         with _on_device(ins + outs + [work]) as (v, back):
             self.srtp_unprotect_device(n, v[0], cap, v[1], v[2], S, v[3], v[4], v[5], v[6], v[7], v[11], work.size, tag_len, v[8], v[9], v[10], sync=True)
+            for k in [0] + list(range(6, 11)):
+                back(k)
+        return dict(zip(SRTP_UNPROTECT_OUTPUTS, outs), ring=ins[0])
+
+    def srtp_gcm_unprotect_device(self, n_items, d_ring_ptr, ring_capacity, d_dg_offsets_ptr, d_dg_sizes_ptr, n_ssrc, d_ssrc_key_ptr, d_ctx_ptr, d_state_in_ptr,
+                                  d_state_out_ptr, d_sizes_out_ptr, d_workspace_ptr, workspace_bytes, d_status_ptr=None, d_index_ptr=None, d_stats_ptr=None,
+                                  hip_stream=None, sync=False):
+        """srtp_unprotect_device for the AEAD suites (lc3plus_dec_batch_srtp_gcm_unprotect): the same arguments without tag_len, ctx [n_ssrc,
+        SRTP_GCM_CTX_WORDS], sources of 16- and 32-byte keys side by side; the workspace is srtp_workspace_bytes(n_items, n_ssrc) bytes."""
+        def p(x):
+            return C.c_void_p(x) if x else None
+        rc = self.lib.lc3plus_dec_batch_srtp_gcm_unprotect(self.h, int(n_items), p(d_ring_ptr), int(ring_capacity), p(d_dg_offsets_ptr), p(d_dg_sizes_ptr),
+                                                           int(n_ssrc), p(d_ssrc_key_ptr), p(d_ctx_ptr), p(d_state_in_ptr), p(d_state_out_ptr), p(d_sizes_out_ptr),
+                                                           p(d_status_ptr), p(d_index_ptr), p(d_stats_ptr), p(d_workspace_ptr), int(workspace_bytes), p(hip_stream),
+                                                           1 if sync else 0)
+        if rc:
+            raise LC3Error(rc, "lc3plus_dec_batch_srtp_gcm_unprotect")
+
+    def srtp_gcm_unprotect(self, ring, dg_offsets, dg_sizes, ssrc_key, ctx, state, optional=SRTP_UNPROTECT_OPTIONAL, ring_capacity=None):
+        """Host convenience: the arrays of plan_srtp_gcm_unprotect uploaded, run on the device and downloaded -> the dict plan_srtp_gcm_unprotect gives."""
+        ins, outs = _srtp_unprotect_arrays(ring, dg_offsets, dg_sizes, ssrc_key, ctx, state, optional, SRTP_GCM_CTX_WORDS)
+        n, S = ins[1].size, ins[3].size
+        cap = ins[0].size if ring_capacity is None else int(ring_capacity)
+        work = np.zeros(max(srtp_workspace_bytes(n, S), 8), np.uint8)
+        with _on_device(ins + outs + [work]) as (v, back):
+            self.srtp_gcm_unprotect_device(n, v[0], cap, v[1], v[2], S, v[3], v[4], v[5], v[6], v[7], v[11], work.size, v[8], v[9], v[10], sync=True)
             for k in [0] + list(range(6, 11)):
                 back(k)
         return dict(zip(SRTP_UNPROTECT_OUTPUTS, outs), ring=ins[0])

@@ -28,6 +28,7 @@
 #include "lc3_rtp_shim.h"
 #include "lc3_rtcp_shim.h"
 #include "lc3_srtp_shim.h"
+#include "lc3_gcm_shim.h"
 
 #ifndef M_PI
 #define M_PI 3.14159265358979323846
@@ -1835,7 +1836,7 @@ LC3_Error lc3plus_frame_info_side(int samplerate, int channels, float frame_ms, 
     return LC3_OK;
 }
 /* ---- the sibling libraries (DESIGN.md "Sibling libraries"): the kernels of every call below lie in a library of their own beside this one ---- */
-enum { SIB_PROBE, SIB_INGEST, SIB_EGRESS, SIB_RTP, SIB_RTCP, SIB_SRTP, SIB_COUNT };
+enum { SIB_PROBE, SIB_INGEST, SIB_EGRESS, SIB_RTP, SIB_RTCP, SIB_SRTP, SIB_GCM, SIB_COUNT };
 /* a row: the file, its one or two entry points, and where they go.  fn holds either all of them or none */
 static struct { const char* file; const char* sym[2]; int tried; void* fn[2]; } siblings[SIB_COUNT] = {
     [SIB_PROBE] = {"liblc3plus_probe_hip.so", {"lc3probe_run", NULL}, 0, {NULL, NULL}},
@@ -1844,6 +1845,7 @@ static struct { const char* file; const char* sym[2]; int tried; void* fn[2]; } 
     [SIB_RTP] = {"liblc3plus_rtp_hip.so", {"lc3rtp_parse_run", "lc3rtp_stamp_run"}, 0, {NULL, NULL}},
     [SIB_RTCP] = {"liblc3plus_rtcp_hip.so", {"lc3rtcp_stats_run", NULL}, 0, {NULL, NULL}},
     [SIB_SRTP] = {"liblc3plus_srtp_hip.so", {"lc3srtp_protect_run", "lc3srtp_unprotect_run"}, 0, {NULL, NULL}},
+    [SIB_GCM] = {"liblc3plus_gcm_hip.so", {"lc3gcm_protect_run", "lc3gcm_unprotect_run"}, 0, {NULL, NULL}},
 };
 static pthread_mutex_t sibling_mu = PTHREAD_MUTEX_INITIALIZER;
 /* The entry points of a sibling, or NULL where the library is missing or lacks one of them.  The file is looked for once per process, on the first call that needs
@@ -2416,8 +2418,8 @@ typedef struct {
     void* dst; int64_t dst_capacity; int64_t dst_stride; int tag_len;
     int64_t* out_offset; int32_t* out_size; uint8_t* out_status; int32_t* next_roc;
 } srtp_protect_args;
-/* the checks every protect call makes first, in the header's order */
-static LC3_Error srtp_protect_check(const srtp_protect_args* a)
+/* the checks every protect call makes first, in the header's order; tag_ok: what the suite says to a->tag_len (the GCM calls have no such argument) */
+static LC3_Error srtp_protect_check(const srtp_protect_args* a, int tag_ok)
 {
     if (!a->n_packets || !a->pkt_route || !a->pkt_offset || !a->pkt_size || !a->pkt_status || !a->wire || !a->ctx || !a->roc || !a->seq_base || !a->dst ||
         !a->out_offset || !a->out_size || !a->out_status)
@@ -2426,7 +2428,7 @@ static LC3_Error srtp_protect_check(const srtp_protect_args* a)
     if (a->max_packets <= 0 || a->max_packets >= LC3S_MAX_ITEMS || a->wire_capacity < 0 || a->payload_room < 0 || a->header_room < LC3R_FIXED ||
         a->header_room - LC3R_FIXED < a->payload_room || a->n_routes <= 0)
         return LC3_ERROR;
-    if (a->dst_capacity < 0 || a->dst_stride <= 0 || a->dst_stride > LC3S_MAX_STRIDE || (a->tag_len != 4 && a->tag_len != 10)) return LC3_ERROR;
+    if (a->dst_capacity < 0 || a->dst_stride <= 0 || a->dst_stride > LC3S_MAX_STRIDE || !tag_ok) return LC3_ERROR;
     const uintptr_t w0 = (uintptr_t)a->wire, d0 = (uintptr_t)a->dst;
     if (d0 < w0 + (uintptr_t)a->wire_capacity && w0 < d0 + (uintptr_t)a->dst_capacity) return LC3_ERROR;          /* out of place only */
     return LC3_OK;
@@ -2438,7 +2440,21 @@ static lc3s_protect_in srtp_protect_in(const srtp_protect_args* a)
                                a->payload_room, a->n_routes, a->tag_len};
     return q;
 }
-/* the rule on the host: the kernels' steps (lc3_srtp.inc) on the text they run */
+/* the rule on the host, behind the checks: the kernels' steps (lc3_srtp.inc; gcm: lc3_gcm.inc) on the text they run */
+static void srtp_protect_plan(const srtp_protect_args* a, int gcm)
+{
+    const lc3s_protect_in q = srtp_protect_in(a);
+    uint32_t te[LC3S_TE_WORDS];
+    for (uint32_t x = 0; x < LC3S_TE_WORDS; x++) te[x] = lc3s_te0(x);
+    const int64_t n = *a->n_packets < a->max_packets ? *a->n_packets : a->max_packets;
+    for (int64_t p = 0; p < n; p++) {
+        int32_t size = 0;
+        const int st = gcm ? lc3g_protect(&q, p, te, 1, NULL, 1, &size) : lc3s_protect(&q, p, te, 1, &size);
+        a->out_offset[p] = p * a->dst_stride; a->out_size[p] = size; a->out_status[p] = (uint8_t)st;
+    }
+    if (a->next_roc)
+        for (int r = 0; r < a->n_routes; r++) lc3s_route_out(&q, r, a->next_roc);
+}
 LC3_Error lc3plus_plan_srtp_protect(int64_t max_packets, const int64_t* n_packets,
     const int32_t* pkt_route, const int64_t* pkt_offset, const int32_t* pkt_size, const uint8_t* pkt_status,
     const void* wire, int64_t wire_capacity, int header_room, int payload_room,
@@ -2448,19 +2464,9 @@ LC3_Error lc3plus_plan_srtp_protect(int64_t max_packets, const int64_t* n_packet
 {
     const srtp_protect_args a = {max_packets, n_packets, pkt_route, pkt_offset, pkt_size, pkt_status, wire, wire_capacity, header_room, payload_room, n_routes, ctx,
                                  roc, seq_base, next_seq, dst, dst_capacity, dst_stride, tag_len, out_offset, out_size, out_status, next_roc};
-    const LC3_Error e = srtp_protect_check(&a);
+    const LC3_Error e = srtp_protect_check(&a, tag_len == 4 || tag_len == 10);
     if (e) return e;
-    const lc3s_protect_in q = srtp_protect_in(&a);
-    uint32_t te[LC3S_TE_WORDS];
-    for (uint32_t x = 0; x < LC3S_TE_WORDS; x++) te[x] = lc3s_te0(x);
-    const int64_t n = *n_packets < max_packets ? *n_packets : max_packets;
-    for (int64_t p = 0; p < n; p++) {
-        int32_t size = 0;
-        const int st = lc3s_protect(&q, p, te, 1, &size);
-        out_offset[p] = p * dst_stride; out_size[p] = size; out_status[p] = (uint8_t)st;
-    }
-    if (next_roc)
-        for (int r = 0; r < n_routes; r++) lc3s_route_out(&q, r, next_roc);
+    srtp_protect_plan(&a, 0);
     return LC3_OK;
 }
 /* what an unprotect call takes behind its batch, in the header's order */
@@ -2469,25 +2475,22 @@ typedef struct {
     int n_ssrc; const int32_t* ssrc_key; const int32_t* ctx; const int32_t* state_in; int32_t* state_out; int tag_len;
     int32_t* sizes_out; uint8_t* status; int64_t* index; int32_t* stats;
 } srtp_unprotect_args;
-static LC3_Error srtp_unprotect_check(const srtp_unprotect_args* a)
+static LC3_Error srtp_unprotect_check(const srtp_unprotect_args* a, int tag_ok)
 {
     if (!a->ring || !a->dg_offsets || !a->dg_sizes || !a->ssrc_key || !a->ctx || !a->state_in || !a->state_out || !a->sizes_out) return LC3_NULL_ERROR;
-    if (a->n_items <= 0 || a->n_items >= LC3S_MAX_ITEMS || a->ring_capacity < 0 || a->n_ssrc <= 0 || (a->tag_len != 4 && a->tag_len != 10)) return LC3_ERROR;
+    if (a->n_items <= 0 || a->n_items >= LC3S_MAX_ITEMS || a->ring_capacity < 0 || a->n_ssrc <= 0 || !tag_ok) return LC3_ERROR;
     return LC3_OK;
 }
 int64_t lc3plus_srtp_workspace_bytes(int64_t n_items, int n_ssrc)
 {
     return (int64_t)lc3s_workspace_bytes((long long)n_items, n_ssrc);
 }
-/* the rule on the host: the kernels' passes one after the other - the first items, the items against state_in, the window bits against the new tops, the state */
-LC3_Error lc3plus_plan_srtp_unprotect(int64_t n_items,
-    void* ring, int64_t ring_capacity, const int64_t* dg_offsets, const int32_t* dg_sizes,
-    int n_ssrc, const int32_t* ssrc_key, const int32_t* ctx, const int32_t* state_in, int32_t* state_out, int tag_len,
-    int32_t* sizes_out, uint8_t* status, int64_t* index, int32_t* stats)
+/* the rule on the host, behind the checks: the kernels' passes one after the other - the first items, the items against state_in, the window bits against the
+ * new tops, the state.  gcm: the AEAD rule (a->tag_len is 16 then) */
+static LC3_Error srtp_unprotect_plan(const srtp_unprotect_args* a, int gcm)
 {
-    const srtp_unprotect_args a = {n_items, ring, ring_capacity, dg_offsets, dg_sizes, n_ssrc, ssrc_key, ctx, state_in, state_out, tag_len, sizes_out, status, index, stats};
-    const LC3_Error e = srtp_unprotect_check(&a);
-    if (e) return e;
+    const int64_t n_items = a->n_items;
+    const int n_ssrc = a->n_ssrc, tag_len = a->tag_len;
     uint32_t te[LC3S_TE_WORDS];
     for (uint32_t x = 0; x < LC3S_TE_WORDS; x++) te[x] = lc3s_te0(x);
     unsigned long long* top1 = calloc((size_t)n_ssrc, sizeof *top1);
@@ -2496,47 +2499,60 @@ LC3_Error lc3plus_plan_srtp_unprotect(int64_t n_items,
     int64_t* accepted = malloc(sizeof *accepted * (size_t)n_items);
     lc3s_item* items = malloc(sizeof *items * (size_t)n_items);
     if (!top1 || !bits || !first || !accepted || !items) { free(top1); free(bits); free(first); free(accepted); free(items); return LC3_ERROR; }
-    uint8_t* r8 = (uint8_t*)ring;
+    uint8_t* r8 = (uint8_t*)a->ring;
     for (int s = 0; s < n_ssrc; s++) first[s] = -1;
-    if (stats) memset(stats, 0, sizeof(int32_t) * LC3S_STATS_WORDS);
+    if (a->stats) memset(a->stats, 0, sizeof(int32_t) * LC3S_STATS_WORDS);
     for (int64_t i = 0; i < n_items; i++) {
-        items[i] = lc3s_check(r8, ring_capacity, dg_offsets[i], dg_sizes[i], tag_len, ssrc_key, n_ssrc);
+        items[i] = lc3s_check(r8, a->ring_capacity, a->dg_offsets[i], a->dg_sizes[i], tag_len, a->ssrc_key, n_ssrc);
         if (items[i].status == LC3S_OK && first[items[i].src] < 0) first[items[i].src] = i;
     }
     for (int64_t i = 0; i < n_items; i++) {
         int st = items[i].status;
         long long idx = 0;
         accepted[i] = -1;
-        sizes_out[i] = 0;
+        a->sizes_out[i] = 0;
         if (st == LC3S_OK) {
             const int s = items[i].src;
-            const int32_t* state = state_in + (size_t)s * LC3S_STATE_WORDS;
-            const uint32_t s_l_first = lc3s_seq_at(r8, dg_offsets[first[s]]);
-            st = lc3s_unprotect(r8, dg_offsets[i], dg_sizes[i], tag_len, &items[i], state, s_l_first, (const uint32_t*)ctx + (size_t)s * LC3S_CTX_WORDS, te, 1, &idx);
+            const int32_t* state = a->state_in + (size_t)s * LC3S_STATE_WORDS;
+            const uint32_t s_l_first = lc3s_seq_at(r8, a->dg_offsets[first[s]]);
+            if (gcm)
+                st = lc3g_unprotect(r8, a->dg_offsets[i], a->dg_sizes[i], &items[i], state, s_l_first, (const uint32_t*)a->ctx + (size_t)s * LC3G_CTX_WORDS, te, 1, NULL, 1, &idx);
+            else
+                st = lc3s_unprotect(r8, a->dg_offsets[i], a->dg_sizes[i], tag_len, &items[i], state, s_l_first, (const uint32_t*)a->ctx + (size_t)s * LC3S_CTX_WORDS, te, 1, &idx);
             if (st == LC3S_OK) {
-                accepted[i] = idx; sizes_out[i] = dg_sizes[i] - tag_len;
+                accepted[i] = idx; a->sizes_out[i] = a->dg_sizes[i] - tag_len;
                 if ((unsigned long long)idx + 1 > top1[s]) top1[s] = (unsigned long long)idx + 1;
             }
         }
-        if (status) status[i] = (uint8_t)st;
-        if (index) index[i] = idx;
-        if (stats) stats[st]++;
+        if (a->status) a->status[i] = (uint8_t)st;
+        if (a->index) a->index[i] = idx;
+        if (a->stats) a->stats[st]++;
     }
     for (int64_t i = 0; i < n_items; i++)
         if (accepted[i] >= 0) {
             const int s = items[i].src;
-            bits[s] |= lc3s_window_bit(state_in + (size_t)s * LC3S_STATE_WORDS, top1[s], accepted[i]);
+            bits[s] |= lc3s_window_bit(a->state_in + (size_t)s * LC3S_STATE_WORDS, top1[s], accepted[i]);
         }
-    for (int s = 0; s < n_ssrc; s++) lc3s_state_out(state_in + (size_t)s * LC3S_STATE_WORDS, state_out + (size_t)s * LC3S_STATE_WORDS, top1[s], bits[s]);
+    for (int s = 0; s < n_ssrc; s++) lc3s_state_out(a->state_in + (size_t)s * LC3S_STATE_WORDS, a->state_out + (size_t)s * LC3S_STATE_WORDS, top1[s], bits[s]);
     free(top1); free(bits); free(first); free(accepted); free(items);
     return LC3_OK;
 }
-/* both protect entry points end here */
-static LC3_Error srtp_protect_queue(void* dev, int decoder, const srtp_protect_args* a, void* hip_stream, int sync)
+LC3_Error lc3plus_plan_srtp_unprotect(int64_t n_items,
+    void* ring, int64_t ring_capacity, const int64_t* dg_offsets, const int32_t* dg_sizes,
+    int n_ssrc, const int32_t* ssrc_key, const int32_t* ctx, const int32_t* state_in, int32_t* state_out, int tag_len,
+    int32_t* sizes_out, uint8_t* status, int64_t* index, int32_t* stats)
+{
+    const srtp_unprotect_args a = {n_items, ring, ring_capacity, dg_offsets, dg_sizes, n_ssrc, ssrc_key, ctx, state_in, state_out, tag_len, sizes_out, status, index, stats};
+    const LC3_Error e = srtp_unprotect_check(&a, tag_len == 4 || tag_len == 10);
+    if (e) return e;
+    return srtp_unprotect_plan(&a, 0);
+}
+/* every protect entry point ends here; which: the suite's sibling */
+static LC3_Error srtp_protect_queue(int which, void* dev, int decoder, const srtp_protect_args* a, void* hip_stream, int sync)
 {
     lc3srtp_protect_call q;
     memset(&q, 0, sizeof q);
-    void* const* fn = sibling_call(SIB_SRTP, dev, decoder, hip_stream, &q.device, &q.hip_stream);
+    void* const* fn = sibling_call(which, dev, decoder, hip_stream, &q.device, &q.hip_stream);
     if (!fn) return LC3_ERROR;
     q.sync = sync; q.max_packets = (long long)a->max_packets; q.n_packets = (const long long*)a->n_packets; q.in = srtp_protect_in(a);
     q.out_offset = (long long*)a->out_offset; q.out_size = a->out_size; q.out_status = a->out_status; q.next_roc = a->next_roc;
@@ -2552,9 +2568,9 @@ LC3_Error lc3plus_enc_batch_srtp_protect(lc3plus_batch* b, int64_t max_packets, 
     if (!b) return LC3_NULL_ERROR;
     const srtp_protect_args a = {max_packets, n_packets, pkt_route, pkt_offset, pkt_size, pkt_status, wire, wire_capacity, header_room, payload_room, n_routes, ctx,
                                  roc, seq_base, next_seq, dst, dst_capacity, dst_stride, tag_len, out_offset, out_size, out_status, next_roc};
-    const LC3_Error e = srtp_protect_check(&a);
+    const LC3_Error e = srtp_protect_check(&a, tag_len == 4 || tag_len == 10);
     if (e) return e;
-    return srtp_protect_queue(b->dev, 0, &a, hip_stream, sync);
+    return srtp_protect_queue(SIB_SRTP, b->dev, 0, &a, hip_stream, sync);
 }
 LC3_Error lc3plus_dec_batch_srtp_protect(lc3plus_dec_batch* b, int64_t max_packets, const int64_t* n_packets,
     const int32_t* pkt_route, const int64_t* pkt_offset, const int32_t* pkt_size, const uint8_t* pkt_status,
@@ -2566,9 +2582,23 @@ LC3_Error lc3plus_dec_batch_srtp_protect(lc3plus_dec_batch* b, int64_t max_packe
     if (!b) return LC3_NULL_ERROR;
     const srtp_protect_args a = {max_packets, n_packets, pkt_route, pkt_offset, pkt_size, pkt_status, wire, wire_capacity, header_room, payload_room, n_routes, ctx,
                                  roc, seq_base, next_seq, dst, dst_capacity, dst_stride, tag_len, out_offset, out_size, out_status, next_roc};
-    const LC3_Error e = srtp_protect_check(&a);
+    const LC3_Error e = srtp_protect_check(&a, tag_len == 4 || tag_len == 10);
     if (e) return e;
-    return srtp_protect_queue(b->dev, 1, &a, hip_stream, sync);
+    return srtp_protect_queue(SIB_SRTP, b->dev, 1, &a, hip_stream, sync);
+}
+/* both unprotect entry points end here, behind the checks of the batch and the workspace's pointer */
+static LC3_Error srtp_unprotect_queue(int which, lc3plus_dec_batch* b, const srtp_unprotect_args* a, void* workspace, int64_t workspace_bytes, void* hip_stream, int sync)
+{
+    if (workspace_bytes < lc3plus_srtp_workspace_bytes(a->n_items, a->n_ssrc)) return LC3_ERROR;
+    lc3srtp_unprotect_call q;
+    memset(&q, 0, sizeof q);
+    void* const* fn = sibling_call(which, b->dev, 1, hip_stream, &q.device, &q.hip_stream);
+    if (!fn) return LC3_ERROR;
+    q.sync = sync; q.n_ssrc = a->n_ssrc; q.tag_len = a->tag_len; q.n_items = (long long)a->n_items; q.ring_capacity = (long long)a->ring_capacity;
+    q.ring = a->ring; q.dg_offsets = (const long long*)a->dg_offsets; q.dg_sizes = a->dg_sizes; q.ssrc_key = a->ssrc_key; q.ctx = a->ctx; q.state_in = a->state_in;
+    q.state_out = a->state_out; q.sizes_out = a->sizes_out; q.status = a->status; q.index = (long long*)a->index; q.stats = a->stats;
+    q.workspace = workspace; q.workspace_bytes = (long long)workspace_bytes;
+    return ((int (*)(const lc3srtp_unprotect_call*))fn[1])(&q) ? LC3_ERROR : LC3_OK;
 }
 LC3_Error lc3plus_dec_batch_srtp_unprotect(lc3plus_dec_batch* b, int64_t n_items,
     void* ring, int64_t ring_capacity, const int64_t* dg_offsets, const int32_t* dg_sizes,
@@ -2579,18 +2609,84 @@ LC3_Error lc3plus_dec_batch_srtp_unprotect(lc3plus_dec_batch* b, int64_t n_items
     if (!b) return LC3_NULL_ERROR;
     const srtp_unprotect_args a = {n_items, ring, ring_capacity, dg_offsets, dg_sizes, n_ssrc, ssrc_key, ctx, state_in, state_out, tag_len, sizes_out, status, index, stats};
     if (!workspace) return LC3_NULL_ERROR;
-    const LC3_Error e = srtp_unprotect_check(&a);
+    const LC3_Error e = srtp_unprotect_check(&a, tag_len == 4 || tag_len == 10);
     if (e) return e;
-    if (workspace_bytes < lc3plus_srtp_workspace_bytes(n_items, n_ssrc)) return LC3_ERROR;
-    lc3srtp_unprotect_call q;
-    memset(&q, 0, sizeof q);
-    void* const* fn = sibling_call(SIB_SRTP, b->dev, 1, hip_stream, &q.device, &q.hip_stream);
-    if (!fn) return LC3_ERROR;
-    q.sync = sync; q.n_ssrc = n_ssrc; q.tag_len = tag_len; q.n_items = (long long)n_items; q.ring_capacity = (long long)ring_capacity;
-    q.ring = ring; q.dg_offsets = (const long long*)dg_offsets; q.dg_sizes = dg_sizes; q.ssrc_key = ssrc_key; q.ctx = ctx; q.state_in = state_in; q.state_out = state_out;
-    q.sizes_out = sizes_out; q.status = status; q.index = (long long*)index; q.stats = stats;
-    q.workspace = workspace; q.workspace_bytes = (long long)workspace_bytes;
-    return ((int (*)(const lc3srtp_unprotect_call*))fn[1])(&q) ? LC3_ERROR : LC3_OK;
+    return srtp_unprotect_queue(SIB_SRTP, b, &a, workspace, workspace_bytes, hip_stream, sync);
+}
+/* ---- Secure RTP, AEAD (include/lc3plus_batch.h "Secure RTP, AEAD"; lc3_gcm_shim.h): the HMAC calls' checks, plans and queues with the GCM rule and sibling ---- */
+LC3_Error lc3plus_srtp_gcm_make_context(const uint8_t* master_key, int key_bytes, const uint8_t* master_salt, int32_t* ctx)
+{
+    if (!master_key || !master_salt || !ctx) return LC3_NULL_ERROR;
+    if (key_bytes != 16 && key_bytes != 32) return LC3_ERROR;
+    lc3g_make_context(master_key, key_bytes, master_salt, ctx);
+    return LC3_OK;
+}
+LC3_Error lc3plus_plan_srtp_gcm_protect(int64_t max_packets, const int64_t* n_packets,
+    const int32_t* pkt_route, const int64_t* pkt_offset, const int32_t* pkt_size, const uint8_t* pkt_status,
+    const void* wire, int64_t wire_capacity, int header_room, int payload_room,
+    int n_routes, const int32_t* ctx, const int32_t* roc, const int32_t* seq_base, const int32_t* next_seq,
+    void* dst, int64_t dst_capacity, int64_t dst_stride,
+    int64_t* out_offset, int32_t* out_size, uint8_t* out_status, int32_t* next_roc)
+{
+    const srtp_protect_args a = {max_packets, n_packets, pkt_route, pkt_offset, pkt_size, pkt_status, wire, wire_capacity, header_room, payload_room, n_routes, ctx,
+                                 roc, seq_base, next_seq, dst, dst_capacity, dst_stride, LC3G_TAG_BYTES, out_offset, out_size, out_status, next_roc};
+    const LC3_Error e = srtp_protect_check(&a, 1);
+    if (e) return e;
+    srtp_protect_plan(&a, 1);
+    return LC3_OK;
+}
+LC3_Error lc3plus_enc_batch_srtp_gcm_protect(lc3plus_batch* b, int64_t max_packets, const int64_t* n_packets,
+    const int32_t* pkt_route, const int64_t* pkt_offset, const int32_t* pkt_size, const uint8_t* pkt_status,
+    const void* wire, int64_t wire_capacity, int header_room, int payload_room,
+    int n_routes, const int32_t* ctx, const int32_t* roc, const int32_t* seq_base, const int32_t* next_seq,
+    void* dst, int64_t dst_capacity, int64_t dst_stride,
+    int64_t* out_offset, int32_t* out_size, uint8_t* out_status, int32_t* next_roc, void* hip_stream, int sync)
+{
+    if (!b) return LC3_NULL_ERROR;
+    const srtp_protect_args a = {max_packets, n_packets, pkt_route, pkt_offset, pkt_size, pkt_status, wire, wire_capacity, header_room, payload_room, n_routes, ctx,
+                                 roc, seq_base, next_seq, dst, dst_capacity, dst_stride, LC3G_TAG_BYTES, out_offset, out_size, out_status, next_roc};
+    const LC3_Error e = srtp_protect_check(&a, 1);
+    if (e) return e;
+    return srtp_protect_queue(SIB_GCM, b->dev, 0, &a, hip_stream, sync);
+}
+LC3_Error lc3plus_dec_batch_srtp_gcm_protect(lc3plus_dec_batch* b, int64_t max_packets, const int64_t* n_packets,
+    const int32_t* pkt_route, const int64_t* pkt_offset, const int32_t* pkt_size, const uint8_t* pkt_status,
+    const void* wire, int64_t wire_capacity, int header_room, int payload_room,
+    int n_routes, const int32_t* ctx, const int32_t* roc, const int32_t* seq_base, const int32_t* next_seq,
+    void* dst, int64_t dst_capacity, int64_t dst_stride,
+    int64_t* out_offset, int32_t* out_size, uint8_t* out_status, int32_t* next_roc, void* hip_stream, int sync)
+{
+    if (!b) return LC3_NULL_ERROR;
+    const srtp_protect_args a = {max_packets, n_packets, pkt_route, pkt_offset, pkt_size, pkt_status, wire, wire_capacity, header_room, payload_room, n_routes, ctx,
+                                 roc, seq_base, next_seq, dst, dst_capacity, dst_stride, LC3G_TAG_BYTES, out_offset, out_size, out_status, next_roc};
+    const LC3_Error e = srtp_protect_check(&a, 1);
+    if (e) return e;
+    return srtp_protect_queue(SIB_GCM, b->dev, 1, &a, hip_stream, sync);
+}
+LC3_Error lc3plus_plan_srtp_gcm_unprotect(int64_t n_items,
+    void* ring, int64_t ring_capacity, const int64_t* dg_offsets, const int32_t* dg_sizes,
+    int n_ssrc, const int32_t* ssrc_key, const int32_t* ctx, const int32_t* state_in, int32_t* state_out,
+    int32_t* sizes_out, uint8_t* status, int64_t* index, int32_t* stats)
+{
+    const srtp_unprotect_args a = {n_items, ring, ring_capacity, dg_offsets, dg_sizes, n_ssrc, ssrc_key, ctx, state_in, state_out, LC3G_TAG_BYTES, sizes_out, status, index,
+                                   stats};
+    const LC3_Error e = srtp_unprotect_check(&a, 1);
+    if (e) return e;
+    return srtp_unprotect_plan(&a, 1);
+}
+LC3_Error lc3plus_dec_batch_srtp_gcm_unprotect(lc3plus_dec_batch* b, int64_t n_items,
+    void* ring, int64_t ring_capacity, const int64_t* dg_offsets, const int32_t* dg_sizes,
+    int n_ssrc, const int32_t* ssrc_key, const int32_t* ctx, const int32_t* state_in, int32_t* state_out,
+    int32_t* sizes_out, uint8_t* status, int64_t* index, int32_t* stats,
+    void* workspace, int64_t workspace_bytes, void* hip_stream, int sync)
+{
+    if (!b) return LC3_NULL_ERROR;
+    const srtp_unprotect_args a = {n_items, ring, ring_capacity, dg_offsets, dg_sizes, n_ssrc, ssrc_key, ctx, state_in, state_out, LC3G_TAG_BYTES, sizes_out, status, index,
+                                   stats};
+    if (!workspace) return LC3_NULL_ERROR;
+    const LC3_Error e = srtp_unprotect_check(&a, 1);
+    if (e) return e;
+    return srtp_unprotect_queue(SIB_GCM, b, &a, workspace, workspace_bytes, hip_stream, sync);
 }
 LC3_Error lc3plus_dec_batch_set_input_ready(lc3plus_dec_batch* b, int ready)
 {

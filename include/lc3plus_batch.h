@@ -938,8 +938,8 @@ LC3_Error lc3plus_plan_rtcp_stats(int64_t n_items,
  * RFC 3711 with its default transform, AES_CM_128_HMAC_SHA1_80, and the _32 variant: AES-128 in counter mode over every payload byte, HMAC-SHA1 over every
  * packet, the tag's length (tag_len: 10 or 4 bytes) a parameter.  lc3plus_*_batch_srtp_protect stands behind the stamp and lc3plus_dec_batch_srtp_unprotect in
  * front of the parse, so that encode_packed -> egress -> stamp -> protect and datagrams -> unprotect -> parse -> probe -> ingest run on one HIP stream with no
- * host wait.  NOT HANDLED: a key derivation rate other than 0, the MKI (master key identifier), SRTCP, the AEAD suites of RFC 7714, header-extension
- * encryption (RFC 6904) and re-keying (a new master key is a new context, made and uploaded by the caller between calls).
+ * host wait.  The AEAD suites of RFC 7714 are the block "Secure RTP, AEAD" below.  NOT HANDLED: a key derivation rate other than 0, the MKI (master key
+ * identifier), SRTCP, header-extension encryption (RFC 6904) and re-keying (a new master key is a new context, made and uploaded by the caller between calls).
  *
  * THE CONTEXT, host only.  lc3plus_srtp_make_context derives the session keys from a master key (16 bytes) and a master salt (14 bytes) by RFC 3711 4.3.1 with
  * key derivation rate 0 - the AES-CM keystream under the master key from the IV (master_salt ^ label << 48) << 16: label 0 the cipher key (16 bytes), label 1
@@ -1079,6 +1079,76 @@ int64_t lc3plus_srtp_workspace_bytes(int64_t n_items, int n_ssrc);
 LC3_Error lc3plus_plan_srtp_unprotect(int64_t n_items,
     void* ring, int64_t ring_capacity, const int64_t* dg_offsets, const int32_t* dg_sizes,
     int n_ssrc, const int32_t* ssrc_key, const int32_t* ctx, const int32_t* state_in, int32_t* state_out, int tag_len,
+    int32_t* sizes_out, uint8_t* status, int64_t* index, int32_t* stats);
+
+/* ---- Secure RTP, AEAD: the same calls with AES-GCM ---------------------------------------------------------------------------------------------------------------
+ * RFC 7714 with its two suites, AEAD_AES_128_GCM and AEAD_AES_256_GCM: AES in Galois/Counter mode (NIST SP 800-38D) over every payload byte with the header as
+ * associated data and a tag of LC3PLUS_SRTP_GCM_TAG_BYTES (16) bytes; the key's size, 16 or 32 bytes, belongs to the context, so routes and sources of both
+ * suites stand side by side in one call.  The calls are those of the block "Secure RTP" above without tag_len, and EVERYTHING NOT SAID HERE IS THAT BLOCK'S
+ * RULE WORD FOR WORD with the tag length 16: the packet list, wire, header_room and payload_room, dst and dst_stride, roc, seq_base, next_seq and next_roc and
+ * the caller's condition on them, LC3PLUS_SRTP_PROTECTED ... _OVERFLOW; the datagram list, the state block of LC3PLUS_SRTP_STATE_WORDS words, the checks 1 to 4
+ * and 6 and LC3PLUS_SRTP_OK ... _AUTH (_SHORT is size < 12 + 16), the stats words, the workspace of lc3plus_srtp_workspace_bytes; the state after the call;
+ * that the call is stateless inside itself; that a refused datagram keeps every byte; that state_out may be state_in; and the refusals and their order, less
+ * that of tag_len.  NOT HANDLED: SRTCP, the MKI, header-extension encryption (RFC 6904), key derivation rates other than 0, re-keying, and the variants with
+ * an 8-byte tag that never reached the RFC.
+ *
+ * THE CONTEXT, host only.  lc3plus_srtp_gcm_make_context derives the session key and salt from a master key (key_bytes: 16 or 32) and a master salt (12 bytes)
+ * by RFC 7714 11: the key derivation of RFC 3711 4.3.1 with key derivation rate 0, the master salt followed by two zero bytes in the 14-byte salt's place,
+ * the PRF AES-128-CM for a 16-byte master key and AES-256-CM (RFC 6188) for a 32-byte one; label 0 gives the session key (key_bytes bytes), label 2 the session
+ * salt (12 bytes), and there is no authentication key.  LC3PLUS_SRTP_GCM_CTX_WORDS (128) words, as the device reads them:
+ *   0 .. 59    the round key words of the session key (FIPS-197 5.2), each big-endian: 44 for a 16-byte key (the rest zero), 60 for a 32-byte key
+ *   60         the number of rounds, 10 or 14
+ *   61 .. 63   the session salt as three big-endian words
+ *   64 .. 127  the GHASH table: the sixteen multiples e(x) * H of H = AES_k(0^128), entry e at words 64 + 4 e .. 64 + 4 e + 3, big-endian, a nibble's highest
+ *              bit the lowest power (entry 8 is H, entry 4 is H x, entry 2 H x^2, entry 1 H x^3)
+ * The caller copies contexts to device memory ([n][128] words, one per route or per source).  The library keeps no copy of any key and wipes its working
+ * copies.  LC3_NULL_ERROR for a NULL argument, then LC3_ERROR for a key_bytes other than 16 or 32.
+ *
+ * THE TRANSFORM (RFC 7714 8.1 and 9).  For a packet with header length h - 12 on the send side, with CSRCs and extension on the receive side - and rollover
+ * counter v (ROC_p of PROTECT, the estimate of check 3 of UNPROTECT): the 12-byte IV is (00 00 || SSRC || v || SEQ) XOR the session salt, SSRC and SEQ the
+ * header's own bytes; the associated data is the header's h bytes; the plaintext is everything behind it, the payload_room bytes and any padding included.
+ * Counter blocks are IV || ctr32: ctr = 1 masks the tag, the payload starts at ctr = 2.  The tag is all 16 bytes of GHASH_H(AAD, C) XOR AES_k(IV || 1); it is
+ * appended behind the ciphertext and v is appended nowhere: out_size = L + 16.  ctx is [n_routes][128] or [n_ssrc][128].
+ * Check 5 of UNPROTECT compares all 16 bytes behind the ciphertext with the tag over header and ciphertext before one byte of the ring is changed; check 6
+ * then decrypts [h, size - 16) in place and sizes_out = size - 16.
+ * THE CALLER'S CONDITION: a (key, IV) pair never repeats - no two packets of one key with the same SSRC, v and SEQ - which the caller keeps through roc and
+ * seq_base exactly as it keeps the keystream of the block above from repeating.  With GCM a repeat gives away the authentication key as well as the XOR of two
+ * plaintexts.
+ *
+ * The kernels live in liblc3plus_gcm_hip.so, which this library loads from its own directory on the first GCM protect or unprotect call: where that file is
+ * missing the call returns LC3_ERROR and nothing else changes. */
+/* (the values in parentheses: tests/test_srtp_cpu.py lists the constants of the block above by the pattern "LC3PLUS_SRTP_ name, bare number", and these two are not of it) */
+#define LC3PLUS_SRTP_GCM_CTX_WORDS (128)
+#define LC3PLUS_SRTP_GCM_TAG_BYTES (16)
+LC3_Error lc3plus_srtp_gcm_make_context(const uint8_t* master_key, int key_bytes, const uint8_t* master_salt, int32_t* ctx);
+LC3_Error lc3plus_enc_batch_srtp_gcm_protect(lc3plus_batch* batch, int64_t max_packets, const int64_t* n_packets,
+    const int32_t* pkt_route, const int64_t* pkt_offset, const int32_t* pkt_size, const uint8_t* pkt_status,
+    const void* wire, int64_t wire_capacity, int header_room, int payload_room,
+    int n_routes, const int32_t* ctx, const int32_t* roc, const int32_t* seq_base, const int32_t* next_seq,
+    void* dst, int64_t dst_capacity, int64_t dst_stride,
+    int64_t* out_offset, int32_t* out_size, uint8_t* out_status, int32_t* next_roc, void* hip_stream, int sync);
+LC3_Error lc3plus_dec_batch_srtp_gcm_protect(lc3plus_dec_batch* batch, int64_t max_packets, const int64_t* n_packets,
+    const int32_t* pkt_route, const int64_t* pkt_offset, const int32_t* pkt_size, const uint8_t* pkt_status,
+    const void* wire, int64_t wire_capacity, int header_room, int payload_room,
+    int n_routes, const int32_t* ctx, const int32_t* roc, const int32_t* seq_base, const int32_t* next_seq,
+    void* dst, int64_t dst_capacity, int64_t dst_stride,
+    int64_t* out_offset, int32_t* out_size, uint8_t* out_status, int32_t* next_roc, void* hip_stream, int sync);
+/* the same rule on the host alone, as lc3plus_plan_srtp_protect */
+LC3_Error lc3plus_plan_srtp_gcm_protect(int64_t max_packets, const int64_t* n_packets,
+    const int32_t* pkt_route, const int64_t* pkt_offset, const int32_t* pkt_size, const uint8_t* pkt_status,
+    const void* wire, int64_t wire_capacity, int header_room, int payload_room,
+    int n_routes, const int32_t* ctx, const int32_t* roc, const int32_t* seq_base, const int32_t* next_seq,
+    void* dst, int64_t dst_capacity, int64_t dst_stride,
+    int64_t* out_offset, int32_t* out_size, uint8_t* out_status, int32_t* next_roc);
+LC3_Error lc3plus_dec_batch_srtp_gcm_unprotect(lc3plus_dec_batch* batch, int64_t n_items,
+    void* ring, int64_t ring_capacity, const int64_t* dg_offsets, const int32_t* dg_sizes,
+    int n_ssrc, const int32_t* ssrc_key, const int32_t* ctx, const int32_t* state_in, int32_t* state_out,
+    int32_t* sizes_out, uint8_t* status, int64_t* index, int32_t* stats,
+    void* workspace, int64_t workspace_bytes, void* hip_stream, int sync);
+/* the same rule on the host alone, as lc3plus_plan_srtp_unprotect */
+LC3_Error lc3plus_plan_srtp_gcm_unprotect(int64_t n_items,
+    void* ring, int64_t ring_capacity, const int64_t* dg_offsets, const int32_t* dg_sizes,
+    int n_ssrc, const int32_t* ssrc_key, const int32_t* ctx, const int32_t* state_in, int32_t* state_out,
     int32_t* sizes_out, uint8_t* status, int64_t* index, int32_t* stats);
 
 /* ---- Sharded batches: one call drives encoders or decoders on several GPUs ------------------------------------------------------------------

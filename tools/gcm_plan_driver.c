@@ -1,0 +1,213 @@
+/* gcm_plan_driver.c -- lc3plus_srtp_gcm_make_context, lc3plus_plan_srtp_gcm_protect, lc3plus_plan_srtp_gcm_unprotect and the refusals of the AES-GCM SRTP calls
+ * in a program of its own, built with lc3_host.c and tools/stub_shim.c under AddressSanitizer + UndefinedBehaviorSanitizer (make -C audio_codec_amd/csrc
+ * gcm_driver; tests/test_gcm_cpu.py runs it as a child process with nothing preloaded).  Every array is a heap block of exactly the size the header names, and
+ * the wire buffer, the destination and the ring are blocks of exactly their capacities, so a read or write one byte too far ends the program.
+ *
+ *   gcm_plan_driver roundtrip SEED N
+ *       N packets of two routes drawn from SEED - route 0 under a 16-byte master key, route 1 under a 32-byte one - laid into a wire buffer back to back at
+ *       every alignment, the first at the buffer's first byte and the last ending at its last; protected into a destination of exactly N slots of the largest
+ *       packet's size; unprotected in place; the payloads compared with what was sent; one tag damaged and the call repeated.  Prints both contexts, the
+ *       protect call's sizes and the unprotect call's outputs as lines of numbers
+ *   gcm_plan_driver refuse
+ *       the refusals in the header's order on a NULL batch, on a zero-filled block in place of a batch and on the host plans; every array is a block of 64 bytes */
+#include <stdint.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+#include "../include/lc3.h"
+#include "../include/lc3plus_batch.h"
+
+static uint32_t lcg_x;
+static uint32_t lcg(void) { lcg_x = (lcg_x * 1103515245u + 12345u) & 0x7FFFFFFFu; return lcg_x >> 8; }
+
+static void* block(size_t n) { void* p = malloc(n ? n : 1); if (!p) exit(3); memset(p, 0x5A, n ? n : 1); return p; }
+#define PRINT(name, a, n, fmt, cast) do { printf("%s", name); for (long long i_ = 0; i_ < (long long)(n); i_++) printf(fmt, (cast)(a)[i_]); printf("\n"); } while (0)
+#define CW LC3PLUS_SRTP_GCM_CTX_WORDS
+#define TAG LC3PLUS_SRTP_GCM_TAG_BYTES
+
+static int roundtrip(char** v)
+{
+    lcg_x = (uint32_t)atoi(v[0]);
+    const int N = atoi(v[1]);
+    if (N < 1 || N > 20000) return 2;                                /* fewer than 2^15 sequence numbers per route */
+    const size_t n = (size_t)N;
+    enum { ROOM = 12, R = 2 };
+    const int key_bytes[R] = {16, 32};
+    int32_t* ctx = block(4 * R * CW);
+    for (int r = 0; r < R; r++) {
+        uint8_t* key = block((size_t)key_bytes[r]);                  /* exactly the key's size: the other suite's read would run past it */
+        uint8_t* salt = block(12);
+        for (int k = 0; k < key_bytes[r]; k++) key[k] = (uint8_t)lcg();
+        for (int k = 0; k < 12; k++) salt[k] = (uint8_t)lcg();
+        if (lc3plus_srtp_gcm_make_context(key, key_bytes[r], salt, ctx + r * CW)) return 1;
+        free(key); free(salt);
+    }
+    PRINT("ctx", ctx, R * CW, " %u", uint32_t);
+    int32_t* route = block(4 * n); int64_t* off = block(8 * n); int32_t* size = block(4 * n); uint8_t* pst = block(n);
+    int32_t* pay = block(4 * n);
+    size_t total = 0, stride = 0;
+    for (int p = 0; p < N; p++) {
+        pay[p] = (int32_t)(lcg() % 7 == 0 ? lcg() % 420 : lcg() % 50);
+        route[p] = (int32_t)(lcg() % R); off[p] = (int64_t)total; size[p] = ROOM + pay[p]; pst[p] = LC3PLUS_RTP_STAMPED;
+        total += (size_t)size[p];
+        if ((size_t)size[p] + TAG > stride) stride = (size_t)size[p] + TAG;
+    }
+    uint8_t* wire = block(total);
+    const uint32_t ssrc[R] = {0x80000001u, 0x00000011u};
+    int32_t roc[R] = {3, (int32_t)0xFFFFFFFFu}, seq_base[R] = {65530, 7}, next_seq[R], next_roc[R];
+    uint32_t nxt[R] = {65530u, 7u};
+    for (int p = 0; p < N; p++) {
+        uint8_t* h = wire + off[p];
+        const int r = route[p];
+        const uint32_t q = nxt[r]++ & 0xFFFFu;
+        h[0] = 0x80; h[1] = 96; h[2] = (uint8_t)(q >> 8); h[3] = (uint8_t)q; h[4] = h[5] = h[6] = 0; h[7] = (uint8_t)p;
+        h[8] = (uint8_t)(ssrc[r] >> 24); h[9] = (uint8_t)(ssrc[r] >> 16); h[10] = (uint8_t)(ssrc[r] >> 8); h[11] = (uint8_t)ssrc[r];
+        for (int k = 0; k < pay[p]; k++) h[12 + k] = (uint8_t)lcg();
+    }
+    for (int r = 0; r < R; r++) next_seq[r] = (int32_t)nxt[r];
+    uint8_t* dst = block(n * stride);
+    int64_t count = N;
+    int64_t* o_off = block(8 * n); int32_t* o_size = block(4 * n); uint8_t* o_st = block(n);
+    LC3_Error e = lc3plus_plan_srtp_gcm_protect(N, &count, route, off, size, pst, wire, (int64_t)total, ROOM, 0, R, ctx, roc, seq_base, next_seq, dst,
+                                                (int64_t)(n * stride), (int64_t)stride, o_off, o_size, o_st, next_roc);
+    printf("rc %d\n", (int)e);
+    if (e) return 1;
+    for (int p = 0; p < N; p++) if (o_st[p] != LC3PLUS_SRTP_PROTECTED || o_size[p] != size[p] + TAG || o_off[p] != (int64_t)p * (int64_t)stride) return 1;
+    PRINT("out_size", o_size, N, " %d", int); PRINT("next_roc", next_roc, R, " %u", uint32_t);
+    /* the receiver: the sources in ascending SSRC order, route 1 first */
+    int32_t* key2 = block(4 * R); int32_t* ctx2 = block(4 * R * CW); int32_t* st_in = block(4 * R * LC3PLUS_SRTP_STATE_WORDS);
+    int32_t* st_out = block(4 * R * LC3PLUS_SRTP_STATE_WORDS);
+    key2[0] = (int32_t)ssrc[1]; key2[1] = (int32_t)ssrc[0];
+    memcpy(ctx2, ctx + CW, 4 * CW); memcpy(ctx2 + CW, ctx, 4 * CW);
+    memset(st_in, 0, 4 * R * LC3PLUS_SRTP_STATE_WORDS);
+    st_in[LC3PLUS_SRTP_ROC] = roc[1]; st_in[LC3PLUS_SRTP_STATE_WORDS + LC3PLUS_SRTP_ROC] = roc[0];
+    uint8_t* keep = block(n * stride);
+    memcpy(keep, dst, n * stride);
+    int32_t* u_size = block(4 * n); uint8_t* u_st = block(n); int64_t* u_idx = block(8 * n); int32_t* u_stats = block(4 * LC3PLUS_SRTP_STATS_WORDS);
+    e = lc3plus_plan_srtp_gcm_unprotect(N, dst, (int64_t)(n * stride), o_off, o_size, R, key2, ctx2, st_in, st_out, u_size, u_st, u_idx, u_stats);
+    printf("rc %d\n", (int)e);
+    if (e) return 1;
+    for (int p = 0; p < N; p++) {
+        if (u_st[p] != LC3PLUS_SRTP_OK || u_size[p] != size[p]) { printf("item %d: status %d size %d\n", p, u_st[p], u_size[p]); return 1; }
+        if (memcmp(dst + o_off[p], wire + off[p], (size_t)size[p])) { printf("item %d: the plaintext did not come back\n", p); return 1; }
+        if (pay[p] > 8 && !memcmp(keep + o_off[p] + ROOM, wire + off[p] + ROOM, (size_t)pay[p])) { printf("item %d was not encrypted\n", p); return 1; }
+    }
+    PRINT("state", st_out, R * LC3PLUS_SRTP_STATE_WORDS, " %u", uint32_t); PRINT("index", u_idx, N, " %lld", long long); PRINT("stats", u_stats, LC3PLUS_SRTP_STATS_WORDS, " %d", int);
+    /* once more with every optional output NULL, in place, and one tag damaged: that item alone fails and keeps its bytes */
+    memcpy(dst, keep, n * stride);
+    const int hit = (int)(lcg() % (uint32_t)N);
+    dst[(size_t)o_off[hit] + (size_t)o_size[hit] - 1] ^= 0x40;
+    keep[(size_t)o_off[hit] + (size_t)o_size[hit] - 1] ^= 0x40;
+    e = lc3plus_plan_srtp_gcm_unprotect(N, dst, (int64_t)(n * stride), o_off, o_size, R, key2, ctx2, st_in, st_in, u_size, NULL, NULL, NULL);
+    if (e) return 1;
+    for (int p = 0; p < N; p++) if ((u_size[p] == 0) != (p == hit)) { printf("damaged %d: item %d has size %d\n", hit, p, u_size[p]); return 1; }
+    if (memcmp(dst + o_off[hit], keep + o_off[hit], (size_t)o_size[hit])) { printf("the refused item was changed\n"); return 1; }
+    printf("damaged ok\n");
+    free(ctx); free(route); free(off); free(size); free(pst); free(pay); free(wire); free(dst); free(o_off); free(o_size); free(o_st); free(key2); free(ctx2);
+    free(st_in); free(st_out); free(keep); free(u_size); free(u_st); free(u_idx); free(u_stats);
+    return 0;
+}
+
+#define WANT(x, code) do { const LC3_Error e_ = (x); if (e_ != (code)) { printf("%s: %d, not %d\n", #x, (int)e_, (int)(code)); return 1; } } while (0)
+static int refuse(void)
+{
+    uint8_t* fake = calloc(1, 4096);                                 /* stands in for a batch: no refusal reads or writes it */
+    int32_t* a = calloc(1, 64);
+    int32_t* d = calloc(1, 64);                                      /* the destination: a block of its own, it may not intersect the wire buffer */
+    if (!fake || !a || !d) return 3;
+    lc3plus_batch* be = (lc3plus_batch*)fake;
+    lc3plus_dec_batch* bd = (lc3plus_dec_batch*)fake;
+    uint8_t* a8 = (uint8_t*)a;
+    int64_t* a64 = (int64_t*)a;
+    WANT(lc3plus_srtp_gcm_make_context(NULL, 16, a8, a), LC3_NULL_ERROR);
+    WANT(lc3plus_srtp_gcm_make_context(a8, 32, NULL, a), LC3_NULL_ERROR);
+    WANT(lc3plus_srtp_gcm_make_context(a8, 16, a8, NULL), LC3_NULL_ERROR);
+    WANT(lc3plus_srtp_gcm_make_context(NULL, 24, a8, a), LC3_NULL_ERROR);                              /* NULL first */
+    WANT(lc3plus_srtp_gcm_make_context(a8, 24, a8, a), LC3_ERROR);
+    WANT(lc3plus_srtp_gcm_make_context(a8, 0, a8, a), LC3_ERROR);
+    /* protect: (batch, max_packets, n_packets, route, offset, size, status, wire, wire_capacity, header_room, payload_room, n_routes, ctx, roc, seq_base, next_seq,
+     * dst, dst_capacity, dst_stride, out_offset, out_size, out_status, next_roc, stream, sync) */
+#define PE(bb, ...) lc3plus_enc_batch_srtp_gcm_protect(bb, __VA_ARGS__, NULL, 1)
+#define PD(bb, ...) lc3plus_dec_batch_srtp_gcm_protect(bb, __VA_ARGS__, NULL, 1)
+#define PP(...) lc3plus_plan_srtp_gcm_protect(__VA_ARGS__)
+#define GOOD 1, a64, a, a64, a, a8, a, 64, 12, 0, 1, a, a, a, a, d, 64, 32, a64, a, a8, a
+    WANT(PE(NULL, GOOD), LC3_NULL_ERROR);
+    WANT(PD(NULL, GOOD), LC3_NULL_ERROR);
+    WANT(PE(NULL, 0, NULL, a, a64, a, a8, a, 64, 12, 0, 1, a, a, a, a, d, 64, 32, a64, a, a8, a), LC3_NULL_ERROR);
+    WANT(PE(be, 1, NULL, a, a64, a, a8, a, 64, 12, 0, 1, a, a, a, a, d, 64, 32, a64, a, a8, a), LC3_NULL_ERROR);
+    WANT(PE(be, 1, a64, NULL, a64, a, a8, a, 64, 12, 0, 1, a, a, a, a, d, 64, 32, a64, a, a8, a), LC3_NULL_ERROR);
+    WANT(PE(be, 1, a64, a, NULL, a, a8, a, 64, 12, 0, 1, a, a, a, a, d, 64, 32, a64, a, a8, a), LC3_NULL_ERROR);
+    WANT(PE(be, 1, a64, a, a64, NULL, a8, a, 64, 12, 0, 1, a, a, a, a, d, 64, 32, a64, a, a8, a), LC3_NULL_ERROR);
+    WANT(PE(be, 1, a64, a, a64, a, NULL, a, 64, 12, 0, 1, a, a, a, a, d, 64, 32, a64, a, a8, a), LC3_NULL_ERROR);
+    WANT(PE(be, 1, a64, a, a64, a, a8, NULL, 64, 12, 0, 1, a, a, a, a, d, 64, 32, a64, a, a8, a), LC3_NULL_ERROR);
+    WANT(PE(be, 1, a64, a, a64, a, a8, a, 64, 12, 0, 1, NULL, a, a, a, d, 64, 32, a64, a, a8, a), LC3_NULL_ERROR);
+    WANT(PE(be, 1, a64, a, a64, a, a8, a, 64, 12, 0, 1, a, NULL, a, a, d, 64, 32, a64, a, a8, a), LC3_NULL_ERROR);
+    WANT(PE(be, 1, a64, a, a64, a, a8, a, 64, 12, 0, 1, a, a, NULL, a, d, 64, 32, a64, a, a8, a), LC3_NULL_ERROR);
+    WANT(PE(be, 1, a64, a, a64, a, a8, a, 64, 12, 0, 1, a, a, a, a, NULL, 64, 32, a64, a, a8, a), LC3_NULL_ERROR);
+    WANT(PE(be, 1, a64, a, a64, a, a8, a, 64, 12, 0, 1, a, a, a, a, d, 64, 32, NULL, a, a8, a), LC3_NULL_ERROR);
+    WANT(PE(be, 1, a64, a, a64, a, a8, a, 64, 12, 0, 1, a, a, a, a, d, 64, 32, a64, NULL, a8, a), LC3_NULL_ERROR);
+    WANT(PE(be, 1, a64, a, a64, a, a8, a, 64, 12, 0, 1, a, a, a, a, d, 64, 32, a64, a, NULL, a), LC3_NULL_ERROR);
+    WANT(PE(be, 1, a64, a, a64, a, a8, a, 64, 12, 0, 1, a, a, a, NULL, d, 64, 32, a64, a, a8, a), LC3_NULL_ERROR);         /* next_roc needs next_seq */
+    WANT(PD(bd, 0, a64, a, a64, a, a8, a, 64, 12, 0, 1, a, a, a, NULL, d, 64, 32, a64, a, a8, a), LC3_NULL_ERROR);         /* NULL first */
+    WANT(PE(be, 0, a64, a, a64, a, a8, a, 64, 12, 0, 1, a, a, a, a, d, 64, 32, a64, a, a8, a), LC3_ERROR);
+    WANT(PE(be, 1LL << 29, a64, a, a64, a, a8, a, 64, 12, 0, 1, a, a, a, a, d, 64, 32, a64, a, a8, a), LC3_ERROR);
+    WANT(PE(be, 1, a64, a, a64, a, a8, a, -1, 12, 0, 1, a, a, a, a, d, 64, 32, a64, a, a8, a), LC3_ERROR);
+    WANT(PE(be, 1, a64, a, a64, a, a8, a, 64, 12, -1, 1, a, a, a, a, d, 64, 32, a64, a, a8, a), LC3_ERROR);
+    WANT(PE(be, 1, a64, a, a64, a, a8, a, 64, 11, 0, 1, a, a, a, a, d, 64, 32, a64, a, a8, a), LC3_ERROR);
+    WANT(PE(be, 1, a64, a, a64, a, a8, a, 64, 14, 3, 1, a, a, a, a, d, 64, 32, a64, a, a8, a), LC3_ERROR);
+    WANT(PE(be, 1, a64, a, a64, a, a8, a, 64, 12, 0, 0, a, a, a, a, d, 64, 32, a64, a, a8, a), LC3_ERROR);
+    WANT(PE(be, 1, a64, a, a64, a, a8, a, 64, 12, 0, 1, a, a, a, a, d, -1, 32, a64, a, a8, a), LC3_ERROR);
+    WANT(PE(be, 1, a64, a, a64, a, a8, a, 64, 12, 0, 1, a, a, a, a, d, 64, 0, a64, a, a8, a), LC3_ERROR);
+    WANT(PE(be, 1, a64, a, a64, a, a8, a, 64, 12, 0, 1, a, a, a, a, d, 64, (1LL << 30) + 1, a64, a, a8, a), LC3_ERROR);
+    WANT(PE(be, 1, a64, a, a64, a, a8, a, 64, 12, 0, 1, a, a, a, a, a8 + 32, 32, 32, a64, a, a8, a), LC3_ERROR);           /* dst inside the wire buffer */
+    WANT(PD(bd, 1, a64, a, a64, a, a8, a8 + 32, 32, 12, 0, 1, a, a, a, a, a, 33, 32, a64, a, a8, a), LC3_ERROR);            /* dst ends inside it */
+    WANT(PE(be, GOOD), LC3_ERROR);                                    /* every check passed: no device behind the stub */
+    WANT(PD(bd, GOOD), LC3_ERROR);
+    WANT(PP(1, NULL, a, a64, a, a8, a, 64, 12, 0, 1, a, a, a, a, d, 64, 32, a64, a, a8, a), LC3_NULL_ERROR);
+    WANT(PP(1, a64, a, a64, a, a8, a, 64, 12, 0, 1, a, a, a, NULL, d, 64, 32, a64, a, a8, a), LC3_NULL_ERROR);
+    WANT(PP(0, a64, a, a64, a, a8, a, 64, 12, 0, 1, a, a, a, a, d, 64, 32, a64, a, a8, a), LC3_ERROR);
+    WANT(PP(1, a64, a, a64, a, a8, a, 64, 12, 0, 1, a, a, a, a, a8 + 8, 64, 32, a64, a, a8, a), LC3_ERROR);
+    /* unprotect: (batch, n_items, ring, ring_capacity, dg_offsets, dg_sizes, n_ssrc, ssrc_key, ctx, state_in, state_out, sizes_out, status, index, stats,
+     * workspace, workspace_bytes, stream, sync) */
+    const int64_t W = lc3plus_srtp_workspace_bytes(1, 1);
+    if (W <= 0) return 1;
+#define UN(bb, n, rg, rc, of, sz, ns, ky, cx, si, so, zo, w, wb) lc3plus_dec_batch_srtp_gcm_unprotect(bb, n, rg, rc, of, sz, ns, ky, cx, si, so, zo, NULL, NULL, NULL, w, wb, NULL, 1)
+    WANT(UN(NULL, 1, a, 64, a64, a, 1, a, a, a, a, a, d, W), LC3_NULL_ERROR);
+    WANT(UN(NULL, 0, NULL, 64, a64, a, 0, a, a, a, a, a, NULL, 0), LC3_NULL_ERROR);
+    WANT(UN(bd, 1, a, 64, a64, a, 1, a, a, a, a, a, NULL, W), LC3_NULL_ERROR);
+    WANT(UN(bd, 1, NULL, 64, a64, a, 1, a, a, a, a, a, d, W), LC3_NULL_ERROR);
+    WANT(UN(bd, 1, a, 64, NULL, a, 1, a, a, a, a, a, d, W), LC3_NULL_ERROR);
+    WANT(UN(bd, 1, a, 64, a64, NULL, 1, a, a, a, a, a, d, W), LC3_NULL_ERROR);
+    WANT(UN(bd, 1, a, 64, a64, a, 1, NULL, a, a, a, a, d, W), LC3_NULL_ERROR);
+    WANT(UN(bd, 1, a, 64, a64, a, 1, a, NULL, a, a, a, d, W), LC3_NULL_ERROR);
+    WANT(UN(bd, 1, a, 64, a64, a, 1, a, a, NULL, a, a, d, W), LC3_NULL_ERROR);
+    WANT(UN(bd, 1, a, 64, a64, a, 1, a, a, a, NULL, a, d, W), LC3_NULL_ERROR);
+    WANT(UN(bd, 1, a, 64, a64, a, 1, a, a, a, a, NULL, d, W), LC3_NULL_ERROR);
+    WANT(UN(bd, 0, a, 64, a64, a, 0, a, a, a, NULL, a, d, 0), LC3_NULL_ERROR);                         /* NULL first */
+    WANT(UN(bd, 0, a, 64, a64, a, 1, a, a, a, a, a, d, W), LC3_ERROR);
+    WANT(UN(bd, 1LL << 29, a, 64, a64, a, 1, a, a, a, a, a, d, INT64_MAX), LC3_ERROR);
+    WANT(UN(bd, 1, a, -1, a64, a, 1, a, a, a, a, a, d, W), LC3_ERROR);
+    WANT(UN(bd, 1, a, 64, a64, a, 0, a, a, a, a, a, d, W), LC3_ERROR);
+    WANT(UN(bd, 1, a, 64, a64, a, 1, a, a, a, a, a, d, W - 1), LC3_ERROR);
+    WANT(UN(bd, 1, a, 64, a64, a, 1, a, a, a, a, a, d, W), LC3_ERROR);                                 /* every check passed: no device behind the stub */
+#define UP(n, rg, of, ns, so, zo) lc3plus_plan_srtp_gcm_unprotect(n, rg, 64, of, a, ns, a, a, a, so, zo, NULL, NULL, NULL)
+    WANT(UP(1, NULL, a64, 1, a, a), LC3_NULL_ERROR);
+    WANT(UP(1, a, NULL, 1, a, a), LC3_NULL_ERROR);
+    WANT(UP(1, a, a64, 1, NULL, a), LC3_NULL_ERROR);
+    WANT(UP(1, a, a64, 1, a, NULL), LC3_NULL_ERROR);
+    WANT(UP(0, a, a64, 1, a, a), LC3_ERROR);
+    WANT(UP(1, a, a64, 0, a, a), LC3_ERROR);
+    for (int k = 0; k < 4096; k++) if (fake[k]) { printf("the batch was written at byte %d\n", k); return 1; }
+    for (int k = 0; k < 64; k++) if (a8[k] || ((uint8_t*)d)[k]) { printf("an array was written at byte %d\n", k); return 1; }
+    free(fake); free(a); free(d);
+    printf("refusals ok\n");
+    return 0;
+}
+
+int main(int argc, char** argv)
+{
+    if (argc == 4 && !strcmp(argv[1], "roundtrip")) return roundtrip(argv + 2);
+    if (argc == 2 && !strcmp(argv[1], "refuse")) return refuse();
+    fprintf(stderr, "usage: gcm_plan_driver roundtrip SEED N | refuse\n");
+    return 2;
+}
