@@ -5,6 +5,7 @@ import of a symbol fails loudly -- there is no Python or CPU fallback path."""
 import contextlib
 import ctypes as C
 import os
+import types
 
 import numpy as np
 
@@ -828,20 +829,25 @@ def srtp_workspace_bytes(n_items, n_ssrc):
     return int(load_library().lc3plus_srtp_workspace_bytes(int(n_items), int(n_ssrc)))
 
 
-def plan_srtp_protect(pkt_route, pkt_offset, pkt_size, pkt_status, wire, ctx, roc, seq_base, dst, dst_stride, tag_len=10, header_room=12, payload_room=0,
-                      next_seq=None, n_packets=None, wire_capacity=None, dst_capacity=None, _gcm=False):
-    """The rule of Batch.srtp_protect_device / DecBatch.srtp_protect_device on the host (lc3plus_plan_srtp_protect, no device needed): the stamp's view of the
-    egress's packet list pkt_route, pkt_offset (int64), pkt_size, pkt_status (uint8) [max_packets] (n_packets of it: all by default), the stamped wire buffer
-    (uint8; wire_capacity bytes of it), per route ctx [n_routes, SRTP_CTX_WORDS], roc, seq_base and optionally next_seq [n_routes]; dst: the destination's
-    contents before the call (uint8; dst_capacity bytes of it) -> dict of dst (the buffer after the call), out_offset (int64), out_size, out_status (uint8)
-    [max_packets] (zero behind n_packets) and next_roc [n_routes] (None without next_seq).  LC3Error for arguments the C call refuses."""
+# A Secure RTP suite as the calls below take it: the infix of its C symbols, the words of a context, and whether the C calls take tag_len (the AEAD suites
+# have one tag length)
+_SRTP_HMAC = types.SimpleNamespace(infix="_srtp", ctx_words=SRTP_CTX_WORDS, has_tag_len=True)
+_SRTP_GCM = types.SimpleNamespace(infix="_srtp_gcm", ctx_words=SRTP_GCM_CTX_WORDS, has_tag_len=False)
+
+
+_ptr = lambda a: (a if a.size else np.zeros(8, np.uint8)).ctypes.data if a is not None else None      # a host array for a C call; None: NULL
+_dptr = lambda x: C.c_void_p(x) if x else None                                                           # a device pointer for a C call; 0 and None: NULL
+
+
+def _plan_srtp_protect(suite, pkt_route, pkt_offset, pkt_size, pkt_status, wire, ctx, roc, seq_base, dst, dst_stride, tag_len, header_room, payload_room, next_seq,
+                       n_packets, wire_capacity, dst_capacity):
     route = np.ascontiguousarray(pkt_route, dtype=np.int32).reshape(-1)
     m = route.size
     off, size = np.ascontiguousarray(pkt_offset, dtype=np.int64).reshape(-1), np.ascontiguousarray(pkt_size, dtype=np.int32).reshape(-1)
     pst = np.ascontiguousarray(pkt_status, dtype=np.uint8).reshape(-1)
     if not (off.size == size.size == pst.size == m):
         raise ValueError("the list arrays hold one entry per packet")
-    ctx = np.ascontiguousarray(_u32(ctx)).reshape(-1, SRTP_GCM_CTX_WORDS if _gcm else SRTP_CTX_WORDS)
+    ctx = np.ascontiguousarray(_u32(ctx)).reshape(-1, suite.ctx_words)
     R = ctx.shape[0]
     roc, seq_base = _u32(roc), _u32(seq_base)
     next_seq = _u32(next_seq) if next_seq is not None else None
@@ -851,35 +857,52 @@ def plan_srtp_protect(pkt_route, pkt_offset, pkt_size, pkt_status, wire, ctx, ro
     dst = np.array(dst, dtype=np.uint8).reshape(-1)                   # a copy: the call's destination starts with these contents
     count = np.array([m if n_packets is None else int(n_packets)], np.int64)
     outs = [np.zeros(m, np.int64), np.zeros(m, np.int32), np.zeros(m, np.uint8), np.zeros(R, np.int32) if next_seq is not None else None]
-    pad = np.zeros(8, np.uint8)
-    ptr = lambda a: (a if a.size else pad).ctypes.data if a is not None else None
-    name = "lc3plus_plan_srtp_gcm_protect" if _gcm else "lc3plus_plan_srtp_protect"
-    rc = getattr(load_library(), name)(m, ptr(count), ptr(route), ptr(off), ptr(size), ptr(pst), ptr(wire),
-                                       wire.size if wire_capacity is None else int(wire_capacity), int(header_room), int(payload_room), R, ptr(ctx),
-                                       ptr(roc), ptr(seq_base), ptr(next_seq), ptr(dst), dst.size if dst_capacity is None else int(dst_capacity),
-                                       int(dst_stride), *([] if _gcm else [int(tag_len)]), *[ptr(a) for a in outs])
+    name = "lc3plus_plan%s_protect" % suite.infix
+    rc = getattr(load_library(), name)(m, _ptr(count), _ptr(route), _ptr(off), _ptr(size), _ptr(pst), _ptr(wire),
+                                       wire.size if wire_capacity is None else int(wire_capacity), int(header_room), int(payload_room), R, _ptr(ctx),
+                                       _ptr(roc), _ptr(seq_base), _ptr(next_seq), _ptr(dst), dst.size if dst_capacity is None else int(dst_capacity),
+                                       int(dst_stride), *([int(tag_len)] if suite.has_tag_len else []), *[_ptr(a) for a in outs])
     if rc:
         raise LC3Error(rc, name)
     return dict(zip(SRTP_PROTECT_OUTPUTS, outs), dst=dst)
 
 
-def _srtp_unprotect_arrays(ring, dg_offsets, dg_sizes, ssrc_key, ctx, state, optional, ctx_words=SRTP_CTX_WORDS):
-    """the arrays of an unprotect call as the C calls take them: (ring - a copy -, dg_offsets, dg_sizes, ssrc_key, ctx, state_in; outputs in
-    SRTP_UNPROTECT_OUTPUTS order, None for NULL)"""
-    ring = np.array(ring, dtype=np.uint8).reshape(-1)                 # a copy: the call decrypts in place
-    dg_offsets = np.ascontiguousarray(dg_offsets, dtype=np.int64).reshape(-1)
-    dg_sizes = np.ascontiguousarray(dg_sizes, dtype=np.int32).reshape(-1)
-    key = _u32(ssrc_key)
-    if dg_offsets.size != dg_sizes.size:
+def plan_srtp_protect(pkt_route, pkt_offset, pkt_size, pkt_status, wire, ctx, roc, seq_base, dst, dst_stride, tag_len=10, header_room=12, payload_room=0,
+                      next_seq=None, n_packets=None, wire_capacity=None, dst_capacity=None):
+    """The rule of Batch.srtp_protect_device / DecBatch.srtp_protect_device on the host (lc3plus_plan_srtp_protect, no device needed): the stamp's view of the
+    egress's packet list pkt_route, pkt_offset (int64), pkt_size, pkt_status (uint8) [max_packets] (n_packets of it: all by default), the stamped wire buffer
+    (uint8; wire_capacity bytes of it), per route ctx [n_routes, SRTP_CTX_WORDS], roc, seq_base and optionally next_seq [n_routes]; dst: the destination's
+    contents before the call (uint8; dst_capacity bytes of it) -> dict of dst (the buffer after the call), out_offset (int64), out_size, out_status (uint8)
+    [max_packets] (zero behind n_packets) and next_roc [n_routes] (None without next_seq).  LC3Error for arguments the C call refuses."""
+    return _plan_srtp_protect(_SRTP_HMAC, pkt_route, pkt_offset, pkt_size, pkt_status, wire, ctx, roc, seq_base, dst, dst_stride, tag_len, header_room, payload_room,
+                              next_seq, n_packets, wire_capacity, dst_capacity)
+
+
+def _srtp_unprotect_arrays(ctx_words, ring, dg_offsets, dg_sizes, ssrc_key, ctx, state, optional, ring_capacity):
+    """the arrays of an unprotect call as the C calls take them, by name (ring: a copy; None for NULL), the list's length n, n_ssrc and the ring's capacity"""
+    a = types.SimpleNamespace(ring=np.array(ring, dtype=np.uint8).reshape(-1), dg_offsets=np.ascontiguousarray(dg_offsets, dtype=np.int64).reshape(-1),
+                              dg_sizes=np.ascontiguousarray(dg_sizes, dtype=np.int32).reshape(-1), ssrc_key=_u32(ssrc_key),
+                              ctx=np.ascontiguousarray(_u32(ctx)).reshape(-1, ctx_words), state_in=np.ascontiguousarray(_u32(state)).reshape(-1, SRTP_STATE_WORDS))
+    a.n, a.n_ssrc, a.capacity = a.dg_offsets.size, a.ssrc_key.size, a.ring.size if ring_capacity is None else int(ring_capacity)
+    if a.n != a.dg_sizes.size:
         raise ValueError("dg_offsets and dg_sizes hold one entry per datagram")
-    ctx = np.ascontiguousarray(_u32(ctx)).reshape(-1, ctx_words)
-    state = np.ascontiguousarray(_u32(state)).reshape(-1, SRTP_STATE_WORDS)
-    if ctx.shape[0] != key.size or state.shape[0] != key.size:
+    if a.ctx.shape[0] != a.n_ssrc or a.state_in.shape[0] != a.n_ssrc:
         raise ValueError("ssrc_key, ctx and state hold one entry per source")
-    n = dg_offsets.size
-    outs = [np.zeros((key.size, SRTP_STATE_WORDS), np.int32), np.zeros(n, np.int32), np.zeros(n, np.uint8) if "status" in optional else None,
-            np.zeros(n, np.int64) if "index" in optional else None, np.zeros(SRTP_STATS_WORDS, np.int32) if "stats" in optional else None]
-    return [ring, dg_offsets, dg_sizes, key, ctx, state], outs
+    a.state_out, a.sizes = np.zeros((a.n_ssrc, SRTP_STATE_WORDS), np.int32), np.zeros(a.n, np.int32)
+    a.status, a.index = np.zeros(a.n, np.uint8) if "status" in optional else None, np.zeros(a.n, np.int64) if "index" in optional else None
+    a.stats = np.zeros(SRTP_STATS_WORDS, np.int32) if "stats" in optional else None
+    a.result = lambda: dict(zip(SRTP_UNPROTECT_OUTPUTS, (a.state_out, a.sizes, a.status, a.index, a.stats)), ring=a.ring)
+    return a
+
+
+def _plan_srtp_unprotect(suite, ring, dg_offsets, dg_sizes, ssrc_key, ctx, state, tag_len, optional, ring_capacity):
+    a = _srtp_unprotect_arrays(suite.ctx_words, ring, dg_offsets, dg_sizes, ssrc_key, ctx, state, optional, ring_capacity)
+    name = "lc3plus_plan%s_unprotect" % suite.infix
+    rc = getattr(load_library(), name)(a.n, _ptr(a.ring), a.capacity, _ptr(a.dg_offsets), _ptr(a.dg_sizes), a.n_ssrc, _ptr(a.ssrc_key), _ptr(a.ctx), _ptr(a.state_in),
+                                       _ptr(a.state_out), *([int(tag_len)] if suite.has_tag_len else []), _ptr(a.sizes), _ptr(a.status), _ptr(a.index), _ptr(a.stats))
+    if rc:
+        raise LC3Error(rc, name)
+    return a.result()
 
 
 def plan_srtp_unprotect(ring, dg_offsets, dg_sizes, ssrc_key, ctx, state, tag_len=10, optional=SRTP_UNPROTECT_OPTIONAL, ring_capacity=None):
@@ -888,15 +911,7 @@ def plan_srtp_unprotect(ring, dg_offsets, dg_sizes, ssrc_key, ctx, state, tag_le
     SRTP_STATE_WORDS] (zeros: a source that has not started) -> dict of ring (the buffer after the call: accepted payloads decrypted), state (the advanced
     state), sizes [n] (rtp_parse's dg_sizes), status (uint8) [n], index (int64) [n] and stats [SRTP_STATS_WORDS]; those of SRTP_UNPROTECT_OPTIONAL not named in
     `optional` are passed as NULL and come back as None.  LC3Error for arguments the C call refuses."""
-    ins, outs = _srtp_unprotect_arrays(ring, dg_offsets, dg_sizes, ssrc_key, ctx, state, optional)
-    pad = np.zeros(8, np.uint8)
-    ptr = lambda a: (a if a.size else pad).ctypes.data if a is not None else None
-    cap = ins[0].size if ring_capacity is None else int(ring_capacity)
-    rc = load_library().lc3plus_plan_srtp_unprotect(ins[1].size, ptr(ins[0]), cap, ptr(ins[1]), ptr(ins[2]), ins[3].size, ptr(ins[3]), ptr(ins[4]), ptr(ins[5]),
-                                                    ptr(outs[0]), int(tag_len), *[ptr(a) for a in outs[1:]])
-    if rc:
-        raise LC3Error(rc, "lc3plus_plan_srtp_unprotect")
-    return dict(zip(SRTP_UNPROTECT_OUTPUTS, outs), ring=ins[0])
+    return _plan_srtp_unprotect(_SRTP_HMAC, ring, dg_offsets, dg_sizes, ssrc_key, ctx, state, tag_len, optional, ring_capacity)
 
 
 def srtp_gcm_make_context(master_key, master_salt):
@@ -918,26 +933,42 @@ def plan_srtp_gcm_protect(pkt_route, pkt_offset, pkt_size, pkt_status, wire, ctx
                           n_packets=None, wire_capacity=None, dst_capacity=None):
     """plan_srtp_protect for the AEAD suites (lc3plus_plan_srtp_gcm_protect): the same arguments without tag_len, ctx [n_routes, SRTP_GCM_CTX_WORDS] -> the same
     dict; a protected packet is SRTP_GCM_TAG_BYTES longer than its RTP packet."""
-    return plan_srtp_protect(pkt_route, pkt_offset, pkt_size, pkt_status, wire, ctx, roc, seq_base, dst, dst_stride, SRTP_GCM_TAG_BYTES, header_room, payload_room,
-                             next_seq, n_packets, wire_capacity, dst_capacity, _gcm=True)
+    return _plan_srtp_protect(_SRTP_GCM, pkt_route, pkt_offset, pkt_size, pkt_status, wire, ctx, roc, seq_base, dst, dst_stride, None, header_room, payload_room,
+                              next_seq, n_packets, wire_capacity, dst_capacity)
 
 
 def plan_srtp_gcm_unprotect(ring, dg_offsets, dg_sizes, ssrc_key, ctx, state, optional=SRTP_UNPROTECT_OPTIONAL, ring_capacity=None):
     """plan_srtp_unprotect for the AEAD suites (lc3plus_plan_srtp_gcm_unprotect): the same arguments without tag_len, ctx [n_ssrc, SRTP_GCM_CTX_WORDS] -> the
     same dict."""
-    ins, outs = _srtp_unprotect_arrays(ring, dg_offsets, dg_sizes, ssrc_key, ctx, state, optional, SRTP_GCM_CTX_WORDS)
-    pad = np.zeros(8, np.uint8)
-    ptr = lambda a: (a if a.size else pad).ctypes.data if a is not None else None
-    cap = ins[0].size if ring_capacity is None else int(ring_capacity)
-    rc = load_library().lc3plus_plan_srtp_gcm_unprotect(ins[1].size, ptr(ins[0]), cap, ptr(ins[1]), ptr(ins[2]), ins[3].size, ptr(ins[3]), ptr(ins[4]), ptr(ins[5]),
-                                                        ptr(outs[0]), *[ptr(a) for a in outs[1:]])
+    return _plan_srtp_unprotect(_SRTP_GCM, ring, dg_offsets, dg_sizes, ssrc_key, ctx, state, None, optional, ring_capacity)
+
+
+def _srtp_protect_device(suite, self, max_packets, d_n_packets_ptr, d_pkt_route_ptr, d_pkt_offset_ptr, d_pkt_size_ptr, d_pkt_status_ptr, d_wire_ptr, wire_capacity,
+                         n_routes, d_ctx_ptr, d_roc_ptr, d_seq_base_ptr, d_dst_ptr, dst_capacity, dst_stride, d_out_offset_ptr, d_out_size_ptr, d_out_status_ptr,
+                         header_room, payload_room, d_next_seq_ptr, d_next_roc_ptr, hip_stream, sync, tag_len=None):
+    """the protect methods of both suites and batch kinds: called with the method's locals()"""
+    p, name = _dptr, suite.infix + "_protect"
+    rc = self._ssf(name)(self.h, int(max_packets), p(d_n_packets_ptr), p(d_pkt_route_ptr), p(d_pkt_offset_ptr), p(d_pkt_size_ptr), p(d_pkt_status_ptr),
+                         p(d_wire_ptr), int(wire_capacity), int(header_room), int(payload_room), int(n_routes), p(d_ctx_ptr), p(d_roc_ptr), p(d_seq_base_ptr),
+                         p(d_next_seq_ptr), p(d_dst_ptr), int(dst_capacity), int(dst_stride), *([int(tag_len)] if suite.has_tag_len else []), p(d_out_offset_ptr),
+                         p(d_out_size_ptr), p(d_out_status_ptr), p(d_next_roc_ptr), p(hip_stream), 1 if sync else 0)
     if rc:
-        raise LC3Error(rc, "lc3plus_plan_srtp_gcm_unprotect")
-    return dict(zip(SRTP_UNPROTECT_OUTPUTS, outs), ring=ins[0])
+        raise LC3Error(rc, self._ss + name)
+
+
+def _srtp_unprotect_device(suite, self, n_items, d_ring_ptr, ring_capacity, d_dg_offsets_ptr, d_dg_sizes_ptr, n_ssrc, d_ssrc_key_ptr, d_ctx_ptr, d_state_in_ptr,
+                           d_state_out_ptr, d_sizes_out_ptr, d_workspace_ptr, workspace_bytes, d_status_ptr, d_index_ptr, d_stats_ptr, hip_stream, sync, tag_len=None):
+    """the unprotect methods of both suites: called with the method's locals()"""
+    p, name = _dptr, "lc3plus_dec_batch%s_unprotect" % suite.infix
+    rc = getattr(self.lib, name)(self.h, int(n_items), p(d_ring_ptr), int(ring_capacity), p(d_dg_offsets_ptr), p(d_dg_sizes_ptr), int(n_ssrc), p(d_ssrc_key_ptr),
+                                 p(d_ctx_ptr), p(d_state_in_ptr), p(d_state_out_ptr), *([int(tag_len)] if suite.has_tag_len else []), p(d_sizes_out_ptr),
+                                 p(d_status_ptr), p(d_index_ptr), p(d_stats_ptr), p(d_workspace_ptr), int(workspace_bytes), p(hip_stream), 1 if sync else 0)
+    if rc:
+        raise LC3Error(rc, name)
 
 
 class _SrtpProtect:
-    """The send side of Secure RTP for both batch kinds (lc3plus_{enc,dec}_batch_srtp_protect; include/lc3plus_batch.h "Secure RTP")."""
+    """The send side of Secure RTP for both batch kinds (lc3plus_{enc,dec}_batch_srtp_protect and _srtp_gcm_protect; include/lc3plus_batch.h "Secure RTP")."""
 
     def srtp_protect_device(self, max_packets, d_n_packets_ptr, d_pkt_route_ptr, d_pkt_offset_ptr, d_pkt_size_ptr, d_pkt_status_ptr, d_wire_ptr, wire_capacity,
                             n_routes, d_ctx_ptr, d_roc_ptr, d_seq_base_ptr, d_dst_ptr, dst_capacity, dst_stride, d_out_offset_ptr, d_out_size_ptr,
@@ -946,14 +977,7 @@ class _SrtpProtect:
         [n_routes, SRTP_CTX_WORDS], roc, seq_base and optionally next_seq -> every stamped packet as an SRTP packet (header, encrypted payload, tag of tag_len
         bytes) at dst + p * dst_stride, out_offset (int64), out_size, out_status (uint8) [max_packets] and the optional next_roc [n_routes].  Stateless: nothing
         of the batch's streams is read or written.  Queued on hip_stream; returns at once unless sync."""
-        def p(x):
-            return C.c_void_p(x) if x else None
-        rc = self._ssf("_srtp_protect")(self.h, int(max_packets), p(d_n_packets_ptr), p(d_pkt_route_ptr), p(d_pkt_offset_ptr), p(d_pkt_size_ptr), p(d_pkt_status_ptr),
-                                        p(d_wire_ptr), int(wire_capacity), int(header_room), int(payload_room), int(n_routes), p(d_ctx_ptr), p(d_roc_ptr),
-                                        p(d_seq_base_ptr), p(d_next_seq_ptr), p(d_dst_ptr), int(dst_capacity), int(dst_stride), int(tag_len), p(d_out_offset_ptr),
-                                        p(d_out_size_ptr), p(d_out_status_ptr), p(d_next_roc_ptr), p(hip_stream), 1 if sync else 0)
-        if rc:
-            raise LC3Error(rc, self._ss + "_srtp_protect")
+        _srtp_protect_device(_SRTP_HMAC, **locals())
 
     def srtp_gcm_protect_device(self, max_packets, d_n_packets_ptr, d_pkt_route_ptr, d_pkt_offset_ptr, d_pkt_size_ptr, d_pkt_status_ptr, d_wire_ptr, wire_capacity,
                                 n_routes, d_ctx_ptr, d_roc_ptr, d_seq_base_ptr, d_dst_ptr, dst_capacity, dst_stride, d_out_offset_ptr, d_out_size_ptr,
@@ -961,14 +985,7 @@ class _SrtpProtect:
         """srtp_protect_device for the AEAD suites (lc3plus_{enc,dec}_batch_srtp_gcm_protect): the same arguments without tag_len, ctx [n_routes,
         SRTP_GCM_CTX_WORDS], routes of 16- and 32-byte keys side by side -> header, AES-GCM ciphertext and a tag of SRTP_GCM_TAG_BYTES bytes at
         dst + p * dst_stride."""
-        def p(x):
-            return C.c_void_p(x) if x else None
-        rc = self._ssf("_srtp_gcm_protect")(self.h, int(max_packets), p(d_n_packets_ptr), p(d_pkt_route_ptr), p(d_pkt_offset_ptr), p(d_pkt_size_ptr),
-                                            p(d_pkt_status_ptr), p(d_wire_ptr), int(wire_capacity), int(header_room), int(payload_room), int(n_routes), p(d_ctx_ptr),
-                                            p(d_roc_ptr), p(d_seq_base_ptr), p(d_next_seq_ptr), p(d_dst_ptr), int(dst_capacity), int(dst_stride), p(d_out_offset_ptr),
-                                            p(d_out_size_ptr), p(d_out_status_ptr), p(d_next_roc_ptr), p(hip_stream), 1 if sync else 0)
-        if rc:
-            raise LC3Error(rc, self._ss + "_srtp_gcm_protect")
+        _srtp_protect_device(_SRTP_GCM, **locals())
 
 
 class _StreamLifecycle:
@@ -1842,6 +1859,18 @@ class DecBatch(_StreamLifecycle, _Egress, _RtpStamp, _SrtpProtect):
                 back(k)
         return dict(zip(RR_OUTPUTS, outs))
 
+    def _srtp_unprotect(self, suite, ring, dg_offsets, dg_sizes, ssrc_key, ctx, state, tag_len, optional, ring_capacity):
+        a = _srtp_unprotect_arrays(suite.ctx_words, ring, dg_offsets, dg_sizes, ssrc_key, ctx, state, optional, ring_capacity)
+        a.work = np.zeros(max(srtp_workspace_bytes(a.n, a.n_ssrc), 8), np.uint8)
+        names = ("ring", "dg_offsets", "dg_sizes", "ssrc_key", "ctx", "state_in", "state_out", "sizes", "status", "index", "stats", "work")
+        with _on_device([getattr(a, k) for k in names]) as (ptrs, back):
+            d = dict(zip(names, ptrs))
+            _srtp_unprotect_device(suite, self, a.n, d["ring"], a.capacity, d["dg_offsets"], d["dg_sizes"], a.n_ssrc, d["ssrc_key"], d["ctx"], d["state_in"],
+                                   d["state_out"], d["sizes"], d["work"], a.work.size, d["status"], d["index"], d["stats"], None, True, tag_len)
+            for k in ("ring", "state_out", "sizes", "status", "index", "stats"):
+                back(names.index(k))
+        return a.result()
+
     def srtp_unprotect_device(self, n_items, d_ring_ptr, ring_capacity, d_dg_offsets_ptr, d_dg_sizes_ptr, n_ssrc, d_ssrc_key_ptr, d_ctx_ptr, d_state_in_ptr,
                               d_state_out_ptr, d_sizes_out_ptr, d_workspace_ptr, workspace_bytes, tag_len=10, d_status_ptr=None, d_index_ptr=None, d_stats_ptr=None,
                               hip_stream=None, sync=False):
@@ -1850,53 +1879,23 @@ class DecBatch(_StreamLifecycle, _Egress, _RtpStamp, _SrtpProtect):
         (they may be one array), a workspace of srtp_workspace_bytes(n_items, n_ssrc) bytes -> the accepted datagrams decrypted in place, sizes_out [n_items]
         (rtp_parse_device's dg_sizes), the advanced state and the optional status (uint8), index (int64) [n_items] and stats [SRTP_STATS_WORDS].  Stateless:
         nothing of the batch's streams is read or written.  Queued on hip_stream; returns at once unless sync."""
-        def p(x):
-            return C.c_void_p(x) if x else None
-        rc = self.lib.lc3plus_dec_batch_srtp_unprotect(self.h, int(n_items), p(d_ring_ptr), int(ring_capacity), p(d_dg_offsets_ptr), p(d_dg_sizes_ptr), int(n_ssrc),
-                                                       p(d_ssrc_key_ptr), p(d_ctx_ptr), p(d_state_in_ptr), p(d_state_out_ptr), int(tag_len), p(d_sizes_out_ptr),
-                                                       p(d_status_ptr), p(d_index_ptr), p(d_stats_ptr), p(d_workspace_ptr), int(workspace_bytes), p(hip_stream),
-                                                       1 if sync else 0)
-        if rc:
-            raise LC3Error(rc, "lc3plus_dec_batch_srtp_unprotect")
+        _srtp_unprotect_device(_SRTP_HMAC, **locals())
 
     def srtp_unprotect(self, ring, dg_offsets, dg_sizes, ssrc_key, ctx, state, tag_len=10, optional=SRTP_UNPROTECT_OPTIONAL, ring_capacity=None):
         """Host convenience: the arrays of plan_srtp_unprotect uploaded, run on the device and downloaded -> the dict plan_srtp_unprotect gives.  Device memory
         through the HIP runtime as in probe(), the workspace too, freed before it returns."""
-        ins, outs = _srtp_unprotect_arrays(ring, dg_offsets, dg_sizes, ssrc_key, ctx, state, optional)
-        n, S = ins[1].size, ins[3].size
-        cap = ins[0].size if ring_capacity is None else int(ring_capacity)
-        work = np.zeros(max(srtp_workspace_bytes(n, S), 8), np.uint8)
-        with _on_device(ins + outs + [work]) as (v, back):
-            self.srtp_unprotect_device(n, v[0], cap, v[1], v[2], S, v[3], v[4], v[5], v[6], v[7], v[11], work.size, tag_len, v[8], v[9], v[10], sync=True)
-            for k in [0] + list(range(6, 11)):
-                back(k)
-        return dict(zip(SRTP_UNPROTECT_OUTPUTS, outs), ring=ins[0])
+        return self._srtp_unprotect(_SRTP_HMAC, ring, dg_offsets, dg_sizes, ssrc_key, ctx, state, tag_len, optional, ring_capacity)
 
     def srtp_gcm_unprotect_device(self, n_items, d_ring_ptr, ring_capacity, d_dg_offsets_ptr, d_dg_sizes_ptr, n_ssrc, d_ssrc_key_ptr, d_ctx_ptr, d_state_in_ptr,
                                   d_state_out_ptr, d_sizes_out_ptr, d_workspace_ptr, workspace_bytes, d_status_ptr=None, d_index_ptr=None, d_stats_ptr=None,
                                   hip_stream=None, sync=False):
         """srtp_unprotect_device for the AEAD suites (lc3plus_dec_batch_srtp_gcm_unprotect): the same arguments without tag_len, ctx [n_ssrc,
         SRTP_GCM_CTX_WORDS], sources of 16- and 32-byte keys side by side; the workspace is srtp_workspace_bytes(n_items, n_ssrc) bytes."""
-        def p(x):
-            return C.c_void_p(x) if x else None
-        rc = self.lib.lc3plus_dec_batch_srtp_gcm_unprotect(self.h, int(n_items), p(d_ring_ptr), int(ring_capacity), p(d_dg_offsets_ptr), p(d_dg_sizes_ptr),
-                                                           int(n_ssrc), p(d_ssrc_key_ptr), p(d_ctx_ptr), p(d_state_in_ptr), p(d_state_out_ptr), p(d_sizes_out_ptr),
-                                                           p(d_status_ptr), p(d_index_ptr), p(d_stats_ptr), p(d_workspace_ptr), int(workspace_bytes), p(hip_stream),
-                                                           1 if sync else 0)
-        if rc:
-            raise LC3Error(rc, "lc3plus_dec_batch_srtp_gcm_unprotect")
+        _srtp_unprotect_device(_SRTP_GCM, **locals())
 
     def srtp_gcm_unprotect(self, ring, dg_offsets, dg_sizes, ssrc_key, ctx, state, optional=SRTP_UNPROTECT_OPTIONAL, ring_capacity=None):
         """Host convenience: the arrays of plan_srtp_gcm_unprotect uploaded, run on the device and downloaded -> the dict plan_srtp_gcm_unprotect gives."""
-        ins, outs = _srtp_unprotect_arrays(ring, dg_offsets, dg_sizes, ssrc_key, ctx, state, optional, SRTP_GCM_CTX_WORDS)
-        n, S = ins[1].size, ins[3].size
-        cap = ins[0].size if ring_capacity is None else int(ring_capacity)
-        work = np.zeros(max(srtp_workspace_bytes(n, S), 8), np.uint8)
-        with _on_device(ins + outs + [work]) as (v, back):
-            self.srtp_gcm_unprotect_device(n, v[0], cap, v[1], v[2], S, v[3], v[4], v[5], v[6], v[7], v[11], work.size, v[8], v[9], v[10], sync=True)
-            for k in [0] + list(range(6, 11)):
-                back(k)
-        return dict(zip(SRTP_UNPROTECT_OUTPUTS, outs), ring=ins[0])
+        return self._srtp_unprotect(_SRTP_GCM, ring, dg_offsets, dg_sizes, ssrc_key, ctx, state, None, optional, ring_capacity)
 
     def decode_traced(self, frames, bfi=None, bps=16):
         frames, T, stride, bfi, pcm, status = self._prep(frames, bfi, bps)

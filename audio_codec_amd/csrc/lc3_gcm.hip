@@ -1,6 +1,13 @@
-/* lc3_gcm.hip -- the Secure RTP AES-GCM library (liblc3plus_gcm_hip.so): the gfx950 kernels of lc3_gcm.inc and the host code that launches them, behind the C ABI
- * of lc3_gcm_shim.h.  A sibling library (DESIGN.md "Sibling libraries"): lc3_host.c loads it on the first GCM call and hands it the batch's device.  It keeps no
- * state but its launch counts, no key, and allocates nothing: all scratch lies in the caller's workspace. */
+/* lc3_gcm.hip -- the Secure RTP AES-GCM library (liblc3plus_gcm_hip.so), behind the C ABI of lc3_gcm_shim.h: the suites of RFC 7714 for the kernels and the
+ * launch code of lc3_srtp_suite.inc.  A sibling library (DESIGN.md "Sibling libraries"): lc3_host.c loads it on the first GCM call and hands it the batch's
+ * device.
+ *
+ * Te0 is computed into LDS by every workgroup; round keys, salt and round count are read from the route's or source's context where it lies, so that contexts of
+ * both key sizes stand side by side.  GHASH is serial inside a packet like SHA-1, 32 table steps a block.  Protect is one walk: fetch, XOR, hash the ciphertext
+ * word, store.  Unprotect is two: hash without a store, compare, then decrypt into the sink.  The lanes of a wave hold different keys, so different GHASH tables:
+ * every lane copies its table (256 bytes of its context) into LDS before its walk, lane-interleaved so that the lanes of a wave read 64 different banks - 64 KiB a
+ * workgroup, two workgroups a CU.  With -DLC3G_LDS_TABLE=0 the table is read from the context in global memory instead, 16 bytes a step; that build measured 1.5
+ * to 1.6 times slower (the comparison of DESIGN 10l, profiles/gcm_tables_ab.txt). */
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stddef.h>
@@ -8,54 +15,38 @@
 #include "lc3_gcm_shim.h"
 
 #define WAVE 64
-#include "lc3_gcm.inc"
 
-/* ---- host ---- */
+/* Te0 into LDS */
+static inline __device__ void lc3g_tables(uint32_t* te)
+{
+    if (threadIdx.x < LC3S_TE_WORDS) te[threadIdx.x] = lc3s_te0(threadIdx.x);
+    __syncthreads();
+}
+#if LC3G_LDS_TABLE
+/* word w of entry e of this lane's table goes to word (4 e + w) * 256 + lane: only this lane reads or writes it, so no barrier */
+static inline __device__ void lc3g_table_in(uint32_t* gtab, const uint32_t* ctx)
+{
+    for (int i = 0; i < 64; i++) gtab[i * LC3S_THREADS + threadIdx.x] = ctx[LC3G_CTX_TABLE + i];
+}
+#define SUITE_LDS __shared__ uint32_t te[LC3S_TE_WORDS]; __shared__ uint32_t gtab[64 * LC3S_THREADS];
+#define SUITE_LANE(ctx) lc3g_table_in(gtab, ctx)
+#define LC3G_TAB (gtab + threadIdx.x)
+#define LC3G_TS LC3S_THREADS
+#else
+#define SUITE_LDS __shared__ uint32_t te[LC3S_TE_WORDS];
+#define SUITE_LANE(ctx) ((void)0)
+#define LC3G_TAB ((const uint32_t*)0)
+#define LC3G_TS 1
+#endif
+
 #define SIB_NAME "lc3plus_gcm"
-#include "lc3_sibling.h"
-static const sib_kernel k_table[] = {SIB_KERNEL(lc3_gcm_protect_kernel), SIB_KERNEL(lc3_gcm_route_kernel), SIB_KERNEL(lc3_gcm_init_kernel),
-                                     SIB_KERNEL(lc3_gcm_scan_kernel), SIB_KERNEL(lc3_gcm_auth_kernel), SIB_KERNEL(lc3_gcm_window_kernel),
-                                     SIB_KERNEL(lc3_gcm_state_kernel)};
-extern "C" long long lc3gcm_launch_count(const char* kernel) { return sib_launch_count(k_table, kernel); }
-
-extern "C" int lc3gcm_protect_run(const lc3srtp_protect_call* q)
-{
-    if (!q || q->max_packets <= 0 || q->max_packets >= LC3S_MAX_ITEMS || !q->n_packets || q->in.n_routes <= 0 || q->in.tag_len != LC3G_TAG_BYTES) return 1;
-    if (!q->in.route || !q->in.offset || !q->in.size || !q->in.status || !q->in.wire || !q->in.ctx || !q->in.roc || !q->in.seq_base || !q->in.dst) return 1;
-    if (!q->out_offset || !q->out_size || !q->out_status || (q->next_roc && !q->in.next_seq)) return 1;
-    if (q->in.dst_stride <= 0 || q->in.dst_stride > LC3S_MAX_STRIDE || q->in.dst_capacity < 0 || q->in.wire_capacity < 0) return 1;
-    SIB_CHK(hipSetDevice(q->device));
-    hipStream_t s = (hipStream_t)q->hip_stream;
-    const unsigned blocks = sib_blocks_for(q->max_packets, LC3S_THREADS, 1 << 16);
-    SIB_LAUNCH(lc3_gcm_protect_kernel, dim3(blocks), dim3(LC3S_THREADS), 0, s, q->in, q->max_packets, q->n_packets, q->out_offset, q->out_size, q->out_status);
-    if (q->next_roc) {
-        SIB_LAUNCH(lc3_gcm_route_kernel, dim3(sib_blocks_for(q->in.n_routes, LC3S_THREADS, 1LL << 30)), dim3(LC3S_THREADS), 0, s, q->in, q->next_roc);
-    }
-    if (q->sync) SIB_CHK(hipStreamSynchronize(s));
-    return 0;
-}
-
-extern "C" int lc3gcm_unprotect_run(const lc3srtp_unprotect_call* q)
-{
-    if (!q || q->n_items <= 0 || q->n_items >= LC3S_MAX_ITEMS || q->n_ssrc <= 0 || q->ring_capacity < 0 || q->tag_len != LC3G_TAG_BYTES) return 1;
-    if (!q->ring || !q->dg_offsets || !q->dg_sizes || !q->ssrc_key || !q->ctx || !q->state_in || !q->state_out || !q->sizes_out || !q->workspace) return 1;
-    if (q->workspace_bytes < lc3s_workspace_bytes(q->n_items, q->n_ssrc)) return 1;
-    SIB_CHK(hipSetDevice(q->device));
-    hipStream_t s = (hipStream_t)q->hip_stream;
-    /* the workspace's arrays (lc3_srtp_shim.h) */
-    lc3g_work w;
-    w.top1 = (unsigned long long*)(((uintptr_t)q->workspace + 15) & ~(uintptr_t)15);
-    w.bits = w.top1 + q->n_ssrc;
-    w.accepted = (long long*)(w.bits + q->n_ssrc);
-    w.first = (int32_t*)(w.accepted + q->n_items);
-    w.src = w.first + q->n_ssrc;
-    const long long per_source = q->n_ssrc > LC3S_STATS_WORDS ? q->n_ssrc : LC3S_STATS_WORDS;
-    SIB_LAUNCH(lc3_gcm_init_kernel, dim3(sib_blocks_for(per_source, LC3S_THREADS, 1LL << 30)), dim3(LC3S_THREADS), 0, s, w, q->n_ssrc, q->stats);
-    const unsigned blocks = sib_blocks_for(q->n_items, LC3S_THREADS, 1 << 16);
-    SIB_LAUNCH(lc3_gcm_scan_kernel, dim3(blocks), dim3(LC3S_THREADS), 0, s, *q, w);
-    SIB_LAUNCH(lc3_gcm_auth_kernel, dim3(blocks), dim3(LC3S_THREADS), 0, s, *q, w);
-    SIB_LAUNCH(lc3_gcm_window_kernel, dim3(blocks), dim3(LC3S_THREADS), 0, s, *q, w);
-    SIB_LAUNCH(lc3_gcm_state_kernel, dim3(sib_blocks_for(q->n_ssrc, LC3S_THREADS, 1LL << 30)), dim3(LC3S_THREADS), 0, s, *q, w);
-    if (q->sync) SIB_CHK(hipStreamSynchronize(s));
-    return 0;
-}
+#define SUITE_KERNEL(x) lc3_gcm_##x##_kernel
+#define SUITE_ABI(x) lc3gcm_##x
+#define SUITE_TAG(q) LC3G_TAG_BYTES
+#define SUITE_TAG_OK(t) ((t) == LC3G_TAG_BYTES)
+#define SUITE_CTX_WORDS LC3G_CTX_WORDS
+#define SUITE_TABLES() lc3g_tables(te)
+#define SUITE_PROTECT(q, p, size) lc3g_protect(q, p, te, 1, LC3G_TAB, LC3G_TS, size)
+#define SUITE_UNPROTECT(ring, off, size, it, state, s_l_first, ctx, index) \
+    lc3g_unprotect(ring, off, size, it, state, s_l_first, ctx, te, 1, LC3G_TAB, LC3G_TS, index)
+#include "lc3_srtp_suite.inc"

@@ -2409,6 +2409,30 @@ LC3_Error lc3plus_srtp_make_context(const uint8_t* master_key, const uint8_t* ma
     lc3s_make_context(master_key, master_salt, ctx);
     return LC3_OK;
 }
+/* A suite of Secure RTP as the calls below take it: its sibling, the two tag lengths it accepts, the words of a context, and its two rules under one
+ * signature for the host plans (te: Te0; a rule that knows its tag length does not read the argument) */
+typedef struct {
+    int sibling, tag_len[2], ctx_words;
+    int (*protect)(const lc3s_protect_in* q, long long p, const uint32_t* te, int32_t* out_size);
+    int (*unprotect)(uint8_t* ring, long long off, int32_t size, int tag_len, const lc3s_item* it, const int32_t* state, uint32_t s_l_first, const uint32_t* ctx,
+                     const uint32_t* te, long long* index);
+} srtp_suite;
+static int hmac_protect(const lc3s_protect_in* q, long long p, const uint32_t* te, int32_t* out_size) { return lc3s_protect(q, p, te, 1, out_size); }
+static int hmac_unprotect(uint8_t* ring, long long off, int32_t size, int tag_len, const lc3s_item* it, const int32_t* state, uint32_t s_l_first, const uint32_t* ctx,
+                          const uint32_t* te, long long* index)
+{
+    return lc3s_unprotect(ring, off, size, tag_len, it, state, s_l_first, ctx, te, 1, index);
+}
+static int gcm_protect(const lc3s_protect_in* q, long long p, const uint32_t* te, int32_t* out_size) { return lc3g_protect(q, p, te, 1, NULL, 1, out_size); }
+static int gcm_unprotect(uint8_t* ring, long long off, int32_t size, int tag_len, const lc3s_item* it, const int32_t* state, uint32_t s_l_first, const uint32_t* ctx,
+                         const uint32_t* te, long long* index)
+{
+    return lc3g_unprotect(ring, off, size, it, state, s_l_first, ctx, te, 1, NULL, 1, index);
+}
+static const srtp_suite SUITE_HMAC = {SIB_SRTP, {4, 10}, LC3S_CTX_WORDS, hmac_protect, hmac_unprotect};
+static const srtp_suite SUITE_GCM = {SIB_GCM, {LC3G_TAG_BYTES, LC3G_TAG_BYTES}, LC3G_CTX_WORDS, gcm_protect, gcm_unprotect};      /* the GCM calls pass LC3G_TAG_BYTES */
+static int srtp_tag_ok(const srtp_suite* u, int tag_len) { return tag_len == u->tag_len[0] || tag_len == u->tag_len[1]; }
+
 /* what a protect call takes behind its batch, in the header's order */
 typedef struct {
     int64_t max_packets; const int64_t* n_packets;
@@ -2418,8 +2442,8 @@ typedef struct {
     void* dst; int64_t dst_capacity; int64_t dst_stride; int tag_len;
     int64_t* out_offset; int32_t* out_size; uint8_t* out_status; int32_t* next_roc;
 } srtp_protect_args;
-/* the checks every protect call makes first, in the header's order; tag_ok: what the suite says to a->tag_len (the GCM calls have no such argument) */
-static LC3_Error srtp_protect_check(const srtp_protect_args* a, int tag_ok)
+/* the checks every protect call makes first, in the header's order */
+static LC3_Error srtp_protect_check(const srtp_suite* u, const srtp_protect_args* a)
 {
     if (!a->n_packets || !a->pkt_route || !a->pkt_offset || !a->pkt_size || !a->pkt_status || !a->wire || !a->ctx || !a->roc || !a->seq_base || !a->dst ||
         !a->out_offset || !a->out_size || !a->out_status)
@@ -2428,7 +2452,7 @@ static LC3_Error srtp_protect_check(const srtp_protect_args* a, int tag_ok)
     if (a->max_packets <= 0 || a->max_packets >= LC3S_MAX_ITEMS || a->wire_capacity < 0 || a->payload_room < 0 || a->header_room < LC3R_FIXED ||
         a->header_room - LC3R_FIXED < a->payload_room || a->n_routes <= 0)
         return LC3_ERROR;
-    if (a->dst_capacity < 0 || a->dst_stride <= 0 || a->dst_stride > LC3S_MAX_STRIDE || !tag_ok) return LC3_ERROR;
+    if (a->dst_capacity < 0 || a->dst_stride <= 0 || a->dst_stride > LC3S_MAX_STRIDE || !srtp_tag_ok(u, a->tag_len)) return LC3_ERROR;
     const uintptr_t w0 = (uintptr_t)a->wire, d0 = (uintptr_t)a->dst;
     if (d0 < w0 + (uintptr_t)a->wire_capacity && w0 < d0 + (uintptr_t)a->dst_capacity) return LC3_ERROR;          /* out of place only */
     return LC3_OK;
@@ -2440,33 +2464,22 @@ static lc3s_protect_in srtp_protect_in(const srtp_protect_args* a)
                                a->payload_room, a->n_routes, a->tag_len};
     return q;
 }
-/* the rule on the host, behind the checks: the kernels' steps (lc3_srtp.inc; gcm: lc3_gcm.inc) on the text they run */
-static void srtp_protect_plan(const srtp_protect_args* a, int gcm)
+/* the checks, then the rule on the host: the kernels' steps (lc3_srtp_suite.inc) on the text they run */
+static LC3_Error srtp_protect_plan(const srtp_suite* u, const srtp_protect_args* a)
 {
+    const LC3_Error e = srtp_protect_check(u, a);
+    if (e) return e;
     const lc3s_protect_in q = srtp_protect_in(a);
     uint32_t te[LC3S_TE_WORDS];
     for (uint32_t x = 0; x < LC3S_TE_WORDS; x++) te[x] = lc3s_te0(x);
     const int64_t n = *a->n_packets < a->max_packets ? *a->n_packets : a->max_packets;
     for (int64_t p = 0; p < n; p++) {
         int32_t size = 0;
-        const int st = gcm ? lc3g_protect(&q, p, te, 1, NULL, 1, &size) : lc3s_protect(&q, p, te, 1, &size);
+        const int st = u->protect(&q, p, te, &size);
         a->out_offset[p] = p * a->dst_stride; a->out_size[p] = size; a->out_status[p] = (uint8_t)st;
     }
     if (a->next_roc)
         for (int r = 0; r < a->n_routes; r++) lc3s_route_out(&q, r, a->next_roc);
-}
-LC3_Error lc3plus_plan_srtp_protect(int64_t max_packets, const int64_t* n_packets,
-    const int32_t* pkt_route, const int64_t* pkt_offset, const int32_t* pkt_size, const uint8_t* pkt_status,
-    const void* wire, int64_t wire_capacity, int header_room, int payload_room,
-    int n_routes, const int32_t* ctx, const int32_t* roc, const int32_t* seq_base, const int32_t* next_seq,
-    void* dst, int64_t dst_capacity, int64_t dst_stride, int tag_len,
-    int64_t* out_offset, int32_t* out_size, uint8_t* out_status, int32_t* next_roc)
-{
-    const srtp_protect_args a = {max_packets, n_packets, pkt_route, pkt_offset, pkt_size, pkt_status, wire, wire_capacity, header_room, payload_room, n_routes, ctx,
-                                 roc, seq_base, next_seq, dst, dst_capacity, dst_stride, tag_len, out_offset, out_size, out_status, next_roc};
-    const LC3_Error e = srtp_protect_check(&a, tag_len == 4 || tag_len == 10);
-    if (e) return e;
-    srtp_protect_plan(&a, 0);
     return LC3_OK;
 }
 /* what an unprotect call takes behind its batch, in the header's order */
@@ -2475,20 +2488,22 @@ typedef struct {
     int n_ssrc; const int32_t* ssrc_key; const int32_t* ctx; const int32_t* state_in; int32_t* state_out; int tag_len;
     int32_t* sizes_out; uint8_t* status; int64_t* index; int32_t* stats;
 } srtp_unprotect_args;
-static LC3_Error srtp_unprotect_check(const srtp_unprotect_args* a, int tag_ok)
+static LC3_Error srtp_unprotect_check(const srtp_suite* u, const srtp_unprotect_args* a)
 {
     if (!a->ring || !a->dg_offsets || !a->dg_sizes || !a->ssrc_key || !a->ctx || !a->state_in || !a->state_out || !a->sizes_out) return LC3_NULL_ERROR;
-    if (a->n_items <= 0 || a->n_items >= LC3S_MAX_ITEMS || a->ring_capacity < 0 || a->n_ssrc <= 0 || !tag_ok) return LC3_ERROR;
+    if (a->n_items <= 0 || a->n_items >= LC3S_MAX_ITEMS || a->ring_capacity < 0 || a->n_ssrc <= 0 || !srtp_tag_ok(u, a->tag_len)) return LC3_ERROR;
     return LC3_OK;
 }
 int64_t lc3plus_srtp_workspace_bytes(int64_t n_items, int n_ssrc)
 {
     return (int64_t)lc3s_workspace_bytes((long long)n_items, n_ssrc);
 }
-/* the rule on the host, behind the checks: the kernels' passes one after the other - the first items, the items against state_in, the window bits against the
- * new tops, the state.  gcm: the AEAD rule (a->tag_len is 16 then) */
-static LC3_Error srtp_unprotect_plan(const srtp_unprotect_args* a, int gcm)
+/* the checks, then the rule on the host: the kernels' passes one after the other - the first items, the items against state_in, the window bits against the
+ * new tops, the state */
+static LC3_Error srtp_unprotect_plan(const srtp_suite* u, const srtp_unprotect_args* a)
 {
+    const LC3_Error e = srtp_unprotect_check(u, a);
+    if (e) return e;
     const int64_t n_items = a->n_items;
     const int n_ssrc = a->n_ssrc, tag_len = a->tag_len;
     uint32_t te[LC3S_TE_WORDS];
@@ -2515,10 +2530,7 @@ static LC3_Error srtp_unprotect_plan(const srtp_unprotect_args* a, int gcm)
             const int s = items[i].src;
             const int32_t* state = a->state_in + (size_t)s * LC3S_STATE_WORDS;
             const uint32_t s_l_first = lc3s_seq_at(r8, a->dg_offsets[first[s]]);
-            if (gcm)
-                st = lc3g_unprotect(r8, a->dg_offsets[i], a->dg_sizes[i], &items[i], state, s_l_first, (const uint32_t*)a->ctx + (size_t)s * LC3G_CTX_WORDS, te, 1, NULL, 1, &idx);
-            else
-                st = lc3s_unprotect(r8, a->dg_offsets[i], a->dg_sizes[i], tag_len, &items[i], state, s_l_first, (const uint32_t*)a->ctx + (size_t)s * LC3S_CTX_WORDS, te, 1, &idx);
+            st = u->unprotect(r8, a->dg_offsets[i], a->dg_sizes[i], tag_len, &items[i], state, s_l_first, (const uint32_t*)a->ctx + (size_t)s * (size_t)u->ctx_words, te, &idx);
             if (st == LC3S_OK) {
                 accepted[i] = idx; a->sizes_out[i] = a->dg_sizes[i] - tag_len;
                 if ((unsigned long long)idx + 1 > top1[s]) top1[s] = (unsigned long long)idx + 1;
@@ -2537,26 +2549,58 @@ static LC3_Error srtp_unprotect_plan(const srtp_unprotect_args* a, int gcm)
     free(top1); free(bits); free(first); free(accepted); free(items);
     return LC3_OK;
 }
+/* every protect entry point of a batch ends here: the checks, then the suite's sibling */
+static LC3_Error srtp_protect_queue(const srtp_suite* u, void* dev, int decoder, const srtp_protect_args* a, void* hip_stream, int sync)
+{
+    const LC3_Error e = srtp_protect_check(u, a);
+    if (e) return e;
+    lc3srtp_protect_call q;
+    memset(&q, 0, sizeof q);
+    void* const* fn = sibling_call(u->sibling, dev, decoder, hip_stream, &q.device, &q.hip_stream);
+    if (!fn) return LC3_ERROR;
+    q.sync = sync; q.max_packets = (long long)a->max_packets; q.n_packets = (const long long*)a->n_packets; q.in = srtp_protect_in(a);
+    q.out_offset = (long long*)a->out_offset; q.out_size = a->out_size; q.out_status = a->out_status; q.next_roc = a->next_roc;
+    return ((int (*)(const lc3srtp_protect_call*))fn[0])(&q) ? LC3_ERROR : LC3_OK;
+}
+/* both unprotect entry points end here, behind the check of the batch: the workspace's pointer, the checks, the workspace's size, then the suite's sibling */
+static LC3_Error srtp_unprotect_queue(const srtp_suite* u, lc3plus_dec_batch* b, const srtp_unprotect_args* a, void* workspace, int64_t workspace_bytes, void* hip_stream,
+                                      int sync)
+{
+    if (!workspace) return LC3_NULL_ERROR;
+    const LC3_Error e = srtp_unprotect_check(u, a);
+    if (e) return e;
+    if (workspace_bytes < lc3plus_srtp_workspace_bytes(a->n_items, a->n_ssrc)) return LC3_ERROR;
+    lc3srtp_unprotect_call q;
+    memset(&q, 0, sizeof q);
+    void* const* fn = sibling_call(u->sibling, b->dev, 1, hip_stream, &q.device, &q.hip_stream);
+    if (!fn) return LC3_ERROR;
+    q.sync = sync; q.n_ssrc = a->n_ssrc; q.tag_len = a->tag_len; q.n_items = (long long)a->n_items; q.ring_capacity = (long long)a->ring_capacity;
+    q.ring = a->ring; q.dg_offsets = (const long long*)a->dg_offsets; q.dg_sizes = a->dg_sizes; q.ssrc_key = a->ssrc_key; q.ctx = a->ctx; q.state_in = a->state_in;
+    q.state_out = a->state_out; q.sizes_out = a->sizes_out; q.status = a->status; q.index = (long long*)a->index; q.stats = a->stats;
+    q.workspace = workspace; q.workspace_bytes = (long long)workspace_bytes;
+    return ((int (*)(const lc3srtp_unprotect_call*))fn[1])(&q) ? LC3_ERROR : LC3_OK;
+}
+/* the ten entry points: the arguments in the header's order into the struct (the GCM calls, which have no tag_len, with LC3G_TAG_BYTES), then the suite */
+#define SRTP_PROTECT_ARGS(tag) {max_packets, n_packets, pkt_route, pkt_offset, pkt_size, pkt_status, wire, wire_capacity, header_room, payload_room, n_routes, ctx, \
+                                roc, seq_base, next_seq, dst, dst_capacity, dst_stride, tag, out_offset, out_size, out_status, next_roc}
+#define SRTP_UNPROTECT_ARGS(tag) {n_items, ring, ring_capacity, dg_offsets, dg_sizes, n_ssrc, ssrc_key, ctx, state_in, state_out, tag, sizes_out, status, index, stats}
+LC3_Error lc3plus_plan_srtp_protect(int64_t max_packets, const int64_t* n_packets,
+    const int32_t* pkt_route, const int64_t* pkt_offset, const int32_t* pkt_size, const uint8_t* pkt_status,
+    const void* wire, int64_t wire_capacity, int header_room, int payload_room,
+    int n_routes, const int32_t* ctx, const int32_t* roc, const int32_t* seq_base, const int32_t* next_seq,
+    void* dst, int64_t dst_capacity, int64_t dst_stride, int tag_len,
+    int64_t* out_offset, int32_t* out_size, uint8_t* out_status, int32_t* next_roc)
+{
+    const srtp_protect_args a = SRTP_PROTECT_ARGS(tag_len);
+    return srtp_protect_plan(&SUITE_HMAC, &a);
+}
 LC3_Error lc3plus_plan_srtp_unprotect(int64_t n_items,
     void* ring, int64_t ring_capacity, const int64_t* dg_offsets, const int32_t* dg_sizes,
     int n_ssrc, const int32_t* ssrc_key, const int32_t* ctx, const int32_t* state_in, int32_t* state_out, int tag_len,
     int32_t* sizes_out, uint8_t* status, int64_t* index, int32_t* stats)
 {
-    const srtp_unprotect_args a = {n_items, ring, ring_capacity, dg_offsets, dg_sizes, n_ssrc, ssrc_key, ctx, state_in, state_out, tag_len, sizes_out, status, index, stats};
-    const LC3_Error e = srtp_unprotect_check(&a, tag_len == 4 || tag_len == 10);
-    if (e) return e;
-    return srtp_unprotect_plan(&a, 0);
-}
-/* every protect entry point ends here; which: the suite's sibling */
-static LC3_Error srtp_protect_queue(int which, void* dev, int decoder, const srtp_protect_args* a, void* hip_stream, int sync)
-{
-    lc3srtp_protect_call q;
-    memset(&q, 0, sizeof q);
-    void* const* fn = sibling_call(which, dev, decoder, hip_stream, &q.device, &q.hip_stream);
-    if (!fn) return LC3_ERROR;
-    q.sync = sync; q.max_packets = (long long)a->max_packets; q.n_packets = (const long long*)a->n_packets; q.in = srtp_protect_in(a);
-    q.out_offset = (long long*)a->out_offset; q.out_size = a->out_size; q.out_status = a->out_status; q.next_roc = a->next_roc;
-    return ((int (*)(const lc3srtp_protect_call*))fn[0])(&q) ? LC3_ERROR : LC3_OK;
+    const srtp_unprotect_args a = SRTP_UNPROTECT_ARGS(tag_len);
+    return srtp_unprotect_plan(&SUITE_HMAC, &a);
 }
 LC3_Error lc3plus_enc_batch_srtp_protect(lc3plus_batch* b, int64_t max_packets, const int64_t* n_packets,
     const int32_t* pkt_route, const int64_t* pkt_offset, const int32_t* pkt_size, const uint8_t* pkt_status,
@@ -2566,11 +2610,8 @@ LC3_Error lc3plus_enc_batch_srtp_protect(lc3plus_batch* b, int64_t max_packets, 
     int64_t* out_offset, int32_t* out_size, uint8_t* out_status, int32_t* next_roc, void* hip_stream, int sync)
 {
     if (!b) return LC3_NULL_ERROR;
-    const srtp_protect_args a = {max_packets, n_packets, pkt_route, pkt_offset, pkt_size, pkt_status, wire, wire_capacity, header_room, payload_room, n_routes, ctx,
-                                 roc, seq_base, next_seq, dst, dst_capacity, dst_stride, tag_len, out_offset, out_size, out_status, next_roc};
-    const LC3_Error e = srtp_protect_check(&a, tag_len == 4 || tag_len == 10);
-    if (e) return e;
-    return srtp_protect_queue(SIB_SRTP, b->dev, 0, &a, hip_stream, sync);
+    const srtp_protect_args a = SRTP_PROTECT_ARGS(tag_len);
+    return srtp_protect_queue(&SUITE_HMAC, b->dev, 0, &a, hip_stream, sync);
 }
 LC3_Error lc3plus_dec_batch_srtp_protect(lc3plus_dec_batch* b, int64_t max_packets, const int64_t* n_packets,
     const int32_t* pkt_route, const int64_t* pkt_offset, const int32_t* pkt_size, const uint8_t* pkt_status,
@@ -2580,25 +2621,8 @@ LC3_Error lc3plus_dec_batch_srtp_protect(lc3plus_dec_batch* b, int64_t max_packe
     int64_t* out_offset, int32_t* out_size, uint8_t* out_status, int32_t* next_roc, void* hip_stream, int sync)
 {
     if (!b) return LC3_NULL_ERROR;
-    const srtp_protect_args a = {max_packets, n_packets, pkt_route, pkt_offset, pkt_size, pkt_status, wire, wire_capacity, header_room, payload_room, n_routes, ctx,
-                                 roc, seq_base, next_seq, dst, dst_capacity, dst_stride, tag_len, out_offset, out_size, out_status, next_roc};
-    const LC3_Error e = srtp_protect_check(&a, tag_len == 4 || tag_len == 10);
-    if (e) return e;
-    return srtp_protect_queue(SIB_SRTP, b->dev, 1, &a, hip_stream, sync);
-}
-/* both unprotect entry points end here, behind the checks of the batch and the workspace's pointer */
-static LC3_Error srtp_unprotect_queue(int which, lc3plus_dec_batch* b, const srtp_unprotect_args* a, void* workspace, int64_t workspace_bytes, void* hip_stream, int sync)
-{
-    if (workspace_bytes < lc3plus_srtp_workspace_bytes(a->n_items, a->n_ssrc)) return LC3_ERROR;
-    lc3srtp_unprotect_call q;
-    memset(&q, 0, sizeof q);
-    void* const* fn = sibling_call(which, b->dev, 1, hip_stream, &q.device, &q.hip_stream);
-    if (!fn) return LC3_ERROR;
-    q.sync = sync; q.n_ssrc = a->n_ssrc; q.tag_len = a->tag_len; q.n_items = (long long)a->n_items; q.ring_capacity = (long long)a->ring_capacity;
-    q.ring = a->ring; q.dg_offsets = (const long long*)a->dg_offsets; q.dg_sizes = a->dg_sizes; q.ssrc_key = a->ssrc_key; q.ctx = a->ctx; q.state_in = a->state_in;
-    q.state_out = a->state_out; q.sizes_out = a->sizes_out; q.status = a->status; q.index = (long long*)a->index; q.stats = a->stats;
-    q.workspace = workspace; q.workspace_bytes = (long long)workspace_bytes;
-    return ((int (*)(const lc3srtp_unprotect_call*))fn[1])(&q) ? LC3_ERROR : LC3_OK;
+    const srtp_protect_args a = SRTP_PROTECT_ARGS(tag_len);
+    return srtp_protect_queue(&SUITE_HMAC, b->dev, 1, &a, hip_stream, sync);
 }
 LC3_Error lc3plus_dec_batch_srtp_unprotect(lc3plus_dec_batch* b, int64_t n_items,
     void* ring, int64_t ring_capacity, const int64_t* dg_offsets, const int32_t* dg_sizes,
@@ -2607,13 +2631,10 @@ LC3_Error lc3plus_dec_batch_srtp_unprotect(lc3plus_dec_batch* b, int64_t n_items
     void* workspace, int64_t workspace_bytes, void* hip_stream, int sync)
 {
     if (!b) return LC3_NULL_ERROR;
-    const srtp_unprotect_args a = {n_items, ring, ring_capacity, dg_offsets, dg_sizes, n_ssrc, ssrc_key, ctx, state_in, state_out, tag_len, sizes_out, status, index, stats};
-    if (!workspace) return LC3_NULL_ERROR;
-    const LC3_Error e = srtp_unprotect_check(&a, tag_len == 4 || tag_len == 10);
-    if (e) return e;
-    return srtp_unprotect_queue(SIB_SRTP, b, &a, workspace, workspace_bytes, hip_stream, sync);
+    const srtp_unprotect_args a = SRTP_UNPROTECT_ARGS(tag_len);
+    return srtp_unprotect_queue(&SUITE_HMAC, b, &a, workspace, workspace_bytes, hip_stream, sync);
 }
-/* ---- Secure RTP, AEAD (include/lc3plus_batch.h "Secure RTP, AEAD"; lc3_gcm_shim.h): the HMAC calls' checks, plans and queues with the GCM rule and sibling ---- */
+/* ---- Secure RTP, AEAD (include/lc3plus_batch.h "Secure RTP, AEAD"; lc3_gcm_shim.h): the calls above with SUITE_GCM ---- */
 LC3_Error lc3plus_srtp_gcm_make_context(const uint8_t* master_key, int key_bytes, const uint8_t* master_salt, int32_t* ctx)
 {
     if (!master_key || !master_salt || !ctx) return LC3_NULL_ERROR;
@@ -2628,12 +2649,8 @@ LC3_Error lc3plus_plan_srtp_gcm_protect(int64_t max_packets, const int64_t* n_pa
     void* dst, int64_t dst_capacity, int64_t dst_stride,
     int64_t* out_offset, int32_t* out_size, uint8_t* out_status, int32_t* next_roc)
 {
-    const srtp_protect_args a = {max_packets, n_packets, pkt_route, pkt_offset, pkt_size, pkt_status, wire, wire_capacity, header_room, payload_room, n_routes, ctx,
-                                 roc, seq_base, next_seq, dst, dst_capacity, dst_stride, LC3G_TAG_BYTES, out_offset, out_size, out_status, next_roc};
-    const LC3_Error e = srtp_protect_check(&a, 1);
-    if (e) return e;
-    srtp_protect_plan(&a, 1);
-    return LC3_OK;
+    const srtp_protect_args a = SRTP_PROTECT_ARGS(LC3G_TAG_BYTES);
+    return srtp_protect_plan(&SUITE_GCM, &a);
 }
 LC3_Error lc3plus_enc_batch_srtp_gcm_protect(lc3plus_batch* b, int64_t max_packets, const int64_t* n_packets,
     const int32_t* pkt_route, const int64_t* pkt_offset, const int32_t* pkt_size, const uint8_t* pkt_status,
@@ -2643,11 +2660,8 @@ LC3_Error lc3plus_enc_batch_srtp_gcm_protect(lc3plus_batch* b, int64_t max_packe
     int64_t* out_offset, int32_t* out_size, uint8_t* out_status, int32_t* next_roc, void* hip_stream, int sync)
 {
     if (!b) return LC3_NULL_ERROR;
-    const srtp_protect_args a = {max_packets, n_packets, pkt_route, pkt_offset, pkt_size, pkt_status, wire, wire_capacity, header_room, payload_room, n_routes, ctx,
-                                 roc, seq_base, next_seq, dst, dst_capacity, dst_stride, LC3G_TAG_BYTES, out_offset, out_size, out_status, next_roc};
-    const LC3_Error e = srtp_protect_check(&a, 1);
-    if (e) return e;
-    return srtp_protect_queue(SIB_GCM, b->dev, 0, &a, hip_stream, sync);
+    const srtp_protect_args a = SRTP_PROTECT_ARGS(LC3G_TAG_BYTES);
+    return srtp_protect_queue(&SUITE_GCM, b->dev, 0, &a, hip_stream, sync);
 }
 LC3_Error lc3plus_dec_batch_srtp_gcm_protect(lc3plus_dec_batch* b, int64_t max_packets, const int64_t* n_packets,
     const int32_t* pkt_route, const int64_t* pkt_offset, const int32_t* pkt_size, const uint8_t* pkt_status,
@@ -2657,22 +2671,16 @@ LC3_Error lc3plus_dec_batch_srtp_gcm_protect(lc3plus_dec_batch* b, int64_t max_p
     int64_t* out_offset, int32_t* out_size, uint8_t* out_status, int32_t* next_roc, void* hip_stream, int sync)
 {
     if (!b) return LC3_NULL_ERROR;
-    const srtp_protect_args a = {max_packets, n_packets, pkt_route, pkt_offset, pkt_size, pkt_status, wire, wire_capacity, header_room, payload_room, n_routes, ctx,
-                                 roc, seq_base, next_seq, dst, dst_capacity, dst_stride, LC3G_TAG_BYTES, out_offset, out_size, out_status, next_roc};
-    const LC3_Error e = srtp_protect_check(&a, 1);
-    if (e) return e;
-    return srtp_protect_queue(SIB_GCM, b->dev, 1, &a, hip_stream, sync);
+    const srtp_protect_args a = SRTP_PROTECT_ARGS(LC3G_TAG_BYTES);
+    return srtp_protect_queue(&SUITE_GCM, b->dev, 1, &a, hip_stream, sync);
 }
 LC3_Error lc3plus_plan_srtp_gcm_unprotect(int64_t n_items,
     void* ring, int64_t ring_capacity, const int64_t* dg_offsets, const int32_t* dg_sizes,
     int n_ssrc, const int32_t* ssrc_key, const int32_t* ctx, const int32_t* state_in, int32_t* state_out,
     int32_t* sizes_out, uint8_t* status, int64_t* index, int32_t* stats)
 {
-    const srtp_unprotect_args a = {n_items, ring, ring_capacity, dg_offsets, dg_sizes, n_ssrc, ssrc_key, ctx, state_in, state_out, LC3G_TAG_BYTES, sizes_out, status, index,
-                                   stats};
-    const LC3_Error e = srtp_unprotect_check(&a, 1);
-    if (e) return e;
-    return srtp_unprotect_plan(&a, 1);
+    const srtp_unprotect_args a = SRTP_UNPROTECT_ARGS(LC3G_TAG_BYTES);
+    return srtp_unprotect_plan(&SUITE_GCM, &a);
 }
 LC3_Error lc3plus_dec_batch_srtp_gcm_unprotect(lc3plus_dec_batch* b, int64_t n_items,
     void* ring, int64_t ring_capacity, const int64_t* dg_offsets, const int32_t* dg_sizes,
@@ -2681,12 +2689,8 @@ LC3_Error lc3plus_dec_batch_srtp_gcm_unprotect(lc3plus_dec_batch* b, int64_t n_i
     void* workspace, int64_t workspace_bytes, void* hip_stream, int sync)
 {
     if (!b) return LC3_NULL_ERROR;
-    const srtp_unprotect_args a = {n_items, ring, ring_capacity, dg_offsets, dg_sizes, n_ssrc, ssrc_key, ctx, state_in, state_out, LC3G_TAG_BYTES, sizes_out, status, index,
-                                   stats};
-    if (!workspace) return LC3_NULL_ERROR;
-    const LC3_Error e = srtp_unprotect_check(&a, 1);
-    if (e) return e;
-    return srtp_unprotect_queue(SIB_GCM, b, &a, workspace, workspace_bytes, hip_stream, sync);
+    const srtp_unprotect_args a = SRTP_UNPROTECT_ARGS(LC3G_TAG_BYTES);
+    return srtp_unprotect_queue(&SUITE_GCM, b, &a, workspace, workspace_bytes, hip_stream, sync);
 }
 LC3_Error lc3plus_dec_batch_set_input_ready(lc3plus_dec_batch* b, int ready)
 {
