@@ -50,6 +50,8 @@ EXPORTS = [
     "lc3plus_dec_batch_srtp_unprotect", "lc3plus_plan_srtp_unprotect", "lc3plus_srtp_workspace_bytes",
     "lc3plus_srtp_gcm_make_context", "lc3plus_enc_batch_srtp_gcm_protect", "lc3plus_dec_batch_srtp_gcm_protect", "lc3plus_plan_srtp_gcm_protect",
     "lc3plus_dec_batch_srtp_gcm_unprotect", "lc3plus_plan_srtp_gcm_unprotect",
+    "lc3plus_enc_batch_red_pack", "lc3plus_dec_batch_red_pack", "lc3plus_plan_red_pack", "lc3plus_red_work_bytes", "lc3plus_dec_batch_red_unpack",
+    "lc3plus_plan_red_unpack",
     "lc3plus_shard_block",
     "lc3plus_enc_sharded_create", "lc3plus_enc_sharded_destroy", "lc3plus_enc_sharded_shards", "lc3plus_enc_sharded_shard", "lc3plus_enc_sharded_device",
     "lc3plus_enc_sharded_owner", "lc3plus_enc_sharded_input_samples", "lc3plus_enc_sharded_num_bytes", "lc3plus_enc_sharded_stride",
@@ -123,6 +125,14 @@ SRTP_STATS_WORDS = 16
 # include/lc3plus_batch.h "Secure RTP, AEAD"): the context's words and the tag's bytes; every other constant is SRTP_*'s
 SRTP_GCM_CTX_WORDS = 128
 SRTP_GCM_TAG_BYTES = 16
+# Redundant audio (Batch.red_pack_device, DecBatch.red_pack_device, DecBatch.red_unpack, plan_red_pack, plan_red_unpack; include/lc3plus_batch.h "Redundant
+# audio"): the deepest redundancy, the flag of a BAD packet, the words of a route's stats, an item's status (also its word in stats), the words of the dropped blocks
+RED_MAX_DEPTH = 4
+RED_PKT_BAD = 2
+RED_STATS_WORDS = 4
+(RED_OK, RED_DROPPED, RED_RANGE, RED_SHORT, RED_DEPTH, RED_LENGTH, RED_PAYLOAD_TYPE) = range(7)
+RED_DROP_TYPE, RED_DROP_OFFSET, RED_DROP_EMPTY = 8, 9, 10
+RED_UNPACK_STATS_WORDS = 16
 LC3_BW_WARNING = 18
 
 
@@ -304,6 +314,16 @@ def load_library():
         L.lc3plus_plan_srtp_gcm_protect.argtypes = gprot
         L.lc3plus_dec_batch_srtp_gcm_unprotect.argtypes = [C.c_void_p] + gunp + [C.c_void_p, C.c_int64, C.c_void_p, C.c_int]
         L.lc3plus_plan_srtp_gcm_unprotect.argtypes = gunp
+        red = ([C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int,
+                C.c_int] + [C.c_void_p] * 6 + [C.c_void_p, C.c_void_p, C.c_int])
+        L.lc3plus_enc_batch_red_pack.argtypes = [C.c_void_p] + red
+        L.lc3plus_dec_batch_red_pack.argtypes = [C.c_void_p] + red
+        L.lc3plus_plan_red_pack.argtypes = [C.c_int] + red
+        L.lc3plus_red_work_bytes.argtypes = [C.c_int64]; L.lc3plus_red_work_bytes.restype = C.c_int64
+        unred = [C.c_int64] + [C.c_void_p] * 6 + [C.c_int64, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 8 + [C.c_void_p, C.c_int]
+        L.lc3plus_dec_batch_red_unpack.argtypes = [C.c_void_p] + unred
+        L.lc3plus_plan_red_unpack.argtypes = [C.c_int] + unred
         _LIB = L
     return _LIB
 
@@ -757,6 +777,188 @@ class _RtpStamp:
         return dict(zip(RTP_STAMP_OPTIONAL, outs), wire=wire)
 
 
+RED_PACK_OPTIONAL = ("red_flags", "red_blocks", "wire_total", "route_stats", "tail")
+RED_PACK_OUTPUTS = ("red_offset", "red_size", "red_flags", "red_blocks", "wire_total", "route_stats")
+RED_UNPACK_OPTIONAL = ("timestamp", "gen", "status", "stats")
+RED_UNPACK_OUTPUTS = ("stream", "seq", "offsets", "num_bytes", "timestamp", "gen", "status", "stats")
+
+
+def red_work_bytes(max_packets):
+    """bytes of the workspace of a red_pack call (lc3plus_red_work_bytes); 0 for a max_packets the calls refuse"""
+    return int(load_library().lc3plus_red_work_bytes(int(max_packets)))
+
+
+def red_tail_stride(max_frame_bytes):
+    """the smallest tail_stride a red_pack call takes for frames of up to max_frame_bytes bytes"""
+    return (min(int(max_frame_bytes), 1023) + 15) & ~15
+
+
+def _red_pack_arrays(n_streams, frames, offsets, num_bytes, pkt_route, pkt_frame, n_packets, block_pt, max_depth, depth, flags, counts, route_src, tail_bytes, tail_sizes,
+                     tail_stride, wire, optional):
+    """the arrays of a pack call as the C calls take them: (inputs by name, None for a NULL one; outputs in RED_PACK_OUTPUTS order, then tail_bytes and tail_sizes;
+    work)"""
+    frames = np.ascontiguousarray(frames, dtype=np.uint8).reshape(-1)
+    offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+    num_bytes = np.ascontiguousarray(num_bytes, dtype=np.int32)
+    if offsets.ndim != 2 or offsets.shape != num_bytes.shape or offsets.shape[0] != n_streams:
+        raise ValueError("offsets and num_bytes must have shape [n_streams, n_frames]")
+    route = np.ascontiguousarray(pkt_route, dtype=np.int32).reshape(-1)
+    frame = np.ascontiguousarray(pkt_frame, dtype=np.int32).reshape(-1)
+    if route.size != frame.size:
+        raise ValueError("pkt_route and pkt_frame hold one entry per packet")
+    m = route.size
+    block_pt = np.ascontiguousarray(block_pt, dtype=np.int32).reshape(-1)
+    R, D = block_pt.size, int(max_depth)
+    opt = lambda a, dt, shape, what: None if a is None else _shaped(np.ascontiguousarray(a, dtype=dt), shape, what)
+    flags = opt(flags, np.uint8, offsets.shape, "flags must have the shape of offsets")
+    counts = opt(counts, np.int32, (n_streams,), "counts holds one entry per stream")
+    route_src = opt(route_src, np.int32, (R,), "route_src and block_pt hold one entry per route")
+    depth = opt(depth, np.int32, (R,), "depth holds one entry per route")
+    if (tail_bytes is None) != (tail_sizes is None):
+        raise ValueError("tail_bytes and tail_sizes come together")
+    tail_bytes = opt(tail_bytes, np.uint8, (n_streams, D, int(tail_stride)), "tail_bytes must have shape [n_streams, max_depth, tail_stride]")
+    tail_sizes = opt(tail_sizes, np.int32, (n_streams, D), "tail_sizes must have shape [n_streams, max_depth]")
+    count = np.array([m if n_packets is None else int(n_packets)], np.int64)
+    wire = np.array(wire, dtype=np.uint8).reshape(-1)                 # a copy: the call's wire buffer starts with these contents
+    ins = dict(frames=frames, offsets=offsets, num_bytes=num_bytes, flags=flags, counts=counts, route_src=route_src, n_packets=count, pkt_route=route, pkt_frame=frame,
+               depth=depth, block_pt=block_pt, tail_bytes=tail_bytes, tail_sizes=tail_sizes, wire=wire)
+    tail = "tail" in optional
+    outs = [np.zeros(m, np.int64), np.zeros(m, np.int32), np.zeros(m, np.uint8) if "red_flags" in optional else None,
+            np.zeros(m, np.uint8) if "red_blocks" in optional else None, np.zeros(1, np.int64) if "wire_total" in optional else None,
+            np.zeros((R, RED_STATS_WORDS), np.int32) if "route_stats" in optional else None,
+            np.zeros((n_streams, D, int(tail_stride)), np.uint8) if tail else None, np.zeros((n_streams, D), np.int32) if tail else None]
+    work = np.zeros(max(red_work_bytes(max(m, 1)), 8) // 8, np.int64)
+    return ins, outs, work
+
+
+def _shaped(a, shape, what):
+    if a.shape != tuple(shape):
+        raise ValueError(what)
+    return a
+
+
+def _red_pack_result(ins, outs):
+    r = dict(zip(RED_PACK_OUTPUTS + ("tail_bytes", "tail_sizes"), outs))
+    r["wire_total"] = int(r["wire_total"][0]) if r["wire_total"] is not None else None
+    r["wire"] = ins["wire"]
+    return r
+
+
+RED_PACK_INPUTS = ("frames", "offsets", "num_bytes", "flags", "counts", "route_src", "n_packets", "pkt_route", "pkt_frame", "depth", "block_pt", "tail_bytes", "tail_sizes",
+                   "wire")
+
+
+def plan_red_pack(n_streams, frames, offsets, num_bytes, max_frame_bytes, pkt_route, pkt_frame, block_pt, ts_step, wire, max_depth=1, depth=None,
+                  max_packet_bytes=1 << 30, n_packets=None, flags=None, skip_mask=0, counts=None, route_src=None, tail_bytes=None, tail_sizes=None, tail_stride=None,
+                  wire_capacity=None, header_room=12, align=1, optional=RED_PACK_OPTIONAL, frames_capacity=None):
+    """The rule of Batch.red_pack_device / DecBatch.red_pack_device on the host (lc3plus_plan_red_pack, no device needed): the egress's frame tables - frames (uint8),
+    offsets (int64) / num_bytes [n_streams, n_frames], optional flags with skip_mask, counts [n_streams], route_src [n_routes] - its in-place list pkt_route,
+    pkt_frame [max_packets] (n_packets of it: all by default), block_pt [n_routes], optional depth [n_routes], the previous call's tail_bytes
+    [n_streams, max_depth, tail_stride] / tail_sizes [n_streams, max_depth] (tail_stride: red_tail_stride(max_frame_bytes) by default) and wire, the wire buffer's
+    contents before the call -> dict of red_offset (int64), red_size, red_flags, red_blocks (uint8) [max_packets] (zero behind n_packets), wire_total (int),
+    route_stats [n_routes, RED_STATS_WORDS], tail_bytes / tail_sizes for the next call and wire (the buffer after the call); the outputs of RED_PACK_OPTIONAL
+    not named in `optional` are passed as NULL and come back as None.  LC3Error for arguments the C call refuses."""
+    stride = red_tail_stride(max_frame_bytes) if tail_stride is None else int(tail_stride)
+    ins, outs, work = _red_pack_arrays(n_streams, frames, offsets, num_bytes, pkt_route, pkt_frame, n_packets, block_pt, max_depth, depth, flags, counts, route_src,
+                                       tail_bytes, tail_sizes, stride, wire, optional)
+    pad = np.zeros(8, np.uint8)                                       # an empty array still has to be a pointer
+    ptr = lambda a: (a if a.size else pad).ctypes.data if a is not None else None
+    fcap = ins["frames"].size if frames_capacity is None else int(frames_capacity)
+    wcap = ins["wire"].size if wire_capacity is None else int(wire_capacity)
+    rc = load_library().lc3plus_plan_red_pack(
+        int(n_streams), ins["offsets"].shape[1], ptr(ins["frames"]), fcap, ptr(ins["offsets"]), ptr(ins["num_bytes"]), int(max_frame_bytes), ptr(ins["flags"]),
+        int(skip_mask), ptr(ins["counts"]), ins["block_pt"].size, ptr(ins["route_src"]), ins["pkt_route"].size, ptr(ins["n_packets"]), ptr(ins["pkt_route"]),
+        ptr(ins["pkt_frame"]), int(max_depth), ptr(ins["depth"]), ptr(ins["block_pt"]), int(ts_step), int(max_packet_bytes), ptr(ins["tail_bytes"]),
+        ptr(ins["tail_sizes"]), stride, ptr(outs[6]), ptr(outs[7]), ptr(ins["wire"]), wcap, int(header_room), int(align), *[ptr(a) for a in outs[:6]], ptr(work), None, 0)
+    if rc:
+        raise LC3Error(rc, "lc3plus_plan_red_pack")
+    return _red_pack_result(ins, outs)
+
+
+class _RedPack:
+    """The send side of the redundant audio for both batch kinds (lc3plus_{enc,dec}_batch_red_pack; include/lc3plus_batch.h "Redundant audio")."""
+
+    def red_pack_device(self, n_frames, d_frames_ptr, frames_capacity, d_offsets_ptr, d_num_bytes_ptr, max_frame_bytes, n_routes, max_packets, d_n_packets_ptr,
+                        d_pkt_route_ptr, d_pkt_frame_ptr, max_depth, d_block_pt_ptr, ts_step, max_packet_bytes, d_wire_ptr, wire_capacity, d_red_offset_ptr,
+                        d_red_size_ptr, d_work_ptr, header_room=12, align=1, d_flags_ptr=None, skip_mask=0, d_counts_ptr=None, d_route_src_ptr=None, d_depth_ptr=None,
+                        d_tail_bytes_in_ptr=None, d_tail_sizes_in_ptr=None, tail_stride=0, d_tail_bytes_out_ptr=None, d_tail_sizes_out_ptr=None, d_red_flags_ptr=None,
+                        d_red_blocks_ptr=None, d_wire_total_ptr=None, d_route_stats_ptr=None, hip_stream=None, sync=False):
+        """Raw device pointers only - the frame tables an egress call took, its in-place list pkt_route / pkt_frame [max_packets] with its length n_packets (one
+        int64, read when the kernels run), block_pt [n_routes] and the optional depth [n_routes] and tails -> RFC 2198 payloads behind header_room bytes each in
+        the wire buffer, the records red_offset (int64), red_size [max_packets] and the optional red_flags, red_blocks (uint8), wire_total (one int64),
+        route_stats [n_routes, RED_STATS_WORDS] and the tails for the next call.  work: red_work_bytes(max_packets) bytes.  Stateless: nothing of the batch's
+        streams is read or written.  Queued on hip_stream; returns at once unless sync."""
+        def p(x):
+            return C.c_void_p(x) if x else None
+        rc = self._ssf("_red_pack")(self.h, int(n_frames), p(d_frames_ptr), int(frames_capacity), p(d_offsets_ptr), p(d_num_bytes_ptr), int(max_frame_bytes),
+                                    p(d_flags_ptr), int(skip_mask), p(d_counts_ptr), int(n_routes), p(d_route_src_ptr), int(max_packets), p(d_n_packets_ptr),
+                                    p(d_pkt_route_ptr), p(d_pkt_frame_ptr), int(max_depth), p(d_depth_ptr), p(d_block_pt_ptr), int(ts_step), int(max_packet_bytes),
+                                    p(d_tail_bytes_in_ptr), p(d_tail_sizes_in_ptr), int(tail_stride), p(d_tail_bytes_out_ptr), p(d_tail_sizes_out_ptr), p(d_wire_ptr),
+                                    int(wire_capacity), int(header_room), int(align), p(d_red_offset_ptr), p(d_red_size_ptr), p(d_red_flags_ptr), p(d_red_blocks_ptr),
+                                    p(d_wire_total_ptr), p(d_route_stats_ptr), p(d_work_ptr), p(hip_stream), 1 if sync else 0)
+        if rc:
+            raise LC3Error(rc, self._ss + "_red_pack")
+
+    def red_pack(self, frames, offsets, num_bytes, max_frame_bytes, pkt_route, pkt_frame, block_pt, ts_step, wire, max_depth=1, depth=None, max_packet_bytes=1 << 30,
+                 n_packets=None, flags=None, skip_mask=0, counts=None, route_src=None, tail_bytes=None, tail_sizes=None, tail_stride=None, wire_capacity=None,
+                 header_room=12, align=1, optional=RED_PACK_OPTIONAL, frames_capacity=None):
+        """Host convenience: the arrays of plan_red_pack uploaded, packed on the device and downloaded -> the dict plan_red_pack gives.  Device memory through the
+        HIP runtime (on the current device: the batch's, unless the caller has switched), freed before it returns."""
+        stride = red_tail_stride(max_frame_bytes) if tail_stride is None else int(tail_stride)
+        ins, outs, work = _red_pack_arrays(self.n_streams, frames, offsets, num_bytes, pkt_route, pkt_frame, n_packets, block_pt, max_depth, depth, flags, counts,
+                                           route_src, tail_bytes, tail_sizes, stride, wire, optional)
+        fcap = ins["frames"].size if frames_capacity is None else int(frames_capacity)
+        wcap = ins["wire"].size if wire_capacity is None else int(wire_capacity)
+        arrays = [ins[k] for k in RED_PACK_INPUTS] + outs + [work]
+        with _on_device(arrays) as (ptrs, back):
+            v = dict(zip(RED_PACK_INPUTS + RED_PACK_OUTPUTS + ("tail_bytes_out", "tail_sizes_out", "work"), ptrs))
+            self.red_pack_device(ins["offsets"].shape[1], v["frames"], fcap, v["offsets"], v["num_bytes"], max_frame_bytes, ins["block_pt"].size, ins["pkt_route"].size,
+                                 v["n_packets"], v["pkt_route"], v["pkt_frame"], max_depth, v["block_pt"], ts_step, max_packet_bytes, v["wire"], wcap, v["red_offset"],
+                                 v["red_size"], v["work"], header_room, align, v["flags"], skip_mask, v["counts"], v["route_src"], v["depth"], v["tail_bytes"],
+                                 v["tail_sizes"], stride, v["tail_bytes_out"], v["tail_sizes_out"], v["red_flags"], v["red_blocks"], v["wire_total"], v["route_stats"],
+                                 sync=True)
+            for k in range(len(RED_PACK_INPUTS) - 1, len(arrays) - 1):  # wire, then every output
+                back(k)
+        return _red_pack_result(ins, outs)
+
+
+def _red_unpack_arrays(n_streams, stream, seq, offsets, num_bytes, timestamp, ring, max_red, block_pt, optional):
+    """the arrays of an unpack call as the C calls take them: (inputs stream, seq, offsets, num_bytes, timestamp, ring, block_pt - None for NULL; outputs in
+    RED_UNPACK_OUTPUTS order likewise)"""
+    stream = np.ascontiguousarray(stream, dtype=np.int32).reshape(-1)
+    n = stream.size
+    seq, offsets = _u32(seq), np.ascontiguousarray(offsets, dtype=np.int64).reshape(-1)
+    num_bytes = np.ascontiguousarray(num_bytes, dtype=np.int32).reshape(-1)
+    timestamp = _u32(timestamp) if timestamp is not None else None
+    if not (seq.size == offsets.size == num_bytes.size == n) or (timestamp is not None and timestamp.size != n):
+        raise ValueError("the item arrays hold one entry per item")
+    ring = np.ascontiguousarray(ring, dtype=np.uint8).reshape(-1)
+    if block_pt is not None:
+        block_pt = _shaped(np.ascontiguousarray(block_pt, dtype=np.int32).reshape(-1), (n_streams,), "block_pt holds one entry per stream")
+    m = n * (int(max_red) + 1)
+    outs = [np.zeros(m, np.int32), np.zeros(m, np.int32), np.zeros(m, np.int64), np.zeros(m, np.int32), np.zeros(m, np.int32) if "timestamp" in optional else None,
+            np.zeros(m, np.uint8) if "gen" in optional else None, np.zeros(n, np.uint8) if "status" in optional else None,
+            np.zeros(RED_UNPACK_STATS_WORDS, np.int32) if "stats" in optional else None]
+    return [stream, seq, offsets, num_bytes, timestamp, ring, block_pt], outs
+
+
+def plan_red_unpack(n_streams, stream, seq, offsets, num_bytes, ring, ts_step, max_red=RED_MAX_DEPTH, timestamp=None, block_pt=None, optional=RED_UNPACK_OPTIONAL,
+                    ring_capacity=None):
+    """The rule of DecBatch.red_unpack on the host (lc3plus_plan_red_unpack, no device needed): the parse's items stream, seq, offsets (int64), num_bytes and the
+    optional timestamp [n] over ring (uint8, ring_capacity bytes of it: all by default), optional block_pt [n_streams] -> dict of stream, seq, offsets (int64),
+    num_bytes, timestamp, gen (uint8) [n * (max_red + 1)] - the item arrays of ingest and probe - status (uint8) [n] and stats [RED_UNPACK_STATS_WORDS]; those of
+    RED_UNPACK_OPTIONAL not named in `optional` are passed as NULL and come back as None.  LC3Error for arguments the C call refuses."""
+    ins, outs = _red_unpack_arrays(n_streams, stream, seq, offsets, num_bytes, timestamp, ring, max_red, block_pt, optional)
+    pad = np.zeros(8, np.uint8)
+    ptr = lambda a: (a if a.size else pad).ctypes.data if a is not None else None
+    cap = ins[5].size if ring_capacity is None else int(ring_capacity)
+    rc = load_library().lc3plus_plan_red_unpack(int(n_streams), ins[0].size, *[ptr(a) for a in ins[:6]], cap, int(max_red), ptr(ins[6]), int(ts_step),
+                                                *[ptr(a) for a in outs], None, 0)
+    if rc:
+        raise LC3Error(rc, "lc3plus_plan_red_unpack")
+    return dict(zip(RED_UNPACK_OUTPUTS, outs))
+
+
 RR_OPTIONAL = ("ext_seq", "item_status", "stream_stats")
 RR_OUTPUTS = ("state", "blocks", "ext_seq", "item_status", "stream_stats")
 
@@ -1069,7 +1271,7 @@ def stream_header_ok(header, blob):
     return bool(load_library().lc3plus_stream_header_ok(h.ctypes.data, b.ctypes.data))
 
 
-class Batch(_StreamLifecycle, _Egress, _RtpStamp, _SrtpProtect):
+class Batch(_StreamLifecycle, _Egress, _RtpStamp, _SrtpProtect, _RedPack):
     """n_streams independent encoders (lc3plus_enc_batch_*), state resident on the GPU between encode() calls."""
 
     def __init__(self, n_streams, samplerate, channels, frame_ms, hrmode, bitrates, device=-1):
@@ -1604,7 +1806,7 @@ def plan_ingest(n_streams, channels, stream, seq, offsets, num_bytes, base, n_fr
     return dict(zip(ING_OUTPUTS, outs))
 
 
-class DecBatch(_StreamLifecycle, _Egress, _RtpStamp, _SrtpProtect):
+class DecBatch(_StreamLifecycle, _Egress, _RtpStamp, _SrtpProtect, _RedPack):
     """n_streams independent decoders (lc3plus_dec_batch_*), state resident on the GPU between decode() calls."""
 
     def __init__(self, n_streams, samplerate, channels, frame_ms, hrmode, num_bytes, device=-1):
@@ -1829,6 +2031,36 @@ class DecBatch(_StreamLifecycle, _Egress, _RtpStamp, _SrtpProtect):
             for k in range(6, 14):
                 back(k)
         return dict(zip(RTP_PARSE_OUTPUTS, outs))
+
+    def red_unpack_device(self, n_items, d_stream_ptr, d_seq_ptr, d_offsets_ptr, d_num_bytes_ptr, d_ring_ptr, ring_capacity, max_red, ts_step, d_out_stream_ptr,
+                          d_out_seq_ptr, d_out_offsets_ptr, d_out_num_bytes_ptr, d_timestamp_ptr=None, d_block_pt_ptr=None, d_out_timestamp_ptr=None,
+                          d_out_gen_ptr=None, d_status_ptr=None, d_stats_ptr=None, hip_stream=None, sync=False):
+        """The receive side of the redundant audio (lc3plus_dec_batch_red_unpack): raw device pointers only - rtp_parse_device's stream, seq, offsets (int64),
+        num_bytes and optional timestamp [n_items] as they stand, over its ring, optional block_pt [n_streams] -> out_stream, out_seq, out_offsets (int64),
+        out_num_bytes [n_items * (max_red + 1)], as ingest_device and probe_device take them, and the optional out_timestamp, out_gen (uint8) of that length,
+        status (uint8) [n_items] and stats [RED_UNPACK_STATS_WORDS].  Stateless: nothing of the batch's streams is read or written.  Queued on hip_stream; returns
+        at once unless sync."""
+        def p(x):
+            return C.c_void_p(x) if x else None
+        rc = self.lib.lc3plus_dec_batch_red_unpack(self.h, int(n_items), p(d_stream_ptr), p(d_seq_ptr), p(d_offsets_ptr), p(d_num_bytes_ptr), p(d_timestamp_ptr),
+                                                   p(d_ring_ptr), int(ring_capacity), int(max_red), p(d_block_pt_ptr), int(ts_step), p(d_out_stream_ptr), p(d_out_seq_ptr),
+                                                   p(d_out_offsets_ptr), p(d_out_num_bytes_ptr), p(d_out_timestamp_ptr), p(d_out_gen_ptr), p(d_status_ptr), p(d_stats_ptr),
+                                                   p(hip_stream), 1 if sync else 0)
+        if rc:
+            raise LC3Error(rc, "lc3plus_dec_batch_red_unpack")
+
+    def red_unpack(self, stream, seq, offsets, num_bytes, ring, ts_step, max_red=RED_MAX_DEPTH, timestamp=None, block_pt=None, optional=RED_UNPACK_OPTIONAL,
+                   ring_capacity=None):
+        """Host convenience: the arrays of plan_red_unpack uploaded, unpacked on the device and downloaded -> the dict plan_red_unpack gives.  Device memory
+        through the HIP runtime as in probe(), freed before it returns."""
+        ins, outs = _red_unpack_arrays(self.n_streams, stream, seq, offsets, num_bytes, timestamp, ring, max_red, block_pt, optional)
+        cap = ins[5].size if ring_capacity is None else int(ring_capacity)
+        with _on_device(ins + outs) as (v, back):
+            self.red_unpack_device(ins[0].size, v[0], v[1], v[2], v[3], v[5], cap, max_red, ts_step, v[7], v[8], v[9], v[10], v[4], v[6], v[11], v[12], v[13], v[14],
+                                   sync=True)
+            for k in range(7, 15):
+                back(k)
+        return dict(zip(RED_UNPACK_OUTPUTS, outs))
 
     def rtcp_stats_device(self, n_items, d_stream_ptr, d_seq_ptr, d_timestamp_ptr, d_arrival_ptr, n_streams, d_state_in_ptr, d_state_out_ptr, d_workspace_ptr,
                           workspace_bytes, make_report=False, d_ssrc_ptr=None, d_lsr_ptr=None, d_dlsr_ptr=None, d_blocks_ptr=None, d_ext_seq_ptr=None,

@@ -29,6 +29,7 @@
 #include "lc3_rtcp_shim.h"
 #include "lc3_srtp_shim.h"
 #include "lc3_gcm_shim.h"
+#include "lc3_red_shim.h"
 
 #ifndef M_PI
 #define M_PI 3.14159265358979323846
@@ -1836,7 +1837,7 @@ LC3_Error lc3plus_frame_info_side(int samplerate, int channels, float frame_ms, 
     return LC3_OK;
 }
 /* ---- the sibling libraries (DESIGN.md "Sibling libraries"): the kernels of every call below lie in a library of their own beside this one ---- */
-enum { SIB_PROBE, SIB_INGEST, SIB_EGRESS, SIB_RTP, SIB_RTCP, SIB_SRTP, SIB_GCM, SIB_COUNT };
+enum { SIB_PROBE, SIB_INGEST, SIB_EGRESS, SIB_RTP, SIB_RTCP, SIB_SRTP, SIB_GCM, SIB_RED, SIB_COUNT };
 /* a row: the file, its one or two entry points, and where they go.  fn holds either all of them or none */
 static struct { const char* file; const char* sym[2]; int tried; void* fn[2]; } siblings[SIB_COUNT] = {
     [SIB_PROBE] = {"liblc3plus_probe_hip.so", {"lc3probe_run", NULL}, 0, {NULL, NULL}},
@@ -1846,6 +1847,7 @@ static struct { const char* file; const char* sym[2]; int tried; void* fn[2]; } 
     [SIB_RTCP] = {"liblc3plus_rtcp_hip.so", {"lc3rtcp_stats_run", NULL}, 0, {NULL, NULL}},
     [SIB_SRTP] = {"liblc3plus_srtp_hip.so", {"lc3srtp_protect_run", "lc3srtp_unprotect_run"}, 0, {NULL, NULL}},
     [SIB_GCM] = {"liblc3plus_gcm_hip.so", {"lc3gcm_protect_run", "lc3gcm_unprotect_run"}, 0, {NULL, NULL}},
+    [SIB_RED] = {"liblc3plus_red_hip.so", {"lc3red_pack_run", "lc3red_unpack_run"}, 0, {NULL, NULL}},
 };
 static pthread_mutex_t sibling_mu = PTHREAD_MUTEX_INITIALIZER;
 /* The entry points of a sibling, or NULL where the library is missing or lacks one of them.  The file is looked for once per process, on the first call that needs
@@ -2315,6 +2317,247 @@ LC3_Error lc3plus_dec_batch_rtp_stamp(lc3plus_dec_batch* b, int64_t max_packets,
     const LC3_Error e = rtp_stamp_check(&a);
     if (e) return e;
     return rtp_stamp_queue(b->dev, 1, &a, hip_stream, sync);
+}
+/* ---- redundant audio (include/lc3plus_batch.h "Redundant audio"; lc3_red_shim.h) ---- */
+/* what every pack call takes behind its batch, in the header's order */
+typedef struct {
+    int n_frames; const void* frames; int64_t frames_capacity; const int64_t* offsets; const int32_t* num_bytes; int max_frame_bytes;
+    const uint8_t* flags; int skip_mask; const int32_t* counts; int n_routes; const int32_t* route_src;
+    int64_t max_packets; const int64_t* n_packets; const int32_t* pkt_route; const int32_t* pkt_frame;
+    int max_depth; const int32_t* depth; const int32_t* block_pt; int ts_step; int max_packet_bytes;
+    const uint8_t* tail_bytes_in; const int32_t* tail_sizes_in; int tail_stride; uint8_t* tail_bytes_out; int32_t* tail_sizes_out;
+    void* wire; int64_t wire_capacity; int header_room; int align;
+    int64_t* red_offset; int32_t* red_size; uint8_t* red_flags; uint8_t* red_blocks; int64_t* wire_total; int32_t* route_stats;
+    void* work;
+} red_pack_args;
+/* the checks every pack call makes first, in the header's order; n_streams < 0: not known yet (the batch is looked at behind them) */
+static LC3_Error red_pack_check(const red_pack_args* a, int n_streams)
+{
+    if (!a->frames || !a->offsets || !a->num_bytes || !a->n_packets || !a->pkt_route || !a->pkt_frame || !a->block_pt || !a->wire || !a->red_offset || !a->red_size ||
+        !a->work)
+        return LC3_NULL_ERROR;
+    if (a->n_frames <= 0 || a->n_routes <= 0 || a->max_frame_bytes <= 0 || a->frames_capacity < 0 || a->wire_capacity < 0 || a->max_packets <= 0 ||
+        a->max_packets >= LC3RED_MAX_PACKETS)
+        return LC3_ERROR;
+    if (a->max_depth < 0 || a->max_depth > LC3RED_MAX_DEPTH || a->ts_step <= 0 || a->max_packet_bytes < 0) return LC3_ERROR;
+    if (!a->tail_bytes_in != !a->tail_sizes_in || !a->tail_bytes_out != !a->tail_sizes_out) return LC3_ERROR;
+    if (a->max_depth && (a->tail_sizes_in || a->tail_sizes_out) && ((a->tail_stride & 15) || a->tail_stride < IMIN(a->max_frame_bytes, LC3RED_MAX_BLOCK))) return LC3_ERROR;
+    if (a->header_room < 0 || a->header_room > INT32_MAX - LC3E_MAX_ALIGN - LC3RED_MAX_EXTRA - a->max_frame_bytes) return LC3_ERROR;
+    if (a->align < 1 || a->align > LC3E_MAX_ALIGN || (a->align & (a->align - 1))) return LC3_ERROR;
+    if (n_streams >= 0 && !a->route_src && a->n_routes != n_streams) return LC3_ERROR;
+    if ((uintptr_t)a->work & 7) return LC3_ERROR;
+    return LC3_OK;
+}
+static lc3red_pack_in red_pack_in(const red_pack_args* a, int n_streams)
+{
+    const lc3red_pack_in q = {a->frames, (const long long*)a->offsets, a->num_bytes, a->flags, a->counts, a->route_src, a->pkt_route, a->pkt_frame, a->depth, a->block_pt,
+                              a->tail_bytes_in, a->tail_sizes_in, (long long)a->frames_capacity, (long long)a->wire_capacity, n_streams, a->n_frames, a->max_frame_bytes,
+                              a->skip_mask, a->n_routes, a->max_depth, a->ts_step, a->max_packet_bytes, a->tail_stride, a->header_room, a->align};
+    return q;
+}
+int64_t lc3plus_red_work_bytes(int64_t max_packets)
+{
+    if (max_packets <= 0 || max_packets >= LC3RED_MAX_PACKETS) return 0;
+    return lc3red_work_bytes((long long)max_packets);
+}
+/* the rule on the host: the steps of the kernels (lc3_red.inc) one after the other, on the text they run and over the same workspace */
+LC3_Error lc3plus_plan_red_pack(int n_streams,
+    int n_frames, const void* frames, int64_t frames_capacity, const int64_t* offsets, const int32_t* num_bytes, int max_frame_bytes,
+    const uint8_t* flags, int skip_mask, const int32_t* counts, int n_routes, const int32_t* route_src,
+    int64_t max_packets, const int64_t* n_packets, const int32_t* pkt_route, const int32_t* pkt_frame,
+    int max_depth, const int32_t* depth, const int32_t* block_pt, int ts_step, int max_packet_bytes,
+    const uint8_t* tail_bytes_in, const int32_t* tail_sizes_in, int tail_stride, uint8_t* tail_bytes_out, int32_t* tail_sizes_out,
+    void* wire, int64_t wire_capacity, int header_room, int align,
+    int64_t* red_offset, int32_t* red_size, uint8_t* red_flags, uint8_t* red_blocks, int64_t* wire_total, int32_t* route_stats,
+    void* work, void* hip_stream, int sync)
+{
+    const red_pack_args a = {n_frames, frames, frames_capacity, offsets, num_bytes, max_frame_bytes, flags, skip_mask, counts, n_routes, route_src, max_packets, n_packets,
+                             pkt_route, pkt_frame, max_depth, depth, block_pt, ts_step, max_packet_bytes, tail_bytes_in, tail_sizes_in, tail_stride, tail_bytes_out,
+                             tail_sizes_out, wire, wire_capacity, header_room, align, red_offset, red_size, red_flags, red_blocks, wire_total, route_stats, work};
+    LC3_Error e = red_pack_check(&a, -1);
+    if (e) return e;
+    if (n_streams <= 0) return LC3_ERROR;
+    e = red_pack_check(&a, n_streams);
+    if (e) return e;
+    const lc3red_pack_in q = red_pack_in(&a, n_streams);
+    const long long n = lc3red_count((const long long*)n_packets, max_packets), n_tiles = lc3red_tiles(max_packets);
+    int32_t* size = (int32_t*)work;
+    long long* sums = (long long*)((char*)work + lc3red_work_sums(max_packets));
+    uint8_t* mask = (uint8_t*)work + lc3red_work_mask(max_packets);
+    /* size */
+    if (route_stats) memset(route_stats, 0, sizeof(int32_t) * LC3RED_RS_WORDS * (size_t)n_routes);
+    for (long long p = 0; p < n; p++) {
+        int s = 0, m = 0;
+        size[p] = lc3red_packet(&q, pkt_route[p], pkt_frame[p], &s, &m);
+        mask[p] = (uint8_t)m;
+    }
+    /* the tiles' sums, then their bases and the total */
+    for (long long b = 0; b < n_tiles; b++) {
+        long long bytes = 0;
+        for (long long p = b * LC3RED_TILE; p < n && p < (b + 1) * LC3RED_TILE; p++) bytes += lc3red_advance(size[p], align);
+        sums[b] = bytes;
+    }
+    long long run_b = 0;
+    for (long long b = 0; b < n_tiles; b++) { const long long bytes = sums[b]; sums[b] = run_b; run_b += bytes; }
+    if (wire_total) *wire_total = run_b;
+    /* scatter, and the copy of each packet that fits */
+    for (long long b = 0; b < n_tiles; b++) {
+        long long run = sums[b];
+        for (long long p = b * LC3RED_TILE; p < n && p < (b + 1) * LC3RED_TILE; p++) {
+            const int32_t sz = size[p];
+            const int fit = lc3e_fits(run, sz, 1, wire_capacity);
+            red_offset[p] = run; red_size[p] = sz;
+            if (red_flags) red_flags[p] = (uint8_t)(sz <= 0 ? LC3RED_PKT_BAD : fit ? 0 : LC3E_PKT_OVERFLOW);
+            if (red_blocks) red_blocks[p] = (uint8_t)(mask[p] & 15);
+            if (sz > 0) {
+                const int r = pkt_route[p], t = pkt_frame[p], s = route_src ? route_src[r] : r, m = mask[p] & 15;
+                int k = 0, block_bytes = 0;
+                for (int j = 1; j <= max_depth; j++) k += m >> (j - 1) & 1;
+                uint8_t* hdr = (uint8_t*)wire + run + header_room;
+                uint8_t* body = hdr + 4 * k + 1;
+                uintptr_t src = 0;
+                for (int j = max_depth; j >= 1; j--) {
+                    if (!(m >> (j - 1) & 1)) continue;
+                    const int32_t bs = lc3red_block(&q, s, t - j, &src);
+                    block_bytes += bs;
+                    if (!fit) continue;
+                    const uint32_t h = lc3red_header(block_pt[r], j * ts_step, bs);
+                    for (int l = 0; l < 4; l++) hdr[l] = (uint8_t)(h >> (8 * l));
+                    egress_copy(body, (const uint8_t*)src, bs);
+                    hdr += 4; body += bs;
+                }
+                if (fit) {
+                    const int32_t nb = lc3red_block(&q, s, t, &src);
+                    *hdr = (uint8_t)(block_pt[r] & 127);
+                    egress_copy(body, (const uint8_t*)src, nb);
+                }
+                if (route_stats) {
+                    int32_t* st = route_stats + (size_t)r * LC3RED_RS_WORDS;
+                    st[LC3RED_RS_PACKETS]++; st[LC3RED_RS_BLOCKS] += k; st[LC3RED_RS_BLOCK_BYTES] += block_bytes; st[LC3RED_RS_MISSED] += mask[p] >> 4;
+                }
+            }
+            run += lc3red_advance(sz, align);
+        }
+    }
+    /* the tails */
+    if (tail_sizes_out)
+        for (int s = 0; s < n_streams; s++)
+            for (int g = 0; g < max_depth; g++) {
+                uintptr_t src = 0;
+                const size_t e_ = (size_t)s * max_depth + g;
+                const int32_t nb = lc3red_tail(&q, s, g, &src);
+                tail_sizes_out[e_] = nb;
+                if (nb > 0) egress_copy(tail_bytes_out + e_ * (size_t)tail_stride, (const uint8_t*)src, nb);
+            }
+    return LC3_OK;
+}
+/* both pack entry points end here.  Of the batch: its device and stream and n_streams.  No stream state, no configuration, no buffer */
+static LC3_Error red_pack_queue(void* dev, int decoder, int n_streams, const red_pack_args* a, void* hip_stream, int sync)
+{
+    if (!a->route_src && a->n_routes != n_streams) return LC3_ERROR;
+    lc3red_pack_call q;
+    memset(&q, 0, sizeof q);
+    void* const* fn = sibling_call(SIB_RED, dev, decoder, hip_stream, &q.device, &q.hip_stream);
+    if (!fn) return LC3_ERROR;
+    q.sync = sync; q.max_packets = (long long)a->max_packets; q.n_packets = (const long long*)a->n_packets; q.in = red_pack_in(a, n_streams);
+    q.tail_bytes_out = a->tail_bytes_out; q.tail_sizes_out = a->tail_sizes_out; q.wire = a->wire;
+    q.red_offset = (long long*)a->red_offset; q.red_size = a->red_size; q.red_flags = a->red_flags; q.red_blocks = a->red_blocks; q.wire_total = (long long*)a->wire_total;
+    q.route_stats = a->route_stats; q.work = a->work;
+    return ((int (*)(const lc3red_pack_call*))fn[0])(&q) ? LC3_ERROR : LC3_OK;
+}
+LC3_Error lc3plus_enc_batch_red_pack(lc3plus_batch* b,
+    int n_frames, const void* frames, int64_t frames_capacity, const int64_t* offsets, const int32_t* num_bytes, int max_frame_bytes,
+    const uint8_t* flags, int skip_mask, const int32_t* counts, int n_routes, const int32_t* route_src,
+    int64_t max_packets, const int64_t* n_packets, const int32_t* pkt_route, const int32_t* pkt_frame,
+    int max_depth, const int32_t* depth, const int32_t* block_pt, int ts_step, int max_packet_bytes,
+    const uint8_t* tail_bytes_in, const int32_t* tail_sizes_in, int tail_stride, uint8_t* tail_bytes_out, int32_t* tail_sizes_out,
+    void* wire, int64_t wire_capacity, int header_room, int align,
+    int64_t* red_offset, int32_t* red_size, uint8_t* red_flags, uint8_t* red_blocks, int64_t* wire_total, int32_t* route_stats,
+    void* work, void* hip_stream, int sync)
+{
+    if (!b) return LC3_NULL_ERROR;
+    const red_pack_args a = {n_frames, frames, frames_capacity, offsets, num_bytes, max_frame_bytes, flags, skip_mask, counts, n_routes, route_src, max_packets, n_packets,
+                             pkt_route, pkt_frame, max_depth, depth, block_pt, ts_step, max_packet_bytes, tail_bytes_in, tail_sizes_in, tail_stride, tail_bytes_out,
+                             tail_sizes_out, wire, wire_capacity, header_room, align, red_offset, red_size, red_flags, red_blocks, wire_total, route_stats, work};
+    const LC3_Error e = red_pack_check(&a, -1);
+    if (e) return e;
+    return red_pack_queue(b->dev, 0, b->n_streams, &a, hip_stream, sync);
+}
+LC3_Error lc3plus_dec_batch_red_pack(lc3plus_dec_batch* b,
+    int n_frames, const void* frames, int64_t frames_capacity, const int64_t* offsets, const int32_t* num_bytes, int max_frame_bytes,
+    const uint8_t* flags, int skip_mask, const int32_t* counts, int n_routes, const int32_t* route_src,
+    int64_t max_packets, const int64_t* n_packets, const int32_t* pkt_route, const int32_t* pkt_frame,
+    int max_depth, const int32_t* depth, const int32_t* block_pt, int ts_step, int max_packet_bytes,
+    const uint8_t* tail_bytes_in, const int32_t* tail_sizes_in, int tail_stride, uint8_t* tail_bytes_out, int32_t* tail_sizes_out,
+    void* wire, int64_t wire_capacity, int header_room, int align,
+    int64_t* red_offset, int32_t* red_size, uint8_t* red_flags, uint8_t* red_blocks, int64_t* wire_total, int32_t* route_stats,
+    void* work, void* hip_stream, int sync)
+{
+    if (!b) return LC3_NULL_ERROR;
+    const red_pack_args a = {n_frames, frames, frames_capacity, offsets, num_bytes, max_frame_bytes, flags, skip_mask, counts, n_routes, route_src, max_packets, n_packets,
+                             pkt_route, pkt_frame, max_depth, depth, block_pt, ts_step, max_packet_bytes, tail_bytes_in, tail_sizes_in, tail_stride, tail_bytes_out,
+                             tail_sizes_out, wire, wire_capacity, header_room, align, red_offset, red_size, red_flags, red_blocks, wire_total, route_stats, work};
+    const LC3_Error e = red_pack_check(&a, -1);
+    if (e) return e;
+    return red_pack_queue(b->dev, 1, b->n_streams, &a, hip_stream, sync);
+}
+/* what an unpack call takes behind its batch, in the header's order */
+typedef struct {
+    int64_t n_items; const int32_t* stream; const int32_t* seq; const int64_t* offsets; const int32_t* num_bytes; const int32_t* timestamp;
+    const void* ring; int64_t ring_capacity; int max_red; const int32_t* block_pt; int ts_step;
+    int32_t* out_stream; int32_t* out_seq; int64_t* out_offsets; int32_t* out_num_bytes; int32_t* out_timestamp; uint8_t* out_gen; uint8_t* status; int32_t* stats;
+} red_unpack_args;
+static LC3_Error red_unpack_check(const red_unpack_args* a)
+{
+    if (!a->stream || !a->seq || !a->offsets || !a->num_bytes || !a->ring || !a->out_stream || !a->out_seq || !a->out_offsets || !a->out_num_bytes) return LC3_NULL_ERROR;
+    if (a->n_items <= 0 || a->n_items >= LC3R_MAX_ITEMS || a->ring_capacity < 0 || a->max_red < 0 || a->max_red > LC3RED_MAX_DEPTH || a->ts_step <= 0) return LC3_ERROR;
+    return LC3_OK;
+}
+static lc3red_unpack_io red_unpack_io(const red_unpack_args* a, int n_streams)
+{
+    const lc3red_unpack_io q = {a->stream, a->seq, (const long long*)a->offsets, a->num_bytes, a->timestamp, (const uint8_t*)a->ring, a->block_pt, a->out_stream, a->out_seq,
+                                (long long*)a->out_offsets, a->out_num_bytes, a->out_timestamp, a->out_gen, a->status, (long long)a->ring_capacity, n_streams, a->max_red,
+                                a->ts_step};
+    return q;
+}
+/* the rule on the host: the kernels' steps (lc3_red.inc) on the text they run */
+LC3_Error lc3plus_plan_red_unpack(int n_streams, int64_t n_items,
+    const int32_t* stream, const int32_t* seq, const int64_t* offsets, const int32_t* num_bytes, const int32_t* timestamp,
+    const void* ring, int64_t ring_capacity, int max_red, const int32_t* block_pt, int ts_step,
+    int32_t* out_stream, int32_t* out_seq, int64_t* out_offsets, int32_t* out_num_bytes, int32_t* out_timestamp, uint8_t* out_gen, uint8_t* status, int32_t* stats,
+    void* hip_stream, int sync)
+{
+    const red_unpack_args a = {n_items, stream, seq, offsets, num_bytes, timestamp, ring, ring_capacity, max_red, block_pt, ts_step,
+                               out_stream, out_seq, out_offsets, out_num_bytes, out_timestamp, out_gen, status, stats};
+    const LC3_Error e = red_unpack_check(&a);
+    if (e) return e;
+    if (n_streams <= 0) return LC3_ERROR;
+    const lc3red_unpack_io q = red_unpack_io(&a, n_streams);
+    if (stats) memset(stats, 0, sizeof(int32_t) * LC3RED_STATS_WORDS);
+    for (int64_t i = 0; i < n_items; i++) {
+        int drops[3] = {0, 0, 0};
+        const int st = lc3red_unpack(&q, i, drops);
+        if (stats) { stats[st]++; stats[LC3RED_ST_DROP_TYPE] += drops[0]; stats[LC3RED_ST_DROP_OFFSET] += drops[1]; stats[LC3RED_ST_DROP_EMPTY] += drops[2]; }
+    }
+    return LC3_OK;
+}
+LC3_Error lc3plus_dec_batch_red_unpack(lc3plus_dec_batch* b, int64_t n_items,
+    const int32_t* stream, const int32_t* seq, const int64_t* offsets, const int32_t* num_bytes, const int32_t* timestamp,
+    const void* ring, int64_t ring_capacity, int max_red, const int32_t* block_pt, int ts_step,
+    int32_t* out_stream, int32_t* out_seq, int64_t* out_offsets, int32_t* out_num_bytes, int32_t* out_timestamp, uint8_t* out_gen, uint8_t* status, int32_t* stats,
+    void* hip_stream, int sync)
+{
+    if (!b) return LC3_NULL_ERROR;
+    const red_unpack_args a = {n_items, stream, seq, offsets, num_bytes, timestamp, ring, ring_capacity, max_red, block_pt, ts_step,
+                               out_stream, out_seq, out_offsets, out_num_bytes, out_timestamp, out_gen, status, stats};
+    const LC3_Error e = red_unpack_check(&a);
+    if (e) return e;
+    lc3red_unpack_call q;
+    memset(&q, 0, sizeof q);
+    void* const* fn = sibling_call(SIB_RED, b->dev, 1, hip_stream, &q.device, &q.hip_stream);
+    if (!fn) return LC3_ERROR;
+    q.sync = sync; q.n_items = (long long)n_items; q.io = red_unpack_io(&a, b->n_streams); q.stats = stats;
+    return ((int (*)(const lc3red_unpack_call*))fn[1])(&q) ? LC3_ERROR : LC3_OK;
 }
 /* ---- reception reports (include/lc3plus_batch.h "Reception reports"; lc3_rtcp_shim.h) ---- */
 /* what a stats call takes behind its batch, in the header's order */

@@ -714,8 +714,9 @@ int64_t lc3plus_egress_work_bytes(int n_routes, int n_frames);
  * is an RTP header there.  lc3plus_dec_batch_rtp_parse turns the first into the second and lc3plus_*_batch_rtp_stamp fills the third, so that
  * datagrams -> parse -> probe -> ingest -> set_frame_counts + decode_packed and encode_packed -> egress -> stamp run on one HIP stream with no host wait.
  * A payload format's own payload header (the LC3plus table of contents is one) stays with the caller: the stamp leaves payload_room untouched bytes between
- * the RTP header and the frame, and the parse skips payload_room bytes.  SRTP is the block "Secure RTP" below; the contents of RTCP packets (SRTCP with them) and
- * several frames per packet are not handled.
+ * the RTP header and the frame, and the parse skips payload_room bytes.  SRTP is the block "Secure RTP" below; the contents of RTCP packets (SRTCP with them) are
+ * not handled.  Several frames per packet are the block "Redundant audio" below: RFC 2198 packets, a primary frame with up to four earlier ones; other
+ * aggregations are not handled.
  *
  * Every pointer but `batch` is a device pointer and is read when the kernels run, so the call queued before on the same stream may produce it.  Both calls are
  * STATELESS and allocate nothing: they borrow the batch's device and n_streams and nothing else, no stream state, configuration or buffer of the batch is read
@@ -830,6 +831,154 @@ LC3_Error lc3plus_plan_rtp_stamp(int64_t max_packets, const int64_t* n_packets,
     int marker_mode, const uint8_t* cell_status, const uint8_t* resume, const int32_t* route_stats,
     void* wire, int64_t wire_capacity, int header_room, int payload_room,
     uint8_t* pkt_status, int32_t* next_ts, uint8_t* next_resume, void* hip_stream, int sync);
+
+/* ---- Redundant audio: pack and unpack RFC 2198 (RED) packets, on the device ---------------------------------------------------------------------------------
+ * The answer to a lost packet other than the decoder's concealment: every packet also carries the one to four frames before its own, so a burst of losses up
+ * to the depth costs bytes and no audio.  lc3plus_*_batch_red_pack writes such packets behind the in-place egress, lc3plus_dec_batch_red_unpack takes them
+ * apart in front of the probe and the ingest, whose one-copy-per-cell rule already lets any copy of a frame fill its cell:
+ *   sender    encode_packed -> egress (in place) -> red_pack -> stamp -> protect
+ *   forwarder ... -> ingest -> egress (in place) -> red_pack -> stamp
+ *   receiver  unprotect -> parse -> red_unpack -> probe -> ingest -> set_frame_counts + decode_packed
+ * on one HIP stream with no host wait.  lc3plus_dec_batch_rtcp_stats keeps taking the parse's arrays, not the unpack's: a redundant block is no packet received.
+ *
+ * Every pointer but `batch` is a device pointer and is read when the kernels run.  The calls are STATELESS and allocate nothing, as the egress and the RTP calls
+ * are: they borrow the batch's device and n_streams and nothing else, and may run beside an encode or decode call of the same batch.  They are queued on
+ * hip_stream (NULL: the batch's stream) and return at once unless sync.  No output may overlap an input or another output.
+ *
+ * The payload of a packet with k redundant blocks (RFC 2198 section 3): k headers of four bytes - 1 | PT(7), then a 14-bit timestamp offset and a 10-bit block
+ * length, big-endian - one final byte 0 | PT(7), the k blocks oldest first, and the primary frame, which runs to the payload's end.  The RTP header's own
+ * payload type is the RED type: the stamp's payload_type[r], as that call stands.
+ *
+ * PACK.
+ *   n_frames, frames, frames_capacity, offsets, num_bytes, max_frame_bytes, flags, skip_mask, counts, n_routes, route_src : the frame tables, as the egress
+ *                           call before took them
+ *   max_packets, n_packets, pkt_route, pkt_frame : that call's list (in-place mode); its pkt_seq is not needed here, the stamp reads it
+ *   max_depth             : 0 ... LC3PLUS_RED_MAX_DEPTH, the most generations a packet carries
+ *   depth                 : [n_routes] each route's depth, clamped to [0, max_depth]; or NULL: max_depth for all
+ *   block_pt              : [n_routes] the payload type of the blocks and the primary (its low 7 bits)
+ *   ts_step               : a frame's samples on the RTP clock, > 0; max_packet_bytes: the size no packet exceeds for the sake of redundancy, >= 0
+ *   tail_bytes_in (uint8) [n_streams][max_depth][tail_stride], tail_sizes_in [n_streams][max_depth] : the history the previous call left, both or neither.  Entry g
+ *                           is frame g + 1 before frame 0; a size outside 1 ... min(1023, tail_stride) means none.  tail_stride: a multiple of 16, at least
+ *                           min(max_frame_bytes, 1023)
+ *   tail_bytes_out, tail_sizes_out : the history for the next call, both or neither
+ *   wire, wire_capacity, header_room, align : the send buffer, under the constraints of the egress's wire mode (header_room + max_frame_bytes + 4 * 1027 + 1 +
+ *                           4096 must fit an int32)
+ *   red_offset (int64), red_size, red_flags (uint8), red_blocks (uint8) : [max_packets] the packet records
+ *   wire_total : one int64; route_stats : [n_routes][LC3PLUS_RED_STATS_WORDS]
+ *   work       : lc3plus_red_work_bytes(max_packets) bytes, 8-byte aligned; its contents mean nothing before or after the call
+ *   flags, counts, route_src, depth, the tails, red_flags, red_blocks, wire_total and route_stats may each be NULL.
+ * The primary.  For each packet p < min(*n_packets, max_packets), with r = pkt_route[p], t = pkt_frame[p], and s and c the egress's route rule for r: the packet
+ *   is BAD where r lies outside [0, n_routes), t outside [0, n_frames), the route is bad, t >= c, or frame (s, t) is not SENT under the egress's cell rule.  A
+ *   BAD packet has red_size 0, red_flags LC3PLUS_RED_PKT_BAD and red_blocks 0; it advances nothing, writes nothing and is in no route's stats.
+ * The blocks.  Generations j = 1 ... depth are looked at in that order; generation j is frame u = t - j of stream s: at u >= 0 frame (s, u) of the tables, which
+ *   exists where its cell is SENT; at u < 0 entry -u - 1 of the stream's tail, which exists where tails are given and its size says so.  A generation that exists
+ *   is carried when its size is at most 1023, j * ts_step <= 16383, and header_room + 1 + the primary's size + (4 + size) of every generation carried so far +
+ *   4 + its size <= max_packet_bytes; otherwise it is counted as missed, and the generations behind it are still looked at.  The primary is always carried.
+ * The record.  red_blocks has bit j - 1 for every carried generation; red_size = header_room + the payload's size; red_offset is the exclusive scan, in list order
+ *   and from 0, of red_size rounded up to align, and *wire_total its end.  A packet with red_offset + red_size > wire_capacity keeps its record, gets
+ *   LC3PLUS_EGR_PKT_OVERFLOW in red_flags and writes nothing.  Every other packet writes exactly [red_offset + header_room, red_offset + red_size) of wire: the
+ *   headers with offset j * ts_step, the block's size and block_pt[r], the final byte, the blocks oldest first, the primary.  Of frames and the tails only
+ *   aligned 32-bit words that hold a byte of a copied frame are read.  Entries at or behind *n_packets are not written.
+ *   The stamp then takes red_offset, red_size and red_flags as its list's offset, size and flags, with payload_room = 0 (a BAD packet is ST_RANGE there); the
+ *   protect calls follow unchanged.
+ * route_stats[r] = {packets that are not BAD, blocks carried, bytes of the carried blocks, generations missed}; packets that overflow are counted.
+ * Tails.  For stream s with c = min(max(counts[s], 0), n_frames) and g = 0 ... max_depth - 1, u = c - 1 - g: at u >= 0 entry g is frame (s, u) where its cell is
+ *   SENT and its size at most 1023, otherwise size 0; at u < 0 it is entry g - c of the tail input, size 0 without one.  The bytes lie at the slot's start.  A
+ *   stream with c = 0 hands its history through, so the caller alternates between two tail buffers.
+ * Refused calls queue nothing, checked in this order before anything of the batch or the device is touched: a NULL batch, frames, offsets, num_bytes, n_packets,
+ * pkt_route, pkt_frame, block_pt, wire, red_offset, red_size or work (LC3_NULL_ERROR); then n_frames <= 0, n_routes <= 0, max_frame_bytes <= 0,
+ * frames_capacity < 0, wire_capacity < 0, max_packets <= 0 or >= 2^31, max_depth outside [0, 4], ts_step <= 0, max_packet_bytes < 0, one of a tail's two arrays
+ * without the other, a bad tail_stride where max_depth > 0 and a tail is given, a bad header_room or align, a NULL route_src with n_routes != n_streams, or a
+ * work that is not 8-byte aligned (LC3_ERROR).
+ *
+ * UNPACK.  Item i is the payload ring[offsets[i] .. offsets[i] + num_bytes[i]) of stream[i] with sequence number seq[i]: the parse's outputs as they stand.
+ *   stream, seq, offsets (int64), num_bytes, timestamp : [n_items]; timestamp may be NULL (taken as 0)
+ *   ring, ring_capacity : the buffer the payloads lie in and its size
+ *   max_red   : 0 ... 4, the most redundant blocks taken from a packet
+ *   block_pt  : [n_streams] the payload type each stream's blocks and primary must have, < 0: any; or NULL: any for all
+ *   ts_step   : a frame's samples on the RTP clock, > 0
+ *   out_stream, out_seq, out_offsets (int64), out_num_bytes : [n_items * (max_red + 1)] the item arrays of the probe and the ingest
+ *   out_timestamp, out_gen (uint8) : of that length, each may be NULL; status (uint8) [n_items] and stats [LC3PLUS_RED_STATS_WORDS] may be NULL
+ * Item i owns slots i * (max_red + 1) + k: slot 0 is the primary, slot k >= 1 the k-th redundant header in wire order.  An unused or dropped slot has stream -1
+ * and 0 everywhere else: the ingest drops it as BAD_STREAM and the probe reads it as lost, so the arrays go to both as they are.
+ * The first check that fails gives the item's status:
+ *   1 DROPPED      stream[i] lies outside [0, n_streams): what the parse refused
+ *   2 RANGE        offsets[i] < 0, num_bytes[i] < 0 or offset + size > ring_capacity (computed without overflow); such a payload is never read
+ *   3 SHORT        the payload ends inside the header list: in front of a header's first byte or inside a header with the F bit; size 0 is SHORT
+ *   4 DEPTH        more than max_red headers have the F bit
+ *   5 LENGTH       the header bytes plus the block lengths exceed the payload
+ *   6 PAYLOAD_TYPE block_pt is given, block_pt[s] >= 0 and it differs from the final byte's type
+ * A refused item fills none of its slots.  In an OK item a single block is dropped, in this order, for a type that differs from a block_pt[s] >= 0, for a
+ * timestamp offset that is 0 or no multiple of ts_step, and for a length of 0; it is tallied in stats[8], stats[9] or stats[10].  A kept block gets
+ * out_seq = (seq - offset / ts_step) mod 2^16, out_timestamp = timestamp - offset, out_gen = offset / ts_step (255 above that), and its place and length in the
+ * ring.  The primary gets seq, timestamp, gen 0 and the rest of the payload; a rest of 0 bytes is the ingest's EMPTY.  stats[k], k < 8, is the number of items
+ * with status k; the call zeroes stats.  Of a payload only header bytes are read - of a header behind the max_red-th only its first - and of the ring only
+ * aligned 32-bit words that hold such a byte; block bytes are never touched.
+ * The sequence numbers of blocks assume a sender that numbers by position, as the egress does: a frame's number is the packet's minus its generation.  Placing
+ * blocks by timestamp for other senders is not done.
+ * Refused calls queue nothing, checked in this order: a NULL batch, stream, seq, offsets, num_bytes, ring, out_stream, out_seq, out_offsets or out_num_bytes
+ * (LC3_NULL_ERROR); then n_items <= 0, n_items >= 2^29, ring_capacity < 0, max_red outside [0, 4] or ts_step <= 0 (LC3_ERROR).
+ *
+ * The kernels live in liblc3plus_red_hip.so, which this library loads from its own directory on the first RED call: where that file is missing the RED calls
+ * alone return LC3_ERROR and nothing else changes. */
+#define LC3PLUS_RED_MAX_DEPTH      4
+#define LC3PLUS_RED_PKT_BAD        2
+#define LC3PLUS_RED_STATS_WORDS    4
+#define LC3PLUS_RED_OK             0
+#define LC3PLUS_RED_DROPPED        1
+#define LC3PLUS_RED_RANGE          2
+#define LC3PLUS_RED_SHORT          3
+#define LC3PLUS_RED_DEPTH          4
+#define LC3PLUS_RED_LENGTH         5
+#define LC3PLUS_RED_PAYLOAD_TYPE   6
+#define LC3PLUS_RED_DROP_TYPE      8
+#define LC3PLUS_RED_DROP_OFFSET    9
+#define LC3PLUS_RED_DROP_EMPTY     10
+#define LC3PLUS_RED_UNPACK_STATS_WORDS 16
+LC3_Error lc3plus_enc_batch_red_pack(lc3plus_batch* batch,
+    int n_frames, const void* frames, int64_t frames_capacity, const int64_t* offsets, const int32_t* num_bytes, int max_frame_bytes,
+    const uint8_t* flags, int skip_mask, const int32_t* counts, int n_routes, const int32_t* route_src,
+    int64_t max_packets, const int64_t* n_packets, const int32_t* pkt_route, const int32_t* pkt_frame,
+    int max_depth, const int32_t* depth, const int32_t* block_pt, int ts_step, int max_packet_bytes,
+    const uint8_t* tail_bytes_in, const int32_t* tail_sizes_in, int tail_stride, uint8_t* tail_bytes_out, int32_t* tail_sizes_out,
+    void* wire, int64_t wire_capacity, int header_room, int align,
+    int64_t* red_offset, int32_t* red_size, uint8_t* red_flags, uint8_t* red_blocks, int64_t* wire_total, int32_t* route_stats,
+    void* work, void* hip_stream, int sync);
+LC3_Error lc3plus_dec_batch_red_pack(lc3plus_dec_batch* batch,
+    int n_frames, const void* frames, int64_t frames_capacity, const int64_t* offsets, const int32_t* num_bytes, int max_frame_bytes,
+    const uint8_t* flags, int skip_mask, const int32_t* counts, int n_routes, const int32_t* route_src,
+    int64_t max_packets, const int64_t* n_packets, const int32_t* pkt_route, const int32_t* pkt_frame,
+    int max_depth, const int32_t* depth, const int32_t* block_pt, int ts_step, int max_packet_bytes,
+    const uint8_t* tail_bytes_in, const int32_t* tail_sizes_in, int tail_stride, uint8_t* tail_bytes_out, int32_t* tail_sizes_out,
+    void* wire, int64_t wire_capacity, int header_room, int align,
+    int64_t* red_offset, int32_t* red_size, uint8_t* red_flags, uint8_t* red_blocks, int64_t* wire_total, int32_t* route_stats,
+    void* work, void* hip_stream, int sync);
+/* The same rule on the host alone, no device: the same arrays in host memory (n_packets and work too), n_streams given instead of a batch; the frames are copied
+ * as the copy kernel copies them.  hip_stream and sync are ignored.  The refusals of the calls above in their order, with n_streams <= 0 (LC3_ERROR) in front of
+ * the route_src check. */
+LC3_Error lc3plus_plan_red_pack(int n_streams,
+    int n_frames, const void* frames, int64_t frames_capacity, const int64_t* offsets, const int32_t* num_bytes, int max_frame_bytes,
+    const uint8_t* flags, int skip_mask, const int32_t* counts, int n_routes, const int32_t* route_src,
+    int64_t max_packets, const int64_t* n_packets, const int32_t* pkt_route, const int32_t* pkt_frame,
+    int max_depth, const int32_t* depth, const int32_t* block_pt, int ts_step, int max_packet_bytes,
+    const uint8_t* tail_bytes_in, const int32_t* tail_sizes_in, int tail_stride, uint8_t* tail_bytes_out, int32_t* tail_sizes_out,
+    void* wire, int64_t wire_capacity, int header_room, int align,
+    int64_t* red_offset, int32_t* red_size, uint8_t* red_flags, uint8_t* red_blocks, int64_t* wire_total, int32_t* route_stats,
+    void* work, void* hip_stream, int sync);
+/* the bytes of `work` for such a call; 0 for a max_packets the calls refuse */
+int64_t lc3plus_red_work_bytes(int64_t max_packets);
+LC3_Error lc3plus_dec_batch_red_unpack(lc3plus_dec_batch* batch, int64_t n_items,
+    const int32_t* stream, const int32_t* seq, const int64_t* offsets, const int32_t* num_bytes, const int32_t* timestamp,
+    const void* ring, int64_t ring_capacity, int max_red, const int32_t* block_pt, int ts_step,
+    int32_t* out_stream, int32_t* out_seq, int64_t* out_offsets, int32_t* out_num_bytes, int32_t* out_timestamp, uint8_t* out_gen, uint8_t* status, int32_t* stats,
+    void* hip_stream, int sync);
+/* The same rule on the host alone: the same arrays in host memory, n_streams given instead of a batch; the payloads are read byte by byte.  hip_stream and sync
+ * are ignored.  The refusals of the call above in their order, then n_streams <= 0 (LC3_ERROR). */
+LC3_Error lc3plus_plan_red_unpack(int n_streams, int64_t n_items,
+    const int32_t* stream, const int32_t* seq, const int64_t* offsets, const int32_t* num_bytes, const int32_t* timestamp,
+    const void* ring, int64_t ring_capacity, int max_red, const int32_t* block_pt, int ts_step,
+    int32_t* out_stream, int32_t* out_seq, int64_t* out_offsets, int32_t* out_num_bytes, int32_t* out_timestamp, uint8_t* out_gen, uint8_t* status, int32_t* stats,
+    void* hip_stream, int sync);
 
 /* ---- Reception reports: per-stream RTP statistics and RR report blocks, on the device ----------------------------------------------------------------------
  * A receiver owes its senders RTCP reception reports (RFC 3550 6.4): per source the extended highest sequence number, the cumulative loss, the loss fraction
