@@ -20,7 +20,7 @@ EXPORTS = [
     "lc3_enc_fl", "lc3_enc16", "lc3_enc24", "lc3_enc32", "lc3_enc_free_memory", "lc3_free_encoder_structs",
     "lc3plus_enc_batch_create", "lc3plus_enc_batch_destroy", "lc3plus_enc_batch_input_samples",
     "lc3plus_enc_batch_num_bytes", "lc3plus_enc_batch_stride", "lc3plus_enc_batch_set_bitrate",
-    "lc3plus_enc_batch_set_bandwidth", "lc3plus_enc_batch_encode", "lc3plus_enc_batch_last_kernel_ms", "lc3plus_enc_batch_last_status", "lc3plus_enc_batch_last_records", "lc3plus_enc_batch_record_words", "lc3plus_enc_batch_set_input_ready", "lc3plus_enc_batch_state_size", "lc3plus_enc_batch_get_state", "lc3plus_enc_batch_set_state",
+    "lc3plus_enc_batch_set_bandwidth", "lc3plus_enc_batch_encode", "lc3plus_enc_batch_last_kernel_ms", "lc3plus_enc_batch_last_status", "lc3plus_enc_batch_last_records", "lc3plus_enc_batch_record_words", "lc3plus_enc_batch_work_buffer", "lc3plus_dec_batch_work_buffer", "lc3plus_enc_batch_set_input_ready", "lc3plus_enc_batch_state_size", "lc3plus_enc_batch_get_state", "lc3plus_enc_batch_set_state",
     "lc3plus_dec_batch_state_size", "lc3plus_dec_batch_get_state", "lc3plus_dec_batch_set_state",
     "lc3plus_enc_init", "lc3plus_enc_set_frame_ms", "lc3plus_enc_set_hrmode", "lc3plus_enc_set_bitrate",
     "lc3plus_enc16", "lc3plus_enc_get_size",
@@ -208,6 +208,7 @@ def load_library():
         L.lc3plus_enc_batch_last_kernel_ms.argtypes = [C.c_void_p]
         L.lc3plus_enc_batch_last_status.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         L.lc3plus_enc_batch_last_records.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+        L.lc3plus_enc_batch_work_buffer.argtypes = L.lc3plus_dec_batch_work_buffer.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 4
         L.lc3plus_enc_batch_set_input_ready.argtypes = [C.c_void_p, C.c_int]
         for nm in ("lc3plus_enc_batch", "lc3plus_dec_batch"):
             getattr(L, nm + "_state_size").argtypes = [C.c_void_p]; getattr(L, nm + "_state_size").restype = C.c_size_t
@@ -326,6 +327,18 @@ def load_library():
         L.lc3plus_plan_red_unpack.argtypes = [C.c_int] + unred
         _LIB = L
     return _LIB
+
+
+WORK_ELEM = {1: np.float32, 2: np.int32, 3: np.uint16, 4: np.uint8, 5: np.int64}        # LC3HIP_ELEM_* (lc3_shim.h)
+
+
+def _work_buffers(fn, h):
+    """the work buffers of a batch as the host runtime lists them: [(name, device pointer or None, bytes, numpy element type)]; waits for the batch's last call"""
+    out = []
+    name, ptr, nbytes, elem = C.c_char_p(), C.c_void_p(), C.c_size_t(), C.c_int()
+    while fn(h, len(out), C.byref(name), C.byref(ptr), C.byref(nbytes), C.byref(elem)) == 0:
+        out.append((name.value.decode(), ptr.value, int(nbytes.value), WORK_ELEM[elem.value]))
+    return out
 
 
 @contextlib.contextmanager
@@ -1448,6 +1461,10 @@ class Batch(_StreamLifecycle, _Egress, _RtpStamp, _SrtpProtect, _RedPack):
             raise LC3Error(1, "lc3plus_enc_batch_last_records (%d of %d words: T does not match the last call)" % (n, rec.size))
         return rec
 
+    def work_buffers(self):
+        """diagnostics (LC3PLUS_POISON_WORK): [(name, device pointer or None, bytes, numpy element type)] of the batch's work buffers"""
+        return _work_buffers(self.lib.lc3plus_enc_batch_work_buffer, self.h)
+
     def encode_traced(self, pcm, bitdepth=16, bitrates=None):
         pcm = np.ascontiguousarray(pcm)
         T = pcm.shape[1]
@@ -2181,6 +2198,10 @@ class DecBatch(_StreamLifecycle, _Egress, _RtpStamp, _SrtpProtect, _RedPack):
 
     def last_kernel_ms(self):
         return float(self.lib.lc3plus_dec_batch_last_kernel_ms(self.h))
+
+    def work_buffers(self):
+        """as Batch.work_buffers"""
+        return _work_buffers(self.lib.lc3plus_dec_batch_work_buffer, self.h)
 
     def close(self):
         if self.h:

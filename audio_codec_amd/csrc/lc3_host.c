@@ -1045,6 +1045,12 @@ int lc3plus_enc_batch_last_records(lc3plus_batch* b, float* records, int max_wor
     return lc3hip_last_records(b->dev, records, max_words);
 }
 int lc3plus_enc_batch_record_words(void) { return FR_WORDS; }
+LC3_Error lc3plus_enc_batch_work_buffer(lc3plus_batch* b, int i, const char** name, void** ptr, size_t* bytes, int* elem)
+{
+    if (!b || !name || !ptr || !bytes || !elem) return LC3_NULL_ERROR;
+    if (lc3hip_wait(b->dev)) return LC3_ERROR;
+    return lc3hip_work_buffer(b->dev, i, name, ptr, bytes, elem) ? LC3_ERROR : LC3_OK;
+}
 
 size_t lc3plus_enc_batch_state_size(const lc3plus_batch* b) { return b ? lc3hip_state_bytes(b->dev) : 0; }
 LC3_Error lc3plus_enc_batch_get_state(lc3plus_batch* b, void* state, size_t size)
@@ -1781,6 +1787,12 @@ LC3_Error lc3plus_dec_batch_decode_traced(lc3plus_dec_batch* b, const void* fram
 }
 int lc3plus_dec_trace_sizeof(void) { return (int)sizeof(lc3d_dec_trace); }
 float lc3plus_dec_batch_last_kernel_ms(lc3plus_dec_batch* b) { return b ? lc3hip_dec_last_ms(b->dev) : 0.0f; }
+LC3_Error lc3plus_dec_batch_work_buffer(lc3plus_dec_batch* b, int i, const char** name, void** ptr, size_t* bytes, int* elem)
+{
+    if (!b || !name || !ptr || !bytes || !elem) return LC3_NULL_ERROR;
+    if (lc3hip_dec_wait(b->dev)) return LC3_ERROR;
+    return lc3hip_dec_work_buffer(b->dev, i, name, ptr, bytes, elem) ? LC3_ERROR : LC3_OK;
+}
 LC3_Error lc3plus_dec_batch_set_pcm_placement(lc3plus_dec_batch* b, const int64_t* offsets, int64_t capacity)
 {
     if (!b) return LC3_NULL_ERROR;

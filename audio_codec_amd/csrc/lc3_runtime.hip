@@ -83,7 +83,8 @@ static struct census_env {
  * that drive two batches never race on them, and a context's behaviour does not change under it. */
 struct lc3hip_opts {
     int fused, no_split, streams5, run_frames, runs, ahead_max, rate_stream /* -1 rule, 0, 1 */, pre_runs, pitch2, scf_wave, front4, shape_fpw, shape_on_s, shape_wave,
-        pack_wpg, pack_stream /* -1 off (default), 0, 1 */, resample48, resample96, dec_imdct4, check_ready, tailw_bytes, dec_parse_pad_kb, pack_pad_kb, pack_split, pack_w5, fuse_vq, stream_order, stream_skip, rate_on, dec_plc_stream, shape_on_pitch, side_prio, ragged_pipe;
+        pack_wpg, pack_stream /* -1 off (default), 0, 1 */, resample48, resample96, dec_imdct4, check_ready, tailw_bytes, dec_parse_pad_kb, pack_pad_kb, pack_split, pack_w5, fuse_vq, stream_order, stream_skip, rate_on, dec_plc_stream, shape_on_pitch, side_prio, ragged_pipe,
+        poison_work /* 0 off, 1 set A, 2 set B */, poison_calls;
 };
 static int env_int(const char* name, int lo, int hi, int dflt) { const char* e = getenv(name); if (!e || !*e) return dflt; const int v = atoi(e); return v >= lo && v <= hi ? v : dflt; }
 static void read_opts(lc3hip_opts* o)
@@ -124,7 +125,18 @@ static void read_opts(lc3hip_opts* o)
     o->ragged_pipe = env_int("LC3PLUS_ENC_RAGGED_PIPE", 0, 1, 1);         /* 0 = every ragged encode call on the one-wave kernels, whatever its length (enc_launch: the A/B handle and a deployment's fallback) */
     o->check_ready = env_int("LC3PLUS_CHECK_READY", 0, 1, 0);        /* debug aid for lc3plus_enc_batch_set_input_ready: refuse a call made while foreign work is pending on the caller's stream */
     o->dec_imdct4 = env_int("LC3PLUS_DEC_IMDCT4", 0, 1, 1);          /* 0 = the one-frame-at-a-time IMDCT for N = 480 too */
+    /* poisoned workspaces (work_poison_new, work_poison_all): A or B fills every work buffer with that set's typed poison where it is allocated; with
+     * LC3PLUS_POISON_CALLS=1 every encode and decode call fills all of them again at its entry.  Debugging aids, off by default */
+    { const char* e = getenv("LC3PLUS_POISON_WORK"); o->poison_work = e && (e[0] == 'A' || e[0] == 'B') && !e[1] ? 1 + (e[0] == 'B') : 0; }
+    o->poison_calls = o->poison_work ? env_int("LC3PLUS_POISON_CALLS", 0, 1, 0) : 0;
 }
+/* The work buffers of a batch: the device buffers that a call fills and reads itself, and that no later call may rely on (DESIGN.md "Every workspace word").  One
+ * table per context struct lists them (enc_work, dec_work): member, how many pointers the member holds, element type, and the bytes of pointer k as they follow from
+ * the capacity the context keeps for it.  The poison routines and the two debug entries (lc3hip_work_buffer, lc3hip_dec_work_buffer) walk the table;
+ * tests/test_poison_work_cpu.py holds it to the structs. */
+struct work_buf { const char* name; size_t off; int n, elem; size_t (*bytes)(const void* ctx, int k); };
+struct work_set { const void* ctx; const work_buf* tab; int n_tab, set /* lc3hip_opts.poison_work */, calls; };
+#define WORK(T, member, n, elem, bytes_expr) {#member, offsetof(T, member), n, elem, [](const void* p_, int k) -> size_t { const T* c = (const T*)p_; (void)k; return (size_t)(bytes_expr); }}
 /* What a batch keeps for those calls: the fresh-row template, and LC3D_SETS staging slots (pinned host memory for the index list, configuration entries and
  * host blobs, and its device copy) used in turn, each guarded by the event recorded behind the call that used it last; ev_done: behind the last call, for
  * later calls on other streams */
@@ -137,7 +149,7 @@ struct lc3hip_ss {
  * once the call that read it has finished (calls with sync = 0) - its event is recorded by the caller behind the last kernel that reads the words. */
 struct lc3hip_stage { uint16_t* d[LC3D_SETS]; uint16_t* h[LC3D_SETS]; size_t cap; hipEvent_t ev[LC3D_SETS]; int armed[LC3D_SETS], k; };
 struct lc3hip_ctx {
-    lc3hip_opts opt;
+    lc3hip_opts opt; work_set wk;
     int device, ncs, n_streams, channels, N, big, state_words, rs48, rs96;
     lc3d_plan* d_plan; lc3d_chan* d_chans; float* d_state;
     void* d_pcm; size_t pcm_cap; uint8_t* d_out; size_t out_cap;
@@ -197,12 +209,79 @@ struct lc3hip_ctx {
 /* waits for the call on s and keeps its kernel time (ev0 ... ev1) */
 #define SYNC_TIMED(c, s) do { HIPCHK(hipStreamSynchronize(s)); float ms_ = 0; if (hipEventElapsedTime(&ms_, (c)->ev0, (c)->ev1) == hipSuccess) (c)->last_ms = ms_; } while (0)
 static size_t ss_up(size_t x) { return (x + 255) & ~(size_t)255; }
+/* the encoder's work buffers.  Not here: d_state, d_chans, d_carry, d_xnext and the lifecycle staging (a later call reads what an earlier one wrote), d_plan, d_etab and
+ * the template (written once), d_status (points into d_statusv) */
+static const work_buf enc_work[] = {
+    WORK(lc3hip_ctx, d_pcm, 1, LC3HIP_ELEM_U8, c->pcm_cap),
+    WORK(lc3hip_ctx, d_out, 1, LC3HIP_ELEM_U8, c->out_cap),
+    WORK(lc3hip_ctx, d_trace, 1, LC3HIP_ELEM_U8, c->trace_cap),
+    WORK(lc3hip_ctx, hp_dpcm, 2, LC3HIP_ELEM_U8, c->hp_pcm_cap),
+    WORK(lc3hip_ctx, d_dumpv, LC3D_SETS, LC3HIP_ELEM_I32, c->dump_capv[k] * sizeof(int)),
+    WORK(lc3hip_ctx, d_y12, LC3D_SETS, LC3HIP_ELEM_F32, c->y12_cap[k] * sizeof(float)),
+    WORK(lc3hip_ctx, d_statusv, LC3D_SETS, LC3HIP_ELEM_U8, c->status_capv[k]),
+    WORK(lc3hip_ctx, d_spec, LC3D_SETS, LC3HIP_ELEM_F32, c->spec_cap[k] * sizeof(float)),
+    WORK(lc3hip_ctx, d_frec, LC3D_SETS, LC3HIP_ELEM_F32, c->frec_cap[k] * sizeof(float)),
+    WORK(lc3hip_ctx, d_cnt, 1, LC3HIP_ELEM_I32, sizeof(int32_t) * (size_t)c->n_streams),
+    WORK(lc3hip_ctx, fsz.d, LC3D_SETS, LC3HIP_ELEM_U16, c->fsz.cap),
+    WORK(lc3hip_ctx, bw.d, LC3D_SETS, LC3HIP_ELEM_U16, c->bw.cap),
+    WORK(lc3hip_ctx, d_pfsz, LC3D_SETS, LC3HIP_ELEM_U16, sizeof(uint16_t) * (size_t)c->n_streams * c->pset_frames),
+    WORK(lc3hip_ctx, d_pbw, LC3D_SETS, LC3HIP_ELEM_U16, sizeof(uint16_t) * (size_t)c->n_streams * c->pset_frames),
+    WORK(lc3hip_ctx, d_pend, LC3D_SETS, LC3HIP_ELEM_I32, sizeof(int4) * (size_t)c->n_streams),
+    WORK(lc3hip_ctx, d_poff, LC3D_SETS + 1, LC3HIP_ELEM_I64, c->poff_cap * sizeof(long long)),
+    WORK(lc3hip_ctx, d_pbsum, 1, LC3HIP_ELEM_I64, (LC3D_SETS + 1) * PKS_SUMS(c->poff_cap) * sizeof(long long)),
+};
+/* one buffer filled with the poison of its element type.  A stale word used as an index must stay tame, one used as a value must be wrong: set A is all ones (a
+ * NaN, -1), set B small, finite and wrong (1.5f, 1) - a NaN can hide behind a comparison that is false or behind fmaxf; an int64 is an offset: -1 in both */
+static int poison_fill(void* p, size_t bytes, int elem, int set)
+{
+    if (!p || !bytes) return 0;
+    const bool a = set == 1;
+    switch (elem) {
+    case LC3HIP_ELEM_F32: HIPCHK(hipMemsetD32((hipDeviceptr_t)p, a ? -1 : 0x3FC00000 /* 1.5f */, bytes / 4)); break;
+    case LC3HIP_ELEM_I32: HIPCHK(hipMemsetD32((hipDeviceptr_t)p, a ? -1 : 1, bytes / 4)); break;
+    case LC3HIP_ELEM_U16: HIPCHK(hipMemsetD16((hipDeviceptr_t)p, a ? 0xFFFF : 1, bytes / 2)); break;
+    case LC3HIP_ELEM_U8: HIPCHK(hipMemsetD8((hipDeviceptr_t)p, a ? 0xFF : 1, bytes)); break;
+    case LC3HIP_ELEM_I64: HIPCHK(hipMemsetD8((hipDeviceptr_t)p, 0xFF, bytes)); break;
+    default: return 1;
+    }
+    return 0;
+}
+/* LC3PLUS_POISON_WORK: the buffers grow_group has just allocated, those of them that the table lists.  The buffers are new - no call reads them - and the fill is
+ * complete when this returns: a call that allocates never overlaps its predecessor, so the overlap under the input-ready promise is what it was */
+struct lc3hip_buf;
+static int work_poison_new(const work_set* wk, const lc3hip_buf* b, int n);
+/* LC3PLUS_POISON_CALLS: every work buffer the batch holds, at the entry of a call.  Between two waits for the whole device: the calls before this one have
+ * finished with the buffers, and no copy or kernel of this call starts before they are filled.  This SERIALISES consecutive calls, the promise's overlap
+ * included - intended: it is the simple correct form (a fill threaded through the set-rotation events would be one more thing to get wrong).  A buffer the
+ * call goes on to grow is poisoned where it is allocated, so every work buffer holds poison when the call's first copy or launch is queued. */
+static int work_poison_all(const work_set* wk)
+{
+    HIPCHK(hipDeviceSynchronize());
+    for (int e = 0; e < wk->n_tab; e++)
+        for (int k = 0; k < wk->tab[e].n; k++)
+            if (poison_fill(*(void* const*)((const char*)wk->ctx + wk->tab[e].off + k * sizeof(void*)), wk->tab[e].bytes(wk->ctx, k), wk->tab[e].elem, wk->set)) return 1;
+    HIPCHK(hipDeviceSynchronize());
+    return 0;
+}
+/* buffer i of the table in member order, for the two debug entries */
+static int work_buffer_at(const work_set* wk, int i, const char** name, void** ptr, size_t* bytes, int* elem)
+{
+    static thread_local char label[64];
+    for (int e = 0; e < wk->n_tab && i >= 0; i -= wk->tab[e++].n)
+        if (i < wk->tab[e].n) {
+            if (wk->tab[e].n > 1) snprintf(label, sizeof label, "%s[%d]", wk->tab[e].name, i); else snprintf(label, sizeof label, "%s", wk->tab[e].name);
+            *name = label; *ptr = *(void* const*)((const char*)wk->ctx + wk->tab[e].off + i * sizeof(void*)); *elem = wk->tab[e].elem;
+            *bytes = *ptr ? wk->tab[e].bytes(wk->ctx, i) : 0;
+            return 0;
+        }
+    return 1;
+}
 /* The one place a buffer grows.  n buffers (device memory, or pinned host memory) share the capacity *cap, in the caller's unit: where it is below `need` they are
  * freed and allocated again, b[i].bytes each.  wait: an earlier call that did not wait may still read them - wait for the device before freeing, unless this is the
  * first allocation.  (hipFree drains the device too; the flag states where the order is the library's to keep.)  The pointers are null and the capacity is 0 before
  * anything is allocated, so a failed allocation leaves nothing in the context to write through or to free twice. */
 struct lc3hip_buf { void** p; size_t bytes; bool pinned; };
-static int grow_group(size_t* cap, size_t need, const lc3hip_buf* b, int n, bool wait)
+static int grow_group(size_t* cap, size_t need, const lc3hip_buf* b, int n, bool wait, const work_set* wk = nullptr)
 {
     if (*cap >= need) return 0;
     bool first = true;
@@ -212,14 +291,24 @@ static int grow_group(size_t* cap, size_t need, const lc3hip_buf* b, int n, bool
     for (int i = 0; i < n; i++) { void* old = *b[i].p; *b[i].p = nullptr; if (old) HIPCHK(b[i].pinned ? hipHostFree(old) : hipFree(old)); }
     for (int i = 0; i < n; i++) HIPCHK(b[i].pinned ? hipHostMalloc(b[i].p, b[i].bytes, hipHostMallocDefault) : hipMalloc(b[i].p, b[i].bytes));
     *cap = need;
+    return wk && wk->set ? work_poison_new(wk, b, n) : 0;
+}
+static int work_poison_new(const work_set* wk, const lc3hip_buf* b, int n)
+{
+    for (int i = 0; i < n; i++) {
+        const size_t at = (size_t)((const char*)b[i].p - (const char*)wk->ctx);
+        for (int e = 0; e < wk->n_tab && !b[i].pinned; e++)
+            if (at >= wk->tab[e].off && at < wk->tab[e].off + wk->tab[e].n * sizeof(void*) && poison_fill(*b[i].p, b[i].bytes, wk->tab[e].elem, wk->set)) return 1;
+    }
+    HIPCHK(hipDeviceSynchronize());
     return 0;
 }
-template <typename T> static int grow(T** p, size_t* cap, size_t need, size_t bytes, bool wait) { const lc3hip_buf b = {(void**)p, bytes, false}; return grow_group(cap, need, &b, 1, wait); }
+template <typename T> static int grow(T** p, size_t* cap, size_t need, size_t bytes, bool wait, const work_set* wk = nullptr) { const lc3hip_buf b = {(void**)p, bytes, false}; return grow_group(cap, need, &b, 1, wait, wk); }
 /* two plain forms: grow_once, a buffer whose size never changes, allocated on first use (capacity 1 once it exists); replace, a buffer allocated anew whatever its size (capacity 0) */
-template <typename T> static int grow_once(T** p, size_t bytes, bool pinned = false) { size_t cap = *p != nullptr; const lc3hip_buf b = {(void**)p, bytes, pinned}; return grow_group(&cap, 1, &b, 1, false); }
+template <typename T> static int grow_once(T** p, size_t bytes, bool pinned = false, const work_set* wk = nullptr) { size_t cap = *p != nullptr; const lc3hip_buf b = {(void**)p, bytes, pinned}; return grow_group(&cap, 1, &b, 1, false, wk); }
 template <typename T> static int replace(T** p, size_t bytes) { size_t cap = 0; const lc3hip_buf b = {(void**)p, bytes, false}; return grow_group(&cap, 1, &b, 1, false); }
 /* src into the set whose turn it is (returned in *set, armed); the copy h -> d is the caller's to queue.  Sized on first use, a call of equal or smaller size allocates nothing. */
-static int stage_words(lc3hip_stage* q, const uint16_t* src, size_t bytes, int* set)
+static int stage_words(lc3hip_stage* q, const uint16_t* src, size_t bytes, int* set, const work_set* wk)
 {
     const int k = q->k;
     if (q->armed[k]) HIPCHK(hipEventSynchronize(q->ev[k]));       /* the set of the call LC3D_SETS back */
@@ -227,7 +316,7 @@ static int stage_words(lc3hip_stage* q, const uint16_t* src, size_t bytes, int* 
         for (int i = 0; i < LC3D_SETS; i++) if (q->armed[i]) { HIPCHK(hipEventSynchronize(q->ev[i])); q->armed[i] = 0; }      /* no call reads them any more: no wait for the device */
         lc3hip_buf b[2 * LC3D_SETS];
         for (int i = 0; i < LC3D_SETS; i++) { b[2 * i] = {(void**)&q->d[i], bytes, false}; b[2 * i + 1] = {(void**)&q->h[i], bytes, true}; }
-        if (grow_group(&q->cap, bytes, b, 2 * LC3D_SETS, false)) return 1;
+        if (grow_group(&q->cap, bytes, b, 2 * LC3D_SETS, false, wk)) return 1;
     }
     if (!q->ev[0]) for (int i = 0; i < LC3D_SETS; i++) HIPCHK(hipEventCreateWithFlags(&q->ev[i], hipEventDisableTiming));
     memcpy(q->h[k], src, bytes);
@@ -330,6 +419,8 @@ extern "C" int lc3hip_create(void** out_ctx, const lc3d_plan* plan, int n_stream
     HIPCHK_OR(hipMalloc((void**)&c->d_chans, sizeof(lc3d_chan) * c->ncs), lc3hip_destroy(c));
     HIPCHK_OR(hipMalloc((void**)&c->d_state, sizeof(float) * c->state_words * (size_t)c->ncs), lc3hip_destroy(c));
     HIPCHK_OR(hipMalloc((void**)&c->d_cnt, sizeof(int32_t) * (size_t)n_streams), lc3hip_destroy(c));
+    c->wk = {c, enc_work, (int)(sizeof enc_work / sizeof *enc_work), c->opt.poison_work, c->opt.poison_calls};
+    if (c->wk.set && work_poison_all(&c->wk)) { lc3hip_destroy(c); return 1; }      /* what exists by now: the counts */
     /* the library's own launch stream is created when a call first needs it (a caller that brings its stream never does): HIP maps streams
      * onto a few hardware queues, and the pipelined path wants its three side streams on queues of their own */
     HIPCHK_OR(hipEventCreate(&c->ev0), lc3hip_destroy(c)); HIPCHK_OR(hipEventCreate(&c->ev1), lc3hip_destroy(c));
@@ -495,20 +586,20 @@ static int enc_size_set(lc3hip_ctx* c, enc_call* q, bool in_kernel_writer)
     if (!in_kernel_writer) {
         q->dstride = PK_STRIDE(c->N, c->hr);
         const size_t need = (size_t)c->ncs * q->dT * q->dstride;
-        for (int i = i0; i < i1; i++) if (grow(&c->d_dumpv[i], &c->dump_capv[i], need, need * sizeof(int), false)) return 1;
+        for (int i = i0; i < i1; i++) if (grow(&c->d_dumpv[i], &c->dump_capv[i], need, need * sizeof(int), false, &c->wk)) return 1;
         q->ddump = c->d_dumpv[set];
     }
     /* ahead of it: the 12.8 kHz resampler of all frames at once and its HP50 recurrence one stream per lane (lc3_enc_pre.inc) */
     if (!q->dtr && !c->fused && (!q->cnt || q->rag_pipe)) {      /* (a ragged call on the one-wave path resamples in its one kernel, as a traced one: the dense pre-kernels read every frame's PCM) */
         const size_t need = (size_t)c->ncs * q->n_frames * 128;
         /* two buffers under the input-ready promise: the next call's resampler may run beside this call's pitch kernel */
-        for (int i = i0; i < i1; i++) if (grow(&c->d_y12[i], &c->y12_cap[i], need, need * sizeof(float), false)) return 1;
+        for (int i = i0; i < i1; i++) if (grow(&c->d_y12[i], &c->y12_cap[i], need, need * sizeof(float), false, &c->wk)) return 1;
         q->dy12 = c->d_y12[set];
     }
     q->split = q->dy12 && q->ddump && !c->opt.no_split;
     if (q->dt0 == 0) {   /* per channel-frame status bits (LC3D_ENC_ST_*), cleared per call: by the stream that runs the kernel that sets them (the writer's, on the pipelined path) */
         const size_t need = (size_t)c->ncs * q->dT;
-        for (int i = i0; i < i1; i++) if (grow(&c->d_statusv[i], &c->status_capv[i], need, need, false)) return 1;
+        for (int i = i0; i < i1; i++) if (grow(&c->d_statusv[i], &c->status_capv[i], need, need, false, &c->wk)) return 1;
         c->d_status = c->d_statusv[set];
         if (!q->split) HIPCHK(hipMemsetAsync(c->d_status, 0, need, q->s));
         c->status_frames = q->dT;
@@ -520,10 +611,11 @@ static int enc_size_set(lc3hip_ctx* c, enc_call* q, bool in_kernel_writer)
         const size_t ns = (size_t)c->ncs * q->dT * c->srow, nr = (size_t)c->ncs * q->dT * FR_WORDS;
         for (int i = i0; i < i1; i++) {
             const size_t had = c->frec_cap[i];
-            if (grow(&c->d_spec[i], &c->spec_cap[i], ns, ns * sizeof(float), false) || grow(&c->d_frec[i], &c->frec_cap[i], nr, nr * sizeof(float), false)) return 1;
+            if (grow(&c->d_spec[i], &c->spec_cap[i], ns, ns * sizeof(float), false, &c->wk) || grow(&c->d_frec[i], &c->frec_cap[i], nr, nr * sizeof(float), false, &c->wk)) return 1;
             /* new records start as zeros, on s in front of the fork (a call that allocates never overlaps its predecessor): a record has padding words that no kernel
-             * writes, and lc3hip_last_records reports the same words for the same call on two batches */
-            if (c->frec_cap[i] != had) HIPCHK(hipMemsetAsync(c->d_frec[i], 0, nr * sizeof(float), q->s));
+             * writes, and lc3hip_last_records reports the same words for the same call on two batches.  (No kernel reads them either: under LC3PLUS_POISON_WORK they
+             * keep the poison, which two batches share as they share the zeros.) */
+            if (c->frec_cap[i] != had && !c->wk.set) HIPCHK(hipMemsetAsync(c->d_frec[i], 0, nr * sizeof(float), q->s));
         }
         for (int i = 0; i < LC3D_SETS + 1; i++) if (grow_once(&c->d_xnext[i], (size_t)c->ncs * q->mc * sizeof(float))) return 1;
     }
@@ -893,7 +985,7 @@ static int encode_host(lc3hip_ctx* c, const void* pcm, int bitdepth, int n_frame
     }
     /* the two chunk slots and the output: no wait for the device - a call through host pointers returns when its work is done */
     const lc3hip_buf dev[] = {{&c->hp_dpcm[0], cin, false}, {&c->hp_dpcm[1], cin, false}}, pin[] = {{&c->hp_pin_in[0], cin, true}, {&c->hp_pin_in[1], cin, true}};
-    if (grow_group(&c->hp_pcm_cap, cin, dev, 2, false) || (!pin_in && grow_group(&c->hp_pin_in_cap, cin, pin, 2, false)) || grow(&c->d_out, &c->out_cap, out_bytes, out_bytes, false)) return 1;
+    if (grow_group(&c->hp_pcm_cap, cin, dev, 2, false, &c->wk) || (!pin_in && grow_group(&c->hp_pin_in_cap, cin, pin, 2, false)) || grow(&c->d_out, &c->out_cap, out_bytes, out_bytes, false, &c->wk)) return 1;
     const size_t in_pitch = (size_t)n_frames * fr_in;
     HIPCHK(hipEventRecord(c->ev0, s));
     HIPCHK(hipMemsetAsync(c->d_out, 0, out_bytes, s));
@@ -934,7 +1026,7 @@ static int upload_fsz(lc3hip_ctx* c, const uint16_t* fsz_host, int n_frames, hip
 {
     const size_t fb = sizeof(uint16_t) * (size_t)c->n_streams * n_frames;
     int k;
-    if (stage_words(&c->fsz, fsz_host, fb, &k)) return 1;
+    if (stage_words(&c->fsz, fsz_host, fb, &k, &c->wk)) return 1;
     HIPCHK(hipMemcpyAsync(c->fsz.d[k], c->fsz.h[k], fb, hipMemcpyHostToDevice, s));
     *dfsz = c->fsz.d[k]; *ev = c->fsz.ev[k];
     return 0;
@@ -944,7 +1036,7 @@ static int stage_bw(lc3hip_ctx* c, const uint16_t* bw_host, int n_frames, const 
 {
     const size_t fb = sizeof(uint16_t) * (size_t)c->n_streams * n_frames;
     int k;
-    if (stage_words(&c->bw, bw_host, fb, &k)) return 1;
+    if (stage_words(&c->bw, bw_host, fb, &k, &c->wk)) return 1;
     if (!c->ev_bwcp) HIPCHK(hipEventCreateWithFlags(&c->ev_bwcp, hipEventDisableTiming));
     c->bw_src = c->bw.h[k]; c->bw_bytes = fb; c->bw_on = nullptr; c->pl.pending = 0;
     *dbw = c->bw.d[k]; *ev = c->bw.ev[k];
@@ -991,6 +1083,7 @@ extern "C" int lc3hip_encode(void* ctx, const void* pcm, int pcm_on_device, int 
     if (fsz_host && !c->d_etab) return 1;
     if (bw_host && c->big) return 1;            /* no large-layout kernels: that layout only serves high-resolution batches, which the host refuses */
     if (c->plo && (!pcm_on_device || trace_host)) return 1;      /* placed PCM: device-pointer calls without traces (the host refuses the others) */
+    if (c->wk.calls && work_poison_all(&c->wk)) return 1;        /* once per call: a host-pointer call's pieces come behind it */
     if (!pcm_on_device && !out_on_device && !trace_host) {
         if (c->chans_armed) HIPCHK(hipStreamWaitEvent(s, c->ev_chans, 0));
         if (fsz_host && upload_fsz(c, fsz_host, n_frames, s, &dfsz, &ev_fsz)) return 1;
@@ -1005,19 +1098,19 @@ extern "C" int lc3hip_encode(void* ctx, const void* pcm, int pcm_on_device, int 
     const size_t out_bytes = (size_t)c->n_streams * n_frames * out_stride;
     const void* dpcm = pcm; uint8_t* dout = (uint8_t*)out;
     if (!pcm_on_device) {
-        if (grow(&c->d_pcm, &c->pcm_cap, pcm_bytes, pcm_bytes, false)) return 1;      /* staging of host arrays (d_pcm, d_out, d_trace): no wait of its own, as in encode_host */
+        if (grow(&c->d_pcm, &c->pcm_cap, pcm_bytes, pcm_bytes, false, &c->wk)) return 1;      /* staging of host arrays (d_pcm, d_out, d_trace): no wait of its own, as in encode_host */
         HIPCHK(hipMemcpyAsync(c->d_pcm, pcm, pcm_bytes, hipMemcpyHostToDevice, s));
         dpcm = c->d_pcm;
     }
     if (!out_on_device) {
-        if (grow(&c->d_out, &c->out_cap, out_bytes, out_bytes, false)) return 1;
+        if (grow(&c->d_out, &c->out_cap, out_bytes, out_bytes, false, &c->wk)) return 1;
         dout = c->d_out;
         HIPCHK(hipMemsetAsync(dout, 0, out_bytes, s));
     }
     lc3d_trace* dtr = nullptr;
     if (trace_host) {
         const size_t tb = sizeof(lc3d_trace) * (size_t)c->ncs * n_frames;
-        if (grow(&c->d_trace, &c->trace_cap, tb, tb, false)) return 1;
+        if (grow(&c->d_trace, &c->trace_cap, tb, tb, false, &c->wk)) return 1;
         HIPCHK(hipMemsetAsync(c->d_trace, 0, tb, s));
         dtr = c->d_trace;
     }
@@ -1057,7 +1150,7 @@ static int pk_tables(lc3hip_ctx* c, size_t n)
     lc3hip_buf b[LC3D_SETS + 2];
     for (int i = 0; i < LC3D_SETS + 1; i++) b[i] = {(void**)&c->d_poff[i], n * sizeof(long long), false};
     b[LC3D_SETS + 1] = {(void**)&c->d_pbsum, (size_t)(LC3D_SETS + 1) * PKS_SUMS(n) * sizeof(long long), false};
-    return grow_group(&c->poff_cap, n, b, LC3D_SETS + 2, true);
+    return grow_group(&c->poff_cap, n, b, LC3D_SETS + 2, true, &c->wk);
 }
 /* the pending call's plan kernel on st: behind the previous call's plan kernel (the carry), behind the call that used this set last, and - when it starts
  * from the configuration the host wrote - behind that write */
@@ -1092,6 +1185,7 @@ extern "C" int lc3hip_encode_rates_device(void* ctx, const void* pcm, int bitdep
     lc3hip_ctx* c = (lc3hip_ctx*)ctx;
     HIPCHK(hipSetDevice(c->device));
     if (!c->d_etab || (bws_dev && c->big)) return 1;
+    if (c->wk.calls && work_poison_all(&c->wk)) return 1;
     if (!hip_stream && !c->stream) HIPCHK(hipStreamCreate(&c->stream));
     hipStream_t s = hip_stream ? (hipStream_t)hip_stream : c->stream;
     if (!c->ev_plan) {
@@ -1101,12 +1195,12 @@ extern "C" int lc3hip_encode_rates_device(void* ctx, const void* pcm, int bitdep
         c->carry_seed = 1;
     }
     if (grow_once(&c->d_carry, sizeof(int4) * (size_t)c->n_streams)) return 1;      /* outside the block above: a call after a failed allocation tries again */
-    for (int i = 0; i < LC3D_SETS; i++) if (grow_once(&c->d_pend[i], sizeof(int4) * (size_t)c->n_streams)) return 1;
+    for (int i = 0; i < LC3D_SETS; i++) if (grow_once(&c->d_pend[i], sizeof(int4) * (size_t)c->n_streams, false, &c->wk)) return 1;
     /* an earlier call that did not wait may still read the smaller sets: growing them waits for the device, once (the first allocation does not) */
     const size_t fb = sizeof(uint16_t) * (size_t)c->n_streams * n_frames;
     lc3hip_buf b[2 * LC3D_SETS];
     for (int i = 0; i < LC3D_SETS; i++) { b[2 * i] = {(void**)&c->d_pfsz[i], fb, false}; b[2 * i + 1] = {(void**)&c->d_pbw[i], fb, false}; }
-    if (grow_group(&c->pset_frames, (size_t)n_frames, b, 2 * LC3D_SETS, true)) return 1;
+    if (grow_group(&c->pset_frames, (size_t)n_frames, b, 2 * LC3D_SETS, true, &c->wk)) return 1;
     /* Ragged (lc3hip_set_frame_counts): the call of this function with the _rag kernels.  Its plan kernel always writes sizes - the carried ones where the caller
      * gave no rates - and an offset table (slotted output: every frame's slot), on s in front of everything else of the call (bw_to below): every other kernel reads
      * the clamped counts it leaves, and on the pipelined path (enc_launch: long calls without rates in the standard layout) the side streams fork from s behind it.
@@ -1295,6 +1389,8 @@ extern "C" float lc3hip_last_ms(void* ctx)
     return c->last_ms;
 }
 
+extern "C" int lc3hip_work_buffer(void* ctx, int i, const char** name, void** ptr, size_t* bytes, int* elem) { return ctx ? work_buffer_at(&((lc3hip_ctx*)ctx)->wk, i, name, ptr, bytes, elem) : 1; }
+
 extern "C" int lc3hip_destroy(void* ctx)
 {
     lc3hip_ctx* c = (lc3hip_ctx*)ctx;
@@ -1334,7 +1430,7 @@ extern "C" int lc3hip_destroy(void* ctx)
 #define DEC_SETS 3                      /* sets of hand-over buffers (records, spectrum rows) under the decoder's input-ready promise: the parser of call k + 2 may write while call k is synthesised */
 #endif
 struct lc3hip_dctx {
-    lc3hip_opts opt;
+    lc3hip_opts opt; work_set wk;
     int device, ncs, n_streams, channels, N, big;
     lc3d_plan* d_plan; lc3d_dchan* d_chans; float* d_state;
     uint8_t* d_in; size_t in_cap; void* d_pcm; size_t pcm_cap; uint8_t* d_bfi; size_t bfi_cap;
@@ -1352,6 +1448,23 @@ struct lc3hip_dctx {
     hipEvent_t ev_ord; int ord_pending;
     lc3hip_ss ss;                                   /* the fresh-row template, lc3hip_dec_stream_state */
 };
+/* the decoder's work buffers.  Not here: d_state and d_chans (a later call reads what an earlier one wrote), the lifecycle staging, d_plan, d_tab and the template */
+static const work_buf dec_work[] = {
+    WORK(lc3hip_dctx, d_in, 1, LC3HIP_ELEM_U8, c->in_cap),
+    WORK(lc3hip_dctx, d_pcm, 1, LC3HIP_ELEM_U8, c->pcm_cap),
+    WORK(lc3hip_dctx, d_bfi, 1, LC3HIP_ELEM_U8, c->bfi_cap),
+    WORK(lc3hip_dctx, d_sizes, 1, LC3HIP_ELEM_U16, c->sizes_cap),
+    WORK(lc3hip_dctx, d_inval, 1, LC3HIP_ELEM_U8, c->inval_cap),
+    WORK(lc3hip_dctx, d_trace, 1, LC3HIP_ELEM_U8, c->trace_cap),
+    WORK(lc3hip_dctx, d_status, 1, LC3HIP_ELEM_U8, c->status_cap),
+    WORK(lc3hip_dctx, d_rec, 1, LC3HIP_ELEM_I32, c->hand_cap * PR_WORDS * sizeof(int)),
+    WORK(lc3hip_dctx, d_ws, 1, LC3HIP_ELEM_F32, c->hand_cap * WS_ROW(c->N) * sizeof(float)),
+    WORK(lc3hip_dctx, d_ov, 1, LC3HIP_ELEM_F32, c->hand_cap * (c->big ? OV_ROW_BIG : OV_ROW_STD) * sizeof(float)),
+    WORK(lc3hip_dctx, d_recx, DEC_SETS - 1, LC3HIP_ELEM_I32, c->handx_cap * PR_WORDS * sizeof(int)),
+    WORK(lc3hip_dctx, d_wsx, DEC_SETS - 1, LC3HIP_ELEM_F32, c->handx_cap * WS_ROW(c->N) * sizeof(float)),
+    WORK(lc3hip_dctx, d_cnt, 1, LC3HIP_ELEM_I32, sizeof(int32_t) * (size_t)c->n_streams),
+};
+extern "C" int lc3hip_dec_work_buffer(void* ctx, int i, const char** name, void** ptr, size_t* bytes, int* elem) { return ctx ? work_buffer_at(&((lc3hip_dctx*)ctx)->wk, i, name, ptr, bytes, elem) : 1; }
 static int dec_side_streams(lc3hip_dctx* c)                       /* the parse-ahead stream, the concealment stream and their events, created once */
 {
     if (c->s_par) return 0;
@@ -1380,6 +1493,8 @@ extern "C" int lc3hip_dec_create(void** out_ctx, const lc3d_plan* plan, const fl
     HIPCHK_OR(hipMalloc((void**)&c->d_chans, sizeof(lc3d_dchan) * c->ncs), lc3hip_dec_destroy(c));
     HIPCHK_OR(hipMalloc((void**)&c->d_state, sizeof(float) * DST_WORDS * (size_t)c->ncs), lc3hip_dec_destroy(c));
     HIPCHK_OR(hipMalloc((void**)&c->d_cnt, sizeof(int32_t) * (size_t)n_streams), lc3hip_dec_destroy(c));
+    c->wk = {c, dec_work, (int)(sizeof dec_work / sizeof *dec_work), c->opt.poison_work, c->opt.poison_calls};
+    if (c->wk.set && work_poison_all(&c->wk)) { lc3hip_dec_destroy(c); return 1; }      /* what exists by now: the counts */
     if (ss_init(&c->ss, c->device, c->d_state, DST_WORDS, c->ncs, tmpl)) { lc3hip_dec_destroy(c); return 1; }
     HIPCHK_OR(hipStreamCreate(&c->stream), lc3hip_dec_destroy(c));
     HIPCHK_OR(hipEventCreate(&c->ev0), lc3hip_dec_destroy(c)); HIPCHK_OR(hipEventCreate(&c->ev1), lc3hip_dec_destroy(c));
@@ -1451,7 +1566,7 @@ static int dec_stage(lc3hip_dctx* c, dec_call* q)
     q->pcm_bytes = (size_t)c->ncs * n_frames * c->N * (size_t)lc3d_pcm_elem_bytes(q->bps);
     q->din = (const uint8_t*)q->frames; q->dpcm = q->pcm;
     /* a device buffer of `bytes` for a host array of the call, and the array (if any: h) copied into it on s */
-    auto up = [&](auto** d, size_t* cap, const void* h, size_t bytes) -> int { if (grow(d, cap, bytes, bytes, false)) return 1; if (h) HIPCHK(hipMemcpyAsync(*d, h, bytes, hipMemcpyHostToDevice, s)); return 0; };
+    auto up = [&](auto** d, size_t* cap, const void* h, size_t bytes) -> int { if (grow(d, cap, bytes, bytes, false, &c->wk)) return 1; if (h) HIPCHK(hipMemcpyAsync(*d, h, bytes, hipMemcpyHostToDevice, s)); return 0; };
     const size_t fb = (size_t)c->n_streams * n_frames;            /* a byte per stream-frame */
     if (!q->frames_on_device) { if (up(&c->d_in, &c->in_cap, q->frames, in_bytes)) return 1; q->din = c->d_in; }
     if (!q->pcm_on_device) { if (up(&c->d_pcm, &c->pcm_cap, nullptr, q->pcm_bytes)) return 1; q->dpcm = c->d_pcm; }
@@ -1471,14 +1586,14 @@ static int dec_stage(lc3hip_dctx* c, dec_call* q)
         if (!c->d_tab) return 1;
         /* a smaller buffer of an earlier call may still be read (calls of this kind do not wait): growing it waits for the device; the first allocation does not.
          * (Three capacities - the host-array calls above grow two of the buffers on their own: each that grows waits, and behind the first wait the device is idle.) */
-        if (grow(&c->d_sizes, &c->sizes_cap, sizeof(uint16_t) * fb, sizeof(uint16_t) * fb, true) || grow(&c->d_bfi, &c->bfi_cap, fb, fb, true) || grow(&c->d_inval, &c->inval_cap, fb, fb, true)) return 1;
+        if (grow(&c->d_sizes, &c->sizes_cap, sizeof(uint16_t) * fb, sizeof(uint16_t) * fb, true, &c->wk) || grow(&c->d_bfi, &c->bfi_cap, fb, fb, true, &c->wk) || grow(&c->d_inval, &c->inval_cap, fb, fb, true, &c->wk)) return 1;
         q->dsizes = c->d_sizes; q->dbfi = c->d_bfi; q->dst = q->status_dev;
     }
     const size_t cf = (size_t)c->ncs * n_frames;
     /* hand-over buffers between the two kernels: records and spectrum rows of every channel-frame of this call; an earlier call that did not wait may still read them (not on the first call) */
     const lc3hip_buf hand[] = {{(void**)&c->d_rec, cf * PR_WORDS * sizeof(int), false}, {(void**)&c->d_ws, cf * WS_ROW(c->N) * sizeof(float), false},
                                {(void**)&c->d_ov, cf * (c->big ? OV_ROW_BIG : OV_ROW_STD) * sizeof(float), false}};
-    if (grow_group(&c->hand_cap, cf, hand, 3, true)) return 1;
+    if (grow_group(&c->hand_cap, cf, hand, 3, true, &c->wk)) return 1;
     /* Under the input-ready promise (the frames of a call are complete on the device when the call is made) the parse kernel - stateless: a frame's
      * record and spectrum row depend on that frame's bytes only - does not wait for what is queued on s: it runs on its own stream into the other set of
      * hand-over buffers while the concealment bookkeeping, transform and synthesis of the call before (the stateful part, in order on s) read theirs. */
@@ -1491,7 +1606,7 @@ static int dec_stage(lc3hip_dctx* c, dec_call* q)
             handx[2 * i] = {(void**)&c->d_recx[i], cf * PR_WORDS * sizeof(int), false};
             handx[2 * i + 1] = {(void**)&c->d_wsx[i], cf * WS_ROW(c->N) * sizeof(float), false};
         }
-        if (grow_group(&c->handx_cap, cf, handx, 2 * (DEC_SETS - 1), true)) return 1;
+        if (grow_group(&c->handx_cap, cf, handx, 2 * (DEC_SETS - 1), true, &c->wk)) return 1;
         if (c->set) { q->rec_w = c->d_recx[c->set - 1]; q->ws_w = c->d_wsx[c->set - 1]; }
     }
     return 0;
@@ -1626,6 +1741,7 @@ static int dec_decode(lc3hip_dctx* c, dec_call* q, void* hip_stream)
     q->cnt = c->counts ? c->d_cnt : nullptr;                       /* per-stream frame counts: the _rag kernels, every one behind the plan kernel that clamps them into d_cnt */
     if (q->cnt && !q->nb_dev) return 1;                             /* ... on the calls with sizes in device memory only (the host refuses the others) */
     hipStream_t s = q->s = hip_stream ? (hipStream_t)hip_stream : c->stream;
+    if (c->wk.calls && work_poison_all(&c->wk)) return 1;
     if (c->ss.done_armed) HIPCHK(hipStreamWaitEvent(s, c->ss.ev_done, 0));      /* behind the last stream-lifecycle call, whichever stream it was queued on */
     if (dec_stage(c, q) || dec_parse_lds(c, q)) return 1;
     hipStream_t sp = q->ahead ? c->s_par : s;

@@ -125,6 +125,16 @@ int   lc3hip_test_fastmath(int kind, const float* x_host, float* y_host, long lo
 void  lc3hip_launch_census_enable(int on);
 void  lc3hip_launch_census_reset(void);
 size_t lc3hip_launch_census_read(char* buf, size_t cap);
+/* Poisoned workspaces (DESIGN.md "Every workspace word"), a debugging aid read with the other LC3PLUS_* switches when a batch is created.  The work buffers of a
+ * batch are the device buffers a call fills and reads itself, none of which a later call may rely on: the runtime lists them in one table per side.
+ * LC3PLUS_POISON_WORK=A|B fills each of them with poison by element type where it is allocated (float 0xFFFFFFFF | 1.5f, int32 -1 | 1, uint16 and uint8 all ones | 1,
+ * int64 -1 | -1); LC3PLUS_POISON_CALLS=1 (with the first) fills all of them again at the entry of every encode and decode call, between two waits for the device.
+ * The two entries below walk the same table: buffer i of the batch - its member name (index in brackets where the member is an array), its device pointer (null
+ * until a call has needed it), its length in bytes and its element type (LC3HIP_ELEM_*); they return 0, or 1 past the table's end.  Nothing is queued or waited
+ * for: the caller waits for the batch first. */
+enum { LC3HIP_ELEM_F32 = 1, LC3HIP_ELEM_I32 = 2, LC3HIP_ELEM_U16 = 3, LC3HIP_ELEM_U8 = 4, LC3HIP_ELEM_I64 = 5 };
+int   lc3hip_work_buffer(void* ctx, int i, const char** name, void** ptr, size_t* bytes, int* elem);
+int   lc3hip_dec_work_buffer(void* ctx, int i, const char** name, void** ptr, size_t* bytes, int* elem);
 #ifdef __cplusplus
 }
 #endif

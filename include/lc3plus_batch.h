@@ -359,6 +359,12 @@ int lc3plus_enc_batch_last_status(lc3plus_batch* batch, uint8_t* status, int max
 int lc3plus_enc_batch_last_records(lc3plus_batch* batch, float* records, int max_words);
 int lc3plus_enc_batch_record_words(void);
 
+/* Diagnostics: work buffer i of the batch - one of the device buffers a call fills and reads itself, as the host runtime lists them (the same list
+ * LC3PLUS_POISON_WORK fills, INTEGRATION.md "Poisoned workspaces"): its name, its device pointer (null until a call has needed it), its length in bytes and
+ * its element type (1 float32, 2 int32, 3 uint16, 4 uint8, 5 int64).  name is valid until the calling thread's next call of either function.  Returns LC3_OK,
+ * or LC3_ERROR past the last buffer.  Waits for the batch's last call.  The tests read the buffers back through it (the decoder's: below). */
+LC3_Error lc3plus_enc_batch_work_buffer(lc3plus_batch* batch, int i, const char** name, void** ptr, size_t* bytes, int* elem);
+
 /* ---- batched decoder: n_streams independent decoder instances, one wavefront per channel-stream; same
  * conventions as the encoder batch.  num_bytes[n_streams] = bytes per stream-frame (all channels; may be NULL
  * and set later per stream, or come with the frames: lc3plus_dec_batch_decode_sizes, from host arrays, or
@@ -431,6 +437,8 @@ LC3_Error lc3plus_dec_plan_packed_lenient(int samplerate, int channels, float fr
                                           const int64_t* offsets, int64_t frames_capacity, int max_frame_bytes, const uint8_t* bfi, int n_frames,
                                           uint16_t* eff, uint8_t* lost, uint8_t* invalid, int* end, int* max_chan);
 float     lc3plus_dec_batch_last_kernel_ms(lc3plus_dec_batch* batch);
+/* the decoder's work buffers, as lc3plus_enc_batch_work_buffer */
+LC3_Error lc3plus_dec_batch_work_buffer(lc3plus_dec_batch* batch, int i, const char** name, void** ptr, size_t* bytes, int* elem);
 /* checkpoint / resume of the decoders' cross-frame state (overlap-add memory, last good spectrum, LTPF histories, concealment words), as
  * for the encoder batch; the frame sizes are configuration (lc3plus_dec_batch_set_num_bytes), not state */
 size_t    lc3plus_dec_batch_state_size(const lc3plus_dec_batch* batch);

@@ -119,6 +119,8 @@ int lc3hip_set_frame_counts(void* ctx, const int32_t* counts_dev) { return stub_
 int lc3hip_dec_set_frame_counts(void* ctx, const int32_t* counts_dev) { return stub_counts(ctx, counts_dev); }
 int lc3hip_last_status(void* ctx, uint8_t* status_host, int n) { return 0; }
 int lc3hip_last_records(void* ctx, float* rec_host, int max_words) { return 0; }
+int lc3hip_work_buffer(void* ctx, int i, const char** name, void** ptr, size_t* bytes, int* elem) { return 1; }           /* no device buffers: the table is empty */
+int lc3hip_dec_work_buffer(void* ctx, int i, const char** name, void** ptr, size_t* bytes, int* elem) { return 1; }
 int lc3hip_test_fastmath(int kind, const float* x_host, float* y_host, long long n) { return 1; }
 
 int lc3hip_encode(void* ctx, const void* pcm, int pcm_on_device, int bitdepth, int n_frames, void* out, int out_stride, int out_on_device, void* hip_stream,
