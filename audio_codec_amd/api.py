@@ -52,6 +52,8 @@ EXPORTS = [
     "lc3plus_dec_batch_srtp_gcm_unprotect", "lc3plus_plan_srtp_gcm_unprotect",
     "lc3plus_enc_batch_red_pack", "lc3plus_dec_batch_red_pack", "lc3plus_plan_red_pack", "lc3plus_red_work_bytes", "lc3plus_dec_batch_red_unpack",
     "lc3plus_plan_red_unpack",
+    "lc3plus_enc_batch_fec_encode", "lc3plus_dec_batch_fec_encode", "lc3plus_plan_fec_encode", "lc3plus_fec_work_bytes", "lc3plus_fec_recover_work_bytes",
+    "lc3plus_dec_batch_fec_recover", "lc3plus_plan_fec_recover",
     "lc3plus_shard_block",
     "lc3plus_enc_sharded_create", "lc3plus_enc_sharded_destroy", "lc3plus_enc_sharded_shards", "lc3plus_enc_sharded_shard", "lc3plus_enc_sharded_device",
     "lc3plus_enc_sharded_owner", "lc3plus_enc_sharded_input_samples", "lc3plus_enc_sharded_num_bytes", "lc3plus_enc_sharded_stride",
@@ -133,6 +135,14 @@ RED_STATS_WORDS = 4
 (RED_OK, RED_DROPPED, RED_RANGE, RED_SHORT, RED_DEPTH, RED_LENGTH, RED_PAYLOAD_TYPE) = range(7)
 RED_DROP_TYPE, RED_DROP_OFFSET, RED_DROP_EMPTY = 8, 9, 10
 RED_UNPACK_STATS_WORDS = 16
+# Generic FEC (Batch.fec_encode_device, DecBatch.fec_encode, DecBatch.fec_recover, plan_fec_encode, plan_fec_recover; include/lc3plus_batch.h "Generic FEC"): the
+# largest group, the words of a route's state and of its stats, the flag of an EMPTY entry, an FEC item's status (also its word in stats)
+FEC_MAX_GROUP = 16
+FEC_STATE_WORDS = 8
+FEC_ROUTE_STATS_WORDS = 4
+FEC_PKT_EMPTY = 2
+(FEC_RECOVERED, FEC_DROPPED, FEC_RANGE, FEC_SHORT, FEC_HEADER, FEC_LENGTH, FEC_COMPLETE, FEC_MISSING, FEC_PARTIAL, FEC_OVERFLOW) = range(10)
+FEC_STATS_WORDS = 16
 LC3_BW_WARNING = 18
 
 
@@ -325,6 +335,17 @@ def load_library():
         unred = [C.c_int64] + [C.c_void_p] * 6 + [C.c_int64, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 8 + [C.c_void_p, C.c_int]
         L.lc3plus_dec_batch_red_unpack.argtypes = [C.c_void_p] + unred
         L.lc3plus_plan_red_unpack.argtypes = [C.c_int] + unred
+        fec = ([C.c_int64] + [C.c_void_p] * 7 + [C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 9 + [C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_int,
+                C.c_int64] + [C.c_void_p] * 10 + [C.c_void_p, C.c_void_p, C.c_int])
+        L.lc3plus_enc_batch_fec_encode.argtypes = [C.c_void_p] + fec
+        L.lc3plus_dec_batch_fec_encode.argtypes = [C.c_void_p] + fec
+        L.lc3plus_plan_fec_encode.argtypes = fec
+        L.lc3plus_fec_work_bytes.argtypes = [C.c_int, C.c_int]; L.lc3plus_fec_work_bytes.restype = C.c_int64
+        L.lc3plus_fec_recover_work_bytes.argtypes = [C.c_int, C.c_int]; L.lc3plus_fec_recover_work_bytes.restype = C.c_int64
+        unfec = ([C.c_int64, C.c_void_p, C.c_int64] + [C.c_void_p] * 4 + [C.c_int64] + [C.c_void_p] * 3 + [C.c_int, C.c_void_p, C.c_int64, C.c_int64] + [C.c_void_p] * 6 +
+                 [C.c_void_p, C.c_int])
+        L.lc3plus_dec_batch_fec_recover.argtypes = [C.c_void_p] + unfec
+        L.lc3plus_plan_fec_recover.argtypes = [C.c_int] + unfec
         _LIB = L
     return _LIB
 
@@ -972,6 +993,203 @@ def plan_red_unpack(n_streams, stream, seq, offsets, num_bytes, ring, ts_step, m
     return dict(zip(RED_UNPACK_OUTPUTS, outs))
 
 
+FEC_ENCODE_INPUTS = ("n_packets", "pkt_route", "pkt_frame", "pkt_offset", "pkt_size", "pkt_status", "wire", "seq_base", "route_stats", "group", "flush", "fec_seq_base",
+                     "state_in", "acc_in")
+FEC_ENCODE_OPTIONAL = ("fec_flags", "fec_mask", "next_fec_seq", "route_stats")
+FEC_ENCODE_OUTPUTS = ("state", "acc", "fec_wire", "n_fec", "fec_route", "fec_seq", "fec_frame", "fec_offset", "fec_size", "fec_flags", "fec_mask", "next_fec_seq",
+                      "route_stats")
+FEC_RECOVER_OPTIONAL = ("status", "stats")
+FEC_RECOVER_OUTPUTS = ("ring", "rec_dg_offsets", "rec_dg_sizes", "rec_seq", "status", "stats")
+
+
+def fec_work_bytes(n_routes, n_frames):
+    """bytes of the workspace of a fec_encode call (lc3plus_fec_work_bytes); 0 for arguments the calls refuse"""
+    return int(load_library().lc3plus_fec_work_bytes(int(n_routes), int(n_frames)))
+
+
+def fec_recover_work_bytes(n_streams, window):
+    """bytes of the workspace of a fec_recover call (lc3plus_fec_recover_work_bytes); 0 for arguments the call refuses"""
+    return int(load_library().lc3plus_fec_recover_work_bytes(int(n_streams), int(window)))
+
+
+def _fec_encode_arrays(pkt_route, pkt_frame, pkt_offset, pkt_size, wire, n_frames, seq_base, group, fec_seq_base, fec_wire, pkt_status, n_packets, route_stats, flush,
+                       state, acc, acc_stride, max_fec_packets, optional):
+    """the arrays of an encode call as the C calls take them: (inputs by name, None for a NULL one; outputs in FEC_ENCODE_OUTPUTS order; work; max_fec_packets)"""
+    route = np.ascontiguousarray(pkt_route, dtype=np.int32).reshape(-1)
+    m = route.size
+    per = lambda a, dt, what: _shaped(np.ascontiguousarray(a, dtype=dt).reshape(-1), (m,), what)
+    frame = per(pkt_frame, np.int32, "pkt_frame holds one entry per packet")
+    offset = per(pkt_offset, np.int64, "pkt_offset holds one entry per packet")
+    size = per(pkt_size, np.int32, "pkt_size holds one entry per packet")
+    status = None if pkt_status is None else per(pkt_status, np.uint8, "pkt_status holds one entry per packet")
+    seq_base = _u32(seq_base)
+    R = seq_base.size
+    rt = lambda a, dt, what: _shaped(np.ascontiguousarray(a, dtype=dt).reshape(-1), (R,), what)
+    group = rt(group, np.int32, "group holds one entry per route")
+    fec_seq_base = _shaped(_u32(fec_seq_base), (R,), "fec_seq_base holds one entry per route")
+    flush = None if flush is None else rt(flush, np.uint8, "flush holds one entry per route")
+    route_stats = None if route_stats is None else _shaped(np.ascontiguousarray(route_stats, dtype=np.int32), (R, EGR_STATS_WORDS), "route_stats is the egress's stats")
+    if (state is None) != (acc is None):
+        raise ValueError("state and acc come together")
+    state_out = acc_out = None
+    if state is not None:
+        state = _shaped(np.ascontiguousarray(state, dtype=np.int32), (R, FEC_STATE_WORDS), "state must have shape [n_routes, FEC_STATE_WORDS]")
+        acc = _shaped(np.ascontiguousarray(acc, dtype=np.uint8), (R, int(acc_stride)), "acc must have shape [n_routes, acc_stride]")
+        state_out, acc_out = np.zeros_like(state), np.zeros_like(acc)
+    count = np.array([m if n_packets is None else int(n_packets)], np.int64)
+    wire = np.ascontiguousarray(wire, dtype=np.uint8).reshape(-1)
+    fec_wire = np.array(fec_wire, dtype=np.uint8).reshape(-1)         # a copy: the call's FEC buffer starts with these contents
+    q = max(R * int(n_frames), 1) if max_fec_packets is None else int(max_fec_packets)
+    n = max(q, 1)
+    ins = dict(n_packets=count, pkt_route=route, pkt_frame=frame, pkt_offset=offset, pkt_size=size, pkt_status=status, wire=wire, seq_base=seq_base,
+               route_stats=route_stats, group=group, flush=flush, fec_seq_base=fec_seq_base, state_in=state, acc_in=acc)
+    outs = [state_out, acc_out, fec_wire, np.zeros(1, np.int64), np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros(n, np.int64),
+            np.zeros(n, np.int32), np.zeros(n, np.uint8) if "fec_flags" in optional else None, np.zeros(n, np.int32) if "fec_mask" in optional else None,
+            np.zeros(R, np.int32) if "next_fec_seq" in optional else None, np.zeros((R, FEC_ROUTE_STATS_WORDS), np.int32) if "route_stats" in optional else None]
+    work = np.zeros(max(fec_work_bytes(R, n_frames), 8) // 8, np.int64)
+    return ins, outs, work, q
+
+
+def _fec_encode_args(ins, outs, work, v, n_frames, header_room, payload_room, acc_stride, fec_stride, fec_header_room, max_fec_packets, wire_capacity, fec_capacity,
+                     seq_in_place=False):
+    """the C calls' arguments behind the batch; v: the pointers of FEC_ENCODE_INPUTS, then of the outputs, then of work.  seq_in_place: next_fec_seq is the array
+    fec_seq_base itself"""
+    k = len(FEC_ENCODE_INPUTS)
+    i, o = dict(zip(FEC_ENCODE_INPUTS, v[:k])), list(v[k:k + len(outs)])
+    if seq_in_place:
+        o[FEC_ENCODE_OUTPUTS.index("next_fec_seq")] = i["fec_seq_base"]
+    wcap = ins["wire"].size if wire_capacity is None else int(wire_capacity)
+    fcap = outs[2].size if fec_capacity is None else int(fec_capacity)
+    return [ins["pkt_route"].size, i["n_packets"], i["pkt_route"], i["pkt_frame"], i["pkt_offset"], i["pkt_size"], i["pkt_status"], i["wire"], wcap, int(header_room),
+            int(payload_room), ins["seq_base"].size, int(n_frames), i["seq_base"], i["route_stats"], i["group"], i["flush"], i["fec_seq_base"], i["state_in"], i["acc_in"],
+            o[0], o[1], int(acc_stride or 0), o[2], fcap, int(fec_stride), int(fec_header_room), int(max_fec_packets)] + list(o[3:]) + [v[-1]]
+
+
+def _fec_encode_result(outs):
+    r = dict(zip(FEC_ENCODE_OUTPUTS, outs))
+    r["n_fec"] = int(r["n_fec"][0])
+    return r
+
+
+def plan_fec_encode(pkt_route, pkt_frame, pkt_offset, pkt_size, wire, n_frames, seq_base, group, fec_seq_base, fec_wire, fec_stride, header_room=12, payload_room=0,
+                    fec_header_room=12, pkt_status=None, n_packets=None, route_stats=None, flush=None, state=None, acc=None, acc_stride=None, max_fec_packets=None,
+                    wire_capacity=None, fec_capacity=None, optional=FEC_ENCODE_OPTIONAL, seq_in_place=False):
+    """The rule of Batch.fec_encode_device / DecBatch.fec_encode_device on the host (lc3plus_plan_fec_encode, no device needed): the stamped list pkt_route,
+    pkt_frame, pkt_offset (int64), pkt_size and optional pkt_status [max_packets] (n_packets of it: all by default) over wire (uint8), per route seq_base, group,
+    fec_seq_base and the optional flush (uint8) and route_stats (the egress's), the previous call's state [n_routes, FEC_STATE_WORDS] with acc
+    [n_routes, acc_stride], and fec_wire, the FEC buffer's contents before the call -> dict of n_fec (int), fec_route, fec_seq, fec_frame, fec_offset (int64),
+    fec_size, fec_flags (uint8), fec_mask [max_fec_packets: n_routes * n_frames by default], next_fec_seq [n_routes], route_stats
+    [n_routes, FEC_ROUTE_STATS_WORDS], state / acc for the next call (None without state) and fec_wire (the buffer after the call); the outputs of
+    FEC_ENCODE_OPTIONAL not named in `optional` are passed as NULL and come back as None.  seq_in_place: the call gets its copy of fec_seq_base as next_fec_seq
+    too, as a caller may who keeps one array.  LC3Error for arguments the C call refuses."""
+    ins, outs, work, q = _fec_encode_arrays(pkt_route, pkt_frame, pkt_offset, pkt_size, wire, n_frames, seq_base, group, fec_seq_base, fec_wire, pkt_status, n_packets,
+                                            route_stats, flush, state, acc, acc_stride, max_fec_packets, optional)
+    pad = np.zeros(8, np.uint8)                                       # an empty array still has to be a pointer
+    ptr = lambda a: (a if a.size else pad).ctypes.data if a is not None else None
+    v = [ptr(ins[k]) for k in FEC_ENCODE_INPUTS] + [ptr(a) for a in outs] + [ptr(work)]
+    rc = load_library().lc3plus_plan_fec_encode(*_fec_encode_args(ins, outs, work, v, n_frames, header_room, payload_room, acc_stride, fec_stride, fec_header_room, q,
+                                                                  wire_capacity, fec_capacity, seq_in_place), None, 0)
+    if rc:
+        raise LC3Error(rc, "lc3plus_plan_fec_encode")
+    if seq_in_place:
+        outs[FEC_ENCODE_OUTPUTS.index("next_fec_seq")] = ins["fec_seq_base"]
+    return _fec_encode_result(outs)
+
+
+class _FecEncode:
+    """The send side of the generic FEC for both batch kinds (lc3plus_{enc,dec}_batch_fec_encode; include/lc3plus_batch.h "Generic FEC")."""
+
+    def fec_encode_device(self, max_packets, d_n_packets_ptr, d_pkt_route_ptr, d_pkt_frame_ptr, d_pkt_offset_ptr, d_pkt_size_ptr, d_wire_ptr, wire_capacity, n_routes,
+                          n_frames, d_seq_base_ptr, d_group_ptr, d_fec_seq_base_ptr, d_fec_wire_ptr, fec_capacity, fec_stride, max_fec_packets, d_n_fec_ptr,
+                          d_fec_route_ptr, d_fec_seq_ptr, d_fec_frame_ptr, d_fec_offset_ptr, d_fec_size_ptr, d_work_ptr, header_room=12, payload_room=0,
+                          fec_header_room=12, d_pkt_status_ptr=None, d_route_stats_ptr=None, d_flush_ptr=None, d_state_in_ptr=None, d_acc_in_ptr=None,
+                          d_state_out_ptr=None, d_acc_out_ptr=None, acc_stride=0, d_fec_flags_ptr=None, d_fec_mask_ptr=None, d_next_fec_seq_ptr=None,
+                          d_route_stats_out_ptr=None, hip_stream=None, sync=False):
+        """Raw device pointers only - the list a stamp call took with the stamp's pkt_status, the stamped wire buffer, per route seq_base, group, fec_seq_base and
+        the optional flush, route_stats (the egress's) and state / accumulator pairs -> RFC 5109 parity packets behind fec_header_room bytes each at
+        fec_wire + q * fec_stride, the FEC list fec_route, fec_seq, fec_frame, fec_offset (int64), fec_size [max_fec_packets] with its length n_fec (one int64) and
+        the optional fec_flags (uint8), fec_mask, next_fec_seq [n_routes], route_stats_out [n_routes, FEC_ROUTE_STATS_WORDS].  work: fec_work_bytes(n_routes,
+        n_frames) bytes.  Stateless: nothing of the batch's streams is read or written.  Queued on hip_stream; returns at once unless sync."""
+        def p(x):
+            return C.c_void_p(x) if x else None
+        rc = self._ssf("_fec_encode")(self.h, int(max_packets), p(d_n_packets_ptr), p(d_pkt_route_ptr), p(d_pkt_frame_ptr), p(d_pkt_offset_ptr), p(d_pkt_size_ptr),
+                                      p(d_pkt_status_ptr), p(d_wire_ptr), int(wire_capacity), int(header_room), int(payload_room), int(n_routes), int(n_frames),
+                                      p(d_seq_base_ptr), p(d_route_stats_ptr), p(d_group_ptr), p(d_flush_ptr), p(d_fec_seq_base_ptr), p(d_state_in_ptr), p(d_acc_in_ptr),
+                                      p(d_state_out_ptr), p(d_acc_out_ptr), int(acc_stride), p(d_fec_wire_ptr), int(fec_capacity), int(fec_stride), int(fec_header_room),
+                                      int(max_fec_packets), p(d_n_fec_ptr), p(d_fec_route_ptr), p(d_fec_seq_ptr), p(d_fec_frame_ptr), p(d_fec_offset_ptr),
+                                      p(d_fec_size_ptr), p(d_fec_flags_ptr), p(d_fec_mask_ptr), p(d_next_fec_seq_ptr), p(d_route_stats_out_ptr), p(d_work_ptr),
+                                      p(hip_stream), 1 if sync else 0)
+        if rc:
+            raise LC3Error(rc, self._ss + "_fec_encode")
+
+    def fec_encode(self, pkt_route, pkt_frame, pkt_offset, pkt_size, wire, n_frames, seq_base, group, fec_seq_base, fec_wire, fec_stride, header_room=12, payload_room=0,
+                   fec_header_room=12, pkt_status=None, n_packets=None, route_stats=None, flush=None, state=None, acc=None, acc_stride=None, max_fec_packets=None,
+                   wire_capacity=None, fec_capacity=None, optional=FEC_ENCODE_OPTIONAL, poison_work=None, seq_in_place=False):
+        """Host convenience: the arrays of plan_fec_encode uploaded, encoded on the device and downloaded -> the dict plan_fec_encode gives.  Device memory through
+        the HIP runtime (on the current device: the batch's, unless the caller has switched), freed before it returns.  poison_work: a byte the workspace is
+        filled with before the call (its contents mean nothing); seq_in_place as in plan_fec_encode."""
+        ins, outs, work, q = _fec_encode_arrays(pkt_route, pkt_frame, pkt_offset, pkt_size, wire, n_frames, seq_base, group, fec_seq_base, fec_wire, pkt_status,
+                                                n_packets, route_stats, flush, state, acc, acc_stride, max_fec_packets, optional)
+        if poison_work is not None:
+            work.view(np.uint8)[:] = int(poison_work)
+        arrays = [ins[k] for k in FEC_ENCODE_INPUTS] + outs + [work]
+        with _on_device(arrays) as (ptrs, back):
+            rc = self._ssf("_fec_encode")(self.h, *_fec_encode_args(ins, outs, work, list(ptrs), n_frames, header_room, payload_room, acc_stride, fec_stride,
+                                                                    fec_header_room, q, wire_capacity, fec_capacity, seq_in_place), None, 1)
+            if rc:
+                raise LC3Error(rc, self._ss + "_fec_encode")
+            for k in range(len(FEC_ENCODE_INPUTS), len(arrays) - 1):
+                back(k)
+            if seq_in_place:
+                back(FEC_ENCODE_INPUTS.index("fec_seq_base"))
+                outs[FEC_ENCODE_OUTPUTS.index("next_fec_seq")] = ins["fec_seq_base"]
+        return _fec_encode_result(outs)
+
+
+def _fec_recover_arrays(n_streams, ring, dg_offsets, dg_sizes, stream, seq, fec_stream, fec_offsets, fec_num_bytes, ssrc, window, optional):
+    """the arrays of a recover call as the C calls take them: (inputs dg_offsets, dg_sizes, stream, seq, fec_stream, fec_offsets, fec_num_bytes, ssrc; outputs in
+    FEC_RECOVER_OUTPUTS order, None for a NULL one; work)"""
+    stream = np.ascontiguousarray(stream, dtype=np.int32).reshape(-1)
+    n = stream.size
+    dg_offsets = _shaped(np.ascontiguousarray(dg_offsets, dtype=np.int64).reshape(-1), (n,), "the item arrays hold one entry per item")
+    dg_sizes = _shaped(np.ascontiguousarray(dg_sizes, dtype=np.int32).reshape(-1), (n,), "the item arrays hold one entry per item")
+    seq = _shaped(_u32(seq), (n,), "the item arrays hold one entry per item")
+    fec_stream = np.ascontiguousarray(fec_stream, dtype=np.int32).reshape(-1)
+    m = fec_stream.size
+    fec_offsets = _shaped(np.ascontiguousarray(fec_offsets, dtype=np.int64).reshape(-1), (m,), "the FEC item arrays hold one entry per FEC item")
+    fec_num_bytes = _shaped(np.ascontiguousarray(fec_num_bytes, dtype=np.int32).reshape(-1), (m,), "the FEC item arrays hold one entry per FEC item")
+    ssrc = _shaped(_u32(ssrc), (int(n_streams),), "ssrc holds one entry per stream")
+    ring = np.array(ring, dtype=np.uint8).reshape(-1)                 # a copy: the call's ring starts with these contents
+    outs = [ring, np.zeros(m, np.int64), np.zeros(m, np.int32), np.zeros(m, np.int32), np.zeros(m, np.uint8) if "status" in optional else None,
+            np.zeros(FEC_STATS_WORDS, np.int32) if "stats" in optional else None]
+    work = np.zeros(max(fec_recover_work_bytes(n_streams, window), 8) // 8, np.int64)
+    return [dg_offsets, dg_sizes, stream, seq, fec_stream, fec_offsets, fec_num_bytes, ssrc], outs, work
+
+
+def _fec_recover_args(ins, outs, v, window, rec_offset, rec_stride, ring_capacity):
+    """the C calls' arguments behind the batch or n_streams; v: the pointers of the inputs, the outputs and work"""
+    cap = outs[0].size if ring_capacity is None else int(ring_capacity)
+    return [ins[0].size, v[8], cap, v[0], v[1], v[2], v[3], ins[4].size, v[4], v[5], v[6], int(window), v[7], int(rec_offset), int(rec_stride), v[9], v[10], v[11], v[12],
+            v[13], v[14]]
+
+
+def plan_fec_recover(n_streams, ring, dg_offsets, dg_sizes, stream, seq, fec_stream, fec_offsets, fec_num_bytes, ssrc, rec_offset, rec_stride, window=1024,
+                     ring_capacity=None, optional=FEC_RECOVER_OPTIONAL):
+    """The rule of DecBatch.fec_recover on the host (lc3plus_plan_fec_recover, no device needed): the datagrams dg_offsets (int64), dg_sizes with the media parse's
+    stream, seq [n_items], the FEC parse's items fec_stream, fec_offsets (int64), fec_num_bytes [n_fec] over ring (uint8, its contents before the call), ssrc
+    [n_streams] -> dict of ring (after the call: recovered packets at rec_offset + f * rec_stride), rec_dg_offsets (int64), rec_dg_sizes, rec_seq, status (uint8)
+    [n_fec] and stats [FEC_STATS_WORDS]; those of FEC_RECOVER_OPTIONAL not named in `optional` are passed as NULL and come back as None.  LC3Error for arguments
+    the C call refuses."""
+    ins, outs, work = _fec_recover_arrays(n_streams, ring, dg_offsets, dg_sizes, stream, seq, fec_stream, fec_offsets, fec_num_bytes, ssrc, window, optional)
+    pad = np.zeros(8, np.uint8)
+    ptr = lambda a: (a if a.size else pad).ctypes.data if a is not None else None
+    v = [ptr(a) for a in ins + outs + [work]]
+    rc = load_library().lc3plus_plan_fec_recover(int(n_streams), *_fec_recover_args(ins, outs, v, window, rec_offset, rec_stride, ring_capacity), None, 0)
+    if rc:
+        raise LC3Error(rc, "lc3plus_plan_fec_recover")
+    return dict(zip(FEC_RECOVER_OUTPUTS, outs))
+
+
 RR_OPTIONAL = ("ext_seq", "item_status", "stream_stats")
 RR_OUTPUTS = ("state", "blocks", "ext_seq", "item_status", "stream_stats")
 
@@ -1284,7 +1502,7 @@ def stream_header_ok(header, blob):
     return bool(load_library().lc3plus_stream_header_ok(h.ctypes.data, b.ctypes.data))
 
 
-class Batch(_StreamLifecycle, _Egress, _RtpStamp, _SrtpProtect, _RedPack):
+class Batch(_StreamLifecycle, _Egress, _RtpStamp, _SrtpProtect, _RedPack, _FecEncode):
     """n_streams independent encoders (lc3plus_enc_batch_*), state resident on the GPU between encode() calls."""
 
     def __init__(self, n_streams, samplerate, channels, frame_ms, hrmode, bitrates, device=-1):
@@ -1823,7 +2041,7 @@ def plan_ingest(n_streams, channels, stream, seq, offsets, num_bytes, base, n_fr
     return dict(zip(ING_OUTPUTS, outs))
 
 
-class DecBatch(_StreamLifecycle, _Egress, _RtpStamp, _SrtpProtect, _RedPack):
+class DecBatch(_StreamLifecycle, _Egress, _RtpStamp, _SrtpProtect, _RedPack, _FecEncode):
     """n_streams independent decoders (lc3plus_dec_batch_*), state resident on the GPU between decode() calls."""
 
     def __init__(self, n_streams, samplerate, channels, frame_ms, hrmode, num_bytes, device=-1):
@@ -2078,6 +2296,40 @@ class DecBatch(_StreamLifecycle, _Egress, _RtpStamp, _SrtpProtect, _RedPack):
             for k in range(7, 15):
                 back(k)
         return dict(zip(RED_UNPACK_OUTPUTS, outs))
+
+    def fec_recover_device(self, n_items, d_ring_ptr, ring_capacity, d_dg_offsets_ptr, d_dg_sizes_ptr, d_stream_ptr, d_seq_ptr, n_fec, d_fec_stream_ptr, d_fec_offsets_ptr,
+                           d_fec_num_bytes_ptr, window, d_ssrc_ptr, rec_offset, rec_stride, d_rec_dg_offsets_ptr, d_rec_dg_sizes_ptr, d_rec_seq_ptr, d_work_ptr,
+                           d_status_ptr=None, d_stats_ptr=None, hip_stream=None, sync=False):
+        """The receive side of the generic FEC (lc3plus_dec_batch_fec_recover): raw device pointers only - the datagram list dg_offsets (int64), dg_sizes with the
+        media parse's stream, seq [n_items], the FEC parse's fec_stream, fec_offsets (int64), fec_num_bytes [n_fec] over the ring, ssrc [n_streams] -> every media
+        packet that is the only one missing of an FEC item's group rebuilt at ring + rec_offset + f * rec_stride, and rec_dg_offsets (int64), rec_dg_sizes,
+        rec_seq [n_fec] - a datagram list for rtp_parse_device - with the optional status (uint8) [n_fec] and stats [FEC_STATS_WORDS].  work:
+        fec_recover_work_bytes(n_streams, window) bytes.  Stateless: nothing of the batch's streams is read or written.  Queued on hip_stream; returns at once
+        unless sync."""
+        def p(x):
+            return C.c_void_p(x) if x else None
+        rc = self.lib.lc3plus_dec_batch_fec_recover(self.h, int(n_items), p(d_ring_ptr), int(ring_capacity), p(d_dg_offsets_ptr), p(d_dg_sizes_ptr), p(d_stream_ptr),
+                                                    p(d_seq_ptr), int(n_fec), p(d_fec_stream_ptr), p(d_fec_offsets_ptr), p(d_fec_num_bytes_ptr), int(window),
+                                                    p(d_ssrc_ptr), int(rec_offset), int(rec_stride), p(d_rec_dg_offsets_ptr), p(d_rec_dg_sizes_ptr), p(d_rec_seq_ptr),
+                                                    p(d_status_ptr), p(d_stats_ptr), p(d_work_ptr), p(hip_stream), 1 if sync else 0)
+        if rc:
+            raise LC3Error(rc, "lc3plus_dec_batch_fec_recover")
+
+    def fec_recover(self, ring, dg_offsets, dg_sizes, stream, seq, fec_stream, fec_offsets, fec_num_bytes, ssrc, rec_offset, rec_stride, window=1024, ring_capacity=None,
+                    optional=FEC_RECOVER_OPTIONAL, poison_work=None):
+        """Host convenience: the arrays of plan_fec_recover uploaded, recovered on the device and downloaded -> the dict plan_fec_recover gives.  Device memory
+        through the HIP runtime as in probe(), freed before it returns.  poison_work: a byte the workspace is filled with before the call."""
+        ins, outs, work = _fec_recover_arrays(self.n_streams, ring, dg_offsets, dg_sizes, stream, seq, fec_stream, fec_offsets, fec_num_bytes, ssrc, window, optional)
+        if poison_work is not None:
+            work.view(np.uint8)[:] = int(poison_work)
+        arrays = ins + outs + [work]
+        with _on_device(arrays) as (v, back):
+            rc = self.lib.lc3plus_dec_batch_fec_recover(self.h, *_fec_recover_args(ins, outs, list(v), window, rec_offset, rec_stride, ring_capacity), None, 1)
+            if rc:
+                raise LC3Error(rc, "lc3plus_dec_batch_fec_recover")
+            for k in range(len(ins), len(arrays) - 1):
+                back(k)
+        return dict(zip(FEC_RECOVER_OUTPUTS, outs))
 
     def rtcp_stats_device(self, n_items, d_stream_ptr, d_seq_ptr, d_timestamp_ptr, d_arrival_ptr, n_streams, d_state_in_ptr, d_state_out_ptr, d_workspace_ptr,
                           workspace_bytes, make_report=False, d_ssrc_ptr=None, d_lsr_ptr=None, d_dlsr_ptr=None, d_blocks_ptr=None, d_ext_seq_ptr=None,

@@ -30,6 +30,7 @@
 #include "lc3_srtp_shim.h"
 #include "lc3_gcm_shim.h"
 #include "lc3_red_shim.h"
+#include "lc3_fec_shim.h"
 
 #ifndef M_PI
 #define M_PI 3.14159265358979323846
@@ -1849,7 +1850,7 @@ LC3_Error lc3plus_frame_info_side(int samplerate, int channels, float frame_ms, 
     return LC3_OK;
 }
 /* ---- the sibling libraries (DESIGN.md "Sibling libraries"): the kernels of every call below lie in a library of their own beside this one ---- */
-enum { SIB_PROBE, SIB_INGEST, SIB_EGRESS, SIB_RTP, SIB_RTCP, SIB_SRTP, SIB_GCM, SIB_RED, SIB_COUNT };
+enum { SIB_PROBE, SIB_INGEST, SIB_EGRESS, SIB_RTP, SIB_RTCP, SIB_SRTP, SIB_GCM, SIB_RED, SIB_FEC, SIB_COUNT };
 /* a row: the file, its one or two entry points, and where they go.  fn holds either all of them or none */
 static struct { const char* file; const char* sym[2]; int tried; void* fn[2]; } siblings[SIB_COUNT] = {
     [SIB_PROBE] = {"liblc3plus_probe_hip.so", {"lc3probe_run", NULL}, 0, {NULL, NULL}},
@@ -1860,6 +1861,7 @@ static struct { const char* file; const char* sym[2]; int tried; void* fn[2]; } 
     [SIB_SRTP] = {"liblc3plus_srtp_hip.so", {"lc3srtp_protect_run", "lc3srtp_unprotect_run"}, 0, {NULL, NULL}},
     [SIB_GCM] = {"liblc3plus_gcm_hip.so", {"lc3gcm_protect_run", "lc3gcm_unprotect_run"}, 0, {NULL, NULL}},
     [SIB_RED] = {"liblc3plus_red_hip.so", {"lc3red_pack_run", "lc3red_unpack_run"}, 0, {NULL, NULL}},
+    [SIB_FEC] = {"liblc3plus_fec_hip.so", {"lc3fec_encode_run", "lc3fec_recover_run"}, 0, {NULL, NULL}},
 };
 static pthread_mutex_t sibling_mu = PTHREAD_MUTEX_INITIALIZER;
 /* The entry points of a sibling, or NULL where the library is missing or lacks one of them.  The file is looked for once per process, on the first call that needs
@@ -2570,6 +2572,277 @@ LC3_Error lc3plus_dec_batch_red_unpack(lc3plus_dec_batch* b, int64_t n_items,
     if (!fn) return LC3_ERROR;
     q.sync = sync; q.n_items = (long long)n_items; q.io = red_unpack_io(&a, b->n_streams); q.stats = stats;
     return ((int (*)(const lc3red_unpack_call*))fn[1])(&q) ? LC3_ERROR : LC3_OK;
+}
+/* ---- generic FEC (include/lc3plus_batch.h "Generic FEC"; lc3_fec_shim.h) ---- */
+/* what every encode call takes behind its batch, in the header's order */
+typedef struct {
+    int64_t max_packets; const int64_t* n_packets; const int32_t* pkt_route; const int32_t* pkt_frame; const int64_t* pkt_offset; const int32_t* pkt_size;
+    const uint8_t* pkt_status; const void* wire; int64_t wire_capacity; int header_room; int payload_room;
+    int n_routes; int n_frames; const int32_t* seq_base; const int32_t* route_stats; const int32_t* group; const uint8_t* flush; const int32_t* fec_seq_base;
+    const int32_t* state_in; const uint8_t* acc_in; int32_t* state_out; uint8_t* acc_out; int acc_stride;
+    void* fec_wire; int64_t fec_capacity; int64_t fec_stride; int fec_header_room;
+    int64_t max_fec_packets; int64_t* n_fec; int32_t* fec_route; int32_t* fec_seq; int32_t* fec_frame; int64_t* fec_offset; int32_t* fec_size; uint8_t* fec_flags;
+    int32_t* fec_mask; int32_t* next_fec_seq; int32_t* route_stats_out; void* work;
+} fec_encode_args;
+/* the checks every encode call makes first, in the header's order */
+static LC3_Error fec_encode_check(const fec_encode_args* a)
+{
+    if (!a->n_packets || !a->pkt_route || !a->pkt_frame || !a->pkt_offset || !a->pkt_size || !a->wire || !a->seq_base || !a->group || !a->fec_seq_base || !a->fec_wire ||
+        !a->n_fec || !a->fec_route || !a->fec_seq || !a->fec_frame || !a->fec_offset || !a->fec_size || !a->work)
+        return LC3_NULL_ERROR;
+    if (a->max_packets <= 0 || a->max_packets >= LC3FEC_MAX_PACKETS || a->wire_capacity < 0 || a->payload_room < 0 || a->header_room < LC3R_FIXED + a->payload_room)
+        return LC3_ERROR;
+    if (a->n_routes <= 0 || a->n_frames <= 0 || (long long)a->n_routes * a->n_frames >= LC3E_MAX_CELLS) return LC3_ERROR;
+    const int given = (a->state_in != NULL) + (a->acc_in != NULL) + (a->state_out != NULL) + (a->acc_out != NULL);
+    if (given != 0 && given != 4) return LC3_ERROR;
+    if (given && (a->acc_stride <= 0 || (a->acc_stride & 15))) return LC3_ERROR;
+    if (given) {                                                      /* an out buffer may not meet its in buffer: the rows of different routes are different waves */
+        const uintptr_t sb = sizeof(int32_t) * LC3FEC_STATE_WORDS * (uintptr_t)a->n_routes, ab = (uintptr_t)a->acc_stride * (uintptr_t)a->n_routes;
+        const uintptr_t si = (uintptr_t)a->state_in, so = (uintptr_t)a->state_out, ai = (uintptr_t)a->acc_in, ao = (uintptr_t)a->acc_out;
+        if ((si < so + sb && so < si + sb) || (ai < ao + ab && ao < ai + ab)) return LC3_ERROR;
+    }
+    if (a->fec_capacity < 0 || a->fec_stride <= 0 || a->fec_stride > LC3FEC_MAX_STRIDE || a->fec_header_room < LC3R_FIXED || a->fec_header_room > LC3FEC_MAX_PKT ||
+        a->max_fec_packets <= 0)
+        return LC3_ERROR;
+    const uintptr_t w0 = (uintptr_t)a->wire, d0 = (uintptr_t)a->fec_wire;
+    if (d0 < w0 + (uintptr_t)a->wire_capacity && w0 < d0 + (uintptr_t)a->fec_capacity) return LC3_ERROR;              /* out of place only */
+    if ((uintptr_t)a->work & 7) return LC3_ERROR;
+    return LC3_OK;
+}
+static void fec_encode_io(const fec_encode_args* a, lc3fec_enc_in* q, lc3fec_enc_out* o)
+{
+    const lc3fec_enc_in in = {(const long long*)a->n_packets, a->pkt_route, a->pkt_frame, (const long long*)a->pkt_offset, a->pkt_size, a->pkt_status,
+                              (const uint8_t*)a->wire, a->seq_base, a->route_stats, a->group, a->flush, a->fec_seq_base, a->state_in, a->acc_in,
+                              (long long)a->max_packets, (long long)a->wire_capacity, (long long)a->max_fec_packets, (long long)a->fec_capacity, (long long)a->fec_stride,
+                              a->header_room, a->payload_room, a->n_routes, a->n_frames, a->state_in ? a->acc_stride : 0, a->fec_header_room, a->state_out != NULL};
+    const lc3fec_enc_out out = {(long long*)a->n_fec, a->fec_route, a->fec_seq, a->fec_frame, (long long*)a->fec_offset, a->fec_size, a->fec_flags, a->fec_mask,
+                                a->next_fec_seq, a->route_stats_out, a->state_out, a->acc_out, (uint8_t*)a->fec_wire};
+    *q = in; *o = out;
+}
+int64_t lc3plus_fec_work_bytes(int n_routes, int n_frames)
+{
+    if (n_routes <= 0 || n_frames <= 0 || (long long)n_routes * n_frames >= LC3E_MAX_CELLS) return 0;
+    return lc3fec_work_bytes(n_routes, n_frames);
+}
+int64_t lc3plus_fec_recover_work_bytes(int n_streams, int window)
+{
+    if (n_streams <= 0 || window < 64 || window > 65536 || (window & (window - 1))) return 0;
+    return lc3fec_recover_work_bytes(n_streams, window);
+}
+/* dst[0 .. n) ^= src[0 .. n) */
+static void fec_xor(uint8_t* dst, const uint8_t* src, int n) { for (int i = 0; i < n; i++) dst[i] ^= src[i]; }
+#define FEC_ENCODE_PARAMS \
+    int64_t max_packets, const int64_t* n_packets, const int32_t* pkt_route, const int32_t* pkt_frame, const int64_t* pkt_offset, const int32_t* pkt_size, \
+    const uint8_t* pkt_status, const void* wire, int64_t wire_capacity, int header_room, int payload_room, \
+    int n_routes, int n_frames, const int32_t* seq_base, const int32_t* route_stats, const int32_t* group, const uint8_t* flush, const int32_t* fec_seq_base, \
+    const int32_t* state_in, const uint8_t* acc_in, int32_t* state_out, uint8_t* acc_out, int acc_stride, \
+    void* fec_wire, int64_t fec_capacity, int64_t fec_stride, int fec_header_room, \
+    int64_t max_fec_packets, int64_t* n_fec, int32_t* fec_route, int32_t* fec_seq, int32_t* fec_frame, int64_t* fec_offset, int32_t* fec_size, uint8_t* fec_flags, \
+    int32_t* fec_mask, int32_t* next_fec_seq, int32_t* route_stats_out, void* work, void* hip_stream, int sync
+#define FEC_ENCODE_ARGS \
+    {max_packets, n_packets, pkt_route, pkt_frame, pkt_offset, pkt_size, pkt_status, wire, wire_capacity, header_room, payload_room, n_routes, n_frames, seq_base, \
+     route_stats, group, flush, fec_seq_base, state_in, acc_in, state_out, acc_out, acc_stride, fec_wire, fec_capacity, fec_stride, fec_header_room, max_fec_packets, \
+     n_fec, fec_route, fec_seq, fec_frame, fec_offset, fec_size, fec_flags, fec_mask, next_fec_seq, route_stats_out, work}
+/* the rule on the host: the steps of the kernels (lc3_fec.inc) one after the other, on the text they run and over the same workspace */
+LC3_Error lc3plus_plan_fec_encode(FEC_ENCODE_PARAMS)
+{
+    (void)hip_stream; (void)sync;
+    const fec_encode_args a = FEC_ENCODE_ARGS;
+    const LC3_Error e = fec_encode_check(&a);
+    if (e) return e;
+    lc3fec_enc_in q;
+    lc3fec_enc_out o;
+    fec_encode_io(&a, &q, &o);
+    const long long cells = (long long)n_routes * n_frames, n = lc3fec_count(q.n_packets, q.max_packets), n_tiles = lc3fec_tiles(n_routes);
+    int32_t* map = (int32_t*)work;
+    long long* sums = (long long*)((char*)work + lc3fec_work_sums(n_routes, n_frames));
+    long long* qbase = (long long*)((char*)work + lc3fec_work_qbase(n_routes, n_frames));
+    int32_t* fseq = (int32_t*)((char*)work + lc3fec_work_fseq(n_routes, n_frames));
+    /* fill and scatter */
+    for (long long i = 0; i < cells; i++) map[i] = LC3FEC_NO_ENTRY;
+    for (long long p = 0; p < n; p++) {
+        const long long cell = lc3fec_entry_cell(&q, p);
+        if (cell >= 0 && (int32_t)p < map[cell]) map[cell] = (int32_t)p;
+    }
+    /* the tiles' sums, their bases and the total, then every route's first entry */
+    for (long long b = 0; b < n_tiles; b++) {
+        long long s = 0;
+        for (long long r = b * LC3FEC_TILE; r < n_routes && r < (b + 1) * LC3FEC_TILE; r++) s += lc3fec_route_plan(&q, (int)r).nclosed;
+        sums[b] = s;
+    }
+    long long run_b = 0;
+    for (long long b = 0; b < n_tiles; b++) { const long long s = sums[b]; sums[b] = run_b; run_b += s; }
+    *n_fec = run_b;
+    for (long long b = 0; b < n_tiles; b++) {
+        long long run = sums[b];
+        for (long long r = b * LC3FEC_TILE; r < n_routes && r < (b + 1) * LC3FEC_TILE; r++) {
+            const int w = lc3fec_route_plan(&q, (int)r).nclosed;
+            qbase[r] = run;
+            fseq[r] = fec_seq_base[r];                                /* next_fec_seq may be fec_seq_base: the records are numbered from this copy */
+            if (next_fec_seq) next_fec_seq[r] = (int32_t)((uint32_t)fseq[r] + (uint32_t)w);
+            if (route_stats_out) memset(route_stats_out + r * LC3FEC_RS_WORDS, 0, sizeof(int32_t) * LC3FEC_RS_WORDS);
+            run += w;
+        }
+    }
+    /* the groups */
+    for (int r = 0; r < n_routes; r++) {
+        const lc3fec_plan P = lc3fec_route_plan(&q, r);
+        for (int g = 0; g < P.ng; g++) {
+            const lc3fec_group G = lc3fec_group_of(&P, g);
+            long long at[LC3FEC_MAX_GROUP];
+            int32_t len[LC3FEC_MAX_GROUP];
+            const int cnt = G.t1 - G.t0;
+            for (int i = 0; i < cnt; i++) { at[i] = 0; len[i] = -1; if (!lc3fec_member(&q, map, r, G.t0 + i, &at[i], &len[i])) len[i] = -1; }
+            const lc3fec_fold f = lc3fec_fold_group(&q, r, &G, at, len);
+            uint8_t* dst = NULL;
+            int nbytes = 0;
+            if (G.closes) {
+                const long long en = qbase[r] + g;
+                int32_t size = 0;
+                if (route_stats_out) route_stats_out[(size_t)r * LC3FEC_RS_WORDS + LC3FEC_RS_GROUPS]++;
+                if (!lc3fec_emit(&q, &o, r, g, &G, &f, en, fseq[r], &size)) continue;
+                uint32_t w[4];
+                dst = o.fec_wire + en * q.fec_stride + q.fec_header_room;
+                lc3fec_header(&f, w);
+                lc3fec_header_out(dst, w);
+                dst += LC3FEC_HEADER; nbytes = f.plen;
+                if (route_stats_out) {
+                    int32_t* st = route_stats_out + (size_t)r * LC3FEC_RS_WORDS;
+                    st[LC3FEC_RS_PACKETS]++; st[LC3FEC_RS_MEDIA] += __builtin_popcount(f.mask); st[LC3FEC_RS_BYTES] += f.plen;
+                }
+                memset(dst, 0, (size_t)nbytes);
+            } else if (q.carry) {
+                const int keep = lc3fec_state_out(&q, state_out + (size_t)r * LC3FEC_STATE_WORDS, &G, &f);
+                dst = acc_out + (size_t)r * acc_stride;
+                memset(dst, 0, (size_t)acc_stride);
+                if (!keep) continue;
+            } else continue;
+            if (G.F0 > 0) {                                           /* the carried accumulator counts up to the length the state names */
+                int32_t xlen = state_in[(size_t)r * LC3FEC_STATE_WORDS + LC3FEC_S_MAX];
+                xlen = xlen < 0 || xlen > q.acc_stride || xlen > f.plen ? 0 : xlen;
+                fec_xor(dst, acc_in + (size_t)r * acc_stride, xlen);
+            }
+            for (int i = 0; i < cnt; i++)
+                if (len[i] > 0) fec_xor(dst, q.wire + at[i], len[i]);
+        }
+        if (q.carry && !P.open) {                                     /* no open group: the state is handed through (c = 0) or ends */
+            if (P.c == 0) {
+                memcpy(state_out + (size_t)r * LC3FEC_STATE_WORDS, state_in + (size_t)r * LC3FEC_STATE_WORDS, sizeof(int32_t) * LC3FEC_STATE_WORDS);
+                memcpy(acc_out + (size_t)r * acc_stride, acc_in + (size_t)r * acc_stride, (size_t)acc_stride);
+            } else {
+                memset(state_out + (size_t)r * LC3FEC_STATE_WORDS, 0, sizeof(int32_t) * LC3FEC_STATE_WORDS);
+                memset(acc_out + (size_t)r * acc_stride, 0, (size_t)acc_stride);
+            }
+        }
+    }
+    return LC3_OK;
+}
+/* both encode entry points end here.  Of the batch: its device and stream.  No stream state, no configuration, no buffer */
+static LC3_Error fec_encode_queue(void* dev, int decoder, const fec_encode_args* a, void* hip_stream, int sync)
+{
+    lc3fec_encode_call q;
+    memset(&q, 0, sizeof q);
+    void* const* fn = sibling_call(SIB_FEC, dev, decoder, hip_stream, &q.device, &q.hip_stream);
+    if (!fn) return LC3_ERROR;
+    q.sync = sync; q.work = a->work;
+    fec_encode_io(a, &q.in, &q.out);
+    return ((int (*)(const lc3fec_encode_call*))fn[0])(&q) ? LC3_ERROR : LC3_OK;
+}
+LC3_Error lc3plus_enc_batch_fec_encode(lc3plus_batch* b, FEC_ENCODE_PARAMS)
+{
+    if (!b) return LC3_NULL_ERROR;
+    const fec_encode_args a = FEC_ENCODE_ARGS;
+    const LC3_Error e = fec_encode_check(&a);
+    if (e) return e;
+    return fec_encode_queue(b->dev, 0, &a, hip_stream, sync);
+}
+LC3_Error lc3plus_dec_batch_fec_encode(lc3plus_dec_batch* b, FEC_ENCODE_PARAMS)
+{
+    if (!b) return LC3_NULL_ERROR;
+    const fec_encode_args a = FEC_ENCODE_ARGS;
+    const LC3_Error e = fec_encode_check(&a);
+    if (e) return e;
+    return fec_encode_queue(b->dev, 1, &a, hip_stream, sync);
+}
+/* what a recover call takes behind its batch, in the header's order */
+typedef struct {
+    int64_t n_items; void* ring; int64_t ring_capacity; const int64_t* dg_offsets; const int32_t* dg_sizes; const int32_t* stream; const int32_t* seq;
+    int64_t n_fec; const int32_t* fec_stream; const int64_t* fec_offsets; const int32_t* fec_num_bytes; int window; const int32_t* ssrc;
+    int64_t rec_offset; int64_t rec_stride; int64_t* rec_dg_offsets; int32_t* rec_dg_sizes; int32_t* rec_seq; uint8_t* status; int32_t* stats; void* work;
+} fec_recover_args;
+static LC3_Error fec_recover_check(const fec_recover_args* a)
+{
+    if (!a->ring || !a->dg_offsets || !a->dg_sizes || !a->stream || !a->seq || !a->fec_stream || !a->fec_offsets || !a->fec_num_bytes || !a->ssrc ||
+        !a->rec_dg_offsets || !a->rec_dg_sizes || !a->rec_seq || !a->work)
+        return LC3_NULL_ERROR;
+    if (a->n_items <= 0 || a->n_items >= LC3R_MAX_ITEMS || a->ring_capacity < 0 || a->n_fec <= 0 || a->n_fec >= LC3R_MAX_ITEMS) return LC3_ERROR;
+    if (a->window < 64 || a->window > 65536 || (a->window & (a->window - 1))) return LC3_ERROR;
+    if (a->rec_offset < 0 || a->rec_stride < LC3R_FIXED || a->rec_stride > LC3FEC_MAX_STRIDE || ((uintptr_t)a->work & 7)) return LC3_ERROR;
+    return LC3_OK;
+}
+static lc3fec_rec_io fec_recover_io(const fec_recover_args* a, int n_streams)
+{
+    const lc3fec_rec_io q = {(uint8_t*)a->ring, (const long long*)a->dg_offsets, a->dg_sizes, a->stream, a->seq, a->fec_stream, (const long long*)a->fec_offsets,
+                             a->fec_num_bytes, a->ssrc, (long long*)a->rec_dg_offsets, a->rec_dg_sizes, a->rec_seq, a->status, (long long)a->ring_capacity,
+                             (long long)a->n_items, (long long)a->n_fec, (long long)a->rec_offset, (long long)a->rec_stride, n_streams, a->window};
+    return q;
+}
+#define FEC_RECOVER_PARAMS \
+    int64_t n_items, void* ring, int64_t ring_capacity, const int64_t* dg_offsets, const int32_t* dg_sizes, const int32_t* stream, const int32_t* seq, \
+    int64_t n_fec, const int32_t* fec_stream, const int64_t* fec_offsets, const int32_t* fec_num_bytes, int window, const int32_t* ssrc, \
+    int64_t rec_offset, int64_t rec_stride, int64_t* rec_dg_offsets, int32_t* rec_dg_sizes, int32_t* rec_seq, uint8_t* status, int32_t* stats, void* work, \
+    void* hip_stream, int sync
+#define FEC_RECOVER_ARGS \
+    {n_items, ring, ring_capacity, dg_offsets, dg_sizes, stream, seq, n_fec, fec_stream, fec_offsets, fec_num_bytes, window, ssrc, rec_offset, rec_stride, \
+     rec_dg_offsets, rec_dg_sizes, rec_seq, status, stats, work}
+/* the rule on the host: the kernels' steps (lc3_fec.inc) on the text they run */
+LC3_Error lc3plus_plan_fec_recover(int n_streams, FEC_RECOVER_PARAMS)
+{
+    (void)hip_stream; (void)sync;
+    const fec_recover_args a = FEC_RECOVER_ARGS;
+    const LC3_Error e = fec_recover_check(&a);
+    if (e) return e;
+    if (n_streams <= 0) return LC3_ERROR;
+    const lc3fec_rec_io q = fec_recover_io(&a, n_streams);
+    int32_t* table = (int32_t*)work;
+    for (long long i = 0; i < (long long)n_streams * window; i++) table[i] = LC3FEC_NO_ENTRY;
+    for (long long i = 0; i < n_items; i++) {
+        const int s = stream[i];
+        if (s < 0 || s >= n_streams) continue;
+        int32_t* e_ = table + (size_t)s * window + ((uint32_t)seq[i] & (uint32_t)(window - 1));
+        if ((int32_t)i < *e_) *e_ = (int32_t)i;
+    }
+    if (stats) memset(stats, 0, sizeof(int32_t) * LC3FEC_STATS_WORDS);
+    for (long long f = 0; f < n_fec; f++) {
+        const int st = lc3fec_verdict(&q, table, f);
+        if (stats) stats[st]++;
+        if (st != LC3FEC_RECOVERED) continue;
+        lc3fec_item h;
+        lc3fec_item_header(&q, f, &h);
+        const int rl = rec_dg_sizes[f] - LC3R_FIXED;
+        uint8_t* dst = q.ring + rec_dg_offsets[f] + LC3R_FIXED;
+        memcpy(dst, q.ring + fec_offsets[f] + h.hl, (size_t)rl);
+        for (int i = 0; i < (h.hl == LC3FEC_HEADER ? 16 : LC3FEC_MAX_BITS); i++) {
+            long long at = 0;
+            int32_t len = 0;
+            if (!(h.mask >> (LC3FEC_MAX_BITS - 1 - i) & 1) || !lc3fec_lookup(&q, table, fec_stream[f], (h.sn + (uint32_t)i) & 0xFFFFu, &at, &len)) continue;
+            fec_xor(dst, q.ring + at, IMIN(len, rl));
+        }
+    }
+    return LC3_OK;
+}
+LC3_Error lc3plus_dec_batch_fec_recover(lc3plus_dec_batch* b, FEC_RECOVER_PARAMS)
+{
+    if (!b) return LC3_NULL_ERROR;
+    const fec_recover_args a = FEC_RECOVER_ARGS;
+    const LC3_Error e = fec_recover_check(&a);
+    if (e) return e;
+    lc3fec_recover_call q;
+    memset(&q, 0, sizeof q);
+    void* const* fn = sibling_call(SIB_FEC, b->dev, 1, hip_stream, &q.device, &q.hip_stream);
+    if (!fn) return LC3_ERROR;
+    q.sync = sync; q.io = fec_recover_io(&a, b->n_streams); q.stats = stats; q.work = work;
+    return ((int (*)(const lc3fec_recover_call*))fn[1])(&q) ? LC3_ERROR : LC3_OK;
 }
 /* ---- reception reports (include/lc3plus_batch.h "Reception reports"; lc3_rtcp_shim.h) ---- */
 /* what a stats call takes behind its batch, in the header's order */

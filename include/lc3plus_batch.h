@@ -988,6 +988,162 @@ LC3_Error lc3plus_plan_red_unpack(int n_streams, int64_t n_items,
     int32_t* out_stream, int32_t* out_seq, int64_t* out_offsets, int32_t* out_num_bytes, int32_t* out_timestamp, uint8_t* out_gen, uint8_t* status, int32_t* stats,
     void* hip_stream, int sync);
 
+/* ---- Generic FEC: XOR parity packets out, lost packets back (RFC 5109), on the device ------------------------------------------------------------------------
+ * Redundant audio costs one whole extra frame per packet and generation.  One parity packet over k media packets repairs a single loss per group for 1/k of the
+ * bytes.  lc3plus_*_batch_fec_encode writes such packets behind the stamp, lc3plus_dec_batch_fec_recover rebuilds lost media packets behind the parse:
+ *   sender    ... egress (wire) [-> red_pack] -> stamp -> fec_encode -> stamp (FEC list) -> protect (media), protect (FEC)
+ *   receiver  unprotect -> parse (media types) + parse (FEC types) -> fec_recover -> parse (recovered) [-> red_unpack] -> probe -> ingest -> decode_packed
+ * all on one HIP stream with no host wait.  NOT HANDLED: interleaved groups on the sender (a group is k consecutive sequence numbers), protection levels above
+ * 0, iterative recovery (the pass is single: a packet recovered by one FEC item is not fed to another), RFC 8627 (FlexFEC), FEC carried inside RED.
+ *
+ * THE WIRE FORMAT.  An FEC packet is an RTP packet; its twelve header bytes are the stamp's work.  Its payload is a 10-byte FEC header, one level header and the
+ * level-0 payload, all fields big-endian:
+ *   byte 0      E(1) L(1) P(1) X(1) CC(4)       byte 1      M(1) PT recovery(7)       bytes 2-3   SN base
+ *   bytes 4-7   TS recovery                      bytes 8-9   length recovery
+ *   level header: the protection length (16 bits) and the mask, 16 bits with L = 0 and 48 bits with L = 1; its most significant bit is i = 0, and bit i set means
+ *   the media packet with sequence number SN base + i mod 2^16 is protected
+ * For a protected RTP packet of n bytes its length is n - 12: CSRC list, extension, payload and padding.  The recovery fields are the XOR, over the protected
+ * packets, of the low 6 bits of byte 0, of byte 1, of bytes 4 ... 7 and of the 16-bit length.  The protection length plen is the largest of those lengths.  The
+ * level-0 payload is the XOR of bytes 12 ... 12 + plen of every protected packet, shorter packets padded with zeros.  E is 0.
+ *
+ * ENCODE.  Every pointer but `batch` is a device pointer and is read when the kernels run.  The call is STATELESS and allocates nothing; it borrows the batch's
+ * device (the encoder form serves a sender, the decoder form a forwarder), is queued on hip_stream (NULL: the batch's stream) and returns at once unless sync.
+ *   max_packets, n_packets, pkt_route, pkt_frame, pkt_offset (int64), pkt_size : the list the stamp took
+ *   pkt_status         : the stamp's output; NULL: every entry counts as stamped
+ *   wire, wire_capacity, header_room, payload_room : as the stamp took them.  The RTP packet of entry p is wire[a .. pkt_offset + pkt_size) with
+ *                        a = pkt_offset + header_room - payload_room - 12.  wire is not modified
+ *   n_routes, n_frames, seq_base [n_routes] (the egress's), route_stats (the egress's stats, may be NULL): the count c of route r is route_stats[r][0] clamped to
+ *                        [0, n_frames], n_frames with route_stats NULL - the stamp's reading
+ *   group [n_routes]   : int32, clamped to [0, LC3PLUS_FEC_MAX_GROUP]; 0: no parity for the route.  A kernel of the caller's sets it from the loss fraction of
+ *                        the reception reports
+ *   flush [n_routes]   : uint8, may be NULL;   fec_seq_base [n_routes] : the sequence number of each route's first FEC packet of this call
+ *   state_in, state_out [n_routes][LC3PLUS_FEC_STATE_WORDS] int32 and acc_in, acc_out [n_routes][acc_stride] bytes (acc_stride a multiple of 16): all four or
+ *                        none.  They join consecutive calls into one stream: real-time calls are one frame long, so a group spans calls.  The words are FILL
+ *                        (positions passed in the open group), K of the open group, SN base, the mask so far, the XOR of header bytes 0-1 (b0 & 63 | b1 << 8),
+ *                        the XOR of the timestamps, the XOR of the lengths, the largest length (-1: the group was dropped); the accumulator row is the open
+ *                        group's XOR so far, zeros behind the largest length.  An out buffer may not be its in buffer: the caller alternates two.  Without them
+ *                        every route starts empty and an open group is dropped at the end.  A state with K outside [1, 16] or FILL outside [1, K) holds no group
+ * THE GROUP RULE, pure arithmetic per route.  Position t of route r has sequence number seq_base[r] + t, whether or not a packet exists there.  With F = FILL and
+ * K from the state: if F > 0, the first K - F positions complete the carried group; after that groups of k = group[r] positions open one after the other; with
+ * k = 0 the remaining positions are unprotected and FILL ends 0.  A group closes when it is full, and after position c - 1 when flush[r] != 0 and its FILL > 0.
+ * Position i of a group is mask bit i, L is 0 always, SN base is the sequence number of the group's position 0.  A route with c = 0 hands its state and
+ * accumulator through.
+ * MEMBERS.  Cell (r, t), t < c, is a member where a list entry p < min(*n_packets, max_packets) names it (the lowest p wins) that is STAMPED (or pkt_status is
+ * NULL), lies in wire as the protect call's RANGE has it (pkt_offset >= 0, header_room <= pkt_size <= 2^20, pkt_offset + pkt_size <= wire_capacity) and whose
+ * length is at most 65 535.  A hole leaves its mask bit 0.
+ * OUTPUT.  One list entry per group that closes in this call, route-major with groups ascending: entry q by an exclusive scan over the routes' closed-group
+ * counts; *n_fec (one int64) their number, which may exceed max_fec_packets.  fec_route; fec_seq = fec_seq_base[r] + the index of the group among the route's
+ * closed groups of this call; fec_frame the last position of the group in this call (the stamp turns it into the timestamp); fec_offset = q * fec_stride;
+ * fec_size = fec_header_room + 14 + plen; fec_flags (uint8, may be NULL); fec_mask (int32, the 16 mask bits as on the wire, may be NULL); next_fec_seq
+ * [n_routes] = fec_seq_base[r] + the route's closed groups, which may be the array fec_seq_base itself (in place, as next_seq of the egress), and route_stats_out [n_routes][4] = {groups closed, packets written, media packets protected by them, bytes of level-0 payload}, each may be NULL.
+ * An entry with mask 0 is LC3PLUS_FEC_PKT_EMPTY with size 0: it keeps its number and writes nothing, and the stamp refuses it as ST_RANGE.  An entry with
+ * fec_size > fec_stride or fec_offset + fec_size > fec_capacity carries LC3PLUS_EGR_PKT_OVERFLOW, keeps its number and writes nothing; an entry with
+ * q >= max_fec_packets keeps its number and writes nothing, not even its record.  An open group whose largest length exceeds acc_stride is dropped: its FILL
+ * keeps advancing, its mask becomes 0 and it closes as EMPTY (a group closed without a packet written: groups closed less packets written).
+ * Every other entry writes exactly fec_wire[fec_offset + fec_header_room, fec_offset + fec_size); fec_header_room >= 12.  No other byte of fec_wire is written;
+ * it may not overlap wire.  acc_out and state_out are written whole.  Of wire only aligned 32-bit words that hold a byte of a member packet are read.  The FEC
+ * list goes to the stamp as it stands - pkt_seq = fec_seq, pkt_frame = fec_frame, header_room = fec_header_room, payload_room 0, MARKER_NEVER, the caller's FEC
+ * SSRC and payload-type arrays - and then to either protect call with contexts of its own.
+ *   work : lc3plus_fec_work_bytes(n_routes, n_frames) bytes, 8-byte aligned; it holds the cell-to-entry map; its contents mean nothing before or after the call
+ * Refused calls queue nothing, checked in this order: a NULL batch, n_packets, pkt_route, pkt_frame, pkt_offset, pkt_size, wire, seq_base, group, fec_seq_base,
+ * fec_wire, n_fec, fec_route, fec_seq, fec_frame, fec_offset, fec_size or work (LC3_NULL_ERROR); then max_packets <= 0 or >= 2^31 - 1, wire_capacity < 0,
+ * payload_room < 0, header_room < 12 + payload_room; n_routes <= 0, n_frames <= 0 or n_routes * n_frames >= 2^31; some but not all of state_in, acc_in, state_out
+ * and acc_out; with them acc_stride <= 0 or no multiple of 16, a state_out range that intersects state_in's or an acc_out range that intersects acc_in's; fec_capacity < 0, fec_stride <= 0 or > 2^30,
+ * fec_header_room < 12 or > 2^20, max_fec_packets <= 0; an fec_wire range that intersects the wire range; a work that is not 8-byte aligned (LC3_ERROR).
+ *
+ * RECOVER.  For a decoder batch (a receiver).  Every pointer but `batch` is a device pointer.
+ *   ring, ring_capacity : the datagrams' bytes; recovered packets are written into it
+ *   dg_offsets (int64), dg_sizes [n_items] : the datagrams, with the plain sizes after unprotect
+ *   stream, seq [n_items] : the media parse's; stream -1 means not a usable media packet
+ *   fec_stream, fec_offsets (int64), fec_num_bytes [n_fec] : the FEC parse's items; the payload there is the FEC header.  These may be the same datagram list
+ *                         parsed with the FEC type table
+ *   window              : a power of two in [64, 65536];   ssrc [n_streams] : the SSRC written into recovered headers
+ *   rec_offset, rec_stride : FEC item f owns ring[rec_offset + f * rec_stride .. + rec_stride); the caller keeps that region of the ring free
+ *   rec_dg_offsets (int64), rec_dg_sizes, rec_seq [n_fec]; status (uint8) [n_fec] and stats [LC3PLUS_FEC_STATS_WORDS], each may be NULL
+ *   work                : lc3plus_fec_recover_work_bytes(n_streams, window) bytes, 8-byte aligned
+ * THE LOOKUP.  A table [n_streams][window] in the workspace holds, at seq & (window - 1), the lowest item index of the stream with that residue.  A wanted packet
+ * is present where the table's item has exactly that stream and that sequence number (and its datagram lies in the ring with at least 12 bytes); otherwise it
+ * is missing.  So a collision can only turn a recovery into MISSING; it can never forge one.
+ * The status of FEC item f is the first check that fails:
+ *   1 DROPPED   stream outside [0, n_streams)
+ *   2 RANGE     the item lies outside ring (computed without overflow); such an item is never read
+ *   3 SHORT     fewer than 14 bytes, or fewer than 18 with the L bit
+ *   4 HEADER    E set, mask 0 or protection length 0
+ *   5 LENGTH    14 (18) + plen > size
+ *   6 COMPLETE  no protected packet is missing
+ *   7 MISSING   two or more are missing
+ *   8 PARTIAL   the recovered length exceeds plen
+ *   9 OVERFLOW  12 + recovered length > rec_stride, or the slot ends behind ring_capacity
+ *   0 RECOVERED
+ * Bytes behind level 0 (further levels) are ignored.  Both mask widths are handled, so foreign and interleaved senders work.  A RECOVERED item writes its slot:
+ * 0x80 | recovered low 6 bits, the recovered byte 1, the missing sequence number, the recovered timestamp, ssrc[s], then the recovered length's bytes of the XOR
+ * of the level-0 payload with bytes 12 ... of every present packet, each cut or padded to plen; rec_dg_offsets[f] is the slot, rec_dg_sizes[f] = 12 + length,
+ * rec_seq[f] the sequence number.  Every other item gets 0 in all three and writes no byte of the ring: the parse refuses a size-0 datagram as SHORT, so its
+ * item is dropped like any other refused one.  stats[k] counts the items of status k; the call zeroes it.  Two FEC items may recover the same packet: the ingest
+ * keeps one.
+ * Refused calls queue nothing, checked in this order: a NULL batch, ring, dg_offsets, dg_sizes, stream, seq, fec_stream, fec_offsets, fec_num_bytes, ssrc,
+ * rec_dg_offsets, rec_dg_sizes, rec_seq or work (LC3_NULL_ERROR); then n_items <= 0 or >= 2^29, ring_capacity < 0, n_fec <= 0 or >= 2^29; a window that is no
+ * power of two in [64, 65536]; rec_offset < 0, rec_stride < 12 or > 2^30, a work that is not 8-byte aligned (LC3_ERROR).
+ *
+ * The kernels live in liblc3plus_fec_hip.so, which this library loads from its own directory on the first FEC call: where that file is missing the FEC calls
+ * alone return LC3_ERROR and nothing else changes. */
+#define LC3PLUS_FEC_MAX_GROUP      16
+#define LC3PLUS_FEC_STATE_WORDS    8
+#define LC3PLUS_FEC_PKT_EMPTY      2
+#define LC3PLUS_FEC_ROUTE_STATS_WORDS 4
+#define LC3PLUS_FEC_RECOVERED      0
+#define LC3PLUS_FEC_DROPPED        1
+#define LC3PLUS_FEC_RANGE          2
+#define LC3PLUS_FEC_SHORT          3
+#define LC3PLUS_FEC_HEADER         4
+#define LC3PLUS_FEC_LENGTH         5
+#define LC3PLUS_FEC_COMPLETE       6
+#define LC3PLUS_FEC_MISSING        7
+#define LC3PLUS_FEC_PARTIAL        8
+#define LC3PLUS_FEC_OVERFLOW       9
+#define LC3PLUS_FEC_STATS_WORDS    16
+LC3_Error lc3plus_enc_batch_fec_encode(lc3plus_batch* batch,
+    int64_t max_packets, const int64_t* n_packets, const int32_t* pkt_route, const int32_t* pkt_frame, const int64_t* pkt_offset, const int32_t* pkt_size,
+    const uint8_t* pkt_status, const void* wire, int64_t wire_capacity, int header_room, int payload_room,
+    int n_routes, int n_frames, const int32_t* seq_base, const int32_t* route_stats, const int32_t* group, const uint8_t* flush, const int32_t* fec_seq_base,
+    const int32_t* state_in, const uint8_t* acc_in, int32_t* state_out, uint8_t* acc_out, int acc_stride,
+    void* fec_wire, int64_t fec_capacity, int64_t fec_stride, int fec_header_room,
+    int64_t max_fec_packets, int64_t* n_fec, int32_t* fec_route, int32_t* fec_seq, int32_t* fec_frame, int64_t* fec_offset, int32_t* fec_size, uint8_t* fec_flags,
+    int32_t* fec_mask, int32_t* next_fec_seq, int32_t* route_stats_out, void* work, void* hip_stream, int sync);
+LC3_Error lc3plus_dec_batch_fec_encode(lc3plus_dec_batch* batch,
+    int64_t max_packets, const int64_t* n_packets, const int32_t* pkt_route, const int32_t* pkt_frame, const int64_t* pkt_offset, const int32_t* pkt_size,
+    const uint8_t* pkt_status, const void* wire, int64_t wire_capacity, int header_room, int payload_room,
+    int n_routes, int n_frames, const int32_t* seq_base, const int32_t* route_stats, const int32_t* group, const uint8_t* flush, const int32_t* fec_seq_base,
+    const int32_t* state_in, const uint8_t* acc_in, int32_t* state_out, uint8_t* acc_out, int acc_stride,
+    void* fec_wire, int64_t fec_capacity, int64_t fec_stride, int fec_header_room,
+    int64_t max_fec_packets, int64_t* n_fec, int32_t* fec_route, int32_t* fec_seq, int32_t* fec_frame, int64_t* fec_offset, int32_t* fec_size, uint8_t* fec_flags,
+    int32_t* fec_mask, int32_t* next_fec_seq, int32_t* route_stats_out, void* work, void* hip_stream, int sync);
+/* The same rule on the host alone, no device: the same arrays in host memory (n_packets, n_fec and work too), no batch; the payloads are XORed byte by byte.
+ * hip_stream and sync are ignored.  The refusals of the calls above in their order, less that of the batch. */
+LC3_Error lc3plus_plan_fec_encode(
+    int64_t max_packets, const int64_t* n_packets, const int32_t* pkt_route, const int32_t* pkt_frame, const int64_t* pkt_offset, const int32_t* pkt_size,
+    const uint8_t* pkt_status, const void* wire, int64_t wire_capacity, int header_room, int payload_room,
+    int n_routes, int n_frames, const int32_t* seq_base, const int32_t* route_stats, const int32_t* group, const uint8_t* flush, const int32_t* fec_seq_base,
+    const int32_t* state_in, const uint8_t* acc_in, int32_t* state_out, uint8_t* acc_out, int acc_stride,
+    void* fec_wire, int64_t fec_capacity, int64_t fec_stride, int fec_header_room,
+    int64_t max_fec_packets, int64_t* n_fec, int32_t* fec_route, int32_t* fec_seq, int32_t* fec_frame, int64_t* fec_offset, int32_t* fec_size, uint8_t* fec_flags,
+    int32_t* fec_mask, int32_t* next_fec_seq, int32_t* route_stats_out, void* work, void* hip_stream, int sync);
+/* the bytes of `work` for an encode call and for a recover call; 0 for arguments the calls refuse */
+int64_t lc3plus_fec_work_bytes(int n_routes, int n_frames);
+int64_t lc3plus_fec_recover_work_bytes(int n_streams, int window);
+LC3_Error lc3plus_dec_batch_fec_recover(lc3plus_dec_batch* batch,
+    int64_t n_items, void* ring, int64_t ring_capacity, const int64_t* dg_offsets, const int32_t* dg_sizes, const int32_t* stream, const int32_t* seq,
+    int64_t n_fec, const int32_t* fec_stream, const int64_t* fec_offsets, const int32_t* fec_num_bytes, int window, const int32_t* ssrc,
+    int64_t rec_offset, int64_t rec_stride, int64_t* rec_dg_offsets, int32_t* rec_dg_sizes, int32_t* rec_seq, uint8_t* status, int32_t* stats, void* work,
+    void* hip_stream, int sync);
+/* The same rule on the host alone: the same arrays in host memory, n_streams given instead of a batch.  hip_stream and sync are ignored.  The refusals of the
+ * call above in their order, then n_streams <= 0 (LC3_ERROR). */
+LC3_Error lc3plus_plan_fec_recover(int n_streams,
+    int64_t n_items, void* ring, int64_t ring_capacity, const int64_t* dg_offsets, const int32_t* dg_sizes, const int32_t* stream, const int32_t* seq,
+    int64_t n_fec, const int32_t* fec_stream, const int64_t* fec_offsets, const int32_t* fec_num_bytes, int window, const int32_t* ssrc,
+    int64_t rec_offset, int64_t rec_stride, int64_t* rec_dg_offsets, int32_t* rec_dg_sizes, int32_t* rec_seq, uint8_t* status, int32_t* stats, void* work,
+    void* hip_stream, int sync);
+
 /* ---- Reception reports: per-stream RTP statistics and RR report blocks, on the device ----------------------------------------------------------------------
  * A receiver owes its senders RTCP reception reports (RFC 3550 6.4): per source the extended highest sequence number, the cumulative loss, the loss fraction
  * of the last interval and the interarrival jitter.  All four follow from what lc3plus_dec_batch_rtp_parse leaves in device memory - stream, seq, timestamp -
