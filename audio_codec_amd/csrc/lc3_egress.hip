@@ -1,5 +1,5 @@
 /* lc3_egress.hip -- the packet egress's library (liblc3plus_egress_hip.so): the gfx950 kernels of lc3_egress.inc and the host code that launches them, behind
- * the C ABI of lc3_egress_shim.h.  A sibling library (DESIGN.md "Sibling libraries"): lc3_host.c loads it on the first egress call and hands it the batch's device
+ * the C ABI of lc3_egress_shim.h.  A sibling library (DESIGN.md "Sibling libraries"): lc3_packet.c loads it on the first egress call and hands it the batch's device
  * and stream count.  It keeps no state but its launch counts and allocates nothing. */
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -1,7 +1,7 @@
 /* lc3_egress_shim.h -- packet egress (include/lc3plus_batch.h "Packet egress": lc3plus_enc_batch_egress, lc3plus_dec_batch_egress, lc3plus_plan_egress): what the
- * host C code (lc3_host.c) and the sibling library that holds the egress kernels (lc3_egress.hip -> liblc3plus_egress_hip.so) share.  The route rule, the cell
+ * host C code (lc3_packet.c) and the sibling library that holds the egress kernels (lc3_egress.hip -> liblc3plus_egress_hip.so) share.  The route rule, the cell
  * rule, the sequence numbers, the packet's advance in the wire buffer and the packet record are one text for the host function and the kernels; the
- * lc3egress_* functions are the sibling's whole C ABI.  lc3_host.c loads the sibling from its own directory on the first egress call; the code objects of the
+ * lc3egress_* functions are the sibling's whole C ABI.  lc3_packet.c loads the sibling from its own directory on the first egress call; the code objects of the
  * other libraries hold none of this. */
 #ifndef LC3_EGRESS_SHIM_H
 #define LC3_EGRESS_SHIM_H

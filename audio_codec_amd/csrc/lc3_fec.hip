@@ -1,5 +1,5 @@
 /* lc3_fec.hip -- the generic-FEC library (liblc3plus_fec_hip.so): the gfx950 kernels of lc3_fec.inc and the host code that launches them, behind the C ABI of
- * lc3_fec_shim.h.  A sibling library (DESIGN.md "Sibling libraries"): lc3_host.c loads it on the first FEC call and hands it the batch's device and stream.
+ * lc3_fec_shim.h.  A sibling library (DESIGN.md "Sibling libraries"): lc3_packet.c loads it on the first FEC call and hands it the batch's device and stream.
  * It keeps no state but its launch counts and allocates nothing. */
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -1,9 +1,9 @@
 /* lc3_fec_shim.h -- generic forward error correction, RFC 5109 (include/lc3plus_batch.h "Generic FEC": lc3plus_{enc,dec}_batch_fec_encode,
- * lc3plus_dec_batch_fec_recover, lc3plus_plan_fec_encode, lc3plus_plan_fec_recover): what the host C code (lc3_host.c) and the sibling library that holds the FEC
+ * lc3plus_dec_batch_fec_recover, lc3plus_plan_fec_encode, lc3plus_plan_fec_recover): what the host C code (lc3_packet.c) and the sibling library that holds the FEC
  * kernels (lc3_fec.hip -> liblc3plus_fec_hip.so) share.  The group rule, the member rule, the fold of a group's header fields, the FEC header's bytes, the state
  * handed to the next call, the lookup and the verdict of the recovery are one text for the host functions and the kernels; they differ only in how payload bytes
  * are fetched and XORed (plain bytes on the host, aligned 32-bit words realigned in registers on the device, the idiom of lc3_rtp_shim.h).  The copy layout is
- * the egress's (lc3_egress_shim.h), by inclusion.  The lc3fec_* functions are the sibling's whole C ABI.  lc3_host.c loads the sibling from its own directory on
+ * the egress's (lc3_egress_shim.h), by inclusion.  The lc3fec_* functions are the sibling's whole C ABI.  lc3_packet.c loads the sibling from its own directory on
  * the first FEC call; the code objects of the other libraries hold none of this. */
 #ifndef LC3_FEC_SHIM_H
 #define LC3_FEC_SHIM_H

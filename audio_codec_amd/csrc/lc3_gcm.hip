@@ -1,5 +1,5 @@
 /* lc3_gcm.hip -- the Secure RTP AES-GCM library (liblc3plus_gcm_hip.so), behind the C ABI of lc3_gcm_shim.h: the suites of RFC 7714 for the kernels and the
- * launch code of lc3_srtp_suite.inc.  A sibling library (DESIGN.md "Sibling libraries"): lc3_host.c loads it on the first GCM call and hands it the batch's
+ * launch code of lc3_srtp_suite.inc.  A sibling library (DESIGN.md "Sibling libraries"): lc3_packet.c loads it on the first GCM call and hands it the batch's
  * device.
  *
  * Te0 is computed into LDS by every workgroup; round keys, salt and round count are read from the route's or source's context where it lies, so that contexts of

@@ -1,10 +1,10 @@
 /* lc3_gcm_shim.h -- Secure RTP with the AEAD suites of RFC 7714, AEAD_AES_128_GCM and AEAD_AES_256_GCM (include/lc3plus_batch.h "Secure RTP, AEAD":
  * lc3plus_srtp_gcm_make_context, lc3plus_{enc,dec}_batch_srtp_gcm_protect, lc3plus_dec_batch_srtp_gcm_unprotect, lc3plus_plan_srtp_gcm_protect,
- * lc3plus_plan_srtp_gcm_unprotect): what the host C code (lc3_host.c) and the sibling library that holds the kernels (lc3_gcm.hip -> liblc3plus_gcm_hip.so)
+ * lc3plus_plan_srtp_gcm_unprotect): what the host C code (lc3_packet.c) and the sibling library that holds the kernels (lc3_gcm.hip -> liblc3plus_gcm_hip.so)
  * share.  Everything around the transform is lc3_srtp_shim.h's as it stands: the AES table, the fetch, align and sink helpers, the receive checks (lc3s_check
  * with a tag of 16 bytes), the index estimate, the window and state functions, the rollover counter of a sent packet, the workspace and the two call structs.
  * This file adds the key expansion for 16- and 32-byte keys, the AES block with the round count as an argument, GHASH, the GCM walk over a packet's words and
- * the two rules, one text for the host functions and the kernels.  The lc3gcm_* functions are the sibling's whole C ABI.  lc3_host.c loads the sibling from
+ * the two rules, one text for the host functions and the kernels.  The lc3gcm_* functions are the sibling's whole C ABI.  lc3_packet.c loads the sibling from
  * its own directory on the first GCM call; the seven other code objects hold none of this. */
 #ifndef LC3_GCM_SHIM_H
 #define LC3_GCM_SHIM_H

@@ -1,5 +1,5 @@
 /* lc3_ingest.hip -- the packet ingest's library (liblc3plus_ingest_hip.so): the gfx950 kernels of lc3_ingest.inc and the host code that launches them, behind the
- * C ABI of lc3_ingest_shim.h.  A sibling library (DESIGN.md "Sibling libraries"): lc3_host.c loads it on the first lc3plus_dec_batch_ingest call and hands it the
+ * C ABI of lc3_ingest_shim.h.  A sibling library (DESIGN.md "Sibling libraries"): lc3_packet.c loads it on the first lc3plus_dec_batch_ingest call and hands it the
  * batch's device, stream count and channel count.  It keeps no state but its launch counts and allocates nothing. */
 #include <hip/hip_runtime.h>
 #include <stdint.h>

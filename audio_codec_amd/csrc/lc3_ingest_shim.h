@@ -1,6 +1,6 @@
-/* lc3_ingest_shim.h -- packet ingest (include/lc3plus_batch.h "Packet ingest": lc3plus_dec_batch_ingest, lc3plus_plan_ingest): what the host C code (lc3_host.c)
+/* lc3_ingest_shim.h -- packet ingest (include/lc3plus_batch.h "Packet ingest": lc3plus_dec_batch_ingest, lc3plus_plan_ingest): what the host C code (lc3_packet.c)
  * and the sibling library that holds the ingest kernels (lc3_ingest.hip -> liblc3plus_ingest_hip.so) share.  The item rule, the cell key and the per-stream
- * count are one text for the host function and the kernels; the lc3ingest_* functions are the sibling's whole C ABI.  lc3_host.c loads the sibling from its own
+ * count are one text for the host function and the kernels; the lc3ingest_* functions are the sibling's whole C ABI.  lc3_packet.c loads the sibling from its own
  * directory on the first ingest call; neither the codec library's nor the probe library's code object holds any of this. */
 #ifndef LC3_INGEST_SHIM_H
 #define LC3_INGEST_SHIM_H

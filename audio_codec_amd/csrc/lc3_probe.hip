@@ -1,5 +1,5 @@
 /* lc3_probe.hip -- the frame probe's library (liblc3plus_probe_hip.so): the gfx950 kernels of lc3_probe.inc and the host code that launches them, behind the
- * C ABI of lc3_probe_shim.h.  A sibling library (DESIGN.md "Sibling libraries"): lc3_host.c loads it on the first lc3plus_dec_batch_probe call and hands it the
+ * C ABI of lc3_probe_shim.h.  A sibling library (DESIGN.md "Sibling libraries"): lc3_packet.c loads it on the first lc3plus_dec_batch_probe call and hands it the
  * batch's device, plan and per-size channel table.  It keeps no state but its launch counts. */
 #include <hip/hip_runtime.h>
 #include <stdint.h>

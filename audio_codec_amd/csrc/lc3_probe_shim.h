@@ -1,6 +1,6 @@
-/* lc3_probe_shim.h -- the frame probe (include/lc3plus_batch.h: lc3plus_dec_batch_probe, lc3plus_frame_info_side): what the host C code (lc3_host.c) and the
+/* lc3_probe_shim.h -- the frame probe (include/lc3plus_batch.h: lc3plus_dec_batch_probe, lc3plus_frame_info_side): what the host C code (lc3_packet.c; lc3_host.c for lc3plus_frame_info_side) and the
  * sibling library that holds the probe kernels (lc3_probe.hip -> liblc3plus_probe_hip.so) share.  The record layout, the item rule and the side-information parse
- * are one text for the host function and the kernels; the lc3probe_* functions are the sibling's whole C ABI.  lc3_host.c loads the sibling from its own
+ * are one text for the host function and the kernels; the lc3probe_* functions are the sibling's whole C ABI.  lc3_packet.c loads the sibling from its own
  * directory on the first probe call; the codec library's own code object holds none of this. */
 #ifndef LC3_PROBE_SHIM_H
 #define LC3_PROBE_SHIM_H

@@ -1,5 +1,5 @@
 /* lc3_red.hip -- the redundant-audio library (liblc3plus_red_hip.so): the gfx950 kernels of lc3_red.inc and the host code that launches them, behind the C ABI
- * of lc3_red_shim.h.  A sibling library (DESIGN.md "Sibling libraries"): lc3_host.c loads it on the first RED call and hands it the batch's device and stream
+ * of lc3_red_shim.h.  A sibling library (DESIGN.md "Sibling libraries"): lc3_packet.c loads it on the first RED call and hands it the batch's device and stream
  * count.  It keeps no state but its launch counts and allocates nothing. */
 #include <hip/hip_runtime.h>
 #include <stdint.h>

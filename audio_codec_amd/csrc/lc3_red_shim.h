@@ -1,9 +1,9 @@
 /* lc3_red_shim.h -- redundant audio, RFC 2198 (include/lc3plus_batch.h "Redundant audio": lc3plus_{enc,dec}_batch_red_pack, lc3plus_dec_batch_red_unpack,
- * lc3plus_plan_red_pack, lc3plus_plan_red_unpack): what the host C code (lc3_host.c) and the sibling library that holds the RED kernels (lc3_red.hip ->
+ * lc3plus_plan_red_pack, lc3plus_plan_red_unpack): what the host C code (lc3_packet.c) and the sibling library that holds the RED kernels (lc3_red.hip ->
  * liblc3plus_red_hip.so) share.  The packet rule, the block header's bytes, the tail rule, the workspace's layout and the unpack rule are one text for the host
  * functions and the kernels; they differ only in how a payload's bytes are fetched (plain bytes on the host, aligned 32-bit words realigned in registers on the
  * device, the idiom of lc3_rtp_shim.h).  The route rule, the cell rule and the copy rule are the egress's (lc3_egress_shim.h), by inclusion.  The lc3red_*
- * functions are the sibling's whole C ABI.  lc3_host.c loads the sibling from its own directory on the first RED call; the code objects of the other libraries
+ * functions are the sibling's whole C ABI.  lc3_packet.c loads the sibling from its own directory on the first RED call; the code objects of the other libraries
  * hold none of this. */
 #ifndef LC3_RED_SHIM_H
 #define LC3_RED_SHIM_H

@@ -1,5 +1,5 @@
 /* lc3_rtcp.hip -- the reception reports' library (liblc3plus_rtcp_hip.so): the gfx950 kernels of lc3_rtcp.inc and the host code that launches them, behind the
- * C ABI of lc3_rtcp_shim.h.  A sibling library (DESIGN.md "Sibling libraries"): lc3_host.c loads it on the first call and hands it the batch's device.  It keeps no
+ * C ABI of lc3_rtcp_shim.h.  A sibling library (DESIGN.md "Sibling libraries"): lc3_packet.c loads it on the first call and hands it the batch's device.  It keeps no
  * state but its launch counts and allocates nothing: all scratch lies in the caller's workspace. */
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -1,7 +1,7 @@
 /* lc3_rtcp_shim.h -- reception reports (include/lc3plus_batch.h "Reception reports": lc3plus_dec_batch_rtcp_stats, lc3plus_plan_rtcp_stats,
- * lc3plus_rtcp_workspace_bytes): what the host C code (lc3_host.c) and the sibling library that holds the kernels (lc3_rtcp.hip -> liblc3plus_rtcp_hip.so)
+ * lc3plus_rtcp_workspace_bytes): what the host C code (lc3_packet.c) and the sibling library that holds the kernels (lc3_rtcp.hip -> liblc3plus_rtcp_hip.so)
  * share.  The rule of one item (RFC 3550 A.1 without probation, A.8), the rule of one report (A.3), the block's words and the workspace's layout are one text
- * for the host function and the kernels.  The lc3rtcp_* functions are the sibling's whole C ABI.  lc3_host.c loads the sibling from its own directory on the
+ * for the host function and the kernels.  The lc3rtcp_* functions are the sibling's whole C ABI.  lc3_packet.c loads the sibling from its own directory on the
  * first call; the code objects of the other libraries hold none of this. */
 #ifndef LC3_RTCP_SHIM_H
 #define LC3_RTCP_SHIM_H

@@ -1,8 +1,8 @@
 /* lc3_rtp_shim.h -- RTP framing (include/lc3plus_batch.h "RTP framing": lc3plus_dec_batch_rtp_parse, lc3plus_{enc,dec}_batch_rtp_stamp, lc3plus_plan_rtp_parse,
- * lc3plus_plan_rtp_stamp): what the host C code (lc3_host.c) and the sibling library that holds the RTP kernels (lc3_rtp.hip -> liblc3plus_rtp_hip.so) share.
+ * lc3plus_plan_rtp_stamp): what the host C code (lc3_packet.c) and the sibling library that holds the RTP kernels (lc3_rtp.hip -> liblc3plus_rtp_hip.so) share.
  * The parse rule, the SSRC search, the stamp rule, the header's words and the per-route outputs are one text for the host functions and the kernels; they
  * differ only in how a datagram's bytes are fetched (lc3r_fetch12, lc3r_fetch_be16, lc3r_fetch_byte: plain bytes on the host, aligned 32-bit words realigned
- * in registers on the device).  The lc3rtp_* functions are the sibling's whole C ABI.  lc3_host.c loads the sibling from its own directory on the first RTP
+ * in registers on the device).  The lc3rtp_* functions are the sibling's whole C ABI.  lc3_packet.c loads the sibling from its own directory on the first RTP
  * call; the code objects of the codec library, the probe library, the ingest library and the egress library hold none of this. */
 #ifndef LC3_RTP_SHIM_H
 #define LC3_RTP_SHIM_H

@@ -1,5 +1,5 @@
 /* lc3_srtp.hip -- the Secure RTP library (liblc3plus_srtp_hip.so), behind the C ABI of lc3_srtp_shim.h: the suite of RFC 3711, AES-CM with HMAC-SHA1, for the
- * kernels and the launch code of lc3_srtp_suite.inc.  A sibling library (DESIGN.md "Sibling libraries"): lc3_host.c loads it on the first call and hands it the
+ * kernels and the launch code of lc3_srtp_suite.inc.  A sibling library (DESIGN.md "Sibling libraries"): lc3_packet.c loads it on the first call and hands it the
  * batch's device.
  *
  * SHA-1 takes sixteen words a compression, its 80 rounds unrolled over a schedule in registers.  The AES table is computed into LDS by the first 256 lanes of

@@ -1,9 +1,9 @@
 /* lc3_srtp_shim.h -- Secure RTP (include/lc3plus_batch.h "Secure RTP": lc3plus_srtp_make_context, lc3plus_{enc,dec}_batch_srtp_protect,
- * lc3plus_dec_batch_srtp_unprotect, lc3plus_plan_srtp_protect, lc3plus_plan_srtp_unprotect): what the host C code (lc3_host.c) and the sibling library that
+ * lc3plus_dec_batch_srtp_unprotect, lc3plus_plan_srtp_protect, lc3plus_plan_srtp_unprotect): what the host C code (lc3_packet.c) and the sibling library that
  * holds the kernels (lc3_srtp.hip -> liblc3plus_srtp_hip.so) share.  AES-128 (key expansion, block encryption, the tables), the SHA-1 compression, the walk over
  * a packet's words that encrypts, hashes and stores, the protect rule, the receive checks, the index estimate and the window are one text for the host functions
  * and the kernels; they differ only in how a packet's bytes are fetched and stored (plain bytes on the host; aligned 32-bit words realigned in registers on the
- * device, whole-word stores where all four bytes are the packet's own).  The lc3srtp_* functions are the sibling's whole C ABI.  lc3_host.c loads the sibling
+ * device, whole-word stores where all four bytes are the packet's own).  The lc3srtp_* functions are the sibling's whole C ABI.  lc3_packet.c loads the sibling
  * from its own directory on the first SRTP call; the six other code objects hold none of this. */
 #ifndef LC3_SRTP_SHIM_H
 #define LC3_SRTP_SHIM_H

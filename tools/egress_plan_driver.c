@@ -1,4 +1,4 @@
-/* egress_plan_driver.c -- lc3plus_plan_egress and the refusals of the egress calls in a program of its own, built with lc3_host.c and tools/stub_shim.c under
+/* egress_plan_driver.c -- lc3plus_plan_egress and the refusals of the egress calls in a program of its own, built with lc3_host.c, lc3_packet.c and tools/stub_shim.c under
  * AddressSanitizer + UndefinedBehaviorSanitizer (make -C audio_codec_amd/csrc egress_driver; tests/test_egress_cpu.py runs it as a child process).  Every array
  * is a heap block of exactly the size the header names, so a read or write one element too far ends the program.
  *

@@ -1,4 +1,4 @@
-/* fec_plan_driver.c -- lc3plus_plan_fec_encode, lc3plus_plan_fec_recover and the refusals of the FEC calls in a program of its own, built with lc3_host.c and
+/* fec_plan_driver.c -- lc3plus_plan_fec_encode, lc3plus_plan_fec_recover and the refusals of the FEC calls in a program of its own, built with lc3_host.c, lc3_packet.c and
  * tools/stub_shim.c under AddressSanitizer + UndefinedBehaviorSanitizer (make -C audio_codec_amd/csrc fec_driver; tests/test_fec_cpu.py runs it as a child
  * process).  Every array is a heap block of exactly the size the header names - the wire buffer, the accumulators, the FEC buffer, the ring and the workspace too
  * - so a read or write one element too far ends the program.

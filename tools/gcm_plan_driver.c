@@ -1,5 +1,5 @@
 /* gcm_plan_driver.c -- lc3plus_srtp_gcm_make_context, lc3plus_plan_srtp_gcm_protect, lc3plus_plan_srtp_gcm_unprotect and the refusals of the AES-GCM SRTP calls
- * in a program of its own, built with lc3_host.c and tools/stub_shim.c under AddressSanitizer + UndefinedBehaviorSanitizer (make -C audio_codec_amd/csrc
+ * in a program of its own, built with lc3_host.c, lc3_packet.c and tools/stub_shim.c under AddressSanitizer + UndefinedBehaviorSanitizer (make -C audio_codec_amd/csrc
  * gcm_driver; tests/test_gcm_cpu.py runs it as a child process with nothing preloaded).  Every array is a heap block of exactly the size the header names, and
  * the wire buffer, the destination and the ring are blocks of exactly their capacities, so a read or write one byte too far ends the program.
  *

@@ -1,4 +1,4 @@
-/* red_plan_driver.c -- lc3plus_plan_red_pack, lc3plus_plan_red_unpack and the refusals of the RED calls in a program of its own, built with lc3_host.c and
+/* red_plan_driver.c -- lc3plus_plan_red_pack, lc3plus_plan_red_unpack and the refusals of the RED calls in a program of its own, built with lc3_host.c, lc3_packet.c and
  * tools/stub_shim.c under AddressSanitizer + UndefinedBehaviorSanitizer (make -C audio_codec_amd/csrc red_driver; tests/test_red_cpu.py runs it as a child
  * process).  Every array is a heap block of exactly the size the header names - the frames, the tails, the ring and the wire buffer too - so a read or write one
  * element too far ends the program.

@@ -1,5 +1,5 @@
 /* rtcp_plan_driver.c -- lc3plus_plan_rtcp_stats, lc3plus_rtcp_workspace_bytes and the refusals of lc3plus_dec_batch_rtcp_stats in a program of its own, built
- * with lc3_host.c and tools/stub_shim.c under AddressSanitizer + UndefinedBehaviorSanitizer (make -C audio_codec_amd/csrc rtcp_driver; tests/test_rtcp_cpu.py
+ * with lc3_host.c, lc3_packet.c and tools/stub_shim.c under AddressSanitizer + UndefinedBehaviorSanitizer (make -C audio_codec_amd/csrc rtcp_driver; tests/test_rtcp_cpu.py
  * runs it as a child process).  Every array is a heap block of exactly the size the header names, so a read or write one element too far ends the program.
  *
  *   rtcp_plan_driver stats SEED N S REPORT INPLACE

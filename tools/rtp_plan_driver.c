@@ -1,5 +1,5 @@
 /* rtp_plan_driver.c -- lc3plus_plan_rtp_parse, lc3plus_plan_rtp_stamp, lc3plus_rtp_sort_ssrc and the refusals of the RTP calls in a program of its own, built
- * with lc3_host.c and tools/stub_shim.c under AddressSanitizer + UndefinedBehaviorSanitizer (make -C audio_codec_amd/csrc rtp_driver; tests/test_rtp_cpu.py runs
+ * with lc3_host.c, lc3_packet.c and tools/stub_shim.c under AddressSanitizer + UndefinedBehaviorSanitizer (make -C audio_codec_amd/csrc rtp_driver; tests/test_rtp_cpu.py runs
  * it as a child process).  Every array is a heap block of exactly the size the header names - the ring and the wire buffer too - so a read or write one element
  * too far ends the program.
  *

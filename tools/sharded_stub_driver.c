@@ -1,4 +1,4 @@
-/* sharded_stub_driver.c -- the threads of the sharded batches under ThreadSanitizer, without a GPU (linked with lc3_host.c and tools/stub_shim.c:
+/* sharded_stub_driver.c -- the threads of the sharded batches under ThreadSanitizer, without a GPU (linked with lc3_host.c, lc3_packet.c and tools/stub_shim.c:
  * csrc/Makefile, target stub).  One sharded encoder and one sharded decoder of 3 shards, 200 calls each from the main thread, then destroy; then a second
  * pair, the encoder driven from one application thread and the decoder from another at the same time.  Exit status 0 and no report: the hand-over between
  * the calling thread and the workers is ordered. */

@@ -1,6 +1,6 @@
 /* stub_shim.c -- every lc3hip_* symbol of audio_codec_amd/csrc/lc3_shim.h as a function that touches no GPU.
  *
- * Linked with lc3_host.c in place of lc3_runtime.hip and the kernels (csrc/Makefile, target stub), it lets the host logic - which pointer, which slice of
+ * Linked with lc3_host.c and lc3_packet.c in place of lc3_runtime.hip and the kernels (csrc/Makefile, target stub), it lets the host logic - which pointer, which slice of
  * which array, which result, which thread - be tested on a machine without a device: every create succeeds, every call returns success and appends one
  * record to a log that lc3stub_log() returns; lc3stub_fail_ctx() makes the encode / decode / state calls of one context fail.  Contexts are numbered in
  * the order they are created, from 0 after lc3stub_reset().  Never part of the product library. */
