@@ -12,7 +12,7 @@ import numpy as np
 import pytest
 
 import audio_codec_amd
-from audio_codec_amd import api
+from audio_codec_amd import api, packet
 import rtcp_ref as ref
 
 NEW = ["lc3plus_dec_batch_rtcp_stats", "lc3plus_plan_rtcp_stats", "lc3plus_rtcp_workspace_bytes"]
@@ -195,12 +195,12 @@ def test_in_place_state():
     L = audio_codec_amd.load_library()
     c = SETS["traffic_5x40"]
     want = plan(c)
-    ins, outs = api._rtcp_arrays(c["stream"], c["seq"], c["timestamp"], c["arrival"], c["state"], True, c["ssrc"], c["lsr"], c["dlsr"], ())
-    state = ins[4].copy()
+    a = packet._rtcp_arrays(c["stream"], c["seq"], c["timestamp"], c["arrival"], c["state"], True, c["ssrc"], c["lsr"], c["dlsr"], ())
+    state = a["state_in"].copy()
     ptr = lambda a: a.ctypes.data if a is not None else None
-    rc = L.lc3plus_plan_rtcp_stats(ins[0].size, ptr(ins[0]), ptr(ins[1]), ptr(ins[2]), ptr(ins[3]), state.shape[0], ptr(state), ptr(state), 1, ptr(ins[5]), ptr(ins[6]),
-                                   ptr(ins[7]), ptr(outs[1]), None, None, None)
-    assert rc == 0 and np.array_equal(state, want["state"]) and np.array_equal(outs[1], want["blocks"])
+    rc = L.lc3plus_plan_rtcp_stats(a["stream"].size, ptr(a["stream"]), ptr(a["seq"]), ptr(a["timestamp"]), ptr(a["arrival"]), state.shape[0], ptr(state), ptr(state), 1,
+                                   ptr(a["ssrc"]), ptr(a["lsr"]), ptr(a["dlsr"]), ptr(a["blocks"]), None, None, None)
+    assert rc == 0 and np.array_equal(state, want["state"]) and np.array_equal(a["blocks"], want["blocks"])
 
 
 @pytest.mark.parametrize("seed,S,T", [(11, 6, 50), (12, 40, 20), (13, 3, 300)])
