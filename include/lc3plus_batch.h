@@ -994,7 +994,7 @@ LC3_Error lc3plus_plan_red_unpack(int n_streams, int64_t n_items,
  *   sender    ... egress (wire) [-> red_pack] -> stamp -> fec_encode -> stamp (FEC list) -> protect (media), protect (FEC)
  *   receiver  unprotect -> parse (media types) + parse (FEC types) -> fec_recover -> parse (recovered) [-> red_unpack] -> probe -> ingest -> decode_packed
  * all on one HIP stream with no host wait.  NOT HANDLED: interleaved groups on the sender (a group is k consecutive sequence numbers), protection levels above
- * 0, iterative recovery (the pass is single: a packet recovered by one FEC item is not fed to another), RFC 8627 (FlexFEC), FEC carried inside RED.
+ * 0, iterative recovery (the pass is single: a packet recovered by one FEC item is not fed to another), RFC 8627 (FlexFEC), FEC carried inside RED, recovery across calls (the recover call knows the items of its own call alone: of a group that spans calls it rebuilds a packet only where the caller keeps the earlier members' datagrams in the ring and their entries in the lists it passes; otherwise those members count as missing).
  *
  * THE WIRE FORMAT.  An FEC packet is an RTP packet; its twelve header bytes are the stamp's work.  Its payload is a 10-byte FEC header, one level header and the
  * level-0 payload, all fields big-endian:
