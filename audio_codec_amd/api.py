@@ -57,6 +57,7 @@ EXPORTS = [
     "lc3plus_plan_red_unpack",
     "lc3plus_enc_batch_fec_encode", "lc3plus_dec_batch_fec_encode", "lc3plus_plan_fec_encode", "lc3plus_fec_work_bytes", "lc3plus_fec_recover_work_bytes",
     "lc3plus_dec_batch_fec_recover", "lc3plus_plan_fec_recover",
+    "lc3plus_dec_batch_fec_repair", "lc3plus_plan_fec_repair", "lc3plus_fec_repair_work_bytes",
     "lc3plus_shard_block",
     "lc3plus_enc_sharded_create", "lc3plus_enc_sharded_destroy", "lc3plus_enc_sharded_shards", "lc3plus_enc_sharded_shard", "lc3plus_enc_sharded_device",
     "lc3plus_enc_sharded_owner", "lc3plus_enc_sharded_input_samples", "lc3plus_enc_sharded_num_bytes", "lc3plus_enc_sharded_stride",

@@ -30,12 +30,13 @@
 #include "lc3_gcm_shim.h"
 #include "lc3_red_shim.h"
 #include "lc3_fec_shim.h"
+#include "lc3_repair_shim.h"
 #include "lc3_batch_view.h"
 
 #define IMIN(a, b) ((a) < (b) ? (a) : (b))
 
 /* ---- the sibling libraries (DESIGN.md "Sibling libraries"): the kernels of every call below lie in a library of their own beside this one ---- */
-enum { SIB_PROBE, SIB_INGEST, SIB_EGRESS, SIB_RTP, SIB_RTCP, SIB_SRTP, SIB_GCM, SIB_RED, SIB_FEC, SIB_COUNT };
+enum { SIB_PROBE, SIB_INGEST, SIB_EGRESS, SIB_RTP, SIB_RTCP, SIB_SRTP, SIB_GCM, SIB_RED, SIB_FEC, SIB_REPAIR, SIB_COUNT };
 /* a row: the file, its one or two entry points, and where they go.  fn holds either all of them or none */
 static struct { const char* file; const char* sym[2]; int tried; void* fn[2]; } siblings[SIB_COUNT] = {
     [SIB_PROBE] = {"liblc3plus_probe_hip.so", {"lc3probe_run", NULL}, 0, {NULL, NULL}},
@@ -47,6 +48,7 @@ static struct { const char* file; const char* sym[2]; int tried; void* fn[2]; } 
     [SIB_GCM] = {"liblc3plus_gcm_hip.so", {"lc3gcm_protect_run", "lc3gcm_unprotect_run"}, 0, {NULL, NULL}},
     [SIB_RED] = {"liblc3plus_red_hip.so", {"lc3red_pack_run", "lc3red_unpack_run"}, 0, {NULL, NULL}},
     [SIB_FEC] = {"liblc3plus_fec_hip.so", {"lc3fec_encode_run", "lc3fec_recover_run"}, 0, {NULL, NULL}},
+    [SIB_REPAIR] = {"liblc3plus_repair_hip.so", {"lc3rep_repair_run", NULL}, 0, {NULL, NULL}},
 };
 static pthread_mutex_t sibling_mu = PTHREAD_MUTEX_INITIALIZER;
 /* The entry points of a sibling, or NULL where the library is missing or lacks one of them.  The file is looked for once per process, on the first call that needs
@@ -944,6 +946,152 @@ LC3_Error lc3plus_dec_batch_fec_recover(lc3plus_dec_batch* b, FEC_RECOVER_PARAMS
     memset(&q, 0, sizeof q);
     q.sync = sync; q.io = fec_recover_io(&a, v.n_streams); q.stats = stats; q.work = work;
     return SIBLING_RUN(lc3fec_recover_call, SIB_FEC, 1, v, hip_stream, &q);
+}
+/* ---- generic FEC, repair across calls (include/lc3plus_batch.h "Generic FEC", REPAIR; lc3_repair_shim.h) ---- */
+/* what a repair call takes behind its batch, in the header's order */
+typedef struct {
+    int64_t n_items; void* ring; int64_t ring_capacity; const int64_t* dg_offsets; const int32_t* dg_sizes; const int32_t* stream; const int32_t* seq;
+    int64_t n_fec; const int32_t* fec_stream; const int64_t* fec_offsets; const int32_t* fec_num_bytes; const int32_t* fec_seq; const int32_t* ssrc;
+    int64_t med_offset; int med_slots; int med_stride; int32_t* med_seq; int32_t* med_size;
+    void* fec_store; int fec_slots; int fec_stride; int32_t* cell_seq; int32_t* cell_size; uint8_t* cell_status; int32_t* state; int passes;
+    int64_t* rec_dg_offsets; int32_t* rec_dg_sizes; int32_t* rec_seq; uint8_t* item_status; uint8_t* fec_status; int32_t* stats; void* work;
+} fec_repair_args;
+static int pow2_in(int v, int lo, int hi) { return v >= lo && v <= hi && !(v & (v - 1)); }
+static LC3_Error fec_repair_check(const fec_repair_args* a, int n_streams)
+{
+    if (!a->ring || !a->ssrc || !a->med_seq || !a->med_size || !a->fec_store || !a->cell_seq || !a->cell_size || !a->cell_status || !a->state || !a->rec_dg_offsets ||
+        !a->rec_dg_sizes || !a->rec_seq || !a->work)
+        return LC3_NULL_ERROR;
+    if (a->n_items > 0 && (!a->dg_offsets || !a->dg_sizes || !a->stream || !a->seq)) return LC3_NULL_ERROR;
+    if (a->n_fec > 0 && (!a->fec_stream || !a->fec_offsets || !a->fec_num_bytes || !a->fec_seq)) return LC3_NULL_ERROR;
+    if (n_streams <= 0 || a->n_items < 0 || a->n_items >= LC3R_MAX_ITEMS || a->ring_capacity < 0 || a->n_fec < 0 || a->n_fec >= LC3R_MAX_ITEMS) return LC3_ERROR;
+    if (a->med_offset < 0 || (a->med_offset & 15) || !pow2_in(a->med_slots, LC3REP_MIN_MED, LC3REP_MAX_MED) || a->med_stride < 16 || a->med_stride > LC3FEC_MAX_PKT ||
+        (a->med_stride & 15))
+        return LC3_ERROR;
+    if (!pow2_in(a->fec_slots, LC3REP_MIN_CELLS, LC3REP_MAX_CELLS) || a->fec_stride < 16 || a->fec_stride > LC3FEC_MAX_PKT || (a->fec_stride & 15)) return LC3_ERROR;
+    if (a->passes < 1 || a->passes > LC3REP_MAX_PASSES) return LC3_ERROR;
+    const long long nh = (long long)n_streams * a->med_slots, np = (long long)n_streams * a->fec_slots;
+    if (nh >= LC3FEC_MAX_PACKETS || np >= LC3FEC_MAX_PACKETS) return LC3_ERROR;
+    if (a->med_offset > a->ring_capacity - nh * a->med_stride) return LC3_ERROR;                  /* the history ends behind the ring */
+    /* fec_store, the history's range of the ring and the metadata arrays lie apart */
+    const uintptr_t at[8] = {(uintptr_t)a->ring + (uintptr_t)a->med_offset, (uintptr_t)a->fec_store, (uintptr_t)a->med_seq, (uintptr_t)a->med_size, (uintptr_t)a->cell_seq,
+                             (uintptr_t)a->cell_size, (uintptr_t)a->cell_status, (uintptr_t)a->state};
+    const uintptr_t len[8] = {(uintptr_t)(nh * a->med_stride), (uintptr_t)(np * a->fec_stride), 4 * (uintptr_t)nh, 4 * (uintptr_t)nh, 4 * (uintptr_t)np, 4 * (uintptr_t)np,
+                              (uintptr_t)np, sizeof(int32_t) * LC3REP_STATE_WORDS * (uintptr_t)n_streams};
+    for (int i = 0; i < 8; i++)
+        for (int j = i + 1; j < 8; j++)
+            if (at[i] < at[j] + len[j] && at[j] < at[i] + len[i]) return LC3_ERROR;
+    if ((uintptr_t)a->work & 7) return LC3_ERROR;
+    return LC3_OK;
+}
+static lc3rep_io fec_repair_io(const fec_repair_args* a, int n_streams)
+{
+    const lc3rep_io q = {(uint8_t*)a->ring, (const long long*)a->dg_offsets, a->dg_sizes, a->stream, a->seq, a->fec_stream, (const long long*)a->fec_offsets,
+                         a->fec_num_bytes, a->fec_seq, a->ssrc, a->med_seq, a->med_size, (uint8_t*)a->fec_store, a->cell_seq, a->cell_size, a->cell_status, a->state,
+                         (long long*)a->rec_dg_offsets, a->rec_dg_sizes, a->rec_seq, a->item_status, a->fec_status, a->stats, (long long)a->ring_capacity,
+                         a->n_items > 0 ? (long long)a->n_items : 0, a->n_fec > 0 ? (long long)a->n_fec : 0, (long long)a->med_offset, n_streams, a->med_slots,
+                         a->med_stride, a->fec_slots, a->fec_stride, a->passes};
+    return q;
+}
+#define FEC_REPAIR_PARAMS \
+    int64_t n_items, void* ring, int64_t ring_capacity, const int64_t* dg_offsets, const int32_t* dg_sizes, const int32_t* stream, const int32_t* seq, \
+    int64_t n_fec, const int32_t* fec_stream, const int64_t* fec_offsets, const int32_t* fec_num_bytes, const int32_t* fec_seq, const int32_t* ssrc, \
+    int64_t med_offset, int med_slots, int med_stride, int32_t* med_seq, int32_t* med_size, \
+    void* fec_store, int fec_slots, int fec_stride, int32_t* cell_seq, int32_t* cell_size, uint8_t* cell_status, int32_t* state, int passes, \
+    int64_t* rec_dg_offsets, int32_t* rec_dg_sizes, int32_t* rec_seq, uint8_t* item_status, uint8_t* fec_status, int32_t* stats, void* work
+#define FEC_REPAIR_ARGS \
+    {n_items, ring, ring_capacity, dg_offsets, dg_sizes, stream, seq, n_fec, fec_stream, fec_offsets, fec_num_bytes, fec_seq, ssrc, med_offset, med_slots, med_stride, \
+     med_seq, med_size, fec_store, fec_slots, fec_stride, cell_seq, cell_size, cell_status, state, passes, rec_dg_offsets, rec_dg_sizes, rec_seq, item_status, fec_status, \
+     stats, work}
+int64_t lc3plus_fec_repair_work_bytes(int n_streams, int med_slots, int fec_slots)
+{
+    if (n_streams <= 0 || !pow2_in(med_slots, LC3REP_MIN_MED, LC3REP_MAX_MED) || !pow2_in(fec_slots, LC3REP_MIN_CELLS, LC3REP_MAX_CELLS)) return 0;
+    if ((long long)n_streams * med_slots >= LC3FEC_MAX_PACKETS || (long long)n_streams * fec_slots >= LC3FEC_MAX_PACKETS) return 0;
+    return lc3rep_work_bytes(n_streams, med_slots, fec_slots);
+}
+/* the rule on the host: the kernels' steps (lc3_repair.inc) one after the other, on the text they run and over the same workspace */
+LC3_Error lc3plus_plan_fec_repair(int n_streams, FEC_REPAIR_PARAMS, void* hip_stream, int sync)
+{
+    (void)hip_stream; (void)sync;
+    const fec_repair_args a = FEC_REPAIR_ARGS;
+    const LC3_Error e = fec_repair_check(&a, n_streams > 0 ? n_streams : 0);
+    if (e) return e;
+    const lc3rep_io q = fec_repair_io(&a, n_streams);
+    const lc3rep_work w = lc3rep_work_of(work, n_streams, med_slots, fec_slots);
+    const long long nh = (long long)n_streams * med_slots, np = (long long)n_streams * fec_slots, items = q.n_items + q.n_fec;
+    /* fill */
+    for (long long i = 0; i < 2LL * n_streams; i++) { w.first[i] = LC3FEC_NO_ENTRY; w.dist[i] = 0; }
+    for (long long i = 0; i < nh; i++) w.mclaim[i] = w.tclaim[i] = LC3FEC_NO_ENTRY;
+    for (long long i = 0; i < np; i++) { w.fclaim[i] = LC3FEC_NO_ENTRY; rec_dg_offsets[i] = 0; rec_dg_sizes[i] = 0; rec_seq[i] = 0; }
+    for (int i = 0; i < LC3REP_PROG_WORDS; i++) w.prog[i] = i == 0;
+    if (stats) memset(stats, 0, sizeof(int32_t) * LC3FEC_STATS_WORDS);
+    for (long long i = 0; i < items; i++) lc3rep_first_step(&q, &w, i);
+    for (long long i = 0; i < items; i++) lc3rep_dist_step(&q, &w, i);
+    for (long long i = 0; i < items; i++) lc3rep_claim_step(&q, &w, i);
+    for (long long i = 0; i < nh; i++) lc3rep_settle_step(&q, &w, LC3REP_MED, i);
+    for (long long i = 0; i < np; i++) lc3rep_settle_step(&q, &w, LC3REP_FEC, i);
+    /* copy */
+    for (long long i = 0; i < items; i++) {
+        const lc3rep_item it = lc3rep_item_of(&q, i);
+        long long slot = 0;
+        const int st = lc3rep_place_step(&q, &w, &it, &slot);
+        if (it.kind == LC3REP_MED && item_status) item_status[i] = (uint8_t)st;
+        if (st != LC3REP_STORED) continue;
+        memcpy(it.kind == LC3REP_FEC ? q.fec_store + lc3rep_cell_at(&q, slot) : q.ring + lc3rep_slot_at(&q, slot), q.ring + it.off, (size_t)it.size);
+    }
+    for (int p = 1; p <= passes; p++) {
+        if (!w.prog[p - 1]) break;                                    /* a pass behind one that rebuilt nothing changes nothing */
+        for (long long c = 0; c < np; c++) {
+            const int st = lc3rep_verdict_step(&q, &w, p, c);
+            if (stats && st > 0 && st != LC3FEC_MISSING && lc3rep_carried(&w, c)) stats[st]++;
+        }
+        if (!w.prog[p]) continue;
+        for (long long c = 0; c < np; c++) {
+            lc3fec_item h;
+            long long k = 0;
+            uint32_t sn = 0;
+            const int st = lc3rep_rebuild_claim(&q, &w, c, &h, &k, &sn);
+            if (st >= 0 && stats && lc3rep_carried(&w, c)) stats[st]++;
+            if (st != LC3FEC_RECOVERED) continue;
+            const int s = (int)(c / fec_slots);
+            uint32_t hdr = 0, ts = 0, len = 0;
+            for (int i = 0; i < LC3FEC_MAX_BITS; i++) {
+                const uint32_t mine = (h.sn + (uint32_t)i) & 0xFFFFu;
+                uint32_t mh, mt, ml;
+                if (!(h.mask >> (LC3FEC_MAX_BITS - 1 - i) & 1) || mine == sn) continue;
+                lc3rep_member_fields(&q, (long long)s * med_slots + (mine & (uint32_t)(med_slots - 1)), &mh, &mt, &ml);
+                hdr ^= mh; ts ^= mt; len ^= ml;
+            }
+            const int rl = lc3rep_rebuild_header(&q, c, &h, k, sn, hdr, ts, len);
+            uint8_t* dst = q.ring + lc3rep_slot_at(&q, k) + LC3R_FIXED;
+            memcpy(dst, q.fec_store + lc3rep_cell_at(&q, c) + h.hl, (size_t)rl);
+            for (int i = 0; i < LC3FEC_MAX_BITS; i++) {
+                const uint32_t mine = (h.sn + (uint32_t)i) & 0xFFFFu;
+                if (!(h.mask >> (LC3FEC_MAX_BITS - 1 - i) & 1) || mine == sn) continue;
+                const long long m = (long long)s * med_slots + (mine & (uint32_t)(med_slots - 1));
+                fec_xor(dst, q.ring + lc3rep_slot_at(&q, m) + LC3R_FIXED, IMIN(med_size[m] - LC3R_FIXED, rl));
+            }
+        }
+    }
+    /* report */
+    for (long long f = 0; f < q.n_fec; f++) {
+        const int st = lc3rep_report_step(&q, &w, f);
+        if (stats) stats[st]++;
+    }
+    for (int s = 0; s < n_streams; s++) lc3rep_state_step(&q, &w, s);
+    return LC3_OK;
+}
+LC3_Error lc3plus_dec_batch_fec_repair(lc3plus_dec_batch* b, FEC_REPAIR_PARAMS, void* hip_stream, int sync)
+{
+    if (!b) return LC3_NULL_ERROR;
+    const fec_repair_args a = FEC_REPAIR_ARGS;
+    const lc3host_view v = lc3host_dec_view(b);
+    const LC3_Error e = fec_repair_check(&a, v.n_streams);
+    if (e) return e;
+    lc3rep_call q;
+    memset(&q, 0, sizeof q);
+    q.sync = sync; q.io = fec_repair_io(&a, v.n_streams); q.work = work;
+    return SIBLING_RUN(lc3rep_call, SIB_REPAIR, 0, v, hip_stream, &q);
 }
 /* ---- reception reports (include/lc3plus_batch.h "Reception reports"; lc3_rtcp_shim.h) ---- */
 /* what a stats call takes behind its batch, in the header's order */

@@ -88,6 +88,11 @@ FEC_ROUTE_STATS_WORDS = 4
 FEC_PKT_EMPTY = 2
 (FEC_RECOVERED, FEC_DROPPED, FEC_RANGE, FEC_SHORT, FEC_HEADER, FEC_LENGTH, FEC_COMPLETE, FEC_MISSING, FEC_PARTIAL, FEC_OVERFLOW) = range(10)
 FEC_STATS_WORDS = 16
+# ... and repair across calls (DecBatch.fec_repair, plan_fec_repair; "Generic FEC", REPAIR): the words of a stream's state, a stored media item's status, the statuses
+# behind FEC_OVERFLOW
+FEC_REPAIR_STATE_WORDS = 4
+FEC_STORED = 0
+(FEC_STALE, FEC_DUPLICATE, FEC_OVERSIZE, FEC_EXPIRED, FEC_TWIN) = range(10, 15)
 
 # the outputs of each call as the keys of the dict its plan and its convenience return, in the header's order, and those of them a caller may leave out
 ING_OPTIONAL = ("next_base", "stats", "item_status")
@@ -111,6 +116,9 @@ FEC_ENCODE_OUTPUTS = ("state", "acc", "fec_wire", "n_fec", "fec_route", "fec_seq
                       "route_stats")
 FEC_RECOVER_OPTIONAL = ("status", "stats")
 FEC_RECOVER_OUTPUTS = ("ring", "rec_dg_offsets", "rec_dg_sizes", "rec_seq", "status", "stats")
+FEC_REPAIR_OPTIONAL = ("item_status", "fec_status", "stats")
+FEC_REPAIR_STORES = ("ring", "med_seq", "med_size", "fec_store", "cell_seq", "cell_size", "cell_status", "state")
+FEC_REPAIR_OUTPUTS = FEC_REPAIR_STORES + ("rec_dg_offsets", "rec_dg_sizes", "rec_seq", "item_status", "fec_status", "stats")
 # the input arrays of the two calls by the plans' argument names (nothing here reads them any more)
 RED_PACK_INPUTS = ("frames", "offsets", "num_bytes", "flags", "counts", "route_src", "n_packets", "pkt_route", "pkt_frame", "depth", "block_pt", "tail_bytes", "tail_sizes",
                    "wire")
@@ -160,6 +168,10 @@ _FEC_ENCODE = _params("int64 max_packets, ptr n_packets, ptr pkt_route, ptr pkt_
 _FEC_RECOVER = _params("int64 n_items, ptr ring, int64 ring_capacity, ptr dg_offsets, ptr dg_sizes, ptr stream, ptr seq, int64 n_fec, ptr fec_stream, ptr fec_offsets, "
                        "ptr fec_num_bytes, int window, ptr ssrc, int64 rec_offset, int64 rec_stride, ptr rec_dg_offsets, ptr rec_dg_sizes, ptr rec_seq, ptr status, "
                        "ptr stats, ptr work")
+_FEC_REPAIR = _params("int64 n_items, ptr ring, int64 ring_capacity, ptr dg_offsets, ptr dg_sizes, ptr stream, ptr seq, int64 n_fec, ptr fec_stream, ptr fec_offsets, "
+                      "ptr fec_num_bytes, ptr fec_seq, ptr ssrc, int64 med_offset, int med_slots, int med_stride, ptr med_seq, ptr med_size, ptr fec_store, int fec_slots, "
+                      "int fec_stride, ptr cell_seq, ptr cell_size, ptr cell_status, ptr state, int passes, ptr rec_dg_offsets, ptr rec_dg_sizes, ptr rec_seq, "
+                      "ptr item_status, ptr fec_status, ptr stats, ptr work")
 # ... what stands in front of it and behind it
 _BATCH, _STREAMS, _NOTHING = _params("ptr batch"), _params("int n_streams"), ()
 _QUEUED = _params("ptr hip_stream, int sync")
@@ -188,10 +200,11 @@ _family("red_pack", _RED_PACK, _STREAMS, _QUEUED)
 _family("red_unpack", _RED_UNPACK, _STREAMS, _QUEUED, kinds=("dec",))
 _family("fec_encode", _FEC_ENCODE, _NOTHING, _QUEUED)
 _family("fec_recover", _FEC_RECOVER, _STREAMS, _QUEUED, kinds=("dec",))
+_family("fec_repair", _FEC_REPAIR, _STREAMS, _QUEUED, kinds=("dec",))
 # the host-only helpers; those named *_bytes return an int64_t
 PARAMS.update({"lc3plus_" + name: _params(text) for name, text in (
     ("egress_work_bytes", "int n_routes, int n_frames"), ("red_work_bytes", "int64 max_packets"), ("fec_work_bytes", "int n_routes, int n_frames"),
-    ("fec_recover_work_bytes", "int n_streams, int window"), ("rtcp_workspace_bytes", "int64 n_items, int n_streams"),
+    ("fec_recover_work_bytes", "int n_streams, int window"), ("fec_repair_work_bytes", "int n_streams, int med_slots, int fec_slots"), ("rtcp_workspace_bytes", "int64 n_items, int n_streams"),
     ("srtp_workspace_bytes", "int64 n_items, int n_ssrc"), ("rtp_sort_ssrc", "int n, ptr ssrc_key, ptr ssrc_stream"),
     ("srtp_make_context", "ptr master_key, ptr master_salt, ptr ctx"), ("srtp_gcm_make_context", "ptr master_key, int key_bytes, ptr master_salt, ptr ctx"))})
 
@@ -760,6 +773,69 @@ def plan_fec_recover(n_streams, ring, dg_offsets, dg_sizes, stream, seq, fec_str
     return _plan("lc3plus_plan_fec_recover", v, FEC_RECOVER_OUTPUTS, n_streams=n_streams)
 
 
+def fec_repair_work_bytes(n_streams, med_slots, fec_slots):
+    """bytes of the workspace of a fec_repair call (lc3plus_fec_repair_work_bytes); 0 for arguments the call refuses"""
+    return int(_lib().lc3plus_fec_repair_work_bytes(int(n_streams), int(med_slots), int(fec_slots)))
+
+
+def fec_repair_stores(n_streams, ring, med_offset, med_slots=16, med_stride=None, fec_slots=4, fec_stride=None):
+    """The stores of a receiver that has received nothing, as plan_fec_repair and DecBatch.fec_repair take and return them: dict of ring (a copy), med_offset,
+    med_slots, med_stride, fec_slots, fec_stride and the zeroed med_seq, med_size [n_streams, H], fec_store [n_streams, P, fec_stride], cell_seq, cell_size,
+    cell_status [n_streams, P], state [n_streams, FEC_REPAIR_STATE_WORDS]"""
+    n, H, P = int(n_streams), int(med_slots), int(fec_slots)
+    return dict(ring=np.array(ring, dtype=np.uint8).reshape(-1), med_offset=int(med_offset), med_slots=H, med_stride=int(med_stride), fec_slots=P,
+                fec_stride=int(fec_stride), med_seq=np.zeros((n, H), np.int32), med_size=np.zeros((n, H), np.int32), fec_store=np.zeros((n, P, int(fec_stride)), np.uint8),
+                cell_seq=np.zeros((n, P), np.int32), cell_size=np.zeros((n, P), np.int32), cell_status=np.zeros((n, P), np.uint8),
+                state=np.zeros((n, FEC_REPAIR_STATE_WORDS), np.int32))
+
+
+def _fec_repair_arrays(n_streams, stores, dg_offsets, dg_sizes, stream, seq, fec_stream, fec_offsets, fec_num_bytes, fec_seq, ssrc, passes, ring_capacity, optional):
+    """the values of a repair call by header parameter name: the item arrays as the C calls take them (None for those of an empty list), copies of the stores,
+    which the call advances in place, the outputs and the workspace"""
+    n, H, P = int(n_streams), int(stores["med_slots"]), int(stores["fec_slots"])
+    stream = np.ascontiguousarray(stream, dtype=np.int32).reshape(-1)
+    m = stream.size
+    fec_stream = np.ascontiguousarray(fec_stream, dtype=np.int32).reshape(-1)
+    k = fec_stream.size
+    per = lambda a, dt, size, what: _shaped(np.ascontiguousarray(a, dtype=dt).reshape(-1), (size,), what) if size else None
+    media, fec = "the item arrays hold one entry per item", "the FEC item arrays hold one entry per FEC item"
+    ring = np.array(stores["ring"], dtype=np.uint8).reshape(-1)
+    v = dict(n_items=m, ring=ring, ring_capacity=ring.size if ring_capacity is None else ring_capacity, dg_offsets=per(dg_offsets, np.int64, m, media),
+             dg_sizes=per(dg_sizes, np.int32, m, media), stream=stream if m else None, seq=_shaped(_u32(seq), (m,), media) if m else None, n_fec=k,
+             fec_stream=fec_stream if k else None, fec_offsets=per(fec_offsets, np.int64, k, fec), fec_num_bytes=per(fec_num_bytes, np.int32, k, fec),
+             fec_seq=_shaped(_u32(fec_seq), (k,), fec) if k else None, ssrc=_shaped(_u32(ssrc), (n,), "ssrc holds one entry per stream"),
+             med_offset=stores["med_offset"], med_slots=H, med_stride=stores["med_stride"], fec_slots=P, fec_stride=stores["fec_stride"], passes=passes)
+    for name, dt, shape in (("med_seq", np.int32, (n, H)), ("med_size", np.int32, (n, H)), ("fec_store", np.uint8, (n, P, int(stores["fec_stride"]))),
+                            ("cell_seq", np.int32, (n, P)), ("cell_size", np.int32, (n, P)), ("cell_status", np.uint8, (n, P)),
+                            ("state", np.int32, (n, FEC_REPAIR_STATE_WORDS))):
+        v[name] = _shaped(np.array(stores[name], dtype=dt), shape, "%s must have shape %r" % (name, shape))
+    v.update(rec_dg_offsets=np.zeros(n * P, np.int64), rec_dg_sizes=np.zeros(n * P, np.int32), rec_seq=np.zeros(n * P, np.int32),
+             item_status=np.zeros(m, np.uint8) if "item_status" in optional else None, fec_status=np.zeros(k, np.uint8) if "fec_status" in optional else None,
+             stats=np.zeros(FEC_STATS_WORDS, np.int32) if "stats" in optional else None,
+             work=np.zeros(max(fec_repair_work_bytes(n, H, P), 8) // 8, np.int64))
+    return v
+
+
+def _fec_repair_result(v, stores):
+    """the dict a repair gives: the outputs and the advanced stores, with the stores' shape parameters - so that it is the next call's `stores`"""
+    r = _result(v, FEC_REPAIR_OUTPUTS)
+    r.update({k: stores[k] for k in ("med_offset", "med_slots", "med_stride", "fec_slots", "fec_stride")})
+    return r
+
+
+def plan_fec_repair(n_streams, stores, dg_offsets, dg_sizes, stream, seq, fec_stream, fec_offsets, fec_num_bytes, fec_seq, ssrc, passes=1, ring_capacity=None,
+                    optional=FEC_REPAIR_OPTIONAL, poison_work=None):
+    """The rule of DecBatch.fec_repair on the host (lc3plus_plan_fec_repair, no device needed).  stores: fec_repair_stores(...) or the dict an earlier call gave,
+    with this call's datagrams written into its ring; the media parse's dg_offsets (int64), dg_sizes, stream, seq [n_items] and the FEC parse's fec_stream,
+    fec_offsets (int64), fec_num_bytes, fec_seq [n_fec] (either list may be empty), ssrc [n_streams] -> dict of the advanced stores (FEC_REPAIR_STORES, copies: the
+    argument stays as it was) with their shape parameters, rec_dg_offsets (int64), rec_dg_sizes, rec_seq [n_streams * P], item_status (uint8) [n_items],
+    fec_status (uint8) [n_fec] and stats [FEC_STATS_WORDS]; those of FEC_REPAIR_OPTIONAL not named in `optional` are passed as NULL and come back as None.  A test
+    chains calls by passing the dict back.  LC3Error for arguments the C call refuses."""
+    v = _fec_repair_arrays(n_streams, stores, dg_offsets, dg_sizes, stream, seq, fec_stream, fec_offsets, fec_num_bytes, fec_seq, ssrc, passes, ring_capacity, optional)
+    _plan("lc3plus_plan_fec_repair", _poison(v, poison_work), (), n_streams=n_streams)
+    return _fec_repair_result(v, stores)
+
+
 # ---- reception reports ----
 def rtcp_workspace_bytes(n_items, n_streams):
     """the bytes of the workspace a DecBatch.rtcp_stats_device call over n_items items and n_streams streams needs (lc3plus_rtcp_workspace_bytes); 0 for
@@ -1063,6 +1139,30 @@ class _Receive:
         v = _fec_recover_arrays(self.n_streams, ring, dg_offsets, dg_sizes, stream, seq, fec_stream, fec_offsets, fec_num_bytes, ssrc, rec_offset, rec_stride, window,
                                 ring_capacity, optional)
         return _run(self, "lc3plus_dec_batch_fec_recover", _poison(v, poison_work), FEC_RECOVER_OUTPUTS)
+
+    def fec_repair_device(self, n_items, d_ring_ptr, ring_capacity, d_dg_offsets_ptr, d_dg_sizes_ptr, d_stream_ptr, d_seq_ptr, n_fec, d_fec_stream_ptr, d_fec_offsets_ptr,
+                          d_fec_num_bytes_ptr, d_fec_seq_ptr, d_ssrc_ptr, med_offset, med_slots, med_stride, d_med_seq_ptr, d_med_size_ptr, d_fec_store_ptr, fec_slots,
+                          fec_stride, d_cell_seq_ptr, d_cell_size_ptr, d_cell_status_ptr, d_state_ptr, d_rec_dg_offsets_ptr, d_rec_dg_sizes_ptr, d_rec_seq_ptr,
+                          d_work_ptr, passes=1, d_item_status_ptr=None, d_fec_status_ptr=None, d_stats_ptr=None, hip_stream=None, sync=False):
+        """Generic FEC across calls (lc3plus_dec_batch_fec_repair): raw device pointers only - this call's media items dg_offsets (int64), dg_sizes, stream, seq
+        [n_items] and FEC items fec_stream, fec_offsets (int64), fec_num_bytes, fec_seq [n_fec] over the ring (either list may be empty, its pointers then 0),
+        ssrc [n_streams], and the caller's stores, advanced in place: the media history inside the ring (med_offset, med_slots, med_stride) with med_seq, med_size
+        [n_streams, H], fec_store [n_streams, P, fec_stride] with cell_seq, cell_size, cell_status (uint8) [n_streams, P], state [n_streams,
+        FEC_REPAIR_STATE_WORDS] -> the arrivals admitted, up to `passes` recovery passes run, rebuilt packets in their media slots and listed in rec_dg_offsets
+        (int64), rec_dg_sizes, rec_seq [n_streams * P] - a datagram list for rtp_parse_device - with the optional item_status (uint8) [n_items], fec_status (uint8)
+        [n_fec] and stats [FEC_STATS_WORDS].  work: fec_repair_work_bytes(n_streams, med_slots, fec_slots) bytes.  Nothing of the batch's streams is read or
+        written.  Queued on hip_stream; returns at once unless sync."""
+        _device_call("lc3plus_dec_batch_fec_repair", locals())
+
+    def fec_repair(self, stores, dg_offsets, dg_sizes, stream, seq, fec_stream, fec_offsets, fec_num_bytes, fec_seq, ssrc, passes=1, ring_capacity=None,
+                   optional=FEC_REPAIR_OPTIONAL, poison_work=None):
+        """Host convenience: the arrays of plan_fec_repair uploaded, repaired on the device and downloaded -> the dict plan_fec_repair gives, the advanced stores
+        in it, so that a caller chains calls by passing it back.  Device memory through the HIP runtime as in probe(), freed before it returns.  poison_work: a
+        byte the workspace is filled with before the call."""
+        v = _fec_repair_arrays(self.n_streams, stores, dg_offsets, dg_sizes, stream, seq, fec_stream, fec_offsets, fec_num_bytes, fec_seq, ssrc, passes, ring_capacity,
+                               optional)
+        _run(self, "lc3plus_dec_batch_fec_repair", _poison(v, poison_work), FEC_REPAIR_OUTPUTS)
+        return _fec_repair_result(v, stores)
 
     def rtcp_stats_device(self, n_items, d_stream_ptr, d_seq_ptr, d_timestamp_ptr, d_arrival_ptr, n_streams, d_state_in_ptr, d_state_out_ptr, d_workspace_ptr,
                           workspace_bytes, make_report=False, d_ssrc_ptr=None, d_lsr_ptr=None, d_dlsr_ptr=None, d_blocks_ptr=None, d_ext_seq_ptr=None,

@@ -994,7 +994,8 @@ LC3_Error lc3plus_plan_red_unpack(int n_streams, int64_t n_items,
  *   sender    ... egress (wire) [-> red_pack] -> stamp -> fec_encode -> stamp (FEC list) -> protect (media), protect (FEC)
  *   receiver  unprotect -> parse (media types) + parse (FEC types) -> fec_recover -> parse (recovered) [-> red_unpack] -> probe -> ingest -> decode_packed
  * all on one HIP stream with no host wait.  NOT HANDLED: interleaved groups on the sender (a group is k consecutive sequence numbers), protection levels above
- * 0, iterative recovery (the pass is single: a packet recovered by one FEC item is not fed to another), RFC 8627 (FlexFEC), FEC carried inside RED, recovery across calls (the recover call knows the items of its own call alone: of a group that spans calls it rebuilds a packet only where the caller keeps the earlier members' datagrams in the ring and their entries in the lists it passes; otherwise those members count as missing).
+ * 0, RFC 8627 (FlexFEC), FEC carried inside RED.  Recovery across calls and iterative recovery are lc3plus_dec_batch_fec_repair's (REPAIR below): the recover call
+ * knows the items of its own call alone and makes a single pass.
  *
  * THE WIRE FORMAT.  An FEC packet is an RTP packet; its twelve header bytes are the stamp's work.  Its payload is a 10-byte FEC header, one level header and the
  * level-0 payload, all fields big-endian:
@@ -1142,6 +1143,100 @@ LC3_Error lc3plus_plan_fec_recover(int n_streams,
     int64_t n_items, void* ring, int64_t ring_capacity, const int64_t* dg_offsets, const int32_t* dg_sizes, const int32_t* stream, const int32_t* seq,
     int64_t n_fec, const int32_t* fec_stream, const int64_t* fec_offsets, const int32_t* fec_num_bytes, int window, const int32_t* ssrc,
     int64_t rec_offset, int64_t rec_stride, int64_t* rec_dg_offsets, int32_t* rec_dg_sizes, int32_t* rec_seq, uint8_t* status, int32_t* stats, void* work,
+    void* hip_stream, int sync);
+
+/* REPAIR.  The stateful sibling of RECOVER, for a receiver whose calls are shorter than a group: a real-time receiver makes one-frame calls, so every group of
+ * more than one packet closes in a later call than its first members arrived in.  The caller holds, in device memory, a per-stream history of recent media
+ * packets and a per-stream store of FEC packets whose groups are not settled yet.  The call admits its arrivals into both, runs up to `passes` recovery passes
+ * over the stored FEC packets against the stored media, writes rebuilt packets into the history - where later passes, later calls and the decoder find them - and
+ * hands them on as a datagram list for the parse:
+ *   receiver  unprotect -> parse + parse -> fec_repair -> parse (rec list) [-> red_unpack] -> probe -> ingest -> decode_packed
+ * The library keeps nothing.  Every pointer but `batch` is a device pointer.
+ *   n_items, ring, ring_capacity, dg_offsets (int64), dg_sizes, stream, seq : the media parse's arrays, as RECOVER takes them
+ *   n_fec, fec_stream, fec_offsets (int64), fec_num_bytes, fec_seq : the FEC parse's items with their own RTP sequence numbers
+ *   ssrc [n_streams]    : the SSRC written into rebuilt headers
+ *   n_items and n_fec may each be 0 and their arrays then NULL; a call with both 0 only expires and runs passes
+ *   med_offset (a multiple of 16), med_slots H (a power of two in [16, 1024]), med_stride (a multiple of 16 in [16, 2^20]) : the media history, inside the ring so
+ *                         that a rebuilt packet is parsed, probed, ingested and decoded by offset like any datagram: slot (s, j) is
+ *                         ring[med_offset + (s * H + j) * med_stride, + med_stride).  A datagram of a call that holds a byte of that range is RANGE
+ *   med_seq, med_size [n_streams][H] int32 : what each slot holds; size 0: nothing
+ *   fec_store [n_streams][P][fec_stride] uint8, fec_slots P (a power of two in [4, 256]), fec_stride (a multiple of 16 in [16, 2^20]) : the stored FEC payloads
+ *                         from their first header byte;  cell_seq, cell_size [n_streams][P] int32, cell_status [n_streams][P] uint8 : what each cell holds
+ *   state [n_streams][LC3PLUS_FEC_REPAIR_STATE_WORDS] int32, read and written in place like med_seq ... cell_status: bit 0 of word 0 the media head is valid,
+ *                         bit 1 the FEC head is valid; word 1 the media head, word 2 the FEC head, word 3 zero.  A stream whose valid bit is 0 has no stored
+ *                         packet of that kind, whatever the arrays hold: four zero words start a stream afresh and nothing else needs initialising - so a
+ *                         caller follows reset_streams
+ *   passes              : 1 ... 4
+ *   rec_dg_offsets (int64), rec_dg_sizes, rec_seq [n_streams * P], by cell c = s * P + j: nonzero only for a cell that rebuilt a packet in this call, the offset
+ *                         its media slot - a datagram list for rtp_parse over the same ring
+ *   item_status (uint8) [n_items], fec_status (uint8) [n_fec], stats [LC3PLUS_FEC_STATS_WORDS] : each may be NULL
+ *   work                : lc3plus_fec_repair_work_bytes(n_streams, med_slots, fec_slots) bytes, 8-byte aligned; its contents mean nothing before or after
+ * THE RULE.  Every step is as if sequential; no outcome depends on scheduling.  Sequence arithmetic is 16-bit serial arithmetic, d(a, b) = (int16)(a - b).  Under
+ * a head h a number sn lies BEHIND a window of n slots where d(h, sn) >= n, and AHEAD of the head where d(sn, h) > 0.
+ * 1 USABLE.  A media item gets the first of DROPPED (stream outside [0, n_streams)), RANGE (its datagram outside the ring, or with a byte inside the history: the
+ *   call would read it while it writes it), SHORT (fewer than 12 bytes), OVERSIZE
+ *   (more than med_stride) that applies, and is usable without one.  An FEC item gets the first of RECOVER's checks 1 ... 5 that fails - RANGE also for a byte inside the history -, then OVERSIZE (more than
+ *   fec_stride), and is usable without one.
+ * 2 HEADS, per stream and kind, over the media space of seq and the FEC space of fec_seq.  With a valid head h: h' = h + max(0, max over the usable items of
+ *   d(seq, h)).  Without one: b the number of the lowest-index usable item, h' = b + max(0, max d(seq, b)), and the kind becomes valid.  A kind with no usable
+ *   item keeps its state, and one that stays without a head keeps its arrays untouched.
+ * 3 EXPIRY.  A stored entry with (h' - seq) & 0xFFFF >= its slot count becomes empty.  A stored FEC cell, whatever its status, is also emptied when every number
+ *   its mask names lies behind the media window.  An empty entry has seq 0, size 0 (and status 0).
+ * 4 ADMISSION.  A usable item with (h' - seq) & 0xFFFF below the slot count goes to slot seq & (slots - 1); the others are STALE.  Inside the window this map is
+ *   one to one, so only copies of one number meet.  Where the slot holds that number already, what is stored stays and the item is DUPLICATE: a packet rebuilt
+ *   earlier is not replaced by its late original.  Of several such items in one call the lowest index is stored, the others are DUPLICATE.  A stored media item
+ *   copies exactly its size bytes from byte 0 of its RTP header into its slot and no other byte of the slot; a stored FEC item copies exactly its size bytes
+ *   and takes cell status MISSING, "not settled yet".
+ * 5 PASSES 1 ... passes.  In pass p every cell with status MISSING gets RECOVER's verdict with the members looked up in the media history as it stood when the
+ *   pass began.  A member is present where the slot of its number holds exactly that number: a collision can lose a recovery and never forge one.  With no
+ *   member missing the cell is COMPLETE.  Otherwise, where a missing number lies behind the media window - the group can never complete - it is EXPIRED.
+ *   Otherwise, with two or more missing, or with the one missing number ahead of the media head (or no media head yet), it stays MISSING: a number ahead of the
+ *   head may still arrive, and is rebuilt by the first call whose arrivals have moved the head up to it.  Otherwise PARTIAL where the recovered length exceeds the
+ *   protection length, OVERFLOW where 12 + length > med_stride, else RECOVERED: the rebuilt packet - the header as RECOVER writes it, with ssrc[s], then the XOR
+ *   bytes - goes to the media slot of the missing number, with med_seq, med_size and the cell's rec_* entry.  Where several cells of one pass rebuild the same
+ *   number, the lowest cell writes and reports; the others become TWIN and have no rec_* entry.  COMPLETE, RECOVERED, PARTIAL, OVERFLOW, EXPIRED and TWIN are
+ *   final: no later pass or call evaluates such a cell again.  All `passes` passes are queued always; a pass behind one that rebuilt nothing changes nothing.
+ *   THE DIFFERENCE FROM RECOVER.  On a single call that holds everything, with no window collision and one pass, statuses 0 ... 9 and the rebuilt bytes are
+ *   RECOVER's - but for a group whose one missing member is the newest number of its stream: RECOVER rebuilds it (RECOVERED), REPAIR leaves the cell MISSING until
+ *   a later call's arrivals move the head up to that number.
+ * 6 REPORTS.  item_status: LC3PLUS_FEC_STORED (0) or the reason the media item was not stored.  fec_status: the reason, or the status of the item's cell after the
+ *   last pass.  stats[k]: the FEC items of this call with status k, and besides them the cells carried in from earlier calls that settled in this call, counted
+ *   under their new status.  stats and the rec_* arrays are zeroed by the call.
+ * Refused calls queue nothing, checked in this order: a NULL batch, ring, ssrc, med_seq, med_size, fec_store, cell_seq, cell_size, cell_status, state,
+ * rec_dg_offsets, rec_dg_sizes, rec_seq or work; with n_items > 0 dg_offsets, dg_sizes, stream or seq; with n_fec > 0 fec_stream, fec_offsets, fec_num_bytes or
+ * fec_seq (LC3_NULL_ERROR); then n_items < 0 or >= 2^29, ring_capacity < 0, n_fec < 0 or >= 2^29; med_offset < 0 or no multiple of 16, med_slots, med_stride;
+ * fec_slots, fec_stride; passes; n_streams * H or n_streams * P of 2^31 - 1 or more; a history that ends behind ring_capacity; any overlap among fec_store, the
+ * history's range of the ring, med_seq, med_size, cell_seq, cell_size, cell_status and state; a work that is not 8-byte aligned (LC3_ERROR).
+ * The kernels live in liblc3plus_repair_hip.so, loaded like the FEC library's on the first repair call. */
+/* the repair call's constants, an enumeration (the #define block above is the encode and recover calls', complete as it stands): the words of a stream's state -
+ * bit 0 media head valid, bit 1 FEC head valid | media head | FEC head | 0 -, item_status of a stored media item, and the statuses beyond
+ * LC3PLUS_FEC_OVERFLOW (9), in the same numbering space and the same stats words */
+enum {
+    LC3PLUS_FEC_REPAIR_STATE_WORDS = 4,
+    LC3PLUS_FEC_STORED = 0,      /* item_status: the media item went into the history */
+    LC3PLUS_FEC_STALE = 10,      /* behind the window of its sequence space */
+    LC3PLUS_FEC_DUPLICATE = 11,  /* that sequence number is stored already, or a lower item of this call has it */
+    LC3PLUS_FEC_OVERSIZE = 12,   /* longer than the slot stride of its store */
+    LC3PLUS_FEC_EXPIRED = 13,    /* a missing member lies behind the media window: the group can no longer be repaired */
+    LC3PLUS_FEC_TWIN = 14        /* in the same pass a lower cell rebuilt the same packet */
+};
+/* the bytes of `work` for a repair call; 0 for arguments the call refuses */
+int64_t lc3plus_fec_repair_work_bytes(int n_streams, int med_slots, int fec_slots);
+LC3_Error lc3plus_dec_batch_fec_repair(lc3plus_dec_batch* batch,
+    int64_t n_items, void* ring, int64_t ring_capacity, const int64_t* dg_offsets, const int32_t* dg_sizes, const int32_t* stream, const int32_t* seq,
+    int64_t n_fec, const int32_t* fec_stream, const int64_t* fec_offsets, const int32_t* fec_num_bytes, const int32_t* fec_seq, const int32_t* ssrc,
+    int64_t med_offset, int med_slots, int med_stride, int32_t* med_seq, int32_t* med_size,
+    void* fec_store, int fec_slots, int fec_stride, int32_t* cell_seq, int32_t* cell_size, uint8_t* cell_status, int32_t* state, int passes,
+    int64_t* rec_dg_offsets, int32_t* rec_dg_sizes, int32_t* rec_seq, uint8_t* item_status, uint8_t* fec_status, int32_t* stats, void* work,
+    void* hip_stream, int sync);
+/* The same rule on the host alone: the same arrays in host memory, n_streams given instead of a batch (n_streams <= 0 is refused with the counts).  hip_stream
+ * and sync are ignored. */
+LC3_Error lc3plus_plan_fec_repair(int n_streams,
+    int64_t n_items, void* ring, int64_t ring_capacity, const int64_t* dg_offsets, const int32_t* dg_sizes, const int32_t* stream, const int32_t* seq,
+    int64_t n_fec, const int32_t* fec_stream, const int64_t* fec_offsets, const int32_t* fec_num_bytes, const int32_t* fec_seq, const int32_t* ssrc,
+    int64_t med_offset, int med_slots, int med_stride, int32_t* med_seq, int32_t* med_size,
+    void* fec_store, int fec_slots, int fec_stride, int32_t* cell_seq, int32_t* cell_size, uint8_t* cell_status, int32_t* state, int passes,
+    int64_t* rec_dg_offsets, int32_t* rec_dg_sizes, int32_t* rec_seq, uint8_t* item_status, uint8_t* fec_status, int32_t* stats, void* work,
     void* hip_stream, int sync);
 
 /* ---- Reception reports: per-stream RTP statistics and RR report blocks, on the device ----------------------------------------------------------------------
