@@ -8,7 +8,7 @@ the claimed entry points were launched.
 
 run_encoder / run_decoder are the two engines.  The expectation never comes from another GPU path: the encoder's bytes are those of lc3_harness.Oracle
 (portable math) given set_bitrate / set_bandwidth before every frame as the host rule (api.enc_plan_rates_ragged) accepts them, over each stream's present frames
-only; the decoder's samples and status are lc3_harness.OracleDecoder's.  Sample types the oracle does not read go through api.pcm_from_native / api.pcm_to_native
+only; the decoder's samples and status are lc3_harness.OracleDecoder's at the output type's depth (_dec_same).  Sample types the oracle does not read go through api.pcm_from_native / api.pcm_to_native
 on the host (float32 is fed on the 16-bit grid, where the format's rule gives the int16 sample); placed and packed calls are laid out with api.pcm_placed_offset,
 api.plan_placed and api.plan_packed.  Every output buffer starts as sentinels and every byte a call may not write is checked untouched.
 
@@ -37,6 +37,7 @@ G48_5S = (48000, 5.0, 0, 2, (129600, 161600, 96000))        # 81, 101, 60 bytes
 G48_25S = (48000, 2.5, 0, 2, (259200, 195200, 128000))      # 81, 61, 40 bytes
 G32S = (32000, 10.0, 0, 2, (128800, 160800, 96000))
 G16S = (16000, 10.0, 0, 2, (64800, 96800, 48000))           # 81, 121, 60 bytes
+G44S = (44100, 10.0, 0, 2, (118400, 147900, 92400))         # 161, 201, 125 bytes; frames of 480 samples that last 10.88 ms (tests/option_pairs.py)
 G48HR = (48000, 10.0, 1, 1, (128000, 256000, 400000))       # high resolution in the standard layout
 G96 = (96000, 10.0, 1, 1, (149600, 256000, 400000))         # the large layout
 G96S = (96000, 10.0, 1, 2, (300000, 400800, 512000))        # 375, 501, 640 bytes
@@ -57,13 +58,15 @@ def E(name, geom, claims, **kw):
     """encoder scenario.  calls: frames per call; how: device (encode_device), host (encode), hostwords (encode_device with host words), rates
     (encode_device_rates), packed (encode_device_packed); words: "", "r", "b", "rb"; form: 16, 24, 32, "f32" or a wire type's name; placed, ragged, ready
     (the input-ready promise); pad: bytes the PCM pointer lies off a 256-byte boundary; order: of packed output; reset: streams reset between the calls;
-    env: environment switches in force while the batch is created"""
+    layout: None, "interleaved" or "channel_major" (the device array is the default one permuted with api.pcm_offset); env: environment switches in force
+    while the batch is created"""
     _add("enc", name, geom, claims, **kw)
 
 
 def D(name, geom, claims, **kw):
     """decoder scenario.  how: host (decode), hostsizes (decode with num_bytes), device (decode_device), devhostsizes (decode_device with host num_bytes),
-    sizes (decode_device_sizes), packed (decode_device_packed); placed, ragged, ready, env as for the encoder"""
+    sizes (decode_device_sizes), packed (decode_device_packed); placed, ragged, ready, layout, env as for the encoder; out: the output sample type, named as
+    the encoder's form; pad: bytes the PCM output pointer lies off a 256-byte boundary (the bytes in front of and behind the buffer are checked untouched)"""
     _add("dec", name, geom, claims, **kw)
 
 
@@ -274,11 +277,34 @@ def _placement(api, fmt, ch, N, S, T, k, invalid):
 def _frame_elems(api, fmt, ch, N, off):
     """element indices [ch, N] of a frame placed at element off"""
     idx = np.zeros((ch, N), np.int64)
+    step = ch if fmt & api.PCM_INTERLEAVED else 1
     for c in range(ch):
         a, b = api.pcm_placed_offset(fmt, ch, N, off, c, 0), api.pcm_placed_offset(fmt, ch, N, off, c, N - 1)
-        assert a >= 0 and b - a == N - 1
-        idx[c] = a + np.arange(N)
+        assert a >= 0 and b - a == (N - 1) * step
+        idx[c] = a + step * np.arange(N)
     return idx
+
+
+def _dense_elems(api, fmt, ch, T, N, s, t):
+    """element indices [ch, N] of frame (s, t) of a dense call of T frames in the layout of format word fmt (api.pcm_offset)"""
+    idx = np.zeros((ch, N), np.int64)
+    for c in range(ch):
+        a, b = api.pcm_offset(fmt, ch, T, N, s, t, c, 0), api.pcm_offset(fmt, ch, T, N, s, t, c, N - 1)
+        assert a >= 0 and (b - a) % (N - 1) == 0
+        idx[c] = a + (b - a) // (N - 1) * np.arange(N)
+    return idx
+
+
+def _lay(api, fmt, arr):
+    """arr [S, T, ch, N (, 3)] in the default layout -> the same samples in the layout of fmt, shape api.pcm_shape: a permutation placed with api.pcm_offset"""
+    if not fmt & (api.PCM_INTERLEAVED | api.PCM_CHANNEL_MAJOR):
+        return arr
+    S, T, ch, N = arr.shape[:4]
+    out = np.zeros((S * T * ch * N,) + arr.shape[4:], arr.dtype)
+    for s in range(S):
+        for t in range(T):
+            out[_dense_elems(api, fmt, ch, T, N, s, t)] = arr[s, t]
+    return out.reshape(api.pcm_shape(fmt, S, T, ch, N))
 
 
 def _words(sc, fs, rates, S, T, k, lenient):
@@ -310,12 +336,16 @@ def run_encoder(dev, sc, amd):
     total = sum(calls)
     x16 = synth_pcm(S * ch, total, N, fs, seed=211 + len(sc["name"])).reshape(S, ch, total, N).transpose(0, 2, 1, 3).copy()
     fmt, xdev, xora, depth = _pcm_forms(api, sc.get("form", 16), x16)
+    if sc.get("layout"):
+        fmt = api.pcm_format(fmt, sc["layout"])
     orc = [Oracle(fs, ch, ms, hr, int(r), portable_math=True) for r in rates]
     for o, n in zip(orc, sizes0):
         o.nbytes = n
     bat = amd.Batch(S, fs, ch, ms, hr, rates, device=0)
     if sc.get("ready"):
         bat.set_input_ready(True)
+    if sc.get("before"):
+        sc["before"](bat)                                                    # (tests/test_gpu_option_pairs.py: a refused call in front of the scenario's own)
     pos = np.zeros(S, np.int64)
     cur_rates, cur_bw = np.array(rates, np.int32), np.zeros(S, np.int32)
     queued = []
@@ -354,6 +384,8 @@ def run_encoder(dev, sc, amd):
                     if not inval[s, t]:
                         arena[_frame_elems(api, fmt, ch, N, int(offs[s, t]))] = arr[s, t]
             arr, d_offs = arena, dev.put(offs)
+        else:
+            arr = _lay(api, fmt, arr)
         # the oracle over the present frames, in the stream's order
         want = [[None] * T for _ in range(S)]
         for s in range(S):
@@ -464,27 +496,61 @@ def _dec_streams(sc, fs, ms, hr, ch, rates, total, var):
     return frames, sizes
 
 
+def _rha(v):
+    """round half away from zero, float64 (np.round rounds half to even)"""
+    return np.sign(v) * np.floor(np.abs(v) + 0.5)
+
+
+def _dec_depths(out):
+    """the depths the oracle decodes at for output type out: its own, the one a wire type stands for, 16 and 24 for float32"""
+    return (16, 24) if out == "f32" else (WIRE_DEPTH[out],) if out in WIRE_DEPTH else (out,)
+
+
+def _dec_same(api, out, fmt, got, want):
+    """is a decoded frame - got: its elements as bytes [ch, N, element bytes] - the oracle's, want: the oracle's frame at every depth of _dec_depths(out).  Integer
+    types: equality.  Wire types: equality with api.pcm_from_native (bytes swapped, 24 bits saturated, G.711 compressed) of the oracle's frame at the depth the
+    type stands for.  float32: the sample rounded half away from zero equals the oracle's 16-bit and 24-bit sample
+    (test_gpu_pcm_format.py: test_float_output_rounds_to_the_integer_outputs)."""
+    got = np.ascontiguousarray(got)
+    if out in (16, 24, 32):
+        return np.array_equal(got.view(np.int16 if out == 16 else np.int32)[..., 0], want[0])
+    if out == "f32":
+        y = got.view(np.float32)[..., 0].astype(np.float64)
+        if not np.abs(y).max() < 256.0:                                            # (what an int32 at 24 bits holds; a NaN fails here too)
+            return False
+        r16 = np.clip(_rha(y * 32768.0), -32768.0, 32767.0).astype(np.int16)
+        return np.array_equal(r16, want[0]) and np.array_equal(_rha(y * float(1 << 23)).astype(np.int64), want[1].astype(np.int64))
+    wire = np.ascontiguousarray(api.pcm_from_native(fmt & 0xFF, want[0]))
+    return np.array_equal(got, wire.view(np.uint8).reshape(got.shape))
+
+
 def run_decoder(dev, sc, amd):
     api = amd.api
     fs, ms, hr, ch, rates = sc["geom"]
     S, N, calls, how = len(rates), frame_len(fs, ms), sc["calls"], sc["how"]
-    ragged, placed = bool(sc.get("ragged")), bool(sc.get("placed"))
+    ragged, placed, pad = bool(sc.get("ragged")), bool(sc.get("placed")), sc.get("pad", 0)
+    out = sc.get("out", 16)
+    fmt = api.pcm_format(api.PCM_FLOAT32 if out == "f32" else out, sc.get("layout"))
+    eb = api.load_library().lc3plus_pcm_elem_bytes(fmt)
+    depths = _dec_depths(out)
     var = how in ("hostsizes", "devhostsizes", "sizes", "packed")
     lenient = how in ("sizes", "packed")
     total = sum(calls)
     frames, sizes = _dec_streams(sc, fs, ms, hr, ch, rates, total, var)
     stride = int(sizes.max())
-    orc = [OracleDecoder(fs, ch, ms, hr, portable_math=True) for _ in range(S)]
+    orc = [[OracleDecoder(fs, ch, ms, hr, portable_math=True) for _ in depths] for _ in range(S)]
     d = amd.DecBatch(S, fs, ch, ms, hr, None if var else [int(sizes[s, 0]) for s in range(S)], device=0)
     if sc.get("ready"):
         d.set_input_ready(True)
+    if sc.get("before"):
+        sc["before"](d)
     pos = np.zeros(S, np.int64)
     queued = []
     for k, T in enumerate(calls):
         if k and sc.get("reset"):
             d.reset_streams(list(sc["reset"]))
             for s in sc["reset"]:
-                orc[s] = OracleDecoder(fs, ch, ms, hr, portable_math=True)
+                orc[s] = [OracleDecoder(fs, ch, ms, hr, portable_math=True) for _ in depths]
         cnt = counts_of(k, T, S) if ragged else np.full(S, T, np.int32)
         present = np.arange(T)[None, :] < cnt[:, None]
         fr = np.full((S, T, stride), 0x33, np.uint8)
@@ -505,40 +571,43 @@ def run_decoder(dev, sc, amd):
         inval = np.zeros((S, T), bool)
         if placed:
             bad = (0, 0) if k == 0 else None                              # stream 0 has every frame of call 0
-            offs, cap, inval = _placement(api, 16, ch, N, S, T, k, bad)
-        want = np.zeros((S, T, ch, N), np.int16)
+            offs, cap, inval = _placement(api, fmt, ch, N, S, T, k, bad)
+        want = [[None] * T for _ in range(S)]
         wst = np.full((S, T), ST_ABSENT, np.uint8)
         for s in range(S):
             for t in range(int(cnt[s])):
                 n = int(nb[s, t])
-                rc, pcm = orc[s].decode(fr[s, t, :max(n, 1)], int(bfi[s, t]) if how != "device" else 0, 16, num_bytes=n)
-                assert rc in (0, 2), rc
-                want[s, t] = pcm
+                res = [o.decode(fr[s, t, :max(n, 1)], int(bfi[s, t]) if how != "device" else 0, dep, num_bytes=n) for o, dep in zip(orc[s], depths)]
+                rc = res[0][0]
+                assert rc in (0, 2) and all(r[0] == rc for r in res), [r[0] for r in res]
+                want[s][t] = [r[1] for r in res]
                 wst[s, t] = (rc == 2) | (ST_PLACE if inval[s, t] else 0)
         q = dict(T=T, cnt=cnt, want=want, wst=wst, inval=inval, present=present)
         if how in ("host", "hostsizes"):
-            q["pcm"], q["st"] = d.decode(fr, bfi, num_bytes=nb if how == "hostsizes" else None)
+            q["pcm"], q["st"] = d.decode(fr, bfi, bps=fmt, num_bytes=nb if how == "hostsizes" else None)
         else:
             d_fr = dev.put(fr)
+            # the PCM: `pad` bytes of sentinels, the call's elements as sentinels, 64 bytes of sentinels
+            q["n"] = cap if placed else S * T * ch * N
+            q["bytes"] = pad + q["n"] * eb + 64
+            q["d_base"] = dev.put(np.full(q["bytes"], 0x5A, np.uint8))
+            q["d_pcm"] = q["d_base"] + pad
             if placed:
-                q["offs"], q["cap"] = offs, cap
-                q["d_pcm"] = dev.put(np.full(cap, 0x5A5A, np.uint16))
+                q["offs"] = offs
                 d.set_pcm_placement(dev.put(offs), cap)
-            else:
-                q["d_pcm"] = dev.put(np.full((S, T, ch, N), 0x5A5A, np.uint16))
             d_cnt = dev.put(cnt) if ragged else None
             if ragged:
                 d.set_frame_counts(d_cnt)
             sync = not sc.get("ready")
             if how == "device":
-                d.decode_device(d_fr, stride, T, q["d_pcm"], sync=sync)
+                d.decode_device(d_fr, stride, T, q["d_pcm"], bps=fmt, sync=sync)
             elif how == "devhostsizes":
-                d.decode_device(d_fr, stride, T, q["d_pcm"], sync=sync, num_bytes=nb, bfi=bfi)
+                d.decode_device(d_fr, stride, T, q["d_pcm"], bps=fmt, sync=sync, num_bytes=nb, bfi=bfi)
             else:
                 q["d_st"] = dev.put(np.full((S, T), ST_SENT, np.uint8))
                 d_nb, d_bfi = dev.put(nb), dev.put(bfi)
                 if how == "sizes":
-                    d.decode_device_sizes(d_fr, stride, T, q["d_pcm"], d_nb, d_bfi, q["d_st"], sync=sync)
+                    d.decode_device_sizes(d_fr, stride, T, q["d_pcm"], d_nb, d_bfi, q["d_st"], bps=fmt, sync=sync)
                 else:
                     # packed: the frames back to back in the other stream order, a gap of one byte between them
                     po = np.zeros((S, T), np.int64)
@@ -551,7 +620,7 @@ def run_decoder(dev, sc, amd):
                     for s in range(S):
                         for t in range(int(cnt[s])):
                             buf[po[s, t]:po[s, t] + nb[s, t]] = fr[s, t, :nb[s, t]]
-                    d.decode_device_packed(dev.put(buf), buf.size, dev.put(po), T, q["d_pcm"], d_nb, stride, d_bfi, q["d_st"], sync=sync)
+                    d.decode_device_packed(dev.put(buf), buf.size, dev.put(po), T, q["d_pcm"], d_nb, stride, d_bfi, q["d_st"], bps=fmt, sync=sync)
             if ragged:
                 d.set_frame_counts(None)
             if placed:
@@ -563,31 +632,28 @@ def run_decoder(dev, sc, amd):
     for k, q in enumerate(queued):
         T, cnt, want, wst = q["T"], q["cnt"], q["want"], q["wst"]
         if "pcm" in q:
-            got = q["pcm"]
+            elems = np.ascontiguousarray(q["pcm"]).view(np.uint8).reshape(-1, eb)
+            assert elems.shape[0] == S * T * ch * N and q["pcm"].shape == api.pcm_shape(fmt, S, T, ch, N)
             st = q["st"]
             assert (st == (wst & 1)).all(), (k, "status", st.tolist(), wst.tolist())
-        elif "offs" in q:
-            raw = dev.get(q["d_pcm"], (q["cap"],), np.int16)
-            exp = np.full(q["cap"], 0x5A5A, np.uint16).view(np.int16)
-            got = np.zeros_like(want)
-            for s in range(S):
-                for t in range(T):
-                    if q["present"][s, t] and not q["inval"][s, t]:
-                        idx = _frame_elems(api, 16, ch, N, int(q["offs"][s, t]))
-                        exp[idx] = want[s, t]
-                        got[s, t] = raw[idx]
-                    else:
-                        got[s, t] = want[s, t]
-            bad += [(k, s, t) for s, t in np.argwhere((got != want).any(axis=(2, 3))).tolist()]
-            assert bad or np.array_equal(raw, exp), (k, "samples outside the frames were written", np.flatnonzero(raw != exp)[:8].tolist())
         else:
-            got = dev.get(q["d_pcm"], (S, T, ch, N), np.int16)
-            want = np.where(q["present"][:, :, None, None], want, np.full(1, 0x5A5A, np.uint16).view(np.int16)[0])
+            raw = dev.get(q["d_base"], (q["bytes"],), np.uint8)
+            elems = raw[pad:pad + q["n"] * eb].reshape(-1, eb)
+        touched = np.zeros(elems.shape[0], bool)
+        for s in range(S):
+            for t in range(T):
+                if not q["present"][s, t] or q["inval"][s, t]:
+                    continue                                                # absent or refused: nothing written, the elements stay sentinels (below)
+                idx = _frame_elems(api, fmt, ch, N, int(q["offs"][s, t])) if "offs" in q else _dense_elems(api, fmt, ch, T, N, s, t)
+                touched[idx] = True
+                if not _dec_same(api, out, fmt, elems[idx], want[s][t]):
+                    bad.append((k, s, t))
+        if "pcm" not in q:
+            dirty = np.flatnonzero(np.concatenate([raw[:pad], np.where(touched[:, None], 0x5A, elems).reshape(-1), raw[pad + q["n"] * eb:]]) != 0x5A)
+            assert bad or not dirty.size, (k, "samples outside the frames were written (byte offsets from the pointer)", (dirty[:8] - pad).tolist())
         if "d_st" in q:
             st = dev.get(q["d_st"], (S, T), np.uint8)
             assert (st == wst).all(), (k, "status", st.tolist(), wst.tolist())
-        if "offs" not in q:
-            bad += [(k, s, t) for s, t in np.argwhere((got != want).any(axis=(2, 3))).tolist()]
     d.close()
     assert not bad, ("frames that differ from the oracle decoder (call, stream, frame)", len(bad), bad[:10])
 
