@@ -73,6 +73,32 @@ static void geom_update_ex(geom_t* g, int decoder)
 }
 static void geom_update(geom_t* g) { geom_update_ex(g, 0); }              /* R/setup_enc_lc3.c:73-193 */
 
+/* The geometry of a call that takes (samplerate, channels, frame_ms, hrmode): a check part, which returns the first error, and a fill part.  Every batch create
+ * and every plan hook is these two; a hook that takes one channel passes 1, and the one that checks less (dec_hook_table) calls geom_check_io alone. */
+static LC3_Error geom_check_io(int samplerate, int channels)
+{
+    if (!samplerate_ok(samplerate)) return LC3_SAMPLERATE_ERROR;
+    if (channels < 1 || channels > MAX_CH) return LC3_CHANNELS_ERROR;
+    return LC3_OK;
+}
+static LC3_Error geom_check(int samplerate, int channels, float frame_ms, int hrmode, int decoder)
+{
+    const LC3_Error e = geom_check_io(samplerate, channels);
+    if (e) return e;
+    { int d = (int)ceil(frame_ms * 10); if (d != 25 && d != 50 && d != 100) return LC3_FRAMEMS_ERROR; }
+    if (decoder) {                                                        /* R/lc3.c:350-351: below 44.1 kHz no hrmode, at 96 kHz nothing else */
+        if (samplerate < 44100 && hrmode != 0) return LC3_SAMPLERATE_ERROR;
+        if (samplerate == 96000 && hrmode == 0) return LC3_HRMODE_ERROR;
+    } else if (samplerate < 48000 && hrmode != 0) return LC3_SAMPLERATE_ERROR;
+    return LC3_OK;
+}
+static void geom_fill(geom_t* g, int samplerate, int channels, float frame_ms, int hrmode, int decoder)
+{
+    geom_init(g, samplerate, channels);
+    g->dms = (int)(frame_ms * 10); g->frame_ms = frame_ms; g->hrmode = hrmode > 0;
+    geom_update_ex(g, decoder);
+}
+
 /* the kernels are built for frame lengths up to LC3D_MAX_N = 960 whose N/2-point DFT has a restated kernel (480 = 15x32, 240 = 15x16,
  * 60 = 4x15, and the prime-factor lengths 10 ... 160) and an MDCT overlap memory of at most 600 samples: every operating point of
  * the reference.  N > 480 or a memory > 300 run in the large-layout kernel (lc3_kernels.hip) */
@@ -146,10 +172,11 @@ static LC3_Error derive_bitrate(const geom_t* g, int bitrate, lc3d_chan* ch /* [
 
 /* per-frame bitrates: the configuration of every channel byte count 0 .. max, from derive_chan (entry 0 zeroed; out_off and the bandwidth words are
  * not used from it: the kernel takes the channel's offset from the stream-frame size and the bandwidth from the stream) */
-static int enc_max_chan_bytes(const geom_t* g) { return g->hrmode ? (g->dms == 25 ? 210 : g->dms == 50 ? 375 : 625) : 400; }
+/* the largest channel frame of the geometry, encoder and decoder alike (R/defines.h MAX_NBYTES; in hrmode per frame length, R/setup_dec_lc3.c:203-299) */
+static int geom_max_chan_bytes(const geom_t* g) { return g->hrmode ? (g->dms == 25 ? 210 : g->dms == 50 ? 375 : 625) : 400; }
 static lc3d_chan* enc_build_table(const geom_t* g, int* n)
 {
-    *n = enc_max_chan_bytes(g) + 1;
+    *n = geom_max_chan_bytes(g) + 1;
     lc3d_chan* tab = (lc3d_chan*)calloc((size_t)*n, sizeof(lc3d_chan));
     if (!tab) return NULL;
     for (int k = 1; k < *n; k++) derive_chan(g, k, &tab[k]);
@@ -163,7 +190,7 @@ static LC3_Error enc_plan_bitrates(const geom_t* g, const int* bitrates, size_t 
     LC3_Error e = bitrate_limits(g, &lo, &hi);
     if (e) return e;
     for (size_t i = 0; i < n; i++) {
-        const int tb = lc3d_enc_rate_bytes(bitrates[i], lo, hi, g->N, g->fs_in, g->channels, enc_max_chan_bytes(g), INT_MAX);   /* (inside the table always, by the limits) */
+        const int tb = lc3d_enc_rate_bytes(bitrates[i], lo, hi, g->N, g->fs_in, g->channels, geom_max_chan_bytes(g), INT_MAX);   /* (inside the table always, by the limits) */
         if (tb < 0) return LC3_BITRATE_ERROR;
         fsz[i] = (uint16_t)tb;
         if (tb > mx) mx = tb;
@@ -363,6 +390,35 @@ static LC3_Error stream_import_host_check(int codec, const geom_t* g, const void
     for (int i = 0; i < n; i++) if (!stream_header_ok(h, (const uint8_t*)blob + (size_t)i * sz)) return LC3_ERROR;
     return LC3_OK;
 }
+/* Export and import of both batch kinds: the checks, the batch's header, the device call of the kind (dev: the batch's context).  Reset is per kind: the two
+ * configurations differ. */
+static int stream_state_call(int codec, void* dev, int mode, const int* streams, int n, void* blob, int blob_on_device, const uint32_t* h, uint8_t* status,
+                             void* hip_stream, int sync)
+{
+    return codec == SS_DEC ? lc3hip_dec_stream_state(dev, mode, streams, n, NULL, blob, blob_on_device, h, status, hip_stream, sync)
+                           : lc3hip_stream_state(dev, mode, streams, n, NULL, blob, blob_on_device, h, status, hip_stream, sync);
+}
+static LC3_Error streams_export(int codec, const geom_t* g, int n_streams, void* dev, const int* streams, int n, void* blob, int blob_on_device, void* hip_stream,
+                                int sync)
+{
+    LC3_Error e = stream_blob_check(n_streams, streams, n, blob, blob_on_device);
+    if (e) return e;
+    uint32_t h[4];
+    stream_header(codec, g, h);
+    return stream_state_call(codec, dev, LC3D_SS_EXPORT, streams, n, blob, blob_on_device, h, NULL, hip_stream, sync) ? LC3_ERROR : LC3_OK;
+}
+static LC3_Error streams_import(int codec, const geom_t* g, int n_streams, void* dev, const int* streams, int n, const void* blob, int blob_on_device,
+                                uint8_t* status, void* hip_stream, int sync)
+{
+    LC3_Error e = stream_blob_check(n_streams, streams, n, blob, blob_on_device);
+    if (!e && !blob_on_device) e = stream_import_host_check(codec, g, blob, n);
+    if (e) return e;
+    uint32_t h[4];
+    stream_header(codec, g, h);
+    if (stream_state_call(codec, dev, LC3D_SS_IMPORT, streams, n, (void*)blob, blob_on_device, h, status, hip_stream, sync)) return LC3_ERROR;
+    if (status && !blob_on_device) memset(status, 0, (size_t)n);
+    return LC3_OK;
+}
 
 /* ------------------------------------------------------------------------------------------------ */
 /* batch object                                                                                      */
@@ -386,6 +442,16 @@ struct lc3plus_batch {
      * launch, so that they clear and upload as ever instead of leaving the word for their next launch to act on again. */
     int resets_unknown;
 };
+/* Grows a host scratch array of a batch (fsz, bwf; the decoder's eff, lost) to n >= 1 elements of `size` bytes; what it held is not kept.  Returns the array,
+ * or NULL where there is no memory: the old array is gone then and the capacity 0, and the call that asked returns LC3_ERROR. */
+static void* scratch_grow(void* p, size_t* cap, size_t n, size_t size)
+{
+    if (*cap >= n) return p;
+    free(p); *cap = 0;
+    p = malloc(n * size);
+    if (p) *cap = n;
+    return p;
+}
 /* all the packet layer sees of an encoder batch (lc3_batch_view.h) */
 lc3host_view lc3host_enc_view(const lc3plus_batch* b) { const lc3host_view v = {b->dev, 0, b->n_streams, b->g.channels, b->g.ylen}; return v; }
 
@@ -395,17 +461,19 @@ lc3host_view lc3host_enc_view(const lc3plus_batch* b) { const lc3host_view v = {
 enum { DRY_BW = 1, DRY_RATES = 2, DRY_ALL = 3 };
 #define DRY_STOP(b, level, res) do { if ((b)->dry && (b)->dry <= (level)) return (res); } while (0)
 static void batch_restride(lc3plus_batch* b);
+/* whether the host copy holds a bandwidth with a cut-off line below 1 (bw_unsafe is this or, since the last look, 1 where set_bandwidth installed one) */
+static int enc_bw_unsafe(const lc3plus_batch* b)
+{
+    for (int i = 0; i < b->n_streams; i++) if (!lc3d_bw_value_ok(b->chans[(size_t)i * b->g.channels].bandwidth, b->g.dms)) return 1;
+    return 0;
+}
 /* Brings the host copy of the configuration back after calls with rates or bandwidths in device memory: waits for the batch's last call and downloads it, once. */
 static LC3_Error enc_refresh(lc3plus_batch* b)
 {
     if (!b->chans_stale) return LC3_OK;
     if (lc3hip_download_chans(b->dev, b->chans)) return LC3_ERROR;
-    const int C = b->g.channels;
-    b->bw_unsafe = 0;
-    for (int i = 0; i < b->n_streams; i++) {
-        b->bitrates[i] = b->chans[(size_t)i * C].bitrate;
-        if (!lc3d_bw_value_ok(b->chans[(size_t)i * C].bandwidth, b->g.dms)) b->bw_unsafe = 1;
-    }
+    for (int i = 0; i < b->n_streams; i++) b->bitrates[i] = b->chans[(size_t)i * b->g.channels].bitrate;
+    b->bw_unsafe = enc_bw_unsafe(b);
     batch_restride(b);
     b->chans_stale = 0; b->resets_unknown = 0;
     return LC3_OK;
@@ -427,17 +495,73 @@ static void batch_restride(lc3plus_batch* b)
     b->stride = s;
 }
 
+/* The end of a call that has launched with host arrays or none (batch_encode, batch_encode_bitrates, batch_encode_bandwidths, encode_packed without words):
+ * bitrates NULL or the call's [n_streams][n_frames] rates (checked by enc_plan_bitrates), bwf NULL or the bandwidths in force of enc_plan_bandwidths.  The launch
+ * has consumed every one-shot attack-detector reset - those pending from set_bitrate and those the call's own rate changes asked for - and leaves each stream
+ * configured with its last frame's rate and the bandwidth in force after its last frame.  The host copy follows and goes to the device only where something
+ * changed: the bandwidth words alone where no rate and no reset did (bw_only: a following per-frame-bandwidth call may still overlap this one).  A call with
+ * arrays does not wait for its kernels (sync = 0), so its copy is queued behind them on the call's stream; the plain call's is the synchronous one.  A stale
+ * copy has no resets to consume (the dense device-word calls consume them, a copy left stale by ragged calls was read back before the launch) and nothing of
+ * it is uploaded. */
+static LC3_Error enc_call_done(lc3plus_batch* b, const int* bitrates, const uint16_t* bwf, int n_frames, void* hip_stream)
+{
+    if (b->chans_stale) return LC3_OK;
+    const int C = b->g.channels;
+    int rate_dirty = 0, bw_dirty = 0;
+    for (int i = 0; i < b->n_streams; i++) {
+        lc3d_chan* ch = b->chans + (size_t)i * C;
+        for (int c = 0; c < C; c++) if (ch[c].reset_attack) { ch[c].reset_attack = 0; rate_dirty = 1; }
+        if (bitrates && bitrates[(size_t)i * n_frames + n_frames - 1] != b->bitrates[i]) {
+            const int br = bitrates[(size_t)i * n_frames + n_frames - 1];
+            if (derive_bitrate(&b->g, br, ch) != LC3_OK) return LC3_ERROR;
+            for (int c = 0; c < C; c++) ch[c].reset_attack = 0;          /* (the kernel has done it) */
+            b->bitrates[i] = br; rate_dirty = 1;
+        }
+        if (bwf && bwf[(size_t)i * n_frames + n_frames - 1] != ch[0].bandwidth) {
+            const int bw = bwf[(size_t)i * n_frames + n_frames - 1];
+            for (int c = 0; c < C; c++) { ch[c].bandwidth = bw; ch[c].bw_cut_bin = lc3d_bw_cut_bin(bw, b->g.dms); ch[c].bw_index = lc3d_bw_index(bw); }
+            bw_dirty = 1;
+        }
+    }
+    if (!rate_dirty && !bw_dirty) return LC3_OK;
+    if (rate_dirty) batch_restride(b);
+    if (!bitrates && !bwf) return batch_upload(b, 0, b->n_streams);
+    return lc3hip_upload_chans_async(b->dev, b->chans, 0, b->n_streams * C, hip_stream, !rate_dirty) ? LC3_ERROR : LC3_OK;
+}
+
+/* The start of a call whose rates or bandwidths are words in device memory (encode_rates_device, encode_packed).  With bandwidths, a value in force with a
+ * cut-off line below 1 is refused as encode_bandwidths refuses it (enc_plan_bandwidths): bw_unsafe says there may be one, the host copy - read back if need be -
+ * whether there is.  Out: *resets, whether one-shot attack-detector resets are pending for the launch to consume: those of set_bitrate in a copy that is
+ * current, and whatever ragged calls may have left behind a stale one (resets_unknown; a copy left stale by dense calls has none). */
+static LC3_Error enc_words_begin(lc3plus_batch* b, int with_bandwidths, int* resets)
+{
+    if (with_bandwidths && b->bw_unsafe) {
+        if (enc_refresh(b)) return LC3_ERROR;
+        b->bw_unsafe = enc_bw_unsafe(b);
+        if (b->bw_unsafe) return LC3_ERROR;
+    }
+    *resets = b->resets_unknown;
+    if (!b->chans_stale) for (int i = 0; i < b->n_streams * b->g.channels; i++) *resets |= b->chans[i].reset_attack != 0;
+    return LC3_OK;
+}
+/* ... and its end: the configuration after the call is on the device only, and the host copy is read back by the next host-side reader or writer.  Until then
+ * encode() checks out_stride against stride_bound: stride() before the first such call, raised to `lim`, the largest stream-frame the call could configure,
+ * where the call had rates (every stream-frame of it fits lim, and so does each stream's carry). */
+static void enc_words_done(lc3plus_batch* b, int with_rates, int lim)
+{
+    if (!b->chans_stale) b->stride_bound = b->stride;
+    if (with_rates && lim > b->stride_bound) b->stride_bound = lim;
+    b->chans_stale = 1;
+    b->resets_unknown = b->ragged;              /* a dense call's tail kernel has cleared every stream's reset; a ragged one's only those of the streams that ran */
+}
+
 /* the geometry of an encoder batch, or the error create gives for it; no device */
 static LC3_Error enc_batch_geometry(geom_t* g, int n_streams, int samplerate, int channels, float frame_ms, int hrmode)
 {
     if (n_streams <= 0) return LC3_ERROR;
-    if (!samplerate_ok(samplerate)) return LC3_SAMPLERATE_ERROR;
-    if (channels < 1 || channels > MAX_CH) return LC3_CHANNELS_ERROR;
-    { int d = (int)ceil(frame_ms * 10); if (d != 25 && d != 50 && d != 100) return LC3_FRAMEMS_ERROR; }
-    if (samplerate < 48000 && hrmode != 0) return LC3_SAMPLERATE_ERROR;
-    geom_init(g, samplerate, channels);
-    g->dms = (int)(frame_ms * 10); g->frame_ms = frame_ms; g->hrmode = hrmode > 0;
-    geom_update(g);
+    const LC3_Error e = geom_check(samplerate, channels, frame_ms, hrmode, 0);
+    if (e) return e;
+    geom_fill(g, samplerate, channels, frame_ms, hrmode, 0);
     if (!geom_supported(g)) {
         fprintf(stderr, "lc3plus_hip: %d Hz / %.1f ms%s is not built into the gfx950 kernels yet\n", samplerate, frame_ms, hrmode ? " hr" : "");
         return LC3_ERROR;
@@ -546,30 +670,29 @@ typedef char pcm_format_words_agree[(LC3PLUS_PCM_FLOAT32 == LC3D_PCM_FLOAT32 && 
                                     LC3PLUS_PCM_CHANNEL_MAJOR == LC3D_PCM_CHANNEL_MAJOR && LC3PLUS_PCM_S16_BE == LC3D_PCM_S16_BE &&
                                     LC3PLUS_PCM_S24_3LE == LC3D_PCM_S24_3LE && LC3PLUS_PCM_S24_3BE == LC3D_PCM_S24_3BE &&
                                     LC3PLUS_PCM_ULAW == LC3D_PCM_ULAW && LC3PLUS_PCM_ALAW == LC3D_PCM_ALAW) ? 1 : -1];
-static int pcm_format_ok(int format) { return lc3d_pcm_format_ok(format); }
 static int pcm_format_plain(int format) { return format == 16 || format == 24 || format == 32; }
 /* Host-only hooks: the format check and the address rule without a GPU (tests/test_pcm_format_cpu.py). */
-LC3_Error lc3plus_pcm_format_check(int format) { return pcm_format_ok(format) ? LC3_OK : LC3_ERROR; }
+LC3_Error lc3plus_pcm_format_check(int format) { return lc3d_pcm_format_ok(format) ? LC3_OK : LC3_ERROR; }
 int64_t lc3plus_pcm_offset(int format, int channels, int n_frames, int samples, int stream, int frame, int channel, int sample)
 {
-    if (!pcm_format_ok(format) || channels <= 0 || n_frames <= 0 || samples <= 0 || stream < 0 || frame < 0 || frame >= n_frames || channel < 0 ||
+    if (!lc3d_pcm_format_ok(format) || channels <= 0 || n_frames <= 0 || samples <= 0 || stream < 0 || frame < 0 || frame >= n_frames || channel < 0 ||
         channel >= channels || sample < 0 || sample >= samples) return -1;
     return (int64_t)(lc3d_pcm_frame(format, channels, n_frames, samples, stream, frame, channel) + (size_t)sample * lc3d_pcm_stride(format, channels));
 }
 
-int lc3plus_pcm_elem_bytes(int format) { return pcm_format_ok(format) ? lc3d_pcm_elem_bytes(format) : -1; }
+int lc3plus_pcm_elem_bytes(int format) { return lc3d_pcm_format_ok(format) ? lc3d_pcm_elem_bytes(format) : -1; }
 /* Placed PCM (lc3_plan.h: lc3d_pcm_placed_*, the text the _plc kernels compile too).  Host-only hooks: the address rule and the validity rule without a GPU
  * (tests/test_pcm_placed_cpu.py). */
 int64_t lc3plus_pcm_placed_offset(int format, int channels, int samples, int64_t frame_offset, int channel, int sample)
 {
-    if (!pcm_format_ok(format) || (format & LC3D_PCM_CHANNEL_MAJOR) || channels <= 0 || samples <= 0 || frame_offset < 0 || channel < 0 || channel >= channels ||
+    if (!lc3d_pcm_format_ok(format) || (format & LC3D_PCM_CHANNEL_MAJOR) || channels <= 0 || samples <= 0 || frame_offset < 0 || channel < 0 || channel >= channels ||
         sample < 0 || sample >= samples) return -1;
     if (frame_offset > INT64_MAX - (int64_t)channels * samples) return -1;
     return (int64_t)(lc3d_pcm_placed_frame(format, channels, samples, (long long)frame_offset, channel) + (size_t)sample * lc3d_pcm_stride(format, channels));
 }
 LC3_Error lc3plus_plan_placed(int format, int channels, int samples, const int64_t* offsets, int64_t n, int64_t capacity, uint8_t* invalid)
 {
-    if (n < 0 || capacity < 0 || channels <= 0 || samples <= 0 || !pcm_format_ok(format) || (format & LC3D_PCM_CHANNEL_MAJOR)) return LC3_ERROR;
+    if (n < 0 || capacity < 0 || channels <= 0 || samples <= 0 || !lc3d_pcm_format_ok(format) || (format & LC3D_PCM_CHANNEL_MAJOR)) return LC3_ERROR;
     if (n > 0 && (!offsets || !invalid)) return LC3_NULL_ERROR;
     for (int64_t i = 0; i < n; i++) invalid[i] = (uint8_t)!lc3d_pcm_placed_ok((long long)offsets[i], channels, samples, (long long)capacity);
     return LC3_OK;
@@ -634,7 +757,7 @@ static LC3_Error batch_encode(lc3plus_batch* b, const void* pcm, int pcm_on_devi
                               int out_on_device, void* hip_stream, int sync, void* trace)
 {
     if (!b || !pcm || !out) return LC3_NULL_ERROR;
-    if (!pcm_format_ok(bitdepth)) return LC3_ERROR;
+    if (!lc3d_pcm_format_ok(bitdepth)) return LC3_ERROR;
     if (placed_refuses(b->placed, pcm_on_device, bitdepth, trace)) return LC3_ERROR;
     if (b->ragged) return LC3_ERROR;                                 /* per-stream frame counts are read by the calls with flags in device memory alone; nothing is touched here */
     if (trace && !pcm_format_plain(bitdepth)) return LC3_ERROR;      /* the traced calls take the integer formats in the default layout only */
@@ -642,13 +765,7 @@ static LC3_Error batch_encode(lc3plus_batch* b, const void* pcm, int pcm_on_devi
     DRY_STOP(b, DRY_ALL, LC3_OK);
     if (b->resets_unknown && enc_refresh(b)) return LC3_ERROR;      /* behind ragged calls: the resets this launch consumes are cleared below, once */
     if (lc3hip_encode(b->dev, pcm, pcm_on_device, bitdepth, n_frames, out, out_stride, out_on_device, hip_stream, sync, trace, NULL, NULL)) return LC3_ERROR;
-    /* one-shot attack-state reset requests have been consumed by this launch (a stale copy has none: the dense device-rate calls consume them, a copy left
-     * stale by ragged calls was read back above, and nothing of a stale copy is uploaded) */
-    if (b->chans_stale) return LC3_OK;
-    int dirty = 0;
-    for (int i = 0; i < b->n_streams * b->g.channels; i++) if (b->chans[i].reset_attack) { b->chans[i].reset_attack = 0; dirty = 1; }
-    if (dirty) return batch_upload(b, 0, b->n_streams);
-    return LC3_OK;
+    return enc_call_done(b, NULL, NULL, n_frames, hip_stream);
 }
 
 LC3_Error lc3plus_enc_batch_encode(lc3plus_batch* b, const void* pcm, int pcm_on_device, int bitdepth, int n_frames, void* out,
@@ -661,19 +778,15 @@ static LC3_Error batch_encode_bitrates(lc3plus_batch* b, const void* pcm, int pc
                                        int out_stride, int out_on_device, int* num_bytes, void* hip_stream, int sync, void* trace)
 {
     if (!b || !pcm || !out || !bitrates) return LC3_NULL_ERROR;
-    if (!pcm_format_ok(bitdepth)) return LC3_ERROR;
+    if (!lc3d_pcm_format_ok(bitdepth)) return LC3_ERROR;
     if (placed_refuses(b->placed, pcm_on_device, bitdepth, trace)) return LC3_ERROR;
     if (b->ragged) return LC3_ERROR;                                 /* as in batch_encode */
     if (trace && !pcm_format_plain(bitdepth)) return LC3_ERROR;
     if (n_frames <= 0) return LC3_ERROR;
     if (enc_refresh(b)) return LC3_ERROR;
     const size_t n = (size_t)b->n_streams * n_frames;
-    if (b->fsz_cap < n) {
-        free(b->fsz); b->fsz_cap = 0;
-        b->fsz = (uint16_t*)malloc(n * sizeof(uint16_t));
-        if (!b->fsz) return LC3_ERROR;
-        b->fsz_cap = n;
-    }
+    b->fsz = (uint16_t*)scratch_grow(b->fsz, &b->fsz_cap, n, sizeof(uint16_t));
+    if (!b->fsz) return LC3_ERROR;
     int max_bytes = 0;
     LC3_Error e = enc_plan_bitrates(&b->g, bitrates, n, b->fsz, &max_bytes);
     if (e) return e;
@@ -682,22 +795,7 @@ static LC3_Error batch_encode_bitrates(lc3plus_batch* b, const void* pcm, int pc
     DRY_STOP(b, DRY_ALL, LC3_OK);
     if (lc3hip_encode(b->dev, pcm, pcm_on_device, bitdepth, n_frames, out, out_stride, out_on_device, hip_stream, sync, trace, b->fsz, NULL)) return LC3_ERROR;
     if (num_bytes) for (size_t i = 0; i < n; i++) num_bytes[i] = b->fsz[i];
-    /* every stream is configured with its last frame's rate; the kernel has done every attack-detector reset the call asked for, and the one-shot
-     * requests pending from set_bitrate before it */
-    int dirty = 0;
-    for (int i = 0; i < b->n_streams; i++) {
-        lc3d_chan* ch = b->chans + (size_t)i * b->g.channels;
-        const int br = bitrates[(size_t)i * n_frames + n_frames - 1];
-        for (int c = 0; c < b->g.channels; c++) if (ch[c].reset_attack) { ch[c].reset_attack = 0; dirty = 1; }
-        if (br == b->bitrates[i]) continue;
-        if (derive_bitrate(&b->g, br, ch) != LC3_OK) return LC3_ERROR;          /* checked by enc_plan_bitrates */
-        for (int c = 0; c < b->g.channels; c++) ch[c].reset_attack = 0;
-        b->bitrates[i] = br; dirty = 1;
-    }
-    if (!dirty) return LC3_OK;
-    batch_restride(b);
-    /* on the call's stream behind its kernels: the call does not wait for them (sync = 0) */
-    return lc3hip_upload_chans_async(b->dev, b->chans, 0, b->n_streams * b->g.channels, hip_stream, 0) ? LC3_ERROR : LC3_OK;
+    return enc_call_done(b, bitrates, NULL, n_frames, hip_stream);
 }
 LC3_Error lc3plus_enc_batch_encode_bitrates(lc3plus_batch* b, const void* pcm, int pcm_on_device, int bitdepth, const int* bitrates, int n_frames, void* out,
                                             int out_stride, int out_on_device, int* num_bytes, void* hip_stream, int sync)
@@ -712,12 +810,11 @@ LC3_Error lc3plus_enc_batch_encode_bitrates_traced(lc3plus_batch* b, const void*
     return batch_encode_bitrates(b, pcm, 0, bitdepth, bitrates, n_frames, out, out_stride, 0, NULL, NULL, 1, traces);
 }
 /* ---- per-frame bandwidths (lc3plus_enc_batch_encode_bandwidths) ---- */
-/* The values a call refuses outright: a negative bandwidth, and a positive one whose cut-off line is below 1 (the controller would write in front of the
- * spectrum, R/cutoff_bandwidth.c:17-19).  0 switches the controller off. */
-static int bw_value_ok(int bw, int dms) { return lc3d_bw_value_ok(bw, dms); }      /* lc3d_bw_cut_bin(bw, dms) >= 1, without overflow */
-/* The per-frame rule: frame t of stream s applies lc3_enc_set_bandwidth(bandwidths[s][t]) to the value in force before it (start[s] for frame 0,
+/* The values a call refuses outright (lc3d_bw_value_ok: lc3d_bw_cut_bin(bw, dms) >= 1, without overflow): a negative bandwidth, and a positive one whose
+ * cut-off line is below 1 (the controller would write in front of the spectrum, R/cutoff_bandwidth.c:17-19).  0 switches the controller off.
+ * The per-frame rule: frame t of stream s applies lc3_enc_set_bandwidth(bandwidths[s][t]) to the value in force before it (start[s] for frame 0,
  * R/lc3.c:187-208): a new value that 2 * bw > min(fs_in, 40000) refuses keeps the value in force and makes the call's result LC3_BW_WARNING.  Values
- * have been checked with bw_value_ok; start values are what set_bandwidth accepted, and one with a cut-off line below 1 that stays in force is refused
+ * have been checked with lc3d_bw_value_ok; start values are what set_bandwidth accepted, and one with a cut-off line below 1 that stays in force is refused
  * here too.  Out: in_force [n_streams][n_frames]. */
 static LC3_Error enc_plan_bandwidths(const geom_t* g, int n_streams, const int* start, const int* bandwidths, int n_frames, uint16_t* in_force)
 {
@@ -729,7 +826,7 @@ static LC3_Error enc_plan_bandwidths(const geom_t* g, int n_streams, const int* 
             const int f = lc3d_enc_bw_step(&cur, bandwidths[(size_t)s * n_frames + t], eff / 2, g->dms);     /* 2 * v > eff: eff is even */
             if (f & LC3D_ENC_FL_BW_RANGE) return LC3_ERROR;                                                     /* (checked before) */
             if (f & LC3D_ENC_FL_BW_REFUSED) res = LC3_BW_WARNING;
-            if (!bw_value_ok(cur, g->dms) || cur > 0xFFFF) return LC3_ERROR;
+            if (!lc3d_bw_value_ok(cur, g->dms) || cur > 0xFFFF) return LC3_ERROR;
             in_force[(size_t)s * n_frames + t] = (uint16_t)cur;
         }
     }
@@ -739,35 +836,27 @@ static LC3_Error batch_encode_bandwidths(lc3plus_batch* b, const void* pcm, int 
                                          int n_frames, void* out, int out_stride, int out_on_device, int* num_bytes, void* hip_stream, int sync)
 {
     if (!b) return LC3_NULL_ERROR;
-    if (placed_refuses(b->placed, pcm_on_device, pcm_format_ok(bitdepth) ? bitdepth : 0, NULL)) return LC3_ERROR;
+    if (placed_refuses(b->placed, pcm_on_device, lc3d_pcm_format_ok(bitdepth) ? bitdepth : 0, NULL)) return LC3_ERROR;
     if (b->ragged) return LC3_ERROR;                                 /* as in batch_encode */
     if (b->g.hrmode) return LC3_HRMODE_BW_ERROR;
     if (enc_refresh(b)) return LC3_ERROR;
     const size_t n = (size_t)b->n_streams * (n_frames > 0 ? n_frames : 0);
-    if (bandwidths) for (size_t i = 0; i < n; i++) if (!bw_value_ok(bandwidths[i], b->g.dms)) return LC3_ERROR;
+    if (bandwidths) for (size_t i = 0; i < n; i++) if (!lc3d_bw_value_ok(bandwidths[i], b->g.dms)) return LC3_ERROR;
     DRY_STOP(b, DRY_BW, LC3_OK);
     if (!pcm || !out || !bandwidths) return LC3_NULL_ERROR;
-    if (!pcm_format_ok(bitdepth)) return LC3_ERROR;
+    if (!lc3d_pcm_format_ok(bitdepth)) return LC3_ERROR;
     if (n_frames <= 0) return LC3_ERROR;
     if (bitrates) {
-        if (b->fsz_cap < n) {
-            free(b->fsz); b->fsz_cap = 0;
-            b->fsz = (uint16_t*)malloc(n * sizeof(uint16_t));
-            if (!b->fsz) return LC3_ERROR;
-            b->fsz_cap = n;
-        }
+        b->fsz = (uint16_t*)scratch_grow(b->fsz, &b->fsz_cap, n, sizeof(uint16_t));
+        if (!b->fsz) return LC3_ERROR;
         int max_bytes = 0;
         LC3_Error e = enc_plan_bitrates(&b->g, bitrates, n, b->fsz, &max_bytes);
         if (e) return e;
         DRY_STOP(b, DRY_RATES, LC3_OK);
         if (out_stride < max_bytes) return LC3_ERROR;
     } else if (out_stride < b->stride) return LC3_ERROR;
-    if (b->bwf_cap < n) {
-        free(b->bwf); b->bwf_cap = 0;
-        b->bwf = (uint16_t*)malloc(n * sizeof(uint16_t));
-        if (!b->bwf) return LC3_ERROR;
-        b->bwf_cap = n;
-    }
+    b->bwf = (uint16_t*)scratch_grow(b->bwf, &b->bwf_cap, n, sizeof(uint16_t));
+    if (!b->bwf) return LC3_ERROR;
     int start[256];
     LC3_Error res = LC3_OK;
     for (int s0 = 0; s0 < b->n_streams; s0 += 256) {          /* the value in force before the call: the stream's configuration */
@@ -781,30 +870,7 @@ static LC3_Error batch_encode_bandwidths(lc3plus_batch* b, const void* pcm, int 
     if (lc3hip_encode(b->dev, pcm, pcm_on_device, bitdepth, n_frames, out, out_stride, out_on_device, hip_stream, sync, NULL, bitrates ? b->fsz : NULL,
                       b->bwf)) return LC3_ERROR;
     if (num_bytes) for (size_t i = 0; i < n; i++) num_bytes[i] = bitrates ? b->fsz[i] : lc3plus_enc_batch_num_bytes(b, (int)(i / n_frames));
-    /* every stream is configured with the bandwidth in force after its last frame, and with its last rate when rates were given; the one-shot
-     * attack-detector resets pending from set_bitrate have been done by this call */
-    int dirty = 0, rate_dirty = 0;
-    for (int i = 0; i < b->n_streams; i++) {
-        lc3d_chan* ch = b->chans + (size_t)i * b->g.channels;
-        for (int c = 0; c < b->g.channels; c++) if (ch[c].reset_attack) { ch[c].reset_attack = 0; rate_dirty = 1; }
-        if (bitrates) {
-            const int br = bitrates[(size_t)i * n_frames + n_frames - 1];
-            if (br != b->bitrates[i]) {
-                if (derive_bitrate(&b->g, br, ch) != LC3_OK) return LC3_ERROR;          /* checked by enc_plan_bitrates */
-                for (int c = 0; c < b->g.channels; c++) ch[c].reset_attack = 0;
-                b->bitrates[i] = br; rate_dirty = 1;
-            }
-        }
-        const int bw = b->bwf[(size_t)i * n_frames + n_frames - 1];
-        if (bw != ch[0].bandwidth) {
-            for (int c = 0; c < b->g.channels; c++) { ch[c].bandwidth = bw; ch[c].bw_cut_bin = lc3d_bw_cut_bin(bw, b->g.dms); ch[c].bw_index = lc3d_bw_index(bw); }
-            dirty = 1;
-        }
-    }
-    if (rate_dirty) batch_restride(b);
-    /* on the call's stream behind its kernels: the call does not wait for them (sync = 0) */
-    if ((dirty || rate_dirty) && lc3hip_upload_chans_async(b->dev, b->chans, 0, b->n_streams * b->g.channels, hip_stream, !rate_dirty)) return LC3_ERROR;
-    return res;
+    return enc_call_done(b, bitrates, b->bwf, n_frames, hip_stream) ? LC3_ERROR : res;
 }
 LC3_Error lc3plus_enc_batch_encode_bandwidths(lc3plus_batch* b, const void* pcm, int pcm_on_device, int bitdepth, const int* bandwidths, const int* bitrates,
                                               int n_frames, void* out, int out_stride, int out_on_device, int* num_bytes, void* hip_stream, int sync)
@@ -824,19 +890,16 @@ LC3_Error lc3plus_enc_plan_bandwidths(int samplerate, float frame_ms, int hrmode
 {
     if (!start || !bandwidths || !in_force) return LC3_NULL_ERROR;
     if (n_streams <= 0 || n_frames <= 0) return LC3_ERROR;
-    if (!samplerate_ok(samplerate)) return LC3_SAMPLERATE_ERROR;
-    { int d = (int)ceil(frame_ms * 10); if (d != 25 && d != 50 && d != 100) return LC3_FRAMEMS_ERROR; }
-    if (samplerate < 48000 && hrmode != 0) return LC3_SAMPLERATE_ERROR;
+    LC3_Error e = geom_check(samplerate, 1, frame_ms, hrmode, 0);
+    if (e) return e;
     geom_t g;
-    geom_init(&g, samplerate, 1);
-    g.dms = (int)(frame_ms * 10); g.frame_ms = frame_ms; g.hrmode = hrmode > 0;
-    geom_update(&g);
+    geom_fill(&g, samplerate, 1, frame_ms, hrmode, 0);
     if (g.hrmode) return LC3_HRMODE_BW_ERROR;
     const size_t n = (size_t)n_streams * n_frames;
-    for (size_t i = 0; i < n; i++) if (!bw_value_ok(bandwidths[i], g.dms)) return LC3_ERROR;
+    for (size_t i = 0; i < n; i++) if (!lc3d_bw_value_ok(bandwidths[i], g.dms)) return LC3_ERROR;
     uint16_t* f = (uint16_t*)malloc(n * sizeof(uint16_t));
     if (!f) return LC3_ERROR;
-    const LC3_Error e = enc_plan_bandwidths(&g, n_streams, start, bandwidths, n_frames, f);
+    e = enc_plan_bandwidths(&g, n_streams, start, bandwidths, n_frames, f);
     if (e == LC3_OK || e == LC3_BW_WARNING) for (size_t i = 0; i < n; i++) in_force[i] = f[i];
     free(f);
     return e;
@@ -848,18 +911,14 @@ LC3_Error lc3plus_enc_plan_bitrates(int samplerate, int channels, float frame_ms
 {
     if (!bitrates || !num_bytes || !max_bytes) return LC3_NULL_ERROR;
     if (n_streams <= 0 || n_frames <= 0) return LC3_ERROR;
-    if (!samplerate_ok(samplerate)) return LC3_SAMPLERATE_ERROR;
-    if (channels < 1 || channels > MAX_CH) return LC3_CHANNELS_ERROR;
-    { int d = (int)ceil(frame_ms * 10); if (d != 25 && d != 50 && d != 100) return LC3_FRAMEMS_ERROR; }
-    if (samplerate < 48000 && hrmode != 0) return LC3_SAMPLERATE_ERROR;
+    LC3_Error e = geom_check(samplerate, channels, frame_ms, hrmode, 0);
+    if (e) return e;
     geom_t g;
-    geom_init(&g, samplerate, channels);
-    g.dms = (int)(frame_ms * 10); g.frame_ms = frame_ms; g.hrmode = hrmode > 0;
-    geom_update(&g);
+    geom_fill(&g, samplerate, channels, frame_ms, hrmode, 0);
     const size_t n = (size_t)n_streams * n_frames;
     uint16_t* fsz = (uint16_t*)malloc(n * sizeof(uint16_t));
     if (!fsz) return LC3_ERROR;
-    LC3_Error e = enc_plan_bitrates(&g, bitrates, n, fsz, max_bytes);
+    e = enc_plan_bitrates(&g, bitrates, n, fsz, max_bytes);
     if (!e) for (size_t i = 0; i < n; i++) num_bytes[i] = fsz[i];
     free(fsz);
     return e;
@@ -871,7 +930,7 @@ static LC3_Error enc_rate_rule(const geom_t* g, int lim, lc3d_rate_rule* r)
 {
     LC3_Error e = bitrate_limits(g, &r->lo, &r->hi);
     if (e) return e;
-    r->N = g->N; r->fs_in = g->fs_in; r->channels = g->channels; r->max_chan = enc_max_chan_bytes(g); r->lim = lim;
+    r->N = g->N; r->fs_in = g->fs_in; r->channels = g->channels; r->max_chan = geom_max_chan_bytes(g); r->lim = lim;
     r->half = (g->fs_in > 40000 ? 40000 : g->fs_in) / 2; r->dms = g->dms;
     return LC3_OK;
 }
@@ -879,29 +938,17 @@ LC3_Error lc3plus_enc_batch_encode_rates_device(lc3plus_batch* b, const void* pc
                                                 int n_frames, void* out, int out_stride, int32_t* num_bytes, uint8_t* flags, void* hip_stream, int sync)
 {
     if (!b || !pcm || !out || (!bitrates && !bandwidths)) return LC3_NULL_ERROR;
-    if (!pcm_format_ok(bitdepth)) return LC3_ERROR;
+    if (!lc3d_pcm_format_ok(bitdepth)) return LC3_ERROR;
     if (placed_refuses(b->placed, 1, bitdepth, NULL)) return LC3_ERROR;
     if (n_frames <= 0 || out_stride < enc_stride_bound(b)) return LC3_ERROR;
     if (bandwidths && b->g.hrmode) return LC3_HRMODE_BW_ERROR;
-    if (bandwidths && b->bw_unsafe) {           /* a value in force with a cut-off line below 1: refused as encode_bandwidths refuses it (enc_plan_bandwidths) */
-        if (enc_refresh(b)) return LC3_ERROR;
-        b->bw_unsafe = 0;
-        for (int i = 0; i < b->n_streams; i++) if (!bw_value_ok(b->chans[(size_t)i * b->g.channels].bandwidth, b->g.dms)) b->bw_unsafe = 1;
-        if (b->bw_unsafe) return LC3_ERROR;
-    }
+    int resets = 0;
+    if (enc_words_begin(b, bandwidths != NULL, &resets)) return LC3_ERROR;
     lc3d_rate_rule r;
     if (enc_rate_rule(&b->g, out_stride, &r)) return LC3_ERROR;
-    int resets = 0;                             /* one-shot attack-detector resets pending from set_bitrate (a stale copy has none) */
-    if (!b->chans_stale) for (int i = 0; i < b->n_streams * b->g.channels; i++) resets |= b->chans[i].reset_attack != 0;
-    resets |= b->resets_unknown;                /* (a stale copy behind ragged calls may have some) */
     if (lc3hip_encode_rates_device(b->dev, pcm, bitdepth, n_frames, out, out_stride, bitrates, bandwidths, &r, num_bytes, flags, resets, hip_stream, sync))
         return LC3_ERROR;
-    /* the configuration after the call is on the device only: the host copy is read back by the next host-side reader or writer; until then encode()
-     * checks out_stride against the bound: every stream-frame of this call fits out_stride, and so does each stream's carry */
-    if (!b->chans_stale) b->stride_bound = b->stride;
-    if (bitrates && out_stride > b->stride_bound) b->stride_bound = out_stride;
-    b->chans_stale = 1;
-    b->resets_unknown = b->ragged;              /* a dense call's tail kernel has cleared every stream's reset; a ragged one's only those of the streams that ran */
+    enc_words_done(b, bitrates != NULL, out_stride);
     return LC3_OK;
 }
 /* test hook: the rule of encode_rates_device on host arrays, without a device.  start_rates, start_bw [n_streams]: the stream's configuration before
@@ -912,21 +959,17 @@ static LC3_Error enc_plan_rates_host(int samplerate, int channels, float frame_m
 {
     if (!start_rates || !start_bw || !num_bytes || !bw_in_force || !flags || !end_rates || (need_words && !bitrates && !bandwidths)) return LC3_NULL_ERROR;
     if (n_streams <= 0 || n_frames <= 0) return LC3_ERROR;
-    if (!samplerate_ok(samplerate)) return LC3_SAMPLERATE_ERROR;
-    if (channels < 1 || channels > MAX_CH) return LC3_CHANNELS_ERROR;
-    { int d = (int)ceil(frame_ms * 10); if (d != 25 && d != 50 && d != 100) return LC3_FRAMEMS_ERROR; }
-    if (samplerate < 48000 && hrmode != 0) return LC3_SAMPLERATE_ERROR;
+    LC3_Error e = geom_check(samplerate, channels, frame_ms, hrmode, 0);
+    if (e) return e;
     geom_t g;
-    geom_init(&g, samplerate, channels);
-    g.dms = (int)(frame_ms * 10); g.frame_ms = frame_ms; g.hrmode = hrmode > 0;
-    geom_update(&g);
+    geom_fill(&g, samplerate, channels, frame_ms, hrmode, 0);
     if (bandwidths && g.hrmode) return LC3_HRMODE_BW_ERROR;
     lc3d_rate_rule r;
-    LC3_Error e = enc_rate_rule(&g, out_stride, &r);
+    e = enc_rate_rule(&g, out_stride, &r);
     if (e) return e;
     for (int s = 0; s < n_streams; s++) {       /* the start: a configuration the batch can hold, and one the call accepts */
         if (lc3d_enc_rate_bytes(start_rates[s], r.lo, r.hi, r.N, r.fs_in, r.channels, r.max_chan, out_stride) < 0) return LC3_BITRATE_ERROR;
-        if (bandwidths && !bw_value_ok(start_bw[s], g.dms)) return LC3_ERROR;
+        if (bandwidths && !lc3d_bw_value_ok(start_bw[s], g.dms)) return LC3_ERROR;
     }
     for (int s = 0; s < n_streams; s++) {
         int rate = start_rates[s], bytes = lc3d_enc_rate_bytes(rate, r.lo, r.hi, r.N, r.fs_in, r.channels, r.max_chan, out_stride), bw = start_bw[s];
@@ -965,38 +1008,22 @@ LC3_Error lc3plus_enc_batch_encode_packed(lc3plus_batch* b, const void* pcm, int
                                           void* hip_stream, int sync)
 {
     if (!b || !pcm || !out) return LC3_NULL_ERROR;
-    if (!pcm_format_ok(bitdepth)) return LC3_ERROR;
+    if (!lc3d_pcm_format_ok(bitdepth)) return LC3_ERROR;
     if (placed_refuses(b->placed, 1, bitdepth, NULL)) return LC3_ERROR;
     if (n_frames <= 0 || (order != LC3D_PACK_STREAM_MAJOR && order != LC3D_PACK_FRAME_MAJOR) || out_capacity < 0) return LC3_ERROR;
     if (bandwidths && b->g.hrmode) return LC3_HRMODE_BW_ERROR;
-    if (bandwidths && b->bw_unsafe) {           /* as encode_rates_device */
-        if (enc_refresh(b)) return LC3_ERROR;
-        b->bw_unsafe = 0;
-        for (int i = 0; i < b->n_streams; i++) if (!bw_value_ok(b->chans[(size_t)i * b->g.channels].bandwidth, b->g.dms)) b->bw_unsafe = 1;
-        if (b->bw_unsafe) return LC3_ERROR;
-    }
     /* no slot: a rate is refused only where set_bitrate refuses it - the bound on the bytes is the geometry's largest stream-frame */
-    const int lim = enc_max_chan_bytes(&b->g) * b->g.channels;
+    const int lim = geom_max_chan_bytes(&b->g) * b->g.channels;
     lc3d_rate_rule r;
     if (enc_rate_rule(&b->g, lim, &r)) return LC3_ERROR;
     const int has = bitrates || bandwidths || b->ragged;      /* (ragged: the plan and tail kernels run whatever the call has, and a stream that did not run keeps a pending reset) */
     if (!has && b->resets_unknown && enc_refresh(b)) return LC3_ERROR;      /* as batch_encode */
-    int resets = b->resets_unknown;             /* one-shot attack-detector resets pending from set_bitrate (a stale copy has none, unless ragged calls left it) */
-    if (!b->chans_stale) for (int i = 0; i < b->n_streams * b->g.channels; i++) resets |= b->chans[i].reset_attack != 0;
+    int resets = 0;
+    if (enc_words_begin(b, bandwidths != NULL, &resets)) return LC3_ERROR;
     if (lc3hip_encode_packed(b->dev, pcm, bitdepth, n_frames, bitrates, bandwidths, &r, order, out, (long long)out_capacity, (long long*)offsets,
                              (long long*)total, num_bytes, flags, resets, hip_stream, sync)) return LC3_ERROR;
-    if (has) {                                  /* the configuration after the call is on the device only, as after encode_rates_device */
-        if (!b->chans_stale) b->stride_bound = b->stride;
-        if (bitrates && lim > b->stride_bound) b->stride_bound = lim;
-        b->chans_stale = 1;
-        b->resets_unknown = b->ragged;
-        return LC3_OK;
-    }
-    /* as encode(): the one-shot attack-state reset requests have been consumed by this launch */
-    if (b->chans_stale) return LC3_OK;
-    int dirty = 0;
-    for (int i = 0; i < b->n_streams * b->g.channels; i++) if (b->chans[i].reset_attack) { b->chans[i].reset_attack = 0; dirty = 1; }
-    if (dirty) return batch_upload(b, 0, b->n_streams);
+    if (!has) return enc_call_done(b, NULL, NULL, n_frames, hip_stream);         /* nothing of the configuration moved: the call ends as encode() does */
+    enc_words_done(b, bitrates != NULL, lim);
     return LC3_OK;
 }
 /* The offsets of packed output on the host alone (the rule of lc3_pack_offsets_kernel): sizes [n_streams][n_frames] -> offsets [n_streams][n_frames], an
@@ -1092,25 +1119,12 @@ LC3_Error lc3plus_enc_batch_reset_streams(lc3plus_batch* b, const int* streams, 
 }
 LC3_Error lc3plus_enc_batch_export_streams(lc3plus_batch* b, const int* streams, int n, void* blob, int blob_on_device, void* hip_stream, int sync)
 {
-    if (!b) return LC3_NULL_ERROR;
-    LC3_Error e = stream_blob_check(b->n_streams, streams, n, blob, blob_on_device);
-    if (e) return e;
-    uint32_t h[4];
-    stream_header(SS_ENC, &b->g, h);
-    return lc3hip_stream_state(b->dev, LC3D_SS_EXPORT, streams, n, NULL, blob, blob_on_device, h, NULL, hip_stream, sync) ? LC3_ERROR : LC3_OK;
+    return b ? streams_export(SS_ENC, &b->g, b->n_streams, b->dev, streams, n, blob, blob_on_device, hip_stream, sync) : LC3_NULL_ERROR;
 }
 LC3_Error lc3plus_enc_batch_import_streams(lc3plus_batch* b, const int* streams, int n, const void* blob, int blob_on_device, uint8_t* status,
                                            void* hip_stream, int sync)
 {
-    if (!b) return LC3_NULL_ERROR;
-    LC3_Error e = stream_blob_check(b->n_streams, streams, n, blob, blob_on_device);
-    if (!e && !blob_on_device) e = stream_import_host_check(SS_ENC, &b->g, blob, n);
-    if (e) return e;
-    uint32_t h[4];
-    stream_header(SS_ENC, &b->g, h);
-    if (lc3hip_stream_state(b->dev, LC3D_SS_IMPORT, streams, n, NULL, (void*)blob, blob_on_device, h, status, hip_stream, sync)) return LC3_ERROR;
-    if (status && !blob_on_device) memset(status, 0, (size_t)n);
-    return LC3_OK;
+    return b ? streams_import(SS_ENC, &b->g, b->n_streams, b->dev, streams, n, blob, blob_on_device, status, hip_stream, sync) : LC3_NULL_ERROR;
 }
 
 LC3_Error lc3plus_enc_batch_set_input_ready(lc3plus_batch* b, int ready)
@@ -1297,9 +1311,6 @@ int lc3plus_enc_get_size(int sr, int ch) { return lc3_enc_get_size(sr, ch); }
 /* ================================================================================================ */
 /* decoder: lc3_dec_* drop-in API and the batched form                          */
 /* ================================================================================================ */
-/* same operating points as the encoder: standard and large kernel layout */
-static int dec_geom_supported(const geom_t* g) { return geom_supported(g); }
-
 /* R/setup_dec_lc3.c:203-299 (update_dec_bitrate) for one channel */
 static LC3_Error derive_dchan(const geom_t* g, int nbytes, lc3d_dchan* d)
 {
@@ -1350,16 +1361,13 @@ static LC3_Error derive_dstream(const geom_t* g, int num_bytes, lc3d_dchan* d /*
 LC3_Error lc3plus_plan_chan(int samplerate, float frame_ms, int hrmode, int nbytes, int* out)
 {
     if (!out) return LC3_NULL_ERROR;
-    if (!samplerate_ok(samplerate)) return LC3_SAMPLERATE_ERROR;
-    { int d = (int)ceil(frame_ms * 10); if (d != 25 && d != 50 && d != 100) return LC3_FRAMEMS_ERROR; }
-    if (samplerate < 48000 && hrmode != 0) return LC3_SAMPLERATE_ERROR;
+    LC3_Error e = geom_check(samplerate, 1, frame_ms, hrmode, 0);
+    if (e) return e;
     geom_t g;
-    geom_init(&g, samplerate, 1);
-    g.dms = (int)(frame_ms * 10); g.frame_ms = frame_ms; g.hrmode = hrmode > 0;
-    geom_update(&g);
+    geom_fill(&g, samplerate, 1, frame_ms, hrmode, 0);
     lc3d_chan s; lc3d_dchan d;
     memset(&s, 0, sizeof s); memset(&d, 0, sizeof d);
-    const LC3_Error e = derive_dchan(&g, nbytes, &d);
+    e = derive_dchan(&g, nbytes, &d);
     if (e) return e;
     derive_chan(&g, nbytes, &s);
     const int v[10] = {s.total_bits, s.target_bits_init, s.lpc_weighting, s.ltpf_enable, s.gg_off, s.attack_handling, s.reg_bits,
@@ -1370,10 +1378,9 @@ LC3_Error lc3plus_plan_chan(int samplerate, float frame_ms, int hrmode, int nbyt
 
 /* per-frame sizes: the configuration of every channel byte count 0 .. max, from derive_dchan (entry 0 and the sizes it rejects: zeroed, which is what a
  * channel created without a size has).  An entry is valid where its nbytes equals its index and is not 0. */
-static int dec_max_chan_bytes(const geom_t* g) { return g->hrmode ? (g->dms == 25 ? 210 : g->dms == 50 ? 375 : 625) : 400; }
 static lc3d_dchan* dec_build_table(const geom_t* g, int* n)
 {
-    *n = dec_max_chan_bytes(g) + 1;
+    *n = geom_max_chan_bytes(g) + 1;
     lc3d_dchan* tab = (lc3d_dchan*)calloc((size_t)*n, sizeof(lc3d_dchan));
     if (!tab) return NULL;
     for (int k = 1; k < *n; k++) if (derive_dchan(g, k, &tab[k])) memset(&tab[k], 0, sizeof tab[k]);
@@ -1413,38 +1420,34 @@ static LC3_Error dec_plan_sizes(const geom_t* g, const lc3d_dchan* tab, int tab_
 
 /* The rule of lc3plus_dec_batch_decode_sizes_device on the host (on the device: lc3_dec_plan_sizes_kernel and lc3_dec_sizes_tail_kernel): as
  * dec_plan_sizes, except that a size or flag the host call refuses does not fail the call - the frame is lost, marked in invalid[s][t], and does not
- * move the carry.  Nothing is refused. */
-static void dec_plan_sizes_lenient(const geom_t* g, const lc3d_dchan* tab, int tab_n, int n_streams, const int* start, const int* num_bytes, const uint8_t* bfi,
-                                   int n_frames, int in_stride, uint16_t* eff, uint8_t* lost, uint8_t* invalid, int* end, int* max_chan)
+ * move the carry.  Nothing is refused.
+ * The same loop serves lc3plus_dec_batch_decode_packed, whose frames are classified by offsets, capacity and max_bytes in place of in_stride: `cls` gives
+ * the class of frame i (LC3D_FRAME_*) from the call's arguments `a`. */
+typedef struct {
+    const lc3d_dchan* tab; int tab_n, channels; const int* num_bytes; const uint8_t* bfi;
+    int in_stride;                                                       /* slots (dec_class_slot) */
+    const int64_t* offsets; int64_t capacity; int max_bytes;             /* packed (dec_class_packed) */
+} dec_class_args;
+static int dec_class_slot(const dec_class_args* a, size_t i)
 {
-    const int C = g->channels;
-    int mx = 0;
-    for (int s = 0; s < n_streams; s++) {
-        int cur = start[s];
-        for (int t = 0; t < n_frames; t++) {
-            const size_t i = (size_t)s * n_frames + t;
-            const int k = lc3d_dec_frame_class(num_bytes[i], bfi ? bfi[i] : 0, in_stride, tab, tab_n, C);
-            if (k == LC3D_FRAME_GOOD) { cur = num_bytes[i]; if ((cur + C - 1) / C > mx) mx = (cur + C - 1) / C; }
-            eff[i] = (uint16_t)cur; lost[i] = k != LC3D_FRAME_GOOD; invalid[i] = k >= LC3D_FRAME_BAD_FLAG;
-        }
-        end[s] = cur;
-    }
-    *max_chan = mx;
+    return lc3d_dec_frame_class(a->num_bytes[i], a->bfi ? a->bfi[i] : 0, a->in_stride, a->tab, a->tab_n, a->channels);
 }
-
-/* The same for lc3plus_dec_batch_decode_packed: offsets, capacity and max_bytes in place of in_stride (lc3d_dec_frame_class_packed). */
-static void dec_plan_packed_lenient(const geom_t* g, const lc3d_dchan* tab, int tab_n, int n_streams, const int* start, const int* num_bytes,
-                                    const int64_t* offsets, int64_t capacity, int max_bytes, const uint8_t* bfi, int n_frames, uint16_t* eff, uint8_t* lost,
-                                    uint8_t* invalid, int* end, int* max_chan)
+static int dec_class_packed(const dec_class_args* a, size_t i)
 {
-    const int C = g->channels;
+    return lc3d_dec_frame_class_packed(a->num_bytes[i], a->bfi ? a->bfi[i] : 0, (long long)a->offsets[i], (long long)a->capacity, a->max_bytes, a->tab, a->tab_n,
+                                       a->channels);
+}
+static void dec_plan_lenient(int (*cls)(const dec_class_args*, size_t), const dec_class_args* a, int n_streams, const int* start, int n_frames, uint16_t* eff,
+                             uint8_t* lost, uint8_t* invalid, int* end, int* max_chan)
+{
+    const int C = a->channels;
     int mx = 0;
     for (int s = 0; s < n_streams; s++) {
         int cur = start[s];
         for (int t = 0; t < n_frames; t++) {
             const size_t i = (size_t)s * n_frames + t;
-            const int k = lc3d_dec_frame_class_packed(num_bytes[i], bfi ? bfi[i] : 0, (long long)offsets[i], (long long)capacity, max_bytes, tab, tab_n, C);
-            if (k == LC3D_FRAME_GOOD) { cur = num_bytes[i]; if ((cur + C - 1) / C > mx) mx = (cur + C - 1) / C; }
+            const int k = cls(a, i);
+            if (k == LC3D_FRAME_GOOD) { cur = a->num_bytes[i]; if ((cur + C - 1) / C > mx) mx = (cur + C - 1) / C; }
             eff[i] = (uint16_t)cur; lost[i] = k != LC3D_FRAME_GOOD; invalid[i] = k >= LC3D_FRAME_BAD_FLAG;
         }
         end[s] = cur;
@@ -1458,7 +1461,7 @@ struct lc3plus_dec_batch {
     int chans_stale;                 /* a call with sizes in device memory has changed the configuration on the device: dec_refresh before reading chans */
     void* dev;
     lc3d_dchan* tab; int tab_n;      /* dec_build_table, also on the device */
-    uint16_t* eff; uint8_t* lost; int* sz; size_t plan_cap;          /* per-frame sizes: host buffers of dec_plan_sizes, grown as needed */
+    uint16_t* eff; size_t eff_cap; uint8_t* lost; size_t lost_cap; int* sz;      /* per-frame sizes: host buffers of dec_plan_sizes, grown as needed */
     int dry;                         /* as lc3plus_batch.dry: the call returns behind its checks */
     int placed;                      /* as lc3plus_batch.placed (lc3plus_dec_batch_set_pcm_placement) */
     int ragged;                      /* lc3plus_dec_batch_set_frame_counts is on: only the calls with sizes in device memory decode, the others refuse */
@@ -1470,15 +1473,10 @@ lc3host_view lc3host_dec_view(const lc3plus_dec_batch* b) { const lc3host_view v
 static LC3_Error dec_batch_geometry(geom_t* g, int n_streams, int samplerate, int channels, float frame_ms, int hrmode)
 {
     if (n_streams <= 0) return LC3_ERROR;
-    if (!samplerate_ok(samplerate)) return LC3_SAMPLERATE_ERROR;
-    if (channels < 1 || channels > MAX_CH) return LC3_CHANNELS_ERROR;
-    { int d = (int)ceil(frame_ms * 10); if (d != 25 && d != 50 && d != 100) return LC3_FRAMEMS_ERROR; }
-    geom_init(g, samplerate, channels);
-    if (g->fs_idx < 4 && hrmode != 0) return LC3_SAMPLERATE_ERROR;          /* R/lc3.c:350 */
-    if (g->fs_idx == 5 && hrmode == 0) return LC3_HRMODE_ERROR;             /* R/lc3.c:351 */
-    g->dms = (int)(frame_ms * 10); g->frame_ms = frame_ms; g->hrmode = hrmode > 0;
-    geom_update_ex(g, 1);
-    if (!dec_geom_supported(g)) {
+    const LC3_Error e = geom_check(samplerate, channels, frame_ms, hrmode, 1);
+    if (e) return e;
+    geom_fill(g, samplerate, channels, frame_ms, hrmode, 1);
+    if (!geom_supported(g)) {
         fprintf(stderr, "lc3plus_hip: decoding %d Hz / %.1f ms%s is not built into the gfx950 kernels yet\n", samplerate, frame_ms, hrmode ? " hr" : "");
         return LC3_ERROR;
     }
@@ -1576,7 +1574,7 @@ static LC3_Error dec_batch_decode(lc3plus_dec_batch* b, const void* frames, int 
                                   void* pcm, int pcm_on_device, int bps, uint8_t* status, void* hip_stream, int sync, void* traces)
 {
     if (!b || !frames || !pcm) return LC3_NULL_ERROR;
-    if (!pcm_format_ok(bps)) return LC3_ERROR;
+    if (!lc3d_pcm_format_ok(bps)) return LC3_ERROR;
     if (placed_refuses(b->placed, pcm_on_device, bps, traces)) return LC3_ERROR;
     if (b->ragged) return LC3_ERROR;                                 /* per-stream frame counts are read by the device-size calls alone; nothing is touched here */
     if (traces && !pcm_format_plain(bps)) return LC3_ERROR;          /* the traced call writes the integer formats in the default layout only */
@@ -1591,18 +1589,15 @@ LC3_Error lc3plus_dec_batch_decode_sizes(lc3plus_dec_batch* b, const void* frame
                                          const uint8_t* bfi, int n_frames, void* pcm, int pcm_on_device, int bps, uint8_t* status, void* hip_stream, int sync)
 {
     if (!b || !frames || !pcm || !num_bytes) return LC3_NULL_ERROR;
-    if (!pcm_format_ok(bps)) return LC3_ERROR;
+    if (!lc3d_pcm_format_ok(bps)) return LC3_ERROR;
     if (placed_refuses(b->placed, pcm_on_device, bps, NULL)) return LC3_ERROR;
     if (b->ragged) return LC3_ERROR;                                 /* as in dec_batch_decode */
     if (n_frames <= 0) return LC3_ERROR;
     if (dec_refresh(b)) return LC3_ERROR;
     const size_t n = (size_t)b->n_streams * n_frames;
-    if (b->plan_cap < n) {
-        free(b->eff); free(b->lost); b->plan_cap = 0;
-        b->eff = (uint16_t*)malloc(n * sizeof(uint16_t)); b->lost = (uint8_t*)malloc(n);
-        if (!b->eff || !b->lost) return LC3_ERROR;
-        b->plan_cap = n;
-    }
+    b->eff = (uint16_t*)scratch_grow(b->eff, &b->eff_cap, n, sizeof(uint16_t));
+    b->lost = (uint8_t*)scratch_grow(b->lost, &b->lost_cap, n, 1);
+    if (!b->eff || !b->lost) return LC3_ERROR;
     if (!b->sz) { b->sz = (int*)malloc(2 * sizeof(int) * (size_t)b->n_streams); if (!b->sz) return LC3_ERROR; }
     int* start = b->sz; int* end = b->sz + b->n_streams;
     for (int i = 0; i < b->n_streams; i++) start[i] = lc3plus_dec_batch_num_bytes(b, i);
@@ -1634,7 +1629,7 @@ LC3_Error lc3plus_dec_batch_decode_sizes_device(lc3plus_dec_batch* b, const void
                                                 int n_frames, void* pcm, int bps, uint8_t* status, void* hip_stream, int sync)
 {
     if (!b || !frames || !pcm || !num_bytes) return LC3_NULL_ERROR;
-    if (!pcm_format_ok(bps)) return LC3_ERROR;
+    if (!lc3d_pcm_format_ok(bps)) return LC3_ERROR;
     if (placed_refuses(b->placed, 1, bps, NULL)) return LC3_ERROR;
     if (n_frames <= 0 || in_stride <= 0) return LC3_ERROR;
     /* the sizes, the carry and the configuration after the call are on the device only: the host mirror is read back by the next host-side reader */
@@ -1646,7 +1641,7 @@ LC3_Error lc3plus_dec_batch_decode_packed(lc3plus_dec_batch* b, const void* fram
                                           int max_frame_bytes, const uint8_t* bfi, int n_frames, void* pcm, int bps, uint8_t* status, void* hip_stream, int sync)
 {
     if (!b || !frames || !pcm || !num_bytes || !offsets) return LC3_NULL_ERROR;
-    if (!pcm_format_ok(bps)) return LC3_ERROR;
+    if (!lc3d_pcm_format_ok(bps)) return LC3_ERROR;
     if (placed_refuses(b->placed, 1, bps, NULL)) return LC3_ERROR;
     if (n_frames <= 0 || max_frame_bytes <= 0 || frames_capacity < 0) return LC3_ERROR;
     if (lc3hip_dec_decode_packed(b->dev, frames, (long long)frames_capacity, (const long long*)offsets, num_bytes, max_frame_bytes, bfi, n_frames, pcm, bps,
@@ -1679,25 +1674,12 @@ LC3_Error lc3plus_dec_batch_reset_streams(lc3plus_dec_batch* b, const int* strea
 }
 LC3_Error lc3plus_dec_batch_export_streams(lc3plus_dec_batch* b, const int* streams, int n, void* blob, int blob_on_device, void* hip_stream, int sync)
 {
-    if (!b) return LC3_NULL_ERROR;
-    LC3_Error e = stream_blob_check(b->n_streams, streams, n, blob, blob_on_device);
-    if (e) return e;
-    uint32_t h[4];
-    stream_header(SS_DEC, &b->g, h);
-    return lc3hip_dec_stream_state(b->dev, LC3D_SS_EXPORT, streams, n, NULL, blob, blob_on_device, h, NULL, hip_stream, sync) ? LC3_ERROR : LC3_OK;
+    return b ? streams_export(SS_DEC, &b->g, b->n_streams, b->dev, streams, n, blob, blob_on_device, hip_stream, sync) : LC3_NULL_ERROR;
 }
 LC3_Error lc3plus_dec_batch_import_streams(lc3plus_dec_batch* b, const int* streams, int n, const void* blob, int blob_on_device, uint8_t* status,
                                            void* hip_stream, int sync)
 {
-    if (!b) return LC3_NULL_ERROR;
-    LC3_Error e = stream_blob_check(b->n_streams, streams, n, blob, blob_on_device);
-    if (!e && !blob_on_device) e = stream_import_host_check(SS_DEC, &b->g, blob, n);
-    if (e) return e;
-    uint32_t h[4];
-    stream_header(SS_DEC, &b->g, h);
-    if (lc3hip_dec_stream_state(b->dev, LC3D_SS_IMPORT, streams, n, NULL, (void*)blob, blob_on_device, h, status, hip_stream, sync)) return LC3_ERROR;
-    if (status && !blob_on_device) memset(status, 0, (size_t)n);
-    return LC3_OK;
+    return b ? streams_import(SS_DEC, &b->g, b->n_streams, b->dev, streams, n, blob, blob_on_device, status, hip_stream, sync) : LC3_NULL_ERROR;
 }
 /* test hooks of the lifecycle rules, without a device: the index-list rule; the blob header of a geometry (decoder != 0: the decoder's; the checks of the
  * batch's create, LC3_ERROR where the kernels do not support the geometry); the header check of an import */
@@ -1705,31 +1687,22 @@ LC3_Error lc3plus_stream_list_check(int n_streams, const int* streams, int n) { 
 LC3_Error lc3plus_stream_state_header(int decoder, int samplerate, int channels, float frame_ms, int hrmode, uint32_t* header)
 {
     if (!header) return LC3_NULL_ERROR;
-    if (!samplerate_ok(samplerate)) return LC3_SAMPLERATE_ERROR;
-    if (channels < 1 || channels > MAX_CH) return LC3_CHANNELS_ERROR;
-    { int d = (int)ceil(frame_ms * 10); if (d != 25 && d != 50 && d != 100) return LC3_FRAMEMS_ERROR; }
+    const LC3_Error e = geom_check(samplerate, channels, frame_ms, hrmode, decoder != 0);
+    if (e) return e;
     geom_t g;
-    geom_init(&g, samplerate, channels);
-    if (decoder) {
-        if (g.fs_idx < 4 && hrmode != 0) return LC3_SAMPLERATE_ERROR;
-        if (g.fs_idx == 5 && hrmode == 0) return LC3_HRMODE_ERROR;
-    } else if (samplerate < 48000 && hrmode != 0) return LC3_SAMPLERATE_ERROR;
-    g.dms = (int)(frame_ms * 10); g.frame_ms = frame_ms; g.hrmode = hrmode > 0;
-    geom_update_ex(&g, decoder != 0);
+    geom_fill(&g, samplerate, channels, frame_ms, hrmode, decoder != 0);
     if (!geom_supported(&g)) return LC3_ERROR;
     stream_header(decoder ? SS_DEC : SS_ENC, &g, header);
     return LC3_OK;
 }
 int lc3plus_stream_header_ok(const uint32_t* header, const void* blob) { return header && blob && stream_header_ok(header, blob); }
 
-/* test hooks: dec_plan_sizes and dec_plan_sizes_lenient for a geometry, without a device (the batch builds the same table at create) */
+/* test hooks: dec_plan_sizes and dec_plan_lenient for a geometry, without a device (the batch builds the same table at create) */
 static LC3_Error dec_hook_table(int samplerate, int channels, float frame_ms, int hrmode, geom_t* g, lc3d_dchan** tab, int* tab_n)
 {
-    if (!samplerate_ok(samplerate)) return LC3_SAMPLERATE_ERROR;
-    if (channels < 1 || channels > MAX_CH) return LC3_CHANNELS_ERROR;
-    geom_init(g, samplerate, channels);
-    g->dms = (int)(frame_ms * 10); g->frame_ms = frame_ms; g->hrmode = hrmode > 0;
-    geom_update_ex(g, 1);
+    const LC3_Error e = geom_check_io(samplerate, channels);               /* (the frame length and hrmode are the caller's to get right) */
+    if (e) return e;
+    geom_fill(g, samplerate, channels, frame_ms, hrmode, 1);
     *tab = dec_build_table(g, tab_n);
     return *tab ? LC3_OK : LC3_ERROR;
 }
@@ -1751,7 +1724,8 @@ LC3_Error lc3plus_dec_plan_sizes_lenient(int samplerate, int channels, float fra
     geom_t g; lc3d_dchan* tab = NULL; int tab_n = 0;
     LC3_Error e = dec_hook_table(samplerate, channels, frame_ms, hrmode, &g, &tab, &tab_n);
     if (e) return e;
-    dec_plan_sizes_lenient(&g, tab, tab_n, n_streams, start, num_bytes, bfi, n_frames, in_stride, eff, lost, invalid, end, max_chan);
+    const dec_class_args a = {tab, tab_n, g.channels, num_bytes, bfi, in_stride, NULL, 0, 0};
+    dec_plan_lenient(dec_class_slot, &a, n_streams, start, n_frames, eff, lost, invalid, end, max_chan);
     free(tab);
     return LC3_OK;
 }
@@ -1764,8 +1738,8 @@ LC3_Error lc3plus_dec_plan_packed_lenient(int samplerate, int channels, float fr
     geom_t g; lc3d_dchan* tab = NULL; int tab_n = 0;
     LC3_Error e = dec_hook_table(samplerate, channels, frame_ms, hrmode, &g, &tab, &tab_n);
     if (e) return e;
-    dec_plan_packed_lenient(&g, tab, tab_n, n_streams, start, num_bytes, offsets, frames_capacity, max_frame_bytes, bfi, n_frames, eff, lost, invalid, end,
-                            max_chan);
+    const dec_class_args a = {tab, tab_n, g.channels, num_bytes, bfi, 0, offsets, frames_capacity, max_frame_bytes};
+    dec_plan_lenient(dec_class_packed, &a, n_streams, start, n_frames, eff, lost, invalid, end, max_chan);
     free(tab);
     return LC3_OK;
 }
@@ -2075,20 +2049,103 @@ static LC3_Error shard_result(const LC3_Error* res, int n)
     return LC3_OK;
 }
 
+/* What a sharded batch of either kind is made of: the split, the shards' batches (lc3plus_batch* of an encoder, lc3plus_dec_batch* of a decoder), the result of
+ * every shard's last call and the workers.  lc3plus_sharded and lc3plus_dec_sharded hold one, what they answer without asking a shard, and the arguments of the
+ * host-pointer call their workers are running.  The helpers take the set of a handle or NULL for a NULL handle (SET), so that an entry point is one line that
+ * says what it returns where there is no such handle, shard or stream. */
+typedef struct {
+    int n_streams, n_shards, decoder;
+    void** sh; int* first; int* count; int* dev; LC3_Error* res;
+    shard_pool pool;
+} shard_set;
+#define SET(s) ((s) ? &(s)->set : NULL)
+
+/* destroys the first `created` shards and frees the arrays (not the workers: shard_pool_stop) */
+static void shard_set_close(shard_set* s, int created)
+{
+    for (int k = 0; k < created; k++) { if (s->decoder) lc3plus_dec_batch_destroy((lc3plus_dec_batch*)s->sh[k]); else lc3plus_enc_batch_destroy((lc3plus_batch*)s->sh[k]); }
+    free(s->sh); free(s->first); free(s->count); free(s->dev); free(s->res);
+}
+/* The arrays, every shard's batch - created on its device with its block of cfg (the streams' bitrates or frame sizes; NULL: none) - and the workers, which
+ * hand `owner` to their jobs.  Returns the first error, with nothing left behind. */
+static LC3_Error shard_set_open(shard_set* s, void* owner, int decoder, int n_streams, int samplerate, int channels, float frame_ms, int hrmode, const int* cfg,
+                                const int* devices, int n_devices)
+{
+    s->n_streams = n_streams; s->n_shards = n_devices; s->decoder = decoder;
+    s->sh = (void**)calloc((size_t)n_devices, sizeof *s->sh);
+    s->first = (int*)calloc((size_t)n_devices, sizeof(int)); s->count = (int*)calloc((size_t)n_devices, sizeof(int));
+    s->dev = (int*)calloc((size_t)n_devices, sizeof(int)); s->res = (LC3_Error*)calloc((size_t)n_devices, sizeof(LC3_Error));
+    if (!s->sh || !s->first || !s->count || !s->dev || !s->res) { shard_set_close(s, 0); return LC3_ERROR; }
+    for (int k = 0; k < n_devices; k++) {
+        lc3plus_shard_block(n_streams, n_devices, k, &s->first[k], &s->count[k]);
+        s->dev[k] = devices[k];
+        const int* c = cfg ? cfg + s->first[k] : NULL;
+        lc3plus_batch* eb = NULL; lc3plus_dec_batch* db = NULL;
+        const LC3_Error e = decoder ? lc3plus_dec_batch_create(&db, s->count[k], samplerate, channels, frame_ms, hrmode, c, devices[k])
+                                    : lc3plus_enc_batch_create(&eb, s->count[k], samplerate, channels, frame_ms, hrmode, c, devices[k]);
+        if (e) { shard_set_close(s, k); return e; }
+        s->sh[k] = decoder ? (void*)db : (void*)eb;
+    }
+    if (shard_pool_start(&s->pool, n_devices, owner)) { shard_set_close(s, n_devices); return LC3_ERROR; }
+    return LC3_OK;
+}
+static int shard_set_shards(const shard_set* s) { return s ? s->n_shards : 0; }
+static void* shard_set_shard(const shard_set* s, int shard) { return s && shard >= 0 && shard < s->n_shards ? s->sh[shard] : NULL; }
+static int shard_set_device(const shard_set* s, int shard) { return s && shard >= 0 && shard < s->n_shards ? s->dev[shard] : -1; }
+static LC3_Error shard_set_owner(const shard_set* s, int stream, int* shard, int* local)
+{
+    if (!s || !shard || !local) return LC3_NULL_ERROR;
+    if (stream < 0 || stream >= s->n_streams) return LC3_ERROR;
+    shard_owner(s->n_streams, s->n_shards, stream, shard, local);
+    return LC3_OK;
+}
+/* the batch that owns a global stream and the stream's index in it, NULL where there is none */
+static void* shard_set_at(const shard_set* s, int stream, int* local)
+{
+    int k = 0;
+    return shard_set_owner(s, stream, &k, local) ? NULL : s->sh[k];
+}
+/* The shards' states one after the other: [channel-stream][state words] over all the streams, which is the state of an unsharded batch of n_streams.  One walk
+ * over the blocks: their sizes summed, or every shard handed its block to fill (set = 0) or to take (set = 1). */
+static size_t shard_state_size(const shard_set* s, int k)
+{
+    return s->decoder ? lc3plus_dec_batch_state_size((lc3plus_dec_batch*)s->sh[k]) : lc3plus_enc_batch_state_size((lc3plus_batch*)s->sh[k]);
+}
+static size_t shard_set_state_size(const shard_set* s)
+{
+    size_t n = 0;
+    if (s) for (int k = 0; k < s->n_shards; k++) n += shard_state_size(s, k);
+    return n;
+}
+static LC3_Error shard_set_state(shard_set* s, void* state, size_t size, int set)
+{
+    if (!s || !state) return LC3_NULL_ERROR;
+    if (size != shard_set_state_size(s)) return LC3_ERROR;
+    uint8_t* p = (uint8_t*)state;
+    for (int k = 0; k < s->n_shards; k++) {
+        const size_t n = shard_state_size(s, k);
+        if (s->decoder) s->res[k] = set ? lc3plus_dec_batch_set_state((lc3plus_dec_batch*)s->sh[k], p, n) : lc3plus_dec_batch_get_state((lc3plus_dec_batch*)s->sh[k], p, n);
+        else s->res[k] = set ? lc3plus_enc_batch_set_state((lc3plus_batch*)s->sh[k], p, n) : lc3plus_enc_batch_get_state((lc3plus_batch*)s->sh[k], p, n);
+        p += n;
+    }
+    return shard_result(s->res, s->n_shards);
+}
+/* The PCM of a host-pointer call from stream `first` on: in all three layouts the stream index is the outermost one, so the slice is an offset (none where the
+ * shard's call refuses the format or the frame count anyway) */
+static char* shard_pcm(const char* pcm, int fmt, int channels, int n_frames, int samples, int first)
+{
+    const int64_t po = pcm && n_frames > 0 && lc3d_pcm_format_ok(fmt) ? lc3plus_pcm_offset(fmt, channels, n_frames, samples, first, 0, 0, 0) : 0;
+    return pcm ? (char*)pcm + (size_t)lc3d_pcm_elem_bytes(fmt) * (size_t)po : NULL;
+}
+
 /* ---- encoders ---- */
 struct lc3plus_sharded {
-    int n_streams, n_shards, channels, N;
-    lc3plus_batch** sh; int* first; int* count; int* dev; LC3_Error* res;
-    shard_pool pool;
+    shard_set set; int channels, N;
     /* the arguments of the host-pointer call the workers are running */
     struct { const char* pcm; int fmt; const int* bw; const int* br; int T; uint8_t* out; int stride; int* nb; } a;
 };
+#define ENC_SHARD(s, k) ((lc3plus_batch*)(s)->set.sh[k])
 
-static void enc_sharded_free(lc3plus_sharded* s, int created)
-{
-    for (int i = 0; i < created; i++) lc3plus_enc_batch_destroy(s->sh[i]);
-    free(s->sh); free(s->first); free(s->count); free(s->dev); free(s->res); free(s);
-}
 LC3_Error lc3plus_enc_sharded_create(lc3plus_sharded** out, int n_streams, int samplerate, int channels, float frame_ms, int hrmode, const int* bitrates,
                                      const int* devices, int n_devices)
 {
@@ -2102,95 +2159,71 @@ LC3_Error lc3plus_enc_sharded_create(lc3plus_sharded** out, int n_streams, int s
     for (int i = 0; i < n_streams; i++) { lc3d_chan tmp[MAX_CH]; e = derive_bitrate(&g, bitrates[i], tmp); if (e) return e; }      /* before any device is touched */
     lc3plus_sharded* s = (lc3plus_sharded*)calloc(1, sizeof *s);
     if (!s) return LC3_ERROR;
-    s->n_streams = n_streams; s->n_shards = n_devices; s->channels = channels; s->N = g.N;
-    s->sh = (lc3plus_batch**)calloc((size_t)n_devices, sizeof *s->sh);
-    s->first = (int*)calloc((size_t)n_devices, sizeof(int)); s->count = (int*)calloc((size_t)n_devices, sizeof(int));
-    s->dev = (int*)calloc((size_t)n_devices, sizeof(int)); s->res = (LC3_Error*)calloc((size_t)n_devices, sizeof(LC3_Error));
-    if (!s->sh || !s->first || !s->count || !s->dev || !s->res) { enc_sharded_free(s, 0); return LC3_ERROR; }
-    for (int k = 0; k < n_devices; k++) {
-        lc3plus_shard_block(n_streams, n_devices, k, &s->first[k], &s->count[k]);
-        s->dev[k] = devices[k];
-        e = lc3plus_enc_batch_create(&s->sh[k], s->count[k], samplerate, channels, frame_ms, hrmode, bitrates + s->first[k], devices[k]);
-        if (e) { enc_sharded_free(s, k); return e; }
-    }
-    if (shard_pool_start(&s->pool, n_devices, s)) { enc_sharded_free(s, n_devices); return LC3_ERROR; }
+    s->channels = channels; s->N = g.N;
+    e = shard_set_open(&s->set, s, 0, n_streams, samplerate, channels, frame_ms, hrmode, bitrates, devices, n_devices);
+    if (e) { free(s); return e; }
     *out = s;
     return LC3_OK;
 }
 LC3_Error lc3plus_enc_sharded_destroy(lc3plus_sharded* s)
 {
     if (!s) return LC3_NULL_ERROR;
-    shard_pool_stop(&s->pool);
-    enc_sharded_free(s, s->n_shards);
+    shard_pool_stop(&s->set.pool);
+    shard_set_close(&s->set, s->set.n_shards);
+    free(s);
     return LC3_OK;
 }
-int lc3plus_enc_sharded_shards(const lc3plus_sharded* s) { return s ? s->n_shards : 0; }
-lc3plus_batch* lc3plus_enc_sharded_shard(lc3plus_sharded* s, int shard) { return s && shard >= 0 && shard < s->n_shards ? s->sh[shard] : NULL; }
-int lc3plus_enc_sharded_device(const lc3plus_sharded* s, int shard) { return s && shard >= 0 && shard < s->n_shards ? s->dev[shard] : -1; }
-LC3_Error lc3plus_enc_sharded_owner(const lc3plus_sharded* s, int stream, int* shard, int* local)
-{
-    if (!s || !shard || !local) return LC3_NULL_ERROR;
-    if (stream < 0 || stream >= s->n_streams) return LC3_ERROR;
-    shard_owner(s->n_streams, s->n_shards, stream, shard, local);
-    return LC3_OK;
-}
-/* the shard and the local index of a global stream, NULL where there is none */
-static lc3plus_batch* enc_sharded_at(const lc3plus_sharded* s, int stream, int* local)
-{
-    int k = 0;
-    if (!s || stream < 0 || stream >= s->n_streams) return NULL;
-    shard_owner(s->n_streams, s->n_shards, stream, &k, local);
-    return s->sh[k];
-}
+int lc3plus_enc_sharded_shards(const lc3plus_sharded* s) { return shard_set_shards(SET(s)); }
+lc3plus_batch* lc3plus_enc_sharded_shard(lc3plus_sharded* s, int shard) { return (lc3plus_batch*)shard_set_shard(SET(s), shard); }
+int lc3plus_enc_sharded_device(const lc3plus_sharded* s, int shard) { return shard_set_device(SET(s), shard); }
+LC3_Error lc3plus_enc_sharded_owner(const lc3plus_sharded* s, int stream, int* shard, int* local) { return shard_set_owner(SET(s), stream, shard, local); }
 int lc3plus_enc_sharded_input_samples(const lc3plus_sharded* s) { return s ? s->N : 0; }
 int lc3plus_enc_sharded_num_bytes(const lc3plus_sharded* s, int stream)
 {
-    int l = 0; lc3plus_batch* b = enc_sharded_at(s, stream, &l);
+    int l = 0; lc3plus_batch* b = (lc3plus_batch*)shard_set_at(SET(s), stream, &l);
     return b ? lc3plus_enc_batch_num_bytes(b, l) : 0;
 }
 int lc3plus_enc_sharded_stride(const lc3plus_sharded* s)
 {
     int m = 0;
     if (!s) return 0;
-    for (int k = 0; k < s->n_shards; k++) { const int v = lc3plus_enc_batch_stride(s->sh[k]); if (v <= 0) return 0; m = IMAX(m, v); }
+    for (int k = 0; k < s->set.n_shards; k++) { const int v = lc3plus_enc_batch_stride(ENC_SHARD(s, k)); if (v <= 0) return 0; m = IMAX(m, v); }
     return m;
 }
 LC3_Error lc3plus_enc_sharded_set_bitrate(lc3plus_sharded* s, int stream, int bitrate)
 {
     if (!s) return LC3_NULL_ERROR;
-    int l = 0; lc3plus_batch* b = enc_sharded_at(s, stream, &l);
+    int l = 0; lc3plus_batch* b = (lc3plus_batch*)shard_set_at(&s->set, stream, &l);
     return b ? lc3plus_enc_batch_set_bitrate(b, l, bitrate) : LC3_ERROR;
 }
 LC3_Error lc3plus_enc_sharded_set_bandwidth(lc3plus_sharded* s, int stream, int bandwidth)
 {
     if (!s) return LC3_NULL_ERROR;
-    int l = 0; lc3plus_batch* b = enc_sharded_at(s, stream, &l);
+    int l = 0; lc3plus_batch* b = (lc3plus_batch*)shard_set_at(&s->set, stream, &l);
     return b ? lc3plus_enc_batch_set_bandwidth(b, l, bandwidth) : LC3_ERROR;
 }
 int lc3plus_enc_sharded_bandwidth(const lc3plus_sharded* s, int stream)
 {
-    int l = 0; lc3plus_batch* b = enc_sharded_at(s, stream, &l);
+    int l = 0; lc3plus_batch* b = (lc3plus_batch*)shard_set_at(SET(s), stream, &l);
     return b ? lc3plus_enc_batch_bandwidth(b, l) : -1;
 }
 
-/* shard k's call of the host-pointer encode: the call an unsharded batch would be given for the same arguments, on the shard's slice of every array.  In
- * all three layouts the stream index is the outermost one, so the slice of the PCM is an offset */
+/* shard k's call of the host-pointer encode: the call an unsharded batch would be given for the same arguments, on the shard's slice of every array */
 static LC3_Error enc_shard_call(lc3plus_sharded* s, int k)
 {
-    const size_t f = (size_t)s->first[k], row = f * (size_t)(s->a.T > 0 ? s->a.T : 0);
-    const int64_t po = s->a.pcm && s->a.T > 0 && pcm_format_ok(s->a.fmt) ? lc3plus_pcm_offset(s->a.fmt, s->channels, s->a.T, s->N, (int)f, 0, 0, 0) : 0;
-    const char* pcm = s->a.pcm ? s->a.pcm + (size_t)lc3d_pcm_elem_bytes(s->a.fmt) * (size_t)po : NULL;
+    const size_t f = (size_t)s->set.first[k], row = f * (size_t)(s->a.T > 0 ? s->a.T : 0);
+    const char* pcm = shard_pcm(s->a.pcm, s->a.fmt, s->channels, s->a.T, s->N, (int)f);
     uint8_t* out = s->a.out ? s->a.out + row * (size_t)(s->a.stride > 0 ? s->a.stride : 0) : NULL;
     const int* br = s->a.br ? s->a.br + row : NULL;
     int* nb = s->a.nb ? s->a.nb + row : NULL;
-    lc3plus_batch* b = s->sh[k];
+    lc3plus_batch* b = ENC_SHARD(s, k);
     if (s->a.bw) return batch_encode_bandwidths(b, pcm, 0, s->a.fmt, s->a.bw + row, br, s->a.T, out, s->a.stride, 0, nb, NULL, 1);
     if (s->a.br) return batch_encode_bitrates(b, pcm, 0, s->a.fmt, br, s->a.T, out, s->a.stride, 0, nb, NULL, 1, NULL);
     const LC3_Error e = batch_encode(b, pcm, 0, s->a.fmt, s->a.T, out, s->a.stride, 0, NULL, 1, NULL);
-    if (!e && nb && !b->dry) for (size_t i = 0; i < (size_t)s->count[k] * s->a.T; i++) nb[i] = lc3plus_enc_batch_num_bytes(b, (int)(i / s->a.T));
+    if (!e && nb && !b->dry) for (size_t i = 0; i < (size_t)s->set.count[k] * s->a.T; i++) nb[i] = lc3plus_enc_batch_num_bytes(b, (int)(i / s->a.T));
     return e;
 }
-static void enc_shard_job(void* owner, int k) { lc3plus_sharded* s = (lc3plus_sharded*)owner; s->res[k] = enc_shard_call(s, k); }
+static void enc_shard_job(void* owner, int k) { lc3plus_sharded* s = (lc3plus_sharded*)owner; s->set.res[k] = enc_shard_call(s, k); }
 /* Every check of the call on every shard, on the calling thread, nothing run: step by step over all shards, so that the code is the one an unsharded batch
  * gives (DRY_*).  LC3_OK and LC3_BW_WARNING let the call go on. */
 static LC3_Error enc_sharded_check(lc3plus_sharded* s)
@@ -2198,10 +2231,10 @@ static LC3_Error enc_sharded_check(lc3plus_sharded* s)
     LC3_Error res = LC3_OK;
     for (int step = s->a.bw ? DRY_BW : s->a.br ? DRY_RATES : DRY_ALL; step <= DRY_ALL && (res == LC3_OK || res == LC3_BW_WARNING); step++) {
         if (step == DRY_RATES && !s->a.br) continue;
-        for (int k = 0; k < s->n_shards && (res == LC3_OK || res == LC3_BW_WARNING); k++) {
-            s->sh[k]->dry = step;
+        for (int k = 0; k < s->set.n_shards && (res == LC3_OK || res == LC3_BW_WARNING); k++) {
+            ENC_SHARD(s, k)->dry = step;
             const LC3_Error e = enc_shard_call(s, k);
-            s->sh[k]->dry = 0;
+            ENC_SHARD(s, k)->dry = 0;
             if (e) res = e;
         }
     }
@@ -2215,65 +2248,37 @@ LC3_Error lc3plus_enc_sharded_encode(lc3plus_sharded* s, const void* pcm, int bi
     s->a.stride = out_stride; s->a.nb = num_bytes;
     const LC3_Error e = enc_sharded_check(s);
     if (e != LC3_OK && e != LC3_BW_WARNING) return e;
-    shard_pool_run(&s->pool, enc_shard_job);
-    return shard_result(s->res, s->n_shards);
+    shard_pool_run(&s->set.pool, enc_shard_job);
+    return shard_result(s->set.res, s->set.n_shards);
 }
 LC3_Error lc3plus_enc_sharded_encode_device(lc3plus_sharded* s, const void* const* pcm, int bitdepth, int n_frames, void* const* out, int out_stride,
                                             void* const* hip_streams, int sync)
 {
     if (!s || !pcm || !out) return LC3_NULL_ERROR;
-    for (int k = 0; k < s->n_shards; k++) {
-        s->sh[k]->dry = DRY_ALL;
-        const LC3_Error e = batch_encode(s->sh[k], pcm[k], 1, bitdepth, n_frames, out[k], out_stride, 1, NULL, 0, NULL);
-        s->sh[k]->dry = 0;
+    for (int k = 0; k < s->set.n_shards; k++) {
+        ENC_SHARD(s, k)->dry = DRY_ALL;
+        const LC3_Error e = batch_encode(ENC_SHARD(s, k), pcm[k], 1, bitdepth, n_frames, out[k], out_stride, 1, NULL, 0, NULL);
+        ENC_SHARD(s, k)->dry = 0;
         if (e) return e;
     }
     /* every shard's call is queued before any is waited for */
-    for (int k = 0; k < s->n_shards; k++)
-        s->res[k] = batch_encode(s->sh[k], pcm[k], 1, bitdepth, n_frames, out[k], out_stride, 1, hip_streams ? hip_streams[k] : NULL, 0, NULL);
-    if (sync) for (int k = 0; k < s->n_shards; k++) if (lc3hip_wait(s->sh[k]->dev) && !s->res[k]) s->res[k] = LC3_ERROR;
-    return shard_result(s->res, s->n_shards);
+    for (int k = 0; k < s->set.n_shards; k++)
+        s->set.res[k] = batch_encode(ENC_SHARD(s, k), pcm[k], 1, bitdepth, n_frames, out[k], out_stride, 1, hip_streams ? hip_streams[k] : NULL, 0, NULL);
+    if (sync) for (int k = 0; k < s->set.n_shards; k++) if (lc3hip_wait(ENC_SHARD(s, k)->dev) && !s->set.res[k]) s->set.res[k] = LC3_ERROR;
+    return shard_result(s->set.res, s->set.n_shards);
 }
-/* the shards' states one after the other: [channel-stream][state words] over all the streams, which is the state of an unsharded batch of n_streams */
-size_t lc3plus_enc_sharded_state_size(const lc3plus_sharded* s)
-{
-    size_t n = 0;
-    if (s) for (int k = 0; k < s->n_shards; k++) n += lc3plus_enc_batch_state_size(s->sh[k]);
-    return n;
-}
-LC3_Error lc3plus_enc_sharded_get_state(lc3plus_sharded* s, void* state, size_t size)
-{
-    if (!s || !state) return LC3_NULL_ERROR;
-    if (size != lc3plus_enc_sharded_state_size(s)) return LC3_ERROR;
-    uint8_t* p = (uint8_t*)state;
-    for (int k = 0; k < s->n_shards; k++) { const size_t n = lc3plus_enc_batch_state_size(s->sh[k]); s->res[k] = lc3plus_enc_batch_get_state(s->sh[k], p, n); p += n; }
-    return shard_result(s->res, s->n_shards);
-}
-LC3_Error lc3plus_enc_sharded_set_state(lc3plus_sharded* s, const void* state, size_t size)
-{
-    if (!s || !state) return LC3_NULL_ERROR;
-    if (size != lc3plus_enc_sharded_state_size(s)) return LC3_ERROR;
-    const uint8_t* p = (const uint8_t*)state;
-    for (int k = 0; k < s->n_shards; k++) { const size_t n = lc3plus_enc_batch_state_size(s->sh[k]); s->res[k] = lc3plus_enc_batch_set_state(s->sh[k], p, n); p += n; }
-    return shard_result(s->res, s->n_shards);
-}
-float lc3plus_enc_sharded_last_kernel_ms(lc3plus_sharded* s, int shard)
-{
-    return s && shard >= 0 && shard < s->n_shards ? lc3plus_enc_batch_last_kernel_ms(s->sh[shard]) : 0.0f;
-}
+size_t lc3plus_enc_sharded_state_size(const lc3plus_sharded* s) { return shard_set_state_size(SET(s)); }
+LC3_Error lc3plus_enc_sharded_get_state(lc3plus_sharded* s, void* state, size_t size) { return shard_set_state(SET(s), state, size, 0); }
+LC3_Error lc3plus_enc_sharded_set_state(lc3plus_sharded* s, const void* state, size_t size) { return shard_set_state(SET(s), (void*)state, size, 1); }
+float lc3plus_enc_sharded_last_kernel_ms(lc3plus_sharded* s, int shard) { return lc3plus_enc_batch_last_kernel_ms((lc3plus_batch*)shard_set_shard(SET(s), shard)); }
 
 /* ---- decoders ---- */
 struct lc3plus_dec_sharded {
-    int n_streams, n_shards, channels, N, delay;
-    lc3plus_dec_batch** sh; int* first; int* count; int* dev; LC3_Error* res;
-    shard_pool pool;
+    shard_set set; int channels, N, delay;
     struct { const uint8_t* frames; int in_stride; const int* nb; const uint8_t* bfi; int T; char* pcm; int fmt; uint8_t* status; } a;
 };
-static void dec_sharded_free(lc3plus_dec_sharded* s, int created)
-{
-    for (int i = 0; i < created; i++) lc3plus_dec_batch_destroy(s->sh[i]);
-    free(s->sh); free(s->first); free(s->count); free(s->dev); free(s->res); free(s);
-}
+#define DEC_SHARD(s, k) ((lc3plus_dec_batch*)(s)->set.sh[k])
+
 LC3_Error lc3plus_dec_sharded_create(lc3plus_dec_sharded** out, int n_streams, int samplerate, int channels, float frame_ms, int hrmode, const int* num_bytes,
                                      const int* devices, int n_devices)
 {
@@ -2287,67 +2292,48 @@ LC3_Error lc3plus_dec_sharded_create(lc3plus_dec_sharded** out, int n_streams, i
     if (num_bytes) for (int i = 0; i < n_streams; i++) { lc3d_dchan tmp[MAX_CH]; memset(tmp, 0, sizeof tmp); e = derive_dstream(&g, num_bytes[i], tmp); if (e) return e; }
     lc3plus_dec_sharded* s = (lc3plus_dec_sharded*)calloc(1, sizeof *s);
     if (!s) return LC3_ERROR;
-    s->n_streams = n_streams; s->n_shards = n_devices; s->channels = channels; s->N = g.N; s->delay = g.N - 2 * g.la;
-    s->sh = (lc3plus_dec_batch**)calloc((size_t)n_devices, sizeof *s->sh);
-    s->first = (int*)calloc((size_t)n_devices, sizeof(int)); s->count = (int*)calloc((size_t)n_devices, sizeof(int));
-    s->dev = (int*)calloc((size_t)n_devices, sizeof(int)); s->res = (LC3_Error*)calloc((size_t)n_devices, sizeof(LC3_Error));
-    if (!s->sh || !s->first || !s->count || !s->dev || !s->res) { dec_sharded_free(s, 0); return LC3_ERROR; }
-    for (int k = 0; k < n_devices; k++) {
-        lc3plus_shard_block(n_streams, n_devices, k, &s->first[k], &s->count[k]);
-        s->dev[k] = devices[k];
-        e = lc3plus_dec_batch_create(&s->sh[k], s->count[k], samplerate, channels, frame_ms, hrmode, num_bytes ? num_bytes + s->first[k] : NULL, devices[k]);
-        if (e) { dec_sharded_free(s, k); return e; }
-    }
-    if (shard_pool_start(&s->pool, n_devices, s)) { dec_sharded_free(s, n_devices); return LC3_ERROR; }
+    s->channels = channels; s->N = g.N; s->delay = g.N - 2 * g.la;
+    e = shard_set_open(&s->set, s, 1, n_streams, samplerate, channels, frame_ms, hrmode, num_bytes, devices, n_devices);
+    if (e) { free(s); return e; }
     *out = s;
     return LC3_OK;
 }
 LC3_Error lc3plus_dec_sharded_destroy(lc3plus_dec_sharded* s)
 {
     if (!s) return LC3_NULL_ERROR;
-    shard_pool_stop(&s->pool);
-    dec_sharded_free(s, s->n_shards);
+    shard_pool_stop(&s->set.pool);
+    shard_set_close(&s->set, s->set.n_shards);
+    free(s);
     return LC3_OK;
 }
-int lc3plus_dec_sharded_shards(const lc3plus_dec_sharded* s) { return s ? s->n_shards : 0; }
-lc3plus_dec_batch* lc3plus_dec_sharded_shard(lc3plus_dec_sharded* s, int shard) { return s && shard >= 0 && shard < s->n_shards ? s->sh[shard] : NULL; }
-int lc3plus_dec_sharded_device(const lc3plus_dec_sharded* s, int shard) { return s && shard >= 0 && shard < s->n_shards ? s->dev[shard] : -1; }
-LC3_Error lc3plus_dec_sharded_owner(const lc3plus_dec_sharded* s, int stream, int* shard, int* local)
-{
-    if (!s || !shard || !local) return LC3_NULL_ERROR;
-    if (stream < 0 || stream >= s->n_streams) return LC3_ERROR;
-    shard_owner(s->n_streams, s->n_shards, stream, shard, local);
-    return LC3_OK;
-}
+int lc3plus_dec_sharded_shards(const lc3plus_dec_sharded* s) { return shard_set_shards(SET(s)); }
+lc3plus_dec_batch* lc3plus_dec_sharded_shard(lc3plus_dec_sharded* s, int shard) { return (lc3plus_dec_batch*)shard_set_shard(SET(s), shard); }
+int lc3plus_dec_sharded_device(const lc3plus_dec_sharded* s, int shard) { return shard_set_device(SET(s), shard); }
+LC3_Error lc3plus_dec_sharded_owner(const lc3plus_dec_sharded* s, int stream, int* shard, int* local) { return shard_set_owner(SET(s), stream, shard, local); }
 int lc3plus_dec_sharded_output_samples(const lc3plus_dec_sharded* s) { return s ? s->N : 0; }
 int lc3plus_dec_sharded_delay(const lc3plus_dec_sharded* s) { return s ? s->delay : 0; }
 int lc3plus_dec_sharded_num_bytes(const lc3plus_dec_sharded* s, int stream)
 {
-    int k = 0, l = 0;
-    if (!s || stream < 0 || stream >= s->n_streams) return 0;
-    shard_owner(s->n_streams, s->n_shards, stream, &k, &l);
-    return lc3plus_dec_batch_num_bytes(s->sh[k], l);
+    int l = 0; lc3plus_dec_batch* b = (lc3plus_dec_batch*)shard_set_at(SET(s), stream, &l);
+    return b ? lc3plus_dec_batch_num_bytes(b, l) : 0;
 }
 LC3_Error lc3plus_dec_sharded_set_num_bytes(lc3plus_dec_sharded* s, int stream, int num_bytes)
 {
-    int k = 0, l = 0;
     if (!s) return LC3_NULL_ERROR;
-    if (stream < 0 || stream >= s->n_streams) return LC3_ERROR;
-    shard_owner(s->n_streams, s->n_shards, stream, &k, &l);
-    return lc3plus_dec_batch_set_num_bytes(s->sh[k], l, num_bytes);
+    int l = 0; lc3plus_dec_batch* b = (lc3plus_dec_batch*)shard_set_at(&s->set, stream, &l);
+    return b ? lc3plus_dec_batch_set_num_bytes(b, l, num_bytes) : LC3_ERROR;
 }
 static LC3_Error dec_shard_call(lc3plus_dec_sharded* s, int k)
 {
-    const size_t f = (size_t)s->first[k], row = f * (size_t)(s->a.T > 0 ? s->a.T : 0);
-    const int64_t po = s->a.pcm && s->a.T > 0 && pcm_format_ok(s->a.fmt) ? lc3plus_pcm_offset(s->a.fmt, s->channels, s->a.T, s->N, (int)f, 0, 0, 0) : 0;
-    char* pcm = s->a.pcm ? s->a.pcm + (size_t)lc3d_pcm_elem_bytes(s->a.fmt) * (size_t)po : NULL;
+    const size_t f = (size_t)s->set.first[k], row = f * (size_t)(s->a.T > 0 ? s->a.T : 0);
+    char* pcm = shard_pcm(s->a.pcm, s->a.fmt, s->channels, s->a.T, s->N, (int)f);
     const uint8_t* frames = s->a.frames ? s->a.frames + row * (size_t)(s->a.in_stride > 0 ? s->a.in_stride : 0) : NULL;
     const uint8_t* bfi = s->a.bfi ? s->a.bfi + row : NULL;
     uint8_t* status = s->a.status ? s->a.status + row : NULL;
-    if (s->a.nb) return lc3plus_dec_batch_decode_sizes(s->sh[k], frames, 0, s->a.in_stride, s->a.nb + row, bfi, s->a.T, pcm, 0, s->a.fmt, status, NULL, 1);
-    return dec_batch_decode(s->sh[k], frames, 0, s->a.in_stride, bfi, s->a.T, pcm, 0, s->a.fmt, status, NULL, 1, NULL);
+    if (s->a.nb) return lc3plus_dec_batch_decode_sizes(DEC_SHARD(s, k), frames, 0, s->a.in_stride, s->a.nb + row, bfi, s->a.T, pcm, 0, s->a.fmt, status, NULL, 1);
+    return dec_batch_decode(DEC_SHARD(s, k), frames, 0, s->a.in_stride, bfi, s->a.T, pcm, 0, s->a.fmt, status, NULL, 1, NULL);
 }
-static void dec_shard_job(void* owner, int k) { lc3plus_dec_sharded* s = (lc3plus_dec_sharded*)owner; s->res[k] = dec_shard_call(s, k); }
+static void dec_shard_job(void* owner, int k) { lc3plus_dec_sharded* s = (lc3plus_dec_sharded*)owner; s->set.res[k] = dec_shard_call(s, k); }
 LC3_Error lc3plus_dec_sharded_decode(lc3plus_dec_sharded* s, const void* frames, int in_stride, const int* num_bytes, const uint8_t* bfi, int n_frames, void* pcm,
                                      int bps, uint8_t* status)
 {
@@ -2356,53 +2342,31 @@ LC3_Error lc3plus_dec_sharded_decode(lc3plus_dec_sharded* s, const void* frames,
     s->a.fmt = bps; s->a.status = status;
     /* every check on every shard first, nothing run: shards are blocks of streams in order, and the checks walk the streams in order, so the first refusal
      * is the unsharded batch's */
-    for (int k = 0; k < s->n_shards; k++) {
-        s->sh[k]->dry = DRY_ALL;
+    for (int k = 0; k < s->set.n_shards; k++) {
+        DEC_SHARD(s, k)->dry = DRY_ALL;
         const LC3_Error e = dec_shard_call(s, k);
-        s->sh[k]->dry = 0;
+        DEC_SHARD(s, k)->dry = 0;
         if (e) return e;
     }
-    shard_pool_run(&s->pool, dec_shard_job);
-    return shard_result(s->res, s->n_shards);
+    shard_pool_run(&s->set.pool, dec_shard_job);
+    return shard_result(s->set.res, s->set.n_shards);
 }
 LC3_Error lc3plus_dec_sharded_decode_device(lc3plus_dec_sharded* s, const void* const* frames, int in_stride, int n_frames, void* const* pcm, int bps,
                                             void* const* hip_streams, int sync)
 {
     if (!s || !frames || !pcm) return LC3_NULL_ERROR;
-    for (int k = 0; k < s->n_shards; k++) {
-        s->sh[k]->dry = DRY_ALL;
-        const LC3_Error e = dec_batch_decode(s->sh[k], frames[k], 1, in_stride, NULL, n_frames, pcm[k], 1, bps, NULL, NULL, 0, NULL);
-        s->sh[k]->dry = 0;
+    for (int k = 0; k < s->set.n_shards; k++) {
+        DEC_SHARD(s, k)->dry = DRY_ALL;
+        const LC3_Error e = dec_batch_decode(DEC_SHARD(s, k), frames[k], 1, in_stride, NULL, n_frames, pcm[k], 1, bps, NULL, NULL, 0, NULL);
+        DEC_SHARD(s, k)->dry = 0;
         if (e) return e;
     }
-    for (int k = 0; k < s->n_shards; k++)
-        s->res[k] = dec_batch_decode(s->sh[k], frames[k], 1, in_stride, NULL, n_frames, pcm[k], 1, bps, NULL, hip_streams ? hip_streams[k] : NULL, 0, NULL);
-    if (sync) for (int k = 0; k < s->n_shards; k++) if (lc3hip_dec_wait(s->sh[k]->dev) && !s->res[k]) s->res[k] = LC3_ERROR;
-    return shard_result(s->res, s->n_shards);
+    for (int k = 0; k < s->set.n_shards; k++)
+        s->set.res[k] = dec_batch_decode(DEC_SHARD(s, k), frames[k], 1, in_stride, NULL, n_frames, pcm[k], 1, bps, NULL, hip_streams ? hip_streams[k] : NULL, 0, NULL);
+    if (sync) for (int k = 0; k < s->set.n_shards; k++) if (lc3hip_dec_wait(DEC_SHARD(s, k)->dev) && !s->set.res[k]) s->set.res[k] = LC3_ERROR;
+    return shard_result(s->set.res, s->set.n_shards);
 }
-size_t lc3plus_dec_sharded_state_size(const lc3plus_dec_sharded* s)
-{
-    size_t n = 0;
-    if (s) for (int k = 0; k < s->n_shards; k++) n += lc3plus_dec_batch_state_size(s->sh[k]);
-    return n;
-}
-LC3_Error lc3plus_dec_sharded_get_state(lc3plus_dec_sharded* s, void* state, size_t size)
-{
-    if (!s || !state) return LC3_NULL_ERROR;
-    if (size != lc3plus_dec_sharded_state_size(s)) return LC3_ERROR;
-    uint8_t* p = (uint8_t*)state;
-    for (int k = 0; k < s->n_shards; k++) { const size_t n = lc3plus_dec_batch_state_size(s->sh[k]); s->res[k] = lc3plus_dec_batch_get_state(s->sh[k], p, n); p += n; }
-    return shard_result(s->res, s->n_shards);
-}
-LC3_Error lc3plus_dec_sharded_set_state(lc3plus_dec_sharded* s, const void* state, size_t size)
-{
-    if (!s || !state) return LC3_NULL_ERROR;
-    if (size != lc3plus_dec_sharded_state_size(s)) return LC3_ERROR;
-    const uint8_t* p = (const uint8_t*)state;
-    for (int k = 0; k < s->n_shards; k++) { const size_t n = lc3plus_dec_batch_state_size(s->sh[k]); s->res[k] = lc3plus_dec_batch_set_state(s->sh[k], p, n); p += n; }
-    return shard_result(s->res, s->n_shards);
-}
-float lc3plus_dec_sharded_last_kernel_ms(lc3plus_dec_sharded* s, int shard)
-{
-    return s && shard >= 0 && shard < s->n_shards ? lc3plus_dec_batch_last_kernel_ms(s->sh[shard]) : 0.0f;
-}
+size_t lc3plus_dec_sharded_state_size(const lc3plus_dec_sharded* s) { return shard_set_state_size(SET(s)); }
+LC3_Error lc3plus_dec_sharded_get_state(lc3plus_dec_sharded* s, void* state, size_t size) { return shard_set_state(SET(s), state, size, 0); }
+LC3_Error lc3plus_dec_sharded_set_state(lc3plus_dec_sharded* s, const void* state, size_t size) { return shard_set_state(SET(s), (void*)state, size, 1); }
+float lc3plus_dec_sharded_last_kernel_ms(lc3plus_dec_sharded* s, int shard) { return lc3plus_dec_batch_last_kernel_ms((lc3plus_dec_batch*)shard_set_shard(SET(s), shard)); }
